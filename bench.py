@@ -18,9 +18,14 @@ aigv_op_frame_resize_ingest -> the same step) as a separately reported variant, 
 second pass, the result gather of score_clips_dp) on gloo with a trivial stand-in model: a rehearsal of the N > 1 path on a
 machine without GPUs, not a measurement.
 
-`roofline`: the bf16 MFMA GEMM kernel (95 % of the FLOPs) timed live with HIP events on the launch stream during the
-timed steps; `cpu_baseline`: the CPU oracle (torch CPU restatement of the reference path) timed on this box's host
-cores on a bounded sample (full-width layers, reduced depth, scaled by layer counts) — a reported baseline only.
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`): nothing else.  `--full` adds
+everything else this file measures or checks, all outside the timed region: the presettle steps and the settling batches in front
+of it, the host enqueue time and the eager step behind it, then `roofline` (the bf16 MFMA GEMM kernel, 95 % of the FLOPs, timed with
+HIP events on the launch stream in a second pass of K steps), `device_calibration`, the greedy-decode and reference-loop figures,
+the parity check against the reference's recorded outputs and `cpu_baseline` (the CPU oracle, a torch CPU restatement of the
+reference path, timed on this box's host cores on a bounded sample: full-width layers, reduced depth, scaled by layer counts).
+`--dump-outputs DIR` writes what the last timed step returned (score1, logit, label) as DIR/<name>.npy; the inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -36,6 +41,20 @@ import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
 PEAK_BF16_TFLOPS = 2500.0   # dense bf16 MFMA peak, MI355X (MI355X_MICROARCH.md)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outs, path):
+    """--dump-outputs: one DIR/<name>.npy per tensor the step returned (host copies), floating outputs as float32 and integer ones (token ids,
+    labels) as float64 - exact either way.  An output larger than its share of DUMP_LIMIT_BYTES is cut to a fixed, seeded sample of its elements."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(outs))
+    for name, t in outs.items():
+        a = (t.float() if t.is_floating_point() else t.double()).numpy()
+        if a.nbytes > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))]
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def flops_per_clip(cfg, T, N, answer_rows):
@@ -508,6 +527,11 @@ def main():
                          "input: motion_feature is a resident synthetic [B, 2304] tensor (SURVEY.md 8d)")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp8"],
                     help="fp8: the InternLM2 prefill linears on the e4m3 MFMA (BASELINE config 5; NOT the headline - the reference path is bf16)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every figure and check outside the headline: presettle + settling, host enqueue, eager step, roofline pass, device "
+                         "calibration, decode, reference loop shape, parity with the reference's recorded outputs, CPU baseline (the --no-* options below "
+                         "leave single ones out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the last timed step returned as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-prof", action="store_true", help="skip the per-launch HIP-event roofline measurement")
     ap.add_argument("--all-rows", action="store_true", help="A/B: run every row through the last decoder layer (no row trimming)")
@@ -681,19 +705,20 @@ def main():
     gc.collect()
     gc.freeze()   # no generation-2 sweep over the (large, static) module graph inside the timed region
 
-    # ---- settling (untimed, reported): some boxes of the pool run their first 10-20 s of GPU work at less than half speed with every kernel at its
+    # ---- settling (--full; untimed, reported): some boxes of the pool run their first 10-20 s of GPU work at less than half speed with every kernel at its
     # usual duration (three of ~50 calls of round 3; it decays by itself and the next process is normal).  Batches of 5 more untimed
     # steps until two consecutive batches agree within 3 %, at most 30 s; on a healthy box this is two batches.  The timed region below is untouched:
     # exactly K steps, fenced on both sides; `settle_ms_per_step` lists what the batches read so that nothing is hidden.
     #  a short timed run BEFORE any settling: what `--steps 5 --warmup W` read in rounds 1-2, reported beside the headline
-    fence()
-    tp = time.perf_counter()
-    for _ in range(min(5, args.steps)):
-        out = step()
-    fence()
-    presettle_ms = (time.perf_counter() - tp) / min(5, args.steps) * 1e3
-    settle = []
-    if not args.no_settle:
+    presettle_ms, settle = None, []
+    if args.full:
+        fence()
+        tp = time.perf_counter()
+        for _ in range(min(5, args.steps)):
+            out = step()
+        fence()
+        presettle_ms = (time.perf_counter() - tp) / min(5, args.steps) * 1e3
+    if args.full and not args.no_settle:
         t_settle = time.perf_counter()
         while True:
             fence()
@@ -719,11 +744,13 @@ def main():
         out = step()
     fence()
     dt = time.perf_counter() - t0
-    # host side of a step: how long the launching thread needs to ENQUEUE one step on an idle GPU (no synchronisation inside; the GPU
+    # host copies now: in graph mode the next step overwrites the device buffers behind `out`
+    last = {k: v.detach().cpu() for k, v in out.items() if torch.is_tensor(v)} if args.dump_outputs and rank == 0 else None
+    # host side of a step (--full): how long the launching thread needs to ENQUEUE one step on an idle GPU (no synchronisation inside; the GPU
     # then works through it).  The step is GPU-bound as long as this stays well under ms_per_step; on a contended host it is the first
     # thing to look at (a box of the pool once returned 282 ms/step with every kernel class at its usual duration).
     host_enqueue_ms = None
-    if not dry:
+    if args.full and not dry:
         hs = []
         for _ in range(3):
             fence()
@@ -733,7 +760,7 @@ def main():
         fence()
         host_enqueue_ms = sorted(hs)[1]
     eager_ms = None
-    if graph_mode:   # the same step launched kernel by kernel from the host, 5 steps, for the record (NOT the headline: `launch` in the line)
+    if args.full and graph_mode:   # the same step launched kernel by kernel from the host, 5 steps, for the record (NOT the headline: `launch` in the line)
         model.enable_graph_replay(False)
         for _ in range(2):
             out = step()
@@ -750,10 +777,10 @@ def main():
     # ---- roofline pass: the same K steps again with one HIP-event pair around every GEMM / attention launch on the
     # launch stream.  Kept out of the timed region above because ~900 event records per step cost ~10 % of wall time;
     # the per-launch durations themselves are unaffected (they agree with the rocprofv3 kernel trace in profiles/).
-    prof = rank == 0 and not args.no_prof and not dry
+    prof = args.full and rank == 0 and not args.no_prof and not dry
     dt_prof = None
     from aigv_assessor_amd import dist_utils as _dist_utils
-    if dist.is_initialized() and not dry and not args.no_prof and dist.get_backend() == "nccl":
+    if dist.is_initialized() and args.full and not dry and not args.no_prof and dist.get_backend() == "nccl":
         _dist_utils.collective_timing = []      # this pass only (every rank alike: same schedule): each all-gather completed at once, between two events
     if prof:
         model.prof_enable(True)
@@ -763,7 +790,7 @@ def main():
             out = step()
         fence()
         dt_prof = time.perf_counter() - t1
-    elif world > 1 and not args.no_prof and not dry:
+    elif world > 1 and args.full and not args.no_prof and not dry:
         # keep the ranks in lock-step with rank 0's roofline pass: the SAME sequence of collectives on every rank - fence, K steps, fence.
         # (Until round 4 the other ranks skipped the first fence: rank 0's extra barrier then paired with their first token all-gather and
         # the run hung at N > 1 - found by the one-card two-rank rehearsal, AIGV_BENCH_SHARE_DEVICE; no multi-GPU run had ever executed.)
@@ -815,15 +842,17 @@ def main():
                                  "HIP graph replay: per rank two captured graphs per step (InternViT shard + SlowFast | projector + InternLM2 + heads) around the RCCL token "
                                  "all-gather, which the host launches between them") + "; same kernels and bits as the eager step (InternVLChatModel.enable_graph_replay; --no-graph = eager)",
                         "eager_ms_per_step": eager_ms,
-                        "eager_note": "the same step with every kernel launched from the host, 5 steps after the timed region; equal on a quiet host, up to 3x slower "
+                        "eager_note": "--full: the same step with every kernel launched from the host, 5 steps after the timed region; equal on a quiet host, up to 3x slower "
                                       "where the container's CPU quota throttles the launching thread (profiles/r5_graph_replay.txt)"} if graph_mode else
                        {"mode": "eager: every kernel launched from the host"}),
             "ms_per_step_by_rank": rank_ms,
             "process_group": ({"backend": dist.get_backend(), "world_size": dist.get_world_size(), "devices": pg_devices,
                                "distinct_devices": len({d["device"] for d in pg_devices})} if dist.is_initialized() else None),
             "ranks_share_one_device": bool(os.environ.get("AIGV_BENCH_SHARE_DEVICE")),
-            "protocol": (f"{args.warmup} warmup steps; {min(5, args.steps)} untimed-but-reported steps (presettle_ms_per_step); "
-                         + ("no settling; " if args.no_settle else "untimed settling batches of 5 steps until two agree within 3 %, at most 30 s (settle_ms_per_step); ")
+            "protocol": (f"{args.warmup} warmup steps; "
+                         + ((f"{min(5, args.steps)} untimed-but-reported steps (presettle_ms_per_step); "
+                             + ("no settling; " if args.no_settle else "untimed settling batches of 5 steps until two agree within 3 %, at most 30 s (settle_ms_per_step); "))
+                            if args.full else "")
                          + f"then EXACTLY {args.steps} timed steps between barrier + synchronize fences"),
             "presettle_ms_per_step": presettle_ms,
             "settle_ms_per_step": settle,
@@ -895,23 +924,25 @@ def main():
             line["device_calibration"] = device_calibration(dev)
         if dry:
             line["dry_run"] = True
-        if world == 1 and not dry and not args.no_decode and args.model == "8b":
+        if args.full and world == 1 and not dry and not args.no_decode and args.model == "8b":
             dm = decode_metric(model, cfg, toks, pv, T, fp8=args.precision == "fp8")
             line.update(dm)
             if "roofline_by_class" in line:
                 line["roofline_by_class"]["decode"] = {"kernels": "generate(): q_len = 1 GEMVs + split-KV attention, batch 1", "bound": "hbm",
                                                        "achieved": dm["decode_hbm_tb_per_s"] * 1e3, "peak": 8000.0, "unit": "GB/s",
                                                        "frac": dm["decode_hbm_frac_of_8tbps"], "ms_per_token": dm["decode_ms_per_token"]}
-        if world == 1 and not dry and not args.no_decode and not args.ingest:
+        if args.full and world == 1 and not dry and not args.no_decode and not args.ingest:
             line["reference_loop_shape"] = reference_loop_metric(model, cfg, toks, dev, T)
-        if (world == 1 and not dry and not args.no_parity and args.model == "8b" and args.precision == "bf16" and T == 8 and Bl == 4
+        if (args.full and world == 1 and not dry and not args.no_parity and args.model == "8b" and args.precision == "bf16" and T == 8 and Bl == 4
                 and not args.all_rows and not args.tune_gemm and not args.attn_kernel and args.attn_numerics == "fp32"):
             par = parity_vs_reference(model, cfg, dev)      # (replaces the model's weights: after every measurement)
             if par:
                 line.update(par)
-        if world == 1 and not dry and not args.no_cpu_baseline:
+        if args.full and world == 1 and not dry and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(cfg, T, N, slowfast=args.motion == "slowfast")
             line["gpu_over_cpu"] = clips_per_s / line["cpu_baseline"]["value"]
+        if last is not None:
+            dump_outputs(last, args.dump_outputs)
         print(json.dumps(line))
     if dist.is_initialized():
         dist.barrier()

@@ -131,7 +131,7 @@ def test_bench_multi_process_control_flow_dry_run():
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--dry-run-cpu",
-           "--clips-per-gpu", "2", "--frames", "2"]
+           "--clips-per-gpu", "2", "--frames", "2", "--full"]
     env = dict(os.environ, OMP_NUM_THREADS="2")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -173,6 +173,36 @@ def test_bench_spawns_its_own_ranks_without_a_launcher():
     t0 = time.time()
     stuck = subprocess.run(cmd + ["--dry-run-fault", "stuck-peer"], capture_output=True, text=True, timeout=200, env=env, cwd=root)
     assert stuck.returncode == 3 and time.time() - t0 < 120, (stuck.returncode, time.time() - t0, stuck.stderr[-500:])
+
+
+def test_bench_dump_outputs_are_the_last_timed_steps_outputs(tmp_path):
+    """`--dump-outputs DIR`: the arrays the timed step returned, as DIR/<name>.npy in float32 (score1) / float64 (token ids, labels), equal to
+    the stand-in model applied to the benchmark's seeded inputs - the same files from a plain run and from a `--full` run.  A plain run
+    times exactly --steps steps and carries none of the --full figures."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines = {}
+    for extra in ([], ["--full"]):
+        d = tmp_path / ("full" if extra else "plain")
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dry-run-cpu", "--dump-outputs", str(d)] + extra
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=dict(os.environ, OMP_NUM_THREADS="2"), cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines[d.name] = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    plain = lines["plain"]
+    assert plain["steps"] == 3 and plain["ms_per_step"] > 0 and plain["settle_ms_per_step"] == [] and plain["presettle_ms_per_step"] is None
+    assert lines["full"]["presettle_ms_per_step"] is not None
+    cfg = pkg.tiny(image_size=56)
+    toks = synth.canonical_tokens(cfg, 4, 8, seed=0)
+    want = bench._DryRunModel(cfg)(pixel_values=synth.synthetic_frames(32, 56, seed=0), input_ids=toks["input_ids"], labels=toks["labels"])
+    for name in ("plain", "full"):
+        assert sorted(os.listdir(tmp_path / name)) == ["label.npy", "logit.npy", "score1.npy"]
+        for k, dtype in (("score1", np.float32), ("logit", np.float64), ("label", np.float64)):
+            a = np.load(tmp_path / name / f"{k}.npy")
+            assert a.dtype == dtype and np.array_equal(a, want[k].double().numpy()), (name, k)
 
 
 def _gather_worker(rank, world, port, q, counts):

@@ -78,7 +78,7 @@ def test_bench_two_ranks_on_one_card_rehearsal():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--model", "tiny", "--clips-per-gpu", "2",
-                        "--frames", "2", "--no-cpu-baseline", "--no-decode", "--no-parity", "--motion", "input"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+                        "--frames", "2", "--full", "--no-cpu-baseline", "--no-decode", "--no-parity", "--motion", "input"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     print(r.stdout[-800:], r.stderr[-1500:])
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -1763,3 +1763,39 @@ def test_fp8_mode_survives_a_weight_reload():
     for x, y in zip(a, b):
         assert torch.equal(x, y)
     assert not torch.equal(a[1], a[3]) or not torch.equal(a[0], a[2])      # the two modes do differ on this input
+
+
+def test_bench_dump_outputs_are_what_the_timed_step_computed(tmp_path):
+    """A plain `bench.py --dump-outputs DIR` run (tiny model, graph replay as benched): exactly --steps timed steps, none of the --full figures
+    in the line, and DIR/<name>.npy holding what its last timed step returned - equal to an eager pass of the same seeded weights and inputs
+    in this process (graph replay runs the same kernels, same bits)."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    from aigv_assessor_amd.modeling import InternVLChatModel
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--model", "tiny", "--clips-per-gpu", "2",
+                        "--frames", "2", "--motion", "input", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=root,
+                       env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4"))
+    print(r.stdout[-800:], r.stderr[-1500:])
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and not {"roofline", "cpu_baseline", "reference_loop_shape"} & set(line)
+    cfg = pkg.tiny(image_size=448)
+    B, T = 2, 2
+    N = synth.canonical_len(cfg, T)
+    dev = torch.device("cuda", 0)
+    toks = synth.canonical_tokens(cfg, B, T, seed=0)
+    model = InternVLChatModel(cfg, device=dev, max_clips=B, max_frames=B * T, max_tokens=B * N)
+    model.load_state_dict(synth.make_state_dict(cfg, seed=0, device=dev, rich=True))
+    model.img_context_token_id = toks["img_context_token_id"]
+    model.eval()
+    want = model(mos=None, pixel_values=synth.synthetic_frames(B * T, cfg.image_size, seed=0).to(dev), input_ids=toks["input_ids"],
+                 attention_mask=toks["attention_mask"], image_flags=torch.ones(B * T, 1, dtype=torch.long), labels=toks["labels"],
+                 motion_feature=synth.synthetic_motion(B, cfg.motion_dim, seed=0).to(dev))
+    assert sorted(os.listdir(d)) == ["label.npy", "logit.npy", "score1.npy"]
+    for k, dtype in (("score1", np.float32), ("logit", np.float64), ("label", np.float64)):
+        a = np.load(d / f"{k}.npy")
+        assert a.dtype == dtype and np.array_equal(a, want[k].double().cpu().numpy()), (k, a[:8], want[k][:8])
