@@ -111,6 +111,8 @@ struct aigv_ctx {
   bf16_t* l_trim = nullptr;   // last-layer row trimming: compact [64, H] x 2 (attention out, normed) + [64, I], reused per 64 consumed rows
   bf16_t* l_trim_h = nullptr; // ... and the consumed rows' hidden states [max_out_rows + max_seqs + 64, H]
   bf16_t* l_score_ws = nullptr;
+  bf16_t* l_lp = nullptr;     // aigv_out_row_logprob: lm-head logits of 64 consumed rows [64, lp_ldo], reused per 64 rows
+  int lp_ldo = 0;
   bf16_t *kc = nullptr, *vc = nullptr;   // [layer][seq][kv head][cap][D]
   bf16_t *kc_alt = nullptr, *vc_alt = nullptr;   // second cache of the same size, made by the first aigv_kv_reorder (beam search gathers into it, then the two swap)
   int32_t* beam_ints = nullptr;                  // [2 * max_seqs]: parent slots | live lengths of a reorder
@@ -839,6 +841,8 @@ static int alloc_workspaces(aigv_ctx* c) {
       for (int i = 0; i < k.n_score_layers; ++i) maxd = std::max(maxd, (int)k.score_dims[i]);
       if ((rc = dalloc(c, &c->l_score_ws, (size_t)3 * 64 * maxd))) break;
     }
+    c->lp_ldo = (k.vocab + 3) / 4 * 4;   // allocated here, never inside a pass: the logprob pass may be captured into a graph
+    if ((rc = dalloc(c, &c->l_lp, (size_t)64 * c->lp_ldo))) break;
     if (k.kv_capacity > 0) {
       const size_t per = (size_t)k.llm_layers * k.max_seqs * k.llm_kv_heads * k.kv_capacity * c->head_dim;
       if ((rc = dalloc(c, &c->kc, per))) break;
@@ -1920,6 +1924,28 @@ int aigv_out_row_logits(aigv_ctx* c, int first_row, int n_rows, void* logits_bf1
   return 0;
 }
 
+int aigv_out_row_logprob(aigv_ctx* c, int first_row, int n_rows, const int64_t* labels, float* logprob, void* stream) {
+  if (!c || !labels || !logprob) return fail(c, AIGV_ERR_ARG, "aigv_out_row_logprob: null argument");
+  if (!c->finalized) return fail(c, AIGV_ERR_STATE, "aigv_out_row_logprob: call aigv_finalize_weights first");
+  const aigv_config& k = c->cfg;
+  const int cap = k.max_out_rows + k.max_seqs + 64;
+  if (first_row < 0 || n_rows <= 0 || first_row + n_rows > cap) return fail(c, AIGV_ERR_ARG, "aigv_out_row_logprob: rows %d..%d outside 0..%d", first_row, first_row + n_rows - 1, cap - 1);
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  for (int r0 = 0; r0 < n_rows; r0 += 64) {
+    const int rr = std::min(64, n_rows - r0);
+    {
+      ProfScope ps(c, AIGV_PROF_SKINNY, 2.0 * rr * (double)k.vocab * k.llm_hidden, 2.0 * (double)k.vocab * k.llm_hidden, s);
+      hipError_t e = aigv_launch_lm_head_logits(c->l_rows + (size_t)(first_row + r0) * k.llm_hidden, rr, k.llm_hidden, c->lm_head, k.vocab,
+                                                c->l_lp, c->lp_ldo, s, /*one_form=*/true);
+      if (e != hipSuccess) return fail(c, e == hipErrorInvalidValue ? AIGV_ERR_ARG : AIGV_ERR_HIP, "lm-head logits (rows=%d ldo=%d): %s", rr, c->lp_ldo, hipGetErrorString(e));
+    }
+    hipError_t e = aigv_launch_label_logprob(c->l_lp, rr, k.vocab, c->lp_ldo, labels + r0, logprob + r0, s);
+    if (e != hipSuccess) return fail(c, e == hipErrorInvalidValue ? AIGV_ERR_ARG : AIGV_ERR_HIP, "label log-probabilities (rows=%d): %s", rr, hipGetErrorString(e));
+  }
+  return 0;
+}
+
 int aigv_out_row_hidden(aigv_ctx* c, int first_row, int n_rows, void* hidden_bf16, int ldo, void* stream) {
   if (!c || !hidden_bf16) return fail(c, AIGV_ERR_ARG, "aigv_out_row_hidden: null argument");
   if (!c->finalized) return fail(c, AIGV_ERR_STATE, "aigv_out_row_hidden: call aigv_finalize_weights first");
@@ -2101,6 +2127,13 @@ int aigv_op_lm_head_argmax(const void* h, int rows, int hidden, const void* W_, 
                            float* val, void* stream) {
   HIPCHK(nullptr, aigv_launch_lm_head_argmax((const bf16_t*)h, rows, hidden, (const bf16_t*)W_, vocab,
                                              (unsigned long long*)scratch_u64, idx, val, (hipStream_t)stream));
+  return 0;
+}
+
+int aigv_op_label_logprob(const void* logits_bf16, int rows, int vocab, int ldo, const int64_t* labels, float* out, void* stream) {
+  if (rows < 0 || vocab < 1 || ldo < vocab || (rows > 0 && (!logits_bf16 || !labels || !out)))
+    return fail(nullptr, AIGV_ERR_ARG, "aigv_op_label_logprob: bad argument (rows %d, vocab %d, ldo %d)", rows, vocab, ldo);
+  HIPCHK(nullptr, aigv_launch_label_logprob((const bf16_t*)logits_bf16, rows, vocab, ldo, labels, out, (hipStream_t)stream));
   return 0;
 }
 

@@ -169,7 +169,13 @@ hipError_t aigv_launch_skinny_rope_kv(const bf16_t* x, int ldx, int R, const bf1
 hipError_t aigv_launch_lm_head_argmax(const bf16_t* h, int R, int H, const bf16_t* W, int V,
                                       unsigned long long* packed, int64_t* out_idx, float* out_val, hipStream_t s);
 // lm-head logits (bf16, the matmul output the reference upcasts) of R rows into out[R, ldo], ldo >= roundup(V, 4)
-hipError_t aigv_launch_lm_head_logits(const bf16_t* h, int R, int H, const bf16_t* W, int V, bf16_t* out, int ldo, hipStream_t s);
+// one_form: the 4-slice form for every row count (that of the fused argmax), so that a row's logits do not depend on how many rows
+// share the launch; otherwise <= 16 rows of a vocabulary <= 4096 take the 8-slice GEMV form
+hipError_t aigv_launch_lm_head_logits(const bf16_t* h, int R, int H, const bf16_t* W, int V, bf16_t* out, int ldo, hipStream_t s,
+                                      bool one_form = false);
+// label log-probabilities: out[r] = logits[r, labels[r]] - logsumexp(logits[r, :V]) in fp32 over bf16 logits [rows, ldo >= V], NaN where
+// labels[r] is outside [0, V); one workgroup per row, fixed lane -> column mapping and reduction tree (batch-invariant bits)
+hipError_t aigv_launch_label_logprob(const bf16_t* logits, int rows, int V, int ldo, const int64_t* labels, float* out, hipStream_t s);
 // score head: x[B,H] -> chain of Linear+ReLU (bf16 rounding after each Linear), NaN/Inf guard on x
 struct ScoreHeadArgs {
   const bf16_t* x; int ldx; int B;

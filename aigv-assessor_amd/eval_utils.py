@@ -117,7 +117,7 @@ def _frames_of(item):
     return pv[0] if pv.dim() == 5 else pv                  # DataLoader(batch_size=1) adds the leading 1 (stage2_eval.py:932 takes [0])
 
 
-def batched(items, model, k: int = 4, frames=None, ahead: bool = True, pad_id: int = 2):
+def batched(items, model, k: int = 4, frames=None, ahead: bool = True, pad_id: int = 2, return_logprobs: bool = False):
     """The reference's eval loop at batch ``k`` instead of batch 1: yields ``(item, output)`` for EVERY item of ``items`` (the loop's
     ``DataLoader(batch_size=1)`` items: ``input_ids`` / ``attention_mask`` / ``labels`` [1, N_i] with N_i ragged, ``image_flags``
     [1, T, 1], ``pixel_values`` [1, T, 3, S, S] or what ``frames(item)`` returns - uint8 [T, H, W, 3] decoded frames are ingested on the
@@ -135,7 +135,10 @@ def batched(items, model, k: int = 4, frames=None, ahead: bool = True, pad_id: i
         for item2, output in eval_utils.batched(eval_utils.shard(train_dataloader, rank, world), model, k=4):
             score1 = output['score1'].item()          # `output = model(...)` and the `.to(model.device)` copies above it go away
 
-    ``items`` may be sharded first (``shard``) so that N ranks score N disjoint shares."""
+    ``items`` may be sharded first (``shard``) so that N ranks score N disjoint shares.
+
+    ``return_logprobs``: ``model(..., return_logprobs=True)`` per group; each item's output adds ``logprob`` [N_i - 1] (bit for bit the
+    item's own pass) and its own ``ce_loss``, ``-(logprob[label != -100]).double().mean().float()`` (NaN without answer labels)."""
     import torch
     import torch.nn.functional as F
     if k < 1:
@@ -182,7 +185,8 @@ def batched(items, model, k: int = 4, frames=None, ahead: bool = True, pad_id: i
             motion = torch.cat([it["motion_feature"].reshape(1, -1) for it, _ in group])
         out = model(mos=None, pixel_values=front, input_ids=torch.stack([pad(i, pad_id) for i in ids]),
                     attention_mask=torch.stack([pad(m, False) for m in masks]), image_flags=flags,
-                    labels=torch.stack([pad(l, -100) for l in labels]), **({} if motion is None else {"motion_feature": motion}))
+                    labels=torch.stack([pad(l, -100) for l in labels]), **({} if motion is None else {"motion_feature": motion}),
+                    **({"return_logprobs": True} if return_logprobs else {}))
         return group, n, nmax, out
 
     def collect(run):
@@ -192,8 +196,12 @@ def batched(items, model, k: int = 4, frames=None, ahead: bool = True, pad_id: i
         logit = out["logit"].view(len(group), nmax - 1).cpu()
         label = out["label"].view(len(group), nmax - 1).cpu()
         score1 = out["score1"].cpu() if "score1" in out else None
+        logprob = out["logprob"].view(len(group), nmax - 1).cpu() if return_logprobs else None
         for b, (it, _) in enumerate(group):
             o = {"logit": logit[b, : n[b] - 1].clone(), "label": label[b, : n[b] - 1].clone()}
+            if logprob is not None:
+                o["logprob"] = logprob[b, : n[b] - 1].clone()
+                o["ce_loss"] = (-o["logprob"][o["label"] != -100]).double().mean().float()
             if score1 is not None:
                 o["score1"] = score1[b: b + 1].clone()
                 mos = it.get("mos")

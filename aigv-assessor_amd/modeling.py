@@ -696,17 +696,24 @@ class InternVLChatModel(nn.Module):
                 position_ids=None, image_flags: Optional[torch.Tensor] = None, past_key_values=None,
                 labels: Optional[torch.Tensor] = None, use_cache=None, output_attentions=None,
                 output_hidden_states=None, return_dict=None, motion_feature: Optional[torch.Tensor] = None,
-                visual_tokens: Optional[torch.Tensor] = None, full_logits: bool = False):
+                visual_tokens: Optional[torch.Tensor] = None, full_logits: bool = False, return_logprobs: bool = False):
         """Stage-2 eval pass (modeling_internvl_chat.py:306-488) or, with ``stage=1``, the stage-1 pass
         (internvl_chat_eval1/modeling_internvl_chat.py:250-366).  ``visual_tokens`` optionally supplies
-        already all-gathered pre-projector tokens (frame-DP) instead of ``pixel_values``."""
+        already all-gathered pre-projector tokens (frame-DP) instead of ``pixel_values``.
+
+        ``return_logprobs=True`` adds ``logprob`` (fp32 [B (N - 1)], laid out like ``label`` / ``logit``: log_softmax of the fp32-upcast
+        bf16 logits at the shifted label, NaN wherever the label is -100) and ``ce_loss`` (fp32 0-dim: the reference's
+        ``CrossEntropyLoss()(shift_logits, shift_labels)``, modeling_internvl_chat.py:452-463 - the mean over the non-ignored labels of the
+        batch, NaN when there are none).  Labels must then be -100 or lie in [0, vocab), and no such label may follow a padded position
+        (the reference would score the padded row itself): ValueError otherwise.  ``loss`` (stage 2: L1 against ``mos``) is unchanged."""
         if position_ids is not None or past_key_values is not None:
             raise NotImplementedError("the eval pass takes default positions and no cache, like the reference drivers")
         if self.img_context_token_id is None:
             raise AssertionError("img_context_token_id must be set by the caller (stage2_eval.py:810)")
         pixel_values, visual_tokens, motion_feature = self._take_ahead(pixel_values, visual_tokens, motion_feature)
         if self._graph_replay_enabled and self._capture_keep is None:
-            out = self._forward_through_graph(mos, pixel_values, input_ids, attention_mask, image_flags, labels, motion_feature, visual_tokens, full_logits)
+            out = self._forward_through_graph(mos, pixel_values, input_ids, attention_mask, image_flags, labels, motion_feature, visual_tokens, full_logits,
+                                              return_logprobs)
             if out is not None:
                 return out
         B, N = input_ids.shape
@@ -714,6 +721,7 @@ class InternVLChatModel(nn.Module):
         # ---- index bookkeeping first, on the host (one small D2H copy if the ids live on the device), so that
         # every kernel of the step can then be enqueued back to back without a host sync in between ----
         plan = self._plan(input_ids, attention_mask, labels, image_flags, n_frames, full_logits)
+        lp_labels = self._logprob_labels(plan) if return_logprobs else None
         motion_feature = self._motion_feature(pixel_values, B, motion_feature)
 
         # ---- device work: ViT -> projector -> motion projector -> LLM pass + heads ----
@@ -721,7 +729,8 @@ class InternVLChatModel(nn.Module):
         vit_embeds, motion = self._visual_inputs(pixel_values, visual_tokens, motion_feature, plan)
         score, amax = self._prefill(plan["ids_packed"], plan["slot"], plan["cu"], vit_embeds, plan["n_vis"], motion,
                                     plan["score_rows"], plan["logit_rows"])
-        return self._outputs(plan, B, N, score, amax, mos)
+        lp = self._row_logprob(B if score is not None else 0, lp_labels) if return_logprobs else None
+        return self._outputs(plan, B, N, score, amax, mos, lp)
 
     # ---- HIP-graph replay of whole scoring passes (opt-in: enable_graph_replay) ---------------------------------------------------------
     _graph_replay_enabled = False
@@ -855,7 +864,8 @@ class InternVLChatModel(nn.Module):
             return tuple(cl(v) for v in outputs)
         return cl(outputs)
 
-    def _forward_through_graph(self, mos, pixel_values, input_ids, attention_mask, image_flags, labels, motion_feature, visual_tokens, full_logits):
+    def _forward_through_graph(self, mos, pixel_values, input_ids, attention_mask, image_flags, labels, motion_feature, visual_tokens, full_logits,
+                               return_logprobs=False):
         """The replay path of ``forward``; returns None when the call does not qualify (the eager path then runs)."""
         src = visual_tokens if visual_tokens is not None else pixel_values
         if self._rope_seq_len(int(input_ids.shape[1])) != getattr(self, "_rope_ntk", 0):
@@ -868,13 +878,15 @@ class InternVLChatModel(nn.Module):
         host_key = ("forward", visual_tokens is not None, bool(full_logits), int(self.img_context_token_id), self._branch_uid(),
                     bool(getattr(self, "overlap_motion_branch", True)), bool(getattr(self, "drop_dead_tail", True)),
                     tuple(None if t is None else (tuple(t.shape), t.dtype, t.numpy().tobytes()) for t in parts))
+        if return_logprobs:
+            host_key += ("logprobs",)        # (appended only when on: the keys of passes without it are those they always were)
         self._join_side_stream()             # (a motion feature started by motion_feature_async: joined BEFORE the graph copies it in)
         self._prepare_motion_branch(pixel_values if (motion_feature is None and visual_tokens is None) else None, int(input_ids.shape[0]))
 
         def fn(src_static, mf_static):
             return self.forward(mos=None, pixel_values=None if visual_tokens is not None else src_static, input_ids=input_ids, attention_mask=attention_mask,
                                 image_flags=image_flags, labels=labels, motion_feature=mf_static, full_logits=full_logits,
-                                visual_tokens=src_static if visual_tokens is not None else None)
+                                visual_tokens=src_static if visual_tokens is not None else None, return_logprobs=return_logprobs)
         return self._graph_call(host_key, [src, motion_feature], fn)
 
     def dp_front(self, frames_local: torch.Tensor, frames_clips: Optional[torch.Tensor], n_clips: int):
@@ -1015,18 +1027,53 @@ class InternVLChatModel(nn.Module):
             vit_embeds = vit_embeds[self._h2d(plan["keep"])]
         return vit_embeds.reshape(-1, H), self.motion_embed(motion_feature)
 
-    def _outputs(self, plan, B, N, score, amax, mos):
+    def _outputs(self, plan, B, N, score, amax, mos, lp=None):
         dev = self.device
         up = self._h2d   # host -> device through pinned memory, never blocking the host (keeps the CPU ahead of the GPU)
         logit = torch.full((B * (N - 1),), -1, dtype=torch.long, device=dev)
         if len(plan["logit_rows"]):
-            logit.index_copy_(0, up(plan["want"].reshape(-1).nonzero().flatten()), amax)   # index list built on the host: no sync
+            idx = up(plan["want"].reshape(-1).nonzero().flatten())                          # index list built on the host: no sync
+            logit.index_copy_(0, idx, amax)
         out = {"label": up(plan["labels_h"][..., 1:].contiguous().view(-1)), "logit": logit.view(-1)}
         if self.stage == 2:
             score1 = score.to(torch.bfloat16)       # the head computes in bf16; the value is exact in fp32
             out["score1"] = score1
             out["loss"] = F.l1_loss(score1, mos.to(dev).to(score1.dtype)) if mos is not None else None
+        if lp is not None:                          # return_logprobs: scattered like `logit`, NaN elsewhere
+            logprob = torch.full((B * (N - 1),), float("nan"), dtype=torch.float32, device=dev)
+            if len(plan["logit_rows"]):
+                logprob.index_copy_(0, idx, lp)
+            out["logprob"] = logprob
+            scored = (plan["labels_h"][..., 1:].reshape(-1) != -100).nonzero().flatten()   # (host: no sync)
+            if scored.numel():   # CrossEntropyLoss(): mean over the non-ignored labels; here in fp64, then rounded once
+                out["ce_loss"] = (-logprob.index_select(0, up(scored))).double().mean().float()
+            else:
+                out["ce_loss"] = torch.full((), float("nan"), dtype=torch.float32, device=dev)
         return out
+
+    def _logprob_labels(self, plan) -> torch.Tensor:
+        """Host int64 labels of the pass's consumed rows (in ``logit_rows`` order), checked first as torch's cross entropy would."""
+        lab = plan["labels_h"][:, 1:].to(torch.long)
+        V = self.config.llm_config.vocab_size
+        scored = lab != -100
+        bad = scored & ((lab < 0) | (lab >= V))
+        if bool(bad.any()):
+            raise ValueError(f"return_logprobs: label {int(lab[bad][0])} is outside [0, {V}) and not the ignore index -100")
+        if bool((scored & ~plan["want"]).any()):
+            raise ValueError("return_logprobs: a label that is not -100 follows a padded (masked) position; the reference would score the "
+                             "padded row itself, which this path does not run - set such labels to -100")
+        return lab[plan["want"]].contiguous()
+
+    def _row_logprob(self, first_row: int, labels_h: torch.Tensor) -> torch.Tensor:
+        """fp32 [R] label log-probabilities of consumed rows first_row .. first_row + R - 1 of the last native pass (aigv_out_row_logprob);
+        the labels go up through pinned memory - no host sync, and no allocation inside the library (the pass may be captured)."""
+        R = int(labels_h.numel())
+        lp = torch.empty(max(R, 1), dtype=torch.float32, device=self.device)
+        if R:
+            lib, ctx = native.load(), self._ctx
+            lab_d = self._h2d(labels_h)
+            native.check(lib.aigv_out_row_logprob(ctx, int(first_row), R, lab_d.data_ptr(), lp.data_ptr(), native.stream_ptr()), ctx)
+        return lp[:R]
 
     @staticmethod
     def _shared_prefix_lengths(plans, B: int) -> List[int]:
@@ -1053,14 +1100,17 @@ class InternVLChatModel(nn.Module):
         return pre
 
     def forward_shared_prefix(self, prompts, pixel_values: Optional[torch.Tensor] = None, image_flags: Optional[torch.Tensor] = None,
-                              motion_feature: Optional[torch.Tensor] = None, visual_tokens: Optional[torch.Tensor] = None, mos=None):
+                              motion_feature: Optional[torch.Tensor] = None, visual_tokens: Optional[torch.Tensor] = None, mos=None,
+                              return_logprobs: bool = False):
         """Score the same clips under several prompts that share their beginning - the reference's four quality
         perspectives ask four questions BEHIND the same system + frame + motion tokens (8f-3) and
         run four full passes (stage2_eval.py evaluates one jsonl per perspective).  Here the common prefix runs once
         (ViT, projector, LLM prefill into the KV cache); every prompt then only continues its own few question / answer
         tokens over the cached keys (``aigv_llm_extend``).  ``prompts``: list of ``(input_ids[B, N_p], attention_mask,
         labels)``; returns the list of ``forward`` result dicts, one per prompt.  Causal attention makes the prefix rows
-        independent of what follows, so each result is that of a separate ``forward`` call up to kernel summation order."""
+        independent of what follows, so each result is that of a separate ``forward`` call up to kernel summation order.
+        ``return_logprobs``: every prompt's dict carries ``logprob`` and ``ce_loss`` as ``forward`` defines them - with candidate answers
+        as the prompts, their log-likelihoods behind one video prefix (README)."""
         if self.img_context_token_id is None:
             raise AssertionError("img_context_token_id must be set by the caller (stage2_eval.py:810)")
         if not prompts:
@@ -1068,6 +1118,7 @@ class InternVLChatModel(nn.Module):
         pixel_values, visual_tokens, motion_feature = self._take_ahead(pixel_values, visual_tokens, motion_feature)
         n_frames = visual_tokens.shape[0] if visual_tokens is not None else pixel_values.shape[0]
         plans = [self._plan(ids, am, lab, image_flags, n_frames) for (ids, am, lab) in prompts]
+        lp_labels = [self._logprob_labels(pl) for pl in plans] if return_logprobs else None
         B = prompts[0][0].shape[0]
         pre = self._shared_prefix_lengths(plans, B)
         p0 = plans[0]
@@ -1112,10 +1163,11 @@ class InternVLChatModel(nn.Module):
                                          native.i32_array(srows) if score is not None else None, native.ptr(score),
                                          native.i32_array(lrows) if lrows else None, len(lrows), amax.data_ptr(), 0,
                                          native.stream_ptr()), ctx)
+        lp = self._row_logprob(len(srows), torch.cat(lp_labels)) if return_logprobs else None   # rows [score rows | logit rows]
         outs, off = [], 0
         for p, (pl, (ids, _, _)) in enumerate(zip(plans, prompts)):
             outs.append(self._outputs(pl, B, ids.shape[1], score[p * B:(p + 1) * B] if score is not None else None,
-                                      amax[off:off + n_l[p]], mos))
+                                      amax[off:off + n_l[p]], mos, lp[off:off + n_l[p]] if lp is not None else None))
             off += n_l[p]
         return outs
 

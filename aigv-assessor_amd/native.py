@@ -11,7 +11,7 @@ from typing import Optional
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AIGV_AMD_LIB") or os.path.join(HERE, "libaigv_amd.so")   # (the override: kernel-ablation builds of scripts/)
-ABI_VERSION = 1
+ABI_VERSION = 2   # = AIGV_ABI_VERSION; raised whenever the exported symbol set changes
 
 
 class NativeError(RuntimeError):
@@ -65,6 +65,7 @@ PROTOTYPES = {
     "aigv_decode_step": (_I, [_P, _P, _P, _P]),
     "aigv_out_row_logits": (_I, [_P, _I, _I, _P, _I, _P]),
     "aigv_out_row_hidden": (_I, [_P, _I, _I, _P, _I, _P]),
+    "aigv_out_row_logprob": (_I, [_P, _I, _I, _P, _P, _P]),
     "aigv_decode_eos": (_I, [_P, _P, _P, _I64P, _I, C.c_int64, _P]),
     "aigv_op_gemm": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
     "aigv_op_gemm_rows": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _I, C.POINTER(C.c_int32), _I, _I, _I, _I, _P]),
@@ -90,6 +91,7 @@ PROTOTYPES = {
     "aigv_op_pixel_shuffle": (_I, [_P, _I, _I, _P, _I, _P]),
     "aigv_op_im2col": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "aigv_op_lm_head_argmax": (_I, [_P, _I, _I, _P, _I, _P, _P, _P, _P]),
+    "aigv_op_label_logprob": (_I, [_P, _I, _I, _I, _P, _P, _P]),
     "aigv_op_frame_ingest": (_I, [_P, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P]),
     "aigv_op_frame_resize_ingest": (_I, [_P, _I, _I, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, _P, _P]),
     "aigv_tune_gemm": (_I, [_I, C.c_double]),
@@ -116,7 +118,10 @@ def load() -> C.CDLL:
     import torch  # noqa: F401  - before the library: it must bind to the HIP runtime torch has loaded (two runtimes in one process do not share devices)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in PROTOTYPES.items():
-        fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:   # a library built from older sources (a stale .so): say so, not just which attribute is absent
+            raise NativeError(f"ABI mismatch: {LIB_PATH} does not match binding ABI {ABI_VERSION} (rebuild it): missing {name}") from None
         fn.restype = res
         fn.argtypes = args
     if lib.aigv_abi_version() != ABI_VERSION:

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define AIGV_ABI_VERSION 1
+#define AIGV_ABI_VERSION 2   /* 2: aigv_out_row_logprob, aigv_op_label_logprob */
 
 typedef struct aigv_ctx aigv_ctx;
 
@@ -200,6 +200,15 @@ int aigv_out_row_logits(aigv_ctx* ctx, int first_row, int n_rows, void* logits_b
  * score rows this is the reference's hidden_states[-1][:, -4, :], the input of its score head (modeling_internvl_chat.py:469-481) - the
  * slice of `output_hidden_states=True` the eval path consumes.  Rows in the order [score rows | logit rows]. */
 int aigv_out_row_hidden(aigv_ctx* ctx, int first_row, int n_rows, void* hidden_bf16, int ldo, void* stream);
+/* Label log-probabilities of the same rows: logprob[i] = log_softmax(logits.float())[labels[i]] of row first_row + i, the per-token term of
+ * the reference's CrossEntropyLoss over the answer tokens (internvl_chat_eval2/modeling_internvl_chat.py:452-463; stage-1 training
+ * minimises its mean, internvl_chat_stage1_lora/modeling_internvl_chat.py:386-398).  logits: the bf16 lm-head output that the reference
+ * upcasts (modeling_internlm2.py:1095-1096), computed again per 64 rows into a context-owned scratch (allocated with the workspaces:
+ * nothing is allocated here, so the call may be captured into a graph) - the 4-slice form of the fused argmax for every row count, so a
+ * row's value does not depend on its batch mates.  The softmax runs in fp32: online max and sum of exponentials per lane, reduced in a
+ * fixed order.  labels: DEVICE int64 [n_rows]; a label outside [0, vocab) (-100 included) gives NaN.  logprob: DEVICE fp32 [n_rows].
+ * Rows in the order [score rows | logit rows], as aigv_out_row_logits. */
+int aigv_out_row_logprob(aigv_ctx* ctx, int first_row, int n_rows, const int64_t* labels, float* logprob, void* stream);
 /* End-of-sequence bookkeeping of generate()'s token loop on the device (the reference defers to HF's loop: next = next * unfinished +
  * pad * (1 - unfinished); unfinished &= next not in eos_token_id; stop when every sequence has finished - modeling_internvl_chat.py:
  * 798-809).  tokens: DEVICE int64[n] (n = sequences of the kept KV state), in: the step's raw tokens (aigv_decode_step's `next`, or the
@@ -275,6 +284,9 @@ int aigv_op_im2col(const void* frames, int n_frames, int channels, int image_siz
                    void* stream);
 int aigv_op_lm_head_argmax(const void* h, int rows, int hidden, const void* W, int vocab, void* scratch_u64,
                            int64_t* idx, float* val, void* stream);
+/* The log-softmax of aigv_out_row_logprob on caller-supplied bf16 logits [rows, ldo >= vocab]: out[r] = fp32 log_softmax(logits[r, :vocab])
+ * [labels[r]], NaN where labels[r] is outside [0, vocab).  One workgroup per row; the bits of a row do not depend on `rows`. */
+int aigv_op_label_logprob(const void* logits_bf16, int rows, int vocab, int ldo, const int64_t* labels, float* out, void* stream);
 
 /* Frame ingest: uint8 [F,H,W,3] RGB frames already at the model resolution -> bf16 NCHW
  * pixel_values = bf16((u/255 - mean[c]) / std[c])  (torchvision ToTensor + Normalize of dataset.py:267-274 and the
