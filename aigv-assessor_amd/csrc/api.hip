@@ -153,6 +153,17 @@ int fail(aigv_ctx* c, int code, const char* fmt, ...) {
     if (r_ != 0) return r_; \
   } while (0)
 
+static_assert(AIGV_MAX_KV_CAPACITY == AIGV_DECODE_MAX_CHUNKS * AIGV_DECODE_KEYS_PER_CHUNK, "the header's bound is the decode merge pass's");
+
+// The KV capacity every kernel of the context can serve: the decode attention's merge pass bounds it (kernels.h); the others
+// address the caches in 64-bit offsets.
+const char* kv_capacity_check(int kv_capacity) {
+  if (kv_capacity < 0 || kv_capacity > AIGV_MAX_KV_CAPACITY)
+    return kv_capacity < 0 ? "kv_capacity must not be negative"
+                           : "kv_capacity above AIGV_MAX_KV_CAPACITY (262144 tokens per clip: the decode attention's merge pass holds its chunk statistics in LDS)";
+  return nullptr;
+}
+
 template <typename T>
 int dalloc(aigv_ctx* c, T** out, size_t count) {
   void* p = nullptr;
@@ -887,6 +898,7 @@ int aigv_ctx_create(int device, const aigv_config* cfg, aigv_ctx** out) {
   if (k.n_score_layers < 1 || k.n_score_layers > 8) return fail(nullptr, AIGV_ERR_ARG, "n_score_layers out of range");
   if (k.max_frames <= 0 || k.vit_chunk <= 0 || k.max_tokens <= 0 || k.max_seqs <= 0 || k.max_out_rows <= 0)
     return fail(nullptr, AIGV_ERR_ARG, "capacities must be positive");
+  if (const char* m = kv_capacity_check(k.kv_capacity)) return fail(nullptr, AIGV_ERR_ARG, "%s", m);
 
   aigv_ctx* c = new (std::nothrow) aigv_ctx();
   if (!c) return fail(nullptr, AIGV_ERR_ALLOC, "out of host memory");
@@ -935,6 +947,7 @@ int aigv_ctx_resize(aigv_ctx* c, const aigv_config* cfg) {
   if (memcmp(&a, &b, sizeof(aigv_config)) != 0) return fail(c, AIGV_ERR_ARG, "aigv_ctx_resize: only the capacities may change (create a new context for another model)");
   if (b.max_frames <= 0 || b.vit_chunk <= 0 || b.max_tokens <= 0 || b.max_seqs <= 0 || b.max_out_rows <= 0)
     return fail(c, AIGV_ERR_ARG, "capacities must be positive");
+  if (const char* m = kv_capacity_check(b.kv_capacity)) return fail(c, AIGV_ERR_ARG, "%s", m);
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipDeviceSynchronize());
   for (void* p : c->ws_allocs) hipFree(p);
@@ -2134,6 +2147,98 @@ int aigv_op_label_logprob(const void* logits_bf16, int rows, int vocab, int ldo,
   if (rows < 0 || vocab < 1 || ldo < vocab || (rows > 0 && (!logits_bf16 || !labels || !out)))
     return fail(nullptr, AIGV_ERR_ARG, "aigv_op_label_logprob: bad argument (rows %d, vocab %d, ldo %d)", rows, vocab, ldo);
   HIPCHK(nullptr, aigv_launch_label_logprob((const bf16_t*)logits_bf16, rows, vocab, ldo, labels, out, (hipStream_t)stream));
+  return 0;
+}
+
+// ---- the decode step's kernels, one by one (test entry points): every argument is checked here, before any HIP call ----
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+int64_t aigv_op_attention_decode_ws_floats(int n_seq, int n_kv, int g, int cap) {
+  if (n_seq < 1 || n_kv < 1 || g < 1 || g > 8 || cap < 1 || cap > AIGV_MAX_KV_CAPACITY) return -1;
+  return (int64_t)aigv_attention_decode_ws_floats(n_seq, n_kv, g, cap);
+}
+
+int aigv_op_attention_decode(const void* q, int ldq, int q_group_stride, const void* kc, const void* vc, const int32_t* kv_lens, int cap,
+                             void* o, int ldo, int n_seq, int n_kv, int g, int head_dim, float post_div, int max_kv_len, float* ws,
+                             int64_t ws_floats, void* stream) {
+  const char* op = "aigv_op_attention_decode";
+  if (!q || !kc || !vc || !kv_lens || !o || !ws) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+  if (head_dim != 128) return fail(nullptr, AIGV_ERR_ARG, "%s: head_dim must be 128, got %d", op, head_dim);
+  if (g < 1 || g > 8) return fail(nullptr, AIGV_ERR_ARG, "%s: g = %d query heads per KV head (1..8)", op, g);
+  if (n_seq < 1 || n_kv < 1) return fail(nullptr, AIGV_ERR_ARG, "%s: n_seq %d, n_kv %d must be positive", op, n_seq, n_kv);
+  if (cap < 1 || cap > AIGV_MAX_KV_CAPACITY || max_kv_len < 1 || max_kv_len > cap)
+    return fail(nullptr, AIGV_ERR_ARG, "%s: needs 1 <= max_kv_len (%d) <= cap (%d) <= %d", op, max_kv_len, cap, AIGV_MAX_KV_CAPACITY);
+  if (q_group_stride < g * head_dim || ldq < (n_kv - 1) * q_group_stride + g * head_dim || ldo < n_kv * g * head_dim)
+    return fail(nullptr, AIGV_ERR_ARG, "%s: strides too small (ldq %d, q_group_stride %d, ldo %d)", op, ldq, q_group_stride, ldo);
+  if (!aligned16(kc) || !aligned16(vc)) return fail(nullptr, AIGV_ERR_ARG, "%s: the caches must be 16-byte aligned", op);
+  const int64_t need = aigv_op_attention_decode_ws_floats(n_seq, n_kv, g, cap);
+  if (ws_floats < need) return fail(nullptr, AIGV_ERR_ARG, "%s: workspace of %lld floats, needs %lld", op, (long long)ws_floats, (long long)need);
+  HIPCHK(nullptr, aigv_launch_attention_decode((const bf16_t*)q, ldq, q_group_stride, (const bf16_t*)kc, (const bf16_t*)vc, kv_lens, cap, (bf16_t*)o,
+                                               ldo, n_seq, n_kv, g, head_dim, post_div, max_kv_len, ws, (hipStream_t)stream));
+  return 0;
+}
+
+// shared checks of the RoPE / KV-append GEMVs (bf16 and e4m3 forms)
+static int check_rope_kv(const char* op, const void* x, int ldx, int R, const void* W, int ldw, int N, int K, const void* qkv, int ldo,
+                         const int32_t* pos, const int32_t* seq, const void* cos, const void* sin, const void* kc, const void* vc, int g,
+                         int n_kv, int cap, int p) {
+  if (!x || !W || !qkv || !pos || !seq || !cos || !sin || !kc || !vc) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+  if (g < 1 || g > 8 || n_kv < 1 || N != n_kv * (g + 2) * 128)
+    return fail(nullptr, AIGV_ERR_ARG, "%s: N = %d is not n_kv (%d) x (g (%d) + 2) x 128 with g in 1..8", op, N, n_kv, g);
+  if (p != 1 && p != 2 && p != 4) return fail(nullptr, AIGV_ERR_ARG, "%s: p must be 1, 2 or 4, got %d", op, p);
+  if (R < 1 || R > (p == 1 ? 64 : 16 / p)) return fail(nullptr, AIGV_ERR_ARG, "%s: R = %d rows outside 1..%d for p = %d", op, R, p == 1 ? 64 : 16 / p, p);
+  if (K < 128 * p || K % (128 * p)) return fail(nullptr, AIGV_ERR_ARG, "%s: K = %d is not a multiple of %d", op, K, 128 * p);
+  if (cap < 1 || cap > AIGV_MAX_KV_CAPACITY) return fail(nullptr, AIGV_ERR_ARG, "%s: cap = %d outside 1..%d", op, cap, AIGV_MAX_KV_CAPACITY);
+  if (ldx < K || ldx % 8 || ldo < N || ldo % 4) return fail(nullptr, AIGV_ERR_ARG, "%s: bad leading dimension (ldx %d, ldo %d)", op, ldx, ldo);
+  if (!aligned16(x) || !aligned16(W) || !aligned16(kc) || !aligned16(vc) || ((uintptr_t)qkv & 7) || ((uintptr_t)cos & 7) || ((uintptr_t)sin & 7))
+    return fail(nullptr, AIGV_ERR_ARG, "%s: misaligned operand", op);
+  return 0;
+}
+
+int aigv_op_skinny_rope_kv(const void* x, int ldx, int R, const void* W, int ldw, int N, int K, void* qkv, int ldo, const int32_t* pos,
+                           const int32_t* seq, const void* cos, const void* sin, void* kc, void* vc, int g, int n_kv, int cap,
+                           const void* norm_w, float eps, int p, void* stream) {
+  const char* op = "aigv_op_skinny_rope_kv";
+  TRY(check_rope_kv(op, x, ldx, R, W, ldw, N, K, qkv, ldo, pos, seq, cos, sin, kc, vc, g, n_kv, cap, p));
+  if (ldw < K || ldw % 8) return fail(nullptr, AIGV_ERR_ARG, "%s: bad ldw %d", op, ldw);
+  if (norm_w && (R > 4 || !aigv_skinny_norm_fusable(K) || !aligned16(norm_w)))
+    return fail(nullptr, AIGV_ERR_ARG, "%s: the fused RMSNorm takes R <= 4 rows (got %d) and K = 4096 or 6144 (got %d)", op, R, K);
+  HIPCHK(nullptr, aigv_launch_skinny_rope_kv((const bf16_t*)x, ldx, R, (const bf16_t*)W, ldw, N, K, (bf16_t*)qkv, ldo, pos, seq, (const bf16_t*)cos,
+                                             (const bf16_t*)sin, (bf16_t*)kc, (bf16_t*)vc, g, n_kv, cap, 128, (hipStream_t)stream,
+                                             (const bf16_t*)norm_w, eps, p));
+  return 0;
+}
+
+int aigv_op_skinny_swiglu_normed(const void* x, int ldx, int R, const void* W, int ldw, int N, int K, void* out, int ldo,
+                                 const void* norm_w, float eps, int p, void* stream) {
+  const char* op = "aigv_op_skinny_swiglu_normed";
+  if (!x || !W || !out || !norm_w) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand (norm_w is required)", op);
+  if (R < 1 || R > 4 || !aigv_skinny_norm_fusable(K))
+    return fail(nullptr, AIGV_ERR_ARG, "%s: takes 1..4 rows (got %d) and K = 4096 or 6144 (got %d)", op, R, K);
+  if (p != 1 && p != 2 && p != 4) return fail(nullptr, AIGV_ERR_ARG, "%s: p must be 1, 2 or 4, got %d", op, p);
+  if (N < 32 || N % 32) return fail(nullptr, AIGV_ERR_ARG, "%s: N = %d is not a multiple of 32", op, N);
+  if (ldx < K || ldx % 8 || ldw < K || ldw % 8 || ldo < N / 2 || ldo % 4)
+    return fail(nullptr, AIGV_ERR_ARG, "%s: bad leading dimension (ldx %d, ldw %d, ldo %d)", op, ldx, ldw, ldo);
+  if (!aligned16(x) || !aligned16(W) || !aligned16(norm_w) || ((uintptr_t)out & 7)) return fail(nullptr, AIGV_ERR_ARG, "%s: misaligned operand", op);
+  HIPCHK(nullptr, aigv_launch_skinny_swiglu_normed((const bf16_t*)x, ldx, R, (const bf16_t*)W, ldw, N, K, (bf16_t*)out, ldo, (const bf16_t*)norm_w, eps,
+                                                   (hipStream_t)stream, p));
+  return 0;
+}
+
+int aigv_op_skinny_rope_kv_fp8(const void* x, int ldx, int R, const void* W_e4m3, int ldw, const float* w_scale, int N, int K, void* qkv,
+                               int ldo, const int32_t* pos, const int32_t* seq, const void* cos, const void* sin, void* kc, void* vc, int g,
+                               int n_kv, int cap, const void* norm_w, float eps, int p, void* stream) {
+  const char* op = "aigv_op_skinny_rope_kv_fp8";
+  TRY(check_rope_kv(op, x, ldx, R, W_e4m3, ldw, N, K, qkv, ldo, pos, seq, cos, sin, kc, vc, g, n_kv, cap, p));
+  if (!w_scale || ((uintptr_t)w_scale & 15)) return fail(nullptr, AIGV_ERR_ARG, "%s: w_scale missing or misaligned", op);
+  if (ldw < K || ldw % 16) return fail(nullptr, AIGV_ERR_ARG, "%s: bad ldw %d (bytes, a multiple of 16)", op, ldw);
+  if (!norm_w || R > 4 || !aigv_skinny_fp8_supported(K, true) || !aligned16(norm_w))
+    return fail(nullptr, AIGV_ERR_ARG, "%s: needs norm_w, R <= 4 rows (got %d) and K = 4096 or 6144 (got %d)", op, R, K);
+  const AigvRopeKv rk{pos, seq, (const bf16_t*)cos, (const bf16_t*)sin, (bf16_t*)kc, (bf16_t*)vc, g, n_kv, cap};
+  hipError_t e = aigv_launch_skinny_fp8((const bf16_t*)x, ldx, R, (const uint8_t*)W_e4m3, ldw, w_scale, N, K, nullptr, 0, (bf16_t*)qkv, ldo, 7, &rk,
+                                        (const bf16_t*)norm_w, eps, p, (hipStream_t)stream);
+  if (e != hipSuccess)
+    return fail(nullptr, e == hipErrorInvalidValue ? AIGV_ERR_ARG : AIGV_ERR_HIP, "%s (R=%d N=%d K=%d p=%d): %s", op, R, N, K, p, hipGetErrorString(e));
   return 0;
 }
 

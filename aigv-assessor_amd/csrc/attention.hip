@@ -677,51 +677,57 @@ __global__ __launch_bounds__(256) void attn_decode_partial_kernel(const bf16_t* 
   if (t < G) { wbase[(size_t)t * (D + 2)] = sM[t]; wbase[(size_t)t * (D + 2) + 1] = sL[t]; }
 }
 
-constexpr int MERGE_MAX_CHUNKS = 128;   // capacity / DC the merge kernel holds in LDS (a 16 384-token cache)
+static_assert(DC == AIGV_DECODE_KEYS_PER_CHUNK, "kernels.h states the chunk length");
+constexpr int merge_heads(int g) { return g >= 2 ? 2 : 1; }   // query heads per merge workgroup
 
 // pass 2: grid (kv heads x pairs of query heads, sequences); a workgroup merges the chunk partials of two query heads (256 outputs,
 // one per thread): chunk maxima -> global maximum, chunk weights exp(m - M), denominator (chunks in order), then the weighted sum
 // of the chunk accumulators with sixteen loads in flight (the chunk loop is a chain of L2 latencies, not of FMAs).
+// LDS: the chunk maxima and weights of its heads, 2 x HP x max_chunks floats, sized by the launch from the cache capacity.
 template <int G>
 __global__ __launch_bounds__(256) void attn_decode_merge_kernel(const float* __restrict__ ws, int max_chunks,
                                                                 const int32_t* __restrict__ kv_lens, bf16_t* __restrict__ o,
                                                                 int ldo) {
   constexpr int D = 128;
-  constexpr int HP = G >= 2 ? 2 : 1;                  // query heads per workgroup
+  constexpr int HP = merge_heads(G);
   constexpr int PAIRS = (G + HP - 1) / HP;
-  __shared__ float sM[HP][MERGE_MAX_CHUNKS], sW[HP][MERGE_MAX_CHUNKS];   // chunk maxima, then chunk weights exp(m - M)
+  extern __shared__ float merge_lds[];
+  float* const sM = merge_lds;                         // [HP][max_chunks] chunk maxima
+  float* const sW = merge_lds + HP * max_chunks;       // [HP][max_chunks] chunk sums, then chunk weights exp(m - M)
   __shared__ float sL[HP];
   const int hk = blockIdx.x / PAIRS, j0 = (blockIdx.x % PAIRS) * HP, seq = blockIdx.y, n_kv = gridDim.x / PAIRS;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int nch = (kv_lens[seq] + DC - 1) / DC;
+  const int nch = min((kv_lens[seq] + DC - 1) / DC, max_chunks);   // (a length past the capacity reads no LDS or workspace out of bounds)
   const float* base = ws + (((size_t)seq * n_kv + hk) * max_chunks) * G * (D + 2);
   for (int i = t; i < nch * HP; i += 256) {
     const int ch = i / HP, jj = i - ch * HP;
     if (j0 + jj < G) {
       const float* pp = base + ((size_t)ch * G + j0 + jj) * (D + 2);
-      sM[jj][ch] = pp[0];
-      sW[jj][ch] = pp[1];
+      sM[jj * max_chunks + ch] = pp[0];
+      sW[jj * max_chunks + ch] = pp[1];
     }
   }
   __syncthreads();
   if (wave < HP && j0 + wave < G) {   // one wave per head
-    const int jj = wave;
+    const float* const sMj = sM + wave * max_chunks;
+    float* const sWj = sW + wave * max_chunks;
     float m = -INFINITY;
-    for (int ch = lane; ch < nch; ch += 64) m = fmaxf(m, sM[jj][ch]);
+    for (int ch = lane; ch < nch; ch += 64) m = fmaxf(m, sMj[ch]);
     m = wave_max(m);
     float l = 0.f;
     for (int c0 = 0; c0 < nch; c0 += 64) {
       const int ch = c0 + lane;
-      const float w = ch < nch ? __expf(sM[jj][ch] - m) : 0.f;
-      const float lw = ch < nch ? sW[jj][ch] * w : 0.f;
-      if (ch < nch) sW[jj][ch] = w;
+      const float w = ch < nch ? __expf(sMj[ch] - m) : 0.f;
+      const float lw = ch < nch ? sWj[ch] * w : 0.f;
+      if (ch < nch) sWj[ch] = w;
       l += wave_sum(lw);
     }
-    if (lane == 0) sL[jj] = l;
+    if (lane == 0) sL[wave] = l;
   }
   __syncthreads();
   const int jj = t / D, d = t % D, j2 = j0 + jj;
   if (jj >= HP || j2 >= G) return;
+  const float* const sWj = sW + jj * max_chunks;
   float A = 0.f;
   int ch = 0;
   for (; ch + 16 <= nch; ch += 16) {
@@ -729,14 +735,14 @@ __global__ __launch_bounds__(256) void attn_decode_merge_kernel(const float* __r
 #pragma unroll
     for (int u = 0; u < 16; ++u) v[u] = base[((size_t)(ch + u) * G + j2) * (D + 2) + 2 + d];
 #pragma unroll
-    for (int u = 0; u < 16; ++u) A += v[u] * sW[jj][ch + u];
+    for (int u = 0; u < 16; ++u) A += v[u] * sWj[ch + u];
   }
   {   // the last partial group with clamped (re-read, weight 0) loads instead of a one-at-a-time tail
     float v[16];
 #pragma unroll
     for (int u = 0; u < 16; ++u) v[u] = ch < nch ? base[((size_t)min(ch + u, nch - 1) * G + j2) * (D + 2) + 2 + d] : 0.f;
 #pragma unroll
-    for (int u = 0; u < 16; ++u) A += ch + u < nch ? v[u] * sW[jj][ch + u] : 0.f;
+    for (int u = 0; u < 16; ++u) A += ch + u < nch ? v[u] * sWj[ch + u] : 0.f;
   }
   const float L = sL[jj];
   o[(size_t)seq * ldo + (size_t)(hk * G + j2) * D + d] = f2bf(L > 0.f ? A / L : 0.f);
@@ -840,13 +846,14 @@ hipError_t aigv_launch_attention_decode(const bf16_t* q, int ldq, int q_group_st
                                         const bf16_t* vc, const int32_t* kv_lens, int cap, bf16_t* o, int ldo,
                                         int n_seq, int n_kv, int g, int head_dim, float post_div, int max_kv_len,
                                         float* ws, hipStream_t s) {
-  if (head_dim != 128 || !ws || max_kv_len <= 0 || max_kv_len > cap || (cap + DC - 1) / DC > MERGE_MAX_CHUNKS) return hipErrorInvalidValue;
+  if (head_dim != 128 || !ws || max_kv_len <= 0 || max_kv_len > cap || (cap + DC - 1) / DC > AIGV_DECODE_MAX_CHUNKS) return hipErrorInvalidValue;
   const int max_chunks = (cap + DC - 1) / DC;
+  const size_t merge_lds = (size_t)2 * merge_heads(g) * max_chunks * sizeof(float);   // <= 32 KB: no LDS attribute needed
   dim3 grid1((max_kv_len + DC - 1) / DC, n_kv, n_seq), grid2(n_kv * (g >= 2 ? (g + 1) / 2 : 1), n_seq);
 #define DEC(G)                                                                                                              \
   hipLaunchKernelGGL((attn_decode_partial_kernel<G>), grid1, dim3(256), 0, s, q, ldq, q_group_stride, kc, vc, kv_lens, cap, \
                      post_div, ws, max_chunks);                                                                              \
-  hipLaunchKernelGGL((attn_decode_merge_kernel<G>), grid2, dim3(256), 0, s, ws, max_chunks, kv_lens, o, ldo)
+  hipLaunchKernelGGL((attn_decode_merge_kernel<G>), grid2, dim3(256), merge_lds, s, ws, max_chunks, kv_lens, o, ldo)
   switch (g) {
     case 1: DEC(1); break;
     case 2: DEC(2); break;

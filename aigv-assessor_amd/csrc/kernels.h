@@ -110,7 +110,10 @@ struct AttnArgs {
 const char* aigv_attn_check(const AttnArgs& a, int head_dim);
 hipError_t aigv_launch_attention(const AttnArgs& a, int head_dim, hipStream_t s);
 // decode: one query row per sequence (fused qkv row), KV cache [seq][kv head][cap][D]; split-KV two-pass kernel,
-// ws = aigv_attention_decode_ws_floats(...) floats of scratch
+// ws = aigv_attention_decode_ws_floats(...) floats of scratch.  The merge pass holds 16 bytes of LDS per 128-key chunk of the
+// capacity: at most AIGV_DECODE_MAX_CHUNKS chunks (= AIGV_MAX_KV_CAPACITY tokens, include/aigv_amd.h)
+constexpr int AIGV_DECODE_KEYS_PER_CHUNK = 128;
+constexpr int AIGV_DECODE_MAX_CHUNKS = 2048;
 size_t aigv_attention_decode_ws_floats(int n_seq, int n_kv, int g, int cap);
 hipError_t aigv_launch_attention_decode(const bf16_t* q, int ldq, int q_group_stride, const bf16_t* kc,
                                         const bf16_t* vc, const int32_t* kv_lens, int cap, bf16_t* o, int ldo,

@@ -11,7 +11,7 @@ from typing import Optional
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AIGV_AMD_LIB") or os.path.join(HERE, "libaigv_amd.so")   # (the override: kernel-ablation builds of scripts/)
-ABI_VERSION = 2   # = AIGV_ABI_VERSION; raised whenever the exported symbol set changes
+ABI_VERSION = 3   # = AIGV_ABI_VERSION; raised whenever the exported symbol set changes
 
 
 class NativeError(RuntimeError):
@@ -92,6 +92,11 @@ PROTOTYPES = {
     "aigv_op_im2col": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "aigv_op_lm_head_argmax": (_I, [_P, _I, _I, _P, _I, _P, _P, _P, _P]),
     "aigv_op_label_logprob": (_I, [_P, _I, _I, _I, _P, _P, _P]),
+    "aigv_op_attention_decode": (_I, [_P, _I, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _F, _I, _P, C.c_int64, _P]),
+    "aigv_op_attention_decode_ws_floats": (C.c_int64, [_I, _I, _I, _I]),
+    "aigv_op_skinny_rope_kv": (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _F, _I, _P]),
+    "aigv_op_skinny_swiglu_normed": (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _I, _P, _F, _I, _P]),
+    "aigv_op_skinny_rope_kv_fp8": (_I, [_P, _I, _I, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _F, _I, _P]),
     "aigv_op_frame_ingest": (_I, [_P, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P]),
     "aigv_op_frame_resize_ingest": (_I, [_P, _I, _I, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, _P, _P]),
     "aigv_tune_gemm": (_I, [_I, C.c_double]),

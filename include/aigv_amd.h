@@ -33,7 +33,11 @@
 extern "C" {
 #endif
 
-#define AIGV_ABI_VERSION 2   /* 2: aigv_out_row_logprob, aigv_op_label_logprob */
+#define AIGV_ABI_VERSION 3   /* 2: aigv_out_row_logprob, aigv_op_label_logprob; 3: the decode-step operators (aigv_op_attention_decode ...) */
+
+/* Largest aigv_config.kv_capacity a context accepts (tokens per clip): the decode attention's merge pass holds 16 bytes of LDS per
+ * 128-key chunk of the capacity (32 KB at this bound). */
+#define AIGV_MAX_KV_CAPACITY 262144
 
 typedef struct aigv_ctx aigv_ctx;
 
@@ -73,7 +77,7 @@ typedef struct aigv_config {
   int32_t max_tokens;        /* packed tokens per aigv_llm_prefill call */
   int32_t max_seqs;          /* clips per call */
   int32_t max_out_rows;      /* lm-head rows per call (answer rows), <= 64 per launch, looped */
-  int32_t kv_capacity;       /* per-clip KV-cache length for decode (0 = no decode support) */
+  int32_t kv_capacity;       /* per-clip KV-cache length for decode (0 = no decode support; at most AIGV_MAX_KV_CAPACITY) */
 } aigv_config;
 
 /* ---- lifetime ------------------------------------------------------------------------------------ */
@@ -287,6 +291,40 @@ int aigv_op_lm_head_argmax(const void* h, int rows, int hidden, const void* W, i
 /* The log-softmax of aigv_out_row_logprob on caller-supplied bf16 logits [rows, ldo >= vocab]: out[r] = fp32 log_softmax(logits[r, :vocab])
  * [labels[r]], NaN where labels[r] is outside [0, vocab).  One workgroup per row; the bits of a row do not depend on `rows`. */
 int aigv_op_label_logprob(const void* logits_bf16, int rows, int vocab, int ldo, const int64_t* labels, float* out, void* stream);
+
+/* ---- the kernels of aigv_decode_step, one by one (parity tests; ABI 3) ----------------------------------------------------------------
+ * Every pointer is DEVICE memory; the arguments are checked on the host before anything is launched (AIGV_ERR_ARG with a message
+ * naming the op); device-side values (kv_lens, pos, seq) are the caller's promise.
+ *
+ * Split-KV decode attention (head_dim 128, g = 1..8 query heads per KV head): for sequence b and query head h = kvh * g + j,
+ *   o[b * ldo + h * 128 + d] = bf16(softmax(q k^T / post_div) v) over keys 0 .. kv_lens[b] - 1 of kc / vc [n_seq][n_kv][cap][128],
+ * q[b * ldq + kvh * q_group_stride + j * 128 + d] (the fused wqkv row).  The eager path's rounding points: scores -> bf16,
+ * / post_div -> bf16, fp32 softmax with P -> bf16 per 128-key chunk, chunks merged in fp32.  1 <= kv_lens[b] <= max_kv_len <= cap
+ * <= AIGV_MAX_KV_CAPACITY.  ws: fp32 scratch of aigv_op_attention_decode_ws_floats(n_seq, n_kv, g, cap) floats (ws_floats = its
+ * size; a smaller one is refused) = n_seq * n_kv * ceil(cap / 128) * g * 130. */
+int aigv_op_attention_decode(const void* q, int ldq, int q_group_stride, const void* kc, const void* vc, const int32_t* kv_lens, int cap,
+                             void* o, int ldo, int n_seq, int n_kv, int g, int head_dim, float post_div, int max_kv_len, float* ws,
+                             int64_t ws_floats, void* stream);
+int64_t aigv_op_attention_decode_ws_floats(int n_seq, int n_kv, int g, int cap);   /* -1 for arguments the op refuses */
+/* The wqkv GEMV of a decode step with RoPE and the KV-cache append in its epilogue: y = x[R, K] . W[N, K]^T, N = n_kv (g + 2) 128 in
+ * groups of [g query heads | K | V].  Row r: query slots -> bf16(y) rotated (three bf16 roundings as aigv_op_rope, tables cos / sin
+ * [max_pos, 64] at position pos[r]) into qkv[r * ldo + slot * 128 ..] (the K / V columns of qkv are not written); the K slot,
+ * rotated, and the V slot, unrotated, into kc / vc [seq][n_kv][cap][128] at [seq[r]][kvh][pos[r]].  norm_w != NULL: x is the raw
+ * residual stream and the kernel applies the RMSNorm (norm_w, eps) itself, with the bits of aigv_op_rmsnorm (R <= 4, K = 4096 or
+ * 6144).  p = 1 / 2 / 4: 16 / 8 / 4 rows of W per workgroup (R <= 64 / 8 / 4); K % (128 p) == 0. */
+int aigv_op_skinny_rope_kv(const void* x, int ldx, int R, const void* W, int ldw, int N, int K, void* qkv, int ldo, const int32_t* pos,
+                           const int32_t* seq, const void* cos, const void* sin, void* kc, void* vc, int g, int n_kv, int cap,
+                           const void* norm_w, float eps, int p, void* stream);
+/* w1|w3 of a decode step with the RMSNorm in front: out[R, N / 2] = SwiGLU(RMSNorm(x) . W^T), W = w1 / w3 interleaved in 16-row blocks
+ * (aigv_op_skinny_gemm epi 2); the bits of aigv_op_rmsnorm followed by aigv_op_skinny_gemm in form p.  R <= 4, K = 4096 or 6144. */
+int aigv_op_skinny_swiglu_normed(const void* x, int ldx, int R, const void* W, int ldw, int N, int K, void* out, int ldo,
+                                 const void* norm_w, float eps, int p, void* stream);
+/* The e4m3 form of aigv_op_skinny_rope_kv (fp8 mode; aigv_op_skinny_gemm_fp8's arithmetic, its epi 7): W_e4m3 [N, ldw bytes] with one
+ * fp32 scale per output channel, x RMS-normalised (norm_w required) and quantised per row inside the kernel.  R <= 4 and <= 16 / p,
+ * K = 4096 or 6144. */
+int aigv_op_skinny_rope_kv_fp8(const void* x, int ldx, int R, const void* W_e4m3, int ldw, const float* w_scale, int N, int K, void* qkv,
+                               int ldo, const int32_t* pos, const int32_t* seq, const void* cos, const void* sin, void* kc, void* vc, int g,
+                               int n_kv, int cap, const void* norm_w, float eps, int p, void* stream);
 
 /* Frame ingest: uint8 [F,H,W,3] RGB frames already at the model resolution -> bf16 NCHW
  * pixel_values = bf16((u/255 - mean[c]) / std[c])  (torchvision ToTensor + Normalize of dataset.py:267-274 and the

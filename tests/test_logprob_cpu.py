@@ -1,4 +1,4 @@
-"""The label log-probability feature without a GPU: the C ABI it adds (header, library exports, ctypes prototypes, ABI version 2),
+"""The label log-probability feature without a GPU: the C ABI it adds (header, library exports, ctypes prototypes; ABI version 2, now 3),
 the clear error a stale library gives, the host-side label checks of ``return_logprobs`` and the per-item results of
 ``eval_utils.batched``."""
 import ctypes
@@ -15,12 +15,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("aigv_out_row_logprob", "aigv_op_label_logprob")
 
 
-def test_abi_2_declares_and_exports_the_logprob_entry_points():
+def test_abi_3_declares_and_exports_the_logprob_entry_points():
     header = open(os.path.join(ROOT, "include", "aigv_amd.h")).read()
-    assert re.search(r"#define AIGV_ABI_VERSION 2\b", header)
-    assert native.ABI_VERSION == 2
+    assert re.search(r"#define AIGV_ABI_VERSION 3\b", header)
+    assert native.ABI_VERSION == 3
     lib = ctypes.CDLL(native.LIB_PATH)
-    assert lib.aigv_abi_version() == 2
+    assert lib.aigv_abi_version() == 3
     for name in NEW:
         assert re.search(r"\bint " + name + r"\(", header), name
         assert name in native.PROTOTYPES
