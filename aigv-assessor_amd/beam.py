@@ -36,9 +36,10 @@ def _gather(x: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
 
 def beam_search(first_logits: torch.Tensor, step: Callable[[torch.Tensor], torch.Tensor], reorder: Callable[[torch.Tensor], None],
                 num_beams: int, max_new_tokens: int, eos_ids: Sequence[int] = (), pad_id: Optional[int] = None,
-                length_penalty: float = 1.0, early_stopping=False, processors: Sequence[Callable] = ()) -> torch.Tensor:
+                length_penalty: float = 1.0, early_stopping=False, processors: Sequence[Callable] = (), return_scores: bool = False):
     """Best hypothesis per item: long [B, L] of NEW tokens, L = the longest returned hypothesis (an end token included), shorter ones
-    filled with ``pad_id`` (or the first end token when no pad id is set, as HF does)."""
+    filled with ``pad_id`` (or the first end token when no pad id is set, as HF does).  ``return_scores``: (tokens, fp32 [B] score of
+    each returned hypothesis - its summed log-probabilities over length ** length_penalty, HF's ``sequences_scores``)."""
     if num_beams < 2:
         raise ValueError("beam_search needs num_beams >= 2")
     if max_new_tokens < 1:
@@ -110,6 +111,8 @@ def beam_search(first_logits: torch.Tensor, step: Callable[[torch.Tensor], torch
         logits = step(run_seq[:, :, cur - 1])
 
     out_len = max(1, int(fin_len[:, 0].max()))
+    if return_scores:
+        return fin_seq[:, 0, :out_len], fin_score[:, 0]
     return fin_seq[:, 0, :out_len]
 
 

@@ -117,6 +117,7 @@ struct aigv_ctx {
   bf16_t *kc_alt = nullptr, *vc_alt = nullptr;   // second cache of the same size, made by the first aigv_kv_reorder (beam search gathers into it, then the two swap)
   int32_t* beam_ints = nullptr;                  // [2 * max_seqs]: parent slots | live lengths of a reorder
   float* dec_ws = nullptr;
+  float2* dec_lse = nullptr;  // aigv_decode_step_logprob: per-16-column log-sum-exp partials [min(max_seqs, 64)][ceil(vocab / 16)]
   int32_t *dec_pos = nullptr, *dec_seq = nullptr, *dec_kvlen = nullptr, *dec_slot = nullptr;   // device-side decode state
   std::vector<int32_t> h_dec;
   std::vector<int32_t> h_pos, h_seq, h_rowidx, h_kvlen;
@@ -854,6 +855,8 @@ static int alloc_workspaces(aigv_ctx* c) {
     }
     c->lp_ldo = (k.vocab + 3) / 4 * 4;   // allocated here, never inside a pass: the logprob pass may be captured into a graph
     if ((rc = dalloc(c, &c->l_lp, (size_t)64 * c->lp_ldo))) break;
+    // allocated here for the same reason (a decode step may be captured); a resize re-runs this function
+    if ((rc = dalloc(c, &c->dec_lse, (size_t)std::min(k.max_seqs, 64) * aigv_lm_head_lse_slots(k.vocab)))) break;
     if (k.kv_capacity > 0) {
       const size_t per = (size_t)k.llm_layers * k.max_seqs * k.llm_kv_heads * k.kv_capacity * c->head_dim;
       if ((rc = dalloc(c, &c->kc, per))) break;
@@ -1826,9 +1829,11 @@ static void decode_forms(aigv_ctx* c, int B, int* pq, int* po, int* p13, int* p2
   }
 }
 
-int aigv_decode_step(aigv_ctx* c, const int64_t* ids, int64_t* next, void* stream) {
-  if (!c || !ids || !next) return fail(c, AIGV_ERR_ARG, "aigv_decode_step: null argument");
-  if (!c->kv_valid) return fail(c, AIGV_ERR_STATE, "aigv_decode_step: no KV state (run aigv_llm_prefill with keep_kv)");
+// aigv_decode_step / aigv_decode_step_logprob (logprob != nullptr: the lm-head runs its argmax + log-sum-exp form)
+static int decode_step(aigv_ctx* c, const int64_t* ids, int64_t* next, float* logprob, void* stream) {
+  const char* op = logprob ? "aigv_decode_step_logprob" : "aigv_decode_step";
+  if (!c || !ids || !next) return fail(c, AIGV_ERR_ARG, "%s: null argument", op);
+  if (!c->kv_valid) return fail(c, AIGV_ERR_STATE, "%s: no KV state (run aigv_llm_prefill with keep_kv)", op);
   const aigv_config& k = c->cfg;
   const int B = c->kv_seqs, H = k.llm_hidden, I = k.llm_inter, D = c->head_dim, g = c->g, nkv = k.llm_kv_heads;
   if (B > 64) return fail(c, AIGV_ERR_ARG, "decode supports at most 64 clips per step");
@@ -1913,10 +1918,18 @@ int aigv_decode_step(aigv_ctx* c, const int64_t* ids, int64_t* next, void* strea
     TRY(run_skinny(c, c->l_ffn, I, B, L.w2, I, H, I, nullptr, c->l_h, H, c->l_h, H, 1, s, p2));
   }
   HIPCHK(c, aigv_launch_rmsnorm(c->l_h, H, c->final_norm, c->l_rows, H, B, H, k.rms_eps, nullptr, s));
-  HIPCHK(c, aigv_launch_lm_head_argmax(c->l_rows, B, H, c->lm_head, k.vocab, c->l_packed, next, nullptr, s));
+  if (logprob) HIPCHK(c, aigv_launch_lm_head_argmax_logprob(c->l_rows, B, H, c->lm_head, k.vocab, c->l_packed, c->dec_lse, next, nullptr, logprob, s));
+  else HIPCHK(c, aigv_launch_lm_head_argmax(c->l_rows, B, H, c->lm_head, k.vocab, c->l_packed, next, nullptr, s));
   HIPCHK(c, aigv_launch_advance(c->dec_pos, c->dec_kvlen, B, s));
   for (int b = 0; b < B; ++b) c->h_kvlen[b] += 1;
   return 0;
+}
+
+int aigv_decode_step(aigv_ctx* c, const int64_t* ids, int64_t* next, void* stream) { return decode_step(c, ids, next, nullptr, stream); }
+
+int aigv_decode_step_logprob(aigv_ctx* c, const int64_t* ids, int64_t* next, float* logprob, void* stream) {
+  if (!logprob) return fail(c, AIGV_ERR_ARG, "aigv_decode_step_logprob: null argument");
+  return decode_step(c, ids, next, logprob, stream);
 }
 
 int aigv_out_row_logits(aigv_ctx* c, int first_row, int n_rows, void* logits_bf16, int ldo, void* stream) {
@@ -2140,6 +2153,28 @@ int aigv_op_lm_head_argmax(const void* h, int rows, int hidden, const void* W_, 
                            float* val, void* stream) {
   HIPCHK(nullptr, aigv_launch_lm_head_argmax((const bf16_t*)h, rows, hidden, (const bf16_t*)W_, vocab,
                                              (unsigned long long*)scratch_u64, idx, val, (hipStream_t)stream));
+  return 0;
+}
+
+int64_t aigv_op_lm_head_argmax_logprob_scratch_bytes(int rows, int vocab) {
+  if (rows < 1 || rows > 64 || vocab < 1) return -1;
+  return (int64_t)(64 * sizeof(unsigned long long) + (size_t)rows * aigv_lm_head_lse_slots(vocab) * sizeof(float2));
+}
+
+int aigv_op_lm_head_argmax_logprob(const void* h, int rows, int hidden, const void* W_, int vocab, void* scratch, int64_t scratch_bytes,
+                                   int64_t* idx, float* val, float* logprob, void* stream) {
+  const char* op = "aigv_op_lm_head_argmax_logprob";
+  if (!h || !W_ || !scratch || !idx || !logprob) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+  if (rows < 1 || rows > 64) return fail(nullptr, AIGV_ERR_ARG, "%s: rows = %d outside 1..64", op, rows);
+  if (hidden < 128 || hidden % 128) return fail(nullptr, AIGV_ERR_ARG, "%s: hidden = %d is not a positive multiple of 128", op, hidden);
+  if (vocab < 1) return fail(nullptr, AIGV_ERR_ARG, "%s: vocab = %d must be positive", op, vocab);
+  if (((uintptr_t)h & 15) || ((uintptr_t)W_ & 15) || ((uintptr_t)scratch & 15)) return fail(nullptr, AIGV_ERR_ARG, "%s: h, W and scratch must be 16-byte aligned", op);
+  const int64_t need = aigv_op_lm_head_argmax_logprob_scratch_bytes(rows, vocab);
+  if (scratch_bytes < need) return fail(nullptr, AIGV_ERR_ARG, "%s: scratch of %lld bytes, needs %lld", op, (long long)scratch_bytes, (long long)need);
+  unsigned long long* packed = (unsigned long long*)scratch;
+  float2* part = (float2*)((char*)scratch + 64 * sizeof(unsigned long long));
+  HIPCHK(nullptr, aigv_launch_lm_head_argmax_logprob((const bf16_t*)h, rows, hidden, (const bf16_t*)W_, vocab, packed, part, idx, val, logprob,
+                                                     (hipStream_t)stream));
   return 0;
 }
 

@@ -18,7 +18,30 @@ namespace {
 #ifndef SKINNY_DEPTH2
 #define SKINNY_DEPTH2 8      // k-steps in flight of the two-slab one-row-tile forms (SwiGLU w1|w3, RoPE wqkv)
 #endif
-enum { SK_STORE = 0, SK_RESID = 1, SK_SWIGLU = 2, SK_GELU = 3, SK_ARGMAX = 4, SK_RELU = 5, SK_LS_RESID = 6, SK_ROPE_KV = 7 };
+enum { SK_STORE = 0, SK_RESID = 1, SK_SWIGLU = 2, SK_GELU = 3, SK_ARGMAX = 4, SK_RELU = 5, SK_LS_RESID = 6, SK_ROPE_KV = 7, SK_ARGMAX_LSE = 8 };
+
+// SK_ARGMAX_LSE: SK_ARGMAX plus the log-sum-exp of every row (generate()'s per-token log-probabilities, modeling_internlm2.py:1095-1096 +
+// log_softmax).  The argmax key is SK_ARGMAX's, bit for bit.  Besides it, every 16-column slab of W writes the (max, sum of exp(x - max))
+// pair of its bf16-rounded logits to its own slot of a partials buffer [R][ceil(N / 16)] - passed as `out`, `ldo` = ceil(N / 16) float2
+// per row - with no atomics: lane fq holds columns 4 fq .. 4 fq + 3 of the slab, pushed in column order, then two butterfly steps.  The
+// slot layout follows the 16-row slabs, not the workgroups (one or four slabs per workgroup depending on R), so a row's partials do
+// not depend on R; lse_finish_kernel merges them in a fixed order.
+__device__ __forceinline__ void lse_combine(float& m, float& s, float m2, float s2) {   // (-inf, 0) is the empty set; as logprob.hip
+  const float M = fmaxf(m, m2);
+  if (M == -INFINITY) return;
+  s = s * expf(m - M) + s2 * expf(m2 - M);
+  m = M;
+}
+
+__device__ __forceinline__ void lse_push(float& m, float& s, float x) {
+  if (x == -INFINITY) return;
+  if (x > m) {
+    s = s * expf(m - x) + 1.0f;
+    m = x;
+  } else {
+    s += expf(x - m);
+  }
+}
 
 // SK_ROPE_KV: the decode step's wqkv GEMV with RoPE and the KV-cache append in its epilogue (head_dim 128).  A workgroup takes the
 // two 16-row slabs of W that rotate_half pairs - dims 16 sub .. and 64 + 16 sub .. of one head slot - so a lane ends up holding
@@ -73,8 +96,9 @@ __global__ __launch_bounds__(NWV * 64) void skinny_kernel(const bf16_t* __restri
   extern __shared__ __attribute__((aligned(16))) bf16_t xs[];   // NORM: the normalised x rows [R][K]
   // W slabs (16 rows each) per workgroup.  The lm-head on the answer rows (40+ x rows) is bound by re-reading the x fragments
   // from L2 once per workgroup, not by streaming W: four slabs per workgroup share them.
-  constexpr int NS = (EPI == SK_SWIGLU || EPI == SK_ROPE_KV) ? 2 : (EPI == SK_ARGMAX && RT >= 2) ? 4 : 1;
-  static_assert(P == 1 || ((P == 2 || P == 4) && RT == 1 && EPI != SK_ARGMAX), "sub-slab forms: one row tile, 8 or 4 rows per slab");
+  constexpr bool AMAX = EPI == SK_ARGMAX || EPI == SK_ARGMAX_LSE;
+  constexpr int NS = (EPI == SK_SWIGLU || EPI == SK_ROPE_KV) ? 2 : (AMAX && RT >= 2) ? 4 : 1;
+  static_assert(P == 1 || ((P == 2 || P == 4) && RT == 1 && !AMAX), "sub-slab forms: one row tile, 8 or 4 rows per slab");
   constexpr int RS = 16 / P;                         // W rows per slab (= x rows the form can take)
   __shared__ float part[NWV - 1][NS][RT][4][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -230,7 +254,7 @@ __global__ __launch_bounds__(NWV * 64) void skinny_kernel(const bf16_t* __restri
 #pragma unroll
   for (int t = 0; t < RT; ++t) {
     const int r = own ? t * 16 + fr : R;
-    if constexpr (EPI == SK_ARGMAX) {
+    if constexpr (AMAX) {
       unsigned long long best = 0ull;
 #pragma unroll
       for (int sl = 0; sl < NS; ++sl)
@@ -245,6 +269,19 @@ __global__ __launch_bounds__(NWV * 64) void skinny_kernel(const bf16_t* __restri
       unsigned long long o = __shfl_xor(best, 16, 64); best = o > best ? o : best;
       o = __shfl_xor(best, 32, 64); best = o > best ? o : best;
       if (fq == 0 && r < R) atomicMax(packed + r, best);
+      if constexpr (EPI == SK_ARGMAX_LSE) {
+        float2* part = reinterpret_cast<float2*>(out);
+#pragma unroll
+        for (int sl = 0; sl < NS; ++sl) {
+          const int ns0 = n0 + sl * 16;            // the slab's first column (slot ns0 / 16)
+          float m = -INFINITY, sum = 0.f;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) lse_push(m, sum, ns0 + 4 * fq + e < N ? rbf(acc[sl][t][e]) : -INFINITY);
+          lse_combine(m, sum, __shfl_xor(m, 16, 64), __shfl_xor(sum, 16, 64));
+          lse_combine(m, sum, __shfl_xor(m, 32, 64), __shfl_xor(sum, 32, 64));
+          if (fq == 0 && r < R && ns0 < N) part[(size_t)r * ldo + ns0 / 16] = make_float2(m, sum);
+        }
+      }
     } else if constexpr (EPI == SK_ROPE_KV) {
       if (r < R) {
         const int hs = blockIdx.x / (64 / RS), d = (int)(blockIdx.x % (64 / RS)) * RS + 4 * fq;   // head slot; dims d .. d+3 and d+64 .. d+67
@@ -326,6 +363,43 @@ __global__ void unpack_argmax_kernel(const unsigned long long* __restrict__ pack
   }
 }
 
+// SK_ARGMAX_LSE's finisher, one workgroup of 256 threads per row: thread t merges slots t, t + 256, ... in order, then a butterfly
+// inside each wave and the four wave results in wave order (label_logprob_kernel's tree) -> lse = M + log S; idx / val as
+// unpack_argmax_kernel, logprob = val - lse.  The order depends on the slot count only: a row's bits do not depend on R.
+constexpr int LSE_THREADS = 256;
+__global__ __launch_bounds__(LSE_THREADS) void lse_finish_kernel(const unsigned long long* __restrict__ packed, const float2* __restrict__ part,
+                                                                int nslot, int64_t* __restrict__ idx, float* __restrict__ val,
+                                                                float* __restrict__ logprob) {
+  const int r = blockIdx.x;
+  const float2* row = part + (size_t)r * nslot;
+  float m = -INFINITY, s = 0.f;
+  for (int i = threadIdx.x; i < nslot; i += LSE_THREADS) {
+    const float2 p = row[i];
+    lse_combine(m, s, p.x, p.y);
+  }
+#pragma unroll
+  for (int off = AIGV_WAVE / 2; off >= 1; off >>= 1) lse_combine(m, s, __shfl_xor(m, off), __shfl_xor(s, off));
+  __shared__ float wm[LSE_THREADS / AIGV_WAVE], ws[LSE_THREADS / AIGV_WAVE];
+  const int wave = threadIdx.x / AIGV_WAVE, lane = threadIdx.x % AIGV_WAVE;
+  if (lane == 0) {
+    wm[wave] = m;
+    ws[wave] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  m = wm[0];
+  s = ws[0];
+#pragma unroll
+  for (int w = 1; w < LSE_THREADS / AIGV_WAVE; ++w) lse_combine(m, s, wm[w], ws[w]);
+  const unsigned long long p = packed[r];
+  unsigned int u = (unsigned)(p >> 32);
+  u = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
+  const float v = __uint_as_float(u);
+  idx[r] = (int64_t)(0xFFFFFFFFu - (unsigned)(p & 0xFFFFFFFFull));
+  if (val) val[r] = v;
+  logprob[r] = v - (m + logf(s));
+}
+
 // ---- score head ------------------------------------------------------------------------------------------
 // x = hidden[:, -4, :] (post final norm); if ANY NaN is present in the batch slice the reference applies
 // nan_to_num(nan=0, posinf=1e9, neginf=-1e9) to every row (modeling_internvl_chat.py:469-473); then a chain
@@ -395,7 +469,7 @@ hipError_t launch_skinny(const bf16_t* x, int ldx, int R, const bf16_t* W, int l
       return hipErrorInvalidValue;
     }
   }
-  const int ns = (EPI == SK_SWIGLU) ? 2 : (EPI == SK_ARGMAX && rt >= 2) ? 4 : 1;   // = NS of the kernel
+  const int ns = (EPI == SK_SWIGLU) ? 2 : ((EPI == SK_ARGMAX || EPI == SK_ARGMAX_LSE) && rt >= 2) ? 4 : 1;   // = NS of the kernel
   const int blocks = (N + 16 * ns - 1) / (16 * ns);
   // (non-temporal weight loads were measured SLOWER on the 8B decode shapes - wqkv 12.5 -> 14.8 us, w2 24.9 -> 29.9 us, w1|w3 47.9 -> 54.9 us -
   //  and the form was removed: plain cache policy everywhere)
@@ -514,6 +588,22 @@ hipError_t aigv_launch_lm_head_argmax(const bf16_t* h, int R, int H, const bf16_
   e = launch_skinny<SK_ARGMAX>(h, H, R, W, H, V, H, nullptr, nullptr, 0, nullptr, 0, packed, s);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(unpack_argmax_kernel, dim3((R + 63) / 64), dim3(64), 0, s, packed, out_idx, out_val, R);
+  return hipGetLastError();
+}
+
+size_t aigv_lm_head_lse_slots(int V) { return (size_t)(V + 15) / 16; }
+
+// aigv_launch_lm_head_argmax + the fused log-sum-exp (SK_ARGMAX_LSE): part holds R * aigv_lm_head_lse_slots(V) float2
+hipError_t aigv_launch_lm_head_argmax_logprob(const bf16_t* h, int R, int H, const bf16_t* W, int V, unsigned long long* packed, float2* part,
+                                              int64_t* out_idx, float* out_val, float* out_logprob, hipStream_t s) {
+  if (R <= 0) return hipSuccess;
+  if (R > 64 || H % 128 || V < 1 || !packed || !part || !out_idx || !out_logprob) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(packed, 0, sizeof(unsigned long long) * R, s);
+  if (e != hipSuccess) return e;
+  const int nslot = (int)aigv_lm_head_lse_slots(V);
+  e = launch_skinny<SK_ARGMAX_LSE>(h, H, R, W, H, V, H, nullptr, nullptr, 0, reinterpret_cast<bf16_t*>(part), nslot, packed, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(lse_finish_kernel, dim3(R), dim3(LSE_THREADS), 0, s, packed, part, nslot, out_idx, out_val, out_logprob);
   return hipGetLastError();
 }
 

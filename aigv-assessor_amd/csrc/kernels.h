@@ -171,6 +171,12 @@ hipError_t aigv_launch_skinny_rope_kv(const bf16_t* x, int ldx, int R, const bf1
 // lm-head on R gathered rows + argmax over the vocabulary (first maximal index, bf16-rounded logits)
 hipError_t aigv_launch_lm_head_argmax(const bf16_t* h, int R, int H, const bf16_t* W, int V,
                                       unsigned long long* packed, int64_t* out_idx, float* out_val, hipStream_t s);
+// the same plus the log-probability of the chosen token: logprob[r] = val[r] - logsumexp(bf16-rounded logits of row r) in fp32, the
+// sum merged from per-16-column partials part[R][aigv_lm_head_lse_slots(V)] in a fixed order (batch-invariant bits); idx / val are
+// aigv_launch_lm_head_argmax's bits.  val may be null.
+size_t aigv_lm_head_lse_slots(int V);
+hipError_t aigv_launch_lm_head_argmax_logprob(const bf16_t* h, int R, int H, const bf16_t* W, int V, unsigned long long* packed, float2* part,
+                                              int64_t* out_idx, float* out_val, float* out_logprob, hipStream_t s);
 // lm-head logits (bf16, the matmul output the reference upcasts) of R rows into out[R, ldo], ldo >= roundup(V, 4)
 // one_form: the 4-slice form for every row count (that of the fused argmax), so that a row's logits do not depend on how many rows
 // share the launch; otherwise <= 16 rows of a vocabulary <= 4096 take the 8-slice GEMV form

@@ -170,9 +170,13 @@ def all_gather_rows(local: torch.Tensor, counts: List[int], group=None) -> torch
 
 def score_clips_dp(model, pixel_values: torch.Tensor, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor],
                    image_flags: Optional[torch.Tensor], labels: torch.Tensor, motion_feature: Optional[torch.Tensor],
-                   mos: Optional[torch.Tensor] = None, group=None, prefer_gathered: bool = False) -> Dict[str, torch.Tensor]:
+                   mos: Optional[torch.Tensor] = None, group=None, prefer_gathered: bool = False,
+                   return_logprobs: bool = False) -> Dict[str, torch.Tensor]:
     """Score a batch of B clips (F frames in total) over all ranks of `group`; every rank passes the same host
     tensors and gets the full result: {'score1' [B], 'logit' [B*(N-1)], 'label' [B*(N-1)]}.
+
+    ``return_logprobs``: also 'logprob' [B*(N-1)] (each rank's clips through ``forward(return_logprobs=True)``, gathered in clip order) and
+    'ce_loss', computed from them with ``forward``'s expression - on one rank both are ``forward``'s own values, bit for bit.
 
     `model` is an InternVLChatModel (or any object with vit_tokens / forward(visual_tokens=...) / device / stage).
     ``prefer_gathered``: always feed the projector / LLM pass from the ALL-GATHERED token buffer, also where the rank's own shard would
@@ -220,6 +224,7 @@ def score_clips_dp(model, pixel_values: torch.Tensor, input_ids: torch.Tensor, a
     n1 = N - 1
     score_l = torch.zeros((chi - clo,), dtype=torch.float32, device=dev)
     logit_l = torch.full(((chi - clo) * n1,), -1, dtype=torch.long, device=dev)
+    logprob_l = torch.full(((chi - clo) * n1,), float("nan"), dtype=torch.float32, device=dev)
     own = chi > clo and lo <= clo * fpc and chi * fpc <= hi and not prefer_gathered
     tokens = None if own else finish_tokens()
     if chi > clo:
@@ -227,8 +232,10 @@ def score_clips_dp(model, pixel_values: torch.Tensor, input_ids: torch.Tensor, a
         out = model(mos=None if mos is None else mos[sl], pixel_values=None, input_ids=input_ids[sl],
                     attention_mask=None if attention_mask is None else attention_mask[sl],
                     image_flags=None if image_flags is None else image_flags[fl], labels=labels[sl],
-                    motion_feature=motion_l, visual_tokens=vis)
+                    motion_feature=motion_l, visual_tokens=vis, **({"return_logprobs": True} if return_logprobs else {}))
         logit_l = out["logit"]
+        if return_logprobs:
+            logprob_l = out["logprob"]
         if "score1" in out:
             score_l = out["score1"].float()
     if own:
@@ -238,6 +245,14 @@ def score_clips_dp(model, pixel_values: torch.Tensor, input_ids: torch.Tensor, a
     score = all_gather_rows(score_l, counts, group)
     logit = all_gather_rows(logit_l.view(chi - clo, n1), counts, group).reshape(-1)
     res = {"logit": logit, "label": labels[..., 1:].contiguous().view(-1).to(logit.device)}
+    if return_logprobs:
+        logprob = all_gather_rows(logprob_l.view(chi - clo, n1), counts, group).reshape(-1)
+        res["logprob"] = logprob
+        scored = (labels[..., 1:].reshape(-1) != -100).nonzero().flatten().to(logprob.device)
+        if scored.numel():   # forward()'s ce_loss: CrossEntropyLoss()'s mean over the non-ignored labels, in fp64, rounded once
+            res["ce_loss"] = (-logprob.index_select(0, scored)).double().mean().float()
+        else:
+            res["ce_loss"] = torch.full((), float("nan"), dtype=torch.float32, device=logprob.device)
     if getattr(model, "stage", 2) == 2:
         res["score1"] = score.to(torch.bfloat16)
     return res

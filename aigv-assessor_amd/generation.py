@@ -1,0 +1,80 @@
+"""What ``generate`` / ``generate2`` / ``generate_stage2`` return beyond the token tensor: HF's ``return_dict_in_generate`` output.
+
+The reference's generate paths hand ``**generate_kwargs`` to HF's ``language_model.generate`` (modeling_internvl_chat.py:798-809), so a caller
+may ask for ``return_dict_in_generate=True`` with ``output_scores`` / ``output_logits`` and read ``out.sequences`` / ``out.scores``.  This
+module holds the host-side part of that: which flags were asked for, the output object (attribute and key access, like transformers'
+``ModelOutput``, without depending on transformers) and the log-probabilities of emitted tokens under the scores they were drawn from.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional, Sequence
+
+import torch
+
+FLAGS = ("return_dict_in_generate", "output_scores", "output_logits", "return_logprobs")
+FIELDS = ("sequences", "sequences_scores", "scores", "logits", "logprobs")
+
+
+class GenerateOutput(dict):
+    """The ``return_dict_in_generate`` result: ``out.sequences`` and ``out["sequences"]`` alike.
+
+    sequences          long [B, T]: the tensor generate returns without the flags
+    scores             (output_scores) tuple of T fp32 [B, V]: the processed scores of each step (after repetition penalty / n-gram
+                       blocking; for sampling also after temperature / top-k / top-p) - HF's ``scores``
+    logits             (output_logits) tuple of T fp32 [B, V]: the raw lm-head logits of each step
+    logprobs           (return_logprobs) fp32 [B, T]: log-probability of each emitted token under the distribution it was chosen from
+                       (``compute_transition_scores(sequences, scores, normalize_logits=True)``), NaN after the sequence's end token
+    sequences_scores   (beam search) fp32 [B]: HF's length-penalised score of the returned hypothesis
+    A field that was not asked for is absent from the keys and reads as None, as in transformers' output classes."""
+
+    def __getattr__(self, name):
+        if name in self:
+            return self[name]
+        if name in FIELDS:
+            return None
+        raise AttributeError(name)
+
+
+def output_flags(generation_config, kw: Dict) -> Dict[str, bool]:
+    """The four output flags from a generation config (dict or object) and the call's kwargs (kwargs win), all False by default."""
+    if isinstance(generation_config, dict):
+        cfg = {k: generation_config.get(k) for k in FLAGS}
+    else:
+        cfg = {k: getattr(generation_config, k, None) for k in FLAGS}
+    cfg.update({k: kw[k] for k in FLAGS if k in kw})
+    return {k: bool(cfg.get(k)) for k in FLAGS}
+
+
+def wants_output(flags: Dict[str, bool]) -> bool:
+    """True when generate returns a GenerateOutput: ``return_dict_in_generate``, or ``return_logprobs`` (which only the output object can
+    carry).  ``output_scores`` / ``output_logits`` alone change nothing, as in HF (the scores are returned only inside the dict)."""
+    return flags["return_dict_in_generate"] or flags["return_logprobs"]
+
+
+def token_logprobs(scores: torch.Tensor, tokens: torch.Tensor) -> torch.Tensor:
+    """fp32 [B]: log_softmax(scores)[b, tokens[b]] - one column of ``compute_transition_scores(..., normalize_logits=True)``."""
+    return torch.log_softmax(scores.float(), dim=-1).gather(1, tokens.view(-1, 1).long()).view(-1)
+
+
+def mask_after_end(logprob: torch.Tensor, live: Optional[torch.Tensor]) -> torch.Tensor:
+    """A column's log-probabilities with NaN where the sequence had already ended before it (``live`` False; None = all live)."""
+    if live is None:
+        return logprob
+    return torch.where(live, logprob, torch.full_like(logprob, float("nan")))
+
+
+def build(sequences: torch.Tensor, flags: Dict[str, bool], scores: Sequence[torch.Tensor] = (), logits: Sequence[torch.Tensor] = (),
+          logprobs: Sequence[torch.Tensor] = (), sequences_scores: Optional[torch.Tensor] = None) -> GenerateOutput:
+    """The output object of one generate call; per-step lists are cut to the returned length."""
+    T = sequences.shape[1]
+    out = GenerateOutput(sequences=sequences)
+    if flags["output_scores"]:
+        out["scores"] = tuple(scores[:T])
+    if flags["output_logits"]:
+        out["logits"] = tuple(logits[:T])
+    if flags["return_logprobs"]:
+        lp = list(logprobs[:T])
+        out["logprobs"] = torch.stack(lp, dim=1) if lp else torch.empty((sequences.shape[0], 0), dtype=torch.float32, device=sequences.device)
+    if sequences_scores is not None:
+        out["sequences_scores"] = sequences_scores
+    return out

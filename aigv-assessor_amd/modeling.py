@@ -1175,11 +1175,19 @@ class InternVLChatModel(nn.Module):
     EOS_CHECK_EVERY = 8     # tokens between two host reads of the device-side "finished" flags
 
     def _greedy(self, ids_packed, slot, cu, vis, n_vis, max_new_tokens: int, eos_ids: List[int], pad_id: int, motion=None, sampler=None,
-                processors=None, beams=None):
+                processors=None, beams=None, flags=None):
         """The token loop of generate(): HF's greedy search / multinomial sampling loop (the reference calls ``language_model.generate``,
         modeling_internvl_chat.py:798-809).  The end-of-sequence bookkeeping runs on the device (aigv_decode_eos): a finished sequence
         emits ``pad_id``, the loop stops once every sequence has emitted an end token - checked by the host only every EOS_CHECK_EVERY
-        tokens, so no per-token host synchronisation; the columns past HF's stopping point are cut off afterwards."""
+        tokens, so no per-token host synchronisation; the columns past HF's stopping point are cut off afterwards.
+
+        ``flags`` (generation.output_flags): with return_dict_in_generate / return_logprobs the result is a generation.GenerateOutput.  Greedy
+        decoding without processors takes its log-probabilities from the decode step's fused lm-head (aigv_decode_step_logprob; the first
+        token's from aigv_out_row_logprob) and never builds a [B, V] tensor; wherever the step's logits are materialised (processors,
+        sampling, output_scores / output_logits) they come from the scores the token was chosen from."""
+        from . import generation
+        flags = flags or {k: False for k in generation.FLAGS}
+        dict_out = generation.wants_output(flags)
         b = len(cu) - 1
         longest = max(cu[i + 1] - cu[i] for i in range(b))
         last_rows = [cu[i + 1] - 1 for i in range(b)]
@@ -1189,7 +1197,8 @@ class InternVLChatModel(nn.Module):
                                kv_cap=longest + max_new_tokens + 1)
         lib, ctx = native.load(), self._ctx
         if beams:
-            return self._beam_decode(b, [cu[i + 1] - cu[i] for i in range(b)], max_new_tokens, eos_ids, pad_id, processors or [], **beams)
+            seq, seq_scores = self._beam_decode(b, [cu[i + 1] - cu[i] for i in range(b)], max_new_tokens, eos_ids, pad_id, processors or [], **beams)
+            return generation.build(seq, flags, sequences_scores=seq_scores) if dict_out else seq
         ntk_decode = self._rope_seq_len(longest + max_new_tokens) != 0
         eos_a = (C.c_int64 * max(len(eos_ids), 1))(*[int(e) for e in eos_ids]) if eos_ids else None
         state = torch.zeros(b + 1, dtype=torch.int32, device=self.device)     # finished flags + live-column count (aigv_amd.h)
@@ -1198,6 +1207,14 @@ class InternVLChatModel(nn.Module):
         host_eos = len(eos_ids) > 8
         eos_t = torch.tensor([int(e) for e in eos_ids], dtype=torch.long, device=self.device) if host_eos else None
         outs: List[torch.Tensor] = []
+        want_scores = dict_out and flags["output_scores"]
+        want_logits = dict_out and flags["output_logits"]
+        want_lp = flags["return_logprobs"]
+        materialise = sampler is not None or bool(processors) or want_scores or want_logits
+        step_scores: List[torch.Tensor] = []
+        step_logits: List[torch.Tensor] = []
+        step_lp: List[torch.Tensor] = []
+        cur_lp: List[Optional[torch.Tensor]] = [None]      # log-probability of the current raw token (before the end-of-sequence rule)
 
         def eos_step(tok):
             live = state[:b] == 0
@@ -1208,22 +1225,41 @@ class InternVLChatModel(nn.Module):
 
         def pick(greedy_tok):
             """The step's raw token: the fused argmax, or - with logits processors / sampling - a choice over the rows' lm-head logits."""
-            if sampler is None and not processors:
+            if not materialise:
                 return greedy_tok
-            logits = self._row_logits(b)
+            raw = self._row_logits(b)
+            logits = raw
             if processors:
                 hist = torch.stack(outs, dim=1) if outs else torch.zeros((b, 0), dtype=torch.long, device=self.device)
                 for proc in processors:
                     logits = proc(hist, logits)
-            return self._sample(logits, **sampler) if sampler is not None else logits.argmax(-1)
+            if sampler is not None:     # = _sample, with the warped scores kept (HF's `scores` of a sampling run)
+                logits = self._warp(logits, sampler["temperature"], sampler["top_k"], sampler["top_p"])
+                tok = torch.multinomial(logits.softmax(-1), 1, generator=sampler["generator"]).squeeze(1)
+            else:
+                tok = greedy_tok if not processors else logits.argmax(-1)
+            if want_logits:
+                step_logits.append(raw)
+            if want_scores:
+                step_scores.append(logits)
+            if want_lp:
+                cur_lp[0] = generation.token_logprobs(logits, tok)
+            return tok
 
         tok = pick(nxt).contiguous()
+        if want_lp and not materialise:     # the first token: the prompt pass's rows, once per call
+            cur_lp[0] = torch.empty(b, dtype=torch.float32, device=self.device)
+            native.check(lib.aigv_out_row_logprob(ctx, 0, b, tok.data_ptr(), cur_lp[0].data_ptr(), native.stream_ptr()), ctx)
         for step in range(max_new_tokens):
+            if want_lp:
+                live = None if not eos_ids else (state[:b] == 0)
             if host_eos:
                 tok = eos_step(tok).contiguous()
             elif eos_ids:     # tok: raw -> emitted (pad for finished sequences); flags / live-column count advance on the device
                 native.check(lib.aigv_decode_eos(ctx, tok.data_ptr(), state.data_ptr(), eos_a, len(eos_ids), int(pad_id), native.stream_ptr()), ctx)
             outs.append(tok)
+            if want_lp:
+                step_lp.append(generation.mask_after_end(cur_lp[0], live))
             if step + 1 == max_new_tokens:
                 break
             if eos_ids and (step + 1) % self.EOS_CHECK_EVERY == 0 and bool(state[:b].all()):
@@ -1231,18 +1267,25 @@ class InternVLChatModel(nn.Module):
             new = torch.empty_like(tok)
             if ntk_decode:
                 self._rope_for_decode(longest + step + 1)
-            native.check(lib.aigv_decode_step(ctx, tok.data_ptr(), new.data_ptr(), native.stream_ptr()), ctx)
+            if want_lp and not materialise:
+                cur_lp[0] = torch.empty(b, dtype=torch.float32, device=self.device)
+                native.check(lib.aigv_decode_step_logprob(ctx, tok.data_ptr(), new.data_ptr(), cur_lp[0].data_ptr(), native.stream_ptr()), ctx)
+            else:
+                native.check(lib.aigv_decode_step(ctx, tok.data_ptr(), new.data_ptr(), native.stream_ptr()), ctx)
             tok = pick(new).contiguous()
         out = torch.stack(outs, dim=1)
         if eos_ids:
             out = out[:, : max(1, int(state[b].item()))]     # HF stops after the column in which the last live sequence ended
+        if dict_out:
+            return generation.build(out, flags, scores=step_scores, logits=step_logits, logprobs=step_lp)
         return out
 
     def _beam_decode(self, b: int, prompt_lens: List[int], max_new_tokens: int, eos_ids: List[int], pad_id, processors, num_beams: int,
-                     length_penalty: float = 1.0, early_stopping=False) -> torch.Tensor:
+                     length_penalty: float = 1.0, early_stopping=False):
         """HF beam search (beam.beam_search) behind a prompt pass that kept its KV: the prompts' caches are replicated once per beam
         (aigv_kv_fork: sequence k * b + i is beam k of prompt i), every step decodes all b * num_beams sequences in one aigv_decode_step
-        (the decoder weights stream once for all beams) and the chosen parents are gathered in the cache (aigv_kv_reorder)."""
+        (the decoder weights stream once for all beams) and the chosen parents are gathered in the cache (aigv_kv_reorder).
+        Returns (tokens, sequences_scores)."""
         from . import beam
         lib, ctx = native.load(), self._ctx
         V = self.config.llm_config.vocab_size
@@ -1273,7 +1316,7 @@ class InternVLChatModel(nn.Module):
             return self._row_logits(n).view(num_beams, b, V).transpose(0, 1)
 
         return beam.beam_search(first, step, reorder, num_beams, max_new_tokens, eos_ids=eos_ids, pad_id=pad_id, length_penalty=length_penalty,
-                                early_stopping=early_stopping, processors=processors)
+                                early_stopping=early_stopping, processors=processors, return_scores=True)
 
     @staticmethod
     def _gen_args(generation_config, kw):
@@ -1311,6 +1354,20 @@ class InternVLChatModel(nn.Module):
         eos = cfg.get("eos_token_id")
         eos = [] if eos is None else ([int(eos)] if not isinstance(eos, (list, tuple)) else [int(e) for e in eos])
         return int(cfg.get("max_new_tokens") or 20), eos, cfg.get("pad_token_id"), sampler, processors, beams
+
+    @staticmethod
+    def _gen_flags(generation_config, kw, beams=None):
+        """HF's output flags (return_dict_in_generate, output_scores, output_logits) and return_logprobs from a generation config / kwargs
+        (generation.output_flags).  Beam search returns ``sequences_scores`` only: per-step scores, logits and log-probabilities of its
+        hypotheses are not implemented and raise."""
+        from . import generation
+        flags = generation.output_flags(generation_config, kw)
+        if beams:
+            asked = [k for k in ("output_scores", "output_logits", "return_logprobs") if flags[k]]
+            if asked:
+                raise NotImplementedError(f"beam search (num_beams > 1) returns sequences and sequences_scores only: {', '.join(asked)} "
+                                          "not implemented")
+        return flags
 
     @staticmethod
     def _repetition_penalty(penalty: float):
@@ -1395,9 +1452,12 @@ class InternVLChatModel(nn.Module):
                  attention_mask: Optional[torch.Tensor] = None, visual_features: Optional[torch.Tensor] = None,
                  generation_config=None, output_hidden_states=None, return_dict=None, **generate_kwargs) -> torch.Tensor:
         """modeling_internvl_chat.py:769-811: every <IMG_CONTEXT> slot takes a visual token (no motion
-        token), then greedy decode with a KV cache.  Returns the NEW tokens [B, <=max_new_tokens]."""
+        token), then greedy decode with a KV cache.  Returns the NEW tokens [B, <=max_new_tokens] - or, with HF's
+        ``return_dict_in_generate`` (``output_scores`` / ``output_logits``) or ``return_logprobs``, a generation.GenerateOutput
+        (``sequences``, ``scores``, ``logits``, ``logprobs``; beam search: ``sequences_scores``)."""
         assert self.img_context_token_id is not None
         max_new, eos, pad, sampler, procs, beams = self._gen_args(generation_config, generate_kwargs)
+        flags = self._gen_flags(generation_config, generate_kwargs, beams)
         pad = self.config.llm_config.pad_token_id if pad is None else pad
         dev = self.device
         input_ids = input_ids.to(dev)
@@ -1413,13 +1473,14 @@ class InternVLChatModel(nn.Module):
             if int(sel.sum()) != n_vis:
                 raise ValueError(f"visual token count mismatch: {int(sel.sum())} slots vs {n_vis} tokens")
             slot[sel] = torch.arange(n_vis, device=dev, dtype=torch.int32)
-        return self._greedy(ids_packed, slot, cu, vis, n_vis, max_new, eos, pad, sampler=sampler, processors=procs, beams=beams)
+        return self._greedy(ids_packed, slot, cu, vis, n_vis, max_new, eos, pad, sampler=sampler, processors=procs, beams=beams, flags=flags)
 
     @torch.no_grad()
     def generate2(self, input_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, visual_features=None,
                   generation_config=None, output_hidden_states=None, return_dict=None, **generate_kwargs) -> torch.Tensor:
-        """modeling_internvl_chat.py:812-853: decode from precomputed input embeddings [B, N, C]."""
+        """modeling_internvl_chat.py:812-853: decode from precomputed input embeddings [B, N, C].  Output flags as ``generate``."""
         max_new, eos, pad, sampler, procs, beams = self._gen_args(generation_config, generate_kwargs)
+        flags = self._gen_flags(generation_config, generate_kwargs, beams)
         pad = self.config.llm_config.pad_token_id if pad is None else pad
         dev = self.device
         b, n, _ = input_embeds.shape
@@ -1432,7 +1493,7 @@ class InternVLChatModel(nn.Module):
         T = emb.shape[0]
         ids = torch.zeros(T, dtype=torch.long, device=dev)
         slot = torch.arange(T, dtype=torch.int32, device=dev)          # every row comes from `emb`
-        return self._greedy(ids, slot, cu, emb, T, max_new, eos, pad, sampler=sampler, processors=procs, beams=beams)
+        return self._greedy(ids, slot, cu, emb, T, max_new, eos, pad, sampler=sampler, processors=procs, beams=beams, flags=flags)
 
     @torch.no_grad()
     def generate_stage2(self, pixel_values, input_ids, attention_mask=None, image_flags=None, motion_feature=None,
@@ -1444,13 +1505,15 @@ class InternVLChatModel(nn.Module):
         if self.img_context_token_id is None:
             raise AssertionError("img_context_token_id must be set (stage2_eval.py:810)")
         max_new, eos, pad, sampler, procs, beams = self._gen_args(generation_config, generate_kwargs)
+        flags = self._gen_flags(generation_config, generate_kwargs, beams)
         pad = self.config.llm_config.pad_token_id if pad is None else pad
         B = input_ids.shape[0]
         plan = self._plan(input_ids, attention_mask, None, image_flags, pixel_values.shape[0], drop_dead_tail=False)
         motion_feature = self._motion_feature(pixel_values, B, motion_feature)
         self._native(n_frames=pixel_values.shape[0], n_tokens=plan["cu"][-1], n_clips=B)
         vit_embeds, motion = self._visual_inputs(pixel_values, None, motion_feature, plan)
-        return self._greedy(plan["ids_packed"], plan["slot"], plan["cu"], vit_embeds, plan["n_vis"], max_new, eos, pad, motion=motion, sampler=sampler, processors=procs, beams=beams)
+        return self._greedy(plan["ids_packed"], plan["slot"], plan["cu"], vit_embeds, plan["n_vis"], max_new, eos, pad, motion=motion, sampler=sampler, processors=procs, beams=beams,
+                            flags=flags)
 
     def chat2(self, tokenizer, pixel_values, input_ids, generation_config, attention_mask, history=None,
               return_history=False, image_flags=None, IMG_START_TOKEN="<img>", IMG_END_TOKEN="</img>",

@@ -63,6 +63,7 @@ PROTOTYPES = {
     "aigv_get_attention_numerics": (_I, [_P]),
     "aigv_ctx_tune": (_I, [_P, _I, _I]),
     "aigv_decode_step": (_I, [_P, _P, _P, _P]),
+    "aigv_decode_step_logprob": (_I, [_P, _P, _P, _P, _P]),
     "aigv_out_row_logits": (_I, [_P, _I, _I, _P, _I, _P]),
     "aigv_out_row_hidden": (_I, [_P, _I, _I, _P, _I, _P]),
     "aigv_out_row_logprob": (_I, [_P, _I, _I, _P, _P, _P]),
@@ -91,6 +92,8 @@ PROTOTYPES = {
     "aigv_op_pixel_shuffle": (_I, [_P, _I, _I, _P, _I, _P]),
     "aigv_op_im2col": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "aigv_op_lm_head_argmax": (_I, [_P, _I, _I, _P, _I, _P, _P, _P, _P]),
+    "aigv_op_lm_head_argmax_logprob": (_I, [_P, _I, _I, _P, _I, _P, C.c_int64, _P, _P, _P, _P]),
+    "aigv_op_lm_head_argmax_logprob_scratch_bytes": (C.c_int64, [_I, _I]),
     "aigv_op_label_logprob": (_I, [_P, _I, _I, _I, _P, _P, _P]),
     "aigv_op_attention_decode": (_I, [_P, _I, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _F, _I, _P, C.c_int64, _P]),
     "aigv_op_attention_decode_ws_floats": (C.c_int64, [_I, _I, _I, _I]),

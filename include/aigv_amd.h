@@ -33,7 +33,9 @@
 extern "C" {
 #endif
 
-#define AIGV_ABI_VERSION 3   /* 2: aigv_out_row_logprob, aigv_op_label_logprob; 3: the decode-step operators (aigv_op_attention_decode ...) */
+#define AIGV_ABI_VERSION 3   /* 2: aigv_out_row_logprob, aigv_op_label_logprob; 3: the decode-step operators (aigv_op_attention_decode ...),
+                                later joined by aigv_decode_step_logprob and aigv_op_lm_head_argmax_logprob (added symbols only: a library
+                                without them is refused at load time, "missing <name>") */
 
 /* Largest aigv_config.kv_capacity a context accepts (tokens per clip): the decode attention's merge pass holds 16 bytes of LDS per
  * 128-key chunk of the capacity (32 KB at this bound). */
@@ -194,6 +196,11 @@ int aigv_set_gemm_mode(aigv_ctx* ctx, int mode);
 /* One greedy decode step for every clip of the last keep_kv prefill (generate(): modeling_internvl_chat.py:769-811,
  * modeling_internlm2.py:1126-1163).  ids[B] int64 device (the previous tokens) -> next[B] int64 device. */
 int aigv_decode_step(aigv_ctx* ctx, const int64_t* ids, int64_t* next, void* stream);
+/* aigv_decode_step plus the log-probability of each raw token it emits: logprob[b] = log_softmax(logits.float())[next[b]] of the bf16
+ * lm-head logits (DEVICE fp32 [B]).  The lm-head GEMV computes the log-sum-exp in the same pass as its argmax (per-16-column partials in a
+ * context workspace, merged in a fixed order: a sequence's bits do not depend on its batch mates); next is aigv_decode_step's, bit for bit.
+ * Nothing is allocated here, so the call may be captured. */
+int aigv_decode_step_logprob(aigv_ctx* ctx, const int64_t* ids, int64_t* next, float* logprob, void* stream);
 /* The full next-token distribution of the rows the last aigv_llm_prefill / aigv_llm_extend / aigv_decode_step consumed: lm-head
  * logits of their final hidden states (kept in the context, in the order [score rows | logit rows]; a decode step keeps its
  * n_clips rows) as the bf16 values the reference upcasts with .float() (modeling_internlm2.py:1095-1096).
@@ -288,6 +295,14 @@ int aigv_op_im2col(const void* frames, int n_frames, int channels, int image_siz
                    void* stream);
 int aigv_op_lm_head_argmax(const void* h, int rows, int hidden, const void* W, int vocab, void* scratch_u64,
                            int64_t* idx, float* val, void* stream);
+/* aigv_op_lm_head_argmax plus the log-probability of the chosen column (the lm-head of aigv_decode_step_logprob): idx / val are
+ * aigv_op_lm_head_argmax's bits (first maximal bf16-rounded logit), logprob[r] = val[r] - logsumexp(bf16-rounded logits of row r) in fp32;
+ * val may be null.  rows 1..64, hidden a multiple of 128, h / W / scratch 16-byte aligned; scratch: DEVICE memory of
+ * aigv_op_lm_head_argmax_logprob_scratch_bytes(rows, vocab) bytes (scratch_bytes = its size; a smaller one is refused).  Arguments are
+ * checked on the host (AIGV_ERR_ARG) before anything is launched. */
+int aigv_op_lm_head_argmax_logprob(const void* h, int rows, int hidden, const void* W, int vocab, void* scratch, int64_t scratch_bytes,
+                                   int64_t* idx, float* val, float* logprob, void* stream);
+int64_t aigv_op_lm_head_argmax_logprob_scratch_bytes(int rows, int vocab);   /* -1 for arguments the op refuses */
 /* The log-softmax of aigv_out_row_logprob on caller-supplied bf16 logits [rows, ldo >= vocab]: out[r] = fp32 log_softmax(logits[r, :vocab])
  * [labels[r]], NaN where labels[r] is outside [0, vocab).  One workgroup per row; the bits of a row do not depend on `rows`. */
 int aigv_op_label_logprob(const void* logits_bf16, int rows, int vocab, int ldo, const int64_t* labels, float* out, void* stream);
