@@ -36,7 +36,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const GemmArgs p) {
 
   // ---- tile mapping -------------------------------------------------------------------------
   // rows: tile tm covers rows [tm * 128, ..) of the matrix, or - with a half-tile table (GemmArgs::row_tab, the per-sequence row plans
-  // of api.hip) - the table's half tm: `valid` rows from its base row
+  // of dispatch.hip) - the table's half tm: `valid` rows from its base row
   const int nbm = p.row_tab ? p.tab_halves : (p.M + BM - 1) / BM, nbn = p.N / BN;
   const int nwg = nbm * nbn;
   int wg;

@@ -18,7 +18,6 @@ namespace {
 #ifndef SKINNY_DEPTH2
 #define SKINNY_DEPTH2 8      // k-steps in flight of the two-slab one-row-tile forms (SwiGLU w1|w3, RoPE wqkv)
 #endif
-enum { SK_STORE = 0, SK_RESID = 1, SK_SWIGLU = 2, SK_GELU = 3, SK_ARGMAX = 4, SK_RELU = 5, SK_LS_RESID = 6, SK_ROPE_KV = 7, SK_ARGMAX_LSE = 8 };
 
 // SK_ARGMAX_LSE: SK_ARGMAX plus the log-sum-exp of every row (generate()'s per-token log-probabilities, modeling_internlm2.py:1095-1096 +
 // log_softmax).  The argmax key is SK_ARGMAX's, bit for bit.  Besides it, every 16-column slab of W writes the (max, sum of exp(x - max))

@@ -21,8 +21,6 @@
 
 namespace {
 
-enum { SK_RESID = 1, SK_SWIGLU = 2, SK_ROPE_KV = 7 };   // head.hip's numbering
-
 typedef int v8i_t __attribute__((ext_vector_type(8)));
 typedef int v4i_t __attribute__((ext_vector_type(4)));
 typedef __attribute__((ext_vector_type(2))) int i32x2;

@@ -39,7 +39,7 @@ struct GemmArgs {
   // fused body + tail-slice launch (aigv_launch_gemm256_fused): the table continues with fuse_tail_halves tail halves; fuse_body_wg is filled
   // in by the launcher
   int fuse_tail_halves, fuse_body_wg;
-  // per-launch tuning selectors (0 = the default; set from the context's / the process's knobs by the dispatcher in api.hip - the kernel files
+  // per-launch tuning selectors (0 = the default; set from the context's / the process's knobs by the dispatcher in dispatch.hip - the kernel files
   // hold no mutable state): order_sel 1 = row groups, 1 + g = groups of g column tiles (0: by weight size); variant_sel 1 + v = schedule
   // variant v of the 256 kernel (0: the shipped one)
   int order_sel, variant_sel;
@@ -142,7 +142,9 @@ hipError_t aigv_launch_rope(bf16_t* qkv, int ld, const int32_t* pos, const bf16_
 // token embedding + visual/motion scatter: slot[t] < 0 -> tok_emb[ids[t]]; < n_vis -> vis[slot]; else motion
 hipError_t aigv_launch_embed(const int64_t* ids, const int32_t* slot, const bf16_t* emb, const bf16_t* vis,
                              const bf16_t* motion, int n_vis, bf16_t* out, int tokens, int H, hipStream_t s);
-// skinny (R <= 64) weight-streaming GEMM; epi: 0 store(+bias) 1 residual 2 swiglu 3 gelu(+bias) 6 layer-scale+residual
+// skinny (R <= 64) weight-streaming GEMM (head.hip; e4m3 forms: head8.hip) and its epilogues; aigv_launch_skinny_gemm takes SK_STORE (+bias),
+// SK_RESID, SK_SWIGLU, SK_GELU (+bias) and SK_LS_RESID
+enum { SK_STORE = 0, SK_RESID = 1, SK_SWIGLU = 2, SK_GELU = 3, SK_ARGMAX = 4, SK_RELU = 5, SK_LS_RESID = 6, SK_ROPE_KV = 7, SK_ARGMAX_LSE = 8 };
 hipError_t aigv_launch_skinny_gemm(const bf16_t* x, int ldx, int R, const bf16_t* W, int ldw, int N, int K,
                                    const bf16_t* bias, const bf16_t* resid, int ldr, bf16_t* out, int ldo, int epi,
                                    hipStream_t s, const bf16_t* ls = nullptr, int p = 1);
@@ -210,7 +212,7 @@ hipError_t aigv_launch_frame_ingest(const uint8_t* hwc, int n_frames, int H, int
 hipError_t aigv_launch_frame_resize_ingest(const uint8_t* hwc, int n_frames, int in_h, int in_w, int out_h, int out_w,
                                            const float* mean, const float* stdv, uint8_t* tmp_u8, uint8_t* out_u8, bf16_t* out_nchw,
                                            hipStream_t s);
-// records a message for aigv_last_error(NULL) from translation units other than api.hip (thread-local, like every handle-less error)
+// records a message for aigv_last_error(NULL) from translation units other than context.hip (thread-local, like every handle-less error)
 void aigv_set_error(const char* msg);
 // a[i] += 1, b[i] += 1 for i < n (decode bookkeeping kept on the device: positions and visible KV lengths)
 hipError_t aigv_launch_advance(int32_t* a, int32_t* b, int n, hipStream_t s);

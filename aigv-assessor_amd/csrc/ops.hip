@@ -1,0 +1,308 @@
+// The context-free single-operator entry points of the C ABI (aigv_op_*: tests, benches and A/B scripts) and their argument checks.
+// Host-side C++ only.
+#include "ctx.h"
+
+using namespace aigv;
+
+extern "C" {
+
+// ---- single operators ----------------------------------------------------------------------------------------
+int aigv_op_gemm(const void* A, int lda, const void* W_, int ldw, void* C, int ldc, const void* bias, const void* ls,
+                 const void* resid, int ldr, const void* pos, int np, int M, int N, int K, int epi, void* stream) {
+  GemmArgs a = gemm_args((const bf16_t*)A, lda, (const bf16_t*)W_, ldw, (bf16_t*)C, ldc, M, N, K);
+  a.bias = (const bf16_t*)bias; a.ls = (const bf16_t*)ls; a.resid = (const bf16_t*)resid; a.ldr = ldr;
+  a.pos = (const bf16_t*)pos; a.np = np;
+  return run_gemm(nullptr, a, epi, (hipStream_t)stream);
+}
+
+// aigv_op_gemm with the rows divided into independent sequences (cu_host[0..n_seq], cu[0] = 0, cu[n_seq] = M): the dispatch the scoring
+// pass uses (struct RowPlan).  Test entry point: allocates the plan's table per call and synchronises the stream before freeing it.
+int aigv_op_gemm_rows(const void* A, int lda, const void* W_, int ldw, void* C, int ldc, const void* bias, const void* ls,
+                      const void* resid, int ldr, const int32_t* cu_host, int n_seq, int N, int K, int epi, void* stream) {
+  if (!cu_host || n_seq < 1 || cu_host[0] != 0) return fail(nullptr, AIGV_ERR_ARG, "aigv_op_gemm_rows: bad cu_seqlens");
+  for (int b = 0; b < n_seq; ++b)
+    if (cu_host[b + 1] <= cu_host[b]) return fail(nullptr, AIGV_ERR_ARG, "aigv_op_gemm_rows: empty sequence %d", b);
+  if (epi == EPI_PATCH) return fail(nullptr, AIGV_ERR_ARG, "aigv_op_gemm_rows: no patch epilogue");
+  const int M = cu_host[n_seq];
+  GemmArgs a = gemm_args((const bf16_t*)A, lda, (const bf16_t*)W_, ldw, (bf16_t*)C, ldc, M, N, K);
+  a.bias = (const bf16_t*)bias; a.ls = (const bf16_t*)ls; a.resid = (const bf16_t*)resid; a.ldr = ldr;
+  RowPlan rp;
+  rp.cap_halves = M / 128 + 2 * n_seq + 2;
+  HIPCHK(nullptr, hipMalloc((void**)&rp.d_tab, (size_t)2 * rp.cap_halves * sizeof(int32_t)));
+  int rc = build_row_plan(nullptr, rp, cu_host, n_seq, (hipStream_t)stream);
+  if (!rc) rc = run_gemm_rows(nullptr, a, epi, rp, (hipStream_t)stream);
+  hipStreamSynchronize((hipStream_t)stream);
+  hipFree(rp.d_tab);
+  return rc;
+}
+
+int aigv_op_gemm_splitk(const void* A, int lda, const void* W_, int ldw, void* C, int ldc, const void* bias, const void* ls,
+                        const void* resid, int ldr, int M, int N, int K, int epi, int k_slices, void* ws_f32, void* stream) {
+  GemmArgs a = gemm_args((const bf16_t*)A, lda, (const bf16_t*)W_, ldw, (bf16_t*)C, ldc, M, N, K);
+  a.bias = (const bf16_t*)bias; a.ls = (const bf16_t*)ls; a.resid = (const bf16_t*)resid; a.ldr = ldr;
+  if (const char* m = aigv_gemm_check(a, epi)) return fail(nullptr, AIGV_ERR_ARG, "%s", m);
+  hipError_t e = aigv_launch_gemm_splitk(a, epi, k_slices, (float*)ws_f32, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(nullptr, e == hipErrorInvalidValue ? AIGV_ERR_ARG : AIGV_ERR_HIP, "split-K gemm: %s", hipGetErrorString(e));
+  return 0;
+}
+
+int aigv_op_gemm_splitk256(const void* A, int lda, const void* W_, int ldw, void* C, int ldc, const void* bias, const void* ls,
+                           const void* resid, int ldr, int M, int N, int K, int epi, int k_slices, void* ws_f32, void* stream) {
+  GemmArgs a = gemm_args((const bf16_t*)A, lda, (const bf16_t*)W_, ldw, (bf16_t*)C, ldc, M, N, K);
+  a.bias = (const bf16_t*)bias; a.ls = (const bf16_t*)ls; a.resid = (const bf16_t*)resid; a.ldr = ldr;
+  if (const char* m = aigv_gemm_check(a, epi)) return fail(nullptr, AIGV_ERR_ARG, "%s", m);
+  hipError_t e = aigv_launch_gemm_splitk(a, epi, k_slices, (float*)ws_f32, (hipStream_t)stream, true);
+  if (e != hipSuccess) return fail(nullptr, e == hipErrorInvalidValue ? AIGV_ERR_ARG : AIGV_ERR_HIP, "split-K gemm (256 tile): %s", hipGetErrorString(e));
+  return 0;
+}
+
+int aigv_op_quant_fp8_rows(const void* x_bf16, int ldx, int rows, int K, void* q_e4m3, int ldq, float* row_scale, void* stream) {
+  hipError_t e = aigv_launch_quant_fp8_rows((const bf16_t*)x_bf16, ldx, rows, K, (uint8_t*)q_e4m3, ldq, row_scale, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(nullptr, e == hipErrorInvalidValue ? AIGV_ERR_ARG : AIGV_ERR_HIP, "fp8 row quantisation (rows=%d K=%d): %s", rows, K, hipGetErrorString(e));
+  return 0;
+}
+
+int aigv_op_gemm_fp8(const void* A_e4m3, int lda, const void* W_e4m3, int ldw, void* C, int ldc, const float* row_scale,
+                     const float* col_scale, const void* bias, const void* ls, const void* resid, int ldr, int M, int N, int K, int epi,
+                     int k_slices, void* ws_f32, void* stream) {
+  GemmArgs a{};
+  a.A = (const bf16_t*)A_e4m3; a.lda = lda; a.W = (const bf16_t*)W_e4m3; a.ldw = ldw; a.C = (bf16_t*)C; a.ldc = ldc;
+  a.M = M; a.N = N; a.K = K; a.bias = (const bf16_t*)bias; a.row_scale = row_scale; a.col_scale = col_scale;
+  a.ls = (const bf16_t*)ls; a.resid = (const bf16_t*)resid; a.ldr = ldr;
+  const int n_out = epi == EPI_SWIGLU ? N / 2 : N;
+  if (ldc < n_out || (ldc % 8) || lda < K || ldw < K)
+    return fail(nullptr, AIGV_ERR_ARG, "aigv_op_gemm_fp8: bad leading dimension (M=%d N=%d K=%d)", M, N, K);
+  hipError_t e = k_slices > 1 ? aigv_launch_gemm_splitk_fp8(a, epi, k_slices, (float*)ws_f32, (hipStream_t)stream)
+                              : aigv_launch_gemm256_fp8(a, epi, (hipStream_t)stream);
+  if (e != hipSuccess)
+    return fail(nullptr, e == hipErrorInvalidValue ? AIGV_ERR_ARG : AIGV_ERR_HIP,
+                "fp8 gemm (M=%d N=%d K=%d epi=%d; needs N %% 256 == 0, K %% 128 == 0, 16-byte row strides, both scale vectors, epi in "
+                "{store, gelu, ls_resid, resid, swiglu}): %s", M, N, K, epi, hipGetErrorString(e));
+  return 0;
+}
+
+int aigv_op_skinny_gemm(const void* x, int ldx, int R, const void* W_, int ldw, int N, int K, const void* bias,
+                        const void* resid, int ldr, void* out, int ldo, int epi, void* stream) {
+  return run_skinny(nullptr, (const bf16_t*)x, ldx, R, (const bf16_t*)W_, ldw, N, K, (const bf16_t*)bias,
+                    (const bf16_t*)resid, ldr, (bf16_t*)out, ldo, epi, (hipStream_t)stream, g_tune[AIGV_TUNE_SKINNY_P] ? g_tune[AIGV_TUNE_SKINNY_P] : 1);
+}
+
+int aigv_op_skinny_gemm_fp8(const void* x, int ldx, int R, const void* W_e4m3, int ldw, const float* w_scale, int N, int K, const void* resid,
+                            int ldr, void* out, int ldo, int epi, const void* norm_w, float eps, int p, void* stream) {
+  if (epi != SK_RESID && epi != SK_SWIGLU) return fail(nullptr, AIGV_ERR_ARG, "aigv_op_skinny_gemm_fp8: epi must be 1 (residual) or 2 (swiglu)");
+  hipError_t e = aigv_launch_skinny_fp8((const bf16_t*)x, ldx, R, (const uint8_t*)W_e4m3, ldw, w_scale, N, K, (const bf16_t*)resid, ldr, (bf16_t*)out, ldo,
+                                        epi, nullptr, (const bf16_t*)norm_w, eps, p, (hipStream_t)stream);
+  if (e != hipSuccess)
+    return fail(nullptr, e == hipErrorInvalidValue ? AIGV_ERR_ARG : AIGV_ERR_HIP, "fp8 skinny gemm (R=%d N=%d K=%d epi=%d p=%d): %s", R, N, K, epi, p, hipGetErrorString(e));
+  return 0;
+}
+
+int aigv_op_layernorm(const void* x, int ldx, const void* w, const void* b, void* y, int ldy, int rows, int H, float eps,
+                      void* stream) {
+  HIPCHK(nullptr, aigv_launch_layernorm((const bf16_t*)x, ldx, (const bf16_t*)w, (const bf16_t*)b, (bf16_t*)y, ldy, rows, H,
+                                        eps, (hipStream_t)stream));
+  return 0;
+}
+
+int aigv_op_rmsnorm(const void* x, int ldx, const void* w, void* y, int ldy, int rows, int H, float eps,
+                    const int32_t* row_idx, void* stream) {
+  HIPCHK(nullptr, aigv_launch_rmsnorm((const bf16_t*)x, ldx, (const bf16_t*)w, (bf16_t*)y, ldy, rows, H, eps, row_idx,
+                                      (hipStream_t)stream));
+  return 0;
+}
+
+int aigv_op_rope(void* qkv, int ld, const int32_t* pos, const void* cos, const void* sin, int tokens, int n_rot, int slots,
+                 int n_groups, int head_dim, void* stream) {
+  HIPCHK(nullptr, aigv_launch_rope((bf16_t*)qkv, ld, pos, (const bf16_t*)cos, (const bf16_t*)sin, tokens, n_rot, slots,
+                                   n_groups, head_dim, (hipStream_t)stream));
+  return 0;
+}
+
+int aigv_op_attention(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo,
+                      const int32_t* cu, int n_seq, int max_len, int n_heads, int n_kv_heads, int q_group_stride,
+                      int kv_head_stride, int head_dim, int causal, float post_div, float q_prescale, void* stream) {
+  return aigv_op_attention_rope(q, ldq, k, ldk, v, ldv, o, ldo, cu, n_seq, max_len, n_heads, n_kv_heads, q_group_stride, kv_head_stride, head_dim,
+                                causal, post_div, q_prescale, nullptr, nullptr, nullptr, stream);   // (no rotation: the same AttnArgs without rope_*)
+}
+
+int aigv_op_attention_rope(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo,
+                           const int32_t* cu, int n_seq, int max_len, int n_heads, int n_kv_heads, int q_group_stride,
+                           int kv_head_stride, int head_dim, int causal, float post_div, float q_prescale, const int32_t* pos,
+                           const void* cos, const void* sin, void* stream) {
+  AttnArgs a{};
+  a.q = (const bf16_t*)q; a.ldq = ldq; a.k = (const bf16_t*)k; a.ldk = ldk; a.v = (const bf16_t*)v; a.ldv = ldv;
+  a.o = (bf16_t*)o; a.ldo = ldo; a.cu = cu; a.n_seq = n_seq; a.max_len = max_len; a.n_heads = n_heads;
+  a.n_kv_heads = n_kv_heads; a.q_group_stride = q_group_stride; a.kv_head_stride = kv_head_stride;
+  a.causal = causal & 1; a.uniform_len = (causal >> 1) & 1; a.post_div = post_div; a.q_prescale = q_prescale;
+  a.round_scores = (causal >> 2) & 1; a.lead_key = (causal >> 3) & 1; a.waves = g_tune[AIGV_TUNE_ATTN_WAVES];
+  a.rope_pos = pos; a.rope_cos = (const bf16_t*)cos; a.rope_sin = (const bf16_t*)sin;
+  if (const char* m = aigv_attn_check(a, head_dim)) return fail(nullptr, AIGV_ERR_ARG, "%s", m);
+  HIPCHK(nullptr, aigv_launch_attention(a, head_dim, (hipStream_t)stream));
+  return 0;
+}
+
+int aigv_op_pixel_shuffle(const void* vit_out, int grid, int vit_hidden, void* out, int n_frames, void* stream) {
+  HIPCHK(nullptr, aigv_launch_pixel_shuffle((const bf16_t*)vit_out, grid, vit_hidden, (bf16_t*)out, n_frames, (hipStream_t)stream));
+  return 0;
+}
+
+int aigv_op_im2col(const void* frames, int n_frames, int channels, int image_size, int patch, int kp, void* out,
+                   void* stream) {
+  HIPCHK(nullptr, aigv_launch_im2col((const bf16_t*)frames, n_frames, channels, image_size, patch, kp, (bf16_t*)out,
+                                     (hipStream_t)stream));
+  return 0;
+}
+
+int aigv_op_lm_head_argmax(const void* h, int rows, int hidden, const void* W_, int vocab, void* scratch_u64, int64_t* idx,
+                           float* val, void* stream) {
+  HIPCHK(nullptr, aigv_launch_lm_head_argmax((const bf16_t*)h, rows, hidden, (const bf16_t*)W_, vocab,
+                                             (unsigned long long*)scratch_u64, idx, val, (hipStream_t)stream));
+  return 0;
+}
+
+int64_t aigv_op_lm_head_argmax_logprob_scratch_bytes(int rows, int vocab) {
+  if (rows < 1 || rows > 64 || vocab < 1) return -1;
+  return (int64_t)(64 * sizeof(unsigned long long) + (size_t)rows * aigv_lm_head_lse_slots(vocab) * sizeof(float2));
+}
+
+int aigv_op_lm_head_argmax_logprob(const void* h, int rows, int hidden, const void* W_, int vocab, void* scratch, int64_t scratch_bytes,
+                                   int64_t* idx, float* val, float* logprob, void* stream) {
+  const char* op = "aigv_op_lm_head_argmax_logprob";
+  if (!h || !W_ || !scratch || !idx || !logprob) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+  if (rows < 1 || rows > 64) return fail(nullptr, AIGV_ERR_ARG, "%s: rows = %d outside 1..64", op, rows);
+  if (hidden < 128 || hidden % 128) return fail(nullptr, AIGV_ERR_ARG, "%s: hidden = %d is not a positive multiple of 128", op, hidden);
+  if (vocab < 1) return fail(nullptr, AIGV_ERR_ARG, "%s: vocab = %d must be positive", op, vocab);
+  if (((uintptr_t)h & 15) || ((uintptr_t)W_ & 15) || ((uintptr_t)scratch & 15)) return fail(nullptr, AIGV_ERR_ARG, "%s: h, W and scratch must be 16-byte aligned", op);
+  const int64_t need = aigv_op_lm_head_argmax_logprob_scratch_bytes(rows, vocab);
+  if (scratch_bytes < need) return fail(nullptr, AIGV_ERR_ARG, "%s: scratch of %lld bytes, needs %lld", op, (long long)scratch_bytes, (long long)need);
+  unsigned long long* packed = (unsigned long long*)scratch;
+  float2* part = (float2*)((char*)scratch + 64 * sizeof(unsigned long long));
+  HIPCHK(nullptr, aigv_launch_lm_head_argmax_logprob((const bf16_t*)h, rows, hidden, (const bf16_t*)W_, vocab, packed, part, idx, val, logprob,
+                                                     (hipStream_t)stream));
+  return 0;
+}
+
+int aigv_op_label_logprob(const void* logits_bf16, int rows, int vocab, int ldo, const int64_t* labels, float* out, void* stream) {
+  if (rows < 0 || vocab < 1 || ldo < vocab || (rows > 0 && (!logits_bf16 || !labels || !out)))
+    return fail(nullptr, AIGV_ERR_ARG, "aigv_op_label_logprob: bad argument (rows %d, vocab %d, ldo %d)", rows, vocab, ldo);
+  HIPCHK(nullptr, aigv_launch_label_logprob((const bf16_t*)logits_bf16, rows, vocab, ldo, labels, out, (hipStream_t)stream));
+  return 0;
+}
+
+// ---- the decode step's kernels, one by one (test entry points): every argument is checked here, before any HIP call ----
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+int64_t aigv_op_attention_decode_ws_floats(int n_seq, int n_kv, int g, int cap) {
+  if (n_seq < 1 || n_kv < 1 || g < 1 || g > 8 || cap < 1 || cap > AIGV_MAX_KV_CAPACITY) return -1;
+  return (int64_t)aigv_attention_decode_ws_floats(n_seq, n_kv, g, cap);
+}
+
+int aigv_op_attention_decode(const void* q, int ldq, int q_group_stride, const void* kc, const void* vc, const int32_t* kv_lens, int cap,
+                             void* o, int ldo, int n_seq, int n_kv, int g, int head_dim, float post_div, int max_kv_len, float* ws,
+                             int64_t ws_floats, void* stream) {
+  const char* op = "aigv_op_attention_decode";
+  if (!q || !kc || !vc || !kv_lens || !o || !ws) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+  if (head_dim != 128) return fail(nullptr, AIGV_ERR_ARG, "%s: head_dim must be 128, got %d", op, head_dim);
+  if (g < 1 || g > 8) return fail(nullptr, AIGV_ERR_ARG, "%s: g = %d query heads per KV head (1..8)", op, g);
+  if (n_seq < 1 || n_kv < 1) return fail(nullptr, AIGV_ERR_ARG, "%s: n_seq %d, n_kv %d must be positive", op, n_seq, n_kv);
+  if (cap < 1 || cap > AIGV_MAX_KV_CAPACITY || max_kv_len < 1 || max_kv_len > cap)
+    return fail(nullptr, AIGV_ERR_ARG, "%s: needs 1 <= max_kv_len (%d) <= cap (%d) <= %d", op, max_kv_len, cap, AIGV_MAX_KV_CAPACITY);
+  if (q_group_stride < g * head_dim || ldq < (n_kv - 1) * q_group_stride + g * head_dim || ldo < n_kv * g * head_dim)
+    return fail(nullptr, AIGV_ERR_ARG, "%s: strides too small (ldq %d, q_group_stride %d, ldo %d)", op, ldq, q_group_stride, ldo);
+  if (!aligned16(kc) || !aligned16(vc)) return fail(nullptr, AIGV_ERR_ARG, "%s: the caches must be 16-byte aligned", op);
+  const int64_t need = aigv_op_attention_decode_ws_floats(n_seq, n_kv, g, cap);
+  if (ws_floats < need) return fail(nullptr, AIGV_ERR_ARG, "%s: workspace of %lld floats, needs %lld", op, (long long)ws_floats, (long long)need);
+  HIPCHK(nullptr, aigv_launch_attention_decode((const bf16_t*)q, ldq, q_group_stride, (const bf16_t*)kc, (const bf16_t*)vc, kv_lens, cap, (bf16_t*)o,
+                                               ldo, n_seq, n_kv, g, head_dim, post_div, max_kv_len, ws, (hipStream_t)stream));
+  return 0;
+}
+
+// shared checks of the RoPE / KV-append GEMVs (bf16 and e4m3 forms)
+static int check_rope_kv(const char* op, const void* x, int ldx, int R, const void* W, int ldw, int N, int K, const void* qkv, int ldo,
+                         const int32_t* pos, const int32_t* seq, const void* cos, const void* sin, const void* kc, const void* vc, int g,
+                         int n_kv, int cap, int p) {
+  if (!x || !W || !qkv || !pos || !seq || !cos || !sin || !kc || !vc) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+  if (g < 1 || g > 8 || n_kv < 1 || N != n_kv * (g + 2) * 128)
+    return fail(nullptr, AIGV_ERR_ARG, "%s: N = %d is not n_kv (%d) x (g (%d) + 2) x 128 with g in 1..8", op, N, n_kv, g);
+  if (p != 1 && p != 2 && p != 4) return fail(nullptr, AIGV_ERR_ARG, "%s: p must be 1, 2 or 4, got %d", op, p);
+  if (R < 1 || R > (p == 1 ? 64 : 16 / p)) return fail(nullptr, AIGV_ERR_ARG, "%s: R = %d rows outside 1..%d for p = %d", op, R, p == 1 ? 64 : 16 / p, p);
+  if (K < 128 * p || K % (128 * p)) return fail(nullptr, AIGV_ERR_ARG, "%s: K = %d is not a multiple of %d", op, K, 128 * p);
+  if (cap < 1 || cap > AIGV_MAX_KV_CAPACITY) return fail(nullptr, AIGV_ERR_ARG, "%s: cap = %d outside 1..%d", op, cap, AIGV_MAX_KV_CAPACITY);
+  if (ldx < K || ldx % 8 || ldo < N || ldo % 4) return fail(nullptr, AIGV_ERR_ARG, "%s: bad leading dimension (ldx %d, ldo %d)", op, ldx, ldo);
+  if (!aligned16(x) || !aligned16(W) || !aligned16(kc) || !aligned16(vc) || ((uintptr_t)qkv & 7) || ((uintptr_t)cos & 7) || ((uintptr_t)sin & 7))
+    return fail(nullptr, AIGV_ERR_ARG, "%s: misaligned operand", op);
+  return 0;
+}
+
+int aigv_op_skinny_rope_kv(const void* x, int ldx, int R, const void* W, int ldw, int N, int K, void* qkv, int ldo, const int32_t* pos,
+                           const int32_t* seq, const void* cos, const void* sin, void* kc, void* vc, int g, int n_kv, int cap,
+                           const void* norm_w, float eps, int p, void* stream) {
+  const char* op = "aigv_op_skinny_rope_kv";
+  TRY(check_rope_kv(op, x, ldx, R, W, ldw, N, K, qkv, ldo, pos, seq, cos, sin, kc, vc, g, n_kv, cap, p));
+  if (ldw < K || ldw % 8) return fail(nullptr, AIGV_ERR_ARG, "%s: bad ldw %d", op, ldw);
+  if (norm_w && (R > 4 || !aigv_skinny_norm_fusable(K) || !aligned16(norm_w)))
+    return fail(nullptr, AIGV_ERR_ARG, "%s: the fused RMSNorm takes R <= 4 rows (got %d) and K = 4096 or 6144 (got %d)", op, R, K);
+  HIPCHK(nullptr, aigv_launch_skinny_rope_kv((const bf16_t*)x, ldx, R, (const bf16_t*)W, ldw, N, K, (bf16_t*)qkv, ldo, pos, seq, (const bf16_t*)cos,
+                                             (const bf16_t*)sin, (bf16_t*)kc, (bf16_t*)vc, g, n_kv, cap, 128, (hipStream_t)stream,
+                                             (const bf16_t*)norm_w, eps, p));
+  return 0;
+}
+
+int aigv_op_skinny_swiglu_normed(const void* x, int ldx, int R, const void* W, int ldw, int N, int K, void* out, int ldo,
+                                 const void* norm_w, float eps, int p, void* stream) {
+  const char* op = "aigv_op_skinny_swiglu_normed";
+  if (!x || !W || !out || !norm_w) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand (norm_w is required)", op);
+  if (R < 1 || R > 4 || !aigv_skinny_norm_fusable(K))
+    return fail(nullptr, AIGV_ERR_ARG, "%s: takes 1..4 rows (got %d) and K = 4096 or 6144 (got %d)", op, R, K);
+  if (p != 1 && p != 2 && p != 4) return fail(nullptr, AIGV_ERR_ARG, "%s: p must be 1, 2 or 4, got %d", op, p);
+  if (N < 32 || N % 32) return fail(nullptr, AIGV_ERR_ARG, "%s: N = %d is not a multiple of 32", op, N);
+  if (ldx < K || ldx % 8 || ldw < K || ldw % 8 || ldo < N / 2 || ldo % 4)
+    return fail(nullptr, AIGV_ERR_ARG, "%s: bad leading dimension (ldx %d, ldw %d, ldo %d)", op, ldx, ldw, ldo);
+  if (!aligned16(x) || !aligned16(W) || !aligned16(norm_w) || ((uintptr_t)out & 7)) return fail(nullptr, AIGV_ERR_ARG, "%s: misaligned operand", op);
+  HIPCHK(nullptr, aigv_launch_skinny_swiglu_normed((const bf16_t*)x, ldx, R, (const bf16_t*)W, ldw, N, K, (bf16_t*)out, ldo, (const bf16_t*)norm_w, eps,
+                                                   (hipStream_t)stream, p));
+  return 0;
+}
+
+int aigv_op_skinny_rope_kv_fp8(const void* x, int ldx, int R, const void* W_e4m3, int ldw, const float* w_scale, int N, int K, void* qkv,
+                               int ldo, const int32_t* pos, const int32_t* seq, const void* cos, const void* sin, void* kc, void* vc, int g,
+                               int n_kv, int cap, const void* norm_w, float eps, int p, void* stream) {
+  const char* op = "aigv_op_skinny_rope_kv_fp8";
+  TRY(check_rope_kv(op, x, ldx, R, W_e4m3, ldw, N, K, qkv, ldo, pos, seq, cos, sin, kc, vc, g, n_kv, cap, p));
+  if (!w_scale || ((uintptr_t)w_scale & 15)) return fail(nullptr, AIGV_ERR_ARG, "%s: w_scale missing or misaligned", op);
+  if (ldw < K || ldw % 16) return fail(nullptr, AIGV_ERR_ARG, "%s: bad ldw %d (bytes, a multiple of 16)", op, ldw);
+  if (!norm_w || R > 4 || !aigv_skinny_fp8_supported(K, true) || !aligned16(norm_w))
+    return fail(nullptr, AIGV_ERR_ARG, "%s: needs norm_w, R <= 4 rows (got %d) and K = 4096 or 6144 (got %d)", op, R, K);
+  const AigvRopeKv rk{pos, seq, (const bf16_t*)cos, (const bf16_t*)sin, (bf16_t*)kc, (bf16_t*)vc, g, n_kv, cap};
+  hipError_t e = aigv_launch_skinny_fp8((const bf16_t*)x, ldx, R, (const uint8_t*)W_e4m3, ldw, w_scale, N, K, nullptr, 0, (bf16_t*)qkv, ldo, SK_ROPE_KV, &rk,
+                                        (const bf16_t*)norm_w, eps, p, (hipStream_t)stream);
+  if (e != hipSuccess)
+    return fail(nullptr, e == hipErrorInvalidValue ? AIGV_ERR_ARG : AIGV_ERR_HIP, "%s (R=%d N=%d K=%d p=%d): %s", op, R, N, K, p, hipGetErrorString(e));
+  return 0;
+}
+
+int aigv_op_frame_ingest(const void* hwc_u8, int n_frames, int height, int width, const float* mean, const float* stdv,
+                         void* out_nchw, void* stream) {
+  HIPCHK(nullptr, aigv_launch_frame_ingest((const uint8_t*)hwc_u8, n_frames, height, width, mean, stdv, (bf16_t*)out_nchw,
+                                           (hipStream_t)stream));
+  return 0;
+}
+
+int aigv_op_frame_resize_ingest(const void* hwc_u8, int n_frames, int in_h, int in_w, int out_h, int out_w, const float* mean,
+                                const float* stdv, void* tmp_u8, void* out_u8_hwc, void* out_nchw, void* stream) {
+  if (!hwc_u8 || !tmp_u8 || (!out_u8_hwc && !out_nchw) || n_frames < 0 || in_h <= 0 || in_w <= 0 || out_h <= 0 || out_w <= 0 ||
+      (out_nchw && (!mean || !stdv)))
+    return fail(nullptr, AIGV_ERR_ARG, "aigv_op_frame_resize_ingest: bad argument (frames %d, %dx%d -> %dx%d)", n_frames, in_h, in_w, out_h, out_w);
+  if (in_h > 16384 || in_w > 16384 || out_h > 16384 || out_w > 16384)
+    return fail(nullptr, AIGV_ERR_ARG, "aigv_op_frame_resize_ingest: sizes above 16384 are not supported");
+  // Pillow (12.2, observed against the live package: tests/manual/fuzz_resize.py) runs the VERTICAL pass first for frames more than 100 times taller than wide
+  // that shrink vertically - the intermediate uint8 image, and so the result, differs from the horizontal-first order implemented here.  Not a video
+  // geometry: refused rather than answered differently from Pillow.
+  if (in_w != out_w && in_h != out_h && in_h > out_h && (long)in_h > 100L * in_w)
+    return fail(nullptr, AIGV_ERR_ARG, "aigv_op_frame_resize_ingest: %dx%d frames (more than 100 times taller than wide) are not supported: Pillow orders its passes differently there", in_h, in_w);
+  HIPCHK(nullptr, aigv_launch_frame_resize_ingest((const uint8_t*)hwc_u8, n_frames, in_h, in_w, out_h, out_w, mean, stdv,
+                                                  (uint8_t*)tmp_u8, (uint8_t*)out_u8_hwc, (bf16_t*)out_nchw, (hipStream_t)stream));
+  return 0;
+}
+
+}  // extern "C"

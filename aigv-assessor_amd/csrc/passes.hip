@@ -1,0 +1,738 @@
+// The passes of the C ABI (include/aigv_amd.h) over the gfx950 kernels: InternViT, the projectors, InternLM2 prefill / extend with the
+// score and lm heads, the KV-cache operations and the decode step.  Host-side C++ only; every device op is one of the hand-written
+// kernels, every GEMM goes through the dispatcher (dispatch.hip).
+#include <cmath>
+
+#include "ctx.h"
+
+using namespace aigv;
+
+extern "C" {
+
+// ---- InternViT ---------------------------------------------------------------------------------------------
+static int vit_norm(aigv_ctx* c, const bf16_t* x, const bf16_t* w, const bf16_t* b, bf16_t* y, int rows, hipStream_t s) {
+  const aigv_config& k = c->cfg;
+  if (k.vit_norm_rms) HIPCHK(c, aigv_launch_rmsnorm(x, k.vit_hidden, w, y, k.vit_hidden, rows, k.vit_hidden, k.vit_eps, nullptr, s));
+  else HIPCHK(c, aigv_launch_layernorm(x, k.vit_hidden, w, b, y, k.vit_hidden, rows, k.vit_hidden, k.vit_eps, s));
+  return 0;
+}
+
+int aigv_vit_forward(aigv_ctx* c, const void* frames, int n_frames, void* out_tokens, void* stream) {
+  if (!c || !frames || !out_tokens) return fail(c, AIGV_ERR_ARG, "aigv_vit_forward: null argument");
+  if (!c->finalized) return fail(c, AIGV_ERR_STATE, "aigv_vit_forward: call aigv_finalize_weights first");
+  const aigv_config& k = c->cfg;
+  if (n_frames <= 0 || n_frames > k.max_frames) return fail(c, AIGV_ERR_ARG, "n_frames %d outside 1..%d", n_frames, k.max_frames);
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  GemmClassScope gcls(c, AIGV_PROF_GEMM_VIT);
+  SplitkVitScope svs(c);
+  const int Hv = k.vit_hidden, Iv = k.vit_inter;
+  int n_layers = k.vit_layers;
+  if (k.select_layer != -1) n_layers = k.select_layer < 0 ? k.vit_layers + 1 + k.select_layer : k.select_layer;
+  if (n_layers < 0 || n_layers > k.vit_layers) return fail(c, AIGV_ERR_ARG, "select_layer %d out of range", k.select_layer);
+  const size_t frame_elems = (size_t)k.num_channels * k.image_size * k.image_size;
+  for (int f0 = 0; f0 < n_frames; f0 += k.vit_chunk) {
+    const int F = std::min(k.vit_chunk, n_frames - f0);
+    const int rows = F * c->S;
+    const bf16_t* fr = (const bf16_t*)frames + (size_t)f0 * frame_elems;
+    {   // every frame is a sequence of S rows; the table is written by every pass (build_row_plan)
+      std::vector<int32_t> cu(F + 1);
+      for (int i = 0; i <= F; ++i) cu[i] = i * c->S;
+      TRY(build_row_plan(c, c->rp_vit, cu.data(), F, s));
+    }
+    const RowPlan& rp = c->rp_vit;
+    // patch embed: im2col + GEMM with the bias / position / row-remap epilogue (modeling_intern_vit.py:95-107)
+    HIPCHK(c, aigv_launch_im2col(fr, F, k.num_channels, k.image_size, k.patch_size, c->Kp, c->v_col, s));
+    HIPCHK(c, aigv_launch_cls_rows(c->cls_pos, c->v_x, F, c->S, Hv, s));
+    {
+      GemmArgs a = gemm_args(c->v_col, c->Kp, c->patch_w, c->Kp, c->v_x, Hv, F * c->np, Hv, c->Kp);
+      a.bias = c->patch_b; a.pos = c->pos; a.np = c->np;
+      // (every row in full K on ONE tile kernel chosen by the shape of a frame: batch-invariant)
+      TRY(launch_one(c, a, EPI_PATCH, Hv % 256 == 0 && resolved_gemm_mode(c) != 1, s));
+    }
+    for (int li = 0; li < n_layers; ++li) {
+      const VitLayer& L = c->vit[li];
+      TRY(vit_norm(c, c->v_x, L.n1w, L.n1b, c->v_t, rows, s));
+      {
+        GemmArgs a = gemm_args(c->v_t, Hv, L.qkv_w, Hv, c->v_qkv, 3 * Hv, rows, 3 * Hv, Hv);
+        a.bias = L.qkv_b;
+        TRY(run_gemm_rows(c, a, EPI_STORE, rp, s));
+      }
+      if (k.vit_qk_norm) {  // full-width RMSNorm of q and k, in place (modeling_intern_vit.py:148-151)
+        HIPCHK(c, aigv_launch_rmsnorm(c->v_qkv, 3 * Hv, L.qn, c->v_qkv, 3 * Hv, rows, Hv, k.vit_eps, nullptr, s));
+        HIPCHK(c, aigv_launch_rmsnorm(c->v_qkv + Hv, 3 * Hv, L.kn, c->v_qkv + Hv, 3 * Hv, rows, Hv, k.vit_eps, nullptr, s));
+      }
+      {
+        AttnArgs a{};
+        a.q = c->v_qkv; a.k = c->v_qkv + Hv; a.v = c->v_qkv + 2 * Hv;
+        a.ldq = a.ldk = a.ldv = 3 * Hv;
+        a.o = c->v_ao; a.ldo = Hv;
+        a.cu = c->v_cu; a.n_seq = F; a.max_len = c->S;
+        a.n_heads = a.n_kv_heads = k.vit_heads;
+        a.q_group_stride = a.kv_head_stride = c->vit_head_dim;
+        a.causal = 0; a.post_div = 1.0f; a.q_prescale = 1.0f / sqrtf((float)c->vit_head_dim);
+        a.round_scores = c->attn_round_scores; a.waves = tune_knob(c, AIGV_TUNE_ATTN_WAVES); a.lead_key = tune_knob(c, AIGV_TUNE_ATTN_LEAD_KEY);
+        a.uniform_len = 1;
+        if (const char* m = aigv_attn_check(a, c->vit_head_dim)) return fail(c, AIGV_ERR_ARG, "%s", m);
+        ProfScope ps(c, AIGV_PROF_ATTN_VIT, 4.0 * F * (double)c->S * c->S * Hv, 2.0 * 4 * rows * (double)Hv, s);
+        HIPCHK(c, aigv_launch_attention(a, c->vit_head_dim, s));
+      }
+      {
+        GemmArgs a = gemm_args(c->v_ao, Hv, L.proj_w, Hv, c->v_x, Hv, rows, Hv, Hv);
+        a.bias = L.proj_b; a.ls = L.ls1; a.resid = c->v_x; a.ldr = Hv;
+        TRY(run_gemm_rows(c, a, EPI_LS_RESID, rp, s));
+      }
+      TRY(vit_norm(c, c->v_x, L.n2w, L.n2b, c->v_t, rows, s));
+      {
+        GemmArgs a = gemm_args(c->v_t, Hv, L.fc1_w, Hv, c->v_h, Iv, rows, Iv, Hv);
+        a.bias = L.fc1_b;
+        TRY(run_gemm_rows(c, a, EPI_GELU, rp, s));
+      }
+      {
+        GemmArgs a = gemm_args(c->v_h, Iv, L.fc2_w, Iv, c->v_x, Hv, rows, Hv, Iv);
+        a.bias = L.fc2_b; a.ls = L.ls2; a.resid = c->v_x; a.ldr = Hv;
+        TRY(run_gemm_rows(c, a, EPI_LS_RESID, rp, s));
+      }
+    }
+    HIPCHK(c, aigv_launch_pixel_shuffle(c->v_x, c->grid, Hv, (bf16_t*)out_tokens + (size_t)f0 * c->ntok * c->proj_in, F, s));
+  }
+  return 0;
+}
+
+int aigv_project(aigv_ctx* c, const void* tokens, int rows, void* out, void* stream) {
+  if (!c || !tokens || !out) return fail(c, AIGV_ERR_ARG, "aigv_project: null argument");
+  if (!c->finalized) return fail(c, AIGV_ERR_STATE, "aigv_project: call aigv_finalize_weights first");
+  if (rows <= 0) return fail(c, AIGV_ERR_ARG, "aigv_project: rows must be positive");
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  const aigv_config& k = c->cfg;
+  const int H = k.llm_hidden, Pin = c->proj_in;
+  GemmClassScope gcls(c, AIGV_PROF_GEMM_VIT);
+  const int chunk = k.vit_chunk * c->ntok;
+  for (int r0 = 0; r0 < rows; r0 += chunk) {
+    const int R = std::min(chunk, rows - r0);
+    const bf16_t* x = (const bf16_t*)tokens + (size_t)r0 * Pin;
+    HIPCHK(c, aigv_launch_layernorm(x, Pin, c->p_ln_w[0], c->p_ln_b[0], c->p_t, Pin, R, Pin, 1e-5f, s));
+    {
+      GemmArgs a = gemm_args(c->p_t, Pin, c->p_w1[0], Pin, c->p_mid, H, R, H, Pin);
+      a.bias = c->p_b1[0];
+      TRY(run_gemm_full(c, a, EPI_GELU, s));
+    }
+    {
+      GemmArgs a = gemm_args(c->p_mid, H, c->p_w2[0], H, (bf16_t*)out + (size_t)r0 * H, H, R, H, H);
+      a.bias = c->p_b2[0];
+      TRY(run_gemm_full(c, a, EPI_STORE, s));
+    }
+  }
+  return 0;
+}
+
+int aigv_motion_project(aigv_ctx* c, const void* motion_feature, int n_clips, void* out, void* stream) {
+  if (!c || !motion_feature || !out) return fail(c, AIGV_ERR_ARG, "aigv_motion_project: null argument");
+  if (!c->finalized) return fail(c, AIGV_ERR_STATE, "aigv_motion_project: call aigv_finalize_weights first");
+  if (n_clips <= 0 || n_clips > c->cfg.max_seqs) return fail(c, AIGV_ERR_ARG, "n_clips %d outside 1..%d", n_clips, c->cfg.max_seqs);
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  const aigv_config& k = c->cfg;
+  const int H = k.llm_hidden, Md = k.motion_dim;
+  // scratch: p_t (>= ntok*proj_in elements) holds the normalised feature, p_mid the hidden layer
+  if ((size_t)n_clips * Md > (size_t)k.vit_chunk * c->ntok * c->proj_in || n_clips > k.vit_chunk * c->ntok)
+    return fail(c, AIGV_ERR_STATE, "motion batch does not fit the projector workspace");
+  HIPCHK(c, aigv_launch_layernorm((const bf16_t*)motion_feature, Md, c->p_ln_w[1], c->p_ln_b[1], c->p_t, Md, n_clips, Md, 1e-5f, s));
+  for (int r0 = 0; r0 < n_clips; r0 += 64) {
+    const int R = std::min(64, n_clips - r0);
+    TRY(run_skinny(c, c->p_t + (size_t)r0 * Md, Md, R, c->p_w1[1], Md, H, Md, c->p_b1[1], nullptr, 0,
+                   c->p_mid + (size_t)r0 * H, H, SK_GELU, s, 0));
+    TRY(run_skinny(c, c->p_mid + (size_t)r0 * H, H, R, c->p_w2[1], H, H, H, c->p_b2[1], nullptr, 0,
+                   (bf16_t*)out + (size_t)r0 * H, H, SK_STORE, s, 0));
+  }
+  return 0;
+}
+
+// ---- InternLM2 -----------------------------------------------------------------------------------------------
+// rows whose final hidden state is consumed: [score rows (one per clip) | logit rows], validated and uploaded to l_rowidx
+static int upload_out_rows(aigv_ctx* c, const int32_t* score_rows, bool with_score, int B, const int32_t* logit_rows, int R,
+                           int total_rows, hipStream_t s) {
+  const aigv_config& k = c->cfg;
+  if (R > k.max_out_rows) return fail(c, AIGV_ERR_ARG, "%d logit rows exceed max_out_rows %d", R, k.max_out_rows);
+  c->h_rowidx.clear();
+  for (int i = 0; i < (with_score ? B : 0); ++i) c->h_rowidx.push_back(score_rows[i]);
+  for (int i = 0; i < R; ++i) c->h_rowidx.push_back(logit_rows[i]);
+  for (int v : c->h_rowidx)
+    if (v < 0 || v >= total_rows) return fail(c, AIGV_ERR_ARG, "output row index %d outside 0..%d", v, total_rows - 1);
+  if (!c->h_rowidx.empty()) HIPCHK(c, aigv_launch_write_ints(c->h_rowidx.data(), (int)c->h_rowidx.size(), c->l_rowidx, s));
+  return 0;
+}
+
+// final RMSNorm + heads on the consumed rows.  compact: `hidden` already holds exactly those rows, in l_rowidx order.
+static int final_rows(aigv_ctx* c, float* score, int B, int R, int64_t* argmax, const bf16_t* hidden, bool compact, hipStream_t s) {
+  const aigv_config& k = c->cfg;
+  const int H = k.llm_hidden;
+  const int nS = score ? B : 0;
+  const int n = nS + R;
+  if (n == 0) return 0;
+  // final RMSNorm only on the rows that are consumed (modeling_internlm2.py:984)
+  HIPCHK(c, aigv_launch_rmsnorm(hidden, H, c->final_norm, c->l_rows, H, n, H, k.rms_eps, compact ? nullptr : c->l_rowidx, s));
+  for (int b0 = 0; b0 < nS; b0 += 64) {
+    // NB: the reference's NaN guard looks at the whole batch slice; batches above 64 clips are guarded per 64
+    ScoreHeadArgs a = c->score;
+    a.x = c->l_rows + (size_t)b0 * H; a.ldx = H; a.B = std::min(64, nS - b0); a.score = score + b0;
+    HIPCHK(c, aigv_launch_score_head(a, c->l_score_ws, s));
+  }
+  for (int r0 = 0; r0 < R; r0 += 64) {
+    const int rr = std::min(64, R - r0);
+    ProfScope ps(c, AIGV_PROF_SKINNY, 2.0 * rr * (double)k.vocab * H, 2.0 * (double)k.vocab * H, s);
+    HIPCHK(c, aigv_launch_lm_head_argmax(c->l_rows + (size_t)(nS + r0) * H, rr, H, c->lm_head, k.vocab, c->l_packed,
+                                         argmax + r0, nullptr, s));
+  }
+  return 0;
+}
+
+// ---- the two halves of an InternLM2 decoder layer around its attention, shared by aigv_llm_prefill and aigv_llm_extend (rows of
+// c->l_h, T of them).  fp8 mode: every linear of the layer in e4m3 except the post-attention half of the LAST layer (wo, w1|w3, w2
+// there act on the few consumed rows - weight streaming, nothing for fp8 MFMA to gain - and stay bf16 with or without row trimming).
+// attention_norm -> wqkv -> RoPE on K in place (one of g + 2 slots per group; the query heads are rotated by the attention kernel as
+// it loads them)
+static int llm_layer_qkv(aigv_ctx* c, int li, int T, hipStream_t s) {
+  const aigv_config& k = c->cfg;
+  const LlmLayer& L = c->llm[li];
+  const int H = k.llm_hidden, D = c->head_dim, g = c->g, nkv = k.llm_kv_heads;
+  if (c->fp8_llm) {
+    HIPCHK(c, aigv_launch_rmsnorm_quant_fp8(c->l_h, H, L.an, c->q8, H, c->q8_scale, T, H, k.rms_eps, s));
+    TRY(run_gemm_fp8(c, nullptr, H, H, c->llm8[li].wqkv, c->llm8[li].s_wqkv, c->l_qkv, c->qkv_out, T, c->qkv_out, EPI_STORE, nullptr, 0, s));
+  } else {
+    HIPCHK(c, aigv_launch_rmsnorm(c->l_h, H, L.an, c->l_t, H, T, H, k.rms_eps, nullptr, s));
+    TRY(run_llm_gemm(c, gemm_args(c->l_t, H, L.wqkv, H, c->l_qkv, c->qkv_out, T, c->qkv_out, H), EPI_STORE, s));
+  }
+  HIPCHK(c, aigv_launch_rope(c->l_qkv, c->qkv_out, c->l_pos, c->rope_cos, c->rope_sin, T, 1, g + 2, nkv, D, s, g));
+  return 0;
+}
+
+// h += wo(attention output);  h += w2(silu(w1 n) * w3 n), n = ffn_norm(h)
+static int llm_layer_post(aigv_ctx* c, int li, int T, hipStream_t s) {
+  const aigv_config& k = c->cfg;
+  const LlmLayer& L = c->llm[li];
+  const int H = k.llm_hidden, I = k.llm_inter;
+  if (c->fp8_llm && li != k.llm_layers - 1) {
+    const LlmLayerFp8& Q = c->llm8[li];
+    TRY(run_gemm_fp8(c, c->l_ao, H, H, Q.wo, Q.s_wo, c->l_h, H, T, H, EPI_RESID, c->l_h, H, s));
+    HIPCHK(c, aigv_launch_rmsnorm_quant_fp8(c->l_h, H, L.fn, c->q8, H, c->q8_scale, T, H, k.rms_eps, s));
+    TRY(run_gemm_fp8(c, nullptr, H, H, Q.w13, Q.s_w13, c->l_ffn, I, T, 2 * I, EPI_SWIGLU, nullptr, 0, s));
+    TRY(run_gemm_fp8(c, c->l_ffn, I, I, Q.w2, Q.s_w2, c->l_h, H, T, H, EPI_RESID, c->l_h, H, s));
+    return 0;
+  }
+  {
+    GemmArgs a = gemm_args(c->l_ao, H, L.wo, H, c->l_h, H, T, H, H);
+    a.resid = c->l_h; a.ldr = H;
+    TRY(run_llm_gemm(c, a, EPI_RESID, s));
+  }
+  HIPCHK(c, aigv_launch_rmsnorm(c->l_h, H, L.fn, c->l_t, H, T, H, k.rms_eps, nullptr, s));
+  TRY(run_llm_gemm(c, gemm_args(c->l_t, H, L.w13, H, c->l_ffn, I, T, 2 * I, H), EPI_SWIGLU, s));
+  GemmArgs a = gemm_args(c->l_ffn, I, L.w2, I, c->l_h, H, T, H, I);
+  a.resid = c->l_h; a.ldr = H;
+  TRY(run_llm_gemm(c, a, EPI_RESID, s));
+  return 0;
+}
+
+// The decode state of the N kept sequences, from their lengths h_kvlen: position of the next token | sequence | visible KV length | slot (-1:
+// a text token), uploaded once and advanced on the device (aigv_launch_advance)
+static int upload_decode_state(aigv_ctx* c, int N, hipStream_t s) {
+  c->h_dec.resize((size_t)4 * N);
+  for (int i = 0; i < N; ++i) {
+    const int len = c->h_kvlen[i];
+    c->h_dec[i] = len; c->h_dec[N + i] = i; c->h_dec[2 * N + i] = len + 1; c->h_dec[3 * N + i] = -1;
+  }
+  HIPCHK(c, aigv_launch_write_ints(c->h_dec.data(), N, c->dec_pos, s));
+  HIPCHK(c, aigv_launch_write_ints(c->h_dec.data() + N, N, c->dec_seq, s));
+  HIPCHK(c, aigv_launch_write_ints(c->h_dec.data() + 2 * N, N, c->dec_kvlen, s));
+  HIPCHK(c, aigv_launch_write_ints(c->h_dec.data() + 3 * N, N, c->dec_slot, s));
+  c->kv_seqs = N;
+  return 0;
+}
+
+// The AttnArgs that aigv_llm_prefill and aigv_llm_extend share: causal GQA attention of the rows of l_qkv, the query heads rotated as they
+// are loaded.  The caller adds where K / V live (k, v, ldk, ldv, kv_head_stride; the cache: kv_seq_stride, kv_off), max_len and q_tail.
+static AttnArgs llm_attn_args(const aigv_ctx* c, int B) {
+  const aigv_config& k = c->cfg;
+  const int D = c->head_dim;
+  AttnArgs a{};
+  a.q = c->l_qkv; a.ldq = c->qkv_out;
+  a.o = c->l_ao; a.ldo = k.llm_hidden;
+  a.cu = c->l_cu; a.n_seq = B;
+  a.n_heads = k.llm_heads; a.n_kv_heads = k.llm_kv_heads;
+  a.q_group_stride = (c->g + 2) * D;
+  a.causal = 1; a.post_div = sqrtf((float)D); a.q_prescale = 1.0f;
+  a.round_scores = c->attn_round_scores; a.waves = tune_knob(c, AIGV_TUNE_ATTN_WAVES);
+  a.rope_pos = c->l_pos; a.rope_cos = c->rope_cos; a.rope_sin = c->rope_sin;
+  a.rope_pos_is_row = 1;   // l_pos[t] = t - cu[seq] (+ the cached length): aigv_launch_seqpos
+  return a;
+}
+
+int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const int32_t* cu, int B, const void* vis,
+                     int n_vis, const void* motion, const int32_t* score_rows, float* score, const int32_t* logit_rows,
+                     int R, int64_t* argmax, int keep_kv, void* stream) {
+  if (!c || !ids || !slot || !cu) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: null argument");
+  if (!c->finalized) return fail(c, AIGV_ERR_STATE, "aigv_llm_prefill: call aigv_finalize_weights first");
+  const aigv_config& k = c->cfg;
+  if (B <= 0 || B > k.max_seqs) return fail(c, AIGV_ERR_ARG, "n_clips %d outside 1..%d", B, k.max_seqs);
+  if (cu[0] != 0) return fail(c, AIGV_ERR_ARG, "cu_seqlens[0] must be 0");
+  int max_len = 0;
+  for (int b = 0; b < B; ++b) {
+    const int len = cu[b + 1] - cu[b];
+    if (len <= 0) return fail(c, AIGV_ERR_ARG, "clip %d has an empty token sequence", b);
+    if (len > k.max_positions) return fail(c, AIGV_ERR_ARG, "clip %d: %d tokens exceed the RoPE table (%d)", b, len, k.max_positions);
+    max_len = std::max(max_len, len);
+  }
+  const int T = cu[B];
+  if (T > k.max_tokens) return fail(c, AIGV_ERR_ARG, "%d packed tokens exceed max_tokens %d", T, k.max_tokens);
+  if ((score && !score_rows) || (R > 0 && (!logit_rows || !argmax))) return fail(c, AIGV_ERR_ARG, "output rows/buffers inconsistent");
+  if (n_vis < 0 || (n_vis > 0 && !vis)) return fail(c, AIGV_ERR_ARG, "visual tokens missing");
+  if (keep_kv && (k.kv_capacity <= 0 || max_len >= k.kv_capacity))
+    return fail(c, AIGV_ERR_STATE, "keep_kv needs kv_capacity > longest prompt (%d vs %d)", k.kv_capacity, max_len);
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  const int H = k.llm_hidden, I = k.llm_inter, D = c->head_dim, g = c->g, nkv = k.llm_kv_heads;
+
+  if (B + 1 > AIGV_SMALL_INTS / 2) return fail(c, AIGV_ERR_ARG, "at most %d clips per prefill call", AIGV_SMALL_INTS / 2 - 1);
+  // positions / sequence ids / cu_seqlens are produced on the device from cu passed as a kernel argument
+  HIPCHK(c, aigv_launch_seqpos(cu, B, c->l_pos, c->l_seq, c->l_cu, T, s));
+  // every clip is a sequence: the kernel form of a row follows from its place in its own clip (struct RowPlan)
+  TRY(build_row_plan(c, c->rp_llm, cu, B, s));
+  RowPlanScope rps(c, &c->rp_llm);   // (fp8 mode: its bf16 GEMMs - the post-attention half of the last layer - follow the per-clip plan too)
+
+  HIPCHK(c, aigv_launch_embed(ids, slot, c->tok_emb, (const bf16_t*)vis, (const bf16_t*)motion, n_vis, c->l_h, T, H, s));
+  TRY(upload_out_rows(c, score_rows, score != nullptr, B, logit_rows, R, T, s));
+  // Row trimming: after the last layer's attention every row is independent, and only the consumed rows (one score row per
+  // clip + the answer rows) are read afterwards (stage2_eval.py:940-941; modeling_internvl_chat.py:469-481).  When they are
+  // few, the last layer finishes just those rows: attention for the query blocks that contain them, then wo / MLP on a
+  // compact copy through the weight-streaming skinny kernel.  K/V of the last layer still cover every row (keep_kv).
+  const int n_out = (int)c->h_rowidx.size();
+  int q_tail = 0;   // the farthest a consumed row lies from the end of its clip
+  // The rule is PER CLIP, so that a clip's consumed rows take the same kernels whatever its batch mates are: the consumed rows of a clip
+  // with at most TRIM_ROWS of them finish on the weight-streaming kernel (its fixed form), those of a clip with more on the tile kernels
+  // with all the other rows.  All clips small (the eval scripts' case): `trim` - the last layer runs for the consumed rows only.  Mixed
+  // batch: the last layer runs for every row AND the small clips' consumed rows are finished on the streaming path and put back in place.
+  constexpr int TRIM_ROWS = 16;
+  std::vector<int32_t> small_rows;
+  {
+    std::vector<int> per_clip(B, 0), clip_of(c->h_rowidx.size());
+    for (size_t i = 0; i < c->h_rowidx.size(); ++i) {
+      int b = 0;
+      while (cu[b + 1] <= c->h_rowidx[i]) ++b;
+      clip_of[i] = b;
+      ++per_clip[b];
+      q_tail = std::max(q_tail, cu[b + 1] - c->h_rowidx[i]);
+    }
+    for (size_t i = 0; i < c->h_rowidx.size(); ++i)
+      if (per_clip[clip_of[i]] <= TRIM_ROWS) small_rows.push_back(c->h_rowidx[i]);
+  }
+  const bool trim_ok = c->trim_last_layer && n_out > 0 && H % 128 == 0 && I % 128 == 0;
+  const bool trim = trim_ok && (int)small_rows.size() == n_out;
+  const bool mixed = trim_ok && !trim && !small_rows.empty();
+  if (mixed) HIPCHK(c, aigv_launch_write_ints(small_rows.data(), (int)small_rows.size(), c->l_rowidx2, s));
+  double attn_flops = 0;
+  for (int b = 0; b < B; ++b) { const double L = cu[b + 1] - cu[b]; attn_flops += 4.0 * (L * (L + 1) / 2) * D * k.llm_heads; }
+  const size_t kv_layer = (size_t)k.max_seqs * nkv * k.kv_capacity * D;
+  for (int li = 0; li < k.llm_layers; ++li) {
+    const LlmLayer& L = c->llm[li];
+    TRY(llm_layer_qkv(c, li, T, s));
+    if (keep_kv)
+      HIPCHK(c, aigv_launch_kv_store(c->l_qkv, c->qkv_out, c->l_seq, c->l_pos, c->kc + li * kv_layer, c->vc + li * kv_layer, T,
+                                     nkv, g, D, k.kv_capacity, s));
+    // a pass that only fills the cache (no output rows) needs nothing of the last layer beyond its K/V
+    if (n_out == 0 && c->trim_last_layer && li == k.llm_layers - 1) break;
+    {
+      AttnArgs a = llm_attn_args(c, B);   // K / V: this pass's rows of l_qkv
+      a.k = c->l_qkv + (size_t)g * D; a.v = c->l_qkv + (size_t)(g + 1) * D;
+      a.ldk = a.ldv = c->qkv_out; a.kv_head_stride = (g + 2) * D;
+      a.max_len = max_len;
+      const bool last_trim = trim && li == k.llm_layers - 1;
+      a.q_tail = last_trim ? q_tail : 0;
+      if (const char* m = aigv_attn_check(a, D)) return fail(c, AIGV_ERR_ARG, "%s", m);
+      ProfScope ps(c, AIGV_PROF_ATTN_LLM, last_trim ? 0.0 : attn_flops, 2.0 * T * ((double)c->qkv_out + H), s);
+      HIPCHK(c, aigv_launch_attention(a, D, s));
+    }
+    if ((trim || mixed) && li == k.llm_layers - 1) {
+      // 64 rows at a time through the weight-streaming kernel in its fixed 4-slice form (p = 0: the same bits whatever the row count);
+      // the finished rows collect in l_trim_h, in l_rowidx (mixed: l_rowidx2) order
+      const int32_t* idx = trim ? c->l_rowidx : c->l_rowidx2;
+      const int n_fin = trim ? n_out : (int)small_rows.size();
+      bf16_t *t_ao = c->l_trim, *t_n = t_ao + (size_t)64 * H, *t_ffn = t_n + (size_t)64 * H, *t_h = c->l_trim_h;
+      for (int r0 = 0; r0 < n_fin; r0 += 64) {
+        const int nr = std::min(64, n_fin - r0);
+        bf16_t* h = t_h + (size_t)r0 * H;
+        HIPCHK(c, aigv_launch_gather_rows(c->l_ao, H, idx + r0, nr, t_ao, H, s));
+        HIPCHK(c, aigv_launch_gather_rows(c->l_h, H, idx + r0, nr, h, H, s));
+        TRY(run_skinny(c, t_ao, H, nr, L.wo, H, H, H, nullptr, h, H, h, H, SK_RESID, s, 0));
+        HIPCHK(c, aigv_launch_rmsnorm(h, H, L.fn, t_n, H, nr, H, k.rms_eps, nullptr, s));
+        TRY(run_skinny(c, t_n, H, nr, L.w13, H, 2 * I, H, nullptr, nullptr, 0, t_ffn, I, SK_SWIGLU, s, 0));
+        TRY(run_skinny(c, t_ffn, I, nr, L.w2, I, H, I, nullptr, h, H, h, H, SK_RESID, s, 0));
+      }
+      if (trim) {
+        TRY(final_rows(c, score, B, R, argmax, t_h, true, s));
+        break;
+      }
+      TRY(llm_layer_post(c, li, T, s));                                                          // every row on the tile kernels ...
+      HIPCHK(c, aigv_launch_scatter_rows(t_h, c->l_rowidx2, n_fin, c->l_h, H, H, s));            // ... the small clips' consumed rows put back
+      break;
+    }
+    TRY(llm_layer_post(c, li, T, s));
+  }
+  if (!trim) TRY(final_rows(c, score, B, R, argmax, c->l_h, false, s));
+  if (keep_kv) {
+    c->h_kvlen.resize(B);
+    for (int b = 0; b < B; ++b) c->h_kvlen[b] = cu[b + 1] - cu[b];
+    TRY(upload_decode_state(c, B, s));
+    c->kv_valid = true;
+  } else {
+    c->kv_valid = false;
+  }
+  return 0;
+}
+
+// Continue the sequences kept by aigv_llm_prefill(keep_kv = 1) with new TEXT tokens: causal attention of the new rows over the
+// cached keys plus themselves.  commit = 0 leaves the cache lengths where they were, so several continuations of ONE prefix
+// (the four quality-perspective questions behind the same video tokens) can be scored one after the other.
+int aigv_llm_extend(aigv_ctx* c, const int64_t* ids, const int32_t* cu, int B, const int32_t* score_rows, float* score,
+                    const int32_t* logit_rows, int R, int64_t* argmax, int commit, void* stream) {
+  if (!c || !ids || !cu) return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: null argument");
+  if (!c->kv_valid) return fail(c, AIGV_ERR_STATE, "aigv_llm_extend: no KV state (run aigv_llm_prefill with keep_kv)");
+  const aigv_config& k = c->cfg;
+  if (B != c->kv_seqs) return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: %d sequences, the cache holds %d", B, c->kv_seqs);
+  if (B + 1 > AIGV_SMALL_INTS / 2) return fail(c, AIGV_ERR_ARG, "at most %d clips per call", AIGV_SMALL_INTS / 2 - 1);
+  if (cu[0] != 0) return fail(c, AIGV_ERR_ARG, "cu_seqlens[0] must be 0");
+  int max_new = 0;
+  for (int b = 0; b < B; ++b) {
+    const int n = cu[b + 1] - cu[b];
+    if (n <= 0) return fail(c, AIGV_ERR_ARG, "clip %d: no new tokens", b);
+    if (c->h_kvlen[b] + n > k.kv_capacity || c->h_kvlen[b] + n > k.max_positions)
+      return fail(c, AIGV_ERR_STATE, "clip %d: KV cache / RoPE table exhausted (%d cached + %d new, capacity %d)", b, c->h_kvlen[b], n, k.kv_capacity);
+    max_new = std::max(max_new, n);
+  }
+  const int T = cu[B];
+  if (T > k.max_tokens) return fail(c, AIGV_ERR_ARG, "%d new tokens exceed max_tokens %d", T, k.max_tokens);
+  if ((score && !score_rows) || (R > 0 && (!logit_rows || !argmax))) return fail(c, AIGV_ERR_ARG, "output rows/buffers inconsistent");
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  const int H = k.llm_hidden, D = c->head_dim, g = c->g, nkv = k.llm_kv_heads;
+  // positions continue after the cached tokens; the cached lengths are the per-sequence key offsets of the attention
+  HIPCHK(c, aigv_launch_seqpos(cu, B, c->l_pos, c->l_seq, c->l_cu, T, s, c->h_kvlen.data()));
+  HIPCHK(c, aigv_launch_write_ints(c->h_kvlen.data(), B, c->l_kvlen, s));
+  HIPCHK(c, aigv_launch_embed(ids, c->l_neg1, c->tok_emb, nullptr, nullptr, 0, c->l_h, T, H, s));
+  TRY(upload_out_rows(c, score_rows, score != nullptr, B, logit_rows, R, T, s));
+  double attn_flops = 0;
+  for (int b = 0; b < B; ++b) { const double n = cu[b + 1] - cu[b]; attn_flops += 4.0 * n * (c->h_kvlen[b] + (n + 1) / 2) * D * k.llm_heads; }
+  const size_t kv_layer = (size_t)k.max_seqs * nkv * k.kv_capacity * D;
+  for (int li = 0; li < k.llm_layers; ++li) {
+    // (fp8 mode: the linears aigv_llm_prefill runs in e4m3 run in e4m3 here too, so a continuation scores like the same tokens inside
+    // one prefill of that mode)
+    TRY(llm_layer_qkv(c, li, T, s));
+    HIPCHK(c, aigv_launch_kv_store(c->l_qkv, c->qkv_out, c->l_seq, c->l_pos, c->kc + li * kv_layer, c->vc + li * kv_layer, T, nkv, g, D,
+                                   k.kv_capacity, s));
+    {
+      AttnArgs a = llm_attn_args(c, B);   // K / V: the cache, the new rows behind each sequence's cached keys
+      a.k = c->kc + li * kv_layer; a.v = c->vc + li * kv_layer;
+      a.ldk = a.ldv = D; a.kv_head_stride = k.kv_capacity * D; a.kv_seq_stride = (size_t)nkv * k.kv_capacity * D;
+      a.kv_off = c->l_kvlen;
+      a.max_len = max_new;
+      if (const char* m = aigv_attn_check(a, D)) return fail(c, AIGV_ERR_ARG, "%s", m);
+      ProfScope ps(c, AIGV_PROF_ATTN_LLM, attn_flops, 2.0 * T * ((double)c->qkv_out + H), s);
+      HIPCHK(c, aigv_launch_attention(a, D, s));
+    }
+    TRY(llm_layer_post(c, li, T, s));
+  }
+  TRY(final_rows(c, score, B, R, argmax, c->l_h, false, s));
+  if (commit) {
+    for (int b = 0; b < B; ++b) {
+      const int len = c->h_kvlen[b] + (cu[b + 1] - cu[b]);
+      c->h_kvlen[b] = len;
+      c->h_dec[b] = len; c->h_dec[2 * B + b] = len + 1;
+    }
+    HIPCHK(c, aigv_launch_write_ints(c->h_dec.data(), B, c->dec_pos, s));
+    HIPCHK(c, aigv_launch_write_ints(c->h_dec.data() + 2 * B, B, c->dec_kvlen, s));
+  }
+  return 0;
+}
+
+// Replicate the kept sequences: slots [0, B) -> [B, 2B), ... so that `copies` different continuations of every sequence can
+// be extended in ONE pass (the decoder weights are then streamed once for all of them).
+int aigv_kv_fork(aigv_ctx* c, int copies, void* stream) {
+  if (!c) return fail(c, AIGV_ERR_ARG, "aigv_kv_fork: null context");
+  if (!c->kv_valid) return fail(c, AIGV_ERR_STATE, "aigv_kv_fork: no KV state (run aigv_llm_prefill with keep_kv)");
+  const aigv_config& k = c->cfg;
+  const int B = c->kv_seqs;
+  if (copies < 1 || (long)B * copies > k.max_seqs) return fail(c, AIGV_ERR_ARG, "aigv_kv_fork: %d x %d sequences exceed max_seqs %d", B, copies, k.max_seqs);
+  if (copies == 1) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  const size_t slot = (size_t)k.llm_kv_heads * k.kv_capacity * c->head_dim;      // elements per sequence and layer
+  const size_t kv_layer = (size_t)k.max_seqs * slot;
+  for (int li = 0; li < k.llm_layers; ++li)
+    for (int cpy = 1; cpy < copies; ++cpy) {
+      HIPCHK(c, hipMemcpyAsync(c->kc + li * kv_layer + (size_t)cpy * B * slot, c->kc + li * kv_layer, (size_t)B * slot * sizeof(bf16_t), hipMemcpyDeviceToDevice, s));
+      HIPCHK(c, hipMemcpyAsync(c->vc + li * kv_layer + (size_t)cpy * B * slot, c->vc + li * kv_layer, (size_t)B * slot * sizeof(bf16_t), hipMemcpyDeviceToDevice, s));
+    }
+  const int N = B * copies;
+  c->h_kvlen.resize(N);
+  for (int i = B; i < N; ++i) c->h_kvlen[i] = c->h_kvlen[i % B];
+  return upload_decode_state(c, N, s);
+}
+
+// Beam search over the kept sequences: sequence i continues from what sequence parent[i] has cached (its first len[i] positions); the
+// device-side positions of aigv_decode_step are untouched (all beams of a search have one length).  A gather into a second cache that
+// is allocated on first use (workspace: freed and re-made by aigv_ctx_resize), after which the two caches swap.
+int aigv_kv_reorder(aigv_ctx* c, const int32_t* parent, const int32_t* len, int n, void* stream) {
+  if (!c || !parent || !len) return fail(c, AIGV_ERR_ARG, "aigv_kv_reorder: null argument");
+  if (!c->kv_valid) return fail(c, AIGV_ERR_STATE, "aigv_kv_reorder: no KV state (run aigv_llm_prefill with keep_kv)");
+  const aigv_config& k = c->cfg;
+  if (n != c->kv_seqs) return fail(c, AIGV_ERR_ARG, "aigv_kv_reorder: %d sequences, the cache holds %d", n, c->kv_seqs);
+  int max_len = 0;
+  for (int i = 0; i < n; ++i) {
+    if (parent[i] < 0 || parent[i] >= n) return fail(c, AIGV_ERR_ARG, "aigv_kv_reorder: parent[%d] = %d outside 0..%d", i, parent[i], n - 1);
+    if (len[i] <= 0 || len[i] > k.kv_capacity) return fail(c, AIGV_ERR_ARG, "aigv_kv_reorder: len[%d] = %d outside 1..%d", i, len[i], k.kv_capacity);
+    max_len = std::max(max_len, len[i]);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (!c->kc_alt || !c->vc_alt || !c->beam_ints) {
+    // The second cache is made on first use.  No memset: the gather below writes every position a later step reads, and a
+    // blocking null-stream memset would not be ordered against a gather on a non-blocking stream `s`.  All three or none: a partial
+    // failure frees what it got, so the next call starts over instead of finding one pointer set.
+    const size_t per = (size_t)k.llm_layers * k.max_seqs * k.llm_kv_heads * k.kv_capacity * c->head_dim;
+    void *a = nullptr, *b = nullptr, *i = nullptr;
+    const hipError_t e1 = hipMalloc(&a, per * sizeof(bf16_t));
+    const hipError_t e2 = e1 == hipSuccess ? hipMalloc(&b, per * sizeof(bf16_t)) : e1;
+    const hipError_t e3 = e2 == hipSuccess ? hipMalloc(&i, (size_t)2 * k.max_seqs * sizeof(int32_t)) : e2;
+    if (e3 != hipSuccess) {
+      if (a) hipFree(a);
+      if (b) hipFree(b);
+      if (i) hipFree(i);
+      c->kc_alt = c->vc_alt = nullptr; c->beam_ints = nullptr;
+      return fail(c, AIGV_ERR_ALLOC, "aigv_kv_reorder: second KV cache (2 x %zu bytes): %s", per * sizeof(bf16_t), hipGetErrorString(e3));
+    }
+    c->kc_alt = (bf16_t*)a; c->vc_alt = (bf16_t*)b; c->beam_ints = (int32_t*)i;
+    c->ws_allocs.push_back(a); c->ws_allocs.push_back(b); c->ws_allocs.push_back(i);
+  }
+  HIPCHK(c, aigv_launch_write_ints(parent, n, c->beam_ints, s));
+  HIPCHK(c, aigv_launch_write_ints(len, n, c->beam_ints + k.max_seqs, s));
+  const size_t kv_layer = (size_t)k.max_seqs * k.llm_kv_heads * k.kv_capacity * c->head_dim;
+  hipError_t e = aigv_launch_kv_reorder(c->kc, c->vc, c->kc_alt, c->vc_alt, c->beam_ints, c->beam_ints + k.max_seqs, n, k.llm_layers, k.llm_kv_heads,
+                                        k.kv_capacity, c->head_dim, kv_layer, max_len, s);
+  if (e != hipSuccess) return fail(c, AIGV_ERR_HIP, "aigv_kv_reorder (n=%d): %s", n, hipGetErrorString(e));
+  std::swap(c->kc, c->kc_alt);
+  std::swap(c->vc, c->vc_alt);
+  return 0;
+}
+
+// Which form (P = 1, 2, 4: 16, 8, 4 rows of W per workgroup and slab) each decode GEMV runs in.  A GEMV's rate depends on how
+// evenly its workgroups fill the 256 CUs and on how many there are (scripts/gemv_balance_probe.py; in-box sweep of the 8B decode
+// step, profiles/r2_decode_forms.txt: wqkv 1 -> 4: -0.16 ms/token, w1|w3 1 -> 2: -0.16, 1 -> 4: -0.24, w2 1 -> 2: -0.08, 1 -> 4: -0.04,
+// wo: no change): the finest form the batch allows whose K sub-range per wave still fills one 8-deep load group; long-K GEMVs
+// (w2) stop at 8 rows.
+static int pick_form(int max_p, int K) {
+  int best = 1;
+  for (int p = 2; p <= max_p; p *= 2) {
+    if (K % (128 * p) || K / (4 * p) < 256 || (K > 8192 && p > 2)) break;
+    best = p;
+  }
+  return best;
+}
+
+static void decode_forms(aigv_ctx* c, int B, int* pq, int* po, int* p13, int* p2) {
+  const aigv_config& k = c->cfg;
+  const int max_p = B <= 4 ? 4 : B <= 8 ? 2 : 1;
+  if (resolved_gemm_mode(c) == 1) {   // batch-invariant bits: ONE form whatever the batch (p = 1 here; run_skinny then pins the K split too)
+    *pq = *po = *p13 = *p2 = 1;
+    return;
+  }
+  *pq = *po = *p13 = pick_form(max_p, k.llm_hidden);
+  *p2 = pick_form(max_p, k.llm_inter);
+  // AIGV_TUNE_SKINNY_P (experiments): one value for all four, or - value = 1000 + a packed "wqkv, wo, w1|w3, w2" word with 3 bits each
+  // (1 / 2 / 4) - one per GEMV (scripts/decode_bench.py; the sweep of profiles/r2_decode_forms.txt)
+  if (const int sp = tune_knob(c, AIGV_TUNE_SKINNY_P)) {
+    if (sp < 1000) *pq = *po = *p13 = *p2 = std::min(sp, max_p);
+    else {
+      int* out[4] = {pq, po, p13, p2};
+      for (int i = 0; i < 4; ++i) {
+        const int v = ((sp - 1000) >> (3 * i)) & 7;
+        if ((v == 1 || v == 2 || v == 4) && v <= max_p) *out[i] = v;
+      }
+    }
+  }
+}
+
+// decode attention of layer `li`: the new token of every sequence over its cached keys
+static int decode_attention(aigv_ctx* c, int li, int B, int max_vis, hipStream_t s) {
+  const aigv_config& k = c->cfg;
+  const int H = k.llm_hidden, D = c->head_dim, g = c->g, nkv = k.llm_kv_heads;
+  const size_t kv_layer = (size_t)k.max_seqs * nkv * k.kv_capacity * D;
+  HIPCHK(c, aigv_launch_attention_decode(c->l_qkv, c->qkv_out, (g + 2) * D, c->kc + li * kv_layer, c->vc + li * kv_layer,
+                                         c->dec_kvlen, k.kv_capacity, c->l_ao, H, B, nkv, g, D, sqrtf((float)D), max_vis,
+                                         c->dec_ws, s));
+  return 0;
+}
+
+// the bf16 tail of a decode layer, from the bf16 weights: h += wo(attention output);  h += w2(silu(w1 n) * w3 n), n = ffn_norm(h) - applied
+// by the w1|w3 GEMV itself when `fused`.  po / p13 / p2: the GEMVs' forms (decode_forms).
+static int decode_tail_bf16(aigv_ctx* c, const LlmLayer& L, int B, bool fused, int po, int p13, int p2, hipStream_t s) {
+  const aigv_config& k = c->cfg;
+  const int H = k.llm_hidden, I = k.llm_inter;
+  TRY(run_skinny(c, c->l_ao, H, B, L.wo, H, H, H, nullptr, c->l_h, H, c->l_h, H, SK_RESID, s, po));
+  if (fused) {
+    ProfScope ps(c, AIGV_PROF_SKINNY, 2.0 * B * 2.0 * I * H, 2.0 * 2.0 * I * H, s);
+    HIPCHK(c, aigv_launch_skinny_swiglu_normed(c->l_h, H, B, L.w13, H, 2 * I, H, c->l_ffn, I, L.fn, k.rms_eps, s, p13));
+  } else {
+    HIPCHK(c, aigv_launch_rmsnorm(c->l_h, H, L.fn, c->l_t, H, B, H, k.rms_eps, nullptr, s));
+    TRY(run_skinny(c, c->l_t, H, B, L.w13, H, 2 * I, H, nullptr, nullptr, 0, c->l_ffn, I, SK_SWIGLU, s, p13));
+  }
+  TRY(run_skinny(c, c->l_ffn, I, B, L.w2, I, H, I, nullptr, c->l_h, H, c->l_h, H, SK_RESID, s, p2));
+  return 0;
+}
+
+// aigv_decode_step / aigv_decode_step_logprob (logprob != nullptr: the lm-head runs its argmax + log-sum-exp form)
+static int decode_step(aigv_ctx* c, const int64_t* ids, int64_t* next, float* logprob, void* stream) {
+  const char* op = logprob ? "aigv_decode_step_logprob" : "aigv_decode_step";
+  if (!c || !ids || !next) return fail(c, AIGV_ERR_ARG, "%s: null argument", op);
+  if (!c->kv_valid) return fail(c, AIGV_ERR_STATE, "%s: no KV state (run aigv_llm_prefill with keep_kv)", op);
+  const aigv_config& k = c->cfg;
+  const int B = c->kv_seqs, H = k.llm_hidden, I = k.llm_inter, D = c->head_dim, g = c->g, nkv = k.llm_kv_heads;
+  if (B > 64) return fail(c, AIGV_ERR_ARG, "decode supports at most 64 clips per step");
+  for (int b = 0; b < B; ++b)
+    if (c->h_kvlen[b] + 1 > k.kv_capacity || c->h_kvlen[b] + 1 > k.max_positions)
+      return fail(c, AIGV_ERR_STATE, "clip %d: KV cache / RoPE table exhausted at %d tokens", b, c->h_kvlen[b]);
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  // positions of the new tokens (= current lengths) and the visible KV lengths live on the device (dec_pos, dec_kvlen)
+  // and are advanced by a one-block kernel at the end of the step: no host copies or syncs inside a decode step
+  int max_vis = 0;
+  for (int b = 0; b < B; ++b) max_vis = std::max(max_vis, c->h_kvlen[b] + 1);
+  HIPCHK(c, aigv_launch_embed(ids, c->dec_slot, c->tok_emb, nullptr, nullptr, 0, c->l_h, B, H, s));
+  const size_t kv_layer = (size_t)k.max_seqs * nkv * k.kv_capacity * D;
+  // Up to 4 sequences: attention_norm / ffn_norm are applied by the GEMV that consumes them (NormArgs in head.hip; same bits), 6
+  // launches per layer instead of 8.  AIGV_TUNE_DECODE_FUSED = 0 keeps the separate norm kernels (A/B).
+  const Tune tn_ = tune_of(c);
+  const bool fused = tn_[AIGV_TUNE_DECODE_FUSED] != 0 && B <= 4 && aigv_skinny_norm_fusable(H);
+  // sub-slab forms of the four GEMVs (skinny_kernel's P; head.hip): chosen so that the workgroups come to a whole number per CU.
+  // AIGV_TUNE_SKINNY_P / aigv_tune_skinny force one value everywhere it is legal (or one per GEMV: decode_forms).
+  int pq, po, p13, p2;
+  decode_forms(c, B, &pq, &po, &p13, &p2);
+  // fp8 mode: the linears the prefill runs in e4m3 stream their e4m3 copies here too (head8.hip: half the bytes per token; the
+  // x rows are normalised and quantised by the GEMV itself) - up to 4 sequences and for the widths the kernel is built for; larger
+  // batches decode from the bf16 weights.  AIGV_TUNE_DECODE_FP8 = 0 keeps the bf16 GEMVs (A/B); AIGV_TUNE_SKINNY_P8 = one form for all four.
+  const bool f8 = tn_[AIGV_TUNE_DECODE_FP8] != 0 && c->fp8_llm && B <= 4 && aigv_skinny_fp8_supported(H, true) && aigv_skinny_fp8_supported(I, false) && D == 128;
+  int q8[4] = {4, 2, 4, 2};
+  {
+    if (const int v = tn_[AIGV_TUNE_SKINNY_P8])
+      for (int i = 0; i < 4; ++i) q8[i] = v;
+    if (I / (4 * q8[3]) < 256 || I % (512 * q8[3])) q8[3] = 1;
+  }
+  for (int li = 0; li < k.llm_layers; ++li) {
+    const LlmLayer& L = c->llm[li];
+    if (f8) {
+      const LlmLayerFp8& Q = c->llm8[li];
+      const bool post8 = li != k.llm_layers - 1;   // the post-attention half of the last layer stays bf16, as in the prefill
+      const AigvRopeKv rk{c->dec_pos, c->dec_seq, c->rope_cos, c->rope_sin, c->kc + li * kv_layer, c->vc + li * kv_layer, g, nkv, k.kv_capacity};
+      {
+        ProfScope ps(c, AIGV_PROF_SKINNY, 2.0 * B * (double)c->qkv_out * H, (double)c->qkv_out * H, s);
+        HIPCHK(c, aigv_launch_skinny_fp8(c->l_h, H, B, Q.wqkv, H, Q.s_wqkv, c->qkv_out, H, nullptr, 0, c->l_qkv, c->qkv_out, SK_ROPE_KV, &rk, L.an, k.rms_eps, q8[0], s));
+      }
+      TRY(decode_attention(c, li, B, max_vis, s));
+      if (post8) {
+        ProfScope ps(c, AIGV_PROF_SKINNY, 2.0 * B * ((double)H * H + 3.0 * H * I), (double)H * H + 3.0 * H * I, s);
+        HIPCHK(c, aigv_launch_skinny_fp8(c->l_ao, H, B, Q.wo, H, Q.s_wo, H, H, c->l_h, H, c->l_h, H, SK_RESID, nullptr, nullptr, 0.f, q8[1], s));
+        HIPCHK(c, aigv_launch_skinny_fp8(c->l_h, H, B, Q.w13, H, Q.s_w13, 2 * I, H, nullptr, 0, c->l_ffn, I, SK_SWIGLU, nullptr, L.fn, k.rms_eps, q8[2], s));
+        HIPCHK(c, aigv_launch_skinny_fp8(c->l_ffn, I, B, Q.w2, I, Q.s_w2, H, I, c->l_h, H, c->l_h, H, SK_RESID, nullptr, nullptr, 0.f, q8[3], s));
+      } else {
+        TRY(decode_tail_bf16(c, L, B, fused, po, p13, p2, s));
+      }
+      continue;
+    }
+    if (!fused) HIPCHK(c, aigv_launch_rmsnorm(c->l_h, H, L.an, c->l_t, H, B, H, k.rms_eps, nullptr, s));
+    {   // wqkv with RoPE + KV-cache append in its epilogue: one launch instead of GEMV + rope / store
+      ProfScope ps(c, AIGV_PROF_SKINNY, 2.0 * B * (double)c->qkv_out * H, 2.0 * (double)c->qkv_out * H, s);
+      HIPCHK(c, aigv_launch_skinny_rope_kv(fused ? c->l_h : c->l_t, H, B, L.wqkv, H, c->qkv_out, H, c->l_qkv, c->qkv_out, c->dec_pos, c->dec_seq, c->rope_cos,
+                                           c->rope_sin, c->kc + li * kv_layer, c->vc + li * kv_layer, g, nkv, k.kv_capacity, D, s,
+                                           fused ? L.an : nullptr, k.rms_eps, pq));
+    }
+    TRY(decode_attention(c, li, B, max_vis, s));
+    TRY(decode_tail_bf16(c, L, B, fused, po, p13, p2, s));
+  }
+  HIPCHK(c, aigv_launch_rmsnorm(c->l_h, H, c->final_norm, c->l_rows, H, B, H, k.rms_eps, nullptr, s));
+  if (logprob) HIPCHK(c, aigv_launch_lm_head_argmax_logprob(c->l_rows, B, H, c->lm_head, k.vocab, c->l_packed, c->dec_lse, next, nullptr, logprob, s));
+  else HIPCHK(c, aigv_launch_lm_head_argmax(c->l_rows, B, H, c->lm_head, k.vocab, c->l_packed, next, nullptr, s));
+  HIPCHK(c, aigv_launch_advance(c->dec_pos, c->dec_kvlen, B, s));
+  for (int b = 0; b < B; ++b) c->h_kvlen[b] += 1;
+  return 0;
+}
+
+int aigv_decode_step(aigv_ctx* c, const int64_t* ids, int64_t* next, void* stream) { return decode_step(c, ids, next, nullptr, stream); }
+
+int aigv_decode_step_logprob(aigv_ctx* c, const int64_t* ids, int64_t* next, float* logprob, void* stream) {
+  if (!logprob) return fail(c, AIGV_ERR_ARG, "aigv_decode_step_logprob: null argument");
+  return decode_step(c, ids, next, logprob, stream);
+}
+
+int aigv_out_row_logits(aigv_ctx* c, int first_row, int n_rows, void* logits_bf16, int ldo, void* stream) {
+  if (!c || !logits_bf16) return fail(c, AIGV_ERR_ARG, "aigv_out_row_logits: null argument");
+  if (!c->finalized) return fail(c, AIGV_ERR_STATE, "aigv_out_row_logits: call aigv_finalize_weights first");
+  const aigv_config& k = c->cfg;
+  const int cap = k.max_out_rows + k.max_seqs + 64;
+  if (first_row < 0 || n_rows <= 0 || first_row + n_rows > cap) return fail(c, AIGV_ERR_ARG, "aigv_out_row_logits: rows %d..%d outside 0..%d", first_row, first_row + n_rows - 1, cap - 1);
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  for (int r0 = 0; r0 < n_rows; r0 += 64) {
+    const int rr = std::min(64, n_rows - r0);
+    ProfScope ps(c, AIGV_PROF_SKINNY, 2.0 * rr * (double)k.vocab * k.llm_hidden, 2.0 * (double)k.vocab * k.llm_hidden, s);
+    hipError_t e = aigv_launch_lm_head_logits(c->l_rows + (size_t)(first_row + r0) * k.llm_hidden, rr, k.llm_hidden, c->lm_head, k.vocab,
+                                              (bf16_t*)logits_bf16 + (size_t)r0 * ldo, ldo, s);
+    if (e != hipSuccess) return fail(c, e == hipErrorInvalidValue ? AIGV_ERR_ARG : AIGV_ERR_HIP, "lm-head logits (rows=%d ldo=%d): %s", rr, ldo, hipGetErrorString(e));
+  }
+  return 0;
+}
+
+int aigv_out_row_logprob(aigv_ctx* c, int first_row, int n_rows, const int64_t* labels, float* logprob, void* stream) {
+  if (!c || !labels || !logprob) return fail(c, AIGV_ERR_ARG, "aigv_out_row_logprob: null argument");
+  if (!c->finalized) return fail(c, AIGV_ERR_STATE, "aigv_out_row_logprob: call aigv_finalize_weights first");
+  const aigv_config& k = c->cfg;
+  const int cap = k.max_out_rows + k.max_seqs + 64;
+  if (first_row < 0 || n_rows <= 0 || first_row + n_rows > cap) return fail(c, AIGV_ERR_ARG, "aigv_out_row_logprob: rows %d..%d outside 0..%d", first_row, first_row + n_rows - 1, cap - 1);
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  for (int r0 = 0; r0 < n_rows; r0 += 64) {
+    const int rr = std::min(64, n_rows - r0);
+    {
+      ProfScope ps(c, AIGV_PROF_SKINNY, 2.0 * rr * (double)k.vocab * k.llm_hidden, 2.0 * (double)k.vocab * k.llm_hidden, s);
+      hipError_t e = aigv_launch_lm_head_logits(c->l_rows + (size_t)(first_row + r0) * k.llm_hidden, rr, k.llm_hidden, c->lm_head, k.vocab,
+                                                c->l_lp, c->lp_ldo, s, /*one_form=*/true);
+      if (e != hipSuccess) return fail(c, e == hipErrorInvalidValue ? AIGV_ERR_ARG : AIGV_ERR_HIP, "lm-head logits (rows=%d ldo=%d): %s", rr, c->lp_ldo, hipGetErrorString(e));
+    }
+    hipError_t e = aigv_launch_label_logprob(c->l_lp, rr, k.vocab, c->lp_ldo, labels + r0, logprob + r0, s);
+    if (e != hipSuccess) return fail(c, e == hipErrorInvalidValue ? AIGV_ERR_ARG : AIGV_ERR_HIP, "label log-probabilities (rows=%d): %s", rr, hipGetErrorString(e));
+  }
+  return 0;
+}
+
+int aigv_out_row_hidden(aigv_ctx* c, int first_row, int n_rows, void* hidden_bf16, int ldo, void* stream) {
+  if (!c || !hidden_bf16) return fail(c, AIGV_ERR_ARG, "aigv_out_row_hidden: null argument");
+  if (!c->finalized) return fail(c, AIGV_ERR_STATE, "aigv_out_row_hidden: call aigv_finalize_weights first");
+  const aigv_config& k = c->cfg;
+  const int cap = k.max_out_rows + k.max_seqs + 64;
+  if (first_row < 0 || n_rows <= 0 || first_row + n_rows > cap || ldo < k.llm_hidden)
+    return fail(c, AIGV_ERR_ARG, "aigv_out_row_hidden: rows %d..%d outside 0..%d or ldo %d < %d", first_row, first_row + n_rows - 1, cap - 1, ldo, k.llm_hidden);
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpy2DAsync(hidden_bf16, (size_t)ldo * sizeof(bf16_t), c->l_rows + (size_t)first_row * k.llm_hidden, (size_t)k.llm_hidden * sizeof(bf16_t),
+                             (size_t)k.llm_hidden * sizeof(bf16_t), n_rows, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return 0;
+}
+
+int aigv_decode_eos(aigv_ctx* c, int64_t* tokens, int32_t* state, const int64_t* eos_ids, int n_eos, int64_t pad_id, void* stream) {
+  if (!c || !tokens || !state) return fail(c, AIGV_ERR_ARG, "aigv_decode_eos: null argument");
+  if (!c->kv_valid) return fail(c, AIGV_ERR_STATE, "aigv_decode_eos: no KV state (run aigv_llm_prefill with keep_kv)");
+  if (n_eos < 0 || n_eos > 8 || (n_eos > 0 && !eos_ids)) return fail(c, AIGV_ERR_ARG, "aigv_decode_eos: 0..8 end-of-sequence ids");
+  if (c->kv_seqs > 64) return fail(c, AIGV_ERR_ARG, "aigv_decode_eos: at most 64 sequences");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, aigv_launch_decode_eos(tokens, state, c->kv_seqs, eos_ids, n_eos, pad_id, (hipStream_t)stream));
+  return 0;
+}
+
+}  // extern "C"

@@ -381,7 +381,8 @@ enum aigv_tune_knob {
   AIGV_TUNE_DECODE_FP8 = 10,     /* decode in fp8 mode: 1 (default) = e4m3 GEMVs, 0 = bf16 GEMVs */
   AIGV_TUNE_SKINNY_P8 = 11,      /* form of the e4m3 decode GEMVs: 0 per-GEMV defaults, 1 / 2 / 4 */
   AIGV_TUNE_FUSE_TAILS = 12,     /* the tail tiles' K slices inside the body's launch: 0 = when the body leaves CUs idle (default), 1 = never, 2 = always; same bits */
-  AIGV_TUNE_LONE_BODY = 13       /* row-plan bodies of <= 128 tiles on the 256x128 kernel's one-workgroup-per-CU form: 0 = by fill, 1 = never (default), 2 = always, 3 / 4 = by fill for GEMMs with / without split-K tails; same bits */
+  AIGV_TUNE_LONE_BODY = 13,      /* row-plan bodies of <= 128 tiles on the 256x128 kernel's one-workgroup-per-CU form: 0 = by fill, 1 = never (default), 2 = always, 3 / 4 = by fill for GEMMs with / without split-K tails; same bits */
+  AIGV_TUNE_COUNT = 14           /* number of knobs, not a knob */
 };
 int aigv_ctx_tune(aigv_ctx* ctx, int knob, int value);
 /* GEMM tile-kernel selection: mode 0 = cost model (default), 1 = always the 128x128 kernel, 2 = always the 256x256

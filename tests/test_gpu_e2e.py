@@ -1237,7 +1237,7 @@ def test_full_size_8b_properties(full_8b):
     assert torch.equal(both["score1"], again["score1"]) and torch.equal(both["logit"], again["logit"])      # deterministic
     n1 = toks["input_ids"].shape[1] - 1
     assert n1 == 2176
-    # Batch invariance in the DEFAULT mode (round 4).  The GEMM dispatch is planned per clip / per frame (csrc/api.hip
+    # Batch invariance in the DEFAULT mode (round 4).  The GEMM dispatch is planned per clip / per frame (csrc/dispatch.hip
     # struct RowPlan): a row's kernel form and K split follow from its place in its own sequence, never from the batch - so a clip scored
     # alone gives the bits it gives inside the batch (until round 3: only to bf16 noise, 0.027 on this very clip).  Modes 1 / 2 (every
     # row on one tile kernel in full K) are batch-invariant as well and stay as test aliases.

@@ -217,6 +217,17 @@ def test_product_path_never_imports_the_oracle():
                 assert "/root/reference" not in txt, f
 
 
+def test_tune_knob_names_follow_the_header_enum():
+    """A knob is a number of ``enum aigv_tune_knob`` (the index of the library's knob table) and a name in
+    ``InternVLChatModel.TUNE_KNOBS``: the two lists must be the same list, so that a knob cannot be added to one of them only."""
+    header = open(os.path.join(ROOT, "include", "aigv_amd.h")).read()
+    body = re.search(r"enum aigv_tune_knob \{(.*?)\};", header, re.S).group(1)
+    enum = {name.lower(): int(num) for name, num in re.findall(r"\bAIGV_TUNE_([A-Z0-9_]+)\s*=\s*(\d+)", body)}
+    count = enum.pop("count")
+    assert sorted(enum.values()) == list(range(count)), enum
+    assert InternVLChatModel.TUNE_KNOBS == enum
+
+
 def test_product_library_reads_no_environment_variable():
     """a stray variable must not be able to re-roll a summation order.  Every experiment knob of the kernels is a field of
     the context (aigv_ctx_tune) or a process default set by an explicit call (aigv_tune_*); the native sources hold no getenv."""
