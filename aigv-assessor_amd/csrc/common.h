@@ -100,6 +100,26 @@ __device__ __forceinline__ float block_sum_256(float v, float* red) {
   return red[0] + red[1] + red[2] + red[3];
 }
 
+// Online log-sum-exp over a set of columns as a (max, sum of exp(x - max)) pair: the arithmetic every log-probability kernel shares
+// (logprob.hip, candlogprob.hip, the SK_ARGMAX_LSE epilogue and its finishers in head.hip), so that they agree bit for bit.
+// (m, s) <- the pair of the union of the two column sets.  Symmetric in its arguments; (-inf, 0) is the empty set.
+__device__ __forceinline__ void lse_combine(float& m, float& s, float m2, float s2) {
+  const float M = fmaxf(m, m2);
+  if (M == -INFINITY) return;
+  s = s * expf(m - M) + s2 * expf(m2 - M);
+  m = M;
+}
+
+__device__ __forceinline__ void lse_push(float& m, float& s, float x) {
+  if (x == -INFINITY) return;          // exp(-inf) adds nothing (and keeps an empty pair from turning into NaN)
+  if (x > m) {
+    s = s * expf(m - x) + 1.0f;
+    m = x;
+  } else {
+    s += expf(x - m);
+  }
+}
+
 #define GLOBAL_AS __attribute__((address_space(1)))
 #define LDS_AS __attribute__((address_space(3)))
 

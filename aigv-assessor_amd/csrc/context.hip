@@ -144,6 +144,7 @@ static int alloc_workspaces(aigv_ctx* c) {
     if ((rc = dalloc(c, &c->l_lp, (size_t)64 * c->lp_ldo))) break;
     // allocated here for the same reason (a decode step may be captured); a resize re-runs this function
     if ((rc = dalloc(c, &c->dec_lse, (size_t)std::min(k.max_seqs, 64) * aigv_lm_head_lse_slots(k.vocab)))) break;
+    if ((rc = dalloc(c, &c->dec_cand, aigv_cand_logit_elems(std::min(k.max_seqs, 64))))) break;
     if (k.kv_capacity > 0) {
       const size_t per = (size_t)k.llm_layers * k.max_seqs * k.llm_kv_heads * k.kv_capacity * c->head_dim;
       if ((rc = dalloc(c, &c->kc, per))) break;

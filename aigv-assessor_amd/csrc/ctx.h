@@ -110,6 +110,7 @@ struct aigv_ctx {
   int32_t* beam_ints = nullptr;                  // [2 * max_seqs]: parent slots | live lengths of a reorder
   float* dec_ws = nullptr;
   float2* dec_lse = nullptr;  // aigv_decode_step_logprob: per-16-column log-sum-exp partials [min(max_seqs, 64)][ceil(vocab / 16)]
+  bf16_t* dec_cand = nullptr; // aigv_decode_step_cand_logprob: bf16 logits of the candidate columns [min(max_seqs, 64)][AIGV_MAX_CANDIDATES]
   int32_t *dec_pos = nullptr, *dec_seq = nullptr, *dec_kvlen = nullptr, *dec_slot = nullptr;   // device-side decode state
   std::vector<int32_t> h_dec;
   std::vector<int32_t> h_pos, h_seq, h_rowidx, h_kvlen;

@@ -25,22 +25,7 @@ namespace {
 // per row - with no atomics: lane fq holds columns 4 fq .. 4 fq + 3 of the slab, pushed in column order, then two butterfly steps.  The
 // slot layout follows the 16-row slabs, not the workgroups (one or four slabs per workgroup depending on R), so a row's partials do
 // not depend on R; lse_finish_kernel merges them in a fixed order.
-__device__ __forceinline__ void lse_combine(float& m, float& s, float m2, float s2) {   // (-inf, 0) is the empty set; as logprob.hip
-  const float M = fmaxf(m, m2);
-  if (M == -INFINITY) return;
-  s = s * expf(m - M) + s2 * expf(m2 - M);
-  m = M;
-}
-
-__device__ __forceinline__ void lse_push(float& m, float& s, float x) {
-  if (x == -INFINITY) return;
-  if (x > m) {
-    s = s * expf(m - x) + 1.0f;
-    m = x;
-  } else {
-    s += expf(x - m);
-  }
-}
+// (lse_push / lse_combine: common.h)
 
 // SK_ROPE_KV: the decode step's wqkv GEMV with RoPE and the KV-cache append in its epilogue (head_dim 128).  A workgroup takes the
 // two 16-row slabs of W that rotate_half pairs - dims 16 sub .. and 64 + 16 sub .. of one head slot - so a lane ends up holding
@@ -592,17 +577,24 @@ hipError_t aigv_launch_lm_head_argmax(const bf16_t* h, int R, int H, const bf16_
 
 size_t aigv_lm_head_lse_slots(int V) { return (size_t)(V + 15) / 16; }
 
+// the lm-head in its SK_ARGMAX_LSE form alone: the packed argmax keys and the per-slab log-sum-exp partials, for a finisher to read
+hipError_t aigv_launch_lm_head_lse_partials(const bf16_t* h, int R, int H, const bf16_t* W, int V, unsigned long long* packed, float2* part,
+                                            hipStream_t s) {
+  if (R <= 0) return hipSuccess;
+  if (R > 64 || H % 128 || V < 1 || !packed || !part) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(packed, 0, sizeof(unsigned long long) * R, s);
+  if (e != hipSuccess) return e;
+  return launch_skinny<SK_ARGMAX_LSE>(h, H, R, W, H, V, H, nullptr, nullptr, 0, reinterpret_cast<bf16_t*>(part), (int)aigv_lm_head_lse_slots(V), packed, s);
+}
+
 // aigv_launch_lm_head_argmax + the fused log-sum-exp (SK_ARGMAX_LSE): part holds R * aigv_lm_head_lse_slots(V) float2
 hipError_t aigv_launch_lm_head_argmax_logprob(const bf16_t* h, int R, int H, const bf16_t* W, int V, unsigned long long* packed, float2* part,
                                               int64_t* out_idx, float* out_val, float* out_logprob, hipStream_t s) {
   if (R <= 0) return hipSuccess;
-  if (R > 64 || H % 128 || V < 1 || !packed || !part || !out_idx || !out_logprob) return hipErrorInvalidValue;
-  hipError_t e = hipMemsetAsync(packed, 0, sizeof(unsigned long long) * R, s);
+  if (!out_idx || !out_logprob) return hipErrorInvalidValue;
+  const hipError_t e = aigv_launch_lm_head_lse_partials(h, R, H, W, V, packed, part, s);
   if (e != hipSuccess) return e;
-  const int nslot = (int)aigv_lm_head_lse_slots(V);
-  e = launch_skinny<SK_ARGMAX_LSE>(h, H, R, W, H, V, H, nullptr, nullptr, 0, reinterpret_cast<bf16_t*>(part), nslot, packed, s);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(lse_finish_kernel, dim3(R), dim3(LSE_THREADS), 0, s, packed, part, nslot, out_idx, out_val, out_logprob);
+  hipLaunchKernelGGL(lse_finish_kernel, dim3(R), dim3(LSE_THREADS), 0, s, packed, part, (int)aigv_lm_head_lse_slots(V), out_idx, out_val, out_logprob);
   return hipGetLastError();
 }
 

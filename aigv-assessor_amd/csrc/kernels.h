@@ -179,6 +179,22 @@ hipError_t aigv_launch_lm_head_argmax(const bf16_t* h, int R, int H, const bf16_
 size_t aigv_lm_head_lse_slots(int V);
 hipError_t aigv_launch_lm_head_argmax_logprob(const bf16_t* h, int R, int H, const bf16_t* W, int V, unsigned long long* packed, float2* part,
                                               int64_t* out_idx, float* out_val, float* out_logprob, hipStream_t s);
+// the first half of aigv_launch_lm_head_argmax_logprob: the lm-head's packed argmax keys and log-sum-exp partials, no finisher
+hipError_t aigv_launch_lm_head_lse_partials(const bf16_t* h, int R, int H, const bf16_t* W, int V, unsigned long long* packed, float2* part,
+                                            hipStream_t s);
+// candidate-token log-probabilities (candlogprob.hip): C <= AIGV_MAX_CANDIDATES token ids, DEVICE int64 [C]; an id outside [0, V) gives a NaN column.
+// Scoring pass: out[r, c] = logits[r, cand[c]] - logsumexp(logits[r, :V]) over bf16 logits [rows, ldo >= V], out fp32 [rows, C];
+// aigv_launch_label_logprob's mapping and tree, so column c holds that kernel's bits for labels = cand[c].
+#ifndef AIGV_MAX_CANDIDATES
+#define AIGV_MAX_CANDIDATES 64   // = include/aigv_amd.h
+#endif
+hipError_t aigv_launch_cand_logprob(const bf16_t* logits, int rows, int V, int ldo, const int64_t* cand, int C, float* out, hipStream_t s);
+// Decode: aigv_launch_lm_head_argmax_logprob (idx / val / logprob: its bits) plus out_cand[r, c] = bf16 logit of column cand[c] - the row's
+// log-sum-exp; the C columns come from a GEMV over the C gathered weight rows.  cand_logit: scratch of aigv_cand_logit_elems(R) bf16.
+size_t aigv_cand_logit_elems(int R);
+hipError_t aigv_launch_lm_head_argmax_cand_logprob(const bf16_t* h, int R, int H, const bf16_t* W, int V, unsigned long long* packed, float2* part,
+                                                   const int64_t* cand, int C, bf16_t* cand_logit, int64_t* out_idx, float* out_val,
+                                                   float* out_logprob, float* out_cand, hipStream_t s);
 // lm-head logits (bf16, the matmul output the reference upcasts) of R rows into out[R, ldo], ldo >= roundup(V, 4)
 // one_form: the 4-slice form for every row count (that of the fused argmax), so that a row's logits do not depend on how many rows
 // share the launch; otherwise <= 16 rows of a vocabulary <= 4096 take the 8-slice GEMV form

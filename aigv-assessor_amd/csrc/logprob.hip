@@ -12,24 +12,6 @@ namespace {
 
 constexpr int LP_THREADS = 256;
 
-// (m, s) <- the pair of the union of the two column sets.  Symmetric in its arguments; (-inf, 0) is the empty set.
-__device__ __forceinline__ void lse_combine(float& m, float& s, float m2, float s2) {
-  const float M = fmaxf(m, m2);
-  if (M == -INFINITY) return;
-  s = s * expf(m - M) + s2 * expf(m2 - M);
-  m = M;
-}
-
-__device__ __forceinline__ void lse_push(float& m, float& s, float x) {
-  if (x == -INFINITY) return;          // exp(-inf) adds nothing (and keeps an empty pair from turning into NaN)
-  if (x > m) {
-    s = s * expf(m - x) + 1.0f;
-    m = x;
-  } else {
-    s += expf(x - m);
-  }
-}
-
 // VEC: every row start is 8-byte aligned (ldo % 4 == 0 and an aligned base): whole chunks come in as one 8-byte load.  The scalar
 // form reads the same columns in the same order - both forms give the same bits.
 template <bool VEC>

@@ -189,6 +189,40 @@ int aigv_op_label_logprob(const void* logits_bf16, int rows, int vocab, int ldo,
   return 0;
 }
 
+int aigv_op_cand_logprob(const void* logits_bf16, int rows, int vocab, int ldo, const int64_t* cand_ids, int C, float* out, void* stream) {
+  const char* op = "aigv_op_cand_logprob";
+  if (C < 1 || C > AIGV_MAX_CANDIDATES) return fail(nullptr, AIGV_ERR_ARG, "%s: C = %d candidates outside 1..%d", op, C, AIGV_MAX_CANDIDATES);
+  if (!cand_ids || (rows > 0 && (!logits_bf16 || !out))) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+  if (rows < 0 || vocab < 1 || ldo < vocab) return fail(nullptr, AIGV_ERR_ARG, "%s: bad argument (rows %d, vocab %d, ldo %d)", op, rows, vocab, ldo);
+  HIPCHK(nullptr, aigv_launch_cand_logprob((const bf16_t*)logits_bf16, rows, vocab, ldo, cand_ids, C, out, (hipStream_t)stream));
+  return 0;
+}
+
+int64_t aigv_op_lm_head_argmax_cand_logprob_scratch_bytes(int rows, int vocab) {
+  const int64_t base = aigv_op_lm_head_argmax_logprob_scratch_bytes(rows, vocab);   // [packed keys | log-sum-exp partials], then the candidate logits
+  return base < 0 ? -1 : (base + 15) / 16 * 16 + (int64_t)(aigv_cand_logit_elems(rows) * sizeof(bf16_t));
+}
+
+int aigv_op_lm_head_argmax_cand_logprob(const void* h, int rows, int hidden, const void* W_, int vocab, const int64_t* cand_ids, int C,
+                                        void* scratch, int64_t scratch_bytes, int64_t* idx, float* val, float* logprob, float* cand_logprob,
+                                        void* stream) {
+  const char* op = "aigv_op_lm_head_argmax_cand_logprob";
+  if (C < 1 || C > AIGV_MAX_CANDIDATES) return fail(nullptr, AIGV_ERR_ARG, "%s: C = %d candidates outside 1..%d", op, C, AIGV_MAX_CANDIDATES);
+  if (!h || !W_ || !scratch || !idx || !logprob || !cand_ids || !cand_logprob) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+  if (rows < 1 || rows > 64) return fail(nullptr, AIGV_ERR_ARG, "%s: rows = %d outside 1..64", op, rows);
+  if (hidden < 128 || hidden % 128) return fail(nullptr, AIGV_ERR_ARG, "%s: hidden = %d is not a positive multiple of 128", op, hidden);
+  if (vocab < 1) return fail(nullptr, AIGV_ERR_ARG, "%s: vocab = %d must be positive", op, vocab);
+  if (((uintptr_t)h & 15) || ((uintptr_t)W_ & 15) || ((uintptr_t)scratch & 15)) return fail(nullptr, AIGV_ERR_ARG, "%s: h, W and scratch must be 16-byte aligned", op);
+  const int64_t need = aigv_op_lm_head_argmax_cand_logprob_scratch_bytes(rows, vocab);
+  if (scratch_bytes < need) return fail(nullptr, AIGV_ERR_ARG, "%s: scratch of %lld bytes, needs %lld", op, (long long)scratch_bytes, (long long)need);
+  unsigned long long* packed = (unsigned long long*)scratch;
+  float2* part = (float2*)((char*)scratch + 64 * sizeof(unsigned long long));
+  bf16_t* cl = (bf16_t*)((char*)scratch + (aigv_op_lm_head_argmax_logprob_scratch_bytes(rows, vocab) + 15) / 16 * 16);
+  HIPCHK(nullptr, aigv_launch_lm_head_argmax_cand_logprob((const bf16_t*)h, rows, hidden, (const bf16_t*)W_, vocab, packed, part, cand_ids, C, cl, idx, val,
+                                                          logprob, cand_logprob, (hipStream_t)stream));
+  return 0;
+}
+
 // ---- the decode step's kernels, one by one (test entry points): every argument is checked here, before any HIP call ----
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 

@@ -589,9 +589,11 @@ static int decode_tail_bf16(aigv_ctx* c, const LlmLayer& L, int B, bool fused, i
   return 0;
 }
 
-// aigv_decode_step / aigv_decode_step_logprob (logprob != nullptr: the lm-head runs its argmax + log-sum-exp form)
-static int decode_step(aigv_ctx* c, const int64_t* ids, int64_t* next, float* logprob, void* stream) {
-  const char* op = logprob ? "aigv_decode_step_logprob" : "aigv_decode_step";
+// aigv_decode_step / aigv_decode_step_logprob (logprob != nullptr: the lm-head runs its argmax + log-sum-exp form) /
+// aigv_decode_step_cand_logprob (cand_lp != nullptr: that form, then the candidates' GEMV and the finisher that subtracts the log-sum-exp)
+static int decode_step(aigv_ctx* c, const int64_t* ids, int64_t* next, float* logprob, void* stream, const int64_t* cand = nullptr, int C = 0,
+                       float* cand_lp = nullptr) {
+  const char* op = cand_lp ? "aigv_decode_step_cand_logprob" : logprob ? "aigv_decode_step_logprob" : "aigv_decode_step";
   if (!c || !ids || !next) return fail(c, AIGV_ERR_ARG, "%s: null argument", op);
   if (!c->kv_valid) return fail(c, AIGV_ERR_STATE, "%s: no KV state (run aigv_llm_prefill with keep_kv)", op);
   const aigv_config& k = c->cfg;
@@ -658,7 +660,9 @@ static int decode_step(aigv_ctx* c, const int64_t* ids, int64_t* next, float* lo
     TRY(decode_tail_bf16(c, L, B, fused, po, p13, p2, s));
   }
   HIPCHK(c, aigv_launch_rmsnorm(c->l_h, H, c->final_norm, c->l_rows, H, B, H, k.rms_eps, nullptr, s));
-  if (logprob) HIPCHK(c, aigv_launch_lm_head_argmax_logprob(c->l_rows, B, H, c->lm_head, k.vocab, c->l_packed, c->dec_lse, next, nullptr, logprob, s));
+  if (cand_lp) HIPCHK(c, aigv_launch_lm_head_argmax_cand_logprob(c->l_rows, B, H, c->lm_head, k.vocab, c->l_packed, c->dec_lse, cand, C, c->dec_cand, next,
+                                                                 nullptr, logprob, cand_lp, s));
+  else if (logprob) HIPCHK(c, aigv_launch_lm_head_argmax_logprob(c->l_rows, B, H, c->lm_head, k.vocab, c->l_packed, c->dec_lse, next, nullptr, logprob, s));
   else HIPCHK(c, aigv_launch_lm_head_argmax(c->l_rows, B, H, c->lm_head, k.vocab, c->l_packed, next, nullptr, s));
   HIPCHK(c, aigv_launch_advance(c->dec_pos, c->dec_kvlen, B, s));
   for (int b = 0; b < B; ++b) c->h_kvlen[b] += 1;
@@ -670,6 +674,14 @@ int aigv_decode_step(aigv_ctx* c, const int64_t* ids, int64_t* next, void* strea
 int aigv_decode_step_logprob(aigv_ctx* c, const int64_t* ids, int64_t* next, float* logprob, void* stream) {
   if (!logprob) return fail(c, AIGV_ERR_ARG, "aigv_decode_step_logprob: null argument");
   return decode_step(c, ids, next, logprob, stream);
+}
+
+int aigv_decode_step_cand_logprob(aigv_ctx* c, const int64_t* ids, int64_t* next, float* logprob, const int64_t* cand_ids, int C, float* cand_logprob,
+                                  void* stream) {
+  const char* op = "aigv_decode_step_cand_logprob";
+  if (C < 1 || C > AIGV_MAX_CANDIDATES) return fail(c, AIGV_ERR_ARG, "%s: C = %d candidates outside 1..%d", op, C, AIGV_MAX_CANDIDATES);
+  if (!logprob || !cand_ids || !cand_logprob) return fail(c, AIGV_ERR_ARG, "%s: null argument", op);
+  return decode_step(c, ids, next, logprob, stream, cand_ids, C, cand_logprob);
 }
 
 int aigv_out_row_logits(aigv_ctx* c, int first_row, int n_rows, void* logits_bf16, int ldo, void* stream) {
@@ -708,6 +720,30 @@ int aigv_out_row_logprob(aigv_ctx* c, int first_row, int n_rows, const int64_t* 
     }
     hipError_t e = aigv_launch_label_logprob(c->l_lp, rr, k.vocab, c->lp_ldo, labels + r0, logprob + r0, s);
     if (e != hipSuccess) return fail(c, e == hipErrorInvalidValue ? AIGV_ERR_ARG : AIGV_ERR_HIP, "label log-probabilities (rows=%d): %s", rr, hipGetErrorString(e));
+  }
+  return 0;
+}
+
+int aigv_out_row_cand_logprob(aigv_ctx* c, int first_row, int n_rows, const int64_t* cand_ids, int C, float* cand_logprob, void* stream) {
+  const char* op = "aigv_out_row_cand_logprob";
+  if (C < 1 || C > AIGV_MAX_CANDIDATES) return fail(c, AIGV_ERR_ARG, "%s: C = %d candidates outside 1..%d", op, C, AIGV_MAX_CANDIDATES);
+  if (!c || !cand_ids || !cand_logprob) return fail(c, AIGV_ERR_ARG, "%s: null argument", op);
+  if (!c->finalized) return fail(c, AIGV_ERR_STATE, "%s: call aigv_finalize_weights first", op);
+  const aigv_config& k = c->cfg;
+  const int cap = k.max_out_rows + k.max_seqs + 64;
+  if (first_row < 0 || n_rows <= 0 || first_row + n_rows > cap) return fail(c, AIGV_ERR_ARG, "%s: rows %d..%d outside 0..%d", op, first_row, first_row + n_rows - 1, cap - 1);
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  for (int r0 = 0; r0 < n_rows; r0 += 64) {     // aigv_out_row_logprob's logits (same form, same scratch), read at C columns
+    const int rr = std::min(64, n_rows - r0);
+    {
+      ProfScope ps(c, AIGV_PROF_SKINNY, 2.0 * rr * (double)k.vocab * k.llm_hidden, 2.0 * (double)k.vocab * k.llm_hidden, s);
+      hipError_t e = aigv_launch_lm_head_logits(c->l_rows + (size_t)(first_row + r0) * k.llm_hidden, rr, k.llm_hidden, c->lm_head, k.vocab,
+                                                c->l_lp, c->lp_ldo, s, /*one_form=*/true);
+      if (e != hipSuccess) return fail(c, e == hipErrorInvalidValue ? AIGV_ERR_ARG : AIGV_ERR_HIP, "lm-head logits (rows=%d ldo=%d): %s", rr, c->lp_ldo, hipGetErrorString(e));
+    }
+    hipError_t e = aigv_launch_cand_logprob(c->l_lp, rr, k.vocab, c->lp_ldo, cand_ids, C, cand_logprob + (size_t)r0 * C, s);
+    if (e != hipSuccess) return fail(c, e == hipErrorInvalidValue ? AIGV_ERR_ARG : AIGV_ERR_HIP, "candidate log-probabilities (rows=%d, C=%d): %s", rr, C, hipGetErrorString(e));
   }
   return 0;
 }

@@ -117,7 +117,16 @@ def _frames_of(item):
     return pv[0] if pv.dim() == 5 else pv                  # DataLoader(batch_size=1) adds the leading 1 (stage2_eval.py:932 takes [0])
 
 
-def batched(items, model, k: int = 4, frames=None, ahead: bool = True, pad_id: int = 2, return_logprobs: bool = False):
+def expected_level(cand_logprob, weights=(1, 2, 3, 4, 5)):
+    """The mean quality level of the closed-set distribution over the level words: ``(softmax(cand_logprob, -1) * weights).sum(-1)`` for
+    ``cand_logprob`` [..., C] (``forward(candidate_ids=...)``'s ``cand_logprob`` / ``generate``'s ``cand_logprobs``, the candidates ordered worst to
+    best) - in [weights[0], weights[-1]], NaN where the row is NaN (no answer token there)."""
+    import torch
+    w = torch.as_tensor(weights, dtype=cand_logprob.dtype, device=cand_logprob.device)
+    return (torch.softmax(cand_logprob, -1) * w).sum(-1)
+
+
+def batched(items, model, k: int = 4, frames=None, ahead: bool = True, pad_id: int = 2, return_logprobs: bool = False, candidate_ids=None):
     """The reference's eval loop at batch ``k`` instead of batch 1: yields ``(item, output)`` for EVERY item of ``items`` (the loop's
     ``DataLoader(batch_size=1)`` items: ``input_ids`` / ``attention_mask`` / ``labels`` [1, N_i] with N_i ragged, ``image_flags``
     [1, T, 1], ``pixel_values`` [1, T, 3, S, S] or what ``frames(item)`` returns - uint8 [T, H, W, 3] decoded frames are ingested on the
@@ -138,7 +147,10 @@ def batched(items, model, k: int = 4, frames=None, ahead: bool = True, pad_id: i
     ``items`` may be sharded first (``shard``) so that N ranks score N disjoint shares.
 
     ``return_logprobs``: ``model(..., return_logprobs=True)`` per group; each item's output adds ``logprob`` [N_i - 1] (bit for bit the
-    item's own pass) and its own ``ce_loss``, ``-(logprob[label != -100]).double().mean().float()`` (NaN without answer labels)."""
+    item's own pass) and its own ``ce_loss``, ``-(logprob[label != -100]).double().mean().float()`` (NaN without answer labels).
+
+    ``candidate_ids``: ``model(..., candidate_ids=...)`` per group; each item's output adds ``cand_logprob`` [N_i - 1, C], bit for bit the
+    item's own pass."""
     import torch
     import torch.nn.functional as F
     if k < 1:
@@ -186,7 +198,8 @@ def batched(items, model, k: int = 4, frames=None, ahead: bool = True, pad_id: i
         out = model(mos=None, pixel_values=front, input_ids=torch.stack([pad(i, pad_id) for i in ids]),
                     attention_mask=torch.stack([pad(m, False) for m in masks]), image_flags=flags,
                     labels=torch.stack([pad(l, -100) for l in labels]), **({} if motion is None else {"motion_feature": motion}),
-                    **({"return_logprobs": True} if return_logprobs else {}))
+                    **({"return_logprobs": True} if return_logprobs else {}),
+                    **({} if candidate_ids is None else {"candidate_ids": candidate_ids}))
         return group, n, nmax, out
 
     def collect(run):
@@ -197,11 +210,14 @@ def batched(items, model, k: int = 4, frames=None, ahead: bool = True, pad_id: i
         label = out["label"].view(len(group), nmax - 1).cpu()
         score1 = out["score1"].cpu() if "score1" in out else None
         logprob = out["logprob"].view(len(group), nmax - 1).cpu() if return_logprobs else None
+        cand = out["cand_logprob"].view(len(group), nmax - 1, -1).cpu() if candidate_ids is not None else None
         for b, (it, _) in enumerate(group):
             o = {"logit": logit[b, : n[b] - 1].clone(), "label": label[b, : n[b] - 1].clone()}
             if logprob is not None:
                 o["logprob"] = logprob[b, : n[b] - 1].clone()
                 o["ce_loss"] = (-o["logprob"][o["label"] != -100]).double().mean().float()
+            if cand is not None:
+                o["cand_logprob"] = cand[b, : n[b] - 1].clone()
             if score1 is not None:
                 o["score1"] = score1[b: b + 1].clone()
                 mos = it.get("mos")

@@ -12,7 +12,7 @@ from typing import Dict, Optional, Sequence
 import torch
 
 FLAGS = ("return_dict_in_generate", "output_scores", "output_logits", "return_logprobs")
-FIELDS = ("sequences", "sequences_scores", "scores", "logits", "logprobs")
+FIELDS = ("sequences", "sequences_scores", "scores", "logits", "logprobs", "cand_logprobs")
 
 
 class GenerateOutput(dict):
@@ -24,6 +24,8 @@ class GenerateOutput(dict):
     logits             (output_logits) tuple of T fp32 [B, V]: the raw lm-head logits of each step
     logprobs           (return_logprobs) fp32 [B, T]: log-probability of each emitted token under the distribution it was chosen from
                        (``compute_transition_scores(sequences, scores, normalize_logits=True)``), NaN after the sequence's end token
+    cand_logprobs      (candidate_ids) fp32 [B, T, C]: full-vocabulary log-probability of each candidate token at each step under the RAW
+                       lm-head logits (before logits processors / sampling warpers), NaN after the sequence's end token
     sequences_scores   (beam search) fp32 [B]: HF's length-penalised score of the returned hypothesis
     A field that was not asked for is absent from the keys and reads as None, as in transformers' output classes."""
 
@@ -56,15 +58,25 @@ def token_logprobs(scores: torch.Tensor, tokens: torch.Tensor) -> torch.Tensor:
     return torch.log_softmax(scores.float(), dim=-1).gather(1, tokens.view(-1, 1).long()).view(-1)
 
 
+def candidate_logprobs(raw_logits: torch.Tensor, cand: torch.Tensor) -> torch.Tensor:
+    """fp32 [B, C]: log_softmax(raw_logits.float())[:, cand] over the full vocabulary; a NaN column for an id outside [0, V)."""
+    V = raw_logits.shape[-1]
+    cand = cand.to(raw_logits.device).long()
+    ok = (cand >= 0) & (cand < V)
+    lp = torch.log_softmax(raw_logits.float(), dim=-1).index_select(1, cand.clamp(0, V - 1))
+    return torch.where(ok.view(1, -1), lp, torch.full_like(lp, float("nan")))
+
+
 def mask_after_end(logprob: torch.Tensor, live: Optional[torch.Tensor]) -> torch.Tensor:
-    """A column's log-probabilities with NaN where the sequence had already ended before it (``live`` False; None = all live)."""
+    """A column's log-probabilities ([B] or [B, C]) with NaN where the sequence had already ended before it (``live`` False; None = all live)."""
     if live is None:
         return logprob
-    return torch.where(live, logprob, torch.full_like(logprob, float("nan")))
+    return torch.where(live.view(-1, *([1] * (logprob.dim() - 1))), logprob, torch.full_like(logprob, float("nan")))
 
 
 def build(sequences: torch.Tensor, flags: Dict[str, bool], scores: Sequence[torch.Tensor] = (), logits: Sequence[torch.Tensor] = (),
-          logprobs: Sequence[torch.Tensor] = (), sequences_scores: Optional[torch.Tensor] = None) -> GenerateOutput:
+          logprobs: Sequence[torch.Tensor] = (), sequences_scores: Optional[torch.Tensor] = None,
+          cand_logprobs: Optional[Sequence[torch.Tensor]] = None) -> GenerateOutput:
     """The output object of one generate call; per-step lists are cut to the returned length."""
     T = sequences.shape[1]
     out = GenerateOutput(sequences=sequences)
@@ -75,6 +87,8 @@ def build(sequences: torch.Tensor, flags: Dict[str, bool], scores: Sequence[torc
     if flags["return_logprobs"]:
         lp = list(logprobs[:T])
         out["logprobs"] = torch.stack(lp, dim=1) if lp else torch.empty((sequences.shape[0], 0), dtype=torch.float32, device=sequences.device)
+    if cand_logprobs is not None:       # candidate_ids: T x [B, C] -> [B, T, C]
+        out["cand_logprobs"] = torch.stack(list(cand_logprobs[:T]), dim=1)
     if sequences_scores is not None:
         out["sequences_scores"] = sequences_scores
     return out

@@ -696,7 +696,8 @@ class InternVLChatModel(nn.Module):
                 position_ids=None, image_flags: Optional[torch.Tensor] = None, past_key_values=None,
                 labels: Optional[torch.Tensor] = None, use_cache=None, output_attentions=None,
                 output_hidden_states=None, return_dict=None, motion_feature: Optional[torch.Tensor] = None,
-                visual_tokens: Optional[torch.Tensor] = None, full_logits: bool = False, return_logprobs: bool = False):
+                visual_tokens: Optional[torch.Tensor] = None, full_logits: bool = False, return_logprobs: bool = False,
+                candidate_ids=None):
         """Stage-2 eval pass (modeling_internvl_chat.py:306-488) or, with ``stage=1``, the stage-1 pass
         (internvl_chat_eval1/modeling_internvl_chat.py:250-366).  ``visual_tokens`` optionally supplies
         already all-gathered pre-projector tokens (frame-DP) instead of ``pixel_values``.
@@ -705,7 +706,16 @@ class InternVLChatModel(nn.Module):
         bf16 logits at the shifted label, NaN wherever the label is -100) and ``ce_loss`` (fp32 0-dim: the reference's
         ``CrossEntropyLoss()(shift_logits, shift_labels)``, modeling_internvl_chat.py:452-463 - the mean over the non-ignored labels of the
         batch, NaN when there are none).  Labels must then be -100 or lie in [0, vocab), and no such label may follow a padded position
-        (the reference would score the padded row itself): ValueError otherwise.  ``loss`` (stage 2: L1 against ``mos``) is unchanged."""
+        (the reference would score the padded row itself): ValueError otherwise.  ``loss`` (stage 2: L1 against ``mos``) is unchanged.
+
+        ``candidate_ids`` (LongTensor [C] or list, 1 <= C <= 64 token ids - ``prompts.level_token_ids``) adds ``cand_logprob`` (fp32
+        [B (N - 1), C], rows laid out like ``logit`` / ``logprob``, NaN rows wherever the label is -100): column c is the FULL-vocabulary
+        ``log_softmax(logits.float())[candidate_ids[c]]`` - bit for bit the ``logprob`` the pass gives with ``candidate_ids[c]`` as that
+        row's label - so ``softmax(cand_logprob, -1)`` is the closed-set distribution over the candidates and
+        ``eval_utils.expected_level`` its mean level, from ONE pass.  An id outside [0, vocab) gives a NaN column.  Needs ``labels`` (they
+        say which rows are answer rows) under ``return_logprobs``' label rules, with or without ``return_logprobs``.  The ids are a device
+        input of a replayed graph: other VALUES replay the same graph, another C is another graph.  fp8 mode: the lm-head stays bf16
+        there, so the same kernels serve."""
         if position_ids is not None or past_key_values is not None:
             raise NotImplementedError("the eval pass takes default positions and no cache, like the reference drivers")
         if self.img_context_token_id is None:
@@ -713,7 +723,7 @@ class InternVLChatModel(nn.Module):
         pixel_values, visual_tokens, motion_feature = self._take_ahead(pixel_values, visual_tokens, motion_feature)
         if self._graph_replay_enabled and self._capture_keep is None:
             out = self._forward_through_graph(mos, pixel_values, input_ids, attention_mask, image_flags, labels, motion_feature, visual_tokens, full_logits,
-                                              return_logprobs)
+                                              return_logprobs, candidate_ids)
             if out is not None:
                 return out
         B, N = input_ids.shape
@@ -721,7 +731,8 @@ class InternVLChatModel(nn.Module):
         # ---- index bookkeeping first, on the host (one small D2H copy if the ids live on the device), so that
         # every kernel of the step can then be enqueued back to back without a host sync in between ----
         plan = self._plan(input_ids, attention_mask, labels, image_flags, n_frames, full_logits)
-        lp_labels = self._logprob_labels(plan) if return_logprobs else None
+        cand = self._candidates(candidate_ids, labels)
+        lp_labels = self._logprob_labels(plan) if return_logprobs or cand is not None else None
         motion_feature = self._motion_feature(pixel_values, B, motion_feature)
 
         # ---- device work: ViT -> projector -> motion projector -> LLM pass + heads ----
@@ -730,7 +741,8 @@ class InternVLChatModel(nn.Module):
         score, amax = self._prefill(plan["ids_packed"], plan["slot"], plan["cu"], vit_embeds, plan["n_vis"], motion,
                                     plan["score_rows"], plan["logit_rows"])
         lp = self._row_logprob(B if score is not None else 0, lp_labels) if return_logprobs else None
-        return self._outputs(plan, B, N, score, amax, mos, lp)
+        clp = self._row_cand_logprob(B if score is not None else 0, len(plan["logit_rows"]), cand) if cand is not None else None
+        return self._outputs(plan, B, N, score, amax, mos, lp, clp)
 
     # ---- HIP-graph replay of whole scoring passes (opt-in: enable_graph_replay) ---------------------------------------------------------
     _graph_replay_enabled = False
@@ -865,7 +877,7 @@ class InternVLChatModel(nn.Module):
         return cl(outputs)
 
     def _forward_through_graph(self, mos, pixel_values, input_ids, attention_mask, image_flags, labels, motion_feature, visual_tokens, full_logits,
-                               return_logprobs=False):
+                               return_logprobs=False, candidate_ids=None):
         """The replay path of ``forward``; returns None when the call does not qualify (the eager path then runs)."""
         src = visual_tokens if visual_tokens is not None else pixel_values
         if self._rope_seq_len(int(input_ids.shape[1])) != getattr(self, "_rope_ntk", 0):
@@ -880,14 +892,19 @@ class InternVLChatModel(nn.Module):
                     tuple(None if t is None else (tuple(t.shape), t.dtype, t.numpy().tobytes()) for t in parts))
         if return_logprobs:
             host_key += ("logprobs",)        # (appended only when on: the keys of passes without it are those they always were)
+        cand = self._candidates(candidate_ids, labels)
+        if cand is not None:
+            host_key += ("candidates",)      # (their number is in the key with the device inputs' shapes; their values are graph INPUT)
+            cand = self._h2d(cand)
         self._join_side_stream()             # (a motion feature started by motion_feature_async: joined BEFORE the graph copies it in)
         self._prepare_motion_branch(pixel_values if (motion_feature is None and visual_tokens is None) else None, int(input_ids.shape[0]))
 
-        def fn(src_static, mf_static):
+        def fn(src_static, mf_static, cand_static):
             return self.forward(mos=None, pixel_values=None if visual_tokens is not None else src_static, input_ids=input_ids, attention_mask=attention_mask,
                                 image_flags=image_flags, labels=labels, motion_feature=mf_static, full_logits=full_logits,
-                                visual_tokens=src_static if visual_tokens is not None else None, return_logprobs=return_logprobs)
-        return self._graph_call(host_key, [src, motion_feature], fn)
+                                visual_tokens=src_static if visual_tokens is not None else None, return_logprobs=return_logprobs,
+                                candidate_ids=cand_static)
+        return self._graph_call(host_key, [src, motion_feature, cand], fn)
 
     def dp_front(self, frames_local: torch.Tensor, frames_clips: Optional[torch.Tensor], n_clips: int):
         """The data-parallel scorer's front half on this rank (dist_utils.score_clips_dp): the SlowFast feature of its own clips (side
@@ -1027,7 +1044,7 @@ class InternVLChatModel(nn.Module):
             vit_embeds = vit_embeds[self._h2d(plan["keep"])]
         return vit_embeds.reshape(-1, H), self.motion_embed(motion_feature)
 
-    def _outputs(self, plan, B, N, score, amax, mos, lp=None):
+    def _outputs(self, plan, B, N, score, amax, mos, lp=None, clp=None):
         dev = self.device
         up = self._h2d   # host -> device through pinned memory, never blocking the host (keeps the CPU ahead of the GPU)
         logit = torch.full((B * (N - 1),), -1, dtype=torch.long, device=dev)
@@ -1049,7 +1066,39 @@ class InternVLChatModel(nn.Module):
                 out["ce_loss"] = (-logprob.index_select(0, up(scored))).double().mean().float()
             else:
                 out["ce_loss"] = torch.full((), float("nan"), dtype=torch.float32, device=dev)
+        if clp is not None:                         # candidate_ids: rows scattered like `logit`, NaN rows elsewhere
+            cand_logprob = torch.full((B * (N - 1), clp.shape[1]), float("nan"), dtype=torch.float32, device=dev)
+            if len(plan["logit_rows"]):
+                cand_logprob.index_copy_(0, idx, clp)
+            out["cand_logprob"] = cand_logprob
         return out
+
+    MAX_CANDIDATES = 64      # = AIGV_MAX_CANDIDATES
+
+    @staticmethod
+    def _candidates(candidate_ids, labels="given") -> Optional[torch.Tensor]:
+        """``candidate_ids`` (None, a list of ints or an integer tensor [C], on any device) -> None or a contiguous int64 tensor [C], 1 <= C <= 64.
+        The VALUES are not looked at (they may live on the device): an id outside the vocabulary gives a NaN column."""
+        if candidate_ids is None:
+            return None
+        if labels is None:
+            raise ValueError("candidate_ids: needs labels (they mark the answer rows whose distribution is read)")
+        t = candidate_ids if torch.is_tensor(candidate_ids) else torch.tensor([int(v) for v in candidate_ids], dtype=torch.long)
+        if t.dim() != 1 or t.is_floating_point() or t.dtype == torch.bool or not 1 <= t.numel() <= InternVLChatModel.MAX_CANDIDATES:
+            raise ValueError(f"candidate_ids: expected 1..{InternVLChatModel.MAX_CANDIDATES} integer token ids in one dimension, got "
+                             f"{tuple(t.shape)} {t.dtype}")
+        return t.to(torch.long).contiguous()
+
+    def _row_cand_logprob(self, first_row: int, R: int, cand: torch.Tensor) -> torch.Tensor:
+        """fp32 [R, C] candidate log-probabilities of consumed rows first_row .. first_row + R - 1 of the last native pass
+        (aigv_out_row_cand_logprob); no host sync, no allocation inside the library (the pass may be captured)."""
+        C_ = int(cand.numel())
+        out = torch.empty((max(R, 1), C_), dtype=torch.float32, device=self.device)
+        if R:
+            lib, ctx = native.load(), self._ctx
+            cand_d = self._h2d(cand)
+            native.check(lib.aigv_out_row_cand_logprob(ctx, int(first_row), R, cand_d.data_ptr(), C_, out.data_ptr(), native.stream_ptr()), ctx)
+        return out[:R]
 
     def _logprob_labels(self, plan) -> torch.Tensor:
         """Host int64 labels of the pass's consumed rows (in ``logit_rows`` order), checked first as torch's cross entropy would."""
@@ -1101,7 +1150,7 @@ class InternVLChatModel(nn.Module):
 
     def forward_shared_prefix(self, prompts, pixel_values: Optional[torch.Tensor] = None, image_flags: Optional[torch.Tensor] = None,
                               motion_feature: Optional[torch.Tensor] = None, visual_tokens: Optional[torch.Tensor] = None, mos=None,
-                              return_logprobs: bool = False):
+                              return_logprobs: bool = False, candidate_ids=None):
         """Score the same clips under several prompts that share their beginning - the reference's four quality
         perspectives ask four questions BEHIND the same system + frame + motion tokens (8f-3) and
         run four full passes (stage2_eval.py evaluates one jsonl per perspective).  Here the common prefix runs once
@@ -1110,7 +1159,8 @@ class InternVLChatModel(nn.Module):
         labels)``; returns the list of ``forward`` result dicts, one per prompt.  Causal attention makes the prefix rows
         independent of what follows, so each result is that of a separate ``forward`` call up to kernel summation order.
         ``return_logprobs``: every prompt's dict carries ``logprob`` and ``ce_loss`` as ``forward`` defines them - with candidate answers
-        as the prompts, their log-likelihoods behind one video prefix (README)."""
+        as the prompts, their log-likelihoods behind one video prefix (README).  ``candidate_ids``: every prompt's dict carries
+        ``cand_logprob`` as ``forward`` defines it (the same candidates for every prompt)."""
         if self.img_context_token_id is None:
             raise AssertionError("img_context_token_id must be set by the caller (stage2_eval.py:810)")
         if not prompts:
@@ -1118,7 +1168,8 @@ class InternVLChatModel(nn.Module):
         pixel_values, visual_tokens, motion_feature = self._take_ahead(pixel_values, visual_tokens, motion_feature)
         n_frames = visual_tokens.shape[0] if visual_tokens is not None else pixel_values.shape[0]
         plans = [self._plan(ids, am, lab, image_flags, n_frames) for (ids, am, lab) in prompts]
-        lp_labels = [self._logprob_labels(pl) for pl in plans] if return_logprobs else None
+        cand = self._candidates(candidate_ids)
+        lp_labels = [self._logprob_labels(pl) for pl in plans] if return_logprobs or cand is not None else None
         B = prompts[0][0].shape[0]
         pre = self._shared_prefix_lengths(plans, B)
         p0 = plans[0]
@@ -1164,10 +1215,12 @@ class InternVLChatModel(nn.Module):
                                          native.i32_array(lrows) if lrows else None, len(lrows), amax.data_ptr(), 0,
                                          native.stream_ptr()), ctx)
         lp = self._row_logprob(len(srows), torch.cat(lp_labels)) if return_logprobs else None   # rows [score rows | logit rows]
+        clp = self._row_cand_logprob(len(srows), len(lrows), cand) if cand is not None else None
         outs, off = [], 0
         for p, (pl, (ids, _, _)) in enumerate(zip(plans, prompts)):
             outs.append(self._outputs(pl, B, ids.shape[1], score[p * B:(p + 1) * B] if score is not None else None,
-                                      amax[off:off + n_l[p]], mos, lp[off:off + n_l[p]] if lp is not None else None))
+                                      amax[off:off + n_l[p]], mos, lp[off:off + n_l[p]] if lp is not None else None,
+                                      clp[off:off + n_l[p]] if clp is not None else None))
             off += n_l[p]
         return outs
 
@@ -1175,7 +1228,7 @@ class InternVLChatModel(nn.Module):
     EOS_CHECK_EVERY = 8     # tokens between two host reads of the device-side "finished" flags
 
     def _greedy(self, ids_packed, slot, cu, vis, n_vis, max_new_tokens: int, eos_ids: List[int], pad_id: int, motion=None, sampler=None,
-                processors=None, beams=None, flags=None):
+                processors=None, beams=None, flags=None, cand=None):
         """The token loop of generate(): HF's greedy search / multinomial sampling loop (the reference calls ``language_model.generate``,
         modeling_internvl_chat.py:798-809).  The end-of-sequence bookkeeping runs on the device (aigv_decode_eos): a finished sequence
         emits ``pad_id``, the loop stops once every sequence has emitted an end token - checked by the host only every EOS_CHECK_EVERY
@@ -1184,10 +1237,14 @@ class InternVLChatModel(nn.Module):
         ``flags`` (generation.output_flags): with return_dict_in_generate / return_logprobs the result is a generation.GenerateOutput.  Greedy
         decoding without processors takes its log-probabilities from the decode step's fused lm-head (aigv_decode_step_logprob; the first
         token's from aigv_out_row_logprob) and never builds a [B, V] tensor; wherever the step's logits are materialised (processors,
-        sampling, output_scores / output_logits) they come from the scores the token was chosen from."""
+        sampling, output_scores / output_logits) they come from the scores the token was chosen from.
+
+        ``cand`` (int64 [C], ``candidate_ids``): ``cand_logprobs`` [B, T, C], the full-vocabulary log-probabilities of the candidates at every
+        step - from the fused decode step (aigv_decode_step_cand_logprob; the first token's from aigv_out_row_cand_logprob) on the greedy
+        path without processors, else the log-softmax of the step's RAW logits (before processors and warpers) at the candidates."""
         from . import generation
         flags = flags or {k: False for k in generation.FLAGS}
-        dict_out = generation.wants_output(flags)
+        dict_out = generation.wants_output(flags) or cand is not None
         b = len(cu) - 1
         longest = max(cu[i + 1] - cu[i] for i in range(b))
         last_rows = [cu[i + 1] - 1 for i in range(b)]
@@ -1215,6 +1272,10 @@ class InternVLChatModel(nn.Module):
         step_logits: List[torch.Tensor] = []
         step_lp: List[torch.Tensor] = []
         cur_lp: List[Optional[torch.Tensor]] = [None]      # log-probability of the current raw token (before the end-of-sequence rule)
+        step_clp: List[torch.Tensor] = []
+        cur_clp: List[Optional[torch.Tensor]] = [None]     # [b, C] candidate log-probabilities of the current step
+        n_cand = 0 if cand is None else int(cand.numel())
+        cand_d = None if cand is None else self._h2d(cand)
 
         def eos_step(tok):
             live = state[:b] == 0
@@ -1244,14 +1305,18 @@ class InternVLChatModel(nn.Module):
                 step_scores.append(logits)
             if want_lp:
                 cur_lp[0] = generation.token_logprobs(logits, tok)
+            if cand_d is not None:
+                cur_clp[0] = generation.candidate_logprobs(raw, cand_d)
             return tok
 
         tok = pick(nxt).contiguous()
         if want_lp and not materialise:     # the first token: the prompt pass's rows, once per call
             cur_lp[0] = torch.empty(b, dtype=torch.float32, device=self.device)
             native.check(lib.aigv_out_row_logprob(ctx, 0, b, tok.data_ptr(), cur_lp[0].data_ptr(), native.stream_ptr()), ctx)
+        if cand_d is not None and not materialise:
+            cur_clp[0] = self._row_cand_logprob(0, b, cand_d)
         for step in range(max_new_tokens):
-            if want_lp:
+            if want_lp or cand_d is not None:
                 live = None if not eos_ids else (state[:b] == 0)
             if host_eos:
                 tok = eos_step(tok).contiguous()
@@ -1260,6 +1325,8 @@ class InternVLChatModel(nn.Module):
             outs.append(tok)
             if want_lp:
                 step_lp.append(generation.mask_after_end(cur_lp[0], live))
+            if cand_d is not None:
+                step_clp.append(generation.mask_after_end(cur_clp[0], live))
             if step + 1 == max_new_tokens:
                 break
             if eos_ids and (step + 1) % self.EOS_CHECK_EVERY == 0 and bool(state[:b].all()):
@@ -1267,7 +1334,12 @@ class InternVLChatModel(nn.Module):
             new = torch.empty_like(tok)
             if ntk_decode:
                 self._rope_for_decode(longest + step + 1)
-            if want_lp and not materialise:
+            if cand_d is not None and not materialise:      # one lm-head pass: token, its log-probability and the candidates'
+                cur_lp[0] = torch.empty(b, dtype=torch.float32, device=self.device)
+                cur_clp[0] = torch.empty((b, n_cand), dtype=torch.float32, device=self.device)
+                native.check(lib.aigv_decode_step_cand_logprob(ctx, tok.data_ptr(), new.data_ptr(), cur_lp[0].data_ptr(), cand_d.data_ptr(), n_cand,
+                                                               cur_clp[0].data_ptr(), native.stream_ptr()), ctx)
+            elif want_lp and not materialise:
                 cur_lp[0] = torch.empty(b, dtype=torch.float32, device=self.device)
                 native.check(lib.aigv_decode_step_logprob(ctx, tok.data_ptr(), new.data_ptr(), cur_lp[0].data_ptr(), native.stream_ptr()), ctx)
             else:
@@ -1277,7 +1349,8 @@ class InternVLChatModel(nn.Module):
         if eos_ids:
             out = out[:, : max(1, int(state[b].item()))]     # HF stops after the column in which the last live sequence ended
         if dict_out:
-            return generation.build(out, flags, scores=step_scores, logits=step_logits, logprobs=step_lp)
+            return generation.build(out, flags, scores=step_scores, logits=step_logits, logprobs=step_lp,
+                                    cand_logprobs=step_clp if cand_d is not None else None)
         return out
 
     def _beam_decode(self, b: int, prompt_lens: List[int], max_new_tokens: int, eos_ids: List[int], pad_id, processors, num_beams: int,
@@ -1356,14 +1429,14 @@ class InternVLChatModel(nn.Module):
         return int(cfg.get("max_new_tokens") or 20), eos, cfg.get("pad_token_id"), sampler, processors, beams
 
     @staticmethod
-    def _gen_flags(generation_config, kw, beams=None):
+    def _gen_flags(generation_config, kw, beams=None, cand=None):
         """HF's output flags (return_dict_in_generate, output_scores, output_logits) and return_logprobs from a generation config / kwargs
         (generation.output_flags).  Beam search returns ``sequences_scores`` only: per-step scores, logits and log-probabilities of its
         hypotheses are not implemented and raise."""
         from . import generation
         flags = generation.output_flags(generation_config, kw)
         if beams:
-            asked = [k for k in ("output_scores", "output_logits", "return_logprobs") if flags[k]]
+            asked = [k for k in ("output_scores", "output_logits", "return_logprobs") if flags[k]] + (["candidate_ids"] if cand is not None else [])
             if asked:
                 raise NotImplementedError(f"beam search (num_beams > 1) returns sequences and sequences_scores only: {', '.join(asked)} "
                                           "not implemented")
@@ -1454,10 +1527,17 @@ class InternVLChatModel(nn.Module):
         """modeling_internvl_chat.py:769-811: every <IMG_CONTEXT> slot takes a visual token (no motion
         token), then greedy decode with a KV cache.  Returns the NEW tokens [B, <=max_new_tokens] - or, with HF's
         ``return_dict_in_generate`` (``output_scores`` / ``output_logits``) or ``return_logprobs``, a generation.GenerateOutput
-        (``sequences``, ``scores``, ``logits``, ``logprobs``; beam search: ``sequences_scores``)."""
+        (``sequences``, ``scores``, ``logits``, ``logprobs``; beam search: ``sequences_scores``).
+
+        ``candidate_ids`` (LongTensor [C] or list, 1 <= C <= 64): the output object also carries ``cand_logprobs`` fp32 [B, T, C], the
+        full-vocabulary log-probability of every candidate token at every step under the RAW lm-head logits (before logits processors and
+        sampling warpers), NaN after a sequence's end token like ``logprobs``; ``softmax(cand_logprobs[:, t], -1)`` is the closed-set
+        distribution at step t.  Greedy decoding without processors reads them in the decode step's own lm-head pass
+        (aigv_decode_step_cand_logprob); beam search refuses them.  fp8 mode: the lm-head stays bf16, the same kernels serve."""
         assert self.img_context_token_id is not None
+        cand = self._candidates(generate_kwargs.pop("candidate_ids", None))
         max_new, eos, pad, sampler, procs, beams = self._gen_args(generation_config, generate_kwargs)
-        flags = self._gen_flags(generation_config, generate_kwargs, beams)
+        flags = self._gen_flags(generation_config, generate_kwargs, beams, cand)
         pad = self.config.llm_config.pad_token_id if pad is None else pad
         dev = self.device
         input_ids = input_ids.to(dev)
@@ -1473,14 +1553,15 @@ class InternVLChatModel(nn.Module):
             if int(sel.sum()) != n_vis:
                 raise ValueError(f"visual token count mismatch: {int(sel.sum())} slots vs {n_vis} tokens")
             slot[sel] = torch.arange(n_vis, device=dev, dtype=torch.int32)
-        return self._greedy(ids_packed, slot, cu, vis, n_vis, max_new, eos, pad, sampler=sampler, processors=procs, beams=beams, flags=flags)
+        return self._greedy(ids_packed, slot, cu, vis, n_vis, max_new, eos, pad, sampler=sampler, processors=procs, beams=beams, flags=flags, cand=cand)
 
     @torch.no_grad()
     def generate2(self, input_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, visual_features=None,
                   generation_config=None, output_hidden_states=None, return_dict=None, **generate_kwargs) -> torch.Tensor:
-        """modeling_internvl_chat.py:812-853: decode from precomputed input embeddings [B, N, C].  Output flags as ``generate``."""
+        """modeling_internvl_chat.py:812-853: decode from precomputed input embeddings [B, N, C].  Output flags and ``candidate_ids`` as ``generate``."""
+        cand = self._candidates(generate_kwargs.pop("candidate_ids", None))
         max_new, eos, pad, sampler, procs, beams = self._gen_args(generation_config, generate_kwargs)
-        flags = self._gen_flags(generation_config, generate_kwargs, beams)
+        flags = self._gen_flags(generation_config, generate_kwargs, beams, cand)
         pad = self.config.llm_config.pad_token_id if pad is None else pad
         dev = self.device
         b, n, _ = input_embeds.shape
@@ -1493,7 +1574,7 @@ class InternVLChatModel(nn.Module):
         T = emb.shape[0]
         ids = torch.zeros(T, dtype=torch.long, device=dev)
         slot = torch.arange(T, dtype=torch.int32, device=dev)          # every row comes from `emb`
-        return self._greedy(ids, slot, cu, emb, T, max_new, eos, pad, sampler=sampler, processors=procs, beams=beams, flags=flags)
+        return self._greedy(ids, slot, cu, emb, T, max_new, eos, pad, sampler=sampler, processors=procs, beams=beams, flags=flags, cand=cand)
 
     @torch.no_grad()
     def generate_stage2(self, pixel_values, input_ids, attention_mask=None, image_flags=None, motion_feature=None,
@@ -1504,8 +1585,9 @@ class InternVLChatModel(nn.Module):
         token / visual / motion rows - no embedding tensor is assembled on the host side."""
         if self.img_context_token_id is None:
             raise AssertionError("img_context_token_id must be set (stage2_eval.py:810)")
+        cand = self._candidates(generate_kwargs.pop("candidate_ids", None))
         max_new, eos, pad, sampler, procs, beams = self._gen_args(generation_config, generate_kwargs)
-        flags = self._gen_flags(generation_config, generate_kwargs, beams)
+        flags = self._gen_flags(generation_config, generate_kwargs, beams, cand)
         pad = self.config.llm_config.pad_token_id if pad is None else pad
         B = input_ids.shape[0]
         plan = self._plan(input_ids, attention_mask, None, image_flags, pixel_values.shape[0], drop_dead_tail=False)
@@ -1513,7 +1595,7 @@ class InternVLChatModel(nn.Module):
         self._native(n_frames=pixel_values.shape[0], n_tokens=plan["cu"][-1], n_clips=B)
         vit_embeds, motion = self._visual_inputs(pixel_values, None, motion_feature, plan)
         return self._greedy(plan["ids_packed"], plan["slot"], plan["cu"], vit_embeds, plan["n_vis"], max_new, eos, pad, motion=motion, sampler=sampler, processors=procs, beams=beams,
-                            flags=flags)
+                            flags=flags, cand=cand)
 
     def chat2(self, tokenizer, pixel_values, input_ids, generation_config, attention_mask, history=None,
               return_history=False, image_flags=None, IMG_START_TOKEN="<img>", IMG_END_TOKEN="</img>",

@@ -86,3 +86,33 @@ def batch_inputs(samples: Sequence[Dict[str, torch.Tensor]], pad_token_id: int =
         k = int(s["input_ids"].numel())
         ids[i, :k], labels[i, :k], mask[i, :k] = s["input_ids"], s["labels"], True
     return {"input_ids": ids, "labels": labels, "attention_mask": mask}
+
+
+def level_token_ids(tokenizer, words: Sequence[str] = ("bad", "poor", "fair", "good", "excellent"),
+                    template: str = "The quality of the video is {}.") -> List[int]:
+    """The candidate token ids of the quality levels for ``forward(candidate_ids=...)`` / ``generate(candidate_ids=...)``: every word is put
+    into the answer ``template`` and tokenised IN CONTEXT (a SentencePiece vocabulary tokenises a word differently behind a space); the id
+    returned for a word is its token at the first position where the candidates' tokenisations differ - the token whose distribution
+    tells the levels apart.  Raises ValueError when two words share that token (multi-token words with a common first piece: score the
+    candidate answers with ``forward_shared_prefix`` instead, README) or when the template has no ``{}``."""
+    if "{}" not in template:
+        raise ValueError("level_token_ids: the template needs a {} for the level word")
+    if len(words) < 1:
+        raise ValueError("level_token_ids: no level words")
+    rows = [list(tokenizer(template.format(w)).input_ids) for w in words]
+    n = min(len(r) for r in rows)
+    pos = next((i for i in range(n) if any(r[i] != rows[0][i] for r in rows)), None)
+    if pos is None:
+        if len(words) > 1:
+            raise ValueError(f"level_token_ids: the tokenisations of {list(words)} do not differ within their first {n} tokens")
+        bare = list(tokenizer(template.format("")).input_ids)      # one word: the first token the word itself brings in
+        pos = next((i for i in range(min(n, len(bare))) if rows[0][i] != bare[i]), None)
+        if pos is None:
+            raise ValueError(f"level_token_ids: {words[0]!r} adds no token of its own to the template")
+    ids = [int(r[pos]) for r in rows]
+    for i, a in enumerate(ids):
+        for j in range(i):
+            if ids[j] == a:
+                raise ValueError(f"level_token_ids: {words[j]!r} and {words[i]!r} share their first distinguishing token {a}; score the whole "
+                                 "candidate answers instead (forward_shared_prefix)")
+    return ids

@@ -34,8 +34,13 @@ extern "C" {
 #endif
 
 #define AIGV_ABI_VERSION 3   /* 2: aigv_out_row_logprob, aigv_op_label_logprob; 3: the decode-step operators (aigv_op_attention_decode ...),
-                                later joined by aigv_decode_step_logprob and aigv_op_lm_head_argmax_logprob (added symbols only: a library
-                                without them is refused at load time, "missing <name>") */
+                                later joined by aigv_decode_step_logprob and aigv_op_lm_head_argmax_logprob, then by the candidate-token
+                                log-probabilities (aigv_out_row_cand_logprob, aigv_decode_step_cand_logprob, aigv_op_cand_logprob,
+                                aigv_op_lm_head_argmax_cand_logprob) - added symbols only: a library without them is refused at load
+                                time, "missing <name>" */
+
+/* Most candidate token ids one candidate log-probability call takes. */
+#define AIGV_MAX_CANDIDATES 64
 
 /* Largest aigv_config.kv_capacity a context accepts (tokens per clip): the decode attention's merge pass holds 16 bytes of LDS per
  * 128-key chunk of the capacity (32 KB at this bound). */
@@ -201,6 +206,14 @@ int aigv_decode_step(aigv_ctx* ctx, const int64_t* ids, int64_t* next, void* str
  * context workspace, merged in a fixed order: a sequence's bits do not depend on its batch mates); next is aigv_decode_step's, bit for bit.
  * Nothing is allocated here, so the call may be captured. */
 int aigv_decode_step_logprob(aigv_ctx* ctx, const int64_t* ids, int64_t* next, float* logprob, void* stream);
+/* aigv_decode_step_logprob plus the log-probabilities of C chosen tokens at every step: cand_logprob[b, c] = log_softmax(logits.float())
+ * [cand_ids[c]] over the FULL vocabulary (DEVICE fp32 [B, C]; cand_ids: DEVICE int64 [C], 1 <= C <= AIGV_MAX_CANDIDATES; an id outside
+ * [0, vocab) gives a NaN column).  The log-sum-exp is the one `logprob` uses; the C logits come from a second, tiny GEMV over just those C
+ * rows of the lm-head weight (ceil16(C) x hidden x 2 extra weight bytes per step) whose arithmetic gives each column the bits the lm-head
+ * itself rounds for it - a candidate that is the step's argmax carries logprob[b], bit for bit.  next / logprob are
+ * aigv_decode_step_logprob's bits.  Nothing is allocated here, so the call may be captured. */
+int aigv_decode_step_cand_logprob(aigv_ctx* ctx, const int64_t* ids, int64_t* next, float* logprob, const int64_t* cand_ids, int C,
+                                  float* cand_logprob, void* stream);
 /* The full next-token distribution of the rows the last aigv_llm_prefill / aigv_llm_extend / aigv_decode_step consumed: lm-head
  * logits of their final hidden states (kept in the context, in the order [score rows | logit rows]; a decode step keeps its
  * n_clips rows) as the bf16 values the reference upcasts with .float() (modeling_internlm2.py:1095-1096).
@@ -220,6 +233,12 @@ int aigv_out_row_hidden(aigv_ctx* ctx, int first_row, int n_rows, void* hidden_b
  * fixed order.  labels: DEVICE int64 [n_rows]; a label outside [0, vocab) (-100 included) gives NaN.  logprob: DEVICE fp32 [n_rows].
  * Rows in the order [score rows | logit rows], as aigv_out_row_logits. */
 int aigv_out_row_logprob(aigv_ctx* ctx, int first_row, int n_rows, const int64_t* labels, float* logprob, void* stream);
+/* Candidate-token log-probabilities of the same rows: cand_logprob[i, c] = log_softmax(logits.float())[cand_ids[c]] of row first_row + i
+ * over the FULL vocabulary - aigv_out_row_logprob's logits, scratch, arithmetic and log-sum-exp, read at C columns, so column c holds the
+ * bits aigv_out_row_logprob gives with labels = cand_ids[c] and a row's bits depend on neither n_rows nor C.  cand_ids: DEVICE int64 [C],
+ * 1 <= C <= AIGV_MAX_CANDIDATES (the first answer tokens of the quality-level words: softmax over the C columns is the closed-set
+ * level distribution); an id outside [0, vocab) gives a NaN column.  cand_logprob: DEVICE fp32 [n_rows, C].  Nothing is allocated here. */
+int aigv_out_row_cand_logprob(aigv_ctx* ctx, int first_row, int n_rows, const int64_t* cand_ids, int C, float* cand_logprob, void* stream);
 /* End-of-sequence bookkeeping of generate()'s token loop on the device (the reference defers to HF's loop: next = next * unfinished +
  * pad * (1 - unfinished); unfinished &= next not in eos_token_id; stop when every sequence has finished - modeling_internvl_chat.py:
  * 798-809).  tokens: DEVICE int64[n] (n = sequences of the kept KV state), in: the step's raw tokens (aigv_decode_step's `next`, or the
@@ -306,6 +325,17 @@ int64_t aigv_op_lm_head_argmax_logprob_scratch_bytes(int rows, int vocab);   /* 
 /* The log-softmax of aigv_out_row_logprob on caller-supplied bf16 logits [rows, ldo >= vocab]: out[r] = fp32 log_softmax(logits[r, :vocab])
  * [labels[r]], NaN where labels[r] is outside [0, vocab).  One workgroup per row; the bits of a row do not depend on `rows`. */
 int aigv_op_label_logprob(const void* logits_bf16, int rows, int vocab, int ldo, const int64_t* labels, float* out, void* stream);
+/* aigv_op_label_logprob at C columns: out[r, c] = fp32 log_softmax(logits[r, :vocab])[cand_ids[c]] (out: DEVICE fp32 [rows, C]; cand_ids:
+ * DEVICE int64 [C], 1 <= C <= AIGV_MAX_CANDIDATES; NaN columns for ids outside [0, vocab)).  Column c holds aigv_op_label_logprob's bits
+ * for labels = cand_ids[c]; they depend on neither `rows`, C nor the candidates' order. */
+int aigv_op_cand_logprob(const void* logits_bf16, int rows, int vocab, int ldo, const int64_t* cand_ids, int C, float* out, void* stream);
+/* The lm-head of aigv_decode_step_cand_logprob: aigv_op_lm_head_argmax_logprob (idx / val / logprob: its bits, its argument rules) plus
+ * cand_logprob[r, c] = bf16 lm-head logit of column cand_ids[c] - the row's log-sum-exp (DEVICE fp32 [rows, C]).  scratch: DEVICE memory
+ * of aigv_op_lm_head_argmax_cand_logprob_scratch_bytes(rows, vocab) bytes. */
+int aigv_op_lm_head_argmax_cand_logprob(const void* h, int rows, int hidden, const void* W, int vocab, const int64_t* cand_ids, int C,
+                                        void* scratch, int64_t scratch_bytes, int64_t* idx, float* val, float* logprob, float* cand_logprob,
+                                        void* stream);
+int64_t aigv_op_lm_head_argmax_cand_logprob_scratch_bytes(int rows, int vocab);   /* -1 for arguments the op refuses */
 
 /* ---- the kernels of aigv_decode_step, one by one (parity tests; ABI 3) ----------------------------------------------------------------
  * Every pointer is DEVICE memory; the arguments are checked on the host before anything is launched (AIGV_ERR_ARG with a message
