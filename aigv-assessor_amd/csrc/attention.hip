@@ -138,6 +138,9 @@ __global__ __launch_bounds__(NW * 64, (D == 64 && NW == 4) ? 4 : 2) void attn_fw
   // query slice and every NW-th key tile each; their softmax states are merged through LDS at the end (key split).
   const bool ksplit = !CAUSAL && NW == 4 && p.q_tail == 0 && (len - q0) <= 32;   // (NW = 4: three published states fit the ring)
   const int qw = ksplit ? q0 : q0 + wave * 32;    // first query row of this wave
+  // last-layer row trimming inside a block that runs: a wave whose 32 rows all lie in front of the consumed ones stages its share of every
+  // tile and joins the barriers, but computes nothing and writes nothing
+  const bool trimmed = p.q_tail > 0 && qw + 32 <= len - p.q_tail;
 
   // ---- Q^T fragments: lane (c,h) holds Q[qw+c][16*ks + 8h + j] --------------------------------------
   // Prologue order: the query rows (and their rotary rows) are REQUESTED first, then the first K/V tiles' LDS-DMA goes out, and only
@@ -275,7 +278,7 @@ __global__ __launch_bounds__(NW * 64, (D == 64 && NW == 4) ? 4 : 2) void attn_fw
     // wave-uniform skips: tiles entirely in this wave's causal future; waves whose 32 query rows all lie past the sequence
     // (1025 = 8 x 128 + 1 rows per ViT frame: three of the last workgroup's four waves).  Such a wave still stages its share
     // of every tile and joins the barriers, but leaves its SIMD's issue slots to the co-resident workgroups.
-    const bool skip = (CAUSAL && key0 > qw + 31 + kv_off) || (qw >= len || (p.q_tail > 0 && qw + 32 <= len - p.q_tail)) || (ksplit && (kt % NW) != wave);
+    const bool skip = (CAUSAL && key0 > qw + 31 + kv_off) || (qw >= len || trimmed) || (ksplit && (kt % NW) != wave);
     // The LDS-DMA requests of tile kt + NB - 1.  d = 128: not in one burst behind the barrier (the stamps priced that burst at 11 % of a
     // wave's lifetime: eight 1-KB requests queue at the CU's address unit) but one behind every second MFMA of S^T = K Q^T; a wave that
     // skips the tile, and the ragged last tile of a sequence, keep the burst.  d = 64 (half the requests, half the MFMAs to hide them
@@ -549,7 +552,7 @@ __global__ __launch_bounds__(NW * 64, (D == 64 && NW == 4) ? 4 : 2) void attn_fw
 
   // ---- normalise and store: lane (c,h) owns O[qw+c][32*dt + 8*(e>>2) + 4h + (e&3)] -------------------------
   const int qr = qw + c;
-  if (qr < len) {
+  if (qr < len && !trimmed) {
     const float inv = l_run > 0.f ? 1.0f / l_run : 0.f;
     bf16_t* op = p.o + (size_t)(row0 + qr) * p.ldo + (size_t)hq * D;
 #pragma unroll

@@ -141,6 +141,49 @@ int aigv_op_attention_rope(const void* q, int ldq, const void* k, int ldk, const
   return 0;
 }
 
+// ---- the address and mask forms of the prefill attention that the scoring passes use (test entry points): checked here, before any HIP call ----
+// AttnArgs as llm_attn_args + the call sites of aigv_llm_prefill (packed K/V, q_tail) and aigv_llm_extend (K/V in the cache, kv_off) fill them.
+int aigv_op_attention_ex(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, const int32_t* cu, int n_seq,
+                         int max_len, int n_heads, int n_kv_heads, int q_group_stride, int kv_head_stride, int64_t kv_seq_stride,
+                         const int32_t* kv_off, int head_dim, int causal, float post_div, float q_prescale, const int32_t* pos, const void* cos,
+                         const void* sin, int pos_is_row, int q_tail, void* stream) {
+  const char* op = "aigv_op_attention_ex";
+  if (!q || !k || !v || !o || !cu) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+  if (q_tail < 0) return fail(nullptr, AIGV_ERR_ARG, "%s: q_tail = %d must not be negative", op, q_tail);
+  if (kv_seq_stride < 0) return fail(nullptr, AIGV_ERR_ARG, "%s: kv_seq_stride = %lld must not be negative", op, (long long)kv_seq_stride);
+  if (kv_off && !kv_seq_stride) return fail(nullptr, AIGV_ERR_ARG, "%s: a key offset needs K/V in cache layout (kv_seq_stride)", op);
+  if (pos_is_row && !cos) return fail(nullptr, AIGV_ERR_ARG, "%s: pos_is_row selects how the query RoPE finds its position: it needs cos and sin", op);
+  AttnArgs a{};
+  a.q = (const bf16_t*)q; a.ldq = ldq; a.k = (const bf16_t*)k; a.ldk = ldk; a.v = (const bf16_t*)v; a.ldv = ldv;
+  a.o = (bf16_t*)o; a.ldo = ldo; a.cu = cu; a.n_seq = n_seq; a.max_len = max_len; a.n_heads = n_heads;
+  a.n_kv_heads = n_kv_heads; a.q_group_stride = q_group_stride; a.kv_head_stride = kv_head_stride;
+  a.kv_seq_stride = (size_t)kv_seq_stride; a.kv_off = kv_off;
+  a.causal = causal & 1; a.uniform_len = (causal >> 1) & 1; a.post_div = post_div; a.q_prescale = q_prescale;
+  a.round_scores = (causal >> 2) & 1; a.lead_key = (causal >> 3) & 1; a.waves = g_tune[AIGV_TUNE_ATTN_WAVES];
+  a.rope_pos = pos; a.rope_cos = (const bf16_t*)cos; a.rope_sin = (const bf16_t*)sin;
+  a.rope_pos_is_row = pos_is_row ? 1 : 0;
+  a.q_tail = q_tail;
+  if (const char* m = aigv_attn_check(a, head_dim)) return fail(nullptr, AIGV_ERR_ARG, "%s: %s", op, m);
+  HIPCHK(nullptr, aigv_launch_attention(a, head_dim, (hipStream_t)stream));
+  return 0;
+}
+
+// K / V slots of fused qkv rows -> the KV cache [seq][kv head][cap][head_dim]: the kernel aigv_llm_prefill (keep_kv) and aigv_llm_extend append with
+int aigv_op_kv_store(const void* qkv, int ld, const int32_t* seq, const int32_t* pos, void* kc, void* vc, int tokens, int n_kv, int g,
+                     int head_dim, int cap, void* stream) {
+  const char* op = "aigv_op_kv_store";
+  if (!qkv || !seq || !pos || !kc || !vc) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+  if (tokens < 0) return fail(nullptr, AIGV_ERR_ARG, "%s: tokens = %d must not be negative", op, tokens);
+  if (g < 1 || g > 8 || n_kv < 1) return fail(nullptr, AIGV_ERR_ARG, "%s: g = %d query heads per KV head (1..8), n_kv = %d (>= 1)", op, g, n_kv);
+  if (head_dim < 8 || head_dim % 8) return fail(nullptr, AIGV_ERR_ARG, "%s: head_dim = %d is not a positive multiple of 8", op, head_dim);
+  if (cap < 1 || cap > AIGV_MAX_KV_CAPACITY) return fail(nullptr, AIGV_ERR_ARG, "%s: cap = %d outside 1..%d", op, cap, AIGV_MAX_KV_CAPACITY);
+  if (ld % 8 || (int64_t)ld < (int64_t)n_kv * (g + 2) * head_dim)
+    return fail(nullptr, AIGV_ERR_ARG, "%s: bad leading dimension (ld %d, needs a multiple of 8 and >= n_kv (g + 2) head_dim)", op, ld);
+  if (((uintptr_t)qkv & 15) || ((uintptr_t)kc & 15) || ((uintptr_t)vc & 15)) return fail(nullptr, AIGV_ERR_ARG, "%s: qkv and the caches must be 16-byte aligned", op);
+  HIPCHK(nullptr, aigv_launch_kv_store((const bf16_t*)qkv, ld, seq, pos, (bf16_t*)kc, (bf16_t*)vc, tokens, n_kv, g, head_dim, cap, (hipStream_t)stream));
+  return 0;
+}
+
 int aigv_op_pixel_shuffle(const void* vit_out, int grid, int vit_hidden, void* out, int n_frames, void* stream) {
   HIPCHK(nullptr, aigv_launch_pixel_shuffle((const bf16_t*)vit_out, grid, vit_hidden, (bf16_t*)out, n_frames, (hipStream_t)stream));
   return 0;

@@ -36,7 +36,8 @@ extern "C" {
 #define AIGV_ABI_VERSION 3   /* 2: aigv_out_row_logprob, aigv_op_label_logprob; 3: the decode-step operators (aigv_op_attention_decode ...),
                                 later joined by aigv_decode_step_logprob and aigv_op_lm_head_argmax_logprob, then by the candidate-token
                                 log-probabilities (aigv_out_row_cand_logprob, aigv_decode_step_cand_logprob, aigv_op_cand_logprob,
-                                aigv_op_lm_head_argmax_cand_logprob) - added symbols only: a library without them is refused at load
+                                aigv_op_lm_head_argmax_cand_logprob), then by the test entry points aigv_op_attention_ex and aigv_op_kv_store
+                                - added symbols only: a library without them is refused at load
                                 time, "missing <name>" */
 
 /* Most candidate token ids one candidate log-probability call takes. */
@@ -309,6 +310,24 @@ int aigv_op_attention_rope(const void* q, int ldq, const void* k, int ldk, const
                            const int32_t* cu, int n_seq, int max_len, int n_heads, int n_kv_heads, int q_group_stride,
                            int kv_head_stride, int head_dim, int causal, float post_div, float q_prescale, const int32_t* pos,
                            const void* cos, const void* sin, void* stream);
+/* aigv_op_attention_rope plus the address and mask forms of the scoring passes (parity tests: tests/test_gpu_attention_forms.py):
+ *   kv_seq_stride  elements; 0 = K / V packed like the query rows, else K / V of sequence s start s * kv_seq_stride elements behind k / v
+ *                  (the KV cache [seq][kv head][cap][head_dim]: ldk = ldv = head_dim, kv_head_stride = cap * head_dim)
+ *   kv_off         DEVICE int32[n_seq] or NULL: keys in front of each sequence's first query row (a continuation); needs kv_seq_stride.
+ *                  Query row r of sequence s sees keys 0 .. kv_off[s] + r of kv_off[s] + len[s] keys.
+ *   pos_is_row     != 0: the rotary position of query row r is kv_off[s] + r, computed by the kernel (pos is not read); 0: pos[row]
+ *   q_tail         > 0: only the last q_tail query rows of every sequence are consumed: rows of whole 32-row waves in front of them are
+ *                  left unwritten, the others are computed as with q_tail = 0
+ * The arguments are checked on the host before anything is launched (AIGV_ERR_ARG with a message naming the op). */
+int aigv_op_attention_ex(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, const int32_t* cu, int n_seq,
+                         int max_len, int n_heads, int n_kv_heads, int q_group_stride, int kv_head_stride, int64_t kv_seq_stride,
+                         const int32_t* kv_off, int head_dim, int causal, float post_div, float q_prescale, const int32_t* pos, const void* cos,
+                         const void* sin, int pos_is_row, int q_tail, void* stream);
+/* The KV-cache append of the prefill and continuation passes: for token t, the K and V slots of every group of the fused row
+ * qkv[t * ld ..] (groups of [g query heads | K | V]) are copied to kc / vc [seq][n_kv][cap][head_dim] at [seq[t]][kvh][pos[t]]; nothing else
+ * is written.  seq / pos: DEVICE int32[tokens] (the caller's promise: seq[t] inside the cache, pos[t] < cap).  Checked on the host. */
+int aigv_op_kv_store(const void* qkv, int ld, const int32_t* seq, const int32_t* pos, void* kc, void* vc, int tokens, int n_kv, int g,
+                     int head_dim, int cap, void* stream);
 int aigv_op_pixel_shuffle(const void* vit_out, int grid, int vit_hidden, void* out, int n_frames, void* stream);
 int aigv_op_im2col(const void* frames, int n_frames, int channels, int image_size, int patch, int kp, void* out,
                    void* stream);

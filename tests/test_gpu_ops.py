@@ -566,28 +566,7 @@ def test_pixel_shuffle_and_im2col_are_bit_exact(lib):
 # ---------------------------------------------------------------------------------------------------------
 # attention
 # ---------------------------------------------------------------------------------------------------------
-def attn_truth(q, k, v, causal, scale_pre, post_div, dtype):
-    """q [n,h,d], k/v [n,hk,d] for ONE sequence.  dtype=float64 -> truth; bf16 -> the reference's eager path
-    (modeling_intern_vit.py:153-157 / modeling_internlm2.py:407-424) with its rounding points."""
-    h, hk = q.shape[1], k.shape[1]
-    rep = h // hk
-    qq = q.transpose(0, 1).to(dtype)
-    kk = k.transpose(0, 1).repeat_interleave(rep, 0).to(dtype)
-    vv = v.transpose(0, 1).repeat_interleave(rep, 0).to(dtype)
-    if scale_pre != 1.0:
-        qq = qq * scale_pre
-    s = qq @ kk.transpose(1, 2)
-    if post_div != 1.0:
-        s = s / post_div
-    if causal:
-        n = q.shape[0]
-        m = torch.full((n, n), torch.finfo(dtype).min, dtype=dtype).triu(1)
-        s = s + m
-    if dtype == BF and post_div != 1.0:
-        p = torch.softmax(s, -1, dtype=torch.float32).to(BF)      # LLM: fp32 softmax, cast back
-    else:
-        p = torch.softmax(s, -1)
-    return (p @ vv).transpose(0, 1)
+from attention_reference import attn_truth, check_sequence  # noqa: E402  (fp64 truth / eager bf16 path of one sequence and the acceptance rule: shared with test_gpu_attention_forms.py)
 
 
 def run_attention(lib, q, k, v, lens, causal, d, pre, post, uniform=False, round_scores=False, lead_key=False):
@@ -623,6 +602,12 @@ def run_attention(lib, q, k, v, lens, causal, d, pre, post, uniform=False, round
     (128, True, 2, 1, [1300]),
     (128, True, 8, 2, [2176]),                   # the canonical clip: 17 x 128 rows, 34 key tiles
     (128, False, 2, 2, [384, 129]),              # InternViT-6B head width, non-causal
+    (128, True, 3, 1, [300, 129]),               # the causal block remap is group-size dependent (gq = n_heads / n_kv_heads): every group size up to 8
+    (128, True, 10, 2, [257, 64]),               # g = 5
+    (128, True, 6, 1, [513, 64, 1]),             # g = 6: InternLM2-20B
+    (128, True, 7, 1, [200, 77]),                # g = 7
+    (128, True, 8, 1, [385]),                    # g = 8
+    (128, True, 48, 8, [300, 77, 129]),          # InternLM2-20B's 48 query heads over 8 KV heads, ragged
 ])
 @pytest.mark.parametrize("round_scores", [True, False])
 def test_attention_matches_eager_reference(lib, d, causal, h, hk, lens, kernel, round_scores):
@@ -653,13 +638,9 @@ def _attention_case(lib, d, causal, h, hk, lens, uniform, round_scores=False):
         sl = slice(off, off + n)
         truth = attn_truth(q[sl], k[sl], v[sl], causal, pre, post, torch.float64)
         eager = attn_truth(q[sl], k[sl], v[sl], causal, pre, post, BF).double()
-        e_hip = (got[sl] - truth).abs()
-        e_ref = (eager - truth).abs()
-        assert torch.isfinite(got[sl]).all()
-        assert e_hip.mean() <= 1.5 * e_ref.mean() + 1e-4, (e_hip.mean().item(), e_ref.mean().item())
-        assert e_hip.max() <= 2.0 * e_ref.max() + 2e-3, (e_hip.max().item(), e_ref.max().item())
-        near += (got[sl] - eager).abs().sum().item()
-        far += e_ref.sum().item()
+        dn, df = check_sequence(got[sl], truth, eager)
+        near += dn
+        far += df
         off += n
     print(f"sum |hip - eager bf16| / sum |eager bf16 - fp64 truth| = {near / max(far, 1e-30):.3f} (round_scores={round_scores})")
     if round_scores:       # what remains is the P rounding (un-normalised here, normalised there) and the output rounding
