@@ -101,7 +101,7 @@ __device__ __forceinline__ float block_sum_256(float v, float* red) {
 }
 
 // Online log-sum-exp over a set of columns as a (max, sum of exp(x - max)) pair: the arithmetic every log-probability kernel shares
-// (logprob.hip, candlogprob.hip, the SK_ARGMAX_LSE epilogue and its finishers in head.hip), so that they agree bit for bit.
+// (the row kernel and the finisher in logprob.hip, the SK_ARGMAX_LSE epilogue in head.hip), so that they agree bit for bit.
 // (m, s) <- the pair of the union of the two column sets.  Symmetric in its arguments; (-inf, 0) is the empty set.
 __device__ __forceinline__ void lse_combine(float& m, float& s, float m2, float s2) {
   const float M = fmaxf(m, m2);
@@ -118,6 +118,56 @@ __device__ __forceinline__ void lse_push(float& m, float& s, float x) {
   } else {
     s += expf(x - m);
   }
+}
+
+// lse_combine with its two products rounded on their own - never one of them fused into the addition.  The compiler is free to contract
+// lse_combine's expression either way; lse_of_block<false> must not depend on that choice.
+__device__ __forceinline__ void lse_combine_unfused(float& m, float& s, float m2, float s2) {
+#pragma clang fp contract(off)
+  const float M = fmaxf(m, m2);
+  if (M == -INFINITY) return;
+  const float a = s * expf(m - M), b = s2 * expf(m2 - M);
+  s = a + b;
+  m = M;
+}
+
+// The 256 per-thread pairs of one row -> the row's log-sum-exp, returned to every thread of the workgroup (LSE_THREADS threads, one
+// row per workgroup, every thread must call).  The one reduction tree of the log-probability kernels: a butterfly inside each wave,
+// lane 0 of each wave to LDS, the four wave pairs combined in wave order 0..3 starting from wave 0's, then m + log s.  The tree is
+// fixed by the thread count alone and every thread runs the last steps on the same values - so a row's bits depend on nothing but
+// the pairs handed in, and all threads hold the same bits.
+// FUSED_TAIL picks the rounding of the three wave-order steps, the one thing the kernels have never shared: the logits-row kernel has
+// always rounded both products before the addition, the lm-head finisher has always fused one (what the compiler made of the same
+// expression in the two places).  Each keeps its bits; the two kernels are never compared with each other bit for bit.
+constexpr int LSE_THREADS = 256;
+template <bool FUSED_TAIL>
+__device__ __forceinline__ float lse_of_block(float m, float s) {
+#pragma unroll
+  for (int off = AIGV_WAVE / 2; off >= 1; off >>= 1) lse_combine(m, s, __shfl_xor(m, off), __shfl_xor(s, off));
+  __shared__ float wm[LSE_THREADS / AIGV_WAVE], ws[LSE_THREADS / AIGV_WAVE];
+  const int wave = threadIdx.x / AIGV_WAVE, lane = threadIdx.x % AIGV_WAVE;
+  if (lane == 0) {
+    wm[wave] = m;
+    ws[wave] = s;
+  }
+  __syncthreads();
+  m = wm[0];
+  s = ws[0];
+#pragma unroll
+  for (int w = 1; w < LSE_THREADS / AIGV_WAVE; ++w) {
+    if (FUSED_TAIL) lse_combine(m, s, wm[w], ws[w]);
+    else lse_combine_unfused(m, s, wm[w], ws[w]);
+  }
+  return m + logf(s);
+}
+
+// The lm-head's packed argmax key (skinny_kernel's SK_ARGMAX forms: order-preserving bits of the bf16-rounded logit in the high word,
+// 0xFFFFFFFF - column in the low word, so that the largest key is the first maximal column) -> (column, logit).
+__device__ __forceinline__ void unpack_argmax_key(unsigned long long p, int64_t& idx, float& val) {
+  unsigned int u = (unsigned)(p >> 32);
+  u = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
+  val = __uint_as_float(u);
+  idx = (int64_t)(0xFFFFFFFFu - (unsigned)(p & 0xFFFFFFFFull));
 }
 
 #define GLOBAL_AS __attribute__((address_space(1)))

@@ -24,7 +24,7 @@ namespace {
 // pair of its bf16-rounded logits to its own slot of a partials buffer [R][ceil(N / 16)] - passed as `out`, `ldo` = ceil(N / 16) float2
 // per row - with no atomics: lane fq holds columns 4 fq .. 4 fq + 3 of the slab, pushed in column order, then two butterfly steps.  The
 // slot layout follows the 16-row slabs, not the workgroups (one or four slabs per workgroup depending on R), so a row's partials do
-// not depend on R; lse_finish_kernel merges them in a fixed order.
+// not depend on R; lse_finish_kernel (logprob.hip) merges them in a fixed order.
 // (lse_push / lse_combine: common.h)
 
 // SK_ROPE_KV: the decode step's wqkv GEMV with RoPE and the KV-cache append in its epilogue (head_dim 128).  A workgroup takes the
@@ -338,50 +338,9 @@ __global__ void unpack_argmax_kernel(const unsigned long long* __restrict__ pack
                                      float* __restrict__ val, int R) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= R) return;
-  const unsigned long long p = packed[r];
-  idx[r] = (int64_t)(0xFFFFFFFFu - (unsigned)(p & 0xFFFFFFFFull));
-  if (val) {
-    unsigned int u = (unsigned)(p >> 32);
-    u = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
-    val[r] = __uint_as_float(u);
-  }
-}
-
-// SK_ARGMAX_LSE's finisher, one workgroup of 256 threads per row: thread t merges slots t, t + 256, ... in order, then a butterfly
-// inside each wave and the four wave results in wave order (label_logprob_kernel's tree) -> lse = M + log S; idx / val as
-// unpack_argmax_kernel, logprob = val - lse.  The order depends on the slot count only: a row's bits do not depend on R.
-constexpr int LSE_THREADS = 256;
-__global__ __launch_bounds__(LSE_THREADS) void lse_finish_kernel(const unsigned long long* __restrict__ packed, const float2* __restrict__ part,
-                                                                int nslot, int64_t* __restrict__ idx, float* __restrict__ val,
-                                                                float* __restrict__ logprob) {
-  const int r = blockIdx.x;
-  const float2* row = part + (size_t)r * nslot;
-  float m = -INFINITY, s = 0.f;
-  for (int i = threadIdx.x; i < nslot; i += LSE_THREADS) {
-    const float2 p = row[i];
-    lse_combine(m, s, p.x, p.y);
-  }
-#pragma unroll
-  for (int off = AIGV_WAVE / 2; off >= 1; off >>= 1) lse_combine(m, s, __shfl_xor(m, off), __shfl_xor(s, off));
-  __shared__ float wm[LSE_THREADS / AIGV_WAVE], ws[LSE_THREADS / AIGV_WAVE];
-  const int wave = threadIdx.x / AIGV_WAVE, lane = threadIdx.x % AIGV_WAVE;
-  if (lane == 0) {
-    wm[wave] = m;
-    ws[wave] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  m = wm[0];
-  s = ws[0];
-#pragma unroll
-  for (int w = 1; w < LSE_THREADS / AIGV_WAVE; ++w) lse_combine(m, s, wm[w], ws[w]);
-  const unsigned long long p = packed[r];
-  unsigned int u = (unsigned)(p >> 32);
-  u = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
-  const float v = __uint_as_float(u);
-  idx[r] = (int64_t)(0xFFFFFFFFu - (unsigned)(p & 0xFFFFFFFFull));
+  float v;
+  unpack_argmax_key(packed[r], idx[r], v);
   if (val) val[r] = v;
-  logprob[r] = v - (m + logf(s));
 }
 
 // ---- score head ------------------------------------------------------------------------------------------
@@ -577,7 +536,7 @@ hipError_t aigv_launch_lm_head_argmax(const bf16_t* h, int R, int H, const bf16_
 
 size_t aigv_lm_head_lse_slots(int V) { return (size_t)(V + 15) / 16; }
 
-// the lm-head in its SK_ARGMAX_LSE form alone: the packed argmax keys and the per-slab log-sum-exp partials, for a finisher to read
+// the lm-head in its SK_ARGMAX_LSE form alone: the packed argmax keys and the per-slab log-sum-exp partials, for lse_finish_kernel (logprob.hip) to read
 hipError_t aigv_launch_lm_head_lse_partials(const bf16_t* h, int R, int H, const bf16_t* W, int V, unsigned long long* packed, float2* part,
                                             hipStream_t s) {
   if (R <= 0) return hipSuccess;
@@ -585,17 +544,6 @@ hipError_t aigv_launch_lm_head_lse_partials(const bf16_t* h, int R, int H, const
   hipError_t e = hipMemsetAsync(packed, 0, sizeof(unsigned long long) * R, s);
   if (e != hipSuccess) return e;
   return launch_skinny<SK_ARGMAX_LSE>(h, H, R, W, H, V, H, nullptr, nullptr, 0, reinterpret_cast<bf16_t*>(part), (int)aigv_lm_head_lse_slots(V), packed, s);
-}
-
-// aigv_launch_lm_head_argmax + the fused log-sum-exp (SK_ARGMAX_LSE): part holds R * aigv_lm_head_lse_slots(V) float2
-hipError_t aigv_launch_lm_head_argmax_logprob(const bf16_t* h, int R, int H, const bf16_t* W, int V, unsigned long long* packed, float2* part,
-                                              int64_t* out_idx, float* out_val, float* out_logprob, hipStream_t s) {
-  if (R <= 0) return hipSuccess;
-  if (!out_idx || !out_logprob) return hipErrorInvalidValue;
-  const hipError_t e = aigv_launch_lm_head_lse_partials(h, R, H, W, V, packed, part, s);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(lse_finish_kernel, dim3(R), dim3(LSE_THREADS), 0, s, packed, part, (int)aigv_lm_head_lse_slots(V), out_idx, out_val, out_logprob);
-  return hipGetLastError();
 }
 
 // scratch: 3 * B * max(dims) bf16 (guarded input + two ping-pong activations)

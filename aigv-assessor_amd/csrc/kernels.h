@@ -174,35 +174,34 @@ hipError_t aigv_launch_skinny_rope_kv(const bf16_t* x, int ldx, int R, const bf1
 hipError_t aigv_launch_lm_head_argmax(const bf16_t* h, int R, int H, const bf16_t* W, int V,
                                       unsigned long long* packed, int64_t* out_idx, float* out_val, hipStream_t s);
 // the same plus the log-probability of the chosen token: logprob[r] = val[r] - logsumexp(bf16-rounded logits of row r) in fp32, the
-// sum merged from per-16-column partials part[R][aigv_lm_head_lse_slots(V)] in a fixed order (batch-invariant bits); idx / val are
-// aigv_launch_lm_head_argmax's bits.  val may be null.
-size_t aigv_lm_head_lse_slots(int V);
-hipError_t aigv_launch_lm_head_argmax_logprob(const bf16_t* h, int R, int H, const bf16_t* W, int V, unsigned long long* packed, float2* part,
-                                              int64_t* out_idx, float* out_val, float* out_logprob, hipStream_t s);
-// the first half of aigv_launch_lm_head_argmax_logprob: the lm-head's packed argmax keys and log-sum-exp partials, no finisher
-hipError_t aigv_launch_lm_head_lse_partials(const bf16_t* h, int R, int H, const bf16_t* W, int V, unsigned long long* packed, float2* part,
-                                            hipStream_t s);
-// candidate-token log-probabilities (candlogprob.hip): C <= AIGV_MAX_CANDIDATES token ids, DEVICE int64 [C]; an id outside [0, V) gives a NaN column.
-// Scoring pass: out[r, c] = logits[r, cand[c]] - logsumexp(logits[r, :V]) over bf16 logits [rows, ldo >= V], out fp32 [rows, C];
-// aigv_launch_label_logprob's mapping and tree, so column c holds that kernel's bits for labels = cand[c].
+// sum merged from per-16-column partials part[R][aigv_lm_head_lse_slots(V)] in a fixed order (batch-invariant bits; lse_finish_kernel,
+// logprob.hip); idx / val are aigv_launch_lm_head_argmax's bits.  val may be null.
+// Candidates are optional (C = 0): with C <= AIGV_MAX_CANDIDATES token ids (DEVICE int64 [C]) out_cand[r, c] = bf16 logit of column cand[c] -
+// the row's log-sum-exp, NaN for an id outside [0, V); the C columns come from a GEMV over the C gathered weight rows into cand_logit, a
+// scratch of aigv_cand_logit_elems(R) bf16.  The same finisher runs either way: idx / val / logprob do not depend on the candidates.
 #ifndef AIGV_MAX_CANDIDATES
 #define AIGV_MAX_CANDIDATES 64   // = include/aigv_amd.h
 #endif
-hipError_t aigv_launch_cand_logprob(const bf16_t* logits, int rows, int V, int ldo, const int64_t* cand, int C, float* out, hipStream_t s);
-// Decode: aigv_launch_lm_head_argmax_logprob (idx / val / logprob: its bits) plus out_cand[r, c] = bf16 logit of column cand[c] - the row's
-// log-sum-exp; the C columns come from a GEMV over the C gathered weight rows.  cand_logit: scratch of aigv_cand_logit_elems(R) bf16.
+size_t aigv_lm_head_lse_slots(int V);
 size_t aigv_cand_logit_elems(int R);
-hipError_t aigv_launch_lm_head_argmax_cand_logprob(const bf16_t* h, int R, int H, const bf16_t* W, int V, unsigned long long* packed, float2* part,
-                                                   const int64_t* cand, int C, bf16_t* cand_logit, int64_t* out_idx, float* out_val,
-                                                   float* out_logprob, float* out_cand, hipStream_t s);
+hipError_t aigv_launch_lm_head_argmax_logprob(const bf16_t* h, int R, int H, const bf16_t* W, int V, unsigned long long* packed, float2* part,
+                                              int64_t* out_idx, float* out_val, float* out_logprob, hipStream_t s, const int64_t* cand = nullptr,
+                                              int C = 0, bf16_t* cand_logit = nullptr, float* out_cand = nullptr);
+// the first half of aigv_launch_lm_head_argmax_logprob: the lm-head's packed argmax keys and log-sum-exp partials, no finisher
+hipError_t aigv_launch_lm_head_lse_partials(const bf16_t* h, int R, int H, const bf16_t* W, int V, unsigned long long* packed, float2* part,
+                                            hipStream_t s);
 // lm-head logits (bf16, the matmul output the reference upcasts) of R rows into out[R, ldo], ldo >= roundup(V, 4)
 // one_form: the 4-slice form for every row count (that of the fused argmax), so that a row's logits do not depend on how many rows
 // share the launch; otherwise <= 16 rows of a vocabulary <= 4096 take the 8-slice GEMV form
 hipError_t aigv_launch_lm_head_logits(const bf16_t* h, int R, int H, const bf16_t* W, int V, bf16_t* out, int ldo, hipStream_t s,
                                       bool one_form = false);
-// label log-probabilities: out[r] = logits[r, labels[r]] - logsumexp(logits[r, :V]) in fp32 over bf16 logits [rows, ldo >= V], NaN where
-// labels[r] is outside [0, V); one workgroup per row, fixed lane -> column mapping and reduction tree (batch-invariant bits)
+// log-probabilities of bf16 logits rows [rows, ldo >= V] in fp32 (row_logprob_kernel, logprob.hip): one workgroup per row, a lane -> column
+// mapping and a reduction tree fixed by V alone (batch-invariant bits); an id outside [0, V) gives NaN.
+//   label:      out[r] = logits[r, labels[r]] - logsumexp(logits[r, :V]), labels DEVICE int64 [rows]
+//   candidates: out[r, c] = logits[r, cand[c]] - logsumexp(logits[r, :V]), cand DEVICE int64 [C], 1 <= C <= AIGV_MAX_CANDIDATES, out [rows, C]
+// Both are the one kernel, so column c of the second holds the first's bits for labels = cand[c].
 hipError_t aigv_launch_label_logprob(const bf16_t* logits, int rows, int V, int ldo, const int64_t* labels, float* out, hipStream_t s);
+hipError_t aigv_launch_cand_logprob(const bf16_t* logits, int rows, int V, int ldo, const int64_t* cand, int C, float* out, hipStream_t s);
 // score head: x[B,H] -> chain of Linear+ReLU (bf16 rounding after each Linear), NaN/Inf guard on x
 struct ScoreHeadArgs {
   const bf16_t* x; int ldx; int B;

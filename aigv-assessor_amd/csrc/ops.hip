@@ -208,21 +208,29 @@ int64_t aigv_op_lm_head_argmax_logprob_scratch_bytes(int rows, int vocab) {
   return (int64_t)(64 * sizeof(unsigned long long) + (size_t)rows * aigv_lm_head_lse_slots(vocab) * sizeof(float2));
 }
 
-int aigv_op_lm_head_argmax_logprob(const void* h, int rows, int hidden, const void* W_, int vocab, void* scratch, int64_t scratch_bytes,
-                                   int64_t* idx, float* val, float* logprob, void* stream) {
-  const char* op = "aigv_op_lm_head_argmax_logprob";
-  if (!h || !W_ || !scratch || !idx || !logprob) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+// aigv_op_lm_head_argmax_logprob / aigv_op_lm_head_argmax_cand_logprob (C >= 1): every argument is checked here, before any HIP call.
+// scratch = [64 packed keys | log-sum-exp partials | (16-byte aligned) candidate logits]
+static int lm_head_logprob_op(const char* op, const void* h, int rows, int hidden, const void* W_, int vocab, const int64_t* cand_ids, int C, void* scratch,
+                              int64_t scratch_bytes, int64_t* idx, float* val, float* logprob, float* cand_logprob, void* stream) {
+  if (!h || !W_ || !scratch || !idx || !logprob || (C && (!cand_ids || !cand_logprob))) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
   if (rows < 1 || rows > 64) return fail(nullptr, AIGV_ERR_ARG, "%s: rows = %d outside 1..64", op, rows);
   if (hidden < 128 || hidden % 128) return fail(nullptr, AIGV_ERR_ARG, "%s: hidden = %d is not a positive multiple of 128", op, hidden);
   if (vocab < 1) return fail(nullptr, AIGV_ERR_ARG, "%s: vocab = %d must be positive", op, vocab);
   if (((uintptr_t)h & 15) || ((uintptr_t)W_ & 15) || ((uintptr_t)scratch & 15)) return fail(nullptr, AIGV_ERR_ARG, "%s: h, W and scratch must be 16-byte aligned", op);
-  const int64_t need = aigv_op_lm_head_argmax_logprob_scratch_bytes(rows, vocab);
+  const int64_t base = aigv_op_lm_head_argmax_logprob_scratch_bytes(rows, vocab);
+  const int64_t need = C ? aigv_op_lm_head_argmax_cand_logprob_scratch_bytes(rows, vocab) : base;
   if (scratch_bytes < need) return fail(nullptr, AIGV_ERR_ARG, "%s: scratch of %lld bytes, needs %lld", op, (long long)scratch_bytes, (long long)need);
   unsigned long long* packed = (unsigned long long*)scratch;
   float2* part = (float2*)((char*)scratch + 64 * sizeof(unsigned long long));
+  bf16_t* cl = C ? (bf16_t*)((char*)scratch + (base + 15) / 16 * 16) : nullptr;
   HIPCHK(nullptr, aigv_launch_lm_head_argmax_logprob((const bf16_t*)h, rows, hidden, (const bf16_t*)W_, vocab, packed, part, idx, val, logprob,
-                                                     (hipStream_t)stream));
+                                                     (hipStream_t)stream, cand_ids, C, cl, cand_logprob));
   return 0;
+}
+
+int aigv_op_lm_head_argmax_logprob(const void* h, int rows, int hidden, const void* W_, int vocab, void* scratch, int64_t scratch_bytes,
+                                   int64_t* idx, float* val, float* logprob, void* stream) {
+  return lm_head_logprob_op("aigv_op_lm_head_argmax_logprob", h, rows, hidden, W_, vocab, nullptr, 0, scratch, scratch_bytes, idx, val, logprob, nullptr, stream);
 }
 
 int aigv_op_label_logprob(const void* logits_bf16, int rows, int vocab, int ldo, const int64_t* labels, float* out, void* stream) {
@@ -251,19 +259,7 @@ int aigv_op_lm_head_argmax_cand_logprob(const void* h, int rows, int hidden, con
                                         void* stream) {
   const char* op = "aigv_op_lm_head_argmax_cand_logprob";
   if (C < 1 || C > AIGV_MAX_CANDIDATES) return fail(nullptr, AIGV_ERR_ARG, "%s: C = %d candidates outside 1..%d", op, C, AIGV_MAX_CANDIDATES);
-  if (!h || !W_ || !scratch || !idx || !logprob || !cand_ids || !cand_logprob) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
-  if (rows < 1 || rows > 64) return fail(nullptr, AIGV_ERR_ARG, "%s: rows = %d outside 1..64", op, rows);
-  if (hidden < 128 || hidden % 128) return fail(nullptr, AIGV_ERR_ARG, "%s: hidden = %d is not a positive multiple of 128", op, hidden);
-  if (vocab < 1) return fail(nullptr, AIGV_ERR_ARG, "%s: vocab = %d must be positive", op, vocab);
-  if (((uintptr_t)h & 15) || ((uintptr_t)W_ & 15) || ((uintptr_t)scratch & 15)) return fail(nullptr, AIGV_ERR_ARG, "%s: h, W and scratch must be 16-byte aligned", op);
-  const int64_t need = aigv_op_lm_head_argmax_cand_logprob_scratch_bytes(rows, vocab);
-  if (scratch_bytes < need) return fail(nullptr, AIGV_ERR_ARG, "%s: scratch of %lld bytes, needs %lld", op, (long long)scratch_bytes, (long long)need);
-  unsigned long long* packed = (unsigned long long*)scratch;
-  float2* part = (float2*)((char*)scratch + 64 * sizeof(unsigned long long));
-  bf16_t* cl = (bf16_t*)((char*)scratch + (aigv_op_lm_head_argmax_logprob_scratch_bytes(rows, vocab) + 15) / 16 * 16);
-  HIPCHK(nullptr, aigv_launch_lm_head_argmax_cand_logprob((const bf16_t*)h, rows, hidden, (const bf16_t*)W_, vocab, packed, part, cand_ids, C, cl, idx, val,
-                                                          logprob, cand_logprob, (hipStream_t)stream));
-  return 0;
+  return lm_head_logprob_op(op, h, rows, hidden, W_, vocab, cand_ids, C, scratch, scratch_bytes, idx, val, logprob, cand_logprob, stream);
 }
 
 // ---- the decode step's kernels, one by one (test entry points): every argument is checked here, before any HIP call ----

@@ -590,7 +590,7 @@ static int decode_tail_bf16(aigv_ctx* c, const LlmLayer& L, int B, bool fused, i
 }
 
 // aigv_decode_step / aigv_decode_step_logprob (logprob != nullptr: the lm-head runs its argmax + log-sum-exp form) /
-// aigv_decode_step_cand_logprob (cand_lp != nullptr: that form, then the candidates' GEMV and the finisher that subtracts the log-sum-exp)
+// aigv_decode_step_cand_logprob (cand_lp != nullptr, C >= 1: the same form, with the candidates' GEMV in front of its finisher)
 static int decode_step(aigv_ctx* c, const int64_t* ids, int64_t* next, float* logprob, void* stream, const int64_t* cand = nullptr, int C = 0,
                        float* cand_lp = nullptr) {
   const char* op = cand_lp ? "aigv_decode_step_cand_logprob" : logprob ? "aigv_decode_step_logprob" : "aigv_decode_step";
@@ -660,9 +660,8 @@ static int decode_step(aigv_ctx* c, const int64_t* ids, int64_t* next, float* lo
     TRY(decode_tail_bf16(c, L, B, fused, po, p13, p2, s));
   }
   HIPCHK(c, aigv_launch_rmsnorm(c->l_h, H, c->final_norm, c->l_rows, H, B, H, k.rms_eps, nullptr, s));
-  if (cand_lp) HIPCHK(c, aigv_launch_lm_head_argmax_cand_logprob(c->l_rows, B, H, c->lm_head, k.vocab, c->l_packed, c->dec_lse, cand, C, c->dec_cand, next,
-                                                                 nullptr, logprob, cand_lp, s));
-  else if (logprob) HIPCHK(c, aigv_launch_lm_head_argmax_logprob(c->l_rows, B, H, c->lm_head, k.vocab, c->l_packed, c->dec_lse, next, nullptr, logprob, s));
+  if (logprob) HIPCHK(c, aigv_launch_lm_head_argmax_logprob(c->l_rows, B, H, c->lm_head, k.vocab, c->l_packed, c->dec_lse, next, nullptr, logprob, s, cand, C,
+                                                            c->dec_cand, cand_lp));
   else HIPCHK(c, aigv_launch_lm_head_argmax(c->l_rows, B, H, c->lm_head, k.vocab, c->l_packed, next, nullptr, s));
   HIPCHK(c, aigv_launch_advance(c->dec_pos, c->dec_kvlen, B, s));
   for (int b = 0; b < B; ++b) c->h_kvlen[b] += 1;
@@ -684,13 +683,20 @@ int aigv_decode_step_cand_logprob(aigv_ctx* c, const int64_t* ids, int64_t* next
   return decode_step(c, ids, next, logprob, stream, cand_ids, C, cand_logprob);
 }
 
-int aigv_out_row_logits(aigv_ctx* c, int first_row, int n_rows, void* logits_bf16, int ldo, void* stream) {
-  if (!c || !logits_bf16) return fail(c, AIGV_ERR_ARG, "aigv_out_row_logits: null argument");
-  if (!c->finalized) return fail(c, AIGV_ERR_STATE, "aigv_out_row_logits: call aigv_finalize_weights first");
-  const aigv_config& k = c->cfg;
-  const int cap = k.max_out_rows + k.max_seqs + 64;
-  if (first_row < 0 || n_rows <= 0 || first_row + n_rows > cap) return fail(c, AIGV_ERR_ARG, "aigv_out_row_logits: rows %d..%d outside 0..%d", first_row, first_row + n_rows - 1, cap - 1);
+// What every aigv_out_row_* entry point checks before it touches the device - the handle and the caller's pointers (args_ok), finalized
+// weights, the row window inside the consumed-row buffer - and the device selection.
+static int out_rows_begin(aigv_ctx* c, const char* op, bool args_ok, int first_row, int n_rows) {
+  if (!c || !args_ok) return fail(c, AIGV_ERR_ARG, "%s: null argument", op);
+  if (!c->finalized) return fail(c, AIGV_ERR_STATE, "%s: call aigv_finalize_weights first", op);
+  const int cap = c->cfg.max_out_rows + c->cfg.max_seqs + 64;
+  if (first_row < 0 || n_rows <= 0 || first_row + n_rows > cap) return fail(c, AIGV_ERR_ARG, "%s: rows %d..%d outside 0..%d", op, first_row, first_row + n_rows - 1, cap - 1);
   HIPCHK(c, hipSetDevice(c->device));
+  return 0;
+}
+
+int aigv_out_row_logits(aigv_ctx* c, int first_row, int n_rows, void* logits_bf16, int ldo, void* stream) {
+  TRY(out_rows_begin(c, "aigv_out_row_logits", logits_bf16, first_row, n_rows));
+  const aigv_config& k = c->cfg;
   hipStream_t s = (hipStream_t)stream;
   for (int r0 = 0; r0 < n_rows; r0 += 64) {
     const int rr = std::min(64, n_rows - r0);
@@ -702,14 +708,11 @@ int aigv_out_row_logits(aigv_ctx* c, int first_row, int n_rows, void* logits_bf1
   return 0;
 }
 
-int aigv_out_row_logprob(aigv_ctx* c, int first_row, int n_rows, const int64_t* labels, float* logprob, void* stream) {
-  if (!c || !labels || !logprob) return fail(c, AIGV_ERR_ARG, "aigv_out_row_logprob: null argument");
-  if (!c->finalized) return fail(c, AIGV_ERR_STATE, "aigv_out_row_logprob: call aigv_finalize_weights first");
+// The loop of aigv_out_row_logprob (labels, one per row) and aigv_out_row_cand_logprob (labels == nullptr: C candidates for every row):
+// consumed rows in chunks of 64, the lm-head logits of a chunk into c->l_lp in the 4-slice form of every row count (a row's logits do
+// not depend on its chunk), then the row kernel of logprob.hip reads them.
+static int out_row_logprobs(aigv_ctx* c, int first_row, int n_rows, const int64_t* labels, const int64_t* cand, int C, float* out, hipStream_t s) {
   const aigv_config& k = c->cfg;
-  const int cap = k.max_out_rows + k.max_seqs + 64;
-  if (first_row < 0 || n_rows <= 0 || first_row + n_rows > cap) return fail(c, AIGV_ERR_ARG, "aigv_out_row_logprob: rows %d..%d outside 0..%d", first_row, first_row + n_rows - 1, cap - 1);
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = (hipStream_t)stream;
   for (int r0 = 0; r0 < n_rows; r0 += 64) {
     const int rr = std::min(64, n_rows - r0);
     {
@@ -718,44 +721,32 @@ int aigv_out_row_logprob(aigv_ctx* c, int first_row, int n_rows, const int64_t* 
                                                 c->l_lp, c->lp_ldo, s, /*one_form=*/true);
       if (e != hipSuccess) return fail(c, e == hipErrorInvalidValue ? AIGV_ERR_ARG : AIGV_ERR_HIP, "lm-head logits (rows=%d ldo=%d): %s", rr, c->lp_ldo, hipGetErrorString(e));
     }
-    hipError_t e = aigv_launch_label_logprob(c->l_lp, rr, k.vocab, c->lp_ldo, labels + r0, logprob + r0, s);
-    if (e != hipSuccess) return fail(c, e == hipErrorInvalidValue ? AIGV_ERR_ARG : AIGV_ERR_HIP, "label log-probabilities (rows=%d): %s", rr, hipGetErrorString(e));
+    const hipError_t e = labels ? aigv_launch_label_logprob(c->l_lp, rr, k.vocab, c->lp_ldo, labels + r0, out + r0, s)
+                                : aigv_launch_cand_logprob(c->l_lp, rr, k.vocab, c->lp_ldo, cand, C, out + (size_t)r0 * C, s);
+    if (e == hipSuccess) continue;
+    const int code = e == hipErrorInvalidValue ? AIGV_ERR_ARG : AIGV_ERR_HIP;
+    if (labels) return fail(c, code, "label log-probabilities (rows=%d): %s", rr, hipGetErrorString(e));
+    return fail(c, code, "candidate log-probabilities (rows=%d, C=%d): %s", rr, C, hipGetErrorString(e));
   }
   return 0;
+}
+
+int aigv_out_row_logprob(aigv_ctx* c, int first_row, int n_rows, const int64_t* labels, float* logprob, void* stream) {
+  TRY(out_rows_begin(c, "aigv_out_row_logprob", labels && logprob, first_row, n_rows));
+  return out_row_logprobs(c, first_row, n_rows, labels, nullptr, 1, logprob, (hipStream_t)stream);
 }
 
 int aigv_out_row_cand_logprob(aigv_ctx* c, int first_row, int n_rows, const int64_t* cand_ids, int C, float* cand_logprob, void* stream) {
   const char* op = "aigv_out_row_cand_logprob";
   if (C < 1 || C > AIGV_MAX_CANDIDATES) return fail(c, AIGV_ERR_ARG, "%s: C = %d candidates outside 1..%d", op, C, AIGV_MAX_CANDIDATES);
-  if (!c || !cand_ids || !cand_logprob) return fail(c, AIGV_ERR_ARG, "%s: null argument", op);
-  if (!c->finalized) return fail(c, AIGV_ERR_STATE, "%s: call aigv_finalize_weights first", op);
-  const aigv_config& k = c->cfg;
-  const int cap = k.max_out_rows + k.max_seqs + 64;
-  if (first_row < 0 || n_rows <= 0 || first_row + n_rows > cap) return fail(c, AIGV_ERR_ARG, "%s: rows %d..%d outside 0..%d", op, first_row, first_row + n_rows - 1, cap - 1);
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = (hipStream_t)stream;
-  for (int r0 = 0; r0 < n_rows; r0 += 64) {     // aigv_out_row_logprob's logits (same form, same scratch), read at C columns
-    const int rr = std::min(64, n_rows - r0);
-    {
-      ProfScope ps(c, AIGV_PROF_SKINNY, 2.0 * rr * (double)k.vocab * k.llm_hidden, 2.0 * (double)k.vocab * k.llm_hidden, s);
-      hipError_t e = aigv_launch_lm_head_logits(c->l_rows + (size_t)(first_row + r0) * k.llm_hidden, rr, k.llm_hidden, c->lm_head, k.vocab,
-                                                c->l_lp, c->lp_ldo, s, /*one_form=*/true);
-      if (e != hipSuccess) return fail(c, e == hipErrorInvalidValue ? AIGV_ERR_ARG : AIGV_ERR_HIP, "lm-head logits (rows=%d ldo=%d): %s", rr, c->lp_ldo, hipGetErrorString(e));
-    }
-    hipError_t e = aigv_launch_cand_logprob(c->l_lp, rr, k.vocab, c->lp_ldo, cand_ids, C, cand_logprob + (size_t)r0 * C, s);
-    if (e != hipSuccess) return fail(c, e == hipErrorInvalidValue ? AIGV_ERR_ARG : AIGV_ERR_HIP, "candidate log-probabilities (rows=%d, C=%d): %s", rr, C, hipGetErrorString(e));
-  }
-  return 0;
+  TRY(out_rows_begin(c, op, cand_ids && cand_logprob, first_row, n_rows));
+  return out_row_logprobs(c, first_row, n_rows, nullptr, cand_ids, C, cand_logprob, (hipStream_t)stream);
 }
 
 int aigv_out_row_hidden(aigv_ctx* c, int first_row, int n_rows, void* hidden_bf16, int ldo, void* stream) {
-  if (!c || !hidden_bf16) return fail(c, AIGV_ERR_ARG, "aigv_out_row_hidden: null argument");
-  if (!c->finalized) return fail(c, AIGV_ERR_STATE, "aigv_out_row_hidden: call aigv_finalize_weights first");
+  TRY(out_rows_begin(c, "aigv_out_row_hidden", hidden_bf16, first_row, n_rows));
   const aigv_config& k = c->cfg;
-  const int cap = k.max_out_rows + k.max_seqs + 64;
-  if (first_row < 0 || n_rows <= 0 || first_row + n_rows > cap || ldo < k.llm_hidden)
-    return fail(c, AIGV_ERR_ARG, "aigv_out_row_hidden: rows %d..%d outside 0..%d or ldo %d < %d", first_row, first_row + n_rows - 1, cap - 1, ldo, k.llm_hidden);
-  HIPCHK(c, hipSetDevice(c->device));
+  if (ldo < k.llm_hidden) return fail(c, AIGV_ERR_ARG, "aigv_out_row_hidden: ldo %d < %d", ldo, k.llm_hidden);
   HIPCHK(c, hipMemcpy2DAsync(hidden_bf16, (size_t)ldo * sizeof(bf16_t), c->l_rows + (size_t)first_row * k.llm_hidden, (size_t)k.llm_hidden * sizeof(bf16_t),
                              (size_t)k.llm_hidden * sizeof(bf16_t), n_rows, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return 0;

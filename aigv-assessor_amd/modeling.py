@@ -740,8 +740,7 @@ class InternVLChatModel(nn.Module):
         vit_embeds, motion = self._visual_inputs(pixel_values, visual_tokens, motion_feature, plan)
         score, amax = self._prefill(plan["ids_packed"], plan["slot"], plan["cu"], vit_embeds, plan["n_vis"], motion,
                                     plan["score_rows"], plan["logit_rows"])
-        lp = self._row_logprob(B if score is not None else 0, lp_labels) if return_logprobs else None
-        clp = self._row_cand_logprob(B if score is not None else 0, len(plan["logit_rows"]), cand) if cand is not None else None
+        lp, clp = self._row_logprobs(B if score is not None else 0, len(plan["logit_rows"]), lp_labels if return_logprobs else None, cand)
         return self._outputs(plan, B, N, score, amax, mos, lp, clp)
 
     # ---- HIP-graph replay of whole scoring passes (opt-in: enable_graph_replay) ---------------------------------------------------------
@@ -1047,30 +1046,27 @@ class InternVLChatModel(nn.Module):
     def _outputs(self, plan, B, N, score, amax, mos, lp=None, clp=None):
         dev = self.device
         up = self._h2d   # host -> device through pinned memory, never blocking the host (keeps the CPU ahead of the GPU)
-        logit = torch.full((B * (N - 1),), -1, dtype=torch.long, device=dev)
-        if len(plan["logit_rows"]):
-            idx = up(plan["want"].reshape(-1).nonzero().flatten())                          # index list built on the host: no sync
-            logit.index_copy_(0, idx, amax)
-        out = {"label": up(plan["labels_h"][..., 1:].contiguous().view(-1)), "logit": logit.view(-1)}
+        idx = up(plan["want"].reshape(-1).nonzero().flatten()) if len(plan["logit_rows"]) else None   # index list built on the host: no sync
+
+        def scatter(rows, fill):
+            """Per-consumed-row values -> their places among the B (N - 1) label positions, ``fill`` everywhere else."""
+            full = torch.full((B * (N - 1),) + tuple(rows.shape[1:]), fill, dtype=rows.dtype, device=dev)
+            return full if idx is None else full.index_copy_(0, idx, rows)
+
+        out = {"label": up(plan["labels_h"][..., 1:].contiguous().view(-1)), "logit": scatter(amax, -1)}
         if self.stage == 2:
             score1 = score.to(torch.bfloat16)       # the head computes in bf16; the value is exact in fp32
             out["score1"] = score1
             out["loss"] = F.l1_loss(score1, mos.to(dev).to(score1.dtype)) if mos is not None else None
         if lp is not None:                          # return_logprobs: scattered like `logit`, NaN elsewhere
-            logprob = torch.full((B * (N - 1),), float("nan"), dtype=torch.float32, device=dev)
-            if len(plan["logit_rows"]):
-                logprob.index_copy_(0, idx, lp)
-            out["logprob"] = logprob
+            out["logprob"] = logprob = scatter(lp, float("nan"))
             scored = (plan["labels_h"][..., 1:].reshape(-1) != -100).nonzero().flatten()   # (host: no sync)
             if scored.numel():   # CrossEntropyLoss(): mean over the non-ignored labels; here in fp64, then rounded once
                 out["ce_loss"] = (-logprob.index_select(0, up(scored))).double().mean().float()
             else:
                 out["ce_loss"] = torch.full((), float("nan"), dtype=torch.float32, device=dev)
         if clp is not None:                         # candidate_ids: rows scattered like `logit`, NaN rows elsewhere
-            cand_logprob = torch.full((B * (N - 1), clp.shape[1]), float("nan"), dtype=torch.float32, device=dev)
-            if len(plan["logit_rows"]):
-                cand_logprob.index_copy_(0, idx, clp)
-            out["cand_logprob"] = cand_logprob
+            out["cand_logprob"] = scatter(clp, float("nan"))
         return out
 
     MAX_CANDIDATES = 64      # = AIGV_MAX_CANDIDATES
@@ -1089,17 +1085,6 @@ class InternVLChatModel(nn.Module):
                              f"{tuple(t.shape)} {t.dtype}")
         return t.to(torch.long).contiguous()
 
-    def _row_cand_logprob(self, first_row: int, R: int, cand: torch.Tensor) -> torch.Tensor:
-        """fp32 [R, C] candidate log-probabilities of consumed rows first_row .. first_row + R - 1 of the last native pass
-        (aigv_out_row_cand_logprob); no host sync, no allocation inside the library (the pass may be captured)."""
-        C_ = int(cand.numel())
-        out = torch.empty((max(R, 1), C_), dtype=torch.float32, device=self.device)
-        if R:
-            lib, ctx = native.load(), self._ctx
-            cand_d = self._h2d(cand)
-            native.check(lib.aigv_out_row_cand_logprob(ctx, int(first_row), R, cand_d.data_ptr(), C_, out.data_ptr(), native.stream_ptr()), ctx)
-        return out[:R]
-
     def _logprob_labels(self, plan) -> torch.Tensor:
         """Host int64 labels of the pass's consumed rows (in ``logit_rows`` order), checked first as torch's cross entropy would."""
         lab = plan["labels_h"][:, 1:].to(torch.long)
@@ -1113,16 +1098,21 @@ class InternVLChatModel(nn.Module):
                              "padded row itself, which this path does not run - set such labels to -100")
         return lab[plan["want"]].contiguous()
 
-    def _row_logprob(self, first_row: int, labels_h: torch.Tensor) -> torch.Tensor:
-        """fp32 [R] label log-probabilities of consumed rows first_row .. first_row + R - 1 of the last native pass (aigv_out_row_logprob);
-        the labels go up through pinned memory - no host sync, and no allocation inside the library (the pass may be captured)."""
-        R = int(labels_h.numel())
-        lp = torch.empty(max(R, 1), dtype=torch.float32, device=self.device)
-        if R:
-            lib, ctx = native.load(), self._ctx
-            lab_d = self._h2d(labels_h)
-            native.check(lib.aigv_out_row_logprob(ctx, int(first_row), R, lab_d.data_ptr(), lp.data_ptr(), native.stream_ptr()), ctx)
-        return lp[:R]
+    def _row_logprobs(self, first_row: int, R: int, labels: Optional[torch.Tensor] = None, cand: Optional[torch.Tensor] = None):
+        """(lp, clp) of consumed rows first_row .. first_row + R - 1 of the last native pass: fp32 [R] log-probabilities of ``labels`` (int64 [R],
+        aigv_out_row_logprob) and fp32 [R, C] of the candidates ``cand`` (int64 [C], aigv_out_row_cand_logprob); None for what is not asked for.
+        Host tensors go up through pinned memory, device tensors are read where they are - no host sync, and no allocation inside the library
+        (the pass may be captured)."""
+        lp = None if labels is None else torch.empty(max(R, 1), dtype=torch.float32, device=self.device)[:R]
+        clp = None if cand is None else torch.empty((max(R, 1), int(cand.numel())), dtype=torch.float32, device=self.device)[:R]
+        if R and lp is not None:
+            lab_d = self._h2d(labels)
+            native.check(native.load().aigv_out_row_logprob(self._ctx, int(first_row), R, lab_d.data_ptr(), lp.data_ptr(), native.stream_ptr()), self._ctx)
+        if R and clp is not None:
+            cand_d = self._h2d(cand)
+            native.check(native.load().aigv_out_row_cand_logprob(self._ctx, int(first_row), R, cand_d.data_ptr(), int(cand.numel()), clp.data_ptr(),
+                                                                 native.stream_ptr()), self._ctx)
+        return lp, clp
 
     @staticmethod
     def _shared_prefix_lengths(plans, B: int) -> List[int]:
@@ -1214,8 +1204,7 @@ class InternVLChatModel(nn.Module):
                                          native.i32_array(srows) if score is not None else None, native.ptr(score),
                                          native.i32_array(lrows) if lrows else None, len(lrows), amax.data_ptr(), 0,
                                          native.stream_ptr()), ctx)
-        lp = self._row_logprob(len(srows), torch.cat(lp_labels)) if return_logprobs else None   # rows [score rows | logit rows]
-        clp = self._row_cand_logprob(len(srows), len(lrows), cand) if cand is not None else None
+        lp, clp = self._row_logprobs(len(srows), len(lrows), torch.cat(lp_labels) if return_logprobs else None, cand)   # rows [score rows | logit rows]
         outs, off = [], 0
         for p, (pl, (ids, _, _)) in enumerate(zip(plans, prompts)):
             outs.append(self._outputs(pl, B, ids.shape[1], score[p * B:(p + 1) * B] if score is not None else None,
@@ -1225,6 +1214,24 @@ class InternVLChatModel(nn.Module):
         return outs
 
     # ---- generation (API surface; greedy) -------------------------------------------------------------------
+    def _decode_step(self, tok: torch.Tensor, want_lp: bool = False, cand_d: Optional[torch.Tensor] = None):
+        """One native decode step for the current tokens ``tok`` [b] -> (next tokens, lp, clp): with ``want_lp`` or candidates (device int64 [C])
+        the lm-head pass that picks the token also gives its fp32 log-probability [b] and the candidates' [b, C]; None for what the step
+        did not compute."""
+        lib, ctx, b = native.load(), self._ctx, tok.numel()
+        new = torch.empty_like(tok)
+        lp = torch.empty(b, dtype=torch.float32, device=self.device) if want_lp or cand_d is not None else None
+        clp = None
+        if cand_d is not None:      # one lm-head pass: token, its log-probability and the candidates'
+            clp = torch.empty((b, cand_d.numel()), dtype=torch.float32, device=self.device)
+            native.check(lib.aigv_decode_step_cand_logprob(ctx, tok.data_ptr(), new.data_ptr(), lp.data_ptr(), cand_d.data_ptr(), cand_d.numel(),
+                                                           clp.data_ptr(), native.stream_ptr()), ctx)
+        elif want_lp:
+            native.check(lib.aigv_decode_step_logprob(ctx, tok.data_ptr(), new.data_ptr(), lp.data_ptr(), native.stream_ptr()), ctx)
+        else:
+            native.check(lib.aigv_decode_step(ctx, tok.data_ptr(), new.data_ptr(), native.stream_ptr()), ctx)
+        return new, lp, clp
+
     EOS_CHECK_EVERY = 8     # tokens between two host reads of the device-side "finished" flags
 
     def _greedy(self, ids_packed, slot, cu, vis, n_vis, max_new_tokens: int, eos_ids: List[int], pad_id: int, motion=None, sampler=None,
@@ -1271,10 +1278,9 @@ class InternVLChatModel(nn.Module):
         step_scores: List[torch.Tensor] = []
         step_logits: List[torch.Tensor] = []
         step_lp: List[torch.Tensor] = []
-        cur_lp: List[Optional[torch.Tensor]] = [None]      # log-probability of the current raw token (before the end-of-sequence rule)
+        cur_lp: Optional[torch.Tensor] = None      # log-probability of the current raw token (before the end-of-sequence rule)
         step_clp: List[torch.Tensor] = []
-        cur_clp: List[Optional[torch.Tensor]] = [None]     # [b, C] candidate log-probabilities of the current step
-        n_cand = 0 if cand is None else int(cand.numel())
+        cur_clp: Optional[torch.Tensor] = None     # [b, C] candidate log-probabilities of the current step
         cand_d = None if cand is None else self._h2d(cand)
 
         def eos_step(tok):
@@ -1286,6 +1292,7 @@ class InternVLChatModel(nn.Module):
 
         def pick(greedy_tok):
             """The step's raw token: the fused argmax, or - with logits processors / sampling - a choice over the rows' lm-head logits."""
+            nonlocal cur_lp, cur_clp
             if not materialise:
                 return greedy_tok
             raw = self._row_logits(b)
@@ -1304,17 +1311,14 @@ class InternVLChatModel(nn.Module):
             if want_scores:
                 step_scores.append(logits)
             if want_lp:
-                cur_lp[0] = generation.token_logprobs(logits, tok)
+                cur_lp = generation.token_logprobs(logits, tok)
             if cand_d is not None:
-                cur_clp[0] = generation.candidate_logprobs(raw, cand_d)
+                cur_clp = generation.candidate_logprobs(raw, cand_d)
             return tok
 
         tok = pick(nxt).contiguous()
-        if want_lp and not materialise:     # the first token: the prompt pass's rows, once per call
-            cur_lp[0] = torch.empty(b, dtype=torch.float32, device=self.device)
-            native.check(lib.aigv_out_row_logprob(ctx, 0, b, tok.data_ptr(), cur_lp[0].data_ptr(), native.stream_ptr()), ctx)
-        if cand_d is not None and not materialise:
-            cur_clp[0] = self._row_cand_logprob(0, b, cand_d)
+        if not materialise:     # the first token: the prompt pass's rows, once per call
+            cur_lp, cur_clp = self._row_logprobs(0, b, tok if want_lp else None, cand_d)
         for step in range(max_new_tokens):
             if want_lp or cand_d is not None:
                 live = None if not eos_ids else (state[:b] == 0)
@@ -1324,26 +1328,17 @@ class InternVLChatModel(nn.Module):
                 native.check(lib.aigv_decode_eos(ctx, tok.data_ptr(), state.data_ptr(), eos_a, len(eos_ids), int(pad_id), native.stream_ptr()), ctx)
             outs.append(tok)
             if want_lp:
-                step_lp.append(generation.mask_after_end(cur_lp[0], live))
+                step_lp.append(generation.mask_after_end(cur_lp, live))
             if cand_d is not None:
-                step_clp.append(generation.mask_after_end(cur_clp[0], live))
+                step_clp.append(generation.mask_after_end(cur_clp, live))
             if step + 1 == max_new_tokens:
                 break
             if eos_ids and (step + 1) % self.EOS_CHECK_EVERY == 0 and bool(state[:b].all()):
                 break
-            new = torch.empty_like(tok)
             if ntk_decode:
                 self._rope_for_decode(longest + step + 1)
-            if cand_d is not None and not materialise:      # one lm-head pass: token, its log-probability and the candidates'
-                cur_lp[0] = torch.empty(b, dtype=torch.float32, device=self.device)
-                cur_clp[0] = torch.empty((b, n_cand), dtype=torch.float32, device=self.device)
-                native.check(lib.aigv_decode_step_cand_logprob(ctx, tok.data_ptr(), new.data_ptr(), cur_lp[0].data_ptr(), cand_d.data_ptr(), n_cand,
-                                                               cur_clp[0].data_ptr(), native.stream_ptr()), ctx)
-            elif want_lp and not materialise:
-                cur_lp[0] = torch.empty(b, dtype=torch.float32, device=self.device)
-                native.check(lib.aigv_decode_step_logprob(ctx, tok.data_ptr(), new.data_ptr(), cur_lp[0].data_ptr(), native.stream_ptr()), ctx)
-            else:
-                native.check(lib.aigv_decode_step(ctx, tok.data_ptr(), new.data_ptr(), native.stream_ptr()), ctx)
+            fused = not materialise     # else pick() reads the step's log-probabilities off the materialised logits
+            new, cur_lp, cur_clp = self._decode_step(tok, want_lp and fused, cand_d if fused else None)
             tok = pick(new).contiguous()
         out = torch.stack(outs, dim=1)
         if eos_ids:
