@@ -163,6 +163,13 @@ __device__ __forceinline__ float lse_of_block(float m, float s) {
 
 // The lm-head's packed argmax key (skinny_kernel's SK_ARGMAX forms: order-preserving bits of the bf16-rounded logit in the high word,
 // 0xFFFFFFFF - column in the low word, so that the largest key is the first maximal column) -> (column, logit).
+__device__ __forceinline__ unsigned int ord_f32(float f) {
+  const unsigned int u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ unsigned long long argmax_key(float logit, int col) {
+  return ((unsigned long long)ord_f32(logit) << 32) | (0xFFFFFFFFu - (unsigned)col);
+}
 __device__ __forceinline__ void unpack_argmax_key(unsigned long long p, int64_t& idx, float& val) {
   unsigned int u = (unsigned)(p >> 32);
   u = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;

@@ -103,7 +103,7 @@ struct aigv_ctx {
   bf16_t* l_trim = nullptr;   // last-layer row trimming: compact [64, H] x 2 (attention out, normed) + [64, I], reused per 64 consumed rows
   bf16_t* l_trim_h = nullptr; // ... and the consumed rows' hidden states [max_out_rows + max_seqs + 64, H]
   bf16_t* l_score_ws = nullptr;
-  bf16_t* l_lp = nullptr;     // aigv_out_row_logprob: lm-head logits of 64 consumed rows [64, lp_ldo], reused per 64 rows
+  bf16_t* l_lp = nullptr;     // aigv_out_row_logprob: lm-head logits of 64 consumed rows [64, lp_ldo], reused per 64 rows; aigv_decode_step_topk_logprob: the step's logits
   int lp_ldo = 0;
   bf16_t *kc = nullptr, *vc = nullptr;   // [layer][seq][kv head][cap][D]
   bf16_t *kc_alt = nullptr, *vc_alt = nullptr;   // second cache of the same size, made by the first aigv_kv_reorder (beam search gathers into it, then the two swap)

@@ -44,10 +44,10 @@ struct RopeKvArgs {
 // workgroup (R x K elements), but no launch: the statistics' L2 round trip and barriers run behind the first weight loads.
 struct NormArgs { const bf16_t* w; float eps; };
 
-__device__ __forceinline__ unsigned int ord_f32(float f) {
-  const unsigned int u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
+// SK_ARGMAX_LSE_STORE: SK_ARGMAX_LSE that also keeps the bf16-rounded logits it reduces, for the top-k selection behind the finisher
+// (topk_of_row, logprob.hip): a lane holds 4 consecutive columns of a slab, so each (row, slab) costs one 8-byte store into
+// st.p[R][st.ld] - st.ld a multiple of 4 >= N and st.p 8-byte aligned (the launcher checks).  Key and partials are SK_ARGMAX_LSE's bits.
+struct LogitStore { bf16_t* p; int ld; };
 
 // NWV: waves per workgroup = K slices.  8 for the decode GEMVs whose N gives at most one workgroup per CU (wo, w2: 256 slabs of 16
 // rows): twice the loads in flight per CU, which is what bounds a weight stream at this occupancy (in-box A/B, scripts/decode_gemv_bench.py:
@@ -74,13 +74,13 @@ __global__ __launch_bounds__(NWV * 64) void skinny_kernel(const bf16_t* __restri
                                                      int ldr, bf16_t* __restrict__ out, int ldo,
                                                      unsigned long long* __restrict__ packed,
                                                      const bf16_t* __restrict__ ls, const RopeKvArgs rk = RopeKvArgs{},
-                                                     const NormArgs na = NormArgs{}) {
+                                                     const NormArgs na = NormArgs{}, const LogitStore st = LogitStore{}) {
   constexpr bool NORM = NC > 0;
   static_assert(!NORM || (RT == 1 && NWV == 4), "the fused norm is the decode form: one row tile, 256 threads (rmsnorm_kernel's reduction)");
   extern __shared__ __attribute__((aligned(16))) bf16_t xs[];   // NORM: the normalised x rows [R][K]
   // W slabs (16 rows each) per workgroup.  The lm-head on the answer rows (40+ x rows) is bound by re-reading the x fragments
   // from L2 once per workgroup, not by streaming W: four slabs per workgroup share them.
-  constexpr bool AMAX = EPI == SK_ARGMAX || EPI == SK_ARGMAX_LSE;
+  constexpr bool AMAX = EPI == SK_ARGMAX || EPI == SK_ARGMAX_LSE || EPI == SK_ARGMAX_LSE_STORE;
   constexpr int NS = (EPI == SK_SWIGLU || EPI == SK_ROPE_KV) ? 2 : (AMAX && RT >= 2) ? 4 : 1;
   static_assert(P == 1 || ((P == 2 || P == 4) && RT == 1 && !AMAX), "sub-slab forms: one row tile, 8 or 4 rows per slab");
   constexpr int RS = 16 / P;                         // W rows per slab (= x rows the form can take)
@@ -253,7 +253,7 @@ __global__ __launch_bounds__(NWV * 64) void skinny_kernel(const bf16_t* __restri
       unsigned long long o = __shfl_xor(best, 16, 64); best = o > best ? o : best;
       o = __shfl_xor(best, 32, 64); best = o > best ? o : best;
       if (fq == 0 && r < R) atomicMax(packed + r, best);
-      if constexpr (EPI == SK_ARGMAX_LSE) {
+      if constexpr (EPI == SK_ARGMAX_LSE || EPI == SK_ARGMAX_LSE_STORE) {
         float2* part = reinterpret_cast<float2*>(out);
 #pragma unroll
         for (int sl = 0; sl < NS; ++sl) {
@@ -264,6 +264,14 @@ __global__ __launch_bounds__(NWV * 64) void skinny_kernel(const bf16_t* __restri
           lse_combine(m, sum, __shfl_xor(m, 16, 64), __shfl_xor(sum, 16, 64));
           lse_combine(m, sum, __shfl_xor(m, 32, 64), __shfl_xor(sum, 32, 64));
           if (fq == 0 && r < R && ns0 < N) part[(size_t)r * ldo + ns0 / 16] = make_float2(m, sum);
+          if constexpr (EPI == SK_ARGMAX_LSE_STORE) {
+            if (r < R && ns0 + 4 * fq < N) {      // columns >= N of the last group are padding inside st.ld
+              u16x4 o;
+#pragma unroll
+              for (int e = 0; e < 4; ++e) o[e] = f2bf(acc[sl][t][e]);
+              *(u16x4*)(st.p + (size_t)r * st.ld + ns0 + 4 * fq) = o;
+            }
+          }
         }
       }
     } else if constexpr (EPI == SK_ROPE_KV) {
@@ -398,7 +406,7 @@ __global__ __launch_bounds__(256) void score_tail_kernel(const ScoreHeadArgs a, 
 template <int EPI>
 hipError_t launch_skinny(const bf16_t* x, int ldx, int R, const bf16_t* W, int ldw, int N, int K, const bf16_t* bias,
                          const bf16_t* resid, int ldr, bf16_t* out, int ldo, unsigned long long* packed,
-                         hipStream_t s, const bf16_t* ls = nullptr, int p = 1) {
+                         hipStream_t s, const bf16_t* ls = nullptr, int p = 1, LogitStore st = LogitStore{}) {
   const int rt = (R + 15) / 16;
   if (p > 1) {   // sub-slab forms of the decode GEMVs (skinny_kernel's P): 16 / p rows per workgroup and slab
     const int rs = 16 / p;
@@ -412,11 +420,23 @@ hipError_t launch_skinny(const bf16_t* x, int ldx, int R, const bf16_t* W, int l
       return hipErrorInvalidValue;
     }
   }
-  const int ns = (EPI == SK_SWIGLU) ? 2 : ((EPI == SK_ARGMAX || EPI == SK_ARGMAX_LSE) && rt >= 2) ? 4 : 1;   // = NS of the kernel
+  const int ns = (EPI == SK_SWIGLU) ? 2 : ((EPI == SK_ARGMAX || EPI == SK_ARGMAX_LSE || EPI == SK_ARGMAX_LSE_STORE) && rt >= 2) ? 4 : 1;   // = NS of the kernel
   const int blocks = (N + 16 * ns - 1) / (16 * ns);
   // (non-temporal weight loads were measured SLOWER on the 8B decode shapes - wqkv 12.5 -> 14.8 us, w2 24.9 -> 29.9 us, w1|w3 47.9 -> 54.9 us -
   //  and the form was removed: plain cache policy everywhere)
 #define GO(RT) hipLaunchKernelGGL((skinny_kernel<RT, EPI>), dim3(blocks), dim3(256), 0, s, x, ldx, R, W, ldw, N, K, bias, resid, ldr, out, ldo, packed, ls)
+  if constexpr (EPI == SK_ARGMAX_LSE_STORE) {
+#define GOS(RT) hipLaunchKernelGGL((skinny_kernel<RT, EPI>), dim3(blocks), dim3(256), 0, s, x, ldx, R, W, ldw, N, K, bias, resid, ldr, out, ldo, packed, ls, RopeKvArgs{}, NormArgs{}, st)
+    switch (rt) {
+      case 1: GOS(1); break;
+      case 2: GOS(2); break;
+      case 3: GOS(3); break;
+      case 4: GOS(4); break;
+      default: return hipErrorInvalidValue;
+    }
+#undef GOS
+    return hipGetLastError();
+  }
   if constexpr (EPI == SK_STORE || EPI == SK_RESID) {
     constexpr int max8 = 256;   // at most one slab per CU
     if (rt == 1 && K % 256 == 0 && blocks <= max8 && p != 0) {   // a decode GEMV with about one slab per CU: 8 K slices per workgroup (p == 0: the caller wants ONE form for every row count)
@@ -537,12 +557,17 @@ hipError_t aigv_launch_lm_head_argmax(const bf16_t* h, int R, int H, const bf16_
 size_t aigv_lm_head_lse_slots(int V) { return (size_t)(V + 15) / 16; }
 
 // the lm-head in its SK_ARGMAX_LSE form alone: the packed argmax keys and the per-slab log-sum-exp partials, for lse_finish_kernel (logprob.hip) to read
+// logits != nullptr: the SK_ARGMAX_LSE_STORE form - the same keys and partials, and the bf16 logits themselves into logits[R][ldl]
 hipError_t aigv_launch_lm_head_lse_partials(const bf16_t* h, int R, int H, const bf16_t* W, int V, unsigned long long* packed, float2* part,
-                                            hipStream_t s) {
+                                            hipStream_t s, bf16_t* logits, int ldl) {
   if (R <= 0) return hipSuccess;
   if (R > 64 || H % 128 || V < 1 || !packed || !part) return hipErrorInvalidValue;
+  if (logits && (ldl % 4 || ldl < (V + 3) / 4 * 4 || (reinterpret_cast<uintptr_t>(logits) & 7))) return hipErrorInvalidValue;
   hipError_t e = hipMemsetAsync(packed, 0, sizeof(unsigned long long) * R, s);
   if (e != hipSuccess) return e;
+  if (logits)
+    return launch_skinny<SK_ARGMAX_LSE_STORE>(h, H, R, W, H, V, H, nullptr, nullptr, 0, reinterpret_cast<bf16_t*>(part), (int)aigv_lm_head_lse_slots(V), packed, s,
+                                              nullptr, 1, LogitStore{logits, ldl});
   return launch_skinny<SK_ARGMAX_LSE>(h, H, R, W, H, V, H, nullptr, nullptr, 0, reinterpret_cast<bf16_t*>(part), (int)aigv_lm_head_lse_slots(V), packed, s);
 }
 

@@ -144,7 +144,7 @@ hipError_t aigv_launch_embed(const int64_t* ids, const int32_t* slot, const bf16
                              const bf16_t* motion, int n_vis, bf16_t* out, int tokens, int H, hipStream_t s);
 // skinny (R <= 64) weight-streaming GEMM (head.hip; e4m3 forms: head8.hip) and its epilogues; aigv_launch_skinny_gemm takes SK_STORE (+bias),
 // SK_RESID, SK_SWIGLU, SK_GELU (+bias) and SK_LS_RESID
-enum { SK_STORE = 0, SK_RESID = 1, SK_SWIGLU = 2, SK_GELU = 3, SK_ARGMAX = 4, SK_RELU = 5, SK_LS_RESID = 6, SK_ROPE_KV = 7, SK_ARGMAX_LSE = 8 };
+enum { SK_STORE = 0, SK_RESID = 1, SK_SWIGLU = 2, SK_GELU = 3, SK_ARGMAX = 4, SK_RELU = 5, SK_LS_RESID = 6, SK_ROPE_KV = 7, SK_ARGMAX_LSE = 8, SK_ARGMAX_LSE_STORE = 9 };
 hipError_t aigv_launch_skinny_gemm(const bf16_t* x, int ldx, int R, const bf16_t* W, int ldw, int N, int K,
                                    const bf16_t* bias, const bf16_t* resid, int ldr, bf16_t* out, int ldo, int epi,
                                    hipStream_t s, const bf16_t* ls = nullptr, int p = 1);
@@ -179,17 +179,27 @@ hipError_t aigv_launch_lm_head_argmax(const bf16_t* h, int R, int H, const bf16_
 // Candidates are optional (C = 0): with C <= AIGV_MAX_CANDIDATES token ids (DEVICE int64 [C]) out_cand[r, c] = bf16 logit of column cand[c] -
 // the row's log-sum-exp, NaN for an id outside [0, V); the C columns come from a GEMV over the C gathered weight rows into cand_logit, a
 // scratch of aigv_cand_logit_elems(R) bf16.  The same finisher runs either way: idx / val / logprob do not depend on the candidates.
+// Top-k is optional too (k = 0): with 1 <= k <= min(V, AIGV_MAX_TOPK) the lm-head also stores its bf16 logits into row_logit[R][ldl]
+// (ldl = aigv_topk_logit_ld(V), 8-byte aligned) and the finisher selects the k largest per row in the order of the packed argmax key -
+// logit descending, equal logits by ascending id - into top_ids / top_logprob [R, k]; top_logprob[r, 0] is out_logprob[r], bit for bit.
 #ifndef AIGV_MAX_CANDIDATES
 #define AIGV_MAX_CANDIDATES 64   // = include/aigv_amd.h
+#endif
+#ifndef AIGV_MAX_TOPK
+#define AIGV_MAX_TOPK 16         // = include/aigv_amd.h
 #endif
 size_t aigv_lm_head_lse_slots(int V);
 size_t aigv_cand_logit_elems(int R);
 hipError_t aigv_launch_lm_head_argmax_logprob(const bf16_t* h, int R, int H, const bf16_t* W, int V, unsigned long long* packed, float2* part,
                                               int64_t* out_idx, float* out_val, float* out_logprob, hipStream_t s, const int64_t* cand = nullptr,
-                                              int C = 0, bf16_t* cand_logit = nullptr, float* out_cand = nullptr);
+                                              int C = 0, bf16_t* cand_logit = nullptr, float* out_cand = nullptr, int k = 0,
+                                              bf16_t* row_logit = nullptr, int ldl = 0, int64_t* top_ids = nullptr, float* top_logprob = nullptr);
+size_t aigv_topk_logit_ld(int V);
 // the first half of aigv_launch_lm_head_argmax_logprob: the lm-head's packed argmax keys and log-sum-exp partials, no finisher
+// logits != nullptr: also the bf16-rounded logits the partials were reduced from, into logits[R][ldl] (ldl % 4 == 0, ldl >= roundup(V, 4),
+// 8-byte aligned; columns >= V of a row are padding) - the rows the decode step's top-k selection reads
 hipError_t aigv_launch_lm_head_lse_partials(const bf16_t* h, int R, int H, const bf16_t* W, int V, unsigned long long* packed, float2* part,
-                                            hipStream_t s);
+                                            hipStream_t s, bf16_t* logits = nullptr, int ldl = 0);
 // lm-head logits (bf16, the matmul output the reference upcasts) of R rows into out[R, ldo], ldo >= roundup(V, 4)
 // one_form: the 4-slice form for every row count (that of the fused argmax), so that a row's logits do not depend on how many rows
 // share the launch; otherwise <= 16 rows of a vocabulary <= 4096 take the 8-slice GEMV form
@@ -202,6 +212,10 @@ hipError_t aigv_launch_lm_head_logits(const bf16_t* h, int R, int H, const bf16_
 // Both are the one kernel, so column c of the second holds the first's bits for labels = cand[c].
 hipError_t aigv_launch_label_logprob(const bf16_t* logits, int rows, int V, int ldo, const int64_t* labels, float* out, hipStream_t s);
 hipError_t aigv_launch_cand_logprob(const bf16_t* logits, int rows, int V, int ldo, const int64_t* cand, int C, float* out, hipStream_t s);
+//   top-k:      top_ids[r, j] = column of the j-th largest logit of row r (equal logits by ascending column: the packed argmax key's order),
+//               top_logprob[r, j] = that logit - logsumexp(logits[r, :V]); 1 <= k <= min(V, AIGV_MAX_TOPK), both [rows, k].  The same fold and
+//               tree as the two above: column j holds their bits for the id it names.
+hipError_t aigv_launch_topk_logprob(const bf16_t* logits, int rows, int V, int ldo, int k, int64_t* top_ids, float* top_logprob, hipStream_t s);
 // score head: x[B,H] -> chain of Linear+ReLU (bf16 rounding after each Linear), NaN/Inf guard on x
 struct ScoreHeadArgs {
   const bf16_t* x; int ldx; int B;

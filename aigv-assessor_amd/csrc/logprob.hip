@@ -13,6 +13,10 @@
 //   finisher == finisher with candidates   one kernel; the candidates add stores after the reduction, never an operation inside it
 //   scalar == vector            VEC changes how a chunk is loaded, not which columns it holds nor the order they are pushed in
 //   alone == in a batch         nothing above reads the row count, the row's index or C before the log-sum-exp is final
+//
+// Top-k (topk_of_row below) is a third set of stores behind the same reductions: the TOPK instantiations of the two kernels run the fold and
+// lse_of_block of the plain ones and then select over the row's bf16 logits - the scoring pass's own row, or the row the lm-head's
+// SK_ARGMAX_LSE_STORE form (head.hip) kept.  The plain instantiations are the code they were.
 #include "common.h"
 #include "kernels.h"
 
@@ -20,12 +24,88 @@ namespace {
 
 constexpr int CAND_LD = AIGV_MAX_CANDIDATES;   // row stride of the decode step's candidate-logit scratch [R][CAND_LD] bf16
 
+// The k largest logits of one row and their log-probabilities, in the order of the lm-head's packed argmax key (argmax_key, common.h: bf16
+// logit descending, equal logits by ascending column) - entry 0 is the argmax token by the first-max rule, entry j the largest key strictly
+// below entry j - 1's.  The keys are a strict total order, so nothing needs an exclusion list.  Every thread keeps the TOPK_KEEP largest
+// keys of its own columns (the 4-column chunks t, t + 256, ... of the row kernel), sorted; a round takes the maximum of the threads' heads
+// over the workgroup (butterfly per wave, four wave maxima through LDS, double-buffered: one barrier per round), thread 0 stores it and
+// its owner pops it - and scans its columns again, for keys below the winner, only once its list has run dry (a row with many of its
+// largest logits in one thread's columns: rows of ties).  So a row costs one pass plus k rounds of shuffles.  Comparisons only: VEC (8-byte
+// loads of whole chunks from 8-byte aligned rows) cannot change a bit.  ids[j] / lp[j] = column and float(logit) - lse.  Called by all
+// LSE_THREADS threads of a workgroup with 1 <= k <= min(V, AIGV_MAX_TOPK); it sees one row and its log-sum-exp, never a row index or count.
+constexpr int TOPK_KEEP = 4;
+
+// top[] <- the TOPK_KEEP largest keys below `below` among this thread's columns, descending, 0 = none (no key is 0: column < 2^32 - 1)
+template <bool VEC>
+__device__ __forceinline__ void topk_scan(const bf16_t* __restrict__ row, int V, unsigned long long below, unsigned long long (&top)[TOPK_KEEP]) {
+#pragma unroll
+  for (int i = 0; i < TOPK_KEEP; ++i) top[i] = 0ull;
+#pragma unroll 4
+  for (int c = 4 * (int)threadIdx.x; c < V; c += 4 * LSE_THREADS) {
+    bf16_t x[4];
+    if (VEC && c + 4 <= V) {
+      const u16x4 v = *(const u16x4*)(row + c);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) x[j] = v[j];
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) x[j] = c + j < V ? row[c + j] : (bf16_t)0;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      unsigned long long key = argmax_key(bf2f(x[j]), c + j);
+      if (c + j < V && key < below && key > top[TOPK_KEEP - 1]) {
+#pragma unroll
+        for (int i = 0; i < TOPK_KEEP; ++i) {      // sorted insert: the key sinks to its place, the last one falls out
+          const unsigned long long hi = key > top[i] ? key : top[i];
+          key = key > top[i] ? top[i] : key;
+          top[i] = hi;
+        }
+      }
+    }
+  }
+}
+
+template <bool VEC>
+__device__ __forceinline__ void topk_of_row(const bf16_t* __restrict__ row, int V, int k, float lse, int64_t* __restrict__ ids, float* __restrict__ lp) {
+  __shared__ unsigned long long wk[2][LSE_THREADS / AIGV_WAVE];
+  const int wave = threadIdx.x / AIGV_WAVE, lane = threadIdx.x % AIGV_WAVE;
+  unsigned long long top[TOPK_KEEP];
+  topk_scan<VEC>(row, V, ~0ull, top);               // (no key is ~0 either: a bf16 logit's order word never has all bits set)
+  for (int j = 0; j < k; ++j) {
+    unsigned long long w = top[0];
+#pragma unroll
+    for (int off = AIGV_WAVE / 2; off >= 1; off >>= 1) {
+      const unsigned long long o = __shfl_xor(w, off);
+      w = o > w ? o : w;
+    }
+    if (lane == 0) wk[j & 1][wave] = w;
+    __syncthreads();
+    w = wk[j & 1][0];
+#pragma unroll
+    for (int i = 1; i < LSE_THREADS / AIGV_WAVE; ++i) w = wk[j & 1][i] > w ? wk[j & 1][i] : w;
+    if (threadIdx.x == 0) {
+      float v;
+      unpack_argmax_key(w, ids[j], v);
+      lp[j] = v - lse;
+    }
+    if (top[0] == w) {                               // keys are distinct: one owner
+#pragma unroll
+      for (int i = 0; i + 1 < TOPK_KEEP; ++i) top[i] = top[i + 1];
+      top[TOPK_KEEP - 1] = 0ull;
+      if (top[0] == 0ull && j + 1 < k) topk_scan<VEC>(row, V, w, top);
+    }
+  }
+}
+
 // out[r][t] = logits[r][id] - lse(row r) with id = ids[r * id_row_stride + t], t < C: labels are (C = 1, stride 1), candidates (C, stride 0).
 // An id outside [0, V) gives NaN.  VEC: every row start is 8-byte aligned (ldo % 4 == 0 and an aligned base): whole chunks come in as one
 // 8-byte load.  The scalar form reads the same columns in the same order - both forms give the same bits.
-template <bool VEC>
+// TOPK: the ids are optional (C = 0) and the row's k largest logits follow the same log-sum-exp (topk_of_row) into top_ids / top_lp [rows][k].
+template <bool VEC, bool TOPK = false>
 __global__ __launch_bounds__(LSE_THREADS) void row_logprob_kernel(const bf16_t* __restrict__ logits, int V, int ldo, const int64_t* __restrict__ ids,
-                                                                 int id_row_stride, int C, float* __restrict__ out) {
+                                                                 int id_row_stride, int C, float* __restrict__ out, int k = 0,
+                                                                 int64_t* __restrict__ top_ids = nullptr, float* __restrict__ top_lp = nullptr) {
   const int r = blockIdx.x;
   const bf16_t* row = logits + (size_t)r * ldo;
   float m = -INFINITY, s = 0.0f;
@@ -44,17 +124,27 @@ __global__ __launch_bounds__(LSE_THREADS) void row_logprob_kernel(const bf16_t* 
     for (int j = 0; j < 4; ++j) lse_push(m, s, x[j]);
   }
   const float lse = lse_of_block<false>(m, s);
+  if constexpr (TOPK) topk_of_row<VEC>(row, V, k, lse, top_ids + (size_t)r * k, top_lp + (size_t)r * k);
   if ((int)threadIdx.x >= C) return;
   const int64_t id = ids[(size_t)r * id_row_stride + threadIdx.x];
   out[(size_t)r * C + threadIdx.x] = (id < 0 || id >= V) ? __builtin_nanf("") : bf2f(row[id]) - lse;
+}
+
+hipError_t launch_row_topk(const bf16_t* logits, int rows, int V, int ldo, int k, int64_t* top_ids, float* top_lp, hipStream_t s) {
+  if (rows <= 0) return hipSuccess;
+  if (!logits || !top_ids || !top_lp || V < 1 || ldo < V || k < 1 || k > AIGV_MAX_TOPK || k > V) return hipErrorInvalidValue;
+  const bool vec = ldo % 4 == 0 && (reinterpret_cast<uintptr_t>(logits) & 7) == 0;
+  if (vec) hipLaunchKernelGGL((row_logprob_kernel<true, true>), dim3(rows), dim3(LSE_THREADS), 0, s, logits, V, ldo, nullptr, 0, 0, nullptr, k, top_ids, top_lp);
+  else hipLaunchKernelGGL((row_logprob_kernel<false, true>), dim3(rows), dim3(LSE_THREADS), 0, s, logits, V, ldo, nullptr, 0, 0, nullptr, k, top_ids, top_lp);
+  return hipGetLastError();
 }
 
 hipError_t launch_row_logprob(const bf16_t* logits, int rows, int V, int ldo, const int64_t* ids, int id_row_stride, int C, float* out, hipStream_t s) {
   if (rows <= 0) return hipSuccess;
   if (!logits || !ids || !out || V < 1 || ldo < V || C < 1 || C > AIGV_MAX_CANDIDATES) return hipErrorInvalidValue;
   const bool vec = ldo % 4 == 0 && (reinterpret_cast<uintptr_t>(logits) & 7) == 0;
-  if (vec) hipLaunchKernelGGL(row_logprob_kernel<true>, dim3(rows), dim3(LSE_THREADS), 0, s, logits, V, ldo, ids, id_row_stride, C, out);
-  else hipLaunchKernelGGL(row_logprob_kernel<false>, dim3(rows), dim3(LSE_THREADS), 0, s, logits, V, ldo, ids, id_row_stride, C, out);
+  if (vec) hipLaunchKernelGGL((row_logprob_kernel<true, false>), dim3(rows), dim3(LSE_THREADS), 0, s, logits, V, ldo, ids, id_row_stride, C, out);
+  else hipLaunchKernelGGL((row_logprob_kernel<false, false>), dim3(rows), dim3(LSE_THREADS), 0, s, logits, V, ldo, ids, id_row_stride, C, out);
   return hipGetLastError();
 }
 
@@ -123,11 +213,15 @@ __global__ __launch_bounds__(256) void cand_gemv_kernel(const bf16_t* __restrict
 
 // SK_ARGMAX_LSE's finisher: the lm-head's per-slab pairs part[r][0 .. nslot) -> the row's log-sum-exp; thread 0 writes idx / val (the
 // packed key's, as unpack_argmax_kernel) and logprob = val - lse.  Candidates are optional (cand == nullptr, C = 0): thread c < C writes
-// cand_logit[r][c] - lse, NaN for an id outside [0, V).
+// cand_logit[r][c] - lse, NaN for an id outside [0, V).  TOPK: the row's k largest logits, selected from the row the lm-head stored
+// (row_logit[r][ldl], 8-byte aligned rows) under this log-sum-exp - so top_lp[r][0] is logprob[r], bit for bit.
+template <bool TOPK>
 __global__ __launch_bounds__(LSE_THREADS) void lse_finish_kernel(const unsigned long long* __restrict__ packed, const float2* __restrict__ part, int nslot,
                                                                 int V, const int64_t* __restrict__ cand, int C, const bf16_t* __restrict__ cand_logit,
                                                                 int64_t* __restrict__ idx, float* __restrict__ val, float* __restrict__ logprob,
-                                                                float* __restrict__ cand_logprob) {
+                                                                float* __restrict__ cand_logprob, const bf16_t* __restrict__ row_logit = nullptr,
+                                                                int ldl = 0, int k = 0, int64_t* __restrict__ top_ids = nullptr,
+                                                                float* __restrict__ top_lp = nullptr) {
   const int r = blockIdx.x;
   const float2* row = part + (size_t)r * nslot;
   float m = -INFINITY, s = 0.f;
@@ -140,6 +234,7 @@ __global__ __launch_bounds__(LSE_THREADS) void lse_finish_kernel(const unsigned 
     const int64_t id = cand[threadIdx.x];
     cand_logprob[(size_t)r * C + threadIdx.x] = (id < 0 || id >= V) ? __builtin_nanf("") : bf2f(cand_logit[(size_t)r * CAND_LD + threadIdx.x]) - lse;
   }
+  if constexpr (TOPK) topk_of_row<true>(row_logit + (size_t)r * ldl, V, k, lse, top_ids + (size_t)r * k, top_lp + (size_t)r * k);
   if (threadIdx.x != 0) return;
   float v;
   unpack_argmax_key(packed[r], idx[r], v);
@@ -157,14 +252,22 @@ hipError_t aigv_launch_cand_logprob(const bf16_t* logits, int rows, int V, int l
   return launch_row_logprob(logits, rows, V, ldo, cand, 0, C, out, s);
 }
 
+hipError_t aigv_launch_topk_logprob(const bf16_t* logits, int rows, int V, int ldo, int k, int64_t* top_ids, float* top_logprob, hipStream_t s) {
+  return launch_row_topk(logits, rows, V, ldo, k, top_ids, top_logprob, s);
+}
+
+size_t aigv_topk_logit_ld(int V) { return (size_t)(V + 3) / 4 * 4; }
+
 size_t aigv_cand_logit_elems(int R) { return (size_t)R * CAND_LD; }
 
 hipError_t aigv_launch_lm_head_argmax_logprob(const bf16_t* h, int R, int H, const bf16_t* W, int V, unsigned long long* packed, float2* part,
                                               int64_t* out_idx, float* out_val, float* out_logprob, hipStream_t s, const int64_t* cand, int C,
-                                              bf16_t* cand_logit, float* out_cand) {
+                                              bf16_t* cand_logit, float* out_cand, int k, bf16_t* row_logit, int ldl, int64_t* top_ids,
+                                              float* top_logprob) {
   if (R <= 0) return hipSuccess;
   if (!out_idx || !out_logprob || C < 0 || C > AIGV_MAX_CANDIDATES || (C > 0 && (!cand || !cand_logit || !out_cand))) return hipErrorInvalidValue;
-  hipError_t e = aigv_launch_lm_head_lse_partials(h, R, H, W, V, packed, part, s);
+  if (k < 0 || k > AIGV_MAX_TOPK || k > V || (k > 0 && (!row_logit || !top_ids || !top_logprob))) return hipErrorInvalidValue;
+  hipError_t e = aigv_launch_lm_head_lse_partials(h, R, H, W, V, packed, part, s, k > 0 ? row_logit : nullptr, ldl);
   if (e != hipSuccess) return e;
   if (C > 0) {
     const dim3 grid((C + 15) / 16);
@@ -179,7 +282,11 @@ hipError_t aigv_launch_lm_head_argmax_logprob(const bf16_t* h, int R, int H, con
     e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(lse_finish_kernel, dim3(R), dim3(LSE_THREADS), 0, s, packed, part, (int)aigv_lm_head_lse_slots(V), V, cand, C,
-                     cand_logit, out_idx, out_val, out_logprob, out_cand);
+  if (k > 0)
+    hipLaunchKernelGGL(lse_finish_kernel<true>, dim3(R), dim3(LSE_THREADS), 0, s, packed, part, (int)aigv_lm_head_lse_slots(V), V, cand, C,
+                       cand_logit, out_idx, out_val, out_logprob, out_cand, row_logit, ldl, k, top_ids, top_logprob);
+  else
+    hipLaunchKernelGGL(lse_finish_kernel<false>, dim3(R), dim3(LSE_THREADS), 0, s, packed, part, (int)aigv_lm_head_lse_slots(V), V, cand, C,
+                       cand_logit, out_idx, out_val, out_logprob, out_cand);
   return hipGetLastError();
 }

@@ -208,23 +208,29 @@ int64_t aigv_op_lm_head_argmax_logprob_scratch_bytes(int rows, int vocab) {
   return (int64_t)(64 * sizeof(unsigned long long) + (size_t)rows * aigv_lm_head_lse_slots(vocab) * sizeof(float2));
 }
 
-// aigv_op_lm_head_argmax_logprob / aigv_op_lm_head_argmax_cand_logprob (C >= 1): every argument is checked here, before any HIP call.
-// scratch = [64 packed keys | log-sum-exp partials | (16-byte aligned) candidate logits]
+// aigv_op_lm_head_argmax_logprob / aigv_op_lm_head_argmax_cand_logprob (C >= 1) / aigv_op_lm_head_argmax_topk_logprob (k >= 1, C >= 0): every
+// argument is checked here, before any HIP call.
+// scratch = [64 packed keys | log-sum-exp partials | (16-byte aligned) candidate logits | (k >= 1: 16-byte aligned) the rows' logits]
 static int lm_head_logprob_op(const char* op, const void* h, int rows, int hidden, const void* W_, int vocab, const int64_t* cand_ids, int C, void* scratch,
-                              int64_t scratch_bytes, int64_t* idx, float* val, float* logprob, float* cand_logprob, void* stream) {
-  if (!h || !W_ || !scratch || !idx || !logprob || (C && (!cand_ids || !cand_logprob))) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+                              int64_t scratch_bytes, int64_t* idx, float* val, float* logprob, float* cand_logprob, void* stream, int k = 0,
+                              int64_t* top_ids = nullptr, float* top_logprob = nullptr) {
+  if (!h || !W_ || !scratch || !idx || !logprob || (C && (!cand_ids || !cand_logprob)) || (k && (!top_ids || !top_logprob)))
+    return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
   if (rows < 1 || rows > 64) return fail(nullptr, AIGV_ERR_ARG, "%s: rows = %d outside 1..64", op, rows);
   if (hidden < 128 || hidden % 128) return fail(nullptr, AIGV_ERR_ARG, "%s: hidden = %d is not a positive multiple of 128", op, hidden);
   if (vocab < 1) return fail(nullptr, AIGV_ERR_ARG, "%s: vocab = %d must be positive", op, vocab);
   if (((uintptr_t)h & 15) || ((uintptr_t)W_ & 15) || ((uintptr_t)scratch & 15)) return fail(nullptr, AIGV_ERR_ARG, "%s: h, W and scratch must be 16-byte aligned", op);
   const int64_t base = aigv_op_lm_head_argmax_logprob_scratch_bytes(rows, vocab);
-  const int64_t need = C ? aigv_op_lm_head_argmax_cand_logprob_scratch_bytes(rows, vocab) : base;
+  const int64_t cbytes = aigv_op_lm_head_argmax_cand_logprob_scratch_bytes(rows, vocab);
+  const int64_t need = k ? aigv_op_lm_head_argmax_topk_logprob_scratch_bytes(rows, vocab) : C ? cbytes : base;
   if (scratch_bytes < need) return fail(nullptr, AIGV_ERR_ARG, "%s: scratch of %lld bytes, needs %lld", op, (long long)scratch_bytes, (long long)need);
   unsigned long long* packed = (unsigned long long*)scratch;
   float2* part = (float2*)((char*)scratch + 64 * sizeof(unsigned long long));
   bf16_t* cl = C ? (bf16_t*)((char*)scratch + (base + 15) / 16 * 16) : nullptr;
+  bf16_t* rl = k ? (bf16_t*)((char*)scratch + (cbytes + 15) / 16 * 16) : nullptr;
   HIPCHK(nullptr, aigv_launch_lm_head_argmax_logprob((const bf16_t*)h, rows, hidden, (const bf16_t*)W_, vocab, packed, part, idx, val, logprob,
-                                                     (hipStream_t)stream, cand_ids, C, cl, cand_logprob));
+                                                     (hipStream_t)stream, cand_ids, C, cl, cand_logprob, k, rl, (int)aigv_topk_logit_ld(vocab), top_ids,
+                                                     top_logprob));
   return 0;
 }
 
@@ -260,6 +266,29 @@ int aigv_op_lm_head_argmax_cand_logprob(const void* h, int rows, int hidden, con
   const char* op = "aigv_op_lm_head_argmax_cand_logprob";
   if (C < 1 || C > AIGV_MAX_CANDIDATES) return fail(nullptr, AIGV_ERR_ARG, "%s: C = %d candidates outside 1..%d", op, C, AIGV_MAX_CANDIDATES);
   return lm_head_logprob_op(op, h, rows, hidden, W_, vocab, cand_ids, C, scratch, scratch_bytes, idx, val, logprob, cand_logprob, stream);
+}
+
+int aigv_op_topk_logprob(const void* logits_bf16, int rows, int vocab, int ldo, int k, int64_t* top_ids, float* top_logprob, void* stream) {
+  const char* op = "aigv_op_topk_logprob";
+  if (rows < 0 || vocab < 1 || ldo < vocab) return fail(nullptr, AIGV_ERR_ARG, "%s: bad argument (rows %d, vocab %d, ldo %d)", op, rows, vocab, ldo);
+  if (k < 1 || k > AIGV_MAX_TOPK || k > vocab) return fail(nullptr, AIGV_ERR_ARG, "%s: k = %d outside 1..min(%d, vocab = %d)", op, k, AIGV_MAX_TOPK, vocab);
+  if (rows > 0 && (!logits_bf16 || !top_ids || !top_logprob)) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+  HIPCHK(nullptr, aigv_launch_topk_logprob((const bf16_t*)logits_bf16, rows, vocab, ldo, k, top_ids, top_logprob, (hipStream_t)stream));
+  return 0;
+}
+
+int64_t aigv_op_lm_head_argmax_topk_logprob_scratch_bytes(int rows, int vocab) {
+  const int64_t cbytes = aigv_op_lm_head_argmax_cand_logprob_scratch_bytes(rows, vocab);   // candidates are optional: their scratch is always laid out
+  return cbytes < 0 ? -1 : (cbytes + 15) / 16 * 16 + (int64_t)((size_t)rows * aigv_topk_logit_ld(vocab) * sizeof(bf16_t));
+}
+
+int aigv_op_lm_head_argmax_topk_logprob(const void* h, int rows, int hidden, const void* W_, int vocab, int k, const int64_t* cand_ids, int C,
+                                        void* scratch, int64_t scratch_bytes, int64_t* idx, float* val, float* logprob, int64_t* top_ids,
+                                        float* top_logprob, float* cand_logprob, void* stream) {
+  const char* op = "aigv_op_lm_head_argmax_topk_logprob";
+  if (k < 1 || k > AIGV_MAX_TOPK || k > vocab) return fail(nullptr, AIGV_ERR_ARG, "%s: k = %d outside 1..min(%d, vocab = %d)", op, k, AIGV_MAX_TOPK, vocab);
+  if (cand_ids ? (C < 1 || C > AIGV_MAX_CANDIDATES) : C != 0) return fail(nullptr, AIGV_ERR_ARG, "%s: C = %d candidates outside 1..%d (0 without cand_ids)", op, C, AIGV_MAX_CANDIDATES);
+  return lm_head_logprob_op(op, h, rows, hidden, W_, vocab, cand_ids, C, scratch, scratch_bytes, idx, val, logprob, cand_logprob, stream, k, top_ids, top_logprob);
 }
 
 // ---- the decode step's kernels, one by one (test entry points): every argument is checked here, before any HIP call ----

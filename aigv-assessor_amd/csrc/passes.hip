@@ -590,10 +590,12 @@ static int decode_tail_bf16(aigv_ctx* c, const LlmLayer& L, int B, bool fused, i
 }
 
 // aigv_decode_step / aigv_decode_step_logprob (logprob != nullptr: the lm-head runs its argmax + log-sum-exp form) /
-// aigv_decode_step_cand_logprob (cand_lp != nullptr, C >= 1: the same form, with the candidates' GEMV in front of its finisher)
+// aigv_decode_step_cand_logprob (cand_lp != nullptr, C >= 1: the same form, with the candidates' GEMV in front of its finisher) /
+// aigv_decode_step_topk_logprob (topk >= 1: the lm-head keeps its bf16 logits in c->l_lp - no scoring pass is in flight on a context that
+// decodes - and the finisher selects from them; candidates stay optional)
 static int decode_step(aigv_ctx* c, const int64_t* ids, int64_t* next, float* logprob, void* stream, const int64_t* cand = nullptr, int C = 0,
-                       float* cand_lp = nullptr) {
-  const char* op = cand_lp ? "aigv_decode_step_cand_logprob" : logprob ? "aigv_decode_step_logprob" : "aigv_decode_step";
+                       float* cand_lp = nullptr, int topk = 0, int64_t* top_ids = nullptr, float* top_lp = nullptr) {
+  const char* op = topk ? "aigv_decode_step_topk_logprob" : cand_lp ? "aigv_decode_step_cand_logprob" : logprob ? "aigv_decode_step_logprob" : "aigv_decode_step";
   if (!c || !ids || !next) return fail(c, AIGV_ERR_ARG, "%s: null argument", op);
   if (!c->kv_valid) return fail(c, AIGV_ERR_STATE, "%s: no KV state (run aigv_llm_prefill with keep_kv)", op);
   const aigv_config& k = c->cfg;
@@ -661,7 +663,7 @@ static int decode_step(aigv_ctx* c, const int64_t* ids, int64_t* next, float* lo
   }
   HIPCHK(c, aigv_launch_rmsnorm(c->l_h, H, c->final_norm, c->l_rows, H, B, H, k.rms_eps, nullptr, s));
   if (logprob) HIPCHK(c, aigv_launch_lm_head_argmax_logprob(c->l_rows, B, H, c->lm_head, k.vocab, c->l_packed, c->dec_lse, next, nullptr, logprob, s, cand, C,
-                                                            c->dec_cand, cand_lp));
+                                                            c->dec_cand, cand_lp, topk, c->l_lp, c->lp_ldo, top_ids, top_lp));
   else HIPCHK(c, aigv_launch_lm_head_argmax(c->l_rows, B, H, c->lm_head, k.vocab, c->l_packed, next, nullptr, s));
   HIPCHK(c, aigv_launch_advance(c->dec_pos, c->dec_kvlen, B, s));
   for (int b = 0; b < B; ++b) c->h_kvlen[b] += 1;
@@ -681,6 +683,15 @@ int aigv_decode_step_cand_logprob(aigv_ctx* c, const int64_t* ids, int64_t* next
   if (C < 1 || C > AIGV_MAX_CANDIDATES) return fail(c, AIGV_ERR_ARG, "%s: C = %d candidates outside 1..%d", op, C, AIGV_MAX_CANDIDATES);
   if (!logprob || !cand_ids || !cand_logprob) return fail(c, AIGV_ERR_ARG, "%s: null argument", op);
   return decode_step(c, ids, next, logprob, stream, cand_ids, C, cand_logprob);
+}
+
+int aigv_decode_step_topk_logprob(aigv_ctx* c, const int64_t* ids, int64_t* next, float* logprob, int k, int64_t* top_ids, float* top_logprob,
+                                  const int64_t* cand_ids, int C, float* cand_logprob, void* stream) {
+  const char* op = "aigv_decode_step_topk_logprob";
+  if (k < 1 || k > AIGV_MAX_TOPK || (c && k > c->cfg.vocab)) return fail(c, AIGV_ERR_ARG, "%s: k = %d outside 1..min(%d, vocab)", op, k, AIGV_MAX_TOPK);
+  if (cand_ids ? (C < 1 || C > AIGV_MAX_CANDIDATES) : C != 0) return fail(c, AIGV_ERR_ARG, "%s: C = %d candidates outside 1..%d (0 without cand_ids)", op, C, AIGV_MAX_CANDIDATES);
+  if (!logprob || !top_ids || !top_logprob || (cand_ids && !cand_logprob)) return fail(c, AIGV_ERR_ARG, "%s: null argument", op);
+  return decode_step(c, ids, next, logprob, stream, cand_ids, C, cand_ids ? cand_logprob : nullptr, k, top_ids, top_logprob);
 }
 
 // What every aigv_out_row_* entry point checks before it touches the device - the handle and the caller's pointers (args_ok), finalized
@@ -708,10 +719,12 @@ int aigv_out_row_logits(aigv_ctx* c, int first_row, int n_rows, void* logits_bf1
   return 0;
 }
 
-// The loop of aigv_out_row_logprob (labels, one per row) and aigv_out_row_cand_logprob (labels == nullptr: C candidates for every row):
+// The loop of aigv_out_row_logprob (labels, one per row), aigv_out_row_cand_logprob (labels == nullptr: C candidates for every row) and
+// aigv_out_row_topk_logprob (top_ids != nullptr: the k = C largest logits of every row, their log-probabilities into out):
 // consumed rows in chunks of 64, the lm-head logits of a chunk into c->l_lp in the 4-slice form of every row count (a row's logits do
 // not depend on its chunk), then the row kernel of logprob.hip reads them.
-static int out_row_logprobs(aigv_ctx* c, int first_row, int n_rows, const int64_t* labels, const int64_t* cand, int C, float* out, hipStream_t s) {
+static int out_row_logprobs(aigv_ctx* c, int first_row, int n_rows, const int64_t* labels, const int64_t* cand, int C, float* out, hipStream_t s,
+                            int64_t* top_ids = nullptr) {
   const aigv_config& k = c->cfg;
   for (int r0 = 0; r0 < n_rows; r0 += 64) {
     const int rr = std::min(64, n_rows - r0);
@@ -721,10 +734,12 @@ static int out_row_logprobs(aigv_ctx* c, int first_row, int n_rows, const int64_
                                                 c->l_lp, c->lp_ldo, s, /*one_form=*/true);
       if (e != hipSuccess) return fail(c, e == hipErrorInvalidValue ? AIGV_ERR_ARG : AIGV_ERR_HIP, "lm-head logits (rows=%d ldo=%d): %s", rr, c->lp_ldo, hipGetErrorString(e));
     }
-    const hipError_t e = labels ? aigv_launch_label_logprob(c->l_lp, rr, k.vocab, c->lp_ldo, labels + r0, out + r0, s)
+    const hipError_t e = top_ids ? aigv_launch_topk_logprob(c->l_lp, rr, k.vocab, c->lp_ldo, C, top_ids + (size_t)r0 * C, out + (size_t)r0 * C, s)
+                         : labels ? aigv_launch_label_logprob(c->l_lp, rr, k.vocab, c->lp_ldo, labels + r0, out + r0, s)
                                 : aigv_launch_cand_logprob(c->l_lp, rr, k.vocab, c->lp_ldo, cand, C, out + (size_t)r0 * C, s);
     if (e == hipSuccess) continue;
     const int code = e == hipErrorInvalidValue ? AIGV_ERR_ARG : AIGV_ERR_HIP;
+    if (top_ids) return fail(c, code, "top-k log-probabilities (rows=%d, k=%d): %s", rr, C, hipGetErrorString(e));
     if (labels) return fail(c, code, "label log-probabilities (rows=%d): %s", rr, hipGetErrorString(e));
     return fail(c, code, "candidate log-probabilities (rows=%d, C=%d): %s", rr, C, hipGetErrorString(e));
   }
@@ -741,6 +756,13 @@ int aigv_out_row_cand_logprob(aigv_ctx* c, int first_row, int n_rows, const int6
   if (C < 1 || C > AIGV_MAX_CANDIDATES) return fail(c, AIGV_ERR_ARG, "%s: C = %d candidates outside 1..%d", op, C, AIGV_MAX_CANDIDATES);
   TRY(out_rows_begin(c, op, cand_ids && cand_logprob, first_row, n_rows));
   return out_row_logprobs(c, first_row, n_rows, nullptr, cand_ids, C, cand_logprob, (hipStream_t)stream);
+}
+
+int aigv_out_row_topk_logprob(aigv_ctx* c, int first_row, int n_rows, int k, int64_t* top_ids, float* top_logprob, void* stream) {
+  const char* op = "aigv_out_row_topk_logprob";
+  if (k < 1 || k > AIGV_MAX_TOPK || (c && k > c->cfg.vocab)) return fail(c, AIGV_ERR_ARG, "%s: k = %d outside 1..min(%d, vocab)", op, k, AIGV_MAX_TOPK);
+  TRY(out_rows_begin(c, op, top_ids && top_logprob, first_row, n_rows));
+  return out_row_logprobs(c, first_row, n_rows, nullptr, nullptr, k, top_logprob, (hipStream_t)stream, top_ids);
 }
 
 int aigv_out_row_hidden(aigv_ctx* c, int first_row, int n_rows, void* hidden_bf16, int ldo, void* stream) {

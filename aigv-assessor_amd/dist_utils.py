@@ -171,7 +171,7 @@ def all_gather_rows(local: torch.Tensor, counts: List[int], group=None) -> torch
 def score_clips_dp(model, pixel_values: torch.Tensor, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor],
                    image_flags: Optional[torch.Tensor], labels: torch.Tensor, motion_feature: Optional[torch.Tensor],
                    mos: Optional[torch.Tensor] = None, group=None, prefer_gathered: bool = False,
-                   return_logprobs: bool = False, candidate_ids=None) -> Dict[str, torch.Tensor]:
+                   return_logprobs: bool = False, candidate_ids=None, top_logprobs=None) -> Dict[str, torch.Tensor]:
     """Score a batch of B clips (F frames in total) over all ranks of `group`; every rank passes the same host
     tensors and gets the full result: {'score1' [B], 'logit' [B*(N-1)], 'label' [B*(N-1)]}.
 
@@ -179,6 +179,8 @@ def score_clips_dp(model, pixel_values: torch.Tensor, input_ids: torch.Tensor, a
     'ce_loss', computed from them with ``forward``'s expression - on one rank both are ``forward``'s own values, bit for bit.
     ``candidate_ids`` (list or LongTensor [C]): also 'cand_logprob' [B*(N-1), C] (``forward(candidate_ids=...)`` on each rank's clips, gathered
     in clip order like 'logprob').
+    ``top_logprobs`` (int k): also 'top_ids' / 'top_logprob' [B*(N-1), k] (``forward(top_logprobs=k)`` on each rank's clips, gathered in clip
+    order like 'logprob').
 
     `model` is an InternVLChatModel (or any object with vit_tokens / forward(visual_tokens=...) / device / stage).
     ``prefer_gathered``: always feed the projector / LLM pass from the ALL-GATHERED token buffer, also where the rank's own shard would
@@ -229,6 +231,9 @@ def score_clips_dp(model, pixel_values: torch.Tensor, input_ids: torch.Tensor, a
     logprob_l = torch.full(((chi - clo) * n1,), float("nan"), dtype=torch.float32, device=dev)
     n_cand = 0 if candidate_ids is None else int(candidate_ids.numel() if torch.is_tensor(candidate_ids) else len(candidate_ids))
     cand_l = torch.full(((chi - clo) * n1, n_cand), float("nan"), dtype=torch.float32, device=dev)
+    n_top = 0 if top_logprobs is None else int(top_logprobs)
+    top_ids_l = torch.full(((chi - clo) * n1, n_top), -1, dtype=torch.long, device=dev)
+    top_lp_l = torch.full(((chi - clo) * n1, n_top), float("nan"), dtype=torch.float32, device=dev)
     own = chi > clo and lo <= clo * fpc and chi * fpc <= hi and not prefer_gathered
     tokens = None if own else finish_tokens()
     if chi > clo:
@@ -237,8 +242,11 @@ def score_clips_dp(model, pixel_values: torch.Tensor, input_ids: torch.Tensor, a
                     attention_mask=None if attention_mask is None else attention_mask[sl],
                     image_flags=None if image_flags is None else image_flags[fl], labels=labels[sl],
                     motion_feature=motion_l, visual_tokens=vis, **({"return_logprobs": True} if return_logprobs else {}),
-                    **({} if candidate_ids is None else {"candidate_ids": candidate_ids}))
+                    **({} if candidate_ids is None else {"candidate_ids": candidate_ids}),
+                    **({} if top_logprobs is None else {"top_logprobs": top_logprobs}))
         logit_l = out["logit"]
+        if top_logprobs is not None:
+            top_ids_l, top_lp_l = out["top_ids"], out["top_logprob"]
         if candidate_ids is not None:
             cand_l = out["cand_logprob"]
         if return_logprobs:
@@ -262,6 +270,9 @@ def score_clips_dp(model, pixel_values: torch.Tensor, input_ids: torch.Tensor, a
             res["ce_loss"] = torch.full((), float("nan"), dtype=torch.float32, device=logprob.device)
     if candidate_ids is not None:
         res["cand_logprob"] = all_gather_rows(cand_l.view(chi - clo, n1 * n_cand), counts, group).reshape(-1, n_cand)
+    if top_logprobs is not None:
+        res["top_ids"] = all_gather_rows(top_ids_l.view(chi - clo, n1 * n_top), counts, group).reshape(-1, n_top)
+        res["top_logprob"] = all_gather_rows(top_lp_l.view(chi - clo, n1 * n_top), counts, group).reshape(-1, n_top)
     if getattr(model, "stage", 2) == 2:
         res["score1"] = score.to(torch.bfloat16)
     return res

@@ -126,7 +126,8 @@ def expected_level(cand_logprob, weights=(1, 2, 3, 4, 5)):
     return (torch.softmax(cand_logprob, -1) * w).sum(-1)
 
 
-def batched(items, model, k: int = 4, frames=None, ahead: bool = True, pad_id: int = 2, return_logprobs: bool = False, candidate_ids=None):
+def batched(items, model, k: int = 4, frames=None, ahead: bool = True, pad_id: int = 2, return_logprobs: bool = False, candidate_ids=None,
+            top_logprobs=None):
     """The reference's eval loop at batch ``k`` instead of batch 1: yields ``(item, output)`` for EVERY item of ``items`` (the loop's
     ``DataLoader(batch_size=1)`` items: ``input_ids`` / ``attention_mask`` / ``labels`` [1, N_i] with N_i ragged, ``image_flags``
     [1, T, 1], ``pixel_values`` [1, T, 3, S, S] or what ``frames(item)`` returns - uint8 [T, H, W, 3] decoded frames are ingested on the
@@ -150,7 +151,10 @@ def batched(items, model, k: int = 4, frames=None, ahead: bool = True, pad_id: i
     item's own pass) and its own ``ce_loss``, ``-(logprob[label != -100]).double().mean().float()`` (NaN without answer labels).
 
     ``candidate_ids``: ``model(..., candidate_ids=...)`` per group; each item's output adds ``cand_logprob`` [N_i - 1, C], bit for bit the
-    item's own pass."""
+    item's own pass.
+
+    ``top_logprobs``: ``model(..., top_logprobs=k)`` per group; each item's output adds ``top_ids`` / ``top_logprob`` [N_i - 1, k], bit for
+    bit the item's own pass."""
     import torch
     import torch.nn.functional as F
     if k < 1:
@@ -199,7 +203,8 @@ def batched(items, model, k: int = 4, frames=None, ahead: bool = True, pad_id: i
                     attention_mask=torch.stack([pad(m, False) for m in masks]), image_flags=flags,
                     labels=torch.stack([pad(l, -100) for l in labels]), **({} if motion is None else {"motion_feature": motion}),
                     **({"return_logprobs": True} if return_logprobs else {}),
-                    **({} if candidate_ids is None else {"candidate_ids": candidate_ids}))
+                    **({} if candidate_ids is None else {"candidate_ids": candidate_ids}),
+                    **({} if top_logprobs is None else {"top_logprobs": top_logprobs}))
         return group, n, nmax, out
 
     def collect(run):
@@ -211,6 +216,8 @@ def batched(items, model, k: int = 4, frames=None, ahead: bool = True, pad_id: i
         score1 = out["score1"].cpu() if "score1" in out else None
         logprob = out["logprob"].view(len(group), nmax - 1).cpu() if return_logprobs else None
         cand = out["cand_logprob"].view(len(group), nmax - 1, -1).cpu() if candidate_ids is not None else None
+        top_ids = out["top_ids"].view(len(group), nmax - 1, -1).cpu() if top_logprobs is not None else None
+        top_lp = out["top_logprob"].view(len(group), nmax - 1, -1).cpu() if top_logprobs is not None else None
         for b, (it, _) in enumerate(group):
             o = {"logit": logit[b, : n[b] - 1].clone(), "label": label[b, : n[b] - 1].clone()}
             if logprob is not None:
@@ -218,6 +225,9 @@ def batched(items, model, k: int = 4, frames=None, ahead: bool = True, pad_id: i
                 o["ce_loss"] = (-o["logprob"][o["label"] != -100]).double().mean().float()
             if cand is not None:
                 o["cand_logprob"] = cand[b, : n[b] - 1].clone()
+            if top_ids is not None:
+                o["top_ids"] = top_ids[b, : n[b] - 1].clone()
+                o["top_logprob"] = top_lp[b, : n[b] - 1].clone()
             if score1 is not None:
                 o["score1"] = score1[b: b + 1].clone()
                 mos = it.get("mos")

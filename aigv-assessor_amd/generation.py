@@ -12,7 +12,7 @@ from typing import Dict, Optional, Sequence
 import torch
 
 FLAGS = ("return_dict_in_generate", "output_scores", "output_logits", "return_logprobs")
-FIELDS = ("sequences", "sequences_scores", "scores", "logits", "logprobs", "cand_logprobs")
+FIELDS = ("sequences", "sequences_scores", "scores", "logits", "logprobs", "cand_logprobs", "top_ids", "top_logprobs")
 
 
 class GenerateOutput(dict):
@@ -26,6 +26,9 @@ class GenerateOutput(dict):
                        (``compute_transition_scores(sequences, scores, normalize_logits=True)``), NaN after the sequence's end token
     cand_logprobs      (candidate_ids) fp32 [B, T, C]: full-vocabulary log-probability of each candidate token at each step under the RAW
                        lm-head logits (before logits processors / sampling warpers), NaN after the sequence's end token
+    top_ids            (top_logprobs=k) long [B, T, k]: the ids of the k largest RAW lm-head logits of each step, equal logits by ascending
+                       id (entry 0 is the greedy token), -1 after the sequence's end token
+    top_logprobs       (top_logprobs=k) fp32 [B, T, k]: their full-vocabulary log-probabilities, NaN after the sequence's end token
     sequences_scores   (beam search) fp32 [B]: HF's length-penalised score of the returned hypothesis
     A field that was not asked for is absent from the keys and reads as None, as in transformers' output classes."""
 
@@ -67,6 +70,23 @@ def candidate_logprobs(raw_logits: torch.Tensor, cand: torch.Tensor) -> torch.Te
     return torch.where(ok.view(1, -1), lp, torch.full_like(lp, float("nan")))
 
 
+def top_logprobs(raw_logits: torch.Tensor, k: int):
+    """(long [B, k], fp32 [B, k]): the ids of the k largest ``raw_logits.float()`` of every row - equal logits by ascending id: the first k
+    of a stable descending sort, the order of the lm-head's fused argmax - and ``log_softmax(raw_logits.float())`` at them."""
+    x = raw_logits.float()
+    if not 1 <= int(k) <= x.shape[-1]:
+        raise ValueError(f"top_logprobs: k = {k} outside 1..{x.shape[-1]}")
+    ids = torch.sort(x, dim=-1, descending=True, stable=True).indices[..., : int(k)].contiguous()
+    return ids, torch.log_softmax(x, dim=-1).gather(-1, ids)
+
+
+def mask_ids_after_end(ids: torch.Tensor, live: Optional[torch.Tensor]) -> torch.Tensor:
+    """mask_after_end for token ids: -1 where the sequence had already ended."""
+    if live is None:
+        return ids
+    return torch.where(live.view(-1, *([1] * (ids.dim() - 1))), ids, torch.full_like(ids, -1))
+
+
 def mask_after_end(logprob: torch.Tensor, live: Optional[torch.Tensor]) -> torch.Tensor:
     """A column's log-probabilities ([B] or [B, C]) with NaN where the sequence had already ended before it (``live`` False; None = all live)."""
     if live is None:
@@ -76,7 +96,8 @@ def mask_after_end(logprob: torch.Tensor, live: Optional[torch.Tensor]) -> torch
 
 def build(sequences: torch.Tensor, flags: Dict[str, bool], scores: Sequence[torch.Tensor] = (), logits: Sequence[torch.Tensor] = (),
           logprobs: Sequence[torch.Tensor] = (), sequences_scores: Optional[torch.Tensor] = None,
-          cand_logprobs: Optional[Sequence[torch.Tensor]] = None) -> GenerateOutput:
+          cand_logprobs: Optional[Sequence[torch.Tensor]] = None, top_ids: Optional[Sequence[torch.Tensor]] = None,
+          top_logprobs: Optional[Sequence[torch.Tensor]] = None) -> GenerateOutput:
     """The output object of one generate call; per-step lists are cut to the returned length."""
     T = sequences.shape[1]
     out = GenerateOutput(sequences=sequences)
@@ -89,6 +110,9 @@ def build(sequences: torch.Tensor, flags: Dict[str, bool], scores: Sequence[torc
         out["logprobs"] = torch.stack(lp, dim=1) if lp else torch.empty((sequences.shape[0], 0), dtype=torch.float32, device=sequences.device)
     if cand_logprobs is not None:       # candidate_ids: T x [B, C] -> [B, T, C]
         out["cand_logprobs"] = torch.stack(list(cand_logprobs[:T]), dim=1)
+    if top_ids is not None:             # top_logprobs=k: T x [B, k] -> [B, T, k]
+        out["top_ids"] = torch.stack(list(top_ids[:T]), dim=1)
+        out["top_logprobs"] = torch.stack(list(top_logprobs[:T]), dim=1)
     if sequences_scores is not None:
         out["sequences_scores"] = sequences_scores
     return out

@@ -697,7 +697,7 @@ class InternVLChatModel(nn.Module):
                 labels: Optional[torch.Tensor] = None, use_cache=None, output_attentions=None,
                 output_hidden_states=None, return_dict=None, motion_feature: Optional[torch.Tensor] = None,
                 visual_tokens: Optional[torch.Tensor] = None, full_logits: bool = False, return_logprobs: bool = False,
-                candidate_ids=None):
+                candidate_ids=None, top_logprobs: Optional[int] = None):
         """Stage-2 eval pass (modeling_internvl_chat.py:306-488) or, with ``stage=1``, the stage-1 pass
         (internvl_chat_eval1/modeling_internvl_chat.py:250-366).  ``visual_tokens`` optionally supplies
         already all-gathered pre-projector tokens (frame-DP) instead of ``pixel_values``.
@@ -715,7 +715,14 @@ class InternVLChatModel(nn.Module):
         ``eval_utils.expected_level`` its mean level, from ONE pass.  An id outside [0, vocab) gives a NaN column.  Needs ``labels`` (they
         say which rows are answer rows) under ``return_logprobs``' label rules, with or without ``return_logprobs``.  The ids are a device
         input of a replayed graph: other VALUES replay the same graph, another C is another graph.  fp8 mode: the lm-head stays bf16
-        there, so the same kernels serve."""
+        there, so the same kernels serve.
+
+        ``top_logprobs=k`` (int, 1 <= k <= 16) adds what the model preferred at every answer row: ``top_ids`` (int64 [B (N - 1), k], -1
+        rows wherever the label is -100) - the ids of the k largest bf16 logits, equal logits by ascending id, i.e. the first k of
+        ``torch.sort(logits.float(), descending=True, stable=True)``; column 0 is ``logit`` - and ``top_logprob`` (fp32, same shape, NaN
+        rows there): their full-vocabulary log-probabilities, bit for bit what ``candidate_ids=top_ids[row]`` gives.  Needs ``labels``
+        under ``return_logprobs``' label rules.  The three options combine freely and none changes another's bits; under graph replay k
+        is part of the graph's key (it is an output shape)."""
         if position_ids is not None or past_key_values is not None:
             raise NotImplementedError("the eval pass takes default positions and no cache, like the reference drivers")
         if self.img_context_token_id is None:
@@ -723,7 +730,7 @@ class InternVLChatModel(nn.Module):
         pixel_values, visual_tokens, motion_feature = self._take_ahead(pixel_values, visual_tokens, motion_feature)
         if self._graph_replay_enabled and self._capture_keep is None:
             out = self._forward_through_graph(mos, pixel_values, input_ids, attention_mask, image_flags, labels, motion_feature, visual_tokens, full_logits,
-                                              return_logprobs, candidate_ids)
+                                              return_logprobs, candidate_ids, top_logprobs)
             if out is not None:
                 return out
         B, N = input_ids.shape
@@ -732,7 +739,8 @@ class InternVLChatModel(nn.Module):
         # every kernel of the step can then be enqueued back to back without a host sync in between ----
         plan = self._plan(input_ids, attention_mask, labels, image_flags, n_frames, full_logits)
         cand = self._candidates(candidate_ids, labels)
-        lp_labels = self._logprob_labels(plan) if return_logprobs or cand is not None else None
+        topk = self._top_logprobs_k(top_logprobs, self.config.llm_config.vocab_size, labels)
+        lp_labels = self._logprob_labels(plan) if return_logprobs or cand is not None or topk else None
         motion_feature = self._motion_feature(pixel_values, B, motion_feature)
 
         # ---- device work: ViT -> projector -> motion projector -> LLM pass + heads ----
@@ -741,7 +749,8 @@ class InternVLChatModel(nn.Module):
         score, amax = self._prefill(plan["ids_packed"], plan["slot"], plan["cu"], vit_embeds, plan["n_vis"], motion,
                                     plan["score_rows"], plan["logit_rows"])
         lp, clp = self._row_logprobs(B if score is not None else 0, len(plan["logit_rows"]), lp_labels if return_logprobs else None, cand)
-        return self._outputs(plan, B, N, score, amax, mos, lp, clp)
+        top = self._row_topk(B if score is not None else 0, len(plan["logit_rows"]), topk) if topk else None
+        return self._outputs(plan, B, N, score, amax, mos, lp, clp, top)
 
     # ---- HIP-graph replay of whole scoring passes (opt-in: enable_graph_replay) ---------------------------------------------------------
     _graph_replay_enabled = False
@@ -876,7 +885,7 @@ class InternVLChatModel(nn.Module):
         return cl(outputs)
 
     def _forward_through_graph(self, mos, pixel_values, input_ids, attention_mask, image_flags, labels, motion_feature, visual_tokens, full_logits,
-                               return_logprobs=False, candidate_ids=None):
+                               return_logprobs=False, candidate_ids=None, top_logprobs=None):
         """The replay path of ``forward``; returns None when the call does not qualify (the eager path then runs)."""
         src = visual_tokens if visual_tokens is not None else pixel_values
         if self._rope_seq_len(int(input_ids.shape[1])) != getattr(self, "_rope_ntk", 0):
@@ -895,6 +904,9 @@ class InternVLChatModel(nn.Module):
         if cand is not None:
             host_key += ("candidates",)      # (their number is in the key with the device inputs' shapes; their values are graph INPUT)
             cand = self._h2d(cand)
+        topk = self._top_logprobs_k(top_logprobs, self.config.llm_config.vocab_size, labels)
+        if topk:
+            host_key += (("top_logprobs", topk),)   # (k is an output shape: another k is another graph)
         self._join_side_stream()             # (a motion feature started by motion_feature_async: joined BEFORE the graph copies it in)
         self._prepare_motion_branch(pixel_values if (motion_feature is None and visual_tokens is None) else None, int(input_ids.shape[0]))
 
@@ -902,7 +914,7 @@ class InternVLChatModel(nn.Module):
             return self.forward(mos=None, pixel_values=None if visual_tokens is not None else src_static, input_ids=input_ids, attention_mask=attention_mask,
                                 image_flags=image_flags, labels=labels, motion_feature=mf_static, full_logits=full_logits,
                                 visual_tokens=src_static if visual_tokens is not None else None, return_logprobs=return_logprobs,
-                                candidate_ids=cand_static)
+                                candidate_ids=cand_static, top_logprobs=top_logprobs)
         return self._graph_call(host_key, [src, motion_feature, cand], fn)
 
     def dp_front(self, frames_local: torch.Tensor, frames_clips: Optional[torch.Tensor], n_clips: int):
@@ -1043,7 +1055,7 @@ class InternVLChatModel(nn.Module):
             vit_embeds = vit_embeds[self._h2d(plan["keep"])]
         return vit_embeds.reshape(-1, H), self.motion_embed(motion_feature)
 
-    def _outputs(self, plan, B, N, score, amax, mos, lp=None, clp=None):
+    def _outputs(self, plan, B, N, score, amax, mos, lp=None, clp=None, top=None):
         dev = self.device
         up = self._h2d   # host -> device through pinned memory, never blocking the host (keeps the CPU ahead of the GPU)
         idx = up(plan["want"].reshape(-1).nonzero().flatten()) if len(plan["logit_rows"]) else None   # index list built on the host: no sync
@@ -1067,9 +1079,32 @@ class InternVLChatModel(nn.Module):
                 out["ce_loss"] = torch.full((), float("nan"), dtype=torch.float32, device=dev)
         if clp is not None:                         # candidate_ids: rows scattered like `logit`, NaN rows elsewhere
             out["cand_logprob"] = scatter(clp, float("nan"))
+        if top is not None:                         # top_logprobs: -1 / NaN rows elsewhere - wherever the label is -100, also under full_logits
+            ids_k, lp_k = top
+            answer = plan["labels_h"][..., 1:][plan["want"]] != -100      # (host: no sync)
+            if not bool(answer.all()):
+                answer = up(answer).view(-1, 1)
+                ids_k, lp_k = torch.where(answer, ids_k, torch.full_like(ids_k, -1)), torch.where(answer, lp_k, torch.full_like(lp_k, float("nan")))
+            out["top_ids"] = scatter(ids_k, -1)
+            out["top_logprob"] = scatter(lp_k, float("nan"))
         return out
 
     MAX_CANDIDATES = 64      # = AIGV_MAX_CANDIDATES
+    MAX_TOPK = 16            # = AIGV_MAX_TOPK
+
+    @staticmethod
+    def _top_logprobs_k(top_logprobs, vocab: int, labels="given") -> int:
+        """``top_logprobs`` (None or an int k, 1 <= k <= min(16, vocab)) -> k, 0 for None."""
+        if top_logprobs is None:
+            return 0
+        if labels is None:
+            raise ValueError("top_logprobs: needs labels (they mark the answer rows whose distribution is read)")
+        k = top_logprobs
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= InternVLChatModel.MAX_TOPK:
+            raise ValueError(f"top_logprobs: expected an int in 1..{InternVLChatModel.MAX_TOPK}, got {k!r}")
+        if k > vocab:
+            raise ValueError(f"top_logprobs: k = {k} exceeds the vocabulary ({vocab} tokens)")
+        return k
 
     @staticmethod
     def _candidates(candidate_ids, labels="given") -> Optional[torch.Tensor]:
@@ -1114,6 +1149,16 @@ class InternVLChatModel(nn.Module):
                                                                  native.stream_ptr()), self._ctx)
         return lp, clp
 
+    def _row_topk(self, first_row: int, R: int, k: int):
+        """(top_ids int64 [R, k], top_logprob fp32 [R, k]) of consumed rows first_row .. first_row + R - 1 of the last native pass
+        (aigv_out_row_topk_logprob): the k largest bf16 logits of every row, equal logits by ascending id, under _row_logprobs' log-sum-exp."""
+        ids = torch.empty((max(R, 1), k), dtype=torch.long, device=self.device)[:R]
+        lp = torch.empty((max(R, 1), k), dtype=torch.float32, device=self.device)[:R]
+        if R:
+            native.check(native.load().aigv_out_row_topk_logprob(self._ctx, int(first_row), R, int(k), ids.data_ptr(), lp.data_ptr(), native.stream_ptr()),
+                         self._ctx)
+        return ids, lp
+
     @staticmethod
     def _shared_prefix_lengths(plans, B: int) -> List[int]:
         """Per clip: the number of leading tokens every prompt shares, capped so that every consumed row (answer rows, score
@@ -1140,7 +1185,7 @@ class InternVLChatModel(nn.Module):
 
     def forward_shared_prefix(self, prompts, pixel_values: Optional[torch.Tensor] = None, image_flags: Optional[torch.Tensor] = None,
                               motion_feature: Optional[torch.Tensor] = None, visual_tokens: Optional[torch.Tensor] = None, mos=None,
-                              return_logprobs: bool = False, candidate_ids=None):
+                              return_logprobs: bool = False, candidate_ids=None, top_logprobs: Optional[int] = None):
         """Score the same clips under several prompts that share their beginning - the reference's four quality
         perspectives ask four questions BEHIND the same system + frame + motion tokens (8f-3) and
         run four full passes (stage2_eval.py evaluates one jsonl per perspective).  Here the common prefix runs once
@@ -1150,7 +1195,8 @@ class InternVLChatModel(nn.Module):
         independent of what follows, so each result is that of a separate ``forward`` call up to kernel summation order.
         ``return_logprobs``: every prompt's dict carries ``logprob`` and ``ce_loss`` as ``forward`` defines them - with candidate answers
         as the prompts, their log-likelihoods behind one video prefix (README).  ``candidate_ids``: every prompt's dict carries
-        ``cand_logprob`` as ``forward`` defines it (the same candidates for every prompt)."""
+        ``cand_logprob`` as ``forward`` defines it (the same candidates for every prompt).  ``top_logprobs``: every prompt's dict carries
+        ``top_ids`` / ``top_logprob`` as ``forward`` defines them."""
         if self.img_context_token_id is None:
             raise AssertionError("img_context_token_id must be set by the caller (stage2_eval.py:810)")
         if not prompts:
@@ -1159,7 +1205,8 @@ class InternVLChatModel(nn.Module):
         n_frames = visual_tokens.shape[0] if visual_tokens is not None else pixel_values.shape[0]
         plans = [self._plan(ids, am, lab, image_flags, n_frames) for (ids, am, lab) in prompts]
         cand = self._candidates(candidate_ids)
-        lp_labels = [self._logprob_labels(pl) for pl in plans] if return_logprobs or cand is not None else None
+        topk = self._top_logprobs_k(top_logprobs, self.config.llm_config.vocab_size)
+        lp_labels = [self._logprob_labels(pl) for pl in plans] if return_logprobs or cand is not None or topk else None
         B = prompts[0][0].shape[0]
         pre = self._shared_prefix_lengths(plans, B)
         p0 = plans[0]
@@ -1205,24 +1252,33 @@ class InternVLChatModel(nn.Module):
                                          native.i32_array(lrows) if lrows else None, len(lrows), amax.data_ptr(), 0,
                                          native.stream_ptr()), ctx)
         lp, clp = self._row_logprobs(len(srows), len(lrows), torch.cat(lp_labels) if return_logprobs else None, cand)   # rows [score rows | logit rows]
+        top = self._row_topk(len(srows), len(lrows), topk) if topk else None
         outs, off = [], 0
         for p, (pl, (ids, _, _)) in enumerate(zip(plans, prompts)):
             outs.append(self._outputs(pl, B, ids.shape[1], score[p * B:(p + 1) * B] if score is not None else None,
                                       amax[off:off + n_l[p]], mos, lp[off:off + n_l[p]] if lp is not None else None,
-                                      clp[off:off + n_l[p]] if clp is not None else None))
+                                      clp[off:off + n_l[p]] if clp is not None else None,
+                                      (top[0][off:off + n_l[p]], top[1][off:off + n_l[p]]) if top is not None else None))
             off += n_l[p]
         return outs
 
     # ---- generation (API surface; greedy) -------------------------------------------------------------------
-    def _decode_step(self, tok: torch.Tensor, want_lp: bool = False, cand_d: Optional[torch.Tensor] = None):
-        """One native decode step for the current tokens ``tok`` [b] -> (next tokens, lp, clp): with ``want_lp`` or candidates (device int64 [C])
-        the lm-head pass that picks the token also gives its fp32 log-probability [b] and the candidates' [b, C]; None for what the step
-        did not compute."""
+    def _decode_step(self, tok: torch.Tensor, want_lp: bool = False, cand_d: Optional[torch.Tensor] = None, topk: int = 0):
+        """One native decode step for the current tokens ``tok`` [b] -> (next tokens, lp, clp, top): with ``want_lp`` or candidates (device
+        int64 [C]) the lm-head pass that picks the token also gives its fp32 log-probability [b] and the candidates' [b, C]; with ``topk`` also
+        top = (ids int64 [b, k], log-probabilities fp32 [b, k]) of the k largest logits; None for what the step did not compute."""
         lib, ctx, b = native.load(), self._ctx, tok.numel()
         new = torch.empty_like(tok)
-        lp = torch.empty(b, dtype=torch.float32, device=self.device) if want_lp or cand_d is not None else None
-        clp = None
-        if cand_d is not None:      # one lm-head pass: token, its log-probability and the candidates'
+        lp = torch.empty(b, dtype=torch.float32, device=self.device) if want_lp or cand_d is not None or topk else None
+        clp = top = None
+        if topk:                    # one lm-head pass: token, its log-probability, the k most likely tokens and (optionally) the candidates
+            top = (torch.empty((b, topk), dtype=torch.long, device=self.device), torch.empty((b, topk), dtype=torch.float32, device=self.device))
+            if cand_d is not None:
+                clp = torch.empty((b, cand_d.numel()), dtype=torch.float32, device=self.device)
+            native.check(lib.aigv_decode_step_topk_logprob(ctx, tok.data_ptr(), new.data_ptr(), lp.data_ptr(), int(topk), top[0].data_ptr(),
+                                                           top[1].data_ptr(), native.ptr(cand_d), 0 if cand_d is None else cand_d.numel(),
+                                                           native.ptr(clp), native.stream_ptr()), ctx)
+        elif cand_d is not None:    # one lm-head pass: token, its log-probability and the candidates'
             clp = torch.empty((b, cand_d.numel()), dtype=torch.float32, device=self.device)
             native.check(lib.aigv_decode_step_cand_logprob(ctx, tok.data_ptr(), new.data_ptr(), lp.data_ptr(), cand_d.data_ptr(), cand_d.numel(),
                                                            clp.data_ptr(), native.stream_ptr()), ctx)
@@ -1230,12 +1286,12 @@ class InternVLChatModel(nn.Module):
             native.check(lib.aigv_decode_step_logprob(ctx, tok.data_ptr(), new.data_ptr(), lp.data_ptr(), native.stream_ptr()), ctx)
         else:
             native.check(lib.aigv_decode_step(ctx, tok.data_ptr(), new.data_ptr(), native.stream_ptr()), ctx)
-        return new, lp, clp
+        return new, lp, clp, top
 
     EOS_CHECK_EVERY = 8     # tokens between two host reads of the device-side "finished" flags
 
     def _greedy(self, ids_packed, slot, cu, vis, n_vis, max_new_tokens: int, eos_ids: List[int], pad_id: int, motion=None, sampler=None,
-                processors=None, beams=None, flags=None, cand=None):
+                processors=None, beams=None, flags=None, cand=None, topk: int = 0):
         """The token loop of generate(): HF's greedy search / multinomial sampling loop (the reference calls ``language_model.generate``,
         modeling_internvl_chat.py:798-809).  The end-of-sequence bookkeeping runs on the device (aigv_decode_eos): a finished sequence
         emits ``pad_id``, the loop stops once every sequence has emitted an end token - checked by the host only every EOS_CHECK_EVERY
@@ -1248,10 +1304,14 @@ class InternVLChatModel(nn.Module):
 
         ``cand`` (int64 [C], ``candidate_ids``): ``cand_logprobs`` [B, T, C], the full-vocabulary log-probabilities of the candidates at every
         step - from the fused decode step (aigv_decode_step_cand_logprob; the first token's from aigv_out_row_cand_logprob) on the greedy
-        path without processors, else the log-softmax of the step's RAW logits (before processors and warpers) at the candidates."""
+        path without processors, else the log-softmax of the step's RAW logits (before processors and warpers) at the candidates.
+
+        ``topk`` (``top_logprobs=k``): ``top_ids`` / ``top_logprobs`` [B, T, k], the k most likely tokens of every step under the RAW logits -
+        from the fused decode step (aigv_decode_step_topk_logprob; the first token's from aigv_out_row_topk_logprob) on the greedy path
+        without processors, else generation.top_logprobs of the step's raw logits."""
         from . import generation
         flags = flags or {k: False for k in generation.FLAGS}
-        dict_out = generation.wants_output(flags) or cand is not None
+        dict_out = generation.wants_output(flags) or cand is not None or bool(topk)
         b = len(cu) - 1
         longest = max(cu[i + 1] - cu[i] for i in range(b))
         last_rows = [cu[i + 1] - 1 for i in range(b)]
@@ -1282,6 +1342,8 @@ class InternVLChatModel(nn.Module):
         step_clp: List[torch.Tensor] = []
         cur_clp: Optional[torch.Tensor] = None     # [b, C] candidate log-probabilities of the current step
         cand_d = None if cand is None else self._h2d(cand)
+        step_top: List[tuple] = []
+        cur_top = None                             # ([b, k] ids, [b, k] log-probabilities) of the current step
 
         def eos_step(tok):
             live = state[:b] == 0
@@ -1292,7 +1354,7 @@ class InternVLChatModel(nn.Module):
 
         def pick(greedy_tok):
             """The step's raw token: the fused argmax, or - with logits processors / sampling - a choice over the rows' lm-head logits."""
-            nonlocal cur_lp, cur_clp
+            nonlocal cur_lp, cur_clp, cur_top
             if not materialise:
                 return greedy_tok
             raw = self._row_logits(b)
@@ -1314,13 +1376,16 @@ class InternVLChatModel(nn.Module):
                 cur_lp = generation.token_logprobs(logits, tok)
             if cand_d is not None:
                 cur_clp = generation.candidate_logprobs(raw, cand_d)
+            if topk:
+                cur_top = generation.top_logprobs(raw, topk)
             return tok
 
         tok = pick(nxt).contiguous()
         if not materialise:     # the first token: the prompt pass's rows, once per call
             cur_lp, cur_clp = self._row_logprobs(0, b, tok if want_lp else None, cand_d)
+            cur_top = self._row_topk(0, b, topk) if topk else None
         for step in range(max_new_tokens):
-            if want_lp or cand_d is not None:
+            if want_lp or cand_d is not None or topk:
                 live = None if not eos_ids else (state[:b] == 0)
             if host_eos:
                 tok = eos_step(tok).contiguous()
@@ -1331,6 +1396,8 @@ class InternVLChatModel(nn.Module):
                 step_lp.append(generation.mask_after_end(cur_lp, live))
             if cand_d is not None:
                 step_clp.append(generation.mask_after_end(cur_clp, live))
+            if topk:
+                step_top.append((generation.mask_ids_after_end(cur_top[0], live), generation.mask_after_end(cur_top[1], live)))
             if step + 1 == max_new_tokens:
                 break
             if eos_ids and (step + 1) % self.EOS_CHECK_EVERY == 0 and bool(state[:b].all()):
@@ -1338,14 +1405,17 @@ class InternVLChatModel(nn.Module):
             if ntk_decode:
                 self._rope_for_decode(longest + step + 1)
             fused = not materialise     # else pick() reads the step's log-probabilities off the materialised logits
-            new, cur_lp, cur_clp = self._decode_step(tok, want_lp and fused, cand_d if fused else None)
+            new, cur_lp, cur_clp, top = self._decode_step(tok, want_lp and fused, cand_d if fused else None, topk if fused else 0)
+            if fused:
+                cur_top = top
             tok = pick(new).contiguous()
         out = torch.stack(outs, dim=1)
         if eos_ids:
             out = out[:, : max(1, int(state[b].item()))]     # HF stops after the column in which the last live sequence ended
         if dict_out:
             return generation.build(out, flags, scores=step_scores, logits=step_logits, logprobs=step_lp,
-                                    cand_logprobs=step_clp if cand_d is not None else None)
+                                    cand_logprobs=step_clp if cand_d is not None else None,
+                                    top_ids=[t[0] for t in step_top] if topk else None, top_logprobs=[t[1] for t in step_top] if topk else None)
         return out
 
     def _beam_decode(self, b: int, prompt_lens: List[int], max_new_tokens: int, eos_ids: List[int], pad_id, processors, num_beams: int,
@@ -1424,14 +1494,15 @@ class InternVLChatModel(nn.Module):
         return int(cfg.get("max_new_tokens") or 20), eos, cfg.get("pad_token_id"), sampler, processors, beams
 
     @staticmethod
-    def _gen_flags(generation_config, kw, beams=None, cand=None):
+    def _gen_flags(generation_config, kw, beams=None, cand=None, topk=0):
         """HF's output flags (return_dict_in_generate, output_scores, output_logits) and return_logprobs from a generation config / kwargs
         (generation.output_flags).  Beam search returns ``sequences_scores`` only: per-step scores, logits and log-probabilities of its
         hypotheses are not implemented and raise."""
         from . import generation
         flags = generation.output_flags(generation_config, kw)
         if beams:
-            asked = [k for k in ("output_scores", "output_logits", "return_logprobs") if flags[k]] + (["candidate_ids"] if cand is not None else [])
+            asked = [k for k in ("output_scores", "output_logits", "return_logprobs") if flags[k]] + (["candidate_ids"] if cand is not None else []) + \
+                (["top_logprobs"] if topk else [])
             if asked:
                 raise NotImplementedError(f"beam search (num_beams > 1) returns sequences and sequences_scores only: {', '.join(asked)} "
                                           "not implemented")
@@ -1528,11 +1599,18 @@ class InternVLChatModel(nn.Module):
         full-vocabulary log-probability of every candidate token at every step under the RAW lm-head logits (before logits processors and
         sampling warpers), NaN after a sequence's end token like ``logprobs``; ``softmax(cand_logprobs[:, t], -1)`` is the closed-set
         distribution at step t.  Greedy decoding without processors reads them in the decode step's own lm-head pass
-        (aigv_decode_step_cand_logprob); beam search refuses them.  fp8 mode: the lm-head stays bf16, the same kernels serve."""
+        (aigv_decode_step_cand_logprob); beam search refuses them.  fp8 mode: the lm-head stays bf16, the same kernels serve.
+
+        ``top_logprobs=k`` (int, 1 <= k <= 16): the output object also carries ``top_ids`` long [B, T, k] and ``top_logprobs`` fp32 [B, T, k] -
+        what the model preferred at every step: the k largest RAW lm-head logits (equal logits by ascending id, so entry 0 is the greedy
+        token) and their full-vocabulary log-probabilities; -1 / NaN after a sequence's end token.  Greedy decoding without processors
+        selects them in the decode step's own lm-head pass (aigv_decode_step_topk_logprob: ``top_logprobs[:, :, 0]`` is ``logprobs``, bit
+        for bit); otherwise they are ``generation.top_logprobs`` of the step's raw logits.  Beam search refuses them."""
         assert self.img_context_token_id is not None
         cand = self._candidates(generate_kwargs.pop("candidate_ids", None))
+        topk = self._top_logprobs_k(generate_kwargs.pop("top_logprobs", None), self.config.llm_config.vocab_size)
         max_new, eos, pad, sampler, procs, beams = self._gen_args(generation_config, generate_kwargs)
-        flags = self._gen_flags(generation_config, generate_kwargs, beams, cand)
+        flags = self._gen_flags(generation_config, generate_kwargs, beams, cand, topk)
         pad = self.config.llm_config.pad_token_id if pad is None else pad
         dev = self.device
         input_ids = input_ids.to(dev)
@@ -1548,15 +1626,16 @@ class InternVLChatModel(nn.Module):
             if int(sel.sum()) != n_vis:
                 raise ValueError(f"visual token count mismatch: {int(sel.sum())} slots vs {n_vis} tokens")
             slot[sel] = torch.arange(n_vis, device=dev, dtype=torch.int32)
-        return self._greedy(ids_packed, slot, cu, vis, n_vis, max_new, eos, pad, sampler=sampler, processors=procs, beams=beams, flags=flags, cand=cand)
+        return self._greedy(ids_packed, slot, cu, vis, n_vis, max_new, eos, pad, sampler=sampler, processors=procs, beams=beams, flags=flags, cand=cand, topk=topk)
 
     @torch.no_grad()
     def generate2(self, input_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, visual_features=None,
                   generation_config=None, output_hidden_states=None, return_dict=None, **generate_kwargs) -> torch.Tensor:
-        """modeling_internvl_chat.py:812-853: decode from precomputed input embeddings [B, N, C].  Output flags and ``candidate_ids`` as ``generate``."""
+        """modeling_internvl_chat.py:812-853: decode from precomputed input embeddings [B, N, C].  Output flags, ``candidate_ids`` and ``top_logprobs`` as ``generate``."""
         cand = self._candidates(generate_kwargs.pop("candidate_ids", None))
+        topk = self._top_logprobs_k(generate_kwargs.pop("top_logprobs", None), self.config.llm_config.vocab_size)
         max_new, eos, pad, sampler, procs, beams = self._gen_args(generation_config, generate_kwargs)
-        flags = self._gen_flags(generation_config, generate_kwargs, beams, cand)
+        flags = self._gen_flags(generation_config, generate_kwargs, beams, cand, topk)
         pad = self.config.llm_config.pad_token_id if pad is None else pad
         dev = self.device
         b, n, _ = input_embeds.shape
@@ -1569,7 +1648,7 @@ class InternVLChatModel(nn.Module):
         T = emb.shape[0]
         ids = torch.zeros(T, dtype=torch.long, device=dev)
         slot = torch.arange(T, dtype=torch.int32, device=dev)          # every row comes from `emb`
-        return self._greedy(ids, slot, cu, emb, T, max_new, eos, pad, sampler=sampler, processors=procs, beams=beams, flags=flags, cand=cand)
+        return self._greedy(ids, slot, cu, emb, T, max_new, eos, pad, sampler=sampler, processors=procs, beams=beams, flags=flags, cand=cand, topk=topk)
 
     @torch.no_grad()
     def generate_stage2(self, pixel_values, input_ids, attention_mask=None, image_flags=None, motion_feature=None,
@@ -1581,8 +1660,9 @@ class InternVLChatModel(nn.Module):
         if self.img_context_token_id is None:
             raise AssertionError("img_context_token_id must be set (stage2_eval.py:810)")
         cand = self._candidates(generate_kwargs.pop("candidate_ids", None))
+        topk = self._top_logprobs_k(generate_kwargs.pop("top_logprobs", None), self.config.llm_config.vocab_size)
         max_new, eos, pad, sampler, procs, beams = self._gen_args(generation_config, generate_kwargs)
-        flags = self._gen_flags(generation_config, generate_kwargs, beams, cand)
+        flags = self._gen_flags(generation_config, generate_kwargs, beams, cand, topk)
         pad = self.config.llm_config.pad_token_id if pad is None else pad
         B = input_ids.shape[0]
         plan = self._plan(input_ids, attention_mask, None, image_flags, pixel_values.shape[0], drop_dead_tail=False)
@@ -1590,7 +1670,7 @@ class InternVLChatModel(nn.Module):
         self._native(n_frames=pixel_values.shape[0], n_tokens=plan["cu"][-1], n_clips=B)
         vit_embeds, motion = self._visual_inputs(pixel_values, None, motion_feature, plan)
         return self._greedy(plan["ids_packed"], plan["slot"], plan["cu"], vit_embeds, plan["n_vis"], max_new, eos, pad, motion=motion, sampler=sampler, processors=procs, beams=beams,
-                            flags=flags, cand=cand)
+                            flags=flags, cand=cand, topk=topk)
 
     def chat2(self, tokenizer, pixel_values, input_ids, generation_config, attention_mask, history=None,
               return_history=False, image_flags=None, IMG_START_TOKEN="<img>", IMG_END_TOKEN="</img>",

@@ -65,10 +65,12 @@ PROTOTYPES = {
     "aigv_decode_step": (_I, [_P, _P, _P, _P]),
     "aigv_decode_step_logprob": (_I, [_P, _P, _P, _P, _P]),
     "aigv_decode_step_cand_logprob": (_I, [_P, _P, _P, _P, _P, _I, _P, _P]),
+    "aigv_decode_step_topk_logprob": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P]),
     "aigv_out_row_logits": (_I, [_P, _I, _I, _P, _I, _P]),
     "aigv_out_row_hidden": (_I, [_P, _I, _I, _P, _I, _P]),
     "aigv_out_row_logprob": (_I, [_P, _I, _I, _P, _P, _P]),
     "aigv_out_row_cand_logprob": (_I, [_P, _I, _I, _P, _I, _P, _P]),
+    "aigv_out_row_topk_logprob": (_I, [_P, _I, _I, _I, _P, _P, _P]),
     "aigv_decode_eos": (_I, [_P, _P, _P, _I64P, _I, C.c_int64, _P]),
     "aigv_op_gemm": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
     "aigv_op_gemm_rows": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _I, C.POINTER(C.c_int32), _I, _I, _I, _I, _P]),
@@ -102,6 +104,9 @@ PROTOTYPES = {
     "aigv_op_cand_logprob": (_I, [_P, _I, _I, _I, _P, _I, _P, _P]),
     "aigv_op_lm_head_argmax_cand_logprob": (_I, [_P, _I, _I, _P, _I, _P, _I, _P, C.c_int64, _P, _P, _P, _P, _P]),
     "aigv_op_lm_head_argmax_cand_logprob_scratch_bytes": (C.c_int64, [_I, _I]),
+    "aigv_op_topk_logprob": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
+    "aigv_op_lm_head_argmax_topk_logprob": (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P]),
+    "aigv_op_lm_head_argmax_topk_logprob_scratch_bytes": (C.c_int64, [_I, _I]),
     "aigv_op_attention_decode": (_I, [_P, _I, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _F, _I, _P, C.c_int64, _P]),
     "aigv_op_attention_decode_ws_floats": (C.c_int64, [_I, _I, _I, _I]),
     "aigv_op_skinny_rope_kv": (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _F, _I, _P]),

@@ -36,12 +36,16 @@ extern "C" {
 #define AIGV_ABI_VERSION 3   /* 2: aigv_out_row_logprob, aigv_op_label_logprob; 3: the decode-step operators (aigv_op_attention_decode ...),
                                 later joined by aigv_decode_step_logprob and aigv_op_lm_head_argmax_logprob, then by the candidate-token
                                 log-probabilities (aigv_out_row_cand_logprob, aigv_decode_step_cand_logprob, aigv_op_cand_logprob,
-                                aigv_op_lm_head_argmax_cand_logprob), then by the test entry points aigv_op_attention_ex and aigv_op_kv_store
+                                aigv_op_lm_head_argmax_cand_logprob), then by the test entry points aigv_op_attention_ex and aigv_op_kv_store,
+                                then by the top-k log-probabilities (aigv_out_row_topk_logprob, aigv_decode_step_topk_logprob,
+                                aigv_op_topk_logprob, aigv_op_lm_head_argmax_topk_logprob)
                                 - added symbols only: a library without them is refused at load
                                 time, "missing <name>" */
 
 /* Most candidate token ids one candidate log-probability call takes. */
 #define AIGV_MAX_CANDIDATES 64
+/* Largest k one top-k log-probability call takes. */
+#define AIGV_MAX_TOPK 16
 
 /* Largest aigv_config.kv_capacity a context accepts (tokens per clip): the decode attention's merge pass holds 16 bytes of LDS per
  * 128-key chunk of the capacity (32 KB at this bound). */
@@ -215,6 +219,15 @@ int aigv_decode_step_logprob(aigv_ctx* ctx, const int64_t* ids, int64_t* next, f
  * aigv_decode_step_logprob's bits.  Nothing is allocated here, so the call may be captured. */
 int aigv_decode_step_cand_logprob(aigv_ctx* ctx, const int64_t* ids, int64_t* next, float* logprob, const int64_t* cand_ids, int C,
                                   float* cand_logprob, void* stream);
+/* aigv_decode_step_logprob plus the k most likely tokens of every step: top_ids[b, j] (DEVICE int64 [B, k]) is the id of the j-th largest
+ * bf16 lm-head logit of sequence b - equal logits by ascending id, the order of the fused argmax, so top_ids[b, 0] == next[b] - and
+ * top_logprob[b, j] (DEVICE fp32 [B, k]) = log_softmax(logits.float())[top_ids[b, j]] under the log-sum-exp `logprob` uses:
+ * top_logprob[b, 0] is logprob[b], bit for bit.  1 <= k <= min(AIGV_MAX_TOPK, vocab).  The lm-head weights are read once: the GEMV that
+ * reduces the logits also stores them (bf16, a context-owned scratch) and the finisher selects from that row.  Candidates are optional:
+ * cand_ids == NULL with C == 0, or aigv_decode_step_cand_logprob's arguments and bits.  next / logprob are aigv_decode_step_logprob's
+ * bits; a sequence's results do not depend on its batch mates nor on k.  Nothing is allocated here, so the call may be captured. */
+int aigv_decode_step_topk_logprob(aigv_ctx* ctx, const int64_t* ids, int64_t* next, float* logprob, int k, int64_t* top_ids,
+                                  float* top_logprob, const int64_t* cand_ids, int C, float* cand_logprob, void* stream);
 /* The full next-token distribution of the rows the last aigv_llm_prefill / aigv_llm_extend / aigv_decode_step consumed: lm-head
  * logits of their final hidden states (kept in the context, in the order [score rows | logit rows]; a decode step keeps its
  * n_clips rows) as the bf16 values the reference upcasts with .float() (modeling_internlm2.py:1095-1096).
@@ -240,6 +253,13 @@ int aigv_out_row_logprob(aigv_ctx* ctx, int first_row, int n_rows, const int64_t
  * 1 <= C <= AIGV_MAX_CANDIDATES (the first answer tokens of the quality-level words: softmax over the C columns is the closed-set
  * level distribution); an id outside [0, vocab) gives a NaN column.  cand_logprob: DEVICE fp32 [n_rows, C].  Nothing is allocated here. */
 int aigv_out_row_cand_logprob(aigv_ctx* ctx, int first_row, int n_rows, const int64_t* cand_ids, int C, float* cand_logprob, void* stream);
+/* The k most likely tokens of the same rows: top_ids[i, j] (DEVICE int64 [n_rows, k]) is the id of the j-th largest bf16 logit of row
+ * first_row + i, equal logits by ascending id (torch.sort(logits.float(), descending=True, stable=True) states the rule; entry 0 is
+ * the fused argmax's token), and top_logprob[i, j] (DEVICE fp32 [n_rows, k]) = log_softmax(logits.float())[top_ids[i, j]] -
+ * aigv_out_row_logprob's logits, scratch, arithmetic and log-sum-exp, so column j holds the bits aigv_out_row_logprob /
+ * aigv_out_row_cand_logprob give for that id and a row's results depend on neither n_rows nor k (the first columns of a larger k are the
+ * smaller k's).  1 <= k <= min(AIGV_MAX_TOPK, vocab).  Nothing is allocated here. */
+int aigv_out_row_topk_logprob(aigv_ctx* ctx, int first_row, int n_rows, int k, int64_t* top_ids, float* top_logprob, void* stream);
 /* End-of-sequence bookkeeping of generate()'s token loop on the device (the reference defers to HF's loop: next = next * unfinished +
  * pad * (1 - unfinished); unfinished &= next not in eos_token_id; stop when every sequence has finished - modeling_internvl_chat.py:
  * 798-809).  tokens: DEVICE int64[n] (n = sequences of the kept KV state), in: the step's raw tokens (aigv_decode_step's `next`, or the
@@ -355,6 +375,18 @@ int aigv_op_lm_head_argmax_cand_logprob(const void* h, int rows, int hidden, con
                                         void* scratch, int64_t scratch_bytes, int64_t* idx, float* val, float* logprob, float* cand_logprob,
                                         void* stream);
 int64_t aigv_op_lm_head_argmax_cand_logprob_scratch_bytes(int rows, int vocab);   /* -1 for arguments the op refuses */
+/* aigv_op_label_logprob's kernel selecting instead of gathering: the k largest logits of every row, equal logits by ascending column
+ * (top_ids: DEVICE int64 [rows, k]), and their fp32 log-probabilities (top_logprob: DEVICE fp32 [rows, k]); 1 <= k <= min(AIGV_MAX_TOPK,
+ * vocab).  Column j holds aigv_op_label_logprob's / aigv_op_cand_logprob's bits for the id it names; results depend on neither `rows`,
+ * k nor the alignment of the rows. */
+int aigv_op_topk_logprob(const void* logits_bf16, int rows, int vocab, int ldo, int k, int64_t* top_ids, float* top_logprob, void* stream);
+/* The lm-head of aigv_decode_step_topk_logprob: aigv_op_lm_head_argmax_logprob (idx / val / logprob: its bits, its argument rules) plus
+ * top_ids / top_logprob [rows, k] and, with cand_ids != NULL (else C == 0), aigv_op_lm_head_argmax_cand_logprob's cand_logprob.
+ * scratch: DEVICE memory of aigv_op_lm_head_argmax_topk_logprob_scratch_bytes(rows, vocab) bytes. */
+int aigv_op_lm_head_argmax_topk_logprob(const void* h, int rows, int hidden, const void* W, int vocab, int k, const int64_t* cand_ids, int C,
+                                        void* scratch, int64_t scratch_bytes, int64_t* idx, float* val, float* logprob, int64_t* top_ids,
+                                        float* top_logprob, float* cand_logprob, void* stream);
+int64_t aigv_op_lm_head_argmax_topk_logprob_scratch_bytes(int rows, int vocab);   /* -1 for arguments the op refuses */
 
 /* ---- the kernels of aigv_decode_step, one by one (parity tests; ABI 3) ----------------------------------------------------------------
  * Every pointer is DEVICE memory; the arguments are checked on the host before anything is launched (AIGV_ERR_ARG with a message
