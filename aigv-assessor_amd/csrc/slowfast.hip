@@ -296,14 +296,16 @@ int conv_k_slices(long rows, int CoutPad, int Kp) {   // rows of ONE clip
   return 1;
 }
 
-// S: K slices decided by the caller (from the PER-CLIP shape, so that a clip's bits do not depend on its batch mates); 1 without workspace
+// S: K slices decided by the caller (from the PER-CLIP shape, so that a clip's bits do not depend on its batch mates).  S > 1 that cannot
+// run (no workspace, one too small, S not dividing the K steps) is refused: the plan sizes the workspace, so that case is a bug
 hipError_t launch_conv(const ConvArgs& a_in, hipStream_t s, int S = 1, float* ws = nullptr, size_t ws_floats = 0) {
   ConvArgs a = a_in;
   if (a.rows <= 0) return hipSuccess;
   if (a.Cin % 8 || a.ld_in % 8 || a.Cout % 4 || a.ld_out % 4 || a.c_off % 4 || a.Kp % 64 || a.CoutPad % 16 || (a.res && a.ld_res % 4) ||
       a.Kp < a.kt * a.kh * a.kw * a.Cin)
     return hipErrorInvalidValue;
-  if (!ws || S < 1 || (a.Kp / 64) % S || (size_t)S * a.rows * a.Cout > ws_floats) S = 1;
+  if (S < 1) S = 1;
+  if (S > 1 && (!ws || (a.Kp / 64) % S || (size_t)S * a.rows * a.Cout > ws_floats)) return hipErrorInvalidValue;
   a.k_slices = S;
   a.part = S > 1 ? ws : nullptr;
   const unsigned gx = (unsigned)((a.rows + 127) / 128);
@@ -344,8 +346,10 @@ struct Op {
   size_t w_off = 0, b_off = 0;
   long rows_per_clip = 0;
   int k_slices = 1;
+  bool pair_stem = false;
+  std::string conv_name, norm_name;   // state-dict names (relative to feature_extraction.)
   // OP_MAXPOOL / OP_POOL
-  int C = 0, T = 0, Hi = 0, Wi = 0, Ho = 0, Wo = 0, ld_out = 0, c_off = 0;
+  int C = 0, T = 0, Hi = 0, Wi = 0, Ho = 0, Wo = 0, ld_out = 0, c_off = 0, window = 0;
   PoolW pw{};
 };
 
@@ -379,6 +383,7 @@ struct aigv_slowfast {
 namespace {
 
 enum { B_IN0 = 0, B_IN1, B_STEM0, B_STEM1, B_X00, B_X01, B_X10, B_X11, B_A0, B_A1, B_B0, B_B1, B_S0, B_S1, B_COUNT };
+static_assert(B_COUNT == AIGV_SF_BUFFERS, "aigv_amd.h names the number of activation buffers");
 
 struct Builder {
   aigv_slowfast* sf;
@@ -424,6 +429,7 @@ struct Builder {
     const int K = taps_k * cin_eff, Kp = (K + 63) / 64 * 64, coutPad = (cout + 15) / 16 * 16;
     Op op;
     op.kind = OP_CONV;
+    op.conv_name = conv_name; op.norm_name = norm_name; op.pair_stem = stem_pairs;
     op.w_off = w.size();
     op.b_off = b.size();
     w.resize(w.size() + (size_t)coutPad * Kp, 0);
@@ -463,6 +469,29 @@ void cover_weights(float* w, int n, int k) {   // how many stride-1 windows of l
   }
 }
 
+// torch.linspace(0, T - 1, T // 4).long() (modeling_internvl_chat.py:109-111): fp32 start + i * step, truncated; the second half is
+// computed from the end (end - (steps - 1 - i) * step) exactly as torch's kernel does.  Returns the count, T / 4 <= 64
+int slow_indices(int T, int* idx) {
+  const int n = T / 4;
+  const float step = n > 1 ? (float)(T - 1) / (float)(n - 1) : 0.f;
+  for (int i = 0; i < n; ++i) idx[i] = i < n / 2 ? (int)(0.f + step * i) : (int)((float)(T - 1) - step * (float)(n - 1 - i));
+  return n;
+}
+
+// head pool over `frames` frames of H x W: temporal window k over the 4x repeated frames, 7x7 spatial, stride 1, then the mean of all
+// windows == separable weights (windows covering a position / windows x window size); frames <= 32, 4 * frames >= k, 7 <= H, W <= 32
+void pool_weights(int frames, int H, int W, int k, float* wt, float* wy, float* wx) {
+  const int L = 4 * frames;
+  float rep[128], ty[32], tx[32];
+  cover_weights(rep, L, k);
+  cover_weights(ty, H, 7);
+  cover_weights(tx, W, 7);
+  const float nt = (float)(L - k + 1) * k, ny = (float)(H - 6) * 7, nx = (float)(W - 6) * 7;
+  for (int t = 0; t < frames; ++t) wt[t] = (rep[4 * t] + rep[4 * t + 1] + rep[4 * t + 2] + rep[4 * t + 3]) / nt;
+  for (int y = 0; y < H; ++y) wy[y] = ty[y] / ny;
+  for (int x = 0; x < W; ++x) wx[x] = tx[x] / nx;
+}
+
 }  // namespace
 
 extern "C" {
@@ -482,11 +511,7 @@ int aigv_slowfast_create(int device, int max_clips, int frames_per_clip, int hei
   aigv_slowfast* sf = new (std::nothrow) aigv_slowfast();
   if (!sf) return sf_fail(AIGV_ERR_ALLOC, "out of host memory");
   sf->device = device; sf->Bcap = max_clips; sf->T = frames_per_clip; sf->Ts = frames_per_clip / 4; sf->H = height; sf->W = width;
-  // torch.linspace(0, T - 1, T // 4).long() (modeling_internvl_chat.py:109-111): fp32 start + i * step, truncated; the second half is
-  // computed from the end (end - (steps - 1 - i) * step) exactly as torch's kernel does
-  const int n = sf->Ts;
-  const float step = n > 1 ? (float)(sf->T - 1) / (float)(n - 1) : 0.f;
-  for (int i = 0; i < n; ++i) sf->slow_idx.v[i] = i < n / 2 ? (int)(0.f + step * i) : (int)((float)(sf->T - 1) - step * (float)(n - 1 - i));
+  slow_indices(sf->T, sf->slow_idx.v);
   *out = sf;
   return 0;
 }
@@ -609,17 +634,10 @@ int aigv_slowfast_finalize(aigv_slowfast* sf) {
   for (int p = 0; p < 2; ++p) {   // head pools: temporal window 8 (slow) / 32 (fast) over the 4x repeated frames, 7x7 spatial, stride 1
     Op op; op.kind = OP_POOL;
     op.in_buf = X[p][cur[p]]; op.C = p ? 256 : 2048; op.T = T[p]; op.Hi = sp_h; op.Wi = sp_w; op.ld_out = 2304; op.c_off = p ? 2048 : 0;
-    const int L = 4 * T[p], k = p ? 32 : 8;
-    if (L < k) return sf_fail(AIGV_ERR_ARG, "too few frames for the head pool");
-    float rep[128];
-    cover_weights(rep, L, k);
-    float ty[32], tx[32];
-    cover_weights(ty, sp_h, 7);
-    cover_weights(tx, sp_w, 7);
-    const float nt = (float)(L - k + 1) * k, ny = (float)(sp_h - 6) * 7, nx = (float)(sp_w - 6) * 7;
-    for (int t = 0; t < T[p]; ++t) op.pw.t[t] = (rep[4 * t] + rep[4 * t + 1] + rep[4 * t + 2] + rep[4 * t + 3]) / nt;
-    for (int y = 0; y < sp_h; ++y) op.pw.y[y] = ty[y] / ny;
-    for (int x = 0; x < sp_w; ++x) op.pw.x[x] = tx[x] / nx;
+    const int k = p ? 32 : 8;
+    if (4 * T[p] < k) return sf_fail(AIGV_ERR_ARG, "too few frames for the head pool");
+    op.window = k;
+    pool_weights(T[p], sp_h, sp_w, k, op.pw.t, op.pw.y, op.pw.x);
     sf->ops.push_back(op);
   }
   // device memory
@@ -652,13 +670,18 @@ int aigv_slowfast_finalize(aigv_slowfast* sf) {
 
 double aigv_slowfast_flops_per_clip(const aigv_slowfast* sf) { return sf ? sf->flops_per_clip : 0.0; }
 
-int aigv_slowfast_forward(aigv_slowfast* sf, const void* frames_nchw_bf16, int clips, void* feature_bf16, void* stream) {
-  if (!sf || !frames_nchw_bf16 || !feature_bf16) return sf_fail(AIGV_ERR_ARG, "aigv_slowfast_forward: null argument");
-  if (!sf->finalized) return sf_fail(AIGV_ERR_STATE, "aigv_slowfast_forward: call aigv_slowfast_finalize first");
-  if (clips <= 0 || clips > sf->Bcap) return sf_fail(AIGV_ERR_ARG, "aigv_slowfast_forward: %d clips, capacity %d", clips, sf->Bcap);
-  if (hipSetDevice(sf->device) != hipSuccess) return sf_fail(AIGV_ERR_HIP, "aigv_slowfast_forward: hipSetDevice(%d) failed", sf->device);
+// ops [first, last] of the plan: the one place the branch's kernels are launched from (the forward is the whole range)
+static int sf_run_ops(aigv_slowfast* sf, const char* who, const void* frames_nchw_bf16, int clips, void* feature_bf16, int first, int last, void* stream) {
+  if (!sf) return sf_fail(AIGV_ERR_ARG, "%s: null argument", who);
+  if (!sf->finalized) return sf_fail(AIGV_ERR_STATE, "%s: call aigv_slowfast_finalize first", who);
+  if (clips <= 0 || clips > sf->Bcap) return sf_fail(AIGV_ERR_ARG, "%s: %d clips, capacity %d", who, clips, sf->Bcap);
+  if (first < 0 || last < first || last >= (int)sf->ops.size()) return sf_fail(AIGV_ERR_ARG, "%s: ops %d..%d outside the plan's %d", who, first, last, (int)sf->ops.size());
+  for (int i = first; i <= last; ++i)
+    if ((sf->ops[i].kind == OP_REPACK && !frames_nchw_bf16) || (sf->ops[i].kind == OP_POOL && !feature_bf16)) return sf_fail(AIGV_ERR_ARG, "%s: null argument", who);
+  if (hipSetDevice(sf->device) != hipSuccess) return sf_fail(AIGV_ERR_HIP, "%s: hipSetDevice(%d) failed", who, sf->device);
   hipStream_t s = (hipStream_t)stream;
-  for (const Op& op : sf->ops) {
+  for (int i = first; i <= last; ++i) {
+    const Op& op = sf->ops[i];
     hipError_t e = hipSuccess;
     switch (op.kind) {
       case OP_REPACK: {
@@ -673,6 +696,9 @@ int aigv_slowfast_forward(aigv_slowfast* sf, const void* frames_nchw_bf16, int c
         a.in = sf->bufs[op.in_buf]; a.out = sf->bufs[op.out_buf]; a.res = op.res_buf >= 0 ? sf->bufs[op.res_buf] : nullptr;
         a.w = sf->d_w + op.w_off; a.bias = sf->d_b + op.b_off;
         a.rows = op.rows_per_clip * clips;
+        if (op.k_slices > 1 && (!sf->d_part || (a.Kp / 64) % op.k_slices || (size_t)op.k_slices * a.rows * a.Cout > sf->part_floats))
+          return sf_fail(AIGV_ERR_STATE, "%s: op %d (%s) is planned with %d K slices but the split-K workspace (%zu floats) cannot hold them", who, i,
+                         op.conv_name.c_str(), op.k_slices, sf->part_floats);
         e = launch_conv(a, s, op.k_slices, sf->d_part, sf->part_floats);
         break;
       }
@@ -690,9 +716,115 @@ int aigv_slowfast_forward(aigv_slowfast* sf, const void* frames_nchw_bf16, int c
         break;
       }
     }
-    if (e != hipSuccess) return sf_fail(e == hipErrorInvalidValue ? AIGV_ERR_ARG : AIGV_ERR_HIP, "aigv_slowfast_forward: launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return sf_fail(e == hipErrorInvalidValue ? AIGV_ERR_ARG : AIGV_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
   }
   return 0;
+}
+
+int aigv_slowfast_forward(aigv_slowfast* sf, const void* frames_nchw_bf16, int clips, void* feature_bf16, void* stream) {
+  if (!sf || !frames_nchw_bf16 || !feature_bf16) return sf_fail(AIGV_ERR_ARG, "aigv_slowfast_forward: null argument");
+  if (!sf->finalized) return sf_fail(AIGV_ERR_STATE, "aigv_slowfast_forward: call aigv_slowfast_finalize first");
+  return sf_run_ops(sf, "aigv_slowfast_forward", frames_nchw_bf16, clips, feature_bf16, 0, (int)sf->ops.size() - 1, stream);
+}
+
+// ---- the plan, one op at a time (tests / profiling) ----
+int aigv_slowfast_run_ops(aigv_slowfast* sf, const void* frames_nchw_bf16, int clips, void* feature_bf16, int first, int last, void* stream) {
+  return sf_run_ops(sf, "aigv_slowfast_run_ops", frames_nchw_bf16, clips, feature_bf16, first, last, stream);
+}
+
+int aigv_slowfast_plan_size(const aigv_slowfast* sf) {
+  if (!sf) return sf_fail(AIGV_ERR_ARG, "aigv_slowfast_plan_size: null handle");
+  if (!sf->finalized) return sf_fail(AIGV_ERR_STATE, "aigv_slowfast_plan_size: call aigv_slowfast_finalize first");
+  return (int)sf->ops.size();
+}
+
+int aigv_slowfast_plan_op(const aigv_slowfast* sf, int index, aigv_slowfast_op* d, int sizeof_op) {
+  if (!sf || !d) return sf_fail(AIGV_ERR_ARG, "aigv_slowfast_plan_op: null argument");
+  if (sizeof_op != (int)sizeof(aigv_slowfast_op)) return sf_fail(AIGV_ERR_ARG, "aigv_slowfast_plan_op: sizeof(aigv_slowfast_op) is %d here, the caller has %d", (int)sizeof(aigv_slowfast_op), sizeof_op);
+  if (!sf->finalized) return sf_fail(AIGV_ERR_STATE, "aigv_slowfast_plan_op: call aigv_slowfast_finalize first");
+  if (index < 0 || index >= (int)sf->ops.size()) return sf_fail(AIGV_ERR_ARG, "aigv_slowfast_plan_op: op %d outside the plan's %d", index, (int)sf->ops.size());
+  const Op& op = sf->ops[index];
+  memset(d, 0, sizeof *d);
+  d->in_buf = d->res_buf = d->out_buf = d->out2_buf = -1;
+  switch (op.kind) {
+    case OP_REPACK:
+      d->kind = AIGV_SF_REPACK;
+      d->out_buf = B_IN1; d->out_elems = (int64_t)sf->T * sf->H * sf->W * 4;
+      d->out2_buf = B_IN0; d->out2_elems = (int64_t)sf->Ts * sf->H * sf->W * 4;
+      d->T = sf->T; d->To = sf->Ts; d->H = sf->H; d->W = sf->W; d->C = 4; d->ld_out = 4;
+      break;
+    case OP_CONV: {
+      const ConvArgs& a = op.a;
+      d->kind = AIGV_SF_CONV;
+      d->in_buf = op.in_buf; d->res_buf = op.res_buf; d->out_buf = op.out_buf; d->pair_stem = op.pair_stem ? 1 : 0;
+      d->in_elems = (int64_t)a.Ti * a.Hi * a.Wi * a.ld_in;
+      d->res_elems = op.res_buf >= 0 ? (int64_t)op.rows_per_clip * a.ld_res : 0;
+      d->out_elems = (int64_t)op.rows_per_clip * a.ld_out;
+      d->ld_in = a.ld_in; d->Cin = a.Cin; d->Ti = a.Ti; d->Hi = a.Hi; d->Wi = a.Wi;
+      d->kt = a.kt; d->kh = a.kh; d->kw = a.kw; d->st = a.st; d->sh = a.sh; d->sw = a.sw; d->pt = a.pt; d->ph = a.ph; d->pw = a.pw;
+      d->To = a.To; d->Ho = a.Ho; d->Wo = a.Wo; d->Cout = a.Cout; d->Kp = a.Kp;
+      d->ld_res = a.ld_res; d->ld_out = a.ld_out; d->c_off = a.c_off; d->relu = a.relu;
+      d->k_slices = op.k_slices;
+      snprintf(d->conv_name, sizeof d->conv_name, "%s", op.conv_name.c_str());
+      snprintf(d->norm_name, sizeof d->norm_name, "%s", op.norm_name.c_str());
+      break;
+    }
+    case OP_MAXPOOL:
+      d->kind = AIGV_SF_MAXPOOL;
+      d->in_buf = op.in_buf; d->out_buf = op.out_buf;
+      d->in_elems = (int64_t)op.T * op.Hi * op.Wi * op.C;
+      d->out_elems = (int64_t)op.T * op.Ho * op.Wo * op.ld_out;
+      d->T = op.T; d->H = op.Hi; d->W = op.Wi; d->C = op.C; d->Hi = op.Hi; d->Wi = op.Wi; d->Ho = op.Ho; d->Wo = op.Wo; d->To = op.T;
+      d->ld_in = op.C; d->ld_out = op.ld_out; d->c_off = 0;
+      break;
+    case OP_POOL:
+      d->kind = AIGV_SF_HEADPOOL;
+      d->in_buf = op.in_buf;
+      d->in_elems = (int64_t)op.T * op.Hi * op.Wi * op.C;
+      d->T = op.T; d->H = op.Hi; d->W = op.Wi; d->C = op.C; d->ld_in = op.C; d->ld_out = op.ld_out; d->c_off = op.c_off; d->window = op.window;
+      break;
+  }
+  if (d->kind != AIGV_SF_CONV) d->k_slices = 1;
+  return 0;
+}
+
+static int sf_buffer_copy(aigv_slowfast* sf, const char* who, int buf, int64_t elems_per_clip, int clips, void* dst, const void* src, bool read, void* stream) {
+  if (!sf || (read ? !dst : !src)) return sf_fail(AIGV_ERR_ARG, "%s: null argument", who);
+  if (!sf->finalized) return sf_fail(AIGV_ERR_STATE, "%s: call aigv_slowfast_finalize first", who);
+  if (buf < 0 || buf >= B_COUNT || clips <= 0 || clips > sf->Bcap || elems_per_clip <= 0 || (size_t)elems_per_clip > sf->buf_elems[buf])
+    return sf_fail(AIGV_ERR_ARG, "%s: buffer %d holds %zu elements per clip for %d clips (asked for %lld x %d)", who, buf, buf >= 0 && buf < B_COUNT ? sf->buf_elems[buf] : (size_t)0,
+                   sf->Bcap, (long long)elems_per_clip, clips);
+  if (hipSetDevice(sf->device) != hipSuccess) return sf_fail(AIGV_ERR_HIP, "%s: hipSetDevice(%d) failed", who, sf->device);
+  const size_t bytes = (size_t)elems_per_clip * clips * sizeof(bf16_t);
+  const hipError_t e = read ? hipMemcpyAsync(dst, sf->bufs[buf], bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream)
+                            : hipMemcpyAsync(sf->bufs[buf], src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+  if (e != hipSuccess) return sf_fail(AIGV_ERR_HIP, "%s: copy failed: %s", who, hipGetErrorString(e));
+  return 0;
+}
+
+int aigv_slowfast_buffer_read(aigv_slowfast* sf, int buf, int64_t elems_per_clip, int clips, void* dst_bf16, void* stream) {
+  return sf_buffer_copy(sf, "aigv_slowfast_buffer_read", buf, elems_per_clip, clips, dst_bf16, nullptr, true, stream);
+}
+
+int aigv_slowfast_buffer_write(aigv_slowfast* sf, int buf, int64_t elems_per_clip, int clips, const void* src_bf16, void* stream) {
+  return sf_buffer_copy(sf, "aigv_slowfast_buffer_write", buf, elems_per_clip, clips, nullptr, src_bf16, false, stream);
+}
+
+int aigv_slowfast_slow_indices(int frames_per_clip, int32_t* idx) {
+  if (!idx || frames_per_clip < 4 || frames_per_clip > 256 || frames_per_clip % 4) return sf_fail(AIGV_ERR_ARG, "aigv_slowfast_slow_indices: needs T %% 4 == 0 in [4, 256]");
+  return slow_indices(frames_per_clip, idx);
+}
+
+int aigv_slowfast_pool_weights(int frames, int H, int W, int window, float* wt, float* wy, float* wx) {
+  if (!wt || !wy || !wx || frames < 1 || frames > 32 || window < 1 || 4 * frames < window || H < 7 || W < 7 || H > 32 || W > 32)
+    return sf_fail(AIGV_ERR_ARG, "aigv_slowfast_pool_weights: needs 1 <= frames <= 32, 4 * frames >= window >= 1, 7 <= H, W <= 32");
+  pool_weights(frames, H, W, window, wt, wy, wx);
+  return 0;
+}
+
+int aigv_slowfast_conv_k_slices(int64_t rows, int CoutPad, int Kp) {
+  if (rows <= 0 || CoutPad <= 0 || CoutPad % 16 || Kp <= 0 || Kp % 64) return sf_fail(AIGV_ERR_ARG, "aigv_slowfast_conv_k_slices: needs rows > 0, CoutPad %% 16 == 0, Kp %% 64 == 0");
+  return conv_k_slices((long)rows, CoutPad, Kp);
 }
 
 // One convolution with the kernel the branch is built from (tests / profiling): x [B, Ti, Hi, Wi, ld_in] channels-last bf16,

@@ -33,6 +33,30 @@ class AigvConfig(C.Structure):
     ]
 
 
+class SlowFastOp(C.Structure):
+    """Mirror of ``struct aigv_slowfast_op`` (include/aigv_amd.h): one op of the SlowFast plan, for tests and profiling."""
+    REPACK, CONV, MAXPOOL, HEADPOOL = 0, 1, 2, 3
+    _fields_ = ([(n, C.c_int32) for n in ("kind", "in_buf", "res_buf", "out_buf", "out2_buf", "pair_stem")] +
+                [(n, C.c_int64) for n in ("in_elems", "res_elems", "out_elems", "out2_elems")] +
+                [(n, C.c_int32) for n in ("ld_in", "Cin", "Ti", "Hi", "Wi", "kt", "kh", "kw", "st", "sh", "sw", "pt", "ph", "pw", "To", "Ho", "Wo", "Cout", "Kp",
+                                          "ld_res", "ld_out", "c_off", "relu", "k_slices", "T", "H", "W", "C", "window", "reserved")] +
+                [("conv_name", C.c_char * 128), ("norm_name", C.c_char * 128)])
+
+
+def slowfast_plan(handle):
+    """Every op of a finalized SlowFast handle's plan, in launch order."""
+    lib = load()
+    n = lib.aigv_slowfast_plan_size(handle)
+    if n < 0:
+        check(n)
+    ops = []
+    for i in range(n):
+        op = SlowFastOp()
+        check(lib.aigv_slowfast_plan_op(handle, i, C.byref(op), C.sizeof(SlowFastOp)))
+        ops.append(op)
+    return ops
+
+
 _P = C.c_void_p
 _I = C.c_int
 _F = C.c_float
@@ -83,6 +107,14 @@ PROTOTYPES = {
     "aigv_slowfast_forward": (_I, [_P, _P, _I, _P, _P]),
     "aigv_slowfast_flops_per_clip": (C.c_double, [_P]),
     "aigv_op_conv3d": (_I, [_P, _I, _I, _I, C.POINTER(_I), _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _P]),
+    "aigv_slowfast_plan_size": (_I, [_P]),
+    "aigv_slowfast_plan_op": (_I, [_P, _I, C.POINTER(SlowFastOp), _I]),
+    "aigv_slowfast_run_ops": (_I, [_P, _P, _I, _P, _I, _I, _P]),
+    "aigv_slowfast_buffer_read": (_I, [_P, _I, C.c_int64, _I, _P, _P]),
+    "aigv_slowfast_buffer_write": (_I, [_P, _I, C.c_int64, _I, _P, _P]),
+    "aigv_slowfast_slow_indices": (_I, [_I, _I32P]),
+    "aigv_slowfast_pool_weights": (_I, [_I, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), C.POINTER(_F)]),
+    "aigv_slowfast_conv_k_slices": (_I, [C.c_int64, _I, _I]),
     "aigv_set_precision": (_I, [_P, _I]),
     "aigv_op_quant_fp8_rows": (_I, [_P, _I, _I, _I, _P, _I, _P, _P]),
     "aigv_op_gemm_fp8": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),

@@ -38,7 +38,9 @@ extern "C" {
                                 log-probabilities (aigv_out_row_cand_logprob, aigv_decode_step_cand_logprob, aigv_op_cand_logprob,
                                 aigv_op_lm_head_argmax_cand_logprob), then by the test entry points aigv_op_attention_ex and aigv_op_kv_store,
                                 then by the top-k log-probabilities (aigv_out_row_topk_logprob, aigv_decode_step_topk_logprob,
-                                aigv_op_topk_logprob, aigv_op_lm_head_argmax_topk_logprob)
+                                aigv_op_topk_logprob, aigv_op_lm_head_argmax_topk_logprob), then by the SlowFast plan walk for tests
+                                (aigv_slowfast_plan_size / _plan_op / _run_ops / _buffer_read / _buffer_write and the host functions
+                                aigv_slowfast_slow_indices / _pool_weights / _conv_k_slices)
                                 - added symbols only: a library without them is refused at load
                                 time, "missing <name>" */
 
@@ -524,6 +526,56 @@ double aigv_slowfast_flops_per_clip(const aigv_slowfast* sf);
  * dims = {Ti, Hi, Wi, kt, kh, kw, st, sh, sw, pt, ph, pw}; out[row, c_off + c] = relu?(conv + bias + res[row, c]) */
 int aigv_op_conv3d(const void* x, int ld_in, int Cin, int B, const int* dims, const void* w_packed, int Kp, const float* bias, int Cout,
                    const void* res, int ld_res, void* out, int ld_out, int c_off, int relu, void* stream);
+
+/* ---- the branch's plan, one op at a time (tests / profiling, like aigv_op_conv3d; not part of the scoring path) ---------------------
+ * A finalized handle holds a PLAN: the list of launches aigv_slowfast_forward makes, in order (one repack, ~105 convolutions, two
+ * max-pools, two head pools).  These entries describe the ops, run a range of them through the code the forward runs, and copy the
+ * activation buffers they work on, so that a test can hold each op alone against a reference computed from the input it really had.
+ *
+ * Activation buffers are numbered 0 .. AIGV_SF_BUFFERS-1 and reused along the plan; an op reads / writes the FRONT of a buffer as
+ * [clips][per-clip elements] bf16, channels-last with a row stride (ld).  The per-clip counts below are those of the op's own view. */
+#define AIGV_SF_BUFFERS 14
+enum aigv_slowfast_op_kind { AIGV_SF_REPACK = 0, AIGV_SF_CONV = 1, AIGV_SF_MAXPOOL = 2, AIGV_SF_HEADPOOL = 3 };
+typedef struct aigv_slowfast_op {
+  int32_t kind;                          /* aigv_slowfast_op_kind */
+  int32_t in_buf, res_buf, out_buf;      /* buffer ids, -1 = none.  Repack: in = the caller's frames (-1), out = the fast stem's input
+                                            [T, H, W, 4]; head pool: out = the caller's feature (-1) */
+  int32_t out2_buf;                      /* repack only: the slow stem's input [To, H, W, 4]; -1 otherwise */
+  int32_t pair_stem;                     /* conv: 1 = a stem, run as a 4-tap conv over PAIRS of 4-channel pixels (3 real channels + a zero
+                                            one): the geometry below is the pair form - Wi = W / 2, Cin = 8, kw = 4, sw = 1, pw = 2 - of the
+                                            state dict's [Cout, 3, kt, 7, 7] kernel with stride (1, 2, 2) and pad (kt / 2, 3, 3) */
+  int64_t in_elems, res_elems, out_elems, out2_elems;   /* per clip; 0 where the id is -1 */
+  /* convolution (also max-pool: Hi, Wi, Ho, Wo, ld_out) */
+  int32_t ld_in, Cin, Ti, Hi, Wi;
+  int32_t kt, kh, kw, st, sh, sw, pt, ph, pw;
+  int32_t To, Ho, Wo, Cout, Kp;          /* repack: To = the number of slow frames */
+  int32_t ld_res, ld_out, c_off, relu;   /* out[row, c_off + c], c < Cout (head pool: c < C, ld_out = 2304) */
+  int32_t k_slices;                      /* planned split-K slices (per-clip shape); > 1: slabs + the finalize kernel */
+  /* pools and repack: the op's input map, T frames of H x W with C channels (repack: the frames, C = 4 channels written) */
+  int32_t T, H, W, C;
+  int32_t window;                        /* head pool: temporal window over the 4x repeated frames (8 slow, 32 fast) */
+  int32_t reserved;
+  char conv_name[128], norm_name[128];   /* conv: state-dict names under feature_extraction. ("" otherwise) */
+} aigv_slowfast_op;
+/* number of ops of a finalized handle's plan (negative aigv_status otherwise) */
+int aigv_slowfast_plan_size(const aigv_slowfast* sf);
+/* describes op `index`; sizeof_op = sizeof(aigv_slowfast_op) of the caller (a mismatch is refused) */
+int aigv_slowfast_plan_op(const aigv_slowfast* sf, int index, aigv_slowfast_op* op, int sizeof_op);
+/* runs ops first .. last (inclusive) for `clips` clips on `stream`.  frames is read by the repack only, feature written by the head pools
+ * only: either may be NULL when the range holds no such op.  aigv_slowfast_forward is this call over the whole plan.  A convolution
+ * whose planned k_slices cannot run (workspace too small) is an error, never a silent unsplit launch. */
+int aigv_slowfast_run_ops(aigv_slowfast* sf, const void* frames_nchw_bf16, int clips, void* feature_bf16, int first, int last, void* stream);
+/* device-to-device copies of the first clips * elems_per_clip bf16 elements of activation buffer `buf`, on `stream` */
+int aigv_slowfast_buffer_read(aigv_slowfast* sf, int buf, int64_t elems_per_clip, int clips, void* dst_bf16, void* stream);
+int aigv_slowfast_buffer_write(aigv_slowfast* sf, int buf, int64_t elems_per_clip, int clips, const void* src_bf16, void* stream);
+/* The host arithmetic of create / finalize, callable without a device (HOST pointers).
+ * slow-pathway frame indices, torch.linspace(0, T - 1, T / 4).long(): writes T / 4 ints (T a multiple of 4 in [4, 256]), returns the count */
+int aigv_slowfast_slow_indices(int frames_per_clip, int32_t* idx);
+/* head pool = repeat_interleave(4) + AvgPool3d((window, 7, 7), stride 1) + AdaptiveAvgPool3d(1) as ONE weighted mean with separable
+ * weights: wt[frames], wy[H], wx[W] (1 <= frames <= 32 with 4 * frames >= window, 7 <= H, W <= 32) */
+int aigv_slowfast_pool_weights(int frames, int H, int W, int window, float* wt, float* wy, float* wx);
+/* split-K slices the plan gives a convolution of `rows` output positions PER CLIP, ceil16(Cout) = CoutPad, padded K = Kp */
+int aigv_slowfast_conv_k_slices(int64_t rows, int CoutPad, int Kp);
 
 #ifdef __cplusplus
 }

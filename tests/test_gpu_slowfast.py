@@ -30,13 +30,17 @@ def _pack_conv(w):
 
 
 CASES = [  # B, Cin, Ti, Hi, Wi, Cout, (kt,kh,kw), (st,sh,sw), (pt,ph,pw), residual, relu, extra ld / c_off
-    (2, 8, 4, 20, 20, 8, (5, 7, 7), (1, 2, 2), (2, 3, 3), False, True, 0),       # the fast stem's geometry (Cin padded to 8)
+    (2, 8, 4, 20, 20, 8, (5, 7, 7), (1, 2, 2), (2, 3, 3), False, True, 0),       # a [5,7,7] stride-2 kernel over 8 channels: the stem's taps as one plain conv (the branch itself runs its stems in pair form,
+                                                                                 # 4 taps over pixel pairs: test_gpu_slowfast_ops.py checks that against the original weights)
     (1, 80, 2, 14, 14, 64, (1, 1, 1), (1, 1, 1), (0, 0, 0), False, True, 0),     # conv_a, Cin not a power of two
     (2, 16, 8, 12, 12, 16, (3, 1, 1), (1, 1, 1), (1, 0, 0), False, True, 0),     # temporal conv_a
     (2, 64, 2, 15, 13, 64, (1, 3, 3), (1, 2, 2), (0, 1, 1), False, True, 0),     # strided conv_b, odd map
     (1, 32, 2, 9, 9, 128, (1, 1, 1), (1, 1, 1), (0, 0, 0), True, True, 0),       # conv_c with residual
     (1, 24, 3, 9, 9, 40, (1, 1, 1), (1, 2, 2), (0, 0, 0), False, False, 0),      # shortcut: strided 1x1x1, no ReLU, Cout % 16 != 0
     (2, 32, 8, 6, 6, 64, (7, 1, 1), (4, 1, 1), (3, 0, 0), False, True, 24),      # fast->slow fusion written at a channel offset
+    (1, 16, 2, 9, 9, 80, (1, 3, 3), (1, 1, 1), (0, 1, 1), False, True, 0),       # Cout = 80: BN = 64 with a partly empty second column tile
+    (2, 8, 4, 8, 4, 32, (3, 1, 1), (1, 1, 1), (1, 0, 0), False, True, 0),        # 256 rows: exactly two full row tiles
+    (1, 8, 1, 5, 5, 16, (1, 3, 3), (1, 1, 1), (0, 1, 1), True, True, 4),         # 25 rows: less than one wave's 32
 ]
 
 
