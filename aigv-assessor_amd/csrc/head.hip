@@ -320,9 +320,9 @@ __global__ __launch_bounds__(NWV * 64) void skinny_kernel(const bf16_t* __restri
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = rbf(gelu_fast(v[e]));
         }
-        if constexpr (EPI == SK_RELU) {
+        if constexpr (EPI == SK_RELU) {   // a NaN stays a NaN, as through F.relu (fmaxf would return the 0)
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+          for (int e = 0; e < 4; ++e) v[e] = v[e] < 0.f ? 0.f : v[e];
         }
         if constexpr (EPI == SK_LS_RESID) {
 #pragma unroll
@@ -354,7 +354,8 @@ __global__ void unpack_argmax_kernel(const unsigned long long* __restrict__ pack
 // ---- score head ------------------------------------------------------------------------------------------
 // x = hidden[:, -4, :] (post final norm); if ANY NaN is present in the batch slice the reference applies
 // nan_to_num(nan=0, posinf=1e9, neginf=-1e9) to every row (modeling_internvl_chat.py:469-473); then a chain
-// of Linear+ReLU with a bf16 rounding after each Linear (:82-94).  The wide layers run on the skinny GEMM
+// of Linear+ReLU with a bf16 rounding after each Linear (:82-94).  Without a NaN the guard leaves an Inf alone: the row then turns
+// into NaN / Inf in the Linears, and the ReLUs pass a NaN on as F.relu does.  The wide layers run on the skinny GEMM
 // (weights streamed once for all clips); the narrow tail (fan-in < 128) runs in one small kernel.
 __global__ __launch_bounds__(256) void score_guard_kernel(const bf16_t* __restrict__ x, int ldx, int B, int H,
                                                           bf16_t* __restrict__ out) {
@@ -395,7 +396,8 @@ __global__ __launch_bounds__(256) void score_tail_kernel(const ScoreHeadArgs a, 
       float s = 0.f;
       for (int i = lane; i < din; i += 64) s += bf2f(w[(size_t)o * din + i]) * buf[cur][i];
       s = wave_sum(s);
-      if (lane == 0) buf[cur ^ 1][o] = fmaxf(rbf(s + bf2f(bb[o])), 0.f);
+      const float y = rbf(s + bf2f(bb[o]));
+      if (lane == 0) buf[cur ^ 1][o] = y < 0.f ? 0.f : y;   // ReLU that keeps a NaN (F.relu does; fmaxf would not)
     }
     __syncthreads();
     cur ^= 1;

@@ -383,6 +383,137 @@ int aigv_op_skinny_rope_kv_fp8(const void* x, int ldx, int R, const void* W_e4m3
   return 0;
 }
 
+// ---- the score head and the row kernels of the passes, one by one (test entry points): every argument is checked here, before any HIP call ----
+// The chain as aigv_launch_score_head splits it: layers with fan-in % 128 == 0 and fan-out % 4 == 0 run on the skinny GEMM, from the first
+// layer that is not such a layer on everything runs in the tail kernel (dims <= 1024 there); the last layer is always a tail layer.
+int aigv_op_score_head(const void* x, int ldx, int B, int n_layers, const int32_t* dims_host, const void* const* w_dev, const void* const* b_dev,
+                       void* scratch, int64_t scratch_bytes, float* score, void* stream) {
+  const char* op = "aigv_op_score_head";
+  if (!x || !dims_host || !w_dev || !b_dev || !scratch || !score) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+  if (B < 1 || B > 64) return fail(nullptr, AIGV_ERR_ARG, "%s: B = %d outside 1..64", op, B);
+  if (n_layers < 1 || n_layers > 8) return fail(nullptr, AIGV_ERR_ARG, "%s: n_layers = %d outside 1..8", op, n_layers);
+  int maxd = 0;
+  for (int i = 0; i <= n_layers; ++i) {
+    if (dims_host[i] < 1 || dims_host[i] > (1 << 20)) return fail(nullptr, AIGV_ERR_ARG, "%s: dims[%d] = %d outside 1..%d", op, i, dims_host[i], 1 << 20);
+    maxd = dims_host[i] > maxd ? dims_host[i] : maxd;
+  }
+  if (ldx < dims_host[0]) return fail(nullptr, AIGV_ERR_ARG, "%s: ldx = %d below dims[0] = %d", op, ldx, dims_host[0]);
+  const int64_t need = (int64_t)3 * B * maxd * (int64_t)sizeof(bf16_t);
+  if (scratch_bytes < need) return fail(nullptr, AIGV_ERR_ARG, "%s: scratch of %lld bytes, needs %lld", op, (long long)scratch_bytes, (long long)need);
+  int L = 0;
+  while (L < n_layers && dims_host[L] % 128 == 0 && dims_host[L + 1] % 4 == 0) ++L;
+  if (L == n_layers)
+    return fail(nullptr, AIGV_ERR_ARG, "%s: no tail layer: the last layer (fan-out %d) must have a fan-in that is no multiple of 128 or a fan-out that is no multiple of 4", op,
+                dims_host[n_layers]);
+  for (int i = L; i <= n_layers; ++i)
+    if (dims_host[i] > 1024) return fail(nullptr, AIGV_ERR_ARG, "%s: tail dim dims[%d] = %d above 1024 (the tail starts at layer %d)", op, i, dims_host[i], L);
+  if (L > 0 && (!aligned16(scratch) || ((int64_t)B * maxd) % 8))
+    return fail(nullptr, AIGV_ERR_ARG, "%s: scratch must be 16-byte aligned and B * max(dims) = %lld a multiple of 8 for the GEMM layers", op, (long long)B * maxd);
+  ScoreHeadArgs a{};
+  a.x = (const bf16_t*)x; a.ldx = ldx; a.B = B; a.n_layers = n_layers; a.score = score;
+  for (int i = 0; i <= n_layers; ++i) a.dims[i] = dims_host[i];
+  for (int i = 0; i < n_layers; ++i) {
+    if (!w_dev[i] || !b_dev[i]) return fail(nullptr, AIGV_ERR_ARG, "%s: null weight or bias of layer %d", op, i);
+    if (i < L && !aligned16(w_dev[i])) return fail(nullptr, AIGV_ERR_ARG, "%s: the weight of GEMM layer %d must be 16-byte aligned", op, i);
+    a.w[i] = (const bf16_t*)w_dev[i]; a.b[i] = (const bf16_t*)b_dev[i];
+  }
+  HIPCHK(nullptr, aigv_launch_score_head(a, (bf16_t*)scratch, (hipStream_t)stream));
+  return 0;
+}
+
+int aigv_op_rmsnorm_quant_fp8(const void* x, int ldx, const void* w, void* q_e4m3, int ldq, float* row_scale, int rows, int H, float eps, void* stream) {
+  const char* op = "aigv_op_rmsnorm_quant_fp8";
+  if (!x || !w || !q_e4m3 || !row_scale) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+  if (rows < 0) return fail(nullptr, AIGV_ERR_ARG, "%s: rows = %d must not be negative", op, rows);
+  if (H < 8 || H % 8 || H > 16384) return fail(nullptr, AIGV_ERR_ARG, "%s: H = %d is not a multiple of 8 in 8..16384", op, H);
+  if (ldx < H || ldx % 8 || ldq < H || ldq % 8) return fail(nullptr, AIGV_ERR_ARG, "%s: bad leading dimension (ldx %d, ldq %d: multiples of 8, >= H)", op, ldx, ldq);
+  if (!aligned16(x) || !aligned16(w) || ((uintptr_t)q_e4m3 & 7)) return fail(nullptr, AIGV_ERR_ARG, "%s: misaligned operand", op);
+  HIPCHK(nullptr, aigv_launch_rmsnorm_quant_fp8((const bf16_t*)x, ldx, (const bf16_t*)w, (uint8_t*)q_e4m3, ldq, row_scale, rows, H, eps, (hipStream_t)stream));
+  return 0;
+}
+
+int aigv_op_rope_slots(void* qkv, int ld, const int32_t* pos, const void* cos, const void* sin, int tokens, int first_rot, int n_rot, int slots,
+                       int n_groups, int head_dim, void* stream) {
+  const char* op = "aigv_op_rope_slots";
+  if (!qkv || !pos || !cos || !sin) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+  if (tokens < 0) return fail(nullptr, AIGV_ERR_ARG, "%s: tokens = %d must not be negative", op, tokens);
+  if (head_dim < 16 || head_dim % 16) return fail(nullptr, AIGV_ERR_ARG, "%s: head_dim = %d is not a positive multiple of 16", op, head_dim);
+  if (n_groups < 1 || slots < 1 || first_rot < 0 || n_rot < 1 || (int64_t)first_rot + n_rot > slots)
+    return fail(nullptr, AIGV_ERR_ARG, "%s: needs n_groups (%d) >= 1, n_rot (%d) >= 1 and 0 <= first_rot (%d), first_rot + n_rot <= slots (%d)", op, n_groups, n_rot,
+                first_rot, slots);
+  if (ld % 8 || (int64_t)ld < (int64_t)n_groups * slots * head_dim)
+    return fail(nullptr, AIGV_ERR_ARG, "%s: bad leading dimension (ld %d, needs a multiple of 8 and >= n_groups slots head_dim)", op, ld);
+  if (!aligned16(qkv) || !aligned16(cos) || !aligned16(sin)) return fail(nullptr, AIGV_ERR_ARG, "%s: qkv and the tables must be 16-byte aligned", op);
+  HIPCHK(nullptr, aigv_launch_rope((bf16_t*)qkv, ld, pos, (const bf16_t*)cos, (const bf16_t*)sin, tokens, n_rot, slots, n_groups, head_dim, (hipStream_t)stream,
+                                   first_rot));
+  return 0;
+}
+
+int aigv_op_embed(const int64_t* ids, const int32_t* slot, const void* emb, const void* vis, const void* motion, int n_vis, void* out, int tokens, int H,
+                  void* stream) {
+  const char* op = "aigv_op_embed";
+  if (!ids || !slot || !emb || !out) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+  if (tokens < 0) return fail(nullptr, AIGV_ERR_ARG, "%s: tokens = %d must not be negative", op, tokens);
+  if (H < 8 || H % 8) return fail(nullptr, AIGV_ERR_ARG, "%s: H = %d is not a positive multiple of 8", op, H);
+  if (n_vis < 0 || (n_vis > 0 && !vis)) return fail(nullptr, AIGV_ERR_ARG, "%s: n_vis = %d needs a visual table (and must not be negative)", op, n_vis);
+  if (!aligned16(emb) || !aligned16(vis) || !aligned16(motion) || !aligned16(out)) return fail(nullptr, AIGV_ERR_ARG, "%s: the tables and out must be 16-byte aligned", op);
+  HIPCHK(nullptr, aigv_launch_embed(ids, slot, (const bf16_t*)emb, (const bf16_t*)vis, (const bf16_t*)motion, n_vis, (bf16_t*)out, tokens, H, (hipStream_t)stream));
+  return 0;
+}
+
+int aigv_op_seqpos(const int32_t* cu_host, int n_seq, const int32_t* pos_offset_host, int32_t* pos, int32_t* seq, int32_t* cu_dev, int tokens, void* stream) {
+  const char* op = "aigv_op_seqpos";
+  if (!cu_host || !pos || !seq || !cu_dev) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+  if (n_seq < 1 || n_seq > AIGV_SMALL_INTS / 2 - 1) return fail(nullptr, AIGV_ERR_ARG, "%s: n_seq = %d outside 1..%d", op, n_seq, AIGV_SMALL_INTS / 2 - 1);
+  if (tokens < 1 || cu_host[0] != 0 || cu_host[n_seq] != tokens) return fail(nullptr, AIGV_ERR_ARG, "%s: needs cu[0] = 0 and cu[n_seq] = tokens = %d >= 1", op, tokens);
+  for (int b = 0; b < n_seq; ++b)
+    if (cu_host[b + 1] < cu_host[b]) return fail(nullptr, AIGV_ERR_ARG, "%s: cu decreases at sequence %d", op, b);
+  HIPCHK(nullptr, aigv_launch_seqpos(cu_host, n_seq, pos, seq, cu_dev, tokens, (hipStream_t)stream, pos_offset_host));
+  return 0;
+}
+
+// shared checks of the row movers: rows of H bf16 in 16-byte chunks
+static int check_rows(const char* op, const void* a, const void* b, const void* idx, bool need_idx, int n, int H, int ld) {
+  if (!a || !b || (need_idx && !idx)) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+  if (n < 0) return fail(nullptr, AIGV_ERR_ARG, "%s: %d rows: must not be negative", op, n);
+  if (H < 8 || H % 8) return fail(nullptr, AIGV_ERR_ARG, "%s: H = %d is not a positive multiple of 8", op, H);
+  if (ld < H || ld % 8) return fail(nullptr, AIGV_ERR_ARG, "%s: bad leading dimension (ld %d, needs a multiple of 8 and >= H = %d)", op, ld, H);
+  if (!aligned16(a) || !aligned16(b)) return fail(nullptr, AIGV_ERR_ARG, "%s: the row buffers must be 16-byte aligned", op);
+  return 0;
+}
+
+// dst[i, :H] = src[idx[i] * ld ..] for i < n (dst is dense: leading dimension H)
+int aigv_op_gather_rows(const void* src, int ld, const int32_t* idx, int n, void* dst, int H, void* stream) {
+  TRY(check_rows("aigv_op_gather_rows", src, dst, idx, true, n, H, ld));
+  HIPCHK(nullptr, aigv_launch_gather_rows((const bf16_t*)src, ld, idx, n, (bf16_t*)dst, H, (hipStream_t)stream));
+  return 0;
+}
+
+// dst[idx[i] * ld ..] = src[i, :H] for i < n (src is dense); duplicate indices must carry identical rows
+int aigv_op_scatter_rows(const void* src, const int32_t* idx, int n, void* dst, int ld, int H, void* stream) {
+  TRY(check_rows("aigv_op_scatter_rows", src, dst, idx, true, n, H, ld));
+  HIPCHK(nullptr, aigv_launch_scatter_rows((const bf16_t*)src, idx, n, (bf16_t*)dst, ld, H, (hipStream_t)stream));
+  return 0;
+}
+
+// x[f * tokens_per_frame, :H] = cls_pos[:H] for f < n_frames (x is dense [n_frames * tokens_per_frame, H])
+int aigv_op_cls_rows(const void* cls_pos, void* x, int n_frames, int tokens_per_frame, int H, void* stream) {
+  const char* op = "aigv_op_cls_rows";
+  TRY(check_rows(op, cls_pos, x, nullptr, false, n_frames, H, H));
+  if (tokens_per_frame < 1) return fail(nullptr, AIGV_ERR_ARG, "%s: tokens_per_frame = %d must be positive", op, tokens_per_frame);
+  HIPCHK(nullptr, aigv_launch_cls_rows((const bf16_t*)cls_pos, (bf16_t*)x, n_frames, tokens_per_frame, H, (hipStream_t)stream));
+  return 0;
+}
+
+// dst[0..n) (DEVICE int32) = host[0..n), passed as kernel arguments in chunks of 256
+int aigv_op_write_ints(const int32_t* host, int n, int32_t* dst, void* stream) {
+  const char* op = "aigv_op_write_ints";
+  if (n < 0) return fail(nullptr, AIGV_ERR_ARG, "%s: n = %d must not be negative", op, n);
+  if (n > 0 && (!host || !dst)) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+  HIPCHK(nullptr, aigv_launch_write_ints(host, n, dst, (hipStream_t)stream));
+  return 0;
+}
+
 int aigv_op_frame_ingest(const void* hwc_u8, int n_frames, int height, int width, const float* mean, const float* stdv,
                          void* out_nchw, void* stream) {
   HIPCHK(nullptr, aigv_launch_frame_ingest((const uint8_t*)hwc_u8, n_frames, height, width, mean, stdv, (bf16_t*)out_nchw,

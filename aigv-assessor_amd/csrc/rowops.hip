@@ -289,45 +289,6 @@ __global__ __launch_bounds__(256) void kv_store_kernel(const bf16_t* __restrict_
   }
 }
 
-// Decode step: RoPE of the new token's q heads and K in place, then K / V appended to the cache - one launch instead of two
-// (a decode layer is a chain of small launches; each costs its latency).  One workgroup per token; chunk c of slot s.
-__global__ __launch_bounds__(256) void rope_kv_store_kernel(bf16_t* __restrict__ qkv, int ld, const int32_t* __restrict__ seq_of_tok,
-                                                            const int32_t* __restrict__ pos, const bf16_t* __restrict__ cs,
-                                                            const bf16_t* __restrict__ sn, bf16_t* __restrict__ kc,
-                                                            bf16_t* __restrict__ vc, int n_groups, int g, int D, int cap) {
-  const int t = blockIdx.x;
-  const int sq = seq_of_tok[t], p = pos[t];
-  const int half = D >> 1, cph = half >> 3, slots = g + 2;
-  // rotated slots: q heads 0..g-1 and K (slot g); V (slot g+1) is copied as is
-  for (int i = threadIdx.x; i < n_groups * (g + 1) * cph; i += 256) {
-    const int c = i % cph, r = i / cph, s = r % (g + 1), gi = r / (g + 1);
-    bf16_t* base = qkv + (size_t)t * ld + (size_t)(gi * slots + s) * D + (c << 3);
-    const size_t tb = (size_t)p * half + (c << 3);
-    const u16x8 lo = *(const u16x8*)base, hi = *(const u16x8*)(base + half);
-    const u16x8 co = *(const u16x8*)(cs + tb), si = *(const u16x8*)(sn + tb);
-    u16x8 olo, ohi;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float x1 = bf2f(lo[e]), x2 = bf2f(hi[e]), cc = bf2f(co[e]), ss = bf2f(si[e]);
-      olo[e] = f2bf(rbf(x1 * cc) + rbf(-x2 * ss));
-      ohi[e] = f2bf(rbf(x2 * cc) + rbf(x1 * ss));
-    }
-    if (s < g) {
-      *(u16x8*)base = olo;
-      *(u16x8*)(base + half) = ohi;
-    } else {   // K: straight into the cache (the qkv row's K slot is not read again in a decode step)
-      bf16_t* dst = kc + (((size_t)sq * n_groups + gi) * cap + p) * D + (c << 3);
-      *(u16x8*)dst = olo;
-      *(u16x8*)(dst + half) = ohi;
-    }
-  }
-  for (int i = threadIdx.x; i < n_groups * (D >> 3); i += 256) {
-    const int c = i % (D >> 3), gi = i / (D >> 3);
-    *(u16x8*)(vc + (((size_t)sq * n_groups + gi) * cap + p) * D + (c << 3)) =
-        *(const u16x8*)(qkv + (size_t)t * ld + (size_t)(gi * slots + g + 1) * D + (c << 3));
-  }
-}
-
 // ---- fp8 row quantisation (groundwork for BASELINE config 5; not on the bf16 scoring path) ------------------------------------
 // One workgroup per row: amax over the row, scale = amax / 448 (e4m3 max), q = e4m3_rne(x * (448 / amax)) - OCP e4m3 (gfx950's
 // v_cvt_pk_fp8_f32), the same three fp32 operations as the torch oracle in tests/test_gpu_ops.py; an all-zero row gets scale 1.
@@ -554,15 +515,6 @@ hipError_t aigv_launch_quant_fp8_rows(const bf16_t* x, int ldx, int rows, int K,
   if (rows <= 0) return hipSuccess;
   if (K <= 0 || K % 8 || ldx % 8 || ldq % 8 || !x || !q || !scale) return hipErrorInvalidValue;
   hipLaunchKernelGGL(quant_fp8_rows_kernel, dim3(rows), dim3(256), 0, s, x, ldx, K, q, ldq, scale);
-  return hipGetLastError();
-}
-
-hipError_t aigv_launch_rope_kv_store(bf16_t* qkv, int ld, const int32_t* seq_of_tok, const int32_t* pos, const bf16_t* cos,
-                                     const bf16_t* sin, bf16_t* kc, bf16_t* vc, int tokens, int n_groups, int g, int D, int cap,
-                                     hipStream_t s) {
-  if (tokens <= 0) return hipSuccess;
-  if (D % 16) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(rope_kv_store_kernel, dim3(tokens), dim3(256), 0, s, qkv, ld, seq_of_tok, pos, cos, sin, kc, vc, n_groups, g, D, cap);
   return hipGetLastError();
 }
 

@@ -144,6 +144,15 @@ PROTOTYPES = {
     "aigv_op_skinny_rope_kv": (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _F, _I, _P]),
     "aigv_op_skinny_swiglu_normed": (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _I, _P, _F, _I, _P]),
     "aigv_op_skinny_rope_kv_fp8": (_I, [_P, _I, _I, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _F, _I, _P]),
+    "aigv_op_score_head": (_I, [_P, _I, _I, _I, _I32P, C.POINTER(_P), C.POINTER(_P), _P, C.c_int64, _P, _P]),
+    "aigv_op_rmsnorm_quant_fp8": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _F, _P]),
+    "aigv_op_rope_slots": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "aigv_op_embed": (_I, [_P, _P, _P, _P, _P, _I, _P, _I, _I, _P]),
+    "aigv_op_seqpos": (_I, [_I32P, _I, _I32P, _P, _P, _P, _I, _P]),
+    "aigv_op_gather_rows": (_I, [_P, _I, _P, _I, _P, _I, _P]),
+    "aigv_op_scatter_rows": (_I, [_P, _P, _I, _P, _I, _I, _P]),
+    "aigv_op_cls_rows": (_I, [_P, _P, _I, _I, _I, _P]),
+    "aigv_op_write_ints": (_I, [_I32P, _I, _P, _P]),
     "aigv_op_frame_ingest": (_I, [_P, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P]),
     "aigv_op_frame_resize_ingest": (_I, [_P, _I, _I, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, _P, _P]),
     "aigv_tune_gemm": (_I, [_I, C.c_double]),

@@ -40,7 +40,9 @@ extern "C" {
                                 then by the top-k log-probabilities (aigv_out_row_topk_logprob, aigv_decode_step_topk_logprob,
                                 aigv_op_topk_logprob, aigv_op_lm_head_argmax_topk_logprob), then by the SlowFast plan walk for tests
                                 (aigv_slowfast_plan_size / _plan_op / _run_ops / _buffer_read / _buffer_write and the host functions
-                                aigv_slowfast_slow_indices / _pool_weights / _conv_k_slices)
+                                aigv_slowfast_slow_indices / _pool_weights / _conv_k_slices), then by the test entry points of the score head
+                                and the row kernels (aigv_op_score_head, aigv_op_rmsnorm_quant_fp8, aigv_op_rope_slots, aigv_op_embed,
+                                aigv_op_seqpos, aigv_op_gather_rows, aigv_op_scatter_rows, aigv_op_cls_rows, aigv_op_write_ints)
                                 - added symbols only: a library without them is refused at load
                                 time, "missing <name>" */
 
@@ -423,6 +425,40 @@ int aigv_op_skinny_swiglu_normed(const void* x, int ldx, int R, const void* W, i
 int aigv_op_skinny_rope_kv_fp8(const void* x, int ldx, int R, const void* W_e4m3, int ldw, const float* w_scale, int N, int K, void* qkv,
                                int ldo, const int32_t* pos, const int32_t* seq, const void* cos, const void* sin, void* kc, void* vc, int g,
                                int n_kv, int cap, const void* norm_w, float eps, int p, void* stream);
+
+/* ---- the score head and the row kernels of the passes, one by one (test entry points) ----
+ * Every argument is checked on the host before anything is launched (AIGV_ERR_ARG with a message that starts with the op's name).
+ *
+ * The score head of one batch slice: x [B, dims[0]] bf16 rows (leading dimension ldx) -> score[B] fp32 (the bf16 result widened).  If ANY
+ * element of x is NaN, the whole slice is passed through nan_to_num(nan = 0, posinf = 1e9, neginf = -1e9) first; then n_layers of
+ * ReLU(bf16(x W^T + b)), W [dims[i + 1], dims[i]] bf16, a NaN staying a NaN through the ReLU.  dims: HOST int32[n_layers + 1]; w / b: HOST
+ * arrays of n_layers DEVICE pointers.  1 <= B <= 64, 1 <= n_layers <= 8, scratch >= 3 B max(dims) bf16.  Layers with a fan-in % 128 == 0
+ * and a fan-out % 4 == 0 run as GEMMs; from the first other layer on, the chain runs in one tail kernel whose dims must all be <= 1024,
+ * and the last layer must be a tail layer (as every fan-out of 1 is). */
+int aigv_op_score_head(const void* x, int ldx, int B, int n_layers, const int32_t* dims_host, const void* const* w_dev, const void* const* b_dev,
+                       void* scratch, int64_t scratch_bytes, float* score, void* stream);
+/* RMSNorm fused with the e4m3 row quantisation of its result: the bytes q [rows, ldq] and scales row_scale[rows] of aigv_op_rmsnorm followed by
+ * aigv_op_quant_fp8_rows.  H a multiple of 8 in 8..16384; ldx, ldq multiples of 8 and >= H. */
+int aigv_op_rmsnorm_quant_fp8(const void* x, int ldx, const void* w, void* q_e4m3, int ldq, float* row_scale, int rows, int H, float eps, void* stream);
+/* aigv_op_rope on slots [first_rot, first_rot + n_rot) of every group (K only: first_rot = g, n_rot = 1); nothing else is written.
+ * pos[t] must lie inside the tables. */
+int aigv_op_rope_slots(void* qkv, int ld, const int32_t* pos, const void* cos, const void* sin, int tokens, int first_rot, int n_rot, int slots,
+                       int n_groups, int head_dim, void* stream);
+/* out[t, :H] = slot[t] < 0 ? emb[ids[t]] : slot[t] < n_vis ? vis[slot[t]] : motion[slot[t] - n_vis]  (ids DEVICE int64[tokens], slot DEVICE
+ * int32[tokens]; vis / motion may be NULL when no slot selects them; the caller's promise: every index inside its table). */
+int aigv_op_embed(const int64_t* ids, const int32_t* slot, const void* emb, const void* vis, const void* motion, int n_vis, void* out, int tokens, int H,
+                  void* stream);
+/* pos[t] = t - cu[s] + pos_offset[s], seq[t] = s for cu[s] <= t < cu[s + 1], and cu_dev[0..n_seq] = cu: cu_host / pos_offset_host (or NULL: 0) are
+ * HOST int32 arrays, the outputs DEVICE int32.  1 <= n_seq <= 127, cu[0] = 0, cu[n_seq] = tokens. */
+int aigv_op_seqpos(const int32_t* cu_host, int n_seq, const int32_t* pos_offset_host, int32_t* pos, int32_t* seq, int32_t* cu_dev, int tokens, void* stream);
+/* The row movers (H and ld multiples of 8; idx DEVICE int32[n], every index inside its buffer):
+ *   gather:  dst[i, :H] = src[idx[i] * ld ..]   (dst dense)      scatter: dst[idx[i] * ld ..] = src[i, :H]  (src dense; equal indices carry equal rows)
+ *   cls:     x[f * tokens_per_frame, :H] = cls_pos[:H], f < n_frames (x dense)
+ *   write_ints: dst[0..n) = host[0..n) (HOST int32 -> DEVICE int32, as kernel arguments) */
+int aigv_op_gather_rows(const void* src, int ld, const int32_t* idx, int n, void* dst, int H, void* stream);
+int aigv_op_scatter_rows(const void* src, const int32_t* idx, int n, void* dst, int ld, int H, void* stream);
+int aigv_op_cls_rows(const void* cls_pos, void* x, int n_frames, int tokens_per_frame, int H, void* stream);
+int aigv_op_write_ints(const int32_t* host, int n, int32_t* dst, void* stream);
 
 /* Frame ingest: uint8 [F,H,W,3] RGB frames already at the model resolution -> bf16 NCHW
  * pixel_values = bf16((u/255 - mean[c]) / std[c])  (torchvision ToTensor + Normalize of dataset.py:267-274 and the
