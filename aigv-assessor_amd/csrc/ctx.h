@@ -232,6 +232,8 @@ int run_gemm_full(aigv_ctx* c, const GemmArgs& a, int epi, hipStream_t s);      
 int run_llm_gemm(aigv_ctx* c, const GemmArgs& a, int epi, hipStream_t s);               // InternLM2 linears: the pass's row plan, else run_gemm
 int run_gemm_fp8(aigv_ctx* c, const bf16_t* A, int lda, int K, const uint8_t* W8, const float* w_scale, bf16_t* C, int ldc, int T, int N,
                  int epi, const bf16_t* resid, int ldr, hipStream_t s);
+const char* skinny_check(const bf16_t* x, int ldx, int R, const bf16_t* W, int ldw, int N, int K, const bf16_t* resid, int ldr,
+                         const bf16_t* out, int ldo, int epi);   // nullptr if run_skinny takes the layout
 int run_skinny(aigv_ctx* c, const bf16_t* x, int ldx, int R, const bf16_t* W, int ldw, int N, int K, const bf16_t* bias,
                const bf16_t* resid, int ldr, bf16_t* out, int ldo, int epi, hipStream_t s, int p = 1);
 constexpr size_t SPLITK_MAX_FLOATS = (size_t)64 << 20;   // 256 MB of fp32 split-K slabs: the planner never asks for more

@@ -1,6 +1,7 @@
 // The GEMM dispatcher of the C ABI: which tile kernel (gemm.hip / gemm256.hip / gemmco.hip / head.hip) runs which rows of a GEMM - the
 // wave-quantisation cost model of the batch-level dispatch, the per-sequence row plans of the scoring pass, split-K scratch.  Host-side
 // C++ only.  Interface: ctx.h.
+#include <atomic>
 #include <mutex>
 
 #include "ctx.h"
@@ -19,6 +20,12 @@ static GemmArgs tuned(const aigv_ctx* c, const GemmArgs& a) {
 //   (512 tiles, two co-resident workgroups per CU) nk * KT128 + FIX128, a last round of <= 256 tiles LONE128 of that.
 double g_rate256 = 1.46;                 // throughput of the 256 kernel relative to the 128 kernel: kt256 = 2 * KT128 / rate
 constexpr double KT128 = 0.95, FIX128 = 6.0, LONE128 = 0.70, FIX256 = 9.0, LAUNCH_GAP = 2.0;
+
+// Which launches the dispatcher has made since the record was last cleared (aigv_gemm_route: AIGV_ROUTE_* bits, one per kind of launch).
+// Written where the launch is issued, so a test that forces a route reads back the route that RAN, not a restatement of the conditions.
+static std::atomic<unsigned> g_route{0};
+static inline void took(unsigned bit) { g_route.fetch_or(bit, std::memory_order_relaxed); }
+
 static double kt256() { return 2.0 * KT128 / g_rate256; }
 
 static double t256(long row_tiles, int N, int nk) {
@@ -110,6 +117,7 @@ static double t_skinny(int rows, int N, int K) {
 
 int launch_one(aigv_ctx* c, const GemmArgs& a, int epi, bool use256, hipStream_t s) {
   GEMM_PROF(c, a, s);
+  took(use256 ? AIGV_ROUTE_256 : AIGV_ROUTE_128);
   HIPCHK(c, use256 ? aigv_launch_gemm256(tuned(c, a), epi, s) : aigv_launch_gemm(a, epi, s));
   return 0;
 }
@@ -117,6 +125,7 @@ int launch_one(aigv_ctx* c, const GemmArgs& a, int epi, bool use256, hipStream_t
 // the co-resident 256x128 kernel (gemmco.hip): every row in full K, ragged row counts and half-tile tables included
 static int launch_co(aigv_ctx* c, const GemmArgs& a, int epi, hipStream_t s) {
   GEMM_PROF(c, a, s);
+  took(AIGV_ROUTE_CO);
   HIPCHK(c, aigv_launch_gemmco(tuned(c, a), epi, s));
   return 0;
 }
@@ -130,6 +139,7 @@ static int launch_splitk(aigv_ctx* c, const GemmArgs& a, int epi, int S, bool ti
   float* ws = nullptr;
   TRY(splitk_scratch(c, (size_t)S * a.M * a.N, &ws));
   GEMM_PROF(c, a, s);
+  took(tile256 ? AIGV_ROUTE_SPLITK_256 : AIGV_ROUTE_SPLITK_128);
   HIPCHK(c, aigv_launch_gemm_splitk(tuned(c, a), epi, S, ws, s, tile256));
   return 0;
 }
@@ -223,6 +233,7 @@ int run_gemm(aigv_ctx* c, const GemmArgs& a, int epi, hipStream_t s) {
   if (use_co(c, a, resolved_gemm_mode(c))) return launch_co(c, a, epi, s);
   const int mode = resolved_gemm_mode(c) == 3 || resolved_gemm_mode(c) == 4 ? 0 : resolved_gemm_mode(c);
   if (const int right = split_columns(a.M, a.N, a.K, epi, mode)) {
+    took(AIGV_ROUTE_COLUMN_BAND);
     TRY(run_gemm(c, col_slice(a, 0, a.N - right), epi, s));
     return launch_one(c, col_slice(a, a.N - right, right), epi, false, s);
   }
@@ -242,6 +253,7 @@ int run_gemm(aigv_ctx* c, const GemmArgs& a, int epi, hipStream_t s) {
     if (pl.last_kind == 1) {
       const int sk = skinny_epi(epi);
       ProfScope ps(c, c ? c->gemm_cls : AIGV_PROF_GEMM, 2.0 * bot.M * (double)a.N * a.K, 2.0 * (double)a.N * a.K, s);
+      took(AIGV_ROUTE_SKINNY);
       hipError_t e = aigv_launch_skinny_gemm(bot.A, bot.lda, bot.M, bot.W, bot.ldw, bot.N, bot.K, bot.bias, bot.resid, bot.ldr,
                                             bot.C, bot.ldc, sk, s, bot.ls);
       if (e != hipSuccess) return fail(c, AIGV_ERR_HIP, "skinny remainder (M=%d N=%d K=%d): %s", bot.M, bot.N, bot.K, hipGetErrorString(e));
@@ -309,11 +321,13 @@ static int launch_tab(aigv_ctx* c, const GemmArgs& a, int epi, const int32_t* ta
   b.row_tab = tab; b.tab_halves = halves;
   GEMM_PROF_ROWS(c, a, rows, s);
   if (S <= 1) {
+    took(AIGV_ROUTE_TAB_256);
     HIPCHK(c, aigv_launch_gemm256(b, epi, s));
     return 0;
   }
   float* ws = nullptr;
   TRY(splitk_scratch(c, (size_t)S * ((halves + 1) / 2) * 256 * a.N, &ws));
+  took(AIGV_ROUTE_TAB_SPLITK);
   HIPCHK(c, aigv_launch_gemm_splitk(b, epi, S, ws, s, true));
   return 0;
 }
@@ -329,6 +343,7 @@ static int run_tiny_tails(aigv_ctx* c, const GemmArgs& a, int epi, const RowPlan
       const int R = std::min(64, t.count - i0);
       const size_t r0 = (size_t)t.row0 + (size_t)i0 * t.stride_rows;
       ProfScope ps(c, c ? c->gemm_cls : AIGV_PROF_GEMM, 2.0 * R * (double)a.N * a.K, 2.0 * (double)a.N * a.K, s);
+      took(t.stride_rows == 1 ? AIGV_ROUTE_TINY : AIGV_ROUTE_TINY_STRIDED);
       hipError_t e = aigv_launch_skinny_gemm(a.A + r0 * a.lda, (int)ldx, R, a.W, a.ldw, a.N, a.K, a.bias, a.resid ? a.resid + r0 * a.ldr : nullptr,
                                             (int)ldr, a.C + r0 * a.ldc, (int)ldo, sk, s, a.ls, 0);
       if (e != hipSuccess) return fail(c, AIGV_ERR_HIP, "skinny tiny tails (R=%d N=%d K=%d): %s", R, a.N, a.K, hipGetErrorString(e));
@@ -350,6 +365,7 @@ int run_gemm_rows(aigv_ctx* c, const GemmArgs& a, int epi, const RowPlan& rp, hi
       GemmArgs b = a;
       b.row_tab = rp.d_tab; b.tab_halves = rp.body_halves + rp.tail_halves;
       GEMM_PROF_ROWS(c, a, rp.body_halves * 128 + rp.tail_rows, s);
+      took(AIGV_ROUTE_TAB_CO);
       HIPCHK(c, aigv_launch_gemmco(tuned(c, b), epi, s));
     }
     return run_tiny_tails(c, a, epi, rp, s);
@@ -382,12 +398,14 @@ int run_gemm_rows(aigv_ctx* c, const GemmArgs& a, int epi, const RowPlan& rp, hi
     b.row_tab = rp.d_tab; b.tab_halves = tails_apart ? rp.body_halves : rp.body_halves + rp.tail_halves;
     b.variant_sel = 7;
     GEMM_PROF_ROWS(c, a, rp.body_halves * 128 + (tails_apart ? 0 : rp.tail_rows), s);
+    took(AIGV_ROUTE_TAB_LONE);
     HIPCHK(c, aigv_launch_gemmco(b, epi, s));
   } else if (body128) {
     {
       GemmArgs b = a;
       b.row_tab = rp.d_tab; b.tab_halves = rp.body_halves;
       GEMM_PROF_ROWS(c, a, rp.body_halves * 128, s);
+      took(AIGV_ROUTE_TAB_128);
       HIPCHK(c, aigv_launch_gemm(b, epi, s));
     }
     if (rp.tail_halves > 0 && !tails_apart) TRY(launch_tab(c, a, epi, rp.d_tab + 2 * rp.body_halves, rp.tail_halves, rp.tail_rows, 1, s));
@@ -407,6 +425,7 @@ int run_gemm_rows(aigv_ctx* c, const GemmArgs& a, int epi, const RowPlan& rp, hi
       GemmArgs b = tuned(c, a);
       b.row_tab = rp.d_tab; b.tab_halves = rp.body_halves; b.fuse_tail_halves = rp.tail_halves; b.part = ws; b.k_slices = S;
       GEMM_PROF_ROWS(c, a, rp.body_halves * 128 + rp.tail_halves * 128, s);
+      took(AIGV_ROUTE_TAB_FUSED);
       HIPCHK(c, aigv_launch_gemm256_fused(b, epi, s));
       GemmArgs f = a;
       f.row_tab = rp.d_tab + 2 * rp.body_halves; f.tab_halves = rp.tail_halves;
@@ -474,8 +493,31 @@ int run_gemm_fp8(aigv_ctx* c, const bf16_t* A, int lda, int K, const uint8_t* W8
 }
 
 
+// What the weight-streaming kernel needs of its row strides (head.hip: x and W rows are read 16 bytes at a time; the epilogue stores a
+// u16x4 at out + r * ldo + n and reads one at resid + r * ldr + n).  nullptr if they fit.  run_skinny asks it; the skinny remainder of
+// run_gemm and run_tiny_tails launch the kernel directly, behind aigv_gemm_check, whose rule (multiples of 8, at least the width)
+// implies this one - a multiple of a multiple of 8 included (the tiny tails' row stride).  R > 64 and K % 128 are named here too, so
+// that no refusal of run_skinny is left to the launcher's bare hipErrorInvalidValue.
+const char* skinny_check(const bf16_t* x, int ldx, int R, const bf16_t* W, int ldw, int N, int K, const bf16_t* resid, int ldr,
+                         const bf16_t* out, int ldo, int epi) {
+  if (R < 0 || N <= 0 || K <= 0) return "skinny gemm: empty problem";
+  if (R > 64) return "skinny gemm: more than 64 rows";
+  if (K % 128) return "skinny gemm: K must be a multiple of 128";
+  if (!x || !W || !out) return "skinny gemm: null operand";
+  if (ldx < K || ldw < K || (ldx % 8) || (ldw % 8)) return "skinny gemm: bad leading dimension (ldx and ldw: at least K, multiples of 8)";
+  const int n_out = epi == SK_SWIGLU ? N / 2 : N;
+  if (ldo < n_out) return "skinny gemm: ldo is below the output width (rows would overlap)";
+  if (ldo % 4) return "skinny gemm: ldo must be a multiple of 4 (the kernel stores 8 bytes at out + row * ldo + n)";
+  if ((epi == SK_RESID || epi == SK_LS_RESID) && !resid) return "skinny gemm: residual epilogue needs resid";
+  if (resid && ldr < n_out) return "skinny gemm: ldr is below the width of the residual rows";
+  if (resid && (ldr % 4)) return "skinny gemm: ldr must be a multiple of 4 (the kernel reads 8 bytes at resid + row * ldr + n)";
+  return nullptr;
+}
+
 int run_skinny(aigv_ctx* c, const bf16_t* x, int ldx, int R, const bf16_t* W, int ldw, int N, int K, const bf16_t* bias,
                const bf16_t* resid, int ldr, bf16_t* out, int ldo, int epi, hipStream_t s, int p) {
+  if (const char* m = skinny_check(x, ldx, R, W, ldw, N, K, resid, ldr, out, ldo, epi))
+    return fail(c, AIGV_ERR_ARG, "%s (R=%d N=%d K=%d epi=%d)", m, R, N, K, epi);
   ProfScope ps(c, AIGV_PROF_SKINNY, 2.0 * R * (double)N * K, 2.0 * (double)N * K, s);
   // p = 0 (the scoring pass: last-layer consumed rows, motion_mlp, tiny sequence tails): the fixed 4-slice form whatever the row count, so
   // that a row's bits do not depend on its batch; p = 1 / 2 / 4 are the decode step's forms (decode_forms).
@@ -501,4 +543,8 @@ extern "C" int aigv_plan_gemm(int M, int N, int K, int epi, int* plan, double* e
   plan[5] = pl.last_slices;
   if (est_us) *est_us = pl.est_us + (right ? t128(M, right, K / 64) + LAUNCH_GAP : 0.0);
   return 0;
+}
+
+extern "C" int aigv_gemm_route(int clear) {
+  return (int)(clear ? g_route.exchange(0, std::memory_order_relaxed) : g_route.load(std::memory_order_relaxed));
 }

@@ -285,12 +285,20 @@ const char* aigv_gemm_check(const GemmArgs& a, int epi) {
   if (a.M <= 0 || a.N <= 0 || a.K <= 0) return "gemm: empty problem";
   if (a.N % BN) return "gemm: N must be a multiple of 128";
   if (a.K % BK) return "gemm: K must be a multiple of 64";
-  if (a.lda < a.K || a.ldw < a.K || (a.lda % 8) || (a.ldw % 8) || (a.ldc % 4)) return "gemm: bad leading dimension";
+  if (a.lda < a.K || a.ldw < a.K || (a.lda % 8) || (a.ldw % 8)) return "gemm: bad leading dimension (lda and ldw: at least K, multiples of 8)";
+  // Row strides of C and of the residual.  The dispatcher may put any rows of a call on any tile kernel, so ONE rule covers the widest access
+  // of them all: the 128 kernel stores and reads 8 bytes (the u16x4 at C + orow * ldc + n and at resid + m * ldr + n above), the 256 and
+  // the co-resident kernels 16 (store_row_segment's u16x8 at C + m * ldc + n in gemm256.hip / gemmco.hip, and the residual's 16-byte
+  // LDS-direct prefetch resid_dma from resid + hb * ldr + n0).  Every width of the models is a multiple of 8.
+  const int n_out = epi == EPI_SWIGLU ? a.N / 2 : a.N;
+  if (a.ldc < n_out) return epi == EPI_SWIGLU ? "gemm: swiglu output is N/2 wide: ldc is below it (rows would overlap)" : "gemm: ldc is below N (rows would overlap)";
+  if (a.ldc % 8) return "gemm: ldc must be a multiple of 8 (the tile kernels store 16 bytes at C + row * ldc + n)";
+  if (a.resid && a.ldr < n_out) return "gemm: ldr is below the width of the residual rows";
+  if (a.resid && (a.ldr % 8)) return "gemm: ldr must be a multiple of 8 (the tile kernels read 16 bytes at resid + row * ldr + n)";
   if (!a.A || !a.W || !a.C) return "gemm: null operand";
   if ((epi == EPI_LS_RESID) && (!a.ls || !a.resid)) return "gemm: layer-scale/residual epilogue needs ls and resid";
   if ((epi == EPI_RESID) && !a.resid) return "gemm: residual epilogue needs resid";
   if ((epi == EPI_PATCH) && (!a.pos || a.np <= 0 || a.M % a.np)) return "gemm: patch epilogue needs pos, np | M";
-  if (epi == EPI_SWIGLU && a.ldc < a.N / 2) return "gemm: swiglu output is N/2 wide";
   if (epi < 0 || epi >= EPI_COUNT) return "gemm: unknown epilogue";
   return nullptr;
 }

@@ -15,6 +15,24 @@ int aigv_op_gemm(const void* A, int lda, const void* W_, int ldw, void* C, int l
   return run_gemm(nullptr, a, epi, (hipStream_t)stream);
 }
 
+// The argument check of aigv_op_gemm / _rows / _splitk* and of aigv_op_skinny_gemm alone: host only, nothing is launched and no pointer is
+// dereferenced.  0 if the call would reach its launch, else AIGV_ERR_ARG with the refusal in aigv_last_error(NULL).
+int aigv_op_gemm_check(const void* A, int lda, const void* W_, int ldw, const void* C, int ldc, const void* bias, const void* ls,
+                       const void* resid, int ldr, const void* pos, int np, int M, int N, int K, int epi) {
+  GemmArgs a = gemm_args((const bf16_t*)A, lda, (const bf16_t*)W_, ldw, (bf16_t*)C, ldc, M, N, K);
+  a.bias = (const bf16_t*)bias; a.ls = (const bf16_t*)ls; a.resid = (const bf16_t*)resid; a.ldr = ldr;
+  a.pos = (const bf16_t*)pos; a.np = np;
+  if (const char* m = aigv_gemm_check(a, epi)) return fail(nullptr, AIGV_ERR_ARG, "%s (M=%d N=%d K=%d epi=%d)", m, M, N, K, epi);
+  return 0;
+}
+
+int aigv_op_skinny_gemm_check(const void* x, int ldx, int R, const void* W_, int ldw, int N, int K, const void* resid, int ldr,
+                              const void* out, int ldo, int epi) {
+  if (const char* m = skinny_check((const bf16_t*)x, ldx, R, (const bf16_t*)W_, ldw, N, K, (const bf16_t*)resid, ldr, (const bf16_t*)out, ldo, epi))
+    return fail(nullptr, AIGV_ERR_ARG, "%s (R=%d N=%d K=%d epi=%d)", m, R, N, K, epi);
+  return 0;
+}
+
 // aigv_op_gemm with the rows divided into independent sequences (cu_host[0..n_seq], cu[0] = 0, cu[n_seq] = M): the dispatch the scoring
 // pass uses (struct RowPlan).  Test entry point: allocates the plan's table per call and synchronises the stream before freeing it.
 int aigv_op_gemm_rows(const void* A, int lda, const void* W_, int ldw, void* C, int ldc, const void* bias, const void* ls,

@@ -97,6 +97,8 @@ PROTOTYPES = {
     "aigv_out_row_topk_logprob": (_I, [_P, _I, _I, _I, _P, _P, _P]),
     "aigv_decode_eos": (_I, [_P, _P, _P, _I64P, _I, C.c_int64, _P]),
     "aigv_op_gemm": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
+    "aigv_op_gemm_check": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I]),
+    "aigv_op_skinny_gemm_check": (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _I, _P, _I, _I]),
     "aigv_op_gemm_rows": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _I, C.POINTER(C.c_int32), _I, _I, _I, _I, _P]),
     "aigv_op_gemm_splitk": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "aigv_op_gemm_splitk256": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
@@ -161,6 +163,7 @@ PROTOTYPES = {
     "aigv_tune_attention": (_I, [_I]),
     "aigv_tune_skinny": (_I, [_I]),
     "aigv_plan_gemm": (_I, [_I, _I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    "aigv_gemm_route": (_I, [_I]),
     "aigv_prof_enable": (_I, [_P, _I]),
     "aigv_prof_read": (_I, [_P, _I, _I64P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }

@@ -274,9 +274,19 @@ int aigv_out_row_topk_logprob(aigv_ctx* ctx, int first_row, int n_rows, int k, i
 int aigv_decode_eos(aigv_ctx* ctx, int64_t* tokens, int32_t* state, const int64_t* eos_ids, int n_eos, int64_t pad_id, void* stream);
 
 /* ---- single operators (parity tests call these through the same ABI) --------------------------------- */
-/* C = epilogue(A[M,K] . W[N,K]^T); epi: 0 store, 1 gelu, 2 layerscale+residual, 3 residual, 4 swiglu, 5 patch */
+/* C = epilogue(A[M,K] . W[N,K]^T); epi: 0 store, 1 gelu, 2 layerscale+residual, 3 residual, 4 swiglu, 5 patch
+ * Row strides, in bf16 elements, for aigv_op_gemm, _gemm_rows, _gemm_splitk and _gemm_splitk256 alike (refused with AIGV_ERR_ARG before
+ * any launch otherwise): lda, ldw >= K; ldc >= the output width (N, or N / 2 for swiglu); ldr >= that width whenever resid is given;
+ * all four multiples of 8 - the dispatcher may run any rows of a call on any tile kernel, and the 256x256 and the co-resident kernels
+ * move 16 bytes at C + row * ldc + n and at resid + row * ldr + n.  resid may alias C (then ldr == ldc). */
 int aigv_op_gemm(const void* A, int lda, const void* W, int ldw, void* C, int ldc, const void* bias, const void* ls,
                  const void* resid, int ldr, const void* pos, int np, int M, int N, int K, int epi, void* stream);
+/* That argument check alone (host only: nothing is launched, no pointer is dereferenced): 0, or AIGV_ERR_ARG and the refusal in
+ * aigv_last_error(NULL).  aigv_op_skinny_gemm_check is the same for aigv_op_skinny_gemm. */
+int aigv_op_gemm_check(const void* A, int lda, const void* W, int ldw, const void* C, int ldc, const void* bias, const void* ls,
+                       const void* resid, int ldr, const void* pos, int np, int M, int N, int K, int epi);
+int aigv_op_skinny_gemm_check(const void* x, int ldx, int R, const void* W, int ldw, int N, int K, const void* resid, int ldr,
+                              const void* out, int ldo, int epi);
 /* The same GEMM with its M = cu_host[n_seq] rows divided into n_seq independent sequences (HOST int32 cu_host[0..n_seq], cu[0] = 0; epi
  * 0..4): the dispatch of the scoring pass.  Every sequence's rows [0, 256 * floor(L / 256)) run in full K as whole tiles addressed
  * through a half-tile table on the 256x256 kernel (AIGV_TUNE_BODY_TILE = 2: on the 128x128 kernel, which sums every element in the same
@@ -306,6 +316,9 @@ int aigv_op_quant_fp8_rows(const void* x_bf16, int ldx, int rows, int K, void* q
 int aigv_op_gemm_fp8(const void* A_e4m3, int lda, const void* W_e4m3, int ldw, void* C, int ldc, const float* row_scale,
                      const float* col_scale, const void* bias, const void* ls, const void* resid, int ldr, int M, int N, int K, int epi,
                      int k_slices, void* ws_f32, void* stream);   /* k_slices > 1: split-K, ws_f32 = k_slices * M * N floats, K/128 % k_slices == 0 */
+/* The weight-streaming GEMM of R <= 64 rows.  Row strides in bf16 elements (refused with AIGV_ERR_ARG before any launch otherwise): ldx,
+ * ldw >= K and multiples of 8; ldo >= the output width (N, or N / 2 for swiglu) and a multiple of 4; ldr the same whenever resid is given
+ * (the kernel moves 8 bytes at out + row * ldo + n and at resid + row * ldr + n). */
 int aigv_op_skinny_gemm(const void* x, int ldx, int R, const void* W, int ldw, int N, int K, const void* bias,
                         const void* resid, int ldr, void* out, int ldo, int epi, void* stream);
 /* The e4m3 form of a decode GEMV (fp8 mode; what aigv_decode_step runs per linear after aigv_set_precision(fp8)): R <= 4 bf16 rows x
@@ -520,6 +533,27 @@ int aigv_tune_default(int knob, int value);
  * column band that runs on the 128x128 kernel over all rows (N = 256 j + 128: plan[0..5] then describe the first 256 j columns;
  * 0 = no column split); `plan` holds 7 ints; est_us = the model's time. */
 int aigv_plan_gemm(int M, int N, int K, int epi, int* plan, double* est_us);
+/* The launches the GEMM dispatcher (aigv_op_gemm, aigv_op_gemm_rows and every pass) has made in this process since the record was last
+ * cleared: the OR of one AIGV_ROUTE_* bit per kind of launch, set where the launch is issued.  clear != 0 returns the record and empties
+ * it.  Host only; for tests that force a route and must prove that it ran (ABI 3, added symbol). */
+enum {
+  AIGV_ROUTE_128 = 1,              /* every row of the (sliced) problem on the 128x128 kernel */
+  AIGV_ROUTE_256 = 2,              /* ... on the 256x256 kernel */
+  AIGV_ROUTE_CO = 4,               /* ... on the co-resident 256x128 kernel */
+  AIGV_ROUTE_SPLITK_128 = 8,       /* a row band as K slices of the 128x128 kernel + finalize */
+  AIGV_ROUTE_SPLITK_256 = 16,      /* a row band as K slices of the 256x256 kernel + finalize */
+  AIGV_ROUTE_SKINNY = 32,          /* the last rows of run_gemm on the weight-streaming kernel */
+  AIGV_ROUTE_COLUMN_BAND = 64,     /* N = 256 j + 128 cut into a left part and a right-hand 128-column band */
+  AIGV_ROUTE_TAB_256 = 128,        /* half tiles of a row plan on the 256x256 kernel, full K */
+  AIGV_ROUTE_TAB_SPLITK = 256,     /* tail half tiles of a row plan as K slices in a launch of their own + finalize */
+  AIGV_ROUTE_TAB_FUSED = 512,      /* body tiles and the tails' K slices in one launch, then finalize */
+  AIGV_ROUTE_TAB_LONE = 1024,      /* half tiles on the co-resident kernel's one-workgroup-per-CU form */
+  AIGV_ROUTE_TAB_128 = 2048,       /* body half tiles on the 128x128 kernel */
+  AIGV_ROUTE_TAB_CO = 4096,        /* body and tail half tiles on the co-resident kernel (K <= AIGV_TUNE_CO_KMAX) */
+  AIGV_ROUTE_TINY = 8192,          /* tiny sequence tails on the weight-streaming kernel, one launch per sequence */
+  AIGV_ROUTE_TINY_STRIDED = 16384  /* uniform tiny tails: one launch per tail row over all sequences, row stride = sequence length */
+};
+int aigv_gemm_route(int clear);
 /* Prefill-attention kernel form (process-wide; experiments and tests): 0 = default (attention.hip: 4 waves x 32 query rows per
  * workgroup, two-deep K/V ring); 4 or 8 = that many waves per workgroup (three-deep rings lost the in-step A/B and were removed:
  * profiles/r3_attn_ring_negative.txt). */
