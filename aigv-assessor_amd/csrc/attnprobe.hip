@@ -1,0 +1,132 @@
+// Score-row attention probe: where ONE query row of a causal GQA attention looks, folded into a few key segments (frames, motion token,
+// text).  The flash prefill kernel (attention.hip) never forms a probability matrix; this stand-alone kernel recomputes the softmax of the
+// few rows somebody asks about from the Q (unrotated) and K (rotated) that llm_layer_qkv leaves in the fused qkv rows - or, for a
+// continuation, from the KV cache - and touches nothing the pass itself reads afterwards.
+//
+// One 256-thread workgroup per (probe row, query head).  For the row at position p = key offset + local row of its sequence:
+//   1. q is rotated at p with rope_pair (common.h: rope_kernel's arithmetic, so the rotated q carries the bits aigv_op_rope would store);
+//   2. s_j = (q . k_j) / sqrt(D) in fp32 for the keys j = 0..p of the SAME sequence (the causal rule: a later key, or another sequence's, is
+//      never read); thread t takes keys t, t + 256, ... in ascending order.  Scores are always fp32 here, whatever the pass's attention
+//      numerics (aigv_set_attention_numerics) say: the probe reports where the row looks, it does not feed the pass;
+//   3. the row maximum m comes out of the log-probability kernels' one reduction tree (lse_of_block, common.h) - only m is used;
+//   4. a second sweep adds e_j = exp(s_j - m) to the thread's own LDS column of bin seg[j] and of the total; an id outside [0, S) drops
+//      the key from the bins, not from the total;
+//   5. columns are summed lanes first (xor butterfly), then waves in wave order; out[seg] = bin[seg] / total, ONE fp32 division.
+// The summation order is a function of the key index alone (no float atomics, nothing depends on the row count, the batch mates or the
+// grid), so a row's bits are its own - and integer-valued e_j (Q = 0: every e_j is 1) give exact counts.
+#include "common.h"
+#include "kernels.h"
+
+namespace {
+
+// (q . k) / post_div with the products accumulated in key-element order by explicit fmaf: both sweeps get the same bits
+template <int D>
+__device__ __forceinline__ float probe_score(const float* __restrict__ qs, const bf16_t* __restrict__ kp, float post_div) {
+  float acc = 0.0f;
+#pragma unroll
+  for (int c = 0; c < D / 8; ++c) {
+    const u16x8 kv = *(const u16x8*)(kp + 8 * c);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc = fmaf(qs[8 * c + e], bf2f(kv[e]), acc);
+  }
+  return acc / post_div;
+}
+
+template <int D>
+__global__ __launch_bounds__(LSE_THREADS) void attn_probe_kernel(const ProbeArgs p) {
+  extern __shared__ float bins[];                      // [n_seg + 1][256]: column = thread, row n_seg = the total
+  __shared__ float qs[D];
+  __shared__ float red[(AIGV_MAX_ATTN_SEGMENTS + 1) * (LSE_THREADS / AIGV_WAVE)];
+  const int tid = threadIdx.x, lane = tid % AIGV_WAVE, wave = tid / AIGV_WAVE;
+  const ProbeRow pr = p.tab.r[blockIdx.x];
+  const int h = blockIdx.y, g = p.n_heads / p.n_kv_heads, hk = h / g;
+  const int pos = pr.off + (pr.row - pr.row0), n_keys = pos + 1, S = p.n_seg;
+  constexpr int half = D / 2;
+
+  if (tid < half) {
+    const bf16_t* q = p.q + (size_t)pr.row * p.ldq + (size_t)hk * p.q_group_stride + (size_t)(h % g) * D;
+    const size_t tb = (size_t)pos * half + tid;
+    bf16_t lo, hi;
+    rope_pair(q[tid], q[tid + half], p.rope_cos[tb], p.rope_sin[tb], lo, hi);
+    qs[tid] = bf2f(lo);
+    qs[tid + half] = bf2f(hi);
+  }
+  for (int s = 0; s <= S; ++s) bins[s * LSE_THREADS + tid] = 0.0f;
+  __syncthreads();
+
+  // packed: the sequence's rows of the pass (row0 + j);  cache: [seq][kv head][cap][D], position j
+  const bf16_t* kb = p.k + (p.kv_seq_stride ? (size_t)pr.seq * p.kv_seq_stride : (size_t)pr.row0 * p.ldk) + (size_t)hk * p.kv_head_stride;
+  float m = -INFINITY, sum = 0.0f;
+  for (int j = tid; j < n_keys; j += LSE_THREADS) lse_push(m, sum, probe_score<D>(qs, kb + (size_t)j * p.ldk, p.post_div));
+  float row_max = 0.0f;
+  lse_of_block<false>(m, sum, &row_max);
+
+  for (int j = tid; j < n_keys; j += LSE_THREADS) {
+    const float e = expf(probe_score<D>(qs, kb + (size_t)j * p.ldk, p.post_div) - row_max);
+    const int sg = j < pr.off ? p.seg_cached[(size_t)pr.seq * p.ld_cached + j] : p.seg_new[pr.row0 + (j - pr.off)];
+    bins[S * LSE_THREADS + tid] += e;
+    if (sg >= 0 && sg < S) bins[sg * LSE_THREADS + tid] += e;
+  }
+  // every thread has written its own column only: no barrier in front of the butterflies
+  for (int s = 0; s <= S; ++s) {
+    const float v = wave_sum(bins[s * LSE_THREADS + tid]);
+    if (lane == 0) red[s * (LSE_THREADS / AIGV_WAVE) + wave] = v;
+  }
+  __syncthreads();
+  if (tid < S) {
+    const float* rt = red + S * (LSE_THREADS / AIGV_WAVE);
+    const float* rb = red + tid * (LSE_THREADS / AIGV_WAVE);
+    const float total = ((rt[0] + rt[1]) + rt[2]) + rt[3];
+    const float bin = ((rb[0] + rb[1]) + rb[2]) + rb[3];
+    p.out[(size_t)blockIdx.x * p.out_row_stride + (size_t)h * S + tid] = bin / total;
+  }
+}
+
+template <int D>
+hipError_t launch_probe(const ProbeArgs& a, hipStream_t s) {
+  static LdsAttrOnce lds_attr;
+  constexpr int max_lds = (AIGV_MAX_ATTN_SEGMENTS + 1) * LSE_THREADS * (int)sizeof(float);
+  if (hipError_t e = lds_attr.ensure((const void*)attn_probe_kernel<D>, max_lds); e != hipSuccess) return e;
+  const int lds = (a.n_seg + 1) * LSE_THREADS * (int)sizeof(float);
+  hipLaunchKernelGGL((attn_probe_kernel<D>), dim3(a.n_rows, a.n_heads), dim3(LSE_THREADS), lds, s, a);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+// Every index the kernel forms is bounded here, on the host, from the host copies of the sequence table: nothing is launched otherwise.
+const char* aigv_probe_check(const ProbeArgs& a, int head_dim, int total_rows, int max_pos) {
+  if (head_dim != 64 && head_dim != 128) return "attention probe: head_dim must be 64 or 128";
+  if (!a.q || !a.k || !a.rope_cos || !a.rope_sin || !a.seg_new || !a.out) return "attention probe: null operand";
+  if (a.n_rows < 1 || a.n_rows > AIGV_MAX_PROBE_ROWS) return "attention probe: the number of probe rows is outside 1..AIGV_MAX_PROBE_ROWS (64)";
+  if (a.n_seg < 1 || a.n_seg > AIGV_MAX_ATTN_SEGMENTS) return "attention probe: the number of segments is outside 1..AIGV_MAX_ATTN_SEGMENTS (64)";
+  if (a.n_kv_heads < 1 || a.n_heads < a.n_kv_heads || a.n_heads % a.n_kv_heads || a.n_heads > 65535) return "attention probe: n_heads must be a multiple of n_kv_heads";
+  const int g = a.n_heads / a.n_kv_heads;
+  if (a.q_group_stride < g * head_dim || (int64_t)a.ldq < (int64_t)(a.n_kv_heads - 1) * a.q_group_stride + g * head_dim) return "attention probe: q strides too small";
+  if (a.ldk % 8 || a.kv_head_stride % 8 || a.kv_seq_stride % 8 || ((uintptr_t)a.k & 15)) return "attention probe: K must be 16-byte aligned with strides that are multiples of 8";
+  if (!(a.post_div > 0.0f)) return "attention probe: post_div must be positive";
+  if (a.out_row_stride < (size_t)a.n_heads * a.n_seg) return "attention probe: out row stride below n_heads * n_segments";
+  int cap = 0;
+  if (a.kv_seq_stride) {   // cache layout [seq][kv head][cap][D]
+    if (a.ldk < head_dim || a.kv_head_stride < a.ldk) return "attention probe: cache strides too small";
+    cap = a.kv_head_stride / a.ldk;
+    if (a.kv_seq_stride < (size_t)a.n_kv_heads * a.kv_head_stride) return "attention probe: kv_seq_stride below n_kv_heads * kv_head_stride";
+  } else if (a.kv_head_stride < head_dim || (int64_t)a.ldk < (int64_t)(a.n_kv_heads - 1) * a.kv_head_stride + head_dim) {
+    return "attention probe: packed K strides too small";
+  }
+  for (int i = 0; i < a.n_rows; ++i) {
+    const ProbeRow& r = a.tab.r[i];
+    if (r.row < 0 || r.row >= total_rows || r.row0 < 0 || r.row0 > r.row || r.seq < 0) return "attention probe: a probe row lies outside the pass";
+    if (r.off < 0 || (r.off > 0 && (!a.kv_seq_stride || !a.seg_cached || a.ld_cached < r.off))) return "attention probe: cached keys need the cache layout and a seg_cached table that covers them";
+    const int pos = r.off + (r.row - r.row0);
+    if (pos >= max_pos) return "attention probe: a probe row's position lies outside the RoPE table";
+    if (a.kv_seq_stride && pos >= cap) return "attention probe: a probe row's position lies outside the KV cache";
+  }
+  return nullptr;
+}
+
+hipError_t aigv_launch_attention_probe(const ProbeArgs& a, int head_dim, hipStream_t s) {
+  if (head_dim == 128) return launch_probe<128>(a, s);
+  if (head_dim == 64) return launch_probe<64>(a, s);
+  return hipErrorInvalidValue;
+}

@@ -79,6 +79,15 @@ __device__ __forceinline__ f32x2 silu2(f32x2 x) {
   return x * f32x2{__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
 }
 
+// RoPE of one (x1, x2) = (x[i], x[i + D/2]) pair (modeling_internlm2.py:247-261): out = bf16(bf16(x*cos) + bf16(rot(x)*sin)), three bf16
+// roundings per element.  The one statement of that arithmetic: rope_kernel (rowops.hip) rotates K (and Q) in place with it, the attention
+// probe (attnprobe.hip) rotates its query row with it - so the probe's rotated q carries the bits aigv_op_rope would store.
+__device__ __forceinline__ void rope_pair(bf16_t lo, bf16_t hi, bf16_t co, bf16_t si, bf16_t& olo, bf16_t& ohi) {
+  const float x1 = bf2f(lo), x2 = bf2f(hi), cc = bf2f(co), ss = bf2f(si);
+  olo = f2bf(rbf(x1 * cc) + rbf(-x2 * ss));
+  ohi = f2bf(rbf(x2 * cc) + rbf(x1 * ss));
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -140,8 +149,10 @@ __device__ __forceinline__ void lse_combine_unfused(float& m, float& s, float m2
 // always rounded both products before the addition, the lm-head finisher has always fused one (what the compiler made of the same
 // expression in the two places).  Each keeps its bits; the two kernels are never compared with each other bit for bit.
 constexpr int LSE_THREADS = 256;
+// row_max (optional): also hands out the row maximum m of the reduced pair - what the attention probe (attnprobe.hip) takes from this tree;
+// it forms its own total and subtracts no log-sum-exp.
 template <bool FUSED_TAIL>
-__device__ __forceinline__ float lse_of_block(float m, float s) {
+__device__ __forceinline__ float lse_of_block(float m, float s, float* row_max = nullptr) {
 #pragma unroll
   for (int off = AIGV_WAVE / 2; off >= 1; off >>= 1) lse_combine(m, s, __shfl_xor(m, off), __shfl_xor(s, off));
   __shared__ float wm[LSE_THREADS / AIGV_WAVE], ws[LSE_THREADS / AIGV_WAVE];
@@ -158,6 +169,7 @@ __device__ __forceinline__ float lse_of_block(float m, float s) {
     if (FUSED_TAIL) lse_combine(m, s, wm[w], ws[w]);
     else lse_combine_unfused(m, s, wm[w], ws[w]);
   }
+  if (row_max) *row_max = m;
   return m + logf(s);
 }
 

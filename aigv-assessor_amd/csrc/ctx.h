@@ -116,6 +116,14 @@ struct aigv_ctx {
   std::vector<int32_t> h_pos, h_seq, h_rowidx, h_kvlen;
   int kv_seqs = 0;
   bool kv_valid = false;
+  // score-row attention probe (aigv_score_attention_arm): armed for exactly the next aigv_llm_prefill / aigv_llm_extend
+  struct {
+    bool armed = false;
+    int n_rows = 0, n_seg = 0, ld_cached = 0;
+    int32_t rows[AIGV_MAX_PROBE_ROWS];
+    const int32_t *seg_new = nullptr, *seg_cached = nullptr;
+    float* out = nullptr;
+  } probe;
   // profiling
   bool prof = false;
   int gemm_cls = AIGV_PROF_GEMM;   // class the GEMM launches are booked under: AIGV_PROF_GEMM_VIT inside aigv_vit_forward / aigv_project
@@ -238,6 +246,17 @@ int run_skinny(aigv_ctx* c, const bf16_t* x, int ldx, int R, const bf16_t* W, in
                const bf16_t* resid, int ldr, bf16_t* out, int ldo, int epi, hipStream_t s, int p = 1);
 constexpr size_t SPLITK_MAX_FLOATS = (size_t)64 << 20;   // 256 MB of fp32 split-K slabs: the planner never asks for more
 int splitk_scratch(aigv_ctx* c, size_t need_floats, float** out);
+
+// ---- the score-row attention probe of an armed pass (probe.hip) --------------------------------------------------------------------
+// DisarmScope: the pass that finds the context armed disarms it on every way out.  probe_plan: the probe's arguments for this pass (rows
+// validated against cu; off_host: keys cached in front of every sequence, or null), built ONCE per pass; probe_layer: the launch of layer li.
+struct DisarmScope {
+  aigv_ctx* c;
+  explicit DisarmScope(aigv_ctx* c_) : c(c_) {}
+  ~DisarmScope() { c->probe.armed = false; }
+};
+int probe_plan(aigv_ctx* c, const char* op, const int32_t* cu, int B, const int32_t* off_host, ProbeArgs* out);
+int probe_layer(aigv_ctx* c, const ProbeArgs& plan, int li, bool cache, hipStream_t s);
 extern double g_rate256;   // the cost model's throughput of the 256 kernel relative to the 128 kernel (aigv_tune_gemm overrides it)
 
 }  // namespace aigv

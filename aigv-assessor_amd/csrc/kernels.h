@@ -120,6 +120,40 @@ hipError_t aigv_launch_attention_decode(const bf16_t* q, int ldq, int q_group_st
                                         int n_seq, int n_kv, int g, int head_dim, float post_div, int max_kv_len,
                                         float* ws, hipStream_t s);
 
+// ---- attention probe (attnprobe.hip) ----------------------------------------------------------------
+// Where ONE query row of a causal GQA attention looks: out[row][head][seg] = sum of softmax(q . K / post_div) over the keys of segment
+// seg, for up to AIGV_MAX_PROBE_ROWS rows per launch.  q: UNROTATED rows of the fused qkv buffer (q head h at column (h / g) *
+// q_group_stride + (h % g) * D), rotated by the kernel at the row's position with rope_kernel's arithmetic; K: already rotated, in one of
+// AttnArgs' two addressing forms - packed (kv_seq_stride = 0: key j of a sequence is row row0 + j, ldk apart) or the KV cache
+// (kv_seq_stride != 0: [seq][kv head][cap][D], ldk = D, kv_head_stride = cap * D; keys [0, off) were cached before the pass, the pass's own
+// rows follow).  Scores are fp32 whatever the pass's attention numerics.  seg ids: seg_new[packed row] for the pass's rows,
+// seg_cached[seq * ld_cached + j] for cached positions j < off; an id outside [0, n_seg) drops the key from the bins, not from the total.
+#ifndef AIGV_MAX_ATTN_SEGMENTS
+#define AIGV_MAX_ATTN_SEGMENTS 64   // = include/aigv_amd.h
+#endif
+#ifndef AIGV_MAX_PROBE_ROWS
+#define AIGV_MAX_PROBE_ROWS 64      // = include/aigv_amd.h
+#endif
+struct ProbeRow { int32_t row, row0, seq, off; };   // packed row | first packed row of its sequence | sequence | keys cached in front of the pass
+struct ProbeRowTab { ProbeRow r[AIGV_MAX_PROBE_ROWS]; };   // by value: a kernel argument (no copy, no allocation - the pass still captures)
+struct ProbeArgs {
+  const bf16_t* q; int ldq;
+  const bf16_t* k; int ldk;
+  int n_heads, n_kv_heads;
+  int q_group_stride, kv_head_stride;
+  size_t kv_seq_stride;
+  float post_div;                        // sqrt(D)
+  const bf16_t* rope_cos; const bf16_t* rope_sin;   // [max_pos, D/2]
+  const int32_t* seg_new; const int32_t* seg_cached; int ld_cached;
+  int n_seg;
+  float* out; size_t out_row_stride;     // out[row * out_row_stride + head * n_seg + seg]
+  int n_rows;
+  ProbeRowTab tab;
+};
+// nullptr if every index the kernel forms stays inside its operand: total_rows = rows of the pass (q, seg_new), max_pos = rows of the RoPE tables
+const char* aigv_probe_check(const ProbeArgs& a, int head_dim, int total_rows, int max_pos);
+hipError_t aigv_launch_attention_probe(const ProbeArgs& a, int head_dim, hipStream_t s);
+
 // ---- row-wise / elementwise ---------------------------------------------------------------------
 // LayerNorm over rows of length H (fp32 statistics, bf16 out).
 hipError_t aigv_launch_layernorm(const bf16_t* x, int ldx, const bf16_t* w, const bf16_t* b, bf16_t* y, int ldy,

@@ -272,6 +272,8 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
                      int n_vis, const void* motion, const int32_t* score_rows, float* score, const int32_t* logit_rows,
                      int R, int64_t* argmax, int keep_kv, void* stream) {
   if (!c || !ids || !slot || !cu) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: null argument");
+  const bool probing = c->probe.armed;   // aigv_score_attention_arm: this pass carries the probe, and disarms on every way out
+  DisarmScope disarm(c);
   if (!c->finalized) return fail(c, AIGV_ERR_STATE, "aigv_llm_prefill: call aigv_finalize_weights first");
   const aigv_config& k = c->cfg;
   if (B <= 0 || B > k.max_seqs) return fail(c, AIGV_ERR_ARG, "n_clips %d outside 1..%d", B, k.max_seqs);
@@ -330,6 +332,8 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
   const bool trim = trim_ok && (int)small_rows.size() == n_out;
   const bool mixed = trim_ok && !trim && !small_rows.empty();
   if (mixed) HIPCHK(c, aigv_launch_write_ints(small_rows.data(), (int)small_rows.size(), c->l_rowidx2, s));
+  ProbeArgs probe{};
+  if (probing) TRY(probe_plan(c, "aigv_llm_prefill", cu, B, nullptr, &probe));
   double attn_flops = 0;
   for (int b = 0; b < B; ++b) { const double L = cu[b + 1] - cu[b]; attn_flops += 4.0 * (L * (L + 1) / 2) * D * k.llm_heads; }
   const size_t kv_layer = (size_t)k.max_seqs * nkv * k.kv_capacity * D;
@@ -339,6 +343,7 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
     if (keep_kv)
       HIPCHK(c, aigv_launch_kv_store(c->l_qkv, c->qkv_out, c->l_seq, c->l_pos, c->kc + li * kv_layer, c->vc + li * kv_layer, T,
                                      nkv, g, D, k.kv_capacity, s));
+    if (probing) TRY(probe_layer(c, probe, li, false, s));   // Q and rotated K of this pass's rows, straight from l_qkv (every layer: it does not read l_ao)
     // a pass that only fills the cache (no output rows) needs nothing of the last layer beyond its K/V
     if (n_out == 0 && c->trim_last_layer && li == k.llm_layers - 1) break;
     {
@@ -396,6 +401,8 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
 int aigv_llm_extend(aigv_ctx* c, const int64_t* ids, const int32_t* cu, int B, const int32_t* score_rows, float* score,
                     const int32_t* logit_rows, int R, int64_t* argmax, int commit, void* stream) {
   if (!c || !ids || !cu) return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: null argument");
+  const bool probing = c->probe.armed;
+  DisarmScope disarm(c);
   if (!c->kv_valid) return fail(c, AIGV_ERR_STATE, "aigv_llm_extend: no KV state (run aigv_llm_prefill with keep_kv)");
   const aigv_config& k = c->cfg;
   if (B != c->kv_seqs) return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: %d sequences, the cache holds %d", B, c->kv_seqs);
@@ -420,6 +427,8 @@ int aigv_llm_extend(aigv_ctx* c, const int64_t* ids, const int32_t* cu, int B, c
   HIPCHK(c, aigv_launch_write_ints(c->h_kvlen.data(), B, c->l_kvlen, s));
   HIPCHK(c, aigv_launch_embed(ids, c->l_neg1, c->tok_emb, nullptr, nullptr, 0, c->l_h, T, H, s));
   TRY(upload_out_rows(c, score_rows, score != nullptr, B, logit_rows, R, T, s));
+  ProbeArgs probe{};
+  if (probing) TRY(probe_plan(c, "aigv_llm_extend", cu, B, c->h_kvlen.data(), &probe));
   double attn_flops = 0;
   for (int b = 0; b < B; ++b) { const double n = cu[b + 1] - cu[b]; attn_flops += 4.0 * n * (c->h_kvlen[b] + (n + 1) / 2) * D * k.llm_heads; }
   const size_t kv_layer = (size_t)k.max_seqs * nkv * k.kv_capacity * D;
@@ -429,6 +438,7 @@ int aigv_llm_extend(aigv_ctx* c, const int64_t* ids, const int32_t* cu, int B, c
     TRY(llm_layer_qkv(c, li, T, s));
     HIPCHK(c, aigv_launch_kv_store(c->l_qkv, c->qkv_out, c->l_seq, c->l_pos, c->kc + li * kv_layer, c->vc + li * kv_layer, T, nkv, g, D,
                                    k.kv_capacity, s));
+    if (probing) TRY(probe_layer(c, probe, li, true, s));   // K from the cache: the cached keys and, behind them, the rows just appended
     {
       AttnArgs a = llm_attn_args(c, B);   // K / V: the cache, the new rows behind each sequence's cached keys
       a.k = c->kc + li * kv_layer; a.v = c->vc + li * kv_layer;

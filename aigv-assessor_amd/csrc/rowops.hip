@@ -252,9 +252,10 @@ __global__ __launch_bounds__(256) void rope_kernel(bf16_t* __restrict__ qkv, int
     u16x8 olo, ohi;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      const float x1 = bf2f(lo[e]), x2 = bf2f(hi[e]), cc = bf2f(co[e]), ss = bf2f(si[e]);
-      olo[e] = f2bf(rbf(x1 * cc) + rbf(-x2 * ss));
-      ohi[e] = f2bf(rbf(x2 * cc) + rbf(x1 * ss));
+      bf16_t a, b;
+      rope_pair(lo[e], hi[e], co[e], si[e], a, b);   // (common.h: the arithmetic the attention probe shares)
+      olo[e] = a;
+      ohi[e] = b;
     }
     *(u16x8*)base = olo;
     *(u16x8*)(base + half) = ohi;

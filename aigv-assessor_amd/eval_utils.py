@@ -126,6 +126,21 @@ def expected_level(cand_logprob, weights=(1, 2, 3, 4, 5)):
     return (torch.softmax(cand_logprob, -1) * w).sum(-1)
 
 
+def frame_saliency(att, layers=None):
+    """Which frames the score row reads: ``att`` is ``forward(return_score_attention=True)``'s ``score_attention`` [B, L, n_heads, F + 4]
+    (bins: F frames, then motion | first token | text before | text after: ``prompts.attention_segments``); returns [B, F] - the mass on
+    the frame bins, averaged over the heads and over ``layers`` (an index list; None: all layers), renormalised over the frames so that a
+    clip's row sums to 1 (NaN where the row puts no mass on any frame)."""
+    import torch
+    from .prompts import N_TEXT_SEGMENTS
+    if att.dim() != 4 or att.shape[-1] <= N_TEXT_SEGMENTS:
+        raise ValueError(f"frame_saliency: expected [B, L, n_heads, F + {N_TEXT_SEGMENTS}] with F >= 1, got {tuple(att.shape)}")
+    if layers is not None:
+        att = att.index_select(1, torch.as_tensor(list(layers), dtype=torch.long, device=att.device))
+    mass = att[..., :att.shape[-1] - N_TEXT_SEGMENTS].double().mean(dim=(1, 2))
+    return (mass / mass.sum(-1, keepdim=True)).to(att.dtype)
+
+
 def batched(items, model, k: int = 4, frames=None, ahead: bool = True, pad_id: int = 2, return_logprobs: bool = False, candidate_ids=None,
             top_logprobs=None):
     """The reference's eval loop at batch ``k`` instead of batch 1: yields ``(item, output)`` for EVERY item of ``items`` (the loop's

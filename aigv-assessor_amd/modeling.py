@@ -672,7 +672,7 @@ class InternVLChatModel(nn.Module):
             keep.append(pinned)
         return pinned.to(self.device, non_blocking=True)
 
-    def _prefill(self, ids_packed, slot, cu, vis, n_vis, motion, score_rows, logit_rows, keep_kv=False, kv_cap=0):
+    def _prefill(self, ids_packed, slot, cu, vis, n_vis, motion, score_rows, logit_rows, keep_kv=False, kv_cap=0, probe=None):
         b = len(cu) - 1
         T = cu[-1]
         lib, ctx = self._native(n_tokens=T, n_clips=b, out_rows=len(logit_rows), kv_cap=kv_cap)
@@ -686,10 +686,68 @@ class InternVLChatModel(nn.Module):
         cu_a = native.i32_array(cu)
         sr_a = native.i32_array(score_rows) if score_rows is not None else None
         lr_a = native.i32_array(logit_rows) if len(logit_rows) else None
+        att = self._arm_score_attention(probe) if probe is not None else None   # (armed for exactly the pass below)
         native.check(lib.aigv_llm_prefill(
             ctx, ids_d.data_ptr(), slot_d.data_ptr(), cu_a, b, native.ptr(vis), n_vis, native.ptr(motion),
             sr_a, native.ptr(score), lr_a, len(logit_rows), amax.data_ptr(), int(keep_kv), native.stream_ptr()), ctx)
+        if probe is not None:
+            return score, amax[: len(logit_rows)], att
         return score, amax[: len(logit_rows)]
+
+    # ---- score-row attention by segment (return_score_attention) -------------------------------------------------------------------------
+    MAX_ATTN_SEGMENTS = 64   # = AIGV_MAX_ATTN_SEGMENTS
+    MAX_PROBE_ROWS = 64      # = AIGV_MAX_PROBE_ROWS
+
+    def _probe_rows(self, plan) -> List[int]:
+        """The packed row of every clip whose attention is reported: the score row (stage 2), else the row that predicts the clip's first
+        answer token."""
+        if plan["score_rows"] is not None:
+            return [int(r) for r in plan["score_rows"]]
+        rows = []
+        answer = (plan["labels_h"][:, 1:] != -100) & (plan["row_of"][:, :-1] >= 0)
+        for b in range(answer.shape[0]):
+            at = answer[b].nonzero().flatten()
+            if not at.numel():
+                raise ValueError(f"return_score_attention: clip {b} has no answer token (a stage-1 model reports the row that predicts the first one: pass labels)")
+            rows.append(int(plan["row_of"][b, int(at[0])]))
+        return rows
+
+    def _default_segments(self, plan):
+        """(``prompts.attention_segments`` of the plan's packed tokens, host int32 [T]; the number of bins F + 4)."""
+        from . import prompts
+        slot, cu, ntok = plan["slot"], plan["cu"], self.num_image_token
+        frames = [int(((slot[cu[b]:cu[b + 1]] >= 0) & (slot[cu[b]:cu[b + 1]] < plan["n_vis"])).sum()) // ntok for b in range(len(cu) - 1)]
+        return prompts.attention_segments(slot, cu, frames, ntok), max(frames) + prompts.N_TEXT_SEGMENTS
+
+    def _score_attention_probe(self, plan, input_ids, attention_segments):
+        """What ``_prefill`` arms the pass with: (probe rows, device int32 segment id per packed token, S).  ``attention_segments``: None -
+        ``prompts.attention_segments`` - or the user's own table, an integer tensor laid out like ``input_ids`` [B, N] (on any device; padded
+        positions are ignored, ids outside [0, S) drop their key from the bins), S = its largest id + 1."""
+        rows = self._probe_rows(plan)
+        if len(rows) > self.MAX_PROBE_ROWS:
+            raise ValueError(f"return_score_attention: at most {self.MAX_PROBE_ROWS} clips per pass, got {len(rows)}")
+        if attention_segments is None:
+            seg, S = self._default_segments(plan)
+            seg_d = self._h2d(seg)
+        else:
+            t = attention_segments
+            if not torch.is_tensor(t) or t.is_floating_point() or t.dtype == torch.bool or tuple(t.shape) != tuple(input_ids.shape):
+                raise ValueError(f"attention_segments: expected an integer tensor shaped like input_ids {tuple(input_ids.shape)}")
+            S = getattr(self, "_probe_n_segments", None) or int(t.max()) + 1     # (a replayed graph carries S in its key: no sync in there)
+            kept = (plan["row_of"] >= 0).flatten().nonzero().flatten()          # [b, p] of every packed row, in packed order (host)
+            seg_d = t.to(self.device).flatten().index_select(0, self._h2d(kept)).to(torch.int32).contiguous()
+        if not 1 <= S <= self.MAX_ATTN_SEGMENTS:
+            raise ValueError(f"return_score_attention: {S} segments, outside 1..{self.MAX_ATTN_SEGMENTS}")
+        return rows, seg_d, None, 0, S
+
+    def _arm_score_attention(self, probe) -> torch.Tensor:
+        """Arm the context's NEXT prefill / continuation pass (aigv_score_attention_arm); returns the fp32 tensor [rows, L, n_heads, S] it fills."""
+        rows, seg_new, seg_cached, ld_cached, S = probe
+        llm = self.config.llm_config
+        att = torch.empty((len(rows), llm.num_hidden_layers, llm.num_attention_heads, S), dtype=torch.float32, device=self.device)
+        native.check(native.load().aigv_score_attention_arm(self._ctx, native.i32_array(rows), len(rows), seg_new.data_ptr(), native.ptr(seg_cached),
+                                                            int(ld_cached), int(S), att.data_ptr()), self._ctx)
+        return att
 
     def forward(self, mos: Optional[torch.Tensor] = None, pixel_values: Optional[torch.Tensor] = None,
                 input_ids: Optional[torch.Tensor] = None, attention_mask: Optional[torch.Tensor] = None,
@@ -697,7 +755,7 @@ class InternVLChatModel(nn.Module):
                 labels: Optional[torch.Tensor] = None, use_cache=None, output_attentions=None,
                 output_hidden_states=None, return_dict=None, motion_feature: Optional[torch.Tensor] = None,
                 visual_tokens: Optional[torch.Tensor] = None, full_logits: bool = False, return_logprobs: bool = False,
-                candidate_ids=None, top_logprobs: Optional[int] = None):
+                candidate_ids=None, top_logprobs: Optional[int] = None, return_score_attention: bool = False, attention_segments=None):
         """Stage-2 eval pass (modeling_internvl_chat.py:306-488) or, with ``stage=1``, the stage-1 pass
         (internvl_chat_eval1/modeling_internvl_chat.py:250-366).  ``visual_tokens`` optionally supplies
         already all-gathered pre-projector tokens (frame-DP) instead of ``pixel_values``.
@@ -722,7 +780,18 @@ class InternVLChatModel(nn.Module):
         ``torch.sort(logits.float(), descending=True, stable=True)``; column 0 is ``logit`` - and ``top_logprob`` (fp32, same shape, NaN
         rows there): their full-vocabulary log-probabilities, bit for bit what ``candidate_ids=top_ids[row]`` gives.  Needs ``labels``
         under ``return_logprobs``' label rules.  The three options combine freely and none changes another's bits; under graph replay k
-        is part of the graph's key (it is an output shape)."""
+        is part of the graph's key (it is an output shape).
+
+        ``return_score_attention=True`` adds ``score_attention`` (fp32 [B, L, n_heads, S]): where the clip's score row - ``hidden[:, -4]``;
+        in a stage-1 model, which has no score head, the row that predicts the first answer token - looks in every layer and head, as the
+        softmax mass it puts on each of S key segments.  Default segments (``prompts.attention_segments``, S = F + 4): frame 0 .. F - 1 |
+        motion token | first token (the sink) | text up to the last visual token | text after it; a row's S values sum to 1.  Or pass
+        ``attention_segments=`` (integer tensor like ``input_ids``; S = largest id + 1 <= 64; an id outside [0, S) drops its key from the
+        bins but not from the softmax).  What the reference reads from ``output_attentions=True`` on its eager attention, here from a
+        small stand-alone kernel per layer that recomputes that one row's softmax in fp32 from the layer's Q and K (the flash kernels
+        never form a probability matrix): no other output of the pass changes a bit, and the option combines freely with the
+        log-probability options.  ``eval_utils.frame_saliency`` folds it to [B, F].  Under graph replay the flag (and S) is part of the
+        graph's key, a user table is a graph input, the tensor a graph output."""
         if position_ids is not None or past_key_values is not None:
             raise NotImplementedError("the eval pass takes default positions and no cache, like the reference drivers")
         if self.img_context_token_id is None:
@@ -730,7 +799,7 @@ class InternVLChatModel(nn.Module):
         pixel_values, visual_tokens, motion_feature = self._take_ahead(pixel_values, visual_tokens, motion_feature)
         if self._graph_replay_enabled and self._capture_keep is None:
             out = self._forward_through_graph(mos, pixel_values, input_ids, attention_mask, image_flags, labels, motion_feature, visual_tokens, full_logits,
-                                              return_logprobs, candidate_ids, top_logprobs)
+                                              return_logprobs, candidate_ids, top_logprobs, return_score_attention, attention_segments)
             if out is not None:
                 return out
         B, N = input_ids.shape
@@ -746,11 +815,17 @@ class InternVLChatModel(nn.Module):
         # ---- device work: ViT -> projector -> motion projector -> LLM pass + heads ----
         self._native(n_frames=n_frames, n_tokens=plan["cu"][-1], n_clips=B, out_rows=len(plan["logit_rows"]), seq_len=N)   # size workspaces once
         vit_embeds, motion = self._visual_inputs(pixel_values, visual_tokens, motion_feature, plan)
-        score, amax = self._prefill(plan["ids_packed"], plan["slot"], plan["cu"], vit_embeds, plan["n_vis"], motion,
-                                    plan["score_rows"], plan["logit_rows"])
+        att = None
+        if return_score_attention:
+            probe = self._score_attention_probe(plan, input_ids, attention_segments)
+            score, amax, att = self._prefill(plan["ids_packed"], plan["slot"], plan["cu"], vit_embeds, plan["n_vis"], motion,
+                                             plan["score_rows"], plan["logit_rows"], probe=probe)
+        else:
+            score, amax = self._prefill(plan["ids_packed"], plan["slot"], plan["cu"], vit_embeds, plan["n_vis"], motion,
+                                        plan["score_rows"], plan["logit_rows"])
         lp, clp = self._row_logprobs(B if score is not None else 0, len(plan["logit_rows"]), lp_labels if return_logprobs else None, cand)
         top = self._row_topk(B if score is not None else 0, len(plan["logit_rows"]), topk) if topk else None
-        return self._outputs(plan, B, N, score, amax, mos, lp, clp, top)
+        return self._outputs(plan, B, N, score, amax, mos, lp, clp, top, att)
 
     # ---- HIP-graph replay of whole scoring passes (opt-in: enable_graph_replay) ---------------------------------------------------------
     _graph_replay_enabled = False
@@ -885,7 +960,7 @@ class InternVLChatModel(nn.Module):
         return cl(outputs)
 
     def _forward_through_graph(self, mos, pixel_values, input_ids, attention_mask, image_flags, labels, motion_feature, visual_tokens, full_logits,
-                               return_logprobs=False, candidate_ids=None, top_logprobs=None):
+                               return_logprobs=False, candidate_ids=None, top_logprobs=None, return_score_attention=False, attention_segments=None):
         """The replay path of ``forward``; returns None when the call does not qualify (the eager path then runs)."""
         src = visual_tokens if visual_tokens is not None else pixel_values
         if self._rope_seq_len(int(input_ids.shape[1])) != getattr(self, "_rope_ntk", 0):
@@ -907,15 +982,32 @@ class InternVLChatModel(nn.Module):
         topk = self._top_logprobs_k(top_logprobs, self.config.llm_config.vocab_size, labels)
         if topk:
             host_key += (("top_logprobs", topk),)   # (k is an output shape: another k is another graph)
+        seg, n_seg = None, 0
+        if return_score_attention:
+            # (the flag is part of the key; the default table follows from the ids, which are; a user table is graph INPUT, its bin count - an output shape - key)
+            if attention_segments is not None:
+                if not torch.is_tensor(attention_segments) or attention_segments.is_floating_point() or tuple(attention_segments.shape) != tuple(input_ids.shape):
+                    raise ValueError(f"attention_segments: expected an integer tensor shaped like input_ids {tuple(input_ids.shape)}")
+                n_seg = int(attention_segments.max()) + 1
+                seg = self._h2d(attention_segments.contiguous())
+            host_key += (("score_attention", n_seg),)
         self._join_side_stream()             # (a motion feature started by motion_feature_async: joined BEFORE the graph copies it in)
         self._prepare_motion_branch(pixel_values if (motion_feature is None and visual_tokens is None) else None, int(input_ids.shape[0]))
 
-        def fn(src_static, mf_static, cand_static):
+        def fn(src_static, mf_static, cand_static, seg_static=None):
+            self._probe_n_segments = n_seg or None      # (S is in the key: the pass inside the capture does not read it back from the device)
+            try:
+                return run(src_static, mf_static, cand_static, seg_static)
+            finally:
+                self._probe_n_segments = None
+
+        def run(src_static, mf_static, cand_static, seg_static):
             return self.forward(mos=None, pixel_values=None if visual_tokens is not None else src_static, input_ids=input_ids, attention_mask=attention_mask,
                                 image_flags=image_flags, labels=labels, motion_feature=mf_static, full_logits=full_logits,
                                 visual_tokens=src_static if visual_tokens is not None else None, return_logprobs=return_logprobs,
-                                candidate_ids=cand_static, top_logprobs=top_logprobs)
-        return self._graph_call(host_key, [src, motion_feature, cand], fn)
+                                candidate_ids=cand_static, top_logprobs=top_logprobs, return_score_attention=return_score_attention,
+                                attention_segments=seg_static)
+        return self._graph_call(host_key, [src, motion_feature, cand] + ([seg] if seg is not None else []), fn)   # (a user table only: the other keys stay what they were)
 
     def dp_front(self, frames_local: torch.Tensor, frames_clips: Optional[torch.Tensor], n_clips: int):
         """The data-parallel scorer's front half on this rank (dist_utils.score_clips_dp): the SlowFast feature of its own clips (side
@@ -1055,7 +1147,7 @@ class InternVLChatModel(nn.Module):
             vit_embeds = vit_embeds[self._h2d(plan["keep"])]
         return vit_embeds.reshape(-1, H), self.motion_embed(motion_feature)
 
-    def _outputs(self, plan, B, N, score, amax, mos, lp=None, clp=None, top=None):
+    def _outputs(self, plan, B, N, score, amax, mos, lp=None, clp=None, top=None, att=None):
         dev = self.device
         up = self._h2d   # host -> device through pinned memory, never blocking the host (keeps the CPU ahead of the GPU)
         idx = up(plan["want"].reshape(-1).nonzero().flatten()) if len(plan["logit_rows"]) else None   # index list built on the host: no sync
@@ -1087,6 +1179,8 @@ class InternVLChatModel(nn.Module):
                 ids_k, lp_k = torch.where(answer, ids_k, torch.full_like(ids_k, -1)), torch.where(answer, lp_k, torch.full_like(lp_k, float("nan")))
             out["top_ids"] = scatter(ids_k, -1)
             out["top_logprob"] = scatter(lp_k, float("nan"))
+        if att is not None:                         # return_score_attention: [B, L, n_heads, S]
+            out["score_attention"] = att
         return out
 
     MAX_CANDIDATES = 64      # = AIGV_MAX_CANDIDATES
@@ -1185,7 +1279,8 @@ class InternVLChatModel(nn.Module):
 
     def forward_shared_prefix(self, prompts, pixel_values: Optional[torch.Tensor] = None, image_flags: Optional[torch.Tensor] = None,
                               motion_feature: Optional[torch.Tensor] = None, visual_tokens: Optional[torch.Tensor] = None, mos=None,
-                              return_logprobs: bool = False, candidate_ids=None, top_logprobs: Optional[int] = None):
+                              return_logprobs: bool = False, candidate_ids=None, top_logprobs: Optional[int] = None,
+                              return_score_attention: bool = False):
         """Score the same clips under several prompts that share their beginning - the reference's four quality
         perspectives ask four questions BEHIND the same system + frame + motion tokens (8f-3) and
         run four full passes (stage2_eval.py evaluates one jsonl per perspective).  Here the common prefix runs once
@@ -1196,7 +1291,9 @@ class InternVLChatModel(nn.Module):
         ``return_logprobs``: every prompt's dict carries ``logprob`` and ``ce_loss`` as ``forward`` defines them - with candidate answers
         as the prompts, their log-likelihoods behind one video prefix (README).  ``candidate_ids``: every prompt's dict carries
         ``cand_logprob`` as ``forward`` defines it (the same candidates for every prompt).  ``top_logprobs``: every prompt's dict carries
-        ``top_ids`` / ``top_logprob`` as ``forward`` defines them."""
+        ``top_ids`` / ``top_logprob`` as ``forward`` defines them.  ``return_score_attention``: every prompt's dict carries its own
+        ``score_attention`` [B, L, n_heads, F + 4] as ``forward`` defines it (default segments), read by the continuation pass over the cached
+        prefix keys and the prompt's own tokens; at most 64 (clip, prompt) pairs."""
         if self.img_context_token_id is None:
             raise AssertionError("img_context_token_id must be set by the caller (stage2_eval.py:810)")
         if not prompts:
@@ -1247,6 +1344,24 @@ class InternVLChatModel(nn.Module):
         ids_d = torch.cat(parts).to(torch.long).contiguous().pin_memory().to(dev, non_blocking=True)
         score = torch.empty(B * P, dtype=torch.float32, device=dev) if self.stage == 2 else None
         amax = torch.empty(max(len(lrows), 1), dtype=torch.long, device=dev)
+        att = None
+        if return_score_attention:
+            # rows: sequence p * B + b of the continuation batch; segments of its new tokens: the prompt's own table behind the prefix; of the
+            # cached keys: the clip's prefix table, tiled over the P prompts (row p * B + b, padded with -1 to the longest prefix)
+            if B * P > self.MAX_PROBE_ROWS:
+                raise ValueError(f"return_score_attention: at most {self.MAX_PROBE_ROWS} (clip, prompt) pairs per call, got {B * P}")
+            prows, seg_parts, S = [], [], 0
+            for p, pl in enumerate(plans):
+                seg_p, S = self._default_segments(pl)
+                for b, r in enumerate(self._probe_rows(pl)):
+                    prows.append(cu_s[p * B + b] + (r - pl["cu"][b] - pre[b]))
+                    seg_parts.append(seg_p[pl["cu"][b] + pre[b]:pl["cu"][b + 1]])
+            seg0, _ = self._default_segments(p0)
+            ld = max(pre)
+            seg_cached = torch.full((P * B, ld), -1, dtype=torch.int32)
+            for b in range(B):
+                seg_cached[b::B, :pre[b]] = seg0[p0["cu"][b]:p0["cu"][b] + pre[b]]
+            att = self._arm_score_attention((prows, self._h2d(torch.cat(seg_parts).contiguous()), self._h2d(seg_cached), ld, S))
         native.check(lib.aigv_llm_extend(ctx, ids_d.data_ptr(), native.i32_array(cu_s), B * P,
                                          native.i32_array(srows) if score is not None else None, native.ptr(score),
                                          native.i32_array(lrows) if lrows else None, len(lrows), amax.data_ptr(), 0,
@@ -1258,7 +1373,8 @@ class InternVLChatModel(nn.Module):
             outs.append(self._outputs(pl, B, ids.shape[1], score[p * B:(p + 1) * B] if score is not None else None,
                                       amax[off:off + n_l[p]], mos, lp[off:off + n_l[p]] if lp is not None else None,
                                       clp[off:off + n_l[p]] if clp is not None else None,
-                                      (top[0][off:off + n_l[p]], top[1][off:off + n_l[p]]) if top is not None else None))
+                                      (top[0][off:off + n_l[p]], top[1][off:off + n_l[p]]) if top is not None else None,
+                                      att[p * B:(p + 1) * B] if att is not None else None))
             off += n_l[p]
         return outs
 

@@ -116,3 +116,53 @@ def level_token_ids(tokenizer, words: Sequence[str] = ("bad", "poor", "fair", "g
                 raise ValueError(f"level_token_ids: {words[j]!r} and {words[i]!r} share their first distinguishing token {a}; score the whole "
                                  "candidate answers instead (forward_shared_prefix)")
     return ids
+
+
+N_TEXT_SEGMENTS = 4             # bins behind the F frame bins: motion token | first token (the sink) | text up to the last visual token | text after it
+
+
+def attention_segments(slot, cu: Sequence[int], n_frames, tokens_per_frame: int) -> torch.Tensor:
+    """The key-segment table of ``forward(return_score_attention=True)``: one int32 id per PACKED token (host, no GPU), so that the
+    score row's attention mass can be read per frame.  ``slot`` is the pass's slot map (int per packed token: -1 a text token, 0 ..
+    n_vis - 1 a visual token in frame order, n_vis + b the motion token of clip b), ``cu`` the clips' row offsets [B + 1].  With F frame
+    bins the ids are
+
+    * ``f``      the visual tokens of the clip's frame f (its visual tokens in order, ``tokens_per_frame`` each),
+    * ``F``      the motion token,
+    * ``F + 1``  the first token of the clip - the BOS sink gets a bin of its own, because it usually takes most of the mass,
+    * ``F + 2``  every other text token in front of the clip's last visual token (system prompt, "Frame i:" separators),
+    * ``F + 3``  the text behind it (question and answer).
+
+    ``n_frames``: an int F - every clip may hold up to F frames - or one count per clip (ragged clips in one packed batch: F is the
+    largest, a shorter clip leaves its later frame bins empty).  Users may build another table and pass it as ``attention_segments=``."""
+    slot = torch.as_tensor(slot).to(torch.long).flatten()
+    cu = [int(v) for v in cu]
+    B = len(cu) - 1
+    if B < 1 or cu[0] != 0 or cu[-1] != slot.numel() or any(cu[b + 1] <= cu[b] for b in range(B)):
+        raise ValueError(f"attention_segments: cu {cu} does not divide the {slot.numel()} packed tokens into non-empty clips")
+    if tokens_per_frame < 1:
+        raise ValueError("attention_segments: tokens_per_frame must be positive")
+    per_clip = [int(n_frames)] * B if isinstance(n_frames, int) else [int(v) for v in n_frames]
+    if len(per_clip) != B or min(per_clip) < 0:
+        raise ValueError(f"attention_segments: n_frames {n_frames!r} is neither an int nor one count per clip ({B} clips)")
+    exact = not isinstance(n_frames, int)
+    F = max(per_clip)
+    n_vis = int((slot >= 0).sum()) - B                  # every clip carries exactly one motion token: the B largest slots
+    if n_vis < 0 or sorted(slot[slot >= 0].tolist()) != list(range(n_vis + B)):
+        raise ValueError("attention_segments: the slots must be 0 .. n_vis - 1 (visual tokens) and n_vis + b (the motion token of clip b), each once")
+    is_motion = slot >= n_vis
+    seg = torch.empty(slot.numel(), dtype=torch.int32)
+    for b in range(B):
+        lo, hi = cu[b], cu[b + 1]
+        vis = ((slot[lo:hi] >= 0) & ~is_motion[lo:hi])
+        n_v = int(vis.sum())
+        if n_v % tokens_per_frame or n_v > per_clip[b] * tokens_per_frame or (exact and n_v != per_clip[b] * tokens_per_frame):
+            raise ValueError(f"attention_segments: clip {b} holds {n_v} visual tokens, expected {'' if exact else 'up to '}{per_clip[b]} frames of {tokens_per_frame}")
+        last_vis = int(vis.nonzero().max()) if n_v else -1
+        part = torch.full((hi - lo,), F + 3, dtype=torch.int32)
+        part[:max(last_vis, 0)] = F + 2
+        part[0] = F + 1
+        part[vis] = (torch.arange(n_v) // tokens_per_frame).to(torch.int32)
+        part[is_motion[lo:hi]] = F
+        seg[lo:hi] = part
+    return seg

@@ -42,7 +42,8 @@ extern "C" {
                                 (aigv_slowfast_plan_size / _plan_op / _run_ops / _buffer_read / _buffer_write and the host functions
                                 aigv_slowfast_slow_indices / _pool_weights / _conv_k_slices), then by the test entry points of the score head
                                 and the row kernels (aigv_op_score_head, aigv_op_rmsnorm_quant_fp8, aigv_op_rope_slots, aigv_op_embed,
-                                aigv_op_seqpos, aigv_op_gather_rows, aigv_op_scatter_rows, aigv_op_cls_rows, aigv_op_write_ints)
+                                aigv_op_seqpos, aigv_op_gather_rows, aigv_op_scatter_rows, aigv_op_cls_rows, aigv_op_write_ints), then by the
+                                score-row attention probe (aigv_score_attention_arm, aigv_op_attention_probe)
                                 - added symbols only: a library without them is refused at load
                                 time, "missing <name>" */
 
@@ -50,6 +51,10 @@ extern "C" {
 #define AIGV_MAX_CANDIDATES 64
 /* Largest k one top-k log-probability call takes. */
 #define AIGV_MAX_TOPK 16
+
+/* Score-row attention probe: most key segments (bins) and most probe rows one armed pass / one aigv_op_attention_probe call takes. */
+#define AIGV_MAX_ATTN_SEGMENTS 64
+#define AIGV_MAX_PROBE_ROWS 64
 
 /* Largest aigv_config.kv_capacity a context accepts (tokens per clip): the decode attention's merge pass holds 16 bytes of LDS per
  * 128-key chunk of the capacity (32 KB at this bound). */
@@ -152,6 +157,27 @@ int aigv_llm_prefill(aigv_ctx* ctx, const int64_t* ids, const int32_t* slot, con
  * Replaces re-running modeling_internvl_chat.py:306-488 from the first token for every question. */
 int aigv_llm_extend(aigv_ctx* ctx, const int64_t* ids, const int32_t* cu, int n_clips, const int32_t* score_rows, float* score,
                     const int32_t* logit_rows, int n_logit_rows, int64_t* argmax, int commit, void* stream);
+
+/* Score-row attention by segment: WHERE a few rows of the next scoring pass look.  Arms exactly the next aigv_llm_prefill or
+ * aigv_llm_extend on this context: that pass launches one small stand-alone kernel per decoder layer, right behind the layer's wqkv + RoPE
+ * (and, in aigv_llm_extend, behind its KV-cache append), which recomputes the causal softmax of the n_rows probe rows per query head from
+ * the layer's Q and K and folds it into n_segments bins:
+ *   out_dev[row][layer][head][seg] = sum over the visible keys j with segment id seg of softmax_j(q . k_j / sqrt(head_dim))      (fp32, DEVICE)
+ * for ALL layers - a row-trimmed last layer included (the probe reads Q and K, not the attention output).  The pass then disarms, also
+ * when it fails.  rows_host: HOST int32[n_rows] packed row indices of that pass, 1 <= n_rows <= AIGV_MAX_PROBE_ROWS.  Segment ids, DEVICE
+ * int32, read when the pass runs: seg_new_dev[packed row of the pass] and - aigv_llm_extend only, where it is required; NULL for a prefill -
+ * seg_cached_dev[sequence * ld_cached + position] for the keys cached before the pass (ld_cached >= the longest cached length).  An id
+ * outside [0, n_segments) drops its key from the bins but not from the softmax total, so a row's bins sum to 1 minus the dropped mass;
+ * 1 <= n_segments <= AIGV_MAX_ATTN_SEGMENTS.
+ * Numerics: the probe is a report, not part of the pass.  Its scores are ALWAYS fp32, whatever aigv_set_attention_numerics says; q is rotated
+ * with the RoPE kernel's own arithmetic (the bf16 bits aigv_op_rope would store); every bin and the total are summed in an order fixed by the
+ * key index alone (no atomics), and out = bin / total is one fp32 division - a row's bits do not depend on the other rows, the batch mates or
+ * the launch grid.  The existing kernels are not touched: armed or not, every other output of the pass keeps its bits.  Nothing is allocated,
+ * so an armed pass still captures into a HIP graph (rows_host is baked into the capture; the tables and out_dev are read / written through
+ * their addresses).  Limits and rows are checked when the pass runs: AIGV_ERR_ARG from the pass, with a message.
+ * Out of scope: aigv_decode_step ignores the feature (an armed context stays armed across decode steps). */
+int aigv_score_attention_arm(aigv_ctx* ctx, const int32_t* rows_host, int n_rows, const int32_t* seg_new_dev, const int32_t* seg_cached_dev,
+                             int ld_cached, int n_segments, float* out_dev);
 
 /* Replicate the n kept sequences `copies` times (cache slots [0, n) -> [n, 2n), ...; needs n * copies <= max_seqs): the copies can
  * then take DIFFERENT continuations in one aigv_llm_extend call over n * copies sequences (sequence c * n + b continues clip b),
@@ -360,6 +386,17 @@ int aigv_op_attention_ex(const void* q, int ldq, const void* k, int ldk, const v
                          int max_len, int n_heads, int n_kv_heads, int q_group_stride, int kv_head_stride, int64_t kv_seq_stride,
                          const int32_t* kv_off, int head_dim, int causal, float post_div, float q_prescale, const int32_t* pos, const void* cos,
                          const void* sin, int pos_is_row, int q_tail, void* stream);
+/* The score-row attention probe on plain pointers (one layer; tests use it without a model): out [n_rows, n_heads, n_segments] fp32 as
+ * aigv_score_attention_arm defines it.  q: UNROTATED fused rows (query head h at column (h / g) * q_group_stride + (h % g) * head_dim), rotated
+ * by the kernel at the row's position from cos / sin [max_pos, head_dim / 2]; k: already rotated, in aigv_op_attention_ex's two forms -
+ * packed (kv_seq_stride = 0, kv_off_host = NULL: key j of a sequence is its row j) or the KV cache (kv_seq_stride != 0: ldk = head_dim,
+ * kv_head_stride = cap * head_dim; the row at local index r of sequence s sees cache positions [0, kv_off_host[s] + r]).  cu_host / kv_off_host /
+ * rows_host are HOST arrays, so that every index the kernel forms is checked before anything is launched (AIGV_ERR_ARG with a message); seg_new
+ * DEVICE int32[cu_host[n_seq]], seg_cached DEVICE int32[n_seq * ld_cached] or NULL.  head_dim 64 or 128. */
+int aigv_op_attention_probe(const void* q, int ldq, const void* k, int ldk, const int32_t* cu_host, int n_seq, int n_heads, int n_kv_heads,
+                            int q_group_stride, int kv_head_stride, int64_t kv_seq_stride, const int32_t* kv_off_host, int head_dim, const void* cos,
+                            const void* sin, int max_pos, const int32_t* rows_host, int n_rows, const int32_t* seg_new, const int32_t* seg_cached,
+                            int ld_cached, int n_segments, float* out, void* stream);
 /* The KV-cache append of the prefill and continuation passes: for token t, the K and V slots of every group of the fused row
  * qkv[t * ld ..] (groups of [g query heads | K | V]) are copied to kc / vc [seq][n_kv][cap][head_dim] at [seq[t]][kvh][pos[t]]; nothing else
  * is written.  seq / pos: DEVICE int32[tokens] (the caller's promise: seq[t] inside the cache, pos[t] < cap).  Checked on the host. */
