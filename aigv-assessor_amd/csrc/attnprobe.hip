@@ -12,6 +12,11 @@
 //   4. a second sweep adds e_j = exp(s_j - m) to the thread's own LDS column of bin seg[j] and of the total; an id outside [0, S) drops
 //      the key from the bins, not from the total;
 //   5. columns are summed lanes first (xor butterfly), then waves in wave order; out[seg] = bin[seg] / total, ONE fp32 division.
+// The DENSE form (a template argument: the plain instantiation is the code above and nothing else) also reports every key on its own:
+//   4'. in the second sweep thread t stores e_j of its keys t, t + 256, ... to tok[j] (coalesced 4-byte stores);
+//   5'. once the total is known every thread reads back the elements IT wrote - no fence: a thread sees its own stores - and stores
+//       tok[j] = e_j / total, the bins' total and the bins' division, so a bin of one key holds that key's dense bits; the columns behind
+//       the row, pos < j < ld_tok, are set to +0.0.  All ld_tok columns are written, nothing outside them.
 // The summation order is a function of the key index alone (no float atomics, nothing depends on the row count, the batch mates or the
 // grid), so a row's bits are its own - and integer-valued e_j (Q = 0: every e_j is 1) give exact counts.
 #include "common.h"
@@ -32,7 +37,10 @@ __device__ __forceinline__ float probe_score(const float* __restrict__ qs, const
   return acc / post_div;
 }
 
-template <int D>
+// the four wave partials of one column of `red`, added in wave order: the last step of every bin's sum and of the total's
+__device__ __forceinline__ float waves_in_order(const float* r) { return ((r[0] + r[1]) + r[2]) + r[3]; }
+
+template <int D, bool DENSE>
 __global__ __launch_bounds__(LSE_THREADS) void attn_probe_kernel(const ProbeArgs p) {
   extern __shared__ float bins[];                      // [n_seg + 1][256]: column = thread, row n_seg = the total
   __shared__ float qs[D];
@@ -61,11 +69,14 @@ __global__ __launch_bounds__(LSE_THREADS) void attn_probe_kernel(const ProbeArgs
   float row_max = 0.0f;
   lse_of_block<false>(m, sum, &row_max);
 
+  float* tok = nullptr;                                // DENSE: the ld_tok columns of this (row, head)
+  if constexpr (DENSE) tok = p.tok + (size_t)blockIdx.x * p.tok_row_stride + (size_t)h * p.ld_tok;
   for (int j = tid; j < n_keys; j += LSE_THREADS) {
     const float e = expf(probe_score<D>(qs, kb + (size_t)j * p.ldk, p.post_div) - row_max);
     const int sg = j < pr.off ? p.seg_cached[(size_t)pr.seq * p.ld_cached + j] : p.seg_new[pr.row0 + (j - pr.off)];
     bins[S * LSE_THREADS + tid] += e;
     if (sg >= 0 && sg < S) bins[sg * LSE_THREADS + tid] += e;
+    if constexpr (DENSE) tok[j] = e;
   }
   // every thread has written its own column only: no barrier in front of the butterflies
   for (int s = 0; s <= S; ++s) {
@@ -74,21 +85,25 @@ __global__ __launch_bounds__(LSE_THREADS) void attn_probe_kernel(const ProbeArgs
   }
   __syncthreads();
   if (tid < S) {
-    const float* rt = red + S * (LSE_THREADS / AIGV_WAVE);
-    const float* rb = red + tid * (LSE_THREADS / AIGV_WAVE);
-    const float total = ((rt[0] + rt[1]) + rt[2]) + rt[3];
-    const float bin = ((rb[0] + rb[1]) + rb[2]) + rb[3];
+    const float total = waves_in_order(red + S * (LSE_THREADS / AIGV_WAVE));
+    const float bin = waves_in_order(red + tid * (LSE_THREADS / AIGV_WAVE));
     p.out[(size_t)blockIdx.x * p.out_row_stride + (size_t)h * S + tid] = bin / total;
+  }
+  if constexpr (DENSE) {
+    const float total = waves_in_order(red + S * (LSE_THREADS / AIGV_WAVE));   // every thread: the bins' total, from the bins' statement of it
+    int j = tid;
+    for (; j < n_keys; j += LSE_THREADS) tok[j] = tok[j] / total;   // the thread's own stores of the second sweep
+    for (; j < p.ld_tok; j += LSE_THREADS) tok[j] = 0.0f;           // (the stride goes on behind the row: the 256 threads cover every column up to ld_tok)
   }
 }
 
-template <int D>
+template <int D, bool DENSE>
 hipError_t launch_probe(const ProbeArgs& a, hipStream_t s) {
   static LdsAttrOnce lds_attr;
   constexpr int max_lds = (AIGV_MAX_ATTN_SEGMENTS + 1) * LSE_THREADS * (int)sizeof(float);
-  if (hipError_t e = lds_attr.ensure((const void*)attn_probe_kernel<D>, max_lds); e != hipSuccess) return e;
+  if (hipError_t e = lds_attr.ensure((const void*)attn_probe_kernel<D, DENSE>, max_lds); e != hipSuccess) return e;
   const int lds = (a.n_seg + 1) * LSE_THREADS * (int)sizeof(float);
-  hipLaunchKernelGGL((attn_probe_kernel<D>), dim3(a.n_rows, a.n_heads), dim3(LSE_THREADS), lds, s, a);
+  hipLaunchKernelGGL((attn_probe_kernel<D, DENSE>), dim3(a.n_rows, a.n_heads), dim3(LSE_THREADS), lds, s, a);
   return hipGetLastError();
 }
 
@@ -106,6 +121,13 @@ const char* aigv_probe_check(const ProbeArgs& a, int head_dim, int total_rows, i
   if (a.ldk % 8 || a.kv_head_stride % 8 || a.kv_seq_stride % 8 || ((uintptr_t)a.k & 15)) return "attention probe: K must be 16-byte aligned with strides that are multiples of 8";
   if (!(a.post_div > 0.0f)) return "attention probe: post_div must be positive";
   if (a.out_row_stride < (size_t)a.n_heads * a.n_seg) return "attention probe: out row stride below n_heads * n_segments";
+  // dense form (one value per key): asked for by either argument, so that a half-given pair is refused and not read as the plain form
+  const bool dense = a.tok || a.ld_tok != 0;
+  if (dense) {
+    if (a.ld_tok < 0 || a.ld_tok > AIGV_MAX_KV_CAPACITY) return "attention probe: ld_tok is outside 0..AIGV_MAX_KV_CAPACITY (262144)";
+    if (!a.tok) return "attention probe: null tok_out with ld_tok > 0";
+    if (a.tok_row_stride < (size_t)a.n_heads * a.ld_tok) return "attention probe: tok row stride below n_heads * ld_tok";
+  }
   int cap = 0;
   if (a.kv_seq_stride) {   // cache layout [seq][kv head][cap][D]
     if (a.ldk < head_dim || a.kv_head_stride < a.ldk) return "attention probe: cache strides too small";
@@ -121,12 +143,13 @@ const char* aigv_probe_check(const ProbeArgs& a, int head_dim, int total_rows, i
     const int pos = r.off + (r.row - r.row0);
     if (pos >= max_pos) return "attention probe: a probe row's position lies outside the RoPE table";
     if (a.kv_seq_stride && pos >= cap) return "attention probe: a probe row's position lies outside the KV cache";
+    if (dense && pos >= a.ld_tok) return "attention probe: ld_tok is below a probe row's key count (position + 1)";
   }
   return nullptr;
 }
 
 hipError_t aigv_launch_attention_probe(const ProbeArgs& a, int head_dim, hipStream_t s) {
-  if (head_dim == 128) return launch_probe<128>(a, s);
-  if (head_dim == 64) return launch_probe<64>(a, s);
+  if (head_dim == 128) return a.tok ? launch_probe<128, true>(a, s) : launch_probe<128, false>(a, s);
+  if (head_dim == 64) return a.tok ? launch_probe<64, true>(a, s) : launch_probe<64, false>(a, s);
   return hipErrorInvalidValue;
 }

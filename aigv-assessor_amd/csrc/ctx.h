@@ -123,6 +123,8 @@ struct aigv_ctx {
     int32_t rows[AIGV_MAX_PROBE_ROWS];
     const int32_t *seg_new = nullptr, *seg_cached = nullptr;
     float* out = nullptr;
+    float* tok = nullptr;   // aigv_score_attention_arm_tokens: the dense rows [n_rows][layers][n_heads][ld_tok], else nullptr / 0
+    int ld_tok = 0;
   } probe;
   // profiling
   bool prof = false;

@@ -128,11 +128,16 @@ hipError_t aigv_launch_attention_decode(const bf16_t* q, int ldq, int q_group_st
 // (kv_seq_stride != 0: [seq][kv head][cap][D], ldk = D, kv_head_stride = cap * D; keys [0, off) were cached before the pass, the pass's own
 // rows follow).  Scores are fp32 whatever the pass's attention numerics.  seg ids: seg_new[packed row] for the pass's rows,
 // seg_cached[seq * ld_cached + j] for cached positions j < off; an id outside [0, n_seg) drops the key from the bins, not from the total.
+// Dense form (tok != nullptr, from the same launch): tok[row][head][j] = softmax_j for the key positions j = 0 .. pos of the row's sequence
+// (cached keys first), +0.0 for pos < j < ld_tok - the bins' scores, maximum, total and division, so a one-key bin equals its key's value.
 #ifndef AIGV_MAX_ATTN_SEGMENTS
 #define AIGV_MAX_ATTN_SEGMENTS 64   // = include/aigv_amd.h
 #endif
 #ifndef AIGV_MAX_PROBE_ROWS
 #define AIGV_MAX_PROBE_ROWS 64      // = include/aigv_amd.h
+#endif
+#ifndef AIGV_MAX_KV_CAPACITY
+#define AIGV_MAX_KV_CAPACITY 262144 // = include/aigv_amd.h: the most columns a dense row takes
 #endif
 struct ProbeRow { int32_t row, row0, seq, off; };   // packed row | first packed row of its sequence | sequence | keys cached in front of the pass
 struct ProbeRowTab { ProbeRow r[AIGV_MAX_PROBE_ROWS]; };   // by value: a kernel argument (no copy, no allocation - the pass still captures)
@@ -149,6 +154,7 @@ struct ProbeArgs {
   float* out; size_t out_row_stride;     // out[row * out_row_stride + head * n_seg + seg]
   int n_rows;
   ProbeRowTab tab;
+  float* tok; int ld_tok; size_t tok_row_stride;   // dense form, or nullptr / 0: tok[row * tok_row_stride + head * ld_tok + j]
 };
 // nullptr if every index the kernel forms stays inside its operand: total_rows = rows of the pass (q, seg_new), max_pos = rows of the RoPE tables
 const char* aigv_probe_check(const ProbeArgs& a, int head_dim, int total_rows, int max_pos);

@@ -1,5 +1,6 @@
-// The score-row attention probe of the C ABI (include/aigv_amd.h): aigv_score_attention_arm, what an armed aigv_llm_prefill /
-// aigv_llm_extend launches per layer (probe_plan / probe_layer, called from passes.hip) and the context-free aigv_op_attention_probe.
+// The score-row attention probe of the C ABI (include/aigv_amd.h): aigv_score_attention_arm / _arm_tokens, what an armed aigv_llm_prefill /
+// aigv_llm_extend launches per layer (probe_plan / probe_layer, called from passes.hip) and the context-free aigv_op_attention_probe /
+// _probe_tokens.
 // Host-side C++ only; the kernel is attnprobe.hip.
 #include <cmath>
 
@@ -41,7 +42,16 @@ int probe_plan(aigv_ctx* c, const char* op, const int32_t* cu, int B, const int3
   a.seg_new = pb.seg_new; a.seg_cached = off_host ? pb.seg_cached : nullptr; a.ld_cached = off_host ? pb.ld_cached : 0;
   a.n_seg = pb.n_seg;
   a.out = pb.out; a.out_row_stride = (size_t)k.llm_layers * k.llm_heads * pb.n_seg;
+  a.tok = pb.tok; a.ld_tok = pb.ld_tok; a.tok_row_stride = (size_t)k.llm_layers * k.llm_heads * (size_t)std::max(pb.ld_tok, 0);
   if (const char* m = fill_rows(a, pb.rows, pb.n_rows, cu, B, off_host)) return fail(c, AIGV_ERR_ARG, "%s: score attention: %s (the pass has %d rows)", op, m, cu[B]);
+  if (pb.tok || pb.ld_tok) {   // the dense rows: refused here, in front of the pass's first layer (aigv_probe_check repeats it per launch)
+    if (!pb.tok || pb.ld_tok < 1 || pb.ld_tok > AIGV_MAX_KV_CAPACITY)
+      return fail(c, AIGV_ERR_ARG, "%s: score attention tokens armed with ld_tok = %d, outside 1..%d, or without an output", op, pb.ld_tok, AIGV_MAX_KV_CAPACITY);
+    for (int i = 0; i < a.n_rows; ++i) {
+      const int keys = a.tab.r[i].off + (a.tab.r[i].row - a.tab.r[i].row0) + 1;
+      if (keys > pb.ld_tok) return fail(c, AIGV_ERR_ARG, "%s: score attention tokens: ld_tok = %d is below the %d keys of probe row %d", op, pb.ld_tok, keys, i);
+    }
+  }
   *out = a;
   return 0;
 }
@@ -57,6 +67,7 @@ int probe_layer(aigv_ctx* c, const ProbeArgs& plan, int li, bool cache, hipStrea
     a.k = c->l_qkv + (size_t)g * D; a.ldk = c->qkv_out; a.kv_head_stride = (g + 2) * D; a.kv_seq_stride = 0;
   }
   a.out = plan.out + (size_t)li * k.llm_heads * plan.n_seg;
+  if (plan.tok) a.tok = plan.tok + (size_t)li * k.llm_heads * plan.ld_tok;
   if (const char* m = aigv_probe_check(a, D, k.max_tokens, k.max_positions)) return fail(c, AIGV_ERR_ARG, "%s", m);
   HIPCHK(c, aigv_launch_attention_probe(a, D, s));
   return 0;
@@ -66,26 +77,39 @@ int probe_layer(aigv_ctx* c, const ProbeArgs& plan, int li, bool cache, hipStrea
 
 extern "C" {
 
-int aigv_score_attention_arm(aigv_ctx* c, const int32_t* rows_host, int n_rows, const int32_t* seg_new_dev, const int32_t* seg_cached_dev,
-                             int ld_cached, int n_segments, float* out_dev) {
-  if (!c) return fail(c, AIGV_ERR_ARG, "aigv_score_attention_arm: null context");
-  if (!rows_host || !seg_new_dev || !out_dev) return fail(c, AIGV_ERR_ARG, "aigv_score_attention_arm: null argument");
-  if (ld_cached < 0) return fail(c, AIGV_ERR_ARG, "aigv_score_attention_arm: ld_cached = %d must not be negative", ld_cached);
+static int arm(aigv_ctx* c, const char* op, const int32_t* rows_host, int n_rows, const int32_t* seg_new_dev, const int32_t* seg_cached_dev, int ld_cached,
+               int n_segments, float* out_dev, float* tok_out_dev, int ld_tok) {
+  if (!c) return fail(c, AIGV_ERR_ARG, "%s: null context", op);
+  if (!rows_host || !seg_new_dev || !out_dev) return fail(c, AIGV_ERR_ARG, "%s: null argument", op);
+  if (ld_cached < 0) return fail(c, AIGV_ERR_ARG, "%s: ld_cached = %d must not be negative", op, ld_cached);
   // limits are refused by the PASS (with a message), as the rows are: the pass is what knows its row count.  Rows beyond the table's
   // capacity are not copied; the count alone makes the pass refuse.
   auto& pb = c->probe;
   pb.n_rows = n_rows; pb.n_seg = n_segments; pb.ld_cached = ld_cached;
   for (int i = 0; i < std::min(std::max(n_rows, 0), AIGV_MAX_PROBE_ROWS); ++i) pb.rows[i] = rows_host[i];
   pb.seg_new = seg_new_dev; pb.seg_cached = seg_cached_dev; pb.out = out_dev;
+  pb.tok = tok_out_dev; pb.ld_tok = ld_tok;
   pb.armed = true;
   return 0;
 }
 
-int aigv_op_attention_probe(const void* q, int ldq, const void* k, int ldk, const int32_t* cu_host, int n_seq, int n_heads, int n_kv_heads,
-                            int q_group_stride, int kv_head_stride, int64_t kv_seq_stride, const int32_t* kv_off_host, int head_dim, const void* cos,
-                            const void* sin, int max_pos, const int32_t* rows_host, int n_rows, const int32_t* seg_new, const int32_t* seg_cached,
-                            int ld_cached, int n_segments, float* out, void* stream) {
-  const char* op = "aigv_op_attention_probe";
+int aigv_score_attention_arm(aigv_ctx* c, const int32_t* rows_host, int n_rows, const int32_t* seg_new_dev, const int32_t* seg_cached_dev,
+                             int ld_cached, int n_segments, float* out_dev) {
+  return arm(c, "aigv_score_attention_arm", rows_host, n_rows, seg_new_dev, seg_cached_dev, ld_cached, n_segments, out_dev, nullptr, 0);
+}
+
+int aigv_score_attention_arm_tokens(aigv_ctx* c, const int32_t* rows_host, int n_rows, const int32_t* seg_new_dev, const int32_t* seg_cached_dev,
+                                    int ld_cached, int n_segments, float* out_dev, float* tok_out_dev, int ld_tok) {
+  const char* op = "aigv_score_attention_arm_tokens";
+  if (c && !tok_out_dev) return fail(c, AIGV_ERR_ARG, "%s: null tok_out_dev", op);
+  if (c && ld_tok < 1) return fail(c, AIGV_ERR_ARG, "%s: ld_tok = %d must be positive", op, ld_tok);   // (too small for the rows, too large: the pass refuses)
+  return arm(c, op, rows_host, n_rows, seg_new_dev, seg_cached_dev, ld_cached, n_segments, out_dev, tok_out_dev, ld_tok);
+}
+
+static int op_probe(const char* op, const void* q, int ldq, const void* k, int ldk, const int32_t* cu_host, int n_seq, int n_heads, int n_kv_heads,
+                    int q_group_stride, int kv_head_stride, int64_t kv_seq_stride, const int32_t* kv_off_host, int head_dim, const void* cos,
+                    const void* sin, int max_pos, const int32_t* rows_host, int n_rows, const int32_t* seg_new, const int32_t* seg_cached,
+                    int ld_cached, int n_segments, float* out, float* tok_out, int ld_tok, void* stream) {
   if (!q || !k || !cu_host || !cos || !sin || !rows_host || !seg_new || !out) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
   if (n_seq < 1 || n_seq > AIGV_SMALL_INTS / 2 - 1 || cu_host[0] != 0) return fail(nullptr, AIGV_ERR_ARG, "%s: needs 1 <= n_seq <= %d and cu[0] = 0", op, AIGV_SMALL_INTS / 2 - 1);
   for (int b = 0; b < n_seq; ++b)
@@ -101,10 +125,27 @@ int aigv_op_attention_probe(const void* q, int ldq, const void* k, int ldk, cons
   a.rope_cos = (const bf16_t*)cos; a.rope_sin = (const bf16_t*)sin;
   a.seg_new = seg_new; a.seg_cached = seg_cached; a.ld_cached = ld_cached; a.n_seg = n_segments;
   a.out = out; a.out_row_stride = (size_t)n_heads * (n_segments > 0 ? n_segments : 0);
+  a.tok = tok_out; a.ld_tok = ld_tok; a.tok_row_stride = (size_t)n_heads * (size_t)(ld_tok > 0 ? ld_tok : 0);
   if (const char* m = fill_rows(a, rows_host, n_rows, cu_host, n_seq, kv_off_host)) return fail(nullptr, AIGV_ERR_ARG, "%s: %s", op, m);
   if (const char* m = aigv_probe_check(a, head_dim, cu_host[n_seq], max_pos)) return fail(nullptr, AIGV_ERR_ARG, "%s: %s", op, m);
   HIPCHK(nullptr, aigv_launch_attention_probe(a, head_dim, (hipStream_t)stream));
   return 0;
+}
+
+int aigv_op_attention_probe(const void* q, int ldq, const void* k, int ldk, const int32_t* cu_host, int n_seq, int n_heads, int n_kv_heads,
+                            int q_group_stride, int kv_head_stride, int64_t kv_seq_stride, const int32_t* kv_off_host, int head_dim, const void* cos,
+                            const void* sin, int max_pos, const int32_t* rows_host, int n_rows, const int32_t* seg_new, const int32_t* seg_cached,
+                            int ld_cached, int n_segments, float* out, void* stream) {
+  return op_probe("aigv_op_attention_probe", q, ldq, k, ldk, cu_host, n_seq, n_heads, n_kv_heads, q_group_stride, kv_head_stride, kv_seq_stride, kv_off_host,
+                  head_dim, cos, sin, max_pos, rows_host, n_rows, seg_new, seg_cached, ld_cached, n_segments, out, nullptr, 0, stream);
+}
+
+int aigv_op_attention_probe_tokens(const void* q, int ldq, const void* k, int ldk, const int32_t* cu_host, int n_seq, int n_heads, int n_kv_heads,
+                                   int q_group_stride, int kv_head_stride, int64_t kv_seq_stride, const int32_t* kv_off_host, int head_dim,
+                                   const void* cos, const void* sin, int max_pos, const int32_t* rows_host, int n_rows, const int32_t* seg_new,
+                                   const int32_t* seg_cached, int ld_cached, int n_segments, float* out, float* tok_out, int ld_tok, void* stream) {
+  return op_probe("aigv_op_attention_probe_tokens", q, ldq, k, ldk, cu_host, n_seq, n_heads, n_kv_heads, q_group_stride, kv_head_stride, kv_seq_stride,
+                  kv_off_host, head_dim, cos, sin, max_pos, rows_host, n_rows, seg_new, seg_cached, ld_cached, n_segments, out, tok_out, ld_tok, stream);
 }
 
 }  // extern "C"

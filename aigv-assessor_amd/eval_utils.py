@@ -141,6 +141,36 @@ def frame_saliency(att, layers=None):
     return (mass / mass.sum(-1, keepdim=True)).to(att.dtype)
 
 
+def frame_heatmaps(tok_att, positions, layers=None):
+    """Where INSIDE each frame the score row reads: ``tok_att`` is ``forward(return_token_attention=True)``'s ``score_attention_tokens``
+    [B, L, n_heads, N] (one softmax value per key), ``positions`` is ``prompts.visual_token_positions`` [B, F, tokens_per_frame] (-1: a
+    ragged clip has no such frame); returns [B, F, g, g] with g * g = tokens_per_frame (ValueError if that is no perfect square) - the
+    mass on every visual token, averaged over the heads and over ``layers`` (an index list; None: all layers) in float64 and renormalised
+    over ALL of the clip's visual tokens: ``heat.sum((2, 3))`` is ``frame_saliency(score_attention, layers)``, a clip's maps sum to 1 (a
+    frame the clip does not have stays 0; NaN where the row puts no mass on any frame).
+
+    Geometry: token t of a frame is cell ``divmod(t, g)`` = (r, c), row-major - pixel-shuffle v2's order (modeling_internvl_chat.py:492-506):
+    cell (r, c) is the concatenation of the ViT patches of patch rows 2r, 2r + 1 x patch columns 2c, 2c + 1.  For a 448 x 448 frame (14-pixel
+    patches, a 32 x 32 patch grid, g = 16) that is the pixel rectangle rows 28r .. 28r + 27 x columns 28c .. 28c + 27: ``heat[b, f]`` lies
+    over the frame as an image does, first axis down, second axis right."""
+    import math
+    import torch
+    if tok_att.dim() != 4 or positions.dim() != 3 or positions.shape[0] != tok_att.shape[0]:
+        raise ValueError(f"frame_heatmaps: expected [B, L, n_heads, N] and [B, F, tokens_per_frame], got {tuple(tok_att.shape)} and {tuple(positions.shape)}")
+    B, F, T = positions.shape
+    g = math.isqrt(T)
+    if g * g != T:
+        raise ValueError(f"frame_heatmaps: tokens_per_frame = {T} is not a perfect square")
+    if int(positions.max()) >= tok_att.shape[-1] or int(positions.min()) < -1:
+        raise ValueError(f"frame_heatmaps: positions outside -1 .. {tok_att.shape[-1] - 1}")
+    if layers is not None:
+        tok_att = tok_att.index_select(1, torch.as_tensor(list(layers), dtype=torch.long, device=tok_att.device))
+    per_key = tok_att.double().mean(dim=(1, 2))                               # [B, N]
+    idx = positions.to(per_key.device).view(B, F * T)
+    mass = per_key.gather(1, idx.clamp_min(0)) * (idx >= 0)
+    return (mass / mass.sum(-1, keepdim=True)).view(B, F, g, g).to(tok_att.dtype)
+
+
 def batched(items, model, k: int = 4, frames=None, ahead: bool = True, pad_id: int = 2, return_logprobs: bool = False, candidate_ids=None,
             top_logprobs=None):
     """The reference's eval loop at batch ``k`` instead of batch 1: yields ``(item, output)`` for EVERY item of ``items`` (the loop's

@@ -672,7 +672,7 @@ class InternVLChatModel(nn.Module):
             keep.append(pinned)
         return pinned.to(self.device, non_blocking=True)
 
-    def _prefill(self, ids_packed, slot, cu, vis, n_vis, motion, score_rows, logit_rows, keep_kv=False, kv_cap=0, probe=None):
+    def _prefill(self, ids_packed, slot, cu, vis, n_vis, motion, score_rows, logit_rows, keep_kv=False, kv_cap=0, probe=None, ld_tok=0):
         b = len(cu) - 1
         T = cu[-1]
         lib, ctx = self._native(n_tokens=T, n_clips=b, out_rows=len(logit_rows), kv_cap=kv_cap)
@@ -686,12 +686,12 @@ class InternVLChatModel(nn.Module):
         cu_a = native.i32_array(cu)
         sr_a = native.i32_array(score_rows) if score_rows is not None else None
         lr_a = native.i32_array(logit_rows) if len(logit_rows) else None
-        att = self._arm_score_attention(probe) if probe is not None else None   # (armed for exactly the pass below)
+        att, tok = self._arm_score_attention(probe, ld_tok) if probe is not None else (None, None)   # (armed for exactly the pass below)
         native.check(lib.aigv_llm_prefill(
             ctx, ids_d.data_ptr(), slot_d.data_ptr(), cu_a, b, native.ptr(vis), n_vis, native.ptr(motion),
             sr_a, native.ptr(score), lr_a, len(logit_rows), amax.data_ptr(), int(keep_kv), native.stream_ptr()), ctx)
         if probe is not None:
-            return score, amax[: len(logit_rows)], att
+            return score, amax[: len(logit_rows)], att, tok
         return score, amax[: len(logit_rows)]
 
     # ---- score-row attention by segment (return_score_attention) -------------------------------------------------------------------------
@@ -740,14 +740,35 @@ class InternVLChatModel(nn.Module):
             raise ValueError(f"return_score_attention: {S} segments, outside 1..{self.MAX_ATTN_SEGMENTS}")
         return rows, seg_d, None, 0, S
 
-    def _arm_score_attention(self, probe) -> torch.Tensor:
-        """Arm the context's NEXT prefill / continuation pass (aigv_score_attention_arm); returns the fp32 tensor [rows, L, n_heads, S] it fills."""
+    def visual_token_positions(self, input_ids, attention_mask=None, image_flags=None, n_frames: Optional[int] = None) -> torch.Tensor:
+        """``prompts.visual_token_positions`` of a batch as ``forward`` would pack it (host only, no GPU work): long [B, F, tokens_per_frame], the
+        column of ``score_attention_tokens[b]`` that holds every visual token of every frame, -1 where a clip has fewer frames than the
+        longest.  ``n_frames``: the frames handed to ``forward`` (``pixel_values.shape[0]``; default: ``image_flags.shape[0]``)."""
+        from . import prompts
+        if n_frames is None:
+            if image_flags is None:
+                raise ValueError("visual_token_positions: pass n_frames or image_flags")
+            n_frames = int(image_flags.shape[0])
+        plan = self._plan(input_ids, attention_mask, None, image_flags, int(n_frames))
+        slot, cu, ntok = plan["slot"], plan["cu"], self.num_image_token
+        frames = [int(((slot[cu[b]:cu[b + 1]] >= 0) & (slot[cu[b]:cu[b + 1]] < plan["n_vis"])).sum()) // ntok for b in range(len(cu) - 1)]
+        return prompts.visual_token_positions(slot, cu, frames, ntok)
+
+    def _arm_score_attention(self, probe, ld_tok: int = 0):
+        """Arm the context's NEXT prefill / continuation pass; returns (att, tok): the fp32 tensor [rows, L, n_heads, S] the pass fills
+        (aigv_score_attention_arm) and - ``ld_tok`` > 0, ``return_token_attention``: aigv_score_attention_arm_tokens - the dense rows [rows, L,
+        n_heads, ld_tok] the same pass fills, else None."""
         rows, seg_new, seg_cached, ld_cached, S = probe
         llm = self.config.llm_config
         att = torch.empty((len(rows), llm.num_hidden_layers, llm.num_attention_heads, S), dtype=torch.float32, device=self.device)
+        if ld_tok:
+            tok = torch.empty((len(rows), llm.num_hidden_layers, llm.num_attention_heads, int(ld_tok)), dtype=torch.float32, device=self.device)
+            native.check(native.load().aigv_score_attention_arm_tokens(self._ctx, native.i32_array(rows), len(rows), seg_new.data_ptr(), native.ptr(seg_cached),
+                                                                       int(ld_cached), int(S), att.data_ptr(), tok.data_ptr(), int(ld_tok)), self._ctx)
+            return att, tok
         native.check(native.load().aigv_score_attention_arm(self._ctx, native.i32_array(rows), len(rows), seg_new.data_ptr(), native.ptr(seg_cached),
                                                             int(ld_cached), int(S), att.data_ptr()), self._ctx)
-        return att
+        return att, None
 
     def forward(self, mos: Optional[torch.Tensor] = None, pixel_values: Optional[torch.Tensor] = None,
                 input_ids: Optional[torch.Tensor] = None, attention_mask: Optional[torch.Tensor] = None,
@@ -755,7 +776,8 @@ class InternVLChatModel(nn.Module):
                 labels: Optional[torch.Tensor] = None, use_cache=None, output_attentions=None,
                 output_hidden_states=None, return_dict=None, motion_feature: Optional[torch.Tensor] = None,
                 visual_tokens: Optional[torch.Tensor] = None, full_logits: bool = False, return_logprobs: bool = False,
-                candidate_ids=None, top_logprobs: Optional[int] = None, return_score_attention: bool = False, attention_segments=None):
+                candidate_ids=None, top_logprobs: Optional[int] = None, return_score_attention: bool = False, attention_segments=None,
+                return_token_attention: bool = False):
         """Stage-2 eval pass (modeling_internvl_chat.py:306-488) or, with ``stage=1``, the stage-1 pass
         (internvl_chat_eval1/modeling_internvl_chat.py:250-366).  ``visual_tokens`` optionally supplies
         already all-gathered pre-projector tokens (frame-DP) instead of ``pixel_values``.
@@ -791,7 +813,14 @@ class InternVLChatModel(nn.Module):
         small stand-alone kernel per layer that recomputes that one row's softmax in fp32 from the layer's Q and K (the flash kernels
         never form a probability matrix): no other output of the pass changes a bit, and the option combines freely with the
         log-probability options.  ``eval_utils.frame_saliency`` folds it to [B, F].  Under graph replay the flag (and S) is part of the
-        graph's key, a user table is a graph input, the tensor a graph output."""
+        graph's key, a user table is a graph input, the tensor a graph output.
+
+        ``return_token_attention=True`` (implies ``return_score_attention``) also adds ``score_attention_tokens`` (fp32 [B, L, n_heads, N], N =
+        ``input_ids.shape[1]``): the same row's softmax per KEY, from the same launch per layer - column j is the clip's j-th un-masked token
+        (``input_ids[b, j]`` for the collator's right-padded inputs), the columns behind the score row and the padding are 0.  The values
+        share the bins' scores, total and division (a bin of one key holds that key's bits); ``score_attention`` and every other output
+        keep their bits.  ``prompts.visual_token_positions`` + ``eval_utils.frame_heatmaps`` fold it to a 16 x 16 map per frame.  Under
+        graph replay the flag and N are part of the graph's key; the tensor is handed back as a copy."""
         if position_ids is not None or past_key_values is not None:
             raise NotImplementedError("the eval pass takes default positions and no cache, like the reference drivers")
         if self.img_context_token_id is None:
@@ -799,7 +828,8 @@ class InternVLChatModel(nn.Module):
         pixel_values, visual_tokens, motion_feature = self._take_ahead(pixel_values, visual_tokens, motion_feature)
         if self._graph_replay_enabled and self._capture_keep is None:
             out = self._forward_through_graph(mos, pixel_values, input_ids, attention_mask, image_flags, labels, motion_feature, visual_tokens, full_logits,
-                                              return_logprobs, candidate_ids, top_logprobs, return_score_attention, attention_segments)
+                                              return_logprobs, candidate_ids, top_logprobs, return_score_attention, attention_segments,
+                                              return_token_attention)
             if out is not None:
                 return out
         B, N = input_ids.shape
@@ -815,17 +845,17 @@ class InternVLChatModel(nn.Module):
         # ---- device work: ViT -> projector -> motion projector -> LLM pass + heads ----
         self._native(n_frames=n_frames, n_tokens=plan["cu"][-1], n_clips=B, out_rows=len(plan["logit_rows"]), seq_len=N)   # size workspaces once
         vit_embeds, motion = self._visual_inputs(pixel_values, visual_tokens, motion_feature, plan)
-        att = None
-        if return_score_attention:
+        att = tok = None
+        if return_score_attention or return_token_attention:
             probe = self._score_attention_probe(plan, input_ids, attention_segments)
-            score, amax, att = self._prefill(plan["ids_packed"], plan["slot"], plan["cu"], vit_embeds, plan["n_vis"], motion,
-                                             plan["score_rows"], plan["logit_rows"], probe=probe)
+            score, amax, att, tok = self._prefill(plan["ids_packed"], plan["slot"], plan["cu"], vit_embeds, plan["n_vis"], motion,
+                                                  plan["score_rows"], plan["logit_rows"], probe=probe, ld_tok=N if return_token_attention else 0)
         else:
             score, amax = self._prefill(plan["ids_packed"], plan["slot"], plan["cu"], vit_embeds, plan["n_vis"], motion,
                                         plan["score_rows"], plan["logit_rows"])
         lp, clp = self._row_logprobs(B if score is not None else 0, len(plan["logit_rows"]), lp_labels if return_logprobs else None, cand)
         top = self._row_topk(B if score is not None else 0, len(plan["logit_rows"]), topk) if topk else None
-        return self._outputs(plan, B, N, score, amax, mos, lp, clp, top, att)
+        return self._outputs(plan, B, N, score, amax, mos, lp, clp, top, att, tok)
 
     # ---- HIP-graph replay of whole scoring passes (opt-in: enable_graph_replay) ---------------------------------------------------------
     _graph_replay_enabled = False
@@ -960,7 +990,8 @@ class InternVLChatModel(nn.Module):
         return cl(outputs)
 
     def _forward_through_graph(self, mos, pixel_values, input_ids, attention_mask, image_flags, labels, motion_feature, visual_tokens, full_logits,
-                               return_logprobs=False, candidate_ids=None, top_logprobs=None, return_score_attention=False, attention_segments=None):
+                               return_logprobs=False, candidate_ids=None, top_logprobs=None, return_score_attention=False, attention_segments=None,
+                               return_token_attention=False):
         """The replay path of ``forward``; returns None when the call does not qualify (the eager path then runs)."""
         src = visual_tokens if visual_tokens is not None else pixel_values
         if self._rope_seq_len(int(input_ids.shape[1])) != getattr(self, "_rope_ntk", 0):
@@ -983,7 +1014,7 @@ class InternVLChatModel(nn.Module):
         if topk:
             host_key += (("top_logprobs", topk),)   # (k is an output shape: another k is another graph)
         seg, n_seg = None, 0
-        if return_score_attention:
+        if return_score_attention or return_token_attention:
             # (the flag is part of the key; the default table follows from the ids, which are; a user table is graph INPUT, its bin count - an output shape - key)
             if attention_segments is not None:
                 if not torch.is_tensor(attention_segments) or attention_segments.is_floating_point() or tuple(attention_segments.shape) != tuple(input_ids.shape):
@@ -991,6 +1022,8 @@ class InternVLChatModel(nn.Module):
                 n_seg = int(attention_segments.max()) + 1
                 seg = self._h2d(attention_segments.contiguous())
             host_key += (("score_attention", n_seg),)
+        if return_token_attention:
+            host_key += (("score_attention_tokens", int(input_ids.shape[1])),)   # (ld_tok is an output shape)
         self._join_side_stream()             # (a motion feature started by motion_feature_async: joined BEFORE the graph copies it in)
         self._prepare_motion_branch(pixel_values if (motion_feature is None and visual_tokens is None) else None, int(input_ids.shape[0]))
 
@@ -1006,7 +1039,7 @@ class InternVLChatModel(nn.Module):
                                 image_flags=image_flags, labels=labels, motion_feature=mf_static, full_logits=full_logits,
                                 visual_tokens=src_static if visual_tokens is not None else None, return_logprobs=return_logprobs,
                                 candidate_ids=cand_static, top_logprobs=top_logprobs, return_score_attention=return_score_attention,
-                                attention_segments=seg_static)
+                                attention_segments=seg_static, return_token_attention=return_token_attention)
         return self._graph_call(host_key, [src, motion_feature, cand] + ([seg] if seg is not None else []), fn)   # (a user table only: the other keys stay what they were)
 
     def dp_front(self, frames_local: torch.Tensor, frames_clips: Optional[torch.Tensor], n_clips: int):
@@ -1147,7 +1180,7 @@ class InternVLChatModel(nn.Module):
             vit_embeds = vit_embeds[self._h2d(plan["keep"])]
         return vit_embeds.reshape(-1, H), self.motion_embed(motion_feature)
 
-    def _outputs(self, plan, B, N, score, amax, mos, lp=None, clp=None, top=None, att=None):
+    def _outputs(self, plan, B, N, score, amax, mos, lp=None, clp=None, top=None, att=None, tok=None):
         dev = self.device
         up = self._h2d   # host -> device through pinned memory, never blocking the host (keeps the CPU ahead of the GPU)
         idx = up(plan["want"].reshape(-1).nonzero().flatten()) if len(plan["logit_rows"]) else None   # index list built on the host: no sync
@@ -1181,6 +1214,8 @@ class InternVLChatModel(nn.Module):
             out["top_logprob"] = scatter(lp_k, float("nan"))
         if att is not None:                         # return_score_attention: [B, L, n_heads, S]
             out["score_attention"] = att
+        if tok is not None:                         # return_token_attention: [B, L, n_heads, N]
+            out["score_attention_tokens"] = tok
         return out
 
     MAX_CANDIDATES = 64      # = AIGV_MAX_CANDIDATES
@@ -1280,7 +1315,7 @@ class InternVLChatModel(nn.Module):
     def forward_shared_prefix(self, prompts, pixel_values: Optional[torch.Tensor] = None, image_flags: Optional[torch.Tensor] = None,
                               motion_feature: Optional[torch.Tensor] = None, visual_tokens: Optional[torch.Tensor] = None, mos=None,
                               return_logprobs: bool = False, candidate_ids=None, top_logprobs: Optional[int] = None,
-                              return_score_attention: bool = False):
+                              return_score_attention: bool = False, return_token_attention: bool = False):
         """Score the same clips under several prompts that share their beginning - the reference's four quality
         perspectives ask four questions BEHIND the same system + frame + motion tokens (8f-3) and
         run four full passes (stage2_eval.py evaluates one jsonl per perspective).  Here the common prefix runs once
@@ -1293,7 +1328,9 @@ class InternVLChatModel(nn.Module):
         ``cand_logprob`` as ``forward`` defines it (the same candidates for every prompt).  ``top_logprobs``: every prompt's dict carries
         ``top_ids`` / ``top_logprob`` as ``forward`` defines them.  ``return_score_attention``: every prompt's dict carries its own
         ``score_attention`` [B, L, n_heads, F + 4] as ``forward`` defines it (default segments), read by the continuation pass over the cached
-        prefix keys and the prompt's own tokens; at most 64 (clip, prompt) pairs."""
+        prefix keys and the prompt's own tokens; at most 64 (clip, prompt) pairs.  ``return_token_attention`` (implies it): every prompt's dict
+        also carries ``score_attention_tokens`` [B, L, n_heads, N] as ``forward`` defines it, N = the longest prefix + prompt length over the
+        prompts; the columns cover the prefix and then the prompt's own tokens, in order."""
         if self.img_context_token_id is None:
             raise AssertionError("img_context_token_id must be set by the caller (stage2_eval.py:810)")
         if not prompts:
@@ -1344,8 +1381,8 @@ class InternVLChatModel(nn.Module):
         ids_d = torch.cat(parts).to(torch.long).contiguous().pin_memory().to(dev, non_blocking=True)
         score = torch.empty(B * P, dtype=torch.float32, device=dev) if self.stage == 2 else None
         amax = torch.empty(max(len(lrows), 1), dtype=torch.long, device=dev)
-        att = None
-        if return_score_attention:
+        att = tok = None
+        if return_score_attention or return_token_attention:
             # rows: sequence p * B + b of the continuation batch; segments of its new tokens: the prompt's own table behind the prefix; of the
             # cached keys: the clip's prefix table, tiled over the P prompts (row p * B + b, padded with -1 to the longest prefix)
             if B * P > self.MAX_PROBE_ROWS:
@@ -1361,7 +1398,9 @@ class InternVLChatModel(nn.Module):
             seg_cached = torch.full((P * B, ld), -1, dtype=torch.int32)
             for b in range(B):
                 seg_cached[b::B, :pre[b]] = seg0[p0["cu"][b]:p0["cu"][b] + pre[b]]
-            att = self._arm_score_attention((prows, self._h2d(torch.cat(seg_parts).contiguous()), self._h2d(seg_cached), ld, S))
+            probe = (prows, self._h2d(torch.cat(seg_parts).contiguous()), self._h2d(seg_cached), ld, S)
+            # (without the dense rows: the one-argument call, the form wrappers of this method have always been written against)
+            att, tok = self._arm_score_attention(probe, longest) if return_token_attention else self._arm_score_attention(probe)
         native.check(lib.aigv_llm_extend(ctx, ids_d.data_ptr(), native.i32_array(cu_s), B * P,
                                          native.i32_array(srows) if score is not None else None, native.ptr(score),
                                          native.i32_array(lrows) if lrows else None, len(lrows), amax.data_ptr(), 0,
@@ -1374,7 +1413,8 @@ class InternVLChatModel(nn.Module):
                                       amax[off:off + n_l[p]], mos, lp[off:off + n_l[p]] if lp is not None else None,
                                       clp[off:off + n_l[p]] if clp is not None else None,
                                       (top[0][off:off + n_l[p]], top[1][off:off + n_l[p]]) if top is not None else None,
-                                      att[p * B:(p + 1) * B] if att is not None else None))
+                                      att[p * B:(p + 1) * B] if att is not None else None,
+                                      tok[p * B:(p + 1) * B] if tok is not None else None))
             off += n_l[p]
         return outs
 

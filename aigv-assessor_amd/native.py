@@ -80,6 +80,7 @@ PROTOTYPES = {
     "aigv_llm_prefill": (_I, [_P, _P, _P, _I32P, _I, _P, _I, _P, _I32P, _P, _I32P, _I, _P, _I, _P]),
     "aigv_llm_extend": (_I, [_P, _P, _I32P, _I, _I32P, _P, _I32P, _I, _P, _I, _P]),
     "aigv_score_attention_arm": (_I, [_P, _I32P, _I, _P, _P, _I, _I, _P]),
+    "aigv_score_attention_arm_tokens": (_I, [_P, _I32P, _I, _P, _P, _I, _I, _P, _P, _I]),
     "aigv_kv_fork": (_I, [_P, _I, _P]),
     "aigv_kv_reorder": (_I, [_P, _P, _P, _I, _P]),
     "aigv_set_row_trimming": (_I, [_P, _I]),
@@ -131,6 +132,7 @@ PROTOTYPES = {
     "aigv_op_attention_ex": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, C.c_int64, _P, _I, _I, _F, _F, _P, _P, _P, _I, _I, _P]),
     "aigv_op_kv_store": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "aigv_op_attention_probe": (_I, [_P, _I, _P, _I, _I32P, _I, _I, _I, _I, _I, C.c_int64, _I32P, _I, _P, _P, _I, _I32P, _I, _P, _P, _I, _I, _P, _P]),
+    "aigv_op_attention_probe_tokens": (_I, [_P, _I, _P, _I, _I32P, _I, _I, _I, _I, _I, C.c_int64, _I32P, _I, _P, _P, _I, _I32P, _I, _P, _P, _I, _I, _P, _P, _I, _P]),
     "aigv_op_pixel_shuffle": (_I, [_P, _I, _I, _P, _I, _P]),
     "aigv_op_im2col": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "aigv_op_lm_head_argmax": (_I, [_P, _I, _I, _P, _I, _P, _P, _P, _P]),

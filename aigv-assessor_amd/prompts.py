@@ -121,6 +121,36 @@ def level_token_ids(tokenizer, words: Sequence[str] = ("bad", "poor", "fair", "g
 N_TEXT_SEGMENTS = 4             # bins behind the F frame bins: motion token | first token (the sink) | text up to the last visual token | text after it
 
 
+def _visual_layout(name: str, slot, cu: Sequence[int], n_frames, tokens_per_frame: int):
+    """What ``attention_segments`` and ``visual_token_positions`` share: the validated slot map -> (F, [(lo, hi, mask of the clip's visual
+    tokens, mask of its motion token, their number)] per clip).  ``name`` heads the messages."""
+    slot = torch.as_tensor(slot).to(torch.long).flatten()
+    cu = [int(v) for v in cu]
+    B = len(cu) - 1
+    if B < 1 or cu[0] != 0 or cu[-1] != slot.numel() or any(cu[b + 1] <= cu[b] for b in range(B)):
+        raise ValueError(f"{name}: cu {cu} does not divide the {slot.numel()} packed tokens into non-empty clips")
+    if tokens_per_frame < 1:
+        raise ValueError(f"{name}: tokens_per_frame must be positive")
+    per_clip = [int(n_frames)] * B if isinstance(n_frames, int) else [int(v) for v in n_frames]
+    if len(per_clip) != B or min(per_clip) < 0:
+        raise ValueError(f"{name}: n_frames {n_frames!r} is neither an int nor one count per clip ({B} clips)")
+    exact = not isinstance(n_frames, int)
+    F = max(per_clip)
+    n_vis = int((slot >= 0).sum()) - B                  # every clip carries exactly one motion token: the B largest slots
+    if n_vis < 0 or sorted(slot[slot >= 0].tolist()) != list(range(n_vis + B)):
+        raise ValueError(f"{name}: the slots must be 0 .. n_vis - 1 (visual tokens) and n_vis + b (the motion token of clip b), each once")
+    is_motion = slot >= n_vis
+    clips = []
+    for b in range(B):
+        lo, hi = cu[b], cu[b + 1]
+        vis = ((slot[lo:hi] >= 0) & ~is_motion[lo:hi])
+        n_v = int(vis.sum())
+        if n_v % tokens_per_frame or n_v > per_clip[b] * tokens_per_frame or (exact and n_v != per_clip[b] * tokens_per_frame):
+            raise ValueError(f"{name}: clip {b} holds {n_v} visual tokens, expected {'' if exact else 'up to '}{per_clip[b]} frames of {tokens_per_frame}")
+        clips.append((lo, hi, vis, is_motion[lo:hi], n_v))
+    return F, clips
+
+
 def attention_segments(slot, cu: Sequence[int], n_frames, tokens_per_frame: int) -> torch.Tensor:
     """The key-segment table of ``forward(return_score_attention=True)``: one int32 id per PACKED token (host, no GPU), so that the
     score row's attention mass can be read per frame.  ``slot`` is the pass's slot map (int per packed token: -1 a text token, 0 ..
@@ -135,34 +165,27 @@ def attention_segments(slot, cu: Sequence[int], n_frames, tokens_per_frame: int)
 
     ``n_frames``: an int F - every clip may hold up to F frames - or one count per clip (ragged clips in one packed batch: F is the
     largest, a shorter clip leaves its later frame bins empty).  Users may build another table and pass it as ``attention_segments=``."""
-    slot = torch.as_tensor(slot).to(torch.long).flatten()
-    cu = [int(v) for v in cu]
-    B = len(cu) - 1
-    if B < 1 or cu[0] != 0 or cu[-1] != slot.numel() or any(cu[b + 1] <= cu[b] for b in range(B)):
-        raise ValueError(f"attention_segments: cu {cu} does not divide the {slot.numel()} packed tokens into non-empty clips")
-    if tokens_per_frame < 1:
-        raise ValueError("attention_segments: tokens_per_frame must be positive")
-    per_clip = [int(n_frames)] * B if isinstance(n_frames, int) else [int(v) for v in n_frames]
-    if len(per_clip) != B or min(per_clip) < 0:
-        raise ValueError(f"attention_segments: n_frames {n_frames!r} is neither an int nor one count per clip ({B} clips)")
-    exact = not isinstance(n_frames, int)
-    F = max(per_clip)
-    n_vis = int((slot >= 0).sum()) - B                  # every clip carries exactly one motion token: the B largest slots
-    if n_vis < 0 or sorted(slot[slot >= 0].tolist()) != list(range(n_vis + B)):
-        raise ValueError("attention_segments: the slots must be 0 .. n_vis - 1 (visual tokens) and n_vis + b (the motion token of clip b), each once")
-    is_motion = slot >= n_vis
-    seg = torch.empty(slot.numel(), dtype=torch.int32)
-    for b in range(B):
-        lo, hi = cu[b], cu[b + 1]
-        vis = ((slot[lo:hi] >= 0) & ~is_motion[lo:hi])
-        n_v = int(vis.sum())
-        if n_v % tokens_per_frame or n_v > per_clip[b] * tokens_per_frame or (exact and n_v != per_clip[b] * tokens_per_frame):
-            raise ValueError(f"attention_segments: clip {b} holds {n_v} visual tokens, expected {'' if exact else 'up to '}{per_clip[b]} frames of {tokens_per_frame}")
+    F, clips = _visual_layout("attention_segments", slot, cu, n_frames, tokens_per_frame)
+    seg = torch.empty(clips[-1][1], dtype=torch.int32)
+    for lo, hi, vis, motion, n_v in clips:
         last_vis = int(vis.nonzero().max()) if n_v else -1
         part = torch.full((hi - lo,), F + 3, dtype=torch.int32)
         part[:max(last_vis, 0)] = F + 2
         part[0] = F + 1
         part[vis] = (torch.arange(n_v) // tokens_per_frame).to(torch.int32)
-        part[is_motion[lo:hi]] = F
+        part[motion] = F
         seg[lo:hi] = part
     return seg
+
+
+def visual_token_positions(slot, cu: Sequence[int], n_frames, tokens_per_frame: int) -> torch.Tensor:
+    """Where every visual token of every frame sits INSIDE its own clip: long [B, F, tokens_per_frame], entry [b, f, t] = the position (0 =
+    the clip's first token) of token t of clip b's frame f - the column of ``forward(return_token_attention=True)``'s
+    ``score_attention_tokens[b]`` that holds its mass - or -1 where a ragged clip has no frame f.  Built from the slot map
+    ``attention_segments`` reads, with its arguments and its validation: position [b, f, t] carries segment id f there.
+    ``eval_utils.frame_heatmaps`` folds the dense attention with it."""
+    F, clips = _visual_layout("visual_token_positions", slot, cu, n_frames, tokens_per_frame)
+    pos = torch.full((len(clips), F * tokens_per_frame), -1, dtype=torch.long)
+    for b, (lo, hi, vis, motion, n_v) in enumerate(clips):
+        pos[b, :n_v] = vis.nonzero().flatten()
+    return pos.view(len(clips), F, tokens_per_frame)

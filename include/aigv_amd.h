@@ -43,7 +43,8 @@ extern "C" {
                                 aigv_slowfast_slow_indices / _pool_weights / _conv_k_slices), then by the test entry points of the score head
                                 and the row kernels (aigv_op_score_head, aigv_op_rmsnorm_quant_fp8, aigv_op_rope_slots, aigv_op_embed,
                                 aigv_op_seqpos, aigv_op_gather_rows, aigv_op_scatter_rows, aigv_op_cls_rows, aigv_op_write_ints), then by the
-                                score-row attention probe (aigv_score_attention_arm, aigv_op_attention_probe)
+                                score-row attention probe (aigv_score_attention_arm, aigv_op_attention_probe), then by its dense per-key
+                                form (aigv_score_attention_arm_tokens, aigv_op_attention_probe_tokens)
                                 - added symbols only: a library without them is refused at load
                                 time, "missing <name>" */
 
@@ -178,6 +179,17 @@ int aigv_llm_extend(aigv_ctx* ctx, const int64_t* ids, const int32_t* cu, int n_
  * Out of scope: aigv_decode_step ignores the feature (an armed context stays armed across decode steps). */
 int aigv_score_attention_arm(aigv_ctx* ctx, const int32_t* rows_host, int n_rows, const int32_t* seg_new_dev, const int32_t* seg_cached_dev,
                              int ld_cached, int n_segments, float* out_dev);
+/* Score-row attention per KEY: aigv_score_attention_arm's arguments and contract (it arms exactly the next aigv_llm_prefill / aigv_llm_extend,
+ * which disarms on every way out; out_dev is filled as above, bit for bit), plus a dense output filled by the SAME launch per layer:
+ *   tok_out_dev[row][layer][head][j] = softmax_j(q . k_j / sqrt(head_dim))   for the key positions j = 0 .. pos of the row's own sequence
+ *                                                                             (the cached keys first, then the rows of this pass)
+ *   tok_out_dev[row][layer][head][j] = +0.0                                  for pos < j < ld_tok
+ * fp32, DEVICE, [n_rows][layers][n_heads][ld_tok]: every column is written, nothing outside them.  The scores, the row maximum, the total
+ * and the one division are the bins': a bin that holds exactly one key carries that key's dense bits, and a row's bits are its own.
+ * ld_tok must be at least the largest pos + 1 over the probe rows and at most AIGV_MAX_KV_CAPACITY: AIGV_ERR_ARG from the pass, with a
+ * message, before its first layer.  Nothing is allocated (the armed pass still captures); aigv_decode_step ignores the feature. */
+int aigv_score_attention_arm_tokens(aigv_ctx* ctx, const int32_t* rows_host, int n_rows, const int32_t* seg_new_dev, const int32_t* seg_cached_dev,
+                                    int ld_cached, int n_segments, float* out_dev, float* tok_out_dev, int ld_tok);
 
 /* Replicate the n kept sequences `copies` times (cache slots [0, n) -> [n, 2n), ...; needs n * copies <= max_seqs): the copies can
  * then take DIFFERENT continuations in one aigv_llm_extend call over n * copies sequences (sequence c * n + b continues clip b),
@@ -397,6 +409,14 @@ int aigv_op_attention_probe(const void* q, int ldq, const void* k, int ldk, cons
                             int q_group_stride, int kv_head_stride, int64_t kv_seq_stride, const int32_t* kv_off_host, int head_dim, const void* cos,
                             const void* sin, int max_pos, const int32_t* rows_host, int n_rows, const int32_t* seg_new, const int32_t* seg_cached,
                             int ld_cached, int n_segments, float* out, void* stream);
+/* aigv_op_attention_probe with the dense per-key output of aigv_score_attention_arm_tokens from the same launch: tok_out [n_rows, n_heads,
+ * ld_tok] fp32 DEVICE (one layer).  Refused on the host (AIGV_ERR_ARG with a message, nothing launched) when ld_tok is below the largest
+ * position + 1 over the probe rows or above AIGV_MAX_KV_CAPACITY, or when tok_out is NULL while ld_tok > 0; tok_out = NULL with ld_tok = 0
+ * is aigv_op_attention_probe.  `out` keeps its bits. */
+int aigv_op_attention_probe_tokens(const void* q, int ldq, const void* k, int ldk, const int32_t* cu_host, int n_seq, int n_heads, int n_kv_heads,
+                                   int q_group_stride, int kv_head_stride, int64_t kv_seq_stride, const int32_t* kv_off_host, int head_dim,
+                                   const void* cos, const void* sin, int max_pos, const int32_t* rows_host, int n_rows, const int32_t* seg_new,
+                                   const int32_t* seg_cached, int ld_cached, int n_segments, float* out, float* tok_out, int ld_tok, void* stream);
 /* The KV-cache append of the prefill and continuation passes: for token t, the K and V slots of every group of the fused row
  * qkv[t * ld ..] (groups of [g query heads | K | V]) are copied to kc / vc [seq][n_kv][cap][head_dim] at [seq[t]][kvh][pos[t]]; nothing else
  * is written.  seq / pos: DEVICE int32[tokens] (the caller's promise: seq[t] inside the cache, pos[t] < cap).  Checked on the host. */
