@@ -25,6 +25,8 @@ from typing import Dict, List, Optional, Tuple
 import torch
 import torch.distributed as dist
 
+from . import readouts
+
 timeout = timedelta(minutes=60)
 # A one-rank group needs no collective.  Set to True to run them anyway (a one-rank RCCL all-gather is a device copy through RCCL's own
 # stream and work handle): how the collective path is exercised on a single MI355X (tests/test_gpu_dist.py, bench.py --force-dp).
@@ -227,13 +229,9 @@ def score_clips_dp(model, pixel_values: torch.Tensor, input_ids: torch.Tensor, a
     dev = local.device
     n1 = N - 1
     score_l = torch.zeros((chi - clo,), dtype=torch.float32, device=dev)
-    logit_l = torch.full(((chi - clo) * n1,), -1, dtype=torch.long, device=dev)
-    logprob_l = torch.full(((chi - clo) * n1,), float("nan"), dtype=torch.float32, device=dev)
-    n_cand = 0 if candidate_ids is None else int(candidate_ids.numel() if torch.is_tensor(candidate_ids) else len(candidate_ids))
-    cand_l = torch.full(((chi - clo) * n1, n_cand), float("nan"), dtype=torch.float32, device=dev)
-    n_top = 0 if top_logprobs is None else int(top_logprobs)
-    top_ids_l = torch.full(((chi - clo) * n1, n_top), -1, dtype=torch.long, device=dev)
-    top_lp_l = torch.full(((chi - clo) * n1, n_top), float("nan"), dtype=torch.float32, device=dev)
+    ro = readouts.ReadOuts(bool(return_logprobs), candidate_ids, top_logprobs)
+    fields = ro.row_fields()      # 'logit' and what the options add: a rank without clips contributes each one's fill
+    rows_l = {name: torch.full(((chi - clo) * n1,) + width, fill, dtype=dt, device=dev) for name, width, dt, fill in fields}
     own = chi > clo and lo <= clo * fpc and chi * fpc <= hi and not prefer_gathered
     tokens = None if own else finish_tokens()
     if chi > clo:
@@ -241,16 +239,8 @@ def score_clips_dp(model, pixel_values: torch.Tensor, input_ids: torch.Tensor, a
         out = model(mos=None if mos is None else mos[sl], pixel_values=None, input_ids=input_ids[sl],
                     attention_mask=None if attention_mask is None else attention_mask[sl],
                     image_flags=None if image_flags is None else image_flags[fl], labels=labels[sl],
-                    motion_feature=motion_l, visual_tokens=vis, **({"return_logprobs": True} if return_logprobs else {}),
-                    **({} if candidate_ids is None else {"candidate_ids": candidate_ids}),
-                    **({} if top_logprobs is None else {"top_logprobs": top_logprobs}))
-        logit_l = out["logit"]
-        if top_logprobs is not None:
-            top_ids_l, top_lp_l = out["top_ids"], out["top_logprob"]
-        if candidate_ids is not None:
-            cand_l = out["cand_logprob"]
-        if return_logprobs:
-            logprob_l = out["logprob"]
+                    motion_feature=motion_l, visual_tokens=vis, **readouts.forward_kwargs(ro))
+        rows_l = {name: out[name] for name, _, _, _ in fields}
         if "score1" in out:
             score_l = out["score1"].float()
     if own:
@@ -258,21 +248,11 @@ def score_clips_dp(model, pixel_values: torch.Tensor, input_ids: torch.Tensor, a
     # 5. results everywhere
     counts = [h - l for l, h in csplit]
     score = all_gather_rows(score_l, counts, group)
-    logit = all_gather_rows(logit_l.view(chi - clo, n1), counts, group).reshape(-1)
-    res = {"logit": logit, "label": labels[..., 1:].contiguous().view(-1).to(logit.device)}
-    if return_logprobs:
-        logprob = all_gather_rows(logprob_l.view(chi - clo, n1), counts, group).reshape(-1)
-        res["logprob"] = logprob
-        scored = (labels[..., 1:].reshape(-1) != -100).nonzero().flatten().to(logprob.device)
-        if scored.numel():   # forward()'s ce_loss: CrossEntropyLoss()'s mean over the non-ignored labels, in fp64, rounded once
-            res["ce_loss"] = (-logprob.index_select(0, scored)).double().mean().float()
-        else:
-            res["ce_loss"] = torch.full((), float("nan"), dtype=torch.float32, device=logprob.device)
-    if candidate_ids is not None:
-        res["cand_logprob"] = all_gather_rows(cand_l.view(chi - clo, n1 * n_cand), counts, group).reshape(-1, n_cand)
-    if top_logprobs is not None:
-        res["top_ids"] = all_gather_rows(top_ids_l.view(chi - clo, n1 * n_top), counts, group).reshape(-1, n_top)
-        res["top_logprob"] = all_gather_rows(top_lp_l.view(chi - clo, n1 * n_top), counts, group).reshape(-1, n_top)
+    res = {name: all_gather_rows(rows_l[name].view(chi - clo, n1 * torch.Size(width).numel()), counts, group).reshape((-1,) + width)
+           for name, width, _, _ in fields}
+    res["label"] = labels[..., 1:].contiguous().view(-1).to(res["logit"].device)
+    if return_logprobs:      # forward()'s ce_loss
+        res["ce_loss"] = readouts.ce_loss(res["logprob"], labels[..., 1:])
     if getattr(model, "stage", 2) == 2:
         res["score1"] = score.to(torch.bfloat16)
     return res

@@ -202,8 +202,10 @@ def batched(items, model, k: int = 4, frames=None, ahead: bool = True, pad_id: i
     bit the item's own pass."""
     import torch
     import torch.nn.functional as F
+    from . import readouts
     if k < 1:
         raise ValueError("k must be >= 1")
+    ro = readouts.ReadOuts(bool(return_logprobs), candidate_ids, top_logprobs)
     get = frames or _frames_of
 
     def groups():
@@ -247,32 +249,19 @@ def batched(items, model, k: int = 4, frames=None, ahead: bool = True, pad_id: i
         out = model(mos=None, pixel_values=front, input_ids=torch.stack([pad(i, pad_id) for i in ids]),
                     attention_mask=torch.stack([pad(m, False) for m in masks]), image_flags=flags,
                     labels=torch.stack([pad(l, -100) for l in labels]), **({} if motion is None else {"motion_feature": motion}),
-                    **({"return_logprobs": True} if return_logprobs else {}),
-                    **({} if candidate_ids is None else {"candidate_ids": candidate_ids}),
-                    **({} if top_logprobs is None else {"top_logprobs": top_logprobs}))
+                    **readouts.forward_kwargs(ro))
         return group, n, nmax, out
 
     def collect(run):
         """The group's results to the host - ONE synchronisation per group (the plain loop has one per clip: score1.item(), stage2_eval.py:938) - and
         out per item."""
         group, n, nmax, out = run
-        logit = out["logit"].view(len(group), nmax - 1).cpu()
-        label = out["label"].view(len(group), nmax - 1).cpu()
+        rows = {name: out[name].view((len(group), nmax - 1) + width).cpu() for name, width in [("label", ())] + [f[:2] for f in ro.row_fields()]}
         score1 = out["score1"].cpu() if "score1" in out else None
-        logprob = out["logprob"].view(len(group), nmax - 1).cpu() if return_logprobs else None
-        cand = out["cand_logprob"].view(len(group), nmax - 1, -1).cpu() if candidate_ids is not None else None
-        top_ids = out["top_ids"].view(len(group), nmax - 1, -1).cpu() if top_logprobs is not None else None
-        top_lp = out["top_logprob"].view(len(group), nmax - 1, -1).cpu() if top_logprobs is not None else None
         for b, (it, _) in enumerate(group):
-            o = {"logit": logit[b, : n[b] - 1].clone(), "label": label[b, : n[b] - 1].clone()}
-            if logprob is not None:
-                o["logprob"] = logprob[b, : n[b] - 1].clone()
+            o = {name: t[b, : n[b] - 1].clone() for name, t in rows.items()}
+            if return_logprobs:
                 o["ce_loss"] = (-o["logprob"][o["label"] != -100]).double().mean().float()
-            if cand is not None:
-                o["cand_logprob"] = cand[b, : n[b] - 1].clone()
-            if top_ids is not None:
-                o["top_ids"] = top_ids[b, : n[b] - 1].clone()
-                o["top_logprob"] = top_lp[b, : n[b] - 1].clone()
             if score1 is not None:
                 o["score1"] = score1[b: b + 1].clone()
                 mos = it.get("mos")

@@ -116,3 +116,110 @@ def build(sequences: torch.Tensor, flags: Dict[str, bool], scores: Sequence[torc
     if sequences_scores is not None:
         out["sequences_scores"] = sequences_scores
     return out
+
+
+def gen_args(generation_config, kw):
+    """(max_new_tokens, eos ids, pad id, sampler, processors, beams) from a HF-style generation config / kwargs.  ``sampler`` is None for greedy
+    decoding or the warper settings of HF's multinomial sampling (temperature -> top-k -> top-p, transformers' order and
+    defaults: top_k 50, top_p 1.0, temperature 1.0); ``processors`` = HF's repetition-penalty / no-repeat-n-gram logits processors
+    when asked for; ``beams`` is None or HF's beam-search settings (num_beams > 1: num_beams, length_penalty, early_stopping)."""
+    cfg = dict(generation_config) if isinstance(generation_config, dict) else {}
+    if generation_config is not None and not isinstance(generation_config, dict):
+        cfg = {k: getattr(generation_config, k) for k in ("max_new_tokens", "do_sample", "num_beams", "eos_token_id", "pad_token_id",
+                                                          "temperature", "top_k", "top_p", "repetition_penalty", "no_repeat_ngram_size",
+                                                          "length_penalty", "early_stopping", "num_return_sequences", "num_beam_groups")
+               if hasattr(generation_config, k)}
+    cfg.update(kw)
+    beams = None
+    if (cfg.get("num_beams") or 1) > 1:
+        if cfg.get("do_sample"):
+            raise NotImplementedError("beam-search multinomial sampling is not implemented on the gfx950 path (beam search, greedy and sampling are)")
+        if (cfg.get("num_return_sequences") or 1) != 1 or (cfg.get("num_beam_groups") or 1) != 1:
+            raise NotImplementedError("beam search returns the best hypothesis only (num_return_sequences = 1, no beam groups)")
+        beams = dict(num_beams=int(cfg["num_beams"]), length_penalty=float(cfg["length_penalty"]) if cfg.get("length_penalty") is not None else 1.0,
+                     early_stopping=cfg.get("early_stopping") if cfg.get("early_stopping") is not None else False)
+    processors = []       # HF's order (GenerationMixin._get_logits_processor): repetition penalty, then n-gram blocking
+    if cfg.get("repetition_penalty") not in (None, 1, 1.0):
+        processors.append(repetition_penalty(float(cfg["repetition_penalty"])))
+    if cfg.get("no_repeat_ngram_size") not in (None, 0):
+        processors.append(no_repeat_ngram(int(cfg["no_repeat_ngram_size"])))
+    sampler = None
+    if cfg.get("do_sample"):
+        sampler = dict(temperature=float(cfg["temperature"]) if cfg.get("temperature") is not None else 1.0,
+                       top_k=int(cfg["top_k"]) if cfg.get("top_k") is not None else 50,
+                       top_p=float(cfg["top_p"]) if cfg.get("top_p") is not None else 1.0, generator=cfg.get("generator"))
+        if sampler["temperature"] <= 0 or not (0 < sampler["top_p"] <= 1.0) or sampler["top_k"] < 0:
+            raise ValueError(f"bad sampling settings {sampler}")
+    eos = cfg.get("eos_token_id")
+    eos = [] if eos is None else ([int(eos)] if not isinstance(eos, (list, tuple)) else [int(e) for e in eos])
+    return int(cfg.get("max_new_tokens") or 20), eos, cfg.get("pad_token_id"), sampler, processors, beams
+
+
+def gen_flags(generation_config, kw, beams=None, cand=None, topk=0):
+    """HF's output flags (return_dict_in_generate, output_scores, output_logits) and return_logprobs from a generation config / kwargs
+    (generation.output_flags).  Beam search returns ``sequences_scores`` only: per-step scores, logits and log-probabilities of its
+    hypotheses are not implemented and raise."""
+    flags = output_flags(generation_config, kw)
+    if beams:
+        asked = [k for k in ("output_scores", "output_logits", "return_logprobs") if flags[k]] + (["candidate_ids"] if cand is not None else []) + \
+            (["top_logprobs"] if topk else [])
+        if asked:
+            raise NotImplementedError(f"beam search (num_beams > 1) returns sequences and sequences_scores only: {', '.join(asked)} "
+                                      "not implemented")
+    return flags
+
+
+def repetition_penalty(penalty: float):
+    """HF RepetitionPenaltyLogitsProcessor over the GENERATED tokens (the reference's generate() passes inputs_embeds, so HF's
+    input_ids start empty): the logit of every token already emitted is divided by ``penalty`` if positive, multiplied if negative."""
+    if penalty <= 0:
+        raise ValueError("repetition_penalty must be a strictly positive float")
+
+    def proc(hist: torch.Tensor, logits: torch.Tensor) -> torch.Tensor:
+        if hist.shape[1] == 0:
+            return logits
+        sc = logits.gather(1, hist)
+        sc = torch.where(sc < 0, sc * penalty, sc / penalty)
+        return logits.scatter(1, hist, sc)
+    return proc
+
+
+def no_repeat_ngram(n: int):
+    """HF NoRepeatNGramLogitsProcessor: a token that would complete an n-gram already present in the generated tokens gets -inf."""
+    if n <= 0:
+        raise ValueError("no_repeat_ngram_size must be a strictly positive integer")
+
+    def proc(hist: torch.Tensor, logits: torch.Tensor) -> torch.Tensor:
+        cur = hist.shape[1]
+        if cur + 1 < n:
+            return logits
+        rows = hist.tolist()          # host glue of generate(): a few dozen tokens per sequence
+        logits = logits.clone()
+        for b, seq in enumerate(rows):
+            prefix = tuple(seq[cur + 1 - n:cur])
+            banned = [seq[i + n - 1] for i in range(cur - n + 1) if tuple(seq[i:i + n - 1]) == prefix]
+            if banned:
+                logits[b, banned] = float("-inf")
+        return logits
+    return proc
+
+
+def sample(logits: torch.Tensor, temperature: float, top_k: int, top_p: float, generator=None) -> torch.Tensor:
+    """One multinomial draw per row after HF's logits warpers in HF's order (TemperatureLogitsWarper, TopKLogitsWarper,
+    TopPLogitsWarper with min_tokens_to_keep = 1; transformers/generation/logits_process.py).  Host-side glue of generate():
+    a handful of torch ops on [B, vocab], not part of the scoring hot path."""
+    return torch.multinomial(warp(logits, temperature, top_k, top_p).softmax(-1), 1, generator=generator).squeeze(1)
+
+
+def warp(logits: torch.Tensor, temperature: float, top_k: int, top_p: float) -> torch.Tensor:
+    """HF's three logits warpers in HF's order (pinned against transformers' own classes in tests/test_host.py)."""
+    x = logits / temperature if temperature != 1.0 else logits
+    if top_k > 0:
+        kth = torch.topk(x, min(top_k, x.shape[-1]))[0][..., -1, None]
+        x = x.masked_fill(x < kth, float("-inf"))
+    if top_p < 1.0:
+        srt, idx = torch.sort(x, descending=False)
+        remove = srt.softmax(-1).cumsum(-1) <= (1.0 - top_p)
+        remove[..., -1:] = False
+        x = x.masked_fill(remove.scatter(1, idx, remove), float("-inf"))
+    return x

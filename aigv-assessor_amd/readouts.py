@@ -1,0 +1,128 @@
+"""Which read-outs a scoring pass carries: label log-probs, candidate log-probs, top-k log-probs, score attention by segment and per token.
+
+This module is the one place that knows that decision.  A new read-out adds, HERE: a member to ``ReadOuts`` and its check to
+``ReadOuts.parse``; the element it appends to a graph's host key to ``ReadOuts.key_tail``; its keyword to ``forward_kwargs``; and - when it
+is laid out per label position like ``logit`` - a row of ``ROW_FIELDS``.  Elsewhere it adds only what computes it: the native call in
+``ScoringPass._read_rows`` (or the probe) and, for generate(), in ``Generation._decode_step``.  ``forward``, the graph key, the shared-prefix
+slices, ``dist_utils.score_clips_dp`` and ``eval_utils.batched`` follow from the record and the table.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Optional
+
+import torch
+
+MAX_CANDIDATES = 64      # = AIGV_MAX_CANDIDATES
+MAX_TOPK = 16            # = AIGV_MAX_TOPK
+
+
+def top_logprobs_k(top_logprobs, vocab: int, labels="given") -> int:
+    """``top_logprobs`` (None or an int k, 1 <= k <= min(16, vocab)) -> k, 0 for None."""
+    if top_logprobs is None:
+        return 0
+    if labels is None:
+        raise ValueError("top_logprobs: needs labels (they mark the answer rows whose distribution is read)")
+    k = top_logprobs
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_TOPK:
+        raise ValueError(f"top_logprobs: expected an int in 1..{MAX_TOPK}, got {k!r}")
+    if k > vocab:
+        raise ValueError(f"top_logprobs: k = {k} exceeds the vocabulary ({vocab} tokens)")
+    return k
+
+
+def candidates(candidate_ids, labels="given") -> Optional[torch.Tensor]:
+    """``candidate_ids`` (None, a list of ints or an integer tensor [C], on any device) -> None or a contiguous int64 tensor [C], 1 <= C <= 64.
+    The VALUES are not looked at (they may live on the device): an id outside the vocabulary gives a NaN column."""
+    if candidate_ids is None:
+        return None
+    if labels is None:
+        raise ValueError("candidate_ids: needs labels (they mark the answer rows whose distribution is read)")
+    t = candidate_ids if torch.is_tensor(candidate_ids) else torch.tensor([int(v) for v in candidate_ids], dtype=torch.long)
+    if t.dim() != 1 or t.is_floating_point() or t.dtype == torch.bool or not 1 <= t.numel() <= MAX_CANDIDATES:
+        raise ValueError(f"candidate_ids: expected 1..{MAX_CANDIDATES} integer token ids in one dimension, got "
+                         f"{tuple(t.shape)} {t.dtype}")
+    return t.to(torch.long).contiguous()
+
+
+_NAN = float("nan")
+# every result laid out per label position, [B (N - 1)] + width: name in the result dict, the ``ReadOuts`` member that switches it on and gives
+# its trailing width (None: always there), dtype, fill wherever the row is not an answer row
+ROW_FIELDS = (("logit", None, torch.long, -1),
+              ("logprob", "logprobs", torch.float32, _NAN),
+              ("cand_logprob", "cand", torch.float32, _NAN),
+              ("top_ids", "topk", torch.long, -1),
+              ("top_logprob", "topk", torch.float32, _NAN))
+
+
+@dataclass(frozen=True, eq=False)
+class ReadOuts:
+    """What one call asked for.  ``parse`` gives the checked form the model works with (``cand`` an int64 tensor, ``topk`` an int or None);
+    the loops that only pass the options on (``score_clips_dp``, ``batched``) fill ``logprobs`` / ``cand`` / ``topk`` in as they got them."""
+    logprobs: bool = False
+    cand: Optional[torch.Tensor] = None         # candidate_ids
+    topk: Optional[int] = None                  # top_logprobs=k
+    score_attention: bool = False               # (return_token_attention implies it)
+    segments: Optional[torch.Tensor] = None     # the user's attention_segments table; None: prompts.attention_segments
+    token_attention: bool = False
+
+    @classmethod
+    def parse(cls, vocab: int, labels="given", return_logprobs: bool = False, candidate_ids=None, top_logprobs: Optional[int] = None,
+              return_score_attention: bool = False, attention_segments=None, return_token_attention: bool = False) -> "ReadOuts":
+        """The record of a call's public keyword arguments, checked.  ``labels=None`` (``forward`` without labels) refuses candidates and top-k;
+        the shared-prefix and generate entry points leave the default.  A user segment table is checked where its bins are counted
+        (``n_segments``: it needs the shape of ``input_ids``)."""
+        cand = candidates(candidate_ids, labels)
+        k = top_logprobs_k(top_logprobs, vocab, labels)
+        att = bool(return_score_attention or return_token_attention)
+        return cls(bool(return_logprobs), cand, k or None, att, attention_segments if att else None, bool(return_token_attention))
+
+    @property
+    def wants_labels(self) -> bool:
+        """The lm-head read-outs, which need the pass's checked answer labels."""
+        return self.logprobs or self.cand is not None or bool(self.topk)
+
+    def n_segments(self, ids_shape) -> int:
+        """S of a user segment table (its largest id + 1; the table is checked first), 0 for the default table.  Reads the table's maximum
+        back from wherever it lives: never called inside a captured pass."""
+        t = self.segments
+        if t is None:
+            return 0
+        if not torch.is_tensor(t) or t.is_floating_point() or t.dtype == torch.bool or tuple(t.shape) != tuple(ids_shape):
+            raise ValueError(f"attention_segments: expected an integer tensor shaped like input_ids {tuple(ids_shape)}")
+        return int(t.max()) + 1
+
+    def key_tail(self, ids_shape, n_seg: Optional[int] = None) -> tuple:
+        """What the record appends to a graph's host key (``n_seg``: ``n_segments`` when the caller has it already).  Nothing for an option
+        that is off: the keys of passes without it are those they always were.  The candidates' VALUES and a user segment table are graph
+        INPUT, not key; the candidates' number is in the key with the device inputs' shapes.  k, a user table's bin count (the default
+        table follows from the ids, which are in the key) and ld_tok = N are output shapes: another value is another graph."""
+        S = (self.n_segments(ids_shape) if n_seg is None else n_seg) if self.score_attention else 0
+        on = ((self.logprobs, "logprobs"), (self.cand is not None, "candidates"), (self.topk is not None, ("top_logprobs", self.topk)),
+              (self.score_attention, ("score_attention", S)), (self.token_attention, ("score_attention_tokens", int(ids_shape[1]))))
+        return tuple(element for yes, element in on if yes)
+
+    def row_fields(self):
+        """[(name, trailing shape, dtype, fill)] of the ``ROW_FIELDS`` this record switches on."""
+        n_cand = 0 if self.cand is None else int(self.cand.numel() if torch.is_tensor(self.cand) else len(self.cand))
+        width = {None: (), "logprobs": () if self.logprobs else None, "cand": None if self.cand is None else (n_cand,),
+                 "topk": None if self.topk is None else (int(self.topk),)}
+        return [(name, width[m], dt, fill) for name, m, dt, fill in ROW_FIELDS if width[m] is not None]
+
+
+def forward_kwargs(r: ReadOuts) -> dict:
+    """The record as keyword arguments of ``forward``.  An option that is off is NOT passed: callers hand these to any object with
+    ``forward``'s call form, which need not know the options it is not asked for."""
+    kw = dict(return_logprobs=r.logprobs or None, candidate_ids=r.cand, top_logprobs=r.topk, return_score_attention=r.score_attention or None,
+              attention_segments=r.segments, return_token_attention=r.token_attention or None)
+    return {k: v for k, v in kw.items() if v is not None}
+
+
+def ce_loss(logprob: torch.Tensor, labels: torch.Tensor, to_device=None) -> torch.Tensor:
+    """The reference's ``CrossEntropyLoss()``: the mean of ``-logprob`` over the non-ignored ``labels`` (both [B (N - 1)]; labels on the
+    host), in fp64, rounded once; NaN when there are none.  ``to_device``: how the host index list goes up (default ``.to``)."""
+    scored = (labels.reshape(-1) != -100).nonzero().flatten()      # (host: no sync)
+    if not scored.numel():
+        return torch.full((), _NAN, dtype=torch.float32, device=logprob.device)
+    scored = to_device(scored) if to_device is not None else scored.to(logprob.device)
+    return (-logprob.index_select(0, scored)).double().mean().float()

@@ -1,0 +1,694 @@
+"""The scoring pass of ``InternVLChatModel``: the visual front, pass planning, prefill, the score-attention probe, ``forward`` and the shared-prefix pass."""
+from __future__ import annotations
+
+import ctypes as C
+from itertools import accumulate
+from typing import List, Optional
+
+import torch
+import torch.nn.functional as F
+
+from . import native, readouts
+
+
+# ------------------------------------------------------------------------------------------------------
+class VisualAhead:
+    """The visual front of a LATER ``forward`` call, started ahead of time by ``InternVLChatModel.prefetch``: pre-projector tokens
+    [F, ntok, 4 Hv], the SlowFast feature of the clips (or None) and the event the consuming stream waits for.  Pass it as ``pixel_values``."""
+    __slots__ = ("tokens", "motion", "event", "n_clips")
+
+    def __init__(self, tokens, motion, event, n_clips):
+        self.tokens, self.motion, self.event, self.n_clips = tokens, motion, event, n_clips
+
+
+class ScoringPass:
+    # ---- hot path -----------------------------------------------------------------------------------------
+    def ingest_frames(self, frames_u8, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225),
+                      size: Optional[int] = None) -> torch.Tensor:
+        """uint8 [F, H, W, 3] RGB frames (one tensor, or a list of per-clip tensors) -> normalised bf16 NCHW ``pixel_values`` on the GPU: the reference's per-frame
+        ``image.resize((448, 448))`` (PIL BICUBIC; dataset.py:702-738 with max_num = 1, stage2_eval.py:453-456) when the
+        frames are not at the model resolution yet, then ToTensor + Normalize + the bf16 cast of its eval transform
+        (dataset.py:267-274, stage2_eval.py:932).  The resize is bit-exact with Pillow (include/aigv_amd.h)."""
+        parts = list(frames_u8) if isinstance(frames_u8, (list, tuple)) else [frames_u8]
+        for t in parts:
+            if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[-1] != 3 or t.shape[1:] != parts[0].shape[1:]:
+                raise ValueError("frames must be uint8 [F, H, W, 3] (or a list of such tensors of one frame size)")
+        lib = native.load()
+        if self.device.type != "cuda":
+            raise native.NativeError("the scorer hot path runs on an MI355X only (no CPU fallback)")
+        S = int(size or self.config.image_size)
+        # (pinned host frames go up without blocking the host: the copy is ordered on the current stream like the kernels that read it.  A list -
+        # the clips of one group, each in its own host buffer - is copied clip by clip and joined on the device: no host-side concatenation)
+        parts = [t.to(self.device, non_blocking=not t.is_cuda and t.is_pinned()) for t in parts]
+        f = (torch.cat(parts) if len(parts) > 1 else parts[0]).contiguous()
+        n, h, w, _ = f.shape
+        out = torch.empty((n, 3, S, S), dtype=torch.bfloat16, device=self.device)
+        m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+        if (h, w) == (S, S):
+            native.check(lib.aigv_op_frame_ingest(f.data_ptr(), n, h, w, m3, s3, out.data_ptr(), native.stream_ptr()))
+        else:
+            tmp = torch.empty(n * h * S * 3, dtype=torch.uint8, device=self.device)
+            native.check(lib.aigv_op_frame_resize_ingest(f.data_ptr(), n, h, w, S, S, m3, s3, tmp.data_ptr(), None, out.data_ptr(),
+                                                         native.stream_ptr()))
+        return out
+
+    def vit_tokens(self, pixel_values: torch.Tensor) -> torch.Tensor:
+        """InternViT -> drop cls -> pixel-shuffle: [F,3,S,S] -> [F, ntok, 4*Hv] pre-projector tokens (the
+        frame-DP all-gather payload; modeling_internvl_chat.py:509-527)."""
+        if pixel_values.dim() != 4:
+            raise ValueError(f"wrong pixel_values size: {pixel_values.shape}")  # modeling_intern_vit.py:345
+        nf = pixel_values.shape[0]
+        S = self.config.image_size
+        if tuple(pixel_values.shape[1:]) != (self.config.vision_config.num_channels, S, S):
+            raise ValueError(f"pixel_values must be [F,{self.config.vision_config.num_channels},{S},{S}], got {tuple(pixel_values.shape)}")
+        lib, ctx = self._native(n_frames=nf)
+        self._wait_for_prefetch()
+        pv = pixel_values.to(device=self.device, dtype=torch.bfloat16).contiguous()
+        out = torch.empty((nf, self.num_image_token, self.config.proj_in), dtype=torch.bfloat16, device=self.device)
+        native.check(lib.aigv_vit_forward(ctx, pv.data_ptr(), nf, out.data_ptr(), native.stream_ptr()), ctx)
+        return out
+
+    def _take_ahead(self, pixel_values, visual_tokens, motion_feature):
+        """``pixel_values`` may be the handle of a visual front started ahead of time (``prefetch``): wait for it on the caller's stream and continue
+        from its tokens / SlowFast feature; a plain ``pixel_values`` first waits for any prefetch in flight (one visual front at a time)."""
+        if isinstance(pixel_values, VisualAhead):
+            torch.cuda.current_stream(self.device).wait_event(pixel_values.event)
+            return None, pixel_values.tokens, pixel_values.motion if motion_feature is None else motion_feature
+        if pixel_values is not None:
+            self._wait_for_prefetch()
+        return pixel_values, visual_tokens, motion_feature
+
+    def _wait_for_prefetch(self):
+        """The InternViT workspaces of the context serve ONE visual front at a time: a pass that runs the ViT on the caller's stream (eager or
+        as a replayed graph) first waits for whatever ``prefetch`` still has in flight on its own stream."""
+        if self._capture_keep is not None:
+            return      # inside a graph capture: the caller (forward / dp_front) already waited before _graph_call; an event recorded on a
+                        # non-capturing stream must not be waited on from the capture stream
+        look = getattr(self, "_look_stream", None)
+        cur = torch.cuda.current_stream(self.device)
+        if look is not None and cur != look:
+            cur.wait_stream(look)
+
+    def project(self, tokens: torch.Tensor) -> torch.Tensor:
+        """mlp1 on pre-projector tokens [..., 4*Hv] -> [..., H] (modeling_internvl_chat.py:529)."""
+        lib, ctx = self._native()
+        t = tokens.to(device=self.device, dtype=torch.bfloat16).contiguous()
+        rows = t.numel() // t.shape[-1]
+        out = torch.empty(t.shape[:-1] + (self.config.llm_config.hidden_size,), dtype=torch.bfloat16, device=self.device)
+        native.check(lib.aigv_project(ctx, t.data_ptr(), rows, out.data_ptr(), native.stream_ptr()), ctx)
+        return out
+
+    def extract_feature(self, pixel_values: torch.Tensor) -> torch.Tensor:
+        """modeling_internvl_chat.py:508-531: [F,3,S,S] -> [F, num_image_token, llm_hidden]."""
+        return self.project(self.vit_tokens(pixel_values))
+
+    def motion_embed(self, motion_feature: torch.Tensor) -> torch.Tensor:
+        """motion_mlp on the SlowFast feature [B, motion_dim] -> [B, H] (modeling_internvl_chat.py:344-345)."""
+        b = motion_feature.shape[0]
+        self._join_side_stream()
+        lib, ctx = self._native(n_clips=b)
+        m = motion_feature.reshape(b, -1).to(device=self.device, dtype=torch.bfloat16).contiguous()
+        if m.shape[1] != self.config.motion_dim:
+            raise ValueError(f"motion_feature must be [B,{self.config.motion_dim}]")
+        out = torch.empty((b, self.config.llm_config.hidden_size), dtype=torch.bfloat16, device=self.device)
+        native.check(lib.aigv_motion_project(ctx, m.data_ptr(), b, out.data_ptr(), native.stream_ptr()), ctx)
+        return out
+
+    def motion_feature(self, pixel_values: torch.Tensor, batch: int) -> torch.Tensor:
+        """SlowFast feature [batch, motion_dim] of the clips in ``pixel_values`` [batch * T, 3, S, S] (modeling_internvl_chat.py:336-343)."""
+        out = self._motion_feature(pixel_values, batch, None)
+        self._join_side_stream()
+        return out
+
+    def motion_feature_async(self, pixel_values: torch.Tensor, batch: int) -> torch.Tensor:
+        """The same, without joining the side stream: the tensor is only safe to consume through ``forward(motion_feature=...)`` /
+        ``motion_embed``, which join it (used by the data-parallel scorer to start the branch before its ViT shard)."""
+        return self._motion_feature(pixel_values, batch, None)
+
+    def _join_side_stream(self):
+        if getattr(self, "_side_pending", False):
+            torch.cuda.current_stream().wait_stream(self._side_stream)
+            self._side_pending = False
+
+    def _motion_feature(self, pixel_values, batch, motion_feature):
+        if motion_feature is not None:
+            return motion_feature
+        if self.slowfast_model is None:
+            raise RuntimeError("the SlowFast motion branch is an input of this path: pass motion_feature=[B, "
+                               f"{self.config.motion_dim}] or set model.slowfast_model (SURVEY.md §2 row 6)")
+        if hasattr(self.slowfast_model, "features"):     # the native branch reads pixel_values as they are and samples the slow pathway itself
+            pv = pixel_values.to(self.device)
+            if not getattr(self, "overlap_motion_branch", True):
+                return self.slowfast_model.features(pv, batch)
+            # The branch depends on the frames only and its result is needed after ViT + projector: enqueue it on a side stream so that its
+            # low-occupancy kernels (the slow pathway's deep layers run ~100 workgroups) fill in around the ViT's; motion_embed() joins.
+            cur = torch.cuda.current_stream()
+            side = getattr(self, "_side_stream", None)
+            if side is None:
+                side = self._side_stream = torch.cuda.Stream(device=self.device)
+            side.wait_stream(cur)
+            with torch.cuda.stream(side):
+                feat = self.slowfast_model.features(pv, batch)
+            feat.record_stream(cur)
+            pv.record_stream(side)
+            self._side_pending = True
+            return feat
+        # a user-supplied callable: reference data flow (modeling_internvl_chat.py:337-344, pack_pathway_output :97-133)
+        S = self.config.image_size
+        frames = pixel_values.view(batch, pixel_values.shape[0] // batch, 3, S, S).permute(0, 2, 1, 3, 4)
+        idx = torch.linspace(0, frames.shape[2] - 1, frames.shape[2] // 4).long().to(frames.device)
+        with torch.no_grad():
+            return self.slowfast_model([frames.index_select(2, idx), frames]).view(batch, -1)
+
+    @staticmethod
+    def _pack(input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor]):
+        """Strip padding: returns (packed ids [T], cu_seqlens list, packed-row index of every [b, p] or -1)."""
+        b, n = input_ids.shape
+        mask = torch.ones_like(input_ids, dtype=torch.bool) if attention_mask is None else attention_mask.bool()
+        lens = mask.sum(1).tolist()
+        cu = list(accumulate((int(x) for x in lens), initial=0))
+        row_of = torch.full((b, n), -1, dtype=torch.long, device=input_ids.device)
+        row_of[mask] = torch.arange(cu[-1], device=input_ids.device)
+        return input_ids[mask].contiguous(), cu, row_of
+
+    def _h2d(self, t):
+        """Host tensor -> device through pinned memory without blocking the host.  While a HIP graph is being captured (``capture_forward``)
+        the pinned staging buffer is kept alive with the graph: its replays copy from that very address."""
+        if t.is_cuda:
+            return t
+        pinned = t.contiguous().pin_memory()
+        keep = getattr(self, "_capture_keep", None)
+        if keep is not None:
+            keep.append(pinned)
+        return pinned.to(self.device, non_blocking=True)
+
+    def _prefill(self, ids_packed, slot, cu, vis, n_vis, motion, score_rows, logit_rows, keep_kv=False, kv_cap=0, probe=None, ld_tok=0):
+        b = len(cu) - 1
+        T = cu[-1]
+        lib, ctx = self._native(n_tokens=T, n_clips=b, out_rows=len(logit_rows), kv_cap=kv_cap)
+        dev = self.device
+        def up(t, dt):   # host index arrays go up through pinned memory without blocking the host
+            return self._h2d(t.to(dt).contiguous())
+        ids_d = up(ids_packed, torch.long)
+        slot_d = up(slot, torch.int32)
+        score = torch.empty(b, dtype=torch.float32, device=dev) if score_rows is not None else None
+        amax = torch.empty(max(len(logit_rows), 1), dtype=torch.long, device=dev)
+        cu_a = native.i32_array(cu)
+        sr_a = native.i32_array(score_rows) if score_rows is not None else None
+        lr_a = native.i32_array(logit_rows) if len(logit_rows) else None
+        att, tok = self._arm_score_attention(probe, ld_tok) if probe is not None else (None, None)   # (armed for exactly the pass below)
+        native.check(lib.aigv_llm_prefill(
+            ctx, ids_d.data_ptr(), slot_d.data_ptr(), cu_a, b, native.ptr(vis), n_vis, native.ptr(motion),
+            sr_a, native.ptr(score), lr_a, len(logit_rows), amax.data_ptr(), int(keep_kv), native.stream_ptr()), ctx)
+        if probe is not None:
+            return score, amax[: len(logit_rows)], att, tok
+        return score, amax[: len(logit_rows)]
+
+    # ---- score-row attention by segment (return_score_attention) -------------------------------------------------------------------------
+    MAX_ATTN_SEGMENTS = 64   # = AIGV_MAX_ATTN_SEGMENTS
+    MAX_PROBE_ROWS = 64      # = AIGV_MAX_PROBE_ROWS
+
+    def _probe_rows(self, plan) -> List[int]:
+        """The packed row of every clip whose attention is reported: the score row (stage 2), else the row that predicts the clip's first
+        answer token."""
+        if plan["score_rows"] is not None:
+            return [int(r) for r in plan["score_rows"]]
+        rows = []
+        answer = (plan["labels_h"][:, 1:] != -100) & (plan["row_of"][:, :-1] >= 0)
+        for b in range(answer.shape[0]):
+            at = answer[b].nonzero().flatten()
+            if not at.numel():
+                raise ValueError(f"return_score_attention: clip {b} has no answer token (a stage-1 model reports the row that predicts the first one: pass labels)")
+            rows.append(int(plan["row_of"][b, int(at[0])]))
+        return rows
+
+    def _frames_per_clip(self, plan) -> List[int]:
+        """The frames every clip of the plan carries: its visual-token slots over the tokens per frame."""
+        slot, cu = plan["slot"], plan["cu"]
+        return [int(((slot[cu[b]:cu[b + 1]] >= 0) & (slot[cu[b]:cu[b + 1]] < plan["n_vis"])).sum()) // self.num_image_token for b in range(len(cu) - 1)]
+
+    def _default_segments(self, plan):
+        """(``prompts.attention_segments`` of the plan's packed tokens, host int32 [T]; the number of bins F + 4)."""
+        from . import prompts
+        frames = self._frames_per_clip(plan)
+        return prompts.attention_segments(plan["slot"], plan["cu"], frames, self.num_image_token), max(frames) + prompts.N_TEXT_SEGMENTS
+
+    def _score_attention_probe(self, plan, input_ids, ro):
+        """What ``_prefill`` arms the pass with: (probe rows, device int32 segment id per packed token, S).  ``ro.segments``: None -
+        ``prompts.attention_segments`` - or the user's own table, an integer tensor laid out like ``input_ids`` [B, N] (on any device; padded
+        positions are ignored, ids outside [0, S) drop their key from the bins), S = its largest id + 1."""
+        rows = self._probe_rows(plan)
+        if len(rows) > self.MAX_PROBE_ROWS:
+            raise ValueError(f"return_score_attention: at most {self.MAX_PROBE_ROWS} clips per pass, got {len(rows)}")
+        if ro.segments is None:
+            seg, S = self._default_segments(plan)
+            seg_d = self._h2d(seg)
+        else:
+            t = ro.segments
+            S = getattr(self, "_probe_n_segments", None) or ro.n_segments(input_ids.shape)     # (a replayed graph carries S in its key: no sync in there)
+            kept = (plan["row_of"] >= 0).flatten().nonzero().flatten()          # [b, p] of every packed row, in packed order (host)
+            seg_d = t.to(self.device).flatten().index_select(0, self._h2d(kept)).to(torch.int32).contiguous()
+        if not 1 <= S <= self.MAX_ATTN_SEGMENTS:
+            raise ValueError(f"return_score_attention: {S} segments, outside 1..{self.MAX_ATTN_SEGMENTS}")
+        return rows, seg_d, None, 0, S
+
+    def visual_token_positions(self, input_ids, attention_mask=None, image_flags=None, n_frames: Optional[int] = None) -> torch.Tensor:
+        """``prompts.visual_token_positions`` of a batch as ``forward`` would pack it (host only, no GPU work): long [B, F, tokens_per_frame], the
+        column of ``score_attention_tokens[b]`` that holds every visual token of every frame, -1 where a clip has fewer frames than the
+        longest.  ``n_frames``: the frames handed to ``forward`` (``pixel_values.shape[0]``; default: ``image_flags.shape[0]``)."""
+        from . import prompts
+        if n_frames is None:
+            if image_flags is None:
+                raise ValueError("visual_token_positions: pass n_frames or image_flags")
+            n_frames = int(image_flags.shape[0])
+        plan = self._plan(input_ids, attention_mask, None, image_flags, int(n_frames))
+        return prompts.visual_token_positions(plan["slot"], plan["cu"], self._frames_per_clip(plan), self.num_image_token)
+
+    def _arm_score_attention(self, probe, ld_tok: int = 0):
+        """Arm the context's NEXT prefill / continuation pass; returns (att, tok): the fp32 tensor [rows, L, n_heads, S] the pass fills
+        (aigv_score_attention_arm) and - ``ld_tok`` > 0, ``return_token_attention``: aigv_score_attention_arm_tokens - the dense rows [rows, L,
+        n_heads, ld_tok] the same pass fills, else None."""
+        rows, seg_new, seg_cached, ld_cached, S = probe
+        llm = self.config.llm_config
+        att = torch.empty((len(rows), llm.num_hidden_layers, llm.num_attention_heads, S), dtype=torch.float32, device=self.device)
+        lib, tok = native.load(), None
+        args = (self._ctx, native.i32_array(rows), len(rows), seg_new.data_ptr(), native.ptr(seg_cached), int(ld_cached), int(S), att.data_ptr())
+        if ld_tok:
+            tok = torch.empty((len(rows), llm.num_hidden_layers, llm.num_attention_heads, int(ld_tok)), dtype=torch.float32, device=self.device)
+            native.check(lib.aigv_score_attention_arm_tokens(*args, tok.data_ptr(), int(ld_tok)), self._ctx)
+        else:
+            native.check(lib.aigv_score_attention_arm(*args), self._ctx)
+        return att, tok
+
+    def forward(self, mos: Optional[torch.Tensor] = None, pixel_values: Optional[torch.Tensor] = None,
+                input_ids: Optional[torch.Tensor] = None, attention_mask: Optional[torch.Tensor] = None,
+                position_ids=None, image_flags: Optional[torch.Tensor] = None, past_key_values=None,
+                labels: Optional[torch.Tensor] = None, use_cache=None, output_attentions=None,
+                output_hidden_states=None, return_dict=None, motion_feature: Optional[torch.Tensor] = None,
+                visual_tokens: Optional[torch.Tensor] = None, full_logits: bool = False, return_logprobs: bool = False,
+                candidate_ids=None, top_logprobs: Optional[int] = None, return_score_attention: bool = False, attention_segments=None,
+                return_token_attention: bool = False):
+        """Stage-2 eval pass (modeling_internvl_chat.py:306-488) or, with ``stage=1``, the stage-1 pass
+        (internvl_chat_eval1/modeling_internvl_chat.py:250-366).  ``visual_tokens`` optionally supplies
+        already all-gathered pre-projector tokens (frame-DP) instead of ``pixel_values``.
+
+        ``return_logprobs=True`` adds ``logprob`` (fp32 [B (N - 1)], laid out like ``label`` / ``logit``: log_softmax of the fp32-upcast
+        bf16 logits at the shifted label, NaN wherever the label is -100) and ``ce_loss`` (fp32 0-dim: the reference's
+        ``CrossEntropyLoss()(shift_logits, shift_labels)``, modeling_internvl_chat.py:452-463 - the mean over the non-ignored labels of the
+        batch, NaN when there are none).  Labels must then be -100 or lie in [0, vocab), and no such label may follow a padded position
+        (the reference would score the padded row itself): ValueError otherwise.  ``loss`` (stage 2: L1 against ``mos``) is unchanged.
+
+        ``candidate_ids`` (LongTensor [C] or list, 1 <= C <= 64 token ids - ``prompts.level_token_ids``) adds ``cand_logprob`` (fp32
+        [B (N - 1), C], rows laid out like ``logit`` / ``logprob``, NaN rows wherever the label is -100): column c is the FULL-vocabulary
+        ``log_softmax(logits.float())[candidate_ids[c]]`` - bit for bit the ``logprob`` the pass gives with ``candidate_ids[c]`` as that
+        row's label - so ``softmax(cand_logprob, -1)`` is the closed-set distribution over the candidates and
+        ``eval_utils.expected_level`` its mean level, from ONE pass.  An id outside [0, vocab) gives a NaN column.  Needs ``labels`` (they
+        say which rows are answer rows) under ``return_logprobs``' label rules, with or without ``return_logprobs``.  The ids are a device
+        input of a replayed graph: other VALUES replay the same graph, another C is another graph.  fp8 mode: the lm-head stays bf16
+        there, so the same kernels serve.
+
+        ``top_logprobs=k`` (int, 1 <= k <= 16) adds what the model preferred at every answer row: ``top_ids`` (int64 [B (N - 1), k], -1
+        rows wherever the label is -100) - the ids of the k largest bf16 logits, equal logits by ascending id, i.e. the first k of
+        ``torch.sort(logits.float(), descending=True, stable=True)``; column 0 is ``logit`` - and ``top_logprob`` (fp32, same shape, NaN
+        rows there): their full-vocabulary log-probabilities, bit for bit what ``candidate_ids=top_ids[row]`` gives.  Needs ``labels``
+        under ``return_logprobs``' label rules.  The three options combine freely and none changes another's bits; under graph replay k
+        is part of the graph's key (it is an output shape).
+
+        ``return_score_attention=True`` adds ``score_attention`` (fp32 [B, L, n_heads, S]): where the clip's score row - ``hidden[:, -4]``;
+        in a stage-1 model, which has no score head, the row that predicts the first answer token - looks in every layer and head, as the
+        softmax mass it puts on each of S key segments.  Default segments (``prompts.attention_segments``, S = F + 4): frame 0 .. F - 1 |
+        motion token | first token (the sink) | text up to the last visual token | text after it; a row's S values sum to 1.  Or pass
+        ``attention_segments=`` (integer tensor like ``input_ids``; S = largest id + 1 <= 64; an id outside [0, S) drops its key from the
+        bins but not from the softmax).  What the reference reads from ``output_attentions=True`` on its eager attention, here from a
+        small stand-alone kernel per layer that recomputes that one row's softmax in fp32 from the layer's Q and K (the flash kernels
+        never form a probability matrix): no other output of the pass changes a bit, and the option combines freely with the
+        log-probability options.  ``eval_utils.frame_saliency`` folds it to [B, F].  Under graph replay the flag (and S) is part of the
+        graph's key, a user table is a graph input, the tensor a graph output.
+
+        ``return_token_attention=True`` (implies ``return_score_attention``) also adds ``score_attention_tokens`` (fp32 [B, L, n_heads, N], N =
+        ``input_ids.shape[1]``): the same row's softmax per KEY, from the same launch per layer - column j is the clip's j-th un-masked token
+        (``input_ids[b, j]`` for the collator's right-padded inputs), the columns behind the score row and the padding are 0.  The values
+        share the bins' scores, total and division (a bin of one key holds that key's bits); ``score_attention`` and every other output
+        keep their bits.  ``prompts.visual_token_positions`` + ``eval_utils.frame_heatmaps`` fold it to a 16 x 16 map per frame.  Under
+        graph replay the flag and N are part of the graph's key; the tensor is handed back as a copy."""
+        if position_ids is not None or past_key_values is not None:
+            raise NotImplementedError("the eval pass takes default positions and no cache, like the reference drivers")
+        if self.img_context_token_id is None:
+            raise AssertionError("img_context_token_id must be set by the caller (stage2_eval.py:810)")
+        pixel_values, visual_tokens, motion_feature = self._take_ahead(pixel_values, visual_tokens, motion_feature)
+        parse = lambda: readouts.ReadOuts.parse(self.config.llm_config.vocab_size, labels, return_logprobs, candidate_ids, top_logprobs,
+                                                return_score_attention, attention_segments, return_token_attention)
+        ro = None
+        if self._graph_replay_enabled and self._capture_keep is None:
+            ro = parse()
+            out = self._forward_through_graph(mos, pixel_values, input_ids, attention_mask, image_flags, labels, motion_feature, visual_tokens, full_logits, ro)
+            if out is not None:
+                return out
+        B, N = input_ids.shape
+        n_frames = visual_tokens.shape[0] if visual_tokens is not None else pixel_values.shape[0]
+        # ---- index bookkeeping first, on the host (one small D2H copy if the ids live on the device), so that
+        # every kernel of the step can then be enqueued back to back without a host sync in between ----
+        plan = self._plan(input_ids, attention_mask, labels, image_flags, n_frames, full_logits)
+        ro = ro or parse()      # (once per call; on the eager path behind the plan's own checks, where the options have always been checked)
+        lp_labels = self._logprob_labels(plan) if ro.wants_labels else None
+        motion_feature = self._motion_feature(pixel_values, B, motion_feature)
+
+        # ---- device work: ViT -> projector -> motion projector -> LLM pass + heads ----
+        self._native(n_frames=n_frames, n_tokens=plan["cu"][-1], n_clips=B, out_rows=len(plan["logit_rows"]), seq_len=N)   # size workspaces once
+        vit_embeds, motion = self._visual_inputs(pixel_values, visual_tokens, motion_feature, plan)
+        probe = self._score_attention_probe(plan, input_ids, ro) if ro.score_attention else None
+        score, amax, *armed = self._prefill(plan["ids_packed"], plan["slot"], plan["cu"], vit_embeds, plan["n_vis"], motion,
+                                            plan["score_rows"], plan["logit_rows"], probe=probe, ld_tok=N if ro.token_attention else 0)
+        att, tok = armed or (None, None)        # (_prefill hands the probe's tensors back only when it armed one)
+        reads = self._read_rows(B if score is not None else 0, len(plan["logit_rows"]), ro, lp_labels)
+        return self._outputs(plan, B, N, score, amax, mos, reads, att, tok)
+
+    def dp_front(self, frames_local: torch.Tensor, frames_clips: Optional[torch.Tensor], n_clips: int):
+        """The data-parallel scorer's front half on this rank (dist_utils.score_clips_dp): the SlowFast feature of its own clips (side
+        stream) beside the InternViT tokens of its frame shard -> (tokens [F_local, ntok, 4 Hv], motion feature [n_clips, motion_dim] or
+        None).  With graph replay enabled the two run as ONE captured graph (joined at its end); the token all-gather and the projector +
+        InternLM2 half (``forward(visual_tokens=...)``, a graph of its own) follow on the host's side of the collective."""
+        self._wait_for_prefetch()
+
+        def fn(fl, fc):
+            mf = self._motion_feature(fc, n_clips, None) if fc is not None else None
+            tok = self.vit_tokens(fl)
+            self._join_side_stream()
+            return tok, mf
+        if (self._graph_replay_enabled and self._capture_keep is None and frames_local.is_cuda and not self._dirty and self._ctx is not None
+                and not getattr(self, "_prof_on", False) and (frames_clips is None or (frames_clips.is_cuda and hasattr(self.slowfast_model, "features")))):
+            self._prepare_motion_branch(frames_clips, int(n_clips))
+            out = self._graph_call(("dp_front", int(n_clips), self._branch_uid(), bool(getattr(self, "overlap_motion_branch", True))),
+                                   [frames_local, frames_clips], fn, clone_outputs=False)
+            if out is not None:
+                return out
+        if frames_clips is None:
+            return self.vit_tokens(frames_local), None
+        mf = self.motion_feature_async(frames_clips, n_clips)       # eager: joined where forward() consumes it
+        return self.vit_tokens(frames_local), mf
+
+    def prefetch(self, pixel_values: Optional[torch.Tensor] = None, frames_u8: Optional[torch.Tensor] = None, n_clips: int = 1) -> VisualAhead:
+        """Start the visual front of a LATER ``forward`` call NOW, on a stream of its own: frame ingest (when ``frames_u8`` [F, H, W, 3] is
+        given: H2D copy + Pillow-exact resize + normalise), InternViT + pixel-shuffle, and the SlowFast branch of the ``n_clips`` clips -
+        everything that depends on the frames only.  The returned handle is passed to ``forward`` as ``pixel_values``; that call waits for
+        the handle's event and runs projector + InternLM2 + heads.  In an eval loop that scores one clip per call (stage2_eval.py:908-941)
+        the next clip's visual front then runs BESIDE the current clip's InternLM2 pass, whose wo / w2 launches leave half the CUs idle at
+        one clip (``eval_utils.lookahead`` wraps a loop that way).  Same kernels, same bits as the plain call; the InternViT workspaces of
+        the context serve one visual front at a time, so a prefetch waits for the previous one.  (HIP deals a process's streams round-robin onto a
+        few hardware queues: should the prefetch stream land on the queue of the caller's stream, the two serialise and the loop runs at the plain
+        loop's speed - with the same results.)"""
+        if (pixel_values is None) == (frames_u8 is None):
+            raise ValueError("prefetch takes pixel_values or frames_u8")
+        cur = torch.cuda.current_stream(self.device)
+        look = getattr(self, "_look_stream", None)
+        if look is None:
+            look = self._look_stream = torch.cuda.Stream(device=self.device)
+        look.wait_stream(cur)                       # inputs produced on the caller's stream; the previous prefetch is ordered by the stream itself
+        with torch.cuda.stream(look):
+            pv = self.ingest_frames(frames_u8) if frames_u8 is not None else pixel_values.to(device=self.device, dtype=torch.bfloat16)
+            need_motion = self.slowfast_model is not None and hasattr(self.slowfast_model, "features")
+            tok, mf = self.dp_front(pv, pv if need_motion else None, n_clips)
+            self._join_side_stream()                # (the eager SlowFast branch forks from and joins back into this stream)
+            tok = tok.clone()                       # (a replayed graph hands out its own output buffers: the next prefetch overwrites them)
+            mf = None if mf is None else mf.clone()
+            ev = torch.cuda.Event()
+            ev.record(look)
+        for t in ([pixel_values] + (list(frames_u8) if isinstance(frames_u8, (list, tuple)) else [frames_u8])):
+            if t is not None and t.is_cuda:
+                t.record_stream(look)
+        tok.record_stream(cur)
+        if mf is not None:
+            mf.record_stream(cur)
+        return VisualAhead(tok, mf, ev, n_clips)
+
+    def _plan(self, input_ids, attention_mask, labels, image_flags, n_frames, full_logits=False, drop_dead_tail=None):
+        """Host-side token bookkeeping of one pass: packed ids, which packed row takes which visual / motion token
+        (modeling_internvl_chat.py:351-378), and the rows whose outputs are consumed."""
+        B, N = input_ids.shape
+        ids_h = input_ids.detach().to("cpu")
+        mask_h = attention_mask.detach().to("cpu") if attention_mask is not None else None
+        labels_h = labels.detach().to("cpu") if labels is not None else torch.full_like(ids_h, -100)
+        flags_h = image_flags.detach().to("cpu").squeeze(-1) if image_flags is not None else None
+        ids_packed, cu, row_of = self._pack(ids_h, mask_h)
+        lens = [cu[i + 1] - cu[i] for i in range(B)]
+        sel = ids_packed == self.img_context_token_id
+        seq_of = torch.repeat_interleave(torch.arange(B), torch.tensor(lens))
+        # last <IMG_CONTEXT> of each clip <- motion token; the others, in order <- visual tokens (:351-378)
+        pos_idx = torch.arange(ids_packed.numel())
+        last_pos = torch.full((B,), -1, dtype=torch.long)
+        last_pos.scatter_reduce_(0, seq_of[sel], pos_idx[sel], reduce="amax")
+        if bool((last_pos < 0).any()):
+            raise ValueError("every clip needs at least one <IMG_CONTEXT> token")
+        is_motion = torch.zeros_like(sel)
+        is_motion[last_pos] = True
+        vis_sel = sel & ~is_motion
+        keep = torch.arange(n_frames) if flags_h is None else (flags_h == 1).nonzero().flatten()
+        n_vis = int(keep.numel()) * self.num_image_token
+        if int(vis_sel.sum()) != n_vis:
+            raise ValueError(f"visual token count mismatch: {int(vis_sel.sum())} <IMG_CONTEXT> slots vs {n_vis} visual tokens")
+        slot = torch.full_like(ids_packed, -1, dtype=torch.int32)
+        slot[vis_sel] = torch.arange(n_vis, dtype=torch.int32)
+        slot[is_motion] = n_vis + seq_of[is_motion].to(torch.int32)
+        # rows whose next-token argmax is consumed: shifted positions p with labels[p+1] != -100
+        if full_logits:
+            want = row_of[:, :-1] >= 0
+        else:
+            want = (labels_h[:, 1:] != -100) & (row_of[:, :-1] >= 0)
+        logit_rows = row_of[:, :-1][want].tolist()
+        score_rows = [cu[i + 1] - 4 for i in range(B)] if self.stage == 2 else None
+        if score_rows is not None and min(lens) < 4:
+            raise ValueError("clips need at least 4 tokens for the score row hidden[:, -4]")
+        # Dead trailing tokens: with causal attention a token influences only later rows, so whatever follows a clip's last
+        # consumed row (the closing <|im_end|>, whose own logits the reference drops with shift_logits = logits[:, :-1],
+        # modeling_internvl_chat.py:451-455) changes no returned value.  Such text tokens are not run at all - for the
+        # canonical clip 2177 -> 2176 = 17 x 128 rows, which also removes the ragged row tile / query block of every kernel.
+        if drop_dead_tail is None:
+            drop_dead_tail = getattr(self, "drop_dead_tail", True)
+        if drop_dead_tail and not full_logits:
+            last_needed = [cu[b] for b in range(B)]
+            for r in logit_rows + (score_rows or []):
+                b = int(seq_of[r])
+                last_needed[b] = max(last_needed[b], r + 1)
+            keep_row = torch.zeros(ids_packed.numel(), dtype=torch.bool)
+            for b in range(B):
+                end = max(last_needed[b], cu[b] + 1)
+                if bool((slot[end:cu[b + 1]] >= 0).any()):      # never drop a visual / motion slot
+                    end = cu[b + 1]
+                keep_row[cu[b]:end] = True
+            if not bool(keep_row.all()):
+                new_index = torch.cumsum(keep_row.long(), 0) - 1
+                remap = lambda rows: [int(new_index[r]) for r in rows]
+                logit_rows = remap(logit_rows)
+                score_rows = remap(score_rows) if score_rows is not None else None
+                last_pos = new_index[last_pos]
+                kept = keep_row.nonzero().flatten()
+                row_of = torch.where(row_of >= 0, torch.where(keep_row[row_of.clamp_min(0)], new_index[row_of.clamp_min(0)], torch.full_like(row_of, -1)), row_of)
+                ids_packed, slot, seq_of = ids_packed[kept], slot[kept], seq_of[kept]
+                lens = [int((seq_of == b).sum()) for b in range(B)]
+                cu = list(accumulate(lens, initial=0))
+        return dict(ids_h=ids_h, mask_h=mask_h, labels_h=labels_h, flags_h=flags_h, ids_packed=ids_packed, cu=cu, row_of=row_of,
+                    lens=lens, slot=slot, n_vis=n_vis, keep=keep, n_frames=n_frames, want=want, logit_rows=logit_rows,
+                    score_rows=score_rows, last_ctx=(last_pos - torch.tensor(cu[:-1])).tolist())
+
+    def _visual_inputs(self, pixel_values, visual_tokens, motion_feature, plan):
+        H = self.config.llm_config.hidden_size
+        if visual_tokens is None:
+            visual_tokens = self.vit_tokens(pixel_values)
+        vit_embeds = self.project(visual_tokens)                       # [F, ntok, H]
+        if plan["flags_h"] is not None and int(plan["keep"].numel()) != plan["n_frames"]:
+            vit_embeds = vit_embeds[self._h2d(plan["keep"])]
+        return vit_embeds.reshape(-1, H), self.motion_embed(motion_feature)
+
+    def _outputs(self, plan, B, N, score, amax, mos, reads, att=None, tok=None):
+        """The result dict of one pass: ``reads`` (``_read_rows``) and the argmax ids, each scattered to its place among the label positions
+        under its ``readouts.ROW_FIELDS`` fill, the score head's outputs and the probe's tensors."""
+        dev = self.device
+        up = self._h2d   # host -> device through pinned memory, never blocking the host (keeps the CPU ahead of the GPU)
+        idx = up(plan["want"].reshape(-1).nonzero().flatten()) if len(plan["logit_rows"]) else None   # index list built on the host: no sync
+
+        def scatter(rows, fill):
+            """Per-consumed-row values -> their places among the B (N - 1) label positions, ``fill`` everywhere else."""
+            full = torch.full((B * (N - 1),) + tuple(rows.shape[1:]), fill, dtype=rows.dtype, device=dev)
+            return full if idx is None else full.index_copy_(0, idx, rows)
+
+        rows = dict(reads, logit=amax)
+        answer = None
+        if "top_ids" in rows:                       # top_logprobs: -1 / NaN rows wherever the label is -100, also under full_logits
+            is_answer = plan["labels_h"][..., 1:][plan["want"]] != -100      # (host: no sync)
+            if not bool(is_answer.all()):
+                answer = up(is_answer).view(-1, 1)
+        out = {"label": up(plan["labels_h"][..., 1:].contiguous().view(-1))}
+        for name, member, _, fill in readouts.ROW_FIELDS:
+            if name in rows:
+                r = rows[name]
+                if member == "topk" and answer is not None:
+                    r = torch.where(answer, r, torch.full_like(r, fill))
+                out[name] = scatter(r, fill)
+        if self.stage == 2:
+            score1 = score.to(torch.bfloat16)       # the head computes in bf16; the value is exact in fp32
+            out["score1"] = score1
+            out["loss"] = F.l1_loss(score1, mos.to(dev).to(score1.dtype)) if mos is not None else None
+        if "logprob" in out:                        # return_logprobs
+            out["ce_loss"] = readouts.ce_loss(out["logprob"], plan["labels_h"][..., 1:], up)
+        if att is not None:                         # return_score_attention: [B, L, n_heads, S]
+            out["score_attention"] = att
+        if tok is not None:                         # return_token_attention: [B, L, n_heads, N]
+            out["score_attention_tokens"] = tok
+        return out
+
+    def _logprob_labels(self, plan) -> torch.Tensor:
+        """Host int64 labels of the pass's consumed rows (in ``logit_rows`` order), checked first as torch's cross entropy would."""
+        lab = plan["labels_h"][:, 1:].to(torch.long)
+        V = self.config.llm_config.vocab_size
+        scored = lab != -100
+        bad = scored & ((lab < 0) | (lab >= V))
+        if bool(bad.any()):
+            raise ValueError(f"return_logprobs: label {int(lab[bad][0])} is outside [0, {V}) and not the ignore index -100")
+        if bool((scored & ~plan["want"]).any()):
+            raise ValueError("return_logprobs: a label that is not -100 follows a padded (masked) position; the reference would score the "
+                             "padded row itself, which this path does not run - set such labels to -100")
+        return lab[plan["want"]].contiguous()
+
+    def _read_rows(self, first_row: int, R: int, ro, labels: Optional[torch.Tensor] = None) -> dict:
+        """Every per-row read-out ``ro`` asks for, of consumed rows first_row .. first_row + R - 1 of the last native pass, keyed by its
+        ``readouts.ROW_FIELDS`` name: ``logprob`` fp32 [R], the log-probabilities of ``labels`` (int64 [R], aigv_out_row_logprob); ``cand_logprob``
+        fp32 [R, C] of the candidates ``ro.cand`` (int64 [C], aigv_out_row_cand_logprob); ``top_ids`` int64 [R, k] / ``top_logprob`` fp32 [R, k]
+        (aigv_out_row_topk_logprob): the k largest bf16 logits of every row, equal logits by ascending id, under the same log-sum-exp.
+        Host tensors go up through pinned memory, device tensors are read where they are - no host sync, and no allocation inside the library
+        (the pass may be captured)."""
+        lib, ctx, first_row = native.load(), self._ctx, int(first_row)
+        out = {name: torch.empty((max(R, 1),) + width, dtype=dt, device=self.device)[:R] for name, width, dt, _ in ro.row_fields() if name != "logit"}
+        if R and ro.logprobs:
+            native.check(lib.aigv_out_row_logprob(ctx, first_row, R, self._h2d(labels).data_ptr(), out["logprob"].data_ptr(), native.stream_ptr()), ctx)
+        if R and ro.cand is not None:
+            native.check(lib.aigv_out_row_cand_logprob(ctx, first_row, R, self._h2d(ro.cand).data_ptr(), int(ro.cand.numel()), out["cand_logprob"].data_ptr(),
+                                                       native.stream_ptr()), ctx)
+        if R and ro.topk:
+            native.check(lib.aigv_out_row_topk_logprob(ctx, first_row, R, int(ro.topk), out["top_ids"].data_ptr(), out["top_logprob"].data_ptr(),
+                                                       native.stream_ptr()), ctx)
+        return out
+
+    @staticmethod
+    def _shared_prefix_lengths(plans, B: int) -> List[int]:
+        """Per clip: the number of leading tokens every prompt shares, capped so that every consumed row (answer rows, score
+        row) stays in the continuation; raises if the prompts diverge before the last <IMG_CONTEXT> token (host logic only)."""
+        pre = []
+        for b in range(B):
+            seqs = [pl["ids_packed"][pl["cu"][b]:pl["cu"][b + 1]] for pl in plans]
+            n = min(len(x) for x in seqs)
+            eq = torch.ones(n, dtype=torch.bool)
+            for x in seqs[1:]:
+                eq &= x[:n] == seqs[0][:n]
+            lcp = int(n if bool(eq.all()) else eq.long().argmin())
+            first_needed = []
+            for pl in plans:
+                rows = [r - pl["cu"][b] for r in pl["logit_rows"] if pl["cu"][b] <= r < pl["cu"][b + 1]]
+                if pl["score_rows"] is not None:
+                    rows.append(pl["score_rows"][b] - pl["cu"][b])
+                first_needed.append(min(rows) if rows else pl["lens"][b] - 1)
+            p_b = min([lcp] + first_needed + [pl["lens"][b] - 1 for pl in plans])
+            if p_b <= max(pl["last_ctx"][b] for pl in plans):
+                raise ValueError(f"clip {b}: the prompts diverge before the last <IMG_CONTEXT> token - no shared video prefix")
+            pre.append(p_b)
+        return pre
+
+    def forward_shared_prefix(self, prompts, pixel_values: Optional[torch.Tensor] = None, image_flags: Optional[torch.Tensor] = None,
+                              motion_feature: Optional[torch.Tensor] = None, visual_tokens: Optional[torch.Tensor] = None, mos=None,
+                              return_logprobs: bool = False, candidate_ids=None, top_logprobs: Optional[int] = None,
+                              return_score_attention: bool = False, return_token_attention: bool = False):
+        """Score the same clips under several prompts that share their beginning - the reference's four quality
+        perspectives ask four questions BEHIND the same system + frame + motion tokens (8f-3) and
+        run four full passes (stage2_eval.py evaluates one jsonl per perspective).  Here the common prefix runs once
+        (ViT, projector, LLM prefill into the KV cache); every prompt then only continues its own few question / answer
+        tokens over the cached keys (``aigv_llm_extend``).  ``prompts``: list of ``(input_ids[B, N_p], attention_mask,
+        labels)``; returns the list of ``forward`` result dicts, one per prompt.  Causal attention makes the prefix rows
+        independent of what follows, so each result is that of a separate ``forward`` call up to kernel summation order.
+        ``return_logprobs``: every prompt's dict carries ``logprob`` and ``ce_loss`` as ``forward`` defines them - with candidate answers
+        as the prompts, their log-likelihoods behind one video prefix (README).  ``candidate_ids``: every prompt's dict carries
+        ``cand_logprob`` as ``forward`` defines it (the same candidates for every prompt).  ``top_logprobs``: every prompt's dict carries
+        ``top_ids`` / ``top_logprob`` as ``forward`` defines them.  ``return_score_attention``: every prompt's dict carries its own
+        ``score_attention`` [B, L, n_heads, F + 4] as ``forward`` defines it (default segments), read by the continuation pass over the cached
+        prefix keys and the prompt's own tokens; at most 64 (clip, prompt) pairs.  ``return_token_attention`` (implies it): every prompt's dict
+        also carries ``score_attention_tokens`` [B, L, n_heads, N] as ``forward`` defines it, N = the longest prefix + prompt length over the
+        prompts; the columns cover the prefix and then the prompt's own tokens, in order."""
+        if self.img_context_token_id is None:
+            raise AssertionError("img_context_token_id must be set by the caller (stage2_eval.py:810)")
+        if not prompts:
+            return []
+        pixel_values, visual_tokens, motion_feature = self._take_ahead(pixel_values, visual_tokens, motion_feature)
+        n_frames = visual_tokens.shape[0] if visual_tokens is not None else pixel_values.shape[0]
+        plans = [self._plan(ids, am, lab, image_flags, n_frames) for (ids, am, lab) in prompts]
+        ro = readouts.ReadOuts.parse(self.config.llm_config.vocab_size, "given", return_logprobs, candidate_ids, top_logprobs, return_score_attention,
+                                     None, return_token_attention)
+        lp_labels = [self._logprob_labels(pl) for pl in plans] if ro.wants_labels else None
+        B = prompts[0][0].shape[0]
+        pre = self._shared_prefix_lengths(plans, B)
+        p0 = plans[0]
+        ids_prefix = torch.cat([p0["ids_packed"][p0["cu"][b]:p0["cu"][b] + pre[b]] for b in range(B)])
+        slot_prefix = torch.cat([p0["slot"][p0["cu"][b]:p0["cu"][b] + pre[b]] for b in range(B)])
+        cu_prefix = list(accumulate(pre, initial=0))
+        motion_feature = self._motion_feature(pixel_values, B, motion_feature)
+        longest = max(max(pl["lens"]) for pl in plans)
+        P = len(plans)
+        n_suffix = sum(pl["cu"][-1] for pl in plans) - P * cu_prefix[-1]
+        self._native(n_frames=n_frames, n_tokens=max(cu_prefix[-1], n_suffix), n_clips=B * P,
+                     out_rows=sum(len(pl["logit_rows"]) for pl in plans), kv_cap=longest + 1,
+                     seq_len=max(ids.shape[1] for (ids, _, _) in prompts))
+        vit_embeds, motion = self._visual_inputs(pixel_values, visual_tokens, motion_feature, p0)
+        self._prefill(ids_prefix, slot_prefix, cu_prefix, vit_embeds, p0["n_vis"], motion, None, [], keep_kv=True, kv_cap=longest + 1)
+        lib, ctx = native.load(), self._ctx
+        dev = self.device
+        # one cache copy per prompt, then ONE continuation pass over B * P sequences (sequence p * B + b = clip b under prompt p):
+        # the decoder weights are streamed once for all prompts
+        native.check(lib.aigv_kv_fork(ctx, P, native.stream_ptr()), ctx)
+        parts, cu_s, lrows, srows, n_l = [], [0], [], [], []
+        for pl in plans:
+            starts = []
+            for b in range(B):
+                parts.append(pl["ids_packed"][pl["cu"][b] + pre[b]:pl["cu"][b + 1]])
+                starts.append(cu_s[-1])
+                cu_s.append(cu_s[-1] + pl["lens"][b] - pre[b])
+            def local(r, pl=pl, starts=starts):   # packed row of the full prompt -> packed row of the suffix batch
+                b = max(i for i in range(B) if pl["cu"][i] <= r)
+                return starts[b] + (r - pl["cu"][b] - pre[b])
+            rows = [local(r) for r in pl["logit_rows"]]
+            lrows += rows
+            n_l.append(len(rows))
+            if pl["score_rows"] is not None:
+                srows += [local(r) for r in pl["score_rows"]]
+        ids_d = torch.cat(parts).to(torch.long).contiguous().pin_memory().to(dev, non_blocking=True)
+        score = torch.empty(B * P, dtype=torch.float32, device=dev) if self.stage == 2 else None
+        amax = torch.empty(max(len(lrows), 1), dtype=torch.long, device=dev)
+        att = tok = None
+        if ro.score_attention:
+            # rows: sequence p * B + b of the continuation batch; segments of its new tokens: the prompt's own table behind the prefix; of the
+            # cached keys: the clip's prefix table, tiled over the P prompts (row p * B + b, padded with -1 to the longest prefix)
+            if B * P > self.MAX_PROBE_ROWS:
+                raise ValueError(f"return_score_attention: at most {self.MAX_PROBE_ROWS} (clip, prompt) pairs per call, got {B * P}")
+            prows, seg_parts, S = [], [], 0
+            for p, pl in enumerate(plans):
+                seg_p, S = self._default_segments(pl)
+                for b, r in enumerate(self._probe_rows(pl)):
+                    prows.append(cu_s[p * B + b] + (r - pl["cu"][b] - pre[b]))
+                    seg_parts.append(seg_p[pl["cu"][b] + pre[b]:pl["cu"][b + 1]])
+            seg0, _ = self._default_segments(p0)
+            ld = max(pre)
+            seg_cached = torch.full((P * B, ld), -1, dtype=torch.int32)
+            for b in range(B):
+                seg_cached[b::B, :pre[b]] = seg0[p0["cu"][b]:p0["cu"][b] + pre[b]]
+            probe = (prows, self._h2d(torch.cat(seg_parts).contiguous()), self._h2d(seg_cached), ld, S)
+            # (without the dense rows: the one-argument call, the form wrappers of this method have always been written against)
+            att, tok = self._arm_score_attention(probe, longest) if ro.token_attention else self._arm_score_attention(probe)
+        native.check(lib.aigv_llm_extend(ctx, ids_d.data_ptr(), native.i32_array(cu_s), B * P,
+                                         native.i32_array(srows) if score is not None else None, native.ptr(score),
+                                         native.i32_array(lrows) if lrows else None, len(lrows), amax.data_ptr(), 0,
+                                         native.stream_ptr()), ctx)
+        reads = self._read_rows(len(srows), len(lrows), ro, torch.cat(lp_labels) if ro.logprobs else None)   # rows [score rows | logit rows]
+        outs, off = [], 0
+        clips_of = lambda t, p: None if t is None else t[p * B:(p + 1) * B]
+        for p, (pl, (ids, _, _)) in enumerate(zip(plans, prompts)):
+            outs.append(self._outputs(pl, B, ids.shape[1], clips_of(score, p), amax[off:off + n_l[p]], mos,
+                                      {k: v[off:off + n_l[p]] for k, v in reads.items()}, clips_of(att, p), clips_of(tok, p)))
+            off += n_l[p]
+        return outs
+

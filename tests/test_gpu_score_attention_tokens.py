@@ -570,3 +570,76 @@ def test_model_more_than_64_rows_and_a_short_ld_tok_are_refused_through_the_new_
     assert float(out.abs().sum()) == 0.0 and float(tok.abs().sum()) == 0.0
     again = model(**kw, return_token_attention=True, **OPTS)
     assert torch.equal(bits(again["score_attention_tokens"]), bits(flagged(2)[5]["score_attention_tokens"]))
+
+
+# ---- 9. every read-out in one call ------------------------------------------------------------------------------------------------------
+def int_bits(t):
+    """A tensor's bit pattern as integers (NaNs compare)."""
+    t = t.detach().cpu().contiguous()
+    return t.view({2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()]) if t.is_floating_point() else t
+
+
+def same_bits(got, want, keys, what):
+    for k in keys:
+        assert got[k].shape == want[k].shape and torch.equal(int_bits(got[k]), int_bits(want[k])), (what, k)
+
+
+def test_model_all_read_outs_at_once_are_each_read_out_alone():
+    """``forward``'s docstring: the read-outs combine freely and none changes another's bits.  One call with all six options on - a ragged pair
+    of clips (one right-padded), two and three answer rows, four candidates of which one lies outside the vocabulary, k = 3, a user segment
+    table - against the calls with one option at a time, bit for bit; the same call replayed from its graph; and ``forward_shared_prefix``
+    over two prompts with every option it takes against its own one-at-a-time calls."""
+    model, cfg, sd, kw0, _ = G.rig(2)
+    V, T = cfg.llm_config.vocab_size, 2
+    t0, t1 = synth.canonical_tokens(cfg, 1, T, seed=910, answer_len=2), synth.canonical_tokens(cfg, 1, T, seed=911, answer_len=1)
+    n, pad = t0["input_ids"].shape[1], t0["input_ids"].shape[1] - t1["input_ids"].shape[1]
+    assert pad > 0
+    ids = torch.cat([t0["input_ids"], torch.cat([t1["input_ids"], torch.zeros(1, pad, dtype=torch.long)], 1)])
+    labels = torch.cat([t0["labels"], torch.cat([t1["labels"], torch.full((1, pad), -100)], 1)])
+    am = torch.ones(2, n, dtype=torch.bool)
+    am[1, n - pad:] = False
+    assert sorted((labels[:, 1:] != -100).sum(1).tolist()) == [2, 3]
+    kw = dict(pixel_values=synth.synthetic_frames(2 * T, 224, seed=910).cuda().to(BF), input_ids=ids, attention_mask=am,
+              image_flags=torch.ones(2 * T, 1, dtype=torch.long), labels=labels, motion_feature=synth.synthetic_motion(2, cfg.motion_dim, seed=910).cuda().to(BF))
+    cand = [5, V + 3, 7, 11]
+    table = (torch.arange(2 * n) % 5).view(2, n)
+    singles = [(dict(return_logprobs=True), ("logprob", "ce_loss")), (dict(candidate_ids=cand), ("cand_logprob",)),
+               (dict(top_logprobs=3), ("top_ids", "top_logprob")), (dict(return_score_attention=True, attention_segments=table), ("score_attention",)),
+               (dict(return_token_attention=True), ("score_attention_tokens",))]
+    everything = {k: v for opts, _ in singles for k, v in opts.items()}
+    assert len(everything) == 6
+    # (a) each output alone
+    off = model(**kw)
+    both = model(**kw, **everything)
+    torch.cuda.synchronize()
+    same_bits(both, off, ("score1", "logit"), "all on against all off")
+    for opts, keys in singles:
+        alone = model(**kw, **opts)
+        same_bits(both, alone, keys + ("score1", "logit"), sorted(opts))
+    assert both["cand_logprob"].shape == (2 * (n - 1), 4) and both["top_ids"].shape == (2 * (n - 1), 3) and both["score_attention"].shape[-1] == 5
+    assert both["score_attention_tokens"].shape[-1] == n
+    answer = labels[:, 1:].reshape(-1) != -100
+    assert torch.equal(~torch.isnan(both["logprob"]).cpu(), answer) and torch.equal((both["top_ids"] >= 0).all(-1).cpu(), answer)
+    assert torch.isnan(both["cand_logprob"][:, 1]).all() and torch.equal(~torch.isnan(both["cand_logprob"][:, 0]).cpu(), answer)
+    # (b) the same call through graph replay: eager, capture, replay
+    all_keys = tuple(k for _, keys in singles for k in keys) + ("score1", "logit")
+    model.enable_graph_replay(True)
+    try:
+        for i in range(3):
+            again = model(**kw, **everything)
+            torch.cuda.synchronize()
+            same_bits(again, both, all_keys, f"graph replay, call {i}")
+        assert sum(isinstance(v, tuple) for v in model._graphs.values()) == 1 and len(model._graphs) == 1
+    finally:
+        model.enable_graph_replay(False)
+    # (c) the shared-prefix pass: every prompt's dict, all options against one at a time
+    toks = synth.canonical_tokens(cfg, 2, T, seed=912)
+    pp = [(p["input_ids"], p["attention_mask"], p["labels"]) for p in synth.perspective_prompts(toks, 2, seed=912)]
+    common = dict(pixel_values=kw["pixel_values"], image_flags=kw["image_flags"], motion_feature=kw["motion_feature"])
+    shared_singles = [(opts, keys) if "attention_segments" not in opts else (dict(return_score_attention=True), keys) for opts, keys in singles]
+    shared_all = model.forward_shared_prefix(pp, **common, **{k: v for opts, _ in shared_singles for k, v in opts.items()})
+    assert len(shared_all) == 2
+    for opts, keys in shared_singles:
+        alone = model.forward_shared_prefix(pp, **common, **opts)
+        for p in range(2):
+            same_bits(shared_all[p], alone[p], keys + ("score1", "logit"), ("shared prefix", p, sorted(opts)))

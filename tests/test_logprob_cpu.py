@@ -118,3 +118,27 @@ def test_batched_passes_the_flag_and_splits_logprob_per_item():
             assert o["ce_loss"].item() == pytest.approx(-want[~torch.isnan(want)].double().mean().item(), rel=1e-6)
         else:
             assert torch.isnan(o["ce_loss"])
+
+
+def test_graph_key_tails_of_the_readouts_record():
+    """What each read-out appends to a graph's host key, written out: nothing for an option that is off, then - in this order - "logprobs",
+    "candidates", ("top_logprobs", k), ("score_attention", S) with S = 0 for the default table and the largest id + 1 for a user table, and
+    ("score_attention_tokens", N).  A record with every option off passes no keyword on."""
+    from aigv_assessor_amd import readouts
+    model, cfg, toks = _model_and_tokens()
+    V = cfg.llm_config.vocab_size
+    input_ids = torch.zeros(2, 24, dtype=torch.long)
+    table = (torch.arange(48) % 5).view(2, 24)
+    assert int(table.max()) == 4
+    tail = lambda **kw: readouts.ReadOuts.parse(V, toks["labels"], **kw).key_tail(input_ids.shape)
+    assert tail() == ()
+    assert tail(return_logprobs=True) == ("logprobs",)
+    assert tail(candidate_ids=[3, 5]) == ("candidates",)
+    assert tail(top_logprobs=3) == (("top_logprobs", 3),)
+    assert tail(return_score_attention=True) == (("score_attention", 0),)
+    assert tail(return_score_attention=True, attention_segments=table) == (("score_attention", 5),)
+    assert tail(return_token_attention=True) == (("score_attention", 0), ("score_attention_tokens", 24))
+    assert tail(return_logprobs=True, candidate_ids=[3, 5], top_logprobs=3, return_score_attention=True, attention_segments=table,
+                return_token_attention=True) == ("logprobs", "candidates", ("top_logprobs", 3), ("score_attention", 5), ("score_attention_tokens", 24))
+    assert readouts.forward_kwargs(readouts.ReadOuts.parse(V, toks["labels"])) == {}
+    assert readouts.forward_kwargs(readouts.ReadOuts()) == {}
