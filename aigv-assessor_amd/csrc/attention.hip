@@ -62,13 +62,35 @@ __device__ unsigned long long g_attn_stamp[2][STAMP_REPL][16];
 #define STAMP_ADD(slot, a, b)
 #endif
 
+// Diagnostic build only (-DAIGV_ATTN_DROP_NO_SKIP, scripts/key_drop_cost.py): a key tile whose keys are all dropped takes the mask loop like any
+// other masked tile instead of the wave-uniform skip - the A/B that prices the skip.  Never defined in the product build.
+#ifdef AIGV_ATTN_DROP_NO_SKIP
+constexpr bool DROP_SKIP = false;
+#else
+constexpr bool DROP_SKIP = true;
+#endif
+
+// The key-drop form's per-tile state; empty in the unmasked forms, whose code must stay what it was: everything that touches it sits in an
+// `if constexpr (DROP)` of its own, and the statements the two forms share are written as they always were.
+template <bool DROP> struct DropTile {
+  const uint64_t* row = nullptr;   // this sequence's words
+  uint64_t w = 0, next = 0;        // the word of the tile at hand, of the tile behind it (requested a tile ahead)
+  uint32_t lane[2] = {0, 0};       // the lane's share of w: half st, shifted down by the lane's 4 h
+};
+template <> struct DropTile<false> {};
+
 // NW = waves per workgroup (32 query rows each).  More waves share one K/V tile: the LDS-DMA issue cost per wave and tile
 // (the dominant overhead next to the MFMAs) halves going from 4 to 8 waves.
 // NB = K/V ring depth: tile t is multiplied while tiles t+1 .. t+NB-2 are in flight behind a counted vmcnt.
 // RS = the reference's rounding points of the SCORE matrix (AttnArgs::round_scores): s1 = bf16(q k^T) and, where the division that
 // follows is not a power of two (InternLM2: / sqrt(128)), s2 = bf16(s1 / post_div); the softmax then runs in fp32 on those values.
-template <int D, bool CAUSAL, int NW, int NB, bool RS>
-__global__ __launch_bounds__(NW * 64, (D == 64 && NW == 4) ? 4 : 2) void attn_fwd_kernel(const AttnArgs p) {
+// DROP = the key-drop form (AttnArgs::key_drop; d = 128 causal only): one 64-bit word per sequence and key tile, bit j & 63 of word j >> 6 set =
+// key j (absolute position, cached keys first) is invisible to every query row and head.  The word is wave-uniform (one scalar load per tile,
+// requested a tile ahead); a tile whose word is zero runs exactly the unmasked path, a tile whose word is all ones is skipped like a tile in
+// the causal future, every other tile takes the mask loop with one more bit test per score.  DROP = false compiles to the code it always was.
+template <int D, bool CAUSAL, int NW, int NB, bool RS, bool DROP = false>
+__global__ __launch_bounds__(NW * 64, (D == 64 && NW == 4) ? 4 : 2) void attn_fwd_kernel(const std::conditional_t<DROP, AttnArgs, AttnArgsUnmasked> p) {
+  static_assert(!DROP || (D == 128 && CAUSAL), "the key-drop form exists for the causal d = 128 kernel only");
   constexpr int QB = NW * 32;                // query rows per workgroup
   constexpr int ROWB = Lay<D>::ROWB;
   constexpr int CPR = D / 8;                 // 16-byte chunks per row
@@ -260,10 +282,20 @@ __global__ __launch_bounds__(NW * 64, (D == 64 && NW == 4) ? 4 : 2) void attn_fw
   const int tr_key = 4 * (gi >> 1) + (li >> 2);       // + 32*st + 16*s + 8*jh
   const int tr_dcol = 16 * (gi & 1) + 4 * (li & 3);   // + 32*dt
 
+  // key-drop words of this sequence: word kt covers keys [64 kt, 64 kt + 64) (lead = 0 in the causal form: the loop's key index is the absolute one)
+  [[maybe_unused]] DropTile<DROP> dk;
+  if constexpr (DROP) {
+    dk.row = p.key_drop + (size_t)seq * p.ld_drop;
+    if (n_tiles > 0) dk.next = dk.row[0];
+  }
   STAMP(t_loop);
   STAMP_ADD(2, t_begin, t_loop);
   for (int kt = 0; kt < n_tiles; ++kt) {
     STAMP(t0);
+    if constexpr (DROP) {
+      dk.w = dk.next;
+      if (kt + 1 < n_tiles) dk.next = dk.row[kt + 1];
+    }
     // tile kt must have landed; up to NB-2 younger tiles may stay in flight
     const int younger = min(NB - 2, n_tiles - 1 - kt);
     if (younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * 2 * IPW) : "memory");
@@ -278,7 +310,8 @@ __global__ __launch_bounds__(NW * 64, (D == 64 && NW == 4) ? 4 : 2) void attn_fw
     // wave-uniform skips: tiles entirely in this wave's causal future; waves whose 32 query rows all lie past the sequence
     // (1025 = 8 x 128 + 1 rows per ViT frame: three of the last workgroup's four waves).  Such a wave still stages its share
     // of every tile and joins the barriers, but leaves its SIMD's issue slots to the co-resident workgroups.
-    const bool skip = (CAUSAL && key0 > qw + 31 + kv_off) || (qw >= len || trimmed) || (ksplit && (kt % NW) != wave);
+    bool skip = (CAUSAL && key0 > qw + 31 + kv_off) || (qw >= len || trimmed) || (ksplit && (kt % NW) != wave);
+    if constexpr (DROP && DROP_SKIP) skip = skip || dk.w == ~0ull;      // key-drop form: and tiles whose keys are all dropped
     // The LDS-DMA requests of tile kt + NB - 1.  d = 128: not in one burst behind the barrier (the stamps priced that burst at 11 % of a
     // wave's lifetime: eight 1-KB requests queue at the CU's address unit) but one behind every second MFMA of S^T = K Q^T; a wave that
     // skips the tile, and the ragged last tile of a sequence, keep the burst.  d = 64 (half the requests, half the MFMAs to hide them
@@ -376,15 +409,21 @@ __global__ __launch_bounds__(NW * 64, (D == 64 && NW == 4) ? 4 : 2) void attn_fw
       }
     }
     const int qpos = qw + c + kv_off;   // index of the last key this query may see (causal)
-    const bool need_mask = (key0 + KT > kv_len) || (CAUSAL && key0 + KT - 1 > qw + kv_off);
+    bool need_mask = (key0 + KT > kv_len) || (CAUSAL && key0 + KT - 1 > qw + kv_off);
+    if constexpr (DROP) need_mask = need_mask || dk.w != 0;
     float tmax = -INFINITY;
     if (need_mask) {
+      if constexpr (DROP) {   // the lane's share of the tile's word: bit (e & 3) + 8 (e >> 2) of half st, shifted down by the lane's 4 h
+        dk.lane[0] = (uint32_t)dk.w >> (4 * h);
+        dk.lane[1] = (uint32_t)(dk.w >> 32) >> (4 * h);
+      }
 #pragma unroll
       for (int st = 0; st < 2; ++st)
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           const int key = key0 + st * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-          const bool vis = key < kv_len && (!CAUSAL || key <= qpos);
+          bool vis = key < kv_len && (!CAUSAL || key <= qpos);
+          if constexpr (DROP) vis = vis && !((dk.lane[st] >> ((e & 3) + 8 * (e >> 2))) & 1u);
           const float sv = vis ? sacc[st][e] : -INFINITY;
           sacc[st][e] = sv;
           tmax = fmaxf(tmax, sv);
@@ -784,23 +823,38 @@ const char* aigv_attn_check(const AttnArgs& a, int head_dim) {
   if ((a.kv_len_offset != 0 || a.kv_off) && !a.kv_seq_stride) return "attention: a key offset needs K/V in cache layout (kv_seq_stride)";
   if (a.kv_len_offset < 0 || (a.kv_seq_stride % 8)) return "attention: bad key offset / cache stride";
   if ((a.rope_cos != nullptr) != (a.rope_sin != nullptr) || (a.rope_cos && !a.rope_pos)) return "attention: query RoPE needs positions, cos and sin";
+  if (a.key_drop) {
+    if (!a.causal || head_dim != 128) return "attention: key_drop exists for the causal head_dim 128 form only";
+    if ((uintptr_t)a.key_drop & 7) return "attention: key_drop must be 8-byte aligned";
+    // with kv_off (device) the caller states the largest of the per-sequence offsets in kv_len_offset, which the kernel does not read then
+    const long long keys = (long long)a.kv_len_offset + a.max_len;
+    if (a.ld_drop < (keys + KT - 1) / KT) return "attention: ld_drop is below ceil((largest key offset + max_len) / 64) words per sequence";
+  }
   return nullptr;
 }
 
 
 // NB = 2: deeper rings (3, 4 buffers) measured 5-15 % slower on the ViT shape - they cost resident workgroups (LDS), and
 // with four workgroups per CU the wait for the next tile is already covered by the others' work
-template <int D, bool CAUSAL, int NW, bool RS, int NB = 2>
+template <int D, bool CAUSAL, int NW, bool RS, int NB = 2, bool DROP = false>
 static hipError_t launch_attn_rs(const AttnArgs& a, hipStream_t s) {
   constexpr int LDS = NB * 2 * KT * (D * 2);
   static LdsAttrOnce lds_attr;
-  if (hipError_t e = lds_attr.ensure((const void*)attn_fwd_kernel<D, CAUSAL, NW, NB, RS>, LDS); e != hipSuccess) return e;
+  if (hipError_t e = lds_attr.ensure((const void*)attn_fwd_kernel<D, CAUSAL, NW, NB, RS, DROP>, LDS); e != hipSuccess) return e;
   const int nqb = (a.max_len + NW * 32 - 1) / (NW * 32) - a.q_begin / (NW * 32);
-  hipLaunchKernelGGL((attn_fwd_kernel<D, CAUSAL, NW, NB, RS>), dim3(nqb * a.n_heads * a.n_seq), dim3(NW * 64), LDS, s, a);
+  // (the unmasked kernels take the fields they have always taken: AttnArgsUnmasked, a's base)
+  hipLaunchKernelGGL((attn_fwd_kernel<D, CAUSAL, NW, NB, RS, DROP>), dim3(nqb * a.n_heads * a.n_seq), dim3(NW * 64), LDS, s,
+                     static_cast<const std::conditional_t<DROP, AttnArgs, AttnArgsUnmasked>&>(a));
   return hipGetLastError();
 }
 template <int D, bool CAUSAL, int NW>
 static hipError_t launch_attn(const AttnArgs& a, hipStream_t s) {
+  if (a.key_drop) {   // the key-drop form: d = 128 causal only (aigv_attn_check refuses the rest); a null pointer reaches the instantiations it always did
+    if constexpr (D == 128 && CAUSAL)
+      return a.round_scores ? launch_attn_rs<D, CAUSAL, NW, true, 2, true>(a, s) : launch_attn_rs<D, CAUSAL, NW, false, 2, true>(a, s);
+    else
+      return hipErrorInvalidValue;
+  }
   return a.round_scores ? launch_attn_rs<D, CAUSAL, NW, true>(a, s) : launch_attn_rs<D, CAUSAL, NW, false>(a, s);
 }
 

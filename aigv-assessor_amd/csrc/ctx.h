@@ -126,6 +126,12 @@ struct aigv_ctx {
     float* tok = nullptr;   // aigv_score_attention_arm_tokens: the dense rows [n_rows][layers][n_heads][ld_tok], else nullptr / 0
     int ld_tok = 0;
   } probe;
+  // key-drop mask (aigv_key_drop_arm): armed for exactly the next aigv_llm_prefill, which applies it in every layer's attention
+  struct {
+    bool armed = false;
+    const uint64_t* words = nullptr;   // device: [n_clips][ld] words, AttnArgs::key_drop's layout
+    int ld = 0;
+  } drop;
   // profiling
   bool prof = false;
   int gemm_cls = AIGV_PROF_GEMM;   // class the GEMM launches are booked under: AIGV_PROF_GEMM_VIT inside aigv_vit_forward / aigv_project
@@ -250,12 +256,12 @@ constexpr size_t SPLITK_MAX_FLOATS = (size_t)64 << 20;   // 256 MB of fp32 split
 int splitk_scratch(aigv_ctx* c, size_t need_floats, float** out);
 
 // ---- the score-row attention probe of an armed pass (probe.hip) --------------------------------------------------------------------
-// DisarmScope: the pass that finds the context armed disarms it on every way out.  probe_plan: the probe's arguments for this pass (rows
+// DisarmScope: the pass that finds the context armed - with the probe, with a key-drop mask (aigv_key_drop_arm) - disarms it on every way out.  probe_plan: the probe's arguments for this pass (rows
 // validated against cu; off_host: keys cached in front of every sequence, or null), built ONCE per pass; probe_layer: the launch of layer li.
 struct DisarmScope {
   aigv_ctx* c;
   explicit DisarmScope(aigv_ctx* c_) : c(c_) {}
-  ~DisarmScope() { c->probe.armed = false; }
+  ~DisarmScope() { c->probe.armed = false; c->drop.armed = false; }
 };
 int probe_plan(aigv_ctx* c, const char* op, const int32_t* cu, int B, const int32_t* off_host, ProbeArgs* out);
 int probe_layer(aigv_ctx* c, const ProbeArgs& plan, int li, bool cache, hipStream_t s);

@@ -78,7 +78,9 @@ hipError_t aigv_launch_gemmco(const GemmArgs& a, int epi, hipStream_t s);
 // q/k/v point at column 0 of head 0 of their operand inside a (possibly fused) row:
 //   q head hq  at column (hq / g) * q_group_stride + (hq % g) * D        (g = n_heads / n_kv_heads)
 //   kv head hk at column hk * kv_head_stride
-struct AttnArgs {
+// (AttnArgsUnmasked: every field but the key-drop pair - the kernel argument of the unmasked kernels, so that their kernarg segment, and with
+// it their code, is what it was before AttnArgs gained that pair; callers fill an AttnArgs)
+struct AttnArgsUnmasked {
   const bf16_t* q; int ldq;
   const bf16_t* k; int ldk;
   const bf16_t* v; int ldv;
@@ -106,6 +108,15 @@ struct AttnArgs {
   int waves;                    // 0 = default (4 waves per workgroup); 4 / 8 forced (A/B: aigv_tune_attention / aigv_ctx_tune)
   int lead_key;                 // != 0: non-causal key counts 64 j + 1 run as full tiles over keys 1.. + key 0 merged in the epilogue (opt-in; attention.hip "lead key")
   int q_begin;                  // the launch computes query rows >= q_begin (a multiple of the workgroup's 128 rows) only; 0 everywhere at present
+};
+struct AttnArgs : AttnArgsUnmasked {
+  // Key drop (causal head_dim 128 only; null = no key is dropped, the kernels that have always run): bit j & 63 of word
+  // key_drop[seq * ld_drop + (j >> 6)] set = key j of that sequence is invisible to every query row and head.  j is the key's absolute position
+  // in its sequence, cached keys first - the packed form and the cache form (kv_off, kv_seq_stride) share the indexing; one word = one 64-key
+  // tile.  ld_drop >= ceil((largest key offset + max_len) / 64); with kv_off the caller states that largest offset in kv_len_offset.  A row left
+  // without a visible key is written as zeros.  The V rows of dropped keys must be finite (0 x NaN = NaN, as in torch).
+  const uint64_t* key_drop;     // device
+  int ld_drop;                  // words per sequence
 };
 const char* aigv_attn_check(const AttnArgs& a, int head_dim);
 hipError_t aigv_launch_attention(const AttnArgs& a, int head_dim, hipStream_t s);

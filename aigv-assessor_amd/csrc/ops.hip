@@ -161,11 +161,10 @@ int aigv_op_attention_rope(const void* q, int ldq, const void* k, int ldk, const
 
 // ---- the address and mask forms of the prefill attention that the scoring passes use (test entry points): checked here, before any HIP call ----
 // AttnArgs as llm_attn_args + the call sites of aigv_llm_prefill (packed K/V, q_tail) and aigv_llm_extend (K/V in the cache, kv_off) fill them.
-int aigv_op_attention_ex(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, const int32_t* cu, int n_seq,
-                         int max_len, int n_heads, int n_kv_heads, int q_group_stride, int kv_head_stride, int64_t kv_seq_stride,
-                         const int32_t* kv_off, int head_dim, int causal, float post_div, float q_prescale, const int32_t* pos, const void* cos,
-                         const void* sin, int pos_is_row, int q_tail, void* stream) {
-  const char* op = "aigv_op_attention_ex";
+static int attention_ex_op(const char* op, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, const int32_t* cu,
+                           int n_seq, int max_len, int n_heads, int n_kv_heads, int q_group_stride, int kv_head_stride, int64_t kv_seq_stride,
+                           const int32_t* kv_off, int head_dim, int causal, float post_div, float q_prescale, const int32_t* pos, const void* cos,
+                           const void* sin, int pos_is_row, int q_tail, const uint64_t* key_drop, int ld_drop, void* stream) {
   if (!q || !k || !v || !o || !cu) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
   if (q_tail < 0) return fail(nullptr, AIGV_ERR_ARG, "%s: q_tail = %d must not be negative", op, q_tail);
   if (kv_seq_stride < 0) return fail(nullptr, AIGV_ERR_ARG, "%s: kv_seq_stride = %lld must not be negative", op, (long long)kv_seq_stride);
@@ -181,9 +180,40 @@ int aigv_op_attention_ex(const void* q, int ldq, const void* k, int ldk, const v
   a.rope_pos = pos; a.rope_cos = (const bf16_t*)cos; a.rope_sin = (const bf16_t*)sin;
   a.rope_pos_is_row = pos_is_row ? 1 : 0;
   a.q_tail = q_tail;
+  if (key_drop) {
+    a.key_drop = key_drop; a.ld_drop = ld_drop;
+    if (kv_off) {
+      // the check needs the largest key offset, which lives on the device: read back here (a test entry point; the passes know theirs on the host)
+      if (n_seq < 1 || n_seq > AIGV_SMALL_INTS) return fail(nullptr, AIGV_ERR_ARG, "%s: key_drop with kv_off takes 1..%d sequences, got %d", op, AIGV_SMALL_INTS, n_seq);
+      int32_t off[AIGV_SMALL_INTS];
+      HIPCHK(nullptr, hipStreamSynchronize((hipStream_t)stream));
+      HIPCHK(nullptr, hipMemcpy(off, kv_off, (size_t)n_seq * sizeof(int32_t), hipMemcpyDeviceToHost));
+      for (int b = 0; b < n_seq; ++b) {
+        if (off[b] < 0) return fail(nullptr, AIGV_ERR_ARG, "%s: kv_off[%d] = %d must not be negative", op, b, off[b]);
+        a.kv_len_offset = std::max(a.kv_len_offset, (int)off[b]);
+      }
+    }
+  }
   if (const char* m = aigv_attn_check(a, head_dim)) return fail(nullptr, AIGV_ERR_ARG, "%s: %s", op, m);
   HIPCHK(nullptr, aigv_launch_attention(a, head_dim, (hipStream_t)stream));
   return 0;
+}
+
+int aigv_op_attention_ex(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, const int32_t* cu, int n_seq,
+                         int max_len, int n_heads, int n_kv_heads, int q_group_stride, int kv_head_stride, int64_t kv_seq_stride,
+                         const int32_t* kv_off, int head_dim, int causal, float post_div, float q_prescale, const int32_t* pos, const void* cos,
+                         const void* sin, int pos_is_row, int q_tail, void* stream) {
+  return attention_ex_op("aigv_op_attention_ex", q, ldq, k, ldk, v, ldv, o, ldo, cu, n_seq, max_len, n_heads, n_kv_heads, q_group_stride, kv_head_stride,
+                         kv_seq_stride, kv_off, head_dim, causal, post_div, q_prescale, pos, cos, sin, pos_is_row, q_tail, nullptr, 0, stream);
+}
+
+// aigv_op_attention_ex under a key-drop mask (AttnArgs::key_drop; null: the same call as aigv_op_attention_ex)
+int aigv_op_attention_drop(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, const int32_t* cu, int n_seq,
+                           int max_len, int n_heads, int n_kv_heads, int q_group_stride, int kv_head_stride, int64_t kv_seq_stride,
+                           const int32_t* kv_off, int head_dim, int causal, float post_div, float q_prescale, const int32_t* pos, const void* cos,
+                           const void* sin, int pos_is_row, int q_tail, const uint64_t* key_drop, int ld_drop, void* stream) {
+  return attention_ex_op("aigv_op_attention_drop", q, ldq, k, ldk, v, ldv, o, ldo, cu, n_seq, max_len, n_heads, n_kv_heads, q_group_stride, kv_head_stride,
+                         kv_seq_stride, kv_off, head_dim, causal, post_div, q_prescale, pos, cos, sin, pos_is_row, q_tail, key_drop, ld_drop, stream);
 }
 
 // K / V slots of fused qkv rows -> the KV cache [seq][kv head][cap][head_dim]: the kernel aigv_llm_prefill (keep_kv) and aigv_llm_extend append with

@@ -273,8 +273,11 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
                      int R, int64_t* argmax, int keep_kv, void* stream) {
   if (!c || !ids || !slot || !cu) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: null argument");
   const bool probing = c->probe.armed;   // aigv_score_attention_arm: this pass carries the probe, and disarms on every way out
+  const bool dropping = c->drop.armed;   // aigv_key_drop_arm: every layer's attention of this pass runs under the mask; disarmed likewise
   DisarmScope disarm(c);
   if (!c->finalized) return fail(c, AIGV_ERR_STATE, "aigv_llm_prefill: call aigv_finalize_weights first");
+  if (dropping && probing) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: a key-drop mask and the score-attention probe are both armed: the probe does not know the mask");
+  if (dropping && keep_kv) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: a key-drop mask with keep_kv: the continuation and decode kernels take no mask");
   const aigv_config& k = c->cfg;
   if (B <= 0 || B > k.max_seqs) return fail(c, AIGV_ERR_ARG, "n_clips %d outside 1..%d", B, k.max_seqs);
   if (cu[0] != 0) return fail(c, AIGV_ERR_ARG, "cu_seqlens[0] must be 0");
@@ -291,6 +294,9 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
   if (n_vis < 0 || (n_vis > 0 && !vis)) return fail(c, AIGV_ERR_ARG, "visual tokens missing");
   if (keep_kv && (k.kv_capacity <= 0 || max_len >= k.kv_capacity))
     return fail(c, AIGV_ERR_STATE, "keep_kv needs kv_capacity > longest prompt (%d vs %d)", k.kv_capacity, max_len);
+  if (dropping && (!c->drop.words || c->drop.ld < (max_len + 63) / 64))
+    return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: key-drop mask armed with %d words per clip, the longest clip (%d tokens) needs %d", c->drop.ld, max_len,
+                (max_len + 63) / 64);
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)stream;
   const int H = k.llm_hidden, I = k.llm_inter, D = c->head_dim, g = c->g, nkv = k.llm_kv_heads;
@@ -353,6 +359,7 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
       a.max_len = max_len;
       const bool last_trim = trim && li == k.llm_layers - 1;
       a.q_tail = last_trim ? q_tail : 0;
+      if (dropping) { a.key_drop = c->drop.words; a.ld_drop = c->drop.ld; }   // every layer, the row-trimmed last one included
       if (const char* m = aigv_attn_check(a, D)) return fail(c, AIGV_ERR_ARG, "%s", m);
       ProfScope ps(c, AIGV_PROF_ATTN_LLM, last_trim ? 0.0 : attn_flops, 2.0 * T * ((double)c->qkv_out + H), s);
       HIPCHK(c, aigv_launch_attention(a, D, s));
@@ -395,6 +402,15 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
   return 0;
 }
 
+// Arms the next aigv_llm_prefill with a key-drop mask (include/aigv_amd.h): the words are read when that pass runs.
+int aigv_key_drop_arm(aigv_ctx* c, const uint64_t* words_dev, int ld_words) {
+  if (!c) return fail(c, AIGV_ERR_ARG, "aigv_key_drop_arm: null context");
+  if (!words_dev || ((uintptr_t)words_dev & 7)) return fail(c, AIGV_ERR_ARG, "aigv_key_drop_arm: words_dev is null or not 8-byte aligned");
+  if (ld_words < 1) return fail(c, AIGV_ERR_ARG, "aigv_key_drop_arm: ld_words = %d must be positive", ld_words);
+  c->drop.words = words_dev; c->drop.ld = ld_words; c->drop.armed = true;
+  return 0;
+}
+
 // Continue the sequences kept by aigv_llm_prefill(keep_kv = 1) with new TEXT tokens: causal attention of the new rows over the
 // cached keys plus themselves.  commit = 0 leaves the cache lengths where they were, so several continuations of ONE prefix
 // (the four quality-perspective questions behind the same video tokens) can be scored one after the other.
@@ -402,7 +418,9 @@ int aigv_llm_extend(aigv_ctx* c, const int64_t* ids, const int32_t* cu, int B, c
                     const int32_t* logit_rows, int R, int64_t* argmax, int commit, void* stream) {
   if (!c || !ids || !cu) return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: null argument");
   const bool probing = c->probe.armed;
+  const bool dropping = c->drop.armed;
   DisarmScope disarm(c);
+  if (dropping) return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: a key-drop mask is armed (aigv_key_drop_arm): the continuation pass takes no mask, only aigv_llm_prefill does");
   if (!c->kv_valid) return fail(c, AIGV_ERR_STATE, "aigv_llm_extend: no KV state (run aigv_llm_prefill with keep_kv)");
   const aigv_config& k = c->cfg;
   if (B != c->kv_seqs) return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: %d sequences, the cache holds %d", B, c->kv_seqs);

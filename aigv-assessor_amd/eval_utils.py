@@ -171,6 +171,34 @@ def frame_heatmaps(tok_att, positions, layers=None):
     return (mass / mass.sum(-1, keepdim=True)).view(B, F, g, g).to(tok_att.dtype)
 
 
+def frame_ablation(model, *, pixel_values, input_ids, attention_mask, image_flags, labels=None, motion_feature=None, **readout_kwargs):
+    """WHAT IF a frame were not there: the batch scored once as it is and once per unit with that unit's tokens hidden from the LLM
+    (``forward(key_drop=model.unit_masks(...)[:, u])``) - unit u < F is frame u's visual tokens, unit F the motion token.  Positions, the
+    "FrameK:" text and every other token stay as they are, so a delta isolates the unit's content.  InternViT and the SlowFast branch run
+    ONCE; their outputs are handed to every pass (``visual_tokens=``, ``motion_feature=``).  ``readout_kwargs`` go to every ``forward`` call.
+
+    Returns a dict: ``outs`` - the F + 2 result dicts of ``forward``, base first, then unit 0 .. F; ``units`` - the masks, bool [B, F + 1, N];
+    and for a stage-2 model ``score1`` [B] (the base scores, fp32), ``ablated`` [B, F + 1] (the score with the unit hidden; NaN where the
+    clip lacks the frame) and ``delta`` = ``score1[:, None] - ablated``: positive where the unit raised the score."""
+    import torch
+    B = int(input_ids.shape[0])
+    units = model.unit_masks(input_ids, attention_mask, image_flags, n_frames=int(pixel_values.shape[0]))      # host bool [B, F + 1, N]
+    if motion_feature is None:
+        motion_feature = model.motion_feature(pixel_values, B)
+    tokens = model.vit_tokens(pixel_values)
+    common = dict(input_ids=input_ids, attention_mask=attention_mask, image_flags=image_flags, labels=labels, visual_tokens=tokens,
+                  motion_feature=motion_feature, **readout_kwargs)
+    outs = [model.forward(**common)] + [model.forward(key_drop=units[:, u], **common) for u in range(units.shape[1])]
+    res = {"outs": outs, "units": units}
+    if "score1" in outs[0]:
+        base = outs[0]["score1"].float()
+        ablated = torch.stack([o["score1"].float() for o in outs[1:]], 1)
+        absent = ~units.any(-1)                                             # [B, F + 1]: the clip has no such frame
+        ablated = ablated.masked_fill(absent.to(ablated.device), float("nan"))
+        res.update(score1=base, ablated=ablated, delta=base[:, None] - ablated)
+    return res
+
+
 def batched(items, model, k: int = 4, frames=None, ahead: bool = True, pad_id: int = 2, return_logprobs: bool = False, candidate_ids=None,
             top_logprobs=None):
     """The reference's eval loop at batch ``k`` instead of batch 1: yields ``(item, output)`` for EVERY item of ``items`` (the loop's

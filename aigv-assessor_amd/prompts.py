@@ -178,6 +178,47 @@ def attention_segments(slot, cu: Sequence[int], n_frames, tokens_per_frame: int)
     return seg
 
 
+def key_drop_words(key_drop, cu: Sequence[int], row_of=None, n_words: Optional[int] = None) -> torch.Tensor:
+    """The key-drop mask of ``forward(key_drop=...)`` in the attention kernel's layout (host only): int64 [B, W], bit ``j & 63`` of word
+    ``[b, j >> 6]`` set = token j of clip b (its position inside the PACKED clip, 0 = its first token) is dropped; bits at and past a clip's
+    length are clear.  One word is one 64-key tile.  ``key_drop``: bool / integer [B, N] laid out like ``input_ids``; ``cu``: the clips' packed
+    row offsets [B + 1]; ``row_of`` [B, N]: the packed row of every [b, p], negative where the pass does not run the token (padding: ignored) -
+    default: clip b's tokens are its first ``cu[b + 1] - cu[b]`` columns (right-padded inputs).  W = ``n_words`` or ceil(longest clip / 64).
+    (int64 because torch has no uint64 arithmetic: bit 63 is the sign bit, the device reads the same 64 bits.)"""
+    import numpy as np
+    kd = torch.as_tensor(key_drop)
+    if kd.dim() != 2 or kd.is_floating_point():
+        raise ValueError("key_drop_words: key_drop must be a bool or integer tensor [B, N]")
+    kd = kd.to("cpu").bool()
+    cu = [int(v) for v in cu]
+    B, N = kd.shape
+    if len(cu) != B + 1 or cu[0] != 0 or any(cu[b + 1] <= cu[b] for b in range(B)):
+        raise ValueError(f"key_drop_words: cu {cu} does not describe {B} non-empty clips")
+    lens = [cu[b + 1] - cu[b] for b in range(B)]
+    W = -(-max(lens) // 64)
+    if n_words is not None:
+        if int(n_words) < W:
+            raise ValueError(f"key_drop_words: n_words = {n_words} is below the {W} words of the longest clip ({max(lens)} tokens)")
+        W = int(n_words)
+    if row_of is None:
+        if max(lens) > N:
+            raise ValueError(f"key_drop_words: a clip of {max(lens)} tokens does not fit the {N} columns of key_drop")
+        j = torch.arange(N).expand(B, N).clone()
+        j[j >= torch.tensor(lens)[:, None]] = -1
+    else:
+        row_of = torch.as_tensor(row_of).to("cpu").long()
+        if tuple(row_of.shape) != (B, N):
+            raise ValueError(f"key_drop_words: row_of {tuple(row_of.shape)} is not laid out like key_drop {(B, N)}")
+        j = torch.where(row_of >= 0, row_of - torch.tensor(cu[:-1])[:, None], torch.full_like(row_of, -1))
+        if bool((j >= torch.tensor(lens)[:, None]).any()) or bool(((row_of >= 0) & (j < 0)).any()):
+            raise ValueError("key_drop_words: row_of points outside its clip")
+    words = np.zeros((B, W), dtype=np.uint64)
+    b_idx, p_idx = (kd & (j >= 0)).nonzero(as_tuple=True)
+    jj = j[b_idx, p_idx].numpy().astype(np.uint64)
+    np.bitwise_or.at(words, (b_idx.numpy(), (jj >> np.uint64(6)).astype(np.int64)), np.uint64(1) << (jj & np.uint64(63)))
+    return torch.from_numpy(words.view(np.int64))
+
+
 def visual_token_positions(slot, cu: Sequence[int], n_frames, tokens_per_frame: int) -> torch.Tensor:
     """Where every visual token of every frame sits INSIDE its own clip: long [B, F, tokens_per_frame], entry [b, f, t] = the position (0 =
     the clip's first token) of token t of clip b's frame f - the column of ``forward(return_token_attention=True)``'s

@@ -1,4 +1,5 @@
-"""Which read-outs a scoring pass carries: label log-probs, candidate log-probs, top-k log-probs, score attention by segment and per token.
+"""Which read-outs a scoring pass carries: label log-probs, candidate log-probs, top-k log-probs, score attention by segment and per token -
+and whether it runs under a key-drop mask (``key_drop``: not a read-out, but a per-call option that travels the same way).
 
 This module is the one place that knows that decision.  A new read-out adds, HERE: a member to ``ReadOuts`` and its check to
 ``ReadOuts.parse``; the element it appends to a graph's host key to ``ReadOuts.key_tail``; its keyword to ``forward_kwargs``; and - when it
@@ -45,6 +46,22 @@ def candidates(candidate_ids, labels="given") -> Optional[torch.Tensor]:
     return t.to(torch.long).contiguous()
 
 
+def key_drop_mask(key_drop, ids_shape=None, probing: bool = False) -> Optional[torch.Tensor]:
+    """``key_drop`` (None, or a bool / integer tensor [B, N] laid out like ``input_ids``, on any device) -> None or a HOST bool tensor [B, N].
+    The shape is checked where ``ids_shape`` is known; the clip-dependent rules (first token, consumed rows) where the plan is
+    (``ScoringPass._key_drop_words``)."""
+    if key_drop is None:
+        return None
+    if probing:
+        raise ValueError("key_drop: cannot be combined with return_score_attention / return_token_attention (the probe does not know the mask)")
+    t = key_drop
+    if not torch.is_tensor(t) or t.is_floating_point() or t.is_complex() or t.dim() != 2:
+        raise ValueError("key_drop: expected a bool or integer tensor [B, N] laid out like input_ids")
+    if ids_shape is not None and tuple(t.shape) != tuple(ids_shape):
+        raise ValueError(f"key_drop: shape {tuple(t.shape)} differs from input_ids {tuple(ids_shape)}")
+    return t.detach().to("cpu").bool().contiguous()
+
+
 _NAN = float("nan")
 # every result laid out per label position, [B (N - 1)] + width: name in the result dict, the ``ReadOuts`` member that switches it on and gives
 # its trailing width (None: always there), dtype, fill wherever the row is not an answer row
@@ -65,17 +82,20 @@ class ReadOuts:
     score_attention: bool = False               # (return_token_attention implies it)
     segments: Optional[torch.Tensor] = None     # the user's attention_segments table; None: prompts.attention_segments
     token_attention: bool = False
+    key_drop: Optional[torch.Tensor] = None     # host bool [B, N]: tokens hidden, as keys, from every row of their clip (forward only)
 
     @classmethod
     def parse(cls, vocab: int, labels="given", return_logprobs: bool = False, candidate_ids=None, top_logprobs: Optional[int] = None,
-              return_score_attention: bool = False, attention_segments=None, return_token_attention: bool = False) -> "ReadOuts":
+              return_score_attention: bool = False, attention_segments=None, return_token_attention: bool = False, key_drop=None,
+              ids_shape=None) -> "ReadOuts":
         """The record of a call's public keyword arguments, checked.  ``labels=None`` (``forward`` without labels) refuses candidates and top-k;
         the shared-prefix and generate entry points leave the default.  A user segment table is checked where its bins are counted
         (``n_segments``: it needs the shape of ``input_ids``)."""
         cand = candidates(candidate_ids, labels)
         k = top_logprobs_k(top_logprobs, vocab, labels)
         att = bool(return_score_attention or return_token_attention)
-        return cls(bool(return_logprobs), cand, k or None, att, attention_segments if att else None, bool(return_token_attention))
+        return cls(bool(return_logprobs), cand, k or None, att, attention_segments if att else None, bool(return_token_attention),
+                   key_drop_mask(key_drop, ids_shape, att))
 
     @property
     def wants_labels(self) -> bool:
@@ -114,7 +134,7 @@ def forward_kwargs(r: ReadOuts) -> dict:
     """The record as keyword arguments of ``forward``.  An option that is off is NOT passed: callers hand these to any object with
     ``forward``'s call form, which need not know the options it is not asked for."""
     kw = dict(return_logprobs=r.logprobs or None, candidate_ids=r.cand, top_logprobs=r.topk, return_score_attention=r.score_attention or None,
-              attention_segments=r.segments, return_token_attention=r.token_attention or None)
+              attention_segments=r.segments, return_token_attention=r.token_attention or None, key_drop=r.key_drop)
     return {k: v for k, v in kw.items() if v is not None}
 
 

@@ -182,7 +182,7 @@ class ScoringPass:
             keep.append(pinned)
         return pinned.to(self.device, non_blocking=True)
 
-    def _prefill(self, ids_packed, slot, cu, vis, n_vis, motion, score_rows, logit_rows, keep_kv=False, kv_cap=0, probe=None, ld_tok=0):
+    def _prefill(self, ids_packed, slot, cu, vis, n_vis, motion, score_rows, logit_rows, keep_kv=False, kv_cap=0, probe=None, ld_tok=0, drop_words=None):
         b = len(cu) - 1
         T = cu[-1]
         lib, ctx = self._native(n_tokens=T, n_clips=b, out_rows=len(logit_rows), kv_cap=kv_cap)
@@ -197,6 +197,9 @@ class ScoringPass:
         sr_a = native.i32_array(score_rows) if score_rows is not None else None
         lr_a = native.i32_array(logit_rows) if len(logit_rows) else None
         att, tok = self._arm_score_attention(probe, ld_tok) if probe is not None else (None, None)   # (armed for exactly the pass below)
+        if drop_words is not None:      # key_drop: host int64 [B, W] (prompts.key_drop_words) -> armed for exactly the pass below, which disarms
+            words_d = up(drop_words, torch.int64)
+            native.check(lib.aigv_key_drop_arm(ctx, words_d.data_ptr(), int(drop_words.shape[1])), ctx)
         native.check(lib.aigv_llm_prefill(
             ctx, ids_d.data_ptr(), slot_d.data_ptr(), cu_a, b, native.ptr(vis), n_vis, native.ptr(motion),
             sr_a, native.ptr(score), lr_a, len(logit_rows), amax.data_ptr(), int(keep_kv), native.stream_ptr()), ctx)
@@ -264,6 +267,43 @@ class ScoringPass:
         plan = self._plan(input_ids, attention_mask, None, image_flags, int(n_frames))
         return prompts.visual_token_positions(plan["slot"], plan["cu"], self._frames_per_clip(plan), self.num_image_token)
 
+    def unit_masks(self, input_ids, attention_mask=None, image_flags=None, n_frames: Optional[int] = None) -> torch.Tensor:
+        """The ablation units of a batch as ``forward(key_drop=...)`` masks (host only, no GPU work): bool [B, F + 1, N] laid out like
+        ``input_ids``; unit u < F marks the visual tokens of the clip's frame u, unit F its motion token.  A clip with fewer frames than the
+        longest has all-False rows for the frames it lacks.  Built from ``prompts.attention_segments`` of the batch as ``forward`` would pack
+        it, the way ``visual_token_positions`` is.  ``n_frames``: the frames handed to ``forward`` (default: ``image_flags.shape[0]``)."""
+        if n_frames is None:
+            if image_flags is None:
+                raise ValueError("unit_masks: pass n_frames or image_flags")
+            n_frames = int(image_flags.shape[0])
+        from . import prompts
+        plan = self._plan(input_ids, attention_mask, None, image_flags, int(n_frames))
+        seg, S = self._default_segments(plan)
+        F = S - prompts.N_TEXT_SEGMENTS
+        row_of = plan["row_of"]
+        seg_of = torch.where(row_of >= 0, seg.long()[row_of.clamp_min(0)], torch.full_like(row_of, -1))      # [B, N]: segment id, -1 where not run
+        return torch.stack([seg_of == u for u in range(F + 1)], 1)
+
+    def _key_drop_words(self, plan, key_drop: torch.Tensor) -> torch.Tensor:
+        """``forward(key_drop=...)``: the host bool mask [B, N] checked against the plan -> ``prompts.key_drop_words`` (host int64 [B, W]).
+        Positions the pass does not run (padding, a dropped dead tail) are ignored.  Refused before anything is launched: dropping a clip's
+        first token (the sink: it guarantees that every row keeps a visible key) and dropping a row whose output is consumed."""
+        from . import prompts
+        row_of, cu = plan["row_of"], plan["cu"]
+        if tuple(key_drop.shape) != tuple(row_of.shape):
+            raise ValueError(f"key_drop: shape {tuple(key_drop.shape)} differs from input_ids {tuple(row_of.shape)}")
+        rows = row_of[key_drop & (row_of >= 0)]                    # the packed rows that are dropped
+        dropped = torch.zeros(cu[-1], dtype=torch.bool)
+        dropped[rows] = True
+        for b in range(len(cu) - 1):
+            if bool(dropped[cu[b]]):
+                raise ValueError(f"key_drop: clip {b}: the first token cannot be dropped (it guarantees every row a visible key)")
+        for r in list(plan["logit_rows"]) + list(plan["score_rows"] or []):
+            if bool(dropped[r]):
+                b = max(i for i in range(len(cu) - 1) if cu[i] <= r)
+                raise ValueError(f"key_drop: clip {b}: token {r - cu[b]} is a consumed row (an answer row or the score row) and cannot be dropped")
+        return prompts.key_drop_words(key_drop, cu, row_of)
+
     def _arm_score_attention(self, probe, ld_tok: int = 0):
         """Arm the context's NEXT prefill / continuation pass; returns (att, tok): the fp32 tensor [rows, L, n_heads, S] the pass fills
         (aigv_score_attention_arm) and - ``ld_tok`` > 0, ``return_token_attention``: aigv_score_attention_arm_tokens - the dense rows [rows, L,
@@ -287,7 +327,7 @@ class ScoringPass:
                 output_hidden_states=None, return_dict=None, motion_feature: Optional[torch.Tensor] = None,
                 visual_tokens: Optional[torch.Tensor] = None, full_logits: bool = False, return_logprobs: bool = False,
                 candidate_ids=None, top_logprobs: Optional[int] = None, return_score_attention: bool = False, attention_segments=None,
-                return_token_attention: bool = False):
+                return_token_attention: bool = False, key_drop: Optional[torch.Tensor] = None):
         """Stage-2 eval pass (modeling_internvl_chat.py:306-488) or, with ``stage=1``, the stage-1 pass
         (internvl_chat_eval1/modeling_internvl_chat.py:250-366).  ``visual_tokens`` optionally supplies
         already all-gathered pre-projector tokens (frame-DP) instead of ``pixel_values``.
@@ -330,18 +370,40 @@ class ScoringPass:
         (``input_ids[b, j]`` for the collator's right-padded inputs), the columns behind the score row and the padding are 0.  The values
         share the bins' scores, total and division (a bin of one key holds that key's bits); ``score_attention`` and every other output
         keep their bits.  ``prompts.visual_token_positions`` + ``eval_utils.frame_heatmaps`` fold it to a 16 x 16 map per frame.  Under
-        graph replay the flag and N are part of the graph's key; the tensor is handed back as a copy."""
+        graph replay the flag and N are part of the graph's key; the tensor is handed back as a copy.
+
+        ``key_drop`` (bool or integer tensor [B, N] laid out like ``input_ids``, on any device): WHAT IF these tokens were not there.  True
+        hides that token, as a key, from every row of its clip in every layer; padded positions are ignored.  Every output - ``score1``,
+        ``logit``, the log-probability read-outs - is that of the masked pass; positions, packing and the dead-tail trimming are untouched.
+        This is what the reference computes for ``attention_mask & ~key_drop``: zeros in the middle of its mask keep every token's position
+        and hide those keys through the additive mask.  This path does NOT do that for interior zeros of ``attention_mask`` itself: it
+        treats every zero as padding and strips the token, which moves the later tokens' positions - that behaviour stays.  The V rows of
+        dropped keys must be finite: they are multiplied by an exact 0, and 0 x NaN is NaN here as it is in torch.  ValueError, before
+        anything is launched, for a wrong shape, for dropping a clip's first token (the sink guarantees every row a visible key) or a
+        consumed row (an answer row, the score row), and in combination with ``return_score_attention`` / ``return_token_attention`` (the
+        probe does not know the mask).  With graph replay enabled a call with ``key_drop`` runs eagerly - the same bits as with replay
+        off - and captures nothing; unmasked calls keep replaying.  ``unit_masks`` builds the per-frame masks,
+        ``eval_utils.frame_ablation`` the per-frame score deltas."""
         if position_ids is not None or past_key_values is not None:
             raise NotImplementedError("the eval pass takes default positions and no cache, like the reference drivers")
         if self.img_context_token_id is None:
             raise AssertionError("img_context_token_id must be set by the caller (stage2_eval.py:810)")
+        drop_words = None
+        if key_drop is not None:        # checked in full on the host before anything touches the device (a plan of its own: host work only)
+            kd = readouts.key_drop_mask(key_drop, input_ids.shape, bool(return_score_attention or return_token_attention))
+            src = visual_tokens if visual_tokens is not None else pixel_values
+            drop_words = self._key_drop_words(self._plan(input_ids, attention_mask, labels, image_flags, (src.tokens if isinstance(src, VisualAhead) else src).shape[0],
+                                                         full_logits), kd)
         pixel_values, visual_tokens, motion_feature = self._take_ahead(pixel_values, visual_tokens, motion_feature)
         parse = lambda: readouts.ReadOuts.parse(self.config.llm_config.vocab_size, labels, return_logprobs, candidate_ids, top_logprobs,
-                                                return_score_attention, attention_segments, return_token_attention)
+                                                return_score_attention, attention_segments, return_token_attention, key_drop,
+                                                None if input_ids is None else input_ids.shape)
         ro = None
         if self._graph_replay_enabled and self._capture_keep is None:
             ro = parse()
-            out = self._forward_through_graph(mos, pixel_values, input_ids, attention_mask, image_flags, labels, motion_feature, visual_tokens, full_logits, ro)
+            # (a masked call stays eager and leaves the graph cache as it is: capturing masked passes is out of scope)
+            out = None if ro.key_drop is not None else self._forward_through_graph(mos, pixel_values, input_ids, attention_mask, image_flags, labels,
+                                                                                  motion_feature, visual_tokens, full_logits, ro)
             if out is not None:
                 return out
         B, N = input_ids.shape
@@ -358,7 +420,8 @@ class ScoringPass:
         vit_embeds, motion = self._visual_inputs(pixel_values, visual_tokens, motion_feature, plan)
         probe = self._score_attention_probe(plan, input_ids, ro) if ro.score_attention else None
         score, amax, *armed = self._prefill(plan["ids_packed"], plan["slot"], plan["cu"], vit_embeds, plan["n_vis"], motion,
-                                            plan["score_rows"], plan["logit_rows"], probe=probe, ld_tok=N if ro.token_attention else 0)
+                                            plan["score_rows"], plan["logit_rows"], probe=probe, ld_tok=N if ro.token_attention else 0,
+                                            drop_words=drop_words)
         att, tok = armed or (None, None)        # (_prefill hands the probe's tensors back only when it armed one)
         reads = self._read_rows(B if score is not None else 0, len(plan["logit_rows"]), ro, lp_labels)
         return self._outputs(plan, B, N, score, amax, mos, reads, att, tok)

@@ -44,7 +44,8 @@ extern "C" {
                                 and the row kernels (aigv_op_score_head, aigv_op_rmsnorm_quant_fp8, aigv_op_rope_slots, aigv_op_embed,
                                 aigv_op_seqpos, aigv_op_gather_rows, aigv_op_scatter_rows, aigv_op_cls_rows, aigv_op_write_ints), then by the
                                 score-row attention probe (aigv_score_attention_arm, aigv_op_attention_probe), then by its dense per-key
-                                form (aigv_score_attention_arm_tokens, aigv_op_attention_probe_tokens)
+                                form (aigv_score_attention_arm_tokens, aigv_op_attention_probe_tokens), then by the key-drop mask of the
+                                prefill attention (aigv_key_drop_arm, aigv_op_attention_drop)
                                 - added symbols only: a library without them is refused at load
                                 time, "missing <name>" */
 
@@ -190,6 +191,21 @@ int aigv_score_attention_arm(aigv_ctx* ctx, const int32_t* rows_host, int n_rows
  * message, before its first layer.  Nothing is allocated (the armed pass still captures); aigv_decode_step ignores the feature. */
 int aigv_score_attention_arm_tokens(aigv_ctx* ctx, const int32_t* rows_host, int n_rows, const int32_t* seg_new_dev, const int32_t* seg_cached_dev,
                                     int ld_cached, int n_segments, float* out_dev, float* tok_out_dev, int ld_tok);
+
+/* Key-drop mask: score the clips with some tokens HIDDEN from the LLM - what the reference computes for attention_mask zeros in the middle of a
+ * sequence (positions stay as they are; the additive mask hides those keys from every query row).  Arms exactly the next aigv_llm_prefill on
+ * this context: the prefill attention of EVERY layer of that pass, the row-trimmed last layer included, runs in its key-drop form, and every
+ * output of the pass (score, argmax, the aigv_out_row_* read-outs) is that of the masked pass.  The pass then disarms, also when it fails.
+ *   words_dev  DEVICE uint64 [n_clips][ld_words], read when the pass runs: bit (j & 63) of word [clip][j >> 6] set = token j of that clip (its
+ *              position inside the clip, 0 = first token) is invisible, as a key, to every query row and head of its clip.  One word is one
+ *              64-key tile of the kernel; bits past a clip's length are ignored.
+ *   ld_words   words per clip, >= ceil(longest clip / 64): AIGV_ERR_ARG from the pass, with a message, otherwise.
+ * A query row left without a visible key has an all-zero attention output (the reference's softmax over a fully masked row is uniform
+ * instead): keep every clip's first token visible.  The V rows of dropped keys must be FINITE: the kernel multiplies them by an exact 0, and
+ * 0 x NaN is NaN, as it is in torch.  Tiles without a dropped key run the unmasked tile body; an unarmed pass enters no new code.
+ * Refused with AIGV_ERR_ARG and a message: an armed aigv_llm_extend (the continuation and decode kernels take no mask), keep_kv != 0 under a
+ * mask, and a pass that is also armed with the score-attention probe (the probe does not know the mask).  Nothing is allocated. */
+int aigv_key_drop_arm(aigv_ctx* ctx, const uint64_t* words_dev, int ld_words);
 
 /* Replicate the n kept sequences `copies` times (cache slots [0, n) -> [n, 2n), ...; needs n * copies <= max_seqs): the copies can
  * then take DIFFERENT continuations in one aigv_llm_extend call over n * copies sequences (sequence c * n + b continues clip b),
@@ -398,6 +414,17 @@ int aigv_op_attention_ex(const void* q, int ldq, const void* k, int ldk, const v
                          int max_len, int n_heads, int n_kv_heads, int q_group_stride, int kv_head_stride, int64_t kv_seq_stride,
                          const int32_t* kv_off, int head_dim, int causal, float post_div, float q_prescale, const int32_t* pos, const void* cos,
                          const void* sin, int pos_is_row, int q_tail, void* stream);
+/* aigv_op_attention_ex under a key-drop mask (tests/test_gpu_key_drop.py): key_drop DEVICE uint64 [n_seq][ld_drop] or NULL (then the same call as
+ * aigv_op_attention_ex, the same kernels).  Bit (j & 63) of word key_drop[s * ld_drop + (j >> 6)] set = key j of sequence s is invisible to every
+ * query row and head; j is the key's absolute position in its sequence, cached keys first, so the packed form and the cache form (kv_off,
+ * kv_seq_stride) share one indexing.  A query row without a visible key is written as zeros.  Dropped keys' V rows must be finite.  Refused
+ * with AIGV_ERR_ARG and a message: key_drop with causal == 0 or head_dim != 128, a misaligned key_drop, and ld_drop < ceil((largest kv_off +
+ * max_len) / 64) - with kv_off the entry point reads the offsets back from the device for that check (it synchronises the stream; at most 256
+ * sequences). */
+int aigv_op_attention_drop(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, const int32_t* cu, int n_seq,
+                           int max_len, int n_heads, int n_kv_heads, int q_group_stride, int kv_head_stride, int64_t kv_seq_stride,
+                           const int32_t* kv_off, int head_dim, int causal, float post_div, float q_prescale, const int32_t* pos, const void* cos,
+                           const void* sin, int pos_is_row, int q_tail, const uint64_t* key_drop, int ld_drop, void* stream);
 /* The score-row attention probe on plain pointers (one layer; tests use it without a model): out [n_rows, n_heads, n_segments] fp32 as
  * aigv_score_attention_arm defines it.  q: UNROTATED fused rows (query head h at column (h / g) * q_group_stride + (h % g) * head_dim), rotated
  * by the kernel at the row's position from cos / sin [max_pos, head_dim / 2]; k: already rotated, in aigv_op_attention_ex's two forms -
