@@ -626,11 +626,23 @@ __global__ __launch_bounds__(NW * 64, (D == 64 && NW == 4) ? 4 : 2) void attn_fw
 // Rounding points as the eager path: score -> bf16, / sqrt(d) -> bf16, softmax fp32, P -> bf16 (un-normalised).
 constexpr int DC = 128;   // keys per chunk
 
-template <int G>
+// DROP = the key-drop form of pass 1 (aigv_launch_attention_decode's key_drop): the two words of the sequence's mask row that cover the chunk, bit j & 63
+// of word j >> 6 set = key j is invisible.  A dropped key's score is never formed from its K row: its slot in sS is -inf.  A chunk whose valid keys are all
+// dropped is written as m = -inf, l = 0 and zero sums without a read of K or V (the unmasked statements would form exp(-inf - (-inf)) = NaN), and so is a
+// head's row left without a finite score.  Pass 2 needs no form of its own: such a chunk's weight is exp(-inf - M) = +0 under a finite M, and when every
+// chunk of a sequence is empty M = -inf makes every weight and the denominator NaN, which fails `L > 0` and stores zeros - the prefill form's rule.
+// V rows of dropped keys in a partly visible chunk meet p = bf16(exp(-inf)) = +0: they must be finite.  Rounding points, key order and chunk order are
+// the unmasked kernel's; under an all-zero mask every statement computes what it computes there.  Every touch of the mask sits in an `if constexpr (DROP)`
+// of its own, and the mask travels in the parameter pack (DROP: const uint64_t* words, int ld; else empty), so that DROP = false keeps the kernarg segment
+// and the code it always had.
+struct DecodeDrop { const uint64_t* words; int ld; };
+
+template <int G, bool DROP = false, typename... Mask>
 __global__ __launch_bounds__(256) void attn_decode_partial_kernel(const bf16_t* __restrict__ q, int ldq, int q_group_stride,
                                                                   const bf16_t* __restrict__ kc, const bf16_t* __restrict__ vc,
                                                                   const int32_t* __restrict__ kv_lens, int cap, float post_div,
-                                                                  float* __restrict__ ws, int max_chunks) {
+                                                                  float* __restrict__ ws, int max_chunks, Mask... mask) {
+  static_assert(sizeof...(Mask) == (DROP ? 2 : 0), "the key-drop form takes (words, ld), the unmasked form nothing");
   constexpr int D = 128;
   __shared__ float sQ[G][D];
   __shared__ float sS[G][DC];          // scores, then probabilities
@@ -643,6 +655,22 @@ __global__ __launch_bounds__(256) void attn_decode_partial_kernel(const bf16_t* 
   float* wbase = ws + ((((size_t)seq * n_kv + hk) * max_chunks + chunk) * G) * (D + 2);
   if (key0 >= kv_len) return;                                       // pass 2 only visits chunks below kv_len
   const int nkeys = min(DC, kv_len - key0);
+  [[maybe_unused]] uint64_t dw0 = 0, dw1 = 0;   // DROP: the chunk's two mask words
+  if constexpr (DROP) {   // loaded once per workgroup (the row is sure to hold word 2 chunk + 1 only when the chunk has more than 64 keys: ld >= ceil(max_kv_len / 64))
+    __shared__ uint64_t sW[2];
+    const DecodeDrop dm{mask...};
+    if (t < 2) sW[t] = (t == 0 || nkeys > 64) ? dm.words[(size_t)seq * dm.ld + 2 * chunk + t] : 0ull;
+    __syncthreads();
+    dw0 = sW[0]; dw1 = sW[1];
+    // bits at or past kv_len are ignored
+    const uint64_t vis0 = ~dw0 & (nkeys >= 64 ? ~0ull : (1ull << nkeys) - 1);
+    const uint64_t vis1 = nkeys > 64 ? ~dw1 & (nkeys >= 128 ? ~0ull : (1ull << (nkeys - 64)) - 1) : 0ull;
+    if ((vis0 | vis1) == 0) {   // no visible key in this chunk: weight 0 in pass 2, K and V unread
+      for (int i = t; i < G * D; i += 256) wbase[(size_t)(i / D) * (D + 2) + 2 + i % D] = 0.f;
+      if (t < G) { wbase[(size_t)t * (D + 2)] = -INFINITY; wbase[(size_t)t * (D + 2) + 1] = 0.f; }
+      return;
+    }
+  }
   for (int i = t; i < G * D; i += 256) sQ[i / D][i % D] = bf2f(q[(size_t)seq * ldq + (size_t)hk * q_group_stride + i]);
   __syncthreads();
   const bf16_t* kb = kc + (((size_t)seq * n_kv + hk) * cap + key0) * D;
@@ -652,7 +680,9 @@ __global__ __launch_bounds__(256) void attn_decode_partial_kernel(const bf16_t* 
     float dot[G];
 #pragma unroll
     for (int j2 = 0; j2 < G; ++j2) dot[j2] = 0.f;
-    if (kk < nkeys) {
+    bool live = kk < nkeys;
+    if constexpr (DROP) live = live && !(((kk < 64 ? dw0 : dw1) >> (kk & 63)) & 1ull);   // a dropped key: K unread, -inf below
+    if (live) {
 #pragma unroll
       for (int c8 = 0; c8 < 8; ++c8) {
         const u16x8 raw = *(const u16x8*)(kb + (size_t)kk * D + half * 64 + c8 * 8);
@@ -670,7 +700,7 @@ __global__ __launch_bounds__(256) void attn_decode_partial_kernel(const bf16_t* 
       if (half == 0) {
         float sc = rbf(tot);
         if (post_div != 1.0f) sc = rbf(sc / post_div);
-        sS[j2][kk] = kk < nkeys ? sc : -INFINITY;
+        sS[j2][kk] = live ? sc : -INFINITY;
       }
     }
   }
@@ -678,7 +708,9 @@ __global__ __launch_bounds__(256) void attn_decode_partial_kernel(const bf16_t* 
   for (int j2 = wave; j2 < G; j2 += 4) {   // chunk softmax statistics: one wave per head
     const float a = sS[j2][lane], b = sS[j2][lane + 64];
     const float m = wave_max(fmaxf(a, b));
-    const float pa = __expf(a - m), pb = __expf(b - m);
+    float m_sub = m;
+    if constexpr (DROP) m_sub = m == -INFINITY ? 0.f : m;   // a row without a finite score: every p = exp(-inf) = 0 and l = 0 under m = -inf
+    const float pa = __expf(a - m_sub), pb = __expf(b - m_sub);
     const float l = wave_sum(pa + pb);
     sS[j2][lane] = rbf(pa);
     sS[j2][lane + 64] = rbf(pb);
@@ -902,14 +934,21 @@ size_t aigv_attention_decode_ws_floats(int n_seq, int n_kv, int g, int cap) {
 hipError_t aigv_launch_attention_decode(const bf16_t* q, int ldq, int q_group_stride, const bf16_t* kc,
                                         const bf16_t* vc, const int32_t* kv_lens, int cap, bf16_t* o, int ldo,
                                         int n_seq, int n_kv, int g, int head_dim, float post_div, int max_kv_len,
-                                        float* ws, hipStream_t s) {
+                                        float* ws, hipStream_t s, const uint64_t* key_drop, int ld_drop) {
+  if (key_drop && (((uintptr_t)key_drop & 7) || ld_drop < (max_kv_len + 63) / 64)) return hipErrorInvalidValue;
   if (head_dim != 128 || !ws || max_kv_len <= 0 || max_kv_len > cap || (cap + DC - 1) / DC > AIGV_DECODE_MAX_CHUNKS) return hipErrorInvalidValue;
   const int max_chunks = (cap + DC - 1) / DC;
   const size_t merge_lds = (size_t)2 * merge_heads(g) * max_chunks * sizeof(float);   // <= 32 KB: no LDS attribute needed
   dim3 grid1((max_kv_len + DC - 1) / DC, n_kv, n_seq), grid2(n_kv * (g >= 2 ? (g + 1) / 2 : 1), n_seq);
-#define DEC(G)                                                                                                              \
-  hipLaunchKernelGGL((attn_decode_partial_kernel<G>), grid1, dim3(256), 0, s, q, ldq, q_group_stride, kc, vc, kv_lens, cap, \
-                     post_div, ws, max_chunks);                                                                              \
+  // (a null key_drop reaches the instantiations it always reached; the merge pass serves both forms: see attn_decode_partial_kernel)
+#define DEC(G)                                                                                                                \
+  if (key_drop) {                                                                                                             \
+    hipLaunchKernelGGL((attn_decode_partial_kernel<G, true, const uint64_t*, int>), grid1, dim3(256), 0, s, q, ldq,           \
+                       q_group_stride, kc, vc, kv_lens, cap, post_div, ws, max_chunks, key_drop, ld_drop);                    \
+  } else {                                                                                                                    \
+    hipLaunchKernelGGL((attn_decode_partial_kernel<G>), grid1, dim3(256), 0, s, q, ldq, q_group_stride, kc, vc, kv_lens, cap, \
+                       post_div, ws, max_chunks);                                                                             \
+  }                                                                                                                           \
   hipLaunchKernelGGL((attn_decode_merge_kernel<G>), grid2, dim3(256), merge_lds, s, ws, max_chunks, kv_lens, o, ldo)
   switch (g) {
     case 1: DEC(1); break;

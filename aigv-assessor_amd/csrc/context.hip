@@ -86,6 +86,7 @@ static int alloc_workspaces(aigv_ctx* c) {
   c->ws_phase = true;
   c->kc = c->vc = nullptr;   // (no KV capacity: no caches)
   c->kc_alt = c->vc_alt = nullptr; c->beam_ints = nullptr;
+  c->kv_drop = c->kv_drop_alt = nullptr; c->kv_drop_ld = 0; c->kv_masked = false;
   c->dec_ws = nullptr; c->dec_pos = c->dec_seq = c->dec_kvlen = c->dec_slot = nullptr;
   const size_t vr = (size_t)k.vit_chunk * c->S;
   const size_t pr = (size_t)k.vit_chunk * c->ntok;
@@ -149,6 +150,9 @@ static int alloc_workspaces(aigv_ctx* c) {
       const size_t per = (size_t)k.llm_layers * k.max_seqs * k.llm_kv_heads * k.kv_capacity * c->head_dim;
       if ((rc = dalloc(c, &c->kc, per))) break;
       if ((rc = dalloc(c, &c->vc, per))) break;
+      c->kv_drop_ld = (k.kv_capacity + 63) / 64;   // the caches' key-drop mask and the buffer aigv_kv_reorder gathers it into (a few KB: never made inside a pass)
+      if ((rc = dalloc(c, &c->kv_drop, (size_t)k.max_seqs * c->kv_drop_ld))) break;
+      if ((rc = dalloc(c, &c->kv_drop_alt, (size_t)k.max_seqs * c->kv_drop_ld))) break;
       if ((rc = dalloc(c, &c->dec_ws, aigv_attention_decode_ws_floats(k.max_seqs, k.llm_kv_heads, c->g, k.kv_capacity)))) break;
       if ((rc = dalloc(c, &c->dec_pos, (size_t)k.max_seqs))) break;
       if ((rc = dalloc(c, &c->dec_seq, (size_t)k.max_seqs))) break;
@@ -250,7 +254,7 @@ int aigv_ctx_resize(aigv_ctx* c, const aigv_config* cfg) {
   }
   const int old_pos = c->cfg.max_positions;
   c->cfg = b;
-  c->kv_valid = false;
+  c->kv_valid = false;   // (alloc_workspaces clears kv_masked with the mask buffers it re-makes)
   int rc = alloc_workspaces(c);
   if (!rc && had_q8) {
     rc = dalloc(c, &c->q8, (size_t)b.max_tokens * (size_t)std::max(b.llm_hidden, b.llm_inter));

@@ -108,6 +108,12 @@ struct aigv_ctx {
   bf16_t *kc = nullptr, *vc = nullptr;   // [layer][seq][kv head][cap][D]
   bf16_t *kc_alt = nullptr, *vc_alt = nullptr;   // second cache of the same size, made by the first aigv_kv_reorder (beam search gathers into it, then the two swap)
   int32_t* beam_ints = nullptr;                  // [2 * max_seqs]: parent slots | live lengths of a reorder
+  // Key-drop mask of the KV cache, [max_seqs][kv_drop_ld = ceil(kv_capacity / 64)] words in AttnArgs::key_drop's layout by absolute position: allocated, freed
+  // and resized with the caches.  Written by aigv_llm_prefill(keep_kv) under an armed mask, which sets kv_masked (an unmasked keep_kv prefill clears it);
+  // read by aigv_llm_extend and the decode steps while kv_masked; aigv_kv_fork replicates its rows, aigv_kv_reorder gathers them into kv_drop_alt and swaps.
+  uint64_t *kv_drop = nullptr, *kv_drop_alt = nullptr;
+  int kv_drop_ld = 0;
+  bool kv_masked = false;
   float* dec_ws = nullptr;
   float2* dec_lse = nullptr;  // aigv_decode_step_logprob: per-16-column log-sum-exp partials [min(max_seqs, 64)][ceil(vocab / 16)]
   bf16_t* dec_cand = nullptr; // aigv_decode_step_cand_logprob: bf16 logits of the candidate columns [min(max_seqs, 64)][AIGV_MAX_CANDIDATES]
@@ -126,7 +132,8 @@ struct aigv_ctx {
     float* tok = nullptr;   // aigv_score_attention_arm_tokens: the dense rows [n_rows][layers][n_heads][ld_tok], else nullptr / 0
     int ld_tok = 0;
   } probe;
-  // key-drop mask (aigv_key_drop_arm): armed for exactly the next aigv_llm_prefill, which applies it in every layer's attention
+  // key-drop mask (aigv_key_drop_arm): armed for exactly the next aigv_llm_prefill, which applies it in every layer's attention (keep_kv: and keeps
+  // it with the cache, kv_drop above)
   struct {
     bool armed = false;
     const uint64_t* words = nullptr;   // device: [n_clips][ld] words, AttnArgs::key_drop's layout

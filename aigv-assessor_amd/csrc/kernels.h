@@ -123,13 +123,18 @@ hipError_t aigv_launch_attention(const AttnArgs& a, int head_dim, hipStream_t s)
 // decode: one query row per sequence (fused qkv row), KV cache [seq][kv head][cap][D]; split-KV two-pass kernel,
 // ws = aigv_attention_decode_ws_floats(...) floats of scratch.  The merge pass holds 16 bytes of LDS per 128-key chunk of the
 // capacity: at most AIGV_DECODE_MAX_CHUNKS chunks (= AIGV_MAX_KV_CAPACITY tokens, include/aigv_amd.h)
+// key_drop (device, [n_seq][ld_drop] words in AttnArgs::key_drop's layout, 8-byte aligned, ld_drop >= ceil(max_kv_len / 64); null = no key is dropped,
+// the kernels that have always run): the masked form of the first pass.  A dropped key's score is never formed from its K row; a 128-key chunk without a
+// visible key is written as m = -inf, l = 0, zero sums without a read of K or V, and the merge pass gives it weight 0; a sequence without a visible key is
+// written as zeros.  The V rows of dropped keys inside a partly visible chunk must be finite (they are multiplied by an exact 0).  Bits at or past
+// kv_lens[seq] are ignored.
 constexpr int AIGV_DECODE_KEYS_PER_CHUNK = 128;
 constexpr int AIGV_DECODE_MAX_CHUNKS = 2048;
 size_t aigv_attention_decode_ws_floats(int n_seq, int n_kv, int g, int cap);
 hipError_t aigv_launch_attention_decode(const bf16_t* q, int ldq, int q_group_stride, const bf16_t* kc,
                                         const bf16_t* vc, const int32_t* kv_lens, int cap, bf16_t* o, int ldo,
                                         int n_seq, int n_kv, int g, int head_dim, float post_div, int max_kv_len,
-                                        float* ws, hipStream_t s);
+                                        float* ws, hipStream_t s, const uint64_t* key_drop = nullptr, int ld_drop = 0);
 
 // ---- attention probe (attnprobe.hip) ----------------------------------------------------------------
 // Where ONE query row of a causal GQA attention looks: out[row][head][seg] = sum of softmax(q . K / post_div) over the keys of segment
@@ -303,3 +308,7 @@ hipError_t aigv_launch_write_ints(const int32_t* host, int n, int32_t* dst, hipS
 // beam search: new KV cache slot i = the first lens[i] positions of slot parent[i] of the current cache (all layers, all kv heads); dst != src
 hipError_t aigv_launch_kv_reorder(const bf16_t* sk, const bf16_t* sv, bf16_t* dk, bf16_t* dv, const int32_t* parent, const int32_t* lens, int n,
                                   int layers, int nkv, int cap, int D, size_t kv_layer, int max_len, hipStream_t s);
+// the KV cache's key-drop mask: dst row i [ld_dst words] = src row parent[i] (null: i) [ld_src words] cut to its first len(i) keys, zero behind them;
+// len(i) = lens[i], or (lens_are_cu) lens[i + 1] - lens[i]; every pointer on the device, dst != src
+hipError_t aigv_launch_kv_drop_rows(const uint64_t* src, int ld_src, const int32_t* parent, const int32_t* lens, int lens_are_cu, uint64_t* dst, int ld_dst,
+                                    int n, hipStream_t s);

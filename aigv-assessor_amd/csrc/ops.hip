@@ -347,10 +347,9 @@ int64_t aigv_op_attention_decode_ws_floats(int n_seq, int n_kv, int g, int cap) 
   return (int64_t)aigv_attention_decode_ws_floats(n_seq, n_kv, g, cap);
 }
 
-int aigv_op_attention_decode(const void* q, int ldq, int q_group_stride, const void* kc, const void* vc, const int32_t* kv_lens, int cap,
-                             void* o, int ldo, int n_seq, int n_kv, int g, int head_dim, float post_div, int max_kv_len, float* ws,
-                             int64_t ws_floats, void* stream) {
-  const char* op = "aigv_op_attention_decode";
+static int attention_decode_op(const char* op, const void* q, int ldq, int q_group_stride, const void* kc, const void* vc, const int32_t* kv_lens, int cap,
+                               void* o, int ldo, int n_seq, int n_kv, int g, int head_dim, float post_div, int max_kv_len, float* ws,
+                               int64_t ws_floats, const uint64_t* key_drop, int ld_drop, void* stream) {
   if (!q || !kc || !vc || !kv_lens || !o || !ws) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
   if (head_dim != 128) return fail(nullptr, AIGV_ERR_ARG, "%s: head_dim must be 128, got %d", op, head_dim);
   if (g < 1 || g > 8) return fail(nullptr, AIGV_ERR_ARG, "%s: g = %d query heads per KV head (1..8)", op, g);
@@ -362,9 +361,29 @@ int aigv_op_attention_decode(const void* q, int ldq, int q_group_stride, const v
   if (!aligned16(kc) || !aligned16(vc)) return fail(nullptr, AIGV_ERR_ARG, "%s: the caches must be 16-byte aligned", op);
   const int64_t need = aigv_op_attention_decode_ws_floats(n_seq, n_kv, g, cap);
   if (ws_floats < need) return fail(nullptr, AIGV_ERR_ARG, "%s: workspace of %lld floats, needs %lld", op, (long long)ws_floats, (long long)need);
+  if (key_drop) {
+    if ((uintptr_t)key_drop & 7) return fail(nullptr, AIGV_ERR_ARG, "%s: key_drop must be 8-byte aligned", op);
+    if (ld_drop < (max_kv_len + 63) / 64)
+      return fail(nullptr, AIGV_ERR_ARG, "%s: ld_drop = %d is below ceil(max_kv_len / 64) = %d words per sequence", op, ld_drop, (max_kv_len + 63) / 64);
+  }
   HIPCHK(nullptr, aigv_launch_attention_decode((const bf16_t*)q, ldq, q_group_stride, (const bf16_t*)kc, (const bf16_t*)vc, kv_lens, cap, (bf16_t*)o,
-                                               ldo, n_seq, n_kv, g, head_dim, post_div, max_kv_len, ws, (hipStream_t)stream));
+                                               ldo, n_seq, n_kv, g, head_dim, post_div, max_kv_len, ws, (hipStream_t)stream, key_drop, ld_drop));
   return 0;
+}
+
+int aigv_op_attention_decode(const void* q, int ldq, int q_group_stride, const void* kc, const void* vc, const int32_t* kv_lens, int cap,
+                             void* o, int ldo, int n_seq, int n_kv, int g, int head_dim, float post_div, int max_kv_len, float* ws,
+                             int64_t ws_floats, void* stream) {
+  return attention_decode_op("aigv_op_attention_decode", q, ldq, q_group_stride, kc, vc, kv_lens, cap, o, ldo, n_seq, n_kv, g, head_dim, post_div, max_kv_len, ws,
+                             ws_floats, nullptr, 0, stream);
+}
+
+// aigv_op_attention_decode under a key-drop mask (aigv_launch_attention_decode's key_drop; null: the same call as aigv_op_attention_decode)
+int aigv_op_attention_decode_drop(const void* q, int ldq, int q_group_stride, const void* kc, const void* vc, const int32_t* kv_lens, int cap,
+                                  void* o, int ldo, int n_seq, int n_kv, int g, int head_dim, float post_div, int max_kv_len, float* ws,
+                                  int64_t ws_floats, const uint64_t* key_drop, int ld_drop, void* stream) {
+  return attention_decode_op("aigv_op_attention_decode_drop", q, ldq, q_group_stride, kc, vc, kv_lens, cap, o, ldo, n_seq, n_kv, g, head_dim, post_div, max_kv_len,
+                             ws, ws_floats, key_drop, ld_drop, stream);
 }
 
 // shared checks of the RoPE / KV-append GEMVs (bf16 and e4m3 forms)

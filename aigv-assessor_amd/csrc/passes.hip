@@ -277,7 +277,6 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
   DisarmScope disarm(c);
   if (!c->finalized) return fail(c, AIGV_ERR_STATE, "aigv_llm_prefill: call aigv_finalize_weights first");
   if (dropping && probing) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: a key-drop mask and the score-attention probe are both armed: the probe does not know the mask");
-  if (dropping && keep_kv) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: a key-drop mask with keep_kv: the continuation and decode kernels take no mask");
   const aigv_config& k = c->cfg;
   if (B <= 0 || B > k.max_seqs) return fail(c, AIGV_ERR_ARG, "n_clips %d outside 1..%d", B, k.max_seqs);
   if (cu[0] != 0) return fail(c, AIGV_ERR_ARG, "cu_seqlens[0] must be 0");
@@ -395,14 +394,19 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
     c->h_kvlen.resize(B);
     for (int b = 0; b < B; ++b) c->h_kvlen[b] = cu[b + 1] - cu[b];
     TRY(upload_decode_state(c, B, s));
+    // a masked pass keeps its mask with the cache: every clip's words cut to its length, zero from there to the row's end (on the pass's stream, into
+    // the context's own buffer: nothing is allocated, the pass still captures); aigv_llm_extend and the decode steps then run under it
+    if (dropping) HIPCHK(c, aigv_launch_kv_drop_rows(c->drop.words, c->drop.ld, nullptr, c->l_cu, 1, c->kv_drop, c->kv_drop_ld, B, s));
+    c->kv_masked = dropping;
     c->kv_valid = true;
   } else {
     c->kv_valid = false;
+    c->kv_masked = false;
   }
   return 0;
 }
 
-// Arms the next aigv_llm_prefill with a key-drop mask (include/aigv_amd.h): the words are read when that pass runs.
+// Arms the next aigv_llm_prefill with a key-drop mask (include/aigv_amd.h): the words are read when that pass runs (keep_kv: and copied into the cache's mask).
 int aigv_key_drop_arm(aigv_ctx* c, const uint64_t* words_dev, int ld_words) {
   if (!c) return fail(c, AIGV_ERR_ARG, "aigv_key_drop_arm: null context");
   if (!words_dev || ((uintptr_t)words_dev & 7)) return fail(c, AIGV_ERR_ARG, "aigv_key_drop_arm: words_dev is null or not 8-byte aligned");
@@ -422,13 +426,15 @@ int aigv_llm_extend(aigv_ctx* c, const int64_t* ids, const int32_t* cu, int B, c
   DisarmScope disarm(c);
   if (dropping) return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: a key-drop mask is armed (aigv_key_drop_arm): the continuation pass takes no mask, only aigv_llm_prefill does");
   if (!c->kv_valid) return fail(c, AIGV_ERR_STATE, "aigv_llm_extend: no KV state (run aigv_llm_prefill with keep_kv)");
+  if (probing && c->kv_masked) return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: the score-attention probe is armed and the KV cache carries a key-drop mask: the probe does not know the mask");
   const aigv_config& k = c->cfg;
   if (B != c->kv_seqs) return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: %d sequences, the cache holds %d", B, c->kv_seqs);
   if (B + 1 > AIGV_SMALL_INTS / 2) return fail(c, AIGV_ERR_ARG, "at most %d clips per call", AIGV_SMALL_INTS / 2 - 1);
   if (cu[0] != 0) return fail(c, AIGV_ERR_ARG, "cu_seqlens[0] must be 0");
-  int max_new = 0;
+  int max_new = 0, max_cached = 0;
   for (int b = 0; b < B; ++b) {
     const int n = cu[b + 1] - cu[b];
+    max_cached = std::max(max_cached, (int)c->h_kvlen[b]);
     if (n <= 0) return fail(c, AIGV_ERR_ARG, "clip %d: no new tokens", b);
     if (c->h_kvlen[b] + n > k.kv_capacity || c->h_kvlen[b] + n > k.max_positions)
       return fail(c, AIGV_ERR_STATE, "clip %d: KV cache / RoPE table exhausted (%d cached + %d new, capacity %d)", b, c->h_kvlen[b], n, k.kv_capacity);
@@ -463,6 +469,9 @@ int aigv_llm_extend(aigv_ctx* c, const int64_t* ids, const int32_t* cu, int B, c
       a.ldk = a.ldv = D; a.kv_head_stride = k.kv_capacity * D; a.kv_seq_stride = (size_t)nkv * k.kv_capacity * D;
       a.kv_off = c->l_kvlen;
       a.max_len = max_new;
+      // a masked cache: the key-drop form under the cache's mask (by absolute position; the new rows' bits are clear, so they see each other and not
+      // what was hidden in front of them); kv_len_offset states the largest cached length for the check, the kernel reads kv_off
+      if (c->kv_masked) { a.key_drop = c->kv_drop; a.ld_drop = c->kv_drop_ld; a.kv_len_offset = max_cached; }
       if (const char* m = aigv_attn_check(a, D)) return fail(c, AIGV_ERR_ARG, "%s", m);
       ProfScope ps(c, AIGV_PROF_ATTN_LLM, attn_flops, 2.0 * T * ((double)c->qkv_out + H), s);
       HIPCHK(c, aigv_launch_attention(a, D, s));
@@ -500,6 +509,9 @@ int aigv_kv_fork(aigv_ctx* c, int copies, void* stream) {
       HIPCHK(c, hipMemcpyAsync(c->kc + li * kv_layer + (size_t)cpy * B * slot, c->kc + li * kv_layer, (size_t)B * slot * sizeof(bf16_t), hipMemcpyDeviceToDevice, s));
       HIPCHK(c, hipMemcpyAsync(c->vc + li * kv_layer + (size_t)cpy * B * slot, c->vc + li * kv_layer, (size_t)B * slot * sizeof(bf16_t), hipMemcpyDeviceToDevice, s));
     }
+  if (c->kv_masked)   // the mask rows go with their slots
+    for (int cpy = 1; cpy < copies; ++cpy)
+      HIPCHK(c, hipMemcpyAsync(c->kv_drop + (size_t)cpy * B * c->kv_drop_ld, c->kv_drop, (size_t)B * c->kv_drop_ld * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
   const int N = B * copies;
   c->h_kvlen.resize(N);
   for (int i = B; i < N; ++i) c->h_kvlen[i] = c->h_kvlen[i % B];
@@ -549,6 +561,10 @@ int aigv_kv_reorder(aigv_ctx* c, const int32_t* parent, const int32_t* len, int 
   if (e != hipSuccess) return fail(c, AIGV_ERR_HIP, "aigv_kv_reorder (n=%d): %s", n, hipGetErrorString(e));
   std::swap(c->kc, c->kc_alt);
   std::swap(c->vc, c->vc_alt);
+  if (c->kv_masked) {   // the mask rows are gathered by parent like the slots (cut to len: what a beam appends is visible), then the two buffers swap
+    HIPCHK(c, aigv_launch_kv_drop_rows(c->kv_drop, c->kv_drop_ld, c->beam_ints, c->beam_ints + k.max_seqs, 0, c->kv_drop_alt, c->kv_drop_ld, n, s));
+    std::swap(c->kv_drop, c->kv_drop_alt);
+  }
   return 0;
 }
 
@@ -596,7 +612,7 @@ static int decode_attention(aigv_ctx* c, int li, int B, int max_vis, hipStream_t
   const size_t kv_layer = (size_t)k.max_seqs * nkv * k.kv_capacity * D;
   HIPCHK(c, aigv_launch_attention_decode(c->l_qkv, c->qkv_out, (g + 2) * D, c->kc + li * kv_layer, c->vc + li * kv_layer,
                                          c->dec_kvlen, k.kv_capacity, c->l_ao, H, B, nkv, g, D, sqrtf((float)D), max_vis,
-                                         c->dec_ws, s));
+                                         c->dec_ws, s, c->kv_masked ? c->kv_drop : nullptr, c->kv_drop_ld));   // a masked cache: the key-drop form (the appended keys' bits are clear)
   return 0;
 }
 

@@ -413,6 +413,33 @@ hipError_t aigv_launch_kv_reorder(const bf16_t* sk, const bf16_t* sv, bf16_t* dk
   return hipGetLastError();
 }
 
+// Rows of a key-drop mask (AttnArgs::key_drop's words) into the KV cache's mask: row i of dst = row parent[i] (null: i) of src cut to its first len(i)
+// keys - len(i) = lens[i], or lens[i + 1] - lens[i] of a cu_seqlens array - and zero from there to ld_dst words, so that keys appended later start out visible.
+// dst != src.  One thread per word.
+namespace {
+__global__ __launch_bounds__(256) void kv_drop_rows_kernel(const uint64_t* __restrict__ src, int ld_src, const int32_t* __restrict__ parent,
+                                                           const int32_t* __restrict__ lens, int lens_are_cu, uint64_t* __restrict__ dst, int ld_dst, int n) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n * ld_dst) return;
+  const int i = idx / ld_dst, w = idx - i * ld_dst;
+  const int len = lens_are_cu ? lens[i + 1] - lens[i] : lens[i];
+  const int live = len - 64 * w;                            // keys of this word below the length
+  uint64_t word = 0;
+  if (w < ld_src && live > 0) {
+    word = src[(size_t)(parent ? parent[i] : i) * ld_src + w];
+    if (live < 64) word &= (1ull << live) - 1;
+  }
+  dst[idx] = word;
+}
+}  // namespace
+
+hipError_t aigv_launch_kv_drop_rows(const uint64_t* src, int ld_src, const int32_t* parent, const int32_t* lens, int lens_are_cu, uint64_t* dst, int ld_dst,
+                                    int n, hipStream_t s) {
+  if (!src || !lens || !dst || src == dst || ld_src < 1 || ld_dst < 1 || n < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kv_drop_rows_kernel, dim3((n * ld_dst + 255) / 256), dim3(256), 0, s, src, ld_src, parent, lens, lens_are_cu, dst, ld_dst, n);
+  return hipGetLastError();
+}
+
 hipError_t aigv_launch_write_ints(const int32_t* host, int n, int32_t* dst, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   for (int off = 0; off < n; off += AIGV_SMALL_INTS) {

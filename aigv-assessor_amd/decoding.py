@@ -7,7 +7,7 @@ from typing import List, Optional
 
 import torch
 
-from . import generation, native, readouts
+from . import generation, native, prompts, readouts
 from .conversation import get_conv_template
 
 
@@ -39,7 +39,7 @@ class Generation:
     EOS_CHECK_EVERY = 8     # tokens between two host reads of the device-side "finished" flags
 
     def _greedy(self, ids_packed, slot, cu, vis, n_vis, max_new_tokens: int, eos_ids: List[int], pad_id: int, motion=None, sampler=None,
-                processors=None, beams=None, flags=None, cand=None, topk: int = 0):
+                processors=None, beams=None, flags=None, cand=None, topk: int = 0, drop_words=None):
         """The token loop of generate(): HF's greedy search / multinomial sampling loop (the reference calls ``language_model.generate``,
         modeling_internvl_chat.py:798-809).  The end-of-sequence bookkeeping runs on the device (aigv_decode_eos): a finished sequence
         emits ``pad_id``, the loop stops once every sequence has emitted an end token - checked by the host only every EOS_CHECK_EVERY
@@ -56,7 +56,11 @@ class Generation:
 
         ``topk`` (``top_logprobs=k``): ``top_ids`` / ``top_logprobs`` [B, T, k], the k most likely tokens of every step under the RAW logits -
         from the fused decode step (aigv_decode_step_topk_logprob; the first token's from aigv_out_row_topk_logprob) on the greedy path
-        without processors, else generation.top_logprobs of the step's raw logits."""
+        without processors, else generation.top_logprobs of the step's raw logits.
+
+        ``drop_words`` (``key_drop``: host int64 [B, W], ``_gen_drop_words``): the prompt pass runs masked and keeps the mask with its KV cache
+        (aigv_key_drop_arm in front of aigv_llm_prefill(keep_kv)); every decode step, the beams' fork and reorder included, then runs under the
+        cache's mask.  Nothing here is captured into a graph: a masked generation runs eagerly like every other."""
         flags = flags or {k: False for k in generation.FLAGS}
         dict_out = generation.wants_output(flags) or cand is not None or bool(topk)
         b = len(cu) - 1
@@ -65,7 +69,7 @@ class Generation:
         nb = beams["num_beams"] if beams else 1
         self._native(seq_len=longest, n_clips=b * nb, out_rows=b * nb)       # (beam search: room for every beam before the prompt pass)
         _, nxt = self._prefill(ids_packed, slot, cu, vis, n_vis, motion, None, last_rows, keep_kv=True,
-                               kv_cap=longest + max_new_tokens + 1)
+                               kv_cap=longest + max_new_tokens + 1, drop_words=drop_words)
         lib, ctx = native.load(), self._ctx
         if beams:
             seq, seq_scores = self._beam_decode(b, [cu[i + 1] - cu[i] for i in range(b)], max_new_tokens, eos_ids, pad_id, processors or [], **beams)
@@ -226,6 +230,25 @@ class Generation:
         native.check(lib.aigv_out_row_hidden(ctx, first_row, n_rows, buf.data_ptr(), H, native.stream_ptr()), ctx)
         return buf
 
+    @staticmethod
+    def _gen_drop_words(key_drop, ids_shape, cu, row_of):
+        """``generate*(key_drop=...)``: None, or the mask [B, N] (laid out like the call's ``input_ids`` / embeddings) checked on the host - before anything
+        is launched - and turned into ``prompts.key_drop_words`` (host int64 [B, W]).  ``cu`` / ``row_of``: the packed prompt (``_pack``).  Padded
+        positions are ignored.  Refused: a wrong shape or dtype (``readouts.key_drop_mask``), a clip's first token (it guarantees every row a
+        visible key) and a clip's last prompt token (its row predicts the first new token: the consumed row of ``forward``'s rule)."""
+        kd = readouts.key_drop_mask(key_drop, ids_shape)
+        if kd is None:
+            return None
+        row_of = row_of.detach().to("cpu")
+        dropped = torch.zeros(cu[-1], dtype=torch.bool)
+        dropped[row_of[kd & (row_of >= 0)]] = True
+        for b in range(len(cu) - 1):
+            if bool(dropped[cu[b]]):
+                raise ValueError(f"key_drop: clip {b}: the first token cannot be dropped (it guarantees every row a visible key)")
+            if bool(dropped[cu[b + 1] - 1]):
+                raise ValueError(f"key_drop: clip {b}: the last prompt token is a consumed row (it predicts the first new token) and cannot be dropped")
+        return prompts.key_drop_words(kd, cu, row_of)
+
     def _gen_setup(self, generation_config, generate_kwargs):
         """What the three generate entry points read from their generation config / kwargs (``candidate_ids`` and ``top_logprobs`` are taken out of
         the kwargs): (max_new_tokens, eos ids, pad id, ``_greedy``'s keyword arguments)."""
@@ -239,7 +262,7 @@ class Generation:
     @torch.no_grad()
     def generate(self, pixel_values: Optional[torch.Tensor] = None, input_ids: Optional[torch.Tensor] = None,
                  attention_mask: Optional[torch.Tensor] = None, visual_features: Optional[torch.Tensor] = None,
-                 generation_config=None, output_hidden_states=None, return_dict=None, **generate_kwargs) -> torch.Tensor:
+                 generation_config=None, output_hidden_states=None, return_dict=None, key_drop=None, **generate_kwargs) -> torch.Tensor:
         """modeling_internvl_chat.py:769-811: every <IMG_CONTEXT> slot takes a visual token (no motion
         token), then greedy decode with a KV cache.  Returns the NEW tokens [B, <=max_new_tokens] - or, with HF's
         ``return_dict_in_generate`` (``output_scores`` / ``output_logits``) or ``return_logprobs``, a generation.GenerateOutput
@@ -255,9 +278,19 @@ class Generation:
         what the model preferred at every step: the k largest RAW lm-head logits (equal logits by ascending id, so entry 0 is the greedy
         token) and their full-vocabulary log-probabilities; -1 / NaN after a sequence's end token.  Greedy decoding without processors
         selects them in the decode step's own lm-head pass (aigv_decode_step_topk_logprob: ``top_logprobs[:, :, 0]`` is ``logprobs``, bit
-        for bit); otherwise they are ``generation.top_logprobs`` of the step's raw logits.  Beam search refuses them."""
+        for bit); otherwise they are ``generation.top_logprobs`` of the step's raw logits.  Beam search refuses them.
+
+        ``key_drop`` (bool or integer tensor [B, N] laid out like ``input_ids``, on any device): WHAT IF these prompt tokens were not there - what
+        the model SAYS without them.  True = the token is hidden, as a key, from every later row of its clip: the prompt pass runs masked as
+        ``forward(key_drop=...)`` does, the mask stays with the KV cache, and every generated token attends under it (the generated tokens see
+        each other).  Positions stay as they are.  Composes with ``candidate_ids``, ``top_logprobs``, ``return_logprobs``, sampling, processors
+        and beam search.  ValueError before anything is launched: a wrong shape or dtype, a clip's first token, a clip's last prompt token (its
+        row predicts the first new token)."""
         assert self.img_context_token_id is not None
         max_new, eos, pad, how = self._gen_setup(generation_config, generate_kwargs)
+        if key_drop is not None:        # checked in full on the host first
+            _, cu_h, row_of = self._pack(input_ids.detach().to("cpu"), attention_mask.detach().to("cpu") if attention_mask is not None else None)
+            how["drop_words"] = self._gen_drop_words(key_drop, input_ids.shape, cu_h, row_of)
         dev = self.device
         input_ids = input_ids.to(dev)
         ids_packed, cu, _ = self._pack(input_ids, attention_mask.to(dev) if attention_mask is not None else None)
@@ -276,11 +309,16 @@ class Generation:
 
     @torch.no_grad()
     def generate2(self, input_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, visual_features=None,
-                  generation_config=None, output_hidden_states=None, return_dict=None, **generate_kwargs) -> torch.Tensor:
-        """modeling_internvl_chat.py:812-853: decode from precomputed input embeddings [B, N, C].  Output flags, ``candidate_ids`` and ``top_logprobs`` as ``generate``."""
+                  generation_config=None, output_hidden_states=None, return_dict=None, key_drop=None, **generate_kwargs) -> torch.Tensor:
+        """modeling_internvl_chat.py:812-853: decode from precomputed input embeddings [B, N, C].  Output flags, ``candidate_ids``, ``top_logprobs`` and
+        ``key_drop`` (laid out like the embeddings' [B, N]) as ``generate``."""
         max_new, eos, pad, how = self._gen_setup(generation_config, generate_kwargs)
         dev = self.device
         b, n, _ = input_embeds.shape
+        if key_drop is not None:        # checked in full on the host first
+            mask_h = torch.ones((b, n), dtype=torch.bool) if attention_mask is None else attention_mask.detach().to("cpu").bool()
+            _, cu_h, row_of = self._pack(torch.zeros((b, n), dtype=torch.long), mask_h)
+            how["drop_words"] = self._gen_drop_words(key_drop, (b, n), cu_h, row_of)
         mask = torch.ones((b, n), dtype=torch.bool, device=dev) if attention_mask is None else attention_mask.to(dev).bool()
         emb = input_embeds.to(dev)[mask].to(torch.bfloat16).contiguous()
         cu = list(accumulate((int(x) for x in mask.sum(1).tolist()), initial=0))
@@ -291,29 +329,36 @@ class Generation:
 
     @torch.no_grad()
     def generate_stage2(self, pixel_values, input_ids, attention_mask=None, image_flags=None, motion_feature=None,
-                        generation_config=None, **generate_kwargs) -> torch.LongTensor:
+                        generation_config=None, visual_tokens=None, key_drop=None, **generate_kwargs) -> torch.LongTensor:
         """Greedy decode behind a stage-2 prompt: the embedding assembly of the reference's ``chat2``
         (modeling_internvl_chat.py:642-707: all <IMG_CONTEXT> slots but the last of each clip take visual tokens, the last one the
         motion token) followed by its ``generate2``.  Ids and slot map go to the native prefill, whose embed kernel gathers
-        token / visual / motion rows - no embedding tensor is assembled on the host side."""
+        token / visual / motion rows - no embedding tensor is assembled on the host side.
+
+        ``visual_tokens`` (``vit_tokens(pixel_values)``, with ``motion_feature``): the visual front computed once and handed to several calls, as
+        ``forward`` takes them; ``pixel_values`` may then be None.  ``key_drop`` [B, N] as ``generate``: ``unit_masks`` builds the per-frame masks,
+        ``eval_utils.frame_ablation_generate`` the per-frame replies."""
         if self.img_context_token_id is None:
             raise AssertionError("img_context_token_id must be set (stage2_eval.py:810)")
         max_new, eos, pad, how = self._gen_setup(generation_config, generate_kwargs)
         B = input_ids.shape[0]
-        plan = self._plan(input_ids, attention_mask, None, image_flags, pixel_values.shape[0], drop_dead_tail=False)
+        n_frames = visual_tokens.shape[0] if visual_tokens is not None else pixel_values.shape[0]
+        plan = self._plan(input_ids, attention_mask, None, image_flags, n_frames, drop_dead_tail=False)
+        how["drop_words"] = self._gen_drop_words(key_drop, input_ids.shape, plan["cu"], plan["row_of"])      # (host only: before anything is launched)
         motion_feature = self._motion_feature(pixel_values, B, motion_feature)
-        self._native(n_frames=pixel_values.shape[0], n_tokens=plan["cu"][-1], n_clips=B)
-        vit_embeds, motion = self._visual_inputs(pixel_values, None, motion_feature, plan)
+        self._native(n_frames=n_frames, n_tokens=plan["cu"][-1], n_clips=B)
+        vit_embeds, motion = self._visual_inputs(pixel_values, visual_tokens, motion_feature, plan)
         return self._greedy(plan["ids_packed"], plan["slot"], plan["cu"], vit_embeds, plan["n_vis"], max_new, eos, pad, motion=motion, **how)
 
     def chat2(self, tokenizer, pixel_values, input_ids, generation_config, attention_mask, history=None,
               return_history=False, image_flags=None, IMG_START_TOKEN="<img>", IMG_END_TOKEN="</img>",
-              IMG_CONTEXT_TOKEN="<IMG_CONTEXT>", verbose=False, motion_feature=None):
-        """modeling_internvl_chat.py:638-767: pre-tokenised stage-2 prompt (with the motion slot) -> decoded response."""
+              IMG_CONTEXT_TOKEN="<IMG_CONTEXT>", verbose=False, motion_feature=None, key_drop=None):
+        """modeling_internvl_chat.py:638-767: pre-tokenised stage-2 prompt (with the motion slot) -> decoded response.  ``key_drop`` as
+        ``generate_stage2``: the response with those prompt tokens hidden."""
         self.img_context_token_id = tokenizer.convert_tokens_to_ids(IMG_CONTEXT_TOKEN)
         template = get_conv_template(self.template)
         generation_config["eos_token_id"] = tokenizer.convert_tokens_to_ids(template.sep)
-        out = self.generate_stage2(pixel_values, input_ids, attention_mask, image_flags, motion_feature, **generation_config)
+        out = self.generate_stage2(pixel_values, input_ids, attention_mask, image_flags, motion_feature, key_drop=key_drop, **generation_config)
         response = tokenizer.batch_decode(out, skip_special_tokens=True)[0].split(template.sep)[0].strip()
         return (response, history) if return_history else response
 

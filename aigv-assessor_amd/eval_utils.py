@@ -199,6 +199,49 @@ def frame_ablation(model, *, pixel_values, input_ids, attention_mask, image_flag
     return res
 
 
+def frame_ablation_generate(model, *, pixel_values, input_ids, attention_mask, image_flags, max_new_tokens, candidate_ids=None, **gen):
+    """WHAT IF a frame were not there, in WORDS: the reply to the stage-2 prompt as it is and once per unit with that unit's tokens hidden from
+    the LLM (``generate_stage2(key_drop=model.unit_masks(...)[:, u])``) - unit u < F is frame u's visual tokens, unit F the motion token.
+    InternViT and the SlowFast branch run ONCE; their outputs are handed to every call (``visual_tokens=``, ``motion_feature=``).  ``gen`` goes to
+    every ``generate_stage2`` call (``eos_token_id``, ``pad_token_id``, ``motion_feature``, sampling settings, ...).
+
+    Returns a dict: ``sequences`` long [B, F + 2, T], T = ``max_new_tokens`` - row 0 the base reply, row u + 1 the reply with unit u hidden, the pad
+    id (``pad_token_id`` of ``gen``, else the model's) after a reply's end token and in the rows of units a clip does not have; ``units`` - the
+    masks, bool [B, F + 1, N]; with ``candidate_ids`` also ``cand_logprobs`` fp32 [B, F + 2, T, C] - the candidates' log-probabilities at every
+    step of every reply, NaN after the end token and for the units a clip does not have."""
+    import torch
+    B, T = int(input_ids.shape[0]), int(max_new_tokens)
+    n_frames = int(pixel_values.shape[0])
+    units = model.unit_masks(input_ids, attention_mask, image_flags, n_frames=n_frames)                        # host bool [B, F + 1, N]
+    gen = dict(gen)
+    motion_feature = gen.pop("motion_feature", None)
+    if motion_feature is None:
+        motion_feature = model.motion_feature(pixel_values, B)
+    tokens = model.vit_tokens(pixel_values)
+    pad = gen.get("pad_token_id")
+    pad = model.config.llm_config.pad_token_id if pad is None else pad
+    common = dict(input_ids=input_ids, attention_mask=attention_mask, image_flags=image_flags, motion_feature=motion_feature, visual_tokens=tokens,
+                  max_new_tokens=T, **gen)
+    if candidate_ids is not None:
+        common["candidate_ids"] = candidate_ids
+    outs = [model.generate_stage2(None, **common)] + [model.generate_stage2(None, key_drop=units[:, u], **common) for u in range(units.shape[1])]
+    seqs = [o if torch.is_tensor(o) else o["sequences"] for o in outs]
+    dev = seqs[0].device
+    absent = torch.cat([torch.zeros(B, 1, dtype=torch.bool), ~units.any(-1)], 1).to(dev)                      # [B, F + 2]: the clip has no such unit
+    sequences = torch.full((B, len(outs), T), int(pad), dtype=torch.long, device=dev)
+    for i, sq in enumerate(seqs):
+        sequences[:, i, : sq.shape[1]] = sq
+    sequences = sequences.masked_fill(absent[:, :, None], int(pad))
+    res = {"sequences": sequences, "units": units}
+    if candidate_ids is not None:
+        C = outs[0]["cand_logprobs"].shape[-1]
+        clp = torch.full((B, len(outs), T, C), float("nan"), dtype=torch.float32, device=dev)
+        for i, o in enumerate(outs):
+            clp[:, i, : o["cand_logprobs"].shape[1]] = o["cand_logprobs"]
+        res["cand_logprobs"] = clp.masked_fill(absent[:, :, None, None], float("nan"))
+    return res
+
+
 def batched(items, model, k: int = 4, frames=None, ahead: bool = True, pad_id: int = 2, return_logprobs: bool = False, candidate_ids=None,
             top_logprobs=None):
     """The reference's eval loop at batch ``k`` instead of batch 1: yields ``(item, output)`` for EVERY item of ``items`` (the loop's

@@ -149,6 +149,7 @@ PROTOTYPES = {
     "aigv_op_lm_head_argmax_topk_logprob_scratch_bytes": (C.c_int64, [_I, _I]),
     "aigv_op_attention_decode": (_I, [_P, _I, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _F, _I, _P, C.c_int64, _P]),
     "aigv_op_attention_decode_ws_floats": (C.c_int64, [_I, _I, _I, _I]),
+    "aigv_op_attention_decode_drop": (_I, [_P, _I, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _F, _I, _P, C.c_int64, _P, _I, _P]),
     "aigv_op_skinny_rope_kv": (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _F, _I, _P]),
     "aigv_op_skinny_swiglu_normed": (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _I, _P, _F, _I, _P]),
     "aigv_op_skinny_rope_kv_fp8": (_I, [_P, _I, _I, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _F, _I, _P]),

@@ -82,7 +82,7 @@ class ReadOuts:
     score_attention: bool = False               # (return_token_attention implies it)
     segments: Optional[torch.Tensor] = None     # the user's attention_segments table; None: prompts.attention_segments
     token_attention: bool = False
-    key_drop: Optional[torch.Tensor] = None     # host bool [B, N]: tokens hidden, as keys, from every row of their clip (forward only)
+    key_drop: Optional[torch.Tensor] = None     # host bool [B, N]: tokens hidden, as keys, from every row of their clip (forward; generate* check theirs with key_drop_mask)
 
     @classmethod
     def parse(cls, vocab: int, labels="given", return_logprobs: bool = False, candidate_ids=None, top_logprobs: Optional[int] = None,

@@ -45,7 +45,8 @@ extern "C" {
                                 aigv_op_seqpos, aigv_op_gather_rows, aigv_op_scatter_rows, aigv_op_cls_rows, aigv_op_write_ints), then by the
                                 score-row attention probe (aigv_score_attention_arm, aigv_op_attention_probe), then by its dense per-key
                                 form (aigv_score_attention_arm_tokens, aigv_op_attention_probe_tokens), then by the key-drop mask of the
-                                prefill attention (aigv_key_drop_arm, aigv_op_attention_drop)
+                                prefill attention (aigv_key_drop_arm, aigv_op_attention_drop), then by the key-drop form of the decode attention
+                                (aigv_op_attention_decode_drop; the mask now travels with the KV cache: aigv_key_drop_arm)
                                 - added symbols only: a library without them is refused at load
                                 time, "missing <name>" */
 
@@ -192,7 +193,7 @@ int aigv_score_attention_arm(aigv_ctx* ctx, const int32_t* rows_host, int n_rows
 int aigv_score_attention_arm_tokens(aigv_ctx* ctx, const int32_t* rows_host, int n_rows, const int32_t* seg_new_dev, const int32_t* seg_cached_dev,
                                     int ld_cached, int n_segments, float* out_dev, float* tok_out_dev, int ld_tok);
 
-/* Key-drop mask: score the clips with some tokens HIDDEN from the LLM - what the reference computes for attention_mask zeros in the middle of a
+/* Key-drop mask: run the clips with some tokens HIDDEN from the LLM - what the reference computes for attention_mask zeros in the middle of a
  * sequence (positions stay as they are; the additive mask hides those keys from every query row).  Arms exactly the next aigv_llm_prefill on
  * this context: the prefill attention of EVERY layer of that pass, the row-trimmed last layer included, runs in its key-drop form, and every
  * output of the pass (score, argmax, the aigv_out_row_* read-outs) is that of the masked pass.  The pass then disarms, also when it fails.
@@ -200,11 +201,19 @@ int aigv_score_attention_arm_tokens(aigv_ctx* ctx, const int32_t* rows_host, int
  *              position inside the clip, 0 = first token) is invisible, as a key, to every query row and head of its clip.  One word is one
  *              64-key tile of the kernel; bits past a clip's length are ignored.
  *   ld_words   words per clip, >= ceil(longest clip / 64): AIGV_ERR_ARG from the pass, with a message, otherwise.
+ * With keep_kv != 0 the mask becomes part of the KV state: the pass copies every clip's words (cut to the clip's length, zero behind it) into a
+ * mask the context owns beside the caches - uint64 [max_seqs][ceil(kv_capacity / 64)], by absolute position, allocated, resized and invalidated
+ * with them; nothing is allocated in the pass - and from then on aigv_llm_extend (the key-drop form of the prefill kernel) and every
+ * aigv_decode_step* (the key-drop form of the decode attention) run under it: what was hidden from the prompt stays hidden from every later
+ * token, while the keys those passes append are visible.  aigv_kv_fork replicates the mask rows with the slots, aigv_kv_reorder gathers them
+ * by parent.  The cache stays masked until the next aigv_llm_prefill: an unmasked keep_kv prefill (or aigv_ctx_resize) drops the mask.
  * A query row left without a visible key has an all-zero attention output (the reference's softmax over a fully masked row is uniform
- * instead): keep every clip's first token visible.  The V rows of dropped keys must be FINITE: the kernel multiplies them by an exact 0, and
- * 0 x NaN is NaN, as it is in torch.  Tiles without a dropped key run the unmasked tile body; an unarmed pass enters no new code.
- * Refused with AIGV_ERR_ARG and a message: an armed aigv_llm_extend (the continuation and decode kernels take no mask), keep_kv != 0 under a
- * mask, and a pass that is also armed with the score-attention probe (the probe does not know the mask).  Nothing is allocated. */
+ * instead): keep every clip's first token visible.  The V rows of dropped keys must be FINITE: the kernels multiply them by an exact 0, and
+ * 0 x NaN is NaN, as it is in torch.  Tiles / chunks without a dropped key run the unmasked arithmetic; an unarmed pass on an unmasked cache
+ * enters no new code.
+ * Refused with AIGV_ERR_ARG and a message: an ARMED aigv_llm_extend (the continuation takes no mask of its own: it inherits the cache's), a pass
+ * that is also armed with the score-attention probe, and the probe armed in front of aigv_llm_extend on a masked cache (the probe does not
+ * know the mask). */
 int aigv_key_drop_arm(aigv_ctx* ctx, const uint64_t* words_dev, int ld_words);
 
 /* Replicate the n kept sequences `copies` times (cache slots [0, n) -> [n, 2n), ...; needs n * copies <= max_seqs): the copies can
@@ -503,6 +512,15 @@ int aigv_op_attention_decode(const void* q, int ldq, int q_group_stride, const v
                              void* o, int ldo, int n_seq, int n_kv, int g, int head_dim, float post_div, int max_kv_len, float* ws,
                              int64_t ws_floats, void* stream);
 int64_t aigv_op_attention_decode_ws_floats(int n_seq, int n_kv, int g, int cap);   /* -1 for arguments the op refuses */
+/* aigv_op_attention_decode under a key-drop mask (tests/test_gpu_key_drop_cache.py): key_drop DEVICE uint64 [n_seq][ld_drop] or NULL (then the same
+ * call as aigv_op_attention_decode, the same kernels).  Bit (j & 63) of word key_drop[b * ld_drop + (j >> 6)] set = key j of sequence b is
+ * invisible to all its query heads; bits at or past kv_lens[b] are ignored.  A dropped key's K row is not read (it may hold anything); its V row,
+ * inside a 128-key chunk that keeps a visible key, is multiplied by an exact 0 and must be finite; a chunk without a visible key is not read at
+ * all.  A sequence without a visible key is written as zeros.  An all-zero mask gives aigv_op_attention_decode's bits.  Refused with
+ * AIGV_ERR_ARG and a message: a key_drop that is not 8-byte aligned, and ld_drop < ceil(max_kv_len / 64). */
+int aigv_op_attention_decode_drop(const void* q, int ldq, int q_group_stride, const void* kc, const void* vc, const int32_t* kv_lens, int cap,
+                                  void* o, int ldo, int n_seq, int n_kv, int g, int head_dim, float post_div, int max_kv_len, float* ws,
+                                  int64_t ws_floats, const uint64_t* key_drop, int ld_drop, void* stream);
 /* The wqkv GEMV of a decode step with RoPE and the KV-cache append in its epilogue: y = x[R, K] . W[N, K]^T, N = n_kv (g + 2) 128 in
  * groups of [g query heads | K | V].  Row r: query slots -> bf16(y) rotated (three bf16 roundings as aigv_op_rope, tables cos / sin
  * [max_pos, 64] at position pos[r]) into qkv[r * ldo + slot * 128 ..] (the K / V columns of qkv are not written); the K slot,
