@@ -20,6 +20,7 @@
 // every Linear output rounds to bf16 (bias added in fp32 first), activations round, layer-scale
 // rounds, residual adds round.
 #include "common.h"
+#include "epilogue.h"
 #include "kernels.h"
 
 namespace {
@@ -136,58 +137,26 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const GemmArgs p) {
 #pragma unroll
       for (int jp = 0; jp < 2; ++jp) {
         const int n = (n0 + wn * 64) / 2 + jp * 16 + fq * 4;
-        u16x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float g = rbf(acc[i][2 * jp][e]), u = rbf(acc[i][2 * jp + 1][e]);
-          o[e] = f2bf(rbf(silu_f(g)) * u);
-        }
-        *(u16x4*)(p.C + (size_t)m * p.ldc + n) = o;
+        *(u16x4*)(p.C + (size_t)m * p.ldc + n) = epi_swiglu4(acc[i][2 * jp], acc[i][2 * jp + 1]);
       }
     } else {
       size_t orow = (size_t)m;
-      const bf16_t* posrow = nullptr;
+      const bf16_t* rrow = nullptr;                      // the row epi_row adds: residual or position row
       if constexpr (EPI == EPI_PATCH) {
         const int f = m / p.np, pi = m - f * p.np;
         orow = (size_t)m + f + 1;                      // skip one class-token row per frame
-        posrow = p.pos + (size_t)(pi + 1) * p.N;
+        rrow = p.pos + (size_t)(pi + 1) * p.N;
       }
+      if constexpr (EPI == EPI_LS_RESID || EPI == EPI_RESID) rrow = p.resid + (size_t)m * p.ldr;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int n = n0 + wn * 64 + j * 16 + fq * 4;
-        float v[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = acc[i][j][e];
-        if (p.bias) {
-          const u16x4 b = *(const u16x4*)(p.bias + n);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] += bf2f(b[e]);
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = rbf(v[e]);  // the Linear's bf16 output
-        if constexpr (EPI == EPI_GELU) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = rbf(gelu_fast(v[e]));
-        }
-        if constexpr (EPI == EPI_LS_RESID) {
-          const u16x4 s = *(const u16x4*)(p.ls + n);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = rbf(v[e] * bf2f(s[e]));
-        }
-        if constexpr (EPI == EPI_LS_RESID || EPI == EPI_RESID) {
-          const u16x4 r = *(const u16x4*)(p.resid + (size_t)m * p.ldr + n);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = rbf(bf2f(r[e]) + v[e]);
-        }
-        if constexpr (EPI == EPI_PATCH) {
-          const u16x4 ps = *(const u16x4*)(posrow + n);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = rbf(v[e] + bf2f(ps[e]));
-        }
-        u16x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = f2bf(v[e]);
-        *(u16x4*)(p.C + orow * p.ldc + n) = o;
+        u16x4 b{}, s{}, r{};
+        if (p.bias) b = *(const u16x4*)(p.bias + n);
+        if constexpr (EPI == EPI_LS_RESID) s = *(const u16x4*)(p.ls + n);
+        const u16x4 v = epi_acc4<EPI>(acc[i][j], p.bias != nullptr, b, s);
+        if constexpr (epi_has_row<EPI>) r = *(const u16x4*)(rrow + n);
+        *(u16x4*)(p.C + orow * p.ldc + n) = epi_row4<EPI>(v, r);
       }
     }
   }
@@ -240,6 +209,9 @@ __global__ __launch_bounds__(256) void gemm_finalize_kernel(const GemmArgs p, co
       for (int e = 0; e < 4; ++e) o[e] = f2bf(rbf(silu_f(rbf(a[e]))) * rbf(u[e]));
       *(u16x4*)(p.C + (size_t)m * p.ldc + blk * 16 + within) = o;
     } else {
+      // This kernel's own text of epilogue.h's chains (epi_acc4 then epi_row4; epi_swiglu4 above).  Through the shared functions the kernel
+      // measured 0.07 ms per step behind the parent's in the benched step (profiles/gemm_epilogue_bench_ab.txt), so the text stays;
+      // scripts/gemm_epilogue_bits.py and test_gelu_and_swiglu_bits_agree_on_every_route hold it in step with the other kernels.
       float v[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] = a[e];
@@ -272,11 +244,14 @@ __global__ __launch_bounds__(256) void gemm_finalize_kernel(const GemmArgs p, co
   }
 }
 
-template <int EPI>
-void launch_finalize(const GemmArgs& a, const float* part, int S, hipStream_t s) {
-  const size_t total = (a.row_tab ? (size_t)a.tab_halves * 128 : (size_t)a.M) * (a.N / 4);
-  const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-  hipLaunchKernelGGL(gemm_finalize_kernel<EPI>, dim3(blocks), dim3(256), 0, s, a, part, S);
+// (no patch epilogue in split-K: the slabs have no class-token row mapping)
+hipError_t launch_finalize(const GemmArgs& a, int epi, const float* part, int S, hipStream_t s) {
+  return with_epi<EPI_MASK_BODY>(epi, [&](auto E) {
+    const size_t total = (a.row_tab ? (size_t)a.tab_halves * 128 : (size_t)a.M) * (a.N / 4);
+    const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+    hipLaunchKernelGGL(gemm_finalize_kernel<decltype(E)::value>, dim3(blocks), dim3(256), 0, s, a, part, S);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace
@@ -311,30 +286,14 @@ hipError_t aigv_launch_gemm_splitk_fp8(const GemmArgs& a, int epi, int k_slices,
   b.k_slices = k_slices;
   hipError_t e = aigv_launch_gemm256_fp8_partial(b, s);
   if (e != hipSuccess) return e;
-  switch (epi) {
-    case EPI_STORE: launch_finalize<EPI_STORE>(a, ws, k_slices, s); break;
-    case EPI_GELU: launch_finalize<EPI_GELU>(a, ws, k_slices, s); break;
-    case EPI_LS_RESID: launch_finalize<EPI_LS_RESID>(a, ws, k_slices, s); break;
-    case EPI_RESID: launch_finalize<EPI_RESID>(a, ws, k_slices, s); break;
-    case EPI_SWIGLU: launch_finalize<EPI_SWIGLU>(a, ws, k_slices, s); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return launch_finalize(a, epi, ws, k_slices, s);
 }
 
 // the second half of a split-K GEMM on its own: sum the k_slices slabs in slice order + epilogue `epi` (a.row_tab / a.tab_halves = the rows
 // the slabs hold, as the slice launch addressed them)
 hipError_t aigv_launch_gemm_finalize(const GemmArgs& a, int epi, int k_slices, const float* ws, hipStream_t s) {
   if (k_slices < 2 || !ws) return hipErrorInvalidValue;
-  switch (epi) {
-    case EPI_STORE: launch_finalize<EPI_STORE>(a, ws, k_slices, s); break;
-    case EPI_GELU: launch_finalize<EPI_GELU>(a, ws, k_slices, s); break;
-    case EPI_LS_RESID: launch_finalize<EPI_LS_RESID>(a, ws, k_slices, s); break;
-    case EPI_RESID: launch_finalize<EPI_RESID>(a, ws, k_slices, s); break;
-    case EPI_SWIGLU: launch_finalize<EPI_SWIGLU>(a, ws, k_slices, s); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return launch_finalize(a, epi, ws, k_slices, s);
 }
 
 hipError_t aigv_launch_gemm_splitk(const GemmArgs& a, int epi, int k_slices, float* ws, hipStream_t s, bool tile256) {
@@ -346,14 +305,7 @@ hipError_t aigv_launch_gemm_splitk(const GemmArgs& a, int epi, int k_slices, flo
     b.k_slices = k_slices;
     hipError_t e = aigv_launch_gemm256_partial(b, s);
     if (e != hipSuccess) return e;
-    switch (epi) {
-      case EPI_STORE: launch_finalize<EPI_STORE>(a, ws, k_slices, s); break;
-      case EPI_GELU: launch_finalize<EPI_GELU>(a, ws, k_slices, s); break;
-      case EPI_LS_RESID: launch_finalize<EPI_LS_RESID>(a, ws, k_slices, s); break;
-      case EPI_RESID: launch_finalize<EPI_RESID>(a, ws, k_slices, s); break;
-      case EPI_SWIGLU: launch_finalize<EPI_SWIGLU>(a, ws, k_slices, s); break;
-    }
-    return hipGetLastError();
+    return launch_finalize(a, epi, ws, k_slices, s);
   }
   static LdsAttrOnce lds_attr;
   if (hipError_t e = lds_attr.ensure((const void*)gemm_bf16_kernel<EPI_PARTIAL>, 2 * STAGE_BYTES); e != hipSuccess) return e;
@@ -362,25 +314,9 @@ hipError_t aigv_launch_gemm_splitk(const GemmArgs& a, int epi, int k_slices, flo
   b.k_slices = k_slices;
   const int nbm = (a.M + BM - 1) / BM, nbn = a.N / BN;
   hipLaunchKernelGGL(gemm_bf16_kernel<EPI_PARTIAL>, dim3(nbm * nbn, k_slices), dim3(256), 2 * STAGE_BYTES, s, b);
-  switch (epi) {
-    case EPI_STORE: launch_finalize<EPI_STORE>(a, ws, k_slices, s); break;
-    case EPI_GELU: launch_finalize<EPI_GELU>(a, ws, k_slices, s); break;
-    case EPI_LS_RESID: launch_finalize<EPI_LS_RESID>(a, ws, k_slices, s); break;
-    case EPI_RESID: launch_finalize<EPI_RESID>(a, ws, k_slices, s); break;
-    case EPI_SWIGLU: launch_finalize<EPI_SWIGLU>(a, ws, k_slices, s); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return launch_finalize(a, epi, ws, k_slices, s);
 }
 
 hipError_t aigv_launch_gemm(const GemmArgs& a, int epi, hipStream_t s) {
-  switch (epi) {
-    case EPI_STORE: return launch<EPI_STORE>(a, s);
-    case EPI_GELU: return launch<EPI_GELU>(a, s);
-    case EPI_LS_RESID: return launch<EPI_LS_RESID>(a, s);
-    case EPI_RESID: return launch<EPI_RESID>(a, s);
-    case EPI_SWIGLU: return launch<EPI_SWIGLU>(a, s);
-    case EPI_PATCH: return launch<EPI_PATCH>(a, s);
-  }
-  return hipErrorInvalidValue;
+  return with_epi<EPI_MASK_ALL>(epi, [&](auto E) { return launch<decltype(E)::value>(a, s); });
 }

@@ -32,6 +32,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "epilogue.h"
 #include "kernels.h"
 
 namespace {
@@ -426,7 +427,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const GemmArgs p) {
     // ---- residual epilogue: residual from LDS (prefetched), output staged 16 rows at a time in the wave's private region ----
     // No compiler-visible global LOAD may appear here: hipcc would wait for it with a vmcnt that also drains the residual DMA
     // still in flight.  The per-column bias / layer-scale vectors are therefore loaded by inline asm as well and tied to the wait.
-    typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
     // (the asm outputs are defined by exactly one asm statement each - no zero-init, no conditional: a phi would let the
     //  compiler copy a register the load has not written yet)
     u32x2 bcol[2][2], scol[2][2];
@@ -468,11 +468,10 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const GemmArgs p) {
             u32x2 o;
 #pragma unroll
             for (int h = 0; h < 2; ++h) {   // element pairs (0,1), (2,3): packed fp32 math, one cvt_pk per rounding point
-              f32x2 v = f32x2{acc[mh][mt][nh][nt][2 * h], acc[mh][mt][nh][nt][2 * h + 1]};
-              if (has_bias) v += unpack_bf2(bcol[nh][nt][h]);
-              v = rbf2(v);
-              if constexpr (EPI == EPI_LS_RESID) v = rbf2(v * unpack_bf2(scol[nh][nt][h]));
-              o[h] = pack_bf2(unpack_bf2(rr[h]) + v);
+              const f32x2 v = f32x2{acc[mh][mt][nh][nt][2 * h], acc[mh][mt][nh][nt][2 * h + 1]};
+              uint32_t ls2 = 0u;            // (scol is written by the asm above for EPI_LS_RESID only)
+              if constexpr (EPI == EPI_LS_RESID) ls2 = scol[nh][nt][h];
+              o[h] = epi_row2<EPI>(epi_acc2<EPI>(v, has_bias, bcol[nh][nt][h], ls2), rr[h]);
             }
             *(u32x2*)(st + fr * STAGE_ROWP + cl * 2) = o;
           }
@@ -500,7 +499,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const GemmArgs p) {
     char* st = smem + wave * (64 * ROWP);
     // per-column bias depends on (nh, nt, fq) only: loaded once, not once per row block.  (EPI_RESID / EPI_LS_RESID take the
     // prefetching epilogue above when VAR has bit 2, so this path carries no layer-scale.)
-    typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
     static_assert(FP8 || (EPI != EPI_RESID && EPI != EPI_LS_RESID), "bf16 residual epilogues use the prefetching path");
     u32x2 bcol[2][2];
     u32x2 scol[2][2];   // layer-scale (fp8 LS_RESID only)
@@ -545,9 +543,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const GemmArgs p) {
                 gt = (gt * rs) * f32x2{wsc[nh][0][2 * h], wsc[nh][0][2 * h + 1]};
                 up = (up * rs) * f32x2{wsc[nh][1][2 * h], wsc[nh][1][2 * h + 1]};
               }
-              gt = rbf2(gt);
-              up = rbf2(up);
-              o[h] = pack_bf2(rbf2(silu2(gt)) * up);
+              o[h] = epi_swiglu2(gt, up);
             }
             *(u32x2*)(rowp + (nh * 16 + fq * 4) * 2) = o;
           }
@@ -565,10 +561,9 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const GemmArgs p) {
                   const float rs = p.row_scale[hb + relc(mh * 64 + mt * 16 + fr)];
                   v = (v * rs) * f32x2{wsc[nh][nt][2 * h], wsc[nh][nt][2 * h + 1]};
                 }
-                if (p.bias) v += unpack_bf2(bcol[nh][nt][h]);   // wave-uniform branch
-                if constexpr (EPI == EPI_GELU) v = gelu_fast2(rbf2(v));
-                if constexpr (EPI == EPI_LS_RESID) v = rbf2(v) * unpack_bf2(scol[nh][nt][h]);
-                o[h] = pack_bf2(v);
+                uint32_t ls2 = 0u;   // (scol is loaded for EPI_LS_RESID only)
+                if constexpr (EPI == EPI_LS_RESID) ls2 = scol[nh][nt][h];
+                o[h] = epi_acc2<EPI>(v, p.bias != nullptr, bcol[nh][nt][h], ls2);   // wave-uniform branch
               }
               *(u32x2*)(rowp + cl * 2) = o;
             }
@@ -589,12 +584,12 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const GemmArgs p) {
             orow = (size_t)m + f + 1;
             const u16x8 ps = *(const u16x8*)(p.pos + (size_t)(pi + 1) * p.N + n);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) val[e] = f2bf(bf2f(val[e]) + bf2f(ps[e]));
+            for (int e = 0; e < 8; ++e) val[e] = epi_row<EPI>(val[e], ps[e]);
           }
           if constexpr (EPI == EPI_RESID || EPI == EPI_LS_RESID) {   // fp8 form only (bf16 takes the prefetching path)
             const u16x8 rs = *(const u16x8*)(p.resid + (size_t)m * p.ldr + n);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) val[e] = f2bf(bf2f(rs[e]) + bf2f(val[e]));
+            for (int e = 0; e < 8; ++e) val[e] = epi_row<EPI>(val[e], rs[e]);
           }
           store_row_segment(p.C + orow * p.ldc + n, val, p.variant_sel);
         }
@@ -614,60 +609,28 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const GemmArgs p) {
 #pragma unroll
         for (int nh = 0; nh < 2; ++nh) {
           const int n = (n0 + wc * 64 + nh * 32) / 2 + fq * 4;
-          u16x4 o;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float gt = rbf(acc[mh][mt][nh][0][e]), up = rbf(acc[mh][mt][nh][1][e]);
-            o[e] = f2bf(rbf(silu_f(gt)) * up);
-          }
-          *(u16x4*)(p.C + (size_t)m * p.ldc + n) = o;
+          *(u16x4*)(p.C + (size_t)m * p.ldc + n) = epi_swiglu4(acc[mh][mt][nh][0], acc[mh][mt][nh][1]);
         }
       } else {
         size_t orow = (size_t)m;
-        const bf16_t* posrow = nullptr;
+        const bf16_t* rrow = nullptr;                      // the row epi_row adds: residual or position row
         if constexpr (EPI == EPI_PATCH) {
           const int f = m / p.np, pi = m - f * p.np;
           orow = (size_t)m + f + 1;
-          posrow = p.pos + (size_t)(pi + 1) * p.N;
+          rrow = p.pos + (size_t)(pi + 1) * p.N;
         }
+        if constexpr (EPI == EPI_LS_RESID || EPI == EPI_RESID) rrow = p.resid + (size_t)m * p.ldr;
 #pragma unroll
         for (int nh = 0; nh < 2; ++nh)
 #pragma unroll
           for (int nt = 0; nt < 2; ++nt) {
             const int n = n0 + wc * 64 + nh * 32 + nt * 16 + fq * 4;
-            float v[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = acc[mh][mt][nh][nt][e];
-            if (p.bias) {
-              const u16x4 b = *(const u16x4*)(p.bias + n);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] += bf2f(b[e]);
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = rbf(v[e]);
-            if constexpr (EPI == EPI_GELU) {
-#pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] = rbf(gelu_fast(v[e]));
-            }
-            if constexpr (EPI == EPI_LS_RESID) {
-              const u16x4 s = *(const u16x4*)(p.ls + n);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] = rbf(v[e] * bf2f(s[e]));
-            }
-            if constexpr (EPI == EPI_LS_RESID || EPI == EPI_RESID) {
-              const u16x4 r = *(const u16x4*)(p.resid + (size_t)m * p.ldr + n);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] = rbf(bf2f(r[e]) + v[e]);
-            }
-            if constexpr (EPI == EPI_PATCH) {
-              const u16x4 ps = *(const u16x4*)(posrow + n);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] = rbf(v[e] + bf2f(ps[e]));
-            }
-            u16x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = f2bf(v[e]);
-            *(u16x4*)(p.C + orow * p.ldc + n) = o;
+            u16x4 b{}, s{}, r{};
+            if (p.bias) b = *(const u16x4*)(p.bias + n);
+            if constexpr (EPI == EPI_LS_RESID) s = *(const u16x4*)(p.ls + n);
+            const u16x4 v = epi_acc4<EPI>(acc[mh][mt][nh][nt], p.bias != nullptr, b, s);
+            if constexpr (epi_has_row<EPI>) r = *(const u16x4*)(rrow + n);
+            *(u16x4*)(p.C + orow * p.ldc + n) = epi_row4<EPI>(v, r);
           }
       }
     }
@@ -694,15 +657,7 @@ hipError_t launch256(const GemmArgs& a, hipStream_t s) {
 
 template <int VAR>
 hipError_t launch256v(const GemmArgs& a, int epi, hipStream_t s) {
-  switch (epi) {
-    case EPI_STORE: return launch256<EPI_STORE, VAR>(a, s);
-    case EPI_GELU: return launch256<EPI_GELU, VAR>(a, s);
-    case EPI_LS_RESID: return launch256<EPI_LS_RESID, VAR>(a, s);
-    case EPI_RESID: return launch256<EPI_RESID, VAR>(a, s);
-    case EPI_SWIGLU: return launch256<EPI_SWIGLU, VAR>(a, s);
-    case EPI_PATCH: return launch256<EPI_PATCH, VAR>(a, s);
-  }
-  return hipErrorInvalidValue;
+  return with_epi<EPI_MASK_ALL>(epi, [&](auto E) { return launch256<decltype(E)::value, VAR>(a, s); });
 }
 
 }  // namespace
@@ -755,14 +710,7 @@ hipError_t aigv_launch_gemm256_fp8(const GemmArgs& a, int epi, hipStream_t s) {
   if (epi == EPI_SWIGLU && a.bias) return hipErrorInvalidValue;
   GemmArgs b = a;
   b.K = a.K / 2; b.lda = a.lda / 2; b.ldw = a.ldw / 2;
-  switch (epi) {
-    case EPI_STORE: return launch256_fp8<EPI_STORE>(b, s);
-    case EPI_GELU: return launch256_fp8<EPI_GELU>(b, s);
-    case EPI_LS_RESID: return launch256_fp8<EPI_LS_RESID>(b, s);
-    case EPI_RESID: return launch256_fp8<EPI_RESID>(b, s);
-    case EPI_SWIGLU: return launch256_fp8<EPI_SWIGLU>(b, s);
-    default: return hipErrorInvalidValue;
-  }
+  return with_epi<EPI_MASK_BODY>(epi, [&](auto E) { return launch256_fp8<decltype(E)::value>(b, s); });   // no patch embedding in e4m3
 }
 
 // split-K slices of the fp8 form (a.K / lda / ldw in e4m3 elements; a.part / a.k_slices filled in; K / 128 divisible by the slices)
@@ -807,14 +755,7 @@ static hipError_t launch256_fused(const GemmArgs& a, hipStream_t s) {
 hipError_t aigv_launch_gemm256_fused(const GemmArgs& a, int epi, hipStream_t s) {
   if (!aigv_gemm256_supported(a) || !a.row_tab || (a.tab_halves & 1) || a.fuse_tail_halves < 1 || a.k_slices < 2 || (a.K / TK) % a.k_slices || !a.part)
     return hipErrorInvalidValue;
-  switch (epi) {
-    case EPI_STORE: return launch256_fused<EPI_STORE>(a, s);
-    case EPI_GELU: return launch256_fused<EPI_GELU>(a, s);
-    case EPI_LS_RESID: return launch256_fused<EPI_LS_RESID>(a, s);
-    case EPI_RESID: return launch256_fused<EPI_RESID>(a, s);
-    case EPI_SWIGLU: return launch256_fused<EPI_SWIGLU>(a, s);
-  }
-  return hipErrorInvalidValue;
+  return with_epi<EPI_MASK_BODY>(epi, [&](auto E) { return launch256_fused<decltype(E)::value>(a, s); });   // a row plan's body: no patch epilogue
 }
 
 hipError_t aigv_launch_gemm256(const GemmArgs& a, int epi, hipStream_t s) {

@@ -41,6 +41,7 @@
 #include <utility>
 
 #include "common.h"
+#include "epilogue.h"
 #include "kernels.h"
 
 namespace {
@@ -410,7 +411,6 @@ __global__ __launch_bounds__(VAR == 6 ? 512 : 256, 2) void gemmco_kernel(const G
   constexpr int OC = (EPI == EPI_SWIGLU) ? 32 : 64;
   constexpr int CPR = OC / 8;
   char* st = smem + wave * (64 * ROWP);
-  typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
   const int ncol = n0 + wc * 64;
   u32x2 bcol[2][2];
   u32x2 scol[2][2];
@@ -439,9 +439,7 @@ __global__ __launch_bounds__(VAR == 6 ? 512 : 256, 2) void gemmco_kernel(const G
           for (int h = 0; h < 2; ++h) {
             f32x2 gt = f32x2{acc[mh][mt][nh][0][2 * h], acc[mh][mt][nh][0][2 * h + 1]};
             f32x2 up = f32x2{acc[mh][mt][nh][1][2 * h], acc[mh][mt][nh][1][2 * h + 1]};
-            gt = rbf2(gt);
-            up = rbf2(up);
-            o[h] = pack_bf2(rbf2(silu2(gt)) * up);
+            o[h] = epi_swiglu2(gt, up);
           }
           *(u32x2*)(rowp + (nh * 16 + fq * 4) * 2) = o;
         }
@@ -455,10 +453,9 @@ __global__ __launch_bounds__(VAR == 6 ? 512 : 256, 2) void gemmco_kernel(const G
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
               f32x2 v = f32x2{acc[mh][mt][nh][nt][2 * h], acc[mh][mt][nh][nt][2 * h + 1]};
-              if (p.bias) v += unpack_bf2(bcol[nh][nt][h]);
-              if constexpr (EPI == EPI_GELU) v = gelu_fast2(rbf2(v));
-              if constexpr (EPI == EPI_LS_RESID) v = rbf2(v) * unpack_bf2(scol[nh][nt][h]);
-              o[h] = pack_bf2(v);
+              uint32_t ls2 = 0u;   // (scol is loaded for EPI_LS_RESID only)
+              if constexpr (EPI == EPI_LS_RESID) ls2 = scol[nh][nt][h];
+              o[h] = epi_acc2<EPI>(v, p.bias != nullptr, bcol[nh][nt][h], ls2);
             }
             *(u32x2*)(rowp + cl * 2) = o;
           }
@@ -478,12 +475,12 @@ __global__ __launch_bounds__(VAR == 6 ? 512 : 256, 2) void gemmco_kernel(const G
           orow = (size_t)m + f + 1;
           const u16x8 ps = *(const u16x8*)(p.pos + (size_t)(pi + 1) * p.N + n);
 #pragma unroll
-          for (int e = 0; e < 8; ++e) val[e] = f2bf(bf2f(val[e]) + bf2f(ps[e]));
+          for (int e = 0; e < 8; ++e) val[e] = epi_row<EPI>(val[e], ps[e]);
         }
         if constexpr (EPI == EPI_RESID || EPI == EPI_LS_RESID) {
           const u16x8 rs = *(const u16x8*)(p.resid + (size_t)m * p.ldr + n);
 #pragma unroll
-          for (int e = 0; e < 8; ++e) val[e] = f2bf(bf2f(rs[e]) + bf2f(val[e]));
+          for (int e = 0; e < 8; ++e) val[e] = epi_row<EPI>(val[e], rs[e]);
         }
         *(u16x8*)(p.C + orow * p.ldc + n) = val;
       }
@@ -523,13 +520,5 @@ bool aigv_gemmco_supported(const GemmArgs& a) { return a.N % CN == 0 && a.K % CK
 
 hipError_t aigv_launch_gemmco(const GemmArgs& a, int epi, hipStream_t s) {
   if (!aigv_gemmco_supported(a)) return hipErrorInvalidValue;
-  switch (epi) {
-    case EPI_STORE: return launch_co<EPI_STORE>(a, s);
-    case EPI_GELU: return launch_co<EPI_GELU>(a, s);
-    case EPI_LS_RESID: return launch_co<EPI_LS_RESID>(a, s);
-    case EPI_RESID: return launch_co<EPI_RESID>(a, s);
-    case EPI_SWIGLU: return launch_co<EPI_SWIGLU>(a, s);
-    case EPI_PATCH: return launch_co<EPI_PATCH>(a, s);
-  }
-  return hipErrorInvalidValue;
+  return with_epi<EPI_MASK_ALL>(epi, [&](auto E) { return launch_co<decltype(E)::value>(a, s); });
 }

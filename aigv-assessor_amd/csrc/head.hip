@@ -11,6 +11,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "epilogue.h"
 #include "kernels.h"
 
 namespace {
@@ -300,17 +301,15 @@ __global__ __launch_bounds__(NWV * 64) void skinny_kernel(const bf16_t* __restri
     } else if constexpr (EPI == SK_SWIGLU) {
       if (r < R) {
         const int n = (int)(blockIdx.x / P) * 16 + (int)(blockIdx.x % P) * RS + 4 * fq;
-        u16x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float g = rbf(acc[0][t][e]), u = rbf(acc[1][t][e]);
-          o[e] = f2bf(rbf(silu_f(g)) * u);
-        }
-        *(u16x4*)(out + (size_t)r * ldo + n) = o;
+        *(u16x4*)(out + (size_t)r * ldo + n) = epi_swiglu4(acc[0][t], acc[1][t]);
       }
     } else {
       const int n = n0 + 4 * fq;
       if (r < R && n < N) {
+        // This kernel's own text of epilogue.h's linear chain (epi_acc4 then epi_row4 for SK_STORE / _GELU / _LS_RESID / _RESID, with a zero added where
+        // there is no bias; SK_RELU is the score head's).  Through the shared functions three of the 3- and 4-row-tile residual forms take two more
+        // VGPRs and one of them loses a wave of occupancy (profiles/gemm_epilogue_kernel_resources.txt), so the text stays; scripts/gemm_epilogue_bits.py
+        // and test_gelu_and_swiglu_bits_agree_on_every_route hold it in step with the other kernels.
         float v[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = acc[0][t][e] + (bias ? bf2f(bias[n + e]) : 0.f);

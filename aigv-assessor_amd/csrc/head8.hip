@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "epilogue.h"
 #include "kernels.h"
 
 namespace {
@@ -212,20 +213,11 @@ __global__ __launch_bounds__(256) void skinny8_kernel(const bf16_t* __restrict__
     *(u16x4*)(dst + 64) = ohi;
   } else if constexpr (EPI == SK_SWIGLU) {
     const int n = (int)(blockIdx.x / P) * 16 + (int)(blockIdx.x % P) * RS + 4 * fq;
-    u16x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float g = rbf(acc[0][e]), u = rbf(acc[1][e]);
-      o[e] = f2bf(rbf(silu_f(g)) * u);
-    }
-    *(u16x4*)(out + (size_t)r * ldo + n) = o;
+    *(u16x4*)(out + (size_t)r * ldo + n) = epi_swiglu4(acc[0], acc[1]);
   } else {
     const int n = n0 + 4 * fq;
     const u16x4 rr = *(const u16x4*)(resid + (size_t)r * ldr + n);
-    u16x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = f2bf(rbf(bf2f(rr[e]) + rbf(acc[0][e])));
-    *(u16x4*)(out + (size_t)r * ldo + n) = o;
+    *(u16x4*)(out + (size_t)r * ldo + n) = epi_row4<EPI_RESID>(epi_acc4<EPI_RESID>(acc[0], false, u16x4{}, u16x4{}), rr);
   }
 }
 

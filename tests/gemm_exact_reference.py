@@ -230,6 +230,21 @@ ROW_LISTS = {
 }
 K_ROWS = 512
 
+# One case of each inexact epilogue (GELU, SwiGLU) run over EVERY route: the accumulators are exact in any order, so all routes must give the
+# same bits (test_gelu_and_swiglu_bits_agree_on_every_route).  M = 520 as the row list 257 + 3 + 260: a ragged 256 tile, a tiny tail, a tail
+# above 128; the skinny kernel takes the first CROSS_ROUTE_SKINNY_ROWS rows of the same A.
+CROSS_ROUTE = [(520, 256, K_ROWS, 1), (520, 256, K_ROWS, 4)]
+CROSS_ROUTE_LENS = ROW_LISTS["tiny_tails"]
+CROSS_ROUTE_TAIL_LENS = [40, 480]              # the same 520 rows with a ragged tile tail (224 rows) for the fused and the lone row plans
+CROSS_ROUTE_SKINNY_ROWS = 64
+
+
+def first_rows(case, R):
+    """The case of the first R rows of ``case``'s A (GELU / SwiGLU cases: no residual, no position rows): a sub-case of an exact case."""
+    assert case["resid"] is None and case["pos"] is None
+    return dict(case, M=R, A=case["A"][:R].contiguous(), want=case["want"][:R].contiguous())
+
+
 SK_OF = {0: 0, 3: 1, 4: 2, 1: 3}                 # GEMM epilogue -> aigv_op_skinny_gemm epilogue (store, residual, swiglu, gelu)
 K_SKINNY = 512
 # the sub-slab forms p = 2 / 4 take at most 16 / p rows and have no GELU epilogue: only the legal combinations are cases
@@ -242,6 +257,7 @@ def tile_cases():
     out += [(M, N, K, e) for M, N, K, e, _ in COST_MODEL.values()] + [(M, N, K, 3) for M, N, K, e, _ in COST_MODEL.values()]
     out += [(M, N, K, e) for M, N, K in SHAPES_SPLITK_128 + SHAPES_SPLITK_256 + SHAPES_FP8 for e in range(5)]
     out += [(sum(lens), N, K_ROWS, e) for lens in ROW_LISTS.values() for N in (256, 512) for e in range(5)]
+    out += CROSS_ROUTE
     return sorted(set(out))
 
 

@@ -155,6 +155,19 @@ def test_every_small_case_is_exact_and_distinguishes_positions():
         assert GX.is_exact(GX.exact_case(R, N, K, epi)), (R, N, K, epi)
 
 
+def test_the_cross_route_cases_are_exact():
+    """The GELU and the SwiGLU case every route must agree on bit for bit, and the rows of them the skinny kernel takes."""
+    assert sum(GX.CROSS_ROUTE_LENS) == GX.CROSS_ROUTE[0][0] and [c[3] for c in GX.CROSS_ROUTE] == [1, 4]
+    assert sum(GX.CROSS_ROUTE_TAIL_LENS) == GX.CROSS_ROUTE[0][0] and GX.CROSS_ROUTE_TAIL_LENS[-1] % 256 > 128          # a tile tail above 128 rows
+    for M, N, K, epi in GX.CROSS_ROUTE:
+        assert (M, N, K, epi) in tile_cases()
+        case = GX.exact_case(M, N, K, epi)
+        assert GX.is_exact(case), (M, N, K, epi)
+        sub = GX.first_rows(case, GX.CROSS_ROUTE_SKINNY_ROWS)
+        assert GX.is_exact(sub) and sub["want"].shape == (GX.CROSS_ROUTE_SKINNY_ROWS, GX.n_out(N, epi))
+        assert torch.equal(GX.want(sub), sub["want"])
+
+
 @pytest.mark.parametrize("M,N,K,epi", LARGE)
 def test_every_large_case_is_exact(M, N, K, epi):
     case = GX.exact_case(M, N, K, epi)

@@ -405,6 +405,81 @@ def test_skinny_kernel_in_place_residual(lib, R, p):
 
 
 # ---------------------------------------------------------------------------------------------------------
+# GELU and SwiGLU: one case each over every route, bit for bit
+# ---------------------------------------------------------------------------------------------------------
+def live_bits(L):
+    """The live elements of layout ``L``'s output, as int16 bit patterns."""
+    n = L.image.numel()
+    got = L.whole.cpu()[FENCE:FENCE + n].view(L.image.shape)
+    return got[FENCE_ROWS + L.rows, :L.no].contiguous().view(torch.int16)
+
+
+@pytest.mark.parametrize("M,N,K,epi", GX.CROSS_ROUTE)
+def test_gelu_and_swiglu_bits_agree_on_every_route(lib, M, N, K, epi):
+    """The accumulator of every element of an exact case is the same number in any summation order, so the GELU / SwiGLU output of one case is
+    ONE bit pattern whichever kernel ran - the same epilogue arithmetic (csrc/epilogue.h) on the same argument - not merely within an ulp
+    of torch, which is all Layout.check asks of these two epilogues.  The plain 128-tile route is the reference; every op below also checks
+    fences, padding and the tolerance as the tests above do."""
+    from aigv_assessor_amd import native
+    lens = GX.CROSS_ROUTE_LENS
+    assert sum(lens) == M
+
+    def fresh():
+        return exact_layout(M, N, K, epi)
+
+    L = fresh()
+    op_gemm(lib, L, 1, proved(on_128(M), "mode 1"), R_128)
+    ref = live_bits(L)
+    routes = {}
+    for variant in VARIANT_WORDS:
+        L = fresh()
+        op_gemm(lib, L, 2 + variant, proved(on_256(M), "mode 2"), R_256)
+        routes[f"256 kernel, schedule word {variant}"] = live_bits(L)
+    for variant in VARIANT_WORDS[:2]:                                  # both shipped schedules (mode 4 makes no plan: the record proves the launch)
+        L = fresh()
+        op_gemm(lib, L, 4 + variant, lambda p: None, R_CO)
+        routes[f"co-resident kernel, schedule word {variant}"] = live_bits(L)
+    for tile256 in (False, True):
+        for S in (2, 4):
+            L = fresh()
+            op_splitk(lib, L, S, tile256)
+            routes[f"split-K, {'256' if tile256 else '128'} tile, {S} slices"] = live_bits(L)
+    L = fresh()
+    op_gemm_rows(lib, L, lens, DEFAULT_ROUTES["tiny_tails"])
+    routes["row plan at the defaults"] = live_bits(L)
+    for knob in ("tail_slices_1", "co_resident"):
+        *knobs, name, route = ROW_KNOBS[knob]
+        assert ROW_LISTS[name] == lens
+        L = fresh()
+        op_gemm_rows(lib, L, lens, route, knobs)
+        routes[f"row plan, {knob}"] = live_bits(L)
+    # the fused body + tail-slice launch and the lone body need a tile tail: the same rows as another list of sequences (a row's bits do not
+    # depend on the sequence it sits in)
+    for what, knobs, route in (("fused tails", (DEFAULT_WORD, 2, 2, 1, 0), R_TAB_FUSED), ("lone body", (DEFAULT_WORD, 0, 0, 2, 0), R_TAB_LONE)):
+        L = fresh()
+        op_gemm_rows(lib, L, GX.CROSS_ROUTE_TAIL_LENS, route, knobs)
+        routes[f"row plan, {what}"] = live_bits(L)
+    for what, got in routes.items():
+        differ = int((got != ref).sum())
+        assert differ == 0, f"{what}: {differ} of {ref.numel()} elements differ from the 128-tile route's bits"
+    # the weight-streaming kernel on the first rows of the same A
+    R = GX.CROSS_ROUTE_SKINNY_ROWS
+    sub = GX.first_rows(L.case, R)
+    assert GX.is_exact(sub), "the case is not exact: the test itself is wrong"
+    S = Layout(sub, False, 12)
+    rc = lib.aigv_op_skinny_gemm_check(S.dA.data_ptr(), S.lda, R, S.dW.data_ptr(), S.ldw, N, K, None, 0, S.C_ptr, S.ldc, SK_OF[epi])
+    assert rc == 0, lib.aigv_last_error(None)
+    try:
+        native.check(lib.aigv_tune_skinny(1))
+        sync(lib.aigv_op_skinny_gemm(S.dA.data_ptr(), S.lda, R, S.dW.data_ptr(), S.ldw, N, K, S.bias_ptr, None, 0, S.C_ptr, S.ldc, SK_OF[epi], None), lib)
+    finally:
+        restore(lib)
+    S.check()
+    differ = int((live_bits(S) != ref[:R]).sum())
+    assert differ == 0, f"skinny kernel: {differ} of {ref[:R].numel()} elements differ from the 128-tile route's bits"
+
+
+# ---------------------------------------------------------------------------------------------------------
 # the fp8 form: row quantisation, the e4m3 tile kernel and its split-K form, the e4m3 decode GEMV
 # ---------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("M,K", [(M, K) for M in (1, 257) for K in (128, 256)])
