@@ -79,6 +79,14 @@ template <bool DROP> struct DropTile {
 };
 template <> struct DropTile<false> {};
 
+// The row-selective form's per-wave state (ROWS: AttnArgs::drop_rows); empty in the two other forms, under the same rule as DropTile.  A wave's 32 query
+// rows are positions qw .. qw + 31 of their sequence, one half of ONE word of the row selector: the word is wave-uniform, loaded once in the prologue.
+template <bool ROWS> struct RowSel {
+  uint32_t lane = 0;               // all ones: this lane's query row is subject to the key mask; 0: it sees every key the causal mask leaves it
+  bool none = false, all = false;  // wave-uniform: none / every one of the wave's rows inside the sequence is selected
+};
+template <> struct RowSel<false> {};
+
 // NW = waves per workgroup (32 query rows each).  More waves share one K/V tile: the LDS-DMA issue cost per wave and tile
 // (the dominant overhead next to the MFMAs) halves going from 4 to 8 waves.
 // NB = K/V ring depth: tile t is multiplied while tiles t+1 .. t+NB-2 are in flight behind a counted vmcnt.
@@ -88,9 +96,17 @@ template <> struct DropTile<false> {};
 // key j (absolute position, cached keys first) is invisible to every query row and head.  The word is wave-uniform (one scalar load per tile,
 // requested a tile ahead); a tile whose word is zero runs exactly the unmasked path, a tile whose word is all ones is skipped like a tile in
 // the causal future, every other tile takes the mask loop with one more bit test per score.  DROP = false compiles to the code it always was.
-template <int D, bool CAUSAL, int NW, int NB, bool RS, bool DROP = false>
-__global__ __launch_bounds__(NW * 64, (D == 64 && NW == 4) ? 4 : 2) void attn_fwd_kernel(const std::conditional_t<DROP, AttnArgs, AttnArgsUnmasked> p) {
+// ROWS = the row-selective key-drop form (AttnArgs::drop_rows; needs DROP, packed prefill only: a row's position is its index in its sequence): a score is
+// hidden iff its key's bit AND its query row's bit are set.  The row word is wave-uniform (one scalar load per wave, in the prologue), the key word stays
+// the one load per tile.  A wave none of whose rows is selected treats every tile's key word as zero - the unmasked path; a wave all of whose rows are
+// selected runs the key-drop form as it is, the skip of an all-ones tile included; a mixed wave takes the mask loop on every tile whose key word is not
+// zero, with the lane's share of the word cleared in the lanes whose row is not selected, and skips no such tile.  ROWS = false compiles to the code the
+// two other forms always were.
+template <int D, bool CAUSAL, int NW, int NB, bool RS, bool DROP = false, bool ROWS = false>
+__global__ __launch_bounds__(NW * 64, (D == 64 && NW == 4) ? 4 : 2) void attn_fwd_kernel(
+    const std::conditional_t<ROWS, AttnArgs, std::conditional_t<DROP, AttnArgsKeyDrop, AttnArgsUnmasked>> p) {
   static_assert(!DROP || (D == 128 && CAUSAL), "the key-drop form exists for the causal d = 128 kernel only");
+  static_assert(!ROWS || DROP, "the row selector qualifies a key-drop mask");
   constexpr int QB = NW * 32;                // query rows per workgroup
   constexpr int ROWB = Lay<D>::ROWB;
   constexpr int CPR = D / 8;                 // 16-byte chunks per row
@@ -288,6 +304,18 @@ __global__ __launch_bounds__(NW * 64, (D == 64 && NW == 4) ? 4 : 2) void attn_fw
     dk.row = p.key_drop + (size_t)seq * p.ld_drop;
     if (n_tiles > 0) dk.next = dk.row[0];
   }
+  // row selector of this wave: bits qw & 32 .. + 31 of word qw >> 6 (a wave past the sequence's end reads nothing: the row holds ceil(len / 64) words for sure)
+  [[maybe_unused]] RowSel<ROWS> rs;
+  if constexpr (ROWS) {
+    const int qw_u = q0 + wave_u * 32;      // = qw (causal: no key split), as a scalar
+    const uint64_t word = qw_u < len ? p.drop_rows[(size_t)seq * p.ld_drop + (qw_u >> 6)] : 0ull;
+    const uint32_t bits = (uint32_t)(word >> (qw_u & 32));
+    const int n_in = min(32, len - qw_u);   // the wave's rows inside the sequence (<= 0: none, the wave computes nothing)
+    const uint32_t in_seq = n_in >= 32 ? ~0u : n_in > 0 ? (1u << n_in) - 1u : 0u;
+    rs.none = (bits & in_seq) == 0;
+    rs.all = (bits & in_seq) == in_seq;
+    rs.lane = 0u - ((bits >> c) & 1u);
+  }
   STAMP(t_loop);
   STAMP_ADD(2, t_begin, t_loop);
   for (int kt = 0; kt < n_tiles; ++kt) {
@@ -295,6 +323,9 @@ __global__ __launch_bounds__(NW * 64, (D == 64 && NW == 4) ? 4 : 2) void attn_fw
     if constexpr (DROP) {
       dk.w = dk.next;
       if (kt + 1 < n_tiles) dk.next = dk.row[kt + 1];
+    }
+    if constexpr (ROWS) {
+      if (rs.none) dk.w = 0;      // no row of this wave is subject to the mask: the unmasked path, tile by tile
     }
     // tile kt must have landed; up to NB-2 younger tiles may stay in flight
     const int younger = min(NB - 2, n_tiles - 1 - kt);
@@ -311,7 +342,8 @@ __global__ __launch_bounds__(NW * 64, (D == 64 && NW == 4) ? 4 : 2) void attn_fw
     // (1025 = 8 x 128 + 1 rows per ViT frame: three of the last workgroup's four waves).  Such a wave still stages its share
     // of every tile and joins the barriers, but leaves its SIMD's issue slots to the co-resident workgroups.
     bool skip = (CAUSAL && key0 > qw + 31 + kv_off) || (qw >= len || trimmed) || (ksplit && (kt % NW) != wave);
-    if constexpr (DROP && DROP_SKIP) skip = skip || dk.w == ~0ull;      // key-drop form: and tiles whose keys are all dropped
+    if constexpr (DROP && DROP_SKIP && !ROWS) skip = skip || dk.w == ~0ull;      // key-drop form: and tiles whose keys are all dropped
+    if constexpr (ROWS && DROP_SKIP) skip = skip || (rs.all && dk.w == ~0ull);   // row-selective form: only when they are dropped for every row of the wave
     // The LDS-DMA requests of tile kt + NB - 1.  d = 128: not in one burst behind the barrier (the stamps priced that burst at 11 % of a
     // wave's lifetime: eight 1-KB requests queue at the CU's address unit) but one behind every second MFMA of S^T = K Q^T; a wave that
     // skips the tile, and the ragged last tile of a sequence, keep the burst.  d = 64 (half the requests, half the MFMAs to hide them
@@ -416,6 +448,10 @@ __global__ __launch_bounds__(NW * 64, (D == 64 && NW == 4) ? 4 : 2) void attn_fw
       if constexpr (DROP) {   // the lane's share of the tile's word: bit (e & 3) + 8 (e >> 2) of half st, shifted down by the lane's 4 h
         dk.lane[0] = (uint32_t)dk.w >> (4 * h);
         dk.lane[1] = (uint32_t)(dk.w >> 32) >> (4 * h);
+      }
+      if constexpr (ROWS) {   // a row that is not selected sees the keys the causal mask leaves it
+        dk.lane[0] &= rs.lane;
+        dk.lane[1] &= rs.lane;
       }
 #pragma unroll
       for (int st = 0; st < 2; ++st)
@@ -862,29 +898,37 @@ const char* aigv_attn_check(const AttnArgs& a, int head_dim) {
     const long long keys = (long long)a.kv_len_offset + a.max_len;
     if (a.ld_drop < (keys + KT - 1) / KT) return "attention: ld_drop is below ceil((largest key offset + max_len) / 64) words per sequence";
   }
+  if (a.drop_rows) {
+    if (!a.key_drop) return "attention: drop_rows qualifies a key_drop mask and needs one";
+    if ((uintptr_t)a.drop_rows & 7) return "attention: drop_rows must be 8-byte aligned";
+    // a query row's bit is found by its index in its sequence, which is its position only where no key precedes the pass's rows
+    if (a.kv_off || a.kv_len_offset != 0) return "attention: drop_rows exists for the packed prefill only, not with a key offset (kv_off / kv_len_offset)";
+  }
   return nullptr;
 }
 
 
 // NB = 2: deeper rings (3, 4 buffers) measured 5-15 % slower on the ViT shape - they cost resident workgroups (LDS), and
 // with four workgroups per CU the wait for the next tile is already covered by the others' work
-template <int D, bool CAUSAL, int NW, bool RS, int NB = 2, bool DROP = false>
+template <int D, bool CAUSAL, int NW, bool RS, int NB = 2, bool DROP = false, bool ROWS = false>
 static hipError_t launch_attn_rs(const AttnArgs& a, hipStream_t s) {
   constexpr int LDS = NB * 2 * KT * (D * 2);
   static LdsAttrOnce lds_attr;
-  if (hipError_t e = lds_attr.ensure((const void*)attn_fwd_kernel<D, CAUSAL, NW, NB, RS, DROP>, LDS); e != hipSuccess) return e;
+  if (hipError_t e = lds_attr.ensure((const void*)attn_fwd_kernel<D, CAUSAL, NW, NB, RS, DROP, ROWS>, LDS); e != hipSuccess) return e;
   const int nqb = (a.max_len + NW * 32 - 1) / (NW * 32) - a.q_begin / (NW * 32);
-  // (the unmasked kernels take the fields they have always taken: AttnArgsUnmasked, a's base)
-  hipLaunchKernelGGL((attn_fwd_kernel<D, CAUSAL, NW, NB, RS, DROP>), dim3(nqb * a.n_heads * a.n_seq), dim3(NW * 64), LDS, s,
-                     static_cast<const std::conditional_t<DROP, AttnArgs, AttnArgsUnmasked>&>(a));
+  // (the unmasked and the key-drop kernels take the fields they have always taken: AttnArgsUnmasked / AttnArgsKeyDrop, a's bases)
+  hipLaunchKernelGGL((attn_fwd_kernel<D, CAUSAL, NW, NB, RS, DROP, ROWS>), dim3(nqb * a.n_heads * a.n_seq), dim3(NW * 64), LDS, s,
+                     static_cast<const std::conditional_t<ROWS, AttnArgs, std::conditional_t<DROP, AttnArgsKeyDrop, AttnArgsUnmasked>>&>(a));
   return hipGetLastError();
 }
 template <int D, bool CAUSAL, int NW>
 static hipError_t launch_attn(const AttnArgs& a, hipStream_t s) {
-  if (a.key_drop) {   // the key-drop form: d = 128 causal only (aigv_attn_check refuses the rest); a null pointer reaches the instantiations it always did
-    if constexpr (D == 128 && CAUSAL)
+  if (a.key_drop) {   // the key-drop forms: d = 128 causal only (aigv_attn_check refuses the rest); a null pointer reaches the instantiations it always did
+    if constexpr (D == 128 && CAUSAL) {
+      if (a.drop_rows)   // the row-selective form; a null selector reaches the key-drop instantiations it always did
+        return a.round_scores ? launch_attn_rs<D, CAUSAL, NW, true, 2, true, true>(a, s) : launch_attn_rs<D, CAUSAL, NW, false, 2, true, true>(a, s);
       return a.round_scores ? launch_attn_rs<D, CAUSAL, NW, true, 2, true>(a, s) : launch_attn_rs<D, CAUSAL, NW, false, 2, true>(a, s);
-    else
+    } else
       return hipErrorInvalidValue;
   }
   return a.round_scores ? launch_attn_rs<D, CAUSAL, NW, true>(a, s) : launch_attn_rs<D, CAUSAL, NW, false>(a, s);

@@ -132,12 +132,15 @@ struct aigv_ctx {
     float* tok = nullptr;   // aigv_score_attention_arm_tokens: the dense rows [n_rows][layers][n_heads][ld_tok], else nullptr / 0
     int ld_tok = 0;
   } probe;
-  // key-drop mask (aigv_key_drop_arm): armed for exactly the next aigv_llm_prefill, which applies it in every layer's attention (keep_kv: and keeps
-  // it with the cache, kv_drop above)
+  // key-drop mask (aigv_key_drop_arm / _ex): armed for exactly the next aigv_llm_prefill, which applies it in the attention of the layers
+  // [layer_begin, layer_end) - every layer for aigv_key_drop_arm - to the query rows `rows` selects (null: every row); keep_kv, which takes
+  // neither qualifier: and keeps it with the cache, kv_drop above
   struct {
     bool armed = false;
     const uint64_t* words = nullptr;   // device: [n_clips][ld] words, AttnArgs::key_drop's layout
+    const uint64_t* rows = nullptr;    // device: [n_clips][ld] words, AttnArgs::drop_rows' layout, or null
     int ld = 0;
+    int layer_begin = 0, layer_end = 0;
   } drop;
   // profiling
   bool prof = false;

@@ -79,7 +79,8 @@ hipError_t aigv_launch_gemmco(const GemmArgs& a, int epi, hipStream_t s);
 //   q head hq  at column (hq / g) * q_group_stride + (hq % g) * D        (g = n_heads / n_kv_heads)
 //   kv head hk at column hk * kv_head_stride
 // (AttnArgsUnmasked: every field but the key-drop pair - the kernel argument of the unmasked kernels, so that their kernarg segment, and with
-// it their code, is what it was before AttnArgs gained that pair; callers fill an AttnArgs)
+// it their code, is what it was before AttnArgs gained that pair; AttnArgsKeyDrop: and that pair - the kernel argument of the key-drop kernels,
+// what it was before AttnArgs gained the row selector; callers fill an AttnArgs)
 struct AttnArgsUnmasked {
   const bf16_t* q; int ldq;
   const bf16_t* k; int ldk;
@@ -109,7 +110,7 @@ struct AttnArgsUnmasked {
   int lead_key;                 // != 0: non-causal key counts 64 j + 1 run as full tiles over keys 1.. + key 0 merged in the epilogue (opt-in; attention.hip "lead key")
   int q_begin;                  // the launch computes query rows >= q_begin (a multiple of the workgroup's 128 rows) only; 0 everywhere at present
 };
-struct AttnArgs : AttnArgsUnmasked {
+struct AttnArgsKeyDrop : AttnArgsUnmasked {
   // Key drop (causal head_dim 128 only; null = no key is dropped, the kernels that have always run): bit j & 63 of word
   // key_drop[seq * ld_drop + (j >> 6)] set = key j of that sequence is invisible to every query row and head.  j is the key's absolute position
   // in its sequence, cached keys first - the packed form and the cache form (kv_off, kv_seq_stride) share the indexing; one word = one 64-key
@@ -117,6 +118,13 @@ struct AttnArgs : AttnArgsUnmasked {
   // without a visible key is written as zeros.  The V rows of dropped keys must be finite (0 x NaN = NaN, as in torch).
   const uint64_t* key_drop;     // device
   int ld_drop;                  // words per sequence
+};
+struct AttnArgs : AttnArgsKeyDrop {
+  // Row selector of the key-drop mask (null = every query row is subject to it: the key-drop kernels that have always run): the same word layout,
+  // [n_seq][ld_drop], bit i & 63 of word drop_rows[seq * ld_drop + (i >> 6)] set = the query row at position i of that sequence is subject to the
+  // mask; a score is hidden iff its key's bit and its row's bit are both set.  Needs key_drop; exists for the packed prefill only (no kv_off, no
+  // kv_len_offset), where a row's position is its index in its sequence.  Bits at or past a sequence's length are ignored.
+  const uint64_t* drop_rows;    // device
 };
 const char* aigv_attn_check(const AttnArgs& a, int head_dim);
 hipError_t aigv_launch_attention(const AttnArgs& a, int head_dim, hipStream_t s);

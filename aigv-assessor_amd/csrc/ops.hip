@@ -164,8 +164,11 @@ int aigv_op_attention_rope(const void* q, int ldq, const void* k, int ldk, const
 static int attention_ex_op(const char* op, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, const int32_t* cu,
                            int n_seq, int max_len, int n_heads, int n_kv_heads, int q_group_stride, int kv_head_stride, int64_t kv_seq_stride,
                            const int32_t* kv_off, int head_dim, int causal, float post_div, float q_prescale, const int32_t* pos, const void* cos,
-                           const void* sin, int pos_is_row, int q_tail, const uint64_t* key_drop, int ld_drop, void* stream) {
+                           const void* sin, int pos_is_row, int q_tail, const uint64_t* key_drop, int ld_drop, void* stream,
+                           const uint64_t* row_words = nullptr) {
   if (!q || !k || !v || !o || !cu) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+  if (row_words && !key_drop) return fail(nullptr, AIGV_ERR_ARG, "%s: row_words qualify a key_drop mask and need one", op);
+  if (row_words && (kv_off || kv_seq_stride)) return fail(nullptr, AIGV_ERR_ARG, "%s: row_words exist for the packed prefill only (no kv_off, no kv_seq_stride)", op);
   if (q_tail < 0) return fail(nullptr, AIGV_ERR_ARG, "%s: q_tail = %d must not be negative", op, q_tail);
   if (kv_seq_stride < 0) return fail(nullptr, AIGV_ERR_ARG, "%s: kv_seq_stride = %lld must not be negative", op, (long long)kv_seq_stride);
   if (kv_off && !kv_seq_stride) return fail(nullptr, AIGV_ERR_ARG, "%s: a key offset needs K/V in cache layout (kv_seq_stride)", op);
@@ -181,7 +184,7 @@ static int attention_ex_op(const char* op, const void* q, int ldq, const void* k
   a.rope_pos_is_row = pos_is_row ? 1 : 0;
   a.q_tail = q_tail;
   if (key_drop) {
-    a.key_drop = key_drop; a.ld_drop = ld_drop;
+    a.key_drop = key_drop; a.ld_drop = ld_drop; a.drop_rows = row_words;
     if (kv_off) {
       // the check needs the largest key offset, which lives on the device: read back here (a test entry point; the passes know theirs on the host)
       if (n_seq < 1 || n_seq > AIGV_SMALL_INTS) return fail(nullptr, AIGV_ERR_ARG, "%s: key_drop with kv_off takes 1..%d sequences, got %d", op, AIGV_SMALL_INTS, n_seq);
@@ -214,6 +217,17 @@ int aigv_op_attention_drop(const void* q, int ldq, const void* k, int ldk, const
                            const void* sin, int pos_is_row, int q_tail, const uint64_t* key_drop, int ld_drop, void* stream) {
   return attention_ex_op("aigv_op_attention_drop", q, ldq, k, ldk, v, ldv, o, ldo, cu, n_seq, max_len, n_heads, n_kv_heads, q_group_stride, kv_head_stride,
                          kv_seq_stride, kv_off, head_dim, causal, post_div, q_prescale, pos, cos, sin, pos_is_row, q_tail, key_drop, ld_drop, stream);
+}
+
+// aigv_op_attention_drop with a row selector (AttnArgs::drop_rows; null: the same call as aigv_op_attention_drop): the packed prefill form only
+int aigv_op_attention_drop_rows(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, const int32_t* cu, int n_seq,
+                                int max_len, int n_heads, int n_kv_heads, int q_group_stride, int kv_head_stride, int64_t kv_seq_stride,
+                                const int32_t* kv_off, int head_dim, int causal, float post_div, float q_prescale, const int32_t* pos, const void* cos,
+                                const void* sin, int pos_is_row, int q_tail, const uint64_t* key_drop, const uint64_t* row_words, int ld_drop,
+                                void* stream) {
+  return attention_ex_op("aigv_op_attention_drop_rows", q, ldq, k, ldk, v, ldv, o, ldo, cu, n_seq, max_len, n_heads, n_kv_heads, q_group_stride,
+                         kv_head_stride, kv_seq_stride, kv_off, head_dim, causal, post_div, q_prescale, pos, cos, sin, pos_is_row, q_tail, key_drop, ld_drop,
+                         stream, row_words);
 }
 
 // K / V slots of fused qkv rows -> the KV cache [seq][kv head][cap][head_dim]: the kernel aigv_llm_prefill (keep_kv) and aigv_llm_extend append with

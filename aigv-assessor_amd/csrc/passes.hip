@@ -273,11 +273,16 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
                      int R, int64_t* argmax, int keep_kv, void* stream) {
   if (!c || !ids || !slot || !cu) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: null argument");
   const bool probing = c->probe.armed;   // aigv_score_attention_arm: this pass carries the probe, and disarms on every way out
-  const bool dropping = c->drop.armed;   // aigv_key_drop_arm: every layer's attention of this pass runs under the mask; disarmed likewise
+  const bool dropping = c->drop.armed;   // aigv_key_drop_arm / _ex: the attention of the armed layers of this pass runs under the mask; disarmed likewise
   DisarmScope disarm(c);
   if (!c->finalized) return fail(c, AIGV_ERR_STATE, "aigv_llm_prefill: call aigv_finalize_weights first");
   if (dropping && probing) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: a key-drop mask and the score-attention probe are both armed: the probe does not know the mask");
   const aigv_config& k = c->cfg;
+  if (dropping && (c->drop.layer_begin < 0 || c->drop.layer_begin > c->drop.layer_end || c->drop.layer_end > k.llm_layers))
+    return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: key-drop mask armed for layers [%d, %d), outside 0 <= begin <= end <= %d", c->drop.layer_begin, c->drop.layer_end, k.llm_layers);
+  if (dropping && keep_kv && (c->drop.rows || c->drop.layer_begin != 0 || c->drop.layer_end != k.llm_layers))
+    return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: keep_kv under a key-drop mask with row words or a partial layer window (aigv_key_drop_arm_ex): the mask kept "
+                                 "beside the KV cache has neither");
   if (B <= 0 || B > k.max_seqs) return fail(c, AIGV_ERR_ARG, "n_clips %d outside 1..%d", B, k.max_seqs);
   if (cu[0] != 0) return fail(c, AIGV_ERR_ARG, "cu_seqlens[0] must be 0");
   int max_len = 0;
@@ -358,7 +363,8 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
       a.max_len = max_len;
       const bool last_trim = trim && li == k.llm_layers - 1;
       a.q_tail = last_trim ? q_tail : 0;
-      if (dropping) { a.key_drop = c->drop.words; a.ld_drop = c->drop.ld; }   // every layer, the row-trimmed last one included
+      // the armed layers, the row-trimmed last one included; the others run the unmasked launch they always ran
+      if (dropping && li >= c->drop.layer_begin && li < c->drop.layer_end) { a.key_drop = c->drop.words; a.ld_drop = c->drop.ld; a.drop_rows = c->drop.rows; }
       if (const char* m = aigv_attn_check(a, D)) return fail(c, AIGV_ERR_ARG, "%s", m);
       ProfScope ps(c, AIGV_PROF_ATTN_LLM, last_trim ? 0.0 : attn_flops, 2.0 * T * ((double)c->qkv_out + H), s);
       HIPCHK(c, aigv_launch_attention(a, D, s));
@@ -407,12 +413,27 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
 }
 
 // Arms the next aigv_llm_prefill with a key-drop mask (include/aigv_amd.h): the words are read when that pass runs (keep_kv: and copied into the cache's mask).
+static int key_drop_arm(const char* op, aigv_ctx* c, const uint64_t* words_dev, const uint64_t* row_words_dev, int ld_words, int layer_begin, int layer_end) {
+  if (!c) return fail(c, AIGV_ERR_ARG, "%s: null context", op);
+  if (!words_dev || ((uintptr_t)words_dev & 7)) return fail(c, AIGV_ERR_ARG, "%s: words_dev is null or not 8-byte aligned", op);
+  if ((uintptr_t)row_words_dev & 7) return fail(c, AIGV_ERR_ARG, "%s: row_words_dev is not 8-byte aligned", op);
+  if (ld_words < 1) return fail(c, AIGV_ERR_ARG, "%s: ld_words = %d must be positive", op, ld_words);
+  if (layer_begin < 0 || layer_begin > layer_end || layer_end > c->cfg.llm_layers)
+    return fail(c, AIGV_ERR_ARG, "%s: layers [%d, %d) outside 0 <= begin <= end <= %d", op, layer_begin, layer_end, c->cfg.llm_layers);
+  c->drop.words = words_dev; c->drop.rows = row_words_dev; c->drop.ld = ld_words;
+  c->drop.layer_begin = layer_begin; c->drop.layer_end = layer_end;
+  c->drop.armed = true;
+  return 0;
+}
+
 int aigv_key_drop_arm(aigv_ctx* c, const uint64_t* words_dev, int ld_words) {
   if (!c) return fail(c, AIGV_ERR_ARG, "aigv_key_drop_arm: null context");
-  if (!words_dev || ((uintptr_t)words_dev & 7)) return fail(c, AIGV_ERR_ARG, "aigv_key_drop_arm: words_dev is null or not 8-byte aligned");
-  if (ld_words < 1) return fail(c, AIGV_ERR_ARG, "aigv_key_drop_arm: ld_words = %d must be positive", ld_words);
-  c->drop.words = words_dev; c->drop.ld = ld_words; c->drop.armed = true;
-  return 0;
+  return key_drop_arm("aigv_key_drop_arm", c, words_dev, nullptr, ld_words, 0, c->cfg.llm_layers);
+}
+
+// ... for the query rows row_words_dev selects (null: every row) in the layers [layer_begin, layer_end) only (include/aigv_amd.h)
+int aigv_key_drop_arm_ex(aigv_ctx* c, const uint64_t* words_dev, const uint64_t* row_words_dev, int ld_words, int layer_begin, int layer_end) {
+  return key_drop_arm("aigv_key_drop_arm_ex", c, words_dev, row_words_dev, ld_words, layer_begin, layer_end);
 }
 
 // Continue the sequences kept by aigv_llm_prefill(keep_kv = 1) with new TEXT tokens: causal attention of the new rows over the

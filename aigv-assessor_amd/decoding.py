@@ -252,6 +252,8 @@ class Generation:
     def _gen_setup(self, generation_config, generate_kwargs):
         """What the three generate entry points read from their generation config / kwargs (``candidate_ids`` and ``top_logprobs`` are taken out of
         the kwargs): (max_new_tokens, eos ids, pad id, ``_greedy``'s keyword arguments)."""
+        # (the knock-out qualifiers of forward(key_drop=...): refused here, before they could pass for sampling settings)
+        readouts.refuse_key_drop_qualifiers("generate*", generate_kwargs.pop("key_drop_rows", None), generate_kwargs.pop("key_drop_layers", None))
         ro = readouts.ReadOuts.parse(self.config.llm_config.vocab_size, candidate_ids=generate_kwargs.pop("candidate_ids", None),
                                      top_logprobs=generate_kwargs.pop("top_logprobs", None))
         max_new, eos, pad, sampler, procs, beams = self._gen_args(generation_config, generate_kwargs)

@@ -199,6 +199,53 @@ def frame_ablation(model, *, pixel_values, input_ids, attention_mask, image_flag
     return res
 
 
+def flow_knockout(model, *, pixel_values, input_ids, attention_mask, image_flags, labels=None, paths=None, width=4, stride=None, **readout_kwargs):
+    """WHICH WAY, AT WHICH DEPTH a group of tokens reaches the score: the attention knock-out.  The batch is scored once as it is and once per
+    (path, layer window) with the edges of that path cut inside that window (``forward(key_drop=keys, key_drop_rows=rows,
+    key_drop_layers=(lo, hi))``); every other edge and layer stays.  ``paths``: a list of ``(name, keys, rows)`` with bool [B, N] masks laid out
+    like ``input_ids`` (``rows`` None: every row) - default, from ``model.segment_masks``: ``frames->score_row``, ``frames->text_after`` and
+    ``text_after->score_row`` (the text behind the frames minus the score row itself, read by the score row).  Windows: ``(lo, min(lo + width,
+    L))`` for lo = 0, stride, 2 stride, ... < L; ``stride`` defaults to ``width``.  InternViT and the SlowFast branch run ONCE; their outputs
+    are handed to every pass.  ``readout_kwargs`` (``motion_feature`` among them) go to every ``forward`` call.
+
+    Returns a dict: ``outs`` - the base result dict, then one per path and window, path-major; ``paths`` - the list of (name, keys, rows);
+    ``windows`` - the list of (lo, hi); and for a stage-2 model ``score1`` [B] (the base scores, fp32), ``knocked`` [B, P, W] (the score under
+    the knock-out; NaN where the clip has no such key or no such row, ``frame_ablation``'s convention for a frame a clip lacks) and ``delta`` =
+    ``score1[:, None, None] - knocked``: positive where the path, in that window, raised the score."""
+    import torch
+    B = int(input_ids.shape[0])
+    L = int(model.config.llm_config.num_hidden_layers)
+    width = int(width)
+    stride = width if stride is None else int(stride)
+    if not 1 <= width <= L or stride < 1:
+        raise ValueError(f"flow_knockout: width = {width} outside 1..{L} or stride = {stride} below 1")
+    windows = [(lo, min(lo + width, L)) for lo in range(0, L, stride)]
+    if paths is None:
+        seg = model.segment_masks(input_ids, attention_mask, image_flags, n_frames=int(pixel_values.shape[0]))
+        paths = [("frames->score_row", seg["frames"], seg["score_row"]), ("frames->text_after", seg["frames"], seg["text_after"]),
+                 ("text_after->score_row", seg["text_after"] & ~seg["score_row"], seg["score_row"])]
+    paths = [(str(name), keys.detach().to("cpu").bool(), None if rows is None else rows.detach().to("cpu").bool()) for name, keys, rows in paths]
+    readout_kwargs = dict(readout_kwargs)
+    motion_feature = readout_kwargs.pop("motion_feature", None)
+    if motion_feature is None:
+        motion_feature = model.motion_feature(pixel_values, B)
+    tokens = model.vit_tokens(pixel_values)
+    common = dict(input_ids=input_ids, attention_mask=attention_mask, image_flags=image_flags, labels=labels, visual_tokens=tokens,
+                  motion_feature=motion_feature, **readout_kwargs)
+    outs = [model.forward(**common)]
+    for name, keys, rows in paths:
+        for w in windows:
+            outs.append(model.forward(key_drop=keys, key_drop_rows=rows, key_drop_layers=w, **common))
+    res = {"outs": outs, "paths": paths, "windows": windows}
+    if "score1" in outs[0]:
+        base = outs[0]["score1"].float()
+        knocked = torch.stack([o["score1"].float() for o in outs[1:]], 1).view(B, len(paths), len(windows))
+        absent = torch.stack([~keys.any(-1) | (torch.zeros(B, dtype=torch.bool) if rows is None else ~rows.any(-1)) for _, keys, rows in paths], 1)   # [B, P]
+        knocked = knocked.masked_fill(absent[:, :, None].to(knocked.device), float("nan"))
+        res.update(score1=base, knocked=knocked, delta=base[:, None, None] - knocked)
+    return res
+
+
 def frame_ablation_generate(model, *, pixel_values, input_ids, attention_mask, image_flags, max_new_tokens, candidate_ids=None, **gen):
     """WHAT IF a frame were not there, in WORDS: the reply to the stage-2 prompt as it is and once per unit with that unit's tokens hidden from
     the LLM (``generate_stage2(key_drop=model.unit_masks(...)[:, u])``) - unit u < F is frame u's visual tokens, unit F the motion token.

@@ -132,6 +132,8 @@ PROTOTYPES = {
     "aigv_op_attention_ex": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, C.c_int64, _P, _I, _I, _F, _F, _P, _P, _P, _I, _I, _P]),
     "aigv_op_attention_drop": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, C.c_int64, _P, _I, _I, _F, _F, _P, _P, _P, _I, _I, _P, _I, _P]),
     "aigv_key_drop_arm": (_I, [_P, _P, _I]),
+    "aigv_key_drop_arm_ex": (_I, [_P, _P, _P, _I, _I, _I]),
+    "aigv_op_attention_drop_rows": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, C.c_int64, _P, _I, _I, _F, _F, _P, _P, _P, _I, _I, _P, _P, _I, _P]),
     "aigv_op_kv_store": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "aigv_op_attention_probe": (_I, [_P, _I, _P, _I, _I32P, _I, _I, _I, _I, _I, C.c_int64, _I32P, _I, _P, _P, _I, _I32P, _I, _P, _P, _I, _I, _P, _P]),
     "aigv_op_attention_probe_tokens": (_I, [_P, _I, _P, _I, _I32P, _I, _I, _I, _I, _I, C.c_int64, _I32P, _I, _P, _P, _I, _I32P, _I, _P, _P, _I, _I, _P, _P, _I, _P]),

@@ -1,5 +1,6 @@
 """Which read-outs a scoring pass carries: label log-probs, candidate log-probs, top-k log-probs, score attention by segment and per token -
-and whether it runs under a key-drop mask (``key_drop``: not a read-out, but a per-call option that travels the same way).
+and whether it runs under a key-drop mask (``key_drop`` with its qualifiers ``key_drop_rows`` / ``key_drop_layers``: not a read-out, but a
+per-call option that travels the same way).
 
 This module is the one place that knows that decision.  A new read-out adds, HERE: a member to ``ReadOuts`` and its check to
 ``ReadOuts.parse``; the element it appends to a graph's host key to ``ReadOuts.key_tail``; its keyword to ``forward_kwargs``; and - when it
@@ -62,6 +63,44 @@ def key_drop_mask(key_drop, ids_shape=None, probing: bool = False) -> Optional[t
     return t.detach().to("cpu").bool().contiguous()
 
 
+def key_drop_qualifiers(key_drop, key_drop_rows=None, key_drop_layers=None, ids_shape=None, n_layers: Optional[int] = None):
+    """The two qualifiers of ``key_drop`` -> (None or a HOST bool tensor [B, N], None or a pair of ints (lo, hi)).  ``key_drop_rows`` (bool or
+    integer tensor [B, N] laid out like ``input_ids``, on any device): the query rows that are cut from the dropped keys - None: every row.
+    ``key_drop_layers`` = (lo, hi): the layers lo <= l < hi run under the mask - None: all of them; 0 <= lo <= hi <= ``n_layers`` where that
+    is known.  Either one without ``key_drop`` is a ValueError.  The clip-dependent rule (no row is cut from itself) is checked where the
+    plan is (``ScoringPass._key_drop_words``)."""
+    rows, window = None, None
+    if key_drop_rows is not None:
+        if key_drop is None:
+            raise ValueError("key_drop_rows: qualifies key_drop and needs one")
+        t = key_drop_rows
+        if not torch.is_tensor(t) or t.is_floating_point() or t.is_complex() or t.dim() != 2:
+            raise ValueError("key_drop_rows: expected a bool or integer tensor [B, N] laid out like input_ids")
+        if ids_shape is not None and tuple(t.shape) != tuple(ids_shape):
+            raise ValueError(f"key_drop_rows: shape {tuple(t.shape)} differs from input_ids {tuple(ids_shape)}")
+        rows = t.detach().to("cpu").bool().contiguous()
+    if key_drop_layers is not None:
+        if key_drop is None:
+            raise ValueError("key_drop_layers: qualifies key_drop and needs one")
+        w = tuple(key_drop_layers) if isinstance(key_drop_layers, (tuple, list)) else None
+        if w is None or len(w) != 2 or any(isinstance(v, bool) or not isinstance(v, int) for v in w):
+            raise ValueError(f"key_drop_layers: expected a pair of ints (lo, hi), got {key_drop_layers!r}")
+        lo, hi = w
+        if not 0 <= lo <= hi or (n_layers is not None and hi > n_layers):
+            raise ValueError(f"key_drop_layers: ({lo}, {hi}) outside 0 <= lo <= hi <= {n_layers if n_layers is not None else 'L'}")
+        window = (lo, hi)
+    return rows, window
+
+
+def refuse_key_drop_qualifiers(where: str, key_drop_rows=None, key_drop_layers=None) -> None:
+    """The entry points that run through the KV cache take ``key_drop`` whole or not at all: the mask kept beside the cache has neither rows
+    nor a layer window."""
+    for name, v in (("key_drop_rows", key_drop_rows), ("key_drop_layers", key_drop_layers)):
+        if v is not None:
+            raise ValueError(f"{name}: {where} does not take it (the key-drop mask kept beside the KV cache has neither query rows nor a layer "
+                             "window); forward() does")
+
+
 _NAN = float("nan")
 # every result laid out per label position, [B (N - 1)] + width: name in the result dict, the ``ReadOuts`` member that switches it on and gives
 # its trailing width (None: always there), dtype, fill wherever the row is not an answer row
@@ -83,19 +122,22 @@ class ReadOuts:
     segments: Optional[torch.Tensor] = None     # the user's attention_segments table; None: prompts.attention_segments
     token_attention: bool = False
     key_drop: Optional[torch.Tensor] = None     # host bool [B, N]: tokens hidden, as keys, from every row of their clip (forward; generate* check theirs with key_drop_mask)
+    key_drop_rows: Optional[torch.Tensor] = None    # host bool [B, N]: ... from these query rows only (None: every row)
+    key_drop_layers: Optional[tuple] = None         # (lo, hi): ... in the layers lo <= l < hi only (None: every layer)
 
     @classmethod
     def parse(cls, vocab: int, labels="given", return_logprobs: bool = False, candidate_ids=None, top_logprobs: Optional[int] = None,
               return_score_attention: bool = False, attention_segments=None, return_token_attention: bool = False, key_drop=None,
-              ids_shape=None) -> "ReadOuts":
+              ids_shape=None, key_drop_rows=None, key_drop_layers=None, n_layers: Optional[int] = None) -> "ReadOuts":
         """The record of a call's public keyword arguments, checked.  ``labels=None`` (``forward`` without labels) refuses candidates and top-k;
         the shared-prefix and generate entry points leave the default.  A user segment table is checked where its bins are counted
         (``n_segments``: it needs the shape of ``input_ids``)."""
         cand = candidates(candidate_ids, labels)
         k = top_logprobs_k(top_logprobs, vocab, labels)
         att = bool(return_score_attention or return_token_attention)
+        rows, window = key_drop_qualifiers(key_drop, key_drop_rows, key_drop_layers, ids_shape, n_layers)
         return cls(bool(return_logprobs), cand, k or None, att, attention_segments if att else None, bool(return_token_attention),
-                   key_drop_mask(key_drop, ids_shape, att))
+                   key_drop_mask(key_drop, ids_shape, att), rows, window)
 
     @property
     def wants_labels(self) -> bool:
@@ -134,7 +176,8 @@ def forward_kwargs(r: ReadOuts) -> dict:
     """The record as keyword arguments of ``forward``.  An option that is off is NOT passed: callers hand these to any object with
     ``forward``'s call form, which need not know the options it is not asked for."""
     kw = dict(return_logprobs=r.logprobs or None, candidate_ids=r.cand, top_logprobs=r.topk, return_score_attention=r.score_attention or None,
-              attention_segments=r.segments, return_token_attention=r.token_attention or None, key_drop=r.key_drop)
+              attention_segments=r.segments, return_token_attention=r.token_attention or None, key_drop=r.key_drop,
+              key_drop_rows=r.key_drop_rows, key_drop_layers=r.key_drop_layers)
     return {k: v for k, v in kw.items() if v is not None}
 
 

@@ -182,7 +182,8 @@ class ScoringPass:
             keep.append(pinned)
         return pinned.to(self.device, non_blocking=True)
 
-    def _prefill(self, ids_packed, slot, cu, vis, n_vis, motion, score_rows, logit_rows, keep_kv=False, kv_cap=0, probe=None, ld_tok=0, drop_words=None):
+    def _prefill(self, ids_packed, slot, cu, vis, n_vis, motion, score_rows, logit_rows, keep_kv=False, kv_cap=0, probe=None, ld_tok=0, drop_words=None,
+                 drop_row_words=None, drop_layers=None):
         b = len(cu) - 1
         T = cu[-1]
         lib, ctx = self._native(n_tokens=T, n_clips=b, out_rows=len(logit_rows), kv_cap=kv_cap)
@@ -199,7 +200,12 @@ class ScoringPass:
         att, tok = self._arm_score_attention(probe, ld_tok) if probe is not None else (None, None)   # (armed for exactly the pass below)
         if drop_words is not None:      # key_drop: host int64 [B, W] (prompts.key_drop_words) -> armed for exactly the pass below, which disarms
             words_d = up(drop_words, torch.int64)
-            native.check(lib.aigv_key_drop_arm(ctx, words_d.data_ptr(), int(drop_words.shape[1])), ctx)
+            if drop_row_words is None and drop_layers is None:
+                native.check(lib.aigv_key_drop_arm(ctx, words_d.data_ptr(), int(drop_words.shape[1])), ctx)
+            else:       # key_drop_rows / key_drop_layers: the mask by query row (same layout, same width) and layer window
+                rows_d = up(drop_row_words, torch.int64) if drop_row_words is not None else None
+                lo, hi = drop_layers if drop_layers is not None else (0, self.config.llm_config.num_hidden_layers)
+                native.check(lib.aigv_key_drop_arm_ex(ctx, words_d.data_ptr(), native.ptr(rows_d), int(drop_words.shape[1]), int(lo), int(hi)), ctx)
         native.check(lib.aigv_llm_prefill(
             ctx, ids_d.data_ptr(), slot_d.data_ptr(), cu_a, b, native.ptr(vis), n_vis, native.ptr(motion),
             sr_a, native.ptr(score), lr_a, len(logit_rows), amax.data_ptr(), int(keep_kv), native.stream_ptr()), ctx)
@@ -284,10 +290,35 @@ class ScoringPass:
         seg_of = torch.where(row_of >= 0, seg.long()[row_of.clamp_min(0)], torch.full_like(row_of, -1))      # [B, N]: segment id, -1 where not run
         return torch.stack([seg_of == u for u in range(F + 1)], 1)
 
-    def _key_drop_words(self, plan, key_drop: torch.Tensor) -> torch.Tensor:
+    def segment_masks(self, input_ids, attention_mask=None, image_flags=None, n_frames: Optional[int] = None) -> dict:
+        """The token groups of a batch as ``key_drop`` / ``key_drop_rows`` masks (host only, no GPU work): a dict of bool [B, N] laid out like
+        ``input_ids`` - ``frames`` (every visual token: the union of ``unit_masks[:, :F]``), ``motion`` (the motion token), ``first`` (the
+        clip's first token, the sink), ``text_before`` (the other text up to the last visual token), ``text_after`` (the text behind it:
+        question and answer) and ``score_row`` (the row the score head reads, inside ``text_after``; all False in a stage-1 model).  The first
+        five partition every clip's tokens.  Built from ``prompts.attention_segments``, the table the attention bins use.  ``n_frames``: the
+        frames handed to ``forward`` (default: ``image_flags.shape[0]``)."""
+        if n_frames is None:
+            if image_flags is None:
+                raise ValueError("segment_masks: pass n_frames or image_flags")
+            n_frames = int(image_flags.shape[0])
+        from . import prompts
+        plan = self._plan(input_ids, attention_mask, None, image_flags, int(n_frames), drop_dead_tail=False)      # (every un-padded token, also those behind the score row)
+        seg, S = self._default_segments(plan)
+        F = S - prompts.N_TEXT_SEGMENTS
+        row_of = plan["row_of"]
+        seg_of = torch.where(row_of >= 0, seg.long()[row_of.clamp_min(0)], torch.full_like(row_of, -1))      # [B, N]: segment id, -1 for padding
+        score = torch.zeros_like(row_of, dtype=torch.bool)
+        for r in plan["score_rows"] or []:
+            score |= row_of == int(r)
+        return {"frames": (seg_of >= 0) & (seg_of < F), "motion": seg_of == F, "first": seg_of == F + 1, "text_before": seg_of == F + 2,
+                "text_after": seg_of == F + 3, "score_row": score}
+
+    def _key_drop_words(self, plan, key_drop: torch.Tensor, key_drop_rows: Optional[torch.Tensor] = None):
         """``forward(key_drop=...)``: the host bool mask [B, N] checked against the plan -> ``prompts.key_drop_words`` (host int64 [B, W]).
         Positions the pass does not run (padding, a dropped dead tail) are ignored.  Refused before anything is launched: dropping a clip's
-        first token (the sink: it guarantees that every row keeps a visible key) and dropping a row whose output is consumed."""
+        first token (the sink: it guarantees that every row keeps a visible key) and dropping a row whose output is consumed.
+        With ``key_drop_rows`` (host bool [B, N]) -> (key words, row words), both [B, W]: no row may be cut from itself (``key_drop_rows &
+        key_drop`` is empty - with the first token that guarantees every row a visible key), and a consumed row may then be a key."""
         from . import prompts
         row_of, cu = plan["row_of"], plan["cu"]
         if tuple(key_drop.shape) != tuple(row_of.shape):
@@ -298,6 +329,13 @@ class ScoringPass:
         for b in range(len(cu) - 1):
             if bool(dropped[cu[b]]):
                 raise ValueError(f"key_drop: clip {b}: the first token cannot be dropped (it guarantees every row a visible key)")
+        if key_drop_rows is not None:
+            if tuple(key_drop_rows.shape) != tuple(row_of.shape):
+                raise ValueError(f"key_drop_rows: shape {tuple(key_drop_rows.shape)} differs from input_ids {tuple(row_of.shape)}")
+            both = (key_drop_rows & key_drop & (row_of >= 0)).any(1)
+            if bool(both.any()):
+                raise ValueError(f"key_drop_rows: clip {int(both.nonzero()[0])}: a token is both a dropped key and a selected row (a row is never cut from itself)")
+            return prompts.key_drop_words(key_drop, cu, row_of), prompts.key_drop_words(key_drop_rows, cu, row_of)
         for r in list(plan["logit_rows"]) + list(plan["score_rows"] or []):
             if bool(dropped[r]):
                 b = max(i for i in range(len(cu) - 1) if cu[i] <= r)
@@ -327,7 +365,8 @@ class ScoringPass:
                 output_hidden_states=None, return_dict=None, motion_feature: Optional[torch.Tensor] = None,
                 visual_tokens: Optional[torch.Tensor] = None, full_logits: bool = False, return_logprobs: bool = False,
                 candidate_ids=None, top_logprobs: Optional[int] = None, return_score_attention: bool = False, attention_segments=None,
-                return_token_attention: bool = False, key_drop: Optional[torch.Tensor] = None):
+                return_token_attention: bool = False, key_drop: Optional[torch.Tensor] = None, key_drop_rows: Optional[torch.Tensor] = None,
+                key_drop_layers: Optional[tuple] = None):
         """Stage-2 eval pass (modeling_internvl_chat.py:306-488) or, with ``stage=1``, the stage-1 pass
         (internvl_chat_eval1/modeling_internvl_chat.py:250-366).  ``visual_tokens`` optionally supplies
         already all-gathered pre-projector tokens (frame-DP) instead of ``pixel_values``.
@@ -383,21 +422,35 @@ class ScoringPass:
         consumed row (an answer row, the score row), and in combination with ``return_score_attention`` / ``return_token_attention`` (the
         probe does not know the mask).  With graph replay enabled a call with ``key_drop`` runs eagerly - the same bits as with replay
         off - and captures nothing; unmasked calls keep replaying.  ``unit_masks`` builds the per-frame masks,
-        ``eval_utils.frame_ablation`` the per-frame score deltas."""
+        ``eval_utils.frame_ablation`` the per-frame score deltas.
+
+        ``key_drop_rows`` / ``key_drop_layers`` qualify ``key_drop`` - WHICH WAY, AT WHICH DEPTH a token's content travels (the attention
+        knock-out): with ``key_drop_rows`` (bool or integer tensor [B, N] like ``input_ids``) only those query rows are cut from the dropped
+        keys, with ``key_drop_layers=(lo, hi)``, 0 <= lo <= hi <= L, only in the layers lo <= l < hi; every other edge and every other layer
+        is untouched.  What the reference computes when the additive mask of those layers also holds ``finfo.min`` at every (row r, key j) with
+        ``key_drop_rows[b, r] and key_drop[b, j]``.  Left at None they change nothing: every row, every layer.  ValueError, before anything
+        is launched: either one without ``key_drop``; a wrong shape or window; a token that is both a dropped key and a selected row (a row is
+        never cut from itself) - under ``key_drop_rows`` a consumed row MAY then be a dropped key; the first token never.  Empty rows, empty
+        keys or an empty window give the plain pass's bits.  ``segment_masks`` builds the usual groups (frames, text after them, the score
+        row), ``eval_utils.flow_knockout`` the score deltas per path and layer window."""
         if position_ids is not None or past_key_values is not None:
             raise NotImplementedError("the eval pass takes default positions and no cache, like the reference drivers")
         if self.img_context_token_id is None:
             raise AssertionError("img_context_token_id must be set by the caller (stage2_eval.py:810)")
-        drop_words = None
+        drop_words = drop_row_words = None
+        n_layers = self.config.llm_config.num_hidden_layers
+        kd_rows, kd_layers = readouts.key_drop_qualifiers(key_drop, key_drop_rows, key_drop_layers, None if input_ids is None else input_ids.shape, n_layers)
         if key_drop is not None:        # checked in full on the host before anything touches the device (a plan of its own: host work only)
             kd = readouts.key_drop_mask(key_drop, input_ids.shape, bool(return_score_attention or return_token_attention))
             src = visual_tokens if visual_tokens is not None else pixel_values
             drop_words = self._key_drop_words(self._plan(input_ids, attention_mask, labels, image_flags, (src.tokens if isinstance(src, VisualAhead) else src).shape[0],
-                                                         full_logits), kd)
+                                                         full_logits), kd, kd_rows)
+            if kd_rows is not None:
+                drop_words, drop_row_words = drop_words
         pixel_values, visual_tokens, motion_feature = self._take_ahead(pixel_values, visual_tokens, motion_feature)
         parse = lambda: readouts.ReadOuts.parse(self.config.llm_config.vocab_size, labels, return_logprobs, candidate_ids, top_logprobs,
                                                 return_score_attention, attention_segments, return_token_attention, key_drop,
-                                                None if input_ids is None else input_ids.shape)
+                                                None if input_ids is None else input_ids.shape, key_drop_rows, key_drop_layers, n_layers)
         ro = None
         if self._graph_replay_enabled and self._capture_keep is None:
             ro = parse()
@@ -421,7 +474,7 @@ class ScoringPass:
         probe = self._score_attention_probe(plan, input_ids, ro) if ro.score_attention else None
         score, amax, *armed = self._prefill(plan["ids_packed"], plan["slot"], plan["cu"], vit_embeds, plan["n_vis"], motion,
                                             plan["score_rows"], plan["logit_rows"], probe=probe, ld_tok=N if ro.token_attention else 0,
-                                            drop_words=drop_words)
+                                            drop_words=drop_words, drop_row_words=drop_row_words, drop_layers=kd_layers)
         att, tok = armed or (None, None)        # (_prefill hands the probe's tensors back only when it armed one)
         reads = self._read_rows(B if score is not None else 0, len(plan["logit_rows"]), ro, lp_labels)
         return self._outputs(plan, B, N, score, amax, mos, reads, att, tok)
@@ -658,7 +711,7 @@ class ScoringPass:
     def forward_shared_prefix(self, prompts, pixel_values: Optional[torch.Tensor] = None, image_flags: Optional[torch.Tensor] = None,
                               motion_feature: Optional[torch.Tensor] = None, visual_tokens: Optional[torch.Tensor] = None, mos=None,
                               return_logprobs: bool = False, candidate_ids=None, top_logprobs: Optional[int] = None,
-                              return_score_attention: bool = False, return_token_attention: bool = False):
+                              return_score_attention: bool = False, return_token_attention: bool = False, key_drop_rows=None, key_drop_layers=None):
         """Score the same clips under several prompts that share their beginning - the reference's four quality
         perspectives ask four questions BEHIND the same system + frame + motion tokens (8f-3) and
         run four full passes (stage2_eval.py evaluates one jsonl per perspective).  Here the common prefix runs once
@@ -673,7 +726,9 @@ class ScoringPass:
         ``score_attention`` [B, L, n_heads, F + 4] as ``forward`` defines it (default segments), read by the continuation pass over the cached
         prefix keys and the prompt's own tokens; at most 64 (clip, prompt) pairs.  ``return_token_attention`` (implies it): every prompt's dict
         also carries ``score_attention_tokens`` [B, L, n_heads, N] as ``forward`` defines it, N = the longest prefix + prompt length over the
-        prompts; the columns cover the prefix and then the prompt's own tokens, in order."""
+        prompts; the columns cover the prefix and then the prompt's own tokens, in order.  ``key_drop_rows`` / ``key_drop_layers`` are refused with
+        a ValueError: the prefix lives in the KV cache, ``forward`` takes them."""
+        readouts.refuse_key_drop_qualifiers("forward_shared_prefix", key_drop_rows, key_drop_layers)
         if self.img_context_token_id is None:
             raise AssertionError("img_context_token_id must be set by the caller (stage2_eval.py:810)")
         if not prompts:

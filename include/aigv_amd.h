@@ -46,7 +46,8 @@ extern "C" {
                                 score-row attention probe (aigv_score_attention_arm, aigv_op_attention_probe), then by its dense per-key
                                 form (aigv_score_attention_arm_tokens, aigv_op_attention_probe_tokens), then by the key-drop mask of the
                                 prefill attention (aigv_key_drop_arm, aigv_op_attention_drop), then by the key-drop form of the decode attention
-                                (aigv_op_attention_decode_drop; the mask now travels with the KV cache: aigv_key_drop_arm)
+                                (aigv_op_attention_decode_drop; the mask now travels with the KV cache: aigv_key_drop_arm), then by the
+                                key-drop mask by query row and layer window (aigv_key_drop_arm_ex, aigv_op_attention_drop_rows)
                                 - added symbols only: a library without them is refused at load
                                 time, "missing <name>" */
 
@@ -215,6 +216,21 @@ int aigv_score_attention_arm_tokens(aigv_ctx* ctx, const int32_t* rows_host, int
  * that is also armed with the score-attention probe, and the probe armed in front of aigv_llm_extend on a masked cache (the probe does not
  * know the mask). */
 int aigv_key_drop_arm(aigv_ctx* ctx, const uint64_t* words_dev, int ld_words);
+/* The key-drop mask by query row and layer window - the attention knock-out: cut the edges from a set of query rows to a set of keys inside a
+ * window of layers.  aigv_key_drop_arm(ctx, w, ld) = aigv_key_drop_arm_ex(ctx, w, NULL, ld, 0, llm_layers).  Arms exactly the next
+ * aigv_llm_prefill, which disarms on every way out.
+ *   row_words_dev  DEVICE uint64 [n_clips][ld_words] in words_dev's layout, or NULL = every row: bit (i & 63) of word [clip][i >> 6] set = the
+ *                  query row at position i of that clip is subject to the mask.  A score is hidden iff its key's bit and its row's bit are both
+ *                  set; every other row sees what the causal mask leaves it.  Bits past a clip's length are ignored.
+ *   layer_begin, layer_end   only the layers layer_begin <= l < layer_end run the masked attention (the row-selective form of the prefill kernel
+ *                  with row words, its key-drop form without); every other layer runs the unmasked launch it always ran.  An empty window is
+ *                  the plain pass.
+ * What the reference computes when the additive attention mask of those layers also holds finfo.min at every (row, key) both words select.
+ * Refused with AIGV_ERR_ARG and a message, nothing armed: a window outside 0 <= layer_begin <= layer_end <= llm_layers, words that are null
+ * (words_dev) or not 8-byte aligned, ld_words < 1.  Refused by the pass, before any launch: ld_words below ceil(longest clip / 64); keep_kv
+ * together with row words or a window other than [0, llm_layers) - the mask kept beside the KV cache has neither; the probe armed as well.
+ * aigv_llm_extend refuses an armed context as it does after aigv_key_drop_arm. */
+int aigv_key_drop_arm_ex(aigv_ctx* ctx, const uint64_t* words_dev, const uint64_t* row_words_dev, int ld_words, int layer_begin, int layer_end);
 
 /* Replicate the n kept sequences `copies` times (cache slots [0, n) -> [n, 2n), ...; needs n * copies <= max_seqs): the copies can
  * then take DIFFERENT continuations in one aigv_llm_extend call over n * copies sequences (sequence c * n + b continues clip b),
@@ -434,6 +450,16 @@ int aigv_op_attention_drop(const void* q, int ldq, const void* k, int ldk, const
                            int max_len, int n_heads, int n_kv_heads, int q_group_stride, int kv_head_stride, int64_t kv_seq_stride,
                            const int32_t* kv_off, int head_dim, int causal, float post_div, float q_prescale, const int32_t* pos, const void* cos,
                            const void* sin, int pos_is_row, int q_tail, const uint64_t* key_drop, int ld_drop, void* stream);
+/* aigv_op_attention_drop with a row selector (tests/test_gpu_key_drop_rows.py): row_words DEVICE uint64 [n_seq][ld_drop] in key_drop's layout, or
+ * NULL (then the same call as aigv_op_attention_drop, the same kernels).  Bit (i & 63) of word row_words[s * ld_drop + (i >> 6)] set = query row i
+ * of sequence s is subject to key_drop; a score is hidden iff its key's bit and its row's bit are both set.  The packed prefill form only.
+ * Refused with AIGV_ERR_ARG and a message, before anything is launched: what aigv_op_attention_drop refuses, row_words without key_drop, row_words
+ * with kv_off or kv_seq_stride, and misaligned row_words. */
+int aigv_op_attention_drop_rows(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, const int32_t* cu,
+                                int n_seq, int max_len, int n_heads, int n_kv_heads, int q_group_stride, int kv_head_stride, int64_t kv_seq_stride,
+                                const int32_t* kv_off, int head_dim, int causal, float post_div, float q_prescale, const int32_t* pos,
+                                const void* cos, const void* sin, int pos_is_row, int q_tail, const uint64_t* key_drop, const uint64_t* row_words,
+                                int ld_drop, void* stream);
 /* The score-row attention probe on plain pointers (one layer; tests use it without a model): out [n_rows, n_heads, n_segments] fp32 as
  * aigv_score_attention_arm defines it.  q: UNROTATED fused rows (query head h at column (h / g) * q_group_stride + (h % g) * head_dim), rotated
  * by the kernel at the row's position from cos / sin [max_pos, head_dim / 2]; k: already rotated, in aigv_op_attention_ex's two forms -

@@ -5,6 +5,8 @@ that drift hits all of them; medians over the blocks' per-call times (device-syn
   step              forward(pixel_values=...)                                  the whole unmasked step (ViT, SlowFast, projector, InternLM2, heads)
   llm               forward(visual_tokens=..., motion_feature=...)             projector + InternLM2 + heads, unmasked: what a masked pass is compared with
   llm, frame 0 off  the same with key_drop = unit_masks[:, 0]                  one frame (256 tokens) of every clip hidden
+  llm, frames->text the same with key_drop = segment_masks["frames"],           the row-selective form in all layers: the text behind the frames cannot
+                    key_drop_rows = segment_masks["text_after"]                read them (every frame token a dropped key, mixed and unselected waves)
   ablation          eval_utils.frame_ablation (8 frames: 10 passes, ViT once)  next to 10 x step, what the loop would cost without the helper
 
 ``--variant-lib PATH`` repeats the two llm variants in a child process on another build of the library (``AIGV_AMD_LIB``; the diagnostic
@@ -42,7 +44,7 @@ def main():
     ap.add_argument("--clips", type=int, default=4)
     ap.add_argument("--frames", type=int, default=8)
     ap.add_argument("--model", default="8b", choices=["8b", "tiny"])
-    ap.add_argument("--llm-only", action="store_true", help="the two llm variants alone (the child process of --variant-lib)")
+    ap.add_argument("--llm-only", action="store_true", help="the llm variants alone (the child process of --variant-lib)")
     ap.add_argument("--variant-lib", default="", help="also measure the two llm variants on this build of the library (child process, same box)")
     ap.add_argument("--build-no-skip", default="", metavar="PATH", help="build the no-skip diagnostic library to PATH and exit (no GPU needed)")
     ap.add_argument("--out", default="")
@@ -77,7 +79,9 @@ def main():
     torch.cuda.synchronize()
     llm_kw = dict(text, visual_tokens=tokens, motion_feature=mf)
 
-    calls = {"llm": lambda: model(**llm_kw), "llm, frame 0 off": lambda: model(**llm_kw, key_drop=units[:, 0])}
+    seg = model.segment_masks(text["input_ids"], text["attention_mask"], flags)
+    calls = {"llm": lambda: model(**llm_kw), "llm, frame 0 off": lambda: model(**llm_kw, key_drop=units[:, 0]),
+             "llm, frames->text": lambda: model(**llm_kw, key_drop=seg["frames"], key_drop_rows=seg["text_after"])}
     if not args.llm_only:
         calls = dict({"step": lambda: model(pixel_values=pv, **text)}, **calls,
                      ablation=lambda: eval_utils.frame_ablation(model, pixel_values=pv, **text))
@@ -103,6 +107,8 @@ def main():
     lines += [f"  {n:18s} {med[n]:9.3f} ms/call (min {min(times[n]):.3f}, max {max(times[n]):.3f}, {len(times[n])} calls)" for n in calls]
     lines.append(f"  llm, frame 0 off - llm {med['llm, frame 0 off'] - med['llm']:+.3f} ms ({100 * (med['llm, frame 0 off'] / med['llm'] - 1):+.2f} %); "
                  f"dropped tokens per clip: {int(units[0, 0].sum())} of {N}")
+    lines.append(f"  llm, frames->text - llm {med['llm, frames->text'] - med['llm']:+.3f} ms ({100 * (med['llm, frames->text'] / med['llm'] - 1):+.2f} %); "
+                 f"dropped keys per clip: {int(seg['frames'][0].sum())}, selected rows per clip: {int(seg['text_after'][0].sum())} of {N}, all layers")
     if not args.llm_only:
         lines.append(f"  ablation / step {med['ablation'] / med['step']:.2f} ({T + 2} passes; {T + 2} x step = {(T + 2) * med['step']:.1f} ms)")
         res = timed(calls["ablation"])[1]
