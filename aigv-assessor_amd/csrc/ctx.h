@@ -142,6 +142,17 @@ struct aigv_ctx {
     int ld = 0;
     int layer_begin = 0, layer_end = 0;
   } drop;
+  // depth lens (aigv_depth_lens_arm): armed for exactly the next aigv_llm_prefill, which copies the rows `rows` = [score rows | token rows] of the
+  // residual stream after the embedding and after every layer into the caller's buffers (raw, and under the final norm) and runs the score head on
+  // the score rows of every depth
+  struct {
+    bool armed = false;
+    int n_score = 0, n_token = 0;
+    int32_t rows[2 * AIGV_MAX_LENS_ROWS];
+    bf16_t *hidden = nullptr, *normed = nullptr;   // device, the caller's: [llm_layers + 1][n_score + n_token][H]
+    float* score = nullptr;                        // device, the caller's: [llm_layers + 1][n_score]
+  } lens;
+  int32_t* l_lensidx = nullptr;   // device [4 * AIGV_MAX_LENS_ROWS]: the armed pass's lens rows | their places among the consumed rows (row trimming)
   // profiling
   bool prof = false;
   int gemm_cls = AIGV_PROF_GEMM;   // class the GEMM launches are booked under: AIGV_PROF_GEMM_VIT inside aigv_vit_forward / aigv_project
@@ -266,12 +277,12 @@ constexpr size_t SPLITK_MAX_FLOATS = (size_t)64 << 20;   // 256 MB of fp32 split
 int splitk_scratch(aigv_ctx* c, size_t need_floats, float** out);
 
 // ---- the score-row attention probe of an armed pass (probe.hip) --------------------------------------------------------------------
-// DisarmScope: the pass that finds the context armed - with the probe, with a key-drop mask (aigv_key_drop_arm) - disarms it on every way out.  probe_plan: the probe's arguments for this pass (rows
+// DisarmScope: the pass that finds the context armed - with the probe, with a key-drop mask (aigv_key_drop_arm), with the depth lens (aigv_depth_lens_arm) - disarms it on every way out.  probe_plan: the probe's arguments for this pass (rows
 // validated against cu; off_host: keys cached in front of every sequence, or null), built ONCE per pass; probe_layer: the launch of layer li.
 struct DisarmScope {
   aigv_ctx* c;
   explicit DisarmScope(aigv_ctx* c_) : c(c_) {}
-  ~DisarmScope() { c->probe.armed = false; c->drop.armed = false; }
+  ~DisarmScope() { c->probe.armed = false; c->drop.armed = false; c->lens.armed = false; }
 };
 int probe_plan(aigv_ctx* c, const char* op, const int32_t* cu, int B, const int32_t* off_host, ProbeArgs* out);
 int probe_layer(aigv_ctx* c, const ProbeArgs& plan, int li, bool cache, hipStream_t s);

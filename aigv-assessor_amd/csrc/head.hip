@@ -7,6 +7,7 @@
 // One workgroup = 4 waves = one 16-row slab of W (two slabs for SwiGLU); the waves split K four ways, stream
 // their W fragments straight from global memory into MFMA A-operands (no LDS round trip: every weight byte
 // is used once), keep the x fragments (L2-resident) as B-operands, and combine partial sums through LDS.
+#include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 
@@ -356,28 +357,43 @@ __global__ void unpack_argmax_kernel(const unsigned long long* __restrict__ pack
 // of Linear+ReLU with a bf16 rounding after each Linear (:82-94).  Without a NaN the guard leaves an Inf alone: the row then turns
 // into NaN / Inf in the Linears, and the ReLUs pass a NaN on as F.relu does.  The wide layers run on the skinny GEMM
 // (weights streamed once for all clips); the narrow tail (fan-in < 128) runs in one small kernel.
+// (the guard of one batch slice by one 256-thread workgroup, X [B, H] rows -> OUT [B, H] dense: written once for the two kernels below.  A macro, not
+// a function: through an inlined function hipcc allocates score_guard_kernel's registers differently, and its device assembly is pinned)
+#define AIGV_SCORE_GUARD_SLICE(X, LDX, B, H, OUT)                              \
+  __shared__ int any_nan;                                                      \
+  if (threadIdx.x == 0) any_nan = 0;                                           \
+  __syncthreads();                                                             \
+  int nan_here = 0;                                                            \
+  for (int i = threadIdx.x; i < (B) * (H); i += 256) {                         \
+    const float v = bf2f((X)[(size_t)(i / (H)) * (LDX) + (i % (H))]);          \
+    nan_here |= (v != v);                                                      \
+  }                                                                            \
+  if (nan_here) atomicOr(&any_nan, 1);                                         \
+  __syncthreads();                                                             \
+  const bool fix = any_nan != 0;                                               \
+  for (int i = threadIdx.x; i < (B) * (H); i += 256) {                         \
+    float v = bf2f((X)[(size_t)(i / (H)) * (LDX) + (i % (H))]);                \
+    if (fix) {                                                                 \
+      if (v != v) v = 0.f;                                                     \
+      else if (isinf(v)) v = v > 0 ? 1e9f : -1e9f;                             \
+    }                                                                          \
+    (OUT)[i] = f2bf(v);                                                        \
+  }
+
 __global__ __launch_bounds__(256) void score_guard_kernel(const bf16_t* __restrict__ x, int ldx, int B, int H,
                                                           bf16_t* __restrict__ out) {
-  __shared__ int any_nan;
-  if (threadIdx.x == 0) any_nan = 0;
-  __syncthreads();
-  int nan_here = 0;
-  for (int i = threadIdx.x; i < B * H; i += 256) {
-    const float v = bf2f(x[(size_t)(i / H) * ldx + (i % H)]);
-    nan_here |= (v != v);
-  }
-  if (nan_here) atomicOr(&any_nan, 1);
-  __syncthreads();
-  const bool fix = any_nan != 0;
-  for (int i = threadIdx.x; i < B * H; i += 256) {
-    float v = bf2f(x[(size_t)(i / H) * ldx + (i % H)]);
-    if (fix) {
-      if (v != v) v = 0.f;
-      else if (isinf(v)) v = v > 0 ? 1e9f : -1e9f;
-    }
-    out[i] = f2bf(v);
-  }
+  AIGV_SCORE_GUARD_SLICE(x, ldx, B, H, out)
 }
+
+// The grouped form (aigv_launch_score_head_groups): workgroup g guards ITS B rows - x + g * group_stride - under its own flag, as the
+// reference would guard G batch slices one after the other; out is dense [G * B, H].
+__global__ __launch_bounds__(256) void score_guard_groups_kernel(const bf16_t* __restrict__ x, int ldx, size_t group_stride, int B, int H,
+                                                                 bf16_t* __restrict__ out) {
+  const bf16_t* xg = x + (size_t)blockIdx.x * group_stride;
+  bf16_t* og = out + (size_t)blockIdx.x * B * H;
+  AIGV_SCORE_GUARD_SLICE(xg, ldx, B, H, og)
+}
+#undef AIGV_SCORE_GUARD_SLICE
 
 // remaining narrow layers: one workgroup per clip; activations ping-pong in LDS (all dims <= 1024 here)
 __global__ __launch_bounds__(256) void score_tail_kernel(const ScoreHeadArgs a, int first_layer) {
@@ -537,10 +553,11 @@ hipError_t aigv_launch_skinny_gemm(const bf16_t* x, int ldx, int R, const bf16_t
 // 1095-1096).  out is [R, ldo] bf16 with ldo >= V rounded up to 4 (the store epilogue writes 4 columns per lane; columns >= V of a
 // row are padding).  Used where the whole distribution is needed - sampling in generate() - the greedy paths use the fused argmax.
 hipError_t aigv_launch_lm_head_logits(const bf16_t* h, int R, int H, const bf16_t* W, int V, bf16_t* out, int ldo, hipStream_t s,
-                                      bool one_form) {
+                                      bool one_form, int ldh) {
   if (R <= 0) return hipSuccess;
-  if (R > 64 || H % 128 || ldo < ((V + 3) / 4) * 4 || (ldo % 4)) return hipErrorInvalidValue;
-  return launch_skinny<SK_STORE>(h, H, R, W, H, V, H, nullptr, nullptr, 0, out, ldo, nullptr, s, nullptr, one_form ? 0 : 1);
+  if (ldh == 0) ldh = H;
+  if (R > 64 || H % 128 || ldo < ((V + 3) / 4) * 4 || (ldo % 4) || ldh < H || ldh % 8) return hipErrorInvalidValue;
+  return launch_skinny<SK_STORE>(h, ldh, R, W, H, V, H, nullptr, nullptr, 0, out, ldo, nullptr, s, nullptr, one_form ? 0 : 1);
 }
 
 hipError_t aigv_launch_lm_head_argmax(const bf16_t* h, int R, int H, const bf16_t* W, int V,
@@ -606,5 +623,46 @@ hipError_t aigv_launch_score_head(const ScoreHeadArgs& a, bf16_t* scratch, hipSt
   } else {
     return hipErrorInvalidValue;   // the last layer (fan-out 1) always runs in the tail kernel
   }
+  return hipGetLastError();
+}
+
+// G batch slices of B rows each in one go (the depth lens: one slice per depth): slice g = rows x + g * group_stride (leading dimension
+// a.ldx), guarded on its own; the GEMM layers then run over all G * B rows in chunks of at most 64 - a row's bits do not depend on how many
+// rows share its launch - and the tail kernel over all of them.  a.score: [G * B].  scratch: 3 * G * B * max(dims) bf16.  Slice for slice
+// the bits of aigv_launch_score_head.
+hipError_t aigv_launch_score_head_groups(const ScoreHeadArgs& a, int G, size_t group_stride, bf16_t* scratch, hipStream_t s) {
+  if (a.B <= 0 || G <= 0) return hipSuccess;
+  if (a.n_layers < 1 || a.n_layers > 8 || a.B > 64 || !scratch) return hipErrorInvalidValue;
+  int maxd = 0;
+  for (int i = 0; i <= a.n_layers; ++i) {
+    if (a.dims[i] <= 0) return hipErrorInvalidValue;
+    maxd = a.dims[i] > maxd ? a.dims[i] : maxd;
+  }
+  int L = 0;
+  while (L < a.n_layers && a.dims[L] % 128 == 0 && a.dims[L + 1] % 4 == 0) ++L;
+  if (L == a.n_layers) return hipErrorInvalidValue;   // the last layer (fan-out 1) always runs in the tail kernel
+  for (int i = L; i <= a.n_layers; ++i)
+    if (a.dims[i] > 1024) return hipErrorInvalidValue;
+  const int rows = G * a.B;
+  bf16_t* xg = scratch;
+  bf16_t* pp[2] = {scratch + (size_t)rows * maxd, scratch + (size_t)2 * rows * maxd};
+  hipLaunchKernelGGL(score_guard_groups_kernel, dim3(G), dim3(256), 0, s, a.x, a.ldx, group_stride, a.B, a.dims[0], xg);
+  const bf16_t* cur = xg;
+  int ld = a.dims[0], flip = 0;
+  for (int l = 0; l < L; ++l) {
+    const int din = a.dims[l], dout = a.dims[l + 1];
+    for (int r0 = 0; r0 < rows; r0 += 64) {
+      hipError_t e = launch_skinny<SK_RELU>(cur + (size_t)r0 * ld, ld, std::min(64, rows - r0), a.w[l], din, dout, din, a.b[l], nullptr, 0,
+                                            pp[flip] + (size_t)r0 * dout, dout, nullptr, s);
+      if (e != hipSuccess) return e;
+    }
+    cur = pp[flip];
+    ld = dout;
+    flip ^= 1;
+  }
+  ScoreHeadArgs t = a;
+  t.x = cur;
+  t.ldx = ld;
+  hipLaunchKernelGGL(score_tail_kernel, dim3(rows), dim3(256), 0, s, t, L);
   return hipGetLastError();
 }

@@ -197,6 +197,9 @@ hipError_t aigv_launch_pixel_shuffle(const bf16_t* vit, int grid, int Hv, bf16_t
 hipError_t aigv_launch_im2col(const bf16_t* frames, int F, int C, int S, int P, int Kp, bf16_t* out, hipStream_t s);
 // x[f*(np+1)] = cls_pos (class token + its position row, precomputed) for every frame
 hipError_t aigv_launch_gather_rows(const bf16_t* src, int ld, const int32_t* idx, int n, bf16_t* dst, int H, hipStream_t s);
+// the depth lens' tap: raw[i, :H] = src[idx[i] * ld ..] unchanged and normed[i, :H] = RMSNorm(that row) * w with aigv_launch_rmsnorm's bits (raw, normed dense)
+hipError_t aigv_launch_lens_tap(const bf16_t* src, int ld, const int32_t* idx, int n, const bf16_t* w, bf16_t* raw, bf16_t* normed, int H, float eps,
+                                hipStream_t s);
 hipError_t aigv_launch_scatter_rows(const bf16_t* src, const int32_t* idx, int n, bf16_t* dst, int ld, int H, hipStream_t s);   // dst[idx[i]] = src[i]
 hipError_t aigv_launch_cls_rows(const bf16_t* cls_pos, bf16_t* x, int F, int tokens_per_frame, int H, hipStream_t s);
 // RoPE in place on the fused qkv rows: per kv group, slots 0..g (q heads and K) are rotated.
@@ -267,8 +270,9 @@ hipError_t aigv_launch_lm_head_lse_partials(const bf16_t* h, int R, int H, const
 // lm-head logits (bf16, the matmul output the reference upcasts) of R rows into out[R, ldo], ldo >= roundup(V, 4)
 // one_form: the 4-slice form for every row count (that of the fused argmax), so that a row's logits do not depend on how many rows
 // share the launch; otherwise <= 16 rows of a vocabulary <= 4096 take the 8-slice GEMV form
+// ldh: leading dimension of the rows of h (0: H)
 hipError_t aigv_launch_lm_head_logits(const bf16_t* h, int R, int H, const bf16_t* W, int V, bf16_t* out, int ldo, hipStream_t s,
-                                      bool one_form = false);
+                                      bool one_form = false, int ldh = 0);
 // log-probabilities of bf16 logits rows [rows, ldo >= V] in fp32 (row_logprob_kernel, logprob.hip): one workgroup per row, a lane -> column
 // mapping and a reduction tree fixed by V alone (batch-invariant bits); an id outside [0, V) gives NaN.
 //   label:      out[r] = logits[r, labels[r]] - logsumexp(logits[r, :V]), labels DEVICE int64 [rows]
@@ -289,6 +293,9 @@ struct ScoreHeadArgs {
 };
 // scratch: 3 * B * max(dims) bf16; B <= 64 per call
 hipError_t aigv_launch_score_head(const ScoreHeadArgs& a, bf16_t* scratch, hipStream_t s);
+// G batch slices of a.B <= 64 rows each, slice g at a.x + g * group_stride elements, every slice under its own NaN guard; a.score [G * a.B];
+// scratch: 3 * G * a.B * max(dims) bf16.  Slice for slice the bits of aigv_launch_score_head (the depth lens: one slice per depth)
+hipError_t aigv_launch_score_head_groups(const ScoreHeadArgs& a, int G, size_t group_stride, bf16_t* scratch, hipStream_t s);
 // KV-cache append: copies the K/V slots of fused qkv rows into [n_seq, n_kv, cap, D] caches
 hipError_t aigv_launch_kv_store(const bf16_t* qkv, int ld, const int32_t* seq_of_tok, const int32_t* pos,
                                 bf16_t* kc, bf16_t* vc, int tokens, int n_groups, int g, int D, int cap,

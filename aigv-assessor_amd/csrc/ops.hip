@@ -467,9 +467,9 @@ int aigv_op_skinny_rope_kv_fp8(const void* x, int ldx, int R, const void* W_e4m3
 // ---- the score head and the row kernels of the passes, one by one (test entry points): every argument is checked here, before any HIP call ----
 // The chain as aigv_launch_score_head splits it: layers with fan-in % 128 == 0 and fan-out % 4 == 0 run on the skinny GEMM, from the first
 // layer that is not such a layer on everything runs in the tail kernel (dims <= 1024 there); the last layer is always a tail layer.
-int aigv_op_score_head(const void* x, int ldx, int B, int n_layers, const int32_t* dims_host, const void* const* w_dev, const void* const* b_dev,
-                       void* scratch, int64_t scratch_bytes, float* score, void* stream) {
-  const char* op = "aigv_op_score_head";
+// (rows: every row the call runs = what the scratch is sized by; B: the rows of one guarded slice)
+static int score_head_op_args(const char* op, const void* x, int ldx, int B, int64_t rows, int n_layers, const int32_t* dims_host, const void* const* w_dev,
+                              const void* const* b_dev, void* scratch, int64_t scratch_bytes, float* score, ScoreHeadArgs* out) {
   if (!x || !dims_host || !w_dev || !b_dev || !scratch || !score) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
   if (B < 1 || B > 64) return fail(nullptr, AIGV_ERR_ARG, "%s: B = %d outside 1..64", op, B);
   if (n_layers < 1 || n_layers > 8) return fail(nullptr, AIGV_ERR_ARG, "%s: n_layers = %d outside 1..8", op, n_layers);
@@ -479,7 +479,7 @@ int aigv_op_score_head(const void* x, int ldx, int B, int n_layers, const int32_
     maxd = dims_host[i] > maxd ? dims_host[i] : maxd;
   }
   if (ldx < dims_host[0]) return fail(nullptr, AIGV_ERR_ARG, "%s: ldx = %d below dims[0] = %d", op, ldx, dims_host[0]);
-  const int64_t need = (int64_t)3 * B * maxd * (int64_t)sizeof(bf16_t);
+  const int64_t need = (int64_t)3 * rows * maxd * (int64_t)sizeof(bf16_t);
   if (scratch_bytes < need) return fail(nullptr, AIGV_ERR_ARG, "%s: scratch of %lld bytes, needs %lld", op, (long long)scratch_bytes, (long long)need);
   int L = 0;
   while (L < n_layers && dims_host[L] % 128 == 0 && dims_host[L + 1] % 4 == 0) ++L;
@@ -488,8 +488,8 @@ int aigv_op_score_head(const void* x, int ldx, int B, int n_layers, const int32_
                 dims_host[n_layers]);
   for (int i = L; i <= n_layers; ++i)
     if (dims_host[i] > 1024) return fail(nullptr, AIGV_ERR_ARG, "%s: tail dim dims[%d] = %d above 1024 (the tail starts at layer %d)", op, i, dims_host[i], L);
-  if (L > 0 && (!aligned16(scratch) || ((int64_t)B * maxd) % 8))
-    return fail(nullptr, AIGV_ERR_ARG, "%s: scratch must be 16-byte aligned and B * max(dims) = %lld a multiple of 8 for the GEMM layers", op, (long long)B * maxd);
+  if (L > 0 && (!aligned16(scratch) || (rows * maxd) % 8))
+    return fail(nullptr, AIGV_ERR_ARG, "%s: scratch must be 16-byte aligned and B * max(dims) = %lld a multiple of 8 for the GEMM layers", op, (long long)rows * maxd);
   ScoreHeadArgs a{};
   a.x = (const bf16_t*)x; a.ldx = ldx; a.B = B; a.n_layers = n_layers; a.score = score;
   for (int i = 0; i <= n_layers; ++i) a.dims[i] = dims_host[i];
@@ -498,7 +498,26 @@ int aigv_op_score_head(const void* x, int ldx, int B, int n_layers, const int32_
     if (i < L && !aligned16(w_dev[i])) return fail(nullptr, AIGV_ERR_ARG, "%s: the weight of GEMM layer %d must be 16-byte aligned", op, i);
     a.w[i] = (const bf16_t*)w_dev[i]; a.b[i] = (const bf16_t*)b_dev[i];
   }
+  *out = a;
+  return 0;
+}
+
+int aigv_op_score_head(const void* x, int ldx, int B, int n_layers, const int32_t* dims_host, const void* const* w_dev, const void* const* b_dev,
+                       void* scratch, int64_t scratch_bytes, float* score, void* stream) {
+  ScoreHeadArgs a{};
+  TRY(score_head_op_args("aigv_op_score_head", x, ldx, B, B, n_layers, dims_host, w_dev, b_dev, scratch, scratch_bytes, score, &a));
   HIPCHK(nullptr, aigv_launch_score_head(a, (bf16_t*)scratch, (hipStream_t)stream));
+  return 0;
+}
+
+int aigv_op_score_head_groups(const void* x, int ldx, int G, int64_t group_stride, int B, int n_layers, const int32_t* dims_host,
+                              const void* const* w_dev, const void* const* b_dev, void* scratch, int64_t scratch_bytes, float* score, void* stream) {
+  const char* op = "aigv_op_score_head_groups";
+  if (G < 1 || (B >= 1 && (int64_t)G * B > 4096)) return fail(nullptr, AIGV_ERR_ARG, "%s: G = %d groups of B = %d rows: needs G >= 1 and G * B <= 4096", op, G, B);
+  if (group_stride < 0) return fail(nullptr, AIGV_ERR_ARG, "%s: group_stride = %lld must not be negative", op, (long long)group_stride);
+  ScoreHeadArgs a{};
+  TRY(score_head_op_args(op, x, ldx, B, (int64_t)G * std::max(B, 1), n_layers, dims_host, w_dev, b_dev, scratch, scratch_bytes, score, &a));
+  HIPCHK(nullptr, aigv_launch_score_head_groups(a, G, (size_t)group_stride, (bf16_t*)scratch, (hipStream_t)stream));
   return 0;
 }
 
@@ -567,6 +586,17 @@ static int check_rows(const char* op, const void* a, const void* b, const void* 
 int aigv_op_gather_rows(const void* src, int ld, const int32_t* idx, int n, void* dst, int H, void* stream) {
   TRY(check_rows("aigv_op_gather_rows", src, dst, idx, true, n, H, ld));
   HIPCHK(nullptr, aigv_launch_gather_rows((const bf16_t*)src, ld, idx, n, (bf16_t*)dst, H, (hipStream_t)stream));
+  return 0;
+}
+
+// raw[i, :H] = src[idx[i] * ld ..] and normed[i, :H] = RMSNorm of that row under w, for i < n (raw and normed are dense): the depth lens' tap
+int aigv_op_lens_tap(const void* src, int ld, const int32_t* idx, int n, const void* w, void* raw, void* normed, int H, float eps, void* stream) {
+  const char* op = "aigv_op_lens_tap";
+  TRY(check_rows(op, src, raw, idx, true, n, H, ld));
+  if (!w || !normed) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+  if (H > 16384) return fail(nullptr, AIGV_ERR_ARG, "%s: H = %d above 16384", op, H);
+  if (!aligned16(w) || !aligned16(normed)) return fail(nullptr, AIGV_ERR_ARG, "%s: the row buffers must be 16-byte aligned", op);
+  HIPCHK(nullptr, aigv_launch_lens_tap((const bf16_t*)src, ld, idx, n, (const bf16_t*)w, (bf16_t*)raw, (bf16_t*)normed, H, eps, (hipStream_t)stream));
   return 0;
 }
 

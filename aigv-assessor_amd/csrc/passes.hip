@@ -274,6 +274,7 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
   if (!c || !ids || !slot || !cu) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: null argument");
   const bool probing = c->probe.armed;   // aigv_score_attention_arm: this pass carries the probe, and disarms on every way out
   const bool dropping = c->drop.armed;   // aigv_key_drop_arm / _ex: the attention of the armed layers of this pass runs under the mask; disarmed likewise
+  const bool lensing = c->lens.armed;    // aigv_depth_lens_arm: this pass taps the lens rows after the embedding and after every layer; disarmed likewise
   DisarmScope disarm(c);
   if (!c->finalized) return fail(c, AIGV_ERR_STATE, "aigv_llm_prefill: call aigv_finalize_weights first");
   if (dropping && probing) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: a key-drop mask and the score-attention probe are both armed: the probe does not know the mask");
@@ -301,6 +302,21 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
   if (dropping && (!c->drop.words || c->drop.ld < (max_len + 63) / 64))
     return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: key-drop mask armed with %d words per clip, the longest clip (%d tokens) needs %d", c->drop.ld, max_len,
                 (max_len + 63) / 64);
+  // the depth lens: every lens row must be a consumed row [score rows | logit rows] - the last layer finishes only those; lens_at: its place among them
+  const int n_lens = lensing ? c->lens.n_score + c->lens.n_token : 0;
+  int32_t lens_at[2 * AIGV_MAX_LENS_ROWS];
+  if (lensing) {
+    const int nS = score ? B : 0;
+    if (nS + R == 0) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: the depth lens is armed and the pass has no output rows (n_out == 0): nothing finishes the last layer");
+    if (c->lens.n_score > 0 && !score) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: the depth lens is armed with %d score rows and the pass has score == NULL (no score head runs)", c->lens.n_score);
+    for (int i = 0; i < n_lens; ++i) {
+      int at = -1;
+      for (int j = 0; j < nS && at < 0; ++j) if (score_rows[j] == c->lens.rows[i]) at = j;
+      for (int j = 0; j < R && at < 0; ++j) if (logit_rows[j] == c->lens.rows[i]) at = nS + j;
+      if (at < 0) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: depth-lens row %d (packed row %d) is not among the pass's consumed rows (its score rows and logit rows): the last layer finishes only those", i, c->lens.rows[i]);
+      lens_at[i] = at;
+    }
+  }
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)stream;
   const int H = k.llm_hidden, I = k.llm_inter, D = c->head_dim, g = c->g, nkv = k.llm_kv_heads;
@@ -314,6 +330,18 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
 
   HIPCHK(c, aigv_launch_embed(ids, slot, c->tok_emb, (const bf16_t*)vis, (const bf16_t*)motion, n_vis, c->l_h, T, H, s));
   TRY(upload_out_rows(c, score_rows, score != nullptr, B, logit_rows, R, T, s));
+  // depth d of the lens: rows idx[0 .. n_lens) of src -> slice d of the caller's two buffers, one launch
+  const int32_t* lens_idx = c->l_lensidx;
+  auto lens_tap = [&](int depth, const bf16_t* src, const int32_t* idx) -> int {
+    const size_t off = (size_t)depth * n_lens * H;
+    HIPCHK(c, aigv_launch_lens_tap(src, H, idx, n_lens, c->final_norm, c->lens.hidden + off, c->lens.normed + off, H, k.rms_eps, s));
+    return 0;
+  };
+  if (lensing) {
+    HIPCHK(c, aigv_launch_write_ints(c->lens.rows, n_lens, c->l_lensidx, s));
+    HIPCHK(c, aigv_launch_write_ints(lens_at, n_lens, c->l_lensidx + 2 * AIGV_MAX_LENS_ROWS, s));
+    TRY(lens_tap(0, c->l_h, lens_idx));
+  }
   // Row trimming: after the last layer's attention every row is independent, and only the consumed rows (one score row per
   // clip + the answer rows) are read afterwards (stage2_eval.py:940-941; modeling_internvl_chat.py:469-481).  When they are
   // few, the last layer finishes just those rows: attention for the query blocks that contain them, then wo / MLP on a
@@ -386,16 +414,29 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
         TRY(run_skinny(c, t_ffn, I, nr, L.w2, I, H, I, nullptr, h, H, h, H, SK_RESID, s, 0));
       }
       if (trim) {
+        if (lensing) TRY(lens_tap(k.llm_layers, t_h, lens_idx + 2 * AIGV_MAX_LENS_ROWS));          // depth L: the finished rows, in l_rowidx order
         TRY(final_rows(c, score, B, R, argmax, t_h, true, s));
         break;
       }
       TRY(llm_layer_post(c, li, T, s));                                                          // every row on the tile kernels ...
       HIPCHK(c, aigv_launch_scatter_rows(t_h, c->l_rowidx2, n_fin, c->l_h, H, H, s));            // ... the small clips' consumed rows put back
+      if (lensing) TRY(lens_tap(k.llm_layers, c->l_h, lens_idx));
       break;
     }
     TRY(llm_layer_post(c, li, T, s));
+    if (lensing) TRY(lens_tap(li + 1, c->l_h, lens_idx));
   }
   if (!trim) TRY(final_rows(c, score, B, R, argmax, c->l_h, false, s));
+  if (lensing && c->lens.n_score > 0) {
+    // the score head on the score rows of every depth: each depth a batch slice with a NaN guard of its own, as many depths per call as the
+    // head's workspace (64 rows) holds
+    const int nS = c->lens.n_score, per = std::max(1, 64 / nS);
+    for (int d0 = 0; d0 <= k.llm_layers; d0 += per) {
+      ScoreHeadArgs a = c->score;
+      a.x = c->lens.normed + (size_t)d0 * n_lens * H; a.ldx = H; a.B = nS; a.score = c->lens.score + (size_t)d0 * nS;
+      HIPCHK(c, aigv_launch_score_head_groups(a, std::min(per, k.llm_layers + 1 - d0), (size_t)n_lens * H, c->l_score_ws, s));
+    }
+  }
   if (keep_kv) {
     c->h_kvlen.resize(B);
     for (int b = 0; b < B; ++b) c->h_kvlen[b] = cu[b + 1] - cu[b];
@@ -436,6 +477,26 @@ int aigv_key_drop_arm_ex(aigv_ctx* c, const uint64_t* words_dev, const uint64_t*
   return key_drop_arm("aigv_key_drop_arm_ex", c, words_dev, row_words_dev, ld_words, layer_begin, layer_end);
 }
 
+// Arms the next aigv_llm_prefill with the depth lens (include/aigv_amd.h): the row lists are copied here, the buffers are written when that pass runs.
+int aigv_depth_lens_arm(aigv_ctx* c, const int32_t* score_rows_host, int n_score, const int32_t* token_rows_host, int n_token, void* hidden_out_bf16,
+                        void* normed_out_bf16, float* score_out) {
+  const char* op = "aigv_depth_lens_arm";
+  if (!c) return fail(c, AIGV_ERR_ARG, "%s: null context", op);
+  if (n_score < 0 || n_score > AIGV_MAX_LENS_ROWS || n_token < 0 || n_token > AIGV_MAX_LENS_ROWS)
+    return fail(c, AIGV_ERR_ARG, "%s: %d score rows and %d token rows: each list holds 0..%d rows", op, n_score, n_token, AIGV_MAX_LENS_ROWS);
+  if (n_score + n_token == 0) return fail(c, AIGV_ERR_ARG, "%s: no row to read (n_score = n_token = 0)", op);
+  if ((n_score > 0 && !score_rows_host) || (n_token > 0 && !token_rows_host)) return fail(c, AIGV_ERR_ARG, "%s: null row list", op);
+  if (!hidden_out_bf16 || ((uintptr_t)hidden_out_bf16 & 15)) return fail(c, AIGV_ERR_ARG, "%s: hidden_out_bf16 is null or not 16-byte aligned", op);
+  if (!normed_out_bf16 || ((uintptr_t)normed_out_bf16 & 15)) return fail(c, AIGV_ERR_ARG, "%s: normed_out_bf16 is null or not 16-byte aligned", op);
+  if (n_score > 0 && (!score_out || ((uintptr_t)score_out & 3))) return fail(c, AIGV_ERR_ARG, "%s: score_out is null or not 4-byte aligned", op);
+  for (int i = 0; i < n_score; ++i) c->lens.rows[i] = score_rows_host[i];
+  for (int i = 0; i < n_token; ++i) c->lens.rows[n_score + i] = token_rows_host[i];
+  c->lens.n_score = n_score; c->lens.n_token = n_token;
+  c->lens.hidden = (bf16_t*)hidden_out_bf16; c->lens.normed = (bf16_t*)normed_out_bf16; c->lens.score = score_out;
+  c->lens.armed = true;
+  return 0;
+}
+
 // Continue the sequences kept by aigv_llm_prefill(keep_kv = 1) with new TEXT tokens: causal attention of the new rows over the
 // cached keys plus themselves.  commit = 0 leaves the cache lengths where they were, so several continuations of ONE prefix
 // (the four quality-perspective questions behind the same video tokens) can be scored one after the other.
@@ -444,7 +505,9 @@ int aigv_llm_extend(aigv_ctx* c, const int64_t* ids, const int32_t* cu, int B, c
   if (!c || !ids || !cu) return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: null argument");
   const bool probing = c->probe.armed;
   const bool dropping = c->drop.armed;
+  const bool lensing = c->lens.armed;
   DisarmScope disarm(c);
+  if (lensing) return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: the depth lens is armed (aigv_depth_lens_arm): the continuation pass takes no lens, only aigv_llm_prefill does");
   if (dropping) return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: a key-drop mask is armed (aigv_key_drop_arm): the continuation pass takes no mask, only aigv_llm_prefill does");
   if (!c->kv_valid) return fail(c, AIGV_ERR_STATE, "aigv_llm_extend: no KV state (run aigv_llm_prefill with keep_kv)");
   if (probing && c->kv_masked) return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: the score-attention probe is armed and the KV cache carries a key-drop mask: the probe does not know the mask");
@@ -784,50 +847,70 @@ int aigv_out_row_logits(aigv_ctx* c, int first_row, int n_rows, void* logits_bf1
   return 0;
 }
 
-// The loop of aigv_out_row_logprob (labels, one per row), aigv_out_row_cand_logprob (labels == nullptr: C candidates for every row) and
-// aigv_out_row_topk_logprob (top_ids != nullptr: the k = C largest logits of every row, their log-probabilities into out):
-// consumed rows in chunks of 64, the lm-head logits of a chunk into c->l_lp in the 4-slice form of every row count (a row's logits do
-// not depend on its chunk), then the row kernel of logprob.hip reads them.
-static int out_row_logprobs(aigv_ctx* c, int first_row, int n_rows, const int64_t* labels, const int64_t* cand, int C, float* out, hipStream_t s,
-                            int64_t* top_ids = nullptr) {
+// The loop of aigv_out_row_logprob (label_out: labels, one per row), aigv_out_row_cand_logprob (cand_out: C candidates for every row),
+// aigv_out_row_topk_logprob (top_out: the k largest logits of every row, their ids into top_ids) and aigv_depth_lens_token_readout (top-1
+// and candidates from one fill): n_rows normed rows at `rows` (leading dimension ld) in chunks of 64, the lm-head logits of a chunk into
+// c->l_lp in the 4-slice form of every row count (a row's logits do not depend on its chunk), then the row kernels of logprob.hip read them.
+static int row_logprobs(aigv_ctx* c, const bf16_t* rows, int ld, int n_rows, const int64_t* labels, float* label_out, const int64_t* cand, int C,
+                        float* cand_out, int k_top, int64_t* top_ids, float* top_out, hipStream_t s) {
   const aigv_config& k = c->cfg;
   for (int r0 = 0; r0 < n_rows; r0 += 64) {
     const int rr = std::min(64, n_rows - r0);
     {
       ProfScope ps(c, AIGV_PROF_SKINNY, 2.0 * rr * (double)k.vocab * k.llm_hidden, 2.0 * (double)k.vocab * k.llm_hidden, s);
-      hipError_t e = aigv_launch_lm_head_logits(c->l_rows + (size_t)(first_row + r0) * k.llm_hidden, rr, k.llm_hidden, c->lm_head, k.vocab,
-                                                c->l_lp, c->lp_ldo, s, /*one_form=*/true);
+      hipError_t e = aigv_launch_lm_head_logits(rows + (size_t)r0 * ld, rr, k.llm_hidden, c->lm_head, k.vocab, c->l_lp, c->lp_ldo, s, /*one_form=*/true, ld);
       if (e != hipSuccess) return fail(c, e == hipErrorInvalidValue ? AIGV_ERR_ARG : AIGV_ERR_HIP, "lm-head logits (rows=%d ldo=%d): %s", rr, c->lp_ldo, hipGetErrorString(e));
     }
-    const hipError_t e = top_ids ? aigv_launch_topk_logprob(c->l_lp, rr, k.vocab, c->lp_ldo, C, top_ids + (size_t)r0 * C, out + (size_t)r0 * C, s)
-                         : labels ? aigv_launch_label_logprob(c->l_lp, rr, k.vocab, c->lp_ldo, labels + r0, out + r0, s)
-                                : aigv_launch_cand_logprob(c->l_lp, rr, k.vocab, c->lp_ldo, cand, C, out + (size_t)r0 * C, s);
-    if (e == hipSuccess) continue;
-    const int code = e == hipErrorInvalidValue ? AIGV_ERR_ARG : AIGV_ERR_HIP;
-    if (top_ids) return fail(c, code, "top-k log-probabilities (rows=%d, k=%d): %s", rr, C, hipGetErrorString(e));
-    if (labels) return fail(c, code, "label log-probabilities (rows=%d): %s", rr, hipGetErrorString(e));
-    return fail(c, code, "candidate log-probabilities (rows=%d, C=%d): %s", rr, C, hipGetErrorString(e));
+    if (top_out) {
+      const hipError_t e = aigv_launch_topk_logprob(c->l_lp, rr, k.vocab, c->lp_ldo, k_top, top_ids + (size_t)r0 * k_top, top_out + (size_t)r0 * k_top, s);
+      if (e != hipSuccess) return fail(c, e == hipErrorInvalidValue ? AIGV_ERR_ARG : AIGV_ERR_HIP, "top-k log-probabilities (rows=%d, k=%d): %s", rr, k_top, hipGetErrorString(e));
+    }
+    if (label_out) {
+      const hipError_t e = aigv_launch_label_logprob(c->l_lp, rr, k.vocab, c->lp_ldo, labels + r0, label_out + r0, s);
+      if (e != hipSuccess) return fail(c, e == hipErrorInvalidValue ? AIGV_ERR_ARG : AIGV_ERR_HIP, "label log-probabilities (rows=%d): %s", rr, hipGetErrorString(e));
+    }
+    if (cand_out) {
+      const hipError_t e = aigv_launch_cand_logprob(c->l_lp, rr, k.vocab, c->lp_ldo, cand, C, cand_out + (size_t)r0 * C, s);
+      if (e != hipSuccess) return fail(c, e == hipErrorInvalidValue ? AIGV_ERR_ARG : AIGV_ERR_HIP, "candidate log-probabilities (rows=%d, C=%d): %s", rr, C, hipGetErrorString(e));
+    }
   }
   return 0;
 }
 
 int aigv_out_row_logprob(aigv_ctx* c, int first_row, int n_rows, const int64_t* labels, float* logprob, void* stream) {
   TRY(out_rows_begin(c, "aigv_out_row_logprob", labels && logprob, first_row, n_rows));
-  return out_row_logprobs(c, first_row, n_rows, labels, nullptr, 1, logprob, (hipStream_t)stream);
+  return row_logprobs(c, c->l_rows + (size_t)first_row * c->cfg.llm_hidden, c->cfg.llm_hidden, n_rows, labels, logprob, nullptr, 0, nullptr, 0, nullptr, nullptr, (hipStream_t)stream);
 }
 
 int aigv_out_row_cand_logprob(aigv_ctx* c, int first_row, int n_rows, const int64_t* cand_ids, int C, float* cand_logprob, void* stream) {
   const char* op = "aigv_out_row_cand_logprob";
   if (C < 1 || C > AIGV_MAX_CANDIDATES) return fail(c, AIGV_ERR_ARG, "%s: C = %d candidates outside 1..%d", op, C, AIGV_MAX_CANDIDATES);
   TRY(out_rows_begin(c, op, cand_ids && cand_logprob, first_row, n_rows));
-  return out_row_logprobs(c, first_row, n_rows, nullptr, cand_ids, C, cand_logprob, (hipStream_t)stream);
+  return row_logprobs(c, c->l_rows + (size_t)first_row * c->cfg.llm_hidden, c->cfg.llm_hidden, n_rows, nullptr, nullptr, cand_ids, C, cand_logprob, 0, nullptr, nullptr, (hipStream_t)stream);
 }
 
 int aigv_out_row_topk_logprob(aigv_ctx* c, int first_row, int n_rows, int k, int64_t* top_ids, float* top_logprob, void* stream) {
   const char* op = "aigv_out_row_topk_logprob";
   if (k < 1 || k > AIGV_MAX_TOPK || (c && k > c->cfg.vocab)) return fail(c, AIGV_ERR_ARG, "%s: k = %d outside 1..min(%d, vocab)", op, k, AIGV_MAX_TOPK);
   TRY(out_rows_begin(c, op, top_ids && top_logprob, first_row, n_rows));
-  return out_row_logprobs(c, first_row, n_rows, nullptr, nullptr, k, top_logprob, (hipStream_t)stream, top_ids);
+  return row_logprobs(c, c->l_rows + (size_t)first_row * c->cfg.llm_hidden, c->cfg.llm_hidden, n_rows, nullptr, nullptr, nullptr, 0, nullptr, k, top_ids, top_logprob, (hipStream_t)stream);
+}
+
+// the depth lens' lm-head read-out (include/aigv_amd.h): the caller's normed rows instead of the consumed-row buffer, top-1 and candidates from one fill
+int aigv_depth_lens_token_readout(aigv_ctx* c, const void* normed_rows_dev, int ld, int n_rows, const int64_t* cand_ids, int C, int64_t* top_id,
+                                  float* top_logprob, float* cand_logprob, void* stream) {
+  const char* op = "aigv_depth_lens_token_readout";
+  if (!c || !normed_rows_dev || !top_id || !top_logprob) return fail(c, AIGV_ERR_ARG, "%s: null argument", op);
+  if (!c->finalized) return fail(c, AIGV_ERR_STATE, "%s: call aigv_finalize_weights first", op);
+  if (n_rows < 1) return fail(c, AIGV_ERR_ARG, "%s: n_rows = %d must be positive", op, n_rows);
+  if (ld < c->cfg.llm_hidden || ld % 8 || ((uintptr_t)normed_rows_dev & 15))
+    return fail(c, AIGV_ERR_ARG, "%s: the rows must be 16-byte aligned with a leading dimension (%d) that is a multiple of 8 and >= %d", op, ld, c->cfg.llm_hidden);
+  if (cand_ids || cand_logprob || C) {
+    if (C < 1 || C > AIGV_MAX_CANDIDATES) return fail(c, AIGV_ERR_ARG, "%s: C = %d candidates outside 1..%d", op, C, AIGV_MAX_CANDIDATES);
+    if (!cand_ids || !cand_logprob) return fail(c, AIGV_ERR_ARG, "%s: null argument (cand_ids and cand_logprob go together)", op);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  return row_logprobs(c, (const bf16_t*)normed_rows_dev, ld, n_rows, nullptr, nullptr, cand_ids, C, cand_logprob, 1, top_id, top_logprob, (hipStream_t)stream);
 }
 
 int aigv_out_row_hidden(aigv_ctx* c, int first_row, int n_rows, void* hidden_bf16, int ldo, void* stream) {

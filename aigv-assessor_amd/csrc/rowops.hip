@@ -89,37 +89,55 @@ __global__ __launch_bounds__(256) void layernorm_wave_kernel(const bf16_t* __res
 }
 
 // ---- RMSNorm: fp32 normalise -> bf16 -> * weight -> bf16 (modeling_internlm2.py:138-143) --------------
+// The kernel's text, written once for rmsnorm_kernel and lens_tap_kernel: row SROW of X (leading dimension LDX) -> row ROW of Y, by one
+// 256-thread workgroup; KEEP_RAW(ch, raw): what else happens to a 16-byte chunk as it is loaded.  (A macro, not a function: through an inlined
+// function hipcc allocates rmsnorm_kernel's registers differently - the kernel's device assembly is pinned, profiles/depth_lens_kernel_resources.txt.)
+#define AIGV_RMSNORM_ROW(X, LDX, SROW, W, Y, LDY, ROW, H, EPS, KEEP_RAW)                          \
+  __shared__ float red[4];                                                                        \
+  const int nchunk = (H) >> 3;                                                                    \
+  float v[MAXC][8];                                                                               \
+  float sq = 0.f;                                                                                 \
+  _Pragma("unroll") for (int c = 0; c < MAXC; ++c) {                                              \
+    const int ch = threadIdx.x + c * 256;                                                         \
+    if (ch < nchunk) {                                                                            \
+      const u16x8 raw = *(const u16x8*)((X) + (size_t)(SROW) * (LDX) + (ch << 3));                \
+      KEEP_RAW(ch, raw);                                                                          \
+      _Pragma("unroll") for (int e = 0; e < 8; ++e) { v[c][e] = bf2f(raw[e]); sq += v[c][e] * v[c][e]; } \
+    }                                                                                             \
+  }                                                                                               \
+  const float rstd = rsqrtf(block_sum_256(sq, red) / (float)(H) + (EPS));                         \
+  _Pragma("unroll") for (int c = 0; c < MAXC; ++c) {                                              \
+    const int ch = threadIdx.x + c * 256;                                                         \
+    if (ch < nchunk) {                                                                            \
+      const u16x8 ww = *(const u16x8*)((W) + (ch << 3));                                          \
+      u16x8 o;                                                                                    \
+      _Pragma("unroll") for (int e = 0; e < 8; ++e) o[e] = f2bf(bf2f(ww[e]) * rbf(v[c][e] * rstd)); \
+      *(u16x8*)((Y) + (size_t)(ROW) * (LDY) + (ch << 3)) = o;                                     \
+    }                                                                                             \
+  }
+#define AIGV_RMSNORM_NO_RAW(ch, raw) (void)0
+
 __global__ __launch_bounds__(256) void rmsnorm_kernel(const bf16_t* __restrict__ x, int ldx,
                                                       const bf16_t* __restrict__ w, bf16_t* __restrict__ y, int ldy,
                                                       int H, float eps, const int32_t* __restrict__ row_idx) {
-  __shared__ float red[4];
   const int row = blockIdx.x;
   const int srow = row_idx ? row_idx[row] : row;
-  const int nchunk = H >> 3;
-  float v[MAXC][8];
-  float sq = 0.f;
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c) {
-    const int ch = threadIdx.x + c * 256;
-    if (ch < nchunk) {
-      const u16x8 raw = *(const u16x8*)(x + (size_t)srow * ldx + (ch << 3));
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { v[c][e] = bf2f(raw[e]); sq += v[c][e] * v[c][e]; }
-    }
-  }
-  const float rstd = rsqrtf(block_sum_256(sq, red) / (float)H + eps);
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c) {
-    const int ch = threadIdx.x + c * 256;
-    if (ch < nchunk) {
-      const u16x8 ww = *(const u16x8*)(w + (ch << 3));
-      u16x8 o;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = f2bf(bf2f(ww[e]) * rbf(v[c][e] * rstd));
-      *(u16x8*)(y + (size_t)row * ldy + (ch << 3)) = o;
-    }
-  }
+  AIGV_RMSNORM_ROW(x, ldx, srow, w, y, ldy, row, H, eps, AIGV_RMSNORM_NO_RAW)
 }
+
+// The depth lens' tap (aigv_depth_lens_arm): row idx[i] of the residual stream -> raw[i] as it is and normed[i] = the final RMSNorm of it, both
+// dense [n, H].  The statistics and the scale are rmsnorm_kernel's text, so normed holds the bits aigv_launch_rmsnorm gives with idx as its row index.
+__global__ __launch_bounds__(256) void lens_tap_kernel(const bf16_t* __restrict__ src, int ld, const int32_t* __restrict__ idx,
+                                                       const bf16_t* __restrict__ w, bf16_t* __restrict__ raw_out, bf16_t* __restrict__ normed,
+                                                       int H, float eps) {
+  const int row = blockIdx.x;
+  const int srow = idx[row];
+#define AIGV_LENS_KEEP_RAW(ch, raw) *(u16x8*)(raw_out + (size_t)row * H + (ch << 3)) = raw
+  AIGV_RMSNORM_ROW(src, ld, srow, w, normed, H, row, H, eps, AIGV_LENS_KEEP_RAW)
+#undef AIGV_LENS_KEEP_RAW
+}
+#undef AIGV_RMSNORM_ROW
+#undef AIGV_RMSNORM_NO_RAW
 
 // RMSNorm fused with the fp8 row quantisation of its result (fp8 mode of the InternLM2 linears): the bf16 value the plain kernel
 // would store is quantised from registers - bit-identical to rmsnorm_kernel followed by quant_fp8_rows_kernel, one pass instead of two.
@@ -481,6 +499,14 @@ hipError_t aigv_launch_rmsnorm(const bf16_t* x, int ldx, const bf16_t* w, bf16_t
   if (rows <= 0) return hipSuccess;
   if (H % 8 || H > MAXC * 256 * 8) return hipErrorInvalidValue;
   hipLaunchKernelGGL(rmsnorm_kernel, dim3(rows), dim3(256), 0, s, x, ldx, w, y, ldy, H, eps, row_idx);
+  return hipGetLastError();
+}
+
+hipError_t aigv_launch_lens_tap(const bf16_t* src, int ld, const int32_t* idx, int n, const bf16_t* w, bf16_t* raw, bf16_t* normed, int H, float eps,
+                                hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (H % 8 || H > MAXC * 256 * 8 || ld % 8 || ld < H || !src || !idx || !w || !raw || !normed) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(lens_tap_kernel, dim3(n), dim3(256), 0, s, src, ld, idx, w, raw, normed, H, eps);
   return hipGetLastError();
 }
 

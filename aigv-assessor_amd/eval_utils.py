@@ -171,6 +171,25 @@ def frame_heatmaps(tok_att, positions, layers=None):
     return (mass / mass.sum(-1, keepdim=True)).view(B, F, g, g).to(tok_att.dtype)
 
 
+def settling_depth(lens_score, tol: float):
+    """AT WHICH DEPTH the score exists: ``lens_score`` is ``forward(return_depth_lens=True)``'s [B, L + 1] (the score head on the score row after
+    d layers, column L the pass's own score); returns int64 [B] - the smallest depth d such that EVERY depth d' >= d has ``|lens_score[:, d'] -
+    lens_score[:, L]| <= tol``, L where only the last depth qualifies.  A NaN never qualifies (a NaN final score: L).  Host-side arithmetic on
+    whatever device the tensor lives on; ``tol`` >= 0."""
+    import torch
+    if lens_score.dim() != 2 or lens_score.shape[1] < 1:
+        raise ValueError(f"settling_depth: expected [B, L + 1], got {tuple(lens_score.shape)}")
+    if not tol >= 0:
+        raise ValueError(f"settling_depth: tol = {tol!r} must be >= 0")
+    s = lens_score.double()
+    L = s.shape[1] - 1
+    ok = (s - s[:, L:]).abs() <= tol                                   # (NaN compares False)
+    ok[:, L] = True                                                    # the last depth stands for itself
+    # the length of the run of qualifying depths that ends at L: every d' >= d qualifies iff no failure at or behind d
+    settled = torch.flip(torch.cumprod(torch.flip(ok.long(), (1,)), 1), (1,))
+    return (L + 1 - settled.sum(1)).to(torch.long)
+
+
 def frame_ablation(model, *, pixel_values, input_ids, attention_mask, image_flags, labels=None, motion_feature=None, **readout_kwargs):
     """WHAT IF a frame were not there: the batch scored once as it is and once per unit with that unit's tokens hidden from the LLM
     (``forward(key_drop=model.unit_masks(...)[:, u])``) - unit u < F is frame u's visual tokens, unit F the motion token.  Positions, the

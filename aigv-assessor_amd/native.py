@@ -133,6 +133,8 @@ PROTOTYPES = {
     "aigv_op_attention_drop": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, C.c_int64, _P, _I, _I, _F, _F, _P, _P, _P, _I, _I, _P, _I, _P]),
     "aigv_key_drop_arm": (_I, [_P, _P, _I]),
     "aigv_key_drop_arm_ex": (_I, [_P, _P, _P, _I, _I, _I]),
+    "aigv_depth_lens_arm": (_I, [_P, _I32P, _I, _I32P, _I, _P, _P, _P]),
+    "aigv_depth_lens_token_readout": (_I, [_P, _P, _I, _I, _P, _I, _P, _P, _P, _P]),
     "aigv_op_attention_drop_rows": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, C.c_int64, _P, _I, _I, _F, _F, _P, _P, _P, _I, _I, _P, _P, _I, _P]),
     "aigv_op_kv_store": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "aigv_op_attention_probe": (_I, [_P, _I, _P, _I, _I32P, _I, _I, _I, _I, _I, C.c_int64, _I32P, _I, _P, _P, _I, _I32P, _I, _P, _P, _I, _I, _P, _P]),
@@ -156,6 +158,8 @@ PROTOTYPES = {
     "aigv_op_skinny_swiglu_normed": (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _I, _P, _F, _I, _P]),
     "aigv_op_skinny_rope_kv_fp8": (_I, [_P, _I, _I, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _F, _I, _P]),
     "aigv_op_score_head": (_I, [_P, _I, _I, _I, _I32P, C.POINTER(_P), C.POINTER(_P), _P, C.c_int64, _P, _P]),
+    "aigv_op_score_head_groups": (_I, [_P, _I, _I, C.c_int64, _I, _I, _I32P, C.POINTER(_P), C.POINTER(_P), _P, C.c_int64, _P, _P]),
+    "aigv_op_lens_tap": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _F, _P]),
     "aigv_op_rmsnorm_quant_fp8": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _F, _P]),
     "aigv_op_rope_slots": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "aigv_op_embed": (_I, [_P, _P, _P, _P, _P, _I, _P, _I, _I, _P]),

@@ -1,5 +1,5 @@
-"""Which read-outs a scoring pass carries: label log-probs, candidate log-probs, top-k log-probs, score attention by segment and per token -
-and whether it runs under a key-drop mask (``key_drop`` with its qualifiers ``key_drop_rows`` / ``key_drop_layers``: not a read-out, but a
+"""Which read-outs a scoring pass carries: label log-probs, candidate log-probs, top-k log-probs, score attention by segment and per token, the
+depth lens - and whether it runs under a key-drop mask (``key_drop`` with its qualifiers ``key_drop_rows`` / ``key_drop_layers``: not a read-out, but a
 per-call option that travels the same way).
 
 This module is the one place that knows that decision.  A new read-out adds, HERE: a member to ``ReadOuts`` and its check to
@@ -17,6 +17,7 @@ import torch
 
 MAX_CANDIDATES = 64      # = AIGV_MAX_CANDIDATES
 MAX_TOPK = 16            # = AIGV_MAX_TOPK
+MAX_LENS_ROWS = 64       # = AIGV_MAX_LENS_ROWS
 
 
 def top_logprobs_k(top_logprobs, vocab: int, labels="given") -> int:
@@ -124,11 +125,12 @@ class ReadOuts:
     key_drop: Optional[torch.Tensor] = None     # host bool [B, N]: tokens hidden, as keys, from every row of their clip (forward; generate* check theirs with key_drop_mask)
     key_drop_rows: Optional[torch.Tensor] = None    # host bool [B, N]: ... from these query rows only (None: every row)
     key_drop_layers: Optional[tuple] = None         # (lo, hi): ... in the layers lo <= l < hi only (None: every layer)
+    depth_lens: bool = False                    # return_depth_lens: the score row and the token row after every layer (forward only)
 
     @classmethod
     def parse(cls, vocab: int, labels="given", return_logprobs: bool = False, candidate_ids=None, top_logprobs: Optional[int] = None,
               return_score_attention: bool = False, attention_segments=None, return_token_attention: bool = False, key_drop=None,
-              ids_shape=None, key_drop_rows=None, key_drop_layers=None, n_layers: Optional[int] = None) -> "ReadOuts":
+              ids_shape=None, key_drop_rows=None, key_drop_layers=None, n_layers: Optional[int] = None, return_depth_lens: bool = False) -> "ReadOuts":
         """The record of a call's public keyword arguments, checked.  ``labels=None`` (``forward`` without labels) refuses candidates and top-k;
         the shared-prefix and generate entry points leave the default.  A user segment table is checked where its bins are counted
         (``n_segments``: it needs the shape of ``input_ids``)."""
@@ -136,8 +138,10 @@ class ReadOuts:
         k = top_logprobs_k(top_logprobs, vocab, labels)
         att = bool(return_score_attention or return_token_attention)
         rows, window = key_drop_qualifiers(key_drop, key_drop_rows, key_drop_layers, ids_shape, n_layers)
+        if return_depth_lens and ids_shape is not None and int(ids_shape[0]) > MAX_LENS_ROWS:
+            raise ValueError(f"return_depth_lens: at most {MAX_LENS_ROWS} clips per pass, got {int(ids_shape[0])}")
         return cls(bool(return_logprobs), cand, k or None, att, attention_segments if att else None, bool(return_token_attention),
-                   key_drop_mask(key_drop, ids_shape, att), rows, window)
+                   key_drop_mask(key_drop, ids_shape, att), rows, window, bool(return_depth_lens))
 
     @property
     def wants_labels(self) -> bool:
@@ -161,7 +165,8 @@ class ReadOuts:
         table follows from the ids, which are in the key) and ld_tok = N are output shapes: another value is another graph."""
         S = (self.n_segments(ids_shape) if n_seg is None else n_seg) if self.score_attention else 0
         on = ((self.logprobs, "logprobs"), (self.cand is not None, "candidates"), (self.topk is not None, ("top_logprobs", self.topk)),
-              (self.score_attention, ("score_attention", S)), (self.token_attention, ("score_attention_tokens", int(ids_shape[1]))))
+              (self.score_attention, ("score_attention", S)), (self.token_attention, ("score_attention_tokens", int(ids_shape[1]))),
+              (self.depth_lens, "depth_lens"))
         return tuple(element for yes, element in on if yes)
 
     def row_fields(self):
@@ -177,7 +182,7 @@ def forward_kwargs(r: ReadOuts) -> dict:
     ``forward``'s call form, which need not know the options it is not asked for."""
     kw = dict(return_logprobs=r.logprobs or None, candidate_ids=r.cand, top_logprobs=r.topk, return_score_attention=r.score_attention or None,
               attention_segments=r.segments, return_token_attention=r.token_attention or None, key_drop=r.key_drop,
-              key_drop_rows=r.key_drop_rows, key_drop_layers=r.key_drop_layers)
+              key_drop_rows=r.key_drop_rows, key_drop_layers=r.key_drop_layers, return_depth_lens=r.depth_lens or None)
     return {k: v for k, v in kw.items() if v is not None}
 
 

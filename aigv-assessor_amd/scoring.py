@@ -183,7 +183,7 @@ class ScoringPass:
         return pinned.to(self.device, non_blocking=True)
 
     def _prefill(self, ids_packed, slot, cu, vis, n_vis, motion, score_rows, logit_rows, keep_kv=False, kv_cap=0, probe=None, ld_tok=0, drop_words=None,
-                 drop_row_words=None, drop_layers=None):
+                 drop_row_words=None, drop_layers=None, lens=None):
         b = len(cu) - 1
         T = cu[-1]
         lib, ctx = self._native(n_tokens=T, n_clips=b, out_rows=len(logit_rows), kv_cap=kv_cap)
@@ -206,6 +206,10 @@ class ScoringPass:
                 rows_d = up(drop_row_words, torch.int64) if drop_row_words is not None else None
                 lo, hi = drop_layers if drop_layers is not None else (0, self.config.llm_config.num_hidden_layers)
                 native.check(lib.aigv_key_drop_arm_ex(ctx, words_d.data_ptr(), native.ptr(rows_d), int(drop_words.shape[1]), int(lo), int(hi)), ctx)
+        if lens is not None:            # return_depth_lens: (score rows, token rows, hidden, normed, score) - armed for exactly the pass below, which disarms
+            l_score, l_token, l_hidden, l_normed, l_out = lens
+            native.check(lib.aigv_depth_lens_arm(ctx, native.i32_array(l_score) if l_score else None, len(l_score), native.i32_array(l_token) if l_token else None,
+                                                 len(l_token), l_hidden.data_ptr(), l_normed.data_ptr(), native.ptr(l_out)), ctx)
         native.check(lib.aigv_llm_prefill(
             ctx, ids_d.data_ptr(), slot_d.data_ptr(), cu_a, b, native.ptr(vis), n_vis, native.ptr(motion),
             sr_a, native.ptr(score), lr_a, len(logit_rows), amax.data_ptr(), int(keep_kv), native.stream_ptr()), ctx)
@@ -358,6 +362,68 @@ class ScoringPass:
             native.check(lib.aigv_score_attention_arm(*args), self._ctx)
         return att, tok
 
+    # ---- the depth lens (return_depth_lens) ---------------------------------------------------------------------------------------------
+    def _depth_lens_rows(self, plan, with_tokens: bool):
+        """(the packed score row of every clip - stage 2, else none; the clips that have an answer token; the packed row that predicts each one's
+        first answer token: ``_probe_rows``' stage-1 rule, applied in both stages)."""
+        score_rows = [int(r) for r in plan["score_rows"]] if plan["score_rows"] is not None else []
+        clips, token_rows = [], []
+        if with_tokens:
+            answer = (plan["labels_h"][:, 1:] != -100) & (plan["row_of"][:, :-1] >= 0)
+            for b in range(answer.shape[0]):
+                at = answer[b].nonzero().flatten()
+                if at.numel():
+                    clips.append(b)
+                    token_rows.append(int(plan["row_of"][b, int(at[0])]))
+        if not score_rows and not token_rows:
+            raise ValueError("return_depth_lens: nothing to read - a stage-1 model needs labels with an answer token (the lens reads the row that predicts the first one)")
+        return score_rows, clips, token_rows
+
+    def _depth_lens_buffers(self, score_rows, token_rows):
+        """What ``_prefill`` arms the pass with (aigv_depth_lens_arm): the row lists and the three tensors the pass fills."""
+        llm = self.config.llm_config
+        D, n = llm.num_hidden_layers + 1, len(score_rows) + len(token_rows)
+        hidden = torch.empty((D, n, llm.hidden_size), dtype=torch.bfloat16, device=self.device)
+        normed = torch.empty_like(hidden)
+        score = torch.empty((D, len(score_rows)), dtype=torch.float32, device=self.device) if score_rows else None
+        return score_rows, token_rows, hidden, normed, score
+
+    def _depth_lens_outputs(self, B, lens, clips, ro, with_tokens: bool) -> dict:
+        """The ``lens_*`` entries of the result dict from the armed pass's buffers; the token read-outs through aigv_depth_lens_token_readout (one pass
+        over the lm-head per 64 rows, top-1 and candidates from the same logits)."""
+        score_rows, token_rows, hidden, normed, score = lens
+        D, n, H = hidden.shape
+        nS, nT = len(score_rows), len(token_rows)
+        dev, out = self.device, {}
+        if nS:
+            out["lens_score"] = score.t().contiguous()                              # [B, L + 1]
+            out["lens_score_hidden"] = hidden[:, :nS].transpose(0, 1).contiguous()    # [B, L + 1, H]
+        if not with_tokens:                 # (without labels the token outputs are absent)
+            return out
+        C = 0 if ro.cand is None else int(ro.cand.numel())
+        tok = torch.full((B, D), -1, dtype=torch.long, device=dev)
+        lp = torch.full((B, D), float("nan"), dtype=torch.float32, device=dev)
+        th = torch.zeros((B, D, H), dtype=torch.bfloat16, device=dev)
+        cl = torch.full((B, D, C), float("nan"), dtype=torch.float32, device=dev) if C else None
+        if nT:
+            lib, ctx = native.load(), self._ctx
+            rows = normed[:, nS:].contiguous()                                      # [L + 1, nT, H]: the token rows of every depth, dense
+            top_id = torch.empty(D * nT, dtype=torch.long, device=dev)
+            top_lp = torch.empty(D * nT, dtype=torch.float32, device=dev)
+            cand_lp = torch.empty((D * nT, C), dtype=torch.float32, device=dev) if C else None
+            native.check(lib.aigv_depth_lens_token_readout(ctx, rows.data_ptr(), H, D * nT, self._h2d(ro.cand).data_ptr() if C else None, C, top_id.data_ptr(),
+                                                           top_lp.data_ptr(), native.ptr(cand_lp), native.stream_ptr()), ctx)
+            at = self._h2d(torch.tensor(clips, dtype=torch.long))
+            tok.index_copy_(0, at, top_id.view(D, nT).t().contiguous())
+            lp.index_copy_(0, at, top_lp.view(D, nT).t().contiguous())
+            th.index_copy_(0, at, hidden[:, nS:].transpose(0, 1).contiguous())
+            if C:
+                cl.index_copy_(0, at, cand_lp.view(D, nT, C).transpose(0, 1).contiguous())
+        out.update(lens_token=tok, lens_token_logprob=lp, lens_token_hidden=th)
+        if C:
+            out["lens_cand_logprob"] = cl
+        return out
+
     def forward(self, mos: Optional[torch.Tensor] = None, pixel_values: Optional[torch.Tensor] = None,
                 input_ids: Optional[torch.Tensor] = None, attention_mask: Optional[torch.Tensor] = None,
                 position_ids=None, image_flags: Optional[torch.Tensor] = None, past_key_values=None,
@@ -366,7 +432,7 @@ class ScoringPass:
                 visual_tokens: Optional[torch.Tensor] = None, full_logits: bool = False, return_logprobs: bool = False,
                 candidate_ids=None, top_logprobs: Optional[int] = None, return_score_attention: bool = False, attention_segments=None,
                 return_token_attention: bool = False, key_drop: Optional[torch.Tensor] = None, key_drop_rows: Optional[torch.Tensor] = None,
-                key_drop_layers: Optional[tuple] = None):
+                key_drop_layers: Optional[tuple] = None, return_depth_lens: bool = False):
         """Stage-2 eval pass (modeling_internvl_chat.py:306-488) or, with ``stage=1``, the stage-1 pass
         (internvl_chat_eval1/modeling_internvl_chat.py:250-366).  ``visual_tokens`` optionally supplies
         already all-gathered pre-projector tokens (frame-DP) instead of ``pixel_values``.
@@ -432,7 +498,22 @@ class ScoringPass:
         is launched: either one without ``key_drop``; a wrong shape or window; a token that is both a dropped key and a selected row (a row is
         never cut from itself) - under ``key_drop_rows`` a consumed row MAY then be a dropped key; the first token never.  Empty rows, empty
         keys or an empty window give the plain pass's bits.  ``segment_masks`` builds the usual groups (frames, text after them, the score
-        row), ``eval_utils.flow_knockout`` the score deltas per path and layer window."""
+        row), ``eval_utils.flow_knockout`` the score deltas per path and layer window.
+
+        ``return_depth_lens=True`` - AT WHICH DEPTH the score exists (the logit lens): the residual stream of two rows per clip after every
+        layer, through the model's own final norm and its own heads.  With L layers, depth d = 0 is the embedding, depth d the stream after d
+        layers, depth L what the final norm consumes.  Stage 2 adds ``lens_score`` (fp32 [B, L + 1]: the score head on the final norm of the
+        score row at depth d, its NaN guard taken over the batch's B score rows of that depth; column L is ``score1``, bit for bit) and
+        ``lens_score_hidden`` (bf16 [B, L + 1, H]: that row's raw, un-normed residual).  With ``labels`` either stage adds, for the row that
+        predicts the clip's first answer token: ``lens_token`` (int64 [B, L + 1]: the most likely token under final norm + lm-head at depth d,
+        equal logits by the lower id, -1 for a clip without an answer token; column L is ``logit`` at that row), ``lens_token_logprob`` (fp32
+        [B, L + 1]: its full-vocabulary log-probability, NaN where the token is -1; column L is ``top_logprob[row, 0]``),
+        ``lens_token_hidden`` (bf16 [B, L + 1, H], zeros for such a clip) and - with ``candidate_ids`` - ``lens_cand_logprob`` (fp32 [B, L + 1,
+        C]: the candidates' columns of the same log-softmax; depth L is ``cand_logprob[row]``).  ``top_logprobs`` does not extend to the lens.
+        The lens reads the stream, not the attention: no other output changes a bit, and it combines with every other option, ``key_drop``
+        and its qualifiers (the lens of the masked pass) and the probe included.  At most 64 clips per pass.  Under graph replay the flag is
+        part of the graph's key; with ``key_drop`` the call runs eagerly as it does without the lens.  ``eval_utils.settling_depth`` folds
+        ``lens_score`` to the depth from which the score stays put."""
         if position_ids is not None or past_key_values is not None:
             raise NotImplementedError("the eval pass takes default positions and no cache, like the reference drivers")
         if self.img_context_token_id is None:
@@ -447,10 +528,15 @@ class ScoringPass:
                                                          full_logits), kd, kd_rows)
             if kd_rows is not None:
                 drop_words, drop_row_words = drop_words
+        if return_depth_lens and self._capture_keep is None:      # likewise: is there a row to read?  (inside a capture the call that led here has checked)
+            src = visual_tokens if visual_tokens is not None else pixel_values
+            self._depth_lens_rows(self._plan(input_ids, attention_mask, labels, image_flags, (src.tokens if isinstance(src, VisualAhead) else src).shape[0], full_logits),
+                                  labels is not None)
         pixel_values, visual_tokens, motion_feature = self._take_ahead(pixel_values, visual_tokens, motion_feature)
         parse = lambda: readouts.ReadOuts.parse(self.config.llm_config.vocab_size, labels, return_logprobs, candidate_ids, top_logprobs,
                                                 return_score_attention, attention_segments, return_token_attention, key_drop,
-                                                None if input_ids is None else input_ids.shape, key_drop_rows, key_drop_layers, n_layers)
+                                                None if input_ids is None else input_ids.shape, key_drop_rows, key_drop_layers, n_layers,
+                                                return_depth_lens)
         ro = None
         if self._graph_replay_enabled and self._capture_keep is None:
             ro = parse()
@@ -466,18 +552,23 @@ class ScoringPass:
         plan = self._plan(input_ids, attention_mask, labels, image_flags, n_frames, full_logits)
         ro = ro or parse()      # (once per call; on the eager path behind the plan's own checks, where the options have always been checked)
         lp_labels = self._logprob_labels(plan) if ro.wants_labels else None
+        lens_rows = self._depth_lens_rows(plan, labels is not None) if ro.depth_lens else None
         motion_feature = self._motion_feature(pixel_values, B, motion_feature)
 
         # ---- device work: ViT -> projector -> motion projector -> LLM pass + heads ----
         self._native(n_frames=n_frames, n_tokens=plan["cu"][-1], n_clips=B, out_rows=len(plan["logit_rows"]), seq_len=N)   # size workspaces once
         vit_embeds, motion = self._visual_inputs(pixel_values, visual_tokens, motion_feature, plan)
         probe = self._score_attention_probe(plan, input_ids, ro) if ro.score_attention else None
+        lens = None if lens_rows is None else self._depth_lens_buffers(lens_rows[0], lens_rows[2])
         score, amax, *armed = self._prefill(plan["ids_packed"], plan["slot"], plan["cu"], vit_embeds, plan["n_vis"], motion,
                                             plan["score_rows"], plan["logit_rows"], probe=probe, ld_tok=N if ro.token_attention else 0,
-                                            drop_words=drop_words, drop_row_words=drop_row_words, drop_layers=kd_layers)
+                                            drop_words=drop_words, drop_row_words=drop_row_words, drop_layers=kd_layers, lens=lens)
         att, tok = armed or (None, None)        # (_prefill hands the probe's tensors back only when it armed one)
         reads = self._read_rows(B if score is not None else 0, len(plan["logit_rows"]), ro, lp_labels)
-        return self._outputs(plan, B, N, score, amax, mos, reads, att, tok)
+        out = self._outputs(plan, B, N, score, amax, mos, reads, att, tok)
+        if lens is not None:
+            out.update(self._depth_lens_outputs(B, lens, lens_rows[1], ro, labels is not None))
+        return out
 
     def dp_front(self, frames_local: torch.Tensor, frames_clips: Optional[torch.Tensor], n_clips: int):
         """The data-parallel scorer's front half on this rank (dist_utils.score_clips_dp): the SlowFast feature of its own clips (side

@@ -47,7 +47,8 @@ extern "C" {
                                 form (aigv_score_attention_arm_tokens, aigv_op_attention_probe_tokens), then by the key-drop mask of the
                                 prefill attention (aigv_key_drop_arm, aigv_op_attention_drop), then by the key-drop form of the decode attention
                                 (aigv_op_attention_decode_drop; the mask now travels with the KV cache: aigv_key_drop_arm), then by the
-                                key-drop mask by query row and layer window (aigv_key_drop_arm_ex, aigv_op_attention_drop_rows)
+                                key-drop mask by query row and layer window (aigv_key_drop_arm_ex, aigv_op_attention_drop_rows), then by the
+                                depth lens (aigv_depth_lens_arm, aigv_depth_lens_token_readout, aigv_op_lens_tap, aigv_op_score_head_groups)
                                 - added symbols only: a library without them is refused at load
                                 time, "missing <name>" */
 
@@ -231,6 +232,36 @@ int aigv_key_drop_arm(aigv_ctx* ctx, const uint64_t* words_dev, int ld_words);
  * together with row words or a window other than [0, llm_layers) - the mask kept beside the KV cache has neither; the probe armed as well.
  * aigv_llm_extend refuses an armed context as it does after aigv_key_drop_arm. */
 int aigv_key_drop_arm_ex(aigv_ctx* ctx, const uint64_t* words_dev, const uint64_t* row_words_dev, int ld_words, int layer_begin, int layer_end);
+
+/* Most score rows, and most token rows, one depth-lens pass takes. */
+#define AIGV_MAX_LENS_ROWS 64
+/* The depth lens: read the residual stream of a few rows after EVERY layer.  Arms exactly the next aigv_llm_prefill, which disarms on every way
+ * out.  With L = llm_layers, depth d = 0 is the embedding, depth d the stream after d layers, depth L what the final norm consumes.
+ *   score_rows_host  HOST int32 [n_score], token_rows_host HOST int32 [n_token]: packed row indices in score_rows' convention (copied here: the
+ *                    arrays need not outlive the call); 0 <= n_score, n_token <= AIGV_MAX_LENS_ROWS, at least one row in all.  Every row must be
+ *                    one of that pass's consumed rows (a score row or a logit row): the last layer finishes only those.
+ *   hidden_out_bf16  DEVICE bf16 [L + 1][n_score + n_token][H]: the rows as they are, score rows first;
+ *   normed_out_bf16  DEVICE bf16, same layout: the model's final RMSNorm of each - the bits the pass's own final norm gives such a row;
+ *   score_out        DEVICE fp32 [L + 1][n_score] (NULL when n_score = 0): the score head on normed_out[d][:n_score], the NaN guard taken over
+ *                    those n_score rows of that depth; score_out[L] holds the bits of the pass's own `score` for the same rows.
+ * The buffers are the caller's (16-byte aligned; score_out 4-byte) and must stay alive until the pass has run; nothing is allocated in the pass,
+ * so it still captures.  The pass adds one launch per depth (the tap) and, after its own heads, the score head over all depths' score rows at
+ * once; nothing it computed before changes a bit, and an unarmed pass enters no new code.  Combines with aigv_key_drop_arm / _ex and the
+ * score-attention probe: it reads the stream, not the attention.
+ * Refused with AIGV_ERR_ARG and a message, nothing armed: a row list longer than AIGV_MAX_LENS_ROWS or no row at all, a null row list, a null or
+ * misaligned buffer.  Refused by the pass, before any launch: a lens row that is not among its consumed rows, score rows when the pass has
+ * score == NULL, a pass without output rows; aigv_llm_extend refuses an armed context. */
+int aigv_depth_lens_arm(aigv_ctx* ctx, const int32_t* score_rows_host, int n_score, const int32_t* token_rows_host, int n_token,
+                        void* hidden_out_bf16, void* normed_out_bf16, float* score_out);
+/* The lm-head read-out of normed rows such as normed_out_bf16's token rows: n_rows >= 1 DEVICE bf16 rows of H elements, leading dimension ld
+ * (a multiple of 8, >= H), 64 rows at a time through the logits scratch of aigv_out_row_logprob in its one form (a row's bits do not depend on
+ * its chunk) - one pass over the lm-head weights per chunk, both read-outs from the same fill:
+ *   top_id [n_rows] int64 / top_logprob [n_rows] fp32   the largest bf16 logit (equal logits: the lower id) and its full-vocabulary
+ *                    log-probability - aigv_out_row_topk_logprob's bits with k = 1;
+ *   cand_logprob [n_rows, C] fp32 (cand_ids DEVICE int64 [C], 1 <= C <= AIGV_MAX_CANDIDATES; both NULL and C = 0: not read)
+ *                    aigv_out_row_cand_logprob's bits. */
+int aigv_depth_lens_token_readout(aigv_ctx* ctx, const void* normed_rows_dev, int ld, int n_rows, const int64_t* cand_ids, int C, int64_t* top_id,
+                                  float* top_logprob, float* cand_logprob, void* stream);
 
 /* Replicate the n kept sequences `copies` times (cache slots [0, n) -> [n, 2n), ...; needs n * copies <= max_seqs): the copies can
  * then take DIFFERENT continuations in one aigv_llm_extend call over n * copies sequences (sequence c * n + b continues clip b),
@@ -578,6 +609,15 @@ int aigv_op_skinny_rope_kv_fp8(const void* x, int ldx, int R, const void* W_e4m3
  * and the last layer must be a tail layer (as every fan-out of 1 is). */
 int aigv_op_score_head(const void* x, int ldx, int B, int n_layers, const int32_t* dims_host, const void* const* w_dev, const void* const* b_dev,
                        void* scratch, int64_t scratch_bytes, float* score, void* stream);
+/* aigv_op_score_head on G batch slices in one go: slice g = the B rows at x + g * group_stride elements (leading dimension ldx), guarded on its
+ * own; score [G * B].  Slice for slice the bits of aigv_op_score_head on that slice alone (the GEMM layers run over all G * B rows in chunks of
+ * at most 64, the tail kernel over all of them).  1 <= G, G * B <= 4096, group_stride >= 0; scratch >= 3 G B max(dims) bf16; B, the dims and
+ * the split into GEMM and tail layers under aigv_op_score_head's rules. */
+int aigv_op_score_head_groups(const void* x, int ldx, int G, int64_t group_stride, int B, int n_layers, const int32_t* dims_host,
+                              const void* const* w_dev, const void* const* b_dev, void* scratch, int64_t scratch_bytes, float* score, void* stream);
+/* The depth lens' tap: raw[i, :H] = src[idx[i] * ld ..] (aigv_op_gather_rows' bits) and normed[i, :H] = its RMSNorm under w (aigv_op_rmsnorm's
+ * bits on the gathered rows), i < n, both dense; one launch.  H a multiple of 8 in 8..16384, ld a multiple of 8 and >= H, idx DEVICE int32 [n]. */
+int aigv_op_lens_tap(const void* src, int ld, const int32_t* idx, int n, const void* w, void* raw, void* normed, int H, float eps, void* stream);
 /* RMSNorm fused with the e4m3 row quantisation of its result: the bytes q [rows, ldq] and scales row_scale[rows] of aigv_op_rmsnorm followed by
  * aigv_op_quant_fp8_rows.  H a multiple of 8 in 8..16384; ldx, ldq multiples of 8 and >= H. */
 int aigv_op_rmsnorm_quant_fp8(const void* x, int ldx, const void* w, void* q_e4m3, int ldq, float* row_scale, int rows, int H, float eps, void* stream);
