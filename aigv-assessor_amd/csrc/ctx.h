@@ -153,6 +153,16 @@ struct aigv_ctx {
     float* score = nullptr;                        // device, the caller's: [llm_layers + 1][n_score]
   } lens;
   int32_t* l_lensidx = nullptr;   // device [4 * AIGV_MAX_LENS_ROWS]: the armed pass's lens rows | their places among the consumed rows (row trimming)
+  // activation patching (aigv_stream_capture_arm / aigv_stream_patch_arm): armed for exactly the next aigv_llm_prefill.  At the top of layer li, lo <= li <
+  // hi, the patch writes slice li - lo of its buffer over the rows `rows` of the residual stream, then the capture copies its rows of the stream - as the
+  // layer consumes it - into slice li - lo of its own.  rows: packed row numbers, copied on arming, checked by the pass (inside [0, T), strictly ascending)
+  struct StreamRows {
+    bool armed = false;
+    int lo = 0, hi = 0;
+    std::vector<int32_t> rows;
+    bf16_t* buf = nullptr;   // device, the caller's: [rows.size()][hi - lo][H]
+  } stream_cap, stream_patch;
+  int32_t* l_streamidx = nullptr;   // device [2 * max_tokens]: the armed pass's patch rows | its capture rows
   // profiling
   bool prof = false;
   int gemm_cls = AIGV_PROF_GEMM;   // class the GEMM launches are booked under: AIGV_PROF_GEMM_VIT inside aigv_vit_forward / aigv_project
@@ -277,15 +287,18 @@ constexpr size_t SPLITK_MAX_FLOATS = (size_t)64 << 20;   // 256 MB of fp32 split
 int splitk_scratch(aigv_ctx* c, size_t need_floats, float** out);
 
 // ---- the score-row attention probe of an armed pass (probe.hip) --------------------------------------------------------------------
-// DisarmScope: the pass that finds the context armed - with the probe, with a key-drop mask (aigv_key_drop_arm), with the depth lens (aigv_depth_lens_arm) - disarms it on every way out.  probe_plan: the probe's arguments for this pass (rows
+// DisarmScope: the pass that finds the context armed - with the probe, with a key-drop mask (aigv_key_drop_arm), with the depth lens (aigv_depth_lens_arm), with a stream capture or patch (aigv_stream_capture_arm, aigv_stream_patch_arm) - disarms it on every way out.  probe_plan: the probe's arguments for this pass (rows
 // validated against cu; off_host: keys cached in front of every sequence, or null), built ONCE per pass; probe_layer: the launch of layer li.
 struct DisarmScope {
   aigv_ctx* c;
   explicit DisarmScope(aigv_ctx* c_) : c(c_) {}
-  ~DisarmScope() { c->probe.armed = false; c->drop.armed = false; c->lens.armed = false; }
+  ~DisarmScope() { c->probe.armed = false; c->drop.armed = false; c->lens.armed = false; c->stream_cap.armed = false; c->stream_patch.armed = false; }
 };
 int probe_plan(aigv_ctx* c, const char* op, const int32_t* cu, int B, const int32_t* off_host, ProbeArgs* out);
 int probe_layer(aigv_ctx* c, const ProbeArgs& plan, int li, bool cache, hipStream_t s);
+// the row list of a stream capture / patch against a pass of T packed rows and L layers (passes.hip; aigv_op_stream_rows shares it): every row inside
+// [0, T), strictly ascending - so a patch's rows are unique - and the window 0 <= lo <= hi <= L
+int stream_rows_check(aigv_ctx* c, const char* op, const int32_t* rows, int n, int T, int lo, int hi, int L);
 extern double g_rate256;   // the cost model's throughput of the 256 kernel relative to the 128 kernel (aigv_tune_gemm overrides it)
 
 }  // namespace aigv

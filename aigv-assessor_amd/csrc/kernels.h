@@ -201,6 +201,11 @@ hipError_t aigv_launch_gather_rows(const bf16_t* src, int ld, const int32_t* idx
 hipError_t aigv_launch_lens_tap(const bf16_t* src, int ld, const int32_t* idx, int n, const bf16_t* w, bf16_t* raw, bf16_t* normed, int H, float eps,
                                 hipStream_t s);
 hipError_t aigv_launch_scatter_rows(const bf16_t* src, const int32_t* idx, int n, bf16_t* dst, int ld, int H, hipStream_t s);   // dst[idx[i]] = src[i]
+// activation patching: rows idx[i] (distinct) of `stream` (leading dimension ld) against slice `depth` of a side buffer whose element (i, d) sits at
+// side + (i * n_depths + d) * H.  to_stream: stream[idx[i]] = side(i, depth) (the patch), else side(i, depth) = stream[idx[i]] (the capture); a bit
+// copy.  H a multiple of 8 in 8..16384, ld a multiple of 8 and >= H, both buffers 16-byte aligned, 0 <= depth < n_depths: else hipErrorInvalidValue
+hipError_t aigv_launch_stream_rows(bf16_t* stream, int ld, const int32_t* idx, int n, bf16_t* side, int n_depths, int depth, int H, bool to_stream,
+                                   hipStream_t s);
 hipError_t aigv_launch_cls_rows(const bf16_t* cls_pos, bf16_t* x, int F, int tokens_per_frame, int H, hipStream_t s);
 // RoPE in place on the fused qkv rows: per kv group, slots 0..g (q heads and K) are rotated.
 // slots [first_rot, first_rot + n_rot) of every group are rotated in place (q heads + K: first_rot 0, n_rot g + 1; K only: g, 1)

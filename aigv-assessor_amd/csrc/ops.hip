@@ -607,6 +607,23 @@ int aigv_op_scatter_rows(const void* src, const int32_t* idx, int n, void* dst, 
   return 0;
 }
 
+// One launch of the activation-patching row copy (aigv_stream_capture_arm / aigv_stream_patch_arm), as a pass of T rows and n_depths armed layers makes
+// it for its layer `depth` of the window: rows_host - checked as the pass checks them - go to idx_dev (DEVICE int32 [n]) as kernel arguments, then rows
+// idx[i] of `stream_rows` (leading dimension ld) are copied to (to_stream = 0) or overwritten from (to_stream = 1) side[(i * n_depths + depth) * H ..]
+int aigv_op_stream_rows(void* stream_rows, int ld, int T, const int32_t* rows_host, int n, int32_t* idx_dev, void* side, int n_depths, int depth, int H,
+                        int to_stream, void* stream) {
+  const char* op = "aigv_op_stream_rows";
+  TRY(check_rows(op, stream_rows, side, rows_host, true, n, H, ld));
+  if (!idx_dev) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+  if (H > 16384) return fail(nullptr, AIGV_ERR_ARG, "%s: H = %d above 16384", op, H);
+  if (T < 0) return fail(nullptr, AIGV_ERR_ARG, "%s: T = %d rows: must not be negative", op, T);
+  if (n_depths < 1 || depth < 0 || depth >= n_depths) return fail(nullptr, AIGV_ERR_ARG, "%s: depth %d outside the window of %d depths", op, depth, n_depths);
+  TRY(stream_rows_check(nullptr, op, rows_host, n, T, 0, n_depths, n_depths));
+  HIPCHK(nullptr, aigv_launch_write_ints(rows_host, n, idx_dev, (hipStream_t)stream));
+  HIPCHK(nullptr, aigv_launch_stream_rows((bf16_t*)stream_rows, ld, idx_dev, n, (bf16_t*)side, n_depths, depth, H, to_stream != 0, (hipStream_t)stream));
+  return 0;
+}
+
 // x[f * tokens_per_frame, :H] = cls_pos[:H] for f < n_frames (x is dense [n_frames * tokens_per_frame, H])
 int aigv_op_cls_rows(const void* cls_pos, void* x, int n_frames, int tokens_per_frame, int H, void* stream) {
   const char* op = "aigv_op_cls_rows";

@@ -7,6 +7,19 @@
 
 using namespace aigv;
 
+// The row list of a stream capture / patch against the pass that runs it (ctx.h); `op`: what the message starts with.
+namespace aigv {
+int stream_rows_check(aigv_ctx* c, const char* op, const int32_t* rows, int n, int T, int lo, int hi, int L) {
+  if (lo < 0 || lo > hi || hi > L) return fail(c, AIGV_ERR_ARG, "%s: depths [%d, %d) outside 0 <= lo <= hi <= %d", op, lo, hi, L);
+  for (int i = 0; i < n; ++i) {
+    if (rows[i] < 0 || rows[i] >= T) return fail(c, AIGV_ERR_ARG, "%s: row %d (packed row %d) outside [0, %d), the rows the pass runs", op, i, rows[i], T);
+    if (i > 0 && rows[i] <= rows[i - 1])
+      return fail(c, AIGV_ERR_ARG, "%s: rows %d and %d (packed rows %d, %d) are not strictly ascending", op, i - 1, i, rows[i - 1], rows[i]);
+  }
+  return 0;
+}
+}  // namespace aigv
+
 extern "C" {
 
 // ---- InternViT ---------------------------------------------------------------------------------------------
@@ -275,6 +288,8 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
   const bool probing = c->probe.armed;   // aigv_score_attention_arm: this pass carries the probe, and disarms on every way out
   const bool dropping = c->drop.armed;   // aigv_key_drop_arm / _ex: the attention of the armed layers of this pass runs under the mask; disarmed likewise
   const bool lensing = c->lens.armed;    // aigv_depth_lens_arm: this pass taps the lens rows after the embedding and after every layer; disarmed likewise
+  const bool patching = c->stream_patch.armed;    // aigv_stream_patch_arm: rows of the residual stream are overwritten in front of the armed layers; disarmed likewise
+  const bool capturing = c->stream_cap.armed;     // aigv_stream_capture_arm: rows of the residual stream are copied out in front of the armed layers; disarmed likewise
   DisarmScope disarm(c);
   if (!c->finalized) return fail(c, AIGV_ERR_STATE, "aigv_llm_prefill: call aigv_finalize_weights first");
   if (dropping && probing) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: a key-drop mask and the score-attention probe are both armed: the probe does not know the mask");
@@ -302,6 +317,14 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
   if (dropping && (!c->drop.words || c->drop.ld < (max_len + 63) / 64))
     return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: key-drop mask armed with %d words per clip, the longest clip (%d tokens) needs %d", c->drop.ld, max_len,
                 (max_len + 63) / 64);
+  // activation patching: the row lists against this pass's T rows and L layers; a pass that keeps its KV cache takes neither (the options are the
+  // scoring pass's: the paths that continue from a cache do not carry them)
+  if ((patching || capturing) && keep_kv)
+    return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: keep_kv while a stream %s is armed (%s): only a pass without a KV cache takes one", patching ? "patch" : "capture",
+                patching ? "aigv_stream_patch_arm" : "aigv_stream_capture_arm");
+  const aigv_ctx::StreamRows &sp = c->stream_patch, &sc = c->stream_cap;
+  if (patching) TRY(stream_rows_check(c, "aigv_llm_prefill: the stream patch (aigv_stream_patch_arm)", sp.rows.data(), (int)sp.rows.size(), T, sp.lo, sp.hi, k.llm_layers));
+  if (capturing) TRY(stream_rows_check(c, "aigv_llm_prefill: the stream capture (aigv_stream_capture_arm)", sc.rows.data(), (int)sc.rows.size(), T, sc.lo, sc.hi, k.llm_layers));
   // the depth lens: every lens row must be a consumed row [score rows | logit rows] - the last layer finishes only those; lens_at: its place among them
   const int n_lens = lensing ? c->lens.n_score + c->lens.n_token : 0;
   int32_t lens_at[2 * AIGV_MAX_LENS_ROWS];
@@ -337,10 +360,11 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
     HIPCHK(c, aigv_launch_lens_tap(src, H, idx, n_lens, c->final_norm, c->lens.hidden + off, c->lens.normed + off, H, k.rms_eps, s));
     return 0;
   };
+  if (patching) HIPCHK(c, aigv_launch_write_ints(sp.rows.data(), (int)sp.rows.size(), c->l_streamidx, s));
+  if (capturing) HIPCHK(c, aigv_launch_write_ints(sc.rows.data(), (int)sc.rows.size(), c->l_streamidx + k.max_tokens, s));
   if (lensing) {
     HIPCHK(c, aigv_launch_write_ints(c->lens.rows, n_lens, c->l_lensidx, s));
     HIPCHK(c, aigv_launch_write_ints(lens_at, n_lens, c->l_lensidx + 2 * AIGV_MAX_LENS_ROWS, s));
-    TRY(lens_tap(0, c->l_h, lens_idx));
   }
   // Row trimming: after the last layer's attention every row is independent, and only the consumed rows (one score row per
   // clip + the answer rows) are read afterwards (stage2_eval.py:940-941; modeling_internvl_chat.py:469-481).  When they are
@@ -377,6 +401,13 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
   const size_t kv_layer = (size_t)k.max_seqs * nkv * k.kv_capacity * D;
   for (int li = 0; li < k.llm_layers; ++li) {
     const LlmLayer& L = c->llm[li];
+    // activation patching: the stream layer li consumes - first the patch's rows written over it, then the capture's rows read from it (so a capture
+    // armed beside a patch sees the patched rows); one launch each
+    if (patching && li >= sp.lo && li < sp.hi)
+      HIPCHK(c, aigv_launch_stream_rows(c->l_h, H, c->l_streamidx, (int)sp.rows.size(), sp.buf, sp.hi - sp.lo, li - sp.lo, H, true, s));
+    if (capturing && li >= sc.lo && li < sc.hi)
+      HIPCHK(c, aigv_launch_stream_rows(c->l_h, H, c->l_streamidx + k.max_tokens, (int)sc.rows.size(), sc.buf, sc.hi - sc.lo, li - sc.lo, H, false, s));
+    if (lensing) TRY(lens_tap(li, c->l_h, lens_idx));   // depth li < L: the stream this layer consumes, behind a patch of this depth
     TRY(llm_layer_qkv(c, li, T, s));
     if (keep_kv)
       HIPCHK(c, aigv_launch_kv_store(c->l_qkv, c->qkv_out, c->l_seq, c->l_pos, c->kc + li * kv_layer, c->vc + li * kv_layer, T,
@@ -424,7 +455,7 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
       break;
     }
     TRY(llm_layer_post(c, li, T, s));
-    if (lensing) TRY(lens_tap(li + 1, c->l_h, lens_idx));
+    if (lensing && li == k.llm_layers - 1) TRY(lens_tap(k.llm_layers, c->l_h, lens_idx));   // depth L of a pass whose last layer ran for every row
   }
   if (!trim) TRY(final_rows(c, score, B, R, argmax, c->l_h, false, s));
   if (lensing && c->lens.n_score > 0) {
@@ -497,6 +528,28 @@ int aigv_depth_lens_arm(aigv_ctx* c, const int32_t* score_rows_host, int n_score
   return 0;
 }
 
+// Arm the next aigv_llm_prefill with a capture / a patch of residual-stream rows (include/aigv_amd.h): the row numbers are copied here and checked, with
+// the window, when that pass runs; the buffer is the caller's.
+static int stream_rows_arm(const char* op, aigv_ctx* c, aigv_ctx::StreamRows* st, const int32_t* rows_host, int n, int lo, int hi, void* buf_bf16_dev) {
+  if (!c) return fail(c, AIGV_ERR_ARG, "%s: null context", op);
+  if (n < 0 || n > c->cfg.max_tokens) return fail(c, AIGV_ERR_ARG, "%s: %d rows outside 0..max_tokens = %d", op, n, c->cfg.max_tokens);
+  if (n > 0 && !rows_host) return fail(c, AIGV_ERR_ARG, "%s: null row list", op);
+  if (n > 0 && hi > lo && (!buf_bf16_dev || ((uintptr_t)buf_bf16_dev & 15))) return fail(c, AIGV_ERR_ARG, "%s: the device buffer is null or not 16-byte aligned", op);
+  st->rows.assign(rows_host, rows_host + n);
+  st->lo = lo; st->hi = hi;
+  st->buf = (bf16_t*)buf_bf16_dev;
+  st->armed = true;
+  return 0;
+}
+
+int aigv_stream_capture_arm(aigv_ctx* c, const int32_t* rows_host, int n, int lo, int hi, void* out_bf16_dev) {
+  return stream_rows_arm("aigv_stream_capture_arm", c, c ? &c->stream_cap : nullptr, rows_host, n, lo, hi, out_bf16_dev);
+}
+
+int aigv_stream_patch_arm(aigv_ctx* c, const int32_t* rows_host, int n, int lo, int hi, const void* values_bf16_dev) {
+  return stream_rows_arm("aigv_stream_patch_arm", c, c ? &c->stream_patch : nullptr, rows_host, n, lo, hi, const_cast<void*>(values_bf16_dev));
+}
+
 // Continue the sequences kept by aigv_llm_prefill(keep_kv = 1) with new TEXT tokens: causal attention of the new rows over the
 // cached keys plus themselves.  commit = 0 leaves the cache lengths where they were, so several continuations of ONE prefix
 // (the four quality-perspective questions behind the same video tokens) can be scored one after the other.
@@ -506,7 +559,11 @@ int aigv_llm_extend(aigv_ctx* c, const int64_t* ids, const int32_t* cu, int B, c
   const bool probing = c->probe.armed;
   const bool dropping = c->drop.armed;
   const bool lensing = c->lens.armed;
+  const bool patching = c->stream_patch.armed, capturing = c->stream_cap.armed;
   DisarmScope disarm(c);
+  if (patching || capturing)
+    return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: a stream %s is armed (%s): the continuation pass takes none, only aigv_llm_prefill does", patching ? "patch" : "capture",
+                patching ? "aigv_stream_patch_arm" : "aigv_stream_capture_arm");
   if (lensing) return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: the depth lens is armed (aigv_depth_lens_arm): the continuation pass takes no lens, only aigv_llm_prefill does");
   if (dropping) return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: a key-drop mask is armed (aigv_key_drop_arm): the continuation pass takes no mask, only aigv_llm_prefill does");
   if (!c->kv_valid) return fail(c, AIGV_ERR_STATE, "aigv_llm_extend: no KV state (run aigv_llm_prefill with keep_kv)");

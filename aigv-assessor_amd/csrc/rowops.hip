@@ -249,6 +249,22 @@ __global__ void scatter_rows_kernel(const bf16_t* __restrict__ src, const int32_
   for (int c = threadIdx.x; c < (H >> 3); c += blockDim.x) *(u16x8*)(row + (c << 3)) = *(const u16x8*)(src + (size_t)i * H + (c << 3));
 }
 
+// Activation patching (aigv_stream_capture_arm / aigv_stream_patch_arm): rows idx[i] of the residual stream against slice `depth` of a side
+// buffer that keeps n_depths depths of every selected row together - element (i, d) at side + (i * n_depths + d) * H.  TO_STREAM: the side
+// buffer's rows overwrite the stream's (the patch); else the stream's rows are copied out (the capture).  One workgroup per row, 16-byte chunks
+// moved as bits: a NaN or Inf payload travels unchanged.  The indices are distinct (the pass checks them strictly ascending).
+template <bool TO_STREAM>
+__global__ __launch_bounds__(256) void stream_rows_kernel(bf16_t* __restrict__ stream, int ld, const int32_t* __restrict__ idx,
+                                                          bf16_t* __restrict__ side, int n_depths, int depth, int H) {
+  const int i = blockIdx.x;
+  bf16_t* srow = stream + (size_t)idx[i] * ld;
+  bf16_t* brow = side + ((size_t)i * n_depths + depth) * H;
+  for (int c = threadIdx.x; c < (H >> 3); c += 256) {
+    if (TO_STREAM) *(u16x8*)(srow + (c << 3)) = *(const u16x8*)(brow + (c << 3));
+    else *(u16x8*)(brow + (c << 3)) = *(const u16x8*)(srow + (c << 3));
+  }
+}
+
 // ---- RoPE in place (modeling_internlm2.py:247-261): out = bf16(bf16(x*cos) + bf16(rot(x)*sin)) ---------
 // qkv row layout: n_groups x slots_per_group x D; slots [0, n_rot) of every group are rotated (q heads + K).
 // cos/sin tables are [max_pos, D/2] bf16 (the second half of the reference's table repeats the first).
@@ -551,6 +567,17 @@ hipError_t aigv_launch_scatter_rows(const bf16_t* src, const int32_t* idx, int n
   if (n <= 0) return hipSuccess;
   if (H % 8 || ld % 8) return hipErrorInvalidValue;
   hipLaunchKernelGGL(scatter_rows_kernel, dim3(n), dim3(256), 0, s, src, idx, dst, ld, H);
+  return hipGetLastError();
+}
+
+hipError_t aigv_launch_stream_rows(bf16_t* stream, int ld, const int32_t* idx, int n, bf16_t* side, int n_depths, int depth, int H, bool to_stream,
+                                   hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (H < 8 || H % 8 || H > MAXC * 256 * 8 || ld % 8 || ld < H || n_depths < 1 || depth < 0 || depth >= n_depths || !stream || !idx || !side ||
+      ((uintptr_t)stream & 15) || ((uintptr_t)side & 15))
+    return hipErrorInvalidValue;
+  if (to_stream) hipLaunchKernelGGL(stream_rows_kernel<true>, dim3(n), dim3(256), 0, s, stream, ld, idx, side, n_depths, depth, H);
+  else hipLaunchKernelGGL(stream_rows_kernel<false>, dim3(n), dim3(256), 0, s, stream, ld, idx, side, n_depths, depth, H);
   return hipGetLastError();
 }
 

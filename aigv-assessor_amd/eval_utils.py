@@ -265,6 +265,91 @@ def flow_knockout(model, *, pixel_values, input_ids, attention_mask, image_flags
     return res
 
 
+def restored_fraction(score, clean_score, corrupt_score):
+    """How far a patched score moved from the corrupt pass's towards the clean pass's: ``(score - corrupt) / (clean - corrupt)``, 0 = the patch did
+    nothing, 1 = the clean score restored.  ``score`` [B, ...], ``clean_score`` / ``corrupt_score`` [B]; fp32; NaN where the denominator is 0."""
+    import torch
+    score, clean, corrupt = score.float(), clean_score.float(), corrupt_score.float()
+    if clean.shape != corrupt.shape or clean.dim() != 1 or score.dim() < 1 or score.shape[0] != clean.shape[0]:
+        raise ValueError(f"restored_fraction: expected score [B, ...] and clean / corrupt [B], got {tuple(score.shape)}, {tuple(clean.shape)}, {tuple(corrupt.shape)}")
+    shape = (-1,) + (1,) * (score.dim() - 1)
+    den = (clean - corrupt).view(shape).expand_as(score)
+    out = (score - corrupt.view(shape)) / den
+    return torch.where(den == 0, torch.full_like(out, float("nan")), out)
+
+
+def causal_trace(model, *, clean, corrupt, groups=None, width=1, stride=1, **readout_kwargs):
+    """WHERE THE QUALITY LIVES: activation patching (causal tracing, Meng et al. 2022) between two clips that share a token layout.  ``clean`` (the
+    donor) and ``corrupt`` (the recipient) are dicts of ``forward``'s inputs (``pixel_values``, ``input_ids``, ``attention_mask``, ``image_flags``,
+    optionally ``labels``, ``motion_feature``, ``mos``) with equal shapes, equal ``attention_mask`` and equal ``<IMG_CONTEXT>`` positions - anything
+    else is a ValueError.  The clean batch runs once, capturing the residual stream of the union of the groups at every depth
+    (``forward(return_stream=...)``); the corrupt batch runs once as it is and once per (group, depth window) with the clean rows of that group
+    patched in at the depths of the window (``forward(stream_patch=...)``).  ``groups``: a list of ``(name, mask)`` with bool [B, N] masks laid out
+    like ``input_ids`` - default: ``frame0`` .. (``model.unit_masks``), ``motion``, ``text_before``, ``text_after`` (minus the score row) and
+    ``score_row`` (``model.segment_masks``).  Windows: ``(lo, min(lo + width, L))`` for lo = 0, stride, 2 stride, ... < L.  The corrupt clip's
+    InternViT and SlowFast branch run ONCE; their outputs are handed to every pass.  ``readout_kwargs`` go to every ``forward`` call.
+
+    Returns a dict: ``outs`` - the clean result dict, the corrupt one, then one per group and window, group-major; ``names``; ``groups`` - the list
+    of (name, mask); ``windows`` - the list of (lo, hi); and for a stage-2 model ``clean_score`` / ``corrupt_score`` [B] (fp32), ``score`` [B, G, W]
+    (the corrupt clip's score under the patch) and ``restored`` = ``restored_fraction(score, clean_score, corrupt_score)``."""
+    import torch
+    from .readouts import StreamPatch
+    ids, ids_c = clean["input_ids"], corrupt["input_ids"]
+    if tuple(ids.shape) != tuple(ids_c.shape):
+        raise ValueError(f"causal_trace: input_ids of shape {tuple(ids.shape)} (clean) and {tuple(ids_c.shape)} (corrupt): the two need one token layout")
+    B, N = (int(v) for v in ids.shape)
+    for key in ("pixel_values", "image_flags"):
+        if tuple(clean[key].shape) != tuple(corrupt[key].shape):
+            raise ValueError(f"causal_trace: {key} of shape {tuple(clean[key].shape)} (clean) and {tuple(corrupt[key].shape)} (corrupt)")
+    am, am_c = clean.get("attention_mask"), corrupt.get("attention_mask")
+    if (am is None) != (am_c is None) or (am is not None and not torch.equal(am.detach().cpu().bool(), am_c.detach().cpu().bool())):
+        raise ValueError("causal_trace: the clean and the corrupt attention_mask differ")
+    ctx_id = model.img_context_token_id
+    if not torch.equal(ids.detach().cpu() == ctx_id, ids_c.detach().cpu() == ctx_id):
+        raise ValueError("causal_trace: the clean and the corrupt input_ids have their <IMG_CONTEXT> tokens at different positions")
+    if not torch.equal(clean["image_flags"].detach().cpu(), corrupt["image_flags"].detach().cpu()):
+        raise ValueError("causal_trace: the clean and the corrupt image_flags differ")
+    L = int(model.config.llm_config.num_hidden_layers)
+    width, stride = int(width), int(stride)
+    if not 1 <= width <= L or stride < 1:
+        raise ValueError(f"causal_trace: width = {width} outside 1..{L} or stride = {stride} below 1")
+    windows = [(lo, min(lo + width, L)) for lo in range(0, L, stride)]
+    n_frames = int(clean["pixel_values"].shape[0])
+    if groups is None:
+        units = model.unit_masks(ids, am, clean["image_flags"], n_frames=n_frames)
+        seg = model.segment_masks(ids, am, clean["image_flags"], n_frames=n_frames)
+        F = units.shape[1] - 1
+        groups = [(f"frame{u}", units[:, u]) for u in range(F)] + [("motion", units[:, F]), ("text_before", seg["text_before"]),
+                                                                     ("text_after", seg["text_after"] & ~seg["score_row"]), ("score_row", seg["score_row"])]
+    groups = [(str(name), mask.detach().to("cpu").bool()) for name, mask in groups]
+    for name, mask in groups:
+        if tuple(mask.shape) != (B, N):
+            raise ValueError(f"causal_trace: group {name!r} has shape {tuple(mask.shape)}, input_ids {(B, N)}")
+    union = torch.zeros(B, N, dtype=torch.bool)
+    for _, mask in groups:
+        union |= mask
+    donor = model.forward(**clean, return_stream=union, **readout_kwargs)                      # all depths: [n, L, H]
+    index = donor["stream_index"].cpu()
+    pixel_values = corrupt["pixel_values"]
+    common = {k: v for k, v in corrupt.items() if k != "pixel_values"}
+    if common.get("motion_feature") is None:
+        common["motion_feature"] = model.motion_feature(pixel_values, B)
+    common.update(visual_tokens=model.vit_tokens(pixel_values), **readout_kwargs)
+    outs = [donor, model.forward(**common)]
+    for name, mask in groups:
+        own = mask[index[:, 0], index[:, 1]]                                                   # the union's rows that belong to this group
+        at = own.nonzero().flatten().to(donor["stream"].device)
+        rows = donor["stream"].index_select(0, at)
+        for lo, hi in windows:
+            outs.append(model.forward(stream_patch=StreamPatch(mask, rows[:, lo:hi].contiguous(), (lo, hi), index[own]), **common))
+    res = {"outs": outs, "names": [name for name, _ in groups], "groups": groups, "windows": windows}
+    if "score1" in outs[0]:
+        clean_score, corrupt_score = outs[0]["score1"].float(), outs[1]["score1"].float()
+        score = torch.stack([o["score1"].float() for o in outs[2:]], 1).view(B, len(groups), len(windows)) if groups else clean_score.new_zeros(B, 0, len(windows))
+        res.update(score=score, clean_score=clean_score, corrupt_score=corrupt_score, restored=restored_fraction(score, clean_score, corrupt_score))
+    return res
+
+
 def frame_ablation_generate(model, *, pixel_values, input_ids, attention_mask, image_flags, max_new_tokens, candidate_ids=None, **gen):
     """WHAT IF a frame were not there, in WORDS: the reply to the stage-2 prompt as it is and once per unit with that unit's tokens hidden from
     the LLM (``generate_stage2(key_drop=model.unit_masks(...)[:, u])``) - unit u < F is frame u's visual tokens, unit F the motion token.

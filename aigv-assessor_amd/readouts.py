@@ -1,6 +1,7 @@
 """Which read-outs a scoring pass carries: label log-probs, candidate log-probs, top-k log-probs, score attention by segment and per token, the
-depth lens - and whether it runs under a key-drop mask (``key_drop`` with its qualifiers ``key_drop_rows`` / ``key_drop_layers``: not a read-out, but a
-per-call option that travels the same way).
+depth lens, a capture of residual-stream rows (``return_stream`` / ``stream_depths``) - and whether it runs under a key-drop mask (``key_drop`` with
+its qualifiers ``key_drop_rows`` / ``key_drop_layers``) or a patch of the stream (``stream_patch``): not read-outs, but per-call options that travel
+the same way.
 
 This module is the one place that knows that decision.  A new read-out adds, HERE: a member to ``ReadOuts`` and its check to
 ``ReadOuts.parse``; the element it appends to a graph's host key to ``ReadOuts.key_tail``; its keyword to ``forward_kwargs``; and - when it
@@ -102,6 +103,66 @@ def refuse_key_drop_qualifiers(where: str, key_drop_rows=None, key_drop_layers=N
                              "window); forward() does")
 
 
+@dataclass(frozen=True, eq=False)
+class StreamPatch:
+    """``forward(stream_patch=...)``: overwrite rows of the residual stream.  ``rows``: bool or integer tensor [B, N] laid out like ``input_ids``
+    (on any device) - the tokens patched; ``depths`` = (lo, hi), 0 <= lo <= hi <= L: immediately before each layer d, lo <= d < hi, runs;
+    ``values``: bf16 [n, hi - lo, H] on the device or the host, laid out exactly like the ``stream`` that ``forward(return_stream=rows,
+    stream_depths=depths)`` returns - n the selected tokens the pass runs, clip-major, position-ascending; ``index``: optionally the donor's
+    ``stream_index`` (int64 [n, 2]), then checked pair by pair against the recipient's."""
+    rows: torch.Tensor
+    values: torch.Tensor
+    depths: tuple
+    index: Optional[torch.Tensor] = None
+
+
+def _token_mask(name: str, t, ids_shape=None) -> torch.Tensor:
+    if not torch.is_tensor(t) or t.is_floating_point() or t.is_complex() or t.dim() != 2:
+        raise ValueError(f"{name}: expected a bool or integer tensor [B, N] laid out like input_ids")
+    if ids_shape is not None and tuple(t.shape) != tuple(ids_shape):
+        raise ValueError(f"{name}: shape {tuple(t.shape)} differs from input_ids {tuple(ids_shape)}")
+    return t.detach().to("cpu").bool().contiguous()
+
+
+def _depth_window(name: str, depths, n_layers: Optional[int] = None) -> tuple:
+    w = tuple(depths) if isinstance(depths, (tuple, list)) else None
+    if w is None or len(w) != 2 or any(isinstance(v, bool) or not isinstance(v, int) for v in w):
+        raise ValueError(f"{name}: expected a pair of ints (lo, hi), got {depths!r}")
+    lo, hi = w
+    if not 0 <= lo <= hi or (n_layers is not None and hi > n_layers):
+        raise ValueError(f"{name}: ({lo}, {hi}) outside 0 <= lo <= hi <= {n_layers if n_layers is not None else 'L'}")
+    return lo, hi
+
+
+def stream_options(return_stream=None, stream_depths=None, stream_patch=None, ids_shape=None, n_layers: Optional[int] = None):
+    """``return_stream`` / ``stream_depths`` / ``stream_patch`` -> (None or a HOST bool mask [B, N], None or (lo, hi), None or a ``StreamPatch``
+    whose ``rows`` is such a mask, whose ``depths`` is a checked pair and whose ``index`` is a HOST int64 [n, 2]).  Depth d, 0 <= d < L, is the
+    stream layer d consumes; ``stream_depths`` defaults to (0, L) and needs ``return_stream``.  The values' dtype and the shapes that do not need
+    the plan are checked here; the counts and the (clip, position) pairs where the plan is (``ScoringPass._stream_rows``)."""
+    rows = window = patch = None
+    if return_stream is not None:
+        rows = _token_mask("return_stream", return_stream, ids_shape)
+        window = _depth_window("stream_depths", stream_depths, n_layers) if stream_depths is not None else (0, n_layers) if n_layers is not None else None
+    elif stream_depths is not None:
+        raise ValueError("stream_depths: qualifies return_stream and needs one")
+    if stream_patch is not None:
+        p = stream_patch
+        if not isinstance(p, StreamPatch):
+            raise ValueError(f"stream_patch: expected a readouts.StreamPatch, got {type(p).__name__}")
+        lo, hi = _depth_window("stream_patch: depths", p.depths, n_layers)
+        v = p.values
+        if not torch.is_tensor(v) or v.dtype != torch.bfloat16 or v.dim() != 3 or int(v.shape[1]) != hi - lo:
+            raise ValueError(f"stream_patch: values must be a bf16 tensor [n, hi - lo = {hi - lo}, H] laid out like a captured stream, got "
+                             f"{tuple(v.shape) if torch.is_tensor(v) else type(v).__name__}{' ' + str(v.dtype) if torch.is_tensor(v) else ''}")
+        idx = p.index
+        if idx is not None:
+            if not torch.is_tensor(idx) or idx.is_floating_point() or idx.dtype == torch.bool or idx.dim() != 2 or int(idx.shape[1]) != 2:
+                raise ValueError("stream_patch: index must be an integer tensor [n, 2] of (clip, position) pairs (a donor's stream_index)")
+            idx = idx.detach().to("cpu").to(torch.long).contiguous()
+        patch = StreamPatch(_token_mask("stream_patch: rows", p.rows, ids_shape), v, (lo, hi), idx)
+    return rows, window, patch
+
+
 _NAN = float("nan")
 # every result laid out per label position, [B (N - 1)] + width: name in the result dict, the ``ReadOuts`` member that switches it on and gives
 # its trailing width (None: always there), dtype, fill wherever the row is not an answer row
@@ -126,11 +187,15 @@ class ReadOuts:
     key_drop_rows: Optional[torch.Tensor] = None    # host bool [B, N]: ... from these query rows only (None: every row)
     key_drop_layers: Optional[tuple] = None         # (lo, hi): ... in the layers lo <= l < hi only (None: every layer)
     depth_lens: bool = False                    # return_depth_lens: the score row and the token row after every layer (forward only)
+    stream_rows: Optional[torch.Tensor] = None      # return_stream: host bool [B, N], the tokens whose residual-stream rows are captured (forward only)
+    stream_depths: Optional[tuple] = None           # (lo, hi): ... at the depths lo <= d < hi (None with stream_rows None)
+    stream_patch: Optional[StreamPatch] = None      # rows of the stream overwritten in front of the layers of its window (forward only)
 
     @classmethod
     def parse(cls, vocab: int, labels="given", return_logprobs: bool = False, candidate_ids=None, top_logprobs: Optional[int] = None,
               return_score_attention: bool = False, attention_segments=None, return_token_attention: bool = False, key_drop=None,
-              ids_shape=None, key_drop_rows=None, key_drop_layers=None, n_layers: Optional[int] = None, return_depth_lens: bool = False) -> "ReadOuts":
+              ids_shape=None, key_drop_rows=None, key_drop_layers=None, n_layers: Optional[int] = None, return_depth_lens: bool = False,
+              return_stream=None, stream_depths=None, stream_patch=None) -> "ReadOuts":
         """The record of a call's public keyword arguments, checked.  ``labels=None`` (``forward`` without labels) refuses candidates and top-k;
         the shared-prefix and generate entry points leave the default.  A user segment table is checked where its bins are counted
         (``n_segments``: it needs the shape of ``input_ids``)."""
@@ -141,7 +206,13 @@ class ReadOuts:
         if return_depth_lens and ids_shape is not None and int(ids_shape[0]) > MAX_LENS_ROWS:
             raise ValueError(f"return_depth_lens: at most {MAX_LENS_ROWS} clips per pass, got {int(ids_shape[0])}")
         return cls(bool(return_logprobs), cand, k or None, att, attention_segments if att else None, bool(return_token_attention),
-                   key_drop_mask(key_drop, ids_shape, att), rows, window, bool(return_depth_lens))
+                   key_drop_mask(key_drop, ids_shape, att), rows, window, bool(return_depth_lens),
+                   *stream_options(return_stream, stream_depths, stream_patch, ids_shape, n_layers))
+
+    @property
+    def touches_stream(self) -> bool:
+        """A capture or a patch of the residual stream: such a call runs eagerly under graph replay, as a masked call does."""
+        return self.stream_rows is not None or self.stream_patch is not None
 
     @property
     def wants_labels(self) -> bool:
@@ -162,7 +233,8 @@ class ReadOuts:
         """What the record appends to a graph's host key (``n_seg``: ``n_segments`` when the caller has it already).  Nothing for an option
         that is off: the keys of passes without it are those they always were.  The candidates' VALUES and a user segment table are graph
         INPUT, not key; the candidates' number is in the key with the device inputs' shapes.  k, a user table's bin count (the default
-        table follows from the ids, which are in the key) and ld_tok = N are output shapes: another value is another graph."""
+        table follows from the ids, which are in the key) and ld_tok = N are output shapes: another value is another graph.  ``key_drop`` and
+        the stream options add nothing: such calls are never captured."""
         S = (self.n_segments(ids_shape) if n_seg is None else n_seg) if self.score_attention else 0
         on = ((self.logprobs, "logprobs"), (self.cand is not None, "candidates"), (self.topk is not None, ("top_logprobs", self.topk)),
               (self.score_attention, ("score_attention", S)), (self.token_attention, ("score_attention_tokens", int(ids_shape[1]))),
@@ -182,7 +254,8 @@ def forward_kwargs(r: ReadOuts) -> dict:
     ``forward``'s call form, which need not know the options it is not asked for."""
     kw = dict(return_logprobs=r.logprobs or None, candidate_ids=r.cand, top_logprobs=r.topk, return_score_attention=r.score_attention or None,
               attention_segments=r.segments, return_token_attention=r.token_attention or None, key_drop=r.key_drop,
-              key_drop_rows=r.key_drop_rows, key_drop_layers=r.key_drop_layers, return_depth_lens=r.depth_lens or None)
+              key_drop_rows=r.key_drop_rows, key_drop_layers=r.key_drop_layers, return_depth_lens=r.depth_lens or None,
+              return_stream=r.stream_rows, stream_depths=r.stream_depths, stream_patch=r.stream_patch)
     return {k: v for k, v in kw.items() if v is not None}
 
 

@@ -183,7 +183,7 @@ class ScoringPass:
         return pinned.to(self.device, non_blocking=True)
 
     def _prefill(self, ids_packed, slot, cu, vis, n_vis, motion, score_rows, logit_rows, keep_kv=False, kv_cap=0, probe=None, ld_tok=0, drop_words=None,
-                 drop_row_words=None, drop_layers=None, lens=None):
+                 drop_row_words=None, drop_layers=None, lens=None, stream_capture=None, stream_patch=None):
         b = len(cu) - 1
         T = cu[-1]
         lib, ctx = self._native(n_tokens=T, n_clips=b, out_rows=len(logit_rows), kv_cap=kv_cap)
@@ -210,6 +210,11 @@ class ScoringPass:
             l_score, l_token, l_hidden, l_normed, l_out = lens
             native.check(lib.aigv_depth_lens_arm(ctx, native.i32_array(l_score) if l_score else None, len(l_score), native.i32_array(l_token) if l_token else None,
                                                  len(l_token), l_hidden.data_ptr(), l_normed.data_ptr(), native.ptr(l_out)), ctx)
+        for armed, arm in ((stream_patch, lib.aigv_stream_patch_arm), (stream_capture, lib.aigv_stream_capture_arm)):
+            if armed is not None:       # stream_patch / return_stream: (packed rows, lo, hi, device bf16 [n, hi - lo, H]) - armed for exactly the pass below, which disarms
+                s_rows, lo, hi, buf = armed     # (s_rows: host int32 tensor, read in place - the library copies the numbers on arming)
+                native.check(arm(ctx, C.cast(s_rows.data_ptr(), native._I32P) if s_rows.numel() else None, int(s_rows.numel()), int(lo), int(hi),
+                                 native.ptr(buf) if buf.numel() else None), ctx)
         native.check(lib.aigv_llm_prefill(
             ctx, ids_d.data_ptr(), slot_d.data_ptr(), cu_a, b, native.ptr(vis), n_vis, native.ptr(motion),
             sr_a, native.ptr(score), lr_a, len(logit_rows), amax.data_ptr(), int(keep_kv), native.stream_ptr()), ctx)
@@ -424,6 +429,34 @@ class ScoringPass:
             out["lens_cand_logprob"] = cl
         return out
 
+    # ---- activation patching (return_stream / stream_patch) -------------------------------------------------------------------------------
+    @staticmethod
+    def _stream_rows(plan, mask: torch.Tensor):
+        """A host bool mask [B, N] -> (host int32 [n]: the packed rows of the selected tokens the pass runs, ascending; host int64 [n, 2]: their
+        (clip, position), clip-major and position-ascending - the same order).  Padded positions and a dropped dead tail are skipped through the
+        plan's ``row_of``."""
+        sel = mask & (plan["row_of"] >= 0)
+        return plan["row_of"][sel].to(torch.int32).contiguous(), sel.nonzero().to(torch.long)
+
+    def _stream_patch_plan(self, plan, patch):
+        """``stream_patch`` checked against the plan, host work only -> None (an empty window or an empty selection: the plain pass) or (packed
+        rows, lo, hi, the values as given).  ValueError: the values' shape, a count mismatch (both counts), the first differing (clip, position)."""
+        rows, index = self._stream_rows(plan, patch.rows)
+        (lo, hi), v, H = patch.depths, patch.values, self.config.llm_config.hidden_size
+        if int(v.shape[2]) != H:
+            raise ValueError(f"stream_patch: values of width {int(v.shape[2])}, the residual stream has H = {H}")
+        n = int(rows.numel())
+        if int(v.shape[0]) != n:
+            raise ValueError(f"stream_patch: values hold {int(v.shape[0])} rows, the mask selects {n} tokens the pass runs")
+        if patch.index is not None:
+            if int(patch.index.shape[0]) != n:
+                raise ValueError(f"stream_patch: index holds {int(patch.index.shape[0])} pairs, the mask selects {n} tokens the pass runs")
+            differ = (patch.index != index).any(1).nonzero().flatten()
+            if differ.numel():
+                i = int(differ[0])
+                raise ValueError(f"stream_patch: pair {i} of index is (clip, position) = {tuple(patch.index[i].tolist())}, the pass's is {tuple(index[i].tolist())}")
+        return (rows, lo, hi, v) if n and hi > lo else None
+
     def forward(self, mos: Optional[torch.Tensor] = None, pixel_values: Optional[torch.Tensor] = None,
                 input_ids: Optional[torch.Tensor] = None, attention_mask: Optional[torch.Tensor] = None,
                 position_ids=None, image_flags: Optional[torch.Tensor] = None, past_key_values=None,
@@ -432,7 +465,8 @@ class ScoringPass:
                 visual_tokens: Optional[torch.Tensor] = None, full_logits: bool = False, return_logprobs: bool = False,
                 candidate_ids=None, top_logprobs: Optional[int] = None, return_score_attention: bool = False, attention_segments=None,
                 return_token_attention: bool = False, key_drop: Optional[torch.Tensor] = None, key_drop_rows: Optional[torch.Tensor] = None,
-                key_drop_layers: Optional[tuple] = None, return_depth_lens: bool = False):
+                key_drop_layers: Optional[tuple] = None, return_depth_lens: bool = False, return_stream: Optional[torch.Tensor] = None,
+                stream_depths: Optional[tuple] = None, stream_patch: Optional[readouts.StreamPatch] = None):
         """Stage-2 eval pass (modeling_internvl_chat.py:306-488) or, with ``stage=1``, the stage-1 pass
         (internvl_chat_eval1/modeling_internvl_chat.py:250-366).  ``visual_tokens`` optionally supplies
         already all-gathered pre-projector tokens (frame-DP) instead of ``pixel_values``.
@@ -513,7 +547,26 @@ class ScoringPass:
         The lens reads the stream, not the attention: no other output changes a bit, and it combines with every other option, ``key_drop``
         and its qualifiers (the lens of the masked pass) and the probe included.  At most 64 clips per pass.  Under graph replay the flag is
         part of the graph's key; with ``key_drop`` the call runs eagerly as it does without the lens.  ``eval_utils.settling_depth`` folds
-        ``lens_score`` to the depth from which the score stays put."""
+        ``lens_score`` to the depth from which the score stays put.
+
+        ``return_stream`` / ``stream_patch`` - WHERE THE QUALITY LIVES (activation patching, causal tracing): rows of the residual stream copied out
+        of the pass, or overwritten in it, by depth.  Depth d, 0 <= d < L, is the stream layer d CONSUMES: d = 0 the embedding with the visual and
+        motion tokens in place, depth d the stream after d layers (the lens' numbering; depth L is not offered - the lens reads it).
+        ``return_stream`` (bool or integer tensor [B, N] laid out like ``input_ids``, on any device) with ``stream_depths=(lo, hi)`` (default (0,
+        L)) adds ``stream`` (bf16 [n, hi - lo, H]: the selected tokens' rows at the depths lo <= d < hi) and ``stream_index`` (int64 [n, 2]: each
+        one's (clip, position), clip-major and position-ascending).  Padded positions and tokens the pass does not run (the dead tail behind a
+        clip's last consumed row) are skipped: ``stream_index`` says what was captured; an empty selection gives n = 0.
+        ``stream_patch=readouts.StreamPatch(rows, values, depths, index=None)``: immediately before each layer d of ``depths`` = (lo, hi) runs, the
+        rows of the tokens ``rows`` selects are overwritten with ``values`` (bf16 [n, hi - lo, H], on the device or the host, laid out exactly like
+        the ``stream`` a capture with that mask and those depths returns) - a bit copy: NaN and Inf payloads travel unchanged.  What the reference
+        computes when a forward pre-hook on ``language_model.model.layers[d]`` assigns ``hidden_states[b, pos] = value``.  Every output -
+        ``score1``, ``logit``, the log-probability read-outs, the lens, a capture (which reads the stream as the layer consumes it, after the
+        patch) - is that of the patched pass.  ValueError, before anything is launched: a wrong shape or window, ``stream_depths`` without
+        ``return_stream``, n other than the number of selected tokens the pass runs (both counts are named), and - with ``index``, a donor's
+        ``stream_index`` - the first (clip, position) pair that differs from the recipient's.  An empty window or selection gives the plain
+        pass's bits.  Steering: capture a row, add a direction in torch, patch it back.  The two options combine with each other and with every
+        other option, fp8 mode included.  With graph replay enabled a call carrying either runs eagerly and captures nothing, as a masked call
+        does.  ``eval_utils.causal_trace`` runs the donor / recipient sweep over token groups and depth windows."""
         if position_ids is not None or past_key_values is not None:
             raise NotImplementedError("the eval pass takes default positions and no cache, like the reference drivers")
         if self.img_context_token_id is None:
@@ -528,6 +581,12 @@ class ScoringPass:
                                                          full_logits), kd, kd_rows)
             if kd_rows is not None:
                 drop_words, drop_row_words = drop_words
+        _, _, patch = readouts.stream_options(return_stream, stream_depths, stream_patch, None if input_ids is None else input_ids.shape, n_layers)
+        patch_plan = patched = None
+        if patch is not None:           # likewise: counts and pairs against the plan (host work only; the eager pass below, which such a call takes, reuses it)
+            src = visual_tokens if visual_tokens is not None else pixel_values
+            patch_plan = self._plan(input_ids, attention_mask, labels, image_flags, (src.tokens if isinstance(src, VisualAhead) else src).shape[0], full_logits)
+            patched = self._stream_patch_plan(patch_plan, patch)
         if return_depth_lens and self._capture_keep is None:      # likewise: is there a row to read?  (inside a capture the call that led here has checked)
             src = visual_tokens if visual_tokens is not None else pixel_values
             self._depth_lens_rows(self._plan(input_ids, attention_mask, labels, image_flags, (src.tokens if isinstance(src, VisualAhead) else src).shape[0], full_logits),
@@ -536,12 +595,13 @@ class ScoringPass:
         parse = lambda: readouts.ReadOuts.parse(self.config.llm_config.vocab_size, labels, return_logprobs, candidate_ids, top_logprobs,
                                                 return_score_attention, attention_segments, return_token_attention, key_drop,
                                                 None if input_ids is None else input_ids.shape, key_drop_rows, key_drop_layers, n_layers,
-                                                return_depth_lens)
+                                                return_depth_lens, return_stream, stream_depths, stream_patch)
         ro = None
         if self._graph_replay_enabled and self._capture_keep is None:
             ro = parse()
             # (a masked call stays eager and leaves the graph cache as it is: capturing masked passes is out of scope)
-            out = None if ro.key_drop is not None else self._forward_through_graph(mos, pixel_values, input_ids, attention_mask, image_flags, labels,
+            # (so does a call that captures or patches the residual stream)
+            out = None if ro.key_drop is not None or ro.touches_stream else self._forward_through_graph(mos, pixel_values, input_ids, attention_mask, image_flags, labels,
                                                                                   motion_feature, visual_tokens, full_logits, ro)
             if out is not None:
                 return out
@@ -549,7 +609,7 @@ class ScoringPass:
         n_frames = visual_tokens.shape[0] if visual_tokens is not None else pixel_values.shape[0]
         # ---- index bookkeeping first, on the host (one small D2H copy if the ids live on the device), so that
         # every kernel of the step can then be enqueued back to back without a host sync in between ----
-        plan = self._plan(input_ids, attention_mask, labels, image_flags, n_frames, full_logits)
+        plan = patch_plan if patch_plan is not None else self._plan(input_ids, attention_mask, labels, image_flags, n_frames, full_logits)
         ro = ro or parse()      # (once per call; on the eager path behind the plan's own checks, where the options have always been checked)
         lp_labels = self._logprob_labels(plan) if ro.wants_labels else None
         lens_rows = self._depth_lens_rows(plan, labels is not None) if ro.depth_lens else None
@@ -560,14 +620,24 @@ class ScoringPass:
         vit_embeds, motion = self._visual_inputs(pixel_values, visual_tokens, motion_feature, plan)
         probe = self._score_attention_probe(plan, input_ids, ro) if ro.score_attention else None
         lens = None if lens_rows is None else self._depth_lens_buffers(lens_rows[0], lens_rows[2])
+        capture = stream_index = None
+        if ro.stream_rows is not None:          # return_stream: the buffer the pass fills, [n, hi - lo, H]
+            cap_rows, stream_index = self._stream_rows(plan, ro.stream_rows)
+            lo, hi = ro.stream_depths
+            capture = (cap_rows, lo, hi, torch.empty((int(cap_rows.numel()), hi - lo, self.config.llm_config.hidden_size), dtype=torch.bfloat16, device=self.device))
+        if patched is not None:             # stream_patch, checked against this very plan on the way in: the values go up (or stay) on the device
+            patched = patched[:3] + (self._h2d(patched[3].detach().contiguous()),)
         score, amax, *armed = self._prefill(plan["ids_packed"], plan["slot"], plan["cu"], vit_embeds, plan["n_vis"], motion,
                                             plan["score_rows"], plan["logit_rows"], probe=probe, ld_tok=N if ro.token_attention else 0,
-                                            drop_words=drop_words, drop_row_words=drop_row_words, drop_layers=kd_layers, lens=lens)
+                                            drop_words=drop_words, drop_row_words=drop_row_words, drop_layers=kd_layers, lens=lens,
+                                            stream_capture=capture if capture is not None and capture[3].numel() else None, stream_patch=patched)
         att, tok = armed or (None, None)        # (_prefill hands the probe's tensors back only when it armed one)
         reads = self._read_rows(B if score is not None else 0, len(plan["logit_rows"]), ro, lp_labels)
         out = self._outputs(plan, B, N, score, amax, mos, reads, att, tok)
         if lens is not None:
             out.update(self._depth_lens_outputs(B, lens, lens_rows[1], ro, labels is not None))
+        if capture is not None:
+            out.update(stream=capture[3], stream_index=self._h2d(stream_index))
         return out
 
     def dp_front(self, frames_local: torch.Tensor, frames_clips: Optional[torch.Tensor], n_clips: int):

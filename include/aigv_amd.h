@@ -48,7 +48,8 @@ extern "C" {
                                 prefill attention (aigv_key_drop_arm, aigv_op_attention_drop), then by the key-drop form of the decode attention
                                 (aigv_op_attention_decode_drop; the mask now travels with the KV cache: aigv_key_drop_arm), then by the
                                 key-drop mask by query row and layer window (aigv_key_drop_arm_ex, aigv_op_attention_drop_rows), then by the
-                                depth lens (aigv_depth_lens_arm, aigv_depth_lens_token_readout, aigv_op_lens_tap, aigv_op_score_head_groups)
+                                depth lens (aigv_depth_lens_arm, aigv_depth_lens_token_readout, aigv_op_lens_tap, aigv_op_score_head_groups),
+                                then by activation patching (aigv_stream_capture_arm, aigv_stream_patch_arm, aigv_op_stream_rows)
                                 - added symbols only: a library without them is refused at load
                                 time, "missing <name>" */
 
@@ -262,6 +263,25 @@ int aigv_depth_lens_arm(aigv_ctx* ctx, const int32_t* score_rows_host, int n_sco
  *                    aigv_out_row_cand_logprob's bits. */
 int aigv_depth_lens_token_readout(aigv_ctx* ctx, const void* normed_rows_dev, int ld, int n_rows, const int64_t* cand_ids, int C, int64_t* top_id,
                                   float* top_logprob, float* cand_logprob, void* stream);
+
+/* Activation patching: copy rows of the residual stream out of a pass (capture) or overwrite them in it (patch), by depth.  Each arms exactly the
+ * next aigv_llm_prefill, which disarms on every way out.  With L = llm_layers, depth d, 0 <= d < L, is the stream layer d CONSUMES - d = 0 the
+ * embedding with the visual and motion tokens in place, depth d the stream after d layers: the depth lens' numbering.  Depth L is not offered.
+ *   rows_host   HOST int32 [n]: packed row numbers in score_rows' convention, copied here (the array need not outlive the call).  The pass checks
+ *               them: each inside [0, T) of its T packed rows, strictly ascending (so a patch's rows are unique); 0 <= n <= max_tokens.
+ *   lo, hi      the window: depths lo <= d < hi, 0 <= lo <= hi <= L (checked by the pass).
+ *   out_bf16_dev / values_bf16_dev   DEVICE bf16 [n][hi - lo][H], 16-byte aligned, the caller's, alive until the pass has run: element (i, d - lo)
+ *               holds row rows_host[i] at depth d.  May be NULL when n = 0 or the window is empty (nothing is then launched).
+ * At the top of layer d the pass first writes the patch's rows over the stream - a bit copy, no arithmetic: NaN and Inf payloads travel unchanged,
+ * and every later layer, read-out and head sees the patched stream - then reads the capture's rows from it, so a capture armed beside a patch
+ * returns the stream as the layer consumes it.  One launch each per armed layer; the row numbers go to a buffer the context owns (sized by
+ * max_tokens): nothing is allocated in the pass.  An unarmed pass takes two untaken branches per layer and enters no new code.  Both combine with
+ * aigv_key_drop_arm / _ex, the score-attention probe, aigv_depth_lens_arm and fp8 mode.
+ * Refused with AIGV_ERR_ARG and a message, nothing armed: a null context, n outside 0..max_tokens, a null row list, a null or misaligned buffer.
+ * Refused by the pass, before any launch: a row outside [0, T), rows not strictly ascending, a window outside [0, L], keep_kv; aigv_llm_extend
+ * refuses an armed context. */
+int aigv_stream_capture_arm(aigv_ctx* ctx, const int32_t* rows_host, int n, int lo, int hi, void* out_bf16_dev);
+int aigv_stream_patch_arm(aigv_ctx* ctx, const int32_t* rows_host, int n, int lo, int hi, const void* values_bf16_dev);
 
 /* Replicate the n kept sequences `copies` times (cache slots [0, n) -> [n, 2n), ...; needs n * copies <= max_seqs): the copies can
  * then take DIFFERENT continuations in one aigv_llm_extend call over n * copies sequences (sequence c * n + b continues clip b),
@@ -640,6 +660,12 @@ int aigv_op_gather_rows(const void* src, int ld, const int32_t* idx, int n, void
 int aigv_op_scatter_rows(const void* src, const int32_t* idx, int n, void* dst, int ld, int H, void* stream);
 int aigv_op_cls_rows(const void* cls_pos, void* x, int n_frames, int tokens_per_frame, int H, void* stream);
 int aigv_op_write_ints(const int32_t* host, int n, int32_t* dst, void* stream);
+/* One launch of the activation-patching row copy, as a pass of T rows makes it for slice `depth` of a window of n_depths depths: rows_host (HOST
+ * int32 [n], checked as the pass checks them: inside [0, T), strictly ascending) are written to idx_dev (DEVICE int32 [n]); then, for i < n,
+ *   to_stream = 0 (capture): side[(i * n_depths + depth) * H ..] = stream_rows[rows[i] * ld ..]      to_stream = 1 (patch): the other way round
+ * - a bit copy of H bf16.  H a multiple of 8 in 8..16384, ld a multiple of 8 and >= H, both buffers 16-byte aligned, 0 <= depth < n_depths. */
+int aigv_op_stream_rows(void* stream_rows, int ld, int T, const int32_t* rows_host, int n, int32_t* idx_dev, void* side, int n_depths, int depth, int H,
+                        int to_stream, void* stream);
 
 /* Frame ingest: uint8 [F,H,W,3] RGB frames already at the model resolution -> bf16 NCHW
  * pixel_values = bf16((u/255 - mean[c]) / std[c])  (torchvision ToTensor + Normalize of dataset.py:267-274 and the
