@@ -163,6 +163,19 @@ struct aigv_ctx {
     bf16_t* buf = nullptr;   // device, the caller's: [rows.size()][hi - lo][H]
   } stream_cap, stream_patch;
   int32_t* l_streamidx = nullptr;   // device [2 * max_tokens]: the armed pass's patch rows | its capture rows
+  // head knock-out / head patching (aigv_head_scale_arm / aigv_head_patch_arm / aigv_head_capture_arm): armed for exactly the next aigv_llm_prefill.  Between
+  // the attention of layer li and its wo, on l_ao [T, n_heads * D]: first the scale (table row li, every head whose factor is not exactly 1), then the patch
+  // (lo <= li < hi: slice li - lo of its buffer over the heads of bits[li - lo]), then the capture (slice li - lo of its own buffer, every head) - so a
+  // capture returns what wo consumes.  rows: packed row numbers, copied on arming, checked by the pass; all_rows (the scale only): every row the pass runs
+  struct HeadRows {
+    bool armed = false, all_rows = false;
+    int lo = 0, hi = 0;
+    std::vector<int32_t> rows;
+    std::vector<uint64_t> bits;   // the patch: one mask per layer of the window (no list on arming: every head)
+    std::vector<float> scale;     // the scale: [llm_layers][llm_heads]
+    bf16_t* buf = nullptr;        // device, the caller's: [rows.size()][hi - lo][n_heads * D]
+  } head_cap, head_patch, head_scale;
+  int32_t* l_headidx = nullptr;   // device [3 * max_tokens]: the armed pass's head-scale rows | head-patch rows | head-capture rows
   // profiling
   bool prof = false;
   int gemm_cls = AIGV_PROF_GEMM;   // class the GEMM launches are booked under: AIGV_PROF_GEMM_VIT inside aigv_vit_forward / aigv_project
@@ -287,12 +300,13 @@ constexpr size_t SPLITK_MAX_FLOATS = (size_t)64 << 20;   // 256 MB of fp32 split
 int splitk_scratch(aigv_ctx* c, size_t need_floats, float** out);
 
 // ---- the score-row attention probe of an armed pass (probe.hip) --------------------------------------------------------------------
-// DisarmScope: the pass that finds the context armed - with the probe, with a key-drop mask (aigv_key_drop_arm), with the depth lens (aigv_depth_lens_arm), with a stream capture or patch (aigv_stream_capture_arm, aigv_stream_patch_arm) - disarms it on every way out.  probe_plan: the probe's arguments for this pass (rows
+// DisarmScope: the pass that finds the context armed - with the probe, with a key-drop mask (aigv_key_drop_arm), with the depth lens (aigv_depth_lens_arm), with a stream capture or patch (aigv_stream_capture_arm, aigv_stream_patch_arm), with a head capture, patch or scale (aigv_head_capture_arm, aigv_head_patch_arm, aigv_head_scale_arm) - disarms it on every way out.  probe_plan: the probe's arguments for this pass (rows
 // validated against cu; off_host: keys cached in front of every sequence, or null), built ONCE per pass; probe_layer: the launch of layer li.
 struct DisarmScope {
   aigv_ctx* c;
   explicit DisarmScope(aigv_ctx* c_) : c(c_) {}
-  ~DisarmScope() { c->probe.armed = false; c->drop.armed = false; c->lens.armed = false; c->stream_cap.armed = false; c->stream_patch.armed = false; }
+  ~DisarmScope() { c->probe.armed = false; c->drop.armed = false; c->lens.armed = false; c->stream_cap.armed = false; c->stream_patch.armed = false;
+                   c->head_cap.armed = false; c->head_patch.armed = false; c->head_scale.armed = false; }
 };
 int probe_plan(aigv_ctx* c, const char* op, const int32_t* cu, int B, const int32_t* off_host, ProbeArgs* out);
 int probe_layer(aigv_ctx* c, const ProbeArgs& plan, int li, bool cache, hipStream_t s);

@@ -206,6 +206,16 @@ hipError_t aigv_launch_scatter_rows(const bf16_t* src, const int32_t* idx, int n
 // copy.  H a multiple of 8 in 8..16384, ld a multiple of 8 and >= H, both buffers 16-byte aligned, 0 <= depth < n_depths: else hipErrorInvalidValue
 hipError_t aigv_launch_stream_rows(bf16_t* stream, int ld, const int32_t* idx, int n, bf16_t* side, int n_depths, int depth, int H, bool to_stream,
                                    hipStream_t s);
+// head knock-out / head patching: rows idx[i] (idx null, HEAD_SCALE only: rows 0 .. n - 1) of the attention output `ao` [.., n_heads * D] (leading
+// dimension ld) against slice `layer` of a side buffer whose element (i, l) sits at side + (i * n_layers + l) * n_heads * D.  Only the heads whose bit
+// of `heads` is set are read or written.  HEAD_CAPTURE: side = ao; HEAD_PATCH: ao = side (bit copies); HEAD_SCALE: ao = bf16(fp32(ao) * scale[h]) -
+// `scale` (HOST, n_heads floats) travels as a kernel argument, `side` is unused.  n_heads in 1..64, D 64 or 128, ld a multiple of 8 and >= n_heads * D,
+// the buffers 16-byte aligned, 0 <= layer < n_layers: else hipErrorInvalidValue
+#define AIGV_MAX_HEAD_BITS 64
+enum { HEAD_CAPTURE = 0, HEAD_PATCH = 1, HEAD_SCALE = 2 };
+struct HeadScales { float v[AIGV_MAX_HEAD_BITS]; };
+hipError_t aigv_launch_head_rows(bf16_t* ao, int ld, const int32_t* idx, int n, bf16_t* side, int n_layers, int layer, int n_heads, int D, int mode,
+                                 uint64_t heads, const float* scale, hipStream_t s);
 hipError_t aigv_launch_cls_rows(const bf16_t* cls_pos, bf16_t* x, int F, int tokens_per_frame, int H, hipStream_t s);
 // RoPE in place on the fused qkv rows: per kv group, slots 0..g (q heads and K) are rotated.
 // slots [first_rot, first_rot + n_rot) of every group are rotated in place (q heads + K: first_rot 0, n_rot g + 1; K only: g, 1)

@@ -624,6 +624,35 @@ int aigv_op_stream_rows(void* stream_rows, int ld, int T, const int32_t* rows_ho
   return 0;
 }
 
+// One launch of the head-rows kernel (aigv_head_capture_arm / aigv_head_patch_arm / aigv_head_scale_arm), as a pass of T rows makes it for slice `layer` of
+// a window of n_layers layers: rows_host - checked as the pass checks them - go to idx_dev (DEVICE int32 [n]) as kernel arguments; mode 0 copies the
+// selected heads of rows idx[i] of `ao` (leading dimension ld, H = n_heads * D) to side[(i * n_layers + layer) * H ..], mode 1 overwrites them from
+// there, mode 2 scales them by scale_host[h] (HOST float [n_heads]; side and n_layers / layer unused; rows_host null: rows 0 .. T - 1, idx_dev unused)
+int aigv_op_head_rows(void* ao, int ld, int T, const int32_t* rows_host, int n, int32_t* idx_dev, void* side, int n_layers, int layer, int n_heads, int D, int mode,
+                      uint64_t head_bits, const float* scale_host, void* stream) {
+  const char* op = "aigv_op_head_rows";
+  if (mode != HEAD_CAPTURE && mode != HEAD_PATCH && mode != HEAD_SCALE) return fail(nullptr, AIGV_ERR_ARG, "%s: mode %d is none of 0 (capture), 1 (patch), 2 (scale)", op, mode);
+  const bool scale = mode == HEAD_SCALE, every = scale && !rows_host;
+  if (n_heads < 1 || n_heads > AIGV_MAX_HEAD_BITS) return fail(nullptr, AIGV_ERR_ARG, "%s: %d heads outside 1..%d, what a head mask holds", op, n_heads, AIGV_MAX_HEAD_BITS);
+  if (D != 64 && D != 128) return fail(nullptr, AIGV_ERR_ARG, "%s: head dimension %d is neither 64 nor 128", op, D);
+  if (T < 0) return fail(nullptr, AIGV_ERR_ARG, "%s: T = %d rows: must not be negative", op, T);
+  if (every) n = T;
+  TRY(check_rows(op, ao, scale ? ao : side, rows_host, !every, n, n_heads * D, ld));
+  if (!every && !idx_dev) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+  if (scale) {
+    if (!scale_host) return fail(nullptr, AIGV_ERR_ARG, "%s: null scale table", op);
+    for (int h = 0; h < n_heads; ++h) if (scale_host[h] != scale_host[h]) return fail(nullptr, AIGV_ERR_ARG, "%s: scale[%d] is NaN", op, h);
+    n_layers = 1; layer = 0;
+  }
+  if (n_layers < 1 || layer < 0 || layer >= n_layers) return fail(nullptr, AIGV_ERR_ARG, "%s: layer %d outside the window of %d layers", op, layer, n_layers);
+  if (!every) {
+    TRY(stream_rows_check(nullptr, op, rows_host, n, T, 0, n_layers, n_layers));
+    HIPCHK(nullptr, aigv_launch_write_ints(rows_host, n, idx_dev, (hipStream_t)stream));
+  }
+  HIPCHK(nullptr, aigv_launch_head_rows((bf16_t*)ao, ld, every ? nullptr : idx_dev, n, (bf16_t*)side, n_layers, layer, n_heads, D, mode, head_bits, scale_host, (hipStream_t)stream));
+  return 0;
+}
+
 // x[f * tokens_per_frame, :H] = cls_pos[:H] for f < n_frames (x is dense [n_frames * tokens_per_frame, H])
 int aigv_op_cls_rows(const void* cls_pos, void* x, int n_frames, int tokens_per_frame, int H, void* stream) {
   const char* op = "aigv_op_cls_rows";

@@ -290,6 +290,7 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
   const bool lensing = c->lens.armed;    // aigv_depth_lens_arm: this pass taps the lens rows after the embedding and after every layer; disarmed likewise
   const bool patching = c->stream_patch.armed;    // aigv_stream_patch_arm: rows of the residual stream are overwritten in front of the armed layers; disarmed likewise
   const bool capturing = c->stream_cap.armed;     // aigv_stream_capture_arm: rows of the residual stream are copied out in front of the armed layers; disarmed likewise
+  const bool h_scaling = c->head_scale.armed, h_patching = c->head_patch.armed, h_capturing = c->head_cap.armed;   // aigv_head_*_arm: l_ao between the attention and wo; disarmed likewise
   DisarmScope disarm(c);
   if (!c->finalized) return fail(c, AIGV_ERR_STATE, "aigv_llm_prefill: call aigv_finalize_weights first");
   if (dropping && probing) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: a key-drop mask and the score-attention probe are both armed: the probe does not know the mask");
@@ -325,6 +326,26 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
   const aigv_ctx::StreamRows &sp = c->stream_patch, &sc = c->stream_cap;
   if (patching) TRY(stream_rows_check(c, "aigv_llm_prefill: the stream patch (aigv_stream_patch_arm)", sp.rows.data(), (int)sp.rows.size(), T, sp.lo, sp.hi, k.llm_layers));
   if (capturing) TRY(stream_rows_check(c, "aigv_llm_prefill: the stream capture (aigv_stream_capture_arm)", sc.rows.data(), (int)sc.rows.size(), T, sc.lo, sc.hi, k.llm_layers));
+  // head knock-out / head patching: likewise.  The scale's window is [0, L) (its table has a row per layer); a pass without output rows breaks out in
+  // front of its last attention, so it takes no head option whose window reaches layer L - 1
+  const aigv_ctx::HeadRows &hs = c->head_scale, &hp = c->head_patch, &hc = c->head_cap;
+  if (h_scaling || h_patching || h_capturing) {
+    const char* what = h_scaling ? "scale" : h_patching ? "patch" : "capture";
+    const char* arm = h_scaling ? "aigv_head_scale_arm" : h_patching ? "aigv_head_patch_arm" : "aigv_head_capture_arm";
+    if (keep_kv) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: keep_kv while a head %s is armed (%s): only a pass without a KV cache takes one", what, arm);
+    if (k.llm_heads > AIGV_MAX_HEAD_BITS || (c->head_dim != 64 && c->head_dim != 128))
+      return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: a head %s is armed (%s) on a model of %d heads x %d: at most %d heads of 64 or 128", what, arm, k.llm_heads, c->head_dim, AIGV_MAX_HEAD_BITS);
+    if (h_scaling && !hs.all_rows) TRY(stream_rows_check(c, "aigv_llm_prefill: the head scale (aigv_head_scale_arm)", hs.rows.data(), (int)hs.rows.size(), T, 0, k.llm_layers, k.llm_layers));
+    if (h_patching) TRY(stream_rows_check(c, "aigv_llm_prefill: the head patch (aigv_head_patch_arm)", hp.rows.data(), (int)hp.rows.size(), T, hp.lo, hp.hi, k.llm_layers));
+    if (h_capturing) TRY(stream_rows_check(c, "aigv_llm_prefill: the head capture (aigv_head_capture_arm)", hc.rows.data(), (int)hc.rows.size(), T, hc.lo, hc.hi, k.llm_layers));
+    if ((score ? B : 0) + R == 0 && c->trim_last_layer) {
+      const int last = k.llm_layers - 1;
+      bool scale_last = false;
+      if (h_scaling) for (int h = 0; h < k.llm_heads; ++h) scale_last |= hs.scale[(size_t)last * k.llm_heads + h] != 1.0f;
+      const bool reaches = scale_last || (h_patching && hp.lo <= last && last < hp.hi) || (h_capturing && hc.lo <= last && last < hc.hi);
+      if (reaches) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: a head option reaches layer %d and the pass has no output rows (n_out == 0): the last layer's attention does not run", last);
+    }
+  }
   // the depth lens: every lens row must be a consumed row [score rows | logit rows] - the last layer finishes only those; lens_at: its place among them
   const int n_lens = lensing ? c->lens.n_score + c->lens.n_token : 0;
   int32_t lens_at[2 * AIGV_MAX_LENS_ROWS];
@@ -362,6 +383,9 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
   };
   if (patching) HIPCHK(c, aigv_launch_write_ints(sp.rows.data(), (int)sp.rows.size(), c->l_streamidx, s));
   if (capturing) HIPCHK(c, aigv_launch_write_ints(sc.rows.data(), (int)sc.rows.size(), c->l_streamidx + k.max_tokens, s));
+  if (h_scaling && !hs.all_rows) HIPCHK(c, aigv_launch_write_ints(hs.rows.data(), (int)hs.rows.size(), c->l_headidx, s));
+  if (h_patching) HIPCHK(c, aigv_launch_write_ints(hp.rows.data(), (int)hp.rows.size(), c->l_headidx + k.max_tokens, s));
+  if (h_capturing) HIPCHK(c, aigv_launch_write_ints(hc.rows.data(), (int)hc.rows.size(), c->l_headidx + 2 * (size_t)k.max_tokens, s));
   if (lensing) {
     HIPCHK(c, aigv_launch_write_ints(c->lens.rows, n_lens, c->l_lensidx, s));
     HIPCHK(c, aigv_launch_write_ints(lens_at, n_lens, c->l_lensidx + 2 * AIGV_MAX_LENS_ROWS, s));
@@ -421,13 +445,25 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
       a.ldk = a.ldv = c->qkv_out; a.kv_head_stride = (g + 2) * D;
       a.max_len = max_len;
       const bool last_trim = trim && li == k.llm_layers - 1;
-      a.q_tail = last_trim ? q_tail : 0;
+      // (a head capture of the last layer reads rows the trimmed launch would skip: that one launch covers every row - in the causal kernel q_tail
+      // only skips blocks and waves, so the consumed rows keep their bits)
+      a.q_tail = last_trim && !(h_capturing && li >= hc.lo && li < hc.hi && !hc.rows.empty()) ? q_tail : 0;
       // the armed layers, the row-trimmed last one included; the others run the unmasked launch they always ran
       if (dropping && li >= c->drop.layer_begin && li < c->drop.layer_end) { a.key_drop = c->drop.words; a.ld_drop = c->drop.ld; a.drop_rows = c->drop.rows; }
       if (const char* m = aigv_attn_check(a, D)) return fail(c, AIGV_ERR_ARG, "%s", m);
       ProfScope ps(c, AIGV_PROF_ATTN_LLM, last_trim ? 0.0 : attn_flops, 2.0 * T * ((double)c->qkv_out + H), s);
       HIPCHK(c, aigv_launch_attention(a, D, s));
     }
+    // head knock-out / head patching: l_ao as wo consumes it - scale, then patch, then capture; at most one launch each (a table row of ones: none)
+    if (h_scaling)
+      HIPCHK(c, aigv_launch_head_rows(c->l_ao, H, hs.all_rows ? nullptr : c->l_headidx, hs.all_rows ? T : (int)hs.rows.size(), nullptr, 1, 0, k.llm_heads, D, HEAD_SCALE,
+                                      ~(uint64_t)0, hs.scale.data() + (size_t)li * k.llm_heads, s));
+    if (h_patching && li >= hp.lo && li < hp.hi)
+      HIPCHK(c, aigv_launch_head_rows(c->l_ao, H, c->l_headidx + k.max_tokens, (int)hp.rows.size(), hp.buf, hp.hi - hp.lo, li - hp.lo, k.llm_heads, D, HEAD_PATCH,
+                                      hp.bits[li - hp.lo], nullptr, s));
+    if (h_capturing && li >= hc.lo && li < hc.hi)
+      HIPCHK(c, aigv_launch_head_rows(c->l_ao, H, c->l_headidx + 2 * (size_t)k.max_tokens, (int)hc.rows.size(), hc.buf, hc.hi - hc.lo, li - hc.lo, k.llm_heads, D, HEAD_CAPTURE,
+                                      ~(uint64_t)0, nullptr, s));
     if ((trim || mixed) && li == k.llm_layers - 1) {
       // 64 rows at a time through the weight-streaming kernel in its fixed 4-slice form (p = 0: the same bits whatever the row count);
       // the finished rows collect in l_trim_h, in l_rowidx (mixed: l_rowidx2) order
@@ -550,6 +586,50 @@ int aigv_stream_patch_arm(aigv_ctx* c, const int32_t* rows_host, int n, int lo, 
   return stream_rows_arm("aigv_stream_patch_arm", c, c ? &c->stream_patch : nullptr, rows_host, n, lo, hi, const_cast<void*>(values_bf16_dev));
 }
 
+// Arm the next aigv_llm_prefill with a capture / a patch / a scale of per-head attention outputs (include/aigv_amd.h): the host arrays are copied here; rows
+// and windows are checked when that pass runs; the device buffer is the caller's.
+static int head_rows_arm(const char* op, aigv_ctx* c, aigv_ctx::HeadRows* st, const int32_t* rows_host, int n, int lo, int hi, void* buf_bf16_dev, bool need_buf) {
+  if (!c) return fail(c, AIGV_ERR_ARG, "%s: null context", op);
+  if (n < 0 || n > c->cfg.max_tokens) return fail(c, AIGV_ERR_ARG, "%s: %d rows outside 0..max_tokens = %d", op, n, c->cfg.max_tokens);
+  if (n > 0 && !rows_host && need_buf) return fail(c, AIGV_ERR_ARG, "%s: null row list", op);
+  if (c->cfg.llm_heads > AIGV_MAX_HEAD_BITS) return fail(c, AIGV_ERR_ARG, "%s: the model has %d query heads: a head mask holds at most %d", op, c->cfg.llm_heads, AIGV_MAX_HEAD_BITS);
+  if (need_buf && n > 0 && hi > lo && (!buf_bf16_dev || ((uintptr_t)buf_bf16_dev & 15))) return fail(c, AIGV_ERR_ARG, "%s: the device buffer is null or not 16-byte aligned", op);
+  st->all_rows = !rows_host && !need_buf;
+  if (rows_host) st->rows.assign(rows_host, rows_host + n); else st->rows.clear();
+  st->lo = lo; st->hi = hi;
+  st->buf = (bf16_t*)buf_bf16_dev;
+  return 0;
+}
+
+int aigv_head_capture_arm(aigv_ctx* c, const int32_t* rows_host, int n, int lo, int hi, void* out_bf16_dev) {
+  TRY(head_rows_arm("aigv_head_capture_arm", c, c ? &c->head_cap : nullptr, rows_host, n, lo, hi, out_bf16_dev, true));
+  c->head_cap.armed = true;
+  return 0;
+}
+
+int aigv_head_patch_arm(aigv_ctx* c, const int32_t* rows_host, int n, int lo, int hi, const uint64_t* head_bits_host, const void* values_bf16_dev) {
+  TRY(head_rows_arm("aigv_head_patch_arm", c, c ? &c->head_patch : nullptr, rows_host, n, lo, hi, const_cast<void*>(values_bf16_dev), true));
+  const int w = hi > lo ? hi - lo : 0;
+  if (head_bits_host) c->head_patch.bits.assign(head_bits_host, head_bits_host + w); else c->head_patch.bits.assign(w, ~(uint64_t)0);
+  c->head_patch.armed = true;
+  return 0;
+}
+
+int aigv_head_scale_arm(aigv_ctx* c, const int32_t* rows_host, int n, const float* scale_host) {
+  const char* op = "aigv_head_scale_arm";
+  if (!c) return fail(c, AIGV_ERR_ARG, "%s: null context", op);
+  if (!scale_host) return fail(c, AIGV_ERR_ARG, "%s: null scale table", op);
+  const size_t cells = (size_t)c->cfg.llm_layers * c->cfg.llm_heads;
+  for (size_t i = 0; i < cells; ++i)
+    if (scale_host[i] != scale_host[i])
+      return fail(c, AIGV_ERR_ARG, "%s: scale[%d][%d] is NaN", op, (int)(i / c->cfg.llm_heads), (int)(i % c->cfg.llm_heads));
+  TRY(head_rows_arm(op, c, &c->head_scale, rows_host, rows_host ? n : 0, 0, 0, nullptr, false));
+  c->head_scale.scale.assign(scale_host, scale_host + cells);
+  c->head_scale.lo = 0; c->head_scale.hi = c->cfg.llm_layers;
+  c->head_scale.armed = true;
+  return 0;
+}
+
 // Continue the sequences kept by aigv_llm_prefill(keep_kv = 1) with new TEXT tokens: causal attention of the new rows over the
 // cached keys plus themselves.  commit = 0 leaves the cache lengths where they were, so several continuations of ONE prefix
 // (the four quality-perspective questions behind the same video tokens) can be scored one after the other.
@@ -560,7 +640,11 @@ int aigv_llm_extend(aigv_ctx* c, const int64_t* ids, const int32_t* cu, int B, c
   const bool dropping = c->drop.armed;
   const bool lensing = c->lens.armed;
   const bool patching = c->stream_patch.armed, capturing = c->stream_cap.armed;
+  const bool h_scaling = c->head_scale.armed, h_patching = c->head_patch.armed, h_capturing = c->head_cap.armed;
   DisarmScope disarm(c);
+  if (h_scaling || h_patching || h_capturing)
+    return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: a head %s is armed (%s): the continuation pass takes none, only aigv_llm_prefill does", h_scaling ? "scale" : h_patching ? "patch" : "capture",
+                h_scaling ? "aigv_head_scale_arm" : h_patching ? "aigv_head_patch_arm" : "aigv_head_capture_arm");
   if (patching || capturing)
     return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: a stream %s is armed (%s): the continuation pass takes none, only aigv_llm_prefill does", patching ? "patch" : "capture",
                 patching ? "aigv_stream_patch_arm" : "aigv_stream_capture_arm");

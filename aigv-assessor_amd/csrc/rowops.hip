@@ -265,6 +265,33 @@ __global__ __launch_bounds__(256) void stream_rows_kernel(bf16_t* __restrict__ s
   }
 }
 
+// Head knock-out and head patching (aigv_head_capture_arm / aigv_head_patch_arm / aigv_head_scale_arm): rows idx[i] (idx null: row i) of the
+// attention output ao [T, n_heads * D] - what wo consumes, head h in columns [h D, (h + 1) D) - against slice `layer` of a side buffer laid out
+// like the stream's, element (i, l) at side + (i * n_layers + l) * H.  One workgroup per row, 16-byte chunks; chunk c belongs to head (8 c) >> d_shift
+// (D = 1 << d_shift, 64 or 128: a chunk never straddles two heads), and a chunk whose head's bit of `heads` is clear is neither read nor written.
+// HEAD_CAPTURE: side = ao, HEAD_PATCH: ao = side - bit copies, a NaN or Inf payload travels unchanged; HEAD_SCALE: ao = bf16(fp32(ao) * scale[h]),
+// the Linear's rounding (f2bf; 0 * Inf = NaN as in torch) - the side buffer is not touched.  The scale factors are a kernel argument: no buffer, no copy.
+template <int MODE>
+__global__ __launch_bounds__(256) void head_rows_kernel(bf16_t* __restrict__ ao, int ld, const int32_t* __restrict__ idx, bf16_t* __restrict__ side,
+                                                        int n_layers, int layer, int H, int d_shift, uint64_t heads, const HeadScales scale) {
+  const int i = blockIdx.x;
+  bf16_t* arow = ao + (size_t)(idx ? idx[i] : i) * ld;
+  bf16_t* brow = MODE == HEAD_SCALE ? nullptr : side + ((size_t)i * n_layers + layer) * H;
+  for (int c = threadIdx.x; c < (H >> 3); c += 256) {
+    const int h = (c << 3) >> d_shift;
+    if (!((heads >> h) & 1)) continue;
+    if (MODE == HEAD_CAPTURE) *(u16x8*)(brow + (c << 3)) = *(const u16x8*)(arow + (c << 3));
+    else if (MODE == HEAD_PATCH) *(u16x8*)(arow + (c << 3)) = *(const u16x8*)(brow + (c << 3));
+    else {
+      const float f = scale.v[h];
+      u16x8 x = *(const u16x8*)(arow + (c << 3));
+#pragma unroll
+      for (int e = 0; e < 8; ++e) x[e] = f2bf(bf2f(x[e]) * f);
+      *(u16x8*)(arow + (c << 3)) = x;
+    }
+  }
+}
+
 // ---- RoPE in place (modeling_internlm2.py:247-261): out = bf16(bf16(x*cos) + bf16(rot(x)*sin)) ---------
 // qkv row layout: n_groups x slots_per_group x D; slots [0, n_rot) of every group are rotated (q heads + K).
 // cos/sin tables are [max_pos, D/2] bf16 (the second half of the reference's table repeats the first).
@@ -578,6 +605,28 @@ hipError_t aigv_launch_stream_rows(bf16_t* stream, int ld, const int32_t* idx, i
     return hipErrorInvalidValue;
   if (to_stream) hipLaunchKernelGGL(stream_rows_kernel<true>, dim3(n), dim3(256), 0, s, stream, ld, idx, side, n_depths, depth, H);
   else hipLaunchKernelGGL(stream_rows_kernel<false>, dim3(n), dim3(256), 0, s, stream, ld, idx, side, n_depths, depth, H);
+  return hipGetLastError();
+}
+
+hipError_t aigv_launch_head_rows(bf16_t* ao, int ld, const int32_t* idx, int n, bf16_t* side, int n_layers, int layer, int n_heads, int D, int mode,
+                                 uint64_t heads, const float* scale, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const int H = n_heads * D;
+  if (n_heads < 1 || n_heads > AIGV_MAX_HEAD_BITS || (D != 64 && D != 128) || ld % 8 || ld < H || !ao || ((uintptr_t)ao & 15)) return hipErrorInvalidValue;
+  if (mode == HEAD_SCALE ? !scale : (!idx || !side || ((uintptr_t)side & 15) || n_layers < 1 || layer < 0 || layer >= n_layers)) return hipErrorInvalidValue;
+  if (n_heads < 64) heads &= ((uint64_t)1 << n_heads) - 1;
+  const int d_shift = D == 64 ? 6 : 7;
+  HeadScales sc{};
+  if (mode == HEAD_SCALE)
+    for (int h = 0; h < n_heads; ++h) {
+      sc.v[h] = scale[h];
+      if (scale[h] == 1.0f) heads &= ~((uint64_t)1 << h);   // exactly 1: the head is not touched - no read, no write
+    }
+  if (!heads) return hipSuccess;   // no head selected (a scale table of ones): nothing is launched
+  if (mode == HEAD_CAPTURE) hipLaunchKernelGGL(head_rows_kernel<HEAD_CAPTURE>, dim3(n), dim3(256), 0, s, ao, ld, idx, side, n_layers, layer, H, d_shift, heads, sc);
+  else if (mode == HEAD_PATCH) hipLaunchKernelGGL(head_rows_kernel<HEAD_PATCH>, dim3(n), dim3(256), 0, s, ao, ld, idx, side, n_layers, layer, H, d_shift, heads, sc);
+  else if (mode == HEAD_SCALE) hipLaunchKernelGGL(head_rows_kernel<HEAD_SCALE>, dim3(n), dim3(256), 0, s, ao, ld, idx, side, 1, 0, H, d_shift, heads, sc);
+  else return hipErrorInvalidValue;
   return hipGetLastError();
 }
 

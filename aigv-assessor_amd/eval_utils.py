@@ -278,6 +278,28 @@ def restored_fraction(score, clean_score, corrupt_score):
     return torch.where(den == 0, torch.full_like(out, float("nan")), out)
 
 
+def _same_layout(where, model, clean, corrupt):
+    """The input checks of a donor / recipient sweep (``causal_trace``, ``head_trace``): equal shapes, equal ``attention_mask``, equal
+    ``<IMG_CONTEXT>`` positions, equal ``image_flags`` - else a ValueError that starts with ``where``.  -> (B, N)."""
+    import torch
+    ids, ids_c = clean["input_ids"], corrupt["input_ids"]
+    if tuple(ids.shape) != tuple(ids_c.shape):
+        raise ValueError(f"{where}: input_ids of shape {tuple(ids.shape)} (clean) and {tuple(ids_c.shape)} (corrupt): the two need one token layout")
+    B, N = (int(v) for v in ids.shape)
+    for key in ("pixel_values", "image_flags"):
+        if tuple(clean[key].shape) != tuple(corrupt[key].shape):
+            raise ValueError(f"{where}: {key} of shape {tuple(clean[key].shape)} (clean) and {tuple(corrupt[key].shape)} (corrupt)")
+    am, am_c = clean.get("attention_mask"), corrupt.get("attention_mask")
+    if (am is None) != (am_c is None) or (am is not None and not torch.equal(am.detach().cpu().bool(), am_c.detach().cpu().bool())):
+        raise ValueError(f"{where}: the clean and the corrupt attention_mask differ")
+    ctx_id = model.img_context_token_id
+    if not torch.equal(ids.detach().cpu() == ctx_id, ids_c.detach().cpu() == ctx_id):
+        raise ValueError(f"{where}: the clean and the corrupt input_ids have their <IMG_CONTEXT> tokens at different positions")
+    if not torch.equal(clean["image_flags"].detach().cpu(), corrupt["image_flags"].detach().cpu()):
+        raise ValueError(f"{where}: the clean and the corrupt image_flags differ")
+    return B, N
+
+
 def causal_trace(model, *, clean, corrupt, groups=None, width=1, stride=1, **readout_kwargs):
     """WHERE THE QUALITY LIVES: activation patching (causal tracing, Meng et al. 2022) between two clips that share a token layout.  ``clean`` (the
     donor) and ``corrupt`` (the recipient) are dicts of ``forward``'s inputs (``pixel_values``, ``input_ids``, ``attention_mask``, ``image_flags``,
@@ -294,21 +316,8 @@ def causal_trace(model, *, clean, corrupt, groups=None, width=1, stride=1, **rea
     (the corrupt clip's score under the patch) and ``restored`` = ``restored_fraction(score, clean_score, corrupt_score)``."""
     import torch
     from .readouts import StreamPatch
-    ids, ids_c = clean["input_ids"], corrupt["input_ids"]
-    if tuple(ids.shape) != tuple(ids_c.shape):
-        raise ValueError(f"causal_trace: input_ids of shape {tuple(ids.shape)} (clean) and {tuple(ids_c.shape)} (corrupt): the two need one token layout")
-    B, N = (int(v) for v in ids.shape)
-    for key in ("pixel_values", "image_flags"):
-        if tuple(clean[key].shape) != tuple(corrupt[key].shape):
-            raise ValueError(f"causal_trace: {key} of shape {tuple(clean[key].shape)} (clean) and {tuple(corrupt[key].shape)} (corrupt)")
-    am, am_c = clean.get("attention_mask"), corrupt.get("attention_mask")
-    if (am is None) != (am_c is None) or (am is not None and not torch.equal(am.detach().cpu().bool(), am_c.detach().cpu().bool())):
-        raise ValueError("causal_trace: the clean and the corrupt attention_mask differ")
-    ctx_id = model.img_context_token_id
-    if not torch.equal(ids.detach().cpu() == ctx_id, ids_c.detach().cpu() == ctx_id):
-        raise ValueError("causal_trace: the clean and the corrupt input_ids have their <IMG_CONTEXT> tokens at different positions")
-    if not torch.equal(clean["image_flags"].detach().cpu(), corrupt["image_flags"].detach().cpu()):
-        raise ValueError("causal_trace: the clean and the corrupt image_flags differ")
+    B, N = _same_layout("causal_trace", model, clean, corrupt)
+    ids, am = clean["input_ids"], clean.get("attention_mask")
     L = int(model.config.llm_config.num_hidden_layers)
     width, stride = int(width), int(stride)
     if not 1 <= width <= L or stride < 1:
@@ -350,7 +359,96 @@ def causal_trace(model, *, clean, corrupt, groups=None, width=1, stride=1, **rea
     return res
 
 
-def frame_ablation_generate(model, *, pixel_values, input_ids, attention_mask, image_flags, max_new_tokens, candidate_ids=None, **gen):
+def _head_grid(where, model, layers, heads):
+    L, nh = int(model.config.llm_config.num_hidden_layers), int(model.config.llm_config.num_attention_heads)
+    layers = list(range(L)) if layers is None else [int(l) for l in layers]
+    heads = list(range(nh)) if heads is None else [int(h) for h in heads]
+    if any(not 0 <= l < L for l in layers) or any(not 0 <= h < nh for h in heads):
+        raise ValueError(f"{where}: layers {layers} outside 0..{L - 1} or heads {heads} outside 0..{nh - 1}")
+    return L, nh, layers, heads
+
+
+def head_knockout(model, *, pixel_values, input_ids, attention_mask, image_flags, labels=None, layers=None, heads=None, rows=None, **readout_kwargs):
+    """WHICH HEADS matter: the head knock-out (Michel et al. 2019).  The batch is scored once as it is and once per (layer, head) with that head's
+    attention output multiplied by 0 in front of that layer's ``wo`` (``forward(head_scale=HeadScale(scale, rows))``, ``scale`` all ones but that
+    entry); every other head and layer stays.  ``layers`` / ``heads``: the layer and head numbers swept (default: all); ``rows``: an optional bool
+    [B, N] mask laid out like ``input_ids`` that restricts the knock-out to those query rows, e.g. ``model.segment_masks(...)["score_row"]``
+    (None: every row).  InternViT and the SlowFast branch run ONCE; their outputs are handed to every pass.  ``readout_kwargs``
+    (``motion_feature`` among them) go to every ``forward`` call.
+
+    Returns a dict: ``outs`` - the base result dict, then one per layer and head, layer-major; ``layers``; ``heads``; and for a stage-2 model
+    ``score1`` [B] (the base scores, fp32), ``knocked`` [B, L', n'] (the score with that head knocked out; NaN where ``rows`` selects no row of
+    the clip, ``flow_knockout``'s convention) and ``delta`` = ``score1[:, None, None] - knocked``: positive where the head raised the score."""
+    import torch
+    from .readouts import HeadScale
+    B = int(input_ids.shape[0])
+    L, nh, layers, heads = _head_grid("head_knockout", model, layers, heads)
+    rows = None if rows is None else rows.detach().to("cpu").bool()
+    readout_kwargs = dict(readout_kwargs)
+    motion_feature = readout_kwargs.pop("motion_feature", None)
+    if motion_feature is None:
+        motion_feature = model.motion_feature(pixel_values, B)
+    tokens = model.vit_tokens(pixel_values)
+    common = dict(input_ids=input_ids, attention_mask=attention_mask, image_flags=image_flags, labels=labels, visual_tokens=tokens,
+                  motion_feature=motion_feature, **readout_kwargs)
+    outs = [model.forward(**common)]
+    for l in layers:
+        for h in heads:
+            scale = torch.ones(L, nh)
+            scale[l, h] = 0.0
+            outs.append(model.forward(head_scale=HeadScale(scale, rows), **common))
+    res = {"outs": outs, "layers": layers, "heads": heads}
+    if "score1" in outs[0]:
+        base = outs[0]["score1"].float()
+        knocked = torch.stack([o["score1"].float() for o in outs[1:]], 1).view(B, len(layers), len(heads)) if len(outs) > 1 else base.new_zeros(B, len(layers), len(heads))
+        if rows is not None:
+            knocked = knocked.masked_fill((~rows.any(-1))[:, None, None].to(knocked.device), float("nan"))
+        res.update(score1=base, knocked=knocked, delta=base[:, None, None] - knocked)
+    return res
+
+
+def head_trace(model, *, clean, corrupt, layers=None, heads=None, rows=None, **readout_kwargs):
+    """WHICH HEADS carry the quality from one clip to another: head-level activation patching (path patching, Wang et al. 2022) between two clips
+    that share a token layout.  ``clean`` (the donor) and ``corrupt`` (the recipient) are dicts of ``forward``'s inputs under ``causal_trace``'s
+    conditions - anything else is a ValueError.  The clean batch runs once, capturing the head outputs of the tokens ``rows`` selects (bool [B, N];
+    default: every token the pass runs) at every layer (``forward(return_heads=...)``); the corrupt batch runs once as it is and once per (layer,
+    head) with that clean head patched in over those rows (``forward(head_patch=HeadPatch(rows, values, (l, l + 1), index, heads={h}))``).  The
+    corrupt clip's InternViT and SlowFast branch run ONCE.  ``readout_kwargs`` go to every ``forward`` call.
+
+    Returns a dict: ``outs`` - the clean result dict, the corrupt one, then one per layer and head, layer-major; ``layers``; ``heads``; and for a
+    stage-2 model ``clean_score`` / ``corrupt_score`` [B] (fp32), ``score`` [B, L', n'] (the corrupt clip's score under the patch) and
+    ``restored`` = ``restored_fraction(score, clean_score, corrupt_score)``."""
+    import torch
+    from .readouts import HeadPatch
+    B, N = _same_layout("head_trace", model, clean, corrupt)
+    L, nh, layers, heads = _head_grid("head_trace", model, layers, heads)
+    rows = torch.ones(B, N, dtype=torch.bool) if rows is None else rows.detach().to("cpu").bool()
+    if tuple(rows.shape) != (B, N):
+        raise ValueError(f"head_trace: rows has shape {tuple(rows.shape)}, input_ids {(B, N)}")
+    donor = model.forward(**clean, return_heads=rows, **readout_kwargs)                        # all layers: [n, L, n_heads, D]
+    index = donor["heads_index"].cpu()
+    pixel_values = corrupt["pixel_values"]
+    common = {k: v for k, v in corrupt.items() if k != "pixel_values"}
+    if common.get("motion_feature") is None:
+        common["motion_feature"] = model.motion_feature(pixel_values, B)
+    common.update(visual_tokens=model.vit_tokens(pixel_values), **readout_kwargs)
+    outs = [donor, model.forward(**common)]
+    for l in layers:
+        values = donor["heads"][:, l:l + 1].contiguous()
+        for h in heads:
+            only = torch.zeros(nh, dtype=torch.bool)
+            only[h] = True
+            outs.append(model.forward(head_patch=HeadPatch(rows, values, (l, l + 1), index, only), **common))
+    res = {"outs": outs, "layers": layers, "heads": heads}
+    if "score1" in outs[0]:
+        clean_score, corrupt_score = outs[0]["score1"].float(), outs[1]["score1"].float()
+        score = torch.stack([o["score1"].float() for o in outs[2:]], 1).view(B, len(layers), len(heads)) if len(outs) > 2 else clean_score.new_zeros(B, len(layers), len(heads))
+        res.update(score=score, clean_score=clean_score, corrupt_score=corrupt_score, restored=restored_fraction(score, clean_score, corrupt_score))
+    return res
+
+
+def frame_ablation_generate(
+model, *, pixel_values, input_ids, attention_mask, image_flags, max_new_tokens, candidate_ids=None, **gen):
     """WHAT IF a frame were not there, in WORDS: the reply to the stage-2 prompt as it is and once per unit with that unit's tokens hidden from
     the LLM (``generate_stage2(key_drop=model.unit_masks(...)[:, u])``) - unit u < F is frame u's visual tokens, unit F the motion token.
     InternViT and the SlowFast branch run ONCE; their outputs are handed to every call (``visual_tokens=``, ``motion_feature=``).  ``gen`` goes to

@@ -1,7 +1,8 @@
 """Which read-outs a scoring pass carries: label log-probs, candidate log-probs, top-k log-probs, score attention by segment and per token, the
-depth lens, a capture of residual-stream rows (``return_stream`` / ``stream_depths``) - and whether it runs under a key-drop mask (``key_drop`` with
-its qualifiers ``key_drop_rows`` / ``key_drop_layers``) or a patch of the stream (``stream_patch``): not read-outs, but per-call options that travel
-the same way.
+depth lens, a capture of residual-stream rows (``return_stream`` / ``stream_depths``) or of per-head attention outputs (``return_heads`` /
+``head_layers``) - and whether it runs under a key-drop mask (``key_drop`` with its qualifiers ``key_drop_rows`` / ``key_drop_layers``), a patch of the
+stream (``stream_patch``), a patch of head outputs (``head_patch``) or a per-head scale (``head_scale``): not read-outs, but per-call options that
+travel the same way.
 
 This module is the one place that knows that decision.  A new read-out adds, HERE: a member to ``ReadOuts`` and its check to
 ``ReadOuts.parse``; the element it appends to a graph's host key to ``ReadOuts.key_tail``; its keyword to ``forward_kwargs``; and - when it
@@ -163,6 +164,95 @@ def stream_options(return_stream=None, stream_depths=None, stream_patch=None, id
     return rows, window, patch
 
 
+MAX_HEADS = 64     # a head mask travels as one uint64 per layer
+
+
+@dataclass(frozen=True, eq=False)
+class HeadPatch:
+    """``forward(head_patch=...)``: overwrite per-head attention outputs - the row ``wo`` of a layer consumes.  ``rows``: bool or integer tensor [B, N]
+    laid out like ``input_ids`` - the tokens patched; ``layers`` = (lo, hi), 0 <= lo <= hi <= L; ``values``: bf16 [n, hi - lo, n_heads, D] on the
+    device or the host, laid out exactly like the ``heads`` that ``forward(return_heads=rows, head_layers=layers)`` returns; ``index``: optionally
+    the donor's ``heads_index`` (int64 [n, 2]), checked pair by pair against the recipient's; ``heads``: bool [n_heads] or [hi - lo, n_heads] - the
+    heads whose columns are overwritten (None: every head); an unselected head's values are not read."""
+    rows: torch.Tensor
+    values: torch.Tensor
+    layers: tuple
+    index: Optional[torch.Tensor] = None
+    heads: Optional[torch.Tensor] = None
+
+
+@dataclass(frozen=True, eq=False)
+class HeadScale:
+    """``forward(head_scale=...)``: multiply per-head attention outputs by a factor.  ``scale``: float tensor [L, n_heads] (taken to fp32 on the
+    host; no NaN) - head h of layer l becomes ``bf16(fp32(x) * scale[l, h])``, an entry that is exactly 1 leaves its head untouched, 0 knocks it
+    out; ``rows``: optional bool or integer tensor [B, N] - the query rows scaled (None: every row the pass runs)."""
+    scale: torch.Tensor
+    rows: Optional[torch.Tensor] = None
+
+
+def head_options(return_heads=None, head_layers=None, head_patch=None, head_scale=None, ids_shape=None, n_layers: Optional[int] = None,
+                 n_heads: Optional[int] = None, head_dim: Optional[int] = None):
+    """``return_heads`` / ``head_layers`` / ``head_patch`` / ``head_scale`` -> (None or a HOST bool mask [B, N], None or (lo, hi), None or a
+    ``HeadPatch`` whose ``rows`` is such a mask, whose ``layers`` is a checked pair, whose ``index`` is a HOST int64 [n, 2] and whose ``heads`` is a
+    HOST bool [hi - lo, n_heads] or None, None or a ``HeadScale`` whose ``scale`` is a HOST fp32 [L, n_heads] and whose ``rows`` is such a mask or
+    None).  Layer l, 0 <= l < L, names the input of that layer's ``wo``; ``head_layers`` defaults to (0, L) and needs ``return_heads``.  Shapes,
+    dtypes and windows are checked here (those that need the model's sizes only when they are given); counts and (clip, position) pairs where the
+    plan is (``ScoringPass._head_patch_plan``)."""
+    rows = window = patch = scale = None
+    if (return_heads is not None or head_patch is not None or head_scale is not None) and n_heads is not None and n_heads > MAX_HEADS:
+        raise ValueError(f"return_heads / head_patch / head_scale: the model has {n_heads} query heads, a head mask holds at most {MAX_HEADS}")
+    if return_heads is not None:
+        rows = _token_mask("return_heads", return_heads, ids_shape)
+        window = _depth_window("head_layers", head_layers, n_layers) if head_layers is not None else (0, n_layers) if n_layers is not None else None
+    elif head_layers is not None:
+        raise ValueError("head_layers: qualifies return_heads and needs one")
+    if head_patch is not None:
+        p = head_patch
+        if not isinstance(p, HeadPatch):
+            raise ValueError(f"head_patch: expected a readouts.HeadPatch, got {type(p).__name__}")
+        lo, hi = _depth_window("head_patch: layers", p.layers, n_layers)
+        v = p.values
+        if (not torch.is_tensor(v) or v.dtype != torch.bfloat16 or v.dim() != 4 or int(v.shape[1]) != hi - lo
+                or (n_heads is not None and int(v.shape[2]) != n_heads) or (head_dim is not None and int(v.shape[3]) != head_dim)):
+            raise ValueError(f"head_patch: values must be a bf16 tensor [n, hi - lo = {hi - lo}, n_heads{'' if n_heads is None else f' = {n_heads}'}, "
+                             f"D{'' if head_dim is None else f' = {head_dim}'}] laid out like captured heads, got "
+                             f"{tuple(v.shape) if torch.is_tensor(v) else type(v).__name__}{' ' + str(v.dtype) if torch.is_tensor(v) else ''}")
+        idx = p.index
+        if idx is not None:
+            if not torch.is_tensor(idx) or idx.is_floating_point() or idx.dtype == torch.bool or idx.dim() != 2 or int(idx.shape[1]) != 2:
+                raise ValueError("head_patch: index must be an integer tensor [n, 2] of (clip, position) pairs (a donor's heads_index)")
+            idx = idx.detach().to("cpu").to(torch.long).contiguous()
+        hm = p.heads
+        if hm is not None:
+            nh = int(v.shape[2])
+            if not torch.is_tensor(hm) or hm.dtype != torch.bool or tuple(hm.shape) not in ((nh,), (hi - lo, nh)):
+                raise ValueError(f"head_patch: heads must be a bool tensor [n_heads = {nh}] or [hi - lo = {hi - lo}, n_heads = {nh}], got "
+                                 f"{tuple(hm.shape) if torch.is_tensor(hm) else type(hm).__name__}{' ' + str(hm.dtype) if torch.is_tensor(hm) else ''}")
+            hm = hm.detach().to("cpu").expand(hi - lo, nh).contiguous()
+        patch = HeadPatch(_token_mask("head_patch: rows", p.rows, ids_shape), v, (lo, hi), idx, hm)
+    if head_scale is not None:
+        q = head_scale
+        if not isinstance(q, HeadScale):
+            raise ValueError(f"head_scale: expected a readouts.HeadScale, got {type(q).__name__}")
+        t = q.scale
+        if (not torch.is_tensor(t) or not t.is_floating_point() or t.dim() != 2 or (n_layers is not None and int(t.shape[0]) != n_layers)
+                or (n_heads is not None and int(t.shape[1]) != n_heads)):
+            raise ValueError(f"head_scale: scale must be a float tensor [L{'' if n_layers is None else f' = {n_layers}'}, "
+                             f"n_heads{'' if n_heads is None else f' = {n_heads}'}], got "
+                             f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}{' ' + str(t.dtype) if torch.is_tensor(t) else ''}")
+        t = t.detach().to("cpu").to(torch.float32).contiguous()
+        if torch.isnan(t).any():
+            l, h = torch.isnan(t).nonzero()[0].tolist()
+            raise ValueError(f"head_scale: scale[{l}, {h}] is NaN")
+        scale = HeadScale(t, None if q.rows is None else _token_mask("head_scale: rows", q.rows, ids_shape))
+    return rows, window, patch, scale
+
+
+def head_bits(heads: torch.Tensor) -> list:
+    """A HOST bool [n_layers, n_heads] -> one int per layer with bit h set where head h is selected (the C ABI's uint64 words)."""
+    return [sum(1 << h for h, on in enumerate(row) if on) for row in heads.tolist()]
+
+
 _NAN = float("nan")
 # every result laid out per label position, [B (N - 1)] + width: name in the result dict, the ``ReadOuts`` member that switches it on and gives
 # its trailing width (None: always there), dtype, fill wherever the row is not an answer row
@@ -190,12 +280,17 @@ class ReadOuts:
     stream_rows: Optional[torch.Tensor] = None      # return_stream: host bool [B, N], the tokens whose residual-stream rows are captured (forward only)
     stream_depths: Optional[tuple] = None           # (lo, hi): ... at the depths lo <= d < hi (None with stream_rows None)
     stream_patch: Optional[StreamPatch] = None      # rows of the stream overwritten in front of the layers of its window (forward only)
+    head_rows: Optional[torch.Tensor] = None        # return_heads: host bool [B, N], the tokens whose per-head attention outputs are captured (forward only)
+    head_layers: Optional[tuple] = None             # (lo, hi): ... at the layers lo <= l < hi (None with head_rows None)
+    head_patch: Optional[HeadPatch] = None          # head outputs overwritten between the attention and wo of the layers of its window (forward only)
+    head_scale: Optional[HeadScale] = None          # head outputs multiplied by a factor per (layer, head) (forward only)
 
     @classmethod
     def parse(cls, vocab: int, labels="given", return_logprobs: bool = False, candidate_ids=None, top_logprobs: Optional[int] = None,
               return_score_attention: bool = False, attention_segments=None, return_token_attention: bool = False, key_drop=None,
               ids_shape=None, key_drop_rows=None, key_drop_layers=None, n_layers: Optional[int] = None, return_depth_lens: bool = False,
-              return_stream=None, stream_depths=None, stream_patch=None) -> "ReadOuts":
+              return_stream=None, stream_depths=None, stream_patch=None, return_heads=None, head_layers=None, head_patch=None, head_scale=None,
+              n_heads: Optional[int] = None, head_dim: Optional[int] = None) -> "ReadOuts":
         """The record of a call's public keyword arguments, checked.  ``labels=None`` (``forward`` without labels) refuses candidates and top-k;
         the shared-prefix and generate entry points leave the default.  A user segment table is checked where its bins are counted
         (``n_segments``: it needs the shape of ``input_ids``)."""
@@ -207,12 +302,15 @@ class ReadOuts:
             raise ValueError(f"return_depth_lens: at most {MAX_LENS_ROWS} clips per pass, got {int(ids_shape[0])}")
         return cls(bool(return_logprobs), cand, k or None, att, attention_segments if att else None, bool(return_token_attention),
                    key_drop_mask(key_drop, ids_shape, att), rows, window, bool(return_depth_lens),
-                   *stream_options(return_stream, stream_depths, stream_patch, ids_shape, n_layers))
+                   *stream_options(return_stream, stream_depths, stream_patch, ids_shape, n_layers),
+                   *head_options(return_heads, head_layers, head_patch, head_scale, ids_shape, n_layers, n_heads, head_dim))
 
     @property
     def touches_stream(self) -> bool:
-        """A capture or a patch of the residual stream: such a call runs eagerly under graph replay, as a masked call does."""
-        return self.stream_rows is not None or self.stream_patch is not None
+        """A capture or a patch of the residual stream, or a capture, patch or scale of head outputs: such a call runs eagerly under graph replay, as
+        a masked call does."""
+        return (self.stream_rows is not None or self.stream_patch is not None or self.head_rows is not None or self.head_patch is not None
+                or self.head_scale is not None)
 
     @property
     def wants_labels(self) -> bool:
@@ -234,7 +332,7 @@ class ReadOuts:
         that is off: the keys of passes without it are those they always were.  The candidates' VALUES and a user segment table are graph
         INPUT, not key; the candidates' number is in the key with the device inputs' shapes.  k, a user table's bin count (the default
         table follows from the ids, which are in the key) and ld_tok = N are output shapes: another value is another graph.  ``key_drop`` and
-        the stream options add nothing: such calls are never captured."""
+        the stream and head options add nothing: such calls are never captured."""
         S = (self.n_segments(ids_shape) if n_seg is None else n_seg) if self.score_attention else 0
         on = ((self.logprobs, "logprobs"), (self.cand is not None, "candidates"), (self.topk is not None, ("top_logprobs", self.topk)),
               (self.score_attention, ("score_attention", S)), (self.token_attention, ("score_attention_tokens", int(ids_shape[1]))),
@@ -255,7 +353,8 @@ def forward_kwargs(r: ReadOuts) -> dict:
     kw = dict(return_logprobs=r.logprobs or None, candidate_ids=r.cand, top_logprobs=r.topk, return_score_attention=r.score_attention or None,
               attention_segments=r.segments, return_token_attention=r.token_attention or None, key_drop=r.key_drop,
               key_drop_rows=r.key_drop_rows, key_drop_layers=r.key_drop_layers, return_depth_lens=r.depth_lens or None,
-              return_stream=r.stream_rows, stream_depths=r.stream_depths, stream_patch=r.stream_patch)
+              return_stream=r.stream_rows, stream_depths=r.stream_depths, stream_patch=r.stream_patch,
+              return_heads=r.head_rows, head_layers=r.head_layers, head_patch=r.head_patch, head_scale=r.head_scale)
     return {k: v for k, v in kw.items() if v is not None}
 
 

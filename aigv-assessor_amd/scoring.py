@@ -183,7 +183,8 @@ class ScoringPass:
         return pinned.to(self.device, non_blocking=True)
 
     def _prefill(self, ids_packed, slot, cu, vis, n_vis, motion, score_rows, logit_rows, keep_kv=False, kv_cap=0, probe=None, ld_tok=0, drop_words=None,
-                 drop_row_words=None, drop_layers=None, lens=None, stream_capture=None, stream_patch=None):
+                 drop_row_words=None, drop_layers=None, lens=None, stream_capture=None, stream_patch=None, head_capture=None, head_patch=None,
+                 head_scale=None):
         b = len(cu) - 1
         T = cu[-1]
         lib, ctx = self._native(n_tokens=T, n_clips=b, out_rows=len(logit_rows), kv_cap=kv_cap)
@@ -215,6 +216,18 @@ class ScoringPass:
                 s_rows, lo, hi, buf = armed     # (s_rows: host int32 tensor, read in place - the library copies the numbers on arming)
                 native.check(arm(ctx, C.cast(s_rows.data_ptr(), native._I32P) if s_rows.numel() else None, int(s_rows.numel()), int(lo), int(hi),
                                  native.ptr(buf) if buf.numel() else None), ctx)
+        # head_scale / head_patch / return_heads: armed for exactly the pass below, which disarms (host arrays are read in place: the library copies them on arming)
+        i32p = lambda t: C.cast(t.data_ptr(), native._I32P) if t is not None and t.numel() else None
+        if head_scale is not None:      # (packed rows or None: every row, host fp32 [L, n_heads])
+            h_rows, table = head_scale
+            native.check(lib.aigv_head_scale_arm(ctx, i32p(h_rows), 0 if h_rows is None else int(h_rows.numel()), C.cast(table.data_ptr(), C.POINTER(C.c_float))), ctx)
+        if head_patch is not None:      # (packed rows, lo, hi, one mask word per layer or None: every head, device bf16 [n, hi - lo, n_heads, D])
+            h_rows, lo, hi, bits, buf = head_patch
+            native.check(lib.aigv_head_patch_arm(ctx, i32p(h_rows), int(h_rows.numel()), int(lo), int(hi), None if bits is None else (C.c_uint64 * len(bits))(*bits),
+                                                 native.ptr(buf) if buf.numel() else None), ctx)
+        if head_capture is not None:    # (packed rows, lo, hi, device bf16 [n, hi - lo, n_heads, D])
+            h_rows, lo, hi, buf = head_capture
+            native.check(lib.aigv_head_capture_arm(ctx, i32p(h_rows), int(h_rows.numel()), int(lo), int(hi), native.ptr(buf) if buf.numel() else None), ctx)
         native.check(lib.aigv_llm_prefill(
             ctx, ids_d.data_ptr(), slot_d.data_ptr(), cu_a, b, native.ptr(vis), n_vis, native.ptr(motion),
             sr_a, native.ptr(score), lr_a, len(logit_rows), amax.data_ptr(), int(keep_kv), native.stream_ptr()), ctx)
@@ -457,6 +470,28 @@ class ScoringPass:
                 raise ValueError(f"stream_patch: pair {i} of index is (clip, position) = {tuple(patch.index[i].tolist())}, the pass's is {tuple(index[i].tolist())}")
         return (rows, lo, hi, v) if n and hi > lo else None
 
+    # ---- head knock-out and head patching (return_heads / head_patch / head_scale) ------------------------------------------------------------
+    def _head_patch_plan(self, plan, patch):
+        """``head_patch`` checked against the plan, host work only -> None (an empty window, an empty selection or no head selected: the plain pass)
+        or (packed rows, lo, hi, one mask word per layer or None, the values as given).  ValueError: the values' shape, a count mismatch (both
+        counts), the first differing (clip, position)."""
+        rows, index = self._stream_rows(plan, patch.rows)
+        (lo, hi), v, l = patch.layers, patch.values, self.config.llm_config
+        if tuple(v.shape[2:]) != (l.num_attention_heads, l.head_dim):
+            raise ValueError(f"head_patch: values of {int(v.shape[2])} heads x {int(v.shape[3])}, the model has {l.num_attention_heads} x {l.head_dim}")
+        n = int(rows.numel())
+        if int(v.shape[0]) != n:
+            raise ValueError(f"head_patch: values hold {int(v.shape[0])} rows, the mask selects {n} tokens the pass runs")
+        if patch.index is not None:
+            if int(patch.index.shape[0]) != n:
+                raise ValueError(f"head_patch: index holds {int(patch.index.shape[0])} pairs, the mask selects {n} tokens the pass runs")
+            differ = (patch.index != index).any(1).nonzero().flatten()
+            if differ.numel():
+                i = int(differ[0])
+                raise ValueError(f"head_patch: pair {i} of index is (clip, position) = {tuple(patch.index[i].tolist())}, the pass's is {tuple(index[i].tolist())}")
+        bits = None if patch.heads is None else readouts.head_bits(patch.heads)
+        return (rows, lo, hi, bits, v) if n and hi > lo and (bits is None or any(bits)) else None
+
     def forward(self, mos: Optional[torch.Tensor] = None, pixel_values: Optional[torch.Tensor] = None,
                 input_ids: Optional[torch.Tensor] = None, attention_mask: Optional[torch.Tensor] = None,
                 position_ids=None, image_flags: Optional[torch.Tensor] = None, past_key_values=None,
@@ -466,7 +501,8 @@ class ScoringPass:
                 candidate_ids=None, top_logprobs: Optional[int] = None, return_score_attention: bool = False, attention_segments=None,
                 return_token_attention: bool = False, key_drop: Optional[torch.Tensor] = None, key_drop_rows: Optional[torch.Tensor] = None,
                 key_drop_layers: Optional[tuple] = None, return_depth_lens: bool = False, return_stream: Optional[torch.Tensor] = None,
-                stream_depths: Optional[tuple] = None, stream_patch: Optional[readouts.StreamPatch] = None):
+                stream_depths: Optional[tuple] = None, stream_patch: Optional[readouts.StreamPatch] = None, return_heads: Optional[torch.Tensor] = None,
+                head_layers: Optional[tuple] = None, head_patch: Optional[readouts.HeadPatch] = None, head_scale: Optional[readouts.HeadScale] = None):
         """Stage-2 eval pass (modeling_internvl_chat.py:306-488) or, with ``stage=1``, the stage-1 pass
         (internvl_chat_eval1/modeling_internvl_chat.py:250-366).  ``visual_tokens`` optionally supplies
         already all-gathered pre-projector tokens (frame-DP) instead of ``pixel_values``.
@@ -566,7 +602,27 @@ class ScoringPass:
         ``stream_index`` - the first (clip, position) pair that differs from the recipient's.  An empty window or selection gives the plain
         pass's bits.  Steering: capture a row, add a direction in torch, patch it back.  The two options combine with each other and with every
         other option, fp8 mode included.  With graph replay enabled a call carrying either runs eagerly and captures nothing, as a masked call
-        does.  ``eval_utils.causal_trace`` runs the donor / recipient sweep over token groups and depth windows."""
+        does.  ``eval_utils.causal_trace`` runs the donor / recipient sweep over token groups and depth windows.
+
+        ``return_heads`` / ``head_patch`` / ``head_scale`` - WHICH HEADS (head knock-out, Michel et al. 2019; head patching / path patching, Wang et
+        al. 2022): the per-head attention outputs of layer l, 0 <= l < L - the row that layer's ``wo`` consumes, bf16 [n_heads, D] per token, what a
+        forward pre-hook on ``layers[l].attention.wo`` sees - copied out, overwritten, or multiplied by a factor per head.  Inside a layer the
+        order is: attention, scale, patch, capture, ``wo``; a capture armed beside the other two returns what ``wo`` consumes, and every later
+        layer, the lens, a stream capture and all heads see the modified pass.  ``return_heads`` (bool or integer tensor [B, N] laid out like
+        ``input_ids``) with ``head_layers=(lo, hi)`` (default (0, L)) adds ``heads`` (bf16 [n, hi - lo, n_heads, D]) and ``heads_index`` (int64
+        [n, 2]); rows are selected exactly as ``return_stream`` selects them.  ``head_patch=readouts.HeadPatch(rows, values, layers, index=None,
+        heads=None)``: ``values`` laid out like a capture; only the columns of the heads ``heads`` selects (bool [n_heads] or [hi - lo, n_heads];
+        None: all) are overwritten - a bit copy, NaN payloads travel unchanged; an unselected head is neither read nor written.
+        ``head_scale=readouts.HeadScale(scale, rows=None)``: ``scale`` a float tensor [L, n_heads]; over the query rows ``rows`` selects (None:
+        every row the pass runs) head h of layer l becomes ``bf16(fp32(x) * scale[l, h])``, round to nearest even - what ``(x.float() *
+        s).to(torch.bfloat16)`` gives.  An entry that is exactly 1.0 leaves its head untouched; scale 0 is the head knock-out.  0 x Inf is NaN, as
+        in torch: a head whose output holds an Inf (or a NaN) is not silenced by a zero - as ``key_drop`` does not silence a NaN in a V row it
+        still reads.  A NaN in ``scale`` is a ValueError, as are a wrong shape or window, ``head_layers`` without ``return_heads``, a count
+        mismatch (both counts named), the first differing (clip, position) pair, and a model of more than 64 query heads - all before anything is
+        launched.  In the row-trimmed last layer a capture makes the attention launch cover every row (the consumed rows keep their bits), so a
+        capture never returns unwritten memory; a patch or scale of a row the last layer does not consume has no effect.  The options combine with
+        each other and with every other option, fp8 mode included; under graph replay a call carrying one runs eagerly.
+        ``eval_utils.head_knockout`` and ``eval_utils.head_trace`` run the sweeps over (layer, head)."""
         if position_ids is not None or past_key_values is not None:
             raise NotImplementedError("the eval pass takes default positions and no cache, like the reference drivers")
         if self.img_context_token_id is None:
@@ -587,6 +643,15 @@ class ScoringPass:
             src = visual_tokens if visual_tokens is not None else pixel_values
             patch_plan = self._plan(input_ids, attention_mask, labels, image_flags, (src.tokens if isinstance(src, VisualAhead) else src).shape[0], full_logits)
             patched = self._stream_patch_plan(patch_plan, patch)
+        llm = self.config.llm_config
+        _, _, h_patch, h_scale = readouts.head_options(return_heads, head_layers, head_patch, head_scale, None if input_ids is None else input_ids.shape, n_layers,
+                                                       llm.num_attention_heads, llm.head_dim)
+        h_patched = None
+        if h_patch is not None:         # likewise
+            if patch_plan is None:
+                src = visual_tokens if visual_tokens is not None else pixel_values
+                patch_plan = self._plan(input_ids, attention_mask, labels, image_flags, (src.tokens if isinstance(src, VisualAhead) else src).shape[0], full_logits)
+            h_patched = self._head_patch_plan(patch_plan, h_patch)
         if return_depth_lens and self._capture_keep is None:      # likewise: is there a row to read?  (inside a capture the call that led here has checked)
             src = visual_tokens if visual_tokens is not None else pixel_values
             self._depth_lens_rows(self._plan(input_ids, attention_mask, labels, image_flags, (src.tokens if isinstance(src, VisualAhead) else src).shape[0], full_logits),
@@ -595,12 +660,13 @@ class ScoringPass:
         parse = lambda: readouts.ReadOuts.parse(self.config.llm_config.vocab_size, labels, return_logprobs, candidate_ids, top_logprobs,
                                                 return_score_attention, attention_segments, return_token_attention, key_drop,
                                                 None if input_ids is None else input_ids.shape, key_drop_rows, key_drop_layers, n_layers,
-                                                return_depth_lens, return_stream, stream_depths, stream_patch)
+                                                return_depth_lens, return_stream, stream_depths, stream_patch, return_heads, head_layers, head_patch, head_scale,
+                                                llm.num_attention_heads, llm.head_dim)
         ro = None
         if self._graph_replay_enabled and self._capture_keep is None:
             ro = parse()
             # (a masked call stays eager and leaves the graph cache as it is: capturing masked passes is out of scope)
-            # (so does a call that captures or patches the residual stream)
+            # (so does a call that captures or patches the residual stream, or captures, patches or scales head outputs)
             out = None if ro.key_drop is not None or ro.touches_stream else self._forward_through_graph(mos, pixel_values, input_ids, attention_mask, image_flags, labels,
                                                                                   motion_feature, visual_tokens, full_logits, ro)
             if out is not None:
@@ -627,10 +693,23 @@ class ScoringPass:
             capture = (cap_rows, lo, hi, torch.empty((int(cap_rows.numel()), hi - lo, self.config.llm_config.hidden_size), dtype=torch.bfloat16, device=self.device))
         if patched is not None:             # stream_patch, checked against this very plan on the way in: the values go up (or stay) on the device
             patched = patched[:3] + (self._h2d(patched[3].detach().contiguous()),)
+        h_capture = heads_index = h_scaled = None
+        if ro.head_rows is not None:            # return_heads: the buffer the pass fills, [n, hi - lo, n_heads, D]
+            cap_rows, heads_index = self._stream_rows(plan, ro.head_rows)
+            lo, hi = ro.head_layers
+            h_capture = (cap_rows, lo, hi, torch.empty((int(cap_rows.numel()), hi - lo, llm.num_attention_heads, llm.head_dim), dtype=torch.bfloat16, device=self.device))
+        if h_patched is not None:
+            h_patched = h_patched[:4] + (self._h2d(h_patched[4].detach().contiguous()),)
+        if ro.head_scale is not None and bool((ro.head_scale.scale != 1).any()):      # (a table of ones: the plain pass)
+            s_rows = None if ro.head_scale.rows is None else self._stream_rows(plan, ro.head_scale.rows)[0]
+            if s_rows is None or s_rows.numel():
+                h_scaled = (s_rows, ro.head_scale.scale)
         score, amax, *armed = self._prefill(plan["ids_packed"], plan["slot"], plan["cu"], vit_embeds, plan["n_vis"], motion,
                                             plan["score_rows"], plan["logit_rows"], probe=probe, ld_tok=N if ro.token_attention else 0,
                                             drop_words=drop_words, drop_row_words=drop_row_words, drop_layers=kd_layers, lens=lens,
-                                            stream_capture=capture if capture is not None and capture[3].numel() else None, stream_patch=patched)
+                                            stream_capture=capture if capture is not None and capture[3].numel() else None, stream_patch=patched,
+                                            head_capture=h_capture if h_capture is not None and h_capture[3].numel() else None, head_patch=h_patched,
+                                            head_scale=h_scaled)
         att, tok = armed or (None, None)        # (_prefill hands the probe's tensors back only when it armed one)
         reads = self._read_rows(B if score is not None else 0, len(plan["logit_rows"]), ro, lp_labels)
         out = self._outputs(plan, B, N, score, amax, mos, reads, att, tok)
@@ -638,6 +717,8 @@ class ScoringPass:
             out.update(self._depth_lens_outputs(B, lens, lens_rows[1], ro, labels is not None))
         if capture is not None:
             out.update(stream=capture[3], stream_index=self._h2d(stream_index))
+        if h_capture is not None:
+            out.update(heads=h_capture[3], heads_index=self._h2d(heads_index))
         return out
 
     def dp_front(self, frames_local: torch.Tensor, frames_clips: Optional[torch.Tensor], n_clips: int):

@@ -49,7 +49,9 @@ extern "C" {
                                 (aigv_op_attention_decode_drop; the mask now travels with the KV cache: aigv_key_drop_arm), then by the
                                 key-drop mask by query row and layer window (aigv_key_drop_arm_ex, aigv_op_attention_drop_rows), then by the
                                 depth lens (aigv_depth_lens_arm, aigv_depth_lens_token_readout, aigv_op_lens_tap, aigv_op_score_head_groups),
-                                then by activation patching (aigv_stream_capture_arm, aigv_stream_patch_arm, aigv_op_stream_rows)
+                                then by activation patching (aigv_stream_capture_arm, aigv_stream_patch_arm, aigv_op_stream_rows),
+                                then by head knock-out and head patching (aigv_head_capture_arm, aigv_head_patch_arm, aigv_head_scale_arm,
+                                aigv_op_head_rows)
                                 - added symbols only: a library without them is refused at load
                                 time, "missing <name>" */
 
@@ -282,6 +284,32 @@ int aigv_depth_lens_token_readout(aigv_ctx* ctx, const void* normed_rows_dev, in
  * refuses an armed context. */
 int aigv_stream_capture_arm(aigv_ctx* ctx, const int32_t* rows_host, int n, int lo, int hi, void* out_bf16_dev);
 int aigv_stream_patch_arm(aigv_ctx* ctx, const int32_t* rows_host, int n, int lo, int hi, const void* values_bf16_dev);
+
+/* Head knock-out and head patching: the per-head attention outputs of a layer - the row its wo consumes, bf16 [n_heads][D] per token, head h in columns
+ * [h D, (h + 1) D) - copied out of a pass (capture), overwritten in it (patch) or multiplied by a factor per head (scale).  Each arms exactly the next
+ * aigv_llm_prefill, which disarms on every way out.  Inside layer l the order is: attention, scale, patch, capture, wo - so a capture armed beside the
+ * other two returns what wo consumes, and every later layer, the lens, a stream capture and all heads see the modified pass.
+ *   rows_host   HOST int32 [n]: packed row numbers, copied here; checked by the pass like a stream capture's (inside [0, T), strictly ascending);
+ *               0 <= n <= max_tokens.  aigv_head_scale_arm: NULL = every row the pass runs (n is then ignored).
+ *   lo, hi      the window: layers lo <= l < hi, 0 <= lo <= hi <= L (checked by the pass).
+ *   out_bf16_dev / values_bf16_dev   DEVICE bf16 [n][hi - lo][n_heads * D], 16-byte aligned, the caller's, alive until the pass has run: element
+ *               (i, l - lo) holds row rows_host[i] at layer l.  May be NULL when n = 0 or the window is empty.
+ *   head_bits_host   HOST uint64 [hi - lo], copied here: bit h of word l - lo selects head h at layer l; NULL = every head.  Only the selected heads'
+ *               columns are overwritten - a bit copy, NaN payloads travel unchanged; an unselected head's bytes are neither read nor written.
+ *   scale_host  HOST float [L][n_heads], copied here: the new value is bf16(fp32(x) * s), round to nearest even (0 * Inf = NaN).  An entry that is
+ *               exactly 1.0 leaves its head untouched (no read, no write); a layer whose row is all ones launches nothing.  Scale 0 knocks a head out.
+ * At most one launch each per armed layer; the row numbers go to a buffer the context owns, the factors travel as kernel arguments: nothing is
+ * allocated or copied in the pass.  An unarmed pass takes three untaken branches per layer.  A capture whose window holds layer L - 1 makes the
+ * row-trimmed last attention launch cover every row (the consumed rows keep their bits); a patch or scale of a row the trimmed layer does not consume
+ * has no consumer and is allowed.  All three combine with each other, aigv_key_drop_arm / _ex, the score-attention probe (it reads Q and K),
+ * aigv_depth_lens_arm, the stream capture / patch and fp8 mode (the ops act on the bf16 rows the e4m3 wo consumes).
+ * Refused with AIGV_ERR_ARG and a message, nothing armed: a null context, n outside 0..max_tokens, a null row list (capture, patch), a null or
+ * misaligned buffer, a model of more than 64 query heads, a null scale table, a NaN scale.  Refused by the pass, before any launch: a row outside
+ * [0, T), rows not strictly ascending, a window outside [0, L], keep_kv, a head dimension other than 64 or 128, a window (a scale row with a factor
+ * other than 1) that reaches layer L - 1 in a pass without output rows (its last attention does not run); aigv_llm_extend refuses an armed context. */
+int aigv_head_capture_arm(aigv_ctx* ctx, const int32_t* rows_host, int n, int lo, int hi, void* out_bf16_dev);
+int aigv_head_patch_arm(aigv_ctx* ctx, const int32_t* rows_host, int n, int lo, int hi, const uint64_t* head_bits_host, const void* values_bf16_dev);
+int aigv_head_scale_arm(aigv_ctx* ctx, const int32_t* rows_host, int n, const float* scale_host);
 
 /* Replicate the n kept sequences `copies` times (cache slots [0, n) -> [n, 2n), ...; needs n * copies <= max_seqs): the copies can
  * then take DIFFERENT continuations in one aigv_llm_extend call over n * copies sequences (sequence c * n + b continues clip b),
@@ -666,6 +694,13 @@ int aigv_op_write_ints(const int32_t* host, int n, int32_t* dst, void* stream);
  * - a bit copy of H bf16.  H a multiple of 8 in 8..16384, ld a multiple of 8 and >= H, both buffers 16-byte aligned, 0 <= depth < n_depths. */
 int aigv_op_stream_rows(void* stream_rows, int ld, int T, const int32_t* rows_host, int n, int32_t* idx_dev, void* side, int n_depths, int depth, int H,
                         int to_stream, void* stream);
+/* One launch of the head-rows kernel, as a pass of T rows makes it for slice `layer` of a window of n_layers layers, on ao [T][ld] with H = n_heads * D
+ * (n_heads in 1..64, D 64 or 128); rows_host as for aigv_op_stream_rows.  Only heads whose bit of head_bits is set are read or written.
+ *   mode 0 (capture): side[(i * n_layers + layer) * H ..] = ao[rows[i] * ld ..]      mode 1 (patch): the other way round      - bit copies
+ *   mode 2 (scale): ao[rows[i]] = bf16(fp32(ao[rows[i]]) * scale_host[h]) for the set heads whose factor is not exactly 1 (HOST float [n_heads], no
+ *   NaN); side, n_layers and layer are unused; rows_host NULL: rows 0 .. T - 1 (idx_dev unused). */
+int aigv_op_head_rows(void* ao, int ld, int T, const int32_t* rows_host, int n, int32_t* idx_dev, void* side, int n_layers, int layer, int n_heads, int D,
+                      int mode, uint64_t head_bits, const float* scale_host, void* stream);
 
 /* Frame ingest: uint8 [F,H,W,3] RGB frames already at the model resolution -> bf16 NCHW
  * pixel_values = bf16((u/255 - mean[c]) / std[c])  (torchvision ToTensor + Normalize of dataset.py:267-274 and the
