@@ -70,34 +70,11 @@ hipError_t aigv_launch_frame_ingest(const uint8_t* hwc, int n_frames, int H, int
 namespace {
 
 constexpr int PRECISION_BITS = 32 - 8 - 2;
+constexpr size_t RESIZE_MAX_ROW_LDS = 60 * 1024;   // the horizontal pass' staged source row: 16384 pixels are 48 KB
 
 __device__ __forceinline__ int clip8(int acc) {
   const int v = acc >> PRECISION_BITS;
   return v < 0 ? 0 : (v > 255 ? 255 : v);
-}
-
-// horizontal pass: in [F, in_h, in_w, 3] rows y_first .. y_first + rows - 1 -> tmp [F, rows, out_w, 3]
-__global__ __launch_bounds__(256) void resize_h_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ tmp, int in_h, int in_w,
-                                                       int out_w, int rows, int y_first, const int* __restrict__ bounds,
-                                                       const int* __restrict__ kk, int ksize, long total) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int xx = (int)(i % out_w);
-    const long fy = i / out_w;
-    const int y = (int)(fy % rows);
-    const long f = fy / rows;
-    const int xmin = bounds[2 * xx], n = bounds[2 * xx + 1];
-    const int* k = kk + (size_t)xx * ksize;
-    const uint8_t* p = in + ((size_t)(f * in_h + y_first + y) * in_w + xmin) * 3;
-    int s0 = 1 << (PRECISION_BITS - 1), s1 = s0, s2 = s0;
-    for (int x = 0; x < n; ++x) {
-      const int c = k[x];
-      s0 += (int)p[3 * x] * c;
-      s1 += (int)p[3 * x + 1] * c;
-      s2 += (int)p[3 * x + 2] * c;
-    }
-    uint8_t* o = tmp + (size_t)i * 3;
-    o[0] = (uint8_t)clip8(s0); o[1] = (uint8_t)clip8(s1); o[2] = (uint8_t)clip8(s2);
-  }
 }
 
 struct ResizeVArgs {
@@ -146,8 +123,8 @@ __global__ __launch_bounds__(256) void resize_v_kernel(const ResizeVArgs a) {
   }
 }
 
-// Fast forms (the generic kernels above stay as the fallback for odd sizes).
-// Horizontal: one source row per workgroup iteration staged in LDS with coalesced dword loads (the per-pixel taps are 39-57
+// Horizontal pass: in [F, in_h, in_w, 3] rows y_first .. y_first + rows - 1 -> tmp [F, rows, out_w, 3].  One source row per
+// workgroup iteration staged in LDS with coalesced dword loads (the per-pixel taps are 39-57
 // contiguous bytes at an arbitrary byte offset: from global memory that is one byte load per tap and lane), then every thread
 // produces output pixels from LDS.  `in_end` = one past the last input byte: the staging never reads beyond it.
 __global__ __launch_bounds__(256) void resize_h_lds_kernel(const uint8_t* __restrict__ in, const uint8_t* in_end, uint8_t* __restrict__ tmp,
@@ -189,7 +166,8 @@ __global__ __launch_bounds__(256) void resize_h_lds_kernel(const uint8_t* __rest
   }
 }
 
-// Vertical: a thread owns 4 consecutive BYTES of an output row (rows are flat [out_w * 3] byte arrays, out_w * 3 % 4 == 0): one
+// Vertical, the fast form (the byte kernel above stays for rows that are no whole number of dwords): a thread owns 4 consecutive
+// BYTES of an output row (rows are flat [out_w * 3] byte arrays, out_w * 3 % 4 == 0): one
 // dword load per tap instead of three byte loads per pixel, four accumulators.
 __global__ __launch_bounds__(256) void resize_v_dword_kernel(const ResizeVArgs a) {
   const int rb = a.out_w * 3, dw_per_row = rb >> 2;
@@ -296,6 +274,8 @@ hipError_t aigv_launch_frame_resize_ingest(const uint8_t* hwc, int n_frames, int
   if (n_frames <= 0) return hipSuccess;
   if (!hwc || !tmp_u8 || (!out_u8 && !out_nchw) || in_h <= 0 || in_w <= 0 || out_h <= 0 || out_w <= 0 || (out_nchw && (!mean || !stdv)))
     return hipErrorInvalidValue;
+  const size_t lds = ((size_t)in_w * 3 + 3 + 15) & ~(size_t)15;
+  if (lds > RESIZE_MAX_ROW_LDS) return hipErrorInvalidValue;   // a source row is staged whole: refused where it would not fit (in_w above 20474)
   DeviceTables t;
   {
     std::lock_guard<std::mutex> lock(g_resize_mutex);
@@ -322,17 +302,9 @@ hipError_t aigv_launch_frame_resize_ingest(const uint8_t* hwc, int n_frames, int
     }
   }
   const long n_rows = (long)n_frames * t.rows;
-  const size_t lds = ((size_t)in_w * 3 + 3 + 15) & ~(size_t)15;
-  if (lds <= 60 * 1024) {
-    hipLaunchKernelGGL(resize_h_lds_kernel, dim3((unsigned)(n_rows < 8192 ? n_rows : 8192)), dim3(256), lds, s, hwc,
-                       hwc + (size_t)n_frames * in_h * in_w * 3, tmp_u8, in_h, in_w, out_w, t.rows, t.y_first, t.bounds_h, t.kk_h,
-                       t.ksize_h, n_rows);
-  } else {
-    const long total_h = n_rows * out_w;
-    const long bh = (total_h + 255) / 256;
-    hipLaunchKernelGGL(resize_h_kernel, dim3((unsigned)(bh < 16384 ? bh : 16384)), dim3(256), 0, s, hwc, tmp_u8, in_h, in_w, out_w, t.rows,
-                       t.y_first, t.bounds_h, t.kk_h, t.ksize_h, total_h);
-  }
+  hipLaunchKernelGGL(resize_h_lds_kernel, dim3((unsigned)(n_rows < 8192 ? n_rows : 8192)), dim3(256), lds, s, hwc,
+                     hwc + (size_t)n_frames * in_h * in_w * 3, tmp_u8, in_h, in_w, out_w, t.rows, t.y_first, t.bounds_h, t.kk_h,
+                     t.ksize_h, n_rows);
   ResizeVArgs a{};
   a.tmp = tmp_u8; a.out_u8 = out_u8; a.out_nchw = out_nchw; a.bounds = t.bounds_v; a.kk = t.kk_v; a.ksize = t.ksize_v;
   a.rows = t.rows; a.out_h = out_h; a.out_w = out_w; a.total = (long)n_frames * out_h * out_w;

@@ -115,15 +115,34 @@ int aigv_op_skinny_gemm_fp8(const void* x, int ldx, int R, const void* W_e4m3, i
   return 0;
 }
 
+// ---- the norm kernels (test entry points; the passes call the launchers): every argument is checked here, before any HIP call ----
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// rows of H bf16 in 16-byte chunks, H <= 16384 (8 chunks per thread of a 256-thread workgroup); b: LayerNorm's bias (has_b)
+static int check_norm(const char* op, const void* x, int ldx, const void* w, const void* b, bool has_b, const void* y, int ldy, int rows, int H) {
+  if (!x || !w || !y || (has_b && !b)) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+  if (rows < 0) return fail(nullptr, AIGV_ERR_ARG, "%s: rows = %d must not be negative", op, rows);
+  if (H < 8 || H % 8 || H > 16384) return fail(nullptr, AIGV_ERR_ARG, "%s: H = %d is not a multiple of 8 in 8..16384", op, H);
+  if (ldx < H || ldx % 8 || ldy < H || ldy % 8)
+    return fail(nullptr, AIGV_ERR_ARG, "%s: bad leading dimension (ldx %d, ldy %d: multiples of 8, >= H = %d)", op, ldx, ldy, H);
+  if (!aligned16(x) || !aligned16(w) || !aligned16(b) || !aligned16(y)) return fail(nullptr, AIGV_ERR_ARG, "%s: the operands must be 16-byte aligned", op);
+  return 0;
+}
+
 int aigv_op_layernorm(const void* x, int ldx, const void* w, const void* b, void* y, int ldy, int rows, int H, float eps,
                       void* stream) {
+  TRY(check_norm("aigv_op_layernorm", x, ldx, w, b, true, y, ldy, rows, H));
   HIPCHK(nullptr, aigv_launch_layernorm((const bf16_t*)x, ldx, (const bf16_t*)w, (const bf16_t*)b, (bf16_t*)y, ldy, rows, H,
                                         eps, (hipStream_t)stream));
   return 0;
 }
 
+// row_idx (DEVICE int32 [rows], may be NULL): row i of y = the norm of row row_idx[i] of x.  y == x is allowed where row i reads row i
+// (the InternViT qk-norm runs in place): every thread has read its chunks before any thread writes.
 int aigv_op_rmsnorm(const void* x, int ldx, const void* w, void* y, int ldy, int rows, int H, float eps,
                     const int32_t* row_idx, void* stream) {
+  TRY(check_norm("aigv_op_rmsnorm", x, ldx, w, nullptr, false, y, ldy, rows, H));
+  if ((uintptr_t)row_idx & 3) return fail(nullptr, AIGV_ERR_ARG, "aigv_op_rmsnorm: row_idx must be 4-byte aligned");
   HIPCHK(nullptr, aigv_launch_rmsnorm((const bf16_t*)x, ldx, (const bf16_t*)w, (bf16_t*)y, ldy, rows, H, eps, row_idx,
                                       (hipStream_t)stream));
   return 0;
@@ -246,13 +265,33 @@ int aigv_op_kv_store(const void* qkv, int ld, const int32_t* seq, const int32_t*
   return 0;
 }
 
+// out [n_frames * (grid / 2)^2, 4 * vit_hidden] = the pixel-shuffled patch tokens of vit_out [n_frames, grid^2 + 1, vit_hidden] (the cls row is dropped)
 int aigv_op_pixel_shuffle(const void* vit_out, int grid, int vit_hidden, void* out, int n_frames, void* stream) {
+  const char* op = "aigv_op_pixel_shuffle";
+  if (!vit_out || !out) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+  if (n_frames < 0) return fail(nullptr, AIGV_ERR_ARG, "%s: %d frames: must not be negative", op, n_frames);
+  if (grid < 2 || grid % 2 || grid > 1024) return fail(nullptr, AIGV_ERR_ARG, "%s: grid = %d is not an even number in 2..1024", op, grid);
+  if (vit_hidden < 8 || vit_hidden % 8 || vit_hidden > 16384)
+    return fail(nullptr, AIGV_ERR_ARG, "%s: vit_hidden = %d is not a multiple of 8 in 8..16384", op, vit_hidden);
+  if ((int64_t)n_frames * (grid / 2) * (grid / 2) > INT32_MAX) return fail(nullptr, AIGV_ERR_ARG, "%s: %d frames of a %d grid: too many output rows", op, n_frames, grid);
+  if (!aligned16(vit_out) || !aligned16(out)) return fail(nullptr, AIGV_ERR_ARG, "%s: the operands must be 16-byte aligned", op);
   HIPCHK(nullptr, aigv_launch_pixel_shuffle((const bf16_t*)vit_out, grid, vit_hidden, (bf16_t*)out, n_frames, (hipStream_t)stream));
   return 0;
 }
 
+// out [n_frames * (image_size / patch)^2, kp] = the patches of frames [n_frames, channels, image_size, image_size]; columns from channels * patch^2 on are zero
 int aigv_op_im2col(const void* frames, int n_frames, int channels, int image_size, int patch, int kp, void* out,
                    void* stream) {
+  const char* op = "aigv_op_im2col";
+  if (!frames || !out) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+  if (n_frames < 0) return fail(nullptr, AIGV_ERR_ARG, "%s: %d frames: must not be negative", op, n_frames);
+  if (channels < 1 || patch < 1 || patch > 1024 || image_size < patch || image_size > 16384)
+    return fail(nullptr, AIGV_ERR_ARG, "%s: needs channels (%d) >= 1 and 1 <= patch (%d) <= image_size (%d) <= 16384", op, channels, patch, image_size);
+  if (image_size % patch) return fail(nullptr, AIGV_ERR_ARG, "%s: image_size = %d is not a multiple of patch = %d", op, image_size, patch);
+  if ((int64_t)kp < (int64_t)channels * patch * patch) return fail(nullptr, AIGV_ERR_ARG, "%s: kp = %d below channels * patch^2 = %lld", op, kp, (long long)channels * patch * patch);
+  const int64_t g = image_size / patch;
+  if ((int64_t)n_frames * g * g > INT32_MAX) return fail(nullptr, AIGV_ERR_ARG, "%s: %d frames of %lld x %lld patches: too many rows", op, n_frames, (long long)g, (long long)g);
+  if (!aligned16(frames) || !aligned16(out)) return fail(nullptr, AIGV_ERR_ARG, "%s: the operands must be 16-byte aligned", op);
   HIPCHK(nullptr, aigv_launch_im2col((const bf16_t*)frames, n_frames, channels, image_size, patch, kp, (bf16_t*)out,
                                      (hipStream_t)stream));
   return 0;
@@ -354,8 +393,6 @@ int aigv_op_lm_head_argmax_topk_logprob(const void* h, int rows, int hidden, con
 }
 
 // ---- the decode step's kernels, one by one (test entry points): every argument is checked here, before any HIP call ----
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 int64_t aigv_op_attention_decode_ws_floats(int n_seq, int n_kv, int g, int cap) {
   if (n_seq < 1 || n_kv < 1 || g < 1 || g > 8 || cap < 1 || cap > AIGV_MAX_KV_CAPACITY) return -1;
   return (int64_t)aigv_attention_decode_ws_floats(n_seq, n_kv, g, cap);
@@ -673,6 +710,15 @@ int aigv_op_write_ints(const int32_t* host, int n, int32_t* dst, void* stream) {
 
 int aigv_op_frame_ingest(const void* hwc_u8, int n_frames, int height, int width, const float* mean, const float* stdv,
                          void* out_nchw, void* stream) {
+  const char* op = "aigv_op_frame_ingest";
+  if (n_frames < 0) return fail(nullptr, AIGV_ERR_ARG, "%s: %d frames: must not be negative", op, n_frames);
+  if (height < 1 || width < 1 || height > 16384 || width > 16384) return fail(nullptr, AIGV_ERR_ARG, "%s: %d x %d frames outside 1..16384", op, height, width);
+  if ((height * width) % 4) return fail(nullptr, AIGV_ERR_ARG, "%s: height * width = %d is not a multiple of 4", op, height * width);
+  if (!mean || !stdv) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+  if (n_frames == 0) return 0;   // (an empty batch has no buffers)
+  if (!hwc_u8 || !out_nchw) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+  if (((uintptr_t)hwc_u8 & 3) || ((uintptr_t)out_nchw & 7))
+    return fail(nullptr, AIGV_ERR_ARG, "%s: the frames must be 4-byte aligned and out_nchw 8-byte aligned", op);
   HIPCHK(nullptr, aigv_launch_frame_ingest((const uint8_t*)hwc_u8, n_frames, height, width, mean, stdv, (bf16_t*)out_nchw,
                                            (hipStream_t)stream));
   return 0;

@@ -486,6 +486,11 @@ int aigv_op_skinny_gemm(const void* x, int ldx, int R, const void* W, int ldw, i
  * (R <= 16 / p). */
 int aigv_op_skinny_gemm_fp8(const void* x, int ldx, int R, const void* W_e4m3, int ldw, const float* w_scale, int N, int K, const void* resid,
                             int ldr, void* out, int ldo, int epi, const void* norm_w, float eps, int p, void* stream);
+/* The norm kernels, rows of H bf16 (H a multiple of 8, 8..16384; ldx, ldy >= H, multiples of 8; every operand 16-byte aligned):
+ *   layernorm  y = bf16((x - mean) * rstd * w + b), fp32 statistics, one rounding
+ *   rmsnorm    y = bf16(w * bf16(x * rsqrt(mean(x^2) + eps))); row_idx (DEVICE int32[rows], may be NULL): row i of y from row row_idx[i] of x.
+ *              y == x with ldy == ldx and no row_idx is allowed (the InternViT qk-norm runs in place on the middle third of its qkv rows).
+ * Checked on the host (AIGV_ERR_ARG) before anything is launched. */
 int aigv_op_layernorm(const void* x, int ldx, const void* w, const void* b, void* y, int ldy, int rows, int H,
                       float eps, void* stream);
 int aigv_op_rmsnorm(const void* x, int ldx, const void* w, void* y, int ldy, int rows, int H, float eps,
@@ -563,6 +568,9 @@ int aigv_op_attention_probe_tokens(const void* q, int ldq, const void* k, int ld
  * is written.  seq / pos: DEVICE int32[tokens] (the caller's promise: seq[t] inside the cache, pos[t] < cap).  Checked on the host. */
 int aigv_op_kv_store(const void* qkv, int ld, const int32_t* seq, const int32_t* pos, void* kc, void* vc, int tokens, int n_kv, int g,
                      int head_dim, int cap, void* stream);
+/* pixel_shuffle: vit_out [n_frames, grid^2 + 1, vit_hidden] -> out [n_frames * (grid / 2)^2, 4 * vit_hidden], the cls row dropped (grid even,
+ * vit_hidden a multiple of 8).  im2col: frames [n_frames, channels, image_size, image_size] -> out [n_frames * (image_size / patch)^2, kp], columns
+ * from channels * patch^2 on zero (image_size a multiple of patch, kp >= channels * patch^2).  Operands 16-byte aligned; checked on the host. */
 int aigv_op_pixel_shuffle(const void* vit_out, int grid, int vit_hidden, void* out, int n_frames, void* stream);
 int aigv_op_im2col(const void* frames, int n_frames, int channels, int image_size, int patch, int kp, void* out,
                    void* stream);
@@ -704,7 +712,8 @@ int aigv_op_head_rows(void* ao, int ld, int T, const int32_t* rows_host, int n, 
 
 /* Frame ingest: uint8 [F,H,W,3] RGB frames already at the model resolution -> bf16 NCHW
  * pixel_values = bf16((u/255 - mean[c]) / std[c])  (torchvision ToTensor + Normalize of dataset.py:267-274 and the
- * bf16 cast of stage2_eval.py:932).  mean/std: HOST float[3]. */
+ * bf16 cast of stage2_eval.py:932).  mean/std: HOST float[3].  height * width must be a multiple of 4, the frames 4-byte and out_nchw
+ * 8-byte aligned; checked on the host. */
 int aigv_op_frame_ingest(const void* hwc_u8, int n_frames, int height, int width, const float* mean, const float* stdv,
                          void* out_nchw, void* stream);
 

@@ -201,7 +201,8 @@ def test_score_head_guard_stays_off_without_a_nan(lib):
 @pytest.mark.parametrize("rows", [1, 33])
 @pytest.mark.parametrize("H", [128, 1032, 4096, 6144, 16384])
 def test_rmsnorm_quant_fp8_is_the_two_step_path_bit_for_bit(lib, H, rows):
-    """The fused kernel promises the bytes and scales of rmsnorm_kernel followed by quant_fp8_rows_kernel (both tied to torch by
+    """The fused kernel promises the bytes and scales of rmsnorm_kernel followed by quant_fp8_rows_kernel (rmsnorm_kernel is held to the fp64
+    truth by tests/test_gpu_norm_ops.py, which also holds this kernel to it directly; the row quantisation is tied to torch by
     tests/test_gpu_ops.py): compared bit for bit, so no +-0 difference either - both convert with the same instruction."""
     g = torch.Generator().manual_seed(H + rows)
     ldx, ldq = H + 24, H + 16
