@@ -120,6 +120,9 @@ static int alloc_workspaces(aigv_ctx* c) {
     if ((rc = dalloc(c, &c->l_lensidx, (size_t)4 * AIGV_MAX_LENS_ROWS))) break;   // (here, never inside a pass: the armed pass may be captured)
     if ((rc = dalloc(c, &c->l_streamidx, (size_t)2 * k.max_tokens))) break;      // (likewise: the row numbers of a stream patch | of a stream capture)
     if ((rc = dalloc(c, &c->l_headidx, (size_t)3 * k.max_tokens))) break;        // (likewise: those of a head scale | of a head patch | of a head capture)
+    if ((rc = dalloc(c, &c->l_neuronidx, (size_t)9 * k.max_tokens))) break;      // (likewise: per neuron option its rows | its last-layer activation rows | their side rows)
+    if ((rc = dalloc(c, &c->l_neuroncol, (size_t)3 * AIGV_MAX_NEURON_SEL))) break;   // (likewise: the column lists of a neuron scale | patch | capture)
+    if ((rc = dalloc(c, &c->l_neuronfac, (size_t)AIGV_MAX_NEURON_SEL))) break;       // (likewise: the factors of a sparse neuron scale)
     c->rp_vit = RowPlan(); c->rp_llm = RowPlan(); c->cur_rp = nullptr;
     c->rp_vit.cap_halves = (int)(vr / 128) + 2 * k.vit_chunk + 2;
     c->rp_llm.cap_halves = (int)(T / 128) + 2 * k.max_seqs + 2;

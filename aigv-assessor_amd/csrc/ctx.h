@@ -176,6 +176,24 @@ struct aigv_ctx {
     bf16_t* buf = nullptr;        // device, the caller's: [rows.size()][hi - lo][n_heads * D]
   } head_cap, head_patch, head_scale;
   int32_t* l_headidx = nullptr;   // device [3 * max_tokens]: the armed pass's head-scale rows | head-patch rows | head-capture rows
+  // MLP neuron knock-out / neuron patching (aigv_neuron_scale_arm / aigv_neuron_patch_arm / aigv_neuron_capture_arm): armed for exactly the next
+  // aigv_llm_prefill.  Between the SwiGLU GEMM of layer li and its w2, on the row w2 consumes (l_ffn [T, I]; the streamed rows of the row-trimmed last layer:
+  // t_ffn): first the scale, then the patch (lo <= li < hi), then the capture - so a capture returns what w2 consumes.  rows: packed row numbers, copied on
+  // arming, checked by the pass; all_rows (the scale only): every row.  cols empty and dense true: every neuron; else the sparse column list (capture,
+  // patch: one list for the window; scale: (layer, column, factor) triples sorted by layer, sel_begin[l] .. sel_begin[l + 1] those of layer l)
+  struct NeuronRows {
+    bool armed = false, all_rows = false, dense = true;
+    int lo = 0, hi = 0;
+    std::vector<int32_t> rows, cols;
+    std::vector<float> layer_scale;   // the scale, dense form: [llm_layers] (empty: none)
+    std::vector<float> factors;       // the scale, sparse form: one per entry of cols
+    std::vector<int32_t> sel_begin;   // the scale, sparse form: [llm_layers + 1]
+    bf16_t* buf = nullptr;            // device, the caller's: [rows.size()][hi - lo][I or cols.size()]
+  } neuron_cap, neuron_patch, neuron_scale;
+  // device: per option (scale | patch | capture) 3 * max_tokens ints - its packed rows | the activation rows of its last-layer launches | their side rows
+  int32_t* l_neuronidx = nullptr;
+  int32_t* l_neuroncol = nullptr;   // device [3 * AIGV_MAX_NEURON_SEL]: the scale's columns | the patch's | the capture's
+  float* l_neuronfac = nullptr;     // device [AIGV_MAX_NEURON_SEL]: the scale's factors
   // profiling
   bool prof = false;
   int gemm_cls = AIGV_PROF_GEMM;   // class the GEMM launches are booked under: AIGV_PROF_GEMM_VIT inside aigv_vit_forward / aigv_project
@@ -300,13 +318,14 @@ constexpr size_t SPLITK_MAX_FLOATS = (size_t)64 << 20;   // 256 MB of fp32 split
 int splitk_scratch(aigv_ctx* c, size_t need_floats, float** out);
 
 // ---- the score-row attention probe of an armed pass (probe.hip) --------------------------------------------------------------------
-// DisarmScope: the pass that finds the context armed - with the probe, with a key-drop mask (aigv_key_drop_arm), with the depth lens (aigv_depth_lens_arm), with a stream capture or patch (aigv_stream_capture_arm, aigv_stream_patch_arm), with a head capture, patch or scale (aigv_head_capture_arm, aigv_head_patch_arm, aigv_head_scale_arm) - disarms it on every way out.  probe_plan: the probe's arguments for this pass (rows
+// DisarmScope: the pass that finds the context armed - with the probe, with a key-drop mask (aigv_key_drop_arm), with the depth lens (aigv_depth_lens_arm), with a stream capture or patch (aigv_stream_capture_arm, aigv_stream_patch_arm), with a head capture, patch or scale (aigv_head_capture_arm, aigv_head_patch_arm, aigv_head_scale_arm), with a neuron capture, patch or scale (aigv_neuron_capture_arm, aigv_neuron_patch_arm, aigv_neuron_scale_arm) - disarms it on every way out.  probe_plan: the probe's arguments for this pass (rows
 // validated against cu; off_host: keys cached in front of every sequence, or null), built ONCE per pass; probe_layer: the launch of layer li.
 struct DisarmScope {
   aigv_ctx* c;
   explicit DisarmScope(aigv_ctx* c_) : c(c_) {}
   ~DisarmScope() { c->probe.armed = false; c->drop.armed = false; c->lens.armed = false; c->stream_cap.armed = false; c->stream_patch.armed = false;
-                   c->head_cap.armed = false; c->head_patch.armed = false; c->head_scale.armed = false; }
+                   c->head_cap.armed = false; c->head_patch.armed = false; c->head_scale.armed = false;
+                   c->neuron_cap.armed = false; c->neuron_patch.armed = false; c->neuron_scale.armed = false; }
 };
 int probe_plan(aigv_ctx* c, const char* op, const int32_t* cu, int B, const int32_t* off_host, ProbeArgs* out);
 int probe_layer(aigv_ctx* c, const ProbeArgs& plan, int li, bool cache, hipStream_t s);

@@ -216,6 +216,16 @@ enum { HEAD_CAPTURE = 0, HEAD_PATCH = 1, HEAD_SCALE = 2 };
 struct HeadScales { float v[AIGV_MAX_HEAD_BITS]; };
 hipError_t aigv_launch_head_rows(bf16_t* ao, int ld, const int32_t* idx, int n, bf16_t* side, int n_layers, int layer, int n_heads, int D, int mode,
                                  uint64_t heads, const float* scale, hipStream_t s);
+// MLP neuron knock-out / neuron patching: rows idx[i] (idx null: rows 0 .. n - 1) of the SwiGLU output `act` [.., I] (leading dimension ld) against
+// slice `layer` of a side buffer whose element (si, l) sits at side + (si * n_layers + l) * W, si = sidx[i] (sidx null: i).  cols null (m = 0): the dense
+// form, W = I, NEURON_SCALE by `dense_factor` (exactly 1: nothing is launched).  cols DEVICE int32 [m], strictly ascending inside [0, I): the sparse form,
+// W = m, element j of a side row is column cols[j]; NEURON_SCALE by factors[j] (DEVICE float [m]; exactly 1: the element is not touched).
+// NEURON_CAPTURE: side = act; NEURON_PATCH: act = side (bit copies); NEURON_SCALE: act = bf16(fp32(act) * s), `side` and `sidx` unused.  I a multiple of
+// 8, ld a multiple of 8 and >= I, the buffers 16-byte aligned, 0 <= layer < n_layers, 0 <= m <= I: else hipErrorInvalidValue
+#define AIGV_MAX_NEURON_SEL 4096
+enum { NEURON_CAPTURE = 0, NEURON_PATCH = 1, NEURON_SCALE = 2 };
+hipError_t aigv_launch_neuron_rows(bf16_t* act, int ld, const int32_t* idx, const int32_t* sidx, int n, bf16_t* side, int n_layers, int layer, int I,
+                                   const int32_t* cols, int m, int mode, const float* factors, float dense_factor, hipStream_t s);
 hipError_t aigv_launch_cls_rows(const bf16_t* cls_pos, bf16_t* x, int F, int tokens_per_frame, int H, hipStream_t s);
 // RoPE in place on the fused qkv rows: per kv group, slots 0..g (q heads and K) are rotated.
 // slots [first_rot, first_rot + n_rot) of every group are rotated in place (q heads + K: first_rot 0, n_rot g + 1; K only: g, 1)

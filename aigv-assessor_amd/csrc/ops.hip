@@ -690,6 +690,56 @@ int aigv_op_head_rows(void* ao, int ld, int T, const int32_t* rows_host, int n, 
   return 0;
 }
 
+// One launch of the neuron-rows kernel (aigv_neuron_capture_arm / aigv_neuron_patch_arm / aigv_neuron_scale_arm), as a pass of T rows makes it for slice
+// `layer` of a window of n_layers layers on act [T][ld] of I columns.  rows_host (checked as the pass checks them; null: rows 0 .. T - 1) go to idx_dev,
+// sidx_host (null: side row i; else n side-row numbers inside [0, n_side)) to sidx_dev, cols_host (null: the dense form; else m columns, strictly ascending
+// inside [0, I)) to cols_dev, factors_host (the sparse scale: m floats, no NaN) to factors_dev - all as kernel arguments.  mode 0 copies the selected
+// columns of the rows to side[(si * n_layers + layer) * W ..] (W = I, or m in the sparse form), mode 1 overwrites them from there, mode 2 scales them by
+// dense_factor (dense) or factors_host[j] (sparse); side, the side rows and n_layers / layer are then unused
+int aigv_op_neuron_rows(void* act, int ld, int T, const int32_t* rows_host, int n, int32_t* idx_dev, const int32_t* sidx_host, int32_t* sidx_dev, int n_side, void* side,
+                        int n_layers, int layer, int I, const int32_t* cols_host, int m, int32_t* cols_dev, int mode, const float* factors_host, float* factors_dev,
+                        float dense_factor, void* stream) {
+  const char* op = "aigv_op_neuron_rows";
+  if (mode != NEURON_CAPTURE && mode != NEURON_PATCH && mode != NEURON_SCALE) return fail(nullptr, AIGV_ERR_ARG, "%s: mode %d is none of 0 (capture), 1 (patch), 2 (scale)", op, mode);
+  const bool scale = mode == NEURON_SCALE, every = !rows_host, sparse = cols_host != nullptr;
+  if (T < 0) return fail(nullptr, AIGV_ERR_ARG, "%s: T = %d rows: must not be negative", op, T);
+  if (every) n = T;
+  TRY(check_rows(op, act, scale ? act : side, rows_host, !every, n, I, ld));
+  if (!every && !idx_dev) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+  if (scale) { n_layers = 1; layer = 0; sidx_host = nullptr; }
+  if (n_layers < 1 || layer < 0 || layer >= n_layers) return fail(nullptr, AIGV_ERR_ARG, "%s: layer %d outside the window of %d layers", op, layer, n_layers);
+  if (sparse) {
+    if (m < 0 || m > I) return fail(nullptr, AIGV_ERR_ARG, "%s: %d columns outside 0..I = %d", op, m, I);   // (the arm calls' cap is their tables': the op's lists are the caller's)
+    if (m > 0 && !cols_dev) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+    for (int j = 0; j < m; ++j) {
+      if (cols_host[j] < 0 || cols_host[j] >= I) return fail(nullptr, AIGV_ERR_ARG, "%s: column %d (entry %d) outside 0..%d", op, cols_host[j], j, I - 1);
+      if (j && cols_host[j] <= cols_host[j - 1]) return fail(nullptr, AIGV_ERR_ARG, "%s: columns not strictly ascending at entry %d", op, j);
+    }
+    if (scale) {
+      if (!factors_host || (m > 0 && !factors_dev)) return fail(nullptr, AIGV_ERR_ARG, "%s: null factor list", op);
+      for (int j = 0; j < m; ++j) if (factors_host[j] != factors_host[j]) return fail(nullptr, AIGV_ERR_ARG, "%s: factor %d is NaN", op, j);
+    }
+  } else {
+    m = 0;
+    if (scale && dense_factor != dense_factor) return fail(nullptr, AIGV_ERR_ARG, "%s: the factor is NaN", op);
+  }
+  if (sidx_host) {
+    if (!sidx_dev) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+    for (int i = 0; i < n; ++i) if (sidx_host[i] < 0 || sidx_host[i] >= n_side) return fail(nullptr, AIGV_ERR_ARG, "%s: side row %d (entry %d) outside 0..%d", op, sidx_host[i], i, n_side - 1);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (!every) {
+    TRY(stream_rows_check(nullptr, op, rows_host, n, T, 0, n_layers, n_layers));
+    HIPCHK(nullptr, aigv_launch_write_ints(rows_host, n, idx_dev, s));
+  }
+  if (sidx_host) HIPCHK(nullptr, aigv_launch_write_ints(sidx_host, n, sidx_dev, s));
+  if (sparse && m > 0) HIPCHK(nullptr, aigv_launch_write_ints(cols_host, m, cols_dev, s));
+  if (sparse && scale && m > 0) HIPCHK(nullptr, aigv_launch_write_ints((const int32_t*)factors_host, m, (int32_t*)factors_dev, s));
+  HIPCHK(nullptr, aigv_launch_neuron_rows((bf16_t*)act, ld, every ? nullptr : idx_dev, sidx_host ? sidx_dev : nullptr, n, (bf16_t*)side, n_layers, layer, I, sparse ? cols_dev : nullptr, m,
+                                          mode, sparse ? factors_dev : nullptr, dense_factor, s));
+  return 0;
+}
+
 // x[f * tokens_per_frame, :H] = cls_pos[:H] for f < n_frames (x is dense [n_frames * tokens_per_frame, H])
 int aigv_op_cls_rows(const void* cls_pos, void* x, int n_frames, int tokens_per_frame, int H, void* stream) {
   const char* op = "aigv_op_cls_rows";

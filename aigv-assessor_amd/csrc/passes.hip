@@ -221,8 +221,54 @@ static int llm_layer_qkv(aigv_ctx* c, int li, int T, hipStream_t s) {
   return 0;
 }
 
-// h += wo(attention output);  h += w2(silu(w1 n) * w3 n), n = ffn_norm(h)
-static int llm_layer_post(aigv_ctx* c, int li, int T, hipStream_t s) {
+// MLP neuron knock-out / neuron patching: what an armed pass launches between a SwiGLU GEMM and its w2.  Built once per pass (neuron_plan); the row
+// tables live in l_neuronidx, per option o (0 scale, 1 patch, 2 capture) at o * 3 * max_tokens: its packed rows | the activation rows of its last-layer
+// launches | their side rows.  The last-layer lists hold, in launch order, the entries of the streamed chunks (activation row: the position inside the
+// 64-row chunk of t_ffn) and then, for a mixed batch, those of every other selected row (activation row: the packed row of l_ffn).
+struct NeuronPlan {
+  bool on[3] = {false, false, false};
+  bool split_last = false;              // the last layer finishes (some) rows on the weight-streaming path: its launches take the last-layer lists
+  struct Last { std::vector<int32_t> act, side; std::vector<int> chunk_begin; int rest_begin = 0; } last[3];
+};
+enum { NEURON_AT_ROWS = -1, NEURON_AT_REST = -2 };   // where a hook acts: every row of l_ffn | l_ffn without the streamed rows | (>= 0) streamed chunk number
+
+// the launches of layer li on `act` [.., I]: scale, then patch, then capture; n_all: the rows `act` holds (what a scale of every row covers)
+static int neuron_hook(aigv_ctx* c, const NeuronPlan& P, int li, bf16_t* act, int where, int n_all, hipStream_t s) {
+  const int I = c->cfg.llm_inter;
+  const size_t mt = (size_t)c->cfg.max_tokens;
+  const bool last = P.split_last && li == c->cfg.llm_layers - 1;
+  const aigv_ctx::NeuronRows* opt[3] = {&c->neuron_scale, &c->neuron_patch, &c->neuron_cap};
+  for (int o = 0; o < 3; ++o) {
+    const aigv_ctx::NeuronRows& r = *opt[o];
+    if (!P.on[o] || li < r.lo || li >= r.hi) continue;
+    const int32_t* base = c->l_neuronidx + (size_t)o * 3 * mt;
+    const int32_t *idx = nullptr, *sidx = nullptr;
+    int n = n_all;
+    if (!r.all_rows) {
+      if (!last) { idx = base; n = (int)r.rows.size(); }
+      else {
+        const NeuronPlan::Last& q = P.last[o];
+        const int b = where == NEURON_AT_REST ? q.rest_begin : q.chunk_begin[where];
+        const int e = where == NEURON_AT_REST ? (int)q.act.size() : q.chunk_begin[where + 1];
+        idx = base + mt + b; sidx = base + 2 * mt + b; n = e - b;
+      }
+    }
+    if (o == 0) {
+      if (!r.layer_scale.empty())
+        HIPCHK(c, aigv_launch_neuron_rows(act, I, idx, nullptr, n, nullptr, 1, 0, I, nullptr, 0, NEURON_SCALE, nullptr, r.layer_scale[li], s));
+      const int b = r.sel_begin.empty() ? 0 : r.sel_begin[li], e = r.sel_begin.empty() ? 0 : r.sel_begin[li + 1];
+      if (e > b) HIPCHK(c, aigv_launch_neuron_rows(act, I, idx, nullptr, n, nullptr, 1, 0, I, c->l_neuroncol + b, e - b, NEURON_SCALE, c->l_neuronfac + b, 1.0f, s));
+    } else {
+      const int32_t* cols = r.dense ? nullptr : c->l_neuroncol + (size_t)o * AIGV_MAX_NEURON_SEL;
+      if (r.dense || !r.cols.empty())
+        HIPCHK(c, aigv_launch_neuron_rows(act, I, idx, sidx, n, r.buf, r.hi - r.lo, li - r.lo, I, cols, (int)r.cols.size(), o == 1 ? NEURON_PATCH : NEURON_CAPTURE, nullptr, 1.0f, s));
+    }
+  }
+  return 0;
+}
+
+// h += wo(attention output);  h += w2(silu(w1 n) * w3 n), n = ffn_norm(h); np (an armed pass): its neuron launches between the SwiGLU GEMM and w2
+static int llm_layer_post(aigv_ctx* c, int li, int T, hipStream_t s, const NeuronPlan* np = nullptr, int where = NEURON_AT_ROWS) {
   const aigv_config& k = c->cfg;
   const LlmLayer& L = c->llm[li];
   const int H = k.llm_hidden, I = k.llm_inter;
@@ -231,6 +277,7 @@ static int llm_layer_post(aigv_ctx* c, int li, int T, hipStream_t s) {
     TRY(run_gemm_fp8(c, c->l_ao, H, H, Q.wo, Q.s_wo, c->l_h, H, T, H, EPI_RESID, c->l_h, H, s));
     HIPCHK(c, aigv_launch_rmsnorm_quant_fp8(c->l_h, H, L.fn, c->q8, H, c->q8_scale, T, H, k.rms_eps, s));
     TRY(run_gemm_fp8(c, nullptr, H, H, Q.w13, Q.s_w13, c->l_ffn, I, T, 2 * I, EPI_SWIGLU, nullptr, 0, s));
+    if (np) TRY(neuron_hook(c, *np, li, c->l_ffn, where, T, s));   // (l_ffn is bf16 here too: run_gemm_fp8 quantises it afterwards)
     TRY(run_gemm_fp8(c, c->l_ffn, I, I, Q.w2, Q.s_w2, c->l_h, H, T, H, EPI_RESID, c->l_h, H, s));
     return 0;
   }
@@ -241,6 +288,7 @@ static int llm_layer_post(aigv_ctx* c, int li, int T, hipStream_t s) {
   }
   HIPCHK(c, aigv_launch_rmsnorm(c->l_h, H, L.fn, c->l_t, H, T, H, k.rms_eps, nullptr, s));
   TRY(run_llm_gemm(c, gemm_args(c->l_t, H, L.w13, H, c->l_ffn, I, T, 2 * I, H), EPI_SWIGLU, s));
+  if (np) TRY(neuron_hook(c, *np, li, c->l_ffn, where, T, s));
   GemmArgs a = gemm_args(c->l_ffn, I, L.w2, I, c->l_h, H, T, H, I);
   a.resid = c->l_h; a.ldr = H;
   TRY(run_llm_gemm(c, a, EPI_RESID, s));
@@ -291,6 +339,7 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
   const bool patching = c->stream_patch.armed;    // aigv_stream_patch_arm: rows of the residual stream are overwritten in front of the armed layers; disarmed likewise
   const bool capturing = c->stream_cap.armed;     // aigv_stream_capture_arm: rows of the residual stream are copied out in front of the armed layers; disarmed likewise
   const bool h_scaling = c->head_scale.armed, h_patching = c->head_patch.armed, h_capturing = c->head_cap.armed;   // aigv_head_*_arm: l_ao between the attention and wo; disarmed likewise
+  const bool n_scaling = c->neuron_scale.armed, n_patching = c->neuron_patch.armed, n_capturing = c->neuron_cap.armed;   // aigv_neuron_*_arm: the row w2 consumes; disarmed likewise
   DisarmScope disarm(c);
   if (!c->finalized) return fail(c, AIGV_ERR_STATE, "aigv_llm_prefill: call aigv_finalize_weights first");
   if (dropping && probing) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: a key-drop mask and the score-attention probe are both armed: the probe does not know the mask");
@@ -344,6 +393,23 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
       if (h_scaling) for (int h = 0; h < k.llm_heads; ++h) scale_last |= hs.scale[(size_t)last * k.llm_heads + h] != 1.0f;
       const bool reaches = scale_last || (h_patching && hp.lo <= last && last < hp.hi) || (h_capturing && hc.lo <= last && last < hc.hi);
       if (reaches) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: a head option reaches layer %d and the pass has no output rows (n_out == 0): the last layer's attention does not run", last);
+    }
+  }
+  // MLP neuron knock-out / neuron patching: likewise.  A pass without output rows breaks out in front of its last attention: its last MLP does not run
+  const aigv_ctx::NeuronRows &ns = c->neuron_scale, &npat = c->neuron_patch, &ncap = c->neuron_cap;
+  const bool n_any = n_scaling || n_patching || n_capturing;
+  if (n_any) {
+    const char* what = n_scaling ? "scale" : n_patching ? "patch" : "capture";
+    const char* arm = n_scaling ? "aigv_neuron_scale_arm" : n_patching ? "aigv_neuron_patch_arm" : "aigv_neuron_capture_arm";
+    if (keep_kv) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: keep_kv while a neuron %s is armed (%s): only a pass without a KV cache takes one", what, arm);
+    if (n_scaling && !ns.all_rows) TRY(stream_rows_check(c, "aigv_llm_prefill: the neuron scale (aigv_neuron_scale_arm)", ns.rows.data(), (int)ns.rows.size(), T, 0, k.llm_layers, k.llm_layers));
+    if (n_patching) TRY(stream_rows_check(c, "aigv_llm_prefill: the neuron patch (aigv_neuron_patch_arm)", npat.rows.data(), (int)npat.rows.size(), T, npat.lo, npat.hi, k.llm_layers));
+    if (n_capturing) TRY(stream_rows_check(c, "aigv_llm_prefill: the neuron capture (aigv_neuron_capture_arm)", ncap.rows.data(), (int)ncap.rows.size(), T, ncap.lo, ncap.hi, k.llm_layers));
+    if ((score ? B : 0) + R == 0 && c->trim_last_layer) {
+      const int last = k.llm_layers - 1;
+      const bool scale_last = n_scaling && ((!ns.layer_scale.empty() && ns.layer_scale[last] != 1.0f) || (!ns.sel_begin.empty() && ns.sel_begin[last + 1] > ns.sel_begin[last]));
+      const bool reaches = scale_last || (n_patching && npat.lo <= last && last < npat.hi) || (n_capturing && ncap.lo <= last && last < ncap.hi);
+      if (reaches) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: a neuron option reaches layer %d and the pass has no output rows (n_out == 0): the last layer's MLP does not run", last);
     }
   }
   // the depth lens: every lens row must be a consumed row [score rows | logit rows] - the last layer finishes only those; lens_at: its place among them
@@ -418,6 +484,46 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
   const bool trim = trim_ok && (int)small_rows.size() == n_out;
   const bool mixed = trim_ok && !trim && !small_rows.empty();
   if (mixed) HIPCHK(c, aigv_launch_write_ints(small_rows.data(), (int)small_rows.size(), c->l_rowidx2, s));
+  // MLP neuron knock-out / neuron patching: the row and column tables go up on this stream.  In the last layer of a trimmed or mixed batch the value
+  // captured, patched or scaled for a row is the input of the w2 launch whose output the pass keeps for it: the streamed rows' (small_rows, 64 at a time)
+  // is t_ffn - the packed row translated to (chunk, position), the side row passed beside it; trim: no other row's MLP runs; mixed: every other row's is l_ffn
+  NeuronPlan nplan;
+  if (n_any) {
+    const aigv_ctx::NeuronRows* opt[3] = {&ns, &npat, &ncap};
+    nplan.on[0] = n_scaling; nplan.on[1] = n_patching; nplan.on[2] = n_capturing;
+    nplan.split_last = trim || mixed;
+    const int last = k.llm_layers - 1, n_fin = (int)small_rows.size();
+    for (int o = 0; o < 3; ++o) {
+      const aigv_ctx::NeuronRows& r = *opt[o];
+      if (!nplan.on[o]) continue;
+      int32_t* base = c->l_neuronidx + (size_t)o * 3 * k.max_tokens;
+      if (!r.all_rows) HIPCHK(c, aigv_launch_write_ints(r.rows.data(), (int)r.rows.size(), base, s));
+      if (!r.cols.empty()) HIPCHK(c, aigv_launch_write_ints(r.cols.data(), (int)r.cols.size(), c->l_neuroncol + (size_t)o * AIGV_MAX_NEURON_SEL, s));
+      if (!r.factors.empty()) HIPCHK(c, aigv_launch_write_ints((const int32_t*)r.factors.data(), (int)r.factors.size(), (int32_t*)c->l_neuronfac, s));
+      if (!nplan.split_last || r.all_rows || last < r.lo || last >= r.hi) continue;
+      NeuronPlan::Last& q = nplan.last[o];
+      std::vector<char> streamed(r.rows.size(), 0);
+      for (int r0 = 0; r0 < n_fin; r0 += 64) {
+        q.chunk_begin.push_back((int)q.act.size());
+        for (int p = r0; p < std::min(n_fin, r0 + 64); ++p) {
+          const auto it = std::lower_bound(r.rows.begin(), r.rows.end(), small_rows[p]);
+          if (it == r.rows.end() || *it != small_rows[p]) continue;
+          q.act.push_back(p - r0); q.side.push_back((int32_t)(it - r.rows.begin()));
+          streamed[it - r.rows.begin()] = 1;
+        }
+      }
+      q.chunk_begin.push_back((int)q.act.size());
+      q.rest_begin = (int)q.act.size();
+      if (mixed)
+        for (size_t i = 0; i < r.rows.size(); ++i) if (!streamed[i]) { q.act.push_back(r.rows[i]); q.side.push_back((int32_t)i); }
+      if ((int)q.act.size() > k.max_tokens) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: the neuron options' last-layer row list (%d entries) exceeds max_tokens = %d", (int)q.act.size(), k.max_tokens);
+      if (!q.act.empty()) {
+        HIPCHK(c, aigv_launch_write_ints(q.act.data(), (int)q.act.size(), base + k.max_tokens, s));
+        HIPCHK(c, aigv_launch_write_ints(q.side.data(), (int)q.side.size(), base + 2 * (size_t)k.max_tokens, s));
+      }
+    }
+  }
+  const NeuronPlan* np = n_any ? &nplan : nullptr;
   ProbeArgs probe{};
   if (probing) TRY(probe_plan(c, "aigv_llm_prefill", cu, B, nullptr, &probe));
   double attn_flops = 0;
@@ -478,6 +584,7 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
         TRY(run_skinny(c, t_ao, H, nr, L.wo, H, H, H, nullptr, h, H, h, H, SK_RESID, s, 0));
         HIPCHK(c, aigv_launch_rmsnorm(h, H, L.fn, t_n, H, nr, H, k.rms_eps, nullptr, s));
         TRY(run_skinny(c, t_n, H, nr, L.w13, H, 2 * I, H, nullptr, nullptr, 0, t_ffn, I, SK_SWIGLU, s, 0));
+        if (np) TRY(neuron_hook(c, *np, li, t_ffn, r0 / 64, nr, s));
         TRY(run_skinny(c, t_ffn, I, nr, L.w2, I, H, I, nullptr, h, H, h, H, SK_RESID, s, 0));
       }
       if (trim) {
@@ -485,12 +592,12 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
         TRY(final_rows(c, score, B, R, argmax, t_h, true, s));
         break;
       }
-      TRY(llm_layer_post(c, li, T, s));                                                          // every row on the tile kernels ...
+      TRY(llm_layer_post(c, li, T, s, np, NEURON_AT_REST));                                      // every row on the tile kernels ...
       HIPCHK(c, aigv_launch_scatter_rows(t_h, c->l_rowidx2, n_fin, c->l_h, H, H, s));            // ... the small clips' consumed rows put back
       if (lensing) TRY(lens_tap(k.llm_layers, c->l_h, lens_idx));
       break;
     }
-    TRY(llm_layer_post(c, li, T, s));
+    TRY(llm_layer_post(c, li, T, s, np));
     if (lensing && li == k.llm_layers - 1) TRY(lens_tap(k.llm_layers, c->l_h, lens_idx));   // depth L of a pass whose last layer ran for every row
   }
   if (!trim) TRY(final_rows(c, score, B, R, argmax, c->l_h, false, s));
@@ -630,6 +737,77 @@ int aigv_head_scale_arm(aigv_ctx* c, const int32_t* rows_host, int n, const floa
   return 0;
 }
 
+// Arm the next aigv_llm_prefill with a capture / a patch / a scale of MLP neurons (include/aigv_amd.h): the host arrays are copied here; rows and windows
+// are checked when that pass runs; the device buffer is the caller's.
+static int neuron_cols_check(const char* op, aigv_ctx* c, const int32_t* cols, int m, int I) {
+  if (m < 0 || m > AIGV_MAX_NEURON_SEL) return fail(c, AIGV_ERR_ARG, "%s: %d columns outside 0..%d", op, m, AIGV_MAX_NEURON_SEL);
+  for (int j = 0; j < m; ++j) {
+    if (cols[j] < 0 || cols[j] >= I) return fail(c, AIGV_ERR_ARG, "%s: column %d (entry %d) outside 0..%d", op, cols[j], j, I - 1);
+    if (j && cols[j] <= cols[j - 1]) return fail(c, AIGV_ERR_ARG, "%s: columns not strictly ascending at entry %d (%d after %d)", op, j, cols[j], cols[j - 1]);
+  }
+  return 0;
+}
+
+static int neuron_rows_arm(const char* op, aigv_ctx* c, aigv_ctx::NeuronRows* st, const int32_t* rows_host, int n, int lo, int hi, const int32_t* cols_host, int m, void* buf_bf16_dev) {
+  if (!c) return fail(c, AIGV_ERR_ARG, "%s: null context", op);
+  if (n < 0 || n > c->cfg.max_tokens) return fail(c, AIGV_ERR_ARG, "%s: %d rows outside 0..max_tokens = %d", op, n, c->cfg.max_tokens);
+  if (n > 0 && !rows_host) return fail(c, AIGV_ERR_ARG, "%s: null row list", op);
+  if (c->cfg.llm_inter % 8) return fail(c, AIGV_ERR_ARG, "%s: the model's intermediate size %d is no multiple of 8", op, c->cfg.llm_inter);
+  if (cols_host) TRY(neuron_cols_check(op, c, cols_host, m, c->cfg.llm_inter));
+  if (n > 0 && hi > lo && (!cols_host || m > 0) && (!buf_bf16_dev || ((uintptr_t)buf_bf16_dev & 15))) return fail(c, AIGV_ERR_ARG, "%s: the device buffer is null or not 16-byte aligned", op);
+  st->all_rows = false;
+  st->rows.assign(rows_host, rows_host + n);
+  st->dense = !cols_host;
+  if (cols_host) st->cols.assign(cols_host, cols_host + m); else st->cols.clear();
+  st->lo = lo; st->hi = hi;
+  st->buf = (bf16_t*)buf_bf16_dev;
+  st->armed = true;
+  return 0;
+}
+
+int aigv_neuron_capture_arm(aigv_ctx* c, const int32_t* rows_host, int n, int lo, int hi, const int32_t* cols_host, int m, void* out_bf16_dev) {
+  return neuron_rows_arm("aigv_neuron_capture_arm", c, c ? &c->neuron_cap : nullptr, rows_host, n, lo, hi, cols_host, m, out_bf16_dev);
+}
+
+int aigv_neuron_patch_arm(aigv_ctx* c, const int32_t* rows_host, int n, int lo, int hi, const int32_t* cols_host, int m, const void* values_bf16_dev) {
+  return neuron_rows_arm("aigv_neuron_patch_arm", c, c ? &c->neuron_patch : nullptr, rows_host, n, lo, hi, cols_host, m, const_cast<void*>(values_bf16_dev));
+}
+
+int aigv_neuron_scale_arm(aigv_ctx* c, const int32_t* rows_host, int n, const float* layer_scale_host, const int32_t* sel_layers_host, const int32_t* sel_cols_host,
+                          const float* sel_factors_host, int m) {
+  const char* op = "aigv_neuron_scale_arm";
+  if (!c) return fail(c, AIGV_ERR_ARG, "%s: null context", op);
+  const int L = c->cfg.llm_layers, I = c->cfg.llm_inter;
+  if (rows_host && (n < 0 || n > c->cfg.max_tokens)) return fail(c, AIGV_ERR_ARG, "%s: %d rows outside 0..max_tokens = %d", op, n, c->cfg.max_tokens);
+  if (I % 8) return fail(c, AIGV_ERR_ARG, "%s: the model's intermediate size %d is no multiple of 8", op, I);
+  if (m < 0 || m > AIGV_MAX_NEURON_SEL) return fail(c, AIGV_ERR_ARG, "%s: %d selected neurons outside 0..%d", op, m, AIGV_MAX_NEURON_SEL);
+  if (m > 0 && (!sel_layers_host || !sel_cols_host || !sel_factors_host)) return fail(c, AIGV_ERR_ARG, "%s: null selection list", op);
+  if (!layer_scale_host && m == 0 && !sel_layers_host) return fail(c, AIGV_ERR_ARG, "%s: neither a per-layer table nor a selection", op);
+  if (layer_scale_host)
+    for (int l = 0; l < L; ++l) if (layer_scale_host[l] != layer_scale_host[l]) return fail(c, AIGV_ERR_ARG, "%s: layer_scale[%d] is NaN", op, l);
+  std::vector<int32_t> begin(L + 1, 0);
+  for (int j = 0; j < m; ++j) {
+    const int l = sel_layers_host[j], col = sel_cols_host[j];
+    if (l < 0 || l >= L) return fail(c, AIGV_ERR_ARG, "%s: layer %d (entry %d) outside 0..%d", op, l, j, L - 1);
+    if (col < 0 || col >= I) return fail(c, AIGV_ERR_ARG, "%s: column %d (entry %d) outside 0..%d", op, col, j, I - 1);
+    if (j && (l < sel_layers_host[j - 1] || (l == sel_layers_host[j - 1] && col <= sel_cols_host[j - 1])))
+      return fail(c, AIGV_ERR_ARG, "%s: the selection is not strictly ascending in (layer, column) at entry %d", op, j);
+    if (sel_factors_host[j] != sel_factors_host[j]) return fail(c, AIGV_ERR_ARG, "%s: factor %d is NaN", op, j);
+    ++begin[l + 1];
+  }
+  for (int l = 0; l < L; ++l) begin[l + 1] += begin[l];
+  aigv_ctx::NeuronRows& st = c->neuron_scale;
+  st.all_rows = !rows_host;
+  if (rows_host) st.rows.assign(rows_host, rows_host + n); else st.rows.clear();
+  if (layer_scale_host) st.layer_scale.assign(layer_scale_host, layer_scale_host + L); else st.layer_scale.clear();
+  st.dense = m == 0;
+  if (m > 0) { st.cols.assign(sel_cols_host, sel_cols_host + m); st.factors.assign(sel_factors_host, sel_factors_host + m); st.sel_begin = begin; }
+  else { st.cols.clear(); st.factors.clear(); st.sel_begin.clear(); }
+  st.lo = 0; st.hi = L; st.buf = nullptr;
+  st.armed = true;
+  return 0;
+}
+
 // Continue the sequences kept by aigv_llm_prefill(keep_kv = 1) with new TEXT tokens: causal attention of the new rows over the
 // cached keys plus themselves.  commit = 0 leaves the cache lengths where they were, so several continuations of ONE prefix
 // (the four quality-perspective questions behind the same video tokens) can be scored one after the other.
@@ -641,7 +819,11 @@ int aigv_llm_extend(aigv_ctx* c, const int64_t* ids, const int32_t* cu, int B, c
   const bool lensing = c->lens.armed;
   const bool patching = c->stream_patch.armed, capturing = c->stream_cap.armed;
   const bool h_scaling = c->head_scale.armed, h_patching = c->head_patch.armed, h_capturing = c->head_cap.armed;
+  const bool n_scaling = c->neuron_scale.armed, n_patching = c->neuron_patch.armed, n_capturing = c->neuron_cap.armed;
   DisarmScope disarm(c);
+  if (n_scaling || n_patching || n_capturing)
+    return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: a neuron %s is armed (%s): the continuation pass takes none, only aigv_llm_prefill does", n_scaling ? "scale" : n_patching ? "patch" : "capture",
+                n_scaling ? "aigv_neuron_scale_arm" : n_patching ? "aigv_neuron_patch_arm" : "aigv_neuron_capture_arm");
   if (h_scaling || h_patching || h_capturing)
     return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: a head %s is armed (%s): the continuation pass takes none, only aigv_llm_prefill does", h_scaling ? "scale" : h_patching ? "patch" : "capture",
                 h_scaling ? "aigv_head_scale_arm" : h_patching ? "aigv_head_patch_arm" : "aigv_head_capture_arm");

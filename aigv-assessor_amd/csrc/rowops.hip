@@ -292,6 +292,44 @@ __global__ __launch_bounds__(256) void head_rows_kernel(bf16_t* __restrict__ ao,
   }
 }
 
+// MLP neuron knock-out and neuron patching (aigv_neuron_capture_arm / aigv_neuron_patch_arm / aigv_neuron_scale_arm): rows idx[i] (idx null: row i) of the
+// SwiGLU output act [.., I] - what w2 consumes - against slice `layer` of a side buffer whose element (si, l) sits at side + (si * n_layers + l) * W,
+// si = sidx[i] (sidx null: i).  One workgroup per row, two column forms.  Dense (cols null, W = I): 16-byte chunks; NEURON_SCALE multiplies by the one
+// factor `dense_factor`.  Sparse (cols: int32 [W], strictly ascending): lane j handles column cols[j] against element j of the compact side row, a 2-byte
+// load and store each - two selected columns may share a dword, and a lane stores its own 16 bits only; NEURON_SCALE multiplies by factors[j], and a
+// factor of exactly 1 neither reads nor writes its element.  NEURON_CAPTURE: side = act, NEURON_PATCH: act = side - bit copies, a NaN or Inf payload
+// travels unchanged; NEURON_SCALE: act = bf16(fp32(act) * s), the Linear's rounding (f2bf; 0 * Inf = NaN as in torch) - the side buffer is not touched.
+template <int MODE>
+__global__ __launch_bounds__(256) void neuron_rows_kernel(bf16_t* __restrict__ act, int ld, const int32_t* __restrict__ idx, const int32_t* __restrict__ sidx,
+                                                          bf16_t* __restrict__ side, int n_layers, int layer, int W, const int32_t* __restrict__ cols,
+                                                          const float* __restrict__ factors, float dense_factor) {
+  const int i = blockIdx.x;
+  bf16_t* arow = act + (size_t)(idx ? idx[i] : i) * ld;
+  bf16_t* brow = MODE == NEURON_SCALE ? nullptr : side + ((size_t)(sidx ? sidx[i] : i) * n_layers + layer) * W;
+  if (!cols) {
+    for (int c = threadIdx.x; c < (W >> 3); c += 256) {
+      if (MODE == NEURON_CAPTURE) *(u16x8*)(brow + (c << 3)) = *(const u16x8*)(arow + (c << 3));
+      else if (MODE == NEURON_PATCH) *(u16x8*)(arow + (c << 3)) = *(const u16x8*)(brow + (c << 3));
+      else {
+        u16x8 x = *(const u16x8*)(arow + (c << 3));
+#pragma unroll
+        for (int e = 0; e < 8; ++e) x[e] = f2bf(bf2f(x[e]) * dense_factor);
+        *(u16x8*)(arow + (c << 3)) = x;
+      }
+    }
+    return;
+  }
+  for (int j = threadIdx.x; j < W; j += 256) {
+    const int col = cols[j];
+    if (MODE == NEURON_CAPTURE) brow[j] = arow[col];
+    else if (MODE == NEURON_PATCH) arow[col] = brow[j];
+    else {
+      const float f = factors[j];
+      if (f != 1.0f) arow[col] = f2bf(bf2f(arow[col]) * f);
+    }
+  }
+}
+
 // ---- RoPE in place (modeling_internlm2.py:247-261): out = bf16(bf16(x*cos) + bf16(rot(x)*sin)) ---------
 // qkv row layout: n_groups x slots_per_group x D; slots [0, n_rot) of every group are rotated (q heads + K).
 // cos/sin tables are [max_pos, D/2] bf16 (the second half of the reference's table repeats the first).
@@ -626,6 +664,22 @@ hipError_t aigv_launch_head_rows(bf16_t* ao, int ld, const int32_t* idx, int n, 
   if (mode == HEAD_CAPTURE) hipLaunchKernelGGL(head_rows_kernel<HEAD_CAPTURE>, dim3(n), dim3(256), 0, s, ao, ld, idx, side, n_layers, layer, H, d_shift, heads, sc);
   else if (mode == HEAD_PATCH) hipLaunchKernelGGL(head_rows_kernel<HEAD_PATCH>, dim3(n), dim3(256), 0, s, ao, ld, idx, side, n_layers, layer, H, d_shift, heads, sc);
   else if (mode == HEAD_SCALE) hipLaunchKernelGGL(head_rows_kernel<HEAD_SCALE>, dim3(n), dim3(256), 0, s, ao, ld, idx, side, 1, 0, H, d_shift, heads, sc);
+  else return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
+hipError_t aigv_launch_neuron_rows(bf16_t* act, int ld, const int32_t* idx, const int32_t* sidx, int n, bf16_t* side, int n_layers, int layer, int I,
+                                   const int32_t* cols, int m, int mode, const float* factors, float dense_factor, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (I < 8 || I % 8 || ld % 8 || ld < I || !act || ((uintptr_t)act & 15)) return hipErrorInvalidValue;
+  if (cols ? (m < 0 || m > I) : m != 0) return hipErrorInvalidValue;
+  if (mode == NEURON_SCALE ? (cols && !factors) : (!side || ((uintptr_t)side & 15) || n_layers < 1 || layer < 0 || layer >= n_layers)) return hipErrorInvalidValue;
+  if (cols && m == 0) return hipSuccess;                                   // no column selected: nothing is launched
+  if (mode == NEURON_SCALE && !cols && dense_factor == 1.0f) return hipSuccess;   // exactly 1: the row is not touched - no read, no write
+  const int W = cols ? m : I;
+  if (mode == NEURON_CAPTURE) hipLaunchKernelGGL(neuron_rows_kernel<NEURON_CAPTURE>, dim3(n), dim3(256), 0, s, act, ld, idx, sidx, side, n_layers, layer, W, cols, factors, 1.0f);
+  else if (mode == NEURON_PATCH) hipLaunchKernelGGL(neuron_rows_kernel<NEURON_PATCH>, dim3(n), dim3(256), 0, s, act, ld, idx, sidx, side, n_layers, layer, W, cols, factors, 1.0f);
+  else if (mode == NEURON_SCALE) hipLaunchKernelGGL(neuron_rows_kernel<NEURON_SCALE>, dim3(n), dim3(256), 0, s, act, ld, idx, nullptr, nullptr, 1, 0, W, cols, factors, dense_factor);
   else return hipErrorInvalidValue;
   return hipGetLastError();
 }

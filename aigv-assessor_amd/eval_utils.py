@@ -447,6 +447,138 @@ def head_trace(model, *, clean, corrupt, layers=None, heads=None, rows=None, **r
     return res
 
 
+def _once_per_batch(model, pixel_values, B, readout_kwargs):
+    """InternViT and the SlowFast branch run ONCE for a sweep: -> (``visual_tokens``, ``motion_feature``, the other keyword arguments)."""
+    readout_kwargs = dict(readout_kwargs)
+    motion_feature = readout_kwargs.pop("motion_feature", None)
+    if motion_feature is None:
+        motion_feature = model.motion_feature(pixel_values, B)
+    return model.vit_tokens(pixel_values), motion_feature, readout_kwargs
+
+
+def _knocked(res, outs, B, shape, rows):
+    """``score1`` / ``knocked`` / ``delta`` of a knock-out sweep whose passes behind the base one are ``outs[1:]`` (``head_knockout``'s convention)."""
+    import torch
+    if "score1" in outs[0]:
+        base = outs[0]["score1"].float()
+        knocked = torch.stack([o["score1"].float() for o in outs[1:]], 1).view(B, *shape) if len(outs) > 1 else base.new_zeros(B, *shape)
+        if rows is not None:
+            knocked = knocked.masked_fill((~rows.any(-1)).view(B, *([1] * len(shape))).to(knocked.device), float("nan"))
+        res.update(score1=base, knocked=knocked, delta=base.view(B, *([1] * len(shape))) - knocked)
+    return res
+
+
+def mlp_knockout(model, *, pixel_values, input_ids, attention_mask, image_flags, labels=None, layers=None, rows=None, **readout_kwargs):
+    """WHICH MLP matters: the whole-block knock-out.  The batch is scored once as it is and once per layer with every neuron of that layer's MLP
+    multiplied by 0 in front of its ``w2`` (``forward(neuron_scale=NeuronScale(scale, rows=rows))``, ``scale`` [L] all ones but that entry) - the
+    MLP then adds nothing to the stream there.  ``layers``: the layers swept (default: all); ``rows``: an optional bool [B, N] mask that restricts
+    the knock-out to those rows (None: every row).  In a row-trimmed last layer only the consumed rows have an MLP to knock out.  InternViT and
+    the SlowFast branch run ONCE.  Beside ``head_knockout`` (all heads of a layer) this answers, per layer, whether attention or the MLP carries
+    the score.
+
+    Returns a dict: ``outs`` - the base result dict, then one per layer; ``layers``; and for a stage-2 model ``score1`` [B], ``knocked`` [B, L']
+    (NaN where ``rows`` selects no row of the clip) and ``delta`` = ``score1[:, None] - knocked``."""
+    import torch
+    from .readouts import NeuronScale
+    B = int(input_ids.shape[0])
+    L = int(model.config.llm_config.num_hidden_layers)
+    layers = list(range(L)) if layers is None else [int(l) for l in layers]
+    if any(not 0 <= l < L for l in layers):
+        raise ValueError(f"mlp_knockout: layers {layers} outside 0..{L - 1}")
+    rows = None if rows is None else rows.detach().to("cpu").bool()
+    tokens, motion_feature, readout_kwargs = _once_per_batch(model, pixel_values, B, readout_kwargs)
+    common = dict(input_ids=input_ids, attention_mask=attention_mask, image_flags=image_flags, labels=labels, visual_tokens=tokens,
+                  motion_feature=motion_feature, **readout_kwargs)
+    outs = [model.forward(**common)]
+    for l in layers:
+        scale = torch.ones(L)
+        scale[l] = 0.0
+        outs.append(model.forward(neuron_scale=NeuronScale(scale, None, rows), **common))
+    return _knocked({"outs": outs, "layers": layers}, outs, B, (len(layers),), rows)
+
+
+def neuron_knockout(model, neurons, *, pixel_values, input_ids, attention_mask, image_flags, labels=None, rows=None, **readout_kwargs):
+    """WHICH NEURONS matter: the single-neuron ablation.  ``neurons``: integer tensor (or list of pairs) [m, 2] of (layer, neuron).  The batch is
+    scored once as it is and once per listed pair with that neuron multiplied by 0 (``forward(neuron_scale=NeuronScale([0.], [[l, j]], rows))``).
+    ``rows`` and the once-per-batch front end as in ``mlp_knockout``.
+
+    Returns a dict: ``outs`` - the base result dict, then one per pair; ``neurons`` (host int64 [m, 2]); and for a stage-2 model ``score1`` [B],
+    ``knocked`` [B, m] and ``delta`` = ``score1[:, None] - knocked``."""
+    import torch
+    from .readouts import NeuronScale
+    B = int(input_ids.shape[0])
+    l = model.config.llm_config
+    neurons = torch.as_tensor(neurons).detach().to("cpu")
+    if neurons.is_floating_point() or neurons.dtype == torch.bool or neurons.dim() != 2 or int(neurons.shape[1]) != 2:
+        raise ValueError("neuron_knockout: neurons must be an integer tensor [m, 2] of (layer, neuron) pairs")
+    neurons = neurons.to(torch.long)
+    if neurons.numel() and (int(neurons.min()) < 0 or int(neurons[:, 0].max()) >= l.num_hidden_layers or int(neurons[:, 1].max()) >= l.intermediate_size):
+        raise ValueError(f"neuron_knockout: a (layer, neuron) pair outside layers 0..{l.num_hidden_layers - 1}, neurons 0..{l.intermediate_size - 1}")
+    rows = None if rows is None else rows.detach().to("cpu").bool()
+    tokens, motion_feature, readout_kwargs = _once_per_batch(model, pixel_values, B, readout_kwargs)
+    common = dict(input_ids=input_ids, attention_mask=attention_mask, image_flags=image_flags, labels=labels, visual_tokens=tokens,
+                  motion_feature=motion_feature, **readout_kwargs)
+    outs = [model.forward(**common)]
+    for pair in neurons:
+        outs.append(model.forward(neuron_scale=NeuronScale(torch.zeros(1), pair[None], rows), **common))
+    return _knocked({"outs": outs, "neurons": neurons}, outs, B, (int(neurons.shape[0]),), rows)
+
+
+def rank_neurons(clean, corrupt, top: int):
+    """The ranking ``neuron_trace`` patches by: ``clean`` / ``corrupt`` - two captures [n, W, I] of the same rows - -> int64 [W, top]: per layer the
+    neurons with the largest |clean - corrupt|, taken in fp32 and summed over the n rows (all clips together), largest first; among equals the
+    lower neuron number first.  A NaN difference (a row the trimmed last layer does not consume) counts as 0."""
+    import torch
+    diff = torch.nan_to_num((clean.float() - corrupt.float()).abs(), nan=0.0, posinf=float("inf")).sum(0)      # [W, I]
+    return torch.sort(diff, dim=-1, descending=True, stable=True).indices[:, :int(top)].cpu()
+
+
+def neuron_trace(model, *, clean, corrupt, layers=None, top: int = 16, rows=None, **readout_kwargs):
+    """WHICH NEURONS carry the quality from one clip to another: neuron-level activation patching between two clips that share a token layout
+    (``causal_trace``'s conditions - anything else is a ValueError).  Both batches run once, capturing the MLP neurons of the tokens ``rows``
+    selects (bool [B, N]; default: the score row) over the window ``layers`` = (lo, hi) (default: every layer).  Per layer the neurons are ranked by
+    |clean - corrupt| (``rank_neurons``), and for each of the ``top`` first the clean neuron is patched into the corrupt batch over those rows in
+    one sparse patch pass (``forward(neuron_patch=NeuronPatch(rows, values, (l, l + 1), index, neurons=[j]))``).  The corrupt clip's InternViT and
+    SlowFast branch run ONCE.
+
+    Returns a dict: ``outs`` - the clean result dict, the corrupt one, then one per layer and rank, layer-major; ``layers`` (the window);
+    ``neurons`` (int64 [hi - lo, top]); and for a stage-2 model ``clean_score`` / ``corrupt_score`` [B], ``score`` [B, hi - lo, top] and
+    ``restored`` = ``restored_fraction(score, clean_score, corrupt_score)``."""
+    import torch
+    from .readouts import NeuronPatch
+    B, N = _same_layout("neuron_trace", model, clean, corrupt)
+    L, I = int(model.config.llm_config.num_hidden_layers), int(model.config.llm_config.intermediate_size)
+    lo, hi = (0, L) if layers is None else (int(layers[0]), int(layers[1]))
+    top = int(top)
+    if not 0 <= lo <= hi <= L or not 1 <= top <= I:
+        raise ValueError(f"neuron_trace: layers ({lo}, {hi}) outside 0 <= lo <= hi <= {L} or top = {top} outside 1..{I}")
+    if rows is None:
+        rows = model.segment_masks(clean["input_ids"], clean.get("attention_mask"), clean["image_flags"])["score_row"]
+    rows = rows.detach().to("cpu").bool()
+    if tuple(rows.shape) != (B, N):
+        raise ValueError(f"neuron_trace: rows has shape {tuple(rows.shape)}, input_ids {(B, N)}")
+    donor = model.forward(**clean, return_neurons=rows, neuron_layers=(lo, hi), **readout_kwargs)         # [n, hi - lo, I]
+    index = donor["neurons_index"].cpu()
+    pixel_values = corrupt["pixel_values"]
+    common = {k: v for k, v in corrupt.items() if k != "pixel_values"}
+    if common.get("motion_feature") is None:
+        common["motion_feature"] = model.motion_feature(pixel_values, B)
+    common.update(visual_tokens=model.vit_tokens(pixel_values), **readout_kwargs)
+    base = model.forward(**common, return_neurons=rows, neuron_layers=(lo, hi))
+    ranked = rank_neurons(donor["neurons"], base["neurons"], top)
+    outs = [donor, base]
+    for w in range(hi - lo):
+        for j in ranked[w].tolist():
+            values = donor["neurons"][:, w:w + 1, j:j + 1].contiguous()
+            outs.append(model.forward(neuron_patch=NeuronPatch(rows, values, (lo + w, lo + w + 1), index, torch.tensor([j])), **common))
+    res = {"outs": outs, "layers": (lo, hi), "neurons": ranked}
+    if "score1" in outs[0]:
+        clean_score, corrupt_score = outs[0]["score1"].float(), outs[1]["score1"].float()
+        score = torch.stack([o["score1"].float() for o in outs[2:]], 1).view(B, hi - lo, top) if len(outs) > 2 else clean_score.new_zeros(B, hi - lo, top)
+        res.update(score=score, clean_score=clean_score, corrupt_score=corrupt_score, restored=restored_fraction(score, clean_score, corrupt_score))
+    return res
+
+
 def frame_ablation_generate(
 model, *, pixel_values, input_ids, attention_mask, image_flags, max_new_tokens, candidate_ids=None, **gen):
     """WHAT IF a frame were not there, in WORDS: the reply to the stage-2 prompt as it is and once per unit with that unit's tokens hidden from

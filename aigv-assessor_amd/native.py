@@ -140,6 +140,9 @@ PROTOTYPES = {
     "aigv_head_capture_arm": (_I, [_P, _I32P, _I, _I, _I, _P]),
     "aigv_head_patch_arm": (_I, [_P, _I32P, _I, _I, _I, C.POINTER(C.c_uint64), _P]),
     "aigv_head_scale_arm": (_I, [_P, _I32P, _I, C.POINTER(C.c_float)]),
+    "aigv_neuron_capture_arm": (_I, [_P, _I32P, _I, _I, _I, _I32P, _I, _P]),
+    "aigv_neuron_patch_arm": (_I, [_P, _I32P, _I, _I, _I, _I32P, _I, _P]),
+    "aigv_neuron_scale_arm": (_I, [_P, _I32P, _I, C.POINTER(C.c_float), _I32P, _I32P, C.POINTER(C.c_float), _I]),
     "aigv_op_attention_drop_rows": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, C.c_int64, _P, _I, _I, _F, _F, _P, _P, _P, _I, _I, _P, _P, _I, _P]),
     "aigv_op_kv_store": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "aigv_op_attention_probe": (_I, [_P, _I, _P, _I, _I32P, _I, _I, _I, _I, _I, C.c_int64, _I32P, _I, _P, _P, _I, _I32P, _I, _P, _P, _I, _I, _P, _P]),
@@ -173,6 +176,7 @@ PROTOTYPES = {
     "aigv_op_scatter_rows": (_I, [_P, _P, _I, _P, _I, _I, _P]),
     "aigv_op_stream_rows": (_I, [_P, _I, _I, _I32P, _I, _P, _P, _I, _I, _I, _I, _P]),
     "aigv_op_head_rows": (_I, [_P, _I, _I, _I32P, _I, _P, _P, _I, _I, _I, _I, _I, C.c_uint64, C.POINTER(C.c_float), _P]),
+    "aigv_op_neuron_rows": (_I, [_P, _I, _I, _I32P, _I, _P, _I32P, _P, _I, _P, _I, _I, _I, _I32P, _I, _P, _I, C.POINTER(C.c_float), _P, _F, _P]),
     "aigv_op_cls_rows": (_I, [_P, _P, _I, _I, _I, _P]),
     "aigv_op_write_ints": (_I, [_I32P, _I, _P, _P]),
     "aigv_op_frame_ingest": (_I, [_P, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P]),

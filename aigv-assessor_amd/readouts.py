@@ -2,7 +2,8 @@
 depth lens, a capture of residual-stream rows (``return_stream`` / ``stream_depths``) or of per-head attention outputs (``return_heads`` /
 ``head_layers``) - and whether it runs under a key-drop mask (``key_drop`` with its qualifiers ``key_drop_rows`` / ``key_drop_layers``), a patch of the
 stream (``stream_patch``), a patch of head outputs (``head_patch``) or a per-head scale (``head_scale``): not read-outs, but per-call options that
-travel the same way.
+travel the same way.  The MLP's side of a layer has the same three: a capture of the neurons ``w2`` consumes (``return_neurons`` / ``neuron_layers`` /
+``neuron_ids``), a patch (``neuron_patch``) and a scale (``neuron_scale``).
 
 This module is the one place that knows that decision.  A new read-out adds, HERE: a member to ``ReadOuts`` and its check to
 ``ReadOuts.parse``; the element it appends to a graph's host key to ``ReadOuts.key_tail``; its keyword to ``forward_kwargs``; and - when it
@@ -253,6 +254,116 @@ def head_bits(heads: torch.Tensor) -> list:
     return [sum(1 << h for h, on in enumerate(row) if on) for row in heads.tolist()]
 
 
+MAX_NEURON_SEL = 4096     # a sparse neuron list: at most this many entries per option (the context's device tables)
+
+
+@dataclass(frozen=True, eq=False)
+class NeuronPatch:
+    """``forward(neuron_patch=...)``: overwrite MLP neurons - the row ``w2`` of a layer consumes.  ``rows``: bool or integer tensor [B, N] laid out
+    like ``input_ids`` - the tokens patched; ``layers`` = (lo, hi), 0 <= lo <= hi <= L; ``values``: bf16 [n, hi - lo, I] - or [n, hi - lo, m] with
+    ``neurons`` - on the device or the host, laid out exactly like the ``neurons`` that ``forward(return_neurons=rows, neuron_layers=layers,
+    neuron_ids=neurons)`` returns; ``index``: optionally the donor's ``neurons_index`` (int64 [n, 2]), checked pair by pair against the
+    recipient's; ``neurons``: integer tensor [m], strictly ascending inside [0, I) - the neurons overwritten (None: all of them); an unselected
+    neuron is neither read nor written."""
+    rows: torch.Tensor
+    values: torch.Tensor
+    layers: tuple
+    index: Optional[torch.Tensor] = None
+    neurons: Optional[torch.Tensor] = None
+
+
+@dataclass(frozen=True, eq=False)
+class NeuronScale:
+    """``forward(neuron_scale=...)``: multiply MLP neurons by a factor.  With ``neurons=None``, ``scale`` is a float tensor [L]: every neuron of
+    layer l becomes ``bf16(fp32(x) * scale[l])`` - 0 knocks the MLP block out.  Otherwise ``neurons`` is an integer tensor [m, 2] of unique
+    (layer, neuron) pairs and ``scale`` a float tensor [m].  A factor that is exactly 1 leaves its neurons untouched; no NaN.  ``rows``: optional
+    bool or integer tensor [B, N] - the rows scaled (None: every row the pass runs)."""
+    scale: torch.Tensor
+    neurons: Optional[torch.Tensor] = None
+    rows: Optional[torch.Tensor] = None
+
+
+def _neuron_ids(name: str, t, n_inter: Optional[int] = None) -> torch.Tensor:
+    if not torch.is_tensor(t) or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool or t.dim() != 1:
+        raise ValueError(f"{name}: expected an integer tensor [m] of neuron numbers")
+    t = t.detach().to("cpu").to(torch.long).contiguous()
+    m = int(t.numel())
+    if m > MAX_NEURON_SEL:
+        raise ValueError(f"{name}: {m} neurons, at most {MAX_NEURON_SEL} per option")
+    if m and (int(t.min()) < 0 or (n_inter is not None and int(t.max()) >= n_inter)):
+        raise ValueError(f"{name}: neuron numbers outside 0..{'I - 1' if n_inter is None else n_inter - 1}")
+    if m > 1 and not bool((t[1:] > t[:-1]).all()):
+        raise ValueError(f"{name}: neuron numbers must be strictly ascending")
+    return t
+
+
+def neuron_options(return_neurons=None, neuron_layers=None, neuron_ids=None, neuron_patch=None, neuron_scale=None, ids_shape=None,
+                   n_layers: Optional[int] = None, n_inter: Optional[int] = None):
+    """``return_neurons`` / ``neuron_layers`` / ``neuron_ids`` / ``neuron_patch`` / ``neuron_scale`` -> (None or a HOST bool mask [B, N], None or
+    (lo, hi), None or a HOST int64 [m], None or a ``NeuronPatch`` whose ``rows`` is such a mask, whose ``layers`` is a checked pair, whose ``index``
+    is a HOST int64 [n, 2] and whose ``neurons`` is a HOST int64 [m] or None, None or a ``NeuronScale`` whose ``scale`` is a HOST fp32 [L] (or
+    [m], beside ``neurons``: a HOST int64 [m, 2] sorted by (layer, neuron)) and whose ``rows`` is such a mask or None).  Layer l, 0 <= l < L, names
+    the input of that layer's ``w2``; ``neuron_layers`` defaults to (0, L); it and ``neuron_ids`` need ``return_neurons``.  Shapes, dtypes, windows
+    and lists are checked here (those that need the model's sizes only when they are given); counts and (clip, position) pairs where the plan is
+    (``ScoringPass._neuron_patch_plan``)."""
+    rows = window = ids = patch = scale = None
+    if return_neurons is not None:
+        rows = _token_mask("return_neurons", return_neurons, ids_shape)
+        window = _depth_window("neuron_layers", neuron_layers, n_layers) if neuron_layers is not None else (0, n_layers) if n_layers is not None else None
+        ids = None if neuron_ids is None else _neuron_ids("neuron_ids", neuron_ids, n_inter)
+    elif neuron_layers is not None or neuron_ids is not None:
+        raise ValueError(f"{'neuron_layers' if neuron_layers is not None else 'neuron_ids'}: qualifies return_neurons and needs one")
+    if neuron_patch is not None:
+        p = neuron_patch
+        if not isinstance(p, NeuronPatch):
+            raise ValueError(f"neuron_patch: expected a readouts.NeuronPatch, got {type(p).__name__}")
+        lo, hi = _depth_window("neuron_patch: layers", p.layers, n_layers)
+        cols = None if p.neurons is None else _neuron_ids("neuron_patch: neurons", p.neurons, n_inter)
+        width = n_inter if cols is None else int(cols.numel())
+        v = p.values
+        if not torch.is_tensor(v) or v.dtype != torch.bfloat16 or v.dim() != 3 or int(v.shape[1]) != hi - lo or (width is not None and int(v.shape[2]) != width):
+            raise ValueError(f"neuron_patch: values must be a bf16 tensor [n, hi - lo = {hi - lo}, {'I' if cols is None else 'm'}{'' if width is None else f' = {width}'}] "
+                             f"laid out like captured neurons, got {tuple(v.shape) if torch.is_tensor(v) else type(v).__name__}"
+                             f"{' ' + str(v.dtype) if torch.is_tensor(v) else ''}")
+        idx = p.index
+        if idx is not None:
+            if not torch.is_tensor(idx) or idx.is_floating_point() or idx.dtype == torch.bool or idx.dim() != 2 or int(idx.shape[1]) != 2:
+                raise ValueError("neuron_patch: index must be an integer tensor [n, 2] of (clip, position) pairs (a donor's neurons_index)")
+            idx = idx.detach().to("cpu").to(torch.long).contiguous()
+        patch = NeuronPatch(_token_mask("neuron_patch: rows", p.rows, ids_shape), v, (lo, hi), idx, cols)
+    if neuron_scale is not None:
+        q = neuron_scale
+        if not isinstance(q, NeuronScale):
+            raise ValueError(f"neuron_scale: expected a readouts.NeuronScale, got {type(q).__name__}")
+        t, sel = q.scale, q.neurons
+        got = f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}{' ' + str(t.dtype) if torch.is_tensor(t) else ''}"
+        if sel is None:
+            if not torch.is_tensor(t) or not t.is_floating_point() or t.dim() != 1 or (n_layers is not None and int(t.shape[0]) != n_layers):
+                raise ValueError(f"neuron_scale: scale must be a float tensor [L{'' if n_layers is None else f' = {n_layers}'}] when neurons is None, got {got}")
+        else:
+            if not torch.is_tensor(sel) or sel.is_floating_point() or sel.dtype == torch.bool or sel.dim() != 2 or int(sel.shape[1]) != 2:
+                raise ValueError("neuron_scale: neurons must be an integer tensor [m, 2] of (layer, neuron) pairs")
+            sel = sel.detach().to("cpu").to(torch.long).contiguous()
+            m = int(sel.shape[0])
+            if m > MAX_NEURON_SEL:
+                raise ValueError(f"neuron_scale: {m} neurons, at most {MAX_NEURON_SEL} per option")
+            if not torch.is_tensor(t) or not t.is_floating_point() or tuple(t.shape) != (m,):
+                raise ValueError(f"neuron_scale: scale must be a float tensor [m = {m}] beside neurons [m, 2], got {got}")
+            if m and (int(sel.min()) < 0 or (n_layers is not None and int(sel[:, 0].max()) >= n_layers) or (n_inter is not None and int(sel[:, 1].max()) >= n_inter)):
+                raise ValueError(f"neuron_scale: a (layer, neuron) pair outside layers 0..{'L - 1' if n_layers is None else n_layers - 1}, "
+                                 f"neurons 0..{'I - 1' if n_inter is None else n_inter - 1}")
+            if int(torch.unique(sel, dim=0).shape[0]) != m:
+                raise ValueError("neuron_scale: the (layer, neuron) pairs must be unique")
+        t = t.detach().to("cpu").to(torch.float32).contiguous()
+        if torch.isnan(t).any():
+            raise ValueError(f"neuron_scale: scale[{int(torch.isnan(t).nonzero()[0])}] is NaN")
+        if sel is not None and sel.shape[0]:        # the C ABI's order: by layer, then by neuron
+            order = torch.argsort(sel[:, 0] * (int(sel[:, 1].max()) + 1) + sel[:, 1])
+            sel, t = sel[order].contiguous(), t[order].contiguous()
+        scale = NeuronScale(t, sel, None if q.rows is None else _token_mask("neuron_scale: rows", q.rows, ids_shape))
+    return rows, window, ids, patch, scale
+
+
 _NAN = float("nan")
 # every result laid out per label position, [B (N - 1)] + width: name in the result dict, the ``ReadOuts`` member that switches it on and gives
 # its trailing width (None: always there), dtype, fill wherever the row is not an answer row
@@ -277,6 +388,12 @@ class ReadOuts:
     key_drop_rows: Optional[torch.Tensor] = None    # host bool [B, N]: ... from these query rows only (None: every row)
     key_drop_layers: Optional[tuple] = None         # (lo, hi): ... in the layers lo <= l < hi only (None: every layer)
     depth_lens: bool = False                    # return_depth_lens: the score row and the token row after every layer (forward only)
+    # (the neuron options stand in front of the stream and head ones: tests/test_head_patch_cpu.py pins that no field follows head_scale)
+    neuron_rows: Optional[torch.Tensor] = None      # return_neurons: host bool [B, N], the tokens whose MLP neurons - the row w2 consumes - are captured (forward only)
+    neuron_layers: Optional[tuple] = None           # (lo, hi): ... at the layers lo <= l < hi (None with neuron_rows None)
+    neuron_ids: Optional[torch.Tensor] = None       # host int64 [m]: ... those neurons only (None: all I of them)
+    neuron_patch: Optional[NeuronPatch] = None      # neurons overwritten between the SwiGLU and w2 of the layers of its window (forward only)
+    neuron_scale: Optional[NeuronScale] = None      # neurons multiplied by a factor per layer or per (layer, neuron) (forward only)
     stream_rows: Optional[torch.Tensor] = None      # return_stream: host bool [B, N], the tokens whose residual-stream rows are captured (forward only)
     stream_depths: Optional[tuple] = None           # (lo, hi): ... at the depths lo <= d < hi (None with stream_rows None)
     stream_patch: Optional[StreamPatch] = None      # rows of the stream overwritten in front of the layers of its window (forward only)
@@ -290,7 +407,8 @@ class ReadOuts:
               return_score_attention: bool = False, attention_segments=None, return_token_attention: bool = False, key_drop=None,
               ids_shape=None, key_drop_rows=None, key_drop_layers=None, n_layers: Optional[int] = None, return_depth_lens: bool = False,
               return_stream=None, stream_depths=None, stream_patch=None, return_heads=None, head_layers=None, head_patch=None, head_scale=None,
-              n_heads: Optional[int] = None, head_dim: Optional[int] = None) -> "ReadOuts":
+              n_heads: Optional[int] = None, head_dim: Optional[int] = None, return_neurons=None, neuron_layers=None, neuron_ids=None, neuron_patch=None,
+              neuron_scale=None, n_inter: Optional[int] = None) -> "ReadOuts":
         """The record of a call's public keyword arguments, checked.  ``labels=None`` (``forward`` without labels) refuses candidates and top-k;
         the shared-prefix and generate entry points leave the default.  A user segment table is checked where its bins are counted
         (``n_segments``: it needs the shape of ``input_ids``)."""
@@ -302,15 +420,16 @@ class ReadOuts:
             raise ValueError(f"return_depth_lens: at most {MAX_LENS_ROWS} clips per pass, got {int(ids_shape[0])}")
         return cls(bool(return_logprobs), cand, k or None, att, attention_segments if att else None, bool(return_token_attention),
                    key_drop_mask(key_drop, ids_shape, att), rows, window, bool(return_depth_lens),
+                   *neuron_options(return_neurons, neuron_layers, neuron_ids, neuron_patch, neuron_scale, ids_shape, n_layers, n_inter),
                    *stream_options(return_stream, stream_depths, stream_patch, ids_shape, n_layers),
                    *head_options(return_heads, head_layers, head_patch, head_scale, ids_shape, n_layers, n_heads, head_dim))
 
     @property
     def touches_stream(self) -> bool:
-        """A capture or a patch of the residual stream, or a capture, patch or scale of head outputs: such a call runs eagerly under graph replay, as
-        a masked call does."""
+        """A capture or a patch of the residual stream, or a capture, patch or scale of head outputs or of MLP neurons: such a call runs eagerly
+        under graph replay, as a masked call does."""
         return (self.stream_rows is not None or self.stream_patch is not None or self.head_rows is not None or self.head_patch is not None
-                or self.head_scale is not None)
+                or self.head_scale is not None or self.neuron_rows is not None or self.neuron_patch is not None or self.neuron_scale is not None)
 
     @property
     def wants_labels(self) -> bool:
@@ -332,7 +451,7 @@ class ReadOuts:
         that is off: the keys of passes without it are those they always were.  The candidates' VALUES and a user segment table are graph
         INPUT, not key; the candidates' number is in the key with the device inputs' shapes.  k, a user table's bin count (the default
         table follows from the ids, which are in the key) and ld_tok = N are output shapes: another value is another graph.  ``key_drop`` and
-        the stream and head options add nothing: such calls are never captured."""
+        the stream, head and neuron options add nothing: such calls are never captured."""
         S = (self.n_segments(ids_shape) if n_seg is None else n_seg) if self.score_attention else 0
         on = ((self.logprobs, "logprobs"), (self.cand is not None, "candidates"), (self.topk is not None, ("top_logprobs", self.topk)),
               (self.score_attention, ("score_attention", S)), (self.token_attention, ("score_attention_tokens", int(ids_shape[1]))),
@@ -354,7 +473,8 @@ def forward_kwargs(r: ReadOuts) -> dict:
               attention_segments=r.segments, return_token_attention=r.token_attention or None, key_drop=r.key_drop,
               key_drop_rows=r.key_drop_rows, key_drop_layers=r.key_drop_layers, return_depth_lens=r.depth_lens or None,
               return_stream=r.stream_rows, stream_depths=r.stream_depths, stream_patch=r.stream_patch,
-              return_heads=r.head_rows, head_layers=r.head_layers, head_patch=r.head_patch, head_scale=r.head_scale)
+              return_heads=r.head_rows, head_layers=r.head_layers, head_patch=r.head_patch, head_scale=r.head_scale,
+              return_neurons=r.neuron_rows, neuron_layers=r.neuron_layers, neuron_ids=r.neuron_ids, neuron_patch=r.neuron_patch, neuron_scale=r.neuron_scale)
     return {k: v for k, v in kw.items() if v is not None}
 
 

@@ -184,7 +184,7 @@ class ScoringPass:
 
     def _prefill(self, ids_packed, slot, cu, vis, n_vis, motion, score_rows, logit_rows, keep_kv=False, kv_cap=0, probe=None, ld_tok=0, drop_words=None,
                  drop_row_words=None, drop_layers=None, lens=None, stream_capture=None, stream_patch=None, head_capture=None, head_patch=None,
-                 head_scale=None):
+                 head_scale=None, neuron_capture=None, neuron_patch=None, neuron_scale=None):
         b = len(cu) - 1
         T = cu[-1]
         lib, ctx = self._native(n_tokens=T, n_clips=b, out_rows=len(logit_rows), kv_cap=kv_cap)
@@ -228,6 +228,17 @@ class ScoringPass:
         if head_capture is not None:    # (packed rows, lo, hi, device bf16 [n, hi - lo, n_heads, D])
             h_rows, lo, hi, buf = head_capture
             native.check(lib.aigv_head_capture_arm(ctx, i32p(h_rows), int(h_rows.numel()), int(lo), int(hi), native.ptr(buf) if buf.numel() else None), ctx)
+        # neuron_scale / neuron_patch / return_neurons: likewise (cols: host int32 [m] or None - every neuron)
+        f32p = lambda t: C.cast(t.data_ptr(), C.POINTER(C.c_float)) if t is not None and t.numel() else None
+        if neuron_scale is not None:    # (packed rows or None: every row, host fp32 [L] or None, host int32 [m] layers / columns and fp32 [m] factors or None)
+            n_rows, table, sel_l, sel_c, sel_f = neuron_scale
+            native.check(lib.aigv_neuron_scale_arm(ctx, i32p(n_rows), 0 if n_rows is None else int(n_rows.numel()), f32p(table), i32p(sel_l), i32p(sel_c), f32p(sel_f),
+                                                   0 if sel_l is None else int(sel_l.numel())), ctx)
+        for arm, armed in ((lib.aigv_neuron_patch_arm, neuron_patch), (lib.aigv_neuron_capture_arm, neuron_capture)):
+            if armed is not None:       # (packed rows, lo, hi, cols, device bf16 [n, hi - lo, I or m])
+                n_rows, lo, hi, cols, buf = armed
+                native.check(arm(ctx, i32p(n_rows), int(n_rows.numel()), int(lo), int(hi), None if cols is None else C.cast(cols.data_ptr(), native._I32P),
+                                 0 if cols is None else int(cols.numel()), native.ptr(buf) if buf.numel() else None), ctx)
         native.check(lib.aigv_llm_prefill(
             ctx, ids_d.data_ptr(), slot_d.data_ptr(), cu_a, b, native.ptr(vis), n_vis, native.ptr(motion),
             sr_a, native.ptr(score), lr_a, len(logit_rows), amax.data_ptr(), int(keep_kv), native.stream_ptr()), ctx)
@@ -492,6 +503,26 @@ class ScoringPass:
         bits = None if patch.heads is None else readouts.head_bits(patch.heads)
         return (rows, lo, hi, bits, v) if n and hi > lo and (bits is None or any(bits)) else None
 
+    # ---- MLP neuron knock-out and neuron patching (return_neurons / neuron_patch / neuron_scale) --------------------------------------------------
+    def _neuron_patch_plan(self, plan, patch):
+        """``neuron_patch`` checked against the plan, host work only -> None (an empty window, an empty selection or no neuron selected: the plain
+        pass) or (packed rows, lo, hi, host int32 columns or None, the values as given).  ValueError: a count mismatch (both counts), the first
+        differing (clip, position)."""
+        rows, index = self._stream_rows(plan, patch.rows)
+        (lo, hi), v = patch.layers, patch.values
+        n = int(rows.numel())
+        if int(v.shape[0]) != n:
+            raise ValueError(f"neuron_patch: values hold {int(v.shape[0])} rows, the mask selects {n} tokens the pass runs")
+        if patch.index is not None:
+            if int(patch.index.shape[0]) != n:
+                raise ValueError(f"neuron_patch: index holds {int(patch.index.shape[0])} pairs, the mask selects {n} tokens the pass runs")
+            differ = (patch.index != index).any(1).nonzero().flatten()
+            if differ.numel():
+                i = int(differ[0])
+                raise ValueError(f"neuron_patch: pair {i} of index is (clip, position) = {tuple(patch.index[i].tolist())}, the pass's is {tuple(index[i].tolist())}")
+        cols = None if patch.neurons is None else patch.neurons.to(torch.int32).contiguous()
+        return (rows, lo, hi, cols, v) if n and hi > lo and (cols is None or cols.numel()) else None
+
     def forward(self, mos: Optional[torch.Tensor] = None, pixel_values: Optional[torch.Tensor] = None,
                 input_ids: Optional[torch.Tensor] = None, attention_mask: Optional[torch.Tensor] = None,
                 position_ids=None, image_flags: Optional[torch.Tensor] = None, past_key_values=None,
@@ -502,7 +533,9 @@ class ScoringPass:
                 return_token_attention: bool = False, key_drop: Optional[torch.Tensor] = None, key_drop_rows: Optional[torch.Tensor] = None,
                 key_drop_layers: Optional[tuple] = None, return_depth_lens: bool = False, return_stream: Optional[torch.Tensor] = None,
                 stream_depths: Optional[tuple] = None, stream_patch: Optional[readouts.StreamPatch] = None, return_heads: Optional[torch.Tensor] = None,
-                head_layers: Optional[tuple] = None, head_patch: Optional[readouts.HeadPatch] = None, head_scale: Optional[readouts.HeadScale] = None):
+                head_layers: Optional[tuple] = None, head_patch: Optional[readouts.HeadPatch] = None, head_scale: Optional[readouts.HeadScale] = None,
+                return_neurons: Optional[torch.Tensor] = None, neuron_layers: Optional[tuple] = None, neuron_ids: Optional[torch.Tensor] = None,
+                neuron_patch: Optional[readouts.NeuronPatch] = None, neuron_scale: Optional[readouts.NeuronScale] = None):
         """Stage-2 eval pass (modeling_internvl_chat.py:306-488) or, with ``stage=1``, the stage-1 pass
         (internvl_chat_eval1/modeling_internvl_chat.py:250-366).  ``visual_tokens`` optionally supplies
         already all-gathered pre-projector tokens (frame-DP) instead of ``pixel_values``.
@@ -622,7 +655,28 @@ class ScoringPass:
         launched.  In the row-trimmed last layer a capture makes the attention launch cover every row (the consumed rows keep their bits), so a
         capture never returns unwritten memory; a patch or scale of a row the last layer does not consume has no effect.  The options combine with
         each other and with every other option, fp8 mode included; under graph replay a call carrying one runs eagerly.
-        ``eval_utils.head_knockout`` and ``eval_utils.head_trace`` run the sweeps over (layer, head)."""
+        ``eval_utils.head_knockout`` and ``eval_utils.head_trace`` run the sweeps over (layer, head).
+
+        ``return_neurons`` / ``neuron_patch`` / ``neuron_scale`` - WHICH MLP, WHICH NEURONS (causal tracing, Meng et al. 2022; neuron ablation, Geva
+        et al. 2021, Dai et al. 2022): the neurons of layer l, 0 <= l < L - the row that layer's ``w2`` consumes, the output of the fused SwiGLU,
+        bf16 [I] per token, what a forward pre-hook on ``layers[l].feed_forward.w2`` sees - copied out, overwritten, or multiplied by a factor.
+        Inside a layer the order is: ``w1|w3`` + SwiGLU, scale, patch, capture, ``w2``; a capture armed beside the other two returns what ``w2``
+        consumes, and every later layer, the lens, a stream capture and a head capture see the modified pass.  ``return_neurons`` (a mask like
+        ``return_heads``) with ``neuron_layers=(lo, hi)`` (default (0, L)) adds ``neurons`` (bf16 [n, hi - lo, I]) and ``neurons_index`` (int64
+        [n, 2]); ``neuron_ids`` (integer tensor [m], strictly ascending, m <= 4096) narrows it to those neurons: bf16 [n, hi - lo, m] - the sparse
+        form, which is what makes a capture of every frame row at every layer affordable (a dense one is 2 I bytes per row and layer: sized by the
+        caller).  ``neuron_patch=readouts.NeuronPatch(rows, values, layers, index=None, neurons=None)``: ``values`` laid out like a capture; a bit
+        copy, NaN payloads travel unchanged; a neuron not listed is neither read nor written.  ``neuron_scale=readouts.NeuronScale(scale,
+        neurons=None, rows=None)``: ``scale`` float [L] - every neuron of layer l becomes ``bf16(fp32(x) * scale[l])``, 0 the MLP-block knock-out -
+        or, with ``neurons`` long [m, 2] of unique (layer, neuron) pairs, float [m]; over ``rows`` (None: every row the pass runs).  A factor of
+        exactly 1.0 touches nothing; 0 x Inf is NaN, as in torch.  A NaN factor, a wrong shape or window, a list that is not strictly ascending or
+        longer than 4096, a qualifier without ``return_neurons``, a count mismatch (both counts named) and the first differing (clip, position)
+        pair are ValueErrors before anything is launched.  THE ROW-TRIMMED LAST LAYER is not un-trimmed: the value captured, patched or scaled for
+        a row is the input of the ``w2`` launch whose output the pass keeps for it; when layer L - 1 runs for the consumed rows only (the score
+        row and the answer rows), any other selected row has no MLP activation there - a patch or scale of it does nothing and its captured
+        (row, L - 1) slice is NaN, as ``logprob`` is where there is no label.  The options combine with each other and with every other option,
+        fp8 mode included; under graph replay a call carrying one runs eagerly.  ``eval_utils.mlp_knockout``, ``eval_utils.neuron_knockout`` and
+        ``eval_utils.neuron_trace`` run the sweeps."""
         if position_ids is not None or past_key_values is not None:
             raise NotImplementedError("the eval pass takes default positions and no cache, like the reference drivers")
         if self.img_context_token_id is None:
@@ -652,6 +706,14 @@ class ScoringPass:
                 src = visual_tokens if visual_tokens is not None else pixel_values
                 patch_plan = self._plan(input_ids, attention_mask, labels, image_flags, (src.tokens if isinstance(src, VisualAhead) else src).shape[0], full_logits)
             h_patched = self._head_patch_plan(patch_plan, h_patch)
+        _, _, _, n_patch, _ = readouts.neuron_options(return_neurons, neuron_layers, neuron_ids, neuron_patch, neuron_scale, None if input_ids is None else input_ids.shape,
+                                                      n_layers, llm.intermediate_size)
+        n_patched = None
+        if n_patch is not None:         # likewise
+            if patch_plan is None:
+                src = visual_tokens if visual_tokens is not None else pixel_values
+                patch_plan = self._plan(input_ids, attention_mask, labels, image_flags, (src.tokens if isinstance(src, VisualAhead) else src).shape[0], full_logits)
+            n_patched = self._neuron_patch_plan(patch_plan, n_patch)
         if return_depth_lens and self._capture_keep is None:      # likewise: is there a row to read?  (inside a capture the call that led here has checked)
             src = visual_tokens if visual_tokens is not None else pixel_values
             self._depth_lens_rows(self._plan(input_ids, attention_mask, labels, image_flags, (src.tokens if isinstance(src, VisualAhead) else src).shape[0], full_logits),
@@ -661,12 +723,13 @@ class ScoringPass:
                                                 return_score_attention, attention_segments, return_token_attention, key_drop,
                                                 None if input_ids is None else input_ids.shape, key_drop_rows, key_drop_layers, n_layers,
                                                 return_depth_lens, return_stream, stream_depths, stream_patch, return_heads, head_layers, head_patch, head_scale,
-                                                llm.num_attention_heads, llm.head_dim)
+                                                llm.num_attention_heads, llm.head_dim, return_neurons, neuron_layers, neuron_ids, neuron_patch, neuron_scale,
+                                                llm.intermediate_size)
         ro = None
         if self._graph_replay_enabled and self._capture_keep is None:
             ro = parse()
             # (a masked call stays eager and leaves the graph cache as it is: capturing masked passes is out of scope)
-            # (so does a call that captures or patches the residual stream, or captures, patches or scales head outputs)
+            # (so does a call that captures or patches the residual stream, or captures, patches or scales head outputs or MLP neurons)
             out = None if ro.key_drop is not None or ro.touches_stream else self._forward_through_graph(mos, pixel_values, input_ids, attention_mask, image_flags, labels,
                                                                                   motion_feature, visual_tokens, full_logits, ro)
             if out is not None:
@@ -704,12 +767,30 @@ class ScoringPass:
             s_rows = None if ro.head_scale.rows is None else self._stream_rows(plan, ro.head_scale.rows)[0]
             if s_rows is None or s_rows.numel():
                 h_scaled = (s_rows, ro.head_scale.scale)
+        n_capture = neurons_index = n_scaled = None
+        if ro.neuron_rows is not None:          # return_neurons: the buffer the pass fills, [n, hi - lo, I or m]
+            cap_rows, neurons_index = self._stream_rows(plan, ro.neuron_rows)
+            lo, hi = ro.neuron_layers
+            cols = None if ro.neuron_ids is None else ro.neuron_ids.to(torch.int32).contiguous()
+            buf = torch.empty((int(cap_rows.numel()), hi - lo, llm.intermediate_size if cols is None else int(cols.numel())), dtype=torch.bfloat16, device=self.device)
+            if lo < hi == llm.num_hidden_layers and buf.numel():
+                buf[:, -1].fill_(float("nan"))      # a selected row the row-trimmed last layer does not consume has no activation there: no launch writes its slice
+            n_capture = (cap_rows, lo, hi, cols, buf)
+        if n_patched is not None:
+            n_patched = n_patched[:4] + (self._h2d(n_patched[4].detach().contiguous()),)
+        if ro.neuron_scale is not None and bool((ro.neuron_scale.scale != 1).any()):      # (factors of one: the plain pass)
+            q = ro.neuron_scale
+            s_rows = None if q.rows is None else self._stream_rows(plan, q.rows)[0]
+            if s_rows is None or s_rows.numel():
+                n_scaled = ((s_rows, q.scale, None, None, None) if q.neurons is None else
+                            (s_rows, None, q.neurons[:, 0].to(torch.int32).contiguous(), q.neurons[:, 1].to(torch.int32).contiguous(), q.scale))
         score, amax, *armed = self._prefill(plan["ids_packed"], plan["slot"], plan["cu"], vit_embeds, plan["n_vis"], motion,
                                             plan["score_rows"], plan["logit_rows"], probe=probe, ld_tok=N if ro.token_attention else 0,
                                             drop_words=drop_words, drop_row_words=drop_row_words, drop_layers=kd_layers, lens=lens,
                                             stream_capture=capture if capture is not None and capture[3].numel() else None, stream_patch=patched,
                                             head_capture=h_capture if h_capture is not None and h_capture[3].numel() else None, head_patch=h_patched,
-                                            head_scale=h_scaled)
+                                            head_scale=h_scaled, neuron_capture=n_capture if n_capture is not None and n_capture[4].numel() else None,
+                                            neuron_patch=n_patched, neuron_scale=n_scaled)
         att, tok = armed or (None, None)        # (_prefill hands the probe's tensors back only when it armed one)
         reads = self._read_rows(B if score is not None else 0, len(plan["logit_rows"]), ro, lp_labels)
         out = self._outputs(plan, B, N, score, amax, mos, reads, att, tok)
@@ -719,6 +800,8 @@ class ScoringPass:
             out.update(stream=capture[3], stream_index=self._h2d(stream_index))
         if h_capture is not None:
             out.update(heads=h_capture[3], heads_index=self._h2d(heads_index))
+        if n_capture is not None:
+            out.update(neurons=n_capture[4], neurons_index=self._h2d(neurons_index))
         return out
 
     def dp_front(self, frames_local: torch.Tensor, frames_clips: Optional[torch.Tensor], n_clips: int):

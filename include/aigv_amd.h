@@ -51,7 +51,8 @@ extern "C" {
                                 depth lens (aigv_depth_lens_arm, aigv_depth_lens_token_readout, aigv_op_lens_tap, aigv_op_score_head_groups),
                                 then by activation patching (aigv_stream_capture_arm, aigv_stream_patch_arm, aigv_op_stream_rows),
                                 then by head knock-out and head patching (aigv_head_capture_arm, aigv_head_patch_arm, aigv_head_scale_arm,
-                                aigv_op_head_rows)
+                                aigv_op_head_rows), then by MLP neuron knock-out and neuron patching (aigv_neuron_capture_arm,
+                                aigv_neuron_patch_arm, aigv_neuron_scale_arm, aigv_op_neuron_rows)
                                 - added symbols only: a library without them is refused at load
                                 time, "missing <name>" */
 
@@ -310,6 +311,39 @@ int aigv_stream_patch_arm(aigv_ctx* ctx, const int32_t* rows_host, int n, int lo
 int aigv_head_capture_arm(aigv_ctx* ctx, const int32_t* rows_host, int n, int lo, int hi, void* out_bf16_dev);
 int aigv_head_patch_arm(aigv_ctx* ctx, const int32_t* rows_host, int n, int lo, int hi, const uint64_t* head_bits_host, const void* values_bf16_dev);
 int aigv_head_scale_arm(aigv_ctx* ctx, const int32_t* rows_host, int n, const float* scale_host);
+
+/* MLP neuron knock-out and neuron patching: the neurons of a layer - the row its w2 (down_proj) consumes, the output of the fused SwiGLU epilogue, bf16
+ * [I] per token - copied out of a pass (capture), overwritten in it (patch) or multiplied by a factor (scale).  Each arms exactly the next
+ * aigv_llm_prefill, which disarms on every way out.  Inside layer l the order is: w1|w3 + SwiGLU, scale, patch, capture, w2 - so a capture armed beside
+ * the other two returns what w2 consumes, and every later layer, the lens, a stream capture and a head capture see the modified pass.
+ *   rows_host   HOST int32 [n]: packed row numbers, copied here; checked by the pass like a stream capture's (inside [0, T), strictly ascending);
+ *               0 <= n <= max_tokens.  aigv_neuron_scale_arm: NULL = every row the pass runs (n is then ignored).
+ *   lo, hi      the window: layers lo <= l < hi, 0 <= lo <= hi <= L (checked by the pass).
+ *   cols_host   HOST int32 [m], copied here: the neurons, strictly ascending inside [0, I), m <= AIGV_MAX_NEURON_SEL = 4096 - the sparse form; NULL: the
+ *               dense form, every neuron (m is then ignored).
+ *   out_bf16_dev / values_bf16_dev   DEVICE bf16 [n][hi - lo][W], W = I (dense) or m (sparse; element j is neuron cols_host[j]), 16-byte aligned, the
+ *               caller's, alive until the pass has run: element (i, l - lo) holds row rows_host[i] at layer l.  May be NULL when nothing is selected.
+ *   layer_scale_host   HOST float [L] or NULL, copied here: every neuron of layer l is multiplied by layer_scale_host[l]; 0 knocks the MLP block out.
+ *   sel_layers_host / sel_cols_host / sel_factors_host   HOST [m] each (m may be 0), copied here: neuron sel_cols_host[j] of layer sel_layers_host[j] is
+ *               multiplied by sel_factors_host[j]; the (layer, column) pairs strictly ascending, layer first.  Applied after the per-layer factor.
+ *               The new value is bf16(fp32(x) * s), round to nearest even (0 * Inf = NaN).  A factor that is exactly 1.0 leaves its elements
+ *               untouched (no read, no write); a layer whose factors are all 1 launches nothing.
+ * One launch per option, form and armed layer; rows, columns and factors go to tables the context owns, on the pass's stream: nothing is allocated in
+ * the pass.  An unarmed pass takes one untaken branch per MLP.  THE ROW-TRIMMED LAST LAYER: the value captured, patched or scaled for a row is the input
+ * of the w2 launch whose output the pass keeps for that row - for the consumed rows of small clips that is the weight-streaming path's 64-row buffer,
+ * for every other row of a mixed batch the tile path's.  When the last layer runs for the consumed rows only, a selected row it does not consume has no
+ * MLP activation there: a patch or scale of it does nothing, and a capture does NOT write its (row, L - 1) slice - the caller fills it beforehand (the
+ * Python host: NaN).  The last layer is not un-trimmed: the consumed rows' bits and every other output stay those of the plain pass.  All three combine
+ * with each other, aigv_key_drop_arm / _ex, the score-attention probe, aigv_depth_lens_arm, the stream and head options and fp8 mode (the ops act on the
+ * bf16 rows the e4m3 w2 consumes, before they are quantised).
+ * Refused with AIGV_ERR_ARG and a message, nothing armed: a null context, n outside 0..max_tokens, a null row list (capture, patch), a null or
+ * misaligned buffer, a column outside [0, I), a list that is not strictly ascending or longer than 4096, a NaN factor, a scale with neither form.
+ * Refused by the pass, before any launch: a row outside [0, T), rows not strictly ascending, a window outside [0, L], keep_kv, an option that reaches
+ * layer L - 1 in a pass without output rows (its last MLP does not run); aigv_llm_extend refuses an armed context. */
+int aigv_neuron_capture_arm(aigv_ctx* ctx, const int32_t* rows_host, int n, int lo, int hi, const int32_t* cols_host, int m, void* out_bf16_dev);
+int aigv_neuron_patch_arm(aigv_ctx* ctx, const int32_t* rows_host, int n, int lo, int hi, const int32_t* cols_host, int m, const void* values_bf16_dev);
+int aigv_neuron_scale_arm(aigv_ctx* ctx, const int32_t* rows_host, int n, const float* layer_scale_host, const int32_t* sel_layers_host,
+                          const int32_t* sel_cols_host, const float* sel_factors_host, int m);
 
 /* Replicate the n kept sequences `copies` times (cache slots [0, n) -> [n, 2n), ...; needs n * copies <= max_seqs): the copies can
  * then take DIFFERENT continuations in one aigv_llm_extend call over n * copies sequences (sequence c * n + b continues clip b),
@@ -709,6 +743,17 @@ int aigv_op_stream_rows(void* stream_rows, int ld, int T, const int32_t* rows_ho
  *   NaN); side, n_layers and layer are unused; rows_host NULL: rows 0 .. T - 1 (idx_dev unused). */
 int aigv_op_head_rows(void* ao, int ld, int T, const int32_t* rows_host, int n, int32_t* idx_dev, void* side, int n_layers, int layer, int n_heads, int D,
                       int mode, uint64_t head_bits, const float* scale_host, void* stream);
+
+/* One launch of the neuron-rows kernel, as a pass of T rows makes it for slice `layer` of a window of n_layers layers, on act [T][ld] of I columns (a
+ * multiple of 8); rows_host as for aigv_op_stream_rows, NULL: rows 0 .. T - 1.  sidx_host (HOST int32 [n], each inside [0, n_side); NULL: i) names the
+ * side row of entry i; cols_host (HOST int32 [m], strictly ascending inside [0, I); NULL: the dense form, W = I) the columns - element j of a side row
+ * of W = m is column cols_host[j].  The host lists go to idx_dev / sidx_dev / cols_dev / factors_dev (DEVICE, n / n / m / m entries) as kernel arguments.
+ *   mode 0 (capture): side[(si * n_layers + layer) * W ..] = the selected columns of act[rows[i]]      mode 1 (patch): the other way round  - bit copies
+ *   mode 2 (scale): act = bf16(fp32(act) * s), s = dense_factor (dense) or factors_host[j] (sparse; HOST float [m], no NaN); a factor of exactly 1
+ *   leaves its elements untouched (dense: nothing is launched); side, the side rows, n_layers and layer are unused. */
+int aigv_op_neuron_rows(void* act, int ld, int T, const int32_t* rows_host, int n, int32_t* idx_dev, const int32_t* sidx_host, int32_t* sidx_dev, int n_side,
+                        void* side, int n_layers, int layer, int I, const int32_t* cols_host, int m, int32_t* cols_dev, int mode, const float* factors_host,
+                        float* factors_dev, float dense_factor, void* stream);
 
 /* Frame ingest: uint8 [F,H,W,3] RGB frames already at the model resolution -> bf16 NCHW
  * pixel_values = bf16((u/255 - mean[c]) / std[c])  (torchvision ToTensor + Normalize of dataset.py:267-274 and the
