@@ -19,6 +19,24 @@
 //       the row, pos < j < ld_tok, are set to +0.0.  All ld_tok columns are written, nothing outside them.
 // The summation order is a function of the key index alone (no float atomics, nothing depends on the row count, the batch mates or the
 // grid), so a row's bits are its own - and integer-valued e_j (Q = 0: every e_j is 1) give exact counts.
+//
+// The VALUES form (attn_probe_values_kernel, a sibling that shares the device functions; the plain and dense instantiations above keep their
+// code) also reports WHAT the row takes from every segment: val[row][head][s][c] = (sum over the keys j of segment s of e_j v_j[c]) / total for
+// s = 0 .. S and c = 0 .. D - 1, slot S collecting the keys whose id lies outside [0, S) - so the S + 1 vectors sum to the head's output.  v_j
+// is the bf16 V row the pass's attention reads (packed: the V columns of the fused rows; cache: the V cache, with K's strides), kv head h / g.
+// The second sweep runs tile by tile, tile i = keys 256 i .. 256 i + 255, a trip count that is uniform over the workgroup:
+//   4v. thread t computes e_j and the id of key j = 256 i + t exactly as step 4 does - the same thread, the same keys in the same order, so
+//       `out` and `tok` carry the plain / dense form's bits - and leaves (e_j, id; an id outside [0, S) as S) in an LDS tile;
+//   5v. behind a barrier the threads regroup as (key lane kl = t / D, column c = t % D), KL = 256 / D key lanes.  Lane kl walks the tile's keys
+//       256 i + kl, 256 i + kl + KL, ... in ascending order and does acc[kl][id][c] = fmaf(e_j, float(v_j[c]), acc[kl][id][c]) - ONE fma per
+//       key, from +0.0; the accumulator of the running id is kept in a register and exchanged with its LDS slot when the id changes (a cache:
+//       the chain is the same).  Tile after tile, so acc[kl][s][c] is the fma chain over the keys j = kl (mod KL) of segment s, ascending;
+//   6v. val[s][c] = (((acc[0][s][c] + acc[1][s][c]) + ...) + acc[KL - 1][s][c]) / total: KL - 1 additions in lane order, ONE fp32 division by
+//       the bins' own total (step 5's bits).  All (S + 1) D elements are written, nothing outside them.
+// The rounding chain of one element, which tests/score_values_reference.py counts: expf's ulp on e_j and on every term of the total, the
+// total's ceil(n / 256) + 9 additions, at most ceil(n / KL) fmas (the longest key lane), KL - 1 lane additions, one division.  The order is a
+// function of the key index alone, as above.  0 x Inf is NaN here as in torch and in the flash kernel: a non-finite V row of a key whose
+// weight underflowed to 0 makes its segment NaN; that is not special-cased.
 #include "common.h"
 #include "kernels.h"
 
@@ -36,6 +54,8 @@ __device__ __forceinline__ float probe_score(const float* __restrict__ qs, const
   }
   return acc / post_div;
 }
+
+constexpr int AIGV_PROBE_VALUES_MAX_LDS = 160 * 1024 - 2048;   // a CDNA4 CU's LDS less the kernel's static arrays (qs, red, the tree's)
 
 // the four wave partials of one column of `red`, added in wave order: the last step of every bin's sum and of the total's
 __device__ __forceinline__ float waves_in_order(const float* r) { return ((r[0] + r[1]) + r[2]) + r[3]; }
@@ -97,6 +117,135 @@ __global__ __launch_bounds__(LSE_THREADS) void attn_probe_kernel(const ProbeArgs
   }
 }
 
+// the thread's key j of the second sweep: e_j = exp(s_j - m), the step-4 statement both forms share
+template <int D>
+__device__ __forceinline__ float probe_weight(const float* qs, const bf16_t* kb, const ProbeArgs& p, int j, float row_max) {
+  return expf(probe_score<D>(qs, kb + (size_t)j * p.ldk, p.post_div) - row_max);
+}
+
+template <int D, bool DENSE>
+__global__ __launch_bounds__(LSE_THREADS) void attn_probe_values_kernel(const ProbeArgs p) {
+  constexpr int KL = LSE_THREADS / D;                  // key lanes
+  extern __shared__ float bins[];                      // [n_seg + 1][256] bins | [KL][n_seg + 1][D] accumulators | the tile: e [256], id [256]
+  __shared__ float qs[D];
+  __shared__ float red[(AIGV_MAX_ATTN_SEGMENTS + 1) * (LSE_THREADS / AIGV_WAVE)];
+  const int tid = threadIdx.x, lane = tid % AIGV_WAVE, wave = tid / AIGV_WAVE;
+  const ProbeRow pr = p.tab.r[blockIdx.x];
+  const int h = blockIdx.y, g = p.n_heads / p.n_kv_heads, hk = h / g;
+  const int pos = pr.off + (pr.row - pr.row0), n_keys = pos + 1, S = p.n_seg;
+  constexpr int half = D / 2;
+  float* acc = bins + (S + 1) * LSE_THREADS;
+  float* tile_e = acc + (S + 1) * LSE_THREADS;         // (KL * D = 256)
+  int* tile_id = (int*)(tile_e + LSE_THREADS);
+
+  if (tid < half) {
+    const bf16_t* q = p.q + (size_t)pr.row * p.ldq + (size_t)hk * p.q_group_stride + (size_t)(h % g) * D;
+    const size_t tb = (size_t)pos * half + tid;
+    bf16_t lo, hi;
+    rope_pair(q[tid], q[tid + half], p.rope_cos[tb], p.rope_sin[tb], lo, hi);
+    qs[tid] = bf2f(lo);
+    qs[tid + half] = bf2f(hi);
+  }
+  for (int s = 0; s <= S; ++s) {
+    bins[s * LSE_THREADS + tid] = 0.0f;
+    acc[s * LSE_THREADS + tid] = 0.0f;                 // (every slot once: [kl][s][c] is kl * (S + 1) * D + s * D + c < (S + 1) * 256)
+  }
+  __syncthreads();
+
+  const size_t kv_base = (p.kv_seq_stride ? (size_t)pr.seq * p.kv_seq_stride : (size_t)pr.row0 * p.ldk) + (size_t)hk * p.kv_head_stride;
+  const bf16_t* kb = p.k + kv_base;
+  const bf16_t* vb = p.v + (p.kv_seq_stride ? kv_base : (size_t)pr.row0 * p.ldv + (size_t)hk * p.kv_head_stride);
+  float m = -INFINITY, sum = 0.0f;
+  for (int j = tid; j < n_keys; j += LSE_THREADS) lse_push(m, sum, probe_score<D>(qs, kb + (size_t)j * p.ldk, p.post_div));
+  float row_max = 0.0f;
+  lse_of_block<false>(m, sum, &row_max);
+
+  float* tok = nullptr;
+  if constexpr (DENSE) tok = p.tok + (size_t)blockIdx.x * p.tok_row_stride + (size_t)h * p.ld_tok;
+  const int kl = tid / D, c = tid % D;
+  float* my_acc = acc + (size_t)kl * (S + 1) * D + c;  // this thread's slots: my_acc[s * D]
+  int run = S;                                         // the running id and its accumulator (the slot holds +0.0 until the first exchange)
+  float run_acc = 0.0f;
+  const int n_tiles = (n_keys + LSE_THREADS - 1) / LSE_THREADS;
+  for (int i = 0; i < n_tiles; ++i) {
+    const int j = i * LSE_THREADS + tid;
+    if (j < n_keys) {
+      const float e = probe_weight<D>(qs, kb, p, j, row_max);
+      const int sg = j < pr.off ? p.seg_cached[(size_t)pr.seq * p.ld_cached + j] : p.seg_new[pr.row0 + (j - pr.off)];
+      bins[S * LSE_THREADS + tid] += e;
+      if (sg >= 0 && sg < S) bins[sg * LSE_THREADS + tid] += e;
+      if constexpr (DENSE) tok[j] = e;
+      tile_e[tid] = e;
+      tile_id[tid] = sg >= 0 && sg < S ? sg : S;
+    }
+    __syncthreads();
+    const int in_tile = min(LSE_THREADS, n_keys - i * LSE_THREADS);
+    const bf16_t* vt = vb + (size_t)i * LSE_THREADS * p.ldv + c;
+    constexpr int UN = 8;                              // V elements in flight per thread: the loads do not depend on the fma chain
+    int jj = kl;
+    for (; jj + (UN - 1) * KL < in_tile; jj += UN * KL) {
+      float v[UN];
+#pragma unroll
+      for (int u = 0; u < UN; ++u) v[u] = bf2f(vt[(size_t)(jj + u * KL) * p.ldv]);
+#pragma unroll
+      for (int u = 0; u < UN; ++u) {
+        const int id = tile_id[jj + u * KL];
+        if (id != run) {
+          my_acc[run * D] = run_acc;
+          run_acc = my_acc[id * D];
+          run = id;
+        }
+        run_acc = fmaf(tile_e[jj + u * KL], v[u], run_acc);
+      }
+    }
+    for (; jj < in_tile; jj += KL) {
+      const int id = tile_id[jj];
+      if (id != run) {
+        my_acc[run * D] = run_acc;
+        run_acc = my_acc[id * D];
+        run = id;
+      }
+      run_acc = fmaf(tile_e[jj], bf2f(vt[(size_t)jj * p.ldv]), run_acc);
+    }
+    __syncthreads();                                   // the tile is rewritten by the next trip
+  }
+  my_acc[run * D] = run_acc;
+  // bins: every thread has written its own column only
+  for (int s = 0; s <= S; ++s) {
+    const float v = wave_sum(bins[s * LSE_THREADS + tid]);
+    if (lane == 0) red[s * (LSE_THREADS / AIGV_WAVE) + wave] = v;
+  }
+  __syncthreads();                                     // (also: every accumulator slot is in LDS)
+  const float total = waves_in_order(red + S * (LSE_THREADS / AIGV_WAVE));
+  if (tid < S) {
+    const float bin = waves_in_order(red + tid * (LSE_THREADS / AIGV_WAVE));
+    p.out[(size_t)blockIdx.x * p.out_row_stride + (size_t)h * S + tid] = bin / total;
+  }
+  if constexpr (DENSE) {
+    int j = tid;
+    for (; j < n_keys; j += LSE_THREADS) tok[j] = tok[j] / total;
+    for (; j < p.ld_tok; j += LSE_THREADS) tok[j] = 0.0f;
+  }
+  float* val = p.val + (size_t)blockIdx.x * p.val_row_stride + (size_t)h * (S + 1) * D;
+  for (int x = tid; x < (S + 1) * D; x += LSE_THREADS) {   // x = s * D + c: coalesced
+    float a = acc[x];
+#pragma unroll
+    for (int l = 1; l < KL; ++l) a += acc[(size_t)l * (S + 1) * D + x];
+    val[x] = a / total;
+  }
+}
+
+// bins + accumulators + tile of the VALUES form, in bytes
+static constexpr int values_lds(int n_seg) { return (2 * (n_seg + 1) + 2) * LSE_THREADS * (int)sizeof(float); }
+
+template <int D, bool DENSE>
+hipError_t launch_probe_values(const ProbeArgs& a, hipStream_t s) {
+  static LdsAttrOnce lds_attr;
+  if (hipError_t e = lds_attr.ensure((const void*)attn_probe_values_kernel<D, DENSE>, values_lds(AIGV_MAX_ATTN_SEGMENTS)); e != hipSuccess) return e;
+  hipLaunchKernelGGL((attn_probe_values_kernel<D, DENSE>), dim3(a.n_rows, a.n_heads), dim3(LSE_THREADS), values_lds(a.n_seg), s, a);
+  return hipGetLastError();
+}
+
 template <int D, bool DENSE>
 hipError_t launch_probe(const ProbeArgs& a, hipStream_t s) {
   static LdsAttrOnce lds_attr;
@@ -128,6 +277,17 @@ const char* aigv_probe_check(const ProbeArgs& a, int head_dim, int total_rows, i
     if (!a.tok) return "attention probe: null tok_out with ld_tok > 0";
     if (a.tok_row_stride < (size_t)a.n_heads * a.ld_tok) return "attention probe: tok row stride below n_heads * ld_tok";
   }
+  // values form (one D-vector per segment and the rest slot): likewise asked for by either argument
+  const bool values = a.v || a.val;
+  if (values) {
+    if (!a.v) return "attention probe: null v with val_out given";
+    if (!a.val) return "attention probe: null val_out with v given";
+    if (a.ldv % 8 || ((uintptr_t)a.v & 15)) return "attention probe: V must be 16-byte aligned with a row stride that is a multiple of 8";
+    if (a.val_row_stride < (size_t)a.n_heads * (a.n_seg + 1) * head_dim) return "attention probe: val row stride below n_heads * (n_segments + 1) * head_dim";
+    if (a.kv_seq_stride ? a.ldv != a.ldk : (int64_t)a.ldv < (int64_t)(a.n_kv_heads - 1) * a.kv_head_stride + head_dim)
+      return a.kv_seq_stride ? "attention probe: the V cache takes K's strides (ldv = ldk)" : "attention probe: packed V strides too small";
+    if (values_lds(a.n_seg) > AIGV_PROBE_VALUES_MAX_LDS) return "attention probe: the values form's bins and accumulators do not fit the LDS";
+  }
   int cap = 0;
   if (a.kv_seq_stride) {   // cache layout [seq][kv head][cap][D]
     if (a.ldk < head_dim || a.kv_head_stride < a.ldk) return "attention probe: cache strides too small";
@@ -149,6 +309,11 @@ const char* aigv_probe_check(const ProbeArgs& a, int head_dim, int total_rows, i
 }
 
 hipError_t aigv_launch_attention_probe(const ProbeArgs& a, int head_dim, hipStream_t s) {
+  if (a.val) {
+    if (head_dim == 128) return a.tok ? launch_probe_values<128, true>(a, s) : launch_probe_values<128, false>(a, s);
+    if (head_dim == 64) return a.tok ? launch_probe_values<64, true>(a, s) : launch_probe_values<64, false>(a, s);
+    return hipErrorInvalidValue;
+  }
   if (head_dim == 128) return a.tok ? launch_probe<128, true>(a, s) : launch_probe<128, false>(a, s);
   if (head_dim == 64) return a.tok ? launch_probe<64, true>(a, s) : launch_probe<64, false>(a, s);
   return hipErrorInvalidValue;

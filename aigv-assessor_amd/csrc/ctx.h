@@ -131,6 +131,7 @@ struct aigv_ctx {
     float* out = nullptr;
     float* tok = nullptr;   // aigv_score_attention_arm_tokens: the dense rows [n_rows][layers][n_heads][ld_tok], else nullptr / 0
     int ld_tok = 0;
+    float* val = nullptr;   // aigv_score_attention_arm_values: the value vectors [n_rows][layers][n_heads][n_seg + 1][D], else nullptr
   } probe;
   // key-drop mask (aigv_key_drop_arm / _ex): armed for exactly the next aigv_llm_prefill, which applies it in the attention of the layers
   // [layer_begin, layer_end) - every layer for aigv_key_drop_arm - to the query rows `rows` selects (null: every row); keep_kv, which takes

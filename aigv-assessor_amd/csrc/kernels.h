@@ -154,6 +154,8 @@ hipError_t aigv_launch_attention_decode(const bf16_t* q, int ldq, int q_group_st
 // seg_cached[seq * ld_cached + j] for cached positions j < off; an id outside [0, n_seg) drops the key from the bins, not from the total.
 // Dense form (tok != nullptr, from the same launch): tok[row][head][j] = softmax_j for the key positions j = 0 .. pos of the row's sequence
 // (cached keys first), +0.0 for pos < j < ld_tok - the bins' scores, maximum, total and division, so a one-key bin equals its key's value.
+// Values form (v and val != nullptr, from the same launch; out and tok keep their bits): val[row][head][s][0..D) = sum over the keys of
+// segment s of softmax_j * v_j, s = n_seg collecting the keys outside [0, n_seg) - the head's output split by where it was read from.
 #ifndef AIGV_MAX_ATTN_SEGMENTS
 #define AIGV_MAX_ATTN_SEGMENTS 64   // = include/aigv_amd.h
 #endif
@@ -179,6 +181,8 @@ struct ProbeArgs {
   int n_rows;
   ProbeRowTab tab;
   float* tok; int ld_tok; size_t tok_row_stride;   // dense form, or nullptr / 0: tok[row * tok_row_stride + head * ld_tok + j]
+  const bf16_t* v; int ldv;              // values form, or nullptr / 0: V in K's addressing form (kv_head_stride, kv_seq_stride; cache: ldv = ldk)
+  float* val; size_t val_row_stride;     // val[row * val_row_stride + (head * (n_seg + 1) + seg) * D + c], slot n_seg = the keys outside [0, n_seg)
 };
 // nullptr if every index the kernel forms stays inside its operand: total_rows = rows of the pass (q, seg_new), max_pos = rows of the RoPE tables
 const char* aigv_probe_check(const ProbeArgs& a, int head_dim, int total_rows, int max_pos);

@@ -1,6 +1,6 @@
-// The score-row attention probe of the C ABI (include/aigv_amd.h): aigv_score_attention_arm / _arm_tokens, what an armed aigv_llm_prefill /
-// aigv_llm_extend launches per layer (probe_plan / probe_layer, called from passes.hip) and the context-free aigv_op_attention_probe /
-// _probe_tokens.
+// The score-row attention probe of the C ABI (include/aigv_amd.h): aigv_score_attention_arm / _arm_tokens / _arm_values, what an armed
+// aigv_llm_prefill / aigv_llm_extend launches per layer (probe_plan / probe_layer, called from passes.hip) and the context-free
+// aigv_op_attention_probe / _probe_tokens / _probe_values.
 // Host-side C++ only; the kernel is attnprobe.hip.
 #include <cmath>
 
@@ -43,6 +43,7 @@ int probe_plan(aigv_ctx* c, const char* op, const int32_t* cu, int B, const int3
   a.n_seg = pb.n_seg;
   a.out = pb.out; a.out_row_stride = (size_t)k.llm_layers * k.llm_heads * pb.n_seg;
   a.tok = pb.tok; a.ld_tok = pb.ld_tok; a.tok_row_stride = (size_t)k.llm_layers * k.llm_heads * (size_t)std::max(pb.ld_tok, 0);
+  a.val = pb.val; a.val_row_stride = (size_t)k.llm_layers * k.llm_heads * (size_t)(pb.n_seg + 1) * D;   // (v: per layer, probe_layer)
   if (const char* m = fill_rows(a, pb.rows, pb.n_rows, cu, B, off_host)) return fail(c, AIGV_ERR_ARG, "%s: score attention: %s (the pass has %d rows)", op, m, cu[B]);
   if (pb.tok || pb.ld_tok) {   // the dense rows: refused here, in front of the pass's first layer (aigv_probe_check repeats it per launch)
     if (!pb.tok || pb.ld_tok < 1 || pb.ld_tok > AIGV_MAX_KV_CAPACITY)
@@ -63,11 +64,14 @@ int probe_layer(aigv_ctx* c, const ProbeArgs& plan, int li, bool cache, hipStrea
   if (cache) {
     const size_t kv_layer = (size_t)k.max_seqs * nkv * k.kv_capacity * D;
     a.k = c->kc + li * kv_layer; a.ldk = D; a.kv_head_stride = k.kv_capacity * D; a.kv_seq_stride = (size_t)nkv * k.kv_capacity * D;
+    if (plan.val) { a.v = c->vc + li * kv_layer; a.ldv = D; }
   } else {
     a.k = c->l_qkv + (size_t)g * D; a.ldk = c->qkv_out; a.kv_head_stride = (g + 2) * D; a.kv_seq_stride = 0;
+    if (plan.val) { a.v = c->l_qkv + (size_t)(g + 1) * D; a.ldv = c->qkv_out; }   // the V columns of the fused rows: at K + D within the kv head's group
   }
   a.out = plan.out + (size_t)li * k.llm_heads * plan.n_seg;
   if (plan.tok) a.tok = plan.tok + (size_t)li * k.llm_heads * plan.ld_tok;
+  if (plan.val) a.val = plan.val + (size_t)li * k.llm_heads * (plan.n_seg + 1) * D;
   if (const char* m = aigv_probe_check(a, D, k.max_tokens, k.max_positions)) return fail(c, AIGV_ERR_ARG, "%s", m);
   HIPCHK(c, aigv_launch_attention_probe(a, D, s));
   return 0;
@@ -78,7 +82,7 @@ int probe_layer(aigv_ctx* c, const ProbeArgs& plan, int li, bool cache, hipStrea
 extern "C" {
 
 static int arm(aigv_ctx* c, const char* op, const int32_t* rows_host, int n_rows, const int32_t* seg_new_dev, const int32_t* seg_cached_dev, int ld_cached,
-               int n_segments, float* out_dev, float* tok_out_dev, int ld_tok) {
+               int n_segments, float* out_dev, float* tok_out_dev, int ld_tok, float* val_out_dev = nullptr) {
   if (!c) return fail(c, AIGV_ERR_ARG, "%s: null context", op);
   if (!rows_host || !seg_new_dev || !out_dev) return fail(c, AIGV_ERR_ARG, "%s: null argument", op);
   if (ld_cached < 0) return fail(c, AIGV_ERR_ARG, "%s: ld_cached = %d must not be negative", op, ld_cached);
@@ -89,6 +93,7 @@ static int arm(aigv_ctx* c, const char* op, const int32_t* rows_host, int n_rows
   for (int i = 0; i < std::min(std::max(n_rows, 0), AIGV_MAX_PROBE_ROWS); ++i) pb.rows[i] = rows_host[i];
   pb.seg_new = seg_new_dev; pb.seg_cached = seg_cached_dev; pb.out = out_dev;
   pb.tok = tok_out_dev; pb.ld_tok = ld_tok;
+  pb.val = val_out_dev;
   pb.armed = true;
   return 0;
 }
@@ -106,10 +111,20 @@ int aigv_score_attention_arm_tokens(aigv_ctx* c, const int32_t* rows_host, int n
   return arm(c, op, rows_host, n_rows, seg_new_dev, seg_cached_dev, ld_cached, n_segments, out_dev, tok_out_dev, ld_tok);
 }
 
+int aigv_score_attention_arm_values(aigv_ctx* c, const int32_t* rows_host, int n_rows, const int32_t* seg_new_dev, const int32_t* seg_cached_dev,
+                                    int ld_cached, int n_segments, float* out_dev, float* tok_out_dev, int ld_tok, float* val_out_dev) {
+  const char* op = "aigv_score_attention_arm_values";
+  if (c && !val_out_dev) return fail(c, AIGV_ERR_ARG, "%s: null val_out_dev", op);
+  if (c && (tok_out_dev ? ld_tok < 1 : ld_tok != 0))   // the dense rows are optional here: both or neither
+    return fail(c, AIGV_ERR_ARG, "%s: ld_tok = %d %s", op, ld_tok, tok_out_dev ? "must be positive" : "without tok_out_dev (pass NULL and 0)");
+  return arm(c, op, rows_host, n_rows, seg_new_dev, seg_cached_dev, ld_cached, n_segments, out_dev, tok_out_dev, ld_tok, val_out_dev);
+}
+
 static int op_probe(const char* op, const void* q, int ldq, const void* k, int ldk, const int32_t* cu_host, int n_seq, int n_heads, int n_kv_heads,
                     int q_group_stride, int kv_head_stride, int64_t kv_seq_stride, const int32_t* kv_off_host, int head_dim, const void* cos,
                     const void* sin, int max_pos, const int32_t* rows_host, int n_rows, const int32_t* seg_new, const int32_t* seg_cached,
-                    int ld_cached, int n_segments, float* out, float* tok_out, int ld_tok, void* stream) {
+                    int ld_cached, int n_segments, float* out, float* tok_out, int ld_tok, void* stream, const void* v = nullptr, int ldv = 0,
+                    float* val_out = nullptr) {
   if (!q || !k || !cu_host || !cos || !sin || !rows_host || !seg_new || !out) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
   if (n_seq < 1 || n_seq > AIGV_SMALL_INTS / 2 - 1 || cu_host[0] != 0) return fail(nullptr, AIGV_ERR_ARG, "%s: needs 1 <= n_seq <= %d and cu[0] = 0", op, AIGV_SMALL_INTS / 2 - 1);
   for (int b = 0; b < n_seq; ++b)
@@ -126,6 +141,7 @@ static int op_probe(const char* op, const void* q, int ldq, const void* k, int l
   a.seg_new = seg_new; a.seg_cached = seg_cached; a.ld_cached = ld_cached; a.n_seg = n_segments;
   a.out = out; a.out_row_stride = (size_t)n_heads * (n_segments > 0 ? n_segments : 0);
   a.tok = tok_out; a.ld_tok = ld_tok; a.tok_row_stride = (size_t)n_heads * (size_t)(ld_tok > 0 ? ld_tok : 0);
+  a.v = (const bf16_t*)v; a.ldv = ldv; a.val = val_out; a.val_row_stride = (size_t)n_heads * (size_t)((n_segments > 0 ? n_segments : 0) + 1) * (size_t)(head_dim > 0 ? head_dim : 0);
   if (const char* m = fill_rows(a, rows_host, n_rows, cu_host, n_seq, kv_off_host)) return fail(nullptr, AIGV_ERR_ARG, "%s: %s", op, m);
   if (const char* m = aigv_probe_check(a, head_dim, cu_host[n_seq], max_pos)) return fail(nullptr, AIGV_ERR_ARG, "%s: %s", op, m);
   HIPCHK(nullptr, aigv_launch_attention_probe(a, head_dim, (hipStream_t)stream));
@@ -146,6 +162,17 @@ int aigv_op_attention_probe_tokens(const void* q, int ldq, const void* k, int ld
                                    const int32_t* seg_cached, int ld_cached, int n_segments, float* out, float* tok_out, int ld_tok, void* stream) {
   return op_probe("aigv_op_attention_probe_tokens", q, ldq, k, ldk, cu_host, n_seq, n_heads, n_kv_heads, q_group_stride, kv_head_stride, kv_seq_stride,
                   kv_off_host, head_dim, cos, sin, max_pos, rows_host, n_rows, seg_new, seg_cached, ld_cached, n_segments, out, tok_out, ld_tok, stream);
+}
+
+int aigv_op_attention_probe_values(const void* q, int ldq, const void* k, int ldk, const int32_t* cu_host, int n_seq, int n_heads, int n_kv_heads,
+                                   int q_group_stride, int kv_head_stride, int64_t kv_seq_stride, const int32_t* kv_off_host, int head_dim,
+                                   const void* cos, const void* sin, int max_pos, const int32_t* rows_host, int n_rows, const int32_t* seg_new,
+                                   const int32_t* seg_cached, int ld_cached, int n_segments, float* out, float* tok_out, int ld_tok, const void* v, int ldv,
+                                   float* val_out, void* stream) {
+  const char* op = "aigv_op_attention_probe_values";
+  if (!v || !val_out) return fail(nullptr, AIGV_ERR_ARG, "%s: null %s", op, v ? "val_out" : "v");   // (this entry point IS the values form: neither half may be missing)
+  return op_probe(op, q, ldq, k, ldk, cu_host, n_seq, n_heads, n_kv_heads, q_group_stride, kv_head_stride, kv_seq_stride, kv_off_host, head_dim, cos, sin,
+                  max_pos, rows_host, n_rows, seg_new, seg_cached, ld_cached, n_segments, out, tok_out, ld_tok, stream, v, ldv, val_out);
 }
 
 }  // extern "C"

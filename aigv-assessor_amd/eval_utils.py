@@ -171,6 +171,62 @@ def frame_heatmaps(tok_att, positions, layers=None):
     return (mass / mass.sum(-1, keepdim=True)).view(B, F, g, g).to(tok_att.dtype)
 
 
+def source_writes(model, out, direction=None, layers=None):
+    """WHAT the score row takes from each source: ``out`` is the result dict of ``forward(return_score_values=True)`` (or one of
+    ``forward_shared_prefix``'s), whose ``score_values`` [B, L, n_heads, S, D] holds, per layer and head, the value-weighted sum the row read from
+    each of the S key segments.  Put through the layer's own ``language_model.model.layers.{l}.attention.wo.weight`` [H, n_heads D] that is the
+    vector each (head, source) WRITES into the score row's residual stream.  ``layers``: an index list (None: all layers; L' of them).
+    With ``direction`` ([H], or [B, H]: one per clip - a steering or good-minus-bad direction from ``lens_score_hidden`` / ``return_stream``):
+    returns fp32 [B, L', n_heads, S], the scalar ``<direction, wo_l[:, hD:(h+1)D] @ score_values[b, l, h, s]>`` - computed as ``direction @ wo_l``
+    viewed [n_heads, D] and dotted with the values; the [.., S, H] tensor is never formed.  Summed over heads and sources (plus the same form of
+    ``score_values_rest``) it is the attention block's write along the direction, bias-free as ``wo`` is.
+    Without ``direction``: returns fp32 [B, L', S], the L2 norm of ``sum_h wo_l[:, hD:(h+1)D] @ score_values[b, l, h, s]`` - the size of what each
+    source writes at that layer (norm-based attention analysis: mass on a key whose value is tiny writes nothing).
+    fp32 arithmetic on the values' device."""
+    import torch
+    val = out["score_values"] if isinstance(out, dict) else out
+    if val.dim() != 5:
+        raise ValueError(f"source_writes: expected score_values [B, L, n_heads, S, D], got {tuple(val.shape)}")
+    B, L, nh, S, D = val.shape
+    idx = list(range(L)) if layers is None else [int(l) for l in layers]
+    if any(not 0 <= l < L for l in idx):
+        raise ValueError(f"source_writes: layers outside 0..{L - 1}")
+    params = dict(model.named_parameters())
+    d = None
+    if direction is not None:
+        d = torch.as_tensor(direction).to(device=val.device, dtype=torch.float32)
+        if d.dim() not in (1, 2) or (d.dim() == 2 and d.shape[0] != B):
+            raise ValueError(f"source_writes: direction must be [H] or [B = {B}, H], got {tuple(d.shape)}")
+        d = d.expand(B, -1) if d.dim() == 2 else d[None].expand(B, -1)
+    res = []
+    for l in idx:
+        wo = params[f"language_model.model.layers.{l}.attention.wo.weight"].detach().to(device=val.device, dtype=torch.float32)      # [H, n_heads D]
+        if tuple(wo.shape[1:]) != (nh * D,) or (d is not None and d.shape[1] != wo.shape[0]):
+            raise ValueError(f"source_writes: wo of layer {l} is {tuple(wo.shape)}, the values have {nh} heads x {D}"
+                             + ("" if d is None else f", the direction {d.shape[1]} elements"))
+        v = val[:, l].to(torch.float32)                                          # [B, n_heads, S, D]
+        if d is not None:
+            res.append(torch.einsum("bhd,bhsd->bhs", (d @ wo).view(B, nh, D), v))
+        else:
+            res.append(torch.linalg.vector_norm(torch.einsum("bhsd,ohd->bso", v, wo.view(-1, nh, D)), dim=-1))
+    return torch.stack(res, 1)
+
+
+def frame_write_saliency(norms, layers=None):
+    """Which frames the score row is WRITTEN from: ``norms`` is ``source_writes(model, out)`` [B, L, F + 4] (the norm form, default segments);
+    returns [B, F] - the frame columns, averaged over ``layers`` (an index list; None: all layers) and renormalised over the frames so that a
+    clip's row sums to 1 (NaN where no frame writes anything).  ``frame_saliency``'s counterpart: that one weighs frames by attention mass, this
+    one by the size of what the mass carries."""
+    import torch
+    from .prompts import N_TEXT_SEGMENTS
+    if norms.dim() != 3 or norms.shape[-1] <= N_TEXT_SEGMENTS:
+        raise ValueError(f"frame_write_saliency: expected [B, L, F + {N_TEXT_SEGMENTS}] with F >= 1, got {tuple(norms.shape)}")
+    if layers is not None:
+        norms = norms.index_select(1, torch.as_tensor(list(layers), dtype=torch.long, device=norms.device))
+    size = norms[..., :norms.shape[-1] - N_TEXT_SEGMENTS].double().mean(dim=1)
+    return (size / size.sum(-1, keepdim=True)).to(norms.dtype)
+
+
 def settling_depth(lens_score, tol: float):
     """AT WHICH DEPTH the score exists: ``lens_score`` is ``forward(return_depth_lens=True)``'s [B, L + 1] (the score head on the score row after
     d layers, column L the pass's own score); returns int64 [B] - the smallest depth d such that EVERY depth d' >= d has ``|lens_score[:, d'] -

@@ -81,6 +81,9 @@ PROTOTYPES = {
     "aigv_llm_extend": (_I, [_P, _P, _I32P, _I, _I32P, _P, _I32P, _I, _P, _I, _P]),
     "aigv_score_attention_arm": (_I, [_P, _I32P, _I, _P, _P, _I, _I, _P]),
     "aigv_score_attention_arm_tokens": (_I, [_P, _I32P, _I, _P, _P, _I, _I, _P, _P, _I]),
+    "aigv_score_attention_arm_values": (_I, [_P, _I32P, _I, _P, _P, _I, _I, _P, _P, _I, _P]),
+    "aigv_op_attention_probe_values": (_I, [_P, _I, _P, _I, _I32P, _I, _I, _I, _I, _I, C.c_int64, _I32P, _I, _P, _P, _I, _I32P, _I, _P, _P, _I, _I, _P, _P, _I, _P, _I,
+                                            _P, _P]),
     "aigv_kv_fork": (_I, [_P, _I, _P]),
     "aigv_kv_reorder": (_I, [_P, _P, _P, _I, _P]),
     "aigv_set_row_trimming": (_I, [_P, _I]),

@@ -1,5 +1,6 @@
 """Which read-outs a scoring pass carries: label log-probs, candidate log-probs, top-k log-probs, score attention by segment and per token, the
-depth lens, a capture of residual-stream rows (``return_stream`` / ``stream_depths``) or of per-head attention outputs (``return_heads`` /
+score row's value vectors per segment (``return_score_values``), the depth lens, a capture of residual-stream rows (``return_stream`` /
+``stream_depths``) or of per-head attention outputs (``return_heads`` /
 ``head_layers``) - and whether it runs under a key-drop mask (``key_drop`` with its qualifiers ``key_drop_rows`` / ``key_drop_layers``), a patch of the
 stream (``stream_patch``), a patch of head outputs (``head_patch``) or a per-head scale (``head_scale``): not read-outs, but per-call options that
 travel the same way.  The MLP's side of a layer has the same three: a capture of the neurons ``w2`` consumes (``return_neurons`` / ``neuron_layers`` /
@@ -21,6 +22,7 @@ import torch
 MAX_CANDIDATES = 64      # = AIGV_MAX_CANDIDATES
 MAX_TOPK = 16            # = AIGV_MAX_TOPK
 MAX_LENS_ROWS = 64       # = AIGV_MAX_LENS_ROWS
+MAX_PROBE_ROWS = 64      # = AIGV_MAX_PROBE_ROWS
 
 
 def top_logprobs_k(top_logprobs, vocab: int, labels="given") -> int:
@@ -58,7 +60,8 @@ def key_drop_mask(key_drop, ids_shape=None, probing: bool = False) -> Optional[t
     if key_drop is None:
         return None
     if probing:
-        raise ValueError("key_drop: cannot be combined with return_score_attention / return_token_attention (the probe does not know the mask)")
+        raise ValueError("key_drop: cannot be combined with return_score_attention / return_token_attention / return_score_values (the probe does not know "
+                         "the mask)")
     t = key_drop
     if not torch.is_tensor(t) or t.is_floating_point() or t.is_complex() or t.dim() != 2:
         raise ValueError("key_drop: expected a bool or integer tensor [B, N] laid out like input_ids")
@@ -384,6 +387,8 @@ class ReadOuts:
     score_attention: bool = False               # (return_token_attention implies it)
     segments: Optional[torch.Tensor] = None     # the user's attention_segments table; None: prompts.attention_segments
     token_attention: bool = False
+    score_values: bool = False                  # return_score_values: what the score row takes from every segment, per head (implies score_attention; forward and
+                                                # forward_shared_prefix only)
     key_drop: Optional[torch.Tensor] = None     # host bool [B, N]: tokens hidden, as keys, from every row of their clip (forward; generate* check theirs with key_drop_mask)
     key_drop_rows: Optional[torch.Tensor] = None    # host bool [B, N]: ... from these query rows only (None: every row)
     key_drop_layers: Optional[tuple] = None         # (lo, hi): ... in the layers lo <= l < hi only (None: every layer)
@@ -408,17 +413,19 @@ class ReadOuts:
               ids_shape=None, key_drop_rows=None, key_drop_layers=None, n_layers: Optional[int] = None, return_depth_lens: bool = False,
               return_stream=None, stream_depths=None, stream_patch=None, return_heads=None, head_layers=None, head_patch=None, head_scale=None,
               n_heads: Optional[int] = None, head_dim: Optional[int] = None, return_neurons=None, neuron_layers=None, neuron_ids=None, neuron_patch=None,
-              neuron_scale=None, n_inter: Optional[int] = None) -> "ReadOuts":
+              neuron_scale=None, n_inter: Optional[int] = None, return_score_values: bool = False) -> "ReadOuts":
         """The record of a call's public keyword arguments, checked.  ``labels=None`` (``forward`` without labels) refuses candidates and top-k;
         the shared-prefix and generate entry points leave the default.  A user segment table is checked where its bins are counted
         (``n_segments``: it needs the shape of ``input_ids``)."""
         cand = candidates(candidate_ids, labels)
         k = top_logprobs_k(top_logprobs, vocab, labels)
-        att = bool(return_score_attention or return_token_attention)
+        att = bool(return_score_attention or return_token_attention or return_score_values)
+        if return_score_values and ids_shape is not None and int(ids_shape[0]) > MAX_PROBE_ROWS:
+            raise ValueError(f"return_score_values: at most {MAX_PROBE_ROWS} clips per pass, got {int(ids_shape[0])}")
         rows, window = key_drop_qualifiers(key_drop, key_drop_rows, key_drop_layers, ids_shape, n_layers)
         if return_depth_lens and ids_shape is not None and int(ids_shape[0]) > MAX_LENS_ROWS:
             raise ValueError(f"return_depth_lens: at most {MAX_LENS_ROWS} clips per pass, got {int(ids_shape[0])}")
-        return cls(bool(return_logprobs), cand, k or None, att, attention_segments if att else None, bool(return_token_attention),
+        return cls(bool(return_logprobs), cand, k or None, att, attention_segments if att else None, bool(return_token_attention), bool(return_score_values),
                    key_drop_mask(key_drop, ids_shape, att), rows, window, bool(return_depth_lens),
                    *neuron_options(return_neurons, neuron_layers, neuron_ids, neuron_patch, neuron_scale, ids_shape, n_layers, n_inter),
                    *stream_options(return_stream, stream_depths, stream_patch, ids_shape, n_layers),
@@ -430,6 +437,12 @@ class ReadOuts:
         under graph replay, as a masked call does."""
         return (self.stream_rows is not None or self.stream_patch is not None or self.head_rows is not None or self.head_patch is not None
                 or self.head_scale is not None or self.neuron_rows is not None or self.neuron_patch is not None or self.neuron_scale is not None)
+
+    @property
+    def runs_eagerly(self) -> bool:
+        """Under graph replay: a masked call, a call that touches the stream and a call that returns the score row's value vectors run eagerly and
+        capture nothing; every other call keeps the graph key it always had (``key_tail``)."""
+        return self.key_drop is not None or self.touches_stream or self.score_values
 
     @property
     def wants_labels(self) -> bool:
@@ -451,7 +464,7 @@ class ReadOuts:
         that is off: the keys of passes without it are those they always were.  The candidates' VALUES and a user segment table are graph
         INPUT, not key; the candidates' number is in the key with the device inputs' shapes.  k, a user table's bin count (the default
         table follows from the ids, which are in the key) and ld_tok = N are output shapes: another value is another graph.  ``key_drop`` and
-        the stream, head and neuron options add nothing: such calls are never captured."""
+        the stream, head and neuron options add nothing: such calls are never captured - nor is one with ``score_values``."""
         S = (self.n_segments(ids_shape) if n_seg is None else n_seg) if self.score_attention else 0
         on = ((self.logprobs, "logprobs"), (self.cand is not None, "candidates"), (self.topk is not None, ("top_logprobs", self.topk)),
               (self.score_attention, ("score_attention", S)), (self.token_attention, ("score_attention_tokens", int(ids_shape[1]))),
@@ -470,7 +483,7 @@ def forward_kwargs(r: ReadOuts) -> dict:
     """The record as keyword arguments of ``forward``.  An option that is off is NOT passed: callers hand these to any object with
     ``forward``'s call form, which need not know the options it is not asked for."""
     kw = dict(return_logprobs=r.logprobs or None, candidate_ids=r.cand, top_logprobs=r.topk, return_score_attention=r.score_attention or None,
-              attention_segments=r.segments, return_token_attention=r.token_attention or None, key_drop=r.key_drop,
+              attention_segments=r.segments, return_token_attention=r.token_attention or None, return_score_values=r.score_values or None, key_drop=r.key_drop,
               key_drop_rows=r.key_drop_rows, key_drop_layers=r.key_drop_layers, return_depth_lens=r.depth_lens or None,
               return_stream=r.stream_rows, stream_depths=r.stream_depths, stream_patch=r.stream_patch,
               return_heads=r.head_rows, head_layers=r.head_layers, head_patch=r.head_patch, head_scale=r.head_scale,

@@ -182,7 +182,7 @@ class ScoringPass:
             keep.append(pinned)
         return pinned.to(self.device, non_blocking=True)
 
-    def _prefill(self, ids_packed, slot, cu, vis, n_vis, motion, score_rows, logit_rows, keep_kv=False, kv_cap=0, probe=None, ld_tok=0, drop_words=None,
+    def _prefill(self, ids_packed, slot, cu, vis, n_vis, motion, score_rows, logit_rows, keep_kv=False, kv_cap=0, probe=None, ld_tok=0, values=False, drop_words=None,
                  drop_row_words=None, drop_layers=None, lens=None, stream_capture=None, stream_patch=None, head_capture=None, head_patch=None,
                  head_scale=None, neuron_capture=None, neuron_patch=None, neuron_scale=None):
         b = len(cu) - 1
@@ -198,7 +198,7 @@ class ScoringPass:
         cu_a = native.i32_array(cu)
         sr_a = native.i32_array(score_rows) if score_rows is not None else None
         lr_a = native.i32_array(logit_rows) if len(logit_rows) else None
-        att, tok = self._arm_score_attention(probe, ld_tok) if probe is not None else (None, None)   # (armed for exactly the pass below)
+        att, tok, *val = self._arm_score_attention(probe, ld_tok, values) if probe is not None else (None, None)   # (armed for exactly the pass below)
         if drop_words is not None:      # key_drop: host int64 [B, W] (prompts.key_drop_words) -> armed for exactly the pass below, which disarms
             words_d = up(drop_words, torch.int64)
             if drop_row_words is None and drop_layers is None:
@@ -243,7 +243,7 @@ class ScoringPass:
             ctx, ids_d.data_ptr(), slot_d.data_ptr(), cu_a, b, native.ptr(vis), n_vis, native.ptr(motion),
             sr_a, native.ptr(score), lr_a, len(logit_rows), amax.data_ptr(), int(keep_kv), native.stream_ptr()), ctx)
         if probe is not None:
-            return score, amax[: len(logit_rows)], att, tok
+            return (score, amax[: len(logit_rows)], att, tok) + tuple(val)      # (the value vectors only when asked for: the four-element form is the one callers know)
         return score, amax[: len(logit_rows)]
 
     # ---- score-row attention by segment (return_score_attention) -------------------------------------------------------------------------
@@ -375,10 +375,11 @@ class ScoringPass:
                 raise ValueError(f"key_drop: clip {b}: token {r - cu[b]} is a consumed row (an answer row or the score row) and cannot be dropped")
         return prompts.key_drop_words(key_drop, cu, row_of)
 
-    def _arm_score_attention(self, probe, ld_tok: int = 0):
+    def _arm_score_attention(self, probe, ld_tok: int = 0, values: bool = False):
         """Arm the context's NEXT prefill / continuation pass; returns (att, tok): the fp32 tensor [rows, L, n_heads, S] the pass fills
         (aigv_score_attention_arm) and - ``ld_tok`` > 0, ``return_token_attention``: aigv_score_attention_arm_tokens - the dense rows [rows, L,
-        n_heads, ld_tok] the same pass fills, else None."""
+        n_heads, ld_tok] the same pass fills, else None.  ``values`` (``return_score_values``: aigv_score_attention_arm_values) -> (att, tok, val),
+        val the fp32 value vectors [rows, L, n_heads, S + 1, D] the same pass fills."""
         rows, seg_new, seg_cached, ld_cached, S = probe
         llm = self.config.llm_config
         att = torch.empty((len(rows), llm.num_hidden_layers, llm.num_attention_heads, S), dtype=torch.float32, device=self.device)
@@ -386,6 +387,11 @@ class ScoringPass:
         args = (self._ctx, native.i32_array(rows), len(rows), seg_new.data_ptr(), native.ptr(seg_cached), int(ld_cached), int(S), att.data_ptr())
         if ld_tok:
             tok = torch.empty((len(rows), llm.num_hidden_layers, llm.num_attention_heads, int(ld_tok)), dtype=torch.float32, device=self.device)
+        if values:
+            val = torch.empty((len(rows), llm.num_hidden_layers, llm.num_attention_heads, S + 1, llm.head_dim), dtype=torch.float32, device=self.device)
+            native.check(lib.aigv_score_attention_arm_values(*args, native.ptr(tok), int(ld_tok), val.data_ptr()), self._ctx)
+            return att, tok, val
+        if ld_tok:
             native.check(lib.aigv_score_attention_arm_tokens(*args, tok.data_ptr(), int(ld_tok)), self._ctx)
         else:
             native.check(lib.aigv_score_attention_arm(*args), self._ctx)
@@ -535,7 +541,7 @@ class ScoringPass:
                 stream_depths: Optional[tuple] = None, stream_patch: Optional[readouts.StreamPatch] = None, return_heads: Optional[torch.Tensor] = None,
                 head_layers: Optional[tuple] = None, head_patch: Optional[readouts.HeadPatch] = None, head_scale: Optional[readouts.HeadScale] = None,
                 return_neurons: Optional[torch.Tensor] = None, neuron_layers: Optional[tuple] = None, neuron_ids: Optional[torch.Tensor] = None,
-                neuron_patch: Optional[readouts.NeuronPatch] = None, neuron_scale: Optional[readouts.NeuronScale] = None):
+                neuron_patch: Optional[readouts.NeuronPatch] = None, neuron_scale: Optional[readouts.NeuronScale] = None, return_score_values: bool = False):
         """Stage-2 eval pass (modeling_internvl_chat.py:306-488) or, with ``stage=1``, the stage-1 pass
         (internvl_chat_eval1/modeling_internvl_chat.py:250-366).  ``visual_tokens`` optionally supplies
         already all-gathered pre-projector tokens (frame-DP) instead of ``pixel_values``.
@@ -580,6 +586,17 @@ class ScoringPass:
         keep their bits.  ``prompts.visual_token_positions`` + ``eval_utils.frame_heatmaps`` fold it to a 16 x 16 map per frame.  Under
         graph replay the flag and N are part of the graph's key; the tensor is handed back as a copy.
 
+        ``return_score_values=True`` (implies ``return_score_attention``) - WHAT the row takes from each source: adds ``score_values`` (fp32 [B, L,
+        n_heads, S, D]: ``sum over the keys j of segment s of softmax_j * v_j``, the head's attention output at the score row split by where it
+        was read from, from the same launch per layer) and ``score_values_rest`` (fp32 [B, L, n_heads, D]: the keys outside every segment - all
+        zeros with the default table); the two are views of one buffer, and ``score_values.sum(3) + score_values_rest`` is the head output the
+        layer's ``wo`` consumes (``return_heads``) up to the flash kernel's bf16 roundings.  Attention mass is a poor proxy for contribution (a
+        sink key holds mass and writes almost nothing); ``eval_utils.source_writes`` puts the vectors through ``wo`` - the norm of what every
+        source writes into the score row's stream, or its projection on a direction - and ``eval_utils.frame_write_saliency`` folds the norms to
+        [B, F] beside ``frame_saliency``.  ``score_attention``, ``score_attention_tokens`` and every other output keep their bits; combines
+        with everything the probe combines with.  0 x Inf is NaN as in the attention itself: a non-finite V row makes its segment NaN.  At most
+        64 clips; with graph replay enabled a call with the flag runs eagerly.
+
         ``key_drop`` (bool or integer tensor [B, N] laid out like ``input_ids``, on any device): WHAT IF these tokens were not there.  True
         hides that token, as a key, from every row of its clip in every layer; padded positions are ignored.  Every output - ``score1``,
         ``logit``, the log-probability read-outs - is that of the masked pass; positions, packing and the dead-tail trimming are untouched.
@@ -588,7 +605,7 @@ class ScoringPass:
         treats every zero as padding and strips the token, which moves the later tokens' positions - that behaviour stays.  The V rows of
         dropped keys must be finite: they are multiplied by an exact 0, and 0 x NaN is NaN here as it is in torch.  ValueError, before
         anything is launched, for a wrong shape, for dropping a clip's first token (the sink guarantees every row a visible key) or a
-        consumed row (an answer row, the score row), and in combination with ``return_score_attention`` / ``return_token_attention`` (the
+        consumed row (an answer row, the score row), and in combination with ``return_score_attention`` / ``return_token_attention`` / ``return_score_values`` (the
         probe does not know the mask).  With graph replay enabled a call with ``key_drop`` runs eagerly - the same bits as with replay
         off - and captures nothing; unmasked calls keep replaying.  ``unit_masks`` builds the per-frame masks,
         ``eval_utils.frame_ablation`` the per-frame score deltas.
@@ -683,9 +700,11 @@ class ScoringPass:
             raise AssertionError("img_context_token_id must be set by the caller (stage2_eval.py:810)")
         drop_words = drop_row_words = None
         n_layers = self.config.llm_config.num_hidden_layers
+        if return_score_values and input_ids is not None and int(input_ids.shape[0]) > self.MAX_PROBE_ROWS:      # (before anything touches the device)
+            raise ValueError(f"return_score_values: at most {self.MAX_PROBE_ROWS} clips per pass, got {int(input_ids.shape[0])}")
         kd_rows, kd_layers = readouts.key_drop_qualifiers(key_drop, key_drop_rows, key_drop_layers, None if input_ids is None else input_ids.shape, n_layers)
         if key_drop is not None:        # checked in full on the host before anything touches the device (a plan of its own: host work only)
-            kd = readouts.key_drop_mask(key_drop, input_ids.shape, bool(return_score_attention or return_token_attention))
+            kd = readouts.key_drop_mask(key_drop, input_ids.shape, bool(return_score_attention or return_token_attention or return_score_values))
             src = visual_tokens if visual_tokens is not None else pixel_values
             drop_words = self._key_drop_words(self._plan(input_ids, attention_mask, labels, image_flags, (src.tokens if isinstance(src, VisualAhead) else src).shape[0],
                                                          full_logits), kd, kd_rows)
@@ -724,13 +743,13 @@ class ScoringPass:
                                                 None if input_ids is None else input_ids.shape, key_drop_rows, key_drop_layers, n_layers,
                                                 return_depth_lens, return_stream, stream_depths, stream_patch, return_heads, head_layers, head_patch, head_scale,
                                                 llm.num_attention_heads, llm.head_dim, return_neurons, neuron_layers, neuron_ids, neuron_patch, neuron_scale,
-                                                llm.intermediate_size)
+                                                llm.intermediate_size, return_score_values)
         ro = None
         if self._graph_replay_enabled and self._capture_keep is None:
             ro = parse()
             # (a masked call stays eager and leaves the graph cache as it is: capturing masked passes is out of scope)
-            # (so does a call that captures or patches the residual stream, or captures, patches or scales head outputs or MLP neurons)
-            out = None if ro.key_drop is not None or ro.touches_stream else self._forward_through_graph(mos, pixel_values, input_ids, attention_mask, image_flags, labels,
+            # (so does a call that captures or patches the residual stream, or captures, patches or scales head outputs or MLP neurons, or returns score values)
+            out = None if ro.runs_eagerly else self._forward_through_graph(mos, pixel_values, input_ids, attention_mask, image_flags, labels,
                                                                                   motion_feature, visual_tokens, full_logits, ro)
             if out is not None:
                 return out
@@ -785,15 +804,15 @@ class ScoringPass:
                 n_scaled = ((s_rows, q.scale, None, None, None) if q.neurons is None else
                             (s_rows, None, q.neurons[:, 0].to(torch.int32).contiguous(), q.neurons[:, 1].to(torch.int32).contiguous(), q.scale))
         score, amax, *armed = self._prefill(plan["ids_packed"], plan["slot"], plan["cu"], vit_embeds, plan["n_vis"], motion,
-                                            plan["score_rows"], plan["logit_rows"], probe=probe, ld_tok=N if ro.token_attention else 0,
+                                            plan["score_rows"], plan["logit_rows"], probe=probe, ld_tok=N if ro.token_attention else 0, values=ro.score_values,
                                             drop_words=drop_words, drop_row_words=drop_row_words, drop_layers=kd_layers, lens=lens,
                                             stream_capture=capture if capture is not None and capture[3].numel() else None, stream_patch=patched,
                                             head_capture=h_capture if h_capture is not None and h_capture[3].numel() else None, head_patch=h_patched,
                                             head_scale=h_scaled, neuron_capture=n_capture if n_capture is not None and n_capture[4].numel() else None,
                                             neuron_patch=n_patched, neuron_scale=n_scaled)
-        att, tok = armed or (None, None)        # (_prefill hands the probe's tensors back only when it armed one)
+        att, tok, *val = armed or (None, None)  # (_prefill hands the probe's tensors back only when it armed one)
         reads = self._read_rows(B if score is not None else 0, len(plan["logit_rows"]), ro, lp_labels)
-        out = self._outputs(plan, B, N, score, amax, mos, reads, att, tok)
+        out = self._outputs(plan, B, N, score, amax, mos, reads, att, tok, *val)
         if lens is not None:
             out.update(self._depth_lens_outputs(B, lens, lens_rows[1], ro, labels is not None))
         if capture is not None:
@@ -940,7 +959,7 @@ class ScoringPass:
             vit_embeds = vit_embeds[self._h2d(plan["keep"])]
         return vit_embeds.reshape(-1, H), self.motion_embed(motion_feature)
 
-    def _outputs(self, plan, B, N, score, amax, mos, reads, att=None, tok=None):
+    def _outputs(self, plan, B, N, score, amax, mos, reads, att=None, tok=None, val=None):
         """The result dict of one pass: ``reads`` (``_read_rows``) and the argmax ids, each scattered to its place among the label positions
         under its ``readouts.ROW_FIELDS`` fill, the score head's outputs and the probe's tensors."""
         dev = self.device
@@ -975,6 +994,8 @@ class ScoringPass:
             out["score_attention"] = att
         if tok is not None:                         # return_token_attention: [B, L, n_heads, N]
             out["score_attention_tokens"] = tok
+        if val is not None:                         # return_score_values: [B, L, n_heads, S + 1, D], slot S = the keys outside every segment
+            out["score_values"], out["score_values_rest"] = val[..., :-1, :], val[..., -1, :]
         return out
 
     def _logprob_labels(self, plan) -> torch.Tensor:
@@ -1036,7 +1057,8 @@ class ScoringPass:
     def forward_shared_prefix(self, prompts, pixel_values: Optional[torch.Tensor] = None, image_flags: Optional[torch.Tensor] = None,
                               motion_feature: Optional[torch.Tensor] = None, visual_tokens: Optional[torch.Tensor] = None, mos=None,
                               return_logprobs: bool = False, candidate_ids=None, top_logprobs: Optional[int] = None,
-                              return_score_attention: bool = False, return_token_attention: bool = False, key_drop_rows=None, key_drop_layers=None):
+                              return_score_attention: bool = False, return_token_attention: bool = False, key_drop_rows=None, key_drop_layers=None,
+                              return_score_values: bool = False):
         """Score the same clips under several prompts that share their beginning - the reference's four quality
         perspectives ask four questions BEHIND the same system + frame + motion tokens (8f-3) and
         run four full passes (stage2_eval.py evaluates one jsonl per perspective).  Here the common prefix runs once
@@ -1062,7 +1084,7 @@ class ScoringPass:
         n_frames = visual_tokens.shape[0] if visual_tokens is not None else pixel_values.shape[0]
         plans = [self._plan(ids, am, lab, image_flags, n_frames) for (ids, am, lab) in prompts]
         ro = readouts.ReadOuts.parse(self.config.llm_config.vocab_size, "given", return_logprobs, candidate_ids, top_logprobs, return_score_attention,
-                                     None, return_token_attention)
+                                     None, return_token_attention, return_score_values=return_score_values)
         lp_labels = [self._logprob_labels(pl) for pl in plans] if ro.wants_labels else None
         B = prompts[0][0].shape[0]
         pre = self._shared_prefix_lengths(plans, B)
@@ -1102,7 +1124,7 @@ class ScoringPass:
         ids_d = torch.cat(parts).to(torch.long).contiguous().pin_memory().to(dev, non_blocking=True)
         score = torch.empty(B * P, dtype=torch.float32, device=dev) if self.stage == 2 else None
         amax = torch.empty(max(len(lrows), 1), dtype=torch.long, device=dev)
-        att = tok = None
+        att = tok = val = None
         if ro.score_attention:
             # rows: sequence p * B + b of the continuation batch; segments of its new tokens: the prompt's own table behind the prefix; of the
             # cached keys: the clip's prefix table, tiled over the P prompts (row p * B + b, padded with -1 to the longest prefix)
@@ -1121,7 +1143,10 @@ class ScoringPass:
                 seg_cached[b::B, :pre[b]] = seg0[p0["cu"][b]:p0["cu"][b] + pre[b]]
             probe = (prows, self._h2d(torch.cat(seg_parts).contiguous()), self._h2d(seg_cached), ld, S)
             # (without the dense rows: the one-argument call, the form wrappers of this method have always been written against)
-            att, tok = self._arm_score_attention(probe, longest) if ro.token_attention else self._arm_score_attention(probe)
+            if ro.score_values:
+                att, tok, val = self._arm_score_attention(probe, longest if ro.token_attention else 0, True)
+            else:
+                att, tok = self._arm_score_attention(probe, longest) if ro.token_attention else self._arm_score_attention(probe)
         native.check(lib.aigv_llm_extend(ctx, ids_d.data_ptr(), native.i32_array(cu_s), B * P,
                                          native.i32_array(srows) if score is not None else None, native.ptr(score),
                                          native.i32_array(lrows) if lrows else None, len(lrows), amax.data_ptr(), 0,
@@ -1131,7 +1156,7 @@ class ScoringPass:
         clips_of = lambda t, p: None if t is None else t[p * B:(p + 1) * B]
         for p, (pl, (ids, _, _)) in enumerate(zip(plans, prompts)):
             outs.append(self._outputs(pl, B, ids.shape[1], clips_of(score, p), amax[off:off + n_l[p]], mos,
-                                      {k: v[off:off + n_l[p]] for k, v in reads.items()}, clips_of(att, p), clips_of(tok, p)))
+                                      {k: v[off:off + n_l[p]] for k, v in reads.items()}, clips_of(att, p), clips_of(tok, p), clips_of(val, p)))
             off += n_l[p]
         return outs
 

@@ -52,7 +52,8 @@ extern "C" {
                                 then by activation patching (aigv_stream_capture_arm, aigv_stream_patch_arm, aigv_op_stream_rows),
                                 then by head knock-out and head patching (aigv_head_capture_arm, aigv_head_patch_arm, aigv_head_scale_arm,
                                 aigv_op_head_rows), then by MLP neuron knock-out and neuron patching (aigv_neuron_capture_arm,
-                                aigv_neuron_patch_arm, aigv_neuron_scale_arm, aigv_op_neuron_rows)
+                                aigv_neuron_patch_arm, aigv_neuron_scale_arm, aigv_op_neuron_rows), then by the probe's value flow
+                                (aigv_score_attention_arm_values, aigv_op_attention_probe_values)
                                 - added symbols only: a library without them is refused at load
                                 time, "missing <name>" */
 
@@ -198,6 +199,21 @@ int aigv_score_attention_arm(aigv_ctx* ctx, const int32_t* rows_host, int n_rows
  * message, before its first layer.  Nothing is allocated (the armed pass still captures); aigv_decode_step ignores the feature. */
 int aigv_score_attention_arm_tokens(aigv_ctx* ctx, const int32_t* rows_host, int n_rows, const int32_t* seg_new_dev, const int32_t* seg_cached_dev,
                                     int ld_cached, int n_segments, float* out_dev, float* tok_out_dev, int ld_tok);
+/* Score-row VALUE flow: aigv_score_attention_arm_tokens' arguments and contract (out_dev and tok_out_dev are filled as above, bit for bit;
+ * tok_out_dev may be NULL with ld_tok = 0: the bins only), plus WHAT the row takes from every segment, filled by the SAME launch per layer:
+ *   val_out_dev[row][layer][head][s][c] = sum over the visible keys j of segment s of softmax_j * v_j[c]     s = 0 .. n_segments, c < head_dim
+ * fp32, DEVICE, [n_rows][layers][n_heads][n_segments + 1][head_dim]: slot s = n_segments collects the keys whose id lies outside
+ * [0, n_segments) - the keys the bins drop and the total keeps - so the n_segments + 1 vectors of a head sum to that head's attention output
+ * at the row (the row its wo consumes), split by where it was read from.  v_j: the bf16 V the pass's own attention reads - the V columns of
+ * the layer's fused qkv rows in aigv_llm_prefill, the V cache in aigv_llm_extend - of kv head (head / g).
+ * Numerics: e_j = expf(s_j - max) are the bins' own; every element is accumulated UNNORMALISED in fp32, one fmaf per key, in an order fixed
+ * by the key index alone (the keys j = l mod KL, KL = 256 / head_dim, ascending, form chain l; the KL chains are added in order l = 0, 1, ..),
+ * then divided ONCE by the bins' total.  No atomics; a row's bits do not depend on the other rows, the batch mates or the grid.  0 x Inf is
+ * NaN, as in the attention kernels: a non-finite V row of a visible key makes its segment NaN even where the key's weight underflowed to 0.
+ * The kernel keeps (2 (n_segments + 1) + 2) KiB of LDS per workgroup (135 KiB at 64 segments).  Nothing is allocated; limits are checked when
+ * the pass runs.  An unarmed pass, or one armed through the two functions above, launches exactly what it always launched. */
+int aigv_score_attention_arm_values(aigv_ctx* ctx, const int32_t* rows_host, int n_rows, const int32_t* seg_new_dev, const int32_t* seg_cached_dev,
+                                    int ld_cached, int n_segments, float* out_dev, float* tok_out_dev, int ld_tok, float* val_out_dev);
 
 /* Key-drop mask: run the clips with some tokens HIDDEN from the LLM - what the reference computes for attention_mask zeros in the middle of a
  * sequence (positions stay as they are; the additive mask hides those keys from every query row).  Arms exactly the next aigv_llm_prefill on
@@ -597,6 +613,16 @@ int aigv_op_attention_probe_tokens(const void* q, int ldq, const void* k, int ld
                                    int q_group_stride, int kv_head_stride, int64_t kv_seq_stride, const int32_t* kv_off_host, int head_dim,
                                    const void* cos, const void* sin, int max_pos, const int32_t* rows_host, int n_rows, const int32_t* seg_new,
                                    const int32_t* seg_cached, int ld_cached, int n_segments, float* out, float* tok_out, int ld_tok, void* stream);
+/* aigv_op_attention_probe_tokens with the value vectors of aigv_score_attention_arm_values from the same launch: val_out [n_rows, n_heads,
+ * n_segments + 1, head_dim] fp32 DEVICE (one layer).  v: bf16 V rows in k's addressing form - packed: row j of a sequence, ldv apart, kv head
+ * kvh at column kvh * kv_head_stride (for fused rows: k + head_dim); cache: [seq][kv head][cap][head_dim] with k's strides (ldv = ldk).
+ * tok_out may be NULL with ld_tok = 0.  Refused on the host (AIGV_ERR_ARG with a message, nothing launched): v or val_out NULL, v not
+ * 16-byte aligned or ldv not a multiple of 8, strides that do not hold the rows.  `out` and `tok_out` keep their bits. */
+int aigv_op_attention_probe_values(const void* q, int ldq, const void* k, int ldk, const int32_t* cu_host, int n_seq, int n_heads, int n_kv_heads,
+                                   int q_group_stride, int kv_head_stride, int64_t kv_seq_stride, const int32_t* kv_off_host, int head_dim,
+                                   const void* cos, const void* sin, int max_pos, const int32_t* rows_host, int n_rows, const int32_t* seg_new,
+                                   const int32_t* seg_cached, int ld_cached, int n_segments, float* out, float* tok_out, int ld_tok, const void* v, int ldv,
+                                   float* val_out, void* stream);
 /* The KV-cache append of the prefill and continuation passes: for token t, the K and V slots of every group of the fused row
  * qkv[t * ld ..] (groups of [g query heads | K | V]) are copied to kc / vc [seq][n_kv][cap][head_dim] at [seq[t]][kvh][pos[t]]; nothing else
  * is written.  seq / pos: DEVICE int32[tokens] (the caller's promise: seq[t] inside the cache, pos[t] < cap).  Checked on the host. */
