@@ -154,43 +154,50 @@ struct aigv_ctx {
     float* score = nullptr;                        // device, the caller's: [llm_layers + 1][n_score]
   } lens;
   int32_t* l_lensidx = nullptr;   // device [4 * AIGV_MAX_LENS_ROWS]: the armed pass's lens rows | their places among the consumed rows (row trimming)
-  // activation patching (aigv_stream_capture_arm / aigv_stream_patch_arm): armed for exactly the next aigv_llm_prefill.  At the top of layer li, lo <= li <
-  // hi, the patch writes slice li - lo of its buffer over the rows `rows` of the residual stream, then the capture copies its rows of the stream - as the
-  // layer consumes it - into slice li - lo of its own.  rows: packed row numbers, copied on arming, checked by the pass (inside [0, T), strictly ascending)
-  struct StreamRows {
-    bool armed = false;
-    int lo = 0, hi = 0;
-    std::vector<int32_t> rows;
-    bf16_t* buf = nullptr;   // device, the caller's: [rows.size()][hi - lo][H]
-  } stream_cap, stream_patch;
-  int32_t* l_streamidx = nullptr;   // device [2 * max_tokens]: the armed pass's patch rows | its capture rows
-  // head knock-out / head patching (aigv_head_scale_arm / aigv_head_patch_arm / aigv_head_capture_arm): armed for exactly the next aigv_llm_prefill.  Between
-  // the attention of layer li and its wo, on l_ao [T, n_heads * D]: first the scale (table row li, every head whose factor is not exactly 1), then the patch
-  // (lo <= li < hi: slice li - lo of its buffer over the heads of bits[li - lo]), then the capture (slice li - lo of its own buffer, every head) - so a
-  // capture returns what wo consumes.  rows: packed row numbers, copied on arming, checked by the pass; all_rows (the scale only): every row the pass runs
-  struct HeadRows {
+  // The row options of a scoring pass: each armed for exactly the next aigv_llm_prefill.  What the eight share: rows - packed row numbers, copied on arming,
+  // checked by the pass (inside [0, T), strictly ascending); all_rows (a scale only): every row the pass runs; the layer window lo <= li < hi; buf - device,
+  // the caller's: [rows.size()][hi - lo][row width], slice li - lo belonging to layer li
+  struct RowOpt {
     bool armed = false, all_rows = false;
     int lo = 0, hi = 0;
     std::vector<int32_t> rows;
+    bf16_t* buf = nullptr;
+  };
+  // activation patching (aigv_stream_capture_arm / aigv_stream_patch_arm), rows of width H.  At the top of layer li the patch writes its slice over the rows
+  // of the residual stream, then the capture copies its rows of the stream - as the layer consumes it - into its own
+  RowOpt stream_patch, stream_cap;
+  int32_t* l_streamidx = nullptr;   // device [2 * max_tokens]: the armed pass's patch rows | its capture rows
+  // head knock-out / head patching (aigv_head_scale_arm / aigv_head_patch_arm / aigv_head_capture_arm), rows of width n_heads * D.  Between the attention of
+  // layer li and its wo, on l_ao: first the scale (table row li, every head whose factor is not exactly 1), then the patch (the heads of bits[li - lo]), then
+  // the capture (every head) - so a capture returns what wo consumes
+  struct HeadRows : RowOpt {
     std::vector<uint64_t> bits;   // the patch: one mask per layer of the window (no list on arming: every head)
     std::vector<float> scale;     // the scale: [llm_layers][llm_heads]
-    bf16_t* buf = nullptr;        // device, the caller's: [rows.size()][hi - lo][n_heads * D]
-  } head_cap, head_patch, head_scale;
+  } head_scale, head_patch, head_cap;
   int32_t* l_headidx = nullptr;   // device [3 * max_tokens]: the armed pass's head-scale rows | head-patch rows | head-capture rows
-  // MLP neuron knock-out / neuron patching (aigv_neuron_scale_arm / aigv_neuron_patch_arm / aigv_neuron_capture_arm): armed for exactly the next
-  // aigv_llm_prefill.  Between the SwiGLU GEMM of layer li and its w2, on the row w2 consumes (l_ffn [T, I]; the streamed rows of the row-trimmed last layer:
-  // t_ffn): first the scale, then the patch (lo <= li < hi), then the capture - so a capture returns what w2 consumes.  rows: packed row numbers, copied on
-  // arming, checked by the pass; all_rows (the scale only): every row.  cols empty and dense true: every neuron; else the sparse column list (capture,
+  // MLP neuron knock-out / neuron patching (aigv_neuron_scale_arm / aigv_neuron_patch_arm / aigv_neuron_capture_arm), rows of width I or cols.size().  Between
+  // the SwiGLU GEMM of layer li and its w2, on the row w2 consumes (l_ffn [T, I]; the streamed rows of the row-trimmed last layer: t_ffn): first the scale,
+  // then the patch, then the capture - so a capture returns what w2 consumes.  cols empty and dense true: every neuron; else the sparse column list (capture,
   // patch: one list for the window; scale: (layer, column, factor) triples sorted by layer, sel_begin[l] .. sel_begin[l + 1] those of layer l)
-  struct NeuronRows {
-    bool armed = false, all_rows = false, dense = true;
-    int lo = 0, hi = 0;
-    std::vector<int32_t> rows, cols;
+  struct NeuronRows : RowOpt {
+    bool dense = true;
+    std::vector<int32_t> cols;
     std::vector<float> layer_scale;   // the scale, dense form: [llm_layers] (empty: none)
     std::vector<float> factors;       // the scale, sparse form: one per entry of cols
     std::vector<int32_t> sel_begin;   // the scale, sparse form: [llm_layers + 1]
-    bf16_t* buf = nullptr;            // device, the caller's: [rows.size()][hi - lo][I or cols.size()]
-  } neuron_cap, neuron_patch, neuron_scale;
+  } neuron_scale, neuron_patch, neuron_cap;
+  // ... and the eight in the order a layer applies them, with the words the passes' messages are built from: family, option, the arming entry point, and what
+  // the last layer of a pass without output rows does not run for that family (the stream: nothing to skip).  DESIGN.md "Adding a pass option"
+  struct RowOptEntry { RowOpt* opt; const char *family, *what, *arm, *skipped; };
+  const RowOptEntry row_opts[8] = {
+      {&stream_patch, "stream", "patch", "aigv_stream_patch_arm", nullptr},
+      {&stream_cap, "stream", "capture", "aigv_stream_capture_arm", nullptr},
+      {&head_scale, "head", "scale", "aigv_head_scale_arm", "attention"},
+      {&head_patch, "head", "patch", "aigv_head_patch_arm", "attention"},
+      {&head_cap, "head", "capture", "aigv_head_capture_arm", "attention"},
+      {&neuron_scale, "neuron", "scale", "aigv_neuron_scale_arm", "MLP"},
+      {&neuron_patch, "neuron", "patch", "aigv_neuron_patch_arm", "MLP"},
+      {&neuron_cap, "neuron", "capture", "aigv_neuron_capture_arm", "MLP"}};
   // device: per option (scale | patch | capture) 3 * max_tokens ints - its packed rows | the activation rows of its last-layer launches | their side rows
   int32_t* l_neuronidx = nullptr;
   int32_t* l_neuroncol = nullptr;   // device [3 * AIGV_MAX_NEURON_SEL]: the scale's columns | the patch's | the capture's
@@ -319,14 +326,16 @@ constexpr size_t SPLITK_MAX_FLOATS = (size_t)64 << 20;   // 256 MB of fp32 split
 int splitk_scratch(aigv_ctx* c, size_t need_floats, float** out);
 
 // ---- the score-row attention probe of an armed pass (probe.hip) --------------------------------------------------------------------
-// DisarmScope: the pass that finds the context armed - with the probe, with a key-drop mask (aigv_key_drop_arm), with the depth lens (aigv_depth_lens_arm), with a stream capture or patch (aigv_stream_capture_arm, aigv_stream_patch_arm), with a head capture, patch or scale (aigv_head_capture_arm, aigv_head_patch_arm, aigv_head_scale_arm), with a neuron capture, patch or scale (aigv_neuron_capture_arm, aigv_neuron_patch_arm, aigv_neuron_scale_arm) - disarms it on every way out.  probe_plan: the probe's arguments for this pass (rows
-// validated against cu; off_host: keys cached in front of every sequence, or null), built ONCE per pass; probe_layer: the launch of layer li.
+// DisarmScope: the pass that finds the context armed - with the probe, a key-drop mask, the depth lens or any row option (aigv_ctx::row_opts; DESIGN.md "Adding
+// a pass option") - disarms it on every way out.  probe_plan: the probe's arguments for this pass (rows validated against cu; off_host: keys cached in front of
+// every sequence, or null), built ONCE per pass; probe_layer: the launch of layer li.
 struct DisarmScope {
   aigv_ctx* c;
   explicit DisarmScope(aigv_ctx* c_) : c(c_) {}
-  ~DisarmScope() { c->probe.armed = false; c->drop.armed = false; c->lens.armed = false; c->stream_cap.armed = false; c->stream_patch.armed = false;
-                   c->head_cap.armed = false; c->head_patch.armed = false; c->head_scale.armed = false;
-                   c->neuron_cap.armed = false; c->neuron_patch.armed = false; c->neuron_scale.armed = false; }
+  ~DisarmScope() {
+    c->probe.armed = c->drop.armed = c->lens.armed = false;
+    for (const aigv_ctx::RowOptEntry& e : c->row_opts) e.opt->armed = false;
+  }
 };
 int probe_plan(aigv_ctx* c, const char* op, const int32_t* cu, int B, const int32_t* off_host, ProbeArgs* out);
 int probe_layer(aigv_ctx* c, const ProbeArgs& plan, int li, bool cache, hipStream_t s);

@@ -2,6 +2,8 @@
 // score and lm heads, the KV-cache operations and the decode step.  Host-side C++ only; every device op is one of the hand-written
 // kernels, every GEMM goes through the dispatcher (dispatch.hip).
 #include <cmath>
+#include <cstdio>
+#include <cstring>
 
 #include "ctx.h"
 
@@ -226,8 +228,7 @@ static int llm_layer_qkv(aigv_ctx* c, int li, int T, hipStream_t s) {
 // launches | their side rows.  The last-layer lists hold, in launch order, the entries of the streamed chunks (activation row: the position inside the
 // 64-row chunk of t_ffn) and then, for a mixed batch, those of every other selected row (activation row: the packed row of l_ffn).
 struct NeuronPlan {
-  bool on[3] = {false, false, false};
-  bool split_last = false;              // the last layer finishes (some) rows on the weight-streaming path: its launches take the last-layer lists
+  bool split_last = false;            // the last layer finishes (some) rows on the weight-streaming path: its launches take the last-layer lists
   struct Last { std::vector<int32_t> act, side; std::vector<int> chunk_begin; int rest_begin = 0; } last[3];
 };
 enum { NEURON_AT_ROWS = -1, NEURON_AT_REST = -2 };   // where a hook acts: every row of l_ffn | l_ffn without the streamed rows | (>= 0) streamed chunk number
@@ -240,7 +241,7 @@ static int neuron_hook(aigv_ctx* c, const NeuronPlan& P, int li, bf16_t* act, in
   const aigv_ctx::NeuronRows* opt[3] = {&c->neuron_scale, &c->neuron_patch, &c->neuron_cap};
   for (int o = 0; o < 3; ++o) {
     const aigv_ctx::NeuronRows& r = *opt[o];
-    if (!P.on[o] || li < r.lo || li >= r.hi) continue;
+    if (!r.armed || li < r.lo || li >= r.hi) continue;
     const int32_t* base = c->l_neuronidx + (size_t)o * 3 * mt;
     const int32_t *idx = nullptr, *sidx = nullptr;
     int n = n_all;
@@ -264,6 +265,78 @@ static int neuron_hook(aigv_ctx* c, const NeuronPlan& P, int li, bf16_t* act, in
         HIPCHK(c, aigv_launch_neuron_rows(act, I, idx, sidx, n, r.buf, r.hi - r.lo, li - r.lo, I, cols, (int)r.cols.size(), o == 1 ? NEURON_PATCH : NEURON_CAPTURE, nullptr, 1.0f, s));
     }
   }
+  return 0;
+}
+
+// The tables of the armed neuron options go up on this stream, and the plan of their last-layer launches is built.  In the last layer of a trimmed or mixed
+// batch the value captured, patched or scaled for a row is the input of the w2 launch whose output the pass keeps for it: the streamed rows' (small_rows, 64 at
+// a time) is t_ffn - the packed row translated to (chunk, position), the side row passed beside it; trim: no other row's MLP runs; mixed: every other row's is l_ffn
+static int neuron_plan(aigv_ctx* c, const std::vector<int32_t>& small_rows, bool trim, bool mixed, hipStream_t s, NeuronPlan* plan) {
+  const aigv_config& k = c->cfg;
+  const aigv_ctx::NeuronRows* opt[3] = {&c->neuron_scale, &c->neuron_patch, &c->neuron_cap};
+  plan->split_last = trim || mixed;
+  const int last = k.llm_layers - 1, n_fin = (int)small_rows.size();
+  for (int o = 0; o < 3; ++o) {
+    const aigv_ctx::NeuronRows& r = *opt[o];
+    if (!r.armed) continue;
+    int32_t* base = c->l_neuronidx + (size_t)o * 3 * k.max_tokens;
+    if (!r.all_rows) HIPCHK(c, aigv_launch_write_ints(r.rows.data(), (int)r.rows.size(), base, s));
+    if (!r.cols.empty()) HIPCHK(c, aigv_launch_write_ints(r.cols.data(), (int)r.cols.size(), c->l_neuroncol + (size_t)o * AIGV_MAX_NEURON_SEL, s));
+    if (!r.factors.empty()) HIPCHK(c, aigv_launch_write_ints((const int32_t*)r.factors.data(), (int)r.factors.size(), (int32_t*)c->l_neuronfac, s));
+    if (!plan->split_last || r.all_rows || last < r.lo || last >= r.hi) continue;
+    NeuronPlan::Last& q = plan->last[o];
+    std::vector<char> streamed(r.rows.size(), 0);
+    for (int r0 = 0; r0 < n_fin; r0 += 64) {
+      q.chunk_begin.push_back((int)q.act.size());
+      for (int p = r0; p < std::min(n_fin, r0 + 64); ++p) {
+        const auto it = std::lower_bound(r.rows.begin(), r.rows.end(), small_rows[p]);
+        if (it == r.rows.end() || *it != small_rows[p]) continue;
+        q.act.push_back(p - r0); q.side.push_back((int32_t)(it - r.rows.begin()));
+        streamed[it - r.rows.begin()] = 1;
+      }
+    }
+    q.chunk_begin.push_back((int)q.act.size());
+    q.rest_begin = (int)q.act.size();
+    if (mixed)
+      for (size_t i = 0; i < r.rows.size(); ++i) if (!streamed[i]) { q.act.push_back(r.rows[i]); q.side.push_back((int32_t)i); }
+    if ((int)q.act.size() > k.max_tokens) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: the neuron options' last-layer row list (%d entries) exceeds max_tokens = %d", (int)q.act.size(), k.max_tokens);
+    if (!q.act.empty()) {
+      HIPCHK(c, aigv_launch_write_ints(q.act.data(), (int)q.act.size(), base + k.max_tokens, s));
+      HIPCHK(c, aigv_launch_write_ints(q.side.data(), (int)q.side.size(), base + 2 * (size_t)k.max_tokens, s));
+    }
+  }
+  return 0;
+}
+
+// activation patching: the stream layer li consumes - first the patch's rows written over it, then the capture's rows read from it (so a capture armed beside
+// a patch sees the patched rows); one launch each.  Row tables: l_streamidx, the patch's | the capture's
+static int stream_hook(aigv_ctx* c, int li, hipStream_t s) {
+  const int H = c->cfg.llm_hidden;
+  const aigv_ctx::RowOpt* opt[2] = {&c->stream_patch, &c->stream_cap};
+  for (int o = 0; o < 2; ++o) {
+    const aigv_ctx::RowOpt& r = *opt[o];
+    if (r.armed && li >= r.lo && li < r.hi)
+      HIPCHK(c, aigv_launch_stream_rows(c->l_h, H, c->l_streamidx + (size_t)o * c->cfg.max_tokens, (int)r.rows.size(), r.buf, r.hi - r.lo, li - r.lo, H, o == 0, s));
+  }
+  return 0;
+}
+
+// head knock-out / head patching: l_ao [T, n_heads * D] as wo of layer li consumes it - scale, then patch, then capture; at most one launch each (a table row
+// of ones: none).  Row tables: l_headidx, the scale's | the patch's | the capture's
+static int head_hook(aigv_ctx* c, int li, int T, hipStream_t s) {
+  const aigv_config& k = c->cfg;
+  const int H = k.llm_hidden, D = c->head_dim;
+  const size_t mt = (size_t)k.max_tokens;
+  const aigv_ctx::HeadRows &hs = c->head_scale, &hp = c->head_patch, &hc = c->head_cap;
+  if (hs.armed)
+    HIPCHK(c, aigv_launch_head_rows(c->l_ao, H, hs.all_rows ? nullptr : c->l_headidx, hs.all_rows ? T : (int)hs.rows.size(), nullptr, 1, 0, k.llm_heads, D, HEAD_SCALE,
+                                    ~(uint64_t)0, hs.scale.data() + (size_t)li * k.llm_heads, s));
+  if (hp.armed && li >= hp.lo && li < hp.hi)
+    HIPCHK(c, aigv_launch_head_rows(c->l_ao, H, c->l_headidx + mt, (int)hp.rows.size(), hp.buf, hp.hi - hp.lo, li - hp.lo, k.llm_heads, D, HEAD_PATCH,
+                                    hp.bits[li - hp.lo], nullptr, s));
+  if (hc.armed && li >= hc.lo && li < hc.hi)
+    HIPCHK(c, aigv_launch_head_rows(c->l_ao, H, c->l_headidx + 2 * mt, (int)hc.rows.size(), hc.buf, hc.hi - hc.lo, li - hc.lo, k.llm_heads, D, HEAD_CAPTURE,
+                                    ~(uint64_t)0, nullptr, s));
   return 0;
 }
 
@@ -329,24 +402,80 @@ static AttnArgs llm_attn_args(const aigv_ctx* c, int B) {
   return a;
 }
 
+// the first armed row option of a family ("stream", "head", "neuron") in the order a layer applies them: the one a refusal names; null: none is armed
+static const aigv_ctx::RowOptEntry* first_armed(const aigv_ctx* c, const char* family) {
+  for (const aigv_ctx::RowOptEntry& e : c->row_opts)
+    if (e.opt->armed && !strcmp(e.family, family)) return &e;
+  return nullptr;
+}
+
+// does the armed option act in layer `last`?  A scale: a factor there that is not exactly 1; a patch, a capture: the window
+static bool acts_in_layer(const aigv_ctx* c, const aigv_ctx::RowOpt* r, int last) {
+  if (r == &c->head_scale) {
+    const float* f = c->head_scale.scale.data() + (size_t)last * c->cfg.llm_heads;
+    return std::any_of(f, f + c->cfg.llm_heads, [](float x) { return x != 1.0f; });
+  }
+  if (r == &c->neuron_scale) {
+    const aigv_ctx::NeuronRows& ns = c->neuron_scale;
+    return (!ns.layer_scale.empty() && ns.layer_scale[last] != 1.0f) || (!ns.sel_begin.empty() && ns.sel_begin[last + 1] > ns.sel_begin[last]);
+  }
+  return r->lo <= last && last < r->hi;
+}
+
+// What aigv_llm_prefill is armed with, against the pass: T packed rows, nS score rows and R logit rows.  The row options family by family - a pass that keeps
+// its KV cache takes none (they are the scoring pass's: the paths that continue from a cache do not carry them); the row lists and windows against T and the L
+// layers; a pass without output rows breaks out in front of its last attention, so it takes no head or neuron option that acts in layer L - 1.  Then the depth
+// lens: every lens row must be a consumed row [score rows | logit rows] - the last layer finishes only those; lens_at: its place among them
+static int pass_options_check(aigv_ctx* c, int T, int keep_kv, const int32_t* score_rows, int nS, const int32_t* logit_rows, int R, int32_t* lens_at) {
+  const aigv_config& k = c->cfg;
+  const int last = k.llm_layers - 1;
+  const bool cut = nS + R == 0 && c->trim_last_layer;   // the pass breaks out in front of its last attention
+  for (const char* family : {"stream", "head", "neuron"}) {
+    const aigv_ctx::RowOptEntry* first = first_armed(c, family);
+    if (!first) continue;
+    if (keep_kv) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: keep_kv while a %s %s is armed (%s): only a pass without a KV cache takes one", family, first->what, first->arm);
+    if (!strcmp(family, "head") && (k.llm_heads > AIGV_MAX_HEAD_BITS || (c->head_dim != 64 && c->head_dim != 128)))
+      return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: a head %s is armed (%s) on a model of %d heads x %d: at most %d heads of 64 or 128", first->what, first->arm, k.llm_heads, c->head_dim, AIGV_MAX_HEAD_BITS);
+    bool reaches = false;
+    for (const aigv_ctx::RowOptEntry& e : c->row_opts) {
+      const aigv_ctx::RowOpt& r = *e.opt;
+      if (!r.armed || strcmp(e.family, family)) continue;
+      char label[96];
+      snprintf(label, sizeof label, "aigv_llm_prefill: the %s %s (%s)", e.family, e.what, e.arm);
+      if (!r.all_rows) TRY(stream_rows_check(c, label, r.rows.data(), (int)r.rows.size(), T, r.lo, r.hi, k.llm_layers));
+      reaches |= cut && e.skipped && acts_in_layer(c, &r, last);
+    }
+    if (reaches)
+      return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: a %s option reaches layer %d and the pass has no output rows (n_out == 0): the last layer's %s does not run", family, last, first->skipped);
+  }
+  if (!c->lens.armed) return 0;
+  if (nS + R == 0) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: the depth lens is armed and the pass has no output rows (n_out == 0): nothing finishes the last layer");
+  if (c->lens.n_score > 0 && nS == 0) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: the depth lens is armed with %d score rows and the pass has score == NULL (no score head runs)", c->lens.n_score);
+  for (int i = 0; i < c->lens.n_score + c->lens.n_token; ++i) {
+    int at = -1;
+    for (int j = 0; j < nS && at < 0; ++j) if (score_rows[j] == c->lens.rows[i]) at = j;
+    for (int j = 0; j < R && at < 0; ++j) if (logit_rows[j] == c->lens.rows[i]) at = nS + j;
+    if (at < 0) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: depth-lens row %d (packed row %d) is not among the pass's consumed rows (its score rows and logit rows): the last layer finishes only those", i, c->lens.rows[i]);
+    lens_at[i] = at;
+  }
+  return 0;
+}
+
 int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const int32_t* cu, int B, const void* vis,
                      int n_vis, const void* motion, const int32_t* score_rows, float* score, const int32_t* logit_rows,
                      int R, int64_t* argmax, int keep_kv, void* stream) {
   if (!c || !ids || !slot || !cu) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: null argument");
-  const bool probing = c->probe.armed;   // aigv_score_attention_arm: this pass carries the probe, and disarms on every way out
-  const bool dropping = c->drop.armed;   // aigv_key_drop_arm / _ex: the attention of the armed layers of this pass runs under the mask; disarmed likewise
-  const bool lensing = c->lens.armed;    // aigv_depth_lens_arm: this pass taps the lens rows after the embedding and after every layer; disarmed likewise
-  const bool patching = c->stream_patch.armed;    // aigv_stream_patch_arm: rows of the residual stream are overwritten in front of the armed layers; disarmed likewise
-  const bool capturing = c->stream_cap.armed;     // aigv_stream_capture_arm: rows of the residual stream are copied out in front of the armed layers; disarmed likewise
-  const bool h_scaling = c->head_scale.armed, h_patching = c->head_patch.armed, h_capturing = c->head_cap.armed;   // aigv_head_*_arm: l_ao between the attention and wo; disarmed likewise
-  const bool n_scaling = c->neuron_scale.armed, n_patching = c->neuron_patch.armed, n_capturing = c->neuron_cap.armed;   // aigv_neuron_*_arm: the row w2 consumes; disarmed likewise
+  // What the pass finds the context armed with stays in the records until the scope below ends, which disarms all of it on every way out.  probe
+  // (aigv_score_attention_arm): this pass carries the probe; drop (aigv_key_drop_arm / _ex): the attention of the armed layers runs under the mask; lens
+  // (aigv_depth_lens_arm): the lens rows are tapped after the embedding and after every layer; the row options (aigv_ctx::row_opts): stream rows overwritten /
+  // copied out in front of the armed layers, l_ao between the attention and wo, the row w2 consumes
   DisarmScope disarm(c);
   if (!c->finalized) return fail(c, AIGV_ERR_STATE, "aigv_llm_prefill: call aigv_finalize_weights first");
-  if (dropping && probing) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: a key-drop mask and the score-attention probe are both armed: the probe does not know the mask");
+  if (c->drop.armed && c->probe.armed) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: a key-drop mask and the score-attention probe are both armed: the probe does not know the mask");
   const aigv_config& k = c->cfg;
-  if (dropping && (c->drop.layer_begin < 0 || c->drop.layer_begin > c->drop.layer_end || c->drop.layer_end > k.llm_layers))
+  if (c->drop.armed && (c->drop.layer_begin < 0 || c->drop.layer_begin > c->drop.layer_end || c->drop.layer_end > k.llm_layers))
     return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: key-drop mask armed for layers [%d, %d), outside 0 <= begin <= end <= %d", c->drop.layer_begin, c->drop.layer_end, k.llm_layers);
-  if (dropping && keep_kv && (c->drop.rows || c->drop.layer_begin != 0 || c->drop.layer_end != k.llm_layers))
+  if (c->drop.armed && keep_kv && (c->drop.rows || c->drop.layer_begin != 0 || c->drop.layer_end != k.llm_layers))
     return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: keep_kv under a key-drop mask with row words or a partial layer window (aigv_key_drop_arm_ex): the mask kept "
                                  "beside the KV cache has neither");
   if (B <= 0 || B > k.max_seqs) return fail(c, AIGV_ERR_ARG, "n_clips %d outside 1..%d", B, k.max_seqs);
@@ -364,69 +493,12 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
   if (n_vis < 0 || (n_vis > 0 && !vis)) return fail(c, AIGV_ERR_ARG, "visual tokens missing");
   if (keep_kv && (k.kv_capacity <= 0 || max_len >= k.kv_capacity))
     return fail(c, AIGV_ERR_STATE, "keep_kv needs kv_capacity > longest prompt (%d vs %d)", k.kv_capacity, max_len);
-  if (dropping && (!c->drop.words || c->drop.ld < (max_len + 63) / 64))
+  if (c->drop.armed && (!c->drop.words || c->drop.ld < (max_len + 63) / 64))
     return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: key-drop mask armed with %d words per clip, the longest clip (%d tokens) needs %d", c->drop.ld, max_len,
                 (max_len + 63) / 64);
-  // activation patching: the row lists against this pass's T rows and L layers; a pass that keeps its KV cache takes neither (the options are the
-  // scoring pass's: the paths that continue from a cache do not carry them)
-  if ((patching || capturing) && keep_kv)
-    return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: keep_kv while a stream %s is armed (%s): only a pass without a KV cache takes one", patching ? "patch" : "capture",
-                patching ? "aigv_stream_patch_arm" : "aigv_stream_capture_arm");
-  const aigv_ctx::StreamRows &sp = c->stream_patch, &sc = c->stream_cap;
-  if (patching) TRY(stream_rows_check(c, "aigv_llm_prefill: the stream patch (aigv_stream_patch_arm)", sp.rows.data(), (int)sp.rows.size(), T, sp.lo, sp.hi, k.llm_layers));
-  if (capturing) TRY(stream_rows_check(c, "aigv_llm_prefill: the stream capture (aigv_stream_capture_arm)", sc.rows.data(), (int)sc.rows.size(), T, sc.lo, sc.hi, k.llm_layers));
-  // head knock-out / head patching: likewise.  The scale's window is [0, L) (its table has a row per layer); a pass without output rows breaks out in
-  // front of its last attention, so it takes no head option whose window reaches layer L - 1
-  const aigv_ctx::HeadRows &hs = c->head_scale, &hp = c->head_patch, &hc = c->head_cap;
-  if (h_scaling || h_patching || h_capturing) {
-    const char* what = h_scaling ? "scale" : h_patching ? "patch" : "capture";
-    const char* arm = h_scaling ? "aigv_head_scale_arm" : h_patching ? "aigv_head_patch_arm" : "aigv_head_capture_arm";
-    if (keep_kv) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: keep_kv while a head %s is armed (%s): only a pass without a KV cache takes one", what, arm);
-    if (k.llm_heads > AIGV_MAX_HEAD_BITS || (c->head_dim != 64 && c->head_dim != 128))
-      return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: a head %s is armed (%s) on a model of %d heads x %d: at most %d heads of 64 or 128", what, arm, k.llm_heads, c->head_dim, AIGV_MAX_HEAD_BITS);
-    if (h_scaling && !hs.all_rows) TRY(stream_rows_check(c, "aigv_llm_prefill: the head scale (aigv_head_scale_arm)", hs.rows.data(), (int)hs.rows.size(), T, 0, k.llm_layers, k.llm_layers));
-    if (h_patching) TRY(stream_rows_check(c, "aigv_llm_prefill: the head patch (aigv_head_patch_arm)", hp.rows.data(), (int)hp.rows.size(), T, hp.lo, hp.hi, k.llm_layers));
-    if (h_capturing) TRY(stream_rows_check(c, "aigv_llm_prefill: the head capture (aigv_head_capture_arm)", hc.rows.data(), (int)hc.rows.size(), T, hc.lo, hc.hi, k.llm_layers));
-    if ((score ? B : 0) + R == 0 && c->trim_last_layer) {
-      const int last = k.llm_layers - 1;
-      bool scale_last = false;
-      if (h_scaling) for (int h = 0; h < k.llm_heads; ++h) scale_last |= hs.scale[(size_t)last * k.llm_heads + h] != 1.0f;
-      const bool reaches = scale_last || (h_patching && hp.lo <= last && last < hp.hi) || (h_capturing && hc.lo <= last && last < hc.hi);
-      if (reaches) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: a head option reaches layer %d and the pass has no output rows (n_out == 0): the last layer's attention does not run", last);
-    }
-  }
-  // MLP neuron knock-out / neuron patching: likewise.  A pass without output rows breaks out in front of its last attention: its last MLP does not run
-  const aigv_ctx::NeuronRows &ns = c->neuron_scale, &npat = c->neuron_patch, &ncap = c->neuron_cap;
-  const bool n_any = n_scaling || n_patching || n_capturing;
-  if (n_any) {
-    const char* what = n_scaling ? "scale" : n_patching ? "patch" : "capture";
-    const char* arm = n_scaling ? "aigv_neuron_scale_arm" : n_patching ? "aigv_neuron_patch_arm" : "aigv_neuron_capture_arm";
-    if (keep_kv) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: keep_kv while a neuron %s is armed (%s): only a pass without a KV cache takes one", what, arm);
-    if (n_scaling && !ns.all_rows) TRY(stream_rows_check(c, "aigv_llm_prefill: the neuron scale (aigv_neuron_scale_arm)", ns.rows.data(), (int)ns.rows.size(), T, 0, k.llm_layers, k.llm_layers));
-    if (n_patching) TRY(stream_rows_check(c, "aigv_llm_prefill: the neuron patch (aigv_neuron_patch_arm)", npat.rows.data(), (int)npat.rows.size(), T, npat.lo, npat.hi, k.llm_layers));
-    if (n_capturing) TRY(stream_rows_check(c, "aigv_llm_prefill: the neuron capture (aigv_neuron_capture_arm)", ncap.rows.data(), (int)ncap.rows.size(), T, ncap.lo, ncap.hi, k.llm_layers));
-    if ((score ? B : 0) + R == 0 && c->trim_last_layer) {
-      const int last = k.llm_layers - 1;
-      const bool scale_last = n_scaling && ((!ns.layer_scale.empty() && ns.layer_scale[last] != 1.0f) || (!ns.sel_begin.empty() && ns.sel_begin[last + 1] > ns.sel_begin[last]));
-      const bool reaches = scale_last || (n_patching && npat.lo <= last && last < npat.hi) || (n_capturing && ncap.lo <= last && last < ncap.hi);
-      if (reaches) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: a neuron option reaches layer %d and the pass has no output rows (n_out == 0): the last layer's MLP does not run", last);
-    }
-  }
-  // the depth lens: every lens row must be a consumed row [score rows | logit rows] - the last layer finishes only those; lens_at: its place among them
-  const int n_lens = lensing ? c->lens.n_score + c->lens.n_token : 0;
-  int32_t lens_at[2 * AIGV_MAX_LENS_ROWS];
-  if (lensing) {
-    const int nS = score ? B : 0;
-    if (nS + R == 0) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: the depth lens is armed and the pass has no output rows (n_out == 0): nothing finishes the last layer");
-    if (c->lens.n_score > 0 && !score) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: the depth lens is armed with %d score rows and the pass has score == NULL (no score head runs)", c->lens.n_score);
-    for (int i = 0; i < n_lens; ++i) {
-      int at = -1;
-      for (int j = 0; j < nS && at < 0; ++j) if (score_rows[j] == c->lens.rows[i]) at = j;
-      for (int j = 0; j < R && at < 0; ++j) if (logit_rows[j] == c->lens.rows[i]) at = nS + j;
-      if (at < 0) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: depth-lens row %d (packed row %d) is not among the pass's consumed rows (its score rows and logit rows): the last layer finishes only those", i, c->lens.rows[i]);
-      lens_at[i] = at;
-    }
-  }
+  const int n_lens = c->lens.armed ? c->lens.n_score + c->lens.n_token : 0;
+  int32_t lens_at[2 * AIGV_MAX_LENS_ROWS];   // the lens rows' places among the consumed rows
+  TRY(pass_options_check(c, T, keep_kv, score_rows, score ? B : 0, logit_rows, R, lens_at));
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)stream;
   const int H = k.llm_hidden, I = k.llm_inter, D = c->head_dim, g = c->g, nkv = k.llm_kv_heads;
@@ -447,12 +519,13 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
     HIPCHK(c, aigv_launch_lens_tap(src, H, idx, n_lens, c->final_norm, c->lens.hidden + off, c->lens.normed + off, H, k.rms_eps, s));
     return 0;
   };
-  if (patching) HIPCHK(c, aigv_launch_write_ints(sp.rows.data(), (int)sp.rows.size(), c->l_streamidx, s));
-  if (capturing) HIPCHK(c, aigv_launch_write_ints(sc.rows.data(), (int)sc.rows.size(), c->l_streamidx + k.max_tokens, s));
-  if (h_scaling && !hs.all_rows) HIPCHK(c, aigv_launch_write_ints(hs.rows.data(), (int)hs.rows.size(), c->l_headidx, s));
-  if (h_patching) HIPCHK(c, aigv_launch_write_ints(hp.rows.data(), (int)hp.rows.size(), c->l_headidx + k.max_tokens, s));
-  if (h_capturing) HIPCHK(c, aigv_launch_write_ints(hc.rows.data(), (int)hc.rows.size(), c->l_headidx + 2 * (size_t)k.max_tokens, s));
-  if (lensing) {
+  // the row tables of the armed stream and head options go up on this stream, a max_tokens slot each in the order a layer applies them (the neuron options': neuron_plan)
+  const aigv_ctx::RowOpt *st[2] = {&c->stream_patch, &c->stream_cap}, *hd[3] = {&c->head_scale, &c->head_patch, &c->head_cap};
+  for (int o = 0; o < 2; ++o)
+    if (st[o]->armed) HIPCHK(c, aigv_launch_write_ints(st[o]->rows.data(), (int)st[o]->rows.size(), c->l_streamidx + (size_t)o * k.max_tokens, s));
+  for (int o = 0; o < 3; ++o)
+    if (hd[o]->armed && !hd[o]->all_rows) HIPCHK(c, aigv_launch_write_ints(hd[o]->rows.data(), (int)hd[o]->rows.size(), c->l_headidx + (size_t)o * k.max_tokens, s));
+  if (c->lens.armed) {
     HIPCHK(c, aigv_launch_write_ints(c->lens.rows, n_lens, c->l_lensidx, s));
     HIPCHK(c, aigv_launch_write_ints(lens_at, n_lens, c->l_lensidx + 2 * AIGV_MAX_LENS_ROWS, s));
   }
@@ -484,65 +557,23 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
   const bool trim = trim_ok && (int)small_rows.size() == n_out;
   const bool mixed = trim_ok && !trim && !small_rows.empty();
   if (mixed) HIPCHK(c, aigv_launch_write_ints(small_rows.data(), (int)small_rows.size(), c->l_rowidx2, s));
-  // MLP neuron knock-out / neuron patching: the row and column tables go up on this stream.  In the last layer of a trimmed or mixed batch the value
-  // captured, patched or scaled for a row is the input of the w2 launch whose output the pass keeps for it: the streamed rows' (small_rows, 64 at a time)
-  // is t_ffn - the packed row translated to (chunk, position), the side row passed beside it; trim: no other row's MLP runs; mixed: every other row's is l_ffn
   NeuronPlan nplan;
-  if (n_any) {
-    const aigv_ctx::NeuronRows* opt[3] = {&ns, &npat, &ncap};
-    nplan.on[0] = n_scaling; nplan.on[1] = n_patching; nplan.on[2] = n_capturing;
-    nplan.split_last = trim || mixed;
-    const int last = k.llm_layers - 1, n_fin = (int)small_rows.size();
-    for (int o = 0; o < 3; ++o) {
-      const aigv_ctx::NeuronRows& r = *opt[o];
-      if (!nplan.on[o]) continue;
-      int32_t* base = c->l_neuronidx + (size_t)o * 3 * k.max_tokens;
-      if (!r.all_rows) HIPCHK(c, aigv_launch_write_ints(r.rows.data(), (int)r.rows.size(), base, s));
-      if (!r.cols.empty()) HIPCHK(c, aigv_launch_write_ints(r.cols.data(), (int)r.cols.size(), c->l_neuroncol + (size_t)o * AIGV_MAX_NEURON_SEL, s));
-      if (!r.factors.empty()) HIPCHK(c, aigv_launch_write_ints((const int32_t*)r.factors.data(), (int)r.factors.size(), (int32_t*)c->l_neuronfac, s));
-      if (!nplan.split_last || r.all_rows || last < r.lo || last >= r.hi) continue;
-      NeuronPlan::Last& q = nplan.last[o];
-      std::vector<char> streamed(r.rows.size(), 0);
-      for (int r0 = 0; r0 < n_fin; r0 += 64) {
-        q.chunk_begin.push_back((int)q.act.size());
-        for (int p = r0; p < std::min(n_fin, r0 + 64); ++p) {
-          const auto it = std::lower_bound(r.rows.begin(), r.rows.end(), small_rows[p]);
-          if (it == r.rows.end() || *it != small_rows[p]) continue;
-          q.act.push_back(p - r0); q.side.push_back((int32_t)(it - r.rows.begin()));
-          streamed[it - r.rows.begin()] = 1;
-        }
-      }
-      q.chunk_begin.push_back((int)q.act.size());
-      q.rest_begin = (int)q.act.size();
-      if (mixed)
-        for (size_t i = 0; i < r.rows.size(); ++i) if (!streamed[i]) { q.act.push_back(r.rows[i]); q.side.push_back((int32_t)i); }
-      if ((int)q.act.size() > k.max_tokens) return fail(c, AIGV_ERR_ARG, "aigv_llm_prefill: the neuron options' last-layer row list (%d entries) exceeds max_tokens = %d", (int)q.act.size(), k.max_tokens);
-      if (!q.act.empty()) {
-        HIPCHK(c, aigv_launch_write_ints(q.act.data(), (int)q.act.size(), base + k.max_tokens, s));
-        HIPCHK(c, aigv_launch_write_ints(q.side.data(), (int)q.side.size(), base + 2 * (size_t)k.max_tokens, s));
-      }
-    }
-  }
-  const NeuronPlan* np = n_any ? &nplan : nullptr;
+  const NeuronPlan* np = first_armed(c, "neuron") ? &nplan : nullptr;
+  if (np) TRY(neuron_plan(c, small_rows, trim, mixed, s, &nplan));
   ProbeArgs probe{};
-  if (probing) TRY(probe_plan(c, "aigv_llm_prefill", cu, B, nullptr, &probe));
+  if (c->probe.armed) TRY(probe_plan(c, "aigv_llm_prefill", cu, B, nullptr, &probe));
   double attn_flops = 0;
   for (int b = 0; b < B; ++b) { const double L = cu[b + 1] - cu[b]; attn_flops += 4.0 * (L * (L + 1) / 2) * D * k.llm_heads; }
   const size_t kv_layer = (size_t)k.max_seqs * nkv * k.kv_capacity * D;
   for (int li = 0; li < k.llm_layers; ++li) {
     const LlmLayer& L = c->llm[li];
-    // activation patching: the stream layer li consumes - first the patch's rows written over it, then the capture's rows read from it (so a capture
-    // armed beside a patch sees the patched rows); one launch each
-    if (patching && li >= sp.lo && li < sp.hi)
-      HIPCHK(c, aigv_launch_stream_rows(c->l_h, H, c->l_streamidx, (int)sp.rows.size(), sp.buf, sp.hi - sp.lo, li - sp.lo, H, true, s));
-    if (capturing && li >= sc.lo && li < sc.hi)
-      HIPCHK(c, aigv_launch_stream_rows(c->l_h, H, c->l_streamidx + k.max_tokens, (int)sc.rows.size(), sc.buf, sc.hi - sc.lo, li - sc.lo, H, false, s));
-    if (lensing) TRY(lens_tap(li, c->l_h, lens_idx));   // depth li < L: the stream this layer consumes, behind a patch of this depth
+    TRY(stream_hook(c, li, s));
+    if (c->lens.armed) TRY(lens_tap(li, c->l_h, lens_idx));   // depth li < L: the stream this layer consumes, behind a patch of this depth
     TRY(llm_layer_qkv(c, li, T, s));
     if (keep_kv)
       HIPCHK(c, aigv_launch_kv_store(c->l_qkv, c->qkv_out, c->l_seq, c->l_pos, c->kc + li * kv_layer, c->vc + li * kv_layer, T,
                                      nkv, g, D, k.kv_capacity, s));
-    if (probing) TRY(probe_layer(c, probe, li, false, s));   // Q and rotated K of this pass's rows, straight from l_qkv (every layer: it does not read l_ao)
+    if (c->probe.armed) TRY(probe_layer(c, probe, li, false, s));   // Q and rotated K of this pass's rows, straight from l_qkv (every layer: it does not read l_ao)
     // a pass that only fills the cache (no output rows) needs nothing of the last layer beyond its K/V
     if (n_out == 0 && c->trim_last_layer && li == k.llm_layers - 1) break;
     {
@@ -553,23 +584,15 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
       const bool last_trim = trim && li == k.llm_layers - 1;
       // (a head capture of the last layer reads rows the trimmed launch would skip: that one launch covers every row - in the causal kernel q_tail
       // only skips blocks and waves, so the consumed rows keep their bits)
-      a.q_tail = last_trim && !(h_capturing && li >= hc.lo && li < hc.hi && !hc.rows.empty()) ? q_tail : 0;
+      const aigv_ctx::HeadRows& hc = c->head_cap;
+      a.q_tail = last_trim && !(hc.armed && li >= hc.lo && li < hc.hi && !hc.rows.empty()) ? q_tail : 0;
       // the armed layers, the row-trimmed last one included; the others run the unmasked launch they always ran
-      if (dropping && li >= c->drop.layer_begin && li < c->drop.layer_end) { a.key_drop = c->drop.words; a.ld_drop = c->drop.ld; a.drop_rows = c->drop.rows; }
+      if (c->drop.armed && li >= c->drop.layer_begin && li < c->drop.layer_end) { a.key_drop = c->drop.words; a.ld_drop = c->drop.ld; a.drop_rows = c->drop.rows; }
       if (const char* m = aigv_attn_check(a, D)) return fail(c, AIGV_ERR_ARG, "%s", m);
       ProfScope ps(c, AIGV_PROF_ATTN_LLM, last_trim ? 0.0 : attn_flops, 2.0 * T * ((double)c->qkv_out + H), s);
       HIPCHK(c, aigv_launch_attention(a, D, s));
     }
-    // head knock-out / head patching: l_ao as wo consumes it - scale, then patch, then capture; at most one launch each (a table row of ones: none)
-    if (h_scaling)
-      HIPCHK(c, aigv_launch_head_rows(c->l_ao, H, hs.all_rows ? nullptr : c->l_headidx, hs.all_rows ? T : (int)hs.rows.size(), nullptr, 1, 0, k.llm_heads, D, HEAD_SCALE,
-                                      ~(uint64_t)0, hs.scale.data() + (size_t)li * k.llm_heads, s));
-    if (h_patching && li >= hp.lo && li < hp.hi)
-      HIPCHK(c, aigv_launch_head_rows(c->l_ao, H, c->l_headidx + k.max_tokens, (int)hp.rows.size(), hp.buf, hp.hi - hp.lo, li - hp.lo, k.llm_heads, D, HEAD_PATCH,
-                                      hp.bits[li - hp.lo], nullptr, s));
-    if (h_capturing && li >= hc.lo && li < hc.hi)
-      HIPCHK(c, aigv_launch_head_rows(c->l_ao, H, c->l_headidx + 2 * (size_t)k.max_tokens, (int)hc.rows.size(), hc.buf, hc.hi - hc.lo, li - hc.lo, k.llm_heads, D, HEAD_CAPTURE,
-                                      ~(uint64_t)0, nullptr, s));
+    TRY(head_hook(c, li, T, s));
     if ((trim || mixed) && li == k.llm_layers - 1) {
       // 64 rows at a time through the weight-streaming kernel in its fixed 4-slice form (p = 0: the same bits whatever the row count);
       // the finished rows collect in l_trim_h, in l_rowidx (mixed: l_rowidx2) order
@@ -588,20 +611,20 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
         TRY(run_skinny(c, t_ffn, I, nr, L.w2, I, H, I, nullptr, h, H, h, H, SK_RESID, s, 0));
       }
       if (trim) {
-        if (lensing) TRY(lens_tap(k.llm_layers, t_h, lens_idx + 2 * AIGV_MAX_LENS_ROWS));          // depth L: the finished rows, in l_rowidx order
+        if (c->lens.armed) TRY(lens_tap(k.llm_layers, t_h, lens_idx + 2 * AIGV_MAX_LENS_ROWS));          // depth L: the finished rows, in l_rowidx order
         TRY(final_rows(c, score, B, R, argmax, t_h, true, s));
         break;
       }
       TRY(llm_layer_post(c, li, T, s, np, NEURON_AT_REST));                                      // every row on the tile kernels ...
       HIPCHK(c, aigv_launch_scatter_rows(t_h, c->l_rowidx2, n_fin, c->l_h, H, H, s));            // ... the small clips' consumed rows put back
-      if (lensing) TRY(lens_tap(k.llm_layers, c->l_h, lens_idx));
+      if (c->lens.armed) TRY(lens_tap(k.llm_layers, c->l_h, lens_idx));
       break;
     }
     TRY(llm_layer_post(c, li, T, s, np));
-    if (lensing && li == k.llm_layers - 1) TRY(lens_tap(k.llm_layers, c->l_h, lens_idx));   // depth L of a pass whose last layer ran for every row
+    if (c->lens.armed && li == k.llm_layers - 1) TRY(lens_tap(k.llm_layers, c->l_h, lens_idx));   // depth L of a pass whose last layer ran for every row
   }
   if (!trim) TRY(final_rows(c, score, B, R, argmax, c->l_h, false, s));
-  if (lensing && c->lens.n_score > 0) {
+  if (c->lens.armed && c->lens.n_score > 0) {
     // the score head on the score rows of every depth: each depth a batch slice with a NaN guard of its own, as many depths per call as the
     // head's workspace (64 rows) holds
     const int nS = c->lens.n_score, per = std::max(1, 64 / nS);
@@ -617,8 +640,8 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
     TRY(upload_decode_state(c, B, s));
     // a masked pass keeps its mask with the cache: every clip's words cut to its length, zero from there to the row's end (on the pass's stream, into
     // the context's own buffer: nothing is allocated, the pass still captures); aigv_llm_extend and the decode steps then run under it
-    if (dropping) HIPCHK(c, aigv_launch_kv_drop_rows(c->drop.words, c->drop.ld, nullptr, c->l_cu, 1, c->kv_drop, c->kv_drop_ld, B, s));
-    c->kv_masked = dropping;
+    if (c->drop.armed) HIPCHK(c, aigv_launch_kv_drop_rows(c->drop.words, c->drop.ld, nullptr, c->l_cu, 1, c->kv_drop, c->kv_drop_ld, B, s));
+    c->kv_masked = c->drop.armed;
     c->kv_valid = true;
   } else {
     c->kv_valid = false;
@@ -671,54 +694,49 @@ int aigv_depth_lens_arm(aigv_ctx* c, const int32_t* score_rows_host, int n_score
   return 0;
 }
 
-// Arm the next aigv_llm_prefill with a capture / a patch of residual-stream rows (include/aigv_amd.h): the row numbers are copied here and checked, with
-// the window, when that pass runs; the buffer is the caller's.
-static int stream_rows_arm(const char* op, aigv_ctx* c, aigv_ctx::StreamRows* st, const int32_t* rows_host, int n, int lo, int hi, void* buf_bf16_dev) {
+// Arm the next aigv_llm_prefill with a row option (include/aigv_amd.h; aigv_ctx::row_opts): what the arming entry points share.  The row numbers are copied
+// here and checked, with the window, when that pass runs; the device buffer is the caller's.  rows_optional (a scale): no row list means every row;
+// need_buf: the option moves data through `buf`; family_check (null: none), handed cols_host and m: the family's own checks, run where they have always run -
+// behind the row list's, in front of the buffer's
+typedef int (*FamilyCheck)(const char* op, aigv_ctx* c, const int32_t* cols_host, int m);
+static int rows_arm(const char* op, aigv_ctx* c, aigv_ctx::RowOpt* st, const int32_t* rows_host, int n, int lo, int hi, void* buf_bf16_dev, bool rows_optional, bool need_buf,
+                    FamilyCheck family_check = nullptr, const int32_t* cols_host = nullptr, int m = 0) {
   if (!c) return fail(c, AIGV_ERR_ARG, "%s: null context", op);
   if (n < 0 || n > c->cfg.max_tokens) return fail(c, AIGV_ERR_ARG, "%s: %d rows outside 0..max_tokens = %d", op, n, c->cfg.max_tokens);
-  if (n > 0 && !rows_host) return fail(c, AIGV_ERR_ARG, "%s: null row list", op);
-  if (n > 0 && hi > lo && (!buf_bf16_dev || ((uintptr_t)buf_bf16_dev & 15))) return fail(c, AIGV_ERR_ARG, "%s: the device buffer is null or not 16-byte aligned", op);
-  st->rows.assign(rows_host, rows_host + n);
+  if (n > 0 && !rows_host && !rows_optional) return fail(c, AIGV_ERR_ARG, "%s: null row list", op);
+  if (family_check) TRY(family_check(op, c, cols_host, m));
+  if (need_buf && n > 0 && hi > lo && (!buf_bf16_dev || ((uintptr_t)buf_bf16_dev & 15))) return fail(c, AIGV_ERR_ARG, "%s: the device buffer is null or not 16-byte aligned", op);
+  st->all_rows = rows_optional && !rows_host;
+  if (rows_host) st->rows.assign(rows_host, rows_host + n); else st->rows.clear();
   st->lo = lo; st->hi = hi;
   st->buf = (bf16_t*)buf_bf16_dev;
   st->armed = true;
   return 0;
 }
 
+// ---- residual-stream rows
 int aigv_stream_capture_arm(aigv_ctx* c, const int32_t* rows_host, int n, int lo, int hi, void* out_bf16_dev) {
-  return stream_rows_arm("aigv_stream_capture_arm", c, c ? &c->stream_cap : nullptr, rows_host, n, lo, hi, out_bf16_dev);
+  return rows_arm("aigv_stream_capture_arm", c, c ? &c->stream_cap : nullptr, rows_host, n, lo, hi, out_bf16_dev, false, true);
 }
 
 int aigv_stream_patch_arm(aigv_ctx* c, const int32_t* rows_host, int n, int lo, int hi, const void* values_bf16_dev) {
-  return stream_rows_arm("aigv_stream_patch_arm", c, c ? &c->stream_patch : nullptr, rows_host, n, lo, hi, const_cast<void*>(values_bf16_dev));
+  return rows_arm("aigv_stream_patch_arm", c, c ? &c->stream_patch : nullptr, rows_host, n, lo, hi, const_cast<void*>(values_bf16_dev), false, true);
 }
 
-// Arm the next aigv_llm_prefill with a capture / a patch / a scale of per-head attention outputs (include/aigv_amd.h): the host arrays are copied here; rows
-// and windows are checked when that pass runs; the device buffer is the caller's.
-static int head_rows_arm(const char* op, aigv_ctx* c, aigv_ctx::HeadRows* st, const int32_t* rows_host, int n, int lo, int hi, void* buf_bf16_dev, bool need_buf) {
-  if (!c) return fail(c, AIGV_ERR_ARG, "%s: null context", op);
-  if (n < 0 || n > c->cfg.max_tokens) return fail(c, AIGV_ERR_ARG, "%s: %d rows outside 0..max_tokens = %d", op, n, c->cfg.max_tokens);
-  if (n > 0 && !rows_host && need_buf) return fail(c, AIGV_ERR_ARG, "%s: null row list", op);
+// ---- per-head attention outputs: the host arrays are copied here
+static int head_count_check(const char* op, aigv_ctx* c, const int32_t*, int) {
   if (c->cfg.llm_heads > AIGV_MAX_HEAD_BITS) return fail(c, AIGV_ERR_ARG, "%s: the model has %d query heads: a head mask holds at most %d", op, c->cfg.llm_heads, AIGV_MAX_HEAD_BITS);
-  if (need_buf && n > 0 && hi > lo && (!buf_bf16_dev || ((uintptr_t)buf_bf16_dev & 15))) return fail(c, AIGV_ERR_ARG, "%s: the device buffer is null or not 16-byte aligned", op);
-  st->all_rows = !rows_host && !need_buf;
-  if (rows_host) st->rows.assign(rows_host, rows_host + n); else st->rows.clear();
-  st->lo = lo; st->hi = hi;
-  st->buf = (bf16_t*)buf_bf16_dev;
   return 0;
 }
 
 int aigv_head_capture_arm(aigv_ctx* c, const int32_t* rows_host, int n, int lo, int hi, void* out_bf16_dev) {
-  TRY(head_rows_arm("aigv_head_capture_arm", c, c ? &c->head_cap : nullptr, rows_host, n, lo, hi, out_bf16_dev, true));
-  c->head_cap.armed = true;
-  return 0;
+  return rows_arm("aigv_head_capture_arm", c, c ? &c->head_cap : nullptr, rows_host, n, lo, hi, out_bf16_dev, false, true, head_count_check);
 }
 
 int aigv_head_patch_arm(aigv_ctx* c, const int32_t* rows_host, int n, int lo, int hi, const uint64_t* head_bits_host, const void* values_bf16_dev) {
-  TRY(head_rows_arm("aigv_head_patch_arm", c, c ? &c->head_patch : nullptr, rows_host, n, lo, hi, const_cast<void*>(values_bf16_dev), true));
+  TRY(rows_arm("aigv_head_patch_arm", c, c ? &c->head_patch : nullptr, rows_host, n, lo, hi, const_cast<void*>(values_bf16_dev), false, true, head_count_check));
   const int w = hi > lo ? hi - lo : 0;
   if (head_bits_host) c->head_patch.bits.assign(head_bits_host, head_bits_host + w); else c->head_patch.bits.assign(w, ~(uint64_t)0);
-  c->head_patch.armed = true;
   return 0;
 }
 
@@ -730,16 +748,16 @@ int aigv_head_scale_arm(aigv_ctx* c, const int32_t* rows_host, int n, const floa
   for (size_t i = 0; i < cells; ++i)
     if (scale_host[i] != scale_host[i])
       return fail(c, AIGV_ERR_ARG, "%s: scale[%d][%d] is NaN", op, (int)(i / c->cfg.llm_heads), (int)(i % c->cfg.llm_heads));
-  TRY(head_rows_arm(op, c, &c->head_scale, rows_host, rows_host ? n : 0, 0, 0, nullptr, false));
+  TRY(rows_arm(op, c, &c->head_scale, rows_host, rows_host ? n : 0, 0, c->cfg.llm_layers, nullptr, true, false, head_count_check));
   c->head_scale.scale.assign(scale_host, scale_host + cells);
-  c->head_scale.lo = 0; c->head_scale.hi = c->cfg.llm_layers;
-  c->head_scale.armed = true;
   return 0;
 }
 
-// Arm the next aigv_llm_prefill with a capture / a patch / a scale of MLP neurons (include/aigv_amd.h): the host arrays are copied here; rows and windows
-// are checked when that pass runs; the device buffer is the caller's.
-static int neuron_cols_check(const char* op, aigv_ctx* c, const int32_t* cols, int m, int I) {
+// ---- MLP neurons: the host arrays are copied here.  The family's checks: the model's I, then the column list (null: every neuron)
+static int neuron_cols_check(const char* op, aigv_ctx* c, const int32_t* cols, int m) {
+  const int I = c->cfg.llm_inter;
+  if (I % 8) return fail(c, AIGV_ERR_ARG, "%s: the model's intermediate size %d is no multiple of 8", op, I);
+  if (!cols) return 0;
   if (m < 0 || m > AIGV_MAX_NEURON_SEL) return fail(c, AIGV_ERR_ARG, "%s: %d columns outside 0..%d", op, m, AIGV_MAX_NEURON_SEL);
   for (int j = 0; j < m; ++j) {
     if (cols[j] < 0 || cols[j] >= I) return fail(c, AIGV_ERR_ARG, "%s: column %d (entry %d) outside 0..%d", op, cols[j], j, I - 1);
@@ -748,29 +766,20 @@ static int neuron_cols_check(const char* op, aigv_ctx* c, const int32_t* cols, i
   return 0;
 }
 
-static int neuron_rows_arm(const char* op, aigv_ctx* c, aigv_ctx::NeuronRows* st, const int32_t* rows_host, int n, int lo, int hi, const int32_t* cols_host, int m, void* buf_bf16_dev) {
-  if (!c) return fail(c, AIGV_ERR_ARG, "%s: null context", op);
-  if (n < 0 || n > c->cfg.max_tokens) return fail(c, AIGV_ERR_ARG, "%s: %d rows outside 0..max_tokens = %d", op, n, c->cfg.max_tokens);
-  if (n > 0 && !rows_host) return fail(c, AIGV_ERR_ARG, "%s: null row list", op);
-  if (c->cfg.llm_inter % 8) return fail(c, AIGV_ERR_ARG, "%s: the model's intermediate size %d is no multiple of 8", op, c->cfg.llm_inter);
-  if (cols_host) TRY(neuron_cols_check(op, c, cols_host, m, c->cfg.llm_inter));
-  if (n > 0 && hi > lo && (!cols_host || m > 0) && (!buf_bf16_dev || ((uintptr_t)buf_bf16_dev & 15))) return fail(c, AIGV_ERR_ARG, "%s: the device buffer is null or not 16-byte aligned", op);
-  st->all_rows = false;
-  st->rows.assign(rows_host, rows_host + n);
+// a capture / a patch of the columns cols_host (null: every neuron); an empty list moves nothing and needs no buffer
+static int neuron_window_arm(const char* op, aigv_ctx* c, aigv_ctx::NeuronRows* st, const int32_t* rows_host, int n, int lo, int hi, const int32_t* cols_host, int m, void* buf_bf16_dev) {
+  TRY(rows_arm(op, c, st, rows_host, n, lo, hi, buf_bf16_dev, false, !cols_host || m > 0, neuron_cols_check, cols_host, m));
   st->dense = !cols_host;
   if (cols_host) st->cols.assign(cols_host, cols_host + m); else st->cols.clear();
-  st->lo = lo; st->hi = hi;
-  st->buf = (bf16_t*)buf_bf16_dev;
-  st->armed = true;
   return 0;
 }
 
 int aigv_neuron_capture_arm(aigv_ctx* c, const int32_t* rows_host, int n, int lo, int hi, const int32_t* cols_host, int m, void* out_bf16_dev) {
-  return neuron_rows_arm("aigv_neuron_capture_arm", c, c ? &c->neuron_cap : nullptr, rows_host, n, lo, hi, cols_host, m, out_bf16_dev);
+  return neuron_window_arm("aigv_neuron_capture_arm", c, c ? &c->neuron_cap : nullptr, rows_host, n, lo, hi, cols_host, m, out_bf16_dev);
 }
 
 int aigv_neuron_patch_arm(aigv_ctx* c, const int32_t* rows_host, int n, int lo, int hi, const int32_t* cols_host, int m, const void* values_bf16_dev) {
-  return neuron_rows_arm("aigv_neuron_patch_arm", c, c ? &c->neuron_patch : nullptr, rows_host, n, lo, hi, cols_host, m, const_cast<void*>(values_bf16_dev));
+  return neuron_window_arm("aigv_neuron_patch_arm", c, c ? &c->neuron_patch : nullptr, rows_host, n, lo, hi, cols_host, m, const_cast<void*>(values_bf16_dev));
 }
 
 int aigv_neuron_scale_arm(aigv_ctx* c, const int32_t* rows_host, int n, const float* layer_scale_host, const int32_t* sel_layers_host, const int32_t* sel_cols_host,
@@ -796,15 +805,13 @@ int aigv_neuron_scale_arm(aigv_ctx* c, const int32_t* rows_host, int n, const fl
     ++begin[l + 1];
   }
   for (int l = 0; l < L; ++l) begin[l + 1] += begin[l];
+  // (its checks done, the shared helper has nothing left to refuse: it fills the base record)
+  TRY(rows_arm(op, c, &c->neuron_scale, rows_host, rows_host ? n : 0, 0, L, nullptr, true, false));
   aigv_ctx::NeuronRows& st = c->neuron_scale;
-  st.all_rows = !rows_host;
-  if (rows_host) st.rows.assign(rows_host, rows_host + n); else st.rows.clear();
   if (layer_scale_host) st.layer_scale.assign(layer_scale_host, layer_scale_host + L); else st.layer_scale.clear();
   st.dense = m == 0;
   if (m > 0) { st.cols.assign(sel_cols_host, sel_cols_host + m); st.factors.assign(sel_factors_host, sel_factors_host + m); st.sel_begin = begin; }
   else { st.cols.clear(); st.factors.clear(); st.sel_begin.clear(); }
-  st.lo = 0; st.hi = L; st.buf = nullptr;
-  st.armed = true;
   return 0;
 }
 
@@ -814,26 +821,14 @@ int aigv_neuron_scale_arm(aigv_ctx* c, const int32_t* rows_host, int n, const fl
 int aigv_llm_extend(aigv_ctx* c, const int64_t* ids, const int32_t* cu, int B, const int32_t* score_rows, float* score,
                     const int32_t* logit_rows, int R, int64_t* argmax, int commit, void* stream) {
   if (!c || !ids || !cu) return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: null argument");
-  const bool probing = c->probe.armed;
-  const bool dropping = c->drop.armed;
-  const bool lensing = c->lens.armed;
-  const bool patching = c->stream_patch.armed, capturing = c->stream_cap.armed;
-  const bool h_scaling = c->head_scale.armed, h_patching = c->head_patch.armed, h_capturing = c->head_cap.armed;
-  const bool n_scaling = c->neuron_scale.armed, n_patching = c->neuron_patch.armed, n_capturing = c->neuron_cap.armed;
-  DisarmScope disarm(c);
-  if (n_scaling || n_patching || n_capturing)
-    return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: a neuron %s is armed (%s): the continuation pass takes none, only aigv_llm_prefill does", n_scaling ? "scale" : n_patching ? "patch" : "capture",
-                n_scaling ? "aigv_neuron_scale_arm" : n_patching ? "aigv_neuron_patch_arm" : "aigv_neuron_capture_arm");
-  if (h_scaling || h_patching || h_capturing)
-    return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: a head %s is armed (%s): the continuation pass takes none, only aigv_llm_prefill does", h_scaling ? "scale" : h_patching ? "patch" : "capture",
-                h_scaling ? "aigv_head_scale_arm" : h_patching ? "aigv_head_patch_arm" : "aigv_head_capture_arm");
-  if (patching || capturing)
-    return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: a stream %s is armed (%s): the continuation pass takes none, only aigv_llm_prefill does", patching ? "patch" : "capture",
-                patching ? "aigv_stream_patch_arm" : "aigv_stream_capture_arm");
-  if (lensing) return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: the depth lens is armed (aigv_depth_lens_arm): the continuation pass takes no lens, only aigv_llm_prefill does");
-  if (dropping) return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: a key-drop mask is armed (aigv_key_drop_arm): the continuation pass takes no mask, only aigv_llm_prefill does");
+  DisarmScope disarm(c);   // (what the context is armed with stays in the records until the scope ends)
+  for (const char* family : {"neuron", "head", "stream"})
+    if (const aigv_ctx::RowOptEntry* e = first_armed(c, family))
+      return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: a %s %s is armed (%s): the continuation pass takes none, only aigv_llm_prefill does", family, e->what, e->arm);
+  if (c->lens.armed) return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: the depth lens is armed (aigv_depth_lens_arm): the continuation pass takes no lens, only aigv_llm_prefill does");
+  if (c->drop.armed) return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: a key-drop mask is armed (aigv_key_drop_arm): the continuation pass takes no mask, only aigv_llm_prefill does");
   if (!c->kv_valid) return fail(c, AIGV_ERR_STATE, "aigv_llm_extend: no KV state (run aigv_llm_prefill with keep_kv)");
-  if (probing && c->kv_masked) return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: the score-attention probe is armed and the KV cache carries a key-drop mask: the probe does not know the mask");
+  if (c->probe.armed && c->kv_masked) return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: the score-attention probe is armed and the KV cache carries a key-drop mask: the probe does not know the mask");
   const aigv_config& k = c->cfg;
   if (B != c->kv_seqs) return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: %d sequences, the cache holds %d", B, c->kv_seqs);
   if (B + 1 > AIGV_SMALL_INTS / 2) return fail(c, AIGV_ERR_ARG, "at most %d clips per call", AIGV_SMALL_INTS / 2 - 1);
@@ -859,7 +854,7 @@ int aigv_llm_extend(aigv_ctx* c, const int64_t* ids, const int32_t* cu, int B, c
   HIPCHK(c, aigv_launch_embed(ids, c->l_neg1, c->tok_emb, nullptr, nullptr, 0, c->l_h, T, H, s));
   TRY(upload_out_rows(c, score_rows, score != nullptr, B, logit_rows, R, T, s));
   ProbeArgs probe{};
-  if (probing) TRY(probe_plan(c, "aigv_llm_extend", cu, B, c->h_kvlen.data(), &probe));
+  if (c->probe.armed) TRY(probe_plan(c, "aigv_llm_extend", cu, B, c->h_kvlen.data(), &probe));
   double attn_flops = 0;
   for (int b = 0; b < B; ++b) { const double n = cu[b + 1] - cu[b]; attn_flops += 4.0 * n * (c->h_kvlen[b] + (n + 1) / 2) * D * k.llm_heads; }
   const size_t kv_layer = (size_t)k.max_seqs * nkv * k.kv_capacity * D;
@@ -869,7 +864,7 @@ int aigv_llm_extend(aigv_ctx* c, const int64_t* ids, const int32_t* cu, int B, c
     TRY(llm_layer_qkv(c, li, T, s));
     HIPCHK(c, aigv_launch_kv_store(c->l_qkv, c->qkv_out, c->l_seq, c->l_pos, c->kc + li * kv_layer, c->vc + li * kv_layer, T, nkv, g, D,
                                    k.kv_capacity, s));
-    if (probing) TRY(probe_layer(c, probe, li, true, s));   // K from the cache: the cached keys and, behind them, the rows just appended
+    if (c->probe.armed) TRY(probe_layer(c, probe, li, true, s));   // K from the cache: the cached keys and, behind them, the rows just appended
     {
       AttnArgs a = llm_attn_args(c, B);   // K / V: the cache, the new rows behind each sequence's cached keys
       a.k = c->kc + li * kv_layer; a.v = c->vc + li * kv_layer;

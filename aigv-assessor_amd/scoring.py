@@ -211,34 +211,31 @@ class ScoringPass:
             l_score, l_token, l_hidden, l_normed, l_out = lens
             native.check(lib.aigv_depth_lens_arm(ctx, native.i32_array(l_score) if l_score else None, len(l_score), native.i32_array(l_token) if l_token else None,
                                                  len(l_token), l_hidden.data_ptr(), l_normed.data_ptr(), native.ptr(l_out)), ctx)
-        for armed, arm in ((stream_patch, lib.aigv_stream_patch_arm), (stream_capture, lib.aigv_stream_capture_arm)):
-            if armed is not None:       # stream_patch / return_stream: (packed rows, lo, hi, device bf16 [n, hi - lo, H]) - armed for exactly the pass below, which disarms
-                s_rows, lo, hi, buf = armed     # (s_rows: host int32 tensor, read in place - the library copies the numbers on arming)
-                native.check(arm(ctx, C.cast(s_rows.data_ptr(), native._I32P) if s_rows.numel() else None, int(s_rows.numel()), int(lo), int(hi),
-                                 native.ptr(buf) if buf.numel() else None), ctx)
-        # head_scale / head_patch / return_heads: armed for exactly the pass below, which disarms (host arrays are read in place: the library copies them on arming)
+        # the row options - stream_patch / return_stream, head_scale / head_patch / return_heads, neuron_scale / neuron_patch / return_neurons: armed for exactly the
+        # pass below, which disarms (host arrays are read in place: the library copies them on arming)
         i32p = lambda t: C.cast(t.data_ptr(), native._I32P) if t is not None and t.numel() else None
+        f32p = lambda t: C.cast(t.data_ptr(), C.POINTER(C.c_float)) if t is not None and t.numel() else None
+
+        def arm_window(arm, opt, extra=lambda opt: ()):     # a patch or a capture: (packed rows, lo, hi, [what ``extra`` passes on,] device bf16 buffer)
+            if opt is not None:
+                rows, lo, hi, buf = *opt[:3], opt[-1]
+                native.check(arm(ctx, i32p(rows), int(rows.numel()), int(lo), int(hi), *extra(opt), native.ptr(buf) if buf.numel() else None), ctx)
+        arm_window(lib.aigv_stream_patch_arm, stream_patch)     # buffers: [n, hi - lo, H]
+        arm_window(lib.aigv_stream_capture_arm, stream_capture)
         if head_scale is not None:      # (packed rows or None: every row, host fp32 [L, n_heads])
             h_rows, table = head_scale
             native.check(lib.aigv_head_scale_arm(ctx, i32p(h_rows), 0 if h_rows is None else int(h_rows.numel()), C.cast(table.data_ptr(), C.POINTER(C.c_float))), ctx)
-        if head_patch is not None:      # (packed rows, lo, hi, one mask word per layer or None: every head, device bf16 [n, hi - lo, n_heads, D])
-            h_rows, lo, hi, bits, buf = head_patch
-            native.check(lib.aigv_head_patch_arm(ctx, i32p(h_rows), int(h_rows.numel()), int(lo), int(hi), None if bits is None else (C.c_uint64 * len(bits))(*bits),
-                                                 native.ptr(buf) if buf.numel() else None), ctx)
-        if head_capture is not None:    # (packed rows, lo, hi, device bf16 [n, hi - lo, n_heads, D])
-            h_rows, lo, hi, buf = head_capture
-            native.check(lib.aigv_head_capture_arm(ctx, i32p(h_rows), int(h_rows.numel()), int(lo), int(hi), native.ptr(buf) if buf.numel() else None), ctx)
-        # neuron_scale / neuron_patch / return_neurons: likewise (cols: host int32 [m] or None - every neuron)
-        f32p = lambda t: C.cast(t.data_ptr(), C.POINTER(C.c_float)) if t is not None and t.numel() else None
+        # buffers: [n, hi - lo, n_heads, D]; the patch: one mask word per layer or None - every head
+        arm_window(lib.aigv_head_patch_arm, head_patch, lambda opt: (None if opt[3] is None else (C.c_uint64 * len(opt[3]))(*opt[3]),))
+        arm_window(lib.aigv_head_capture_arm, head_capture)
         if neuron_scale is not None:    # (packed rows or None: every row, host fp32 [L] or None, host int32 [m] layers / columns and fp32 [m] factors or None)
             n_rows, table, sel_l, sel_c, sel_f = neuron_scale
             native.check(lib.aigv_neuron_scale_arm(ctx, i32p(n_rows), 0 if n_rows is None else int(n_rows.numel()), f32p(table), i32p(sel_l), i32p(sel_c), f32p(sel_f),
                                                    0 if sel_l is None else int(sel_l.numel())), ctx)
-        for arm, armed in ((lib.aigv_neuron_patch_arm, neuron_patch), (lib.aigv_neuron_capture_arm, neuron_capture)):
-            if armed is not None:       # (packed rows, lo, hi, cols, device bf16 [n, hi - lo, I or m])
-                n_rows, lo, hi, cols, buf = armed
-                native.check(arm(ctx, i32p(n_rows), int(n_rows.numel()), int(lo), int(hi), None if cols is None else C.cast(cols.data_ptr(), native._I32P),
-                                 0 if cols is None else int(cols.numel()), native.ptr(buf) if buf.numel() else None), ctx)
+        # buffers: [n, hi - lo, I or m]; cols: host int32 [m] or None - every neuron (an empty list is a list)
+        cols = lambda opt: (None, 0) if opt[3] is None else (C.cast(opt[3].data_ptr(), native._I32P), int(opt[3].numel()))
+        arm_window(lib.aigv_neuron_patch_arm, neuron_patch, cols)
+        arm_window(lib.aigv_neuron_capture_arm, neuron_capture, cols)
         native.check(lib.aigv_llm_prefill(
             ctx, ids_d.data_ptr(), slot_d.data_ptr(), cu_a, b, native.ptr(vis), n_vis, native.ptr(motion),
             sr_a, native.ptr(score), lr_a, len(logit_rows), amax.data_ptr(), int(keep_kv), native.stream_ptr()), ctx)
@@ -468,6 +465,21 @@ class ScoringPass:
         sel = mask & (plan["row_of"] >= 0)
         return plan["row_of"][sel].to(torch.int32).contiguous(), sel.nonzero().to(torch.long)
 
+    @staticmethod
+    def _patch_rows_check(name: str, n: int, patch, index) -> None:
+        """What the three patch planners check alike - ``name`` is the option's: the values hold one row per token the mask selects in the pass (``n``), and a
+        donor's ``index``, when given, lists exactly the pass's (clip, position) pairs (``index``).  ValueError: a count mismatch (both counts), the first
+        differing pair."""
+        if int(patch.values.shape[0]) != n:
+            raise ValueError(f"{name}: values hold {int(patch.values.shape[0])} rows, the mask selects {n} tokens the pass runs")
+        if patch.index is not None:
+            if int(patch.index.shape[0]) != n:
+                raise ValueError(f"{name}: index holds {int(patch.index.shape[0])} pairs, the mask selects {n} tokens the pass runs")
+            differ = (patch.index != index).any(1).nonzero().flatten()
+            if differ.numel():
+                i = int(differ[0])
+                raise ValueError(f"{name}: pair {i} of index is (clip, position) = {tuple(patch.index[i].tolist())}, the pass's is {tuple(index[i].tolist())}")
+
     def _stream_patch_plan(self, plan, patch):
         """``stream_patch`` checked against the plan, host work only -> None (an empty window or an empty selection: the plain pass) or (packed
         rows, lo, hi, the values as given).  ValueError: the values' shape, a count mismatch (both counts), the first differing (clip, position)."""
@@ -476,15 +488,7 @@ class ScoringPass:
         if int(v.shape[2]) != H:
             raise ValueError(f"stream_patch: values of width {int(v.shape[2])}, the residual stream has H = {H}")
         n = int(rows.numel())
-        if int(v.shape[0]) != n:
-            raise ValueError(f"stream_patch: values hold {int(v.shape[0])} rows, the mask selects {n} tokens the pass runs")
-        if patch.index is not None:
-            if int(patch.index.shape[0]) != n:
-                raise ValueError(f"stream_patch: index holds {int(patch.index.shape[0])} pairs, the mask selects {n} tokens the pass runs")
-            differ = (patch.index != index).any(1).nonzero().flatten()
-            if differ.numel():
-                i = int(differ[0])
-                raise ValueError(f"stream_patch: pair {i} of index is (clip, position) = {tuple(patch.index[i].tolist())}, the pass's is {tuple(index[i].tolist())}")
+        self._patch_rows_check("stream_patch", n, patch, index)
         return (rows, lo, hi, v) if n and hi > lo else None
 
     # ---- head knock-out and head patching (return_heads / head_patch / head_scale) ------------------------------------------------------------
@@ -497,15 +501,7 @@ class ScoringPass:
         if tuple(v.shape[2:]) != (l.num_attention_heads, l.head_dim):
             raise ValueError(f"head_patch: values of {int(v.shape[2])} heads x {int(v.shape[3])}, the model has {l.num_attention_heads} x {l.head_dim}")
         n = int(rows.numel())
-        if int(v.shape[0]) != n:
-            raise ValueError(f"head_patch: values hold {int(v.shape[0])} rows, the mask selects {n} tokens the pass runs")
-        if patch.index is not None:
-            if int(patch.index.shape[0]) != n:
-                raise ValueError(f"head_patch: index holds {int(patch.index.shape[0])} pairs, the mask selects {n} tokens the pass runs")
-            differ = (patch.index != index).any(1).nonzero().flatten()
-            if differ.numel():
-                i = int(differ[0])
-                raise ValueError(f"head_patch: pair {i} of index is (clip, position) = {tuple(patch.index[i].tolist())}, the pass's is {tuple(index[i].tolist())}")
+        self._patch_rows_check("head_patch", n, patch, index)
         bits = None if patch.heads is None else readouts.head_bits(patch.heads)
         return (rows, lo, hi, bits, v) if n and hi > lo and (bits is None or any(bits)) else None
 
@@ -515,19 +511,10 @@ class ScoringPass:
         pass) or (packed rows, lo, hi, host int32 columns or None, the values as given).  ValueError: a count mismatch (both counts), the first
         differing (clip, position)."""
         rows, index = self._stream_rows(plan, patch.rows)
-        (lo, hi), v = patch.layers, patch.values
-        n = int(rows.numel())
-        if int(v.shape[0]) != n:
-            raise ValueError(f"neuron_patch: values hold {int(v.shape[0])} rows, the mask selects {n} tokens the pass runs")
-        if patch.index is not None:
-            if int(patch.index.shape[0]) != n:
-                raise ValueError(f"neuron_patch: index holds {int(patch.index.shape[0])} pairs, the mask selects {n} tokens the pass runs")
-            differ = (patch.index != index).any(1).nonzero().flatten()
-            if differ.numel():
-                i = int(differ[0])
-                raise ValueError(f"neuron_patch: pair {i} of index is (clip, position) = {tuple(patch.index[i].tolist())}, the pass's is {tuple(index[i].tolist())}")
+        (lo, hi), n = patch.layers, int(rows.numel())
+        self._patch_rows_check("neuron_patch", n, patch, index)
         cols = None if patch.neurons is None else patch.neurons.to(torch.int32).contiguous()
-        return (rows, lo, hi, cols, v) if n and hi > lo and (cols is None or cols.numel()) else None
+        return (rows, lo, hi, cols, patch.values) if n and hi > lo and (cols is None or cols.numel()) else None
 
     def forward(self, mos: Optional[torch.Tensor] = None, pixel_values: Optional[torch.Tensor] = None,
                 input_ids: Optional[torch.Tensor] = None, attention_mask: Optional[torch.Tensor] = None,
@@ -700,43 +687,33 @@ class ScoringPass:
             raise AssertionError("img_context_token_id must be set by the caller (stage2_eval.py:810)")
         drop_words = drop_row_words = None
         n_layers = self.config.llm_config.num_hidden_layers
+        built = []
+
+        def host_plan():    # the host plan of this call, built on first use: by the first option below that is checked against it, else by the eager pass
+            if not built:
+                src = visual_tokens if visual_tokens is not None else pixel_values
+                built.append(self._plan(input_ids, attention_mask, labels, image_flags, (src.tokens if isinstance(src, VisualAhead) else src).shape[0], full_logits))
+            return built[0]
         if return_score_values and input_ids is not None and int(input_ids.shape[0]) > self.MAX_PROBE_ROWS:      # (before anything touches the device)
             raise ValueError(f"return_score_values: at most {self.MAX_PROBE_ROWS} clips per pass, got {int(input_ids.shape[0])}")
         kd_rows, kd_layers = readouts.key_drop_qualifiers(key_drop, key_drop_rows, key_drop_layers, None if input_ids is None else input_ids.shape, n_layers)
         if key_drop is not None:        # checked in full on the host before anything touches the device (a plan of its own: host work only)
             kd = readouts.key_drop_mask(key_drop, input_ids.shape, bool(return_score_attention or return_token_attention or return_score_values))
-            src = visual_tokens if visual_tokens is not None else pixel_values
-            drop_words = self._key_drop_words(self._plan(input_ids, attention_mask, labels, image_flags, (src.tokens if isinstance(src, VisualAhead) else src).shape[0],
-                                                         full_logits), kd, kd_rows)
+            drop_words = self._key_drop_words(host_plan(), kd, kd_rows)
             if kd_rows is not None:
                 drop_words, drop_row_words = drop_words
         _, _, patch = readouts.stream_options(return_stream, stream_depths, stream_patch, None if input_ids is None else input_ids.shape, n_layers)
-        patch_plan = patched = None
-        if patch is not None:           # likewise: counts and pairs against the plan (host work only; the eager pass below, which such a call takes, reuses it)
-            src = visual_tokens if visual_tokens is not None else pixel_values
-            patch_plan = self._plan(input_ids, attention_mask, labels, image_flags, (src.tokens if isinstance(src, VisualAhead) else src).shape[0], full_logits)
-            patched = self._stream_patch_plan(patch_plan, patch)
+        # likewise: counts and pairs against the plan (host work only; the eager pass below, which such a call takes, reuses it)
+        patched = None if patch is None else self._stream_patch_plan(host_plan(), patch)
         llm = self.config.llm_config
         _, _, h_patch, h_scale = readouts.head_options(return_heads, head_layers, head_patch, head_scale, None if input_ids is None else input_ids.shape, n_layers,
                                                        llm.num_attention_heads, llm.head_dim)
-        h_patched = None
-        if h_patch is not None:         # likewise
-            if patch_plan is None:
-                src = visual_tokens if visual_tokens is not None else pixel_values
-                patch_plan = self._plan(input_ids, attention_mask, labels, image_flags, (src.tokens if isinstance(src, VisualAhead) else src).shape[0], full_logits)
-            h_patched = self._head_patch_plan(patch_plan, h_patch)
+        h_patched = None if h_patch is None else self._head_patch_plan(host_plan(), h_patch)
         _, _, _, n_patch, _ = readouts.neuron_options(return_neurons, neuron_layers, neuron_ids, neuron_patch, neuron_scale, None if input_ids is None else input_ids.shape,
                                                       n_layers, llm.intermediate_size)
-        n_patched = None
-        if n_patch is not None:         # likewise
-            if patch_plan is None:
-                src = visual_tokens if visual_tokens is not None else pixel_values
-                patch_plan = self._plan(input_ids, attention_mask, labels, image_flags, (src.tokens if isinstance(src, VisualAhead) else src).shape[0], full_logits)
-            n_patched = self._neuron_patch_plan(patch_plan, n_patch)
+        n_patched = None if n_patch is None else self._neuron_patch_plan(host_plan(), n_patch)
         if return_depth_lens and self._capture_keep is None:      # likewise: is there a row to read?  (inside a capture the call that led here has checked)
-            src = visual_tokens if visual_tokens is not None else pixel_values
-            self._depth_lens_rows(self._plan(input_ids, attention_mask, labels, image_flags, (src.tokens if isinstance(src, VisualAhead) else src).shape[0], full_logits),
-                                  labels is not None)
+            self._depth_lens_rows(host_plan(), labels is not None)
         pixel_values, visual_tokens, motion_feature = self._take_ahead(pixel_values, visual_tokens, motion_feature)
         parse = lambda: readouts.ReadOuts.parse(self.config.llm_config.vocab_size, labels, return_logprobs, candidate_ids, top_logprobs,
                                                 return_score_attention, attention_segments, return_token_attention, key_drop,
@@ -757,7 +734,7 @@ class ScoringPass:
         n_frames = visual_tokens.shape[0] if visual_tokens is not None else pixel_values.shape[0]
         # ---- index bookkeeping first, on the host (one small D2H copy if the ids live on the device), so that
         # every kernel of the step can then be enqueued back to back without a host sync in between ----
-        plan = patch_plan if patch_plan is not None else self._plan(input_ids, attention_mask, labels, image_flags, n_frames, full_logits)
+        plan = host_plan()
         ro = ro or parse()      # (once per call; on the eager path behind the plan's own checks, where the options have always been checked)
         lp_labels = self._logprob_labels(plan) if ro.wants_labels else None
         lens_rows = self._depth_lens_rows(plan, labels is not None) if ro.depth_lens else None
@@ -768,59 +745,46 @@ class ScoringPass:
         vit_embeds, motion = self._visual_inputs(pixel_values, visual_tokens, motion_feature, plan)
         probe = self._score_attention_probe(plan, input_ids, ro) if ro.score_attention else None
         lens = None if lens_rows is None else self._depth_lens_buffers(lens_rows[0], lens_rows[2])
-        capture = stream_index = None
-        if ro.stream_rows is not None:          # return_stream: the buffer the pass fills, [n, hi - lo, H]
-            cap_rows, stream_index = self._stream_rows(plan, ro.stream_rows)
-            lo, hi = ro.stream_depths
-            capture = (cap_rows, lo, hi, torch.empty((int(cap_rows.numel()), hi - lo, self.config.llm_config.hidden_size), dtype=torch.bfloat16, device=self.device))
-        if patched is not None:             # stream_patch, checked against this very plan on the way in: the values go up (or stay) on the device
-            patched = patched[:3] + (self._h2d(patched[3].detach().contiguous()),)
-        h_capture = heads_index = h_scaled = None
-        if ro.head_rows is not None:            # return_heads: the buffer the pass fills, [n, hi - lo, n_heads, D]
-            cap_rows, heads_index = self._stream_rows(plan, ro.head_rows)
-            lo, hi = ro.head_layers
-            h_capture = (cap_rows, lo, hi, torch.empty((int(cap_rows.numel()), hi - lo, llm.num_attention_heads, llm.head_dim), dtype=torch.bfloat16, device=self.device))
-        if h_patched is not None:
-            h_patched = h_patched[:4] + (self._h2d(h_patched[4].detach().contiguous()),)
+        def capture_of(mask, window, *width):   # a capture's (packed rows, lo, hi, the bf16 buffer the pass fills [n, hi - lo, *width]) and its (clip, position) index
+            rows, index = self._stream_rows(plan, mask)
+            return (rows, *window, torch.empty((int(rows.numel()), window[1] - window[0], *width), dtype=torch.bfloat16, device=self.device)), index
+        to_device = lambda p: p and p[:-1] + (self._h2d(p[-1].detach().contiguous()),)   # a patch, checked against this very plan on the way in: its values go up (or stay) on the device
+        capture, stream_index = capture_of(ro.stream_rows, ro.stream_depths, llm.hidden_size) if ro.stream_rows is not None else (None, None)      # return_stream
+        patched = to_device(patched)
+        h_capture, heads_index = capture_of(ro.head_rows, ro.head_layers, llm.num_attention_heads, llm.head_dim) if ro.head_rows is not None else (None, None)     # return_heads
+        h_patched, h_scaled = to_device(h_patched), None
         if ro.head_scale is not None and bool((ro.head_scale.scale != 1).any()):      # (a table of ones: the plain pass)
             s_rows = None if ro.head_scale.rows is None else self._stream_rows(plan, ro.head_scale.rows)[0]
             if s_rows is None or s_rows.numel():
                 h_scaled = (s_rows, ro.head_scale.scale)
         n_capture = neurons_index = n_scaled = None
-        if ro.neuron_rows is not None:          # return_neurons: the buffer the pass fills, [n, hi - lo, I or m]
-            cap_rows, neurons_index = self._stream_rows(plan, ro.neuron_rows)
-            lo, hi = ro.neuron_layers
+        if ro.neuron_rows is not None:          # return_neurons: [n, hi - lo, I or m]
             cols = None if ro.neuron_ids is None else ro.neuron_ids.to(torch.int32).contiguous()
-            buf = torch.empty((int(cap_rows.numel()), hi - lo, llm.intermediate_size if cols is None else int(cols.numel())), dtype=torch.bfloat16, device=self.device)
+            (cap_rows, lo, hi, buf), neurons_index = capture_of(ro.neuron_rows, ro.neuron_layers, llm.intermediate_size if cols is None else int(cols.numel()))
             if lo < hi == llm.num_hidden_layers and buf.numel():
                 buf[:, -1].fill_(float("nan"))      # a selected row the row-trimmed last layer does not consume has no activation there: no launch writes its slice
             n_capture = (cap_rows, lo, hi, cols, buf)
-        if n_patched is not None:
-            n_patched = n_patched[:4] + (self._h2d(n_patched[4].detach().contiguous()),)
+        n_patched = to_device(n_patched)
         if ro.neuron_scale is not None and bool((ro.neuron_scale.scale != 1).any()):      # (factors of one: the plain pass)
             q = ro.neuron_scale
             s_rows = None if q.rows is None else self._stream_rows(plan, q.rows)[0]
             if s_rows is None or s_rows.numel():
                 n_scaled = ((s_rows, q.scale, None, None, None) if q.neurons is None else
                             (s_rows, None, q.neurons[:, 0].to(torch.int32).contiguous(), q.neurons[:, 1].to(torch.int32).contiguous(), q.scale))
+        live = lambda cap: cap if cap is not None and cap[-1].numel() else None     # (an empty capture arms nothing: its empty buffer is the result)
         score, amax, *armed = self._prefill(plan["ids_packed"], plan["slot"], plan["cu"], vit_embeds, plan["n_vis"], motion,
                                             plan["score_rows"], plan["logit_rows"], probe=probe, ld_tok=N if ro.token_attention else 0, values=ro.score_values,
                                             drop_words=drop_words, drop_row_words=drop_row_words, drop_layers=kd_layers, lens=lens,
-                                            stream_capture=capture if capture is not None and capture[3].numel() else None, stream_patch=patched,
-                                            head_capture=h_capture if h_capture is not None and h_capture[3].numel() else None, head_patch=h_patched,
-                                            head_scale=h_scaled, neuron_capture=n_capture if n_capture is not None and n_capture[4].numel() else None,
-                                            neuron_patch=n_patched, neuron_scale=n_scaled)
+                                            stream_capture=live(capture), stream_patch=patched, head_capture=live(h_capture), head_patch=h_patched,
+                                            head_scale=h_scaled, neuron_capture=live(n_capture), neuron_patch=n_patched, neuron_scale=n_scaled)
         att, tok, *val = armed or (None, None)  # (_prefill hands the probe's tensors back only when it armed one)
         reads = self._read_rows(B if score is not None else 0, len(plan["logit_rows"]), ro, lp_labels)
         out = self._outputs(plan, B, N, score, amax, mos, reads, att, tok, *val)
         if lens is not None:
             out.update(self._depth_lens_outputs(B, lens, lens_rows[1], ro, labels is not None))
-        if capture is not None:
-            out.update(stream=capture[3], stream_index=self._h2d(stream_index))
-        if h_capture is not None:
-            out.update(heads=h_capture[3], heads_index=self._h2d(heads_index))
-        if n_capture is not None:
-            out.update(neurons=n_capture[4], neurons_index=self._h2d(neurons_index))
+        for name, cap, index in (("stream", capture, stream_index), ("heads", h_capture, heads_index), ("neurons", n_capture, neurons_index)):
+            if cap is not None:
+                out.update({name: cap[-1], name + "_index": self._h2d(index)})
         return out
 
     def dp_front(self, frames_local: torch.Tensor, frames_clips: Optional[torch.Tensor], n_clips: int):

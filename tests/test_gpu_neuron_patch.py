@@ -539,6 +539,85 @@ def test_a_stream_capture_and_a_head_capture_behind_the_layer_see_the_modified_p
     assert same(out["heads"][clip == 0, 1], base["heads"][clip == 0, 1]) and not same(out["heads"][clip == 1, 1], base["heads"][clip == 1, 1])
 
 
+ROW_KEYS = ("stream", "stream_index", "heads", "heads_index") + NEURON_KEYS
+ALL_EIGHT = ("stream_patch", "stream_capture", "head_scale", "head_patch", "head_capture", "neuron_scale", "neuron_patch", "neuron_capture")
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_score_with_layer_2_mlp_negated():
+    """KNOCKOUTS[3] - layer 2's MLP x -1, exactly representable, 6 bf16 ulps off the oracle's plain score (tests/test_neuron_patch_cpu.py) - on clip 0
+    alone: (the product's option, the composed oracle's score [1])."""
+    model, cfg, sd, kw, seg, plain, whole, nwhole, consumed = neurons_rig()
+    one, inputs, own, _ = oracle_clip0()
+    options = knockout_options(KNOCKOUTS[3], oracle_score_row_capture())
+    states, _ = NP.composed_states(sd, cfg, **inputs, **options)
+    return neuron_scale_of(options), NP.lens(sd, cfg, states, one["attention_mask"], one["labels"], 2)["score"][:, LAYERS]
+
+
+@pytest.mark.parametrize("form", ["trimmed", "mixed", "full_logits"])
+def test_all_eight_row_options_armed_in_one_pass(form):
+    """Stream, head and neuron patch, capture and scale - and the lens - in ONE pass, over the three forms of the last layer: trimmed (11 consumed rows
+    per clip), mixed (clip 1 with 12 more answer rows: 23 > 16, its rows finish on the tile kernels, clip 0's on the streaming path), every row
+    (full_logits).  Five rows per clip: the first token, a token of each frame, the score row, the last answer row.  Pass one captures them over the
+    full windows.  Pass two patches every capture back in - three self-patches - beside the three captures and both scales, all factors 1: every
+    output is the plain pass's and every capture pass one's, bit for bit.  forward() arms no scale whose factors are all 1, so the unit tables are
+    handed to _prefill itself: the pass then runs with all eight armed, which _prefill's arguments show.  Pass three: one factor off 1 - layer 2's MLP
+    x -1 (no inverse anywhere) - with the patches cut to the windows in front of it (behind it they would put the plain pass back); clip 0's score
+    against the composed oracle's under score_ok's bar, the captures in front of the factor pass one's bits, the neurons of layer 2 their negation."""
+    model, cfg, sd, kw, seg, plain, whole, nwhole, consumed = neurons_rig()
+    kw, extra = dict(kw), {}
+    if form == "mixed":
+        free = (seg["text_after"][1] & (kw["labels"][1] == -100)).nonzero().flatten()[1:13]      # (a label at p makes p - 1 a consumed row)
+        kw["labels"] = kw["labels"].clone()
+        kw["labels"][1, free] = kw["input_ids"][1, free]
+        plan = model._plan(kw["input_ids"], kw["attention_mask"], kw["labels"], kw["image_flags"], 4)
+        per_clip = [sum(plan["cu"][b] <= int(r) < plan["cu"][b + 1] for r in list(plan["score_rows"]) + list(plan["logit_rows"])) for b in range(2)]
+        assert per_clip == [11, 23], per_clip
+    if form == "full_logits":
+        extra["full_logits"] = True
+    base = plain if form == "trimmed" else model(**kw, **READS, **extra)
+    mask = seg["score_row"].clone()
+    mask[:, [0, 70, 130, 213]] = True
+    every = dict(return_stream=mask, return_heads=mask, return_neurons=mask)
+    first = model(**kw, **READS, **every, **extra)
+    assert first["stream_index"].tolist() == [[b, p] for b in range(2) for p in (0, 70, 130, 211, 213)]
+    assert_same_outputs(first, base, skip=ROW_KEYS)
+
+    def patches(d_stream, d_head, d_neuron):      # pass one's captures cut to the windows [0, d)
+        cut = lambda key, d: first[key][:, :d].contiguous()
+        return dict(stream_patch=StreamPatch(mask, cut("stream", d_stream), (0, d_stream), first["stream_index"]),
+                    head_patch=HeadPatch(mask, cut("heads", d_head), (0, d_head), first["heads_index"]),
+                    neuron_patch=NeuronPatch(mask, cut("neurons", d_neuron), (0, d_neuron), first["neurons_index"]))
+
+    seen = []
+    keep = model._prefill
+
+    def prefill_with_unit_scales(*a, **k):
+        if k.get("head_scale") is None:
+            k["head_scale"] = (None, torch.ones(LAYERS, HEADS))
+        if k.get("neuron_scale") is None:
+            k["neuron_scale"] = (None, torch.ones(LAYERS), None, None, None)
+        seen.append([name for name in ALL_EIGHT if k.get(name) is not None] + (["lens"] if k.get("lens") is not None else []))
+        return keep(*a, **k)
+
+    model._prefill = prefill_with_unit_scales
+    try:
+        second = model(**kw, **READS, **every, **patches(LAYERS, LAYERS, LAYERS), **extra)
+        scale, want = oracle_score_with_layer_2_mlp_negated()
+        third = model(**kw, **READS, **every, **patches(3, 3, 2), neuron_scale=scale, **extra)
+    finally:
+        del model._prefill
+    assert seen == [list(ALL_EIGHT) + ["lens"]] * 2, seen
+    assert_same_outputs(second, base, skip=ROW_KEYS)
+    for key in ROW_KEYS:
+        assert same(second[key], first[key]), key
+    score_ok(third["score1"][0:1], want)
+    assert not same(third["score1"], base["score1"])
+    assert same(third["stream"][:, :3], first["stream"][:, :3]) and same(third["heads"][:, :3], first["heads"][:, :3]) and same(third["neurons"][:, :2], first["neurons"][:, :2])
+    assert same(third["neurons"][:, 2], (-first["neurons"][:, 2].float()).to(BF)) and not same(third["stream"][:, 3], first["stream"][:, 3])
+    assert_same_outputs(model(**kw, **READS, **extra), base)                                  # every option disarmed with its pass
+
+
 def test_fp8_mode_self_patch_is_bit_neutral():
     model, cfg, sd, kw, seg, plain, whole, nwhole, consumed = neurons_rig()
     model.set_precision("fp8")
