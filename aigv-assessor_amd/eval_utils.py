@@ -246,6 +246,59 @@ def settling_depth(lens_score, tol: float):
     return (L + 1 - settled.sum(1)).to(torch.long)
 
 
+# ---- what the sweeps below share -----------------------------------------------------------------------------------------------------
+def _once_per_batch(model, pixel_values, readout_kwargs, **inputs):
+    """InternViT and the SlowFast branch run ONCE for a sweep -> the keyword arguments every pass of it shares: ``inputs`` (``input_ids`` among
+    them), ``visual_tokens``, ``motion_feature`` (the one in ``readout_kwargs``, else computed here) and the other ``readout_kwargs``."""
+    readout_kwargs = dict(readout_kwargs)
+    motion_feature = readout_kwargs.pop("motion_feature", None)
+    if motion_feature is None:
+        motion_feature = model.motion_feature(pixel_values, int(inputs["input_ids"].shape[0]))
+    return dict(inputs, visual_tokens=model.vit_tokens(pixel_values), motion_feature=motion_feature, **readout_kwargs)
+
+
+def _recipient(model, corrupt, B, readout_kwargs):
+    """The ``corrupt`` dict of a donor / recipient sweep as the keyword arguments every pass of the recipient shares: its SlowFast feature and its
+    InternViT tokens computed ONCE, no ``pixel_values``, ``readout_kwargs`` on top."""
+    common = {k: v for k, v in corrupt.items() if k != "pixel_values"}
+    if common.get("motion_feature") is None:
+        common["motion_feature"] = model.motion_feature(corrupt["pixel_values"], B)
+    common.update(visual_tokens=model.vit_tokens(corrupt["pixel_values"]), **readout_kwargs)
+    return common
+
+
+def _windows(where, L, width, stride):
+    """The layer windows of a sweep: ``(lo, min(lo + width, L))`` for lo = 0, stride, 2 stride, ... < L; ``stride`` None: ``width``."""
+    width = int(width)
+    stride = width if stride is None else int(stride)
+    if not 1 <= width <= L or stride < 1:
+        raise ValueError(f"{where}: width = {width} outside 1..{L} or stride = {stride} below 1")
+    return [(lo, min(lo + width, L)) for lo in range(0, L, stride)]
+
+
+def _knocked(res, outs, B, shape, absent):
+    """``score1`` / ``knocked`` [B, *shape] / ``delta`` of a knock-out sweep whose passes behind the base one are ``outs[1:]``.  ``absent``: None, or
+    bool [B] or [B, shape[0]] - where the clip has nothing to knock out (no selected row; in ``flow_knockout``, per path, no key or no row): NaN."""
+    import torch
+    if "score1" in outs[0]:
+        base = outs[0]["score1"].float()
+        knocked = torch.stack([o["score1"].float() for o in outs[1:]], 1).view(B, *shape) if len(outs) > 1 else base.new_zeros(B, *shape)
+        if absent is not None:
+            knocked = knocked.masked_fill(absent.view(*absent.shape, *([1] * (1 + len(shape) - absent.dim()))).to(knocked.device), float("nan"))
+        res.update(score1=base, knocked=knocked, delta=base.view(B, *([1] * len(shape))) - knocked)
+    return res
+
+
+def _restored(res, outs, B, shape):
+    """``clean_score`` / ``corrupt_score`` / ``score`` [B, *shape] / ``restored`` of a donor / recipient sweep whose patched passes are ``outs[2:]``."""
+    import torch
+    if "score1" in outs[0]:
+        clean_score, corrupt_score = outs[0]["score1"].float(), outs[1]["score1"].float()
+        score = torch.stack([o["score1"].float() for o in outs[2:]], 1).view(B, *shape) if len(outs) > 2 else clean_score.new_zeros(B, *shape)
+        res.update(score=score, clean_score=clean_score, corrupt_score=corrupt_score, restored=restored_fraction(score, clean_score, corrupt_score))
+    return res
+
+
 def frame_ablation(model, *, pixel_values, input_ids, attention_mask, image_flags, labels=None, motion_feature=None, **readout_kwargs):
     """WHAT IF a frame were not there: the batch scored once as it is and once per unit with that unit's tokens hidden from the LLM
     (``forward(key_drop=model.unit_masks(...)[:, u])``) - unit u < F is frame u's visual tokens, unit F the motion token.  Positions, the
@@ -256,13 +309,9 @@ def frame_ablation(model, *, pixel_values, input_ids, attention_mask, image_flag
     and for a stage-2 model ``score1`` [B] (the base scores, fp32), ``ablated`` [B, F + 1] (the score with the unit hidden; NaN where the
     clip lacks the frame) and ``delta`` = ``score1[:, None] - ablated``: positive where the unit raised the score."""
     import torch
-    B = int(input_ids.shape[0])
     units = model.unit_masks(input_ids, attention_mask, image_flags, n_frames=int(pixel_values.shape[0]))      # host bool [B, F + 1, N]
-    if motion_feature is None:
-        motion_feature = model.motion_feature(pixel_values, B)
-    tokens = model.vit_tokens(pixel_values)
-    common = dict(input_ids=input_ids, attention_mask=attention_mask, image_flags=image_flags, labels=labels, visual_tokens=tokens,
-                  motion_feature=motion_feature, **readout_kwargs)
+    common = _once_per_batch(model, pixel_values, dict(readout_kwargs, motion_feature=motion_feature), input_ids=input_ids, attention_mask=attention_mask,
+                             image_flags=image_flags, labels=labels)
     outs = [model.forward(**common)] + [model.forward(key_drop=units[:, u], **common) for u in range(units.shape[1])]
     res = {"outs": outs, "units": units}
     if "score1" in outs[0]:
@@ -289,36 +338,19 @@ def flow_knockout(model, *, pixel_values, input_ids, attention_mask, image_flags
     ``score1[:, None, None] - knocked``: positive where the path, in that window, raised the score."""
     import torch
     B = int(input_ids.shape[0])
-    L = int(model.config.llm_config.num_hidden_layers)
-    width = int(width)
-    stride = width if stride is None else int(stride)
-    if not 1 <= width <= L or stride < 1:
-        raise ValueError(f"flow_knockout: width = {width} outside 1..{L} or stride = {stride} below 1")
-    windows = [(lo, min(lo + width, L)) for lo in range(0, L, stride)]
+    windows = _windows("flow_knockout", int(model.config.llm_config.num_hidden_layers), width, stride)
     if paths is None:
         seg = model.segment_masks(input_ids, attention_mask, image_flags, n_frames=int(pixel_values.shape[0]))
         paths = [("frames->score_row", seg["frames"], seg["score_row"]), ("frames->text_after", seg["frames"], seg["text_after"]),
                  ("text_after->score_row", seg["text_after"] & ~seg["score_row"], seg["score_row"])]
     paths = [(str(name), keys.detach().to("cpu").bool(), None if rows is None else rows.detach().to("cpu").bool()) for name, keys, rows in paths]
-    readout_kwargs = dict(readout_kwargs)
-    motion_feature = readout_kwargs.pop("motion_feature", None)
-    if motion_feature is None:
-        motion_feature = model.motion_feature(pixel_values, B)
-    tokens = model.vit_tokens(pixel_values)
-    common = dict(input_ids=input_ids, attention_mask=attention_mask, image_flags=image_flags, labels=labels, visual_tokens=tokens,
-                  motion_feature=motion_feature, **readout_kwargs)
+    common = _once_per_batch(model, pixel_values, readout_kwargs, input_ids=input_ids, attention_mask=attention_mask, image_flags=image_flags, labels=labels)
     outs = [model.forward(**common)]
     for name, keys, rows in paths:
         for w in windows:
             outs.append(model.forward(key_drop=keys, key_drop_rows=rows, key_drop_layers=w, **common))
-    res = {"outs": outs, "paths": paths, "windows": windows}
-    if "score1" in outs[0]:
-        base = outs[0]["score1"].float()
-        knocked = torch.stack([o["score1"].float() for o in outs[1:]], 1).view(B, len(paths), len(windows))
-        absent = torch.stack([~keys.any(-1) | (torch.zeros(B, dtype=torch.bool) if rows is None else ~rows.any(-1)) for _, keys, rows in paths], 1)   # [B, P]
-        knocked = knocked.masked_fill(absent[:, :, None].to(knocked.device), float("nan"))
-        res.update(score1=base, knocked=knocked, delta=base[:, None, None] - knocked)
-    return res
+    absent = [~keys.any(-1) | (torch.zeros(B, dtype=torch.bool) if rows is None else ~rows.any(-1)) for _, keys, rows in paths]      # per path: keys or rows missing
+    return _knocked({"outs": outs, "paths": paths, "windows": windows}, outs, B, (len(paths), len(windows)), torch.stack(absent, 1) if paths else None)
 
 
 def restored_fraction(score, clean_score, corrupt_score):
@@ -374,11 +406,7 @@ def causal_trace(model, *, clean, corrupt, groups=None, width=1, stride=1, **rea
     from .readouts import StreamPatch
     B, N = _same_layout("causal_trace", model, clean, corrupt)
     ids, am = clean["input_ids"], clean.get("attention_mask")
-    L = int(model.config.llm_config.num_hidden_layers)
-    width, stride = int(width), int(stride)
-    if not 1 <= width <= L or stride < 1:
-        raise ValueError(f"causal_trace: width = {width} outside 1..{L} or stride = {stride} below 1")
-    windows = [(lo, min(lo + width, L)) for lo in range(0, L, stride)]
+    windows = _windows("causal_trace", int(model.config.llm_config.num_hidden_layers), width, stride)
     n_frames = int(clean["pixel_values"].shape[0])
     if groups is None:
         units = model.unit_masks(ids, am, clean["image_flags"], n_frames=n_frames)
@@ -395,11 +423,7 @@ def causal_trace(model, *, clean, corrupt, groups=None, width=1, stride=1, **rea
         union |= mask
     donor = model.forward(**clean, return_stream=union, **readout_kwargs)                      # all depths: [n, L, H]
     index = donor["stream_index"].cpu()
-    pixel_values = corrupt["pixel_values"]
-    common = {k: v for k, v in corrupt.items() if k != "pixel_values"}
-    if common.get("motion_feature") is None:
-        common["motion_feature"] = model.motion_feature(pixel_values, B)
-    common.update(visual_tokens=model.vit_tokens(pixel_values), **readout_kwargs)
+    common = _recipient(model, corrupt, B, readout_kwargs)
     outs = [donor, model.forward(**common)]
     for name, mask in groups:
         own = mask[index[:, 0], index[:, 1]]                                                   # the union's rows that belong to this group
@@ -407,12 +431,7 @@ def causal_trace(model, *, clean, corrupt, groups=None, width=1, stride=1, **rea
         rows = donor["stream"].index_select(0, at)
         for lo, hi in windows:
             outs.append(model.forward(stream_patch=StreamPatch(mask, rows[:, lo:hi].contiguous(), (lo, hi), index[own]), **common))
-    res = {"outs": outs, "names": [name for name, _ in groups], "groups": groups, "windows": windows}
-    if "score1" in outs[0]:
-        clean_score, corrupt_score = outs[0]["score1"].float(), outs[1]["score1"].float()
-        score = torch.stack([o["score1"].float() for o in outs[2:]], 1).view(B, len(groups), len(windows)) if groups else clean_score.new_zeros(B, 0, len(windows))
-        res.update(score=score, clean_score=clean_score, corrupt_score=corrupt_score, restored=restored_fraction(score, clean_score, corrupt_score))
-    return res
+    return _restored({"outs": outs, "names": [name for name, _ in groups], "groups": groups, "windows": windows}, outs, B, (len(groups), len(windows)))
 
 
 def _head_grid(where, model, layers, heads):
@@ -440,27 +459,14 @@ def head_knockout(model, *, pixel_values, input_ids, attention_mask, image_flags
     B = int(input_ids.shape[0])
     L, nh, layers, heads = _head_grid("head_knockout", model, layers, heads)
     rows = None if rows is None else rows.detach().to("cpu").bool()
-    readout_kwargs = dict(readout_kwargs)
-    motion_feature = readout_kwargs.pop("motion_feature", None)
-    if motion_feature is None:
-        motion_feature = model.motion_feature(pixel_values, B)
-    tokens = model.vit_tokens(pixel_values)
-    common = dict(input_ids=input_ids, attention_mask=attention_mask, image_flags=image_flags, labels=labels, visual_tokens=tokens,
-                  motion_feature=motion_feature, **readout_kwargs)
+    common = _once_per_batch(model, pixel_values, readout_kwargs, input_ids=input_ids, attention_mask=attention_mask, image_flags=image_flags, labels=labels)
     outs = [model.forward(**common)]
     for l in layers:
         for h in heads:
             scale = torch.ones(L, nh)
             scale[l, h] = 0.0
             outs.append(model.forward(head_scale=HeadScale(scale, rows), **common))
-    res = {"outs": outs, "layers": layers, "heads": heads}
-    if "score1" in outs[0]:
-        base = outs[0]["score1"].float()
-        knocked = torch.stack([o["score1"].float() for o in outs[1:]], 1).view(B, len(layers), len(heads)) if len(outs) > 1 else base.new_zeros(B, len(layers), len(heads))
-        if rows is not None:
-            knocked = knocked.masked_fill((~rows.any(-1))[:, None, None].to(knocked.device), float("nan"))
-        res.update(score1=base, knocked=knocked, delta=base[:, None, None] - knocked)
-    return res
+    return _knocked({"outs": outs, "layers": layers, "heads": heads}, outs, B, (len(layers), len(heads)), None if rows is None else ~rows.any(-1))
 
 
 def head_trace(model, *, clean, corrupt, layers=None, heads=None, rows=None, **readout_kwargs):
@@ -483,11 +489,7 @@ def head_trace(model, *, clean, corrupt, layers=None, heads=None, rows=None, **r
         raise ValueError(f"head_trace: rows has shape {tuple(rows.shape)}, input_ids {(B, N)}")
     donor = model.forward(**clean, return_heads=rows, **readout_kwargs)                        # all layers: [n, L, n_heads, D]
     index = donor["heads_index"].cpu()
-    pixel_values = corrupt["pixel_values"]
-    common = {k: v for k, v in corrupt.items() if k != "pixel_values"}
-    if common.get("motion_feature") is None:
-        common["motion_feature"] = model.motion_feature(pixel_values, B)
-    common.update(visual_tokens=model.vit_tokens(pixel_values), **readout_kwargs)
+    common = _recipient(model, corrupt, B, readout_kwargs)
     outs = [donor, model.forward(**common)]
     for l in layers:
         values = donor["heads"][:, l:l + 1].contiguous()
@@ -495,33 +497,7 @@ def head_trace(model, *, clean, corrupt, layers=None, heads=None, rows=None, **r
             only = torch.zeros(nh, dtype=torch.bool)
             only[h] = True
             outs.append(model.forward(head_patch=HeadPatch(rows, values, (l, l + 1), index, only), **common))
-    res = {"outs": outs, "layers": layers, "heads": heads}
-    if "score1" in outs[0]:
-        clean_score, corrupt_score = outs[0]["score1"].float(), outs[1]["score1"].float()
-        score = torch.stack([o["score1"].float() for o in outs[2:]], 1).view(B, len(layers), len(heads)) if len(outs) > 2 else clean_score.new_zeros(B, len(layers), len(heads))
-        res.update(score=score, clean_score=clean_score, corrupt_score=corrupt_score, restored=restored_fraction(score, clean_score, corrupt_score))
-    return res
-
-
-def _once_per_batch(model, pixel_values, B, readout_kwargs):
-    """InternViT and the SlowFast branch run ONCE for a sweep: -> (``visual_tokens``, ``motion_feature``, the other keyword arguments)."""
-    readout_kwargs = dict(readout_kwargs)
-    motion_feature = readout_kwargs.pop("motion_feature", None)
-    if motion_feature is None:
-        motion_feature = model.motion_feature(pixel_values, B)
-    return model.vit_tokens(pixel_values), motion_feature, readout_kwargs
-
-
-def _knocked(res, outs, B, shape, rows):
-    """``score1`` / ``knocked`` / ``delta`` of a knock-out sweep whose passes behind the base one are ``outs[1:]`` (``head_knockout``'s convention)."""
-    import torch
-    if "score1" in outs[0]:
-        base = outs[0]["score1"].float()
-        knocked = torch.stack([o["score1"].float() for o in outs[1:]], 1).view(B, *shape) if len(outs) > 1 else base.new_zeros(B, *shape)
-        if rows is not None:
-            knocked = knocked.masked_fill((~rows.any(-1)).view(B, *([1] * len(shape))).to(knocked.device), float("nan"))
-        res.update(score1=base, knocked=knocked, delta=base.view(B, *([1] * len(shape))) - knocked)
-    return res
+    return _restored({"outs": outs, "layers": layers, "heads": heads}, outs, B, (len(layers), len(heads)))
 
 
 def mlp_knockout(model, *, pixel_values, input_ids, attention_mask, image_flags, labels=None, layers=None, rows=None, **readout_kwargs):
@@ -542,15 +518,13 @@ def mlp_knockout(model, *, pixel_values, input_ids, attention_mask, image_flags,
     if any(not 0 <= l < L for l in layers):
         raise ValueError(f"mlp_knockout: layers {layers} outside 0..{L - 1}")
     rows = None if rows is None else rows.detach().to("cpu").bool()
-    tokens, motion_feature, readout_kwargs = _once_per_batch(model, pixel_values, B, readout_kwargs)
-    common = dict(input_ids=input_ids, attention_mask=attention_mask, image_flags=image_flags, labels=labels, visual_tokens=tokens,
-                  motion_feature=motion_feature, **readout_kwargs)
+    common = _once_per_batch(model, pixel_values, readout_kwargs, input_ids=input_ids, attention_mask=attention_mask, image_flags=image_flags, labels=labels)
     outs = [model.forward(**common)]
     for l in layers:
         scale = torch.ones(L)
         scale[l] = 0.0
         outs.append(model.forward(neuron_scale=NeuronScale(scale, None, rows), **common))
-    return _knocked({"outs": outs, "layers": layers}, outs, B, (len(layers),), rows)
+    return _knocked({"outs": outs, "layers": layers}, outs, B, (len(layers),), None if rows is None else ~rows.any(-1))
 
 
 def neuron_knockout(model, neurons, *, pixel_values, input_ids, attention_mask, image_flags, labels=None, rows=None, **readout_kwargs):
@@ -571,13 +545,11 @@ def neuron_knockout(model, neurons, *, pixel_values, input_ids, attention_mask, 
     if neurons.numel() and (int(neurons.min()) < 0 or int(neurons[:, 0].max()) >= l.num_hidden_layers or int(neurons[:, 1].max()) >= l.intermediate_size):
         raise ValueError(f"neuron_knockout: a (layer, neuron) pair outside layers 0..{l.num_hidden_layers - 1}, neurons 0..{l.intermediate_size - 1}")
     rows = None if rows is None else rows.detach().to("cpu").bool()
-    tokens, motion_feature, readout_kwargs = _once_per_batch(model, pixel_values, B, readout_kwargs)
-    common = dict(input_ids=input_ids, attention_mask=attention_mask, image_flags=image_flags, labels=labels, visual_tokens=tokens,
-                  motion_feature=motion_feature, **readout_kwargs)
+    common = _once_per_batch(model, pixel_values, readout_kwargs, input_ids=input_ids, attention_mask=attention_mask, image_flags=image_flags, labels=labels)
     outs = [model.forward(**common)]
     for pair in neurons:
         outs.append(model.forward(neuron_scale=NeuronScale(torch.zeros(1), pair[None], rows), **common))
-    return _knocked({"outs": outs, "neurons": neurons}, outs, B, (int(neurons.shape[0]),), rows)
+    return _knocked({"outs": outs, "neurons": neurons}, outs, B, (int(neurons.shape[0]),), None if rows is None else ~rows.any(-1))
 
 
 def rank_neurons(clean, corrupt, top: int):
@@ -615,11 +587,7 @@ def neuron_trace(model, *, clean, corrupt, layers=None, top: int = 16, rows=None
         raise ValueError(f"neuron_trace: rows has shape {tuple(rows.shape)}, input_ids {(B, N)}")
     donor = model.forward(**clean, return_neurons=rows, neuron_layers=(lo, hi), **readout_kwargs)         # [n, hi - lo, I]
     index = donor["neurons_index"].cpu()
-    pixel_values = corrupt["pixel_values"]
-    common = {k: v for k, v in corrupt.items() if k != "pixel_values"}
-    if common.get("motion_feature") is None:
-        common["motion_feature"] = model.motion_feature(pixel_values, B)
-    common.update(visual_tokens=model.vit_tokens(pixel_values), **readout_kwargs)
+    common = _recipient(model, corrupt, B, readout_kwargs)
     base = model.forward(**common, return_neurons=rows, neuron_layers=(lo, hi))
     ranked = rank_neurons(donor["neurons"], base["neurons"], top)
     outs = [donor, base]
@@ -627,12 +595,7 @@ def neuron_trace(model, *, clean, corrupt, layers=None, top: int = 16, rows=None
         for j in ranked[w].tolist():
             values = donor["neurons"][:, w:w + 1, j:j + 1].contiguous()
             outs.append(model.forward(neuron_patch=NeuronPatch(rows, values, (lo + w, lo + w + 1), index, torch.tensor([j])), **common))
-    res = {"outs": outs, "layers": (lo, hi), "neurons": ranked}
-    if "score1" in outs[0]:
-        clean_score, corrupt_score = outs[0]["score1"].float(), outs[1]["score1"].float()
-        score = torch.stack([o["score1"].float() for o in outs[2:]], 1).view(B, hi - lo, top) if len(outs) > 2 else clean_score.new_zeros(B, hi - lo, top)
-        res.update(score=score, clean_score=clean_score, corrupt_score=corrupt_score, restored=restored_fraction(score, clean_score, corrupt_score))
-    return res
+    return _restored({"outs": outs, "layers": (lo, hi), "neurons": ranked}, outs, B, (hi - lo, top))
 
 
 def frame_ablation_generate(

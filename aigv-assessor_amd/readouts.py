@@ -11,11 +11,17 @@ This module is the one place that knows that decision.  A new read-out adds, HER
 is laid out per label position like ``logit`` - a row of ``ROW_FIELDS``.  Elsewhere it adds only what computes it: the native call in
 ``ScoringPass._read_rows`` (or the probe) and, for generate(), in ``Generation._decode_step``.  ``forward``, the graph key, the shared-prefix
 slices, ``dist_utils.score_clips_dp`` and ``eval_utils.batched`` follow from the record and the table.
+
+The stream, head and neuron options are three lines of ONE table, ``FAMILIES``: a line names the family's keywords, records, messages' words and
+``ReadOuts`` fields, and ``_capture`` / ``_patch`` / ``_scale`` check what the families share.  A new option of a family adds its slot to the line
+and its check to the function of its kind; a new family adds a line, its records, the hooks for what only it has (a patch's extra field, a
+scale's shape rules), a thin ``*_options`` front, its ``ReadOuts`` fields with their call in ``parse``, and ``forward()``'s keywords with their
+paragraph.  ``touches_stream``, ``forward_kwargs``, ``ScoringPass.forward``'s eager half and its patch planner walk the table.
 """
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Optional
+from typing import Callable, NamedTuple, Optional
 
 import torch
 
@@ -53,72 +59,9 @@ def candidates(candidate_ids, labels="given") -> Optional[torch.Tensor]:
     return t.to(torch.long).contiguous()
 
 
-def key_drop_mask(key_drop, ids_shape=None, probing: bool = False) -> Optional[torch.Tensor]:
-    """``key_drop`` (None, or a bool / integer tensor [B, N] laid out like ``input_ids``, on any device) -> None or a HOST bool tensor [B, N].
-    The shape is checked where ``ids_shape`` is known; the clip-dependent rules (first token, consumed rows) where the plan is
-    (``ScoringPass._key_drop_words``)."""
-    if key_drop is None:
-        return None
-    if probing:
-        raise ValueError("key_drop: cannot be combined with return_score_attention / return_token_attention / return_score_values (the probe does not know "
-                         "the mask)")
-    t = key_drop
-    if not torch.is_tensor(t) or t.is_floating_point() or t.is_complex() or t.dim() != 2:
-        raise ValueError("key_drop: expected a bool or integer tensor [B, N] laid out like input_ids")
-    if ids_shape is not None and tuple(t.shape) != tuple(ids_shape):
-        raise ValueError(f"key_drop: shape {tuple(t.shape)} differs from input_ids {tuple(ids_shape)}")
-    return t.detach().to("cpu").bool().contiguous()
-
-
-def key_drop_qualifiers(key_drop, key_drop_rows=None, key_drop_layers=None, ids_shape=None, n_layers: Optional[int] = None):
-    """The two qualifiers of ``key_drop`` -> (None or a HOST bool tensor [B, N], None or a pair of ints (lo, hi)).  ``key_drop_rows`` (bool or
-    integer tensor [B, N] laid out like ``input_ids``, on any device): the query rows that are cut from the dropped keys - None: every row.
-    ``key_drop_layers`` = (lo, hi): the layers lo <= l < hi run under the mask - None: all of them; 0 <= lo <= hi <= ``n_layers`` where that
-    is known.  Either one without ``key_drop`` is a ValueError.  The clip-dependent rule (no row is cut from itself) is checked where the
-    plan is (``ScoringPass._key_drop_words``)."""
-    rows, window = None, None
-    if key_drop_rows is not None:
-        if key_drop is None:
-            raise ValueError("key_drop_rows: qualifies key_drop and needs one")
-        t = key_drop_rows
-        if not torch.is_tensor(t) or t.is_floating_point() or t.is_complex() or t.dim() != 2:
-            raise ValueError("key_drop_rows: expected a bool or integer tensor [B, N] laid out like input_ids")
-        if ids_shape is not None and tuple(t.shape) != tuple(ids_shape):
-            raise ValueError(f"key_drop_rows: shape {tuple(t.shape)} differs from input_ids {tuple(ids_shape)}")
-        rows = t.detach().to("cpu").bool().contiguous()
-    if key_drop_layers is not None:
-        if key_drop is None:
-            raise ValueError("key_drop_layers: qualifies key_drop and needs one")
-        w = tuple(key_drop_layers) if isinstance(key_drop_layers, (tuple, list)) else None
-        if w is None or len(w) != 2 or any(isinstance(v, bool) or not isinstance(v, int) for v in w):
-            raise ValueError(f"key_drop_layers: expected a pair of ints (lo, hi), got {key_drop_layers!r}")
-        lo, hi = w
-        if not 0 <= lo <= hi or (n_layers is not None and hi > n_layers):
-            raise ValueError(f"key_drop_layers: ({lo}, {hi}) outside 0 <= lo <= hi <= {n_layers if n_layers is not None else 'L'}")
-        window = (lo, hi)
-    return rows, window
-
-
-def refuse_key_drop_qualifiers(where: str, key_drop_rows=None, key_drop_layers=None) -> None:
-    """The entry points that run through the KV cache take ``key_drop`` whole or not at all: the mask kept beside the cache has neither rows
-    nor a layer window."""
-    for name, v in (("key_drop_rows", key_drop_rows), ("key_drop_layers", key_drop_layers)):
-        if v is not None:
-            raise ValueError(f"{name}: {where} does not take it (the key-drop mask kept beside the KV cache has neither query rows nor a layer "
-                             "window); forward() does")
-
-
-@dataclass(frozen=True, eq=False)
-class StreamPatch:
-    """``forward(stream_patch=...)``: overwrite rows of the residual stream.  ``rows``: bool or integer tensor [B, N] laid out like ``input_ids``
-    (on any device) - the tokens patched; ``depths`` = (lo, hi), 0 <= lo <= hi <= L: immediately before each layer d, lo <= d < hi, runs;
-    ``values``: bf16 [n, hi - lo, H] on the device or the host, laid out exactly like the ``stream`` that ``forward(return_stream=rows,
-    stream_depths=depths)`` returns - n the selected tokens the pass runs, clip-major, position-ascending; ``index``: optionally the donor's
-    ``stream_index`` (int64 [n, 2]), then checked pair by pair against the recipient's."""
-    rows: torch.Tensor
-    values: torch.Tensor
-    depths: tuple
-    index: Optional[torch.Tensor] = None
+def _got(t) -> str:
+    """How a message names what it got: a tensor's shape and dtype, anything else's type."""
+    return f"{tuple(t.shape)} {t.dtype}" if torch.is_tensor(t) else type(t).__name__
 
 
 def _token_mask(name: str, t, ids_shape=None) -> torch.Tensor:
@@ -139,33 +82,57 @@ def _depth_window(name: str, depths, n_layers: Optional[int] = None) -> tuple:
     return lo, hi
 
 
-def stream_options(return_stream=None, stream_depths=None, stream_patch=None, ids_shape=None, n_layers: Optional[int] = None):
-    """``return_stream`` / ``stream_depths`` / ``stream_patch`` -> (None or a HOST bool mask [B, N], None or (lo, hi), None or a ``StreamPatch``
-    whose ``rows`` is such a mask, whose ``depths`` is a checked pair and whose ``index`` is a HOST int64 [n, 2]).  Depth d, 0 <= d < L, is the
-    stream layer d consumes; ``stream_depths`` defaults to (0, L) and needs ``return_stream``.  The values' dtype and the shapes that do not need
-    the plan are checked here; the counts and the (clip, position) pairs where the plan is (``ScoringPass._stream_rows``)."""
-    rows = window = patch = None
-    if return_stream is not None:
-        rows = _token_mask("return_stream", return_stream, ids_shape)
-        window = _depth_window("stream_depths", stream_depths, n_layers) if stream_depths is not None else (0, n_layers) if n_layers is not None else None
-    elif stream_depths is not None:
-        raise ValueError("stream_depths: qualifies return_stream and needs one")
-    if stream_patch is not None:
-        p = stream_patch
-        if not isinstance(p, StreamPatch):
-            raise ValueError(f"stream_patch: expected a readouts.StreamPatch, got {type(p).__name__}")
-        lo, hi = _depth_window("stream_patch: depths", p.depths, n_layers)
-        v = p.values
-        if not torch.is_tensor(v) or v.dtype != torch.bfloat16 or v.dim() != 3 or int(v.shape[1]) != hi - lo:
-            raise ValueError(f"stream_patch: values must be a bf16 tensor [n, hi - lo = {hi - lo}, H] laid out like a captured stream, got "
-                             f"{tuple(v.shape) if torch.is_tensor(v) else type(v).__name__}{' ' + str(v.dtype) if torch.is_tensor(v) else ''}")
-        idx = p.index
-        if idx is not None:
-            if not torch.is_tensor(idx) or idx.is_floating_point() or idx.dtype == torch.bool or idx.dim() != 2 or int(idx.shape[1]) != 2:
-                raise ValueError("stream_patch: index must be an integer tensor [n, 2] of (clip, position) pairs (a donor's stream_index)")
-            idx = idx.detach().to("cpu").to(torch.long).contiguous()
-        patch = StreamPatch(_token_mask("stream_patch: rows", p.rows, ids_shape), v, (lo, hi), idx)
-    return rows, window, patch
+def key_drop_mask(key_drop, ids_shape=None, probing: bool = False) -> Optional[torch.Tensor]:
+    """``key_drop`` (None, or a bool / integer tensor [B, N] laid out like ``input_ids``, on any device) -> None or a HOST bool tensor [B, N].
+    The shape is checked where ``ids_shape`` is known; the clip-dependent rules (first token, consumed rows) where the plan is
+    (``ScoringPass._key_drop_words``)."""
+    if key_drop is None:
+        return None
+    if probing:
+        raise ValueError("key_drop: cannot be combined with return_score_attention / return_token_attention / return_score_values (the probe does not know "
+                         "the mask)")
+    return _token_mask("key_drop", key_drop, ids_shape)
+
+
+def key_drop_qualifiers(key_drop, key_drop_rows=None, key_drop_layers=None, ids_shape=None, n_layers: Optional[int] = None):
+    """The two qualifiers of ``key_drop`` -> (None or a HOST bool tensor [B, N], None or a pair of ints (lo, hi)).  ``key_drop_rows`` (bool or
+    integer tensor [B, N] laid out like ``input_ids``, on any device): the query rows that are cut from the dropped keys - None: every row.
+    ``key_drop_layers`` = (lo, hi): the layers lo <= l < hi run under the mask - None: all of them; 0 <= lo <= hi <= ``n_layers`` where that
+    is known.  Either one without ``key_drop`` is a ValueError.  The clip-dependent rule (no row is cut from itself) is checked where the
+    plan is (``ScoringPass._key_drop_words``)."""
+    rows, window = None, None
+    if key_drop_rows is not None:
+        if key_drop is None:
+            raise ValueError("key_drop_rows: qualifies key_drop and needs one")
+        rows = _token_mask("key_drop_rows", key_drop_rows, ids_shape)
+    if key_drop_layers is not None:
+        if key_drop is None:
+            raise ValueError("key_drop_layers: qualifies key_drop and needs one")
+        window = _depth_window("key_drop_layers", key_drop_layers, n_layers)
+    return rows, window
+
+
+def refuse_key_drop_qualifiers(where: str, key_drop_rows=None, key_drop_layers=None) -> None:
+    """The entry points that run through the KV cache take ``key_drop`` whole or not at all: the mask kept beside the cache has neither rows
+    nor a layer window."""
+    for name, v in (("key_drop_rows", key_drop_rows), ("key_drop_layers", key_drop_layers)):
+        if v is not None:
+            raise ValueError(f"{name}: {where} does not take it (the key-drop mask kept beside the KV cache has neither query rows nor a layer "
+                             "window); forward() does")
+
+
+# ---- the row options: a capture, a patch and a scale of the rows a layer consumes, per family (FAMILIES below) -----------------------------------
+@dataclass(frozen=True, eq=False)
+class StreamPatch:
+    """``forward(stream_patch=...)``: overwrite rows of the residual stream.  ``rows``: bool or integer tensor [B, N] laid out like ``input_ids``
+    (on any device) - the tokens patched; ``depths`` = (lo, hi), 0 <= lo <= hi <= L: immediately before each layer d, lo <= d < hi, runs;
+    ``values``: bf16 [n, hi - lo, H] on the device or the host, laid out exactly like the ``stream`` that ``forward(return_stream=rows,
+    stream_depths=depths)`` returns - n the selected tokens the pass runs, clip-major, position-ascending; ``index``: optionally the donor's
+    ``stream_index`` (int64 [n, 2]), then checked pair by pair against the recipient's."""
+    rows: torch.Tensor
+    values: torch.Tensor
+    depths: tuple
+    index: Optional[torch.Tensor] = None
 
 
 MAX_HEADS = 64     # a head mask travels as one uint64 per layer
@@ -192,69 +159,6 @@ class HeadScale:
     out; ``rows``: optional bool or integer tensor [B, N] - the query rows scaled (None: every row the pass runs)."""
     scale: torch.Tensor
     rows: Optional[torch.Tensor] = None
-
-
-def head_options(return_heads=None, head_layers=None, head_patch=None, head_scale=None, ids_shape=None, n_layers: Optional[int] = None,
-                 n_heads: Optional[int] = None, head_dim: Optional[int] = None):
-    """``return_heads`` / ``head_layers`` / ``head_patch`` / ``head_scale`` -> (None or a HOST bool mask [B, N], None or (lo, hi), None or a
-    ``HeadPatch`` whose ``rows`` is such a mask, whose ``layers`` is a checked pair, whose ``index`` is a HOST int64 [n, 2] and whose ``heads`` is a
-    HOST bool [hi - lo, n_heads] or None, None or a ``HeadScale`` whose ``scale`` is a HOST fp32 [L, n_heads] and whose ``rows`` is such a mask or
-    None).  Layer l, 0 <= l < L, names the input of that layer's ``wo``; ``head_layers`` defaults to (0, L) and needs ``return_heads``.  Shapes,
-    dtypes and windows are checked here (those that need the model's sizes only when they are given); counts and (clip, position) pairs where the
-    plan is (``ScoringPass._head_patch_plan``)."""
-    rows = window = patch = scale = None
-    if (return_heads is not None or head_patch is not None or head_scale is not None) and n_heads is not None and n_heads > MAX_HEADS:
-        raise ValueError(f"return_heads / head_patch / head_scale: the model has {n_heads} query heads, a head mask holds at most {MAX_HEADS}")
-    if return_heads is not None:
-        rows = _token_mask("return_heads", return_heads, ids_shape)
-        window = _depth_window("head_layers", head_layers, n_layers) if head_layers is not None else (0, n_layers) if n_layers is not None else None
-    elif head_layers is not None:
-        raise ValueError("head_layers: qualifies return_heads and needs one")
-    if head_patch is not None:
-        p = head_patch
-        if not isinstance(p, HeadPatch):
-            raise ValueError(f"head_patch: expected a readouts.HeadPatch, got {type(p).__name__}")
-        lo, hi = _depth_window("head_patch: layers", p.layers, n_layers)
-        v = p.values
-        if (not torch.is_tensor(v) or v.dtype != torch.bfloat16 or v.dim() != 4 or int(v.shape[1]) != hi - lo
-                or (n_heads is not None and int(v.shape[2]) != n_heads) or (head_dim is not None and int(v.shape[3]) != head_dim)):
-            raise ValueError(f"head_patch: values must be a bf16 tensor [n, hi - lo = {hi - lo}, n_heads{'' if n_heads is None else f' = {n_heads}'}, "
-                             f"D{'' if head_dim is None else f' = {head_dim}'}] laid out like captured heads, got "
-                             f"{tuple(v.shape) if torch.is_tensor(v) else type(v).__name__}{' ' + str(v.dtype) if torch.is_tensor(v) else ''}")
-        idx = p.index
-        if idx is not None:
-            if not torch.is_tensor(idx) or idx.is_floating_point() or idx.dtype == torch.bool or idx.dim() != 2 or int(idx.shape[1]) != 2:
-                raise ValueError("head_patch: index must be an integer tensor [n, 2] of (clip, position) pairs (a donor's heads_index)")
-            idx = idx.detach().to("cpu").to(torch.long).contiguous()
-        hm = p.heads
-        if hm is not None:
-            nh = int(v.shape[2])
-            if not torch.is_tensor(hm) or hm.dtype != torch.bool or tuple(hm.shape) not in ((nh,), (hi - lo, nh)):
-                raise ValueError(f"head_patch: heads must be a bool tensor [n_heads = {nh}] or [hi - lo = {hi - lo}, n_heads = {nh}], got "
-                                 f"{tuple(hm.shape) if torch.is_tensor(hm) else type(hm).__name__}{' ' + str(hm.dtype) if torch.is_tensor(hm) else ''}")
-            hm = hm.detach().to("cpu").expand(hi - lo, nh).contiguous()
-        patch = HeadPatch(_token_mask("head_patch: rows", p.rows, ids_shape), v, (lo, hi), idx, hm)
-    if head_scale is not None:
-        q = head_scale
-        if not isinstance(q, HeadScale):
-            raise ValueError(f"head_scale: expected a readouts.HeadScale, got {type(q).__name__}")
-        t = q.scale
-        if (not torch.is_tensor(t) or not t.is_floating_point() or t.dim() != 2 or (n_layers is not None and int(t.shape[0]) != n_layers)
-                or (n_heads is not None and int(t.shape[1]) != n_heads)):
-            raise ValueError(f"head_scale: scale must be a float tensor [L{'' if n_layers is None else f' = {n_layers}'}, "
-                             f"n_heads{'' if n_heads is None else f' = {n_heads}'}], got "
-                             f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}{' ' + str(t.dtype) if torch.is_tensor(t) else ''}")
-        t = t.detach().to("cpu").to(torch.float32).contiguous()
-        if torch.isnan(t).any():
-            l, h = torch.isnan(t).nonzero()[0].tolist()
-            raise ValueError(f"head_scale: scale[{l}, {h}] is NaN")
-        scale = HeadScale(t, None if q.rows is None else _token_mask("head_scale: rows", q.rows, ids_shape))
-    return rows, window, patch, scale
-
-
-def head_bits(heads: torch.Tensor) -> list:
-    """A HOST bool [n_layers, n_heads] -> one int per layer with bit h set where head h is selected (the C ABI's uint64 words)."""
-    return [sum(1 << h for h, on in enumerate(row) if on) for row in heads.tolist()]
 
 
 MAX_NEURON_SEL = 4096     # a sparse neuron list: at most this many entries per option (the context's device tables)
@@ -286,6 +190,11 @@ class NeuronScale:
     rows: Optional[torch.Tensor] = None
 
 
+def head_bits(heads: torch.Tensor) -> list:
+    """A HOST bool [n_layers, n_heads] -> one int per layer with bit h set where head h is selected (the C ABI's uint64 words)."""
+    return [sum(1 << h for h, on in enumerate(row) if on) for row in heads.tolist()]
+
+
 def _neuron_ids(name: str, t, n_inter: Optional[int] = None) -> torch.Tensor:
     if not torch.is_tensor(t) or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool or t.dim() != 1:
         raise ValueError(f"{name}: expected an integer tensor [m] of neuron numbers")
@@ -300,6 +209,180 @@ def _neuron_ids(name: str, t, n_inter: Optional[int] = None) -> torch.Tensor:
     return t
 
 
+# the families' own hooks.  ``sizes``: what is known of the model - n_layers, n_heads, head_dim, n_inter, hidden; a missing or None entry is not checked
+def _patch_heads(p, values, lo, hi, sizes):
+    """``HeadPatch.heads`` (checked behind the values, whose head count it goes by) -> None or a HOST bool [hi - lo, n_heads]."""
+    hm, nh = p.heads, int(values.shape[2])
+    if hm is None:
+        return None
+    if not torch.is_tensor(hm) or hm.dtype != torch.bool or tuple(hm.shape) not in ((nh,), (hi - lo, nh)):
+        raise ValueError(f"head_patch: heads must be a bool tensor [n_heads = {nh}] or [hi - lo = {hi - lo}, n_heads = {nh}], got {_got(hm)}")
+    return hm.detach().to("cpu").expand(hi - lo, nh).contiguous()
+
+
+def _patch_neurons(p, values, lo, hi, sizes):
+    """``NeuronPatch.neurons`` (checked in front of the values, whose width it sets) -> None or a HOST int64 [m]."""
+    return None if p.neurons is None else _neuron_ids("neuron_patch: neurons", p.neurons, sizes.get("n_inter"))
+
+
+def _head_scale_rules(q, sizes):
+    t, L, nh = q.scale, sizes.get("n_layers"), sizes.get("n_heads")
+    if not torch.is_tensor(t) or not t.is_floating_point() or t.dim() != 2 or (L is not None and int(t.shape[0]) != L) or (nh is not None and int(t.shape[1]) != nh):
+        raise ValueError(f"head_scale: scale must be a float tensor [L{'' if L is None else f' = {L}'}, n_heads{'' if nh is None else f' = {nh}'}], got {_got(t)}")
+    return HeadScale
+
+
+def _neuron_scale_rules(q, sizes):
+    """[L] factors, or [m] beside [m, 2] unique (layer, neuron) pairs - which then travel in the C ABI's order: by layer, then by neuron."""
+    t, sel, L, I = q.scale, q.neurons, sizes.get("n_layers"), sizes.get("n_inter")
+    if sel is None:
+        if not torch.is_tensor(t) or not t.is_floating_point() or t.dim() != 1 or (L is not None and int(t.shape[0]) != L):
+            raise ValueError(f"neuron_scale: scale must be a float tensor [L{'' if L is None else f' = {L}'}] when neurons is None, got {_got(t)}")
+        return lambda t, rows: NeuronScale(t, None, rows)
+    if not torch.is_tensor(sel) or sel.is_floating_point() or sel.dtype == torch.bool or sel.dim() != 2 or int(sel.shape[1]) != 2:
+        raise ValueError("neuron_scale: neurons must be an integer tensor [m, 2] of (layer, neuron) pairs")
+    sel = sel.detach().to("cpu").to(torch.long).contiguous()
+    m = int(sel.shape[0])
+    if m > MAX_NEURON_SEL:
+        raise ValueError(f"neuron_scale: {m} neurons, at most {MAX_NEURON_SEL} per option")
+    if not torch.is_tensor(t) or not t.is_floating_point() or tuple(t.shape) != (m,):
+        raise ValueError(f"neuron_scale: scale must be a float tensor [m = {m}] beside neurons [m, 2], got {_got(t)}")
+    if m and (int(sel.min()) < 0 or (L is not None and int(sel[:, 0].max()) >= L) or (I is not None and int(sel[:, 1].max()) >= I)):
+        raise ValueError(f"neuron_scale: a (layer, neuron) pair outside layers 0..{'L - 1' if L is None else L - 1}, neurons 0..{'I - 1' if I is None else I - 1}")
+    if int(torch.unique(sel, dim=0).shape[0]) != m:
+        raise ValueError("neuron_scale: the (layer, neuron) pairs must be unique")
+    order = torch.argsort(sel[:, 0] * (int(sel[:, 1].max()) + 1) + sel[:, 1]) if m else torch.arange(0)
+    return lambda t, rows: NeuronScale(t[order].contiguous(), sel[order].contiguous(), rows)
+
+
+class Family(NamedTuple):
+    """One line of ``FAMILIES``: what differs between the families of row options.  ``_capture``, ``_patch`` and ``_scale`` below check what they
+    share; ``ScoringPass.forward`` and its patch planner walk the same lines."""
+    name: str                   # ``_prefill``'s keywords are <name>_capture, <name>_patch, <name>_scale
+    capture: str                # forward()'s keywords: the capture's mask, ...
+    window: str                 # ... its window, also the ``ReadOuts`` field, ...
+    ids: Optional[str]          # ... a further qualifier of the capture, ...
+    patch: str                  # ... the patch, ...
+    scale: Optional[str]        # ... and the scale, where the family has them
+    rows: str                   # the ``ReadOuts`` field of the capture's mask (every other field carries its keyword's name)
+    word: str                   # the window's name in a patch record and in messages
+    Patch: type
+    Scale: Optional[type]
+    dims: Callable              # (sizes, the patch's extra) -> ((message word, size or None), ...): the trailing dims of a captured row
+    like: str                   # what a patch's values are laid out like
+    result: str                 # the result dict's entry (beside <result>_index)
+    extra: Optional[str] = None             # a patch record's own field ...
+    patch_extra: Optional[Callable] = None  # ... its check (p, values, lo, hi, sizes) -> the checked field ...
+    extra_first: bool = False               # ... run in front of the values' check (it sets their width) or behind it (it goes by their shape)
+    scale_rules: Optional[Callable] = None  # (q, sizes): the scale's shape rules -> what builds the checked record from (fp32 factors, rows)
+    # ---- what ``ScoringPass`` reads -----
+    misfit: Optional[Callable] = None       # (got dims, the model's) -> the planner's message for values of another width
+    pack: Optional[Callable] = None         # the extra as the C ABI takes it -> (packed or None: everything, whether it selects anything)
+    scale_args: Optional[Callable] = None   # the checked scale record -> what ``_prefill`` arms behind the packed rows
+    trimmed_last: bool = False              # a capture's slice of the row-trimmed last layer is NaN where no launch writes it
+
+    @property
+    def keywords(self) -> tuple:
+        return tuple(k for k in (self.capture, self.window, self.ids, self.patch, self.scale) if k)
+
+    @property
+    def fields(self) -> tuple:
+        """The ``ReadOuts`` fields, in the order of ``keywords`` - and of the tuple the family's ``*_options`` returns."""
+        return (self.rows,) + self.keywords[1:]
+
+
+FAMILIES = (
+    Family("stream", "return_stream", "stream_depths", None, "stream_patch", None, "stream_rows", "depths", StreamPatch, None,
+           lambda sizes, _: (("H", sizes.get("hidden")),), "a captured stream", "stream",
+           misfit=lambda got, want: f"values of width {got[0]}, the residual stream has H = {want[0]}"),
+    Family("head", "return_heads", "head_layers", None, "head_patch", "head_scale", "head_rows", "layers", HeadPatch, HeadScale,
+           lambda sizes, _: (("n_heads", sizes.get("n_heads")), ("D", sizes.get("head_dim"))), "captured heads", "heads",
+           extra="heads", patch_extra=_patch_heads, scale_rules=_head_scale_rules,
+           misfit=lambda got, want: f"values of {got[0]} heads x {got[1]}, the model has {want[0]} x {want[1]}",
+           pack=lambda heads: (None, True) if heads is None else (head_bits(heads), bool(heads.any())), scale_args=lambda q: (q.scale,)),
+    Family("neuron", "return_neurons", "neuron_layers", "neuron_ids", "neuron_patch", "neuron_scale", "neuron_rows", "layers", NeuronPatch, NeuronScale,
+           lambda sizes, cols: (("I", sizes.get("n_inter")),) if cols is None else (("m", int(cols.numel())),), "captured neurons", "neurons",
+           extra="neurons", patch_extra=_patch_neurons, extra_first=True, scale_rules=_neuron_scale_rules,
+           pack=lambda cols: (None, True) if cols is None else (cols.to(torch.int32).contiguous(), bool(cols.numel())),
+           scale_args=lambda q: (q.scale, None, None, None) if q.neurons is None else
+           (None, q.neurons[:, 0].to(torch.int32).contiguous(), q.neurons[:, 1].to(torch.int32).contiguous(), q.scale), trimmed_last=True),
+)
+STREAM, HEAD, NEURON = FAMILIES
+
+
+def _capture(fam: Family, mask, window, ids=None, ids_shape=None, n_layers: Optional[int] = None):
+    """A capture with its qualifiers -> (None or a HOST bool mask [B, N], None or (lo, hi) - by default (0, L) where L is known).  A qualifier
+    without the capture is refused."""
+    if mask is None:
+        for name, v in ((fam.window, window), (fam.ids, ids)):
+            if v is not None:
+                raise ValueError(f"{name}: qualifies {fam.capture} and needs one")
+        return None, None
+    return (_token_mask(fam.capture, mask, ids_shape),
+            _depth_window(fam.window, window, n_layers) if window is not None else (0, n_layers) if n_layers is not None else None)
+
+
+def _patch(fam: Family, p, ids_shape=None, **sizes):
+    """A patch record, checked without the plan: its type, window, values' layout, donor index and row mask, the family's extra where the line
+    says -> None or the record with HOST masks and index, a checked window and the values as given."""
+    if p is None:
+        return None
+    if not isinstance(p, fam.Patch):
+        raise ValueError(f"{fam.patch}: expected a readouts.{fam.Patch.__name__}, got {type(p).__name__}")
+    lo, hi = _depth_window(f"{fam.patch}: {fam.word}", getattr(p, fam.word), sizes.get("n_layers"))
+    v, extra = p.values, ()
+    if fam.extra_first:
+        extra = (fam.patch_extra(p, v, lo, hi, sizes),)
+    dims = fam.dims(sizes, *extra or (None,))
+    if (not torch.is_tensor(v) or v.dtype != torch.bfloat16 or v.dim() != 2 + len(dims) or int(v.shape[1]) != hi - lo
+            or any(size is not None and int(n) != size for n, (_, size) in zip(v.shape[2:], dims))):
+        layout = ", ".join(word + ("" if size is None else f" = {size}") for word, size in dims)
+        raise ValueError(f"{fam.patch}: values must be a bf16 tensor [n, hi - lo = {hi - lo}, {layout}] laid out like {fam.like}, got {_got(v)}")
+    idx = p.index
+    if idx is not None:
+        if not torch.is_tensor(idx) or idx.is_floating_point() or idx.dtype == torch.bool or idx.dim() != 2 or int(idx.shape[1]) != 2:
+            raise ValueError(f"{fam.patch}: index must be an integer tensor [n, 2] of (clip, position) pairs (a donor's {fam.result}_index)")
+        idx = idx.detach().to("cpu").to(torch.long).contiguous()
+    if fam.patch_extra is not None and not fam.extra_first:
+        extra = (fam.patch_extra(p, v, lo, hi, sizes),)
+    return fam.Patch(_token_mask(f"{fam.patch}: rows", p.rows, ids_shape), v, (lo, hi), idx, *extra)
+
+
+def _scale(fam: Family, q, ids_shape=None, **sizes):
+    """A scale record, checked: its type, the family's shape rules, the factors as HOST fp32 without a NaN, the optional row mask."""
+    if q is None:
+        return None
+    if not isinstance(q, fam.Scale):
+        raise ValueError(f"{fam.scale}: expected a readouts.{fam.Scale.__name__}, got {type(q).__name__}")
+    build = fam.scale_rules(q, sizes)
+    t = q.scale.detach().to("cpu").to(torch.float32).contiguous()
+    if torch.isnan(t).any():
+        raise ValueError(f"{fam.scale}: scale[{', '.join(str(i) for i in torch.isnan(t).nonzero()[0].tolist())}] is NaN")
+    return build(t, None if q.rows is None else _token_mask(f"{fam.scale}: rows", q.rows, ids_shape))
+
+
+def stream_options(return_stream=None, stream_depths=None, stream_patch=None, ids_shape=None, n_layers: Optional[int] = None):
+    """``return_stream`` / ``stream_depths`` / ``stream_patch`` -> (None or a HOST bool mask [B, N], None or (lo, hi), None or a ``StreamPatch``
+    whose ``rows`` is such a mask, whose ``depths`` is a checked pair and whose ``index`` is a HOST int64 [n, 2]).  Depth d, 0 <= d < L, is the
+    stream layer d consumes; ``stream_depths`` defaults to (0, L) and needs ``return_stream``.  The values' dtype and the shapes that do not need
+    the plan are checked here; the counts and the (clip, position) pairs where the plan is (``ScoringPass._stream_rows``)."""
+    return (*_capture(STREAM, return_stream, stream_depths, None, ids_shape, n_layers), _patch(STREAM, stream_patch, ids_shape, n_layers=n_layers))
+
+
+def head_options(return_heads=None, head_layers=None, head_patch=None, head_scale=None, ids_shape=None, n_layers: Optional[int] = None,
+                 n_heads: Optional[int] = None, head_dim: Optional[int] = None):
+    """``return_heads`` / ``head_layers`` / ``head_patch`` / ``head_scale`` -> (None or a HOST bool mask [B, N], None or (lo, hi), None or a
+    ``HeadPatch`` whose ``rows`` is such a mask, whose ``layers`` is a checked pair, whose ``index`` is a HOST int64 [n, 2] and whose ``heads`` is a
+    HOST bool [hi - lo, n_heads] or None, None or a ``HeadScale`` whose ``scale`` is a HOST fp32 [L, n_heads] and whose ``rows`` is such a mask or
+    None).  Layer l, 0 <= l < L, names the input of that layer's ``wo``; ``head_layers`` defaults to (0, L) and needs ``return_heads``.  Shapes,
+    dtypes and windows are checked here (those that need the model's sizes only when they are given); counts and (clip, position) pairs where the
+    plan is (``ScoringPass._head_patch_plan``)."""
+    if (return_heads is not None or head_patch is not None or head_scale is not None) and n_heads is not None and n_heads > MAX_HEADS:
+        raise ValueError(f"return_heads / head_patch / head_scale: the model has {n_heads} query heads, a head mask holds at most {MAX_HEADS}")
+    sizes = dict(n_layers=n_layers, n_heads=n_heads, head_dim=head_dim)
+    return (*_capture(HEAD, return_heads, head_layers, None, ids_shape, n_layers), _patch(HEAD, head_patch, ids_shape, **sizes), _scale(HEAD, head_scale, ids_shape, **sizes))
+
+
 def neuron_options(return_neurons=None, neuron_layers=None, neuron_ids=None, neuron_patch=None, neuron_scale=None, ids_shape=None,
                    n_layers: Optional[int] = None, n_inter: Optional[int] = None):
     """``return_neurons`` / ``neuron_layers`` / ``neuron_ids`` / ``neuron_patch`` / ``neuron_scale`` -> (None or a HOST bool mask [B, N], None or
@@ -309,62 +392,10 @@ def neuron_options(return_neurons=None, neuron_layers=None, neuron_ids=None, neu
     the input of that layer's ``w2``; ``neuron_layers`` defaults to (0, L); it and ``neuron_ids`` need ``return_neurons``.  Shapes, dtypes, windows
     and lists are checked here (those that need the model's sizes only when they are given); counts and (clip, position) pairs where the plan is
     (``ScoringPass._neuron_patch_plan``)."""
-    rows = window = ids = patch = scale = None
-    if return_neurons is not None:
-        rows = _token_mask("return_neurons", return_neurons, ids_shape)
-        window = _depth_window("neuron_layers", neuron_layers, n_layers) if neuron_layers is not None else (0, n_layers) if n_layers is not None else None
-        ids = None if neuron_ids is None else _neuron_ids("neuron_ids", neuron_ids, n_inter)
-    elif neuron_layers is not None or neuron_ids is not None:
-        raise ValueError(f"{'neuron_layers' if neuron_layers is not None else 'neuron_ids'}: qualifies return_neurons and needs one")
-    if neuron_patch is not None:
-        p = neuron_patch
-        if not isinstance(p, NeuronPatch):
-            raise ValueError(f"neuron_patch: expected a readouts.NeuronPatch, got {type(p).__name__}")
-        lo, hi = _depth_window("neuron_patch: layers", p.layers, n_layers)
-        cols = None if p.neurons is None else _neuron_ids("neuron_patch: neurons", p.neurons, n_inter)
-        width = n_inter if cols is None else int(cols.numel())
-        v = p.values
-        if not torch.is_tensor(v) or v.dtype != torch.bfloat16 or v.dim() != 3 or int(v.shape[1]) != hi - lo or (width is not None and int(v.shape[2]) != width):
-            raise ValueError(f"neuron_patch: values must be a bf16 tensor [n, hi - lo = {hi - lo}, {'I' if cols is None else 'm'}{'' if width is None else f' = {width}'}] "
-                             f"laid out like captured neurons, got {tuple(v.shape) if torch.is_tensor(v) else type(v).__name__}"
-                             f"{' ' + str(v.dtype) if torch.is_tensor(v) else ''}")
-        idx = p.index
-        if idx is not None:
-            if not torch.is_tensor(idx) or idx.is_floating_point() or idx.dtype == torch.bool or idx.dim() != 2 or int(idx.shape[1]) != 2:
-                raise ValueError("neuron_patch: index must be an integer tensor [n, 2] of (clip, position) pairs (a donor's neurons_index)")
-            idx = idx.detach().to("cpu").to(torch.long).contiguous()
-        patch = NeuronPatch(_token_mask("neuron_patch: rows", p.rows, ids_shape), v, (lo, hi), idx, cols)
-    if neuron_scale is not None:
-        q = neuron_scale
-        if not isinstance(q, NeuronScale):
-            raise ValueError(f"neuron_scale: expected a readouts.NeuronScale, got {type(q).__name__}")
-        t, sel = q.scale, q.neurons
-        got = f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}{' ' + str(t.dtype) if torch.is_tensor(t) else ''}"
-        if sel is None:
-            if not torch.is_tensor(t) or not t.is_floating_point() or t.dim() != 1 or (n_layers is not None and int(t.shape[0]) != n_layers):
-                raise ValueError(f"neuron_scale: scale must be a float tensor [L{'' if n_layers is None else f' = {n_layers}'}] when neurons is None, got {got}")
-        else:
-            if not torch.is_tensor(sel) or sel.is_floating_point() or sel.dtype == torch.bool or sel.dim() != 2 or int(sel.shape[1]) != 2:
-                raise ValueError("neuron_scale: neurons must be an integer tensor [m, 2] of (layer, neuron) pairs")
-            sel = sel.detach().to("cpu").to(torch.long).contiguous()
-            m = int(sel.shape[0])
-            if m > MAX_NEURON_SEL:
-                raise ValueError(f"neuron_scale: {m} neurons, at most {MAX_NEURON_SEL} per option")
-            if not torch.is_tensor(t) or not t.is_floating_point() or tuple(t.shape) != (m,):
-                raise ValueError(f"neuron_scale: scale must be a float tensor [m = {m}] beside neurons [m, 2], got {got}")
-            if m and (int(sel.min()) < 0 or (n_layers is not None and int(sel[:, 0].max()) >= n_layers) or (n_inter is not None and int(sel[:, 1].max()) >= n_inter)):
-                raise ValueError(f"neuron_scale: a (layer, neuron) pair outside layers 0..{'L - 1' if n_layers is None else n_layers - 1}, "
-                                 f"neurons 0..{'I - 1' if n_inter is None else n_inter - 1}")
-            if int(torch.unique(sel, dim=0).shape[0]) != m:
-                raise ValueError("neuron_scale: the (layer, neuron) pairs must be unique")
-        t = t.detach().to("cpu").to(torch.float32).contiguous()
-        if torch.isnan(t).any():
-            raise ValueError(f"neuron_scale: scale[{int(torch.isnan(t).nonzero()[0])}] is NaN")
-        if sel is not None and sel.shape[0]:        # the C ABI's order: by layer, then by neuron
-            order = torch.argsort(sel[:, 0] * (int(sel[:, 1].max()) + 1) + sel[:, 1])
-            sel, t = sel[order].contiguous(), t[order].contiguous()
-        scale = NeuronScale(t, sel, None if q.rows is None else _token_mask("neuron_scale: rows", q.rows, ids_shape))
-    return rows, window, ids, patch, scale
+    rows, window = _capture(NEURON, return_neurons, neuron_layers, neuron_ids, ids_shape, n_layers)
+    ids = None if rows is None or neuron_ids is None else _neuron_ids("neuron_ids", neuron_ids, n_inter)
+    sizes = dict(n_layers=n_layers, n_inter=n_inter)
+    return rows, window, ids, _patch(NEURON, neuron_patch, ids_shape, **sizes), _scale(NEURON, neuron_scale, ids_shape, **sizes)
 
 
 _NAN = float("nan")
@@ -408,7 +439,7 @@ class ReadOuts:
     head_scale: Optional[HeadScale] = None          # head outputs multiplied by a factor per (layer, head) (forward only)
 
     @classmethod
-    def parse(cls, vocab: int, labels="given", return_logprobs: bool = False, candidate_ids=None, top_logprobs: Optional[int] = None,
+    def parse(cls, vocab: int, labels="given", *, return_logprobs: bool = False, candidate_ids=None, top_logprobs: Optional[int] = None,
               return_score_attention: bool = False, attention_segments=None, return_token_attention: bool = False, key_drop=None,
               ids_shape=None, key_drop_rows=None, key_drop_layers=None, n_layers: Optional[int] = None, return_depth_lens: bool = False,
               return_stream=None, stream_depths=None, stream_patch=None, return_heads=None, head_layers=None, head_patch=None, head_scale=None,
@@ -416,27 +447,29 @@ class ReadOuts:
               neuron_scale=None, n_inter: Optional[int] = None, return_score_values: bool = False) -> "ReadOuts":
         """The record of a call's public keyword arguments, checked.  ``labels=None`` (``forward`` without labels) refuses candidates and top-k;
         the shared-prefix and generate entry points leave the default.  A user segment table is checked where its bins are counted
-        (``n_segments``: it needs the shape of ``input_ids``)."""
-        cand = candidates(candidate_ids, labels)
-        k = top_logprobs_k(top_logprobs, vocab, labels)
+        (``n_segments``: it needs the shape of ``input_ids``).  Every check that needs no plan, in the order a call meets them: the clip count of
+        ``return_score_values``, the key-drop qualifiers, ``key_drop``, the stream, head and neuron families, ``candidate_ids``,
+        ``top_logprobs``, the clip count of ``return_depth_lens``."""
         att = bool(return_score_attention or return_token_attention or return_score_values)
         if return_score_values and ids_shape is not None and int(ids_shape[0]) > MAX_PROBE_ROWS:
             raise ValueError(f"return_score_values: at most {MAX_PROBE_ROWS} clips per pass, got {int(ids_shape[0])}")
         rows, window = key_drop_qualifiers(key_drop, key_drop_rows, key_drop_layers, ids_shape, n_layers)
+        mask = key_drop_mask(key_drop, ids_shape, att)
+        stream = stream_options(return_stream, stream_depths, stream_patch, ids_shape, n_layers)
+        heads = head_options(return_heads, head_layers, head_patch, head_scale, ids_shape, n_layers, n_heads, head_dim)
+        neurons = neuron_options(return_neurons, neuron_layers, neuron_ids, neuron_patch, neuron_scale, ids_shape, n_layers, n_inter)
+        cand = candidates(candidate_ids, labels)
+        k = top_logprobs_k(top_logprobs, vocab, labels)
         if return_depth_lens and ids_shape is not None and int(ids_shape[0]) > MAX_LENS_ROWS:
             raise ValueError(f"return_depth_lens: at most {MAX_LENS_ROWS} clips per pass, got {int(ids_shape[0])}")
         return cls(bool(return_logprobs), cand, k or None, att, attention_segments if att else None, bool(return_token_attention), bool(return_score_values),
-                   key_drop_mask(key_drop, ids_shape, att), rows, window, bool(return_depth_lens),
-                   *neuron_options(return_neurons, neuron_layers, neuron_ids, neuron_patch, neuron_scale, ids_shape, n_layers, n_inter),
-                   *stream_options(return_stream, stream_depths, stream_patch, ids_shape, n_layers),
-                   *head_options(return_heads, head_layers, head_patch, head_scale, ids_shape, n_layers, n_heads, head_dim))
+                   mask, rows, window, bool(return_depth_lens), *neurons, *stream, *heads)
 
     @property
     def touches_stream(self) -> bool:
         """A capture or a patch of the residual stream, or a capture, patch or scale of head outputs or of MLP neurons: such a call runs eagerly
         under graph replay, as a masked call does."""
-        return (self.stream_rows is not None or self.stream_patch is not None or self.head_rows is not None or self.head_patch is not None
-                or self.head_scale is not None or self.neuron_rows is not None or self.neuron_patch is not None or self.neuron_scale is not None)
+        return any(getattr(self, f) is not None for fam in FAMILIES for f in (fam.rows, fam.patch, fam.scale) if f)
 
     @property
     def runs_eagerly(self) -> bool:
@@ -485,9 +518,7 @@ def forward_kwargs(r: ReadOuts) -> dict:
     kw = dict(return_logprobs=r.logprobs or None, candidate_ids=r.cand, top_logprobs=r.topk, return_score_attention=r.score_attention or None,
               attention_segments=r.segments, return_token_attention=r.token_attention or None, return_score_values=r.score_values or None, key_drop=r.key_drop,
               key_drop_rows=r.key_drop_rows, key_drop_layers=r.key_drop_layers, return_depth_lens=r.depth_lens or None,
-              return_stream=r.stream_rows, stream_depths=r.stream_depths, stream_patch=r.stream_patch,
-              return_heads=r.head_rows, head_layers=r.head_layers, head_patch=r.head_patch, head_scale=r.head_scale,
-              return_neurons=r.neuron_rows, neuron_layers=r.neuron_layers, neuron_ids=r.neuron_ids, neuron_patch=r.neuron_patch, neuron_scale=r.neuron_scale)
+              **{k: getattr(r, f) for fam in FAMILIES for k, f in zip(fam.keywords, fam.fields)})
     return {k: v for k, v in kw.items() if v is not None}
 
 

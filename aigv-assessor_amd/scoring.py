@@ -480,41 +480,35 @@ class ScoringPass:
                 i = int(differ[0])
                 raise ValueError(f"{name}: pair {i} of index is (clip, position) = {tuple(patch.index[i].tolist())}, the pass's is {tuple(index[i].tolist())}")
 
-    def _stream_patch_plan(self, plan, patch):
-        """``stream_patch`` checked against the plan, host work only -> None (an empty window or an empty selection: the plain pass) or (packed
-        rows, lo, hi, the values as given).  ValueError: the values' shape, a count mismatch (both counts), the first differing (clip, position)."""
-        rows, index = self._stream_rows(plan, patch.rows)
-        (lo, hi), v, H = patch.depths, patch.values, self.config.llm_config.hidden_size
-        if int(v.shape[2]) != H:
-            raise ValueError(f"stream_patch: values of width {int(v.shape[2])}, the residual stream has H = {H}")
-        n = int(rows.numel())
-        self._patch_rows_check("stream_patch", n, patch, index)
-        return (rows, lo, hi, v) if n and hi > lo else None
+    def _model_sizes(self) -> dict:
+        """The model's sizes under the names ``readouts.FAMILIES`` reads them by."""
+        llm = self.config.llm_config
+        return dict(n_layers=llm.num_hidden_layers, n_heads=llm.num_attention_heads, head_dim=llm.head_dim, n_inter=llm.intermediate_size, hidden=llm.hidden_size)
 
-    # ---- head knock-out and head patching (return_heads / head_patch / head_scale) ------------------------------------------------------------
-    def _head_patch_plan(self, plan, patch):
-        """``head_patch`` checked against the plan, host work only -> None (an empty window, an empty selection or no head selected: the plain pass)
-        or (packed rows, lo, hi, one mask word per layer or None, the values as given).  ValueError: the values' shape, a count mismatch (both
-        counts), the first differing (clip, position)."""
-        rows, index = self._stream_rows(plan, patch.rows)
-        (lo, hi), v, l = patch.layers, patch.values, self.config.llm_config
-        if tuple(v.shape[2:]) != (l.num_attention_heads, l.head_dim):
-            raise ValueError(f"head_patch: values of {int(v.shape[2])} heads x {int(v.shape[3])}, the model has {l.num_attention_heads} x {l.head_dim}")
-        n = int(rows.numel())
-        self._patch_rows_check("head_patch", n, patch, index)
-        bits = None if patch.heads is None else readouts.head_bits(patch.heads)
-        return (rows, lo, hi, bits, v) if n and hi > lo and (bits is None or any(bits)) else None
-
-    # ---- MLP neuron knock-out and neuron patching (return_neurons / neuron_patch / neuron_scale) --------------------------------------------------
-    def _neuron_patch_plan(self, plan, patch):
-        """``neuron_patch`` checked against the plan, host work only -> None (an empty window, an empty selection or no neuron selected: the plain
-        pass) or (packed rows, lo, hi, host int32 columns or None, the values as given).  ValueError: a count mismatch (both counts), the first
+    # ---- the patches of the three families (stream_patch; head_patch: head patching; neuron_patch: neuron patching) -------------------------------
+    def _patch_plan(self, fam, plan, patch):
+        """A checked patch record of the family ``fam`` (a line of ``readouts.FAMILIES``) against the plan, host work only -> None (an empty window,
+        an empty selection or an extra that selects nothing: the plain pass) or (packed rows, lo, hi, [the family's extra as the C ABI takes it or
+        None,] the values as given).  ValueError: the values' width (where the family checks it here), a count mismatch (both counts), the first
         differing (clip, position)."""
         rows, index = self._stream_rows(plan, patch.rows)
-        (lo, hi), n = patch.layers, int(rows.numel())
-        self._patch_rows_check("neuron_patch", n, patch, index)
-        cols = None if patch.neurons is None else patch.neurons.to(torch.int32).contiguous()
-        return (rows, lo, hi, cols, patch.values) if n and hi > lo and (cols is None or cols.numel()) else None
+        (lo, hi), v = getattr(patch, fam.word), patch.values
+        want = tuple(size for _, size in fam.dims(self._model_sizes(), None))
+        if fam.misfit is not None and tuple(v.shape[2:]) != want:
+            raise ValueError(f"{fam.patch}: {fam.misfit(tuple(v.shape[2:]), want)}")
+        n = int(rows.numel())
+        self._patch_rows_check(fam.patch, n, patch, index)
+        packed, any_selected = fam.pack(getattr(patch, fam.extra)) if fam.extra else (None, True)
+        return (rows, lo, hi, *((packed,) if fam.extra else ()), v) if n and hi > lo and any_selected else None
+
+    def _stream_patch_plan(self, plan, patch):
+        return self._patch_plan(readouts.STREAM, plan, patch)
+
+    def _head_patch_plan(self, plan, patch):
+        return self._patch_plan(readouts.HEAD, plan, patch)
+
+    def _neuron_patch_plan(self, plan, patch):
+        return self._patch_plan(readouts.NEURON, plan, patch)
 
     def forward(self, mos: Optional[torch.Tensor] = None, pixel_values: Optional[torch.Tensor] = None,
                 input_ids: Optional[torch.Tensor] = None, attention_mask: Optional[torch.Tensor] = None,
@@ -680,13 +674,27 @@ class ScoringPass:
         row and the answer rows), any other selected row has no MLP activation there - a patch or scale of it does nothing and its captured
         (row, L - 1) slice is NaN, as ``logprob`` is where there is no label.  The options combine with each other and with every other option,
         fp8 mode included; under graph replay a call carrying one runs eagerly.  ``eval_utils.mlp_knockout``, ``eval_utils.neuron_knockout`` and
-        ``eval_utils.neuron_trace`` run the sweeps."""
+        ``eval_utils.neuron_trace`` run the sweeps.
+
+        Of several faults in one call the first in this order is raised: every check that needs no plan (``readouts.ReadOuts.parse``: the clip count
+        of ``return_score_values``, the key-drop options, the stream, head and neuron options, ``candidate_ids``, ``top_logprobs``, the clip count of
+        ``return_depth_lens``), then the token plan's own checks and those against it (key-drop, the stream, head and neuron patches, the lens' rows)."""
         if position_ids is not None or past_key_values is not None:
             raise NotImplementedError("the eval pass takes default positions and no cache, like the reference drivers")
         if self.img_context_token_id is None:
             raise AssertionError("img_context_token_id must be set by the caller (stage2_eval.py:810)")
+        llm, sizes = self.config.llm_config, self._model_sizes()
+        # every option, checked once, before anything needs a plan or touches the device; every later step reads the record
+        ro = readouts.ReadOuts.parse(
+            llm.vocab_size, labels, return_logprobs=return_logprobs, candidate_ids=candidate_ids, top_logprobs=top_logprobs,
+            return_score_attention=return_score_attention, attention_segments=attention_segments, return_token_attention=return_token_attention,
+            return_score_values=return_score_values, key_drop=key_drop, key_drop_rows=key_drop_rows, key_drop_layers=key_drop_layers,
+            return_depth_lens=return_depth_lens, return_stream=return_stream, stream_depths=stream_depths, stream_patch=stream_patch,
+            return_heads=return_heads, head_layers=head_layers, head_patch=head_patch, head_scale=head_scale, return_neurons=return_neurons,
+            neuron_layers=neuron_layers, neuron_ids=neuron_ids, neuron_patch=neuron_patch, neuron_scale=neuron_scale,
+            ids_shape=None if input_ids is None else input_ids.shape, n_layers=sizes["n_layers"], n_heads=sizes["n_heads"], head_dim=sizes["head_dim"],
+            n_inter=sizes["n_inter"])
         drop_words = drop_row_words = None
-        n_layers = self.config.llm_config.num_hidden_layers
         built = []
 
         def host_plan():    # the host plan of this call, built on first use: by the first option below that is checked against it, else by the eager pass
@@ -694,36 +702,17 @@ class ScoringPass:
                 src = visual_tokens if visual_tokens is not None else pixel_values
                 built.append(self._plan(input_ids, attention_mask, labels, image_flags, (src.tokens if isinstance(src, VisualAhead) else src).shape[0], full_logits))
             return built[0]
-        if return_score_values and input_ids is not None and int(input_ids.shape[0]) > self.MAX_PROBE_ROWS:      # (before anything touches the device)
-            raise ValueError(f"return_score_values: at most {self.MAX_PROBE_ROWS} clips per pass, got {int(input_ids.shape[0])}")
-        kd_rows, kd_layers = readouts.key_drop_qualifiers(key_drop, key_drop_rows, key_drop_layers, None if input_ids is None else input_ids.shape, n_layers)
-        if key_drop is not None:        # checked in full on the host before anything touches the device (a plan of its own: host work only)
-            kd = readouts.key_drop_mask(key_drop, input_ids.shape, bool(return_score_attention or return_token_attention or return_score_values))
-            drop_words = self._key_drop_words(host_plan(), kd, kd_rows)
-            if kd_rows is not None:
+        # the checks against the plan, host work only (the eager pass below, which such a call takes, reuses the plan): key_drop in full, ...
+        if ro.key_drop is not None:
+            drop_words = self._key_drop_words(host_plan(), ro.key_drop, ro.key_drop_rows)
+            if ro.key_drop_rows is not None:
                 drop_words, drop_row_words = drop_words
-        _, _, patch = readouts.stream_options(return_stream, stream_depths, stream_patch, None if input_ids is None else input_ids.shape, n_layers)
-        # likewise: counts and pairs against the plan (host work only; the eager pass below, which such a call takes, reuses it)
-        patched = None if patch is None else self._stream_patch_plan(host_plan(), patch)
-        llm = self.config.llm_config
-        _, _, h_patch, h_scale = readouts.head_options(return_heads, head_layers, head_patch, head_scale, None if input_ids is None else input_ids.shape, n_layers,
-                                                       llm.num_attention_heads, llm.head_dim)
-        h_patched = None if h_patch is None else self._head_patch_plan(host_plan(), h_patch)
-        _, _, _, n_patch, _ = readouts.neuron_options(return_neurons, neuron_layers, neuron_ids, neuron_patch, neuron_scale, None if input_ids is None else input_ids.shape,
-                                                      n_layers, llm.intermediate_size)
-        n_patched = None if n_patch is None else self._neuron_patch_plan(host_plan(), n_patch)
-        if return_depth_lens and self._capture_keep is None:      # likewise: is there a row to read?  (inside a capture the call that led here has checked)
+        # ... a patch's counts and pairs, ...
+        patched = {fam.patch: self._patch_plan(fam, host_plan(), getattr(ro, fam.patch)) for fam in readouts.FAMILIES if getattr(ro, fam.patch) is not None}
+        if ro.depth_lens and self._capture_keep is None:      # ... and the lens: is there a row to read?  (inside a capture the call that led here has checked)
             self._depth_lens_rows(host_plan(), labels is not None)
         pixel_values, visual_tokens, motion_feature = self._take_ahead(pixel_values, visual_tokens, motion_feature)
-        parse = lambda: readouts.ReadOuts.parse(self.config.llm_config.vocab_size, labels, return_logprobs, candidate_ids, top_logprobs,
-                                                return_score_attention, attention_segments, return_token_attention, key_drop,
-                                                None if input_ids is None else input_ids.shape, key_drop_rows, key_drop_layers, n_layers,
-                                                return_depth_lens, return_stream, stream_depths, stream_patch, return_heads, head_layers, head_patch, head_scale,
-                                                llm.num_attention_heads, llm.head_dim, return_neurons, neuron_layers, neuron_ids, neuron_patch, neuron_scale,
-                                                llm.intermediate_size, return_score_values)
-        ro = None
         if self._graph_replay_enabled and self._capture_keep is None:
-            ro = parse()
             # (a masked call stays eager and leaves the graph cache as it is: capturing masked passes is out of scope)
             # (so does a call that captures or patches the residual stream, or captures, patches or scales head outputs or MLP neurons, or returns score values)
             out = None if ro.runs_eagerly else self._forward_through_graph(mos, pixel_values, input_ids, attention_mask, image_flags, labels,
@@ -735,7 +724,6 @@ class ScoringPass:
         # ---- index bookkeeping first, on the host (one small D2H copy if the ids live on the device), so that
         # every kernel of the step can then be enqueued back to back without a host sync in between ----
         plan = host_plan()
-        ro = ro or parse()      # (once per call; on the eager path behind the plan's own checks, where the options have always been checked)
         lp_labels = self._logprob_labels(plan) if ro.wants_labels else None
         lens_rows = self._depth_lens_rows(plan, labels is not None) if ro.depth_lens else None
         motion_feature = self._motion_feature(pixel_values, B, motion_feature)
@@ -745,46 +733,35 @@ class ScoringPass:
         vit_embeds, motion = self._visual_inputs(pixel_values, visual_tokens, motion_feature, plan)
         probe = self._score_attention_probe(plan, input_ids, ro) if ro.score_attention else None
         lens = None if lens_rows is None else self._depth_lens_buffers(lens_rows[0], lens_rows[2])
-        def capture_of(mask, window, *width):   # a capture's (packed rows, lo, hi, the bf16 buffer the pass fills [n, hi - lo, *width]) and its (clip, position) index
-            rows, index = self._stream_rows(plan, mask)
-            return (rows, *window, torch.empty((int(rows.numel()), window[1] - window[0], *width), dtype=torch.bfloat16, device=self.device)), index
-        to_device = lambda p: p and p[:-1] + (self._h2d(p[-1].detach().contiguous()),)   # a patch, checked against this very plan on the way in: its values go up (or stay) on the device
-        capture, stream_index = capture_of(ro.stream_rows, ro.stream_depths, llm.hidden_size) if ro.stream_rows is not None else (None, None)      # return_stream
-        patched = to_device(patched)
-        h_capture, heads_index = capture_of(ro.head_rows, ro.head_layers, llm.num_attention_heads, llm.head_dim) if ro.head_rows is not None else (None, None)     # return_heads
-        h_patched, h_scaled = to_device(h_patched), None
-        if ro.head_scale is not None and bool((ro.head_scale.scale != 1).any()):      # (a table of ones: the plain pass)
-            s_rows = None if ro.head_scale.rows is None else self._stream_rows(plan, ro.head_scale.rows)[0]
-            if s_rows is None or s_rows.numel():
-                h_scaled = (s_rows, ro.head_scale.scale)
-        n_capture = neurons_index = n_scaled = None
-        if ro.neuron_rows is not None:          # return_neurons: [n, hi - lo, I or m]
-            cols = None if ro.neuron_ids is None else ro.neuron_ids.to(torch.int32).contiguous()
-            (cap_rows, lo, hi, buf), neurons_index = capture_of(ro.neuron_rows, ro.neuron_layers, llm.intermediate_size if cols is None else int(cols.numel()))
-            if lo < hi == llm.num_hidden_layers and buf.numel():
-                buf[:, -1].fill_(float("nan"))      # a selected row the row-trimmed last layer does not consume has no activation there: no launch writes its slice
-            n_capture = (cap_rows, lo, hi, cols, buf)
-        n_patched = to_device(n_patched)
-        if ro.neuron_scale is not None and bool((ro.neuron_scale.scale != 1).any()):      # (factors of one: the plain pass)
-            q = ro.neuron_scale
-            s_rows = None if q.rows is None else self._stream_rows(plan, q.rows)[0]
-            if s_rows is None or s_rows.numel():
-                n_scaled = ((s_rows, q.scale, None, None, None) if q.neurons is None else
-                            (s_rows, None, q.neurons[:, 0].to(torch.int32).contiguous(), q.neurons[:, 1].to(torch.int32).contiguous(), q.scale))
-        live = lambda cap: cap if cap is not None and cap[-1].numel() else None     # (an empty capture arms nothing: its empty buffer is the result)
-        score, amax, *armed = self._prefill(plan["ids_packed"], plan["slot"], plan["cu"], vit_embeds, plan["n_vis"], motion,
-                                            plan["score_rows"], plan["logit_rows"], probe=probe, ld_tok=N if ro.token_attention else 0, values=ro.score_values,
-                                            drop_words=drop_words, drop_row_words=drop_row_words, drop_layers=kd_layers, lens=lens,
-                                            stream_capture=live(capture), stream_patch=patched, head_capture=live(h_capture), head_patch=h_patched,
-                                            head_scale=h_scaled, neuron_capture=live(n_capture), neuron_patch=n_patched, neuron_scale=n_scaled)
-        att, tok, *val = armed or (None, None)  # (_prefill hands the probe's tensors back only when it armed one)
+        armed, captured = {}, []    # what ``_prefill`` arms the pass with, by its keyword; (result name, buffer, (clip, position) index) of every capture
+        for fam in readouts.FAMILIES:
+            mask, p, q = getattr(ro, fam.rows), patched.get(fam.patch), getattr(ro, fam.scale) if fam.scale else None
+            if mask is not None:    # a capture: (packed rows, lo, hi, [the further qualifier as the C ABI takes it,] the bf16 buffer the pass fills [n, hi - lo, *dims])
+                ids = getattr(ro, fam.ids) if fam.ids else None
+                rows, index = self._stream_rows(plan, mask)
+                lo, hi = getattr(ro, fam.window)
+                buf = torch.empty((int(rows.numel()), hi - lo, *(size for _, size in fam.dims(sizes, ids))), dtype=torch.bfloat16, device=self.device)
+                if fam.trimmed_last and lo < hi == llm.num_hidden_layers and buf.numel():
+                    buf[:, -1].fill_(float("nan"))      # a selected row the row-trimmed last layer does not consume has no activation there: no launch writes its slice
+                captured.append((fam.result, buf, index))
+                if buf.numel():     # (an empty capture arms nothing: its empty buffer is the result)
+                    armed[fam.name + "_capture"] = (rows, lo, hi, *((fam.pack(ids)[0],) if fam.ids else ()), buf)
+            if p is not None:       # a patch, checked against this very plan on the way in: its values go up (or stay) on the device
+                armed[fam.patch] = p[:-1] + (self._h2d(p[-1].detach().contiguous()),)
+            if q is not None and bool((q.scale != 1).any()):      # (factors of one: the plain pass)
+                rows = None if q.rows is None else self._stream_rows(plan, q.rows)[0]
+                if rows is None or rows.numel():
+                    armed[fam.scale] = (rows, *fam.scale_args(q))
+        score, amax, *probed = self._prefill(plan["ids_packed"], plan["slot"], plan["cu"], vit_embeds, plan["n_vis"], motion,
+                                             plan["score_rows"], plan["logit_rows"], probe=probe, ld_tok=N if ro.token_attention else 0, values=ro.score_values,
+                                             drop_words=drop_words, drop_row_words=drop_row_words, drop_layers=ro.key_drop_layers, lens=lens, **armed)
+        att, tok, *val = probed or (None, None)  # (_prefill hands the probe's tensors back only when it armed one)
         reads = self._read_rows(B if score is not None else 0, len(plan["logit_rows"]), ro, lp_labels)
         out = self._outputs(plan, B, N, score, amax, mos, reads, att, tok, *val)
         if lens is not None:
             out.update(self._depth_lens_outputs(B, lens, lens_rows[1], ro, labels is not None))
-        for name, cap, index in (("stream", capture, stream_index), ("heads", h_capture, heads_index), ("neurons", n_capture, neurons_index)):
-            if cap is not None:
-                out.update({name: cap[-1], name + "_index": self._h2d(index)})
+        for name, buf, index in captured:
+            out.update({name: buf, name + "_index": self._h2d(index)})
         return out
 
     def dp_front(self, frames_local: torch.Tensor, frames_clips: Optional[torch.Tensor], n_clips: int):
@@ -1047,8 +1024,8 @@ class ScoringPass:
         pixel_values, visual_tokens, motion_feature = self._take_ahead(pixel_values, visual_tokens, motion_feature)
         n_frames = visual_tokens.shape[0] if visual_tokens is not None else pixel_values.shape[0]
         plans = [self._plan(ids, am, lab, image_flags, n_frames) for (ids, am, lab) in prompts]
-        ro = readouts.ReadOuts.parse(self.config.llm_config.vocab_size, "given", return_logprobs, candidate_ids, top_logprobs, return_score_attention,
-                                     None, return_token_attention, return_score_values=return_score_values)
+        ro = readouts.ReadOuts.parse(self.config.llm_config.vocab_size, "given", return_logprobs=return_logprobs, candidate_ids=candidate_ids, top_logprobs=top_logprobs,
+                                     return_score_attention=return_score_attention, return_token_attention=return_token_attention, return_score_values=return_score_values)
         lp_labels = [self._logprob_labels(pl) for pl in plans] if ro.wants_labels else None
         B = prompts[0][0].shape[0]
         pre = self._shared_prefix_lengths(plans, B)
