@@ -20,6 +20,13 @@
 //
 // Two copies are left, by measurement: skinny_kernel's bf16 linear chain (head.hip) and gemm_finalize_kernel's epilogues (gemm.hip); see
 // there.  The cross-route test (tests/test_gpu_gemm_layouts.py) and scripts/gemm_epilogue_bits.py hold them to these functions.
+//
+// What holds every route to round-to-nearest-even AT EACH of these rounding points is tests/test_gpu_gemm_rounding.py: its accumulators are
+// exact in any summation order and sit on ties (even and odd neighbour), a sticky bit beside a tie, a carry into the exponent, a tie that
+// only the second rounding sees (a stage fused onto the unrounded accumulator gives another answer), fp32 subnormals, the tie below 2^128
+// and signed zeros, at every column residue mod 8 of every half tile.  Each has ONE correct bit pattern, computed on the CPU
+// (tests/gemm_rounding_reference.py); truncation, round-half-up, a skipped rounding, a flush, saturation or a lost sign of zero in any
+// kernel, in either form below or in one of the two copies fails there.  A change to this file should meet that test first.
 #pragma once
 #include <type_traits>
 

@@ -514,8 +514,11 @@ class Fp8Layout(Layout):
     def put_operands(self, ldo_pad):
         """The e4m3 operands take the place of the bf16 ones: lda8 / ldw8 are in BYTES."""
         case = self.case
-        ops = GX.fp8_operands(case)
-        assert GX.fp8_is_exact(case, ops), "the case is not exact: the test itself is wrong"
+        if "fp8" in case:                                          # a case that brings its own e4m3 operands (tests/gemm_rounding_reference.py,
+            ops = case["fp8"]                                      # whose tests assert its bound themselves)
+        else:
+            ops = GX.fp8_operands(case)
+            assert GX.fp8_is_exact(case, ops), "the case is not exact: the test itself is wrong"
         K = case["K"]
         self.lda8, self.ldw8 = K + 16, K + 32
         assert len({self.lda8, self.ldw8, self.ldc}) == 3 and self.ldr not in (self.lda8, self.ldw8)
