@@ -133,6 +133,17 @@ struct aigv_ctx {
     int ld_tok = 0;
     float* val = nullptr;   // aigv_score_attention_arm_values: the value vectors [n_rows][layers][n_heads][n_seg + 1][D], else nullptr
   } probe;
+  // attention flow map (aigv_attention_map_arm): armed for exactly the next aigv_llm_prefill, which launches the all-rows map kernel (attnmap.hip) after
+  // llm_layer_qkv of every layer - into slice li - lo of rows_out for the layers of the window, else into scratch - and folds it into seg_out
+  struct {
+    bool armed = false;
+    const int32_t* seg = nullptr;      // device [T]
+    int n_seg = 0;
+    float* scratch = nullptr;          // device, the caller's: [T][n_heads][n_seg], rewritten by every layer outside the window
+    float* seg_out = nullptr;          // device, the caller's: [n_clips][layers][n_heads][n_seg][n_seg], or nullptr
+    float* rows_out = nullptr;         // device, the caller's: [hi - lo][T][n_heads][n_seg], or nullptr
+    int lo = 0, hi = 0;
+  } amap;
   // key-drop mask (aigv_key_drop_arm / _ex): armed for exactly the next aigv_llm_prefill, which applies it in the attention of the layers
   // [layer_begin, layer_end) - every layer for aigv_key_drop_arm - to the query rows `rows` selects (null: every row); keep_kv, which takes
   // neither qualifier: and keeps it with the cache, kv_drop above
@@ -333,12 +344,16 @@ struct DisarmScope {
   aigv_ctx* c;
   explicit DisarmScope(aigv_ctx* c_) : c(c_) {}
   ~DisarmScope() {
-    c->probe.armed = c->drop.armed = c->lens.armed = false;
+    c->probe.armed = c->drop.armed = c->lens.armed = c->amap.armed = false;
     for (const aigv_ctx::RowOptEntry& e : c->row_opts) e.opt->armed = false;
   }
 };
 int probe_plan(aigv_ctx* c, const char* op, const int32_t* cu, int B, const int32_t* off_host, ProbeArgs* out);
 int probe_layer(aigv_ctx* c, const ProbeArgs& plan, int li, bool cache, hipStream_t s);
+// the attention flow map of an armed prefill (probe.hip): map_plan refuses what the pass cannot carry, checks every index (aigv_attn_map_check) and builds the arguments ONCE per pass, in front of
+// its first launch; map_layer: the launch of layer li (nothing where the layer lies outside the window and no fold is asked for)
+int map_plan(aigv_ctx* c, const int32_t* cu, int B, int keep_kv, AttnMapArgs* out);
+int map_layer(aigv_ctx* c, const AttnMapArgs& plan, int li, hipStream_t s);
 // the row list of a stream capture / patch against a pass of T packed rows and L layers (passes.hip; aigv_op_stream_rows shares it): every row inside
 // [0, T), strictly ascending - so a patch's rows are unique - and the window 0 <= lo <= hi <= L
 int stream_rows_check(aigv_ctx* c, const char* op, const int32_t* rows, int n, int T, int lo, int hi, int L);

@@ -188,6 +188,30 @@ struct ProbeArgs {
 const char* aigv_probe_check(const ProbeArgs& a, int head_dim, int total_rows, int max_pos);
 hipError_t aigv_launch_attention_probe(const ProbeArgs& a, int head_dim, hipStream_t s);
 
+// ---- attention flow map (attnmap.hip) ----------------------------------------------------------------
+// Where EVERY query row of a causal GQA attention looks, on the matrix cores: rows[t][head][seg] = sum of softmax(q . K / post_div) over the
+// keys of segment seg, for all cu[n_seq] packed rows.  Packed layout only: q and K are the probe's packed operands (q UNROTATED, rotated by the
+// kernel at the row's position; K rotated), seg one id per packed row, an id outside [0, n_seg) counting for the total only.  Scores and
+// weights are fp32 whatever the pass's attention numerics.  seg_out (optional): the fold seg_out[b * seg_out_seq_stride + (head * n_seg + a) *
+// n_seg + c] = mean over the query rows of sequence b whose id is a of rows[.][head][c], NaN where a has no row.
+constexpr int AIGV_MAP_MAX_SEQS = 127;   // = AIGV_SMALL_INTS / 2 - 1: what one prefill call takes
+struct AttnMapArgs {
+  const bf16_t* q; int ldq;
+  const bf16_t* k; int ldk;
+  int n_heads, n_kv_heads;
+  int q_group_stride, kv_head_stride;
+  float post_div;                        // sqrt(D)
+  const bf16_t* rope_cos; const bf16_t* rope_sin;   // [max_pos, D/2], 16-byte aligned
+  const int32_t* seg; int n_seg;
+  float* rows;                           // [cu[n_seq]][n_heads][n_seg]
+  float* seg_out; size_t seg_out_seq_stride;
+  int n_seq;
+  int32_t cu[AIGV_MAP_MAX_SEQS + 1];     // by value: a kernel argument (no copy, no allocation)
+};
+// nullptr if every index the two kernels form stays inside its operand: max_pos = rows of the RoPE tables
+const char* aigv_attn_map_check(const AttnMapArgs& a, int head_dim, int max_pos);
+hipError_t aigv_launch_attention_map(const AttnMapArgs& a, int head_dim, hipStream_t s);
+
 // ---- row-wise / elementwise ---------------------------------------------------------------------
 // LayerNorm over rows of length H (fp32 statistics, bf16 out).
 hipError_t aigv_launch_layernorm(const bf16_t* x, int ldx, const bf16_t* w, const bf16_t* b, bf16_t* y, int ldy,
@@ -345,6 +369,7 @@ hipError_t aigv_launch_decode_eos(int64_t* tok, int32_t* state, int n, const int
 // small host int arrays passed by value as kernel arguments (no memcpy, no implicit host/stream sync)
 #define AIGV_SMALL_INTS 256
 struct SmallInts { int32_t v[AIGV_SMALL_INTS]; };
+static_assert(AIGV_MAP_MAX_SEQS == AIGV_SMALL_INTS / 2 - 1, "the attention map takes the sequences one prefill call takes");
 // pos[t] = t - cu[seq(t)] (+ pos_offset[seq(t)]), seq[t], and a device copy of cu[0..n_seq]; at most 127 sequences
 hipError_t aigv_launch_seqpos(const int32_t* cu_host, int n_seq, int32_t* pos, int32_t* seq, int32_t* cu_dev, int tokens,
                               hipStream_t s, const int32_t* pos_offset_host = nullptr);

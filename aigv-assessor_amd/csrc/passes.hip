@@ -499,6 +499,8 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
   const int n_lens = c->lens.armed ? c->lens.n_score + c->lens.n_token : 0;
   int32_t lens_at[2 * AIGV_MAX_LENS_ROWS];   // the lens rows' places among the consumed rows
   TRY(pass_options_check(c, T, keep_kv, score_rows, score ? B : 0, logit_rows, R, lens_at));
+  AttnMapArgs amap{};
+  if (c->amap.armed) TRY(map_plan(c, cu, B, keep_kv, &amap));   // (refusals: in front of the pass's first launch)
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)stream;
   const int H = k.llm_hidden, I = k.llm_inter, D = c->head_dim, g = c->g, nkv = k.llm_kv_heads;
@@ -574,6 +576,7 @@ int aigv_llm_prefill(aigv_ctx* c, const int64_t* ids, const int32_t* slot, const
       HIPCHK(c, aigv_launch_kv_store(c->l_qkv, c->qkv_out, c->l_seq, c->l_pos, c->kc + li * kv_layer, c->vc + li * kv_layer, T,
                                      nkv, g, D, k.kv_capacity, s));
     if (c->probe.armed) TRY(probe_layer(c, probe, li, false, s));   // Q and rotated K of this pass's rows, straight from l_qkv (every layer: it does not read l_ao)
+    if (c->amap.armed) TRY(map_layer(c, amap, li, s));              // every row of every head, from the same columns (the row-trimmed last layer included: Q and K exist for all T rows)
     // a pass that only fills the cache (no output rows) needs nothing of the last layer beyond its K/V
     if (n_out == 0 && c->trim_last_layer && li == k.llm_layers - 1) break;
     {
@@ -826,6 +829,7 @@ int aigv_llm_extend(aigv_ctx* c, const int64_t* ids, const int32_t* cu, int B, c
     if (const aigv_ctx::RowOptEntry* e = first_armed(c, family))
       return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: a %s %s is armed (%s): the continuation pass takes none, only aigv_llm_prefill does", family, e->what, e->arm);
   if (c->lens.armed) return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: the depth lens is armed (aigv_depth_lens_arm): the continuation pass takes no lens, only aigv_llm_prefill does");
+  if (c->amap.armed) return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: the attention map is armed (aigv_attention_map_arm): the continuation pass takes no map (it has no cache form), only aigv_llm_prefill does");
   if (c->drop.armed) return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: a key-drop mask is armed (aigv_key_drop_arm): the continuation pass takes no mask, only aigv_llm_prefill does");
   if (!c->kv_valid) return fail(c, AIGV_ERR_STATE, "aigv_llm_extend: no KV state (run aigv_llm_prefill with keep_kv)");
   if (c->probe.armed && c->kv_masked) return fail(c, AIGV_ERR_ARG, "aigv_llm_extend: the score-attention probe is armed and the KV cache carries a key-drop mask: the probe does not know the mask");

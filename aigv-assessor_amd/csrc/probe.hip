@@ -1,7 +1,8 @@
 // The score-row attention probe of the C ABI (include/aigv_amd.h): aigv_score_attention_arm / _arm_tokens / _arm_values, what an armed
 // aigv_llm_prefill / aigv_llm_extend launches per layer (probe_plan / probe_layer, called from passes.hip) and the context-free
-// aigv_op_attention_probe / _probe_tokens / _probe_values.
-// Host-side C++ only; the kernel is attnprobe.hip.
+// aigv_op_attention_probe / _probe_tokens / _probe_values - and its all-rows sibling, the attention flow map: aigv_attention_map_arm, what an armed
+// aigv_llm_prefill launches per layer (map_plan / map_layer) and the context-free aigv_op_attention_map.
+// Host-side C++ only; the kernels are attnprobe.hip and attnmap.hip.
 #include <cmath>
 
 #include "ctx.h"
@@ -77,9 +78,94 @@ int probe_layer(aigv_ctx* c, const ProbeArgs& plan, int li, bool cache, hipStrea
   return 0;
 }
 
+// ---- the attention flow map (attnmap.hip): every row of every head, per layer ---------------------------------------------------------
+static const char* fill_cu(AttnMapArgs& a, const int32_t* cu, int B) {
+  if (B < 1 || B > AIGV_MAP_MAX_SEQS) return "the number of sequences is outside 1..127";
+  a.n_seq = B;
+  for (int b = 0; b <= B; ++b) a.cu[b] = cu[b];
+  return nullptr;
+}
+
+int map_plan(aigv_ctx* c, const int32_t* cu, int B, int keep_kv, AttnMapArgs* out) {
+  const char* op = "aigv_llm_prefill";
+  const aigv_config& k = c->cfg;
+  const int D = c->head_dim, g = c->g;
+  const auto& mp = c->amap;
+  if (c->drop.armed) return fail(c, AIGV_ERR_ARG, "%s: a key-drop mask and the attention map are both armed: the map does not know the mask", op);
+  if (keep_kv) return fail(c, AIGV_ERR_ARG, "%s: keep_kv with the attention map armed: the map has no cache form, and a pass that keeps its KV is followed by continuations it cannot cover", op);
+  if (mp.n_seg < 1 || mp.n_seg > AIGV_MAX_ATTN_SEGMENTS) return fail(c, AIGV_ERR_ARG, "%s: attention map armed with %d segments, outside 1..%d", op, mp.n_seg, AIGV_MAX_ATTN_SEGMENTS);
+  if (!mp.seg) return fail(c, AIGV_ERR_ARG, "%s: attention map armed without a segment table", op);
+  if (!mp.seg_out && !mp.rows_out) return fail(c, AIGV_ERR_ARG, "%s: attention map armed without an output (seg_out and rows_out both NULL)", op);
+  if (mp.lo < 0 || mp.lo > mp.hi || mp.hi > k.llm_layers) return fail(c, AIGV_ERR_ARG, "%s: attention map rows armed for layers [%d, %d), outside 0 <= lo <= hi <= %d", op, mp.lo, mp.hi, k.llm_layers);
+  if (!mp.rows_out && mp.lo != mp.hi) return fail(c, AIGV_ERR_ARG, "%s: attention map armed with the layer window [%d, %d) and rows_out NULL", op, mp.lo, mp.hi);
+  if (mp.seg_out && !mp.scratch && mp.hi - mp.lo < k.llm_layers) return fail(c, AIGV_ERR_ARG, "%s: attention map armed with seg_out and without the per-layer scratch the layers outside [%d, %d) need", op, mp.lo, mp.hi);
+  AttnMapArgs a{};
+  a.q = c->l_qkv; a.ldq = c->qkv_out;
+  a.k = c->l_qkv + (size_t)g * D; a.ldk = c->qkv_out;
+  a.n_heads = k.llm_heads; a.n_kv_heads = k.llm_kv_heads;
+  a.q_group_stride = a.kv_head_stride = (g + 2) * D;
+  a.post_div = sqrtf((float)D);
+  a.rope_cos = c->rope_cos; a.rope_sin = c->rope_sin;
+  a.seg = mp.seg; a.n_seg = mp.n_seg;
+  a.rows = mp.scratch ? mp.scratch : mp.rows_out;   // (per layer: map_layer; here only so that the check sees an output)
+  a.seg_out = mp.seg_out; a.seg_out_seq_stride = (size_t)k.llm_layers * k.llm_heads * mp.n_seg * mp.n_seg;
+  if (const char* m = fill_cu(a, cu, B)) return fail(c, AIGV_ERR_ARG, "%s: attention map: %s", op, m);
+  if (const char* m = aigv_attn_map_check(a, D, k.max_positions)) return fail(c, AIGV_ERR_ARG, "%s: %s", op, m);
+  *out = a;
+  return 0;
+}
+
+int map_layer(aigv_ctx* c, const AttnMapArgs& plan, int li, hipStream_t s) {
+  const aigv_config& k = c->cfg;
+  const auto& mp = c->amap;
+  const bool in_window = mp.rows_out && li >= mp.lo && li < mp.hi;
+  if (!in_window && !mp.seg_out) return 0;   // nobody reads this layer's rows
+  AttnMapArgs a = plan;
+  const size_t layer_rows = (size_t)a.cu[a.n_seq] * k.llm_heads * a.n_seg;
+  a.rows = in_window ? mp.rows_out + (size_t)(li - mp.lo) * layer_rows : mp.scratch;
+  if (mp.seg_out) a.seg_out = mp.seg_out + (size_t)li * k.llm_heads * a.n_seg * a.n_seg;
+  // (checked by map_plan: only the two output addresses differ from layer to layer, and its refusals leave neither null where it is used)
+  HIPCHK(c, aigv_launch_attention_map(a, c->head_dim, s));
+  return 0;
+}
+
 }  // namespace aigv
 
 extern "C" {
+
+int aigv_attention_map_arm(aigv_ctx* c, const int32_t* seg_dev, int n_segments, float* scratch_dev, float* seg_out_dev, float* rows_out_dev, int layer_lo,
+                           int layer_hi) {
+  const char* op = "aigv_attention_map_arm";
+  if (!c) return fail(c, AIGV_ERR_ARG, "%s: null context", op);
+  if (!seg_dev) return fail(c, AIGV_ERR_ARG, "%s: null segment table", op);
+  if (!seg_out_dev && !rows_out_dev) return fail(c, AIGV_ERR_ARG, "%s: seg_out_dev and rows_out_dev are both null: nothing to report", op);
+  // limits (segments, the window, the scratch a fold needs) are refused by the PASS, with a message: it is what knows its layers and rows
+  auto& mp = c->amap;
+  mp.seg = seg_dev; mp.n_seg = n_segments; mp.scratch = scratch_dev; mp.seg_out = seg_out_dev; mp.rows_out = rows_out_dev;
+  mp.lo = layer_lo; mp.hi = layer_hi;
+  mp.armed = true;
+  return 0;
+}
+
+int aigv_op_attention_map(const void* q, int ldq, const void* k, int ldk, const int32_t* cu_host, int n_seq, int n_heads, int n_kv_heads, int q_group_stride,
+                          int kv_head_stride, int head_dim, const void* cos, const void* sin, int max_pos, const int32_t* seg, int n_segments, float* rows_out,
+                          float* seg_out, void* stream) {
+  const char* op = "aigv_op_attention_map";
+  if (!q || !k || !cu_host || !cos || !sin || !seg || !rows_out) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+  if (max_pos < 1) return fail(nullptr, AIGV_ERR_ARG, "%s: max_pos must be positive", op);
+  AttnMapArgs a{};
+  a.q = (const bf16_t*)q; a.ldq = ldq; a.k = (const bf16_t*)k; a.ldk = ldk;
+  a.n_heads = n_heads; a.n_kv_heads = n_kv_heads; a.q_group_stride = q_group_stride; a.kv_head_stride = kv_head_stride;
+  a.post_div = sqrtf((float)head_dim);
+  a.rope_cos = (const bf16_t*)cos; a.rope_sin = (const bf16_t*)sin;
+  a.seg = seg; a.n_seg = n_segments;
+  a.rows = rows_out;
+  a.seg_out = seg_out; a.seg_out_seq_stride = (size_t)(n_heads > 0 ? n_heads : 0) * (size_t)(n_segments > 0 ? n_segments : 0) * (size_t)(n_segments > 0 ? n_segments : 0);
+  if (const char* m = fill_cu(a, cu_host, n_seq)) return fail(nullptr, AIGV_ERR_ARG, "%s: %s", op, m);
+  if (const char* m = aigv_attn_map_check(a, head_dim, max_pos)) return fail(nullptr, AIGV_ERR_ARG, "%s: %s", op, m);
+  HIPCHK(nullptr, aigv_launch_attention_map(a, head_dim, (hipStream_t)stream));
+  return 0;
+}
 
 static int arm(aigv_ctx* c, const char* op, const int32_t* rows_host, int n_rows, const int32_t* seg_new_dev, const int32_t* seg_cached_dev, int ld_cached,
                int n_segments, float* out_dev, float* tok_out_dev, int ld_tok, float* val_out_dev = nullptr) {

@@ -171,6 +171,67 @@ def frame_heatmaps(tok_att, positions, layers=None):
     return (mass / mass.sum(-1, keepdim=True)).view(B, F, g, g).to(tok_att.dtype)
 
 
+def flow_segments(model, input_ids, attention_mask=None, image_flags=None):
+    """The table to pass as ``forward(attention_segments=..., return_segment_attention=True)`` for the question WHO READS WHOM (host only, no
+    GPU work): long [B, N] laid out like ``input_ids`` - the default bins (``prompts.attention_segments``: frame 0 .. F - 1 | motion token F |
+    first token F + 1 | text up to the last visual token F + 2 | text after it F + 3) with the SCORE ROW as a bin of its own, F + 4; S = F + 5.
+    -1 on the padding.  Built from ``model.unit_masks`` and ``model.segment_masks``; a stage-1 model has no score row and leaves bin F + 4 empty
+    (its rows of ``segment_attention`` are NaN)."""
+    import torch
+    units = model.unit_masks(input_ids, attention_mask, image_flags)          # [B, F + 1, N]: the frames, the motion token
+    groups = model.segment_masks(input_ids, attention_mask, image_flags)
+    F = units.shape[1] - 1
+    table = torch.full(tuple(units.shape[::2]), -1, dtype=torch.long)
+    for name, s in (("first", F + 1), ("text_before", F + 2), ("text_after", F + 3)):
+        table[groups[name]] = s
+    for u in range(F + 1):
+        table[units[:, u]] = u
+    table[groups["score_row"]] = F + 4
+    return table
+
+
+def _pick(t, dim, index, what):
+    import torch
+    if index is None:
+        return t
+    idx = torch.as_tensor(list(index), dtype=torch.long, device=t.device)
+    if idx.numel() == 0 or int(idx.min()) < 0 or int(idx.max()) >= t.shape[dim]:
+        raise ValueError(f"{what}: an index list inside 0..{t.shape[dim] - 1} with at least one entry, got {list(index)}")
+    return t.index_select(dim, idx)
+
+
+def segment_flow(seg_att, layers=None, heads=None):
+    """Who reads whom, in one matrix per clip: ``seg_att`` is ``forward(return_segment_attention=True)``'s ``segment_attention`` [B, L, n_heads,
+    S, S]; returns [B, S, S] - entry [a, c], the mass the rows of segment a put on the keys of segment c, averaged in float64 over ``layers`` and
+    ``heads`` (index lists; None: all).  The row of a segment the clip does not have stays NaN."""
+    if seg_att.dim() != 5 or seg_att.shape[-1] != seg_att.shape[-2]:
+        raise ValueError(f"segment_flow: expected [B, L, n_heads, S, S], got {tuple(seg_att.shape)}")
+    t = _pick(_pick(seg_att, 1, layers, "segment_flow: layers"), 2, heads, "segment_flow: heads")
+    return t.double().mean(dim=(1, 2)).to(seg_att.dtype)
+
+
+def attention_rollout(seg_att, alpha: float = 0.5, layers=None):
+    """Attention rollout over the segments (Abnar & Zuidema 2020): ``seg_att`` [B, L, n_heads, S, S] as above; returns [B, S, S] - the product
+    over depth, the deepest layer leftmost, of ``alpha I + (1 - alpha) A_l`` with A_l the head mean of layer l (``alpha``: the residual
+    connection's share, 0 <= alpha <= 1); entry [a, c] is how much of segment c's INPUT reaches the rows of segment a at the top through
+    attention and residual paths.  The row of a segment the clip does not have (NaN in ``seg_att``) is the identity's in every layer, so it stays
+    out of every other row.  ``layers``: an index list (multiplied in the order given, the last one leftmost); None: all layers.  float64
+    inside; alpha = 1 gives I exactly, alpha = 0 with permutation matrices gives their product exactly."""
+    import torch
+    if seg_att.dim() != 5 or seg_att.shape[-1] != seg_att.shape[-2]:
+        raise ValueError(f"attention_rollout: expected [B, L, n_heads, S, S], got {tuple(seg_att.shape)}")
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError(f"attention_rollout: alpha = {alpha!r} outside 0..1")
+    a = _pick(seg_att, 1, layers, "attention_rollout: layers").double().mean(2)              # [B, L', S, S]
+    eye = torch.eye(a.shape[-1], dtype=torch.float64, device=a.device)
+    empty = torch.isnan(a).any(-1, keepdim=True)
+    step = torch.where(empty, eye, float(alpha) * eye + (1.0 - float(alpha)) * torch.nan_to_num(a))
+    out = eye.expand(a.shape[0], -1, -1)
+    for l in range(a.shape[1]):
+        out = step[:, l] @ out
+    return out.to(seg_att.dtype)
+
+
 def source_writes(model, out, direction=None, layers=None):
     """WHAT the score row takes from each source: ``out`` is the result dict of ``forward(return_score_values=True)`` (or one of
     ``forward_shared_prefix``'s), whose ``score_values`` [B, L, n_heads, S, D] holds, per layer and head, the value-weighted sum the row read from

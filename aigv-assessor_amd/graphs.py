@@ -2,7 +2,6 @@
 from __future__ import annotations
 
 import os
-from dataclasses import replace
 
 import torch
 
@@ -175,7 +174,7 @@ class GraphReplay:
                 return self.forward(mos=None, pixel_values=None if visual_tokens is not None else src_static, input_ids=input_ids, attention_mask=attention_mask,
                                     image_flags=image_flags, labels=labels, motion_feature=mf_static, full_logits=full_logits,
                                     visual_tokens=src_static if visual_tokens is not None else None,
-                                    **readouts.forward_kwargs(replace(ro, cand=cand_static, segments=seg_static)))
+                                    **readouts.forward_kwargs(ro.with_(cand=cand_static, segments=seg_static)))      # (with_, not dataclasses.replace: it keeps ro.attention_map, which is no field)
             finally:
                 self._probe_n_segments = None
         return self._graph_call(host_key, [src, motion_feature, cand] + ([seg] if seg is not None else []), fn)   # (a user table only: the other keys stay what they were)

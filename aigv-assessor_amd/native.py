@@ -84,6 +84,8 @@ PROTOTYPES = {
     "aigv_score_attention_arm_values": (_I, [_P, _I32P, _I, _P, _P, _I, _I, _P, _P, _I, _P]),
     "aigv_op_attention_probe_values": (_I, [_P, _I, _P, _I, _I32P, _I, _I, _I, _I, _I, C.c_int64, _I32P, _I, _P, _P, _I, _I32P, _I, _P, _P, _I, _I, _P, _P, _I, _P, _I,
                                             _P, _P]),
+    "aigv_attention_map_arm": (_I, [_P, _P, _I, _P, _P, _P, _I, _I]),
+    "aigv_op_attention_map": (_I, [_P, _I, _P, _I, _I32P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _I, _P, _P, _P]),
     "aigv_kv_fork": (_I, [_P, _I, _P]),
     "aigv_kv_reorder": (_I, [_P, _P, _P, _I, _P]),
     "aigv_set_row_trimming": (_I, [_P, _I]),

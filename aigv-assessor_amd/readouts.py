@@ -4,7 +4,8 @@ score row's value vectors per segment (``return_score_values``), the depth lens,
 ``head_layers``) - and whether it runs under a key-drop mask (``key_drop`` with its qualifiers ``key_drop_rows`` / ``key_drop_layers``), a patch of the
 stream (``stream_patch``), a patch of head outputs (``head_patch``) or a per-head scale (``head_scale``): not read-outs, but per-call options that
 travel the same way.  The MLP's side of a layer has the same three: a capture of the neurons ``w2`` consumes (``return_neurons`` / ``neuron_layers`` /
-``neuron_ids``), a patch (``neuron_patch``) and a scale (``neuron_scale``).
+``neuron_ids``), a patch (``neuron_patch``) and a scale (``neuron_scale``).  The attention flow map of every query row (``return_segment_attention`` /
+``return_row_attention``) travels as ``ReadOuts.attention_map``, a plain attribute beside the fields.
 
 This module is the one place that knows that decision.  A new read-out adds, HERE: a member to ``ReadOuts`` and its check to
 ``ReadOuts.parse``; the element it appends to a graph's host key to ``ReadOuts.key_tail``; its keyword to ``forward_kwargs``; and - when it
@@ -20,7 +21,7 @@ paragraph.  ``touches_stream``, ``forward_kwargs``, ``ScoringPass.forward``'s ea
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Callable, NamedTuple, Optional
 
 import torch
@@ -29,6 +30,8 @@ MAX_CANDIDATES = 64      # = AIGV_MAX_CANDIDATES
 MAX_TOPK = 16            # = AIGV_MAX_TOPK
 MAX_LENS_ROWS = 64       # = AIGV_MAX_LENS_ROWS
 MAX_PROBE_ROWS = 64      # = AIGV_MAX_PROBE_ROWS
+MAX_ATTN_SEGMENTS = 64   # = AIGV_MAX_ATTN_SEGMENTS
+MAX_MAP_CLIPS = 127      # the attention map's sequence table: what one prefill call takes
 
 
 def top_logprobs_k(top_logprobs, vocab: int, labels="given") -> int:
@@ -119,6 +122,28 @@ def refuse_key_drop_qualifiers(where: str, key_drop_rows=None, key_drop_layers=N
         if v is not None:
             raise ValueError(f"{name}: {where} does not take it (the key-drop mask kept beside the KV cache has neither query rows nor a layer "
                              "window); forward() does")
+
+
+class AttentionMap(NamedTuple):
+    """``forward(return_segment_attention=..., return_row_attention=...)``, checked: the attention flow map of EVERY query row.  ``segments``: the
+    segment-to-segment matrix per layer and head is returned; ``rows``: None, or the layer window (lo, hi) whose per-row bins are returned."""
+    segments: bool
+    rows: Optional[tuple]
+
+
+def attention_map(return_segment_attention=False, return_row_attention=None, key_drop=None, n_layers: Optional[int] = None, ids_shape=None) -> Optional[AttentionMap]:
+    """``return_segment_attention`` / ``return_row_attention`` -> None (both off) or the checked ``AttentionMap``.  ValueError for a window
+    outside 0 <= lo <= hi <= L and for a call that also carries ``key_drop`` (the map recomputes the unmasked softmax: it does not know the
+    mask) - and, where ``ids_shape`` is known, for more than 127 clips (the kernels' sequence table).  The bin count (at most 64) is checked
+    where the table is counted (``ReadOuts.map_segments``)."""
+    if not return_segment_attention and return_row_attention is None:
+        return None
+    if key_drop is not None:
+        raise ValueError("key_drop: cannot be combined with return_segment_attention / return_row_attention (the map does not know the mask)")
+    window = None if return_row_attention is None else _depth_window("return_row_attention", return_row_attention, n_layers)
+    if ids_shape is not None and int(ids_shape[0]) > MAX_MAP_CLIPS:
+        raise ValueError(f"return_segment_attention / return_row_attention: at most {MAX_MAP_CLIPS} clips per pass, got {int(ids_shape[0])}")
+    return AttentionMap(bool(return_segment_attention), window)
 
 
 # ---- the row options: a capture, a patch and a scale of the rows a layer consumes, per family (FAMILIES below) -----------------------------------
@@ -437,6 +462,16 @@ class ReadOuts:
     head_layers: Optional[tuple] = None             # (lo, hi): ... at the layers lo <= l < hi (None with head_rows None)
     head_patch: Optional[HeadPatch] = None          # head outputs overwritten between the attention and wo of the layers of its window (forward only)
     head_scale: Optional[HeadScale] = None          # head outputs multiplied by a factor per (layer, head) (forward only)
+    # The attention flow map (return_segment_attention / return_row_attention; forward only): None or an ``AttentionMap``.  NOT a dataclass field - the
+    # field list is pinned from both ends (tests/test_head_patch_cpu.py: nothing follows head_scale; tests/test_option_parse_cpu.py: the families start at
+    # field 11) - so it is a plain attribute that ``parse`` sets on the record it returns; the constructor leaves it None.
+    attention_map = None
+
+    def with_(self, **changes) -> "ReadOuts":
+        """``dataclasses.replace`` that keeps ``attention_map``: ``replace`` rebuilds the record from its FIELDS alone and would drop it."""
+        ro = replace(self, **changes)
+        object.__setattr__(ro, "attention_map", self.attention_map)
+        return ro
 
     @classmethod
     def parse(cls, vocab: int, labels="given", *, return_logprobs: bool = False, candidate_ids=None, top_logprobs: Optional[int] = None,
@@ -444,17 +479,19 @@ class ReadOuts:
               ids_shape=None, key_drop_rows=None, key_drop_layers=None, n_layers: Optional[int] = None, return_depth_lens: bool = False,
               return_stream=None, stream_depths=None, stream_patch=None, return_heads=None, head_layers=None, head_patch=None, head_scale=None,
               n_heads: Optional[int] = None, head_dim: Optional[int] = None, return_neurons=None, neuron_layers=None, neuron_ids=None, neuron_patch=None,
-              neuron_scale=None, n_inter: Optional[int] = None, return_score_values: bool = False) -> "ReadOuts":
+              neuron_scale=None, n_inter: Optional[int] = None, return_score_values: bool = False, return_segment_attention: bool = False,
+              return_row_attention=None) -> "ReadOuts":
         """The record of a call's public keyword arguments, checked.  ``labels=None`` (``forward`` without labels) refuses candidates and top-k;
         the shared-prefix and generate entry points leave the default.  A user segment table is checked where its bins are counted
         (``n_segments``: it needs the shape of ``input_ids``).  Every check that needs no plan, in the order a call meets them: the clip count of
-        ``return_score_values``, the key-drop qualifiers, ``key_drop``, the stream, head and neuron families, ``candidate_ids``,
-        ``top_logprobs``, the clip count of ``return_depth_lens``."""
+        ``return_score_values``, the key-drop qualifiers, ``key_drop``, the attention map's window and its refusal of ``key_drop``, the stream, head
+        and neuron families, ``candidate_ids``, ``top_logprobs``, the clip count of ``return_depth_lens``."""
         att = bool(return_score_attention or return_token_attention or return_score_values)
         if return_score_values and ids_shape is not None and int(ids_shape[0]) > MAX_PROBE_ROWS:
             raise ValueError(f"return_score_values: at most {MAX_PROBE_ROWS} clips per pass, got {int(ids_shape[0])}")
         rows, window = key_drop_qualifiers(key_drop, key_drop_rows, key_drop_layers, ids_shape, n_layers)
         mask = key_drop_mask(key_drop, ids_shape, att)
+        amap = attention_map(return_segment_attention, return_row_attention, key_drop, n_layers, ids_shape)
         stream = stream_options(return_stream, stream_depths, stream_patch, ids_shape, n_layers)
         heads = head_options(return_heads, head_layers, head_patch, head_scale, ids_shape, n_layers, n_heads, head_dim)
         neurons = neuron_options(return_neurons, neuron_layers, neuron_ids, neuron_patch, neuron_scale, ids_shape, n_layers, n_inter)
@@ -462,8 +499,10 @@ class ReadOuts:
         k = top_logprobs_k(top_logprobs, vocab, labels)
         if return_depth_lens and ids_shape is not None and int(ids_shape[0]) > MAX_LENS_ROWS:
             raise ValueError(f"return_depth_lens: at most {MAX_LENS_ROWS} clips per pass, got {int(ids_shape[0])}")
-        return cls(bool(return_logprobs), cand, k or None, att, attention_segments if att else None, bool(return_token_attention), bool(return_score_values),
-                   mask, rows, window, bool(return_depth_lens), *neurons, *stream, *heads)
+        ro = cls(bool(return_logprobs), cand, k or None, att, attention_segments if att or amap else None, bool(return_token_attention), bool(return_score_values),
+                 mask, rows, window, bool(return_depth_lens), *neurons, *stream, *heads)
+        object.__setattr__(ro, "attention_map", amap)      # (frozen: the record is not rebound afterwards)
+        return ro
 
     @property
     def touches_stream(self) -> bool:
@@ -473,9 +512,9 @@ class ReadOuts:
 
     @property
     def runs_eagerly(self) -> bool:
-        """Under graph replay: a masked call, a call that touches the stream and a call that returns the score row's value vectors run eagerly and
-        capture nothing; every other call keeps the graph key it always had (``key_tail``)."""
-        return self.key_drop is not None or self.touches_stream or self.score_values
+        """Under graph replay: a masked call, a call that touches the stream, a call that returns the score row's value vectors and a call that returns
+        the attention map run eagerly and capture nothing; every other call keeps the graph key it always had (``key_tail``)."""
+        return self.key_drop is not None or self.touches_stream or self.score_values or self.attention_map is not None
 
     @property
     def wants_labels(self) -> bool:
@@ -492,12 +531,20 @@ class ReadOuts:
             raise ValueError(f"attention_segments: expected an integer tensor shaped like input_ids {tuple(ids_shape)}")
         return int(t.max()) + 1
 
+    def map_segments(self, ids_shape, default: int) -> int:
+        """S of the attention map: a user table's bin count, else ``default`` (the default table's, which the caller has from its plan) - checked
+        against the most bins a pass takes."""
+        S = self.n_segments(ids_shape) if self.segments is not None else int(default)
+        if not 1 <= S <= MAX_ATTN_SEGMENTS:
+            raise ValueError(f"return_segment_attention / return_row_attention: {S} segments, outside 1..{MAX_ATTN_SEGMENTS}")
+        return S
+
     def key_tail(self, ids_shape, n_seg: Optional[int] = None) -> tuple:
         """What the record appends to a graph's host key (``n_seg``: ``n_segments`` when the caller has it already).  Nothing for an option
         that is off: the keys of passes without it are those they always were.  The candidates' VALUES and a user segment table are graph
         INPUT, not key; the candidates' number is in the key with the device inputs' shapes.  k, a user table's bin count (the default
         table follows from the ids, which are in the key) and ld_tok = N are output shapes: another value is another graph.  ``key_drop`` and
-        the stream, head and neuron options add nothing: such calls are never captured - nor is one with ``score_values``."""
+        the stream, head and neuron options add nothing: such calls are never captured - nor is one with ``score_values`` or with the attention map."""
         S = (self.n_segments(ids_shape) if n_seg is None else n_seg) if self.score_attention else 0
         on = ((self.logprobs, "logprobs"), (self.cand is not None, "candidates"), (self.topk is not None, ("top_logprobs", self.topk)),
               (self.score_attention, ("score_attention", S)), (self.token_attention, ("score_attention_tokens", int(ids_shape[1]))),
@@ -518,6 +565,8 @@ def forward_kwargs(r: ReadOuts) -> dict:
     kw = dict(return_logprobs=r.logprobs or None, candidate_ids=r.cand, top_logprobs=r.topk, return_score_attention=r.score_attention or None,
               attention_segments=r.segments, return_token_attention=r.token_attention or None, return_score_values=r.score_values or None, key_drop=r.key_drop,
               key_drop_rows=r.key_drop_rows, key_drop_layers=r.key_drop_layers, return_depth_lens=r.depth_lens or None,
+              return_segment_attention=(r.attention_map is not None and r.attention_map.segments) or None,
+              return_row_attention=None if r.attention_map is None else r.attention_map.rows,
               **{k: getattr(r, f) for fam in FAMILIES for k, f in zip(fam.keywords, fam.fields)})
     return {k: v for k, v in kw.items() if v is not None}
 

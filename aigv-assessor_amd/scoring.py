@@ -184,7 +184,7 @@ class ScoringPass:
 
     def _prefill(self, ids_packed, slot, cu, vis, n_vis, motion, score_rows, logit_rows, keep_kv=False, kv_cap=0, probe=None, ld_tok=0, values=False, drop_words=None,
                  drop_row_words=None, drop_layers=None, lens=None, stream_capture=None, stream_patch=None, head_capture=None, head_patch=None,
-                 head_scale=None, neuron_capture=None, neuron_patch=None, neuron_scale=None):
+                 head_scale=None, neuron_capture=None, neuron_patch=None, neuron_scale=None, attention_map=None):
         b = len(cu) - 1
         T = cu[-1]
         lib, ctx = self._native(n_tokens=T, n_clips=b, out_rows=len(logit_rows), kv_cap=kv_cap)
@@ -207,6 +207,9 @@ class ScoringPass:
                 rows_d = up(drop_row_words, torch.int64) if drop_row_words is not None else None
                 lo, hi = drop_layers if drop_layers is not None else (0, self.config.llm_config.num_hidden_layers)
                 native.check(lib.aigv_key_drop_arm_ex(ctx, words_d.data_ptr(), native.ptr(rows_d), int(drop_words.shape[1]), int(lo), int(hi)), ctx)
+        if attention_map is not None:   # return_segment_attention / return_row_attention: (device int32 [T] table, S, scratch, seg_out, rows_out, lo, hi) - armed likewise
+            m_seg, m_S, m_scratch, m_fold, m_rows, m_lo, m_hi = attention_map
+            native.check(lib.aigv_attention_map_arm(ctx, m_seg.data_ptr(), int(m_S), native.ptr(m_scratch), native.ptr(m_fold), native.ptr(m_rows), int(m_lo), int(m_hi)), ctx)
         if lens is not None:            # return_depth_lens: (score rows, token rows, hidden, normed, score) - armed for exactly the pass below, which disarms
             l_score, l_token, l_hidden, l_normed, l_out = lens
             native.check(lib.aigv_depth_lens_arm(ctx, native.i32_array(l_score) if l_score else None, len(l_score), native.i32_array(l_token) if l_token else None,
@@ -290,6 +293,46 @@ class ScoringPass:
         if not 1 <= S <= self.MAX_ATTN_SEGMENTS:
             raise ValueError(f"return_score_attention: {S} segments, outside 1..{self.MAX_ATTN_SEGMENTS}")
         return rows, seg_d, None, 0, S
+
+    def _attention_map_table(self, plan, input_ids, ro):
+        """The attention map's table for this plan, on the HOST: (int32 [T] segment id per packed token, S).  ``ro.segments``: None -
+        ``prompts.attention_segments`` - or the user's table [B, N] (on any device), the probe's rules.  ValueError for more than 64 bins."""
+        if ro.segments is None:
+            seg, S = self._default_segments(plan)
+            return seg.to(torch.int32).contiguous(), ro.map_segments(input_ids.shape, S)
+        S = ro.map_segments(input_ids.shape, 0)
+        kept = (plan["row_of"] >= 0).flatten().nonzero().flatten()              # [b, p] of every packed row, in packed order (host)
+        return ro.segments.detach().to("cpu").flatten().index_select(0, kept).to(torch.int32).contiguous(), S
+
+    def _attention_map_buffers(self, plan, seg, S, amap):
+        """What ``_prefill`` arms the map with: (device table, S, scratch [T, n_heads, S] or None, seg_out [B, L, n_heads, S, S] or None, rows_out
+        [hi - lo, T, n_heads, S] or None, lo, hi), fp32 on the device."""
+        llm = self.config.llm_config
+        T, B, L, nh = plan["cu"][-1], len(plan["cu"]) - 1, llm.num_hidden_layers, llm.num_attention_heads
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
+        lo, hi = amap.rows if amap.rows is not None and amap.rows[0] < amap.rows[1] else (0, 0)
+        fold = new(B, L, nh, S, S) if amap.segments else None
+        return (self._h2d(seg), S, new(T, nh, S) if fold is not None and hi - lo < L else None, fold, new(hi - lo, T, nh, S) if hi > lo else None, lo, hi)
+
+    def _attention_map_outputs(self, plan, N, seg, armed, amap) -> dict:
+        """The map's entries of the result dict: ``segment_attention`` / ``segment_rows`` and ``row_attention`` (``forward``'s docstring)."""
+        _, S, _, fold, rows, lo, hi = armed
+        cu, out = plan["cu"], {}
+        B = len(cu) - 1
+        if amap.segments:
+            count = torch.zeros(B, S, dtype=torch.long)
+            for b in range(B):
+                mine = seg[cu[b]:cu[b + 1]].long()
+                count[b] = torch.bincount(mine[(mine >= 0) & (mine < S)], minlength=S)
+            out["segment_attention"], out["segment_rows"] = fold, self._h2d(count)
+        if amap.rows is not None:
+            nh = self.config.llm_config.num_attention_heads
+            full = torch.full((B, amap.rows[1] - amap.rows[0], nh, N, S), float("nan"), dtype=torch.float32, device=self.device)
+            if rows is not None:
+                for b in range(B):
+                    full[b, :, :, :cu[b + 1] - cu[b]] = rows[:, cu[b]:cu[b + 1]].permute(0, 2, 1, 3)
+            out["row_attention"] = full
+        return out
 
     def visual_token_positions(self, input_ids, attention_mask=None, image_flags=None, n_frames: Optional[int] = None) -> torch.Tensor:
         """``prompts.visual_token_positions`` of a batch as ``forward`` would pack it (host only, no GPU work): long [B, F, tokens_per_frame], the
@@ -522,7 +565,8 @@ class ScoringPass:
                 stream_depths: Optional[tuple] = None, stream_patch: Optional[readouts.StreamPatch] = None, return_heads: Optional[torch.Tensor] = None,
                 head_layers: Optional[tuple] = None, head_patch: Optional[readouts.HeadPatch] = None, head_scale: Optional[readouts.HeadScale] = None,
                 return_neurons: Optional[torch.Tensor] = None, neuron_layers: Optional[tuple] = None, neuron_ids: Optional[torch.Tensor] = None,
-                neuron_patch: Optional[readouts.NeuronPatch] = None, neuron_scale: Optional[readouts.NeuronScale] = None, return_score_values: bool = False):
+                neuron_patch: Optional[readouts.NeuronPatch] = None, neuron_scale: Optional[readouts.NeuronScale] = None, return_score_values: bool = False,
+                return_segment_attention: bool = False, return_row_attention: Optional[tuple] = None):
         """Stage-2 eval pass (modeling_internvl_chat.py:306-488) or, with ``stage=1``, the stage-1 pass
         (internvl_chat_eval1/modeling_internvl_chat.py:250-366).  ``visual_tokens`` optionally supplies
         already all-gathered pre-projector tokens (frame-DP) instead of ``pixel_values``.
@@ -577,6 +621,24 @@ class ScoringPass:
         [B, F] beside ``frame_saliency``.  ``score_attention``, ``score_attention_tokens`` and every other output keep their bits; combines
         with everything the probe combines with.  0 x Inf is NaN as in the attention itself: a non-finite V row makes its segment NaN.  At most
         64 clips; with graph replay enabled a call with the flag runs eagerly.
+
+        ``return_segment_attention`` / ``return_row_attention`` - WHO READS WHOM (the attention flow map): the same bins for EVERY query row of the
+        pass, not the score row alone, from a stand-alone MFMA kernel per layer that recomputes the causal softmax of all rows in fp32 from the
+        layer's Q and K.  One table per call, shared with the probe: ``attention_segments=`` or the default; ``eval_utils.flow_segments`` is the
+        default with the score row as a bin of its own (S = F + 5).  ``return_segment_attention=True`` adds ``segment_attention`` (fp32 [B, L,
+        n_heads, S, S]: entry [a, c] is the mean, over the clip's query rows of segment a, of the mass a row puts on the keys of segment c - the
+        rows added in ascending order in fp32, one division; a row of the matrix sums to 1 minus the mass on keys outside every bin; NaN where
+        the clip has no token of segment a) and ``segment_rows`` (int64 [B, S]: the clip's query rows per segment).
+        ``return_row_attention=(lo, hi)``, 0 <= lo <= hi <= L, adds ``row_attention`` (fp32 [B, hi - lo, n_heads, N, S]: the bins of every
+        token at the layers lo <= l < hi; column n is the clip's n-th un-masked token, as in ``score_attention_tokens``; NaN at padding
+        positions and at tokens the pass does not run) - B (hi - lo) n_heads N S 4 bytes, 14.5 MB per layer at the benched shape (4 clips of 8
+        frames, 32 heads, N = 2177, S = 13 with ``flow_segments``), 0.46 GB for all 32 layers: size the window accordingly.  At the score row ``row_attention`` is ``score_attention`` up to summation
+        order.  Under teacher forcing the rows of the answer tokens say which frames each answer token reads.  ``score_attention`` and every
+        other output keep their bits with the map armed.  ValueError, before anything is launched: together with ``key_drop`` (the map does not
+        know the mask), a window outside 0 <= lo <= hi <= L, more than 64 segments, more than 127 clips.  With graph replay enabled a call with either option runs
+        eagerly and captures nothing.  ``forward_shared_prefix``, ``generate*``, ``eval_utils.batched`` and ``score_clips_dp`` do not take the
+        options.  ``eval_utils.segment_flow`` folds the matrix over layers and heads, ``eval_utils.attention_rollout`` multiplies it through the
+        depth (Abnar & Zuidema 2020).
 
         ``key_drop`` (bool or integer tensor [B, N] laid out like ``input_ids``, on any device): WHAT IF these tokens were not there.  True
         hides that token, as a key, from every row of its clip in every layer; padded positions are ignored.  Every output - ``score1``,
@@ -692,6 +754,7 @@ class ScoringPass:
             return_depth_lens=return_depth_lens, return_stream=return_stream, stream_depths=stream_depths, stream_patch=stream_patch,
             return_heads=return_heads, head_layers=head_layers, head_patch=head_patch, head_scale=head_scale, return_neurons=return_neurons,
             neuron_layers=neuron_layers, neuron_ids=neuron_ids, neuron_patch=neuron_patch, neuron_scale=neuron_scale,
+            return_segment_attention=return_segment_attention, return_row_attention=return_row_attention,
             ids_shape=None if input_ids is None else input_ids.shape, n_layers=sizes["n_layers"], n_heads=sizes["n_heads"], head_dim=sizes["head_dim"],
             n_inter=sizes["n_inter"])
         drop_words = drop_row_words = None
@@ -709,6 +772,7 @@ class ScoringPass:
                 drop_words, drop_row_words = drop_words
         # ... a patch's counts and pairs, ...
         patched = {fam.patch: self._patch_plan(fam, host_plan(), getattr(ro, fam.patch)) for fam in readouts.FAMILIES if getattr(ro, fam.patch) is not None}
+        map_table = self._attention_map_table(host_plan(), input_ids, ro) if ro.attention_map is not None else None     # ... the map's bin count, ...
         if ro.depth_lens and self._capture_keep is None:      # ... and the lens: is there a row to read?  (inside a capture the call that led here has checked)
             self._depth_lens_rows(host_plan(), labels is not None)
         pixel_values, visual_tokens, motion_feature = self._take_ahead(pixel_values, visual_tokens, motion_feature)
@@ -733,6 +797,7 @@ class ScoringPass:
         vit_embeds, motion = self._visual_inputs(pixel_values, visual_tokens, motion_feature, plan)
         probe = self._score_attention_probe(plan, input_ids, ro) if ro.score_attention else None
         lens = None if lens_rows is None else self._depth_lens_buffers(lens_rows[0], lens_rows[2])
+        amap = None if map_table is None else self._attention_map_buffers(plan, *map_table, ro.attention_map)
         armed, captured = {}, []    # what ``_prefill`` arms the pass with, by its keyword; (result name, buffer, (clip, position) index) of every capture
         for fam in readouts.FAMILIES:
             mask, p, q = getattr(ro, fam.rows), patched.get(fam.patch), getattr(ro, fam.scale) if fam.scale else None
@@ -754,7 +819,8 @@ class ScoringPass:
                     armed[fam.scale] = (rows, *fam.scale_args(q))
         score, amax, *probed = self._prefill(plan["ids_packed"], plan["slot"], plan["cu"], vit_embeds, plan["n_vis"], motion,
                                              plan["score_rows"], plan["logit_rows"], probe=probe, ld_tok=N if ro.token_attention else 0, values=ro.score_values,
-                                             drop_words=drop_words, drop_row_words=drop_row_words, drop_layers=ro.key_drop_layers, lens=lens, **armed)
+                                             drop_words=drop_words, drop_row_words=drop_row_words, drop_layers=ro.key_drop_layers, lens=lens,
+                                             attention_map=amap if amap is not None and (amap[3] is not None or amap[4] is not None) else None, **armed)   # (an empty window alone arms nothing)
         att, tok, *val = probed or (None, None)  # (_prefill hands the probe's tensors back only when it armed one)
         reads = self._read_rows(B if score is not None else 0, len(plan["logit_rows"]), ro, lp_labels)
         out = self._outputs(plan, B, N, score, amax, mos, reads, att, tok, *val)
@@ -762,6 +828,8 @@ class ScoringPass:
             out.update(self._depth_lens_outputs(B, lens, lens_rows[1], ro, labels is not None))
         for name, buf, index in captured:
             out.update({name: buf, name + "_index": self._h2d(index)})
+        if amap is not None:
+            out.update(self._attention_map_outputs(plan, N, map_table[0], amap, ro.attention_map))
         return out
 
     def dp_front(self, frames_local: torch.Tensor, frames_clips: Optional[torch.Tensor], n_clips: int):

@@ -53,7 +53,8 @@ extern "C" {
                                 then by head knock-out and head patching (aigv_head_capture_arm, aigv_head_patch_arm, aigv_head_scale_arm,
                                 aigv_op_head_rows), then by MLP neuron knock-out and neuron patching (aigv_neuron_capture_arm,
                                 aigv_neuron_patch_arm, aigv_neuron_scale_arm, aigv_op_neuron_rows), then by the probe's value flow
-                                (aigv_score_attention_arm_values, aigv_op_attention_probe_values)
+                                (aigv_score_attention_arm_values, aigv_op_attention_probe_values), then by the attention flow map of
+                                every query row (aigv_attention_map_arm, aigv_op_attention_map)
                                 - added symbols only: a library without them is refused at load
                                 time, "missing <name>" */
 
@@ -214,6 +215,28 @@ int aigv_score_attention_arm_tokens(aigv_ctx* ctx, const int32_t* rows_host, int
  * the pass runs.  An unarmed pass, or one armed through the two functions above, launches exactly what it always launched. */
 int aigv_score_attention_arm_values(aigv_ctx* ctx, const int32_t* rows_host, int n_rows, const int32_t* seg_new_dev, const int32_t* seg_cached_dev,
                                     int ld_cached, int n_segments, float* out_dev, float* tok_out_dev, int ld_tok, float* val_out_dev);
+/* Attention flow map: where EVERY query row of the pass looks, per layer and head, folded into key segments - the observational sibling of the
+ * probe above, for all T packed rows instead of a few.  Arms exactly the next aigv_llm_prefill on this context, which launches a stand-alone
+ * MFMA kernel after the fused wqkv GEMM + RoPE of EVERY layer - a row-trimmed last layer included (it reads Q and K, which exist for all rows) -
+ * and disarms on every way out.  For the packed row t at position p of its clip and query head h:
+ *   rows[t][h][s] = (sum over the keys j <= p of the same clip with seg_dev[j] == s of e_j) / (sum over the keys j <= p of e_j),
+ *   e_j = expf(s_j - max_j s_j),  s_j = (q . k_j) / sqrt(head_dim) in fp32, q rotated with the RoPE kernel's own arithmetic.
+ * seg_dev: DEVICE int32 [T], read when the pass runs; an id outside [0, n_segments) counts for the total only.  1 <= n_segments <=
+ * AIGV_MAX_ATTN_SEGMENTS.  Outputs, fp32, DEVICE, the caller's, each optional (at least one):
+ *   rows_out_dev [layer_hi - layer_lo][T][n_heads][n_segments]: the rows of the layers layer_lo <= l < layer_hi (0 <= lo <= hi <= layers; pass
+ *     NULL with lo = hi); every element is written, nothing outside;
+ *   seg_out_dev [n_clips][layers][n_heads][n_segments][n_segments]: seg_out[b][l][h][a][c] = the mean over the query rows of clip b whose id is
+ *     a of rows[.][h][c] - the rows added in ascending order in fp32, ONE division by their number; NaN where clip b has no row of segment a.
+ * scratch_dev [T][n_heads][n_segments]: where the rows of a layer outside the window go in front of the fold; required with seg_out_dev unless
+ * the window covers every layer.  A layer whose rows nobody reads (outside the window, no seg_out_dev) launches nothing.
+ * Numerics: scores and weights are ALWAYS fp32, whatever aigv_set_attention_numerics says; the bf16 products of a score are exact, a bin is a
+ * chain of fp32 additions in an order fixed by the key index alone (no atomics), the last step is one fp32 division bin / total - a row's
+ * bits depend on its own keys, its position and the table, not on the other rows, the batch mates or the grid.  The existing kernels are not
+ * touched: armed or not, every other output of the pass keeps its bits.  Nothing is allocated.
+ * Refused by the pass, AIGV_ERR_ARG with a message, before it launches anything: an armed key-drop mask (the map does not know the mask),
+ * keep_kv, limits and a missing scratch.  aigv_llm_extend refuses an armed map (there is no cache form). */
+int aigv_attention_map_arm(aigv_ctx* ctx, const int32_t* seg_dev, int n_segments, float* scratch_dev, float* seg_out_dev, float* rows_out_dev,
+                           int layer_lo, int layer_hi);
 
 /* Key-drop mask: run the clips with some tokens HIDDEN from the LLM - what the reference computes for attention_mask zeros in the middle of a
  * sequence (positions stay as they are; the additive mask hides those keys from every query row).  Arms exactly the next aigv_llm_prefill on
@@ -623,6 +646,15 @@ int aigv_op_attention_probe_values(const void* q, int ldq, const void* k, int ld
                                    const void* cos, const void* sin, int max_pos, const int32_t* rows_host, int n_rows, const int32_t* seg_new,
                                    const int32_t* seg_cached, int ld_cached, int n_segments, float* out, float* tok_out, int ld_tok, const void* v, int ldv,
                                    float* val_out, void* stream);
+/* The attention flow map's two kernels on plain pointers, no context (tests): rows_out [cu_host[n_seq], n_heads, n_segments] as
+ * aigv_attention_map_arm defines one layer of rows_out_dev; seg_out (may be NULL) [n_seq, n_heads, n_segments, n_segments] the fold of those
+ * rows.  q / k / cos / sin / the strides: aigv_op_attention_probe's packed form (q UNROTATED fused rows, k rotated), seg: DEVICE int32
+ * [cu_host[n_seq]], 1 <= n_seq <= 127.  Refused on the host (AIGV_ERR_ARG with a message, nothing launched): a null operand, head_dim other
+ * than 64 / 128, n_segments outside 1..AIGV_MAX_ATTN_SEGMENTS, q / k / the tables not 16-byte aligned or strides that are no multiple of 8 or
+ * do not hold the rows, an empty sequence, a sequence longer than max_pos. */
+int aigv_op_attention_map(const void* q, int ldq, const void* k, int ldk, const int32_t* cu_host, int n_seq, int n_heads, int n_kv_heads,
+                          int q_group_stride, int kv_head_stride, int head_dim, const void* cos, const void* sin, int max_pos, const int32_t* seg,
+                          int n_segments, float* rows_out, float* seg_out, void* stream);
 /* The KV-cache append of the prefill and continuation passes: for token t, the K and V slots of every group of the fused row
  * qkv[t * ld ..] (groups of [g query heads | K | V]) are copied to kc / vc [seq][n_kv][cap][head_dim] at [seq[t]][kvh][pos[t]]; nothing else
  * is written.  seq / pos: DEVICE int32[tokens] (the caller's promise: seq[t] inside the cache, pos[t] < cap).  Checked on the host. */
