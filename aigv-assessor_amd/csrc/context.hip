@@ -99,6 +99,7 @@ static int alloc_workspaces(aigv_ctx* c) {
     if ((rc = dalloc(c, &c->v_ao, vr * k.vit_hidden))) break;
     if ((rc = dalloc(c, &c->v_h, vr * k.vit_inter))) break;
     if ((rc = dalloc(c, &c->v_cu, (size_t)k.vit_chunk + 1))) break;
+    if ((rc = dalloc(c, &c->v_mapstats, (size_t)k.vit_chunk * k.vit_heads * c->S))) break;   // (here, never inside a pass: aigv_vit_attention_arm)
     if ((rc = dalloc(c, &c->p_t, pr * c->proj_in))) break;
     if ((rc = dalloc(c, &c->p_mid, pr * k.llm_hidden))) break;
     if ((rc = dalloc(c, &c->l_h, T * k.llm_hidden))) break;

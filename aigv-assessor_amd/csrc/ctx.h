@@ -144,6 +144,14 @@ struct aigv_ctx {
     float* rows_out = nullptr;         // device, the caller's: [hi - lo][T][n_heads][n_seg], or nullptr
     int lo = 0, hi = 0;
   } amap;
+  // InternViT attention map (aigv_vit_attention_arm): armed for exactly the next aigv_vit_forward, which launches the map kernels (vitmap.hip) between the
+  // QK-norm and the flash attention of every layer lo <= li < hi - into out[absolute frame][li - lo] - and nothing for a layer outside the window
+  struct {
+    bool armed = false;
+    float* out = nullptr;              // device, the caller's: [n_frames][hi - lo][S][S], per_head: [n_frames][hi - lo][vit_heads][S][S]
+    int lo = 0, hi = 0, per_head = 0;
+  } vmap;
+  float2* v_mapstats = nullptr;        // [vit_chunk][vit_heads][S] (m, total) of the map's rows: owned by the context, nothing is allocated in the pass
   // key-drop mask (aigv_key_drop_arm / _ex): armed for exactly the next aigv_llm_prefill, which applies it in the attention of the layers
   // [layer_begin, layer_end) - every layer for aigv_key_drop_arm - to the query rows `rows` selects (null: every row); keep_kv, which takes
   // neither qualifier: and keeps it with the cache, kv_drop above

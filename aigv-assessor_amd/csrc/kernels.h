@@ -212,6 +212,29 @@ struct AttnMapArgs {
 const char* aigv_attn_map_check(const AttnMapArgs& a, int head_dim, int max_pos);
 hipError_t aigv_launch_attention_map(const AttnMapArgs& a, int head_dim, hipStream_t s);
 
+// ---- InternViT attention map (vitmap.hip) ------------------------------------------------------------
+// The full, non-causal softmax matrix of every query row of every frame, from the bf16 Q and K of a ViT layer's fused rows.  For frame f,
+// head h, query row i, key j, 0 <= i, j < S:
+//   acc_ij = the fp32 MFMA accumulation of the exact bf16 products q_i . k_j;  s_ij = acc_ij / sqrtf(D);  m_i = max_j s_ij;
+//   e_ij = expf(s_ij - m_i);  total_i = the fp32 sum of the e_ij, in an order fixed by the key index alone;  p_ij = e_ij / total_i
+// per head:  out[f * out_frame_stride + (h * S + i) * S + j] = p_ij
+// head mean: out[f * out_frame_stride + i * S + j] = (p0_ij + p1_ij + ... in ascending h, starting from +0.0) / n_heads, one fp32 division
+// Frames are n_seq runs of S consecutive rows; head h sits at column h * D of a row.  fp32 scores and weights whatever the pass's attention
+// numerics; the unscaled bf16 Q (no q_prescale rounding).  stats: [n_seq][n_heads][S] (m, total) pairs, written by the first kernel.
+constexpr int AIGV_VIT_MAP_MAX_HEADS = 64, AIGV_VIT_MAP_MAX_FRAMES = 65535, AIGV_VIT_MAP_MAX_ROWS = 32768;
+struct VitMapArgs {
+  const bf16_t* q; int ldq;
+  const bf16_t* k; int ldk;
+  int n_seq, S, n_heads;
+  float post_div;                        // sqrt(D)
+  float* out; size_t out_frame_stride;   // in floats
+  int per_head;
+  float2* stats;
+};
+// nullptr if every index the two kernels form stays inside its operand
+const char* aigv_vit_map_check(const VitMapArgs& a, int head_dim);
+hipError_t aigv_launch_vit_map(const VitMapArgs& a, int head_dim, hipStream_t s);
+
 // ---- row-wise / elementwise ---------------------------------------------------------------------
 // LayerNorm over rows of length H (fp32 statistics, bf16 out).
 hipError_t aigv_launch_layernorm(const bf16_t* x, int ldx, const bf16_t* w, const bf16_t* b, bf16_t* y, int ldy,

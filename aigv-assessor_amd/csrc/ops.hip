@@ -791,4 +791,20 @@ int aigv_op_frame_resize_ingest(const void* hwc_u8, int n_frames, int in_h, int 
   return 0;
 }
 
+// The InternViT attention map's two kernels on plain pointers, no context (tests; vitmap.hip).  Everything is checked before anything is launched.
+int aigv_op_vit_attention_map(const void* q, int ldq, const void* k, int ldk, int n_seq, int S, int n_heads, int head_dim, float* out, int per_head,
+                              void* stats_scratch, void* stream) {
+  const char* op = "aigv_op_vit_attention_map";
+  VitMapArgs a{};
+  a.q = (const bf16_t*)q; a.ldq = ldq; a.k = (const bf16_t*)k; a.ldk = ldk;
+  a.n_seq = n_seq; a.S = S; a.n_heads = n_heads;
+  a.post_div = sqrtf((float)(head_dim > 0 ? head_dim : 1));
+  a.out = out; a.per_head = per_head ? 1 : 0;
+  a.out_frame_stride = (size_t)(per_head ? std::max(n_heads, 0) : 1) * (size_t)std::max(S, 0) * (size_t)std::max(S, 0);
+  a.stats = (float2*)stats_scratch;
+  if (const char* m = aigv_vit_map_check(a, head_dim)) return fail(nullptr, AIGV_ERR_ARG, "%s: %s", op, m);
+  HIPCHK(nullptr, aigv_launch_vit_map(a, head_dim, (hipStream_t)stream));
+  return 0;
+}
+
 }  // extern "C"

@@ -32,8 +32,33 @@ static int vit_norm(aigv_ctx* c, const bf16_t* x, const bf16_t* w, const bf16_t*
   return 0;
 }
 
+// The InternViT attention map of an armed pass (aigv_vit_attention_arm; vitmap.hip): the arguments of layer li's launch for the chunk of F frames that
+// starts at frame f0.  Only the frame count and the output address differ from launch to launch.
+static VitMapArgs vit_map_args(const aigv_ctx* c, int f0, int F, int li) {
+  const aigv_config& k = c->cfg;
+  const auto& vm = c->vmap;
+  VitMapArgs a{};
+  a.q = c->v_qkv; a.k = c->v_qkv + k.vit_hidden; a.ldq = a.ldk = 3 * k.vit_hidden;
+  a.n_seq = F; a.S = c->S; a.n_heads = k.vit_heads;
+  a.post_div = sqrtf((float)c->vit_head_dim);
+  a.per_head = vm.per_head;
+  const size_t map_floats = (size_t)(vm.per_head ? k.vit_heads : 1) * c->S * c->S;
+  a.out_frame_stride = (size_t)(vm.hi - vm.lo) * map_floats;
+  a.out = vm.out + (size_t)f0 * a.out_frame_stride + (size_t)(li - vm.lo) * map_floats;
+  a.stats = c->v_mapstats;
+  return a;
+}
+
+struct VitDisarmScope {   // the aigv_vit_forward that finds the context armed disarms it on every way out
+  aigv_ctx* c;
+  explicit VitDisarmScope(aigv_ctx* c_) : c(c_) {}
+  ~VitDisarmScope() { c->vmap.armed = false; }
+};
+
 int aigv_vit_forward(aigv_ctx* c, const void* frames, int n_frames, void* out_tokens, void* stream) {
-  if (!c || !frames || !out_tokens) return fail(c, AIGV_ERR_ARG, "aigv_vit_forward: null argument");
+  if (!c) return fail(c, AIGV_ERR_ARG, "aigv_vit_forward: null argument");
+  VitDisarmScope disarm(c);
+  if (!frames || !out_tokens) return fail(c, AIGV_ERR_ARG, "aigv_vit_forward: null argument");
   if (!c->finalized) return fail(c, AIGV_ERR_STATE, "aigv_vit_forward: call aigv_finalize_weights first");
   const aigv_config& k = c->cfg;
   if (n_frames <= 0 || n_frames > k.max_frames) return fail(c, AIGV_ERR_ARG, "n_frames %d outside 1..%d", n_frames, k.max_frames);
@@ -45,6 +70,14 @@ int aigv_vit_forward(aigv_ctx* c, const void* frames, int n_frames, void* out_to
   int n_layers = k.vit_layers;
   if (k.select_layer != -1) n_layers = k.select_layer < 0 ? k.vit_layers + 1 + k.select_layer : k.select_layer;
   if (n_layers < 0 || n_layers > k.vit_layers) return fail(c, AIGV_ERR_ARG, "select_layer %d out of range", k.select_layer);
+  const bool mapped = c->vmap.armed;
+  if (mapped) {   // refused before anything is launched: the window against the layers THIS pass runs (select_layer's count), every index of the launches
+    const auto& vm = c->vmap;
+    if (vm.lo < 0 || vm.lo >= vm.hi || vm.hi > n_layers)
+      return fail(c, AIGV_ERR_ARG, "aigv_vit_forward: attention map armed for layers [%d, %d), outside 0 <= lo < hi <= %d, the layers the pass runs", vm.lo, vm.hi, n_layers);
+    if (!c->v_mapstats) return fail(c, AIGV_ERR_STATE, "aigv_vit_forward: attention map armed on a context without its stats scratch");
+    if (const char* m = aigv_vit_map_check(vit_map_args(c, 0, std::min(k.vit_chunk, n_frames), vm.lo), c->vit_head_dim)) return fail(c, AIGV_ERR_ARG, "aigv_vit_forward: %s", m);
+  }
   const size_t frame_elems = (size_t)k.num_channels * k.image_size * k.image_size;
   for (int f0 = 0; f0 < n_frames; f0 += k.vit_chunk) {
     const int F = std::min(k.vit_chunk, n_frames - f0);
@@ -77,6 +110,7 @@ int aigv_vit_forward(aigv_ctx* c, const void* frames, int n_frames, void* out_to
         HIPCHK(c, aigv_launch_rmsnorm(c->v_qkv, 3 * Hv, L.qn, c->v_qkv, 3 * Hv, rows, Hv, k.vit_eps, nullptr, s));
         HIPCHK(c, aigv_launch_rmsnorm(c->v_qkv + Hv, 3 * Hv, L.kn, c->v_qkv + Hv, 3 * Hv, rows, Hv, k.vit_eps, nullptr, s));
       }
+      if (mapped && li >= c->vmap.lo && li < c->vmap.hi) HIPCHK(c, aigv_launch_vit_map(vit_map_args(c, f0, F, li), c->vit_head_dim, s));   // (reads q and k; writes the caller's buffer and v_mapstats alone)
       {
         AttnArgs a{};
         a.q = c->v_qkv; a.k = c->v_qkv + Hv; a.v = c->v_qkv + 2 * Hv;
@@ -111,6 +145,18 @@ int aigv_vit_forward(aigv_ctx* c, const void* frames, int n_frames, void* out_to
     }
     HIPCHK(c, aigv_launch_pixel_shuffle(c->v_x, c->grid, Hv, (bf16_t*)out_tokens + (size_t)f0 * c->ntok * c->proj_in, F, s));
   }
+  return 0;
+}
+
+int aigv_vit_attention_arm(aigv_ctx* c, float* out_dev, int layer_lo, int layer_hi, int per_head) {
+  const char* op = "aigv_vit_attention_arm";
+  if (!c) return fail(c, AIGV_ERR_ARG, "%s: null context", op);
+  if (!out_dev) return fail(c, AIGV_ERR_ARG, "%s: null out_dev", op);
+  if ((uintptr_t)out_dev & 3) return fail(c, AIGV_ERR_ARG, "%s: out_dev must be 4-byte aligned", op);
+  // the window is refused by the PASS, with a message: it is what knows how many layers it runs (select_layer)
+  auto& vm = c->vmap;
+  vm.out = out_dev; vm.lo = layer_lo; vm.hi = layer_hi; vm.per_head = per_head ? 1 : 0;
+  vm.armed = true;
   return 0;
 }
 

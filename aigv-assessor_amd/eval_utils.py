@@ -232,6 +232,55 @@ def attention_rollout(seg_att, alpha: float = 0.5, layers=None):
     return out.to(seg_att.dtype)
 
 
+def vit_rollout(att, alpha: float = 0.5, layers=None):
+    """Attention rollout INSIDE the vision tower (Abnar & Zuidema 2020), per frame: ``att`` is ``model.vit_attention(pixel_values)``'s head-mean
+    ``vit_attention`` [F, L', S, S] (S = patches + 1, row / column 0 the cls token); returns [F, S, S] - the product over depth, the deepest layer
+    leftmost, of ``alpha I + (1 - alpha) A_l`` (``alpha``: the residual connection's share, 0 <= alpha <= 1); entry [i, j] is how much of patch
+    row j's INPUT reaches row i at the top of the tower through attention and residual paths.  ``layers``: an index list (multiplied in the
+    order given, the last one leftmost); None: all layers of ``att``.  float64 inside, one frame at a time (a frame's product is S x S doubles:
+    8.4 MB at S = 1025); alpha = 1 gives I exactly, alpha = 0 with permutation matrices gives their product exactly."""
+    import torch
+    if att.dim() != 4 or att.shape[-1] != att.shape[-2]:
+        raise ValueError(f"vit_rollout: expected the head-mean maps [F, L, S, S], got {tuple(att.shape)}")
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError(f"vit_rollout: alpha = {alpha!r} outside 0..1")
+    att = _pick(att, 1, layers, "vit_rollout: layers")
+    eye = torch.eye(att.shape[-1], dtype=torch.float64, device=att.device)
+    out = torch.empty(att.shape[0], att.shape[-1], att.shape[-1], dtype=att.dtype, device=att.device)
+    for f in range(att.shape[0]):
+        roll = eye
+        for l in range(att.shape[1]):
+            roll = (float(alpha) * eye + (1.0 - float(alpha)) * att[f, l].double()) @ roll
+        out[f] = roll.to(att.dtype)
+    return out
+
+
+def pixel_heatmaps(heat, rollout):
+    """From visual tokens back to the pixels: ``heat`` is ``frame_heatmaps``' [B, F, g, g] (the score row's mass per visual token), ``rollout``
+    is ``vit_rollout``'s [B * F, S, S] in clip-major frame order (frame f of clip b at index b * F + f), S = (2 g)^2 + 1; returns
+    ``(pix [B, F, 2g, 2g], cls [B, F])`` in float64 - one cell per ViT patch (14 x 14 pixels of a 448 x 448 frame: ``pix[b, f]`` lies over the
+    frame as an image does), and what lands on the cls token's input.
+
+    A visual token is the CONCATENATION of the four ViT patches of its cell (``frame_heatmaps``' geometry paragraph), so nothing says how its
+    heat divides among them.  The convention here is the EQUAL SPLIT: a quarter of cell (r, c)'s heat goes to each of the rollout rows
+    1 + 2g * y + x of its patches (y, x) in {2r, 2r + 1} x {2c, 2c + 1}; a row passes its share on along its rollout row - ``pix`` collects
+    the columns 1 .., patch (y, x) at column 1 + 2g * y + x, ``cls`` column 0.  Wherever the rollout's rows sum to 1,
+    ``pix.sum((2, 3)) + cls == heat.sum((2, 3))`` up to float64 rounding.  An identity rollout gives each cell's heat / 4 on its four patches
+    exactly; a permutation rollout moves those quarters exactly."""
+    import torch
+    if heat.dim() != 4 or heat.shape[-1] != heat.shape[-2] or rollout.dim() != 3 or rollout.shape[-1] != rollout.shape[-2]:
+        raise ValueError(f"pixel_heatmaps: expected [B, F, g, g] and [B * F, S, S], got {tuple(heat.shape)} and {tuple(rollout.shape)}")
+    B, F, g, _ = heat.shape
+    n = 2 * g
+    if rollout.shape[0] != B * F or rollout.shape[-1] != n * n + 1:
+        raise ValueError(f"pixel_heatmaps: heat [B = {B}, F = {F}, g = {g}] needs rollout [{B * F}, {n * n + 1}, {n * n + 1}], got {tuple(rollout.shape)}")
+    rows = (heat.double() / 4.0).repeat_interleave(2, 2).repeat_interleave(2, 3).reshape(B * F, 1, n * n)      # the weight of rollout row 1 + 2g y + x
+    out = torch.empty(B * F, n * n + 1, dtype=torch.float64, device=heat.device)
+    for i in range(B * F):                                                  # (a frame at a time: the float64 copy of one rollout matrix)
+        out[i] = (rows[i] @ rollout[i, 1:].to(heat.device).double())[0]
+    return out[:, 1:].reshape(B, F, n, n), out[:, 0].reshape(B, F)
+
+
 def source_writes(model, out, direction=None, layers=None):
     """WHAT the score row takes from each source: ``out`` is the result dict of ``forward(return_score_values=True)`` (or one of
     ``forward_shared_prefix``'s), whose ``score_values`` [B, L, n_heads, S, D] holds, per layer and head, the value-weighted sum the row read from

@@ -86,6 +86,8 @@ PROTOTYPES = {
                                             _P, _P]),
     "aigv_attention_map_arm": (_I, [_P, _P, _I, _P, _P, _P, _I, _I]),
     "aigv_op_attention_map": (_I, [_P, _I, _P, _I, _I32P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _I, _P, _P, _P]),
+    "aigv_vit_attention_arm": (_I, [_P, _P, _I, _I, _I]),
+    "aigv_op_vit_attention_map": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P]),
     "aigv_kv_fork": (_I, [_P, _I, _P]),
     "aigv_kv_reorder": (_I, [_P, _P, _P, _I, _P]),
     "aigv_set_row_trimming": (_I, [_P, _I]),

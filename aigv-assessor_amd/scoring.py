@@ -68,6 +68,54 @@ class ScoringPass:
         native.check(lib.aigv_vit_forward(ctx, pv.data_ptr(), nf, out.data_ptr(), native.stream_ptr()), ctx)
         return out
 
+    def vit_layers_run(self) -> int:
+        """The number of InternViT layers a pass runs: ``select_layer``'s count (-1: all of them), not ``num_hidden_layers``."""
+        n = self.config.vision_config.num_hidden_layers
+        sel = self.select_layer
+        return n if sel == -1 else n + 1 + sel if sel < 0 else sel
+
+    def vit_attention(self, pixel_values: torch.Tensor, layers=None, per_head: bool = False) -> dict:
+        """INSIDE the vision tower: the full, non-causal softmax matrix of every row of every frame, per layer - what the flash kernel never forms
+        (csrc/vitmap.hip; ``aigv_vit_attention_arm`` in include/aigv_amd.h defines the quantity: fp32 scores and weights whatever the attention
+        numerics, the unscaled bf16 Q - the flash kernel's bf16 ``q_prescale`` rounding is not reproduced).  Returns ``{"vit_attention": fp32
+        [F, hi - lo, S, S] - the head mean - or [F, hi - lo, n_heads, S, S] with ``per_head``, "tokens": the pass's pre-projector tokens, bit
+        for bit ``vit_tokens(pixel_values)``}``; S = patches + 1, row / column 0 the cls token, patch (y, x) at 1 + grid * y + x.
+        ``layers = (lo, hi)``: the window 0 <= lo < hi <= ``vit_layers_run()``; None: every layer the pass runs.  Runs eagerly on the current
+        stream (never inside a graph capture) after waiting for a prefetch in flight.  ValueError for a bad window and - with the byte count -
+        for a result that does not fit the device's free memory: F (hi - lo) S^2 4 bytes, times n_heads per head (3.2 GB for 32 frames x 24
+        layers at S = 1025, head mean).  ``eval_utils.vit_rollout`` / ``pixel_heatmaps`` carry a heat map through it to the pixels."""
+        if pixel_values.dim() != 4:
+            raise ValueError(f"wrong pixel_values size: {pixel_values.shape}")
+        v = self.config.vision_config
+        nf, size = pixel_values.shape[0], self.config.image_size
+        if nf < 1 or tuple(pixel_values.shape[1:]) != (v.num_channels, size, size):
+            raise ValueError(f"pixel_values must be [F,{v.num_channels},{size},{size}] with F >= 1, got {tuple(pixel_values.shape)}")
+        n_run = self.vit_layers_run()
+        try:
+            lo, hi = (0, n_run) if layers is None else (int(x) for x in layers)
+        except (TypeError, ValueError):
+            lo, hi = 0, 0
+        if not 0 <= lo < hi <= n_run:
+            raise ValueError(f"vit_attention: layers = {layers!r} is no window (lo, hi) with 0 <= lo < hi <= {n_run}, the layers the pass runs")
+        if self._capture_keep is not None or native._captures_underway > 0 or (self.device.type == "cuda" and torch.cuda.is_current_stream_capturing()):
+            raise RuntimeError("vit_attention runs eagerly: it cannot be part of a graph capture")
+        if self.device.type != "cuda":
+            raise native.NativeError("the scorer hot path runs on an MI355X only (no CPU fallback)")
+        S = (size // v.patch_size) ** 2 + 1
+        shape = (nf, hi - lo) + ((v.num_attention_heads,) if per_head else ()) + (S, S)
+        need = 4 * nf * (hi - lo) * (v.num_attention_heads if per_head else 1) * S * S
+        free = torch.cuda.mem_get_info(self.device)[0]
+        if need > free:      # (before the context grows for the frames: nothing is allocated for a refused call)
+            raise ValueError(f"vit_attention: the result {list(shape)} takes {need} bytes, the device has {free} free: narrow `layers` or pass fewer frames")
+        lib, ctx = self._native(n_frames=nf)
+        self._wait_for_prefetch()
+        pv = pixel_values.to(device=self.device, dtype=torch.bfloat16).contiguous()
+        tokens = torch.empty((nf, self.num_image_token, self.config.proj_in), dtype=torch.bfloat16, device=self.device)
+        att = torch.empty(shape, dtype=torch.float32, device=self.device)
+        native.check(lib.aigv_vit_attention_arm(ctx, att.data_ptr(), lo, hi, int(bool(per_head))), ctx)
+        native.check(lib.aigv_vit_forward(ctx, pv.data_ptr(), nf, tokens.data_ptr(), native.stream_ptr()), ctx)
+        return {"vit_attention": att, "tokens": tokens}
+
     def _take_ahead(self, pixel_values, visual_tokens, motion_feature):
         """``pixel_values`` may be the handle of a visual front started ahead of time (``prefetch``): wait for it on the caller's stream and continue
         from its tokens / SlowFast feature; a plain ``pixel_values`` first waits for any prefetch in flight (one visual front at a time)."""

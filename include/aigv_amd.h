@@ -54,7 +54,8 @@ extern "C" {
                                 aigv_op_head_rows), then by MLP neuron knock-out and neuron patching (aigv_neuron_capture_arm,
                                 aigv_neuron_patch_arm, aigv_neuron_scale_arm, aigv_op_neuron_rows), then by the probe's value flow
                                 (aigv_score_attention_arm_values, aigv_op_attention_probe_values), then by the attention flow map of
-                                every query row (aigv_attention_map_arm, aigv_op_attention_map)
+                                every query row (aigv_attention_map_arm, aigv_op_attention_map), then by the InternViT attention map
+                                (aigv_vit_attention_arm, aigv_op_vit_attention_map)
                                 - added symbols only: a library without them is refused at load
                                 time, "missing <name>" */
 
@@ -145,6 +146,29 @@ int aigv_finalize_weights(aigv_ctx* ctx);             /* checks that every tenso
  * modeling_internvl_chat.py:492-527).  frames: [F,3,S,S] bf16 NCHW.  out: [F*ntok, shuffle^2*vit_hidden] bf16
  * pre-projector tokens — the payload of the frame-DP all-gather. */
 int aigv_vit_forward(aigv_ctx* ctx, const void* frames, int n_frames, void* out_tokens, void* stream);
+/* InternViT attention map: the full, NON-causal softmax matrix of every query row of every frame, per layer - what the flash kernel never
+ * forms.  Arms exactly the next aigv_vit_forward on the context (that call disarms on every way out), which launches two stand-alone kernels
+ * between the QK-norm and the flash attention of every layer layer_lo <= l < layer_hi; a layer outside the window launches nothing.  They
+ * read the bf16 Q and K of the layer's fused qkv rows (after the full-width QK RMSNorm where the config has one) and write the caller's
+ * buffer and a stats scratch the context owns (sized at create / resize from vit_chunk: nothing is allocated in the pass) - nothing the pass
+ * reads afterwards: armed or not, out_tokens keeps its bits.
+ * Mapped quantity, for frame f, head h, query row i, key j, 0 <= i, j < S = patches + 1:
+ *   acc_ij  = the fp32 MFMA accumulation of the exact bf16 products q_i . k_j
+ *   s_ij    = acc_ij / sqrtf(D)
+ *   m_i     = max_j s_ij
+ *   e_ij    = expf(s_ij - m_i)
+ *   total_i = the fp32 sum of the e_ij, in an order fixed by the key index alone
+ *   p_ij    = e_ij / total_i
+ * per head (per_head != 0): out[f][l - layer_lo][h][i][j] = p_ij
+ * head mean (per_head == 0): out[f][l - layer_lo][i][j] = (p0_ij + p1_ij + ... in ascending h, starting from +0.0) / n_heads, one fp32 division
+ * Scores and weights are ALWAYS fp32, whatever aigv_set_attention_numerics says, and the UNSCALED bf16 Q is used: the flash kernel's bf16
+ * q_prescale rounding (exact only for D = 64) is not reproduced.  No atomics; a row's bits depend on its own frame's Q and K alone (not on
+ * the batch mates, the chunk or the window); keys past the frame's end never enter arithmetic.
+ * out_dev: the caller's fp32 device buffer [n_frames][layer_hi - layer_lo][S][S] (per_head: [n_frames][layer_hi - layer_lo][vit_heads][S][S]),
+ * indexed by the absolute frame number across vit_chunk chunks; every element is written and nothing outside is.
+ * Refused by the pass, AIGV_ERR_ARG with a message, before it launches anything: a window outside 0 <= layer_lo < layer_hi <= the number of
+ * layers the pass RUNS (select_layer's count, not vit_layers). */
+int aigv_vit_attention_arm(aigv_ctx* ctx, float* out_dev, int layer_lo, int layer_hi, int per_head);
 /* mlp1: LayerNorm -> Linear -> GELU -> Linear (modeling_internvl_chat.py:238-243,529). rows x proj_in -> rows x llm_hidden */
 int aigv_project(aigv_ctx* ctx, const void* tokens, int rows, void* out, void* stream);
 /* motion_mlp on the SlowFast feature (modeling_internvl_chat.py:244-249,345). [B, motion_dim] -> [B, llm_hidden] */
@@ -655,6 +679,14 @@ int aigv_op_attention_probe_values(const void* q, int ldq, const void* k, int ld
 int aigv_op_attention_map(const void* q, int ldq, const void* k, int ldk, const int32_t* cu_host, int n_seq, int n_heads, int n_kv_heads,
                           int q_group_stride, int kv_head_stride, int head_dim, const void* cos, const void* sin, int max_pos, const int32_t* seg,
                           int n_segments, float* rows_out, float* seg_out, void* stream);
+/* The InternViT attention map's two kernels on plain pointers, no context (tests): the quantity aigv_vit_attention_arm defines, for n_seq
+ * frames of S consecutive rows each; head h sits at column h * head_dim of a row of q (row stride ldq) and of k (ldk).  out: fp32
+ * [n_seq][S][S], per_head: [n_seq][n_heads][S][S].  stats_scratch: DEVICE, 8-byte aligned, n_seq * n_heads * S * 2 floats, overwritten.
+ * Refused on the host (AIGV_ERR_ARG with a message, nothing launched, nothing written): a null operand, head_dim other than 64 / 128, n_heads
+ * outside 1..64, n_seq outside 1..65535, S outside 1..32768, q / k not 16-byte aligned or row strides that are no multiple of 8 or do not
+ * hold n_heads * head_dim columns, a misaligned out / stats_scratch. */
+int aigv_op_vit_attention_map(const void* q, int ldq, const void* k, int ldk, int n_seq, int S, int n_heads, int head_dim, float* out,
+                              int per_head, void* stats_scratch, void* stream);
 /* The KV-cache append of the prefill and continuation passes: for token t, the K and V slots of every group of the fused row
  * qkv[t * ld ..] (groups of [g query heads | K | V]) are copied to kc / vc [seq][n_kv][cap][head_dim] at [seq[t]][kvh][pos[t]]; nothing else
  * is written.  seq / pos: DEVICE int32[tokens] (the caller's promise: seq[t] inside the cache, pos[t] < cap).  Checked on the host. */
