@@ -3,24 +3,20 @@
 // stand-alone kernel recomputes the softmax of all rows from the Q (unrotated) and K (rotated) that llm_layer_qkv leaves in the fused qkv rows
 // and touches nothing the pass itself reads afterwards.  Packed layout only.
 //
-// One wave per (32 query rows of ONE sequence, query head): query tile i of a sequence is its positions 32 i .. 32 i + 31, key tile kt its
-// keys 32 kt .. 32 kt + 31 - both counted from the sequence's first row, so a row's arithmetic is a function of its position, never of where
-// the sequence lies in the pack.  attention.hip's "key on the row, query on the lane":
-//   1. lane (r, hf) = (lane & 31, lane >> 5) loads the columns 16 s + 8 hf .. + 7 (s = 0 .. D / 16 - 1) of query row r and rotates them at the
-//      row's position with rope_pair (common.h) - both halves of a rotary pair lie on the same lane - the bf16 bits the probe and the flash
-//      kernel use.  These are the B fragments of every product below;
-//   2. S^T[key, q] = K . Q^T per key tile on v_mfma_f32_32x32x16_bf16 (bf16 products are exact; fp32 accumulation): accumulator register i of
-//      lane (r, hf) is the score of key 32 kt + rho(i, hf), rho = (i & 3) + 8 (i >> 2) + 4 hf, for query r.  A lane owns ONE query column;
-//   3. sweep 1 over the key tiles 0 .. i takes the maximum of the raw accumulators over the keys j <= p (the causal rule; a key behind the row,
-//      or past the sequence's end, is selected away and never enters arithmetic - NaN there is harmless), one lane ^ 32 exchange, then
-//      m = max / sqrt(D): division by a positive number is monotonic, so this IS max_j s_j with s_j = acc_j / sqrt(D);
-//   4. sweep 2 recomputes the same accumulators (the same instructions: the same bits), e_j = expf(acc_j / sqrt(D) - m), 0 for a key the row
-//      does not see; the lane adds its 16 e_j per tile to its total in register order, tile after tile;
-//   5. binning without rounding the weights and without atomics: bins^T[seg, q] += OneHot^T[seg, key] . P^T[key, q] on the fp32-input
+// One wave per (32 query rows of ONE sequence, query head), in the lane layout of qk_tiles.h (lane (r, hf), rho, the tile product, the two
+// sweeps): query tile i of a sequence is its positions 32 i .. 32 i + 31, key tile kt its keys 32 kt .. 32 kt + 31 - both counted from the
+// sequence's first row, so a row's arithmetic is a function of its position, never of where the sequence lies in the pack.
+//   1. lane (r, hf) loads its columns of query row r and rotates them at the row's position with rope_pair (common.h) - both halves of a rotary
+//      pair lie on the same lane - the bf16 bits the probe and the flash kernel use.  These are the B fragments of every product below;
+//   2. sweep 1 (qk_raw_max) over the key tiles 0 .. i takes the maximum of the raw accumulators over the keys j <= p (the causal rule; a key
+//      behind the row, or past the sequence's end, never enters arithmetic), then m = max / sqrt(D);
+//   3. sweep 2 (qk_weights) recomputes the same accumulators, e_j = expf(acc_j / sqrt(D) - m), 0 for a key the row does not see; the lane adds
+//      its 16 e_j per tile to its total in register order, tile after tile;
+//   4. binning without rounding the weights and without atomics: bins^T[seg, q] += OneHot^T[seg, key] . P^T[key, q] on the fp32-input
 //      v_mfma_f32_32x32x2_f32 - bit for bit a k-ordered fmaf chain, the factor exactly 1 or 0 - whose B operand IS accumulator register i
 //      (k = hf), the A operand the lane's own comparison seg[key rho(i, hf)] == r.  32 segments per pass, a second accumulator for 33 .. 64.
 //      The chain of one bin: key tiles ascending, inside a tile the keys 0, 4, 1, 5, 2, 6, 3, 7, 8, 12, ... (rho's order);
-//   6. total = the two lane halves' totals added (one lane ^ 32 exchange); rows[t][h][seg] = bin / total, ONE fp32 division.
+//   5. total = the two lane halves' totals added (one lane ^ 32 exchange); rows[t][h][seg] = bin / total, ONE fp32 division.
 // Key tiles behind the query tile are never visited.  Rows past the sequence's end inside its last tile are loaded from the sequence's last
 // row (a valid address) and never stored.  A row's bits depend on its own keys, its position and the segment table alone: nothing depends on
 // the batch mates, the grid or the row count - and integer-valued e_j (Q = 0: every e_j is 1) give exact counts.
@@ -30,21 +26,9 @@
 // 0 / 0 = NaN where the segment has no row.  No atomics.
 #include "common.h"
 #include "kernels.h"
+#include "qk_tiles.h"
 
 namespace {
-
-__device__ __forceinline__ int map_rho(int i, int hf) { return (i & 3) + 8 * (i >> 2) + 4 * hf; }
-
-template <int D>
-__device__ __forceinline__ f32x16 map_scores(const bf16_t* __restrict__ kp, const bf16x8* qf) {
-  f32x16 acc = {};
-#pragma unroll
-  for (int s = 0; s < D / 16; ++s) {
-    const bf16x8 a = *(const bf16x8*)(kp + 16 * s);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, qf[s], acc, 0, 0, 0);
-  }
-  return acc;
-}
 
 template <int D, int NP>
 __global__ __launch_bounds__(AIGV_WAVE) void attn_map_kernel(const AttnMapArgs p) {
@@ -82,15 +66,8 @@ __global__ __launch_bounds__(AIGV_WAVE) void attn_map_kernel(const AttnMapArgs p
     for (int s = 0; s < NS; ++s) qf[s] = __builtin_bit_cast(bf16x8, raw[s]);
   }
 
-  const bf16_t* kb = p.k + (size_t)row0 * p.ldk + (size_t)hk * p.kv_head_stride + 8 * hf;
-  const int n_kt = qt + 1;
-  float mx = -INFINITY;
-  for (int kt = 0; kt < n_kt; ++kt) {
-    const f32x16 acc = map_scores<D>(kb + (size_t)min(32 * kt + r, len - 1) * p.ldk, qf);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) mx = 32 * kt + map_rho(i, hf) <= qc ? fmaxf(mx, acc[i]) : mx;
-  }
-  mx = fmaxf(mx, __shfl_xor(mx, 32));
+  const QkSweep sw = {p.k + (size_t)row0 * p.ldk + (size_t)hk * p.kv_head_stride + 8 * hf, p.ldk, qt + 1, qc, len - 1, r, hf};
+  const float mx = qk_raw_max<D>(sw, qf);
   const float m = mx / p.post_div;
 
   f32x16 bins[NP];
@@ -98,18 +75,12 @@ __global__ __launch_bounds__(AIGV_WAVE) void attn_map_kernel(const AttnMapArgs p
   for (int q = 0; q < NP; ++q) bins[q] = f32x16{};
   float total = 0.0f;
   const int32_t* sg = p.seg + row0;
-  for (int kt = 0; kt < n_kt; ++kt) {
-    const f32x16 acc = map_scores<D>(kb + (size_t)min(32 * kt + r, len - 1) * p.ldk, qf);
+  qk_weights<D>(sw, qf, p.post_div, m, [&](int, int, int key, float e) {
+    const int id = sg[min(key, len - 1)];
+    total += e;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int key = 32 * kt + map_rho(i, hf);
-      const float e = key <= qc ? expf(acc[i] / p.post_div - m) : 0.0f;
-      const int id = sg[min(key, len - 1)];
-      total += e;
-#pragma unroll
-      for (int q = 0; q < NP; ++q) bins[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(id == r + 32 * q ? 1.0f : 0.0f, e, bins[q], 0, 0, 0);
-    }
-  }
+    for (int q = 0; q < NP; ++q) bins[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(id == r + 32 * q ? 1.0f : 0.0f, e, bins[q], 0, 0, 0);
+  });
   total += __shfl_xor(total, 32);
 
   if (qpos < len) {
@@ -118,7 +89,7 @@ __global__ __launch_bounds__(AIGV_WAVE) void attn_map_kernel(const AttnMapArgs p
     for (int q = 0; q < NP; ++q)
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const int s = 32 * q + map_rho(i, hf);
+        const int s = 32 * q + qk_rho(i, hf);
         if (s < S) out[s] = bins[q][i] / total;
       }
   }

@@ -20,8 +20,9 @@
 // The summation order is a function of the key index alone (no float atomics, nothing depends on the row count, the batch mates or the
 // grid), so a row's bits are its own - and integer-valued e_j (Q = 0: every e_j is 1) give exact counts.
 //
-// The VALUES form (attn_probe_values_kernel, a sibling that shares the device functions; the plain and dense instantiations above keep their
-// code) also reports WHAT the row takes from every segment: val[row][head][s][c] = (sum over the keys j of segment s of e_j v_j[c]) / total for
+// The VALUES form (the third template argument of the ONE kernel: steps 1 - 3, step 4's statement for key j, the bins' reduction, `out` and the
+// dense tail are the same source lines in every form; the plain and dense instantiations hold no barrier, LDS byte or loop of this form) also
+// reports WHAT the row takes from every segment: val[row][head][s][c] = (sum over the keys j of segment s of e_j v_j[c]) / total for
 // s = 0 .. S and c = 0 .. D - 1, slot S collecting the keys whose id lies outside [0, S) - so the S + 1 vectors sum to the head's output.  v_j
 // is the bf16 V row the pass's attention reads (packed: the V columns of the fused rows; cache: the V cache, with K's strides), kv head h / g.
 // The second sweep runs tile by tile, tile i = keys 256 i .. 256 i + 255, a trip count that is uniform over the workgroup:
@@ -60,200 +61,176 @@ constexpr int AIGV_PROBE_VALUES_MAX_LDS = 160 * 1024 - 2048;   // a CDNA4 CU's L
 // the four wave partials of one column of `red`, added in wave order: the last step of every bin's sum and of the total's
 __device__ __forceinline__ float waves_in_order(const float* r) { return ((r[0] + r[1]) + r[2]) + r[3]; }
 
-template <int D, bool DENSE>
-__global__ __launch_bounds__(LSE_THREADS) void attn_probe_kernel(const ProbeArgs p) {
-  extern __shared__ float bins[];                      // [n_seg + 1][256]: column = thread, row n_seg = the total
-  __shared__ float qs[D];
-  __shared__ float red[(AIGV_MAX_ATTN_SEGMENTS + 1) * (LSE_THREADS / AIGV_WAVE)];
-  const int tid = threadIdx.x, lane = tid % AIGV_WAVE, wave = tid / AIGV_WAVE;
-  const ProbeRow pr = p.tab.r[blockIdx.x];
-  const int h = blockIdx.y, g = p.n_heads / p.n_kv_heads, hk = h / g;
-  const int pos = pr.off + (pr.row - pr.row0), n_keys = pos + 1, S = p.n_seg;
+// step 1: q of head h rotated at pos, as fp32, into qs[D] (the first D / 2 threads; the caller's barrier publishes it)
+template <int D>
+__device__ __forceinline__ void probe_rotate_q(const ProbeArgs& p, const ProbeRow& pr, int h, int pos, float* qs) {
   constexpr int half = D / 2;
-
+  const int tid = threadIdx.x, g = p.n_heads / p.n_kv_heads;
   if (tid < half) {
-    const bf16_t* q = p.q + (size_t)pr.row * p.ldq + (size_t)hk * p.q_group_stride + (size_t)(h % g) * D;
+    const bf16_t* q = p.q + (size_t)pr.row * p.ldq + (size_t)(h / g) * p.q_group_stride + (size_t)(h % g) * D;
     const size_t tb = (size_t)pos * half + tid;
     bf16_t lo, hi;
     rope_pair(q[tid], q[tid + half], p.rope_cos[tb], p.rope_sin[tb], lo, hi);
     qs[tid] = bf2f(lo);
     qs[tid + half] = bf2f(hi);
   }
-  for (int s = 0; s <= S; ++s) bins[s * LSE_THREADS + tid] = 0.0f;
-  __syncthreads();
+}
 
-  // packed: the sequence's rows of the pass (row0 + j);  cache: [seq][kv head][cap][D], position j
-  const bf16_t* kb = p.k + (p.kv_seq_stride ? (size_t)pr.seq * p.kv_seq_stride : (size_t)pr.row0 * p.ldk) + (size_t)hk * p.kv_head_stride;
+// steps 2 and 3: the maximum of the row's scores, out of the log-probability kernels' tree
+template <int D>
+__device__ __forceinline__ float probe_row_max(const ProbeArgs& p, const float* qs, const bf16_t* kb, int n_keys) {
   float m = -INFINITY, sum = 0.0f;
-  for (int j = tid; j < n_keys; j += LSE_THREADS) lse_push(m, sum, probe_score<D>(qs, kb + (size_t)j * p.ldk, p.post_div));
+  for (int j = threadIdx.x; j < n_keys; j += LSE_THREADS) lse_push(m, sum, probe_score<D>(qs, kb + (size_t)j * p.ldk, p.post_div));
   float row_max = 0.0f;
   lse_of_block<false>(m, sum, &row_max);
-
-  float* tok = nullptr;                                // DENSE: the ld_tok columns of this (row, head)
-  if constexpr (DENSE) tok = p.tok + (size_t)blockIdx.x * p.tok_row_stride + (size_t)h * p.ld_tok;
-  for (int j = tid; j < n_keys; j += LSE_THREADS) {
-    const float e = expf(probe_score<D>(qs, kb + (size_t)j * p.ldk, p.post_div) - row_max);
-    const int sg = j < pr.off ? p.seg_cached[(size_t)pr.seq * p.ld_cached + j] : p.seg_new[pr.row0 + (j - pr.off)];
-    bins[S * LSE_THREADS + tid] += e;
-    if (sg >= 0 && sg < S) bins[sg * LSE_THREADS + tid] += e;
-    if constexpr (DENSE) tok[j] = e;
-  }
-  // every thread has written its own column only: no barrier in front of the butterflies
-  for (int s = 0; s <= S; ++s) {
-    const float v = wave_sum(bins[s * LSE_THREADS + tid]);
-    if (lane == 0) red[s * (LSE_THREADS / AIGV_WAVE) + wave] = v;
-  }
-  __syncthreads();
-  if (tid < S) {
-    const float total = waves_in_order(red + S * (LSE_THREADS / AIGV_WAVE));
-    const float bin = waves_in_order(red + tid * (LSE_THREADS / AIGV_WAVE));
-    p.out[(size_t)blockIdx.x * p.out_row_stride + (size_t)h * S + tid] = bin / total;
-  }
-  if constexpr (DENSE) {
-    const float total = waves_in_order(red + S * (LSE_THREADS / AIGV_WAVE));   // every thread: the bins' total, from the bins' statement of it
-    int j = tid;
-    for (; j < n_keys; j += LSE_THREADS) tok[j] = tok[j] / total;   // the thread's own stores of the second sweep
-    for (; j < p.ld_tok; j += LSE_THREADS) tok[j] = 0.0f;           // (the stride goes on behind the row: the 256 threads cover every column up to ld_tok)
-  }
+  return row_max;
 }
 
-// the thread's key j of the second sweep: e_j = exp(s_j - m), the step-4 statement both forms share
-template <int D>
-__device__ __forceinline__ float probe_weight(const float* qs, const bf16_t* kb, const ProbeArgs& p, int j, float row_max) {
-  return expf(probe_score<D>(qs, kb + (size_t)j * p.ldk, p.post_div) - row_max);
+// the segment id of key j: a cached key's from the sequence's row of seg_cached, a key of the pass from seg_new
+__device__ __forceinline__ int probe_segment(const ProbeArgs& p, const ProbeRow& pr, int j) {
+  return j < pr.off ? p.seg_cached[(size_t)pr.seq * p.ld_cached + j] : p.seg_new[pr.row0 + (j - pr.off)];
 }
 
-template <int D, bool DENSE>
-__global__ __launch_bounds__(LSE_THREADS) void attn_probe_values_kernel(const ProbeArgs p) {
-  constexpr int KL = LSE_THREADS / D;                  // key lanes
-  extern __shared__ float bins[];                      // [n_seg + 1][256] bins | [KL][n_seg + 1][D] accumulators | the tile: e [256], id [256]
+// step 5': the thread's own stores of the second sweep, divided; the stride goes on behind the row, so the 256 threads cover every column up to
+// ld_tok
+__device__ __forceinline__ void probe_dense_tail(float* tok, float total, int n_keys, int ld_tok) {
+  int j = threadIdx.x;
+  for (; j < n_keys; j += LSE_THREADS) tok[j] = tok[j] / total;
+  for (; j < ld_tok; j += LSE_THREADS) tok[j] = 0.0f;
+}
+
+template <int D, bool DENSE, bool VALUES>
+__global__ __launch_bounds__(LSE_THREADS) void attn_probe_kernel(const ProbeArgs p) {
+  constexpr int KL = LSE_THREADS / D;                  // VALUES: key lanes
+  extern __shared__ float bins[];                      // [n_seg + 1][256]: column = thread, row n_seg = the total
+                                                       // VALUES: | [KL][n_seg + 1][D] accumulators | the tile: e [256], id [256]
   __shared__ float qs[D];
   __shared__ float red[(AIGV_MAX_ATTN_SEGMENTS + 1) * (LSE_THREADS / AIGV_WAVE)];
   const int tid = threadIdx.x, lane = tid % AIGV_WAVE, wave = tid / AIGV_WAVE;
   const ProbeRow pr = p.tab.r[blockIdx.x];
-  const int h = blockIdx.y, g = p.n_heads / p.n_kv_heads, hk = h / g;
+  const int h = blockIdx.y, hk = h / (p.n_heads / p.n_kv_heads);
   const int pos = pr.off + (pr.row - pr.row0), n_keys = pos + 1, S = p.n_seg;
-  constexpr int half = D / 2;
   float* acc = bins + (S + 1) * LSE_THREADS;
   float* tile_e = acc + (S + 1) * LSE_THREADS;         // (KL * D = 256)
   int* tile_id = (int*)(tile_e + LSE_THREADS);
 
-  if (tid < half) {
-    const bf16_t* q = p.q + (size_t)pr.row * p.ldq + (size_t)hk * p.q_group_stride + (size_t)(h % g) * D;
-    const size_t tb = (size_t)pos * half + tid;
-    bf16_t lo, hi;
-    rope_pair(q[tid], q[tid + half], p.rope_cos[tb], p.rope_sin[tb], lo, hi);
-    qs[tid] = bf2f(lo);
-    qs[tid + half] = bf2f(hi);
-  }
+  probe_rotate_q<D>(p, pr, h, pos, qs);
   for (int s = 0; s <= S; ++s) {
     bins[s * LSE_THREADS + tid] = 0.0f;
-    acc[s * LSE_THREADS + tid] = 0.0f;                 // (every slot once: [kl][s][c] is kl * (S + 1) * D + s * D + c < (S + 1) * 256)
+    if constexpr (VALUES) acc[s * LSE_THREADS + tid] = 0.0f;   // (every slot once: [kl][s][c] is kl * (S + 1) * D + s * D + c < (S + 1) * 256)
   }
   __syncthreads();
 
+  // packed: the sequence's rows of the pass (row0 + j);  cache: [seq][kv head][cap][D], position j
   const size_t kv_base = (p.kv_seq_stride ? (size_t)pr.seq * p.kv_seq_stride : (size_t)pr.row0 * p.ldk) + (size_t)hk * p.kv_head_stride;
   const bf16_t* kb = p.k + kv_base;
-  const bf16_t* vb = p.v + (p.kv_seq_stride ? kv_base : (size_t)pr.row0 * p.ldv + (size_t)hk * p.kv_head_stride);
-  float m = -INFINITY, sum = 0.0f;
-  for (int j = tid; j < n_keys; j += LSE_THREADS) lse_push(m, sum, probe_score<D>(qs, kb + (size_t)j * p.ldk, p.post_div));
-  float row_max = 0.0f;
-  lse_of_block<false>(m, sum, &row_max);
+  const float row_max = probe_row_max<D>(p, qs, kb, n_keys);
 
-  float* tok = nullptr;
+  float* tok = nullptr;                                // DENSE: the ld_tok columns of this (row, head)
   if constexpr (DENSE) tok = p.tok + (size_t)blockIdx.x * p.tok_row_stride + (size_t)h * p.ld_tok;
-  const int kl = tid / D, c = tid % D;
-  float* my_acc = acc + (size_t)kl * (S + 1) * D + c;  // this thread's slots: my_acc[s * D]
-  int run = S;                                         // the running id and its accumulator (the slot holds +0.0 until the first exchange)
-  float run_acc = 0.0f;
-  const int n_tiles = (n_keys + LSE_THREADS - 1) / LSE_THREADS;
-  for (int i = 0; i < n_tiles; ++i) {
-    const int j = i * LSE_THREADS + tid;
-    if (j < n_keys) {
-      const float e = probe_weight<D>(qs, kb, p, j, row_max);
-      const int sg = j < pr.off ? p.seg_cached[(size_t)pr.seq * p.ld_cached + j] : p.seg_new[pr.row0 + (j - pr.off)];
-      bins[S * LSE_THREADS + tid] += e;
-      if (sg >= 0 && sg < S) bins[sg * LSE_THREADS + tid] += e;
-      if constexpr (DENSE) tok[j] = e;
-      tile_e[tid] = e;
-      tile_id[tid] = sg >= 0 && sg < S ? sg : S;
+  // step 4 for the thread's key j, the one statement of it: returns e_j, hands out the key's id
+  auto weigh = [&](int j, int& sg) {
+    const float e = expf(probe_score<D>(qs, kb + (size_t)j * p.ldk, p.post_div) - row_max);
+    sg = probe_segment(p, pr, j);
+    bins[S * LSE_THREADS + tid] += e;
+    if (sg >= 0 && sg < S) bins[sg * LSE_THREADS + tid] += e;
+    if constexpr (DENSE) tok[j] = e;
+    return e;
+  };
+  if constexpr (!VALUES) {
+    for (int j = tid; j < n_keys; j += LSE_THREADS) {
+      int sg;
+      weigh(j, sg);
     }
-    __syncthreads();
-    const int in_tile = min(LSE_THREADS, n_keys - i * LSE_THREADS);
-    const bf16_t* vt = vb + (size_t)i * LSE_THREADS * p.ldv + c;
-    constexpr int UN = 8;                              // V elements in flight per thread: the loads do not depend on the fma chain
-    int jj = kl;
-    for (; jj + (UN - 1) * KL < in_tile; jj += UN * KL) {
-      float v[UN];
+  } else {
+    const bf16_t* vb = p.v + (p.kv_seq_stride ? kv_base : (size_t)pr.row0 * p.ldv + (size_t)hk * p.kv_head_stride);
+    const int kl = tid / D, c = tid % D;
+    float* my_acc = acc + (size_t)kl * (S + 1) * D + c;  // this thread's slots: my_acc[s * D]
+    int run = S;                                       // the running id and its accumulator (the slot holds +0.0 until the first exchange)
+    float run_acc = 0.0f;
+    const int n_tiles = (n_keys + LSE_THREADS - 1) / LSE_THREADS;
+    for (int i = 0; i < n_tiles; ++i) {
+      const int j = i * LSE_THREADS + tid;
+      if (j < n_keys) {
+        int sg;
+        tile_e[tid] = weigh(j, sg);
+        tile_id[tid] = sg >= 0 && sg < S ? sg : S;
+      }
+      __syncthreads();
+      const int in_tile = min(LSE_THREADS, n_keys - i * LSE_THREADS);
+      const bf16_t* vt = vb + (size_t)i * LSE_THREADS * p.ldv + c;
+      constexpr int UN = 8;                            // V elements in flight per thread: the loads do not depend on the fma chain
+      int jj = kl;
+      for (; jj + (UN - 1) * KL < in_tile; jj += UN * KL) {
+        float v[UN];
 #pragma unroll
-      for (int u = 0; u < UN; ++u) v[u] = bf2f(vt[(size_t)(jj + u * KL) * p.ldv]);
+        for (int u = 0; u < UN; ++u) v[u] = bf2f(vt[(size_t)(jj + u * KL) * p.ldv]);
 #pragma unroll
-      for (int u = 0; u < UN; ++u) {
-        const int id = tile_id[jj + u * KL];
+        for (int u = 0; u < UN; ++u) {
+          const int id = tile_id[jj + u * KL];
+          if (id != run) {
+            my_acc[run * D] = run_acc;
+            run_acc = my_acc[id * D];
+            run = id;
+          }
+          run_acc = fmaf(tile_e[jj + u * KL], v[u], run_acc);
+        }
+      }
+      for (; jj < in_tile; jj += KL) {
+        const int id = tile_id[jj];
         if (id != run) {
           my_acc[run * D] = run_acc;
           run_acc = my_acc[id * D];
           run = id;
         }
-        run_acc = fmaf(tile_e[jj + u * KL], v[u], run_acc);
+        run_acc = fmaf(tile_e[jj], bf2f(vt[(size_t)jj * p.ldv]), run_acc);
       }
+      __syncthreads();                                 // the tile is rewritten by the next trip
     }
-    for (; jj < in_tile; jj += KL) {
-      const int id = tile_id[jj];
-      if (id != run) {
-        my_acc[run * D] = run_acc;
-        run_acc = my_acc[id * D];
-        run = id;
-      }
-      run_acc = fmaf(tile_e[jj], bf2f(vt[(size_t)jj * p.ldv]), run_acc);
-    }
-    __syncthreads();                                   // the tile is rewritten by the next trip
+    my_acc[run * D] = run_acc;
   }
-  my_acc[run * D] = run_acc;
-  // bins: every thread has written its own column only
+  // step 5.  Every thread has written its own column of `bins` only: no barrier in front of the butterflies.  (The reduction and the `out` store
+  // stand here and not in functions: handed `red` as a pointer argument, hipcc schedules the plain instantiations differently from the code they
+  // were - profiles/readout_kernels_refactor.txt.)
   for (int s = 0; s <= S; ++s) {
     const float v = wave_sum(bins[s * LSE_THREADS + tid]);
     if (lane == 0) red[s * (LSE_THREADS / AIGV_WAVE) + wave] = v;
   }
-  __syncthreads();                                     // (also: every accumulator slot is in LDS)
-  const float total = waves_in_order(red + S * (LSE_THREADS / AIGV_WAVE));
+  __syncthreads();                                     // (VALUES also: every accumulator slot is in LDS)
   if (tid < S) {
+    const float total = waves_in_order(red + S * (LSE_THREADS / AIGV_WAVE));
     const float bin = waves_in_order(red + tid * (LSE_THREADS / AIGV_WAVE));
     p.out[(size_t)blockIdx.x * p.out_row_stride + (size_t)h * S + tid] = bin / total;
   }
-  if constexpr (DENSE) {
-    int j = tid;
-    for (; j < n_keys; j += LSE_THREADS) tok[j] = tok[j] / total;
-    for (; j < p.ld_tok; j += LSE_THREADS) tok[j] = 0.0f;
-  }
-  float* val = p.val + (size_t)blockIdx.x * p.val_row_stride + (size_t)h * (S + 1) * D;
-  for (int x = tid; x < (S + 1) * D; x += LSE_THREADS) {   // x = s * D + c: coalesced
-    float a = acc[x];
+  // the bins' total, from the bins' statement of it: every form divides by these bits
+  if constexpr (DENSE) probe_dense_tail(tok, waves_in_order(red + S * (LSE_THREADS / AIGV_WAVE)), n_keys, p.ld_tok);
+  if constexpr (VALUES) {
+    const float total = waves_in_order(red + S * (LSE_THREADS / AIGV_WAVE));
+    float* val = p.val + (size_t)blockIdx.x * p.val_row_stride + (size_t)h * (S + 1) * D;
+    for (int x = tid; x < (S + 1) * D; x += LSE_THREADS) {   // x = s * D + c: coalesced
+      float a = acc[x];
 #pragma unroll
-    for (int l = 1; l < KL; ++l) a += acc[(size_t)l * (S + 1) * D + x];
-    val[x] = a / total;
+      for (int l = 1; l < KL; ++l) a += acc[(size_t)l * (S + 1) * D + x];
+      val[x] = a / total;
+    }
   }
 }
 
-// bins + accumulators + tile of the VALUES form, in bytes
-static constexpr int values_lds(int n_seg) { return (2 * (n_seg + 1) + 2) * LSE_THREADS * (int)sizeof(float); }
+// the dynamic LDS in bytes: the bins; VALUES: bins + accumulators + tile
+constexpr int probe_lds(bool values, int n_seg) { return (values ? 2 * (n_seg + 1) + 2 : n_seg + 1) * LSE_THREADS * (int)sizeof(float); }
 
-template <int D, bool DENSE>
-hipError_t launch_probe_values(const ProbeArgs& a, hipStream_t s) {
-  static LdsAttrOnce lds_attr;
-  if (hipError_t e = lds_attr.ensure((const void*)attn_probe_values_kernel<D, DENSE>, values_lds(AIGV_MAX_ATTN_SEGMENTS)); e != hipSuccess) return e;
-  hipLaunchKernelGGL((attn_probe_values_kernel<D, DENSE>), dim3(a.n_rows, a.n_heads), dim3(LSE_THREADS), values_lds(a.n_seg), s, a);
-  return hipGetLastError();
-}
-
-template <int D, bool DENSE>
+template <int D, bool DENSE, bool VALUES>
 hipError_t launch_probe(const ProbeArgs& a, hipStream_t s) {
   static LdsAttrOnce lds_attr;
-  constexpr int max_lds = (AIGV_MAX_ATTN_SEGMENTS + 1) * LSE_THREADS * (int)sizeof(float);
-  if (hipError_t e = lds_attr.ensure((const void*)attn_probe_kernel<D, DENSE>, max_lds); e != hipSuccess) return e;
-  const int lds = (a.n_seg + 1) * LSE_THREADS * (int)sizeof(float);
-  hipLaunchKernelGGL((attn_probe_kernel<D, DENSE>), dim3(a.n_rows, a.n_heads), dim3(LSE_THREADS), lds, s, a);
+  if (hipError_t e = lds_attr.ensure((const void*)attn_probe_kernel<D, DENSE, VALUES>, probe_lds(VALUES, AIGV_MAX_ATTN_SEGMENTS)); e != hipSuccess) return e;
+  hipLaunchKernelGGL((attn_probe_kernel<D, DENSE, VALUES>), dim3(a.n_rows, a.n_heads), dim3(LSE_THREADS), probe_lds(VALUES, a.n_seg), s, a);
   return hipGetLastError();
+}
+
+template <int D>
+hipError_t launch_probe_form(const ProbeArgs& a, hipStream_t s) {
+  if (a.val) return a.tok ? launch_probe<D, true, true>(a, s) : launch_probe<D, false, true>(a, s);
+  return a.tok ? launch_probe<D, true, false>(a, s) : launch_probe<D, false, false>(a, s);
 }
 
 }  // namespace
@@ -286,7 +263,7 @@ const char* aigv_probe_check(const ProbeArgs& a, int head_dim, int total_rows, i
     if (a.val_row_stride < (size_t)a.n_heads * (a.n_seg + 1) * head_dim) return "attention probe: val row stride below n_heads * (n_segments + 1) * head_dim";
     if (a.kv_seq_stride ? a.ldv != a.ldk : (int64_t)a.ldv < (int64_t)(a.n_kv_heads - 1) * a.kv_head_stride + head_dim)
       return a.kv_seq_stride ? "attention probe: the V cache takes K's strides (ldv = ldk)" : "attention probe: packed V strides too small";
-    if (values_lds(a.n_seg) > AIGV_PROBE_VALUES_MAX_LDS) return "attention probe: the values form's bins and accumulators do not fit the LDS";
+    if (probe_lds(true, a.n_seg) > AIGV_PROBE_VALUES_MAX_LDS) return "attention probe: the values form's bins and accumulators do not fit the LDS";
   }
   int cap = 0;
   if (a.kv_seq_stride) {   // cache layout [seq][kv head][cap][D]
@@ -309,12 +286,5 @@ const char* aigv_probe_check(const ProbeArgs& a, int head_dim, int total_rows, i
 }
 
 hipError_t aigv_launch_attention_probe(const ProbeArgs& a, int head_dim, hipStream_t s) {
-  if (a.val) {
-    if (head_dim == 128) return a.tok ? launch_probe_values<128, true>(a, s) : launch_probe_values<128, false>(a, s);
-    if (head_dim == 64) return a.tok ? launch_probe_values<64, true>(a, s) : launch_probe_values<64, false>(a, s);
-    return hipErrorInvalidValue;
-  }
-  if (head_dim == 128) return a.tok ? launch_probe<128, true>(a, s) : launch_probe<128, false>(a, s);
-  if (head_dim == 64) return a.tok ? launch_probe<64, true>(a, s) : launch_probe<64, false>(a, s);
-  return hipErrorInvalidValue;
+  return head_dim == 128 ? launch_probe_form<128>(a, s) : head_dim == 64 ? launch_probe_form<64>(a, s) : hipErrorInvalidValue;
 }

@@ -15,15 +15,12 @@
 // Scores and weights are fp32 whatever aigv_set_attention_numerics says, and the UNSCALED bf16 Q is used: the flash kernel's bf16 q_prescale
 // rounding (exact only for D = 64) is not reproduced.
 //
-// Both kernels are attnmap.hip's "key on the row, query on the lane": lane (r, hf) = (lane & 31, lane >> 5) holds the columns 16 s + 8 hf .. + 7
-// of query row 32 qt + r as the B fragments, the key tile's rows are the A fragments of v_mfma_f32_32x32x16_bf16, and accumulator register i of
-// the lane is the score of key 32 kt + rho(i, hf), rho = (i & 3) + 8 (i >> 2) + 4 hf, for the lane's query.
-//   stats kernel, one wave per (32 query rows, head, frame): sweep 1 over ALL key tiles takes the maximum of the raw accumulators over the keys
-//     j < S (a key past the frame's end inside the last tile is selected away and never enters arithmetic - NaN there is harmless), one
-//     lane ^ 32 exchange, m = max / sqrt(D) (division by a positive number is monotonic: this IS max_j s_ij).  Sweep 2 recomputes the same
-//     accumulators (the same instructions: the same bits) and adds the lane's 16 e_ij per tile in register order, tile after tile; the two
-//     lane halves' totals are added (one exchange).  The order of total_i's chain: lane half hf adds, key tiles ascending, the keys
-//     rho(0, hf), rho(1, hf), ... of each tile; then half 0 + half 1.  (m_i, total_i) go to stats[f][h][i].
+// Both kernels use the lane layout of qk_tiles.h (lane (r, hf), rho, the tile product, the two sweeps); the bf16 Q is loaded as it stands.
+//   stats kernel, one wave per (32 query rows, head, frame): sweep 1 (qk_raw_max) over ALL key tiles takes the maximum of the raw accumulators
+//     over the keys j < S (a key past the frame's end inside the last tile never enters arithmetic), m = max / sqrt(D).  Sweep 2 (qk_weights)
+//     recomputes the same accumulators and adds the lane's 16 e_ij per tile in register order, tile after tile; the two lane halves' totals
+//     are added (one exchange).  The order of total_i's chain: lane half hf adds, key tiles ascending, the keys rho(0, hf), rho(1, hf), ... of
+//     each tile; then half 0 + half 1.  (m_i, total_i) go to stats[f][h][i].
 //   write kernel, one wave per (query tile, key tile, frame): for h = 0, 1, ... it recomputes the 32 x 32 accumulator tile (again the same
 //     instructions), forms p_ij = expf(acc_ij / sqrt(D) - m_i) / total_i and either stores it or adds it to the head mean kept in registers,
 //     which is divided once at the end.  The tile crosses the lanes through LDS so that a store instruction writes 32 consecutive keys of
@@ -33,26 +30,14 @@
 // integer-valued e_ij (Q = 0: every e_ij is 1) give total_i = S exactly.  Every offset into the output is 64-bit.
 #include "common.h"
 #include "kernels.h"
+#include "qk_tiles.h"
 
 namespace {
-
-__device__ __forceinline__ int vm_rho(int i, int hf) { return (i & 3) + 8 * (i >> 2) + 4 * hf; }
 
 template <int D>
 __device__ __forceinline__ void vm_load_q(const bf16_t* __restrict__ qp, bf16x8* qf) {
 #pragma unroll
   for (int s = 0; s < D / 16; ++s) qf[s] = *(const bf16x8*)(qp + 16 * s);
-}
-
-template <int D>
-__device__ __forceinline__ f32x16 vm_scores(const bf16_t* __restrict__ kp, const bf16x8* qf) {
-  f32x16 acc = {};
-#pragma unroll
-  for (int s = 0; s < D / 16; ++s) {
-    const bf16x8 a = *(const bf16x8*)(kp + 16 * s);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, qf[s], acc, 0, 0, 0);
-  }
-  return acc;
 }
 
 template <int D>
@@ -63,24 +48,12 @@ __global__ __launch_bounds__(AIGV_WAVE) void vit_map_stats_kernel(const VitMapAr
   const size_t row0 = (size_t)f * S;
   bf16x8 qf[D / 16];
   vm_load_q<D>(p.q + (row0 + qc) * p.ldq + (size_t)h * D + 8 * hf, qf);
-  const bf16_t* kb = p.k + row0 * p.ldk + (size_t)h * D + 8 * hf;
-  const int n_kt = (S + 31) >> 5;
-
-  float mx = -INFINITY;
-  for (int kt = 0; kt < n_kt; ++kt) {
-    const f32x16 acc = vm_scores<D>(kb + (size_t)min(32 * kt + r, S - 1) * p.ldk, qf);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) mx = 32 * kt + vm_rho(i, hf) < S ? fmaxf(mx, acc[i]) : mx;
-  }
-  mx = fmaxf(mx, __shfl_xor(mx, 32));
+  const QkSweep sw = {p.k + row0 * p.ldk + (size_t)h * D + 8 * hf, p.ldk, (S + 31) >> 5, S - 1, S - 1, r, hf};
+  const float mx = qk_raw_max<D>(sw, qf);
   const float m = mx / p.post_div;
 
   float total = 0.0f;
-  for (int kt = 0; kt < n_kt; ++kt) {
-    const f32x16 acc = vm_scores<D>(kb + (size_t)min(32 * kt + r, S - 1) * p.ldk, qf);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) total += 32 * kt + vm_rho(i, hf) < S ? expf(acc[i] / p.post_div - m) : 0.0f;
-  }
+  qk_weights<D>(sw, qf, p.post_div, m, [&](int, int, int, float e) { total += e; });
   total += __shfl_xor(total, 32);
   if (hf == 0 && qpos < S) p.stats[((size_t)f * p.n_heads + h) * S + qpos] = make_float2(m, total);
 }
@@ -100,7 +73,7 @@ __global__ __launch_bounds__(AIGV_WAVE) void vit_map_write_kernel(const VitMapAr
 
   auto store = [&](const f32x16& v, float* base) {     // base: element [query 0][key 0] of the S x S matrix
 #pragma unroll
-    for (int i = 0; i < 16; ++i) tile[r][vm_rho(i, hf)] = v[i];
+    for (int i = 0; i < 16; ++i) tile[r][qk_rho(i, hf)] = v[i];
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
@@ -114,7 +87,7 @@ __global__ __launch_bounds__(AIGV_WAVE) void vit_map_write_kernel(const VitMapAr
   for (int h = 0; h < p.n_heads; ++h) {
     bf16x8 qf[D / 16];
     vm_load_q<D>(qp + (size_t)h * D, qf);
-    const f32x16 acc = vm_scores<D>(kp + (size_t)h * D, qf);
+    const f32x16 acc = qk_scores<D>(kp + (size_t)h * D, qf);
     const float2 mt = st[(size_t)h * S];
     f32x16 pr;
 #pragma unroll

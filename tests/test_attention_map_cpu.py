@@ -41,7 +41,9 @@ def test_abi_header_prototypes_exports_and_host_refusals():
     for phrase in ("ALWAYS fp32", "one fp32 division", "no atomics", "does not know the mask", "keep_kv", "NaN where clip b has no row"):
         assert phrase in doc, phrase
     kernel = open(os.path.join(build.CSRC, "attnmap.hip")).read()
-    assert "__builtin_amdgcn_mfma_f32_32x32x16_bf16" in kernel and "__builtin_amdgcn_mfma_f32_32x32x2f32" in kernel and "atomic" not in kernel.split('#include "kernels.h"')[1]
+    tiles = open(os.path.join(build.CSRC, "qk_tiles.h")).read()                                             # the score tiles' product: shared with vitmap.hip
+    assert '#include "qk_tiles.h"' in kernel and "qk_tiles.h" in build.HEADERS and "__builtin_amdgcn_mfma_f32_32x32x16_bf16" in tiles
+    assert "__builtin_amdgcn_mfma_f32_32x32x2f32" in kernel and "atomic" not in kernel.split('#include "kernels.h"')[1] and "atomic" not in tiles.split("#pragma once")[1]
     # host refusals: before any pointer is used (a small aligned HOST buffer stands for every operand; no accepted call is made)
     buf = (ctypes.c_char * 64)()
     p = ctypes.addressof(buf)

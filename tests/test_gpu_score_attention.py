@@ -37,22 +37,22 @@ def tables():
     return cos.cuda(), sin.cuda()
 
 
-def probe(lib, fused_d, g, rows, seg_new_d, lens=R.LENS, cache=None, n_seg=S, cos_sin=None):
-    """aigv_op_attention_probe on fused rows [T, HK (g + 2) D]; cache = (kc, cap, kv_off list, seg_cached_d, ld_cached) for the cache form.
+def probe(lib, fused_d, g, rows, seg_new_d, lens=R.LENS, cache=None, n_seg=S, cos_sin=None, d=D):
+    """aigv_op_attention_probe on fused rows [T, HK (g + 2) d]; cache = (kc, cap, kv_off list, seg_cached_d, ld_cached) for the cache form.
     `out` sits between two sentinel pads inside one allocation that starts as the sentinel: returns fp32 [rows, heads, n_seg] after checking
     that the pads kept their bits and that every element of `out` was written."""
-    h, ld = HK * g, HK * (g + 2) * D
+    h, ld = HK * g, HK * (g + 2) * d
     n = len(rows) * h * n_seg
     whole = torch.full((PAD + n + PAD,), SENTINEL, dtype=torch.int32, device="cuda")
     out_ptr = whole.data_ptr() + 4 * PAD
     cos, sin = cos_sin or tables()
     cu = native.i32_array(R.cu_of(lens))
     if cache is None:
-        k_ptr, ldk, hs, ss, off, segc, ldc = fused_d.data_ptr() + 2 * g * D, ld, (g + 2) * D, 0, None, None, 0
+        k_ptr, ldk, hs, ss, off, segc, ldc = fused_d.data_ptr() + 2 * g * d, ld, (g + 2) * d, 0, None, None, 0
     else:
         kc, cap, kv_off, segc_d, ldc = cache
-        k_ptr, ldk, hs, ss, off, segc = kc.data_ptr(), D, cap * D, HK * cap * D, native.i32_array(kv_off), segc_d.data_ptr()
-    native.check(lib.aigv_op_attention_probe(fused_d.data_ptr(), ld, k_ptr, ldk, cu, len(lens), h, HK, (g + 2) * D, hs, ss, off, D, cos.data_ptr(),
+        k_ptr, ldk, hs, ss, off, segc = kc.data_ptr(), d, cap * d, HK * cap * d, native.i32_array(kv_off), segc_d.data_ptr()
+    native.check(lib.aigv_op_attention_probe(fused_d.data_ptr(), ld, k_ptr, ldk, cu, len(lens), h, HK, (g + 2) * d, hs, ss, off, d, cos.data_ptr(),
                                              sin.data_ptr(), cos.shape[0], native.i32_array(rows), len(rows), seg_new_d.data_ptr(), segc, ldc, n_seg,
                                              ctypes.c_void_p(out_ptr), native.stream_ptr()))
     torch.cuda.synchronize()

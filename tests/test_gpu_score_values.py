@@ -145,7 +145,8 @@ def test_op_census_every_slot_holds_the_integer_sum_over_n(lib, g):
 
 
 def test_op_head_dim_64_census_and_random_data(lib):
-    """The D = 64 instantiation (four key lanes, another thread-to-column map): the census bit-exact, random data within the derived bound."""
+    """The D = 64 instantiation (four key lanes, another thread-to-column map): the census bit-exact, random data within the derived bound - and
+    on that random data the bins and the dense rows bit-equal to the plain and the dense call, the values the same beside the dense rows."""
     g, d = 2, 64
     census_check(lib, g, d=d)
     gen = torch.Generator().manual_seed(6400)
@@ -153,7 +154,13 @@ def test_op_head_dim_64_census_and_random_data(lib):
     q, k, v = (torch.randn(T, HK, *s, generator=gen).to(BF) for s in ((g, d), (d,), (d,)))
     cos, sin = R.rope_table(d, R.N_POS)
     seg = R.seg_table()
-    _, _, val = probe_values(lib, R.fused(q, k, v).cuda(), g, ROWS, seg.cuda(), d=d)
+    fused, seg_d = R.fused(q, k, v).cuda(), seg.cuda()
+    out, _, val = probe_values(lib, fused, g, ROWS, seg_d, d=d)
+    out_d, tok_d, val_d = probe_values(lib, fused, g, ROWS, seg_d, d=d, dense=True)
+    assert torch.equal(bits(out_d), bits(out)) and torch.equal(bits(val_d), bits(val))
+    assert torch.equal(bits(out), bits(G.probe(lib, fused, g, ROWS, seg_d, cos_sin=GT.tables(d), d=d)))
+    out_t, tok_t = GT.probe_tokens(lib, fused, g, ROWS, seg_d, d=d)
+    assert torch.equal(bits(out), bits(out_t)) and torch.equal(bits(tok_d), bits(tok_t))
     q_rot = R.rotate_q(q, R.positions(), cos, sin)
     worst = 0.0
     for i, (b, r, t) in enumerate(R.probe_rows()):

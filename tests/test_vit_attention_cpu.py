@@ -36,7 +36,9 @@ def test_abi_header_prototypes_exports_and_host_refusals():
         assert phrase in doc and phrase in kernel.split("#include")[0], phrase
     for phrase in ("ALWAYS fp32", "one fp32 division", "No atomics", "select_layer", "disarms on every way out"):
         assert phrase in doc, phrase
-    assert "__builtin_amdgcn_mfma_f32_32x32x16_bf16" in kernel and "atomic" not in kernel.split('#include "kernels.h"')[1]
+    tiles = open(os.path.join(build.CSRC, "qk_tiles.h")).read()                                             # the score tiles' product: shared with attnmap.hip
+    assert '#include "qk_tiles.h"' in kernel and "qk_tiles.h" in build.HEADERS and "__builtin_amdgcn_mfma_f32_32x32x16_bf16" in tiles
+    assert "atomic" not in kernel.split('#include "kernels.h"')[1] and "atomic" not in tiles.split("#pragma once")[1]
     # host refusals: before any pointer is used (a small aligned HOST buffer stands for every operand; no accepted call is made)
     buf = (ctypes.c_char * 64)()
     p = ctypes.addressof(buf)
