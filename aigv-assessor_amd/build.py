@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 SOURCES = ["context.hip", "dispatch.hip", "passes.hip", "ops.hip", "tune.hip", "gemm.hip", "gemm256.hip", "gemmco.hip", "attention.hip", "rowops.hip", "head.hip", "head8.hip", "ingest.hip", "slowfast.hip",
            "logprob.hip", "attnprobe.hip", "attnmap.hip", "probe.hip", "vitmap.hip"]
-HEADERS = ["common.h", "epilogue.h", "kernels.h", "attn_lay.h", "ctx.h", "qk_tiles.h", os.path.join("..", "..", "include", "aigv_amd.h")]
+HEADERS = ["common.h", "epilogue.h", "kernels.h", "attn_lay.h", "ctx.h", "qk_tiles.h", "skinny_tiles.h", os.path.join("..", "..", "include", "aigv_amd.h")]
 OUT = os.path.join(HERE, "libaigv_amd.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
 # per-file additions.  The attention kernels' softmax is written one score at a time on purpose (v_pk_*_f32 is slower beside MFMAs): keep

@@ -14,6 +14,7 @@
 #include "common.h"
 #include "epilogue.h"
 #include "kernels.h"
+#include "skinny_tiles.h"
 
 namespace {
 
@@ -29,20 +30,9 @@ namespace {
 // not depend on R; lse_finish_kernel (logprob.hip) merges them in a fixed order.
 // (lse_push / lse_combine: common.h)
 
-// SK_ROPE_KV: the decode step's wqkv GEMV with RoPE and the KV-cache append in its epilogue (head_dim 128).  A workgroup takes the
-// two 16-row slabs of W that rotate_half pairs - dims 16 sub .. and 64 + 16 sub .. of one head slot - so a lane ends up holding
-// x_i and x_{i+64} of the same token: query slots are rotated and stored to the qkv row, the K slot is rotated and the V slot
-// copied straight into the caches (modeling_internlm2.py:247-261, 397-402; same three bf16 roundings as rope_kernel).
-struct RopeKvArgs {
-  const int32_t* pos; const int32_t* seq;      // position / cache sequence of every x row (device)
-  const bf16_t* cos; const bf16_t* sin;        // [max_pos, 64]
-  bf16_t* kc; bf16_t* vc;                      // [seq][kv head][cap][128]
-  int g, n_kv, cap;
-};
-
 // NORM: the GEMV applies the RMSNorm in front of it (attention_norm before wqkv, ffn_norm before w1|w3; modeling_internlm2.py:138-143)
 // to its x rows itself: x is the raw residual stream, every workgroup normalises the R <= 4 rows into LDS with rmsnorm_kernel's exact
-// arithmetic (same thread -> chunk mapping, same reduction tree) and takes its B fragments from there.  Redundant work per
+// arithmetic (skinny_tiles.h) and takes its B fragments from there.  Redundant work per
 // workgroup (R x K elements), but no launch: the statistics' L2 round trip and barriers run behind the first weight loads.
 struct NormArgs { const bf16_t* w; float eps; };
 
@@ -62,12 +52,8 @@ __device__ __forceinline__ bf16x8 wload(const bf16_t* p) {
   else return *(const bf16x8*)p;
 }
 
-// P: sub-slab form of a decode GEMV (one x row tile, R <= 16 / P rows).  A workgroup takes RS = 16 / P rows of W per slab instead
-// of 16, and the MFMA's other rows / columns carry P - 1 further K sub-ranges of the SAME rows: A row m = W row (m mod RS) over
-// sub-range (m / RS), B column n = x row (n mod RS) over sub-range (n / RS), so D[m][n] is a partial product wherever m / RS ==
-// n / RS and the result is the sum of those P diagonal blocks (a shuffle per block).  Every lane still loads distinct weight
-// bytes; what changes is the GRID: N / RS workgroups of 1 / P the bytes - a width whose 16-row slabs come to a non-integer
-// number of workgroups per CU (w1|w3 of InternLM2-7B: 3.5; fused wqkv: 0.75) runs at the rate of the next integer
+// P: sub-slab form of a decode GEMV (one x row tile, R <= 16 / P rows; geometry: skinny_tiles.h).  A width whose 16-row slabs come to a
+// non-integer number of workgroups per CU (w1|w3 of InternLM2-7B: 3.5; fused wqkv: 0.75) runs at the rate of the next integer
 // (scripts/gemv_balance_probe.py: 3.5 per CU 4.97 TB/s, 3 per CU 5.34, 4 per CU 5.45).
 template <int RT, int EPI, int NWV = 4, bool NT = false, int NC = 0, int P = 1>   // NC: fused-norm form, K = NC x 2048 (0 = off)
 __global__ __launch_bounds__(NWV * 64) void skinny_kernel(const bf16_t* __restrict__ x, int ldx, int R,
@@ -75,7 +61,7 @@ __global__ __launch_bounds__(NWV * 64) void skinny_kernel(const bf16_t* __restri
                                                      const bf16_t* __restrict__ bias, const bf16_t* __restrict__ resid,
                                                      int ldr, bf16_t* __restrict__ out, int ldo,
                                                      unsigned long long* __restrict__ packed,
-                                                     const bf16_t* __restrict__ ls, const RopeKvArgs rk = RopeKvArgs{},
+                                                     const bf16_t* __restrict__ ls, const AigvRopeKv rk = AigvRopeKv{},
                                                      const NormArgs na = NormArgs{}, const LogitStore st = LogitStore{}) {
   constexpr bool NORM = NC > 0;
   static_assert(!NORM || (RT == 1 && NWV == 4), "the fused norm is the decode form: one row tile, 256 threads (rmsnorm_kernel's reduction)");
@@ -85,25 +71,18 @@ __global__ __launch_bounds__(NWV * 64) void skinny_kernel(const bf16_t* __restri
   constexpr bool AMAX = EPI == SK_ARGMAX || EPI == SK_ARGMAX_LSE || EPI == SK_ARGMAX_LSE_STORE;
   constexpr int NS = (EPI == SK_SWIGLU || EPI == SK_ROPE_KV) ? 2 : (AMAX && RT >= 2) ? 4 : 1;
   static_assert(P == 1 || ((P == 2 || P == 4) && RT == 1 && !AMAX), "sub-slab forms: one row tile, 8 or 4 rows per slab");
-  constexpr int RS = 16 / P;                         // W rows per slab (= x rows the form can take)
   __shared__ float part[NWV - 1][NS][RT][4][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int fr = lane & 15, fq = lane >> 4;
-  const int sr = fr % RS, sp = fr / RS;              // this lane's slab row / x row, and its K sub-range (P == 1: fr, 0)
-  // first W row of the workgroup's slab(s).  SK_ROPE_KV: block = (head slot, RS-dim group), its two slabs are 64 rows apart;
-  // SK_SWIGLU: w1 / w3 alternate in 16-row blocks, block = (32-row pair, RS-row group), the slabs 16 rows apart
-  const int n0 = EPI == SK_ROPE_KV ? (int)(blockIdx.x / (64 / RS)) * 128 + (int)(blockIdx.x % (64 / RS)) * RS
-                 : EPI == SK_SWIGLU ? (int)(blockIdx.x / P) * 32 + (int)(blockIdx.x % P) * RS
-                                    : blockIdx.x * RS * NS;
-  constexpr int SLAB_STEP = EPI == SK_ROPE_KV ? 64 : 16;
-  const int kper = K / (NWV * P), kbeg = (wave * P + sp) * kper;      // K % (32 * NWV * P) == 0 checked by the launcher
+  const SkinnySlab<EPI, P, NS, 8> g(lane, wave, K, NWV);
+  constexpr int RS = g.RS;
+  const int fq = g.fq, n0 = g.n0, kper = g.kper;
 
   const bf16_t* wrow[NS];
 #pragma unroll
-  for (int s = 0; s < NS; ++s) wrow[s] = W + (size_t)min(n0 + s * SLAB_STEP + sr, N - 1) * ldw + kbeg + fq * 8;
+  for (int s = 0; s < NS; ++s) wrow[s] = g.wfrag(W, s, N, ldw);
   const bf16_t* xrow[RT];
 #pragma unroll
-  for (int t = 0; t < RT; ++t) xrow[t] = x + (size_t)min(t * 16 + sr, R - 1) * ldx + kbeg + fq * 8;
+  for (int t = 0; t < RT; ++t) xrow[t] = g.frag(x, t * 16 + g.sr, R - 1, ldx);
 
   f32x4 acc[NS][RT];
 #pragma unroll
@@ -115,18 +94,18 @@ __global__ __launch_bounds__(NWV * 64) void skinny_kernel(const bf16_t* __restri
   // GEMV (one x row tile, few workgroups per CU when N is small) needs the deeper form to cover the HBM latency
   constexpr int DEPTH = RT == 1 ? (NS == 1 ? 16 : SKINNY_DEPTH2) : (RT == 2 && NS == 1) ? 8 : 4;   // (two row tiles: InternViT's 32 leftover rows per pass)
   int k = 0;
-  const int xs_off = min(sr, R - 1) * K + kbeg + fq * 8;          // NORM: this lane's fragment origin in xs
+  const int xs_off = min(g.sr, R - 1) * K + g.kbeg + fq * 8;         // NORM: this lane's fragment origin in xs
   if constexpr (NORM) {
     // Load order matters (vmcnt retires in issue order): the x rows and the norm weight - a few L2 hits - go out FIRST, then the
     // first DEPTH weight k-steps; the statistics then wait only for the former, with the weight stream in flight behind them.
-    // Rows past R repeat row R - 1 (never normalised); thread -> chunk mapping and sums as rmsnorm_kernel.
+    // Rows past R repeat row R - 1 (never normalised).
     u16x8 xr[4][NC], gw[NC];
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
-      for (int c = 0; c < NC; ++c) xr[r][c] = *(const u16x8*)(x + (size_t)min(r, R - 1) * ldx + ((threadIdx.x + c * 256) << 3));
+      for (int c = 0; c < NC; ++c) xr[r][c] = *(const u16x8*)(x + (size_t)min(r, R - 1) * ldx + skinny_chunk(c));
 #pragma unroll
-    for (int c = 0; c < NC; ++c) gw[c] = *(const u16x8*)(na.w + ((threadIdx.x + c * 256) << 3));
+    for (int c = 0; c < NC; ++c) gw[c] = *(const u16x8*)(na.w + skinny_chunk(c));
     bf16x8 wf[DEPTH][NS];
 #pragma unroll
     for (int u = 0; u < DEPTH; ++u)
@@ -147,8 +126,8 @@ __global__ __launch_bounds__(NWV * 64) void skinny_kernel(const bf16_t* __restri
           for (int c = 0; c < NC; ++c) {
             u16x8 o;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = f2bf(bf2f(gw[c][e]) * rbf(bf2f(xr[r][c][e]) * rstd));
-            *(u16x8*)(xs + (size_t)r * K + ((threadIdx.x + c * 256) << 3)) = o;
+            for (int e = 0; e < 8; ++e) o[e] = f2bf(skinny_normed(gw[c][e], xr[r][c][e], rstd));
+            *(u16x8*)(xs + (size_t)r * K + skinny_chunk(c)) = o;
           }
         }
       }
@@ -192,54 +171,13 @@ __global__ __launch_bounds__(NWV * 64) void skinny_kernel(const bf16_t* __restri
   if constexpr (DEPTH > 4) run(std::integral_constant<int, 4>{});
   run(std::integral_constant<int, 1>{});
 
-  // ---- combine the four K slices: waves 1..3 publish, wave 0 sums in a fixed order -------------------------
-  if (wave > 0) {
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-#pragma unroll
-      for (int t = 0; t < RT; ++t)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) part[wave - 1][s][t][e][lane] = acc[s][t][e];
-  }
-  __syncthreads();
-  if (wave != 0) return;
-#pragma unroll
-  for (int s = 0; s < NS; ++s)
-#pragma unroll
-    for (int t = 0; t < RT; ++t)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        if constexpr (NWV == 4) {
-          acc[s][t][e] += (part[0][s][t][e][lane] + part[1][s][t][e][lane]) + part[2][s][t][e][lane];
-        } else {
-          float sum = 0.f;
-#pragma unroll
-          for (int w = 0; w < NWV - 1; ++w) sum += part[w][s][t][e][lane];   // fixed order
-          acc[s][t][e] += sum;
-        }
-      }
-
-  // sub-slab forms: sum the P diagonal blocks (sub-range p lives in lanes fr = p RS + i, fq = p RS / 4 + j / 4), in order
-  if constexpr (P == 2) {
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[s][0][e] += __shfl(acc[s][0][e], (lane + 40) & 63, 64);
-  } else if constexpr (P == 4) {
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float v = acc[s][0][e];
-        acc[s][0][e] = ((v + __shfl(v, (lane + 20) & 63, 64)) + __shfl(v, (lane + 40) & 63, 64)) + __shfl(v, (lane + 60) & 63, 64);
-      }
-  }
-  const bool own = P == 1 || (fr < RS && fq < RS / 4);   // lanes that hold finished sums
+  SKINNY_COMBINE(acc, part, NWV, NS, RT, P, wave, lane)       // K slices and sub-slab blocks, fixed order (skinny_tiles.h)
+  const bool own = g.own();
 
   // lane owns x row r = 16t + fr and W rows n = n0 + 4*fq + e
 #pragma unroll
   for (int t = 0; t < RT; ++t) {
-    const int r = own ? t * 16 + fr : R;
+    const int r = own ? t * 16 + g.fr : R;
     if constexpr (AMAX) {
       unsigned long long best = 0ull;
 #pragma unroll
@@ -277,33 +215,9 @@ __global__ __launch_bounds__(NWV * 64) void skinny_kernel(const bf16_t* __restri
         }
       }
     } else if constexpr (EPI == SK_ROPE_KV) {
-      if (r < R) {
-        const int hs = blockIdx.x / (64 / RS), d = (int)(blockIdx.x % (64 / RS)) * RS + 4 * fq;   // head slot; dims d .. d+3 and d+64 .. d+67
-        const int slot = hs % (rk.g + 2), gi = hs / (rk.g + 2);
-        const int p = rk.pos[r];
-        u16x4 olo, ohi;
-        if (slot <= rk.g) {
-          const u16x4 co = *(const u16x4*)(rk.cos + (size_t)p * 64 + d), si = *(const u16x4*)(rk.sin + (size_t)p * 64 + d);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float x1 = rbf(acc[0][t][e]), x2 = rbf(acc[1][t][e]), cc = bf2f(co[e]), ss = bf2f(si[e]);
-            olo[e] = f2bf(rbf(x1 * cc) + rbf(-x2 * ss));
-            ohi[e] = f2bf(rbf(x2 * cc) + rbf(x1 * ss));
-          }
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { olo[e] = f2bf(acc[0][t][e]); ohi[e] = f2bf(acc[1][t][e]); }
-        }
-        bf16_t* dst = slot < rk.g ? out + (size_t)r * ldo + (size_t)hs * 128 + d
-                                  : (slot == rk.g ? rk.kc : rk.vc) + (((size_t)rk.seq[r] * rk.n_kv + gi) * rk.cap + p) * 128 + d;
-        *(u16x4*)dst = olo;
-        *(u16x4*)(dst + 64) = ohi;
-      }
+      if (r < R) SKINNY_ROPE_KV_STORE(RS, acc[0][t], acc[1][t], rk, r, fq, out, ldo)
     } else if constexpr (EPI == SK_SWIGLU) {
-      if (r < R) {
-        const int n = (int)(blockIdx.x / P) * 16 + (int)(blockIdx.x % P) * RS + 4 * fq;
-        *(u16x4*)(out + (size_t)r * ldo + n) = epi_swiglu4(acc[0][t], acc[1][t]);
-      }
+      if (r < R) *(u16x4*)(out + (size_t)r * ldo + g.swiglu_col()) = epi_swiglu4(acc[0][t], acc[1][t]);
     } else {
       const int n = n0 + 4 * fq;
       if (r < R && n < N) {
@@ -357,43 +271,32 @@ __global__ void unpack_argmax_kernel(const unsigned long long* __restrict__ pack
 // of Linear+ReLU with a bf16 rounding after each Linear (:82-94).  Without a NaN the guard leaves an Inf alone: the row then turns
 // into NaN / Inf in the Linears, and the ReLUs pass a NaN on as F.relu does.  The wide layers run on the skinny GEMM
 // (weights streamed once for all clips); the narrow tail (fan-in < 128) runs in one small kernel.
-// (the guard of one batch slice by one 256-thread workgroup, X [B, H] rows -> OUT [B, H] dense: written once for the two kernels below.  A macro, not
-// a function: through an inlined function hipcc allocates score_guard_kernel's registers differently, and its device assembly is pinned)
-#define AIGV_SCORE_GUARD_SLICE(X, LDX, B, H, OUT)                              \
-  __shared__ int any_nan;                                                      \
-  if (threadIdx.x == 0) any_nan = 0;                                           \
-  __syncthreads();                                                             \
-  int nan_here = 0;                                                            \
-  for (int i = threadIdx.x; i < (B) * (H); i += 256) {                         \
-    const float v = bf2f((X)[(size_t)(i / (H)) * (LDX) + (i % (H))]);          \
-    nan_here |= (v != v);                                                      \
-  }                                                                            \
-  if (nan_here) atomicOr(&any_nan, 1);                                         \
-  __syncthreads();                                                             \
-  const bool fix = any_nan != 0;                                               \
-  for (int i = threadIdx.x; i < (B) * (H); i += 256) {                         \
-    float v = bf2f((X)[(size_t)(i / (H)) * (LDX) + (i % (H))]);                \
-    if (fix) {                                                                 \
-      if (v != v) v = 0.f;                                                     \
-      else if (isinf(v)) v = v > 0 ? 1e9f : -1e9f;                             \
-    }                                                                          \
-    (OUT)[i] = f2bf(v);                                                        \
-  }
-
-__global__ __launch_bounds__(256) void score_guard_kernel(const bf16_t* __restrict__ x, int ldx, int B, int H,
-                                                          bf16_t* __restrict__ out) {
-  AIGV_SCORE_GUARD_SLICE(x, ldx, B, H, out)
-}
-
-// The grouped form (aigv_launch_score_head_groups): workgroup g guards ITS B rows - x + g * group_stride - under its own flag, as the
-// reference would guard G batch slices one after the other; out is dense [G * B, H].
+// The guard: workgroup g guards ITS batch slice - the B rows at x + g * group_stride, leading dimension ldx - under its own flag, as the reference
+// would guard G batch slices one after the other; out is dense [G * B, H].  (aigv_launch_score_head: G = 1)
 __global__ __launch_bounds__(256) void score_guard_groups_kernel(const bf16_t* __restrict__ x, int ldx, size_t group_stride, int B, int H,
                                                                  bf16_t* __restrict__ out) {
   const bf16_t* xg = x + (size_t)blockIdx.x * group_stride;
   bf16_t* og = out + (size_t)blockIdx.x * B * H;
-  AIGV_SCORE_GUARD_SLICE(xg, ldx, B, H, og)
+  __shared__ int any_nan;
+  if (threadIdx.x == 0) any_nan = 0;
+  __syncthreads();
+  int nan_here = 0;
+  for (int i = threadIdx.x; i < B * H; i += 256) {
+    const float v = bf2f(xg[(size_t)(i / H) * ldx + (i % H)]);
+    nan_here |= (v != v);
+  }
+  if (nan_here) atomicOr(&any_nan, 1);
+  __syncthreads();
+  const bool fix = any_nan != 0;
+  for (int i = threadIdx.x; i < B * H; i += 256) {
+    float v = bf2f(xg[(size_t)(i / H) * ldx + (i % H)]);
+    if (fix) {
+      if (v != v) v = 0.f;
+      else if (isinf(v)) v = v > 0 ? 1e9f : -1e9f;
+    }
+    og[i] = f2bf(v);
+  }
 }
-#undef AIGV_SCORE_GUARD_SLICE
 
 // remaining narrow layers: one workgroup per clip; activations ping-pong in LDS (all dims <= 1024 here)
 __global__ __launch_bounds__(256) void score_tail_kernel(const ScoreHeadArgs a, int first_layer) {
@@ -425,51 +328,30 @@ hipError_t launch_skinny(const bf16_t* x, int ldx, int R, const bf16_t* W, int l
                          const bf16_t* resid, int ldr, bf16_t* out, int ldo, unsigned long long* packed,
                          hipStream_t s, const bf16_t* ls = nullptr, int p = 1, LogitStore st = LogitStore{}) {
   const int rt = (R + 15) / 16;
+  auto go = [&](auto rtag, auto wtag, auto ptag, int blocks) {
+    constexpr int RT = decltype(rtag)::value, NWV = decltype(wtag)::value, P = decltype(ptag)::value;
+    hipLaunchKernelGGL((skinny_kernel<RT, EPI, NWV, false, 0, P>), dim3(blocks), dim3(NWV * 64), 0, s, x, ldx, R, W, ldw, N, K, bias, resid, ldr, out, ldo, packed, ls,
+                       AigvRopeKv{}, NormArgs{}, st);
+    return hipGetLastError();
+  };
   if (p > 1) {   // sub-slab forms of the decode GEMVs (skinny_kernel's P): 16 / p rows per workgroup and slab
     const int rs = 16 / p;
     if ((p != 2 && p != 4) || R > rs || K % (128 * p) || N % (EPI == SK_SWIGLU ? 32 : rs)) return hipErrorInvalidValue;
-    if constexpr (EPI == SK_STORE || EPI == SK_RESID || EPI == SK_SWIGLU) {
-      const int blocks = EPI == SK_SWIGLU ? N / 32 * p : N / rs;
-      if (p == 2) hipLaunchKernelGGL((skinny_kernel<1, EPI, 4, false, 0, 2>), dim3(blocks), dim3(256), 0, s, x, ldx, R, W, ldw, N, K, bias, resid, ldr, out, ldo, packed, ls);
-      else hipLaunchKernelGGL((skinny_kernel<1, EPI, 4, false, 0, 4>), dim3(blocks), dim3(256), 0, s, x, ldx, R, W, ldw, N, K, bias, resid, ldr, out, ldo, packed, ls);
-      return hipGetLastError();
-    } else {
+    if constexpr (EPI == SK_STORE || EPI == SK_RESID || EPI == SK_SWIGLU)
+      return with_int<2, 4>(p, [&](auto pp) { return go(int_c<1>{}, int_c<4>{}, pp, EPI == SK_SWIGLU ? N / 32 * p : N / rs); });
+    else
       return hipErrorInvalidValue;
-    }
   }
   const int ns = (EPI == SK_SWIGLU) ? 2 : ((EPI == SK_ARGMAX || EPI == SK_ARGMAX_LSE || EPI == SK_ARGMAX_LSE_STORE) && rt >= 2) ? 4 : 1;   // = NS of the kernel
   const int blocks = (N + 16 * ns - 1) / (16 * ns);
   // (non-temporal weight loads were measured SLOWER on the 8B decode shapes - wqkv 12.5 -> 14.8 us, w2 24.9 -> 29.9 us, w1|w3 47.9 -> 54.9 us -
   //  and the form was removed: plain cache policy everywhere)
-#define GO(RT) hipLaunchKernelGGL((skinny_kernel<RT, EPI>), dim3(blocks), dim3(256), 0, s, x, ldx, R, W, ldw, N, K, bias, resid, ldr, out, ldo, packed, ls)
-  if constexpr (EPI == SK_ARGMAX_LSE_STORE) {
-#define GOS(RT) hipLaunchKernelGGL((skinny_kernel<RT, EPI>), dim3(blocks), dim3(256), 0, s, x, ldx, R, W, ldw, N, K, bias, resid, ldr, out, ldo, packed, ls, RopeKvArgs{}, NormArgs{}, st)
-    switch (rt) {
-      case 1: GOS(1); break;
-      case 2: GOS(2); break;
-      case 3: GOS(3); break;
-      case 4: GOS(4); break;
-      default: return hipErrorInvalidValue;
-    }
-#undef GOS
-    return hipGetLastError();
-  }
   if constexpr (EPI == SK_STORE || EPI == SK_RESID) {
     constexpr int max8 = 256;   // at most one slab per CU
-    if (rt == 1 && K % 256 == 0 && blocks <= max8 && p != 0) {   // a decode GEMV with about one slab per CU: 8 K slices per workgroup (p == 0: the caller wants ONE form for every row count)
-      hipLaunchKernelGGL((skinny_kernel<1, EPI, 8>), dim3(blocks), dim3(512), 0, s, x, ldx, R, W, ldw, N, K, bias, resid, ldr, out, ldo, packed, ls);
-      return hipGetLastError();
-    }
+    // a decode GEMV with about one slab per CU: 8 K slices per workgroup (p == 0: the caller wants ONE form for every row count)
+    if (rt == 1 && K % 256 == 0 && blocks <= max8 && p != 0) return go(int_c<1>{}, int_c<8>{}, int_c<1>{}, blocks);
   }
-  switch (rt) {
-    case 1: GO(1); break;
-    case 2: GO(2); break;
-    case 3: GO(3); break;
-    case 4: GO(4); break;
-    default: return hipErrorInvalidValue;
-  }
-#undef GO
-  return hipGetLastError();
+  return with_int<1, 2, 3, 4>(rt, [&](auto t) { return go(t, int_c<4>{}, int_c<1>{}, blocks); });
 }
 
 }  // namespace
@@ -485,33 +367,21 @@ hipError_t aigv_launch_skinny_rope_kv(const bf16_t* x, int ldx, int R, const bf1
   if (R > 64 || K % 128 || (ldx % 8) || (ldw % 8) || (ldo % 4) || head_dim != 128 || N != n_kv * (g + 2) * 128 || !pos || !seq || !cos ||
       !sin || !kc || !vc)
     return hipErrorInvalidValue;
-  RopeKvArgs rk{pos, seq, cos, sin, kc, vc, g, n_kv, cap};
+  const AigvRopeKv rk{pos, seq, cos, sin, kc, vc, g, n_kv, cap};
   const int rt = (R + 15) / 16, blocks = N / 32 * p;
   if ((p != 1 && p != 2 && p != 4) || R > (p == 1 ? 64 : 16 / p) || K % (128 * p)) return hipErrorInvalidValue;
-  if (norm_w) {   // x = the raw residual rows; attention_norm applied by the kernel (NormArgs above)
+  auto go = [&](auto rtag, auto nctag, auto ptag) {   // NC > 0: x = the raw residual rows; attention_norm applied by the kernel (NormArgs above)
+    constexpr int RT = decltype(rtag)::value, NC = decltype(nctag)::value, P = decltype(ptag)::value;
+    hipLaunchKernelGGL((skinny_kernel<RT, SK_ROPE_KV, 4, false, NC, P>), dim3(blocks), dim3(256), NC ? (size_t)R * K * sizeof(bf16_t) : 0, s, x, ldx, R, W, ldw, N, K,
+                       nullptr, nullptr, 0, qkv, ldo, nullptr, nullptr, rk, NormArgs{norm_w, norm_eps});
+    return hipGetLastError();
+  };
+  if (norm_w) {
     if (R > 4 || !aigv_skinny_norm_fusable(K)) return hipErrorInvalidValue;
-#define GO(NC, PP) hipLaunchKernelGGL((skinny_kernel<1, SK_ROPE_KV, 4, false, NC, PP>), dim3(blocks), dim3(256), (size_t)R * K * sizeof(bf16_t), s, x, ldx, R, W, ldw, N, K, \
-                                      nullptr, nullptr, 0, qkv, ldo, nullptr, nullptr, rk, NormArgs{norm_w, norm_eps})
-    if (K == 4096) { if (p == 1) GO(2, 1); else if (p == 2) GO(2, 2); else GO(2, 4); }
-    else { if (p == 1) GO(3, 1); else if (p == 2) GO(3, 2); else GO(3, 4); }
-#undef GO
-    return hipGetLastError();
+    return with_int<2, 3>(K / 2048, [&](auto nc) { return with_int<1, 2, 4>(p, [&](auto pp) { return go(int_c<1>{}, nc, pp); }); });
   }
-  if (p != 1) {
-    if (p == 2) hipLaunchKernelGGL((skinny_kernel<1, SK_ROPE_KV, 4, false, 0, 2>), dim3(blocks), dim3(256), 0, s, x, ldx, R, W, ldw, N, K, nullptr, nullptr, 0, qkv, ldo, nullptr, nullptr, rk);
-    else hipLaunchKernelGGL((skinny_kernel<1, SK_ROPE_KV, 4, false, 0, 4>), dim3(blocks), dim3(256), 0, s, x, ldx, R, W, ldw, N, K, nullptr, nullptr, 0, qkv, ldo, nullptr, nullptr, rk);
-    return hipGetLastError();
-  }
-#define GO(RT) hipLaunchKernelGGL((skinny_kernel<RT, SK_ROPE_KV, 4, false>), dim3(blocks), dim3(256), 0, s, x, ldx, R, W, ldw, N, K, nullptr, nullptr, 0, qkv, ldo, nullptr, nullptr, rk)
-  switch (rt) {
-    case 1: GO(1); break;
-    case 2: GO(2); break;
-    case 3: GO(3); break;
-    case 4: GO(4); break;
-    default: return hipErrorInvalidValue;
-  }
-#undef GO
-  return hipGetLastError();
+  if (p != 1) return with_int<2, 4>(p, [&](auto pp) { return go(int_c<1>{}, int_c<0>{}, pp); });
+  return with_int<1, 2, 3, 4>(rt, [&](auto t) { return go(t, int_c<0>{}, int_c<1>{}); });
 }
 
 // decode: SwiGLU(x_n W13^T) with x_n = RMSNorm(x) * norm_w computed by the kernel itself (R <= 4 rows; NormArgs above)
@@ -519,12 +389,13 @@ hipError_t aigv_launch_skinny_swiglu_normed(const bf16_t* x, int ldx, int R, con
                                             const bf16_t* norm_w, float norm_eps, hipStream_t s, int p) {
   if (R <= 0) return hipSuccess;
   if (R > 4 || !aigv_skinny_norm_fusable(K) || (ldx % 8) || (ldw % 8) || (ldo % 4) || (N % 32) || !norm_w || (p != 1 && p != 2 && p != 4)) return hipErrorInvalidValue;
-#define GO(NC, PP) hipLaunchKernelGGL((skinny_kernel<1, SK_SWIGLU, 4, false, NC, PP>), dim3(N / 32 * p), dim3(256), (size_t)R * K * sizeof(bf16_t), s, x, ldx, R, W, ldw, N, K, \
-                                      nullptr, nullptr, 0, out, ldo, nullptr, nullptr, RopeKvArgs{}, NormArgs{norm_w, norm_eps})
-  if (K == 4096) { if (p == 1) GO(2, 1); else if (p == 2) GO(2, 2); else GO(2, 4); }
-  else { if (p == 1) GO(3, 1); else if (p == 2) GO(3, 2); else GO(3, 4); }
-#undef GO
-  return hipGetLastError();
+  return with_int<2, 3>(K / 2048, [&](auto nc) {
+    return with_int<1, 2, 4>(p, [&](auto pp) {
+      hipLaunchKernelGGL((skinny_kernel<1, SK_SWIGLU, 4, false, decltype(nc)::value, decltype(pp)::value>), dim3(N / 32 * p), dim3(256), (size_t)R * K * sizeof(bf16_t), s,
+                         x, ldx, R, W, ldw, N, K, nullptr, nullptr, 0, out, ldo, nullptr, nullptr, AigvRopeKv{}, NormArgs{norm_w, norm_eps});
+      return hipGetLastError();
+    });
+  });
 }
 
 // epi: 0 store(+bias) | 1 residual(+bias) | 2 swiglu (16-row interleaved w1/w3, out is N/2 wide) | 3 gelu(+bias)
@@ -589,47 +460,10 @@ hipError_t aigv_launch_lm_head_lse_partials(const bf16_t* h, int R, int H, const
   return launch_skinny<SK_ARGMAX_LSE>(h, H, R, W, H, V, H, nullptr, nullptr, 0, reinterpret_cast<bf16_t*>(part), (int)aigv_lm_head_lse_slots(V), packed, s);
 }
 
-// scratch: 3 * B * max(dims) bf16 (guarded input + two ping-pong activations)
-hipError_t aigv_launch_score_head(const ScoreHeadArgs& a, bf16_t* scratch, hipStream_t s) {
-  if (a.B <= 0) return hipSuccess;
-  if (a.n_layers < 1 || a.n_layers > 8 || a.B > 64 || !scratch) return hipErrorInvalidValue;
-  int maxd = 0;
-  for (int i = 0; i <= a.n_layers; ++i) {
-    if (a.dims[i] <= 0) return hipErrorInvalidValue;
-    maxd = a.dims[i] > maxd ? a.dims[i] : maxd;
-  }
-  bf16_t* xg = scratch;
-  bf16_t* pp[2] = {scratch + (size_t)a.B * maxd, scratch + (size_t)2 * a.B * maxd};
-  hipLaunchKernelGGL(score_guard_kernel, dim3(1), dim3(256), 0, s, a.x, a.ldx, a.B, a.dims[0], xg);
-  const bf16_t* cur = xg;
-  int ld = a.dims[0], L = 0, flip = 0;
-  for (; L < a.n_layers; ++L) {
-    const int din = a.dims[L], dout = a.dims[L + 1];
-    if (din % 128 || dout % 4) break;
-    hipError_t e = launch_skinny<SK_RELU>(cur, ld, a.B, a.w[L], din, dout, din, a.b[L], nullptr, 0, pp[flip], dout, nullptr, s);
-    if (e != hipSuccess) return e;
-    cur = pp[flip];
-    ld = dout;
-    flip ^= 1;
-  }
-  if (L < a.n_layers) {
-    if (a.dims[L] > 1024) return hipErrorInvalidValue;
-    for (int i = L + 1; i <= a.n_layers; ++i)
-      if (a.dims[i] > 1024) return hipErrorInvalidValue;
-    ScoreHeadArgs t = a;
-    t.x = cur;
-    t.ldx = ld;
-    hipLaunchKernelGGL(score_tail_kernel, dim3(a.B), dim3(256), 0, s, t, L);
-  } else {
-    return hipErrorInvalidValue;   // the last layer (fan-out 1) always runs in the tail kernel
-  }
-  return hipGetLastError();
-}
-
 // G batch slices of B rows each in one go (the depth lens: one slice per depth): slice g = rows x + g * group_stride (leading dimension
 // a.ldx), guarded on its own; the GEMM layers then run over all G * B rows in chunks of at most 64 - a row's bits do not depend on how many
-// rows share its launch - and the tail kernel over all of them.  a.score: [G * B].  scratch: 3 * G * B * max(dims) bf16.  Slice for slice
-// the bits of aigv_launch_score_head.
+// rows share its launch - and the tail kernel over all of them.  a.score: [G * B].  scratch: 3 * G * B * max(dims) bf16 (guarded input + two
+// ping-pong activations).
 hipError_t aigv_launch_score_head_groups(const ScoreHeadArgs& a, int G, size_t group_stride, bf16_t* scratch, hipStream_t s) {
   if (a.B <= 0 || G <= 0) return hipSuccess;
   if (a.n_layers < 1 || a.n_layers > 8 || a.B > 64 || !scratch) return hipErrorInvalidValue;
@@ -666,3 +500,6 @@ hipError_t aigv_launch_score_head_groups(const ScoreHeadArgs& a, int G, size_t g
   hipLaunchKernelGGL(score_tail_kernel, dim3(rows), dim3(256), 0, s, t, L);
   return hipGetLastError();
 }
+
+// one batch slice: scratch 3 * B * max(dims) bf16.  (A chain without a tail layer, or with a tail dimension above 1024, is refused before anything is launched.)
+hipError_t aigv_launch_score_head(const ScoreHeadArgs& a, bf16_t* scratch, hipStream_t s) { return aigv_launch_score_head_groups(a, 1, 0, scratch, s); }

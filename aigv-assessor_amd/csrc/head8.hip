@@ -5,7 +5,7 @@
 //
 // A decode step is a weight stream; with one byte per weight the stream is half as long.  Structure = head.hip's skinny_kernel in
 // its decode forms (one x row tile of R <= 4 rows, 4 waves = 4 K slices, sub-slab forms P, RoPE / KV-append / SwiGLU / residual
-// epilogues) with three differences:
+// epilogues; what the two share is skinny_tiles.h) with three differences:
 //   * W fragments are 32 e4m3 bytes per lane and k-step (two 16-byte loads), the MFMA is v_mfma_scale_f32_16x16x128_f8f6f4 with
 //     unit block scales (K = 128 per instruction);
 //   * every workgroup quantises the x rows itself, in front of its K loop and behind its first weight loads: optional RMSNorm
@@ -19,6 +19,7 @@
 #include "common.h"
 #include "epilogue.h"
 #include "kernels.h"
+#include "skinny_tiles.h"
 
 namespace {
 
@@ -35,34 +36,29 @@ __global__ __launch_bounds__(256) void skinny8_kernel(const bf16_t* __restrict__
                                                       bf16_t* __restrict__ out, int ldo, const AigvRopeKv rk, const bf16_t* __restrict__ norm_w,
                                                       float eps) {
   constexpr int NS = EPI == SK_RESID ? 1 : 2;
-  constexpr int RS = 16 / P;
   extern __shared__ __attribute__((aligned(16))) uint8_t xs8[];   // the quantised x rows [R][K]
-  __shared__ float part[3][NS][4][64];
+  __shared__ float part[3][NS][1][4][64];
   __shared__ float red[4], redm[4], sx[4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int fr = lane & 15, fq = lane >> 4;
-  const int sr = fr % RS, sp = fr / RS;
-  const int n0 = EPI == SK_ROPE_KV ? (int)(blockIdx.x / (64 / RS)) * 128 + (int)(blockIdx.x % (64 / RS)) * RS
-                 : EPI == SK_SWIGLU ? (int)(blockIdx.x / P) * 32 + (int)(blockIdx.x % P) * RS
-                                    : blockIdx.x * RS;
-  constexpr int SLAB_STEP = EPI == SK_ROPE_KV ? 64 : 16;
-  const int kper = K / (4 * P), kbeg = (wave * P + sp) * kper;      // bytes = elements; kper % 128 == 0 checked by the launcher
+  const SkinnySlab<EPI, P, NS, 32> g(lane, wave, K, 4);             // bytes = elements; kper % 128 == 0 checked by the launcher
+  constexpr int RS = g.RS;
+  const int fq = g.fq, n0 = g.n0, kper = g.kper;
 
   const uint8_t* wrow[NS];
 #pragma unroll
-  for (int s = 0; s < NS; ++s) wrow[s] = W8 + (size_t)min(n0 + s * SLAB_STEP + sr, N - 1) * ldw + kbeg + fq * 32;
-  f32x4 acc[NS];
+  for (int s = 0; s < NS; ++s) wrow[s] = g.wfrag(W8, s, N, ldw);
+  f32x4 acc[NS][1];
 #pragma unroll
-  for (int s = 0; s < NS; ++s) acc[s] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int s = 0; s < NS; ++s) acc[s][0] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   // ---- x rows -> (RMSNorm) -> e4m3 + row scale, in LDS.  Load order matters (vmcnt retires in issue order): row 0 of x and the norm
   // weight first, then the first two weight k-steps, which stay in flight behind the statistics.
   u16x8 raw[NCH], gw[NORM ? NCH : 1];
 #pragma unroll
-  for (int c = 0; c < NCH; ++c) raw[c] = *(const u16x8*)(x + ((threadIdx.x + c * 256) << 3));
+  for (int c = 0; c < NCH; ++c) raw[c] = *(const u16x8*)(x + skinny_chunk(c));
   if constexpr (NORM) {
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) gw[c] = *(const u16x8*)(norm_w + ((threadIdx.x + c * 256) << 3));
+    for (int c = 0; c < NCH; ++c) gw[c] = *(const u16x8*)(norm_w + skinny_chunk(c));
   }
   constexpr int PF = 2;                                              // kper >= 256 checked by the launcher
   v4i_t wpf[PF][NS][2];
@@ -76,7 +72,7 @@ __global__ __launch_bounds__(256) void skinny8_kernel(const bf16_t* __restrict__
   for (int r = 0; r < R; ++r) {
     if (r > 0) {
 #pragma unroll
-      for (int c = 0; c < NCH; ++c) raw[c] = *(const u16x8*)(x + (size_t)r * ldx + ((threadIdx.x + c * 256) << 3));
+      for (int c = 0; c < NCH; ++c) raw[c] = *(const u16x8*)(x + (size_t)r * ldx + skinny_chunk(c));
     }
     float rstd = 1.f;
     if constexpr (NORM) {
@@ -88,7 +84,7 @@ __global__ __launch_bounds__(256) void skinny8_kernel(const bf16_t* __restrict__
       rstd = rsqrtf(block_sum_256(sq, red) / (float)K + eps);
     }
     auto value = [&](int c, int e) {                                // the bf16 value the bf16 path would feed the linear
-      if constexpr (NORM) return rbf(bf2f(gw[c][e]) * rbf(bf2f(raw[c][e]) * rstd));
+      if constexpr (NORM) return rbf(skinny_normed(gw[c][e], raw[c][e], rstd));
       else return bf2f(raw[c][e]);
     };
     float amax = 0.f;
@@ -110,20 +106,20 @@ __global__ __launch_bounds__(256) void skinny8_kernel(const bf16_t* __restrict__
       lo = __builtin_amdgcn_cvt_pk_fp8_f32(value(c, 2) * inv, value(c, 3) * inv, lo, true);
       hi = __builtin_amdgcn_cvt_pk_fp8_f32(value(c, 4) * inv, value(c, 5) * inv, hi, false);
       hi = __builtin_amdgcn_cvt_pk_fp8_f32(value(c, 6) * inv, value(c, 7) * inv, hi, true);
-      *(i32x2*)(xs8 + (size_t)r * K + ((threadIdx.x + c * 256) << 3)) = i32x2{lo, hi};
+      *(i32x2*)(xs8 + (size_t)r * K + skinny_chunk(c)) = i32x2{lo, hi};
     }
   }
   __syncthreads();
 
   // ---- K loop: lane (fr, fq) holds W row sr / x row sr over K sub-range sp, bytes [32 fq, 32 fq + 32) of every 128-byte k-step ----
-  const uint8_t* xf0 = xs8 + (size_t)min(sr, R - 1) * K + kbeg + fq * 32;
+  const uint8_t* xf0 = g.frag(xs8, g.sr, R - 1, K);
   auto xfrag = [&](int k) { return cat8(*(const v4i_t*)(xf0 + k), *(const v4i_t*)(xf0 + k + 16)); };
 #pragma unroll
   for (int u = 0; u < PF; ++u) {
     const v8i_t xf = xfrag(128 * u);
 #pragma unroll
     for (int s = 0; s < NS; ++s)
-      acc[s] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(cat8(wpf[u][s][0], wpf[u][s][1]), xf, acc[s], 0, 0, 0, 127, 0, 127);
+      acc[s][0] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(cat8(wpf[u][s][0], wpf[u][s][1]), xf, acc[s][0], 0, 0, 0, 127, 0, 127);
   }
   int k = 128 * PF;
   auto run = [&](auto dtag) {
@@ -142,7 +138,7 @@ __global__ __launch_bounds__(256) void skinny8_kernel(const bf16_t* __restrict__
         const v8i_t xf = xfrag(k + 128 * u);
 #pragma unroll
         for (int s = 0; s < NS; ++s)
-          acc[s] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(cat8(wf[u][s][0], wf[u][s][1]), xf, acc[s], 0, 0, 0, 127, 0, 127);
+          acc[s][0] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(cat8(wf[u][s][0], wf[u][s][1]), xf, acc[s][0], 0, 0, 0, 127, 0, 127);
       }
     }
   };
@@ -152,89 +148,26 @@ __global__ __launch_bounds__(256) void skinny8_kernel(const bf16_t* __restrict__
   run(std::integral_constant<int, 2>{});
   run(std::integral_constant<int, 1>{});
 
-  // ---- combine the four K slices (fixed order), then the P diagonal blocks ----
-  if (wave > 0) {
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) part[wave - 1][s][e][lane] = acc[s][e];
-  }
-  __syncthreads();
-  if (wave != 0) return;
-#pragma unroll
-  for (int s = 0; s < NS; ++s)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc[s][e] += (part[0][s][e][lane] + part[1][s][e][lane]) + part[2][s][e][lane];
-  if constexpr (P == 2) {
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[s][e] += __shfl(acc[s][e], (lane + 40) & 63, 64);
-  } else if constexpr (P == 4) {
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float v = acc[s][e];
-        acc[s][e] = ((v + __shfl(v, (lane + 20) & 63, 64)) + __shfl(v, (lane + 40) & 63, 64)) + __shfl(v, (lane + 60) & 63, 64);
-      }
-  }
-  const bool own = P == 1 || (fr < RS && fq < RS / 4);
-  const int r = own ? fr : R;
+  SKINNY_COMBINE(acc, part, 4, NS, 1, P, wave, lane)                // K slices and sub-slab blocks, fixed order (skinny_tiles.h)
+  const int r = g.own() ? g.fr : R;
   if (r >= R) return;
   // (acc * row scale) * channel scale: oracle/fp8.py's order
   const float rs = sx[r];
 #pragma unroll
   for (int s = 0; s < NS; ++s) {
-    const f32x4 cs = *(const f32x4*)(w_scale + n0 + s * SLAB_STEP + 4 * fq);
+    const f32x4 cs = *(const f32x4*)(w_scale + n0 + s * g.STEP + 4 * fq);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) acc[s][e] = (acc[s][e] * rs) * cs[e];
+    for (int e = 0; e < 4; ++e) acc[s][0][e] = (acc[s][0][e] * rs) * cs[e];
   }
   if constexpr (EPI == SK_ROPE_KV) {
-    const int hs = blockIdx.x / (64 / RS), d = (int)(blockIdx.x % (64 / RS)) * RS + 4 * fq;   // head slot; dims d .. d+3 and d+64 .. d+67
-    const int slot = hs % (rk.g + 2), gi = hs / (rk.g + 2);
-    const int p = rk.pos[r];
-    u16x4 olo, ohi;
-    if (slot <= rk.g) {
-      const u16x4 co = *(const u16x4*)(rk.cos + (size_t)p * 64 + d), si = *(const u16x4*)(rk.sin + (size_t)p * 64 + d);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float x1 = rbf(acc[0][e]), x2 = rbf(acc[1][e]), cc = bf2f(co[e]), ss = bf2f(si[e]);
-        olo[e] = f2bf(rbf(x1 * cc) + rbf(-x2 * ss));
-        ohi[e] = f2bf(rbf(x2 * cc) + rbf(x1 * ss));
-      }
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { olo[e] = f2bf(acc[0][e]); ohi[e] = f2bf(acc[1][e]); }
-    }
-    bf16_t* dst = slot < rk.g ? out + (size_t)r * ldo + (size_t)hs * 128 + d
-                              : (slot == rk.g ? rk.kc : rk.vc) + (((size_t)rk.seq[r] * rk.n_kv + gi) * rk.cap + p) * 128 + d;
-    *(u16x4*)dst = olo;
-    *(u16x4*)(dst + 64) = ohi;
+    SKINNY_ROPE_KV_STORE(RS, acc[0][0], acc[1][0], rk, r, fq, out, ldo)
   } else if constexpr (EPI == SK_SWIGLU) {
-    const int n = (int)(blockIdx.x / P) * 16 + (int)(blockIdx.x % P) * RS + 4 * fq;
-    *(u16x4*)(out + (size_t)r * ldo + n) = epi_swiglu4(acc[0], acc[1]);
+    *(u16x4*)(out + (size_t)r * ldo + g.swiglu_col()) = epi_swiglu4(acc[0][0], acc[1][0]);
   } else {
     const int n = n0 + 4 * fq;
     const u16x4 rr = *(const u16x4*)(resid + (size_t)r * ldr + n);
-    *(u16x4*)(out + (size_t)r * ldo + n) = epi_row4<EPI_RESID>(epi_acc4<EPI_RESID>(acc[0], false, u16x4{}, u16x4{}), rr);
+    *(u16x4*)(out + (size_t)r * ldo + n) = epi_row4<EPI_RESID>(epi_acc4<EPI_RESID>(acc[0][0], false, u16x4{}, u16x4{}), rr);
   }
-}
-
-template <int EPI, bool NORM, int NCH>
-hipError_t launch8p(int p, int blocks, size_t lds, hipStream_t s, const bf16_t* x, int ldx, int R, const uint8_t* W8, int ldw, const float* w_scale, int N,
-                    int K, const bf16_t* resid, int ldr, bf16_t* out, int ldo, const AigvRopeKv& rk, const bf16_t* norm_w, float eps) {
-  // the quantised rows of a long-K GEMV (4 x 16384 bytes) exceed the default dynamic-LDS limit
-#define GO(PP)                                                                                                                                        \
-  do {                                                                                                                                                \
-    static LdsAttrOnce lds_attr;                                                                                                                     \
-    if (hipError_t e = lds_attr.ensure((const void*)skinny8_kernel<EPI, NORM, NCH, PP>, 4 * 16384); e != hipSuccess) return e; \
-    hipLaunchKernelGGL((skinny8_kernel<EPI, NORM, NCH, PP>), dim3(blocks), dim3(256), lds, s, x, ldx, R, W8, ldw, w_scale, N, K, resid, ldr, out, ldo, \
-                       rk, norm_w, eps);                                                                                                              \
-  } while (0)
-  if (p == 1) GO(1); else if (p == 2) GO(2); else GO(4);
-#undef GO
-  return hipGetLastError();
 }
 
 }  // namespace
@@ -249,29 +182,28 @@ hipError_t aigv_launch_skinny_fp8(const bf16_t* x, int ldx, int R, const uint8_t
       (ldx % 8) || (ldw % 16) || (ldo % 4) || !x || !W8 || !w_scale || !out)
     return hipErrorInvalidValue;
   const int rs = 16 / p, nch = K / 2048;
-  const size_t lds = (size_t)R * K;
   const AigvRopeKv none{};
+  auto go = [&](auto etag, auto nchtag, int blocks) {
+    return with_int<1, 2, 4>(p, [&](auto ptag) {
+      constexpr int EPI = decltype(etag)::value;
+      auto* kernel = skinny8_kernel<EPI, EPI != SK_RESID, decltype(nchtag)::value, decltype(ptag)::value>;
+      static LdsAttrOnce lds_attr;   // the quantised rows of a long-K GEMV (4 x 16384 bytes) exceed the default dynamic-LDS limit
+      if (hipError_t e = lds_attr.ensure((const void*)kernel, 4 * 16384); e != hipSuccess) return e;
+      hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), (size_t)R * K, s, x, ldx, R, W8, ldw, w_scale, N, K, resid, ldr, out, ldo, rk ? *rk : none, norm_w, eps);
+      return hipGetLastError();
+    });
+  };
   if (epi == SK_ROPE_KV) {
     if (!rk || !norm_w || N % 128 || N != rk->n_kv * (rk->g + 2) * 128) return hipErrorInvalidValue;
-    const int blocks = N / 128 * (64 / rs);
-    return nch == 2 ? launch8p<SK_ROPE_KV, true, 2>(p, blocks, lds, s, x, ldx, R, W8, ldw, w_scale, N, K, nullptr, 0, out, ldo, *rk, norm_w, eps)
-                    : launch8p<SK_ROPE_KV, true, 3>(p, blocks, lds, s, x, ldx, R, W8, ldw, w_scale, N, K, nullptr, 0, out, ldo, *rk, norm_w, eps);
+    return with_int<2, 3>(nch, [&](auto c) { return go(int_c<SK_ROPE_KV>{}, c, N / 128 * (64 / rs)); });
   }
   if (epi == SK_SWIGLU) {
     if (!norm_w || N % 32) return hipErrorInvalidValue;
-    const int blocks = N / 32 * p;
-    return nch == 2 ? launch8p<SK_SWIGLU, true, 2>(p, blocks, lds, s, x, ldx, R, W8, ldw, w_scale, N, K, nullptr, 0, out, ldo, none, norm_w, eps)
-                    : launch8p<SK_SWIGLU, true, 3>(p, blocks, lds, s, x, ldx, R, W8, ldw, w_scale, N, K, nullptr, 0, out, ldo, none, norm_w, eps);
+    return with_int<2, 3>(nch, [&](auto c) { return go(int_c<SK_SWIGLU>{}, c, N / 32 * p); });
   }
   if (epi == SK_RESID) {
     if (norm_w || !resid || N % rs || (ldr % 4)) return hipErrorInvalidValue;
-    const int blocks = N / rs;
-    switch (nch) {
-      case 2: return launch8p<SK_RESID, false, 2>(p, blocks, lds, s, x, ldx, R, W8, ldw, w_scale, N, K, resid, ldr, out, ldo, none, nullptr, 0.f);
-      case 3: return launch8p<SK_RESID, false, 3>(p, blocks, lds, s, x, ldx, R, W8, ldw, w_scale, N, K, resid, ldr, out, ldo, none, nullptr, 0.f);
-      case 7: return launch8p<SK_RESID, false, 7>(p, blocks, lds, s, x, ldx, R, W8, ldw, w_scale, N, K, resid, ldr, out, ldo, none, nullptr, 0.f);
-      case 8: return launch8p<SK_RESID, false, 8>(p, blocks, lds, s, x, ldx, R, W8, ldw, w_scale, N, K, resid, ldr, out, ldo, none, nullptr, 0.f);
-    }
+    return with_int<2, 3, 7, 8>(nch, [&](auto c) { return go(int_c<SK_RESID>{}, c, N / rs); });
   }
   return hipErrorInvalidValue;
 }

@@ -285,8 +285,9 @@ hipError_t aigv_launch_rope(bf16_t* qkv, int ld, const int32_t* pos, const bf16_
 // token embedding + visual/motion scatter: slot[t] < 0 -> tok_emb[ids[t]]; < n_vis -> vis[slot]; else motion
 hipError_t aigv_launch_embed(const int64_t* ids, const int32_t* slot, const bf16_t* emb, const bf16_t* vis,
                              const bf16_t* motion, int n_vis, bf16_t* out, int tokens, int H, hipStream_t s);
-// skinny (R <= 64) weight-streaming GEMM (head.hip; e4m3 forms: head8.hip) and its epilogues; aigv_launch_skinny_gemm takes SK_STORE (+bias),
-// SK_RESID, SK_SWIGLU, SK_GELU (+bias) and SK_LS_RESID
+// skinny (R <= 64) weight-streaming GEMM (head.hip; e4m3 forms: head8.hip; what the two kernels share - slab geometry, K-slice combine, RoPE /
+// KV-append epilogue - is skinny_tiles.h) and its epilogues; aigv_launch_skinny_gemm takes SK_STORE (+bias), SK_RESID, SK_SWIGLU, SK_GELU (+bias)
+// and SK_LS_RESID
 enum { SK_STORE = 0, SK_RESID = 1, SK_SWIGLU = 2, SK_GELU = 3, SK_ARGMAX = 4, SK_RELU = 5, SK_LS_RESID = 6, SK_ROPE_KV = 7, SK_ARGMAX_LSE = 8, SK_ARGMAX_LSE_STORE = 9 };
 hipError_t aigv_launch_skinny_gemm(const bf16_t* x, int ldx, int R, const bf16_t* W, int ldw, int N, int K,
                                    const bf16_t* bias, const bf16_t* resid, int ldr, bf16_t* out, int ldo, int epi,
@@ -296,7 +297,7 @@ hipError_t aigv_launch_skinny_gemm(const bf16_t* x, int ldx, int R, const bf16_t
 // same result up to fp32 summation order, 2x / 4x the workgroups - for widths whose 16-row slabs leave CUs unevenly loaded
 // e4m3 form of the decode GEMVs (head8.hip; fp8 mode of the InternLM2 linears).  epi: 1 residual, 2 swiglu, 7 wqkv with RoPE + KV append
 // (rk); norm_w != null: the RMSNorm in front of the linear is applied by the kernel.  R <= 4 rows; W8 [N][ldw bytes] e4m3, w_scale [N]
-struct AigvRopeKv {
+struct AigvRopeKv {                            // the RoPE / KV-append arguments of SK_ROPE_KV, bf16 and e4m3 form alike (SKINNY_ROPE_KV_STORE, skinny_tiles.h)
   const int32_t* pos; const int32_t* seq;      // position / cache sequence of every x row (device)
   const bf16_t* cos; const bf16_t* sin;        // [max_pos, 64]
   bf16_t* kc; bf16_t* vc;                      // [seq][kv head][cap][128]

@@ -212,7 +212,9 @@ SHAPES_FP8 = [(M, 256, K) for M in (1, 257) for K in (128, 256)]
 COST_MODEL = {
     # feature: (M, N, K, epi, what the plan must show)
     "skinny_remainder": (1, 256, 128, 0, lambda p: p[4] == 1 and p[3] == 1),                          # the smallest
-    "skinny_remainder_ls_resid": (33, 256, 128, 2, lambda p: p[4] == 1 and p[3] == 33),
+    "skinny_remainder_ls_resid": (33, 256, 128, 2, lambda p: p[4] == 1 and p[3] == 33),                # three row tiles of the skinny kernel
+    "skinny_remainder_ls_resid_2_tiles": (17, 256, 128, 2, lambda p: p[4] == 1 and p[3] == 17),
+    "skinny_remainder_ls_resid_4_tiles": (64, 256, 128, 2, lambda p: p[4] == 1 and p[3] == 64),
     "splitk_last_band_128": (1, 256, 960, 3, lambda p: p[4] == 2 and p[5] > 1),                       # the smallest
     "splitk_last_band_128_ragged": (130, 256, 960, 2, lambda p: p[4] == 2 and p[5] > 1),
     "splitk_mid_band_256": (1280, 3328, 3840, 2, lambda p: p[1] > 0 and p[2] > 1),

@@ -255,7 +255,7 @@ def _inputs(R, N, K, seed):
     return x.cuda(), W.cuda(), gw.cuda()
 
 
-@pytest.mark.parametrize("R,p,K,g,n_kv", [(1, 1, 512, 4, 2), (3, 1, 512, 4, 2), (4, 1, 1024, 4, 2), (17, 1, 512, 6, 1), (64, 1, 384, 1, 3),
+@pytest.mark.parametrize("R,p,K,g,n_kv", [(1, 1, 512, 4, 2), (3, 1, 512, 4, 2), (4, 1, 1024, 4, 2), (17, 1, 512, 6, 1), (64, 1, 384, 1, 3), (33, 1, 128, 1, 1),
                                           (8, 2, 1024, 4, 2), (3, 2, 512, 2, 2), (4, 4, 1024, 4, 2), (1, 4, 2048, 8, 1)])
 def test_rope_kv_gemv_matches_reference(lib, R, p, K, g, n_kv):
     """Rows with their own cache sequence and position: query slots rotated into the qkv row, K rotated and V as computed into
@@ -266,7 +266,7 @@ def test_rope_kv_gemv_matches_reference(lib, R, p, K, g, n_kv):
     _rope_kv_case(lib, x, W, g, n_kv, p, want_y)
 
 
-@pytest.mark.parametrize("R,p,K", [(1, 1, 4096), (4, 1, 6144), (3, 2, 4096), (4, 4, 6144), (2, 4, 4096)])
+@pytest.mark.parametrize("R,p,K", [(1, 1, 4096), (4, 1, 6144), (3, 2, 4096), (4, 4, 6144), (2, 4, 4096), (2, 2, 6144)])
 def test_rope_kv_gemv_fused_norm_is_rmsnorm_then_the_gemv(lib, R, p, K):
     """norm_w: the kernel normalises the raw residual rows itself - the same bits as aigv_op_rmsnorm followed by the plain form."""
     g, n_kv = 4, 2
@@ -280,7 +280,7 @@ def test_rope_kv_gemv_fused_norm_is_rmsnorm_then_the_gemv(lib, R, p, K):
         assert torch.equal(a.view(torch.int16), b.view(torch.int16))
 
 
-@pytest.mark.parametrize("R,p,K,N", [(1, 1, 4096, 1024), (4, 2, 6144, 512), (3, 4, 4096, 768), (2, 1, 6144, 256)])
+@pytest.mark.parametrize("R,p,K,N", [(1, 1, 4096, 1024), (4, 2, 6144, 512), (3, 4, 4096, 768), (2, 1, 6144, 256), (2, 2, 4096, 64), (4, 4, 6144, 64)])
 def test_swiglu_normed_gemv_is_rmsnorm_then_the_swiglu_gemv(lib, R, p, K, N):
     x, W, gw = _inputs(R, N, K, seed=3 * R + p + K + N)
     xn = _rmsnorm(lib, x, gw)

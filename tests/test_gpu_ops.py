@@ -705,7 +705,9 @@ def test_attention_with_fused_query_rope_equals_rope_then_attention(lib):
 # ---------------------------------------------------------------------------------------------------------
 # skinny GEMM / lm-head argmax
 # ---------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("R,N,K,epi", [(5, 272, 256, 0), (16, 512, 384, 1), (33, 256, 1152, 3), (64, 640, 256, 2), (1, 128, 128, 0)])
+@pytest.mark.parametrize("R,N,K,epi", [(5, 272, 256, 0), (16, 512, 384, 1), (33, 256, 1152, 3), (64, 640, 256, 2), (1, 128, 128, 0),
+                                       # two and three row tiles of every epilogue, at the smallest legal shape (one workgroup, one k-step per K slice)
+                                       (17, 16, 128, 0), (33, 16, 128, 0), (17, 16, 128, 1), (33, 16, 128, 1), (17, 32, 128, 2), (33, 32, 128, 2), (17, 16, 128, 3)])
 def test_skinny_gemm(lib, R, N, K, epi):
     from aigv_assessor_amd.native import ptr
     g = torch.Generator().manual_seed(R + N + K)
@@ -750,7 +752,7 @@ def test_skinny_gemm_sub_slab_forms(lib, p, R, N, K, epi):
     assert (outs[0] != outs[1]).float().mean() < 0.03            # the two forms differ by summation order only
 
 
-@pytest.mark.parametrize("R,V,H", [(10, 1009, 256), (40, 92553, 512), (64, 4099, 128)])
+@pytest.mark.parametrize("R,V,H", [(10, 1009, 256), (20, 1009, 256), (40, 92553, 512), (64, 4099, 128)])       # one to four row tiles
 def test_lm_head_argmax_first_max_on_ties(lib, R, V, H):
     from aigv_assessor_amd.native import ptr
     g = torch.Generator().manual_seed(V)
@@ -971,7 +973,7 @@ def test_fp8_gemm_epilogues(lib, M, N, K, epi):
 
 @pytest.mark.parametrize("p", [1, 2, 4])
 @pytest.mark.parametrize("R,N,K,epi,norm", [(1, 512, 4096, 1, False), (3, 256, 14336, 1, False), (4, 1024, 4096, 2, True), (2, 384, 6144, 2, True),
-                                            (1, 128, 16384, 1, False)])
+                                            (1, 128, 16384, 1, False), (2, 128, 6144, 1, False)])
 def test_fp8_decode_gemv(lib, p, R, N, K, epi, norm):
     """The e4m3 form of the decode GEMVs (csrc/head8.hip): the kernel normalises (optionally) and quantises the x rows itself; the
     result is the fp8 mode's definition (oracle/fp8.py: per-row / per-channel scales, exact products, fp32 sums) with the bf16

@@ -97,7 +97,7 @@ def run_score_head(lib, x, dims, Ws, bs, ldx=None):
     return got[FENCE:FENCE + B].clone()
 
 
-@pytest.mark.parametrize("B", [1, 3, 17, 64])
+@pytest.mark.parametrize("B", [1, 3, 17, 40, 64])         # one to four row tiles of the GEMM layers
 @pytest.mark.parametrize("dims", CHAINS, ids=lambda d: "-".join(map(str, d)))
 def test_score_head_exact_arithmetic(lib, dims, B):
     """Sparse dyadic weights, biases and inputs: every sum is a bf16 number (asserted on the CPU first), so the score must EQUAL the
@@ -193,6 +193,35 @@ def test_score_head_guard_stays_off_without_a_nan(lib):
     got = run_score_head(lib, x, PRODUCTION, Ws, bs)
     assert torch.equal(torch.isnan(got), torch.isnan(want)) and torch.equal(torch.isinf(got), torch.isinf(want)), (got.tolist(), want.tolist())
     assert torch.allclose(got, want, rtol=0, atol=0, equal_nan=True), (got.tolist(), want.tolist())
+
+
+@pytest.mark.parametrize("dirty", [False, True], ids=["finite", "nan-and-inf"])
+@pytest.mark.parametrize("B", [1, 3, 64])
+@pytest.mark.parametrize("dims", CHAINS, ids=lambda d: "-".join(map(str, d)))
+def test_score_head_is_the_one_group_case_of_the_grouped_op(lib, dims, B, dirty):
+    """aigv_op_score_head(x, B) and aigv_op_score_head_groups(x, G = 1, stride 0, B): the same bits, with a NaN in one row and an Inf in
+    another (the guard fires for the slice) and without."""
+    g = torch.Generator().manual_seed(7000 + B + len(dims))
+    Ws = [(torch.randn(o, i, generator=g) * (2.0 / i) ** 0.5).to(BF) for i, o in zip(dims[:-1], dims[1:])]
+    bs = [(0.1 * torch.randn(o, generator=g) + 0.05).to(BF) for o in dims[1:]]
+    x = torch.randn(B, dims[0], generator=g).to(BF)
+    if dirty:
+        x[B // 2, 3] = float("nan")
+        x[B - 1, 7] = float("inf")
+    single = run_score_head(lib, x, dims, Ws, bs)
+    n = len(Ws)
+    xd, wd, bd = dev(x), [dev(w) for w in Ws], [dev(b) for b in bs]
+    wp, bp = (ctypes.c_void_p * n)(*[ptr(w) for w in wd]), (ctypes.c_void_p * n)(*[ptr(b) for b in bd])
+    n_scratch = 3 * B * max(dims)
+    scratch_whole, scratch = fenced(sentinel_like((n_scratch,), BF))
+    score_whole, score = fenced(sentinel_like((B,), torch.float32))
+    sync(lib.aigv_op_score_head_groups(ptr(xd), dims[0], 1, 0, B, n, i32(dims), wp, bp, ptr(scratch), n_scratch * 2, ptr(score), None), lib)
+    grouped = score_whole.cpu()[FENCE:FENCE + B]
+    assert torch.equal(grouped.view(torch.int32), single.view(torch.int32)), (grouped.tolist(), single.tolist())
+    sw = scratch_whole.cpu().view(torch.int16)
+    fence16 = torch.full((FENCE,), SENTINEL[BF], dtype=torch.int16)
+    assert torch.equal(sw[:FENCE], fence16) and torch.equal(sw[FENCE + n_scratch:], fence16), "scratch fences"
+    assert dirty or torch.isfinite(single).all()
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -213,6 +213,26 @@ def test_op_lm_head_topk_holds_the_lm_heads_own_bits(V, H):
         assert torch.equal(t, full[0][:R]) and torch.equal(bits(tl), bits(full[1][:R])), R
 
 
+def test_op_lm_head_topk_at_four_row_tiles():
+    """R = 64: the four-row-tile form of the storing lm-head (the test above stops at three) - the stored logits' top-k in the key's order, and
+    the argmax / log-prob bits of the form that stores nothing."""
+    lib = native.load()
+    V, H, R, k = 2053, 128, 64, 5
+    g = torch.Generator(device="cuda").manual_seed(V + R)
+    h = torch.randn((R, H), generator=g, device="cuda").to(BF)
+    W = (torch.randn((V, H), generator=g, device="cuda") * 0.05).to(BF)
+    W[V - 1] = W[3]
+    idx0, val0, lp0 = _argmax_logprob(lib, h, W, V)
+    logits = _store_logits(lib, h, W, V).cpu()
+    idx, val, lp, tid, tlp, _ = _argmax_topk_logprob(lib, h, W, V, k)
+    torch.cuda.synchronize()
+    assert torch.equal(idx, idx0) and torch.equal(bits(val), bits(val0)) and torch.equal(bits(lp), bits(lp0))
+    assert torch.equal(tid.cpu(), stable_topk(logits, k))
+    assert torch.equal(tid[:, 0], idx) and torch.equal(bits(tlp[:, 0]), bits(lp))
+    err = (tlp.cpu().double() - torch.log_softmax(logits.double(), -1).gather(-1, tid.cpu())).abs().max().item()
+    assert err <= 1e-5, err
+
+
 # ---- 3. the scoring pass -------------------------------------------------------------------------------------------------------------
 
 def _ragged_batch(cfg, seed, T=2):
