@@ -92,10 +92,22 @@ template <> struct RowSel<false> {};
 // NB = K/V ring depth: tile t is multiplied while tiles t+1 .. t+NB-2 are in flight behind a counted vmcnt.
 // RS = the reference's rounding points of the SCORE matrix (AttnArgs::round_scores): s1 = bf16(q k^T) and, where the division that
 // follows is not a power of two (InternLM2: / sqrt(128)), s2 = bf16(s1 / post_div); the softmax then runs in fp32 on those values.
-// DROP = the key-drop form (AttnArgs::key_drop; d = 128 causal only): one 64-bit word per sequence and key tile, bit j & 63 of word j >> 6 set =
-// key j (absolute position, cached keys first) is invisible to every query row and head.  The word is wave-uniform (one scalar load per tile,
-// requested a tile ahead); a tile whose word is zero runs exactly the unmasked path, a tile whose word is all ones is skipped like a tile in
+// DROP = the key-drop form (AttnArgs::key_drop; causal d = 128, non-causal d = 64 and 128): one 64-bit word per sequence and key tile, bit j & 63 of
+// word j >> 6 set = key j (absolute position, cached keys first) is invisible to every query row and head.  The word is wave-uniform (one scalar load
+// per tile, requested a tile ahead); a tile whose word is zero runs exactly the unmasked path, a tile whose word is all ones is skipped like a tile in
 // the causal future, every other tile takes the mask loop with one more bit test per score.  DROP = false compiles to the code it always was.
+// The non-causal form (InternViT: the packed layout only, aigv_attn_check) meets what the causal one never does:
+//   - a skipped tile can be the FIRST of a wave's walk (causal: a row that sees key 0 computes tile 0 or skips it with every later one).  A skip leaves
+//     m = -inf, l = 0, O = 0 untouched, which is the state the next computed tile starts from like tile 0 does: its first maximum is an infinite jump,
+//     alpha = exp2(-inf) = 0 scales the zero accumulators;
+//   - the ragged last tile (1025 = 16 x 64 + 1) with its one valid key dropped: no visible key, but a word that is not all ones.  It takes the mask loop
+//     with every score -inf: tmax = -inf moves no maximum (-inf - -inf compares false; -inf - m < 8), mc = 0 under m = -inf, every p = exp2(-inf) = +0 -
+//     l and O gain exact zeros (the tile's V rows are re-reads of the dropped key's row: finite by the contract);
+//   - the key split: a wave applies the word of the tile it computes (every wave loads every tile's word: the load is wave-uniform and the walk shared);
+//     a wave whose tiles are all dropped or skipped publishes m = -inf, l = 0, O = 0, which the merge weighs with 0 by its m == -inf tests, never with
+//     exp2(-inf - -inf); when every wave does, M = -inf, l = 0 and the row is written as zeros like any row without a visible key;
+//   - the lead key: with it the loop's key index is the absolute position minus one, so words would no longer cover tiles.  The masked form runs with
+//     lead = 0 whatever AttnArgs::lead_key says - under a zero mask its bits are those of the unmasked kernel with the knob off, the default.
 // ROWS = the row-selective key-drop form (AttnArgs::drop_rows; needs DROP, packed prefill only: a row's position is its index in its sequence): a score is
 // hidden iff its key's bit AND its query row's bit are set.  The row word is wave-uniform (one scalar load per wave, in the prologue), the key word stays
 // the one load per tile.  A wave none of whose rows is selected treats every tile's key word as zero - the unmasked path; a wave all of whose rows are
@@ -105,8 +117,8 @@ template <> struct RowSel<false> {};
 template <int D, bool CAUSAL, int NW, int NB, bool RS, bool DROP = false, bool ROWS = false>
 __global__ __launch_bounds__(NW * 64, (D == 64 && NW == 4) ? 4 : 2) void attn_fwd_kernel(
     const std::conditional_t<ROWS, AttnArgs, std::conditional_t<DROP, AttnArgsKeyDrop, AttnArgsUnmasked>> p) {
-  static_assert(!DROP || (D == 128 && CAUSAL), "the key-drop form exists for the causal d = 128 kernel only");
-  static_assert(!ROWS || DROP, "the row selector qualifies a key-drop mask");
+  static_assert(!DROP || D == 128 || !CAUSAL, "the causal key-drop form exists for d = 128 only");
+  static_assert(!ROWS || (DROP && CAUSAL), "the row selector qualifies a causal key-drop mask");
   constexpr int QB = NW * 32;                // query rows per workgroup
   constexpr int ROWB = Lay<D>::ROWB;
   constexpr int CPR = D / 8;                 // 16-byte chunks per row
@@ -169,7 +181,7 @@ __global__ __launch_bounds__(NW * 64, (D == 64 && NW == 4) ? 4 : 2) void attn_fw
   // registers are free).  OPT-IN: -2 % on the InternViT shape in-step and statistically neutral on the 13 reference-recorded clips (mean 2.96
   // against 3.19 bf16 ulps from the reference's scores), but another fp32 summation order re-rolls each clip's rounding noise, and the recorded
   // per-batch numbers of the default path are kept as they are (profiles/r4_attn_stagger_negative.txt, 6).
-  const int lead = (!CAUSAL && p.lead_key && kv_off == 0 && (kv_all % KT) == 1) ? 1 : 0;
+  const int lead = (!CAUSAL && !DROP && p.lead_key && kv_off == 0 && (kv_all % KT) == 1) ? 1 : 0;   // (the key-drop form: never, see DROP)
   const int kv_len = kv_all - lead;               // keys the tile loop covers (K / V tile bases advance by `lead` rows)
   // Ragged last block of a NON-causal sequence with at most 32 rows (ViT: 1025 = 8 x 128 + 1): instead of one wave doing the
   // whole key range for those rows while three idle - the block would last as long as a full one - all waves take the SAME
@@ -298,7 +310,7 @@ __global__ __launch_bounds__(NW * 64, (D == 64 && NW == 4) ? 4 : 2) void attn_fw
   const int tr_key = 4 * (gi >> 1) + (li >> 2);       // + 32*st + 16*s + 8*jh
   const int tr_dcol = 16 * (gi & 1) + 4 * (li & 3);   // + 32*dt
 
-  // key-drop words of this sequence: word kt covers keys [64 kt, 64 kt + 64) (lead = 0 in the causal form: the loop's key index is the absolute one)
+  // key-drop words of this sequence: word kt covers keys [64 kt, 64 kt + 64) (lead = 0 in the key-drop forms: the loop's key index is the absolute one)
   [[maybe_unused]] DropTile<DROP> dk;
   if constexpr (DROP) {
     dk.row = p.key_drop + (size_t)seq * p.ld_drop;
@@ -881,7 +893,7 @@ extern "C" int aigv_debug_attn_stamps(unsigned long long* out32, int reset) {   
 }
 #endif
 
-const char* aigv_attn_check(const AttnArgs& a, int head_dim) {
+const char* aigv_attn_check(const AttnArgs& a, int head_dim, bool drop_noncausal) {
   if (head_dim != 64 && head_dim != 128) return "attention: head_dim must be 64 or 128";
   if (a.n_seq <= 0 || a.max_len <= 0) return "attention: empty problem";
   if (a.n_kv_heads <= 0 || a.n_heads % a.n_kv_heads) return "attention: n_heads must be a multiple of n_kv_heads";
@@ -891,6 +903,15 @@ const char* aigv_attn_check(const AttnArgs& a, int head_dim) {
   if ((a.kv_len_offset != 0 || a.kv_off) && !a.kv_seq_stride) return "attention: a key offset needs K/V in cache layout (kv_seq_stride)";
   if (a.kv_len_offset < 0 || (a.kv_seq_stride % 8)) return "attention: bad key offset / cache stride";
   if ((a.rope_cos != nullptr) != (a.rope_sin != nullptr) || (a.rope_cos && !a.rope_pos)) return "attention: query RoPE needs positions, cos and sin";
+  if (a.key_drop && drop_noncausal) {   // the non-causal key-drop form (InternViT): the packed layout, every row under the mask, every row computed
+    if (a.causal) return "attention: the non-causal key_drop form was asked for with causal != 0";
+    if (a.kv_off || a.kv_len_offset != 0 || a.kv_seq_stride) return "attention: the non-causal key_drop form exists for the packed layout only (no kv_off, no kv_len_offset, no kv_seq_stride)";
+    if (a.drop_rows) return "attention: drop_rows exists for the causal key_drop form only";
+    if (a.q_tail != 0) return "attention: the non-causal key_drop form takes no q_tail";
+    if ((uintptr_t)a.key_drop & 7) return "attention: key_drop must be 8-byte aligned";
+    if (a.ld_drop < ((long long)a.max_len + KT - 1) / KT) return "attention: ld_drop is below ceil(max_len / 64) words per sequence";
+    return nullptr;
+  }
   if (a.key_drop) {
     if (!a.causal || head_dim != 128) return "attention: key_drop exists for the causal head_dim 128 form only";
     if ((uintptr_t)a.key_drop & 7) return "attention: key_drop must be 8-byte aligned";
@@ -923,10 +944,13 @@ static hipError_t launch_attn_rs(const AttnArgs& a, hipStream_t s) {
 }
 template <int D, bool CAUSAL, int NW>
 static hipError_t launch_attn(const AttnArgs& a, hipStream_t s) {
-  if (a.key_drop) {   // the key-drop forms: d = 128 causal only (aigv_attn_check refuses the rest); a null pointer reaches the instantiations it always did
+  if (a.key_drop) {   // the key-drop forms: causal d = 128, non-causal d = 64 and 128 (aigv_attn_check refuses the rest); a null pointer reaches the instantiations it always did
     if constexpr (D == 128 && CAUSAL) {
       if (a.drop_rows)   // the row-selective form; a null selector reaches the key-drop instantiations it always did
         return a.round_scores ? launch_attn_rs<D, CAUSAL, NW, true, 2, true, true>(a, s) : launch_attn_rs<D, CAUSAL, NW, false, 2, true, true>(a, s);
+      return a.round_scores ? launch_attn_rs<D, CAUSAL, NW, true, 2, true>(a, s) : launch_attn_rs<D, CAUSAL, NW, false, 2, true>(a, s);
+    } else if constexpr (!CAUSAL) {
+      if (a.drop_rows) return hipErrorInvalidValue;
       return a.round_scores ? launch_attn_rs<D, CAUSAL, NW, true, 2, true>(a, s) : launch_attn_rs<D, CAUSAL, NW, false, 2, true>(a, s);
     } else
       return hipErrorInvalidValue;

@@ -151,6 +151,14 @@ struct aigv_ctx {
     float* out = nullptr;              // device, the caller's: [n_frames][hi - lo][S][S], per_head: [n_frames][hi - lo][vit_heads][S][S]
     int lo = 0, hi = 0, per_head = 0;
   } vmap;
+  // InternViT patch mask (aigv_vit_key_drop_arm): armed for exactly the next aigv_vit_forward, whose flash attention of every layer lo <= li < hi runs
+  // the non-causal key-drop form under the words of its chunk's frames, words + f0 * ld; the other layers run the unmasked kernel
+  struct {
+    bool armed = false;
+    const uint64_t* words = nullptr;   // device, the caller's: [n_frames][ld] words, AttnArgs::key_drop's layout (key 0 = cls, key 1 + grid * y + x = patch (y, x))
+    int ld = 0;
+    int lo = 0, hi = 0;
+  } vdrop;
   float2* v_mapstats = nullptr;        // [vit_chunk][vit_heads][S] (m, total) of the map's rows: owned by the context, nothing is allocated in the pass
   // key-drop mask (aigv_key_drop_arm / _ex): armed for exactly the next aigv_llm_prefill, which applies it in the attention of the layers
   // [layer_begin, layer_end) - every layer for aigv_key_drop_arm - to the query rows `rows` selects (null: every row); keep_kv, which takes

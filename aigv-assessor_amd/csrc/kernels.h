@@ -111,11 +111,16 @@ struct AttnArgsUnmasked {
   int q_begin;                  // the launch computes query rows >= q_begin (a multiple of the workgroup's 128 rows) only; 0 everywhere at present
 };
 struct AttnArgsKeyDrop : AttnArgsUnmasked {
-  // Key drop (causal head_dim 128 only; null = no key is dropped, the kernels that have always run): bit j & 63 of word
+  // Key drop (causal head_dim 128, and - where the caller asks aigv_attn_check for it - non-causal head_dim 64 / 128; null = no key is dropped, the
+  // kernels that have always run): bit j & 63 of word
   // key_drop[seq * ld_drop + (j >> 6)] set = key j of that sequence is invisible to every query row and head.  j is the key's absolute position
   // in its sequence, cached keys first - the packed form and the cache form (kv_off, kv_seq_stride) share the indexing; one word = one 64-key
   // tile.  ld_drop >= ceil((largest key offset + max_len) / 64); with kv_off the caller states that largest offset in kv_len_offset.  A row left
   // without a visible key is written as zeros.  The V rows of dropped keys must be finite (0 x NaN = NaN, as in torch).
+  // Non-causal form (InternViT's patch mask, aigv_vit_key_drop_arm): the packed layout only - no kv_off, kv_len_offset, kv_seq_stride, q_tail or drop_rows;
+  // ld_drop >= ceil(max_len / 64).  A dropped key is hidden from its own row too.  It runs with the lead key OFF whatever lead_key says (with it the loop's
+  // key index is the absolute position minus one and words no longer cover tiles): under a zero mask the output is, bit for bit, that of the unmasked
+  // kernel with lead_key = 0, the default - NOT that of the unmasked kernel with the knob on.  Both workgroup sizes (waves) exist.
   const uint64_t* key_drop;     // device
   int ld_drop;                  // words per sequence
 };
@@ -126,7 +131,8 @@ struct AttnArgs : AttnArgsKeyDrop {
   // kv_len_offset), where a row's position is its index in its sequence.  Bits at or past a sequence's length are ignored.
   const uint64_t* drop_rows;    // device
 };
-const char* aigv_attn_check(const AttnArgs& a, int head_dim);
+// drop_noncausal: the caller asks for the non-causal key-drop form; without it key_drop with causal == 0 (or head_dim 64) is refused as it always was
+const char* aigv_attn_check(const AttnArgs& a, int head_dim, bool drop_noncausal = false);
 hipError_t aigv_launch_attention(const AttnArgs& a, int head_dim, hipStream_t s);
 // decode: one query row per sequence (fused qkv row), KV cache [seq][kv head][cap][D]; split-KV two-pass kernel,
 // ws = aigv_attention_decode_ws_floats(...) floats of scratch.  The merge pass holds 16 bytes of LDS per 128-key chunk of the

@@ -184,8 +184,11 @@ static int attention_ex_op(const char* op, const void* q, int ldq, const void* k
                            int n_seq, int max_len, int n_heads, int n_kv_heads, int q_group_stride, int kv_head_stride, int64_t kv_seq_stride,
                            const int32_t* kv_off, int head_dim, int causal, float post_div, float q_prescale, const int32_t* pos, const void* cos,
                            const void* sin, int pos_is_row, int q_tail, const uint64_t* key_drop, int ld_drop, void* stream,
-                           const uint64_t* row_words = nullptr) {
+                           const uint64_t* row_words = nullptr, bool drop_noncausal = false) {
   if (!q || !k || !v || !o || !cu) return fail(nullptr, AIGV_ERR_ARG, "%s: null operand", op);
+  if (drop_noncausal && (causal & 1)) return fail(nullptr, AIGV_ERR_ARG, "%s: the non-causal key-drop form, got causal != 0 (aigv_op_attention_drop is the causal one)", op);
+  if (drop_noncausal && key_drop && (kv_off || kv_seq_stride))   // (here, in front of the read-back of kv_off below)
+    return fail(nullptr, AIGV_ERR_ARG, "%s: key_drop exists for the packed layout only (no kv_off, no kv_seq_stride)", op);
   if (row_words && !key_drop) return fail(nullptr, AIGV_ERR_ARG, "%s: row_words qualify a key_drop mask and need one", op);
   if (row_words && (kv_off || kv_seq_stride)) return fail(nullptr, AIGV_ERR_ARG, "%s: row_words exist for the packed prefill only (no kv_off, no kv_seq_stride)", op);
   if (q_tail < 0) return fail(nullptr, AIGV_ERR_ARG, "%s: q_tail = %d must not be negative", op, q_tail);
@@ -216,7 +219,7 @@ static int attention_ex_op(const char* op, const void* q, int ldq, const void* k
       }
     }
   }
-  if (const char* m = aigv_attn_check(a, head_dim)) return fail(nullptr, AIGV_ERR_ARG, "%s: %s", op, m);
+  if (const char* m = aigv_attn_check(a, head_dim, drop_noncausal)) return fail(nullptr, AIGV_ERR_ARG, "%s: %s", op, m);
   HIPCHK(nullptr, aigv_launch_attention(a, head_dim, (hipStream_t)stream));
   return 0;
 }
@@ -247,6 +250,16 @@ int aigv_op_attention_drop_rows(const void* q, int ldq, const void* k, int ldk, 
   return attention_ex_op("aigv_op_attention_drop_rows", q, ldq, k, ldk, v, ldv, o, ldo, cu, n_seq, max_len, n_heads, n_kv_heads, q_group_stride,
                          kv_head_stride, kv_seq_stride, kv_off, head_dim, causal, post_div, q_prescale, pos, cos, sin, pos_is_row, q_tail, key_drop, ld_drop,
                          stream, row_words);
+}
+
+// aigv_op_attention_ex under the NON-causal key-drop mask (InternViT's patch mask; null: the same call as aigv_op_attention_ex with causal == 0)
+int aigv_op_attention_nc_drop(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, const int32_t* cu, int n_seq,
+                              int max_len, int n_heads, int n_kv_heads, int q_group_stride, int kv_head_stride, int64_t kv_seq_stride,
+                              const int32_t* kv_off, int head_dim, int causal, float post_div, float q_prescale, const int32_t* pos, const void* cos,
+                              const void* sin, int pos_is_row, int q_tail, const uint64_t* key_drop, int ld_drop, void* stream) {
+  return attention_ex_op("aigv_op_attention_nc_drop", q, ldq, k, ldk, v, ldv, o, ldo, cu, n_seq, max_len, n_heads, n_kv_heads, q_group_stride,
+                         kv_head_stride, kv_seq_stride, kv_off, head_dim, causal, post_div, q_prescale, pos, cos, sin, pos_is_row, q_tail, key_drop, ld_drop,
+                         stream, nullptr, true);
 }
 
 // K / V slots of fused qkv rows -> the KV cache [seq][kv head][cap][head_dim]: the kernel aigv_llm_prefill (keep_kv) and aigv_llm_extend append with

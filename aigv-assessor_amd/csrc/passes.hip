@@ -52,7 +52,7 @@ static VitMapArgs vit_map_args(const aigv_ctx* c, int f0, int F, int li) {
 struct VitDisarmScope {   // the aigv_vit_forward that finds the context armed disarms it on every way out
   aigv_ctx* c;
   explicit VitDisarmScope(aigv_ctx* c_) : c(c_) {}
-  ~VitDisarmScope() { c->vmap.armed = false; }
+  ~VitDisarmScope() { c->vmap.armed = false; c->vdrop.armed = false; }
 };
 
 int aigv_vit_forward(aigv_ctx* c, const void* frames, int n_frames, void* out_tokens, void* stream) {
@@ -77,6 +77,14 @@ int aigv_vit_forward(aigv_ctx* c, const void* frames, int n_frames, void* out_to
       return fail(c, AIGV_ERR_ARG, "aigv_vit_forward: attention map armed for layers [%d, %d), outside 0 <= lo < hi <= %d, the layers the pass runs", vm.lo, vm.hi, n_layers);
     if (!c->v_mapstats) return fail(c, AIGV_ERR_STATE, "aigv_vit_forward: attention map armed on a context without its stats scratch");
     if (const char* m = aigv_vit_map_check(vit_map_args(c, 0, std::min(k.vit_chunk, n_frames), vm.lo), c->vit_head_dim)) return fail(c, AIGV_ERR_ARG, "aigv_vit_forward: %s", m);
+  }
+  const bool masked = c->vdrop.armed;
+  if (masked) {   // refused before anything is launched, like the map's window
+    const auto& vd = c->vdrop;
+    if (mapped) return fail(c, AIGV_ERR_ARG, "aigv_vit_forward: armed with both the attention map and a patch mask: the map kernel does not know the mask");
+    if (vd.lo < 0 || vd.lo >= vd.hi || vd.hi > n_layers)
+      return fail(c, AIGV_ERR_ARG, "aigv_vit_forward: patch mask armed for layers [%d, %d), outside 0 <= lo < hi <= %d, the layers the pass runs", vd.lo, vd.hi, n_layers);
+    if (vd.ld < (c->S + 63) / 64) return fail(c, AIGV_ERR_ARG, "aigv_vit_forward: patch mask with %d words per frame, below ceil(%d / 64)", vd.ld, c->S);
   }
   const size_t frame_elems = (size_t)k.num_channels * k.image_size * k.image_size;
   for (int f0 = 0; f0 < n_frames; f0 += k.vit_chunk) {
@@ -122,7 +130,9 @@ int aigv_vit_forward(aigv_ctx* c, const void* frames, int n_frames, void* out_to
         a.causal = 0; a.post_div = 1.0f; a.q_prescale = 1.0f / sqrtf((float)c->vit_head_dim);
         a.round_scores = c->attn_round_scores; a.waves = tune_knob(c, AIGV_TUNE_ATTN_WAVES); a.lead_key = tune_knob(c, AIGV_TUNE_ATTN_LEAD_KEY);
         a.uniform_len = 1;
-        if (const char* m = aigv_attn_check(a, c->vit_head_dim)) return fail(c, AIGV_ERR_ARG, "%s", m);
+        const bool drop = masked && li >= c->vdrop.lo && li < c->vdrop.hi;
+        if (drop) { a.key_drop = c->vdrop.words + (size_t)f0 * c->vdrop.ld; a.ld_drop = c->vdrop.ld; }   // (the chunk's own frames)
+        if (const char* m = aigv_attn_check(a, c->vit_head_dim, drop)) return fail(c, AIGV_ERR_ARG, "%s", m);
         ProfScope ps(c, AIGV_PROF_ATTN_VIT, 4.0 * F * (double)c->S * c->S * Hv, 2.0 * 4 * rows * (double)Hv, s);
         HIPCHK(c, aigv_launch_attention(a, c->vit_head_dim, s));
       }
@@ -157,6 +167,19 @@ int aigv_vit_attention_arm(aigv_ctx* c, float* out_dev, int layer_lo, int layer_
   auto& vm = c->vmap;
   vm.out = out_dev; vm.lo = layer_lo; vm.hi = layer_hi; vm.per_head = per_head ? 1 : 0;
   vm.armed = true;
+  return 0;
+}
+
+int aigv_vit_key_drop_arm(aigv_ctx* c, const uint64_t* words_dev, int ld_words, int layer_lo, int layer_hi) {
+  const char* op = "aigv_vit_key_drop_arm";
+  if (!c) return fail(c, AIGV_ERR_ARG, "%s: null context", op);
+  if (!words_dev) return fail(c, AIGV_ERR_ARG, "%s: null words_dev", op);
+  if ((uintptr_t)words_dev & 7) return fail(c, AIGV_ERR_ARG, "%s: words_dev must be 8-byte aligned", op);
+  if (ld_words < (c->S + 63) / 64) return fail(c, AIGV_ERR_ARG, "%s: ld_words = %d is below ceil(%d / 64) words per frame", op, ld_words, c->S);
+  // the window is refused by the PASS, with a message: it is what knows how many layers it runs (select_layer)
+  auto& vd = c->vdrop;
+  vd.words = words_dev; vd.ld = ld_words; vd.lo = layer_lo; vd.hi = layer_hi;
+  vd.armed = true;
   return 0;
 }
 

@@ -255,6 +255,24 @@ def vit_rollout(att, alpha: float = 0.5, layers=None):
     return out
 
 
+def _cells_to_patches(t):
+    """The ONE statement of which ViT patches a visual token's cell holds (``frame_heatmaps``' geometry paragraph): [..., g, g] over cells ->
+    [..., 2g, 2g] over patches, cell (r, c)'s value on its patches (y, x) in {2r, 2r + 1} x {2c, 2c + 1}.  ``pixel_heatmaps`` spreads heat with
+    it, ``cell_patches`` marks patches with it."""
+    return t.repeat_interleave(2, -2).repeat_interleave(2, -1)
+
+
+def cell_patches(cells):
+    """Bool [..., g, g] over visual tokens (cells, ``frame_heatmaps``' layout) -> bool [..., 2g, 2g] over ViT patches: the four patches of every
+    marked cell, by the index ``pixel_heatmaps`` spreads a cell's heat with - what ``vit_tokens(patch_drop=...)`` takes for a region picked on a
+    token heat map."""
+    import torch
+    cells = torch.as_tensor(cells)
+    if cells.dtype != torch.bool or cells.dim() < 2 or cells.shape[-1] != cells.shape[-2]:
+        raise ValueError(f"cell_patches: expected a bool tensor [..., g, g], got {cells.dtype} {tuple(cells.shape)}")
+    return _cells_to_patches(cells)
+
+
 def pixel_heatmaps(heat, rollout):
     """From visual tokens back to the pixels: ``heat`` is ``frame_heatmaps``' [B, F, g, g] (the score row's mass per visual token), ``rollout``
     is ``vit_rollout``'s [B * F, S, S] in clip-major frame order (frame f of clip b at index b * F + f), S = (2 g)^2 + 1; returns
@@ -274,7 +292,7 @@ def pixel_heatmaps(heat, rollout):
     n = 2 * g
     if rollout.shape[0] != B * F or rollout.shape[-1] != n * n + 1:
         raise ValueError(f"pixel_heatmaps: heat [B = {B}, F = {F}, g = {g}] needs rollout [{B * F}, {n * n + 1}, {n * n + 1}], got {tuple(rollout.shape)}")
-    rows = (heat.double() / 4.0).repeat_interleave(2, 2).repeat_interleave(2, 3).reshape(B * F, 1, n * n)      # the weight of rollout row 1 + 2g y + x
+    rows = _cells_to_patches(heat.double() / 4.0).reshape(B * F, 1, n * n)      # the weight of rollout row 1 + 2g y + x
     out = torch.empty(B * F, n * n + 1, dtype=torch.float64, device=heat.device)
     for i in range(B * F):                                                  # (a frame at a time: the float64 copy of one rollout matrix)
         out[i] = (rows[i] @ rollout[i, 1:].to(heat.device).double())[0]
@@ -430,6 +448,85 @@ def frame_ablation(model, *, pixel_values, input_ids, attention_mask, image_flag
         absent = ~units.any(-1)                                             # [B, F + 1]: the clip has no such frame
         ablated = ablated.masked_fill(absent.to(ablated.device), float("nan"))
         res.update(score1=base, ablated=ablated, delta=base[:, None] - ablated)
+    return res
+
+
+def patch_occlusion(model, *, pixel_values, input_ids, attention_mask, image_flags, labels=None, cell=4, frames=None, hide_tokens=True, **readout_kwargs):
+    """WHAT IF a region of a frame could not be read INSIDE the vision tower: occlusion sensitivity (Zeiler & Fergus 2014) without grey pixels.  Per
+    clip, per frame and per block of ``cell`` x ``cell`` visual tokens the batch is scored with the block's ViT patches (``cell_patches``) hidden, as
+    keys, from every row of their frame in every layer of the tower (``vit_tokens(patch_drop=...)``): pixels, positions, cls and every other patch
+    stay.  The hidden patches' own rows still carry their content into the block's own tokens; with ``hide_tokens`` those tokens are hidden from the
+    LLM as well (``forward(key_drop=...)``) and the delta is the region's whole contribution; without it the delta is what THE REST of the frame loses
+    when it cannot read the region.  ``cell`` must divide the token grid T (T * T = tokens per frame); ``frames``: the frame indices to sweep
+    (default: all F).  ``readout_kwargs`` (``motion_feature`` among them) go to every ``forward`` call.
+
+    The sweep shares ``frame_ablation``'s structure: InternViT (unmasked) and the SlowFast branch run ONCE; per frame index one masked ViT batch
+    holds, for every clip that has the frame, the frame repeated (T / cell)^2 + 1 times - an EMPTY mask first, the control, then one mask per
+    block; a variant's tokens are spliced into the base tokens (``forward(visual_tokens=...)``); one LLM pass per (frame index, block) over all B
+    clips, plus the control's.  ``delta`` is measured against the control, which went through the same ViT batch as the variants (InternViT is
+    batch-invariant: tests/test_gpu_vit_attention.py, a frame alone across a chunk boundary), so a block whose mask is empty gives 0 exactly.
+    ``control`` has ``score1``'s bits unless the lead-key tune knob is on (the masked attention kernel runs without it).
+
+    Returns a dict: ``outs`` - the base result dict, then per swept frame index the control's and the blocks', row-major; ``blocks`` - bool
+    [T / cell, T / cell, T, T], the cells of every block; and for a stage-2 model ``score1`` [B] (the base scores, fp32), ``control`` [B, F],
+    ``occluded`` [B, F, T / cell, T / cell] (NaN where the clip lacks the frame or the frame was not swept) and ``delta`` = ``control[:, :, None,
+    None] - occluded``: positive where the region raised the score."""
+    import math
+    import torch
+    B, NF = int(input_ids.shape[0]), int(pixel_values.shape[0])
+    T = math.isqrt(int(model.num_image_token))
+    v = model.config.vision_config
+    if T * T != model.num_image_token or 2 * T != model.config.image_size // v.patch_size:
+        raise ValueError(f"patch_occlusion: {model.num_image_token} tokens per frame are no T x T grid of 2 x 2 patch cells")
+    cell = int(cell)
+    if cell < 1 or T % cell:
+        raise ValueError(f"patch_occlusion: cell = {cell} does not divide the token grid {T}")
+    nb = T // cell
+    blocks = torch.zeros(nb, nb, T, T, dtype=torch.bool)
+    for r in range(nb):
+        for c in range(nb):
+            blocks[r, c, r * cell:(r + 1) * cell, c * cell:(c + 1) * cell] = True
+    units = model.unit_masks(input_ids, attention_mask, image_flags, n_frames=NF)[:, :-1]                      # host bool [B, F, N]: frame f's tokens
+    F = int(units.shape[1])
+    has = units.any(-1)                                                                                        # [B, F]
+    sweep = list(range(F)) if frames is None else [int(f) for f in frames]
+    if any(not 0 <= f < F for f in sweep) or len(set(sweep)) != len(sweep):
+        raise ValueError(f"patch_occlusion: frames = {frames!r} are not distinct indices in 0..{F - 1}")
+    flags = None if image_flags is None else image_flags.detach().to("cpu").reshape(-1)
+    keep = torch.arange(NF) if flags is None else (flags == 1).nonzero().flatten()                             # the frames the clips' visual tokens come from, in order
+    first = [0] + torch.cumsum(has.sum(1), 0).tolist()                                                         # clip b's frame f is keep[first[b] + f]
+    common = _once_per_batch(model, pixel_values, readout_kwargs, input_ids=input_ids, attention_mask=attention_mask, image_flags=image_flags, labels=labels)
+    base_tokens = common.pop("visual_tokens")
+    outs = [model.forward(visual_tokens=base_tokens, **common)]
+    patch_masks = torch.cat([torch.zeros(1, 2 * T, 2 * T, dtype=torch.bool), cell_patches(blocks).view(nb * nb, 2 * T, 2 * T)])      # [1 + blocks, G, G], the control first
+    nv = patch_masks.shape[0]
+    for f in sweep:
+        clips = [b for b in range(B) if bool(has[b, f])]                                                       # (never empty: the longest clip has every f < F)
+        src = [int(keep[first[b] + f]) for b in clips]
+        pv = pixel_values[src].repeat_interleave(nv, 0)                                                        # clip-major, variant-minor
+        variants = model.vit_tokens(pv, patch_drop=patch_masks.repeat(len(clips), 1, 1)).view(len(clips), nv, *base_tokens.shape[1:])
+        for i in range(nv):
+            tokens = base_tokens.clone()
+            tokens[src] = variants[:, i]
+            kw = {}
+            if hide_tokens and i > 0:
+                keys = torch.zeros(units.shape[0], units.shape[2], dtype=torch.bool)
+                for b in clips:
+                    keys[b, units[b, f].nonzero().flatten()[blocks.view(nb * nb, T * T)[i - 1]]] = True      # the block's tokens among frame f's, in order
+                kw["key_drop"] = keys
+            outs.append(model.forward(visual_tokens=tokens, **kw, **common))
+    res = {"outs": outs, "blocks": blocks}
+    if "score1" in outs[0]:
+        base = outs[0]["score1"].float()
+        control = torch.full((B, F), float("nan"), dtype=torch.float32, device=base.device)
+        occluded = torch.full((B, F, nb * nb), float("nan"), dtype=torch.float32, device=base.device)
+        for n, f in enumerate(sweep):
+            got = outs[1 + n * nv:1 + (n + 1) * nv]
+            there = has[:, f].to(base.device)
+            control[:, f] = torch.where(there, got[0]["score1"].float(), control[:, f])
+            occluded[:, f] = torch.where(there[:, None], torch.stack([o["score1"].float() for o in got[1:]], 1), occluded[:, f])
+        occluded = occluded.view(B, F, nb, nb)
+        res.update(score1=base, control=control, occluded=occluded, delta=control[:, :, None, None] - occluded)
     return res
 
 

@@ -87,6 +87,8 @@ PROTOTYPES = {
     "aigv_attention_map_arm": (_I, [_P, _P, _I, _P, _P, _P, _I, _I]),
     "aigv_op_attention_map": (_I, [_P, _I, _P, _I, _I32P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _I, _P, _P, _P]),
     "aigv_vit_attention_arm": (_I, [_P, _P, _I, _I, _I]),
+    "aigv_vit_key_drop_arm": (_I, [_P, _P, _I, _I, _I]),
+    "aigv_op_attention_nc_drop": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, C.c_int64, _P, _I, _I, _F, _F, _P, _P, _P, _I, _I, _P, _I, _P]),
     "aigv_op_vit_attention_map": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P]),
     "aigv_kv_fork": (_I, [_P, _I, _P]),
     "aigv_kv_reorder": (_I, [_P, _P, _P, _I, _P]),

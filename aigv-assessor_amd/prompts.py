@@ -178,6 +178,19 @@ def attention_segments(slot, cu: Sequence[int], n_frames, tokens_per_frame: int)
     return seg
 
 
+def patch_drop_words(patch_drop) -> torch.Tensor:
+    """The patch mask of ``vit_tokens(patch_drop=...)`` in the attention kernel's layout (host only): bool [F, G, G] -> int64 [F, ceil((G * G + 1) /
+    64)] in ``key_drop_words``' word layout, one row per frame.  Key 0 of a frame is its cls token, which the mask cannot address: bit 0 of word 0
+    is always clear, so no row is ever without a visible key.  Key ``1 + G * y + x`` is patch (y, x)."""
+    pd = torch.as_tensor(patch_drop)
+    if pd.dim() != 3 or pd.shape[1] != pd.shape[2] or pd.dtype != torch.bool or pd.shape[0] < 1 or pd.shape[1] < 1:
+        raise ValueError(f"patch_drop_words: patch_drop must be a bool tensor [F, G, G] with F, G >= 1, got {pd.dtype} {tuple(pd.shape)}")
+    n_f, G, _ = pd.shape
+    S = G * G + 1
+    keys = torch.cat([torch.zeros(n_f, 1, dtype=torch.bool), pd.to("cpu").reshape(n_f, G * G)], 1)      # [F, S]: cls in front, never dropped
+    return key_drop_words(keys, [f * S for f in range(n_f + 1)])
+
+
 def key_drop_words(key_drop, cu: Sequence[int], row_of=None, n_words: Optional[int] = None) -> torch.Tensor:
     """The key-drop mask of ``forward(key_drop=...)`` in the attention kernel's layout (host only): int64 [B, W], bit ``j & 63`` of word
     ``[b, j >> 6]`` set = token j of clip b (its position inside the PACKED clip, 0 = its first token) is dropped; bits at and past a clip's

@@ -52,9 +52,21 @@ class ScoringPass:
                                                          native.stream_ptr()))
         return out
 
-    def vit_tokens(self, pixel_values: torch.Tensor) -> torch.Tensor:
+    def vit_tokens(self, pixel_values: torch.Tensor, patch_drop: Optional[torch.Tensor] = None, patch_drop_layers=None) -> torch.Tensor:
         """InternViT -> drop cls -> pixel-shuffle: [F,3,S,S] -> [F, ntok, 4*Hv] pre-projector tokens (the
-        frame-DP all-gather payload; modeling_internvl_chat.py:509-527)."""
+        frame-DP all-gather payload; modeling_internvl_chat.py:509-527).
+
+        ``patch_drop`` (None: exactly the call without it): PATCH OCCLUSION inside the tower - bool [F, G, G], G = image_size // patch_size, True =
+        patch (y, x) of that frame is hidden, AS A KEY, from every row of its frame in the tower's attention (the non-causal key-drop form of the
+        attention kernel; ``aigv_vit_key_drop_arm``).  Pixels, positions, the cls token and every other patch stay as they are; cls is not
+        addressable, so no row is ever without a key.  The hidden patches' own rows still run and still carry their own content to their cell's
+        token - ``eval_utils.patch_occlusion`` hides those tokens from the LLM.  ``patch_drop_layers = (lo, hi)``: the mask applies in layers
+        lo <= l < hi only, 0 <= lo < hi <= ``vit_layers_run()``; None: every layer the pass runs.  The masked call runs eagerly on the current
+        stream (never inside a graph capture) after waiting for a prefetch in flight; ValueError for a wrong shape, dtype or window."""
+        if patch_drop is not None:
+            return self._vit_tokens_masked(pixel_values, patch_drop, patch_drop_layers)
+        if patch_drop_layers is not None:
+            raise ValueError("vit_tokens: patch_drop_layers qualifies a patch_drop mask and needs one")
         if pixel_values.dim() != 4:
             raise ValueError(f"wrong pixel_values size: {pixel_values.shape}")  # modeling_intern_vit.py:345
         nf = pixel_values.shape[0]
@@ -67,6 +79,39 @@ class ScoringPass:
         out = torch.empty((nf, self.num_image_token, self.config.proj_in), dtype=torch.bfloat16, device=self.device)
         native.check(lib.aigv_vit_forward(ctx, pv.data_ptr(), nf, out.data_ptr(), native.stream_ptr()), ctx)
         return out
+
+    def _vit_tokens_masked(self, pixel_values, patch_drop, patch_drop_layers) -> torch.Tensor:
+        """``vit_tokens(patch_drop=...)``: the checks, the host-built words, the armed pass."""
+        from . import prompts
+        if pixel_values.dim() != 4:
+            raise ValueError(f"wrong pixel_values size: {pixel_values.shape}")
+        v = self.config.vision_config
+        nf, size = pixel_values.shape[0], self.config.image_size
+        if nf < 1 or tuple(pixel_values.shape[1:]) != (v.num_channels, size, size):
+            raise ValueError(f"pixel_values must be [F,{v.num_channels},{size},{size}] with F >= 1, got {tuple(pixel_values.shape)}")
+        G = size // v.patch_size
+        if not torch.is_tensor(patch_drop) or patch_drop.dtype != torch.bool or tuple(patch_drop.shape) != (nf, G, G):
+            raise ValueError(f"vit_tokens: patch_drop must be a bool tensor [{nf}, {G}, {G}] (frames, patch rows, patch columns), got "
+                             f"{getattr(patch_drop, 'dtype', type(patch_drop).__name__)} {tuple(getattr(patch_drop, 'shape', ()))}")
+        n_run = self.vit_layers_run()
+        try:
+            lo, hi = (0, n_run) if patch_drop_layers is None else (int(x) for x in patch_drop_layers)
+        except (TypeError, ValueError):
+            lo, hi = 0, 0
+        if not 0 <= lo < hi <= n_run:
+            raise ValueError(f"vit_tokens: patch_drop_layers = {patch_drop_layers!r} is no window (lo, hi) with 0 <= lo < hi <= {n_run}, the layers the pass runs")
+        if self._capture_keep is not None or native._captures_underway > 0 or (self.device.type == "cuda" and torch.cuda.is_current_stream_capturing()):
+            raise RuntimeError("vit_tokens(patch_drop=...) runs eagerly: it cannot be part of a graph capture")
+        if self.device.type != "cuda":
+            raise native.NativeError("the scorer hot path runs on an MI355X only (no CPU fallback)")
+        words = prompts.patch_drop_words(patch_drop).to(self.device)      # int64 [F, W]: the 64 bits the kernel reads
+        lib, ctx = self._native(n_frames=nf)
+        self._wait_for_prefetch()
+        pv = pixel_values.to(device=self.device, dtype=torch.bfloat16).contiguous()
+        out = torch.empty((nf, self.num_image_token, self.config.proj_in), dtype=torch.bfloat16, device=self.device)
+        native.check(lib.aigv_vit_key_drop_arm(ctx, words.data_ptr(), int(words.shape[1]), lo, hi), ctx)
+        native.check(lib.aigv_vit_forward(ctx, pv.data_ptr(), nf, out.data_ptr(), native.stream_ptr()), ctx)
+        return out      # (`words` stays referenced until the launches are queued; the caching allocator keeps freed memory stream-ordered)
 
     def vit_layers_run(self) -> int:
         """The number of InternViT layers a pass runs: ``select_layer``'s count (-1: all of them), not ``num_hidden_layers``."""

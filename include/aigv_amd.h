@@ -55,7 +55,8 @@ extern "C" {
                                 aigv_neuron_patch_arm, aigv_neuron_scale_arm, aigv_op_neuron_rows), then by the probe's value flow
                                 (aigv_score_attention_arm_values, aigv_op_attention_probe_values), then by the attention flow map of
                                 every query row (aigv_attention_map_arm, aigv_op_attention_map), then by the InternViT attention map
-                                (aigv_vit_attention_arm, aigv_op_vit_attention_map)
+                                (aigv_vit_attention_arm, aigv_op_vit_attention_map), then by the InternViT patch mask - key-drop for the
+                                non-causal attention (aigv_vit_key_drop_arm, aigv_op_attention_nc_drop)
                                 - added symbols only: a library without them is refused at load
                                 time, "missing <name>" */
 
@@ -169,6 +170,16 @@ int aigv_vit_forward(aigv_ctx* ctx, const void* frames, int n_frames, void* out_
  * Refused by the pass, AIGV_ERR_ARG with a message, before it launches anything: a window outside 0 <= layer_lo < layer_hi <= the number of
  * layers the pass RUNS (select_layer's count, not vit_layers). */
 int aigv_vit_attention_arm(aigv_ctx* ctx, float* out_dev, int layer_lo, int layer_hi, int per_head);
+/* Patch occlusion inside the tower: arms exactly the NEXT aigv_vit_forward, whose flash attention of every layer layer_lo <= l < layer_hi (of the layers
+ * the pass runs) hides keys from every query row and head of their frame - the non-causal key-drop form of the attention kernel.  The armament is
+ * consumed on EVERY way out of that call.  words_dev: DEVICE uint64 [n_frames][ld_words], 8-byte aligned, ld_words >= ceil(S / 64), indexed by the
+ * absolute frame number across vit_chunk chunks; bit (j & 63) of word f * ld_words + (j >> 6) set = key j of frame f is hidden.  Key 0 is cls, key
+ * 1 + grid * y + x is patch (y, x).  Bits at or past S are ignored.  A dropped key is hidden from its own row too; its row still runs (as a query),
+ * so its patch reaches its own token through the residual stream.  A frame whose every key is hidden has zero attention output rows.  The layers
+ * outside the window, and an unarmed pass, run the unmasked kernel.  The masked kernel runs with the lead-key tune knob off whatever it is set to.
+ * Refused by the pass, AIGV_ERR_ARG with a message, before it launches anything: a window outside 0 <= layer_lo < layer_hi <= the layers the pass
+ * RUNS, and a pass armed with both aigv_vit_attention_arm and a mask (the map kernel does not know the mask). */
+int aigv_vit_key_drop_arm(aigv_ctx* ctx, const uint64_t* words_dev, int ld_words, int layer_lo, int layer_hi);
 /* mlp1: LayerNorm -> Linear -> GELU -> Linear (modeling_internvl_chat.py:238-243,529). rows x proj_in -> rows x llm_hidden */
 int aigv_project(aigv_ctx* ctx, const void* tokens, int rows, void* out, void* stream);
 /* motion_mlp on the SlowFast feature (modeling_internvl_chat.py:244-249,345). [B, motion_dim] -> [B, llm_hidden] */
@@ -641,6 +652,16 @@ int aigv_op_attention_drop_rows(const void* q, int ldq, const void* k, int ldk, 
                                 const int32_t* kv_off, int head_dim, int causal, float post_div, float q_prescale, const int32_t* pos,
                                 const void* cos, const void* sin, int pos_is_row, int q_tail, const uint64_t* key_drop, const uint64_t* row_words,
                                 int ld_drop, void* stream);
+/* aigv_op_attention_ex under the NON-causal key-drop mask (tests/test_gpu_vit_key_drop.py; head_dim 64 or 128): key_drop in aigv_op_attention_drop's
+ * layout, or NULL (then the same call as aigv_op_attention_ex).  A dropped key is hidden from every query row, its own included; a row without a
+ * visible key is written as zeros; dropped keys' V rows must be finite; bits at or past a sequence's length are ignored.  The masked kernel ignores
+ * the lead-key bit of `causal`: under a zero mask its output is that of aigv_op_attention_ex with the bit clear.  Refused with AIGV_ERR_ARG and a
+ * message, before anything is launched: causal != 0, key_drop with kv_off, kv_seq_stride or q_tail, a misaligned key_drop, ld_drop <
+ * ceil(max_len / 64). */
+int aigv_op_attention_nc_drop(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, const int32_t* cu, int n_seq,
+                              int max_len, int n_heads, int n_kv_heads, int q_group_stride, int kv_head_stride, int64_t kv_seq_stride,
+                              const int32_t* kv_off, int head_dim, int causal, float post_div, float q_prescale, const int32_t* pos, const void* cos,
+                              const void* sin, int pos_is_row, int q_tail, const uint64_t* key_drop, int ld_drop, void* stream);
 /* The score-row attention probe on plain pointers (one layer; tests use it without a model): out [n_rows, n_heads, n_segments] fp32 as
  * aigv_score_attention_arm defines it.  q: UNROTATED fused rows (query head h at column (h / g) * q_group_stride + (h % g) * head_dim), rotated
  * by the kernel at the row's position from cos / sin [max_pos, head_dim / 2]; k: already rotated, in aigv_op_attention_ex's two forms -
